@@ -34,6 +34,7 @@ WORKLOADS = {
     "uhd": (3840, 2160, 256, 21, 4),         # configs[4] geometry
 }
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_BYTES = 63 * 10**6  # --dump-outputs: array bytes in all (with the .npy headers the files stay under 64 MB)
 
 
 def usable_cores():
@@ -131,6 +132,22 @@ def launch_ranks(n):
     return rc
 
 
+def dump_outputs(out_dir, disp):
+    """--dump-outputs: the (n, H, W) int16 disparity maps `disp` as out_dir/disparity.npy in float32 (exact). When all n maps
+    exceed DUMP_BYTES, a fixed seeded sample of whole maps, kept in pair order."""
+    import numpy as np
+    import torch
+
+    n, h, w = disp.shape
+    k = min(n, DUMP_BYTES // (4 * h * w))
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    maps = disp[torch.from_numpy(idx).to(disp.device)].cpu().numpy().astype(np.float32)
+    d = pathlib.Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "disparity.npy", maps)
+    print(f"bench.py: wrote {d / 'disparity.npy'}: pairs {idx.tolist()} of the {n} maps of the last timed step", file=sys.stderr)
+
+
 def probe_opencv():
     """SURVEY.md 8c / BASELINE.md 3.1: use the real cv::StereoBM as checker and CPU baseline if this host has it."""
     try:
@@ -176,7 +193,12 @@ def main():
     ap.add_argument("--no-multi", action="store_true", help="N>1: skip the one-process C++ leg (sbm_compute_batch_multi over the visible devices)")
     ap.add_argument("--sg-timeout", type=float, default=180.0, help="N>1: wall-clock limit of the scatter/gather child processes")
     ap.add_argument("--sg-child", action="store_true", help=argparse.SUPPRESS)   # internal: this process IS a scatter/gather child
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the disparity maps of the last timed step (rank 0's; a seeded sample of "
+                         "whole maps beyond 63 MB) as DIR/disparity.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
 
@@ -415,6 +437,17 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed to its caller, taken before any later pass writes the same buffers again
+        if scatter:
+            last = gD
+        elif gathered is not None:
+            last = gathered
+        elif host_feed:
+            last = torch.from_numpy(feed_sets[(feed_i[0] - 1) % 3][2] if feed_async else hDn)
+        else:
+            last = dD
+        dump_outputs(args.dump_outputs, last)
 
     kernel_name = bm.last_kernel()
 

@@ -1,59 +1,12 @@
-"""Pin the block-matching output against the REAL cv::StereoBM wherever a box has it (SURVEY.md 8c last row, BASELINE.md
-3.1). Probed in round 2: the GPU image has no cv2 and no libopencv_* (profiles/r02_opencv_probe.txt),
-so today this skips with that reason; it turns into the parity gate the day an image ships OpenCV. Nothing from
-/root/reference or from OpenCV's sources is needed at run time: inputs are the committed golden pair and synthetic frames."""
+"""The pin kit (tools/pin_kit.py, tests/golden/pin_kit.npz) against this engine: the kit holds the engine's stage-by-stage
+outputs for every risk case of SURVEY.md A.7, and these tests keep it current. The comparison with the real cv::StereoBM
+(SURVEY.md 8c last row) needs OpenCV, which no machine this suite runs on has
+(profiles/r02_opencv_probe.txt): it is made off-box with `python tools/verify_with_opencv.py tests/golden/pin_kit.npz`
+(numpy + cv2 only)."""
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
-
-
-def _cv2():
-    try:
-        import cv2
-
-        return cv2
-    except Exception as e:  # noqa: BLE001
-        pytest.skip(f"OpenCV unavailable on this box (import cv2: {type(e).__name__}): cv::StereoBM parity stays unpinned; the engine is "
-                    "checked against the in-repo restatement instead. To settle it off-box: python tools/verify_with_opencv.py "
-                    "tests/golden/pin_kit.npz (numpy + cv2 only) -- the kit holds this engine's stage-by-stage outputs for every risk case")
-
-
-def _cv_bm(cv2, nd, w):
-    m = cv2.StereoBM_create(numDisparities=nd, blockSize=w)
-    m.setPreFilterCap(31); m.setMinDisparity(0); m.setTextureThreshold(10); m.setUniquenessRatio(10)
-    m.setSpeckleWindowSize(50); m.setSpeckleRange(32); m.setDisp12MaxDiff(1)      # main.cpp:204-212
-    return m
-
-
-@pytest.mark.parametrize("w", [9, 21])
-def test_reference_pair_against_opencv(pkg, oracle, golden, w):
-    cv2 = _cv2()
-    print("OpenCV", cv2.__version__)
-    ref = _cv_bm(cv2, 64, w).compute(golden["rect_l"], golden["rect_r"])
-    bm = pkg.StereoBM.create(64, w)
-    bm.setPreFilterCap(31); bm.setTextureThreshold(10); bm.setUniquenessRatio(10)
-    bm.setSpeckleWindowSize(50); bm.setSpeckleRange(32); bm.setDisp12MaxDiff(1)
-    got = bm.compute(golden["rect_l"], golden["rect_r"])
-    assert np.array_equal(got, ref), int((got != ref).sum())
-    # and the oracle itself gets pinned by the same comparison
-    assert np.array_equal(oracle.compute(oracle.make_params(64, w, 31, 0, 10, 10, 50, 32, 1), golden["rect_l"], golden["rect_r"]), ref)
-
-
-@pytest.mark.parametrize("shape", [(1242, 375, 128, 15, 3), (1920, 1080, 256, 21, 1)])
-def test_synthetic_frames_against_opencv(pkg, shape):
-    cv2 = _cv2()
-    from u96_slam_amd import synth
-
-    W, H, nd, w, n = shape
-    L, R = synth.make_batch(0, n, W, H, nd)
-    bm = pkg.StereoBM.create(nd, w)
-    bm.setPreFilterCap(31); bm.setTextureThreshold(10); bm.setUniquenessRatio(10)
-    bm.setSpeckleWindowSize(50); bm.setSpeckleRange(32); bm.setDisp12MaxDiff(1)
-    got = bm.compute(L, R)
-    m = _cv_bm(cv2, nd, w)
-    for i in range(n):
-        assert np.array_equal(got[i], m.compute(L[i], R[i])), i
 
 
 # ---- the pin kit (tools/pin_kit.py): one case per risk item of SURVEY.md A.7 + getValidDisparityROI's "- minDisparity" --------
@@ -115,27 +68,3 @@ def test_engine_reproduces_the_alternative_readings_of_the_kit(pkg, monkeypatch)
                 assert np.array_equal(got, want), (name, int(b), str(st), int((got != want).sum()))
                 n += 1
     assert n >= 4 * 9
-
-
-def test_pin_kit_against_opencv():
-    """The one-command pin, run in-tree where a box has cv2: every risk case, first differing stage reported."""
-    cv2 = _cv2()
-    import importlib.util
-    import pathlib
-
-    root = pathlib.Path(__file__).resolve().parents[1]
-    spec = importlib.util.spec_from_file_location("verify_with_opencv", root / "tools" / "verify_with_opencv.py")
-    ver = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ver)
-    kit = _kit()
-    fields = [str(f) for f in kit["fields"]]
-    bad = []
-    for name in kit["names"]:
-        name = str(name)
-        p = dict(zip(fields, kit[f"{name}/params"].tolist()))
-        for st in kit["stages"]:
-            got = ver.make_bm(cv2, ver.stage_params(p, str(st))).compute(kit[f"{name}/left"], kit[f"{name}/right"])
-            if not np.array_equal(got, kit[f"{name}/{st}"]):
-                bad.append((name, str(st), int((got != kit[f"{name}/{st}"]).sum())))
-                break
-    assert not bad, bad
