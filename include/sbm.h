@@ -35,18 +35,20 @@
  * speckleWindowSize up to 2048; larger images or windows take its row-walking kernels (same results, ~3x the stage time).
  *
  * The hand-tuned kernels accumulate in place with v_mqsad_pk_u16_u8 (vdst == src2), which the hardware does right and the
- * compiler's register model forbids; a device self-test (once per device and process, on the first handle's stream: pseudo-random
- * operands, single instructions and dependent chains, at 1 / 4 / 8 wavefronts per SIMD) guards it. What the self-test does NOT
- * cover is a device that miscomputes only in instruction mixes it does not generate. If it fails, or with SBM_FAST_INPLACE=0, the
- * two-accumulator build runs instead: same results, 64-disparity layouts (~1.3x slower at 128 disparities), block sizes up to 27
- * and up to 256 disparities -- block sizes 29 / 31 and 257..512 disparities then fall to the sliding-sum kernel (8-25x slower; the
- * kernel name, sbm_last_kernel_name(), then reads "sad_wide_kernel [in-place accumulate unavailable]").
+ * compiler's register model forbids; a device self-test (once per device and process, on the stream of the first call that would
+ * take the interior SAD kernel: pseudo-random operands, single instructions and dependent chains, at 1 / 4 / 8 wavefronts per SIMD)
+ * guards it. What the self-test does NOT cover is a device that miscomputes only in instruction mixes it does not generate. If it
+ * fails, or with SBM_FAST_INPLACE=0, the sliding-sum kernel takes every configuration of the interior kernel's envelope: same
+ * results, 8-25x slower SAD stage; the kernel name, sbm_last_kernel_name(), then reads
+ * "sad_wide_kernel [in-place accumulate unavailable]". If the self-test cannot run (one of its HIP calls fails), that call
+ * returns SBM_ERR_HIP (SBM_ERR_NOMEM if its 8-byte allocation fails) with the error in sbm_last_hip_error(), nothing is
+ * remembered, and the next call runs the self-test again.
  *
  * Environment. The library reads these nine variables (nothing else); an integrator never needs to set any of them:
  *   variable            default  read      who sets it, and what for
- *   SBM_FAST_INPLACE    1        once      0 = run the two-accumulator build of the SAD kernel (the fallback that is taken
- *                                          automatically when the device self-test of the in-place v_mqsad accumulate
- *                                          fails); set by the GPU tests to check that fallback
+ *   SBM_FAST_INPLACE    1        once      0 = run the sliding-sum SAD kernel instead of the interior one (the fallback that
+ *                                          is taken automatically when the device self-test of the in-place v_mqsad
+ *                                          accumulate fails); set by the GPU tests to check that fallback
  *   SBM_FAST_PFSHIFT    2        once      0 = unscaled prefiltered planes (plain winner search), 1 = at most one tag bit;
  *                                          GPU tests
  *   SBM_FAST_CS3        1        per call  0 = plain column strips only (no column-stride-3 strips); GPU tests
@@ -228,9 +230,10 @@ int sbm_set_profiling(sbm_handle* h, int enabled);
 int sbm_get_profile(sbm_handle* h, const char* name, float* ms);
 
 /* Which SAD kernel the LAST sbm_compute_device call launched, as text: the template instantiation of the interior
- * kernel ("sad_fast_kernel<128,1,5,3,true> pfshift=2"; "sad_fast_pp_kernel<...>" = its two-accumulator fallback build)
- * or "sad_wide_kernel" / "sad_generic_kernel" when the configuration is outside the fast envelope. bench.py compares it with the kernel the
- * committed counter profile was taken on, so that stale counters are never attached to a different kernel. */
+ * kernel ("sad_fast_kernel<128,1,5,3,true> pfshift=2"), or "sad_wide_kernel" / "sad_generic_kernel" when the configuration
+ * is outside the fast envelope ("sad_wide_kernel [in-place accumulate unavailable]" when it is inside but the device self-test
+ * above failed or SBM_FAST_INPLACE=0). bench.py compares it with the kernel the committed counter profile was taken on, so
+ * that stale counters are never attached to a different kernel. */
 int sbm_last_kernel_name(sbm_handle* h, char* dst, size_t dst_bytes);
 
 /* ---- consumers of the disparity map --------------------------------------------

@@ -223,7 +223,7 @@ def test_async_dense_feed_matches_the_synchronous_call():
 
 
 @pytest.mark.parametrize("env,args,kernel", [
-    ({"SBM_FAST_INPLACE": "0"}, ["--pairs", "8"], "sad_fast_pp_kernel<64,2,5,3,false,true> pfshift=2"),   # two-accumulator fallback build (64-disparity layouts, masked-count kernels only)
+    ({"SBM_FAST_INPLACE": "0"}, ["--pairs", "8"], "sad_wide_kernel [in-place accumulate unavailable]"),   # no in-place accumulate: the sliding-sum kernel
     ({}, ["--pairs", "1"], "sad_fast_kernel<64,2,5,3,true,true> pfshift=2"),                              # one pair per call: the disparities split over two cooperating wavefronts
     ({"SBM_FAST_PFSHIFT": "0"}, ["--pairs", "8"], "sad_fast_kernel<128,1,5,3,true,true> pfshift=0"),      # unscaled planes, plain key search
     ({"SBM_FAST_PFSHIFT": "1"}, ["--pairs", "8"], "sad_fast_kernel<128,1,5,3,true,true> pfshift=0"),      # w 15 kernels hold the two-bit variant only

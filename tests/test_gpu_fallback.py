@@ -1,8 +1,8 @@
-"""The two-accumulator fallback build of the interior SAD kernel (sbm_sad_fast_pp.hip: what runs when the device self-test of
-the in-place v_mqsad accumulate fails, selected here with SBM_FAST_INPLACE=0). Round 5 reduced it to the 64-disparity layouts
-with masked-count kernels only and it is the last user of the register-staged strip, so it gets its own parity sweep: every
-layout (one to four cooperating wavefronts), exact and masked counts, 3- and 1-column sums, one-pair and batched launches.
-The switch is read once per process, hence the subprocess."""
+"""What runs when the device self-test of the in-place v_mqsad accumulate fails (selected here with SBM_FAST_INPLACE=0): the
+sliding-sum kernel (sbm_sad_wide.hip) takes the interior kernel's whole envelope, and the kernel name says why. Its parity
+sweep spans that envelope: windows 5 to 29 (3- and 1-column sums in the interior kernel), 16 to 384 disparities (exact and
+masked counts of its one to four wavefront layouts), one-pair and batched launches, each against the oracle. The switch is
+read once per process, hence the subprocess."""
 import json
 import pathlib
 import subprocess
@@ -22,7 +22,7 @@ from u96_slam_amd import synth
 out = []
 for W, H, nd, w, n in [(320, 96, 64, 21, 5), (400, 80, 128, 15, 9), (640, 120, 256, 21, 2), (333, 77, 48, 11, 7), (300, 70, 96, 27, 17),
                        (500, 90, 192, 19, 3), (420, 80, 112, 15, 40), (360, 70, 16, 5, 1), (400, 90, 160, 25, 2), (640, 480, 64, 21, 1),
-                       (700, 60, 320, 15, 2), (400, 90, 64, 29, 2), (900, 66, 384, 9, 1)]:   # (the last three: beyond 256 disparities / 27 x 27 the fallback build hands over to the sliding-sum kernel)
+                       (700, 60, 320, 15, 2), (400, 90, 64, 29, 2), (900, 66, 384, 9, 1)]:
     L, R = synth.make_batch(3, n, W, H, nd)
     bm = pkg.StereoBM.create(nd, w)
     bm.setUniquenessRatio(10); bm.setDisp12MaxDiff(1); bm.setSpeckleWindowSize(30); bm.setSpeckleRange(16)
@@ -35,7 +35,7 @@ print(json.dumps(out))
 
 
 @pytest.mark.gpu
-def test_fallback_build_parity_sweep():
+def test_fallback_sliding_sum_parity_sweep():
     import os
 
     env = dict(os.environ, SBM_FAST_INPLACE="0")
@@ -43,13 +43,8 @@ def test_fallback_build_parity_sweep():
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("[")][-1])
     assert len(res) == 13
-    for e in res[-3:]:     # the documented cliff (include/sbm.h): right results, from the sliding-sum kernel, and the name says why
+    for e in res:     # the documented cliff (include/sbm.h): right results, from the sliding-sum kernel, and the name says why
         assert e["kernel"] == "sad_wide_kernel [in-place accumulate unavailable]" and e["ok"], e
-    res = res[:-3]
-    for e in res:
-        assert e["kernel"].startswith("sad_fast_pp_kernel<64,"), e
-        assert e["ok"], e
-    assert {e["kernel"].split(",")[1] for e in res} == {"1", "2", "3", "4"}      # every layout of the fallback ran
 
 
 @pytest.mark.gpu

@@ -515,12 +515,15 @@ int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_r
   if (st != SBM_OK) return st;
   h->last = g; h->have_last = true;
 
+  // The interior kernel needs the in-place v_mqsad accumulate: its device self-test runs on this handle's stream, once per
+  // device (a check that could not run fails this call with its HIP error and runs again on the next one). Without it the
+  // sliding-sum kernel takes the whole envelope.
+  const bool in_envelope = any_rows && sad_fast_supported(g);
+  bool inplace = false;
+  if (in_envelope) HIPCHK(h, mqsad_inplace_ok(h->stream, &inplace));
+  const bool fast = in_envelope && inplace;
   // 16-bit cost plane when every producer is a 16-bit-sum kernel (fast interior + border kernels, w/2 clamped columns on
   // each side); the generic kernel needs int32
-  // (the once-per-device self-test behind the in-place accumulate runs on THIS handle's stream, before the envelope predicate
-  // below can trigger it on the legacy stream)
-  const bool inplace = mqsad_inplace_ok(h->stream);
-  const bool fast = any_rows && sad_fast_supported(g);
   int fa = 0, fb = 0;
   if (fast) {
     const int xhi = std::min(g.W - g.lofs - 1, g.W - g.rofs - g.nd);
@@ -564,10 +567,9 @@ int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_r
       }
     } else if (sad_wide_supported(g) && env_switch("SBM_WIDE", 1)) {
       HIPCHK(h, launch_sad_wide(h->pf_l, h->pf_r, h->disp_pre, h->cost, g, 0, g.xend, h->stream));
-      // (say so when this configuration only left the interior kernel's envelope because the in-place accumulate is off or
-      // its device self-test failed: windows 29 / 31 and 257..512 disparities are 8-25x slower here, see include/sbm.h)
-      const bool narrowed = !inplace && g.wsz <= 31 && g.nd <= kFastNdMax && (g.wsz > 27 || g.nd > 256);
-      snprintf(h->last_kernel, sizeof(h->last_kernel), narrowed ? "sad_wide_kernel [in-place accumulate unavailable]" : "sad_wide_kernel");
+      // (say so when the interior kernel was left out only because the in-place accumulate is off or its device self-test
+      // failed: 8-25x slower, see include/sbm.h)
+      snprintf(h->last_kernel, sizeof(h->last_kernel), in_envelope ? "sad_wide_kernel [in-place accumulate unavailable]" : "sad_wide_kernel");
     } else {
       HIPCHK(h, launch_sad_generic(h->pf_l, h->pf_r, h->disp_pre, h->cost, g, 0, g.xend, h->stream));
       snprintf(h->last_kernel, sizeof(h->last_kernel), "sad_generic_kernel");

@@ -11,8 +11,8 @@ namespace sbm {
 
 // Environment switches of the library -- the complete list, documented for integrators in include/sbm.h ("Environment").
 //   env_switch(): read in every build. They select a tested fallback or a code path that the GPU tests compare with the
-//                 default one: SBM_FAST_INPLACE, SBM_FAST_PFSHIFT, SBM_FAST_CS3, SBM_SPECKLE_LISTS, SBM_SPECKLE_BAND,
-//                 SBM_SPECKLE_SEG, SBM_HOST_ZEROCOPY, SBM_WIDE, SBM_CV_READING.
+//                 default one: SBM_FAST_INPLACE (0: the sliding-sum kernel in place of the interior one), SBM_FAST_PFSHIFT,
+//                 SBM_FAST_CS3, SBM_SPECKLE_LISTS, SBM_SPECKLE_BAND, SBM_SPECKLE_SEG, SBM_HOST_ZEROCOPY, SBM_WIDE, SBM_CV_READING.
 //   SBM_TUNE():   tuning knobs behind the sweeps of tools/exp (SBM_FAST_NSEG, SBM_FAST_TAPER,
 //                 SBM_FAST_UNIQ_PLAIN, SBM_FAST_SPLIT, SBM_PF_ROWS, SBM_HOST_CHUNK, SBM_HOST_PIPELINE, SBM_DEV_*): compiled in
 //                 only with -DSBM_DEV (the development library of tools/exp/r05_devlib.sh; sbm_sad_fast_dev.h lists the interior
@@ -88,7 +88,9 @@ hipError_t launch_sad_wide(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* di
 // name of the SAD kernel instantiation of the calling thread's last launch (template tuple; sbm_last_kernel_name())
 extern thread_local char g_sad_kernel_name[96];
 bool sad_fast_supported(const Geom& g);
-bool mqsad_inplace_ok(hipStream_t s);   // device self-test behind the in-place v_mqsad accumulate (cached per device)
+// device self-test behind the in-place v_mqsad accumulate, on stream s: *ok once it ran (cached per device); a HIP error when it
+// could not run (nothing cached)
+hipError_t mqsad_inplace_ok(hipStream_t s, bool* ok);
 constexpr int kFastNdMax = 512;   // disparities the interior kernel takes (four cooperating 128-disparity wavefronts)
 bool sad_fast_borders_in_launch(const Geom& g);   // the clamped border columns ride in the interior launch (up to 256 disparities)
 int sad_fast_pfshift(const Geom& g);   // 2 or 1 when the interior kernel wants pre-scaled planes (see kPfBias), else 0

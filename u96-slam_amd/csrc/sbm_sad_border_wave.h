@@ -221,11 +221,7 @@ __device__ __forceinline__ void sad_border_wave_body(const FastArgs& a, unsigned
     auto pat = [&](int v) { return (u32)lb[4 * v]; };
     auto acc = [&](u64& h, int v) {
       const u32 l = pat(v);
-#if SBM_FAST_PINGPONG
-      h = __builtin_amdgcn_mqsad_pk_u16_u8(win(v), l, h);
-#else
       asm("v_mqsad_pk_u16_u8 %0, %1, %2, %0" : "+v"(h) : "v"(win(v)), "v"(l));
-#endif
     };
     auto apply = [&](u64& s, const u64 h) {
       uint2 sv = __builtin_bit_cast(uint2, s);

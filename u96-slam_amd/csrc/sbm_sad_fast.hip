@@ -13,12 +13,11 @@
 //               One v_mqsad_pk_u16_u8 produces H3 for 4 consecutive disparities AND accumulates (pattern = 3 left
 //               bytes + a zero byte, which the instruction masks; sliding 8-byte window = right bytes).
 //               Entering row: V = mqsad(R, L, V), accumulated IN PLACE (vdst == src2: right on gfx950, checked by a device
-//               self-test; sbm_sad_fast_pp.hip is the two-array fallback).  Leaving row: V -= mqsad(R, L, 0).
+//               self-test; a device that fails it takes the sliding-sum kernel).  Leaving row: V -= mqsad(R, L, 0).
 //   LDS       = the right row piece of the wavefront, staged by LDS-direct loads (buffer_load_dword ... lds: no staging
 //               registers) into a 4x-expanded layout -- dword slot p holds bytes p..p+3, so a quad's 8-byte window is the
 //               dword pair (4q, 4q+4) behind the lane's slot, one conflict-free ds_read2_b32 (sad_fast_strip_dma,
-//               sbm_sad_fast_strip.h). The register-staged strip with its 16x-expanded layout (sbm_sad_fast_pp_strip.h) remains
-//               for the fallback build.
+//               sbm_sad_fast_strip.h).
 //   exchange  = horizontal window: S(c + w/2) = sum_k V(c + 3k), k < w/3: lanes publish V to LDS ([quad pair][lane],
 //               16 B entries) and read the shifted copies back; from 7 terms on in two levels (HPlan: T = a few V,
 //               published again, window = a few T + the remaining V). Lanes whose partners fall outside the wavefront
@@ -35,15 +34,16 @@
 // changes. Columns left over by the last full triple take CS = 1 strips -- both bodies live in one kernel, chosen by a
 // workgroup-uniform branch on the strip index.
 // Windows that are not multiples of 3 use 1-column sums (template parameter PW = 1: single-byte pattern, w-1 partners).
-// Envelope (sad_fast_supported(); everything else takes the sliding-sum kernel, sbm_sad_wide.hip): odd w in 5..31, nd <= 512,
-// w*w*2*cap <= 65534 (16-bit sums), 2*(maxS*uniq/100+1) < 65535, valid-ROI rows inside [w/2, H-w/2).
+// Envelope (sad_fast_supported(); everything else, and everything on a device without the in-place accumulate, takes the
+// sliding-sum kernel, sbm_sad_wide.hip): odd w in 5..31, nd <= 512, w*w*2*cap <= 65534 (16-bit sums),
+// 2*(maxS*uniq/100+1) < 65535, valid-ROI rows inside [w/2, H-w/2).
 //
 // Source layout: sbm_sad_fast_core.h (arguments, LDS carve-up, exchange plan, the per-row tail: winner search / uniqueness /
 // neighbours / sub-pixel), sbm_sad_fast_strip.h (the strip), sbm_sad_border_wave.h (the clamped border columns, extra wavefronts
 // of the same launch), sbm_sad_fast_kernel.h (kernel + layout choice), sbm_sad_fast_dev.h (development knobs), and this file:
 // the host side -- envelope, device self-test of the in-place accumulate, strips / row segments of a launch -- plus the kernels
 // of the windows 15 and 21. The ~270 instantiations compile as four translation units side by side (this one, sbm_sad_fast_pw1 /
-// _pw2 / _pw3.hip: the other windows) + the fallback build sbm_sad_fast_pp.hip.
+// _pw2 / _pw3.hip: the other windows).
 #include "sbm_sad_fast_kernel.h"
 
 namespace sbm {
@@ -74,34 +74,42 @@ __global__ void __launch_bounds__(256) mqsad_inplace_selftest_kernel(unsigned* b
   atomicAdd(bad + 1, 1u);   // "this workgroup's thread ran": a launch that never executed must not read as a pass
 }
 
-// Runs once per device and process (std::call_once: handles may be created from several threads). The check is launched at
-// three occupancies -- 1, 4 and 8 wavefronts per SIMD chip-wide -- and passes only if every thread of every launch reported
-// in and none saw a difference; a failed launch, copy or synchronisation counts as "not ok" (the ping-pong build then runs).
-bool mqsad_inplace_ok(hipStream_t s) {
-  static std::once_flag once[64];
-  static bool ok[64];
+// The check is launched at three occupancies -- 1, 4 and 8 wavefronts per SIMD chip-wide -- and passes only if every thread of
+// every launch reported in and none saw a difference. A check that ran is cached per device for the process (under a mutex:
+// handles may be created and used from several threads); one that could not run -- any of its HIP calls failed -- caches
+// nothing and returns that call's error, so the next call runs it again. SBM_FAST_INPLACE=0 (read once) reports unavailable.
+hipError_t mqsad_inplace_ok(hipStream_t s, bool* ok) {
+  static const bool forced_off = env_switch("SBM_FAST_INPLACE", 1) == 0;
+  static std::mutex mu;
+  static signed char known[64];   // per device: 0 not run yet, 1 passed, -1 ran and mismatched
+  *ok = false;
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  std::call_once(once[dev], [&] {
-    ok[dev] = false;
-    if (env_switch("SBM_FAST_INPLACE", 1) == 0) return;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess || forced_off || dev < 0 || dev >= 64) return e;
+  std::lock_guard<std::mutex> lock(mu);
+  if (!known[dev]) {
     unsigned* d = nullptr;
-    if (hipMalloc(&d, 8) != hipSuccess) return;
+    if ((e = hipMalloc(&d, 8)) != hipSuccess) return e;
     bool pass = true;
     const unsigned grids[3] = {256u, 1024u, 2048u};   // x 256 threads = 4 wavefronts per workgroup
-    for (int k = 0; k < 3 && pass; k++) {
+    for (int k = 0; k < 3 && pass && e == hipSuccess; k++) {
       unsigned h[2] = {1u, 0u};
-      pass = hipMemsetAsync(d, 0, 8, s) == hipSuccess;
-      if (pass) {
+      e = hipMemsetAsync(d, 0, 8, s);
+      if (e == hipSuccess) {
         hipLaunchKernelGGL(mqsad_inplace_selftest_kernel, dim3(grids[k]), dim3(256), 0, s, d);
-        pass = hipGetLastError() == hipSuccess && hipMemcpyAsync(h, d, 8, hipMemcpyDeviceToHost, s) == hipSuccess &&
-               hipStreamSynchronize(s) == hipSuccess && h[0] == 0u && h[1] == grids[k] * 256u;
+        e = hipGetLastError();
       }
+      if (e == hipSuccess) e = hipMemcpyAsync(h, d, 8, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipStreamSynchronize(s);
+      pass = h[0] == 0u && h[1] == grids[k] * 256u;
     }
-    (void)hipFree(d);
-    ok[dev] = pass;
-  });
-  return ok[dev];
+    const hipError_t ef = hipFree(d);
+    if (e == hipSuccess) e = ef;
+    if (e != hipSuccess) return e;
+    known[dev] = pass ? 1 : -1;
+  }
+  *ok = known[dev] > 0;
+  return hipSuccess;
 }
 
 // Pre-scaled planes for the tagged winner search: (value << sh) + 1 must fit a byte and (maxS << sh) + tag a packed half;
@@ -125,12 +133,9 @@ bool sad_fast_borders_in_launch(const Geom& g) { return g.nd <= 256; }
 
 bool sad_fast_supported(const Geom& g) {
   if (g.wsz < 5 || g.wsz > 31) return false;   // every odd window 5..31: multiples of 3 with 3-column sums, the rest 1-column
-  // (mqsad_inplace_ok: cached per device; sbm_compute_device has primed it on the handle's stream before it asks here)
-  if (g.wsz > 27 && !mqsad_inplace_ok(nullptr)) return false;   // 29 and 31 are not in the two-accumulator fallback build
+  // up to 512 disparities: beyond 256 three / four cooperating 128-disparity wavefronts, whose border columns come from the
+  // sliding-sum kernel (sbm_sad_wide.hip) in launches of their own
   if (g.nd > kFastNdMax) return false;
-  // beyond 256 disparities: three / four cooperating 128-disparity wavefronts (not in the two-accumulator fallback build);
-  // their border columns come from the sliding-sum kernel (sbm_sad_wide.hip) in launches of their own
-  if (g.nd > 256 && !mqsad_inplace_ok(nullptr)) return false;
   const long maxs = (long)g.wsz * g.wsz * 2 * g.cap;
   if (maxs > 65534) return false;
   if (2 * (maxs * g.uniq / 100 + 1) >= 65535) return false;
@@ -145,7 +150,6 @@ hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* di
                            int* xa, int* xb, bool border, hipStream_t s) {
   *xa = *xb = 0;
   if (!sad_fast_supported(g)) return hipSuccess;
-  const bool inplace = mqsad_inplace_ok(s);   // else: the two-accumulator build (sbm_sad_fast_pp.hip)
   FastArgs a;
   a.pf_l = pf_l; a.pf_r = pf_r; a.disp = disp; a.cost = g.want_cost ? reinterpret_cast<uint16_t*>(cost) : nullptr;
   a.W = g.W; a.H = g.H; a.pitch = g.pitch; a.padl = g.padl; a.plane = g.plane;
@@ -235,18 +239,14 @@ hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* di
   }
   const bool split = (long)strips * nseg * g.n < 1024 && fast_tune().split;
   hipError_t e;
-  if (!inplace) {
-    e = launch_sad_fast_pp(a, g.wsz, border, split, s);
-  } else {
-    switch (g.wsz) {
-      case 15: e = launch_nd<5, 3>(a, border, split, s); break;
-      case 21: e = launch_nd<7, 3>(a, border, split, s); break;
+  switch (g.wsz) {
+    case 15: e = launch_nd<5, 3>(a, border, split, s); break;
+    case 21: e = launch_nd<7, 3>(a, border, split, s); break;
 #ifdef SBM_DEV_FEW   // (development builds, sbm_sad_fast_dev.h: only the bench workloads' windows)
-      default: e = hipErrorInvalidValue; break;
+    default: e = hipErrorInvalidValue; break;
 #else
-      default: e = launch_sad_fast_pw1(a, g.wsz, border, split, s); break;   // the other windows: sbm_sad_fast_pw1 / _pw2 / _pw3.hip
+    default: e = launch_sad_fast_pw1(a, g.wsz, border, split, s); break;   // the other windows: sbm_sad_fast_pw1 / _pw2 / _pw3.hip
 #endif
-    }
   }
   *xa = a.xc0; *xb = a.xc1;
   return e;

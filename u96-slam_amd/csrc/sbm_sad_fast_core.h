@@ -1,7 +1,7 @@
 // sbm_sad_fast_core.h -- what every translation unit of the interior SAD kernel shares: launch arguments, small packed-math
-// helpers, the LDS carve-up of a wavefront, the plan of the horizontal window sum, and the per-row tail of a strip (winner
-// search, uniqueness, neighbour look-up, sub-pixel) that the LDS-direct strip (sbm_sad_fast_strip.h) and the two-accumulator
-// fallback strip (sbm_sad_fast_pp_strip.h) have in common. gfx950 only. See sbm_sad_fast.hip for the kernel's description.
+// helpers, the LDS carve-up of a wavefront, the plan of the horizontal window sum, and the per-row tail of the strip
+// (sbm_sad_fast_strip.h): winner search, uniqueness, neighbour look-up, sub-pixel. gfx950 only. See sbm_sad_fast.hip for the
+// kernel's description.
 #pragma once
 #include <stdio.h>
 #include <stdlib.h>
@@ -12,10 +12,6 @@
 #include <type_traits>
 
 #include "sbm_common.h"
-
-#ifndef SBM_FAST_PINGPONG   // 1 in sbm_sad_fast_pp.hip only: the fallback build with two accumulator arrays
-#define SBM_FAST_PINGPONG 0
-#endif
 
 namespace sbm {
 
@@ -84,14 +80,7 @@ struct FastLds {
   // CS*63 + 4 + 16 * (4 * (NCH - 1) + 3)
   static constexpr int NSLOT = ((CS * 63 + 4 + 16 * (4 * (NCH - 1) + 3) + 1) + 63) / 64 * 64;
   static constexpr int KS = CS == 3 ? 1 : PW;  // lane distance between two partners of the horizontal window
-  // horizontal exchange of the register-staged strip (fallback build): XCH quads at a time, XS entries per quad pair (64 lanes
-  // + the KS*(NTERM-1) halo). Chunk sizes from round 3: 4 quads for the cooperating 64-disparity wavefronts, 2 where one
-  // wavefront holds 128 disparities.
-  static constexpr int XCHMAX = NDW >= 128 ? 2 : 4;
-  static constexpr int XCH = NQ < XCHMAX ? NQ : XCHMAX;
-  static constexpr int XS = 64 + KS * (NTERM - 1);
-  static constexpr int XSLOT = (XCH / 2) * XS + (XS * 4 + 15) / 16;
-  static constexpr int WSLOT = NSLOT > XSLOT ? NSLOT : XSLOT;
+  static constexpr int XS = 64 + KS * (NTERM - 1);   // exchange entries per quad pair: 64 lanes + the KS*(NTERM-1) halo
   static_assert(CS == 1 || (CS == 3 && PW == 3), "column stride 3 goes with 3-column sums");
 };
 
@@ -126,7 +115,8 @@ template <int NDW, int NWAVES, int NTERM, int PW, int CS>
 struct DmaLds {
   using L = FastLds<NDW, NTERM, PW, CS>;
   using P = HPlan<NTERM, PW>;
-  static constexpr int XCH = L::NQ >= 2 ? 2 : L::XCH;                       // exchange chunk (quads)
+  static constexpr int XCH = 2;                                             // exchange chunk (quads)
+  static_assert(L::NQ >= XCH, "a wavefront holds at least two disparity quads");
   static constexpr int STAGE_B = L::NSLOT * 4;                              // one staged right row piece, 4x-expanded (dword slots)
   static constexpr int XLEV_B = ((XCH / 2) * L::XS + (L::XS * 4 + 15) / 16) * 16;   // one exchange level: quad entries + texture column
   static constexpr int PAT_OFS = STAGE_B > XLEV_B ? STAGE_B : XLEV_B;       // the left patterns of a staged row

@@ -1,29 +1,22 @@
 // sbm_sad_fast_kernel.h -- the interior SAD kernel (grid decode + strip dispatch) and its launchers, instantiated by each of the
 // kernel's translation units for its share of the windows (sbm_sad_fast.hip: 15 and 21; _pw1 / _pw2 / _pw3: the other
-// windows; _pp: the two-accumulator fallback build of all of them). gfx950 only.
+// windows). gfx950 only.
 #pragma once
 #include "sbm_sad_fast_core.h"
 #include "sbm_sad_fast_dev.h"
-#if SBM_FAST_PINGPONG
-#include "sbm_sad_fast_pp_strip.h"
-#define SBM_FAST_KERNEL sad_fast_pp_kernel
-#define SBM_FAST_WAVES_PER_EU
-#else
 #include "sbm_sad_fast_strip.h"
-#define SBM_FAST_KERNEL sad_fast_kernel
-// wavefronts per SIMD the register allocation aims at: 3 for a 128-disparity wavefront (168 VGPRs with the in-place accumulate),
-// 5 for three or four cooperating 64-disparity wavefronts (their two barriers per row want the extra wavefront to cover the
-// waits), 4 otherwise (a lone wavefront: measured slower at 5; two cooperating wavefronts of <= 64 disparities only run small
-// launches -- one pair per call -- and 128 VGPRs keep their border wavefronts free of scratch: at 96 VGPRs their spill reloads
-// were memory round trips inside the serial chain that IS the length of a one-pair SAD stage, 0.089 -> 0.071 ms)
-#define SBM_FAST_WAVES_PER_EU __attribute__((amdgpu_waves_per_eu(NDW > 64 ? 3 : (NWAVES > 2 ? 5 : 4))))
-#endif
 
 namespace sbm {
 
-// DUAL (windows that are multiples of 3): strips [0, strips3) are column-stride-3 strips in triples, the rest plain ones
+// DUAL (windows that are multiples of 3): strips [0, strips3) are column-stride-3 strips in triples, the rest plain ones.
+// amdgpu_waves_per_eu: wavefronts per SIMD the register allocation aims at: 3 for a 128-disparity wavefront (168 VGPRs with
+// the in-place accumulate), 5 for three or four cooperating 64-disparity wavefronts (their two barriers per row want the extra
+// wavefront to cover the waits), 4 otherwise (a lone wavefront: measured slower at 5; two cooperating wavefronts of <= 64 disparities only run small
+// launches -- one pair per call -- and 128 VGPRs keep their border wavefronts free of scratch: at 96 VGPRs their spill reloads
+// were memory round trips inside the serial chain that IS the length of a one-pair SAD stage, 0.089 -> 0.071 ms)
 template <int NDW, int NWAVES, int NTERM, int PW, bool EXACT_ND, bool DUAL>
-__global__ void __launch_bounds__(64 * NWAVES) SBM_FAST_WAVES_PER_EU SBM_FAST_KERNEL(FastArgs a) {
+__global__ void __launch_bounds__(64 * NWAVES) __attribute__((amdgpu_waves_per_eu(NDW > 64 ? 3 : (NWAVES > 2 ? 5 : 4))))
+sad_fast_kernel(FastArgs a) {
   // XCD-aware decode of the 1-D workgroup id: consecutive ids go round-robin over the 8 XCDs (each with its own
   // 4 MiB L2), so give XCD k the pairs k, k+8, ...: all strips and row segments of a pair then share one L2.
   // (Placement only affects speed; any mapping is correct.)
@@ -64,10 +57,6 @@ __global__ void __launch_bounds__(64 * NWAVES) SBM_FAST_WAVES_PER_EU SBM_FAST_KE
     pair = p;
     strip = inner;
   }
-#if SBM_FAST_PINGPONG
-  // LDS of the workgroup: per wavefront one area of WSLOT slots (staged row / exchange), then the merge area
-  auto strip_at = [&](auto cs_tag, const int cb) { sad_fast_pp_strip<NDW, NWAVES, NTERM, PW, EXACT_ND, decltype(cs_tag)::value>(a, cb, segi, pair); };
-#else
   // LDS of the workgroup: per wavefront the areas of DmaLds (two staged rows, further exchange levels), then the merge area
   const int wvk = NWAVES > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
   unsigned char* const ldsb = reinterpret_cast<unsigned char*>(fast_lds);
@@ -79,7 +68,6 @@ __global__ void __launch_bounds__(64 * NWAVES) SBM_FAST_WAVES_PER_EU SBM_FAST_KE
     sad_fast_strip_dma<NDW, NWAVES, NTERM, PW, EXACT_ND, CSV>(a, wb, wb + D::AREA_B, xl,
                                                             reinterpret_cast<u32*>(ldsb + NWAVES * D::WAVE_B), cb, segi, pair);
   };
-#endif
   if constexpr (DUAL) {
     constexpr int NV3 = 64 - (NTERM - 1), NV1 = 64 - PW * (NTERM - 1);
     if (strip < a.strips3) {
@@ -103,14 +91,9 @@ constexpr double kBorderModelRate = 3.6e12, kBorderRowUs = 2.0, kBorderColUs = 0
 template <int NDW, int NWAVES, int NTERM, int PW>
 static hipError_t launch_t(FastArgs a, bool border, hipStream_t s) {
   constexpr bool DUAL = PW == 3;
-  constexpr int WSLOT1 = FastLds<NDW, NTERM, PW, 1>::WSLOT, WSLOT3 = FastLds<NDW, NTERM, PW, DUAL ? 3 : 1>::WSLOT;
-  constexpr int WSLOTM = WSLOT1 > WSLOT3 ? WSLOT1 : WSLOT3;
-  // fallback build: per wavefront the staged-row / exchange area, then the workgroup's merge area
-  size_t lds = (size_t)NWAVES * WSLOTM * 16 + (NWAVES > 1 ? (size_t)2 * NWAVES * 64 * (4 + 8) : 0);
-  if (!SBM_FAST_PINGPONG) {  // LDS-direct strips: per wavefront the areas of DmaLds, then the merge area
-    constexpr int WB1 = DmaLds<NDW, NWAVES, NTERM, PW, 1>::WAVE_B, WB3 = DmaLds<NDW, NWAVES, NTERM, PW, DUAL ? 3 : 1>::WAVE_B;
-    lds = (size_t)NWAVES * (WB1 > WB3 ? WB1 : WB3) + (NWAVES > 1 ? (size_t)2 * NWAVES * 64 * (4 + 8) : 0);
-  }
+  // per wavefront the areas of DmaLds, then the workgroup's merge area
+  constexpr int WB1 = DmaLds<NDW, NWAVES, NTERM, PW, 1>::WAVE_B, WB3 = DmaLds<NDW, NWAVES, NTERM, PW, DUAL ? 3 : 1>::WAVE_B;
+  size_t lds = (size_t)NWAVES * (WB1 > WB3 ? WB1 : WB3) + (NWAVES > 1 ? (size_t)2 * NWAVES * 64 * (4 + 8) : 0);
   a.bord = a.bnw = 0;
   a.bseg = a.row1 - a.row0;
   a.nbseg = 0;
@@ -141,21 +124,21 @@ static hipError_t launch_t(FastArgs a, bool border, hipStream_t s) {
             a.nseg, a.npairs, a.bord, a.nbseg, grid.x, lds);
   // development builds: time the border wavefronts alone (results are wrong by construction)
   if (fast_tune().border_only) grid.x = (unsigned)(a.bord * a.nbseg);
-  // (the fallback build only carries the masked-count kernels: they are right for every count up to NDW * NWAVES)
-  // ... and <64,4> only runs one-pair calls beyond 192 disparities: its masked kernel serves 256 as well
+  // (the masked-count kernels are right for every count up to NDW * NWAVES; <64,4> only runs one-pair calls beyond 192
+  // disparities: its masked kernel serves 256 as well)
   // (three and four 128-disparity wavefronts, 257 .. 512 disparities: exact kernels for 384 and 512 -- 5-7 % over the masked ones,
   // profiles/r05_exact512.txt)
-  constexpr bool HAS_EXACT = !SBM_FAST_PINGPONG && !(NDW == 64 && NWAVES == 4);
+  constexpr bool HAS_EXACT = !(NDW == 64 && NWAVES == 4);
   const bool exact = HAS_EXACT && a.nd == NDW * NWAVES;
-  snprintf(g_sad_kernel_name, sizeof(g_sad_kernel_name), "%s<%d,%d,%d,%d,%s,%s> pfshift=%d", SBM_FAST_PINGPONG ? "sad_fast_pp_kernel" : "sad_fast_kernel",
+  snprintf(g_sad_kernel_name, sizeof(g_sad_kernel_name), "sad_fast_kernel<%d,%d,%d,%d,%s,%s> pfshift=%d",
            NDW, NWAVES, NTERM, PW, exact ? "true" : "false", DUAL ? "true" : "false", a.pfshift);
   if constexpr (HAS_EXACT) {
     if (exact) {
-      hipLaunchKernelGGL((SBM_FAST_KERNEL<NDW, NWAVES, NTERM, PW, true, DUAL>), grid, dim3(64 * NWAVES), lds, s, a);
+      hipLaunchKernelGGL((sad_fast_kernel<NDW, NWAVES, NTERM, PW, true, DUAL>), grid, dim3(64 * NWAVES), lds, s, a);
       return hipGetLastError();
     }
   }
-    hipLaunchKernelGGL((SBM_FAST_KERNEL<NDW, NWAVES, NTERM, PW, false, DUAL>), grid, dim3(64 * NWAVES), lds, s, a);
+    hipLaunchKernelGGL((sad_fast_kernel<NDW, NWAVES, NTERM, PW, false, DUAL>), grid, dim3(64 * NWAVES), lds, s, a);
   return hipGetLastError();
 }
 
@@ -165,15 +148,8 @@ static hipError_t launch_t(FastArgs a, bool border, hipStream_t s) {
 // per step against four 64-disparity wavefronts) -- except at exactly 192, where three 64-disparity wavefronts have no masked
 // disparities to carry (1080p nd 192: 2.09 against 2.51 ms; profiles/r04_dma_nd.txt). `split`: launches that cannot fill the chip
 // (one pair per call) spread the disparities over two to four narrower wavefronts instead -- half the serial work per row.
-// The fallback build has the 64-disparity layouts only.
 template <int NTERM, int PW>
 static hipError_t launch_nd(const FastArgs& a, bool border, bool split, hipStream_t s) {
-#if SBM_FAST_PINGPONG
-  if (a.nd <= 64) return launch_t<64, 1, NTERM, PW>(a, border, s);
-  if (a.nd <= 128) return launch_t<64, 2, NTERM, PW>(a, border, s);
-  if (a.nd <= 192) return launch_t<64, 3, NTERM, PW>(a, border, s);
-  return launch_t<64, 4, NTERM, PW>(a, border, s);
-#else
   if (a.nd > 384) return launch_t<128, 4, NTERM, PW>(a, border, s);
   if (a.nd > 256) return launch_t<128, 3, NTERM, PW>(a, border, s);
   if (a.nd <= 32) return launch_t<32, 1, NTERM, PW>(a, border, s);
@@ -183,7 +159,6 @@ static hipError_t launch_nd(const FastArgs& a, bool border, bool split, hipStrea
   if (a.nd <= 128) return launch_t<64, 2, NTERM, PW>(a, border, s);
   if (a.nd <= 192) return launch_t<64, 3, NTERM, PW>(a, border, s);
   return launch_t<64, 4, NTERM, PW>(a, border, s);
-#endif
 }
 
 // window dispatch of the other translation units (each holds the kernels of its windows; an unknown window falls through to the
@@ -191,6 +166,5 @@ static hipError_t launch_nd(const FastArgs& a, bool border, bool split, hipStrea
 hipError_t launch_sad_fast_pw1(const FastArgs& a, int wsz, bool border, bool split, hipStream_t s);   // sbm_sad_fast_pw1.hip: 5, 7, 9, 11, 13
 hipError_t launch_sad_fast_pw2(const FastArgs& a, int wsz, bool border, bool split, hipStream_t s);   // sbm_sad_fast_pw2.hip: 17, 19, 23, 25
 hipError_t launch_sad_fast_pw3(const FastArgs& a, int wsz, bool border, bool split, hipStream_t s);   // sbm_sad_fast_pw3.hip: 27, 29, 31
-hipError_t launch_sad_fast_pp(const FastArgs& a, int wsz, bool border, bool split, hipStream_t s);    // sbm_sad_fast_pp.hip: the fallback build, 5 .. 27
 
 }  // namespace sbm

@@ -1,5 +1,5 @@
 // sbm_sad_fast_strip.h -- one strip of the interior SAD kernel: 64 lanes x NDW disparities marching down a row segment, rows
-// staged by LDS-direct loads. Included by sbm_sad_fast_kernel.h (every build but the two-accumulator fallback). gfx950 only.
+// staged by LDS-direct loads. Included by sbm_sad_fast_kernel.h. gfx950 only.
 #pragma once
 #include "sbm_sad_fast_core.h"
 
@@ -62,7 +62,7 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
 
   // vertical sums, packed 4 x u16 per quad (low dword = indices 4q, 4q+1, high dword = 4q+2, 4q+3), accumulated in place
   // (v_mqsad_pk_u16_u8 with vdst == src2: right on gfx950 although LLVM marks vdst early-clobber -- tools/ubench/mqsad_alias, 9.4e9
-  // results, and the device self-test mqsad_inplace_ok(); sbm_sad_fast_pp.hip is the two-array fallback)
+  // results, and the device self-test mqsad_inplace_ok(); a device that fails it takes the sliding-sum kernel instead)
   u64 VB[NQ];
 #pragma unroll
   for (int q = 0; q < NQ; q++) VB[q] = 0ull;
