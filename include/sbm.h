@@ -31,8 +31,16 @@
  * would see a wrapped cost where this engine (and its oracle) keep the true one.
  *
  * Limits (SBM_ERR_UNSUPPORTED beyond them; cv::StereoBM itself has none of these): numDisparities <= 4096, at most 32 767 pairs
- * per call, image height <= 65 535. The speckle filter's band walk serves images up to 65 535 columns and (W + 288) * H < 2^27 and
- * speckleWindowSize up to 2048; larger images or windows take its row-walking kernels (same results, ~3x the stage time).
+ * per call, image height <= 65 535. There is no width limit: the left-right check keeps a row's claim table in LDS up to 8192
+ * columns and in device scratch beyond. The speckle filter's band walk serves images up to 65 535 columns and
+ * (W + 288) * H < 2^27 and speckleWindowSize up to 2048; larger images or windows take its row-walking kernels (same results,
+ * ~3x the stage time). tests/test_gpu_limits.py computes each of these edges and the first value past it. Disparities of 2048
+ * and more do not fit the int16 map: 16 * d wraps, as cv::StereoBM's (short) cast does, and the LR check ignores a claim that
+ * such a value points outside the row.
+ * Device scratch per pixel of a call (n * W * H), held by the handle until the size changes: ~4 B (prefiltered planes with their
+ * padding + the pre-check map), + 4 B with the LR check on (cost plane), + 8 B more when that check meets rows wider than 8192
+ * columns (its claim table), + 16 * (W + 288) / W + ~2 B with the speckle filter on (run records, seam lists), + 4 B for
+ * PREFILTER_NORMALIZED_RESPONSE. Every pixel of a host-memory call adds 4 B of staging.
  *
  * The hand-tuned kernels accumulate in place with v_mqsad_pk_u16_u8 (vdst == src2), which the hardware does right and the
  * compiler's register model forbids; a device self-test (once per device and process, on the stream of the first call that would

@@ -381,6 +381,9 @@ void sbmo_validate_disparity(int16_t* disp, size_t dstride, const int32_t* cost,
       if (d == INVALID) continue;
       int c = (g_reading & SBMO_READ_COST_SHORT) ? (int)(short)cp[x] : cp[x];
       int x2 = x - ((d + DISP_SCALE / 2) >> DISP_SHIFT);
+      /* beyond 2047 disparities 16 * d wraps in the int16 map (cv's (short) cast), so a claim can point outside the row:
+       * it claims nothing (the engine's LR kernels skip it the same way) */
+      if (x2 < 0 || x2 >= width) continue;
       if ((g_reading & SBMO_READ_LR_TIE_LATER) ? cost2[x2] >= c : cost2[x2] > c) {
         cost2[x2] = c;
         disp2[x2] = d;

@@ -29,6 +29,8 @@ struct sbm_handle {
   uint8_t *pf_l, *pf_r;
   int16_t* disp_pre;
   int32_t* cost;
+  unsigned long long* lr_keys;   // claim table of the LR check for rows wider than kLrLdsCols (lr_keys_bytes), else null
+  size_t lr_keys_bytes;
   void* spk_runs;        // speckle filter: 16 bytes per pixel (run records of the band walk / labels + sizes of the row-walking kernels)
   int32_t* spk_nheads;   // cap_n * H (runs per row)
   uint32_t* spk_seam;    // contacts across band seams (band walk of the speckle filter): cap_n * ceil(H/2) * W entries
@@ -197,6 +199,8 @@ int sbm_version(void) { return SBM_VERSION_MAJOR * 1000 + SBM_VERSION_MINOR; }
 
 static void free_scratch(sbm_handle* h) {
   hipFree(h->pf_l); hipFree(h->pf_r); hipFree(h->disp_pre); hipFree(h->cost);
+  hipFree(h->lr_keys);
+  h->lr_keys = nullptr; h->lr_keys_bytes = 0;
   hipFree(h->spk_runs); hipFree(h->spk_nheads); hipFree(h->spk_seam); hipFree(h->spk_nseam);
   h->spk_runs = nullptr; h->spk_nheads = nullptr; h->spk_seam = nullptr; h->spk_nseam = nullptr;
   hipFree(h->vsum);
@@ -243,6 +247,7 @@ static size_t scratch_bytes(const sbm_handle* h) {
   const size_t npix = (size_t)h->cap_n * h->cap_W * h->cap_H, plane = (size_t)h->cap_n * h->cap_pitch * h->cap_H;
   size_t b = 2 * plane + npix * 2;
   if (h->cost) b += npix * 4;
+  b += h->lr_keys_bytes;
   if (h->spk_runs) b += (size_t)h->cap_n * h->cap_H * (16 * ((size_t)h->cap_W + kSpkRecordPad) + 2 * ((size_t)h->cap_W + kSpkSeamPad) + 24);   // run records, seam lists, run / contact counts
   if (h->vsum) b += 2 * npix * sizeof(uint16_t);
   b += (size_t)h->st_n * h->st_W * h->st_H * 4 + h->pin_bytes;
@@ -433,6 +438,13 @@ static int ensure_scratch(sbm_handle* h, int n, int W, int H, int pitch, bool ne
   }
   const size_t npix = (size_t)h->cap_n * W * H;
   if (need_cost && !h->cost) HIPCHK(h, hipMalloc((void**)&h->cost, npix * sizeof(int32_t)));
+  const size_t keys = lr_keys_bytes(h->cap_n, W, H, need_cost);
+  if (keys > h->lr_keys_bytes) {
+    hipFree(h->lr_keys);
+    h->lr_keys = nullptr; h->lr_keys_bytes = 0;
+    HIPCHK(h, hipMalloc((void**)&h->lr_keys, keys));
+    h->lr_keys_bytes = keys;
+  }
   if (need_speckle && !h->spk_nseam) {   // keyed on the LAST buffer of the set: an attempt that failed half way is redone
     hipFree(h->spk_runs); hipFree(h->spk_nheads); hipFree(h->spk_seam);
     h->spk_runs = nullptr; h->spk_nheads = nullptr; h->spk_seam = nullptr;
@@ -576,7 +588,7 @@ int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_r
     }
   }
   mark(h, 2);
-  HIPCHK(h, launch_lrcheck(h->disp_pre, h->cost, out, g, p.disp12_max_diff, h->stream));
+  HIPCHK(h, launch_lrcheck(h->disp_pre, h->cost, out, h->lr_keys, g, p.disp12_max_diff, h->stream));
   mark(h, 4);
   if (speckle)
     HIPCHK(h, launch_speckle(out, h->spk_runs, h->spk_nheads, h->spk_seam, h->spk_nseam, g, p.speckle_window_size, p.speckle_range, h->stream));

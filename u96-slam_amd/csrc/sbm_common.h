@@ -100,8 +100,14 @@ hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* di
                            int* xa, int* xb, bool border, hipStream_t s);
 
 // Left-right consistency (cv validateDisparity) + invalid rows/columns fill. Reads disp_pre/cost, writes disp_out.
-hipError_t launch_lrcheck(const int16_t* disp_pre, const int32_t* cost, int16_t* disp_out, const Geom& g,
-                          int disp12_max_diff, hipStream_t s);
+// Rows wider than kLrLdsCols keep their claim table in global memory: keys = n * H * W 64-bit words (lr_keys_bytes; null
+// when the LR check is off or every row fits LDS).
+constexpr int kLrLdsCols = 8192;   // 8 B per column: 64 KiB of LDS, the most a kernel gets without asking
+inline size_t lr_keys_bytes(int n, int W, int H, bool do_lr) {
+  return do_lr && W > kLrLdsCols ? (size_t)n * H * W * sizeof(unsigned long long) : 0;
+}
+hipError_t launch_lrcheck(const int16_t* disp_pre, const int32_t* cost, int16_t* disp_out, unsigned long long* keys,
+                          const Geom& g, int disp12_max_diff, hipStream_t s);
 
 // cv filterSpeckles as parallel connected components (union-find). Scratch, for n pairs of W x H (the band walk cuts a row into
 // up to kSpkMaxSeg column segments with books of their own, hence the padding): runs: 16 * n * H * (W + kSpkRecordPad) bytes (run

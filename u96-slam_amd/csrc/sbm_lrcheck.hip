@@ -17,6 +17,8 @@ namespace sbm {
 // the claimant with minimum (cost, x).  That is order-free: one LDS atomicMin on the 64-bit key cost<<32|x per
 // pixel.  Pass 2 is per-pixel.  One workgroup owns one image row; the same kernel writes the never-valid rows and
 // columns (outside the valid ROI) as FILTERED, which cv does after validateDisparity.
+// The claim table of a row is W 64-bit keys: in LDS up to kLrLdsCols (8192) columns, the 64 KiB a kernel gets without
+// hipFuncSetAttribute; wider rows (GK) use the row's slice of a global table of n * H * W keys from the handle's scratch.
 // ---------------------------------------------------------------------------------------------------------
 struct LrArgs {
   const int16_t* disp_pre;
@@ -26,10 +28,12 @@ struct LrArgs {
   int W, H, mindisp, nd, tol, filtered, row0, row1, col0, col1, do_lr;
   int cx0, cx1;  // columns [cx0,cx1) of disp_pre were computed; the rest reads as FILTERED
   int cost_short, tie_later;   // alternative readings (sbm_common.h kRead*): generic kernel only
+  unsigned long long* keys;    // global claim table (n * H * W keys), rows wider than kLrLdsCols only
 };
 
 extern __shared__ __attribute__((aligned(16))) unsigned long long lr_keys[];
 
+template <bool GK>
 __global__ void __launch_bounds__(256) lrcheck_kernel(LrArgs a) {
   const int y = blockIdx.x;
   const size_t base = ((size_t)blockIdx.y * a.H + y) * a.W;
@@ -48,7 +52,9 @@ __global__ void __launch_bounds__(256) lrcheck_kernel(LrArgs a) {
   const int32_t* cp32 = static_cast<const int32_t*>(a.cost) + base;
   const int INV = a.filtered;
   const int minX1 = max(max(a.mindisp + a.nd, 0), a.cx0), maxX1 = min(a.W + min(a.mindisp, 0), a.cx1);
-  for (int x = threadIdx.x; x < a.W; x += 256) lr_keys[x] = ~0ull;
+  unsigned long long* const keys = GK ? a.keys + base : lr_keys;
+  for (int x = threadIdx.x; x < a.W; x += 256) keys[x] = ~0ull;
+  if (GK) __threadfence();   // the row's reset reaches L2 before any wavefront of the workgroup claims
   __syncthreads();
   for (int x = minX1 + threadIdx.x; x < maxX1; x += 256) {
     const int d = dp[x];
@@ -58,10 +64,17 @@ __global__ void __launch_bounds__(256) lrcheck_kernel(LrArgs a) {
       unsigned c = a.cost16 ? (unsigned)cp16[x] : (unsigned)cp32[x];
       if (a.cost_short) c = (unsigned)((int)(short)c + 32768);            // order of the wrapped `short`
       // cheapest claimant, then the earliest x (cv's strict '>'); tie_later: then the latest x
-      atomicMin(&lr_keys[x2], ((unsigned long long)c << 32) | (unsigned)(a.tie_later ? a.W - 1 - x : x));
+      atomicMin(&keys[x2], ((unsigned long long)c << 32) | (unsigned)(a.tie_later ? a.W - 1 - x : x));
     }
   }
+  if (GK) __threadfence();
   __syncthreads();
+  // Global table: the claims were atomics, performed in L2; a plain load could hit a line the per-CU vector L1 still holds
+  // from before them (the reset above), so the keys are read with agent-scope atomic loads, which go to L2.
+  auto key_at = [&](int i) -> unsigned long long {
+    if (GK) return __hip_atomic_load(&keys[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return keys[i];
+  };
   for (int x = threadIdx.x; x < a.W; x += 256) {
     int d = (x >= a.cx0 && x < a.cx1) ? dp[x] : INV;
     if (x < a.col0 || x >= a.col1) {
@@ -70,7 +83,7 @@ __global__ void __launch_bounds__(256) lrcheck_kernel(LrArgs a) {
       const int xa = x - (d >> 4), xb = x - ((d + 15) >> 4);
       bool bad_a = false, bad_b = false;
       if (xa >= 0 && xa < a.W) {
-        const unsigned long long k = lr_keys[xa];
+        const unsigned long long k = key_at(xa);
         if (k != ~0ull) {
           const int xw = (int)(k & 0xffffffffu);
           const int d2 = dp[a.tie_later ? a.W - 1 - xw : xw];
@@ -78,7 +91,7 @@ __global__ void __launch_bounds__(256) lrcheck_kernel(LrArgs a) {
         }
       }
       if (xb >= 0 && xb < a.W) {
-        const unsigned long long k = lr_keys[xb];
+        const unsigned long long k = key_at(xb);
         if (k != ~0ull) {
           const int xw = (int)(k & 0xffffffffu);
           const int d2 = dp[a.tie_later ? a.W - 1 - xw : xw];
@@ -245,9 +258,10 @@ __global__ void __launch_bounds__(320) lrcheck16_kernel(LrArgs a) {
   }
 }
 
-hipError_t launch_lrcheck(const int16_t* disp_pre, const int32_t* cost, int16_t* disp_out, const Geom& g,
-                          int disp12_max_diff, hipStream_t s) {
+hipError_t launch_lrcheck(const int16_t* disp_pre, const int32_t* cost, int16_t* disp_out, unsigned long long* keys,
+                          const Geom& g, int disp12_max_diff, hipStream_t s) {
   LrArgs a;
+  a.keys = keys;
   a.disp_pre = disp_pre; a.cost = cost; a.disp_out = disp_out; a.cost16 = g.cost16;
   a.W = g.W; a.H = g.H; a.mindisp = g.mindisp; a.nd = g.nd; a.tol = disp12_max_diff * 16; a.filtered = g.filtered;
   a.row0 = g.row0; a.row1 = g.row1; a.col0 = g.col0; a.col1 = g.col1; a.do_lr = disp12_max_diff >= 0;
@@ -284,8 +298,13 @@ hipError_t launch_lrcheck(const int16_t* disp_pre, const int32_t* cost, int16_t*
     if (launched) return hipGetLastError();
     a.tol = disp12_max_diff * 16;   // (no such instantiation: the generic kernel below)
   }
-  size_t lds = a.do_lr ? (size_t)g.W * sizeof(unsigned long long) : 0;
-  hipLaunchKernelGGL(lrcheck_kernel, dim3(g.H, g.n), dim3(256), lds, s, a);
+  if (a.do_lr && g.W > kLrLdsCols) {
+    if (!keys) return hipErrorInvalidValue;   // (the caller sizes the table with lr_keys_bytes)
+    hipLaunchKernelGGL(lrcheck_kernel<true>, dim3(g.H, g.n), dim3(256), 0, s, a);
+  } else {
+    const size_t lds = a.do_lr ? (size_t)g.W * sizeof(unsigned long long) : 0;
+    hipLaunchKernelGGL(lrcheck_kernel<false>, dim3(g.H, g.n), dim3(256), lds, s, a);
+  }
   return hipGetLastError();
 }
 

@@ -146,6 +146,12 @@ hipError_t launch_sad_generic(const uint8_t* pf_l, const uint8_t* pf_r, int16_t*
   a.row0 = g.row0; a.row1 = g.row1; a.xa = xa; a.xb = xb;
   dim3 grid((xb - xa + kGenCols - 1) / kGenCols, (g.row1 - g.row0 + kGenSeg - 1) / kGenSeg, g.n);
   size_t lds = (size_t)kGenCols * (g.nd + 2) * sizeof(int);
+  // (at 4096 disparities that is more than the 64 KB of dynamic LDS a kernel gets without asking; idempotent)
+  if (lds > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sad_generic_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+  }
   hipLaunchKernelGGL(sad_generic_kernel, grid, dim3(64 * kGenCols), lds, s, a);
   return hipGetLastError();
 }
