@@ -79,7 +79,8 @@
  *                                          prefiltered instead of filled with preFilterCap, 16 = LR check: equal cost -> the later x
  *                                          wins. The oracle has the same bits; tests/golden/pin_kit.npz holds this engine's outputs
  *                                          under both readings of each, and tools/verify_with_opencv.py (numpy + cv2 only) names the
- *                                          reading a given OpenCV implements -- adopting it is a default flip here, not a rewrite
+ *                                          reading a given OpenCV implements -- adopting it is a default flip here, not a rewrite;
+ *                                          bits 32 and 64 belong to the semi-global matcher (see sbm_sgbm_params below)
  * Tuning knobs of the measurement scripts (SBM_FAST_NSEG, SBM_FAST_TAPER, SBM_FAST_UNIQ_PLAIN,
  * SBM_FAST_SPLIT, SBM_PF_ROWS, SBM_HOST_CHUNK, SBM_HOST_PIPELINE, SBM_DEV_*; the interior kernel's are listed in
  * u96-slam_amd/csrc/sbm_sad_fast_dev.h) exist only in development builds (-DSBM_DEV, tools/exp/r05_devlib.sh); this library
@@ -369,6 +370,67 @@ int sbm_gftt_eig_device(sbm_handle* h, int n, const void* d_img, int width, int 
 /* Host-memory form for one image (what FPGA.cpp:283-291 builds: a CV_16UC1 map and the Max register). Synchronous. */
 int sbm_gftt_eig(sbm_handle* h, const uint8_t* img, size_t img_stride, int width, int height, uint16_t* eig, size_t eig_stride,
                  uint32_t* max_out);
+
+/* ---- semi-global matcher: cv::StereoSGBM (the reference's DEPTH_METHOD_CV_SGBM, main.cpp:218-234) -------------------------
+ * Restatement of cv::StereoSGBM::compute() for 8-bit single-channel pairs in MODE_HH (two passes, 8 paths: the reference's
+ * mode, main.cpp:219-230) and MODE_SGBM (OpenCV's default: one pass, 5 paths). Output contract as for the block matcher:
+ * int16, 1/16 px, invalid pixels hold (minDisparity - 1) * 16. Stages: Birchfield-Tomasi costs on the clipped x-Sobel and on
+ * the raw image (that one >> 2), summed over the block with clamped borders -> C (int16, biased by P2 as OpenCV keeps it) over
+ * the width1 = maxX1 - minX1 computable columns -> path sweeps summed into S -> winner-take-all, uniqueness, parabolic sub-pixel
+ * and SGBM's own left-right check through its claim table -> 3x3 median (replicated border) -> speckle filter with
+ * 16 * speckleRange. Parameters are passed per call and run on an existing handle (its stream and device).
+ *
+ * Exactness envelope. With blockSize_eff = 2 * (blockSize / 2) + 1 (blockSize <= 0 -> 5), ftzero = max(preFilterCap, 15) | 1
+ * and P2_eff = max(P2 > 0 ? P2 : 5, P1_eff + 1), every call with blockSize_eff^2 * (2 * ftzero + 63) + P2_eff <= 32767 is
+ * computed; inside it every path cost lies in [C - P2_eff, C] and is non-negative, so OpenCV's two saturating int16 sums equal
+ * min(32767, sum of all path costs) in any order, which is what the engine computes. Outside it OpenCV's int16 casts wrap; such
+ * calls return SBM_ERR_UNSUPPORTED (the reference's call is at 12 253). Other limits (SBM_ERR_UNSUPPORTED beyond them):
+ * numDisparities <= 512, width <= 8192, height <= 65 535, preFilterCap <= 63, uniquenessRatio <= 65 535, minDisparity >= -2047
+ * and minDisparity + numDisparities <= 2047 (every disparity * 16 fits the int16 map), speckleRange >= 0 when the speckle filter
+ * is on, at most 32 767 pairs per call. tests/test_gpu_sgbm.py computes each edge and the first value past it.
+ * Device scratch: a call works through its pairs in chunks, every stage (median and speckle filter included) chunk by chunk, so
+ * that the scratch of one chunk stays within 2 GiB (one pair at a time when a single pair is larger): per pair, C and S at 4 B
+ * per cell (width1 * height * numDisparities), the map before the median at 2 B per pixel, and with speckleWindowSize > 0 the
+ * speckle filter's scratch, 16 * (W + 288) / W + ~2 B per pixel. Every pixel of a host-memory call adds 4 B of staging.
+ * Readings nobody could pin (bits of SBM_CV_READING above the block matcher's, which ignores them): 32 = no medianBlur stage,
+ * 64 = the bottom rows (y + blockSize/2 >= height, y > 0) sum a clamped window instead of keeping what OpenCV's incremental
+ * box sum leaves there (the P2 bias alone in MODE_HH, the previous row's C in MODE_SGBM). */
+#define SBM_SGBM_MODE_SGBM 0
+#define SBM_SGBM_MODE_HH 1
+#define SBM_SGBM_MODE_SGBM_3WAY 2
+#define SBM_SGBM_MODE_HH4 3
+
+typedef struct sbm_sgbm_params {  /* one field per cv::StereoSGBM::create argument, in its order */
+  int32_t min_disparity;           /* default 0                                                   */
+  int32_t num_disparities;         /* default 16; > 0 and divisible by 16                         */
+  int32_t block_size;              /* default 3; <= 0 -> 5                                        */
+  int32_t p1;                      /* default 0 -> 2                                              */
+  int32_t p2;                      /* default 0 -> max(5, P1 + 1)                                 */
+  int32_t disp12_max_diff;         /* default 0; <= 0 -> 1 (the LR check is always on)            */
+  int32_t prefilter_cap;           /* default 0; ftzero = max(cap, 15) | 1                        */
+  int32_t uniqueness_ratio;        /* default 0; < 0 -> 10                                        */
+  int32_t speckle_window_size;     /* default 0 (off)                                             */
+  int32_t speckle_range;           /* default 0; the filter gets 16 * speckleRange                */
+  int32_t mode;                    /* default SBM_SGBM_MODE_SGBM                                  */
+} sbm_sgbm_params;
+
+/* Fill *p with cv::StereoSGBM::create(minDisparity, numDisparities, blockSize) and the defaults of the other arguments. */
+void sbm_sgbm_params_default(sbm_sgbm_params* p, int min_disparity, int num_disparities, int block_size);
+/* SBM_ERR_SIZE (width/height <= 0), SBM_ERR_NUM_DISPARITIES (<= 0 or not divisible by 16), SBM_ERR_UNSUPPORTED (MODE_HH4,
+ * MODE_SGBM_3WAY, an unknown mode, outside the exactness envelope or the limits above), else SBM_OK. */
+int sbm_sgbm_params_validate(const sbm_sgbm_params* p, int width, int height);
+/* One pair in HOST memory (the main.cpp:233 shape): strided 8-bit inputs, strided int16 output, strides in bytes. Synchronous. */
+int sbm_sgbm_compute(sbm_handle* h, const sbm_sgbm_params* p, const uint8_t* left, size_t left_stride, const uint8_t* right,
+                     size_t right_stride, int width, int height, int16_t* disp, size_t disp_stride);
+/* n dense pairs resident in DEVICE memory; disp = n*height*width int16. Asynchronous on the handle's stream unless sync != 0,
+ * with the ordering rules of sbm_compute_device. */
+int sbm_sgbm_compute_device(sbm_handle* h, const sbm_sgbm_params* p, int n, const void* d_left, const void* d_right, int width,
+                            int height, void* d_disp, int sync);
+/* sbm_debug_fetch `which` values for the LAST sbm_sgbm_compute_device call: 4 = C, 5 = S (int16, n * height * width1 *
+ * numDisparities, [pair][y][x - minX1][d - minDisparity]; SBM_ERR_UNSUPPORTED when width1 < 1), 6 = the map before the median
+ * (int16, n*height*width); all three only when the call's pairs fitted one chunk, else SBM_ERR_UNSUPPORTED.
+ * sbm_get_profile: while profiling is enabled (any mode) SGBM calls synchronise after each chunk and record "sgbm_cost",
+ * "sgbm_aggregate", "sgbm_select", "sgbm_median", "sgbm_speckle", "sgbm_total" (ms of the last call, summed over its chunks). */
 
 /* The raw HIP stream (hipStream_t) as void*, so callers can order their own work behind ours (record an event on it
  * after sbm_compute_device(..., sync = 0)) or ours behind theirs (hipStreamWaitEvent on it before the call). Every entry

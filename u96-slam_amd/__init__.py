@@ -4,6 +4,7 @@ sdoira/U96-SLAM, src/slam/src/core/main.cpp:197-217).
 Layout
   csrc/         hand-written HIP kernels (gfx950) + the C-ABI (include/sbm.h)  -> lib/libsbm_hip.so
   stereobm.py   host-side mirror of the cv::StereoBM interface over that C-ABI (ctypes)
+  stereosgbm.py the same for cv::StereoSGBM (MODE_HH / MODE_SGBM)
   synth.py      deterministic synthetic stereo frames
   shard.py      one-process-per-GPU sharding of pair batches (torch.distributed; RCCL on GPU, gloo on CPU)
 
@@ -13,7 +14,9 @@ GPU raises. The CPU oracle lives in /oracle and is only used by the tests and by
 from .stereobm import (StereoBM, StereoBMError, SbmParams, StereoModel, library_path, load_library, PREFILTER_XSOBEL,  # noqa: F401
                        PREFILTER_NORMALIZED_RESPONSE, RectCam, make_rect_cam, PREFILTER_FLAVOUR_CV, PREFILTER_FLAVOUR_RTL, trim,
                        FpgaParams, fpga_params, fpga_params_from_regs, fpga_sad_size_reg, fpga_validate, compute_multi)
+from .stereosgbm import StereoSGBM, SgbmParams, sgbm_params, sgbm_validate  # noqa: F401
 
 __all__ = ["StereoBM", "StereoBMError", "SbmParams", "StereoModel", "library_path", "load_library", "PREFILTER_XSOBEL",
            "PREFILTER_NORMALIZED_RESPONSE", "RectCam", "make_rect_cam", "PREFILTER_FLAVOUR_CV", "PREFILTER_FLAVOUR_RTL", "trim",
-           "FpgaParams", "fpga_params", "fpga_params_from_regs", "fpga_sad_size_reg", "fpga_validate", "compute_multi"]
+           "FpgaParams", "fpga_params", "fpga_params_from_regs", "fpga_sad_size_reg", "fpga_validate", "compute_multi",
+           "StereoSGBM", "SgbmParams", "sgbm_params", "sgbm_validate"]

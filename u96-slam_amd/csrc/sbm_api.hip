@@ -85,6 +85,20 @@ struct sbm_handle {
   bool ev_ok;
   unsigned calls;  // calls recorded since profiling was (re)enabled
   float ms_prefilter, ms_sad, ms_border, ms_lr, ms_speckle, ms_total;
+  // semi-global matcher (allocated on first use): C and S for sg_chunk pairs, the map before the median for sg_n pairs, the
+  // speckle filter's scratch for sg_n pairs; the geometry of the last call for sbm_debug_fetch
+  int16_t *sg_C, *sg_S;
+  size_t sg_cs_bytes;
+  int16_t* sg_pre;
+  size_t sg_pre_bytes;
+  int sg_spk_n, sg_spk_W, sg_spk_H;
+  void* sg_spk_runs;
+  int32_t *sg_spk_nheads, *sg_spk_nseam;
+  uint32_t* sg_spk_seam;
+  SgbmGeom sg_last;
+  bool sg_have_last, sg_last_one_chunk;
+  hipEvent_t sg_ev[6];
+  float sg_ms[6];   // cost, aggregate, select, median, speckle, total
 };
 
 // Entry points select the handle's device and put the caller's current device back on return.
@@ -209,6 +223,15 @@ static void free_scratch(sbm_handle* h) {
   h->cap_n = h->cap_W = h->cap_H = h->cap_pitch = 0;
 }
 
+static void free_sgbm(sbm_handle* h) {
+  hipFree(h->sg_C); hipFree(h->sg_S); hipFree(h->sg_pre);
+  h->sg_C = h->sg_S = h->sg_pre = nullptr; h->sg_cs_bytes = h->sg_pre_bytes = 0;
+  hipFree(h->sg_spk_runs); hipFree(h->sg_spk_nheads); hipFree(h->sg_spk_seam); hipFree(h->sg_spk_nseam);
+  h->sg_spk_runs = nullptr; h->sg_spk_nheads = h->sg_spk_nseam = nullptr; h->sg_spk_seam = nullptr;
+  h->sg_spk_n = h->sg_spk_W = h->sg_spk_H = 0;
+  h->sg_have_last = false;
+}
+
 static void free_fpga(sbm_handle* h) {
   hipFree(h->fp_xs_l); hipFree(h->fp_xs_r); hipFree(h->fp_rec); hipFree(h->fp_flag);
   h->fp_xs_l = h->fp_xs_r = nullptr; h->fp_rec = nullptr; h->fp_flag = nullptr;
@@ -253,6 +276,8 @@ static size_t scratch_bytes(const sbm_handle* h) {
   b += (size_t)h->st_n * h->st_W * h->st_H * 4 + h->pin_bytes;
   b += (size_t)h->fq_n * h->fq_W * h->fq_H * 8;
   b += (size_t)h->fp_n * h->fp_W * h->fp_H * 10;
+  b += 2 * h->sg_cs_bytes + h->sg_pre_bytes;
+  if (h->sg_spk_runs) b += (size_t)h->sg_spk_n * h->sg_spk_H * (16 * ((size_t)h->sg_spk_W + kSpkRecordPad) + 4 * ((size_t)h->sg_spk_W + kSpkSeamPad) + 24);
   return b;
 }
 
@@ -278,9 +303,11 @@ int sbm_create(sbm_handle** out, const sbm_params* p, int device) {
         h->p = *p;
         h->last_hip = 0;
         h->have_last = false;
+        h->sg_have_last = false;
         h->profiling = 0;
         h->calls = 0;
         h->ms_prefilter = h->ms_sad = h->ms_border = h->ms_lr = h->ms_speckle = h->ms_total = 0.f;
+        for (float& t : h->sg_ms) t = 0.f;
         *out = h;
         return SBM_OK;
       }
@@ -332,6 +359,7 @@ void sbm_destroy(sbm_handle* h) {
         free_staging(h);
         free_feed(h);
         free_fpga(h);
+        free_sgbm(h);
       }
       g_pool[g_pool_n++] = h;
       return;
@@ -350,6 +378,9 @@ static void destroy_now(sbm_handle* h) {
   free_staging(h);
   free_feed(h);
   free_fpga(h);
+  free_sgbm(h);
+  for (int i = 0; i < 6; i++)
+    if (h->sg_ev[i]) hipEventDestroy(h->sg_ev[i]);
   for (int r = 0; r < sbm_handle::kRing; r++)
     for (int i = 0; i < sbm_handle::kMarks; i++)
       if (h->ev[r][i]) hipEventDestroy(h->ev[r][i]);
@@ -402,6 +433,7 @@ int sbm_set_profiling(sbm_handle* h, int enabled) {
   h->ncall = 0;
   h->instr = false;
   h->ms_prefilter = h->ms_sad = h->ms_border = h->ms_lr = h->ms_speckle = h->ms_total = 0.f;
+  for (float& t : h->sg_ms) t = 0.f;
   return SBM_OK;
 }
 
@@ -750,6 +782,193 @@ int sbm_fpga_compute(sbm_handle* h, const uint8_t* left, size_t left_stride, con
   return SBM_OK;
 }
 
+// ---- semi-global matcher (cv::StereoSGBM, MODE_HH / MODE_SGBM) ---------------------------------------------------------------
+void sbm_sgbm_params_default(sbm_sgbm_params* p, int min_disparity, int num_disparities, int block_size) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->min_disparity = min_disparity;
+  p->num_disparities = num_disparities;
+  p->block_size = block_size;
+  p->mode = SBM_SGBM_MODE_SGBM;
+}
+
+static void sgbm_effective(const sbm_sgbm_params& p, int& bs, int& ftzero, int& P1, int& P2) {
+  bs = 2 * ((p.block_size > 0 ? p.block_size : 5) / 2) + 1;
+  ftzero = std::max(p.prefilter_cap, 15) | 1;
+  P1 = p.p1 > 0 ? p.p1 : 2;
+  P2 = std::max(p.p2 > 0 ? p.p2 : 5, P1 + 1);
+}
+
+int sbm_sgbm_params_validate(const sbm_sgbm_params* p, int width, int height) {
+  if (!p) return SBM_ERR_NULL;
+  if (width <= 0 || height <= 0) return SBM_ERR_SIZE;
+  if (p->num_disparities <= 0 || p->num_disparities % 16 != 0) return SBM_ERR_NUM_DISPARITIES;
+  if (p->mode != SBM_SGBM_MODE_SGBM && p->mode != SBM_SGBM_MODE_HH) return SBM_ERR_UNSUPPORTED;
+  if (p->num_disparities > kSgbmNdMax || width > kSgbmWMax || height > 65535 || p->prefilter_cap > 63 ||
+      p->uniqueness_ratio > 65535 || (p->speckle_window_size > 0 && p->speckle_range < 0))
+    return SBM_ERR_UNSUPPORTED;
+  // (every disparity * 16 of the map, (minDisparity - 1) * 16 included, must fit int16)
+  if (p->min_disparity < -2047 || (long)p->min_disparity + p->num_disparities > 2047) return SBM_ERR_UNSUPPORTED;
+  int bs, ftzero, P1, P2;
+  sgbm_effective(*p, bs, ftzero, P1, P2);
+  if ((long)bs * bs * (2 * ftzero + 63) + P2 > 32767) return SBM_ERR_UNSUPPORTED;   // the exactness envelope
+  return SBM_OK;
+}
+
+static int ensure_sgbm(sbm_handle* h, size_t cs_bytes, size_t pre_bytes, int n, int W, int H, bool speckle) {
+  if (cs_bytes > h->sg_cs_bytes || pre_bytes > h->sg_pre_bytes) HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (cs_bytes > h->sg_cs_bytes) {
+    hipFree(h->sg_C); hipFree(h->sg_S);
+    h->sg_C = h->sg_S = nullptr; h->sg_cs_bytes = 0;
+    HIPCHK(h, hipMalloc((void**)&h->sg_C, cs_bytes));
+    HIPCHK(h, hipMalloc((void**)&h->sg_S, cs_bytes));
+    h->sg_cs_bytes = cs_bytes;
+  }
+  if (pre_bytes > h->sg_pre_bytes) {
+    hipFree(h->sg_pre);
+    h->sg_pre = nullptr; h->sg_pre_bytes = 0;
+    HIPCHK(h, hipMalloc((void**)&h->sg_pre, pre_bytes));
+    h->sg_pre_bytes = pre_bytes;
+  }
+  if (speckle && !(h->sg_spk_nseam && n <= h->sg_spk_n && W == h->sg_spk_W && H == h->sg_spk_H)) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hipFree(h->sg_spk_runs); hipFree(h->sg_spk_nheads); hipFree(h->sg_spk_seam); hipFree(h->sg_spk_nseam);
+    h->sg_spk_runs = nullptr; h->sg_spk_nheads = h->sg_spk_nseam = nullptr; h->sg_spk_seam = nullptr;
+    h->sg_spk_n = h->sg_spk_W = h->sg_spk_H = 0;
+    // sizes: launch_speckle (sbm_common.h)
+    HIPCHK(h, hipMalloc(&h->sg_spk_runs, (size_t)n * H * ((size_t)W + kSpkRecordPad) * 16));
+    HIPCHK(h, hipMalloc((void**)&h->sg_spk_nheads, (size_t)n * H * kSpkMaxSeg * sizeof(int32_t)));
+    const size_t seams = (size_t)n * ((H + 1) / 2);
+    HIPCHK(h, hipMalloc((void**)&h->sg_spk_seam, seams * ((size_t)W + kSpkSeamPad) * sizeof(uint32_t)));
+    HIPCHK(h, hipMalloc((void**)&h->sg_spk_nseam, seams * kSpkMaxSeg * sizeof(int32_t)));
+    h->sg_spk_n = n; h->sg_spk_W = W; h->sg_spk_H = H;
+  }
+  return SBM_OK;
+}
+
+// Device scratch of one chunk of pairs -- C, S, the map before the median and (speckle filter on) its scratch -- stays within
+// kSgbmChunkBytes; a single pair larger than that runs alone.
+static constexpr size_t kSgbmChunkBytes = (size_t)2 << 30;
+
+static size_t sgbm_speckle_bytes_per_pair(int W, int H) {   // sizes: launch_speckle (sbm_common.h), as allocated by ensure_sgbm
+  const size_t seams = (size_t)(H + 1) / 2;
+  return (size_t)H * ((size_t)W + kSpkRecordPad) * 16 + (size_t)H * kSpkMaxSeg * sizeof(int32_t) +
+         seams * (((size_t)W + kSpkSeamPad) * sizeof(uint32_t) + kSpkMaxSeg * sizeof(int32_t));
+}
+
+int sbm_sgbm_compute_device(sbm_handle* h, const sbm_sgbm_params* p, int n, const void* d_left, const void* d_right, int width,
+                            int height, void* d_disp, int sync) {
+  if (!h || !p || !d_left || !d_right || !d_disp) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  int st = sbm_sgbm_params_validate(p, width, height);
+  if (st != SBM_OK) return st;
+  if (n > 32767) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+
+  SgbmGeom g;
+  memset(&g, 0, sizeof(g));
+  int bs, ftzero, P1, P2;
+  sgbm_effective(*p, bs, ftzero, P1, P2);
+  g.W = width; g.H = height;
+  g.minD = p->min_disparity; g.D = p->num_disparities;
+  g.minX1 = std::max(g.minD + g.D, 0); g.maxX1 = width + std::min(g.minD, 0); g.W1 = g.maxX1 - g.minX1;
+  g.SW2 = bs / 2; g.P1 = P1; g.P2 = P2; g.ftzero = ftzero;
+  g.uniq = p->uniqueness_ratio >= 0 ? p->uniqueness_ratio : 10;
+  g.d12 = p->disp12_max_diff > 0 ? p->disp12_max_diff : 1;
+  g.fullDP = p->mode == SBM_SGBM_MODE_HH;
+  g.reading = env_switch("SBM_CV_READING", 0);
+  const bool speckle = p->speckle_window_size > 0;
+  const size_t npix = (size_t)width * height;
+  const size_t pair_cs = g.W1 >= 1 ? (size_t)g.W1 * height * g.D * sizeof(int16_t) : 0;
+  const size_t pair_bytes = 2 * pair_cs + npix * sizeof(int16_t) + (speckle ? sgbm_speckle_bytes_per_pair(width, height) : 0);
+  const int chunk = (int)std::min<size_t>(n, std::max<size_t>(1, kSgbmChunkBytes / pair_bytes));
+  st = ensure_sgbm(h, pair_cs * chunk, (size_t)chunk * npix * sizeof(int16_t), chunk, width, height, speckle);
+  if (st != SBM_OK) return st;
+  g.n = n;
+  h->sg_last = g;
+  h->sg_have_last = true;
+  h->sg_last_one_chunk = chunk == n;
+
+  const bool prof = h->profiling != 0;
+  if (prof) {
+    for (int i = 0; i < 6; i++)
+      if (!h->sg_ev[i]) HIPCHK(h, hipEventCreate(&h->sg_ev[i]));
+    for (int i = 0; i < 6; i++) h->sg_ms[i] = 0.f;
+  }
+  auto mark = [&](int i) -> hipError_t { return prof ? hipEventRecord(h->sg_ev[i], h->stream) : hipSuccess; };
+  auto lap = [&](int a, int b, int slot) -> hipError_t {
+    float ms = 0.f;
+    hipError_t e = hipEventSynchronize(h->sg_ev[b]);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, h->sg_ev[a], h->sg_ev[b]);
+    h->sg_ms[slot] += ms;
+    return e;
+  };
+  const uint8_t* dl = (const uint8_t*)d_left;
+  const uint8_t* dr = (const uint8_t*)d_right;
+  const int inv = (g.minD - 1) * 16;
+  const int max_diff = (int)std::min<long>(16L * p->speckle_range, 1L << 17);
+  // every stage, the median and the speckle filter included, runs chunk by chunk
+  for (int c0 = 0; c0 < n; c0 += chunk) {
+    SgbmGeom gc = g;
+    gc.n = std::min(chunk, n - c0);
+    int16_t* out = (int16_t*)d_disp + (size_t)c0 * npix;
+    HIPCHK(h, mark(0));
+    if (pair_cs) {
+      HIPCHK(h, launch_sgbm_cost(dl + (size_t)c0 * npix, dr + (size_t)c0 * npix, h->sg_S, h->sg_C, gc, h->stream));
+      HIPCHK(h, mark(1));
+      HIPCHK(h, launch_sgbm_paths(h->sg_C, h->sg_S, gc, h->stream));
+      HIPCHK(h, mark(2));
+      HIPCHK(h, launch_sgbm_select(h->sg_S, h->sg_pre, gc, h->stream));
+    } else {   // no computable column: every pixel is invalid (the median and the speckle filter keep it so)
+      HIPCHK(h, mark(1));
+      HIPCHK(h, mark(2));
+      HIPCHK(h, launch_sgbm_fill(h->sg_pre, (size_t)gc.n * npix, inv, h->stream));
+    }
+    HIPCHK(h, mark(3));
+    if (g.reading & kReadSgbmNoMedian)
+      HIPCHK(h, hipMemcpyAsync(out, h->sg_pre, (size_t)gc.n * npix * sizeof(int16_t), hipMemcpyDeviceToDevice, h->stream));
+    else
+      HIPCHK(h, launch_sgbm_median(h->sg_pre, out, gc.n, width, height, h->stream));
+    HIPCHK(h, mark(4));
+    if (speckle) {
+      // the block matcher's filter, with cv::StereoSGBM's arguments: newVal = (minD - 1) * 16, maxDiff = 16 * speckleRange (the
+      // block matcher's own x16 reading bit does not apply here)
+      Geom sg;
+      memset(&sg, 0, sizeof(sg));
+      sg.W = width; sg.H = height; sg.n = gc.n; sg.filtered = inv; sg.reading = 0;
+      HIPCHK(h, launch_speckle(out, h->sg_spk_runs, h->sg_spk_nheads, h->sg_spk_seam, h->sg_spk_nseam, sg, p->speckle_window_size,
+                               max_diff, h->stream));
+    }
+    HIPCHK(h, mark(5));
+    if (prof) {
+      HIPCHK(h, lap(0, 1, 0)); HIPCHK(h, lap(1, 2, 1)); HIPCHK(h, lap(2, 3, 2)); HIPCHK(h, lap(3, 4, 3)); HIPCHK(h, lap(4, 5, 4));
+      HIPCHK(h, lap(0, 5, 5));
+    }
+  }
+  if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+
+int sbm_sgbm_compute(sbm_handle* h, const sbm_sgbm_params* p, const uint8_t* left, size_t left_stride, const uint8_t* right,
+                     size_t right_stride, int width, int height, int16_t* disp, size_t disp_stride) {
+  if (!h || !p || !left || !right || !disp) return SBM_ERR_NULL;
+  int st = sbm_sgbm_params_validate(p, width, height);
+  if (st != SBM_OK) return st;
+  if (left_stride < (size_t)width || right_stride < (size_t)width || disp_stride < (size_t)width * 2) return SBM_ERR_SIZE;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  st = ensure_staging(h, 1, width, height);
+  if (st != SBM_OK) return st;
+  HIPCHK(h, hipMemcpy2DAsync(h->st_l, width, left, left_stride, width, height, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpy2DAsync(h->st_r, width, right, right_stride, width, height, hipMemcpyHostToDevice, h->stream));
+  st = sbm_sgbm_compute_device(h, p, 1, h->st_l, h->st_r, width, height, h->st_d, 0);
+  if (st != SBM_OK) return st;
+  HIPCHK(h, hipMemcpy2DAsync(disp, disp_stride, h->st_d, (size_t)width * 2, (size_t)width * 2, height, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+
 int sbm_gftt_eig(sbm_handle* h, const uint8_t* img, size_t img_stride, int width, int height, uint16_t* eig, size_t eig_stride,
                  uint32_t* max_out) {
   if (!h || !img || !eig) return SBM_ERR_NULL;
@@ -840,6 +1059,13 @@ int sbm_get_profile(sbm_handle* h, const char* name, float* ms) {
   else if (!strcmp(name, "lrcheck")) *ms = h->ms_lr;
   else if (!strcmp(name, "speckle")) *ms = h->ms_speckle;
   else if (!strcmp(name, "total")) *ms = h->ms_total;
+  else if (!strncmp(name, "sgbm_", 5)) {
+    static const char* const kSg[6] = {"sgbm_cost", "sgbm_aggregate", "sgbm_select", "sgbm_median", "sgbm_speckle", "sgbm_total"};
+    int i = 0;
+    while (i < 6 && strcmp(name, kSg[i])) i++;
+    if (i == 6) return SBM_ERR_UNSUPPORTED;
+    *ms = h->sg_ms[i];
+  }
   else return SBM_ERR_UNSUPPORTED;
   return SBM_OK;
 }
@@ -852,6 +1078,25 @@ int sbm_last_kernel_name(sbm_handle* h, char* dst, size_t dst_bytes) {
 
 int sbm_debug_fetch(sbm_handle* h, int which, void* dst, size_t dst_bytes) {
   if (!h || !dst) return SBM_ERR_NULL;
+  if (which >= 4 && which <= 6) {   // the last semi-global matcher call
+    if (!h->sg_have_last) return SBM_ERR_UNSUPPORTED;
+    const SgbmGeom& g = h->sg_last;
+    DeviceScope dscope(h->device);
+    HIPCHK(h, dscope.enter());
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (!h->sg_last_one_chunk) return SBM_ERR_UNSUPPORTED;
+    if (which == 6) {
+      const size_t bytes = (size_t)g.n * g.W * g.H * sizeof(int16_t);
+      if (dst_bytes < bytes) return SBM_ERR_SIZE;
+      HIPCHK(h, hipMemcpy(dst, h->sg_pre, bytes, hipMemcpyDeviceToHost));
+      return SBM_OK;
+    }
+    if (g.W1 < 1) return SBM_ERR_UNSUPPORTED;
+    const size_t bytes = (size_t)g.n * g.H * g.W1 * g.D * sizeof(int16_t);
+    if (dst_bytes < bytes) return SBM_ERR_SIZE;
+    HIPCHK(h, hipMemcpy(dst, which == 4 ? h->sg_C : h->sg_S, bytes, hipMemcpyDeviceToHost));
+    return SBM_OK;
+  }
   if (!h->have_last) return SBM_ERR_UNSUPPORTED;
   const Geom& g = h->last;
   DeviceScope dscope(h->device);

@@ -141,4 +141,23 @@ hipError_t launch_reproject(const int16_t* disp, float* xyz, int n, int W, int H
 hipError_t launch_keypoints3d(const int16_t* disp, const float* kp, float* xyz, int W, int H, int nk,
                               const sbm_stereo_model& m, float min_depth, float max_depth, hipStream_t s);
 
+// Semi-global matcher (sbm_sgbm.hip). Naming follows cv::StereoSGBM (calib3d stereosgbm.cpp): computable columns
+// X = minX1 + x, x in [0, W1); buffer index d <-> disparity minD + d; P1, P2, d12 and uniq are the effective values.
+// C, S, hsum: n * H * W1 * D int16 ([pair][y][x][d]).
+constexpr int kReadSgbmNoMedian = 32;        // SBM_CV_READING: no medianBlur stage
+constexpr int kReadSgbmBottomClamped = 64;   // SBM_CV_READING: rows with y + SH2 >= H (y > 0) sum a clamped window
+constexpr int kSgbmNdMax = 512, kSgbmWMax = 8192;
+struct SgbmGeom {
+  int W, H, n;
+  int minD, D, minX1, maxX1, W1;
+  int SW2, P1, P2, ftzero, uniq, d12;
+  int fullDP;          // MODE_HH: 8 paths
+  int reading;
+};
+hipError_t launch_sgbm_cost(const uint8_t* left, const uint8_t* right, int16_t* hsum, int16_t* C, const SgbmGeom& g, hipStream_t s);
+hipError_t launch_sgbm_paths(const int16_t* C, int16_t* S, const SgbmGeom& g, hipStream_t s);
+hipError_t launch_sgbm_select(const int16_t* S, int16_t* pre, const SgbmGeom& g, hipStream_t s);
+hipError_t launch_sgbm_median(const int16_t* src, int16_t* dst, int n, int W, int H, hipStream_t s);
+hipError_t launch_sgbm_fill(int16_t* dst, size_t count, int v, hipStream_t s);
+
 }  // namespace sbm
