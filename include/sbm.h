@@ -371,6 +371,56 @@ int sbm_gftt_eig_device(sbm_handle* h, int n, const void* d_img, int width, int 
 int sbm_gftt_eig(sbm_handle* h, const uint8_t* img, size_t img_stride, int width, int height, uint16_t* eig, size_t eig_stride,
                  uint32_t* max_out);
 
+/* ---- GFTT keypoint selection: generateKeypoints2 (src/slam/src/core/GFTT.cpp:41-170) --------------------------------------
+ * The CPU half of the reference's KPTS_METHOD_FPGA_GFTT path (main.cpp:238-243), on the device, so that the keypoints of
+ * frames on the GPU go straight from sbm_gftt_eig_device to sbm_keypoints3d_device. Per map, exactly as the reference:
+ *   threshold  thr = (double)(max & 0xffff) * quality_level; the candidates are the pixels with (float)eig[y][x] >= thr,
+ *              1 <= y < height - 1, 1 <= x < width - 1 (max = 0: every interior pixel, zeros included);
+ *   order      value descending, ties by the higher raster index y * width + x first (greaterThanPtr on a dense map);
+ *   trim       min_distance >= 1: cells of cvRound(min_distance) (half to even) pixels; a candidate is rejected by an accepted
+ *              point of the 3x3 cells around its own one with dx^2 + dy^2 < min_distance^2 (points two cells away are not
+ *              looked at when the cell is smaller than min_distance, as in the reference); min_distance < 1: no trim;
+ *   stop       after max_features accepted points when max_features > 0.
+ * Output: points (x, y) as float, in acceptance order. The result with a cap is the prefix of the result without one.
+ * Limits: width and height 3..2048 (SBM_ERR_SIZE below 3, SBM_ERR_UNSUPPORTED above 2048), at most 65 535 maps per call,
+ * quality_level finite and >= 0, min_distance finite and in [0, 255] (SBM_ERR_UNSUPPORTED otherwise). block_size is carried
+ * for the C++ adaptor (cv::KeyPoint size) only.
+ * Kernels: one workgroup of 1024 threads per map; the accepted points live in a cell table of 16 B per
+ * cell, ceil(width / cell) * ceil(height / cell) cells. When that table fits in LDS next to the sort keys (at 640 x 480 every
+ * min_distance >= 5.5, i.e. cells of 6 and more) there is no device scratch; otherwise the tables live in device scratch held by
+ * the handle, worked through in chunks of maps whose tables stay within 2 GiB (64 MiB per 2048 x 2048 map at cell 1).
+ * sbm_get_profile: while profiling is enabled (any mode) these calls synchronise and record "gftt_select_eig" (the map of
+ * sbm_gftt_detect_device, else 0), "gftt_select_select" and "gftt_select_total" (ms of the last call). */
+typedef struct sbm_gftt_select_params {  /* generateKeypoints2's constants (GFTT.cpp:50-53) */
+  int32_t max_features;     /* nfeatures, default 1500; <= 0: no limit                      */
+  double quality_level;     /* qualityLevel, default 0.01                                   */
+  double min_distance;      /* minDistance, default 7.0                                     */
+  int32_t block_size;       /* blockSize, default 3: the size of the adaptor's cv::KeyPoint */
+} sbm_gftt_select_params;
+
+/* Fill *p with the reference's constants: 1500, 0.01, 7.0, 3. */
+void sbm_gftt_select_params_default(sbm_gftt_select_params* p);
+/* SBM_ERR_NULL, SBM_ERR_SIZE (width or height < 3), SBM_ERR_UNSUPPORTED (above 2048, or a parameter outside the limits above),
+ * else SBM_OK. */
+int sbm_gftt_select_params_validate(const sbm_gftt_select_params* p, int width, int height);
+/* n dense uint16 maps in DEVICE memory (d_eig: n * height * width), d_max: n uint32 as sbm_gftt_eig_device writes them (the low
+ * 16 bits are the reference's unsigned short) or NULL: each map's own maximum. cap = max_features > 0 ? max_features :
+ * (width - 2) * (height - 2); d_kpts: n * cap float pairs (x, y), map i's points from i * cap * 2 on -- a slice
+ * sbm_keypoints3d_device takes directly; entries past the count are left as they were; d_count: n int32. Asynchronous on the
+ * handle's stream unless sync != 0. */
+int sbm_gftt_select_device(sbm_handle* h, int n, const void* d_eig, const void* d_max, int width, int height,
+                           const sbm_gftt_select_params* p, void* d_kpts, void* d_count, int sync);
+/* Host form for ONE map, shaped like generateKeypoints2(eig, max, kpts2d): eig strided (eig_stride in bytes), max_eig the
+ * register value, kpts at least cap float pairs (capacity counts pairs; SBM_ERR_SIZE below cap). *count receives the number of
+ * points. Synchronous. */
+int sbm_gftt_select(sbm_handle* h, const uint16_t* eig, size_t eig_stride, int width, int height, uint16_t max_eig,
+                    const sbm_gftt_select_params* p, float* kpts, size_t capacity, int* count);
+/* The whole KPTS_METHOD_FPGA_GFTT front end on n dense u8 frames: sbm_gftt_eig_device into d_eig / d_max (both required), then
+ * sbm_gftt_select_device on them, in one call on the handle's stream. The map's limits apply: width 3..1023, height 5..511
+ * (SBM_ERR_SIZE outside). */
+int sbm_gftt_detect_device(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_select_params* p,
+                           void* d_eig, void* d_max, void* d_kpts, void* d_count, int sync);
+
 /* ---- semi-global matcher: cv::StereoSGBM (the reference's DEPTH_METHOD_CV_SGBM, main.cpp:218-234) -------------------------
  * Restatement of cv::StereoSGBM::compute() for 8-bit single-channel pairs in MODE_HH (two passes, 8 paths: the reference's
  * mode, main.cpp:219-230) and MODE_SGBM (OpenCV's default: one pass, 5 paths). Output contract as for the block matcher:

@@ -1,0 +1,223 @@
+"""GPU keypoint selection (u96-slam_amd/csrc/sbm_gftt_select.hip) bit for bit against the CPU restatement of generateKeypoints2
+(oracle_gftt/): counts and every (x, y) in order, through the device, detect, host and asynchronous entry points."""
+import pathlib
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT / "oracle_gftt"))
+sys.path.insert(0, str(ROOT / "tests"))
+import gftt_select_ref as ref  # noqa: E402
+from gftt_select_cases import PARAM_EDGES, crafted_maps, random_case  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def bm(pkg):
+    return pkg.StereoBM.create(64, 21)
+
+
+def dev(a):
+    import torch
+
+    a = np.ascontiguousarray(a)
+    if a.dtype == np.uint16:
+        return torch.from_numpy(a.view(np.int16)).to("cuda:0")
+    return torch.from_numpy(a).to("cuda:0")
+
+
+def check(kpts, count, i, want, what=""):
+    k = int(count[i])
+    got = kpts[i, :k]
+    assert k == len(want), (what, i, k, len(want))
+    assert np.array_equal(got, want), (what, i, int((got != want).any(axis=1).sum()))
+
+
+def run_select(bm, maps, mxs, mf, q, md, with_max=True):
+    import torch
+
+    mx = torch.tensor(mxs, dtype=torch.int64).to(torch.int32).to("cuda:0") if with_max else None
+    kp, cn = bm.gftt_select(dev(np.stack(maps)), mx, max_features=mf, quality_level=q, min_distance=md)
+    return kp.cpu().numpy(), cn.cpu().numpy()
+
+
+def test_reference_parameters_on_the_golden_frames(bm, oracle, golden):
+    imgs = np.stack([golden["rect_l"], golden["rect_r"]])
+    refs = [oracle.gftt_eig(im) for im in imgs]
+    kp, cn = run_select(bm, [e for e, _ in refs], [m for _, m in refs], 1500, 0.01, 7.0)
+    for i, (e, m) in enumerate(refs):
+        check(kp, cn, i, ref.select(e, m), "select")
+    kp2, cn2 = bm.gftt_detect(dev(imgs))
+    kp2, cn2 = kp2.cpu().numpy(), cn2.cpu().numpy()
+    for i, (e, m) in enumerate(refs):
+        check(kp2, cn2, i, ref.select(e, m), "detect")
+        assert cn2[i] > 100
+
+
+@pytest.mark.parametrize("mf,q,md", PARAM_EDGES)
+def test_crafted_maps_and_edges_in_one_batch(bm, mf, q, md):
+    maps = crafted_maps()
+    names = sorted(maps)
+    kp, cn = run_select(bm, [maps[k][0] for k in names], [maps[k][1] for k in names], mf, q, md)
+    for i, k in enumerate(names):
+        check(kp, cn, i, ref.select(maps[k][0], maps[k][1], mf, q, md), k)
+
+
+def test_seeded_fuzz_240_cases(bm):
+    rng = np.random.default_rng(77)
+    for c in range(240):
+        m, mx, mf, q, md = random_case(rng)
+        kp, cn = run_select(bm, [m], [mx], mf, q, md)
+        check(kp, cn, 0, ref.select(m, mx, mf, q, md), f"case {c}: {m.shape} max {mx} {mf} {q} {md}")
+
+
+@pytest.mark.parametrize("W,H", [(3, 3), (3, 5), (5, 3), (7, 9), (13, 11), (65, 17), (127, 33), (641, 479), (999, 7)])
+@pytest.mark.parametrize("md", [0.0, 1.0, 2.5, 7.0, 7.4, 30.0])
+def test_sizes(bm, W, H, md):
+    rng = np.random.default_rng(W * 1000 + H)
+    m = rng.integers(0, 5000, (H, W)).astype(np.uint16)
+    kp, cn = run_select(bm, [m], [int(m.max())], -1, 0.02, md)
+    check(kp, cn, 0, ref.select(m, int(m.max()), -1, 0.02, md), (W, H, md))
+
+
+def test_2048_and_2049(bm, pkg):
+    import torch
+
+    rng = np.random.default_rng(2048)
+    m = rng.integers(0, 65536, (2048, 2048)).astype(np.uint16)
+    for md in (7.0, 1.5, 0.0):
+        kp, cn = run_select(bm, [m], [65535], 1500, 0.5, md)
+        check(kp, cn, 0, ref.select(m, 65535, 1500, 0.5, md), md)
+    for shape in ((10, 2049), (2049, 10)):
+        with pytest.raises(pkg.StereoBMError) as e:
+            bm.gftt_select(torch.zeros(shape, dtype=torch.int16, device="cuda:0"), None)
+        assert e.value.code == -23
+
+
+def test_plateaus_larger_than_a_window(bm):
+    H, W = 480, 640
+    rng = np.random.default_rng(4)
+    zeros = np.zeros((H, W), np.uint16)
+    plateau = rng.integers(0, 9000, (H, W)).astype(np.uint16)
+    plateau[rng.random((H, W)) < 0.3] = 5000            # ~92 000 ties in the middle of the order
+    plateau[100:400, 100:500] = 7000                     # and 120 000 above them
+    many = rng.integers(0, 65536, (H, W)).astype(np.uint16)   # many windows of distinct values
+    for mf, q, md in ((1500, 0.01, 7.0), (-1, 0.0, 7.0), (-1, 0.0, 2.5), (20000, 0.0, 0.0), (-1, 0.3, 1.0)):
+        kp, cn = run_select(bm, [zeros, plateau, many], [0, 9000, 65535], mf, q, md)
+        check(kp, cn, 0, ref.select(zeros, 0, mf, q, md), ("zeros", mf, q, md))
+        check(kp, cn, 1, ref.select(plateau, 9000, mf, q, md), ("plateau", mf, q, md))
+        check(kp, cn, 2, ref.select(many, 65535, mf, q, md), ("many", mf, q, md))
+
+
+@pytest.mark.parametrize("md", [0.0, 1.0, 3.5, 7.0, 7.4])
+def test_prefix_property(bm, md):
+    rng = np.random.default_rng(12)
+    m = rng.integers(0, 3000, (200, 300)).astype(np.uint16)
+    kf, cf = run_select(bm, [m], [3000], -1, 0.05, md)
+    full = kf[0, :cf[0]]
+    assert np.array_equal(full, ref.select(m, 3000, -1, 0.05, md))
+    for cap in (1, 63, 64, 65, 1000, int(cf[0])):
+        kc, cc = run_select(bm, [m], [3000], cap, 0.05, md)
+        assert np.array_equal(kc[0, :cc[0]], full[:cap]), cap
+
+
+def test_max_null_uses_the_map_maximum(bm):
+    rng = np.random.default_rng(21)
+    maps = [rng.integers(0, hi, (61, 77)).astype(np.uint16) for hi in (2, 700, 65536)]
+    kp, cn = run_select(bm, maps, [0, 0, 0], 1500, 0.01, 7.0, with_max=False)
+    for i, m in enumerate(maps):
+        check(kp, cn, i, ref.select(m, int(m.max()), 1500, 0.01, 7.0), i)
+
+
+def test_batch_across_table_chunks(bm):
+    # cell 1 on 2048 x 2048 maps: 64 MiB of cell table per map, so 33 maps run as two chunks of the global-table kernel
+    import torch
+
+    n, H, W = 33, 2048, 2048
+    g = torch.Generator(device="cuda:0").manual_seed(5)
+    eig = torch.randint(0, 65536, (n, H, W), generator=g, device="cuda:0", dtype=torch.int32)
+    mx = torch.full((n,), 65535, dtype=torch.int32, device="cuda:0")
+    kp, cn = bm.gftt_select(eig, mx, max_features=300, quality_level=0.99, min_distance=1.2)
+    kp, cn = kp.cpu().numpy(), cn.cpu().numpy()
+    for i in (0, 1, 31, 32):
+        m = eig[i].cpu().numpy().astype(np.uint16)
+        check(kp, cn, i, ref.select(m, 65535, 300, 0.99, 1.2), i)
+
+
+def test_host_strided_and_async(bm):
+    import torch
+
+    rng = np.random.default_rng(31)
+    big = rng.integers(0, 65536, (97, 160)).astype(np.uint16)
+    view = big[:, 5:140]                                    # a strided map (row stride 320 B, 135 columns)
+    for md in (0.0, 2.5, 7.0):
+        got = bm.gftt_select_host(view, 40000, max_features=-1, quality_level=0.1, min_distance=md)
+        assert np.array_equal(got, ref.select(view, 40000, -1, 0.1, md)), md
+    maps = [rng.integers(0, 65536, (97, 135)).astype(np.uint16) for _ in range(3)]
+    kp, cn = bm.gftt_select(dev(np.stack(maps)), torch.tensor([65535] * 3, dtype=torch.int32, device="cuda:0"), sync=False)
+    bm.synchronize()
+    kp, cn = kp.cpu().numpy(), cn.cpu().numpy()
+    for i, m in enumerate(maps):
+        check(kp, cn, i, ref.select(m, 65535), i)
+
+
+def test_detect_then_keypoints3d(bm, pkg, oracle, golden):
+    import torch
+
+    L, R = golden["rect_l"], golden["rect_r"]
+    disp = bm.compute(dev(L), dev(R))
+    kp, cn = bm.gftt_detect(dev(L))
+    k = int(cn[0])
+    e, m = oracle.gftt_eig(L)
+    want = ref.select(e, m)
+    assert np.array_equal(kp[0, :k].cpu().numpy(), want)
+    import ctypes
+
+    mo = oracle.make_model()
+    mg = pkg.StereoModel()
+    ctypes.memmove(ctypes.byref(mg), ctypes.byref(mo), ctypes.sizeof(mg))
+    xyz = bm.keypoints3d(disp, kp[0, :k], mg, 0.0, 0.0).cpu().numpy()
+    exp = oracle.keypoints3d(disp.cpu().numpy(), want, mo, 0.0, 0.0)
+    assert np.isfinite(exp).all(axis=1).sum() > 20
+    assert np.array_equal(np.isnan(xyz), np.isnan(exp))
+    assert np.array_equal(xyz[~np.isnan(xyz)], exp[~np.isnan(exp)])
+
+
+def test_profile_records_stages(bm, golden):
+    bm.set_profiling(1)
+    try:
+        bm.gftt_detect(dev(np.stack([golden["rect_l"]] * 4)))
+        prof = bm.gftt_profile()
+    finally:
+        bm.set_profiling(0)
+    assert prof["gftt_select_eig"] > 0 and prof["gftt_select_select"] > 0
+    assert prof["gftt_select_total"] >= prof["gftt_select_select"]
+
+
+@pytest.mark.parametrize("mock", [False, True], ids=["plain", "mock_opencv"])
+def test_cpp_callsite_through_the_adaptor(tmp_path, oracle, golden, mock):
+    e, m = oracle.gftt_eig(golden["rect_l"])
+    H, W = e.shape
+    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv_features")] if mock else []
+    lib = ROOT / "u96-slam_amd" / "lib"
+    exe = tmp_path / "cs"
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-I", str(ROOT / "include"), *extra,
+                        str(ROOT / "tests" / "cpp" / "gftt_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip", f"-Wl,-rpath,{lib}",
+                        "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    (tmp_path / "eig.raw").write_bytes(np.ascontiguousarray(e).tobytes())
+    r = subprocess.run([str(exe), str(tmp_path / "eig.raw"), str(W), str(H), str(m), str(tmp_path / "k.raw")],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    out = np.fromfile(tmp_path / "k.raw", np.float32)
+    want = ref.select(e, m)
+    k = len(want)
+    assert np.array_equal(out[:2 * k].reshape(-1, 2), want)
+    if mock:
+        assert np.array_equal(out[2 * k:], np.full(k, 3.0, np.float32))   # cv::KeyPoint(pt, blockSize)
+    else:
+        assert len(out) == 2 * k

@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <chrono>
 #include <mutex>
 #include <new>
@@ -99,6 +100,14 @@ struct sbm_handle {
   bool sg_have_last, sg_last_one_chunk;
   hipEvent_t sg_ev[6];
   float sg_ms[6];   // cost, aggregate, select, median, speckle, total
+  // keypoint selection (allocated on first use): the cell tables of the global-table kernel for one chunk of images; the
+  // points and counts of the host-memory entry point
+  unsigned* gs_tab;
+  size_t gs_tab_bytes;
+  void* gs_out;
+  size_t gs_out_bytes;
+  hipEvent_t gs_ev[3];
+  float gs_ms[3];   // eig, select, total
 };
 
 // Entry points select the handle's device and put the caller's current device back on return.
@@ -232,6 +241,11 @@ static void free_sgbm(sbm_handle* h) {
   h->sg_have_last = false;
 }
 
+static void free_gftt_sel(sbm_handle* h) {
+  hipFree(h->gs_tab); hipFree(h->gs_out);
+  h->gs_tab = nullptr; h->gs_out = nullptr; h->gs_tab_bytes = h->gs_out_bytes = 0;
+}
+
 static void free_fpga(sbm_handle* h) {
   hipFree(h->fp_xs_l); hipFree(h->fp_xs_r); hipFree(h->fp_rec); hipFree(h->fp_flag);
   h->fp_xs_l = h->fp_xs_r = nullptr; h->fp_rec = nullptr; h->fp_flag = nullptr;
@@ -308,6 +322,7 @@ int sbm_create(sbm_handle** out, const sbm_params* p, int device) {
         h->calls = 0;
         h->ms_prefilter = h->ms_sad = h->ms_border = h->ms_lr = h->ms_speckle = h->ms_total = 0.f;
         for (float& t : h->sg_ms) t = 0.f;
+        for (float& t : h->gs_ms) t = 0.f;
         *out = h;
         return SBM_OK;
       }
@@ -360,6 +375,7 @@ void sbm_destroy(sbm_handle* h) {
         free_feed(h);
         free_fpga(h);
         free_sgbm(h);
+        free_gftt_sel(h);
       }
       g_pool[g_pool_n++] = h;
       return;
@@ -379,8 +395,11 @@ static void destroy_now(sbm_handle* h) {
   free_feed(h);
   free_fpga(h);
   free_sgbm(h);
+  free_gftt_sel(h);
   for (int i = 0; i < 6; i++)
     if (h->sg_ev[i]) hipEventDestroy(h->sg_ev[i]);
+  for (int i = 0; i < 3; i++)
+    if (h->gs_ev[i]) hipEventDestroy(h->gs_ev[i]);
   for (int r = 0; r < sbm_handle::kRing; r++)
     for (int i = 0; i < sbm_handle::kMarks; i++)
       if (h->ev[r][i]) hipEventDestroy(h->ev[r][i]);
@@ -434,6 +453,7 @@ int sbm_set_profiling(sbm_handle* h, int enabled) {
   h->instr = false;
   h->ms_prefilter = h->ms_sad = h->ms_border = h->ms_lr = h->ms_speckle = h->ms_total = 0.f;
   for (float& t : h->sg_ms) t = 0.f;
+  for (float& t : h->gs_ms) t = 0.f;
   return SBM_OK;
 }
 
@@ -1001,6 +1021,135 @@ int sbm_gftt_eig_device(sbm_handle* h, int n, const void* d_img, int width, int 
   return SBM_OK;
 }
 
+// ---- keypoint selection of generateKeypoints2 (GFTT.cpp:41-170) ---------------------------------------------------------------
+void sbm_gftt_select_params_default(sbm_gftt_select_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->max_features = 1500;
+  p->quality_level = 0.01;
+  p->min_distance = 7.0;
+  p->block_size = 3;
+}
+
+int sbm_gftt_select_params_validate(const sbm_gftt_select_params* p, int width, int height) {
+  if (!p) return SBM_ERR_NULL;
+  if (width < 3 || height < 3) return SBM_ERR_SIZE;
+  if (width > kGftSelWMax || height > kGftSelWMax) return SBM_ERR_UNSUPPORTED;
+  if (!std::isfinite(p->quality_level) || p->quality_level < 0) return SBM_ERR_UNSUPPORTED;
+  if (!std::isfinite(p->min_distance) || p->min_distance < 0 || p->min_distance > 255) return SBM_ERR_UNSUPPORTED;
+  return SBM_OK;
+}
+
+// Enqueues the selection of n dense maps; with tm (profiling) the eig event tm[0] is already recorded by the caller.
+static int gftt_select_enqueue(sbm_handle* h, int n, const void* d_eig, const void* d_max, int width, int height,
+                               const sbm_gftt_select_params* p, void* d_kpts, void* d_count) {
+  const GftSelPlan pl = gftt_select_plan(width, height, p->max_features, p->quality_level, p->min_distance);
+  // the global-table kernel works through the images in chunks whose tables stay within 2 GiB
+  int chunk = n;
+  if (pl.global_table) {
+    chunk = (int)std::min<size_t>(n, std::max<size_t>(1, ((size_t)2 << 30) / pl.table_bytes_per_image));
+    const size_t bytes = pl.table_bytes_per_image * chunk;
+    if (bytes > h->gs_tab_bytes) {
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      hipFree(h->gs_tab);
+      h->gs_tab = nullptr; h->gs_tab_bytes = 0;
+      HIPCHK(h, hipMalloc((void**)&h->gs_tab, bytes));
+      h->gs_tab_bytes = bytes;
+    }
+  }
+  for (int c0 = 0; c0 < n; c0 += chunk)
+    HIPCHK(h, launch_gftt_select((const uint16_t*)d_eig, (const unsigned*)d_max, (float*)d_kpts, (int*)d_count, h->gs_tab, pl, c0,
+                                 std::min(chunk, n - c0), h->stream));
+  return SBM_OK;
+}
+
+static int gftt_select_run(sbm_handle* h, int n, const void* d_img, const void* d_eig, const void* d_max, int width, int height,
+                           const sbm_gftt_select_params* p, void* d_kpts, void* d_count, int sync) {
+  const bool prof = h->profiling != 0;
+  if (prof) {
+    for (int i = 0; i < 3; i++)
+      if (!h->gs_ev[i]) HIPCHK(h, hipEventCreate(&h->gs_ev[i]));
+    HIPCHK(h, hipEventRecord(h->gs_ev[0], h->stream));
+  }
+  if (d_img)
+    HIPCHK(h, launch_gftt_eig((const uint8_t*)d_img, (uint16_t*)d_eig, (unsigned*)d_max, n, width, height, h->stream));
+  if (prof) HIPCHK(h, hipEventRecord(h->gs_ev[1], h->stream));
+  const int st = gftt_select_enqueue(h, n, d_eig, d_max, width, height, p, d_kpts, d_count);
+  if (st != SBM_OK) return st;
+  if (prof) {
+    HIPCHK(h, hipEventRecord(h->gs_ev[2], h->stream));
+    HIPCHK(h, hipEventSynchronize(h->gs_ev[2]));
+    HIPCHK(h, hipEventElapsedTime(&h->gs_ms[0], h->gs_ev[0], h->gs_ev[1]));
+    HIPCHK(h, hipEventElapsedTime(&h->gs_ms[1], h->gs_ev[1], h->gs_ev[2]));
+    HIPCHK(h, hipEventElapsedTime(&h->gs_ms[2], h->gs_ev[0], h->gs_ev[2]));
+  }
+  if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+
+int sbm_gftt_select_device(sbm_handle* h, int n, const void* d_eig, const void* d_max, int width, int height,
+                           const sbm_gftt_select_params* p, void* d_kpts, void* d_count, int sync) {
+  if (!h || !p || !d_eig || !d_kpts || !d_count) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  const int st = sbm_gftt_select_params_validate(p, width, height);
+  if (st != SBM_OK) return st;
+  if (n > 65535) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  return gftt_select_run(h, n, nullptr, d_eig, d_max, width, height, p, d_kpts, d_count, sync);
+}
+
+int sbm_gftt_detect_device(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_select_params* p,
+                           void* d_eig, void* d_max, void* d_kpts, void* d_count, int sync) {
+  if (!h || !p || !d_img || !d_eig || !d_max || !d_kpts || !d_count) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  if (width < 3 || height < 5 || width > 1023 || height > 511) return SBM_ERR_SIZE;   // the eigenvalue map's limits
+  const int st = sbm_gftt_select_params_validate(p, width, height);
+  if (st != SBM_OK) return st;
+  if (n > 65535) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  return gftt_select_run(h, n, d_img, d_eig, d_max, width, height, p, d_kpts, d_count, sync);
+}
+
+int sbm_gftt_select(sbm_handle* h, const uint16_t* eig, size_t eig_stride, int width, int height, uint16_t max_eig,
+                    const sbm_gftt_select_params* p, float* kpts, size_t capacity, int* count) {
+  if (!h || !p || !eig || !kpts || !count) return SBM_ERR_NULL;
+  int st = sbm_gftt_select_params_validate(p, width, height);
+  if (st != SBM_OK) return st;
+  const size_t cap = p->max_features > 0 ? (size_t)p->max_features : (size_t)(width - 2) * (height - 2);
+  if (eig_stride < (size_t)width * 2 || capacity < cap) return SBM_ERR_SIZE;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  st = ensure_staging(h, 1, width, height);
+  if (st != SBM_OK) return st;
+  const size_t out_bytes = cap * 2 * sizeof(float) + 16;   // points, then the count
+  if (out_bytes > h->gs_out_bytes) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hipFree(h->gs_out);
+    h->gs_out = nullptr; h->gs_out_bytes = 0;
+    HIPCHK(h, hipMalloc(&h->gs_out, out_bytes));
+    h->gs_out_bytes = out_bytes;
+  }
+  // st_d: the map, st_r: the Max word
+  const uint32_t mx = max_eig;
+  HIPCHK(h, hipMemcpy2DAsync(h->st_d, (size_t)width * 2, eig, eig_stride, (size_t)width * 2, height, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->st_r, &mx, sizeof(mx), hipMemcpyHostToDevice, h->stream));
+  float* d_k = (float*)h->gs_out;
+  int* d_n = (int*)((char*)h->gs_out + cap * 2 * sizeof(float));
+  st = gftt_select_run(h, 1, nullptr, h->st_d, h->st_r, width, height, p, d_k, d_n, 0);
+  if (st != SBM_OK) {
+    hipStreamSynchronize(h->stream);   // `mx` is read by an enqueued copy
+    return st;
+  }
+  int k = 0;
+  HIPCHK(h, hipMemcpyAsync(&k, d_n, sizeof(k), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (k > 0) HIPCHK(h, hipMemcpy(kpts, d_k, (size_t)k * 2 * sizeof(float), hipMemcpyDeviceToHost));
+  *count = k;
+  return SBM_OK;
+}
+
 int sbm_disparity_to_float_device(sbm_handle* h, int n, const void* d_disp, int width, int height, void* d_out, int sync) {
   if (!h || !d_disp || !d_out) return SBM_ERR_NULL;
   if (n <= 0) return SBM_ERR_BATCH;
@@ -1065,6 +1214,13 @@ int sbm_get_profile(sbm_handle* h, const char* name, float* ms) {
     while (i < 6 && strcmp(name, kSg[i])) i++;
     if (i == 6) return SBM_ERR_UNSUPPORTED;
     *ms = h->sg_ms[i];
+  }
+  else if (!strncmp(name, "gftt_select_", 12)) {
+    static const char* const kGs[3] = {"gftt_select_eig", "gftt_select_select", "gftt_select_total"};
+    int i = 0;
+    while (i < 3 && strcmp(name, kGs[i])) i++;
+    if (i == 3) return SBM_ERR_UNSUPPORTED;
+    *ms = h->gs_ms[i];
   }
   else return SBM_ERR_UNSUPPORTED;
   return SBM_OK;

@@ -133,6 +133,31 @@ hipError_t launch_fpga_bm(const uint8_t* xl, const uint8_t* xr, void* rec, int* 
 // GFTT minimum-eigenvalue map of the PL (sbm_gftt.hip): eig = n*H*W uint16, maxv = n uint32 (`Max` register per image).
 hipError_t launch_gftt_eig(const uint8_t* img, uint16_t* eig, unsigned* maxv, int n, int W, int H, hipStream_t s);
 
+// Keypoint selection of generateKeypoints2 on those maps (sbm_gftt_select.hip): one workgroup per image. The cell table of the
+// minimum-distance trim (16 B per cell, ceil(W/cell) * ceil(H/cell) cells) sits in LDS next to the sort keys when it fits
+// (global_table = false), else in device scratch of table_bytes_per_image per image, zeroed by the launch.
+constexpr size_t kGftSelLds = 160 * 1024;     // LDS of one workgroup
+constexpr int kGftSelKeysMax = 8192;          // keys sorted per value window (64 KiB)
+constexpr int kGftSelWMax = 2048;             // width and height limit: (x, y) pack into 16 bits each, indices into 22 bits
+struct GftSelGeom {
+  int W, H, img0;
+  int cap;                  // points per image slot: max_features > 0 ? max_features : (W - 2) * (H - 2)
+  int trim;                 // min_distance >= 1
+  int cell, gw, gh, lim;    // cvRound(min_distance), grid size, ceil(min_distance^2)
+  int nkeys;                // key capacity of a value window (a power of two)
+  double q;                 // quality_level
+  unsigned long long magic; // floor(2^40 / W) + 1: y = (p * magic) >> 40
+};
+struct GftSelPlan {
+  GftSelGeom g;
+  bool global_table;
+  size_t lds_bytes, table_bytes_per_image;
+};
+GftSelPlan gftt_select_plan(int W, int H, int max_features, double quality, double min_distance);
+// eig: dense uint16 maps, maxv: their Max words (null: each map's maximum); images [img0, img0 + n) of the batch
+hipError_t launch_gftt_select(const uint16_t* eig, const unsigned* maxv, float* kpts, int* count, unsigned* gtab, const GftSelPlan& pl,
+                              int img0, int n, hipStream_t s);
+
 // Consumers of the map (sbm_consume.hip): decimation, reprojection, keypoint depth.
 hipError_t launch_disp_to_float(const int16_t* disp, float* out, size_t count, hipStream_t s);
 hipError_t launch_decimate(const int16_t* disp, int16_t* out, int n, int W, int H, int scale, hipStream_t s);

@@ -1,0 +1,374 @@
+// sbm_gftt_select.hip -- keypoint selection of the reference's FPGA feature path, generateKeypoints2()
+// (src/slam/src/core/GFTT.cpp:41-170), on gfx950: threshold, order (value descending, ties by the higher raster index first),
+// greedy minimum-distance trim on a grid of cvRound(minDistance) cells, stop at nfeatures.
+//
+// One workgroup of 1024 threads per image works through the candidates in value windows, from the top:
+//   1. window: a 256-bin histogram of the high byte of the values still to be taken, then one of the low byte inside the bin
+//      where the running count from the top reaches the key capacity B, give the lowest value `lo` of the window: fewer than B
+//      candidates lie in (lo, hi);
+//   2. those are gathered into LDS as 64-bit keys (value << 32 | index) and sorted, descending, by a bitonic network;
+//   3. the candidates equal to `lo` either fit behind them (same sort) or, when `lo` is a large plateau, are streamed in
+//      descending raster order, 1024 pixels at a time, by an ordered compaction: no sort is needed inside one value;
+//   4. wavefront 0 trims each ordered run, 64 candidates per step (gftt_trim), until nfeatures are accepted.
+// Only the prefix that is consumed gets ordered; a plateau (an all-zero map with max = 0) costs one pass per 1024 pixels it
+// scans, never a sort.
+//
+// The accepted points live in a cell table of 4 words per cell: a count and up to three packed points (x | y << 16). Points of
+// one cell are at least minDistance >= cell - 0.5 apart inside a square of side cell - 1, so a cell never holds four. The table
+// sits in LDS when it fits next to the keys (gftt_select_kernel<false>), else in device scratch (<true>; small cells on large
+// images). Both are exact: the candidate test, the in-batch conflicts and the acceptance order are the same code.
+#include <math.h>
+#include <string.h>
+
+#include "sbm_common.h"
+
+namespace sbm {
+
+constexpr int GS_THREADS = 1024, GS_WAVES = GS_THREADS / 64;
+constexpr int GS_FIXED_LDS = 1280;   // hist[256], wave sums[16], scalars[16] (words), rounded to 16 B
+
+struct GsShared {
+  unsigned hist[256];
+  int wsum[GS_WAVES];
+  int acc, hi, lo, inc, cnt_gt, cnt_eq, nk, mx, cut_bin, cut_above, tmin, pad_[5];
+};
+static_assert(sizeof(GsShared) <= GS_FIXED_LDS, "fixed LDS");
+
+__device__ __forceinline__ void gs_xy(unsigned p, const GftSelGeom& g, int& x, int& y) {
+  y = (int)(((unsigned long long)p * g.magic) >> 40);   // exact for p < 2^22, W <= 2048
+  x = (int)p - y * g.W;
+}
+
+// Wave 0: the largest bin b with sum(hist[b..255]) >= need, and sum(hist[b+1..255]); b = -1 when the total is below need.
+__device__ void gs_cut(GsShared* sh, unsigned need) {
+  const int lane = threadIdx.x & 63;
+  const unsigned h0 = sh->hist[4 * lane], h1 = sh->hist[4 * lane + 1], h2 = sh->hist[4 * lane + 2], h3 = sh->hist[4 * lane + 3];
+  const unsigned s = h0 + h1 + h2 + h3;
+  unsigned suf = s;   // inclusive suffix sum over lanes >= lane
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned t = __shfl_down(suf, o, 64);
+    if (lane + o < 64) suf += t;
+  }
+  const unsigned long long m = __ballot(suf >= need);
+  if (m == 0) {
+    if (lane == 0) { sh->cut_bin = -1; sh->cut_above = 0; }
+    return;
+  }
+  const int L = 63 - __builtin_clzll(m);
+  if (lane == L) {
+    unsigned above = suf - s;   // lanes > L
+    int b = 4 * L + 3;
+    const unsigned hv[4] = {h0, h1, h2, h3};
+    for (int k = 3; k >= 0; k--) {
+      b = 4 * L + k;
+      if (above + hv[k] >= need) break;
+      above += hv[k];
+    }
+    sh->cut_bin = b;
+    sh->cut_above = (int)above;
+  }
+}
+
+// Wave 0: trim the ordered keys [0, nk) against the table, 64 per step, and append the accepted points to `out`.
+template <bool GT>
+__device__ void gftt_trim(const unsigned long long* keys, int nk, GsShared* sh, unsigned* tab, float* out, const GftSelGeom& g) {
+  const int lane = threadIdx.x & 63;
+  int acc = sh->acc;
+  for (int b0 = 0; b0 < nk && acc < g.cap; b0 += 64) {
+    const int i = b0 + lane;
+    const bool live = i < nk;
+    const unsigned idx = live ? (unsigned)keys[i] : 0u;
+    int x = 0, y = 0;
+    gs_xy(idx, g, x, y);
+    bool good = live;
+    unsigned long long conf = 0;   // earlier lanes of this batch within minDistance in the 3x3 cells
+    int cx = 0, cy = 0;
+    if (g.trim) {
+      cx = x / g.cell; cy = y / g.cell;
+      if (live) {
+        const int x1 = max(cx - 1, 0), x2 = min(cx + 1, g.gw - 1), y1 = max(cy - 1, 0), y2 = min(cy + 1, g.gh - 1);
+        for (int yy = y1; yy <= y2 && good; yy++)
+          for (int xx = x1; xx <= x2 && good; xx++) {
+            const unsigned* c = tab + 4 * ((size_t)yy * g.gw + xx);
+            unsigned w[4];
+            if constexpr (GT) {
+              for (int k = 0; k < 4; k++) w[k] = __hip_atomic_load(c + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else {
+              const uint4 v = *reinterpret_cast<const uint4*>(c);
+              w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+            }
+            const int nc = min((int)w[0], 3);
+            for (int s = 0; s < nc; s++) {
+              const int dx = x - (int)(w[1 + s] & 0xffffu), dy = y - (int)(w[1 + s] >> 16);
+              if (dx * dx + dy * dy < g.lim) good = false;
+            }
+          }
+      }
+      const int last = min(nk - b0, 64);
+      for (int j = 0; j < last - 1; j++) {
+        const int xj = __shfl(x, j, 64), yj = __shfl(y, j, 64), cxj = __shfl(cx, j, 64), cyj = __shfl(cy, j, 64);
+        const int dx = x - xj, dy = y - yj;
+        if (j < lane && abs(cx - cxj) <= 1 && abs(cy - cyj) <= 1 && dx * dx + dy * dy < g.lim) conf |= 1ull << j;
+      }
+    }
+    const unsigned long long G = __ballot(good);
+    unsigned long long A = G;
+    if (g.trim && __ballot(good && (conf & G) != 0)) {   // some good lane meets an earlier good one: resolve in order
+      A = 0;
+      unsigned long long rest = G;
+      while (rest) {
+        const int j = __builtin_ctzll(rest);
+        rest &= rest - 1;
+        const unsigned long long cj = ((unsigned long long)(unsigned)__shfl((int)(conf >> 32), j, 64) << 32) |
+                                      (unsigned)__shfl((int)(unsigned)conf, j, 64);
+        if (!(cj & A)) A |= 1ull << j;
+      }
+    }
+    int room = g.cap - acc, na = __popcll(A);
+    while (na > room) { A &= ~(1ull << (63 - __builtin_clzll(A))); na--; }   // acceptance is in order: keep the first `room`
+    if ((A >> lane) & 1ull) {
+      const int r = acc + __popcll(A & ((1ull << lane) - 1ull));
+      out[2 * (size_t)r] = (float)x;
+      out[2 * (size_t)r + 1] = (float)y;
+      if (g.trim) {
+        unsigned* c = tab + 4 * ((size_t)cy * g.gw + cx);
+        const unsigned slot = atomicAdd(c, 1u);
+        if (slot < 3) {
+          if constexpr (GT) __hip_atomic_store(c + 1 + slot, (unsigned)x | ((unsigned)y << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          else c[1 + slot] = (unsigned)x | ((unsigned)y << 16);
+        }
+      }
+    }
+    if constexpr (GT) __threadfence();
+    acc += na;
+  }
+  if (lane == 0) sh->acc = acc;
+}
+
+template <bool GT>
+__global__ void __launch_bounds__(GS_THREADS) gftt_select_kernel(const uint16_t* __restrict__ eig, const unsigned* __restrict__ maxv,
+                                                                 float* __restrict__ kpts, int* __restrict__ count,
+                                                                 unsigned* __restrict__ gtab, GftSelGeom g) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char gs_lds[];
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(gs_lds);
+  GsShared* sh = reinterpret_cast<GsShared*>(gs_lds + (size_t)g.nkeys * 8);
+  unsigned* tab = GT ? gtab + (size_t)blockIdx.x * 4 * g.gw * g.gh
+                     : reinterpret_cast<unsigned*>(gs_lds + (size_t)g.nkeys * 8 + GS_FIXED_LDS);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t img = (size_t)g.img0 + blockIdx.x;
+  const uint16_t* map = eig + img * g.W * g.H;
+  float* out = kpts + img * (size_t)g.cap * 2;
+  const int npix = g.W * g.H;
+  const int p0 = g.W + 1, p1 = (g.H - 1) * g.W - 1;   // rows 1..H-2 (columns 0 and W-1 are skipped by the x test)
+
+  if (tid == 0) { sh->acc = 0; sh->hi = 65536; sh->mx = 0; }
+  if (!GT && g.trim)
+    for (int c = tid; c < g.gw * g.gh; c += GS_THREADS) tab[4 * c] = 0u;
+  __syncthreads();
+  // the Max register: the caller's low 16 bits, or the map's maximum
+  if (maxv) {
+    if (tid == 0) sh->mx = (int)(maxv[img] & 0xffffu);
+  } else {
+    unsigned m = 0;
+    for (int p = tid; p < npix; p += GS_THREADS) m = max(m, (unsigned)map[p]);
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+    if (lane == 0) atomicMax(&sh->mx, (int)m);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const double thr = (double)sh->mx * g.q;   // (float)value >= thr, value an integer: value >= ceil(thr)
+    sh->tmin = thr <= 0.0 ? 0 : (thr > 65535.0 ? 65536 : (int)ceil(thr));
+  }
+  __syncthreads();
+  const int tmin = sh->tmin;
+  const unsigned B = (unsigned)g.nkeys;
+
+  while (true) {
+    const int hi = sh->hi;
+    if (tmin >= hi || sh->acc >= g.cap) break;
+    // 1. the window: high-byte histogram of the values in [tmin, hi)
+    for (int k = tid; k < 256; k += GS_THREADS) sh->hist[k] = 0;
+    __syncthreads();
+    {
+      int cb = -1, cc = 0;   // runs of one bin are counted in a register (plateaus would serialise the LDS atomics)
+#pragma unroll 4
+      for (int p = p0 + tid; p < p1; p += GS_THREADS) {
+        int x, y;
+        gs_xy((unsigned)p, g, x, y);
+        const int v = map[p];
+        if (x >= 1 && x <= g.W - 2 && v >= tmin && v < hi) {
+          const int b = v >> 8;
+          if (b != cb) { if (cc) atomicAdd(&sh->hist[cb], (unsigned)cc); cb = b; cc = 0; }
+          cc++;
+        }
+      }
+      if (cc) atomicAdd(&sh->hist[cb], (unsigned)cc);
+    }
+    __syncthreads();
+    if (wave == 0) gs_cut(sh, B + 1);   // more than B candidates left?
+    __syncthreads();
+    if (sh->cut_bin < 0) {   // all of them fit: one sorted run
+      if (tid == 0) { sh->lo = tmin; sh->inc = 1; }
+    } else {
+      const int b1 = sh->cut_bin;
+      const unsigned above1 = (unsigned)sh->cut_above;
+      __syncthreads();
+      for (int k = tid; k < 256; k += GS_THREADS) sh->hist[k] = 0;
+      __syncthreads();
+      const int va = max(tmin, b1 << 8), vb = min(hi, (b1 << 8) + 256);
+      int cb = -1, cc = 0;
+#pragma unroll 4
+      for (int p = p0 + tid; p < p1; p += GS_THREADS) {
+        int x, y;
+        gs_xy((unsigned)p, g, x, y);
+        const int v = map[p];
+        if (x >= 1 && x <= g.W - 2 && v >= va && v < vb) {
+          const int b = v & 255;
+          if (b != cb) { if (cc) atomicAdd(&sh->hist[cb], (unsigned)cc); cb = b; cc = 0; }
+          cc++;
+        }
+      }
+      if (cc) atomicAdd(&sh->hist[cb], (unsigned)cc);
+      __syncthreads();
+      if (wave == 0) gs_cut(sh, B - above1);   // >= 1; the bin holds more than that
+      __syncthreads();
+      if (tid == 0) {
+        const int b2 = sh->cut_bin;
+        const int gt = (int)above1 + sh->cut_above, eq = (int)sh->hist[b2];
+        sh->lo = (b1 << 8) + b2;
+        sh->cnt_gt = gt;
+        sh->cnt_eq = eq;
+        sh->inc = (unsigned)(gt + eq) <= B;
+      }
+    }
+    if (tid == 0) sh->nk = 0;
+    __syncthreads();
+    const int lo = sh->lo, inc = sh->inc;
+    // 2. gather (lo, hi) -- and lo itself when it fits -- and sort
+    {
+      const int vlo = inc ? lo : lo + 1;
+      for (int pb = p0; pb < p1; pb += GS_THREADS) {
+        const int p = pb + tid;
+        int x = 0, y = 0;
+        bool f = false;
+        unsigned v = 0;
+        if (p < p1) {
+          gs_xy((unsigned)p, g, x, y);
+          v = map[p];
+          f = x >= 1 && x <= g.W - 2 && (int)v >= vlo && (int)v < hi;
+        }
+        const unsigned long long m = __ballot(f);
+        if (m) {
+          int base = 0;
+          if (lane == __builtin_ctzll(m)) base = atomicAdd(&sh->nk, __popcll(m));
+          base = __shfl(base, __builtin_ctzll(m), 64);
+          if (f) keys[base + __popcll(m & ((1ull << lane) - 1ull))] = ((unsigned long long)v << 32) | (unsigned)p;
+        }
+      }
+    }
+    __syncthreads();
+    const int nk = sh->nk;
+    if (nk > 1) {
+      int P = 1;
+      while (P < nk) P <<= 1;
+      for (int k = nk + tid; k < P; k += GS_THREADS) keys[k] = 0ull;   // real keys are > 0 (index >= W + 1)
+      __syncthreads();
+      for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+          for (int i = tid; i < P; i += GS_THREADS) {
+            const int ixj = i ^ j;
+            if (ixj > i) {
+              const unsigned long long a = keys[i], b = keys[ixj];
+              if (((i & k) == 0) ? (a < b) : (a > b)) { keys[i] = b; keys[ixj] = a; }
+            }
+          }
+          __syncthreads();
+        }
+    }
+    if (wave == 0 && nk > 0) gftt_trim<GT>(keys, nk, sh, tab, out, g);
+    __syncthreads();
+    // 3. a plateau at lo that did not fit: descending raster order, 1024 pixels at a time
+    if (!inc) {
+      int left = sh->cnt_eq;
+      for (int pb = p1 - 1; pb >= p0 && left > 0 && sh->acc < g.cap; pb -= GS_THREADS) {
+        const int p = pb - tid;
+        bool f = false;
+        if (p >= p0) {
+          int x, y;
+          gs_xy((unsigned)p, g, x, y);
+          f = x >= 1 && x <= g.W - 2 && (int)map[p] == lo;
+        }
+        const unsigned long long m = __ballot(f);
+        if (lane == 0) sh->wsum[wave] = __popcll(m);
+        __syncthreads();
+        int base = 0, tot = 0;
+        for (int w = 0; w < GS_WAVES; w++) {
+          const int c = sh->wsum[w];
+          base += w < wave ? c : 0;
+          tot += c;
+        }
+        if (f) keys[base + __popcll(m & ((1ull << lane) - 1ull))] = ((unsigned long long)lo << 32) | (unsigned)p;
+        __syncthreads();
+        if (wave == 0 && tot > 0) gftt_trim<GT>(keys, tot, sh, tab, out, g);
+        left -= tot;
+        __syncthreads();
+      }
+    }
+    if (tid == 0) sh->hi = lo;
+    __syncthreads();
+  }
+  if (tid == 0) count[img] = sh->acc;
+}
+
+GftSelPlan gftt_select_plan(int W, int H, int max_features, double quality, double min_distance) {
+  GftSelPlan pl;
+  memset(&pl, 0, sizeof(pl));
+  GftSelGeom& g = pl.g;
+  g.W = W; g.H = H;
+  g.cap = max_features > 0 ? max_features : (W - 2) * (H - 2);
+  g.q = quality;
+  g.trim = min_distance >= 1.0;
+  g.magic = ((1ull << 40) / (unsigned long long)W) + 1ull;
+  if (g.trim) {
+    g.cell = (int)lrint(min_distance);   // cvRound: half to even
+    g.gw = (W + g.cell - 1) / g.cell;
+    g.gh = (H + g.cell - 1) / g.cell;
+    g.lim = (int)ceil(min_distance * min_distance);   // integer d2 < md^2 (double)  <=>  d2 < ceil(md^2)
+  }
+  const size_t table = g.trim ? (size_t)16 * g.gw * g.gh : 0;
+  const size_t room = kGftSelLds - GS_FIXED_LDS;
+  if (table + (size_t)8 * 1024 <= room) {
+    size_t B = 1024;
+    while (2 * B <= kGftSelKeysMax && 2 * B * 8 + table <= room) B *= 2;
+    g.nkeys = (int)B;
+    pl.global_table = false;
+    pl.lds_bytes = (size_t)B * 8 + GS_FIXED_LDS + table;
+  } else {
+    g.nkeys = kGftSelKeysMax;
+    pl.global_table = true;
+    pl.lds_bytes = (size_t)kGftSelKeysMax * 8 + GS_FIXED_LDS;
+    pl.table_bytes_per_image = table;
+  }
+  return pl;
+}
+
+hipError_t launch_gftt_select(const uint16_t* eig, const unsigned* maxv, float* kpts, int* count, unsigned* gtab, const GftSelPlan& pl,
+                              int img0, int n, hipStream_t s) {
+  GftSelGeom g = pl.g;
+  g.img0 = img0;
+  if (pl.global_table) {
+    hipError_t e = hipMemsetAsync(gtab, 0, pl.table_bytes_per_image * n, s);
+    if (e != hipSuccess) return e;
+  }
+  auto kern = pl.global_table ? gftt_select_kernel<true> : gftt_select_kernel<false>;
+  // (more than 64 KB of dynamic LDS has to be granted per kernel; idempotent, so unsynchronised repeats are harmless)
+  if (pl.lds_bytes > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)kGftSelLds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(n), dim3(GS_THREADS), pl.lds_bytes, s, eig, maxv, kpts, count, gtab, g);
+  return hipGetLastError();
+}
+
+}  // namespace sbm

@@ -94,6 +94,28 @@ def fpga_validate(params):
     return int(load_library().sbm_fpga_params_validate(ctypes.byref(params)))
 
 
+class GfttSelectParams(ctypes.Structure):
+    """`sbm_gftt_select_params` of include/sbm.h: generateKeypoints2's constants (src/slam/src/core/GFTT.cpp:50-53)."""
+
+    _fields_ = [("max_features", ctypes.c_int32), ("quality_level", ctypes.c_double), ("min_distance", ctypes.c_double),
+                ("block_size", ctypes.c_int32)]
+
+
+def gftt_select_params(max_features=1500, quality_level=0.01, min_distance=7.0, block_size=3):
+    """The reference's constants by default."""
+    return GfttSelectParams(int(max_features), float(quality_level), float(min_distance), int(block_size))
+
+
+def gftt_select_validate(params, width, height):
+    """Status code of sbm_gftt_select_params_validate (0 = ok)."""
+    return load_library().sbm_gftt_select_params_validate(ctypes.byref(params), width, height)
+
+
+def gftt_select_capacity(params, width, height):
+    """Points per image slot: max_features, or every interior pixel when max_features <= 0."""
+    return params.max_features if params.max_features > 0 else (width - 2) * (height - 2)
+
+
 class StereoBMError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"sbm status {code}: {message}")
@@ -170,6 +192,13 @@ def load_library():
     L.sbm_gftt_eig_device.argtypes = [vp, ci, vp, ci, ci, vp, vp, ci]
     L.sbm_fpga_compute.argtypes = [vp, vp, sz, vp, sz, fp, vp, sz]
     L.sbm_gftt_eig.argtypes = [vp, vp, sz, ci, ci, vp, sz, ctypes.POINTER(u32)]
+    gp = ctypes.POINTER(GfttSelectParams)
+    L.sbm_gftt_select_params_default.argtypes = [gp]
+    L.sbm_gftt_select_params_default.restype = None
+    L.sbm_gftt_select_params_validate.argtypes = [gp, ci, ci]
+    L.sbm_gftt_select_device.argtypes = [vp, ci, vp, vp, ci, ci, gp, vp, vp, ci]
+    L.sbm_gftt_select.argtypes = [vp, vp, sz, ci, ci, ctypes.c_uint16, gp, vp, sz, ctypes.POINTER(ctypes.c_int)]
+    L.sbm_gftt_detect_device.argtypes = [vp, ci, vp, ci, ci, gp, vp, vp, vp, vp, ci]
     L.sbm_stream.argtypes = [vp]
     L.sbm_stream.restype = vp
     L.sbm_strerror.argtypes = [ci]
@@ -532,6 +561,91 @@ class StereoBM:
         torch.cuda.current_stream(img.device).synchronize()
         _check(self._L.sbm_gftt_eig_device(self._h, n, img.data_ptr(), w, h, eig.data_ptr(), mx.data_ptr(), 1), self._h)
         return eig.to(torch.int32) & 0xffff, mx
+
+    # ---- keypoint selection of generateKeypoints2 (src/slam/src/core/GFTT.cpp:41-170) ------------------------------------------
+    @staticmethod
+    def _gftt_params(params, kw):
+        if params is None:
+            return gftt_select_params(**kw)
+        if kw:
+            raise TypeError("pass either a GfttSelectParams or keyword parameters")
+        return params
+
+    def gftt_select(self, eig, mx=None, params=None, sync=True, **kw):
+        """generateKeypoints2 on torch CUDA maps (n,H,W) or (H,W) -- uint16 payload as int16 (what sbm_gftt_eig_device writes), or
+        int32 holding 0..65535 (what gftt_eig returns) -- and their Max words mx (n,) int32, or None: each map's maximum.
+        Returns (kpts float32 (n, cap, 2), count int32 (n,)); map i's points are kpts[i, :count[i]], in acceptance order.
+        sync=False leaves the call running on the engine's stream (call synchronize() before reading the results)."""
+        import torch
+
+        p = self._gftt_params(params, kw)
+        e3 = eig if eig.dim() == 3 else eig[None]
+        if e3.dim() != 3 or not e3.is_cuda:
+            raise StereoBMError(-2, "eig must be a torch CUDA (n,H,W) or (H,W) tensor")
+        if e3.dtype in (torch.int32, torch.int64):
+            e3 = torch.where(e3 > 32767, e3 - 65536, e3).to(torch.int16)
+        elif e3.dtype != torch.int16 and str(e3.dtype) != "torch.uint16":
+            raise StereoBMError(-2, "eig must hold uint16 values (int16, uint16 or int32 tensor)")
+        e3 = e3.contiguous()
+        n, h, w = e3.shape
+        cap = gftt_select_capacity(p, w, h)
+        kpts = torch.zeros((n, max(cap, 1), 2), dtype=torch.float32, device=e3.device)
+        count = torch.zeros((n,), dtype=torch.int32, device=e3.device)
+        mp = None
+        if mx is not None:
+            mp = mx.reshape(-1).to(device=e3.device, dtype=torch.int32).contiguous()
+            if mp.numel() != n:
+                raise StereoBMError(-2, f"mx holds {mp.numel()} values for {n} maps")
+        torch.cuda.current_stream(e3.device).synchronize()
+        _check(self._L.sbm_gftt_select_device(self._h, n, e3.data_ptr(), None if mp is None else mp.data_ptr(), w, h,
+                                               ctypes.byref(p), kpts.data_ptr(), count.data_ptr(), 1 if sync else 0), self._h)
+        if not sync:
+            self._inflight.append((e3, mp, kpts, count))
+        return kpts, count
+
+    def gftt_detect(self, img, params=None, sync=True, **kw):
+        """The KPTS_METHOD_FPGA_GFTT front end on torch CUDA uint8 frames (n,H,W) or (H,W): eigenvalue map, then
+        generateKeypoints2, in one call. Returns (kpts float32 (n, cap, 2), count int32 (n,))."""
+        import torch
+
+        p = self._gftt_params(params, kw)
+        self._check_device_images(img)
+        i3 = (img if img.dim() == 3 else img[None]).contiguous()
+        n, h, w = i3.shape
+        cap = gftt_select_capacity(p, w, h)
+        eig = torch.empty((n, h, w), dtype=torch.int16, device=i3.device)
+        mx = torch.empty((n,), dtype=torch.int32, device=i3.device)
+        kpts = torch.zeros((n, max(cap, 1), 2), dtype=torch.float32, device=i3.device)
+        count = torch.zeros((n,), dtype=torch.int32, device=i3.device)
+        torch.cuda.current_stream(i3.device).synchronize()
+        _check(self._L.sbm_gftt_detect_device(self._h, n, i3.data_ptr(), w, h, ctypes.byref(p), eig.data_ptr(), mx.data_ptr(),
+                                               kpts.data_ptr(), count.data_ptr(), 1 if sync else 0), self._h)
+        if not sync:
+            self._inflight.append((i3, eig, mx, kpts, count))
+        return kpts, count
+
+    def gftt_select_host(self, eig, max_eig, params=None, **kw):
+        """numpy uint16 (H,W) map (rows may be strided) + the Max register -> numpy float32 (k, 2) points, as
+        generateKeypoints2(eig, max, kpts2d) fills kpts2d."""
+        p = self._gftt_params(params, kw)
+        if not isinstance(eig, np.ndarray) or eig.dtype != np.uint16 or eig.ndim != 2 or eig.strides[1] != 2 or \
+                eig.strides[0] < 2 * eig.shape[1]:
+            raise StereoBMError(-2, "eig must be an (H,W) uint16 array with dense rows")
+        h, w = eig.shape
+        cap = gftt_select_capacity(p, w, h)
+        out = np.zeros((max(cap, 1), 2), np.float32)
+        k = ctypes.c_int()
+        _check(self._L.sbm_gftt_select(self._h, eig.ctypes.data, eig.strides[0], w, h, int(max_eig) & 0xffff, ctypes.byref(p),
+                                       out.ctypes.data, max(cap, 0), ctypes.byref(k)), self._h)
+        return out[:k.value].copy()
+
+    def gftt_profile(self):
+        out = {}
+        for k in ("gftt_select_eig", "gftt_select_select", "gftt_select_total"):
+            v = ctypes.c_float()
+            _check(self._L.sbm_get_profile(self._h, k.encode(), ctypes.byref(v)), self._h)
+            out[k] = v.value
+        return out
 
     def synchronize(self):
         _check(self._L.sbm_synchronize(self._h), self._h)
