@@ -80,7 +80,8 @@
  *                                          wins. The oracle has the same bits; tests/golden/pin_kit.npz holds this engine's outputs
  *                                          under both readings of each, and tools/verify_with_opencv.py (numpy + cv2 only) names the
  *                                          reading a given OpenCV implements -- adopting it is a default flip here, not a rewrite;
- *                                          bits 32 and 64 belong to the semi-global matcher (see sbm_sgbm_params below)
+ *                                          bits 32 and 64 belong to the semi-global matcher (see sbm_sgbm_params below),
+ *                                          bit 128 to the ORB descriptor's blur (see sbm_orb_params below)
  * Tuning knobs of the measurement scripts (SBM_FAST_NSEG, SBM_FAST_TAPER, SBM_FAST_UNIQ_PLAIN,
  * SBM_FAST_SPLIT, SBM_PF_ROWS, SBM_HOST_CHUNK, SBM_HOST_PIPELINE, SBM_DEV_*; the interior kernel's are listed in
  * u96-slam_amd/csrc/sbm_sad_fast_dev.h) exist only in development builds (-DSBM_DEV, tools/exp/r05_devlib.sh); this library
@@ -420,6 +421,63 @@ int sbm_gftt_select(sbm_handle* h, const uint16_t* eig, size_t eig_stride, int w
  * (SBM_ERR_SIZE outside). */
 int sbm_gftt_detect_device(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_select_params* p,
                            void* d_eig, void* d_max, void* d_kpts, void* d_count, int sync);
+
+/* ---- ORB descriptors: computeDescriptor (src/slam/src/opencv/CvORB.cpp; main.cpp:246-248) ----------------------------------
+ * The reference's descriptor step for the keypoints generateKeypoints2 produces (cv::KeyPoint(pt, blockSize): angle -1, octave
+ * 0), on the device, so that a frame's keypoints, descriptors and depth stay there. What the reference computes at level 0:
+ *   blur      GaussianBlur(7x7, sigma 2, BORDER_REFLECT_101) of the image-sized ROI of the frame's reflect-101 bordered copy. The
+ *             ROI is a sub-matrix without BORDER_ISOLATED, so (recalled, not pinned) OpenCV takes sepFilter2D's 8-bit path:
+ *             taps cvRound(256 g) of getGaussianKernel(7, 2) = [18, 34, 49, 55, 49, 34, 18] (they sum to 257), exact integer
+ *             row sums r, column sums S = sum k_j r_j, out = min(255, round(S / 2^16)); the pixels around the ROI are the
+ *             unblurred frame's reflect-101 copy. Rounding of S / 2^16 ties: half to even (the vectorised column filter, every
+ *             column at width 640), or half up with bit 128 of SBM_CV_READING (the scalar tail's (S + 32768) >> 16).
+ *   border    runByImageBorder(kpts, size, edge_threshold): the points outside Rect(Point(e, e), Point(W - e, H - e)) are
+ *             erased, keeping the order; all of them when W <= 2e or H <= 2e. Rect::contains receives the point converted to
+ *             Point by saturate_cast, i.e. cvRound (half to even) -- recalled, not pinned; GFTT's integral points do not care.
+ *   describe  a = (float)cos(angle * (float)(CV_PI / 180.f)), b = (float)sin(...) (in double); per pattern point p, in float
+ *             without contraction, dx = cvRound(p.x * a - p.y * b), dy = cvRound(p.x * b + p.y * a); byte i of a descriptor
+ *             holds in bit k blur[c + d(16i + 2k)] < blur[c + d(16i + 2k + 1)], c = (cvRound(y), cvRound(x)).
+ * The pattern is the caller's: 512 points (x, y) as 1024 ints, pairs of consecutive points compared -- the reference passes
+ * bit_pattern_31_2 from its CvORB.h. Coordinates in [-13, 13] (SBM_ERR_UNSUPPORTED outside), so that every sample lies within 18
+ * pixels of its centre. Scope: level 0, one angle per call, WTA_K 2, 32-byte descriptors, no mask.
+ * Limits (status codes): width and height 1..8192 (SBM_ERR_SIZE outside; at or below 2 * edge_threshold every keypoint is
+ * erased and nothing is blurred -- count 0, not an error), at most 65 535 frames per call (SBM_ERR_UNSUPPORTED), cap >= 1
+ * (SBM_ERR_SIZE); device pointers d_kpts / d_kpts_out 8-byte and d_desc 4-byte aligned (SBM_ERR_UNSUPPORTED).
+ * Kernels: a tiled blur of every frame, a per-frame compaction, and the descriptors over all (frame,
+ * keypoint) slots. Without d_blur the blurred frames go to handle-owned scratch, in chunks of frames of at most 256 MiB.
+ * sbm_get_profile: while profiling is enabled (any mode) these calls synchronise and record "orb_blur", "orb_desc" (compaction
+ * and descriptors) and "orb_total" (ms of the last call; sbm_orb_features_device's keypoint detection is not in them). */
+typedef struct sbm_orb_params {
+  int32_t edge_threshold;   /* edgeThreshold, default 19; 18..4096 (samples reach 18 pixels from the centre)       */
+  float angle;              /* the keypoints' shared cv::KeyPoint::angle in degrees, default -1; finite          */
+  int32_t blur_ksize;       /* GaussianBlur's kernel size: 7, the reference's (nothing else is supported)        */
+  double blur_sigma;        /* GaussianBlur's sigma: 2.0, the reference's (nothing else is supported)            */
+} sbm_orb_params;
+
+/* Fill *p with the reference's values: 19, -1, 7, 2.0. */
+void sbm_orb_params_default(sbm_orb_params* p);
+/* SBM_ERR_NULL, SBM_ERR_UNSUPPORTED (a field outside the limits above), else SBM_OK. */
+int sbm_orb_params_validate(const sbm_orb_params* p);
+/* n dense u8 frames in DEVICE memory (d_img: n * height * width); keypoints in the layout sbm_gftt_select_device writes: frame
+ * i's float (x, y) pairs from d_kpts + i * cap * 2, d_count n int32 read on the device (clamped to [0, cap]). Writes the kept
+ * keypoints (stable order, same layout; d_kpts_out == d_kpts is allowed), the kept counts d_count_out (n int32; may be
+ * d_count), and the descriptors d_desc (n * cap * 32 bytes, row j of frame i at (i * cap + j) * 32; rows past the kept count
+ * are left as they were). d_blur: NULL, or n * height * width bytes that receive the blurred frames (untouched when width or
+ * height <= 2 * edge_threshold). pattern: 1024 host ints. Asynchronous on the handle's stream unless sync != 0. */
+int sbm_orb_describe_device(sbm_handle* h, int n, const void* d_img, int width, int height, int cap, const void* d_kpts,
+                            const void* d_count, const int* pattern, const sbm_orb_params* p, void* d_kpts_out, void* d_count_out,
+                            void* d_desc, void* d_blur, int sync);
+/* Host form for ONE frame, shaped like computeDescriptor(image, noArray(), kpts, true, desc): img strided (img_stride in
+ * bytes), count float (x, y) pairs in kpts; the kept pairs go to kpts_out (count entries; may be kpts), their number to
+ * *count_out, their descriptors to desc (32 bytes each). Synchronous. */
+int sbm_orb_describe(sbm_handle* h, const uint8_t* img, size_t img_stride, int width, int height, const float* kpts, int count,
+                     const int* pattern, const sbm_orb_params* p, float* kpts_out, int* count_out, uint8_t* desc);
+/* The whole KPTS_METHOD_FPGA_GFTT + desc front end on n dense u8 frames: sbm_gftt_detect_device (d_eig, d_max, d_kpts, d_count
+ * as there; cap = the selection's), then sbm_orb_describe_device on its output with the keypoints compacted in place, in one
+ * call on the handle's stream. The eigenvalue map's limits apply: width 3..1023, height 5..511 (SBM_ERR_SIZE outside). */
+int sbm_orb_features_device(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_select_params* gp,
+                            const int* pattern, const sbm_orb_params* p, void* d_eig, void* d_max, void* d_kpts, void* d_count,
+                            void* d_desc, void* d_blur, int sync);
 
 /* ---- semi-global matcher: cv::StereoSGBM (the reference's DEPTH_METHOD_CV_SGBM, main.cpp:218-234) -------------------------
  * Restatement of cv::StereoSGBM::compute() for 8-bit single-channel pairs in MODE_HH (two passes, 8 paths: the reference's

@@ -14,11 +14,12 @@ GPU raises. The CPU oracle lives in /oracle and is only used by the tests and by
 from .stereobm import (StereoBM, StereoBMError, SbmParams, StereoModel, library_path, load_library, PREFILTER_XSOBEL,  # noqa: F401
                        PREFILTER_NORMALIZED_RESPONSE, RectCam, make_rect_cam, PREFILTER_FLAVOUR_CV, PREFILTER_FLAVOUR_RTL, trim,
                        FpgaParams, fpga_params, fpga_params_from_regs, fpga_sad_size_reg, fpga_validate, compute_multi,
-                       GfttSelectParams, gftt_select_params, gftt_select_validate, gftt_select_capacity)
+                       GfttSelectParams, gftt_select_params, gftt_select_validate, gftt_select_capacity,
+                       OrbParams, orb_params, orb_validate)
 from .stereosgbm import StereoSGBM, SgbmParams, sgbm_params, sgbm_validate  # noqa: F401
 
 __all__ = ["StereoBM", "StereoBMError", "SbmParams", "StereoModel", "library_path", "load_library", "PREFILTER_XSOBEL",
            "PREFILTER_NORMALIZED_RESPONSE", "RectCam", "make_rect_cam", "PREFILTER_FLAVOUR_CV", "PREFILTER_FLAVOUR_RTL", "trim",
            "FpgaParams", "fpga_params", "fpga_params_from_regs", "fpga_sad_size_reg", "fpga_validate", "compute_multi",
            "StereoSGBM", "SgbmParams", "sgbm_params", "sgbm_validate", "GfttSelectParams", "gftt_select_params",
-           "gftt_select_validate", "gftt_select_capacity"]
+           "gftt_select_validate", "gftt_select_capacity", "OrbParams", "orb_params", "orb_validate"]

@@ -108,6 +108,14 @@ struct sbm_handle {
   size_t gs_out_bytes;
   hipEvent_t gs_ev[3];
   float gs_ms[3];   // eig, select, total
+  // ORB descriptors (allocated on first use): blurred frames of one chunk; the keypoints, counts and descriptors of the
+  // host-memory entry point
+  uint8_t* or_blur;
+  size_t or_blur_bytes;
+  void* or_io;
+  size_t or_io_bytes;
+  hipEvent_t or_ev[3];
+  float or_ms[3];   // blur, desc, total
 };
 
 // Entry points select the handle's device and put the caller's current device back on return.
@@ -246,6 +254,11 @@ static void free_gftt_sel(sbm_handle* h) {
   h->gs_tab = nullptr; h->gs_out = nullptr; h->gs_tab_bytes = h->gs_out_bytes = 0;
 }
 
+static void free_orb(sbm_handle* h) {
+  hipFree(h->or_blur); hipFree(h->or_io);
+  h->or_blur = nullptr; h->or_io = nullptr; h->or_blur_bytes = h->or_io_bytes = 0;
+}
+
 static void free_fpga(sbm_handle* h) {
   hipFree(h->fp_xs_l); hipFree(h->fp_xs_r); hipFree(h->fp_rec); hipFree(h->fp_flag);
   h->fp_xs_l = h->fp_xs_r = nullptr; h->fp_rec = nullptr; h->fp_flag = nullptr;
@@ -291,6 +304,7 @@ static size_t scratch_bytes(const sbm_handle* h) {
   b += (size_t)h->fq_n * h->fq_W * h->fq_H * 8;
   b += (size_t)h->fp_n * h->fp_W * h->fp_H * 10;
   b += 2 * h->sg_cs_bytes + h->sg_pre_bytes;
+  b += h->or_blur_bytes + h->or_io_bytes;
   if (h->sg_spk_runs) b += (size_t)h->sg_spk_n * h->sg_spk_H * (16 * ((size_t)h->sg_spk_W + kSpkRecordPad) + 4 * ((size_t)h->sg_spk_W + kSpkSeamPad) + 24);
   return b;
 }
@@ -376,6 +390,7 @@ void sbm_destroy(sbm_handle* h) {
         free_fpga(h);
         free_sgbm(h);
         free_gftt_sel(h);
+        free_orb(h);
       }
       g_pool[g_pool_n++] = h;
       return;
@@ -396,10 +411,13 @@ static void destroy_now(sbm_handle* h) {
   free_fpga(h);
   free_sgbm(h);
   free_gftt_sel(h);
+  free_orb(h);
   for (int i = 0; i < 6; i++)
     if (h->sg_ev[i]) hipEventDestroy(h->sg_ev[i]);
   for (int i = 0; i < 3; i++)
     if (h->gs_ev[i]) hipEventDestroy(h->gs_ev[i]);
+  for (int i = 0; i < 3; i++)
+    if (h->or_ev[i]) hipEventDestroy(h->or_ev[i]);
   for (int r = 0; r < sbm_handle::kRing; r++)
     for (int i = 0; i < sbm_handle::kMarks; i++)
       if (h->ev[r][i]) hipEventDestroy(h->ev[r][i]);
@@ -454,6 +472,7 @@ int sbm_set_profiling(sbm_handle* h, int enabled) {
   h->ms_prefilter = h->ms_sad = h->ms_border = h->ms_lr = h->ms_speckle = h->ms_total = 0.f;
   for (float& t : h->sg_ms) t = 0.f;
   for (float& t : h->gs_ms) t = 0.f;
+  for (float& t : h->or_ms) t = 0.f;
   return SBM_OK;
 }
 
@@ -1150,6 +1169,197 @@ int sbm_gftt_select(sbm_handle* h, const uint16_t* eig, size_t eig_stride, int w
   return SBM_OK;
 }
 
+// ---- ORB descriptors of computeDescriptor (CvORB.cpp) --------------------------------------------------------------------------
+void sbm_orb_params_default(sbm_orb_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->edge_threshold = 19;
+  p->angle = -1.f;
+  p->blur_ksize = 7;
+  p->blur_sigma = 2.0;
+}
+
+int sbm_orb_params_validate(const sbm_orb_params* p) {
+  if (!p) return SBM_ERR_NULL;
+  if (p->edge_threshold < 18 || p->edge_threshold > 4096) return SBM_ERR_UNSUPPORTED;
+  if (!std::isfinite(p->angle)) return SBM_ERR_UNSUPPORTED;
+  if (p->blur_ksize != 7 || p->blur_sigma != 2.0) return SBM_ERR_UNSUPPORTED;
+  return SBM_OK;
+}
+
+// The 512 sample offsets of computeOrbDescriptors' GET_VALUE, as the reference evaluates them: float products and differences
+// without contraction (hipcc contracts by default), cvRound half to even.
+static int orb_offsets(const int* pattern, float angle_deg, int W, OrbOffsets* o) {
+#pragma clang fp contract(off)
+  for (int i = 0; i < 1024; i++)
+    if (pattern[i] < -13 || pattern[i] > 13) return SBM_ERR_UNSUPPORTED;
+  const float angle = angle_deg * (float)(3.14159265358979323846 / 180.f);
+  const float a = (float)cos((double)angle), b = (float)sin((double)angle);
+  for (int i = 0; i < 512; i++) {
+    const float px = (float)pattern[2 * i], py = (float)pattern[2 * i + 1];
+    const float x = px * a - py * b, y = px * b + py * a;
+    o->off[i] = (int)std::nearbyint(y) * W + (int)std::nearbyint(x);
+  }
+  return SBM_OK;
+}
+
+static int orb_check(int n, int width, int height, int cap, const void* d_kpts, const void* d_kpts_out, const void* d_desc) {
+  if (n <= 0) return SBM_ERR_BATCH;
+  if (width < 1 || height < 1 || width > 8192 || height > 8192 || cap < 1) return SBM_ERR_SIZE;
+  if (n > 65535) return SBM_ERR_UNSUPPORTED;
+  if (((uintptr_t)d_kpts & 7) || ((uintptr_t)d_kpts_out & 7) || ((uintptr_t)d_desc & 3)) return SBM_ERR_UNSUPPORTED;
+  return SBM_OK;
+}
+
+// Enqueues compaction, blur and descriptors; with profiling, synchronises on its own events (tm[0..2] of the call).
+static int orb_run(sbm_handle* h, int n, const void* d_img, int width, int height, int cap, const void* d_kpts, const void* d_count,
+                   const OrbOffsets& offs, const sbm_orb_params* p, void* d_kpts_out, void* d_count_out, void* d_desc,
+                   void* d_blur, int sync) {
+  const bool prof = h->profiling != 0;
+  float ms[3] = {0.f, 0.f, 0.f};
+  if (prof)
+    for (int i = 0; i < 3; i++)
+      if (!h->or_ev[i]) HIPCHK(h, hipEventCreate(&h->or_ev[i]));
+  auto lap = [&](int i, int j, float* acc) -> int {   // acc += elapsed(or_ev[i], or_ev[j]) once or_ev[j] is reached
+    HIPCHK(h, hipEventSynchronize(h->or_ev[j]));
+    float t = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&t, h->or_ev[i], h->or_ev[j]));
+    *acc += t;
+    return SBM_OK;
+  };
+  const int edge = p->edge_threshold;
+  if (prof) HIPCHK(h, hipEventRecord(h->or_ev[0], h->stream));
+  HIPCHK(h, launch_orb_compact((const float*)d_kpts, (const int*)d_count, (float*)d_kpts_out, (int*)d_count_out, n, cap, width,
+                               height, edge, h->stream));
+  if (prof) {
+    HIPCHK(h, hipEventRecord(h->or_ev[1], h->stream));
+    const int st = lap(0, 1, &ms[1]);
+    if (st != SBM_OK) return st;
+  }
+  if (width > 2 * edge && height > 2 * edge) {   // else every keypoint is gone and nothing needs the blur
+    const int reading = env_switch("SBM_CV_READING", 0);
+    const size_t plane = (size_t)width * height;
+    int chunk = n;
+    uint8_t* blur = (uint8_t*)d_blur;
+    if (!blur) {
+      chunk = (int)std::min<size_t>(n, std::max<size_t>(1, ((size_t)256 << 20) / plane));
+      const size_t bytes = plane * chunk;
+      if (bytes > h->or_blur_bytes) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        hipFree(h->or_blur);
+        h->or_blur = nullptr; h->or_blur_bytes = 0;
+        HIPCHK(h, hipMalloc((void**)&h->or_blur, bytes));
+        h->or_blur_bytes = bytes;
+      }
+    }
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+      const int m = std::min(chunk, n - c0);
+      uint8_t* bc = d_blur ? blur + plane * c0 : h->or_blur;
+      if (prof) HIPCHK(h, hipEventRecord(h->or_ev[0], h->stream));
+      HIPCHK(h, launch_orb_blur((const uint8_t*)d_img + plane * c0, bc, m, width, height, (reading & kReadOrbHalfUp) ? 1 : 0,
+                                h->stream));
+      if (prof) HIPCHK(h, hipEventRecord(h->or_ev[1], h->stream));
+      HIPCHK(h, launch_orb_desc(bc, (const float*)d_kpts_out, (const int*)d_count_out, (uint8_t*)d_desc, c0, m, cap, width, height,
+                                offs, h->stream));
+      if (prof) {
+        HIPCHK(h, hipEventRecord(h->or_ev[2], h->stream));
+        int st = lap(0, 1, &ms[0]);
+        if (st == SBM_OK) st = lap(1, 2, &ms[1]);
+        if (st != SBM_OK) return st;
+      }
+    }
+  }
+  if (prof) {
+    ms[2] = ms[0] + ms[1];
+    for (int i = 0; i < 3; i++) h->or_ms[i] = ms[i];
+  }
+  if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+
+int sbm_orb_describe_device(sbm_handle* h, int n, const void* d_img, int width, int height, int cap, const void* d_kpts,
+                            const void* d_count, const int* pattern, const sbm_orb_params* p, void* d_kpts_out, void* d_count_out,
+                            void* d_desc, void* d_blur, int sync) {
+  if (!h || !d_img || !d_kpts || !d_count || !pattern || !p || !d_kpts_out || !d_count_out || !d_desc) return SBM_ERR_NULL;
+  int st = sbm_orb_params_validate(p);
+  if (st == SBM_OK) st = orb_check(n, width, height, cap, d_kpts, d_kpts_out, d_desc);
+  if (st != SBM_OK) return st;
+  OrbOffsets offs;
+  st = orb_offsets(pattern, p->angle, width, &offs);
+  if (st != SBM_OK) return st;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  return orb_run(h, n, d_img, width, height, cap, d_kpts, d_count, offs, p, d_kpts_out, d_count_out, d_desc, d_blur, sync);
+}
+
+int sbm_orb_features_device(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_select_params* gp,
+                            const int* pattern, const sbm_orb_params* p, void* d_eig, void* d_max, void* d_kpts, void* d_count,
+                            void* d_desc, void* d_blur, int sync) {
+  if (!h || !gp || !d_img || !d_eig || !d_max || !d_kpts || !d_count || !pattern || !p || !d_desc) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  if (width < 3 || height < 5 || width > 1023 || height > 511) return SBM_ERR_SIZE;   // the eigenvalue map's limits
+  int st = sbm_gftt_select_params_validate(gp, width, height);
+  if (st == SBM_OK) st = sbm_orb_params_validate(p);
+  const int cap = gp->max_features > 0 ? gp->max_features : (width - 2) * (height - 2);
+  if (st == SBM_OK) st = orb_check(n, width, height, cap, d_kpts, d_kpts, d_desc);
+  if (st != SBM_OK) return st;
+  OrbOffsets offs;
+  st = orb_offsets(pattern, p->angle, width, &offs);
+  if (st != SBM_OK) return st;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  st = gftt_select_run(h, n, d_img, d_eig, d_max, width, height, gp, d_kpts, d_count, 0);
+  if (st != SBM_OK) return st;
+  return orb_run(h, n, d_img, width, height, cap, d_kpts, d_count, offs, p, d_kpts, d_count, d_desc, d_blur, sync);
+}
+
+int sbm_orb_describe(sbm_handle* h, const uint8_t* img, size_t img_stride, int width, int height, const float* kpts, int count,
+                     const int* pattern, const sbm_orb_params* p, float* kpts_out, int* count_out, uint8_t* desc) {
+  if (!h || !img || !pattern || !p || !count_out || (count > 0 && (!kpts || !kpts_out || !desc))) return SBM_ERR_NULL;
+  if (count < 0 || img_stride < (size_t)width) return SBM_ERR_SIZE;
+  const int cap = std::max(count, 1);
+  int st = sbm_orb_params_validate(p);
+  if (st == SBM_OK) st = orb_check(1, width, height, cap, nullptr, nullptr, nullptr);
+  if (st != SBM_OK) return st;
+  OrbOffsets offs;
+  st = orb_offsets(pattern, p->angle, width, &offs);
+  if (st != SBM_OK) return st;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  st = ensure_staging(h, 1, width, height);
+  if (st != SBM_OK) return st;
+  const size_t kb = (size_t)cap * 8, out_bytes = 2 * kb + (size_t)cap * 32 + 16;   // points in, points out, descriptors, counts
+  if (out_bytes > h->or_io_bytes) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    hipFree(h->or_io);
+    h->or_io = nullptr; h->or_io_bytes = 0;
+    HIPCHK(h, hipMalloc(&h->or_io, out_bytes));
+    h->or_io_bytes = out_bytes;
+  }
+  char* io = (char*)h->or_io;
+  float* d_ki = (float*)io;
+  float* d_ko = (float*)(io + kb);
+  uint8_t* d_de = (uint8_t*)(io + 2 * kb);
+  int* d_n = (int*)(io + 2 * kb + (size_t)cap * 32);
+  HIPCHK(h, hipMemcpy2DAsync(h->st_l, width, img, img_stride, width, height, hipMemcpyHostToDevice, h->stream));
+  if (count > 0) HIPCHK(h, hipMemcpyAsync(d_ki, kpts, (size_t)count * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_n, &count, sizeof(int), hipMemcpyHostToDevice, h->stream));
+  st = orb_run(h, 1, h->st_l, width, height, cap, d_ki, d_n, offs, p, d_ko, d_n + 1, d_de, nullptr, 0);
+  if (st != SBM_OK) {
+    hipStreamSynchronize(h->stream);   // `count` is read by an enqueued copy
+    return st;
+  }
+  int k = 0;
+  HIPCHK(h, hipMemcpyAsync(&k, d_n + 1, sizeof(k), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (k > 0) {
+    HIPCHK(h, hipMemcpy(kpts_out, d_ko, (size_t)k * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(desc, d_de, (size_t)k * 32, hipMemcpyDeviceToHost));
+  }
+  *count_out = k;
+  return SBM_OK;
+}
+
 int sbm_disparity_to_float_device(sbm_handle* h, int n, const void* d_disp, int width, int height, void* d_out, int sync) {
   if (!h || !d_disp || !d_out) return SBM_ERR_NULL;
   if (n <= 0) return SBM_ERR_BATCH;
@@ -1221,6 +1431,13 @@ int sbm_get_profile(sbm_handle* h, const char* name, float* ms) {
     while (i < 3 && strcmp(name, kGs[i])) i++;
     if (i == 3) return SBM_ERR_UNSUPPORTED;
     *ms = h->gs_ms[i];
+  }
+  else if (!strncmp(name, "orb_", 4)) {
+    static const char* const kOr[3] = {"orb_blur", "orb_desc", "orb_total"};
+    int i = 0;
+    while (i < 3 && strcmp(name, kOr[i])) i++;
+    if (i == 3) return SBM_ERR_UNSUPPORTED;
+    *ms = h->or_ms[i];
   }
   else return SBM_ERR_UNSUPPORTED;
   return SBM_OK;

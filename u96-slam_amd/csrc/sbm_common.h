@@ -158,6 +158,19 @@ GftSelPlan gftt_select_plan(int W, int H, int max_features, double quality, doub
 hipError_t launch_gftt_select(const uint16_t* eig, const unsigned* maxv, float* kpts, int* count, unsigned* gtab, const GftSelPlan& pl,
                               int img0, int n, hipStream_t s);
 
+// ORB descriptors of computeDescriptor at level 0 (sbm_orb.hip). blur: n dense u8 frames -> n dense u8 frames (W, H >= 4);
+// compact: runByImageBorder per frame (one workgroup each; in place allowed); desc: frames [f0, f0 + n) of the batch, `blur`
+// holding exactly those n frames, 32 bytes per kept keypoint at (f * cap + j) * 32.
+constexpr int kReadOrbHalfUp = 128;   // SBM_CV_READING: the blur's column filter rounds half up instead of half to even
+struct OrbOffsets {
+  int off[512];   // dy * W + dx of the 512 rotated pattern points, in pattern order
+};
+hipError_t launch_orb_blur(const uint8_t* src, uint8_t* dst, int n, int W, int H, int half_up, hipStream_t s);
+hipError_t launch_orb_compact(const float* kin, const int* cin, float* kout, int* cout, int n, int cap, int W, int H, int edge,
+                              hipStream_t s);
+hipError_t launch_orb_desc(const uint8_t* blur, const float* kpts, const int* count, uint8_t* desc, int f0, int n, int cap, int W,
+                           int H, const OrbOffsets& offs, hipStream_t s);
+
 // Consumers of the map (sbm_consume.hip): decimation, reprojection, keypoint depth.
 hipError_t launch_disp_to_float(const int16_t* disp, float* out, size_t count, hipStream_t s);
 hipError_t launch_decimate(const int16_t* disp, int16_t* out, int n, int W, int H, int scale, hipStream_t s);

@@ -116,6 +116,31 @@ def gftt_select_capacity(params, width, height):
     return params.max_features if params.max_features > 0 else (width - 2) * (height - 2)
 
 
+class OrbParams(ctypes.Structure):
+    """`sbm_orb_params` of include/sbm.h: computeDescriptor's constants (src/slam/src/opencv/CvORB.cpp) and the keypoints' angle."""
+
+    _fields_ = [("edge_threshold", ctypes.c_int32), ("angle", ctypes.c_float), ("blur_ksize", ctypes.c_int32),
+                ("blur_sigma", ctypes.c_double)]
+
+
+def orb_params(edge_threshold=19, angle=-1.0, blur_ksize=7, blur_sigma=2.0):
+    """The reference's values by default."""
+    return OrbParams(int(edge_threshold), float(angle), int(blur_ksize), float(blur_sigma))
+
+
+def orb_validate(params):
+    """Status code of sbm_orb_params_validate (0 = ok)."""
+    return load_library().sbm_orb_params_validate(ctypes.byref(params))
+
+
+def orb_pattern_array(pattern):
+    """512 (x, y) points as a contiguous int32 array of 1024 values (ctypes pointer + keep-alive)."""
+    p = np.ascontiguousarray(np.asarray(pattern, dtype=np.int32).reshape(-1))
+    if p.size != 1024:
+        raise StereoBMError(-2, f"the pattern holds {p.size} values, not 1024 (512 points)")
+    return p
+
+
 class StereoBMError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"sbm status {code}: {message}")
@@ -199,6 +224,13 @@ def load_library():
     L.sbm_gftt_select_device.argtypes = [vp, ci, vp, vp, ci, ci, gp, vp, vp, ci]
     L.sbm_gftt_select.argtypes = [vp, vp, sz, ci, ci, ctypes.c_uint16, gp, vp, sz, ctypes.POINTER(ctypes.c_int)]
     L.sbm_gftt_detect_device.argtypes = [vp, ci, vp, ci, ci, gp, vp, vp, vp, vp, ci]
+    op = ctypes.POINTER(OrbParams)
+    L.sbm_orb_params_default.argtypes = [op]
+    L.sbm_orb_params_default.restype = None
+    L.sbm_orb_params_validate.argtypes = [op]
+    L.sbm_orb_describe_device.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp, op, vp, vp, vp, vp, ci]
+    L.sbm_orb_describe.argtypes = [vp, vp, sz, ci, ci, vp, ci, vp, op, vp, ctypes.POINTER(ctypes.c_int), vp]
+    L.sbm_orb_features_device.argtypes = [vp, ci, vp, ci, ci, gp, vp, op, vp, vp, vp, vp, vp, vp, ci]
     L.sbm_stream.argtypes = [vp]
     L.sbm_stream.restype = vp
     L.sbm_strerror.argtypes = [ci]
@@ -638,6 +670,99 @@ class StereoBM:
         _check(self._L.sbm_gftt_select(self._h, eig.ctypes.data, eig.strides[0], w, h, int(max_eig) & 0xffff, ctypes.byref(p),
                                        out.ctypes.data, max(cap, 0), ctypes.byref(k)), self._h)
         return out[:k.value].copy()
+
+    # ---- ORB descriptors of computeDescriptor (src/slam/src/opencv/CvORB.cpp) -------------------------------------------------
+    @staticmethod
+    def _orb_params(params, angle, edge_threshold):
+        return params if params is not None else orb_params(edge_threshold=edge_threshold, angle=angle)
+
+    def orb_describe(self, img, kpts, count, pattern, angle=-1.0, edge_threshold=19, params=None, out=None, blur=False,
+                     sync=True):
+        """computeDescriptor on torch CUDA uint8 frames (n,H,W) or (H,W) with keypoints in sbm_gftt_select_device's layout:
+        kpts float32 (n, cap, 2), count int32 (n,) on the device. Returns (desc uint8 (n, cap, 32), kpts_kept (n, cap, 2),
+        count_kept (n,)), plus the blurred frames (n, H, W) when blur=True. out="inplace" compacts into kpts / count themselves;
+        otherwise new tensors (copies of kpts, so slots past the kept count keep their old values). Descriptor rows past the
+        kept count are zero here (the C-ABI leaves them as they were)."""
+        import torch
+
+        p = self._orb_params(params, angle, edge_threshold)
+        pat = orb_pattern_array(pattern)
+        self._check_device_images(img)
+        i3 = (img if img.dim() == 3 else img[None]).contiguous()
+        n, h, w = i3.shape
+        k3 = kpts if kpts.dim() == 3 else kpts[None]
+        if k3.dtype != torch.float32 or k3.shape[0] != n or k3.shape[2] != 2 or not k3.is_contiguous() or not k3.is_cuda:
+            raise StereoBMError(-2, "kpts must be a contiguous float32 CUDA tensor (n, cap, 2)")
+        c1 = count.reshape(-1)
+        if c1.dtype != torch.int32 or c1.numel() != n or not c1.is_cuda:
+            raise StereoBMError(-2, "count must be an int32 CUDA tensor of n values")
+        c1 = c1.contiguous()
+        cap = k3.shape[1]
+        if out == "inplace":
+            ko, co = k3, c1
+        else:
+            ko, co = k3.clone(), torch.zeros_like(c1)
+        desc = torch.zeros((n, cap, 32), dtype=torch.uint8, device=i3.device)
+        bl = torch.zeros((n, h, w), dtype=torch.uint8, device=i3.device) if blur else None
+        torch.cuda.current_stream(i3.device).synchronize()
+        _check(self._L.sbm_orb_describe_device(self._h, n, i3.data_ptr(), w, h, cap, k3.data_ptr(), c1.data_ptr(),
+                                                pat.ctypes.data, ctypes.byref(p), ko.data_ptr(), co.data_ptr(), desc.data_ptr(),
+                                                None if bl is None else bl.data_ptr(), 1 if sync else 0), self._h)
+        if not sync:
+            self._inflight.append((i3, k3, c1, ko, co, desc, bl))
+        return (desc, ko, co, bl) if blur else (desc, ko, co)
+
+    def orb_describe_host(self, img, kpts, pattern, angle=-1.0, edge_threshold=19, params=None):
+        """numpy uint8 (H,W) frame (rows may be strided) + float32 (k, 2) keypoints -> (desc uint8 (m, 32), kept (m, 2)), as
+        computeDescriptor(image, noArray(), kpts, true, desc) leaves desc and kpts."""
+        p = self._orb_params(params, angle, edge_threshold)
+        pat = orb_pattern_array(pattern)
+        if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or img.ndim != 2 or img.strides[1] != 1:
+            raise StereoBMError(-2, "img must be an (H,W) uint8 array with dense rows")
+        h, w = img.shape
+        kp = np.ascontiguousarray(np.asarray(kpts, dtype=np.float32).reshape(-1, 2))
+        k = kp.shape[0]
+        kept = np.zeros((max(k, 1), 2), np.float32)
+        desc = np.zeros((max(k, 1), 32), np.uint8)
+        m = ctypes.c_int()
+        _check(self._L.sbm_orb_describe(self._h, img.ctypes.data, img.strides[0], w, h, kp.ctypes.data, k, pat.ctypes.data,
+                                        ctypes.byref(p), kept.ctypes.data, ctypes.byref(m), desc.ctypes.data), self._h)
+        return desc[:m.value].copy(), kept[:m.value].copy()
+
+    def orb_features(self, img, pattern, gftt=None, angle=-1.0, edge_threshold=19, params=None, blur=False, sync=True, **kw):
+        """The KPTS_METHOD_FPGA_GFTT + desc front end on torch CUDA uint8 frames (n,H,W) or (H,W): eigenvalue map,
+        generateKeypoints2, computeDescriptor, in one call. gftt: a GfttSelectParams (or keyword parameters of
+        gftt_select_params). Returns (desc (n, cap, 32), kpts (n, cap, 2), count (n,)) [+ blurred frames]."""
+        import torch
+
+        gp = self._gftt_params(gftt, kw)
+        p = self._orb_params(params, angle, edge_threshold)
+        pat = orb_pattern_array(pattern)
+        self._check_device_images(img)
+        i3 = (img if img.dim() == 3 else img[None]).contiguous()
+        n, h, w = i3.shape
+        cap = max(gftt_select_capacity(gp, w, h), 1)
+        eig = torch.empty((n, h, w), dtype=torch.int16, device=i3.device)
+        mx = torch.empty((n,), dtype=torch.int32, device=i3.device)
+        kpts = torch.zeros((n, cap, 2), dtype=torch.float32, device=i3.device)
+        count = torch.zeros((n,), dtype=torch.int32, device=i3.device)
+        desc = torch.zeros((n, cap, 32), dtype=torch.uint8, device=i3.device)
+        bl = torch.zeros((n, h, w), dtype=torch.uint8, device=i3.device) if blur else None
+        torch.cuda.current_stream(i3.device).synchronize()
+        _check(self._L.sbm_orb_features_device(self._h, n, i3.data_ptr(), w, h, ctypes.byref(gp), pat.ctypes.data, ctypes.byref(p),
+                                                eig.data_ptr(), mx.data_ptr(), kpts.data_ptr(), count.data_ptr(), desc.data_ptr(),
+                                                None if bl is None else bl.data_ptr(), 1 if sync else 0), self._h)
+        if not sync:
+            self._inflight.append((i3, eig, mx, kpts, count, desc, bl))
+        return (desc, kpts, count, bl) if blur else (desc, kpts, count)
+
+    def orb_profile(self):
+        out = {}
+        for k in ("orb_blur", "orb_desc", "orb_total"):
+            v = ctypes.c_float()
+            _check(self._L.sbm_get_profile(self._h, k.encode(), ctypes.byref(v)), self._h)
+            out[k] = v.value
+        return out
 
     def gftt_profile(self):
         out = {}
