@@ -221,3 +221,17 @@ def test_cpp_callsite_through_the_adaptor(tmp_path, oracle, golden, mock):
         assert np.array_equal(out[2 * k:], np.full(k, 3.0, np.float32))   # cv::KeyPoint(pt, blockSize)
     else:
         assert len(out) == 2 * k
+
+
+def test_profile_of_a_reused_handle_starts_at_zero(pkg, golden):
+    pkg.trim()                                  # an empty pool: the create below re-arms the handle closed here
+    bm1 = pkg.StereoBM.create(64, 21)
+    bm1.set_profiling(1)
+    bm1.gftt_detect(dev(np.stack([golden["rect_l"]] * 2)))
+    assert bm1.gftt_profile()["gftt_select_total"] > 0
+    bm1.close()                                 # parked for re-use
+    bm2 = pkg.StereoBM.create(64, 21)           # re-armed from the parked handles
+    try:
+        assert bm2.gftt_profile() == {"gftt_select_eig": 0.0, "gftt_select_select": 0.0, "gftt_select_total": 0.0}
+    finally:
+        bm2.close()

@@ -338,3 +338,17 @@ def test_engine_reproduces_the_pin_kit(bm, reading):
         assert np.array_equal(bl[0], kit[f"{name}/blur_r{r}"])
         assert np.array_equal(kk[0, :k], kit[f"{name}/kpts"])
         assert np.array_equal(d[0, :k], kit[f"{name}/desc_r{r}"])
+
+
+def test_profile_of_a_reused_handle_starts_at_zero(pkg, golden, pattern):
+    pkg.trim()                                  # an empty pool: the create below re-arms the handle closed here
+    bm1 = pkg.StereoBM.create(64, 21)
+    bm1.set_profiling(1)
+    bm1.orb_features(dev(np.stack([golden["rect_l"]] * 2)), pattern)
+    assert bm1.orb_profile()["orb_total"] > 0
+    bm1.close()                                 # parked for re-use
+    bm2 = pkg.StereoBM.create(64, 21)           # re-armed from the parked handles
+    try:
+        assert bm2.orb_profile() == {"orb_blur": 0.0, "orb_desc": 0.0, "orb_total": 0.0}
+    finally:
+        bm2.close()

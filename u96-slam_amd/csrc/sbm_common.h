@@ -109,14 +109,8 @@ inline size_t lr_keys_bytes(int n, int W, int H, bool do_lr) {
 hipError_t launch_lrcheck(const int16_t* disp_pre, const int32_t* cost, int16_t* disp_out, unsigned long long* keys,
                           const Geom& g, int disp12_max_diff, hipStream_t s);
 
-// cv filterSpeckles as parallel connected components (union-find). Scratch, for n pairs of W x H (the band walk cuts a row into
-// up to kSpkMaxSeg column segments with books of their own, hence the padding): runs: 16 * n * H * (W + kSpkRecordPad) bytes (run
-// records of the band walk, or the per-pixel labels + sizes of the row-walking kernels); nheads: n * H * kSpkMaxSeg int32 (runs
-// per row and segment; null -> row-walking kernels); seam: n * ceil(H/2) * (W + kSpkSeamPad) uint32, nseam: n * ceil(H/2) *
-// kSpkMaxSeg int32 (contacts across band seams).
+// Speckle filter: launch_speckle and its scratch are in sbm_handle.h.
 constexpr int kSpkMaxSeg = 4, kSpkRecordPad = 288, kSpkSeamPad = 512;
-hipError_t launch_speckle(int16_t* disp, void* runs, int32_t* nheads, uint32_t* seam, int32_t* nseam, const Geom& g, int max_size,
-                          int max_diff, hipStream_t s);
 
 // Stand-alone prefilter of dense images (either flavour) and the rectifier in front of it (sbm_rectify.hip).
 hipError_t launch_prefilter_dense(const uint8_t* d_src, uint8_t* d_dst, int n, int W, int H, int rtl, int cap,
@@ -125,51 +119,8 @@ hipError_t launch_rect_map(const sbm_rect_cam& cam, int W, int H, int16_t* d_map
 hipError_t launch_rect_remap(const uint8_t* d_src, const int16_t* d_map, uint8_t* d_dst, int n, int W, int H,
                              hipStream_t s);
 
-// FPGA-flavour matcher (sbm_fpga.hip). rec: n*sad_hgt*sad_wdt*8 bytes (touched beyond 128 disparities only); flag: n ints,
-// zero when allocated; gen: grows with every call on these buffers (> 0).
-hipError_t launch_fpga_bm(const uint8_t* xl, const uint8_t* xr, void* rec, int* flag, int gen, int16_t* disp, int n,
-                          const sbm_fpga_params& p, hipStream_t s);
-
 // GFTT minimum-eigenvalue map of the PL (sbm_gftt.hip): eig = n*H*W uint16, maxv = n uint32 (`Max` register per image).
 hipError_t launch_gftt_eig(const uint8_t* img, uint16_t* eig, unsigned* maxv, int n, int W, int H, hipStream_t s);
-
-// Keypoint selection of generateKeypoints2 on those maps (sbm_gftt_select.hip): one workgroup per image. The cell table of the
-// minimum-distance trim (16 B per cell, ceil(W/cell) * ceil(H/cell) cells) sits in LDS next to the sort keys when it fits
-// (global_table = false), else in device scratch of table_bytes_per_image per image, zeroed by the launch.
-constexpr size_t kGftSelLds = 160 * 1024;     // LDS of one workgroup
-constexpr int kGftSelKeysMax = 8192;          // keys sorted per value window (64 KiB)
-constexpr int kGftSelWMax = 2048;             // width and height limit: (x, y) pack into 16 bits each, indices into 22 bits
-struct GftSelGeom {
-  int W, H, img0;
-  int cap;                  // points per image slot: max_features > 0 ? max_features : (W - 2) * (H - 2)
-  int trim;                 // min_distance >= 1
-  int cell, gw, gh, lim;    // cvRound(min_distance), grid size, ceil(min_distance^2)
-  int nkeys;                // key capacity of a value window (a power of two)
-  double q;                 // quality_level
-  unsigned long long magic; // floor(2^40 / W) + 1: y = (p * magic) >> 40
-};
-struct GftSelPlan {
-  GftSelGeom g;
-  bool global_table;
-  size_t lds_bytes, table_bytes_per_image;
-};
-GftSelPlan gftt_select_plan(int W, int H, int max_features, double quality, double min_distance);
-// eig: dense uint16 maps, maxv: their Max words (null: each map's maximum); images [img0, img0 + n) of the batch
-hipError_t launch_gftt_select(const uint16_t* eig, const unsigned* maxv, float* kpts, int* count, unsigned* gtab, const GftSelPlan& pl,
-                              int img0, int n, hipStream_t s);
-
-// ORB descriptors of computeDescriptor at level 0 (sbm_orb.hip). blur: n dense u8 frames -> n dense u8 frames (W, H >= 4);
-// compact: runByImageBorder per frame (one workgroup each; in place allowed); desc: frames [f0, f0 + n) of the batch, `blur`
-// holding exactly those n frames, 32 bytes per kept keypoint at (f * cap + j) * 32.
-constexpr int kReadOrbHalfUp = 128;   // SBM_CV_READING: the blur's column filter rounds half up instead of half to even
-struct OrbOffsets {
-  int off[512];   // dy * W + dx of the 512 rotated pattern points, in pattern order
-};
-hipError_t launch_orb_blur(const uint8_t* src, uint8_t* dst, int n, int W, int H, int half_up, hipStream_t s);
-hipError_t launch_orb_compact(const float* kin, const int* cin, float* kout, int* cout, int n, int cap, int W, int H, int edge,
-                              hipStream_t s);
-hipError_t launch_orb_desc(const uint8_t* blur, const float* kpts, const int* count, uint8_t* desc, int f0, int n, int cap, int W,
-                           int H, const OrbOffsets& offs, hipStream_t s);
 
 // Consumers of the map (sbm_consume.hip): decimation, reprojection, keypoint depth.
 hipError_t launch_disp_to_float(const int16_t* disp, float* out, size_t count, hipStream_t s);
@@ -182,9 +133,6 @@ hipError_t launch_keypoints3d(const int16_t* disp, const float* kp, float* xyz, 
 // Semi-global matcher (sbm_sgbm.hip). Naming follows cv::StereoSGBM (calib3d stereosgbm.cpp): computable columns
 // X = minX1 + x, x in [0, W1); buffer index d <-> disparity minD + d; P1, P2, d12 and uniq are the effective values.
 // C, S, hsum: n * H * W1 * D int16 ([pair][y][x][d]).
-constexpr int kReadSgbmNoMedian = 32;        // SBM_CV_READING: no medianBlur stage
-constexpr int kReadSgbmBottomClamped = 64;   // SBM_CV_READING: rows with y + SH2 >= H (y > 0) sum a clamped window
-constexpr int kSgbmNdMax = 512, kSgbmWMax = 8192;
 struct SgbmGeom {
   int W, H, n;
   int minD, D, minX1, maxX1, W1;
@@ -192,10 +140,5 @@ struct SgbmGeom {
   int fullDP;          // MODE_HH: 8 paths
   int reading;
 };
-hipError_t launch_sgbm_cost(const uint8_t* left, const uint8_t* right, int16_t* hsum, int16_t* C, const SgbmGeom& g, hipStream_t s);
-hipError_t launch_sgbm_paths(const int16_t* C, int16_t* S, const SgbmGeom& g, hipStream_t s);
-hipError_t launch_sgbm_select(const int16_t* S, int16_t* pre, const SgbmGeom& g, hipStream_t s);
-hipError_t launch_sgbm_median(const int16_t* src, int16_t* dst, int n, int W, int H, hipStream_t s);
-hipError_t launch_sgbm_fill(int16_t* dst, size_t count, int v, hipStream_t s);
 
 }  // namespace sbm

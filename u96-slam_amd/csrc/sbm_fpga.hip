@@ -26,7 +26,7 @@
 // pairs strictly top to bottom.
 #include <algorithm>
 
-#include "sbm_common.h"
+#include "sbm_handle.h"
 
 namespace sbm {
 
@@ -447,7 +447,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NPH == 
 
 // xl/xr: dense n*H*W x-Sobel planes on the device. rec: n*sad_hgt*sad_wdt uint2 (used beyond 128 disparities only),
 // flag: n ints, zero when allocated; gen: a number that grows with every call on these buffers (> 0).
-hipError_t launch_fpga_bm(const uint8_t* xl, const uint8_t* xr, void* rec, int* flag, int gen, int16_t* disp, int n,
+static hipError_t launch_fpga_bm(const uint8_t* xl, const uint8_t* xr, void* rec, int* flag, int gen, int16_t* disp, int n,
                           const sbm_fpga_params& p, hipStream_t s) {
   FpgaArgs a;
   const int W = p.width, H = p.height;
@@ -495,3 +495,120 @@ hipError_t launch_fpga_bm(const uint8_t* xl, const uint8_t* xr, void* rec, int* 
 }
 
 }  // namespace sbm
+
+// ---- register decode (bm.v:172-193), limits, entry points ----------------------------------------------------------------
+using namespace sbm;
+
+extern "C" {
+
+int sbm_fpga_params_from_regs(uint32_t image_size, uint32_t bm_setting, uint32_t uni_filt_ctrl, sbm_fpga_params* out) {
+  if (!out) return SBM_ERR_NULL;
+  out->width = (int32_t)(image_size & 0x3ffu);
+  out->height = (int32_t)((image_size >> 16) & 0x1ffu);
+  out->block_size = (int32_t)((bm_setting >> 16) & 0x1fu);
+  out->num_disparities = (int32_t)(bm_setting & 0x1ffu);
+  out->uni_enable = (int32_t)((uni_filt_ctrl >> 31) & 1u);
+  out->uni_mode = (int32_t)((uni_filt_ctrl >> 16) & 1u);
+  out->uni_threshold = (int32_t)(uni_filt_ctrl & 0x3ffu);
+  return SBM_OK;
+}
+
+uint32_t sbm_fpga_sad_size_reg(const sbm_fpga_params* p) {
+  if (!p) return 0;
+  const uint32_t hwsz = ((uint32_t)p->block_size >> 1) & 0xfu;
+  const uint32_t hsad_wdt = ((uint32_t)p->width - (uint32_t)p->num_disparities - 1u) & 0x3ffu;   // bm.v:249
+  const uint32_t sad_wdt = (hsad_wdt - 2u * hwsz) & 0x3ffu;                                        // bm.v:252
+  const uint32_t sad_hgt = ((uint32_t)p->height - 2u * hwsz) & 0x1ffu;                             // bm.v:255
+  return (sad_hgt << 16) | sad_wdt;
+}
+
+int sbm_fpga_params_validate(const sbm_fpga_params* p) {
+  if (!p) return SBM_ERR_NULL;
+  if (p->width <= 0 || p->height <= 0 || p->width > 1023 || p->height > 511) return SBM_ERR_SIZE;
+  if (p->block_size < 3 || p->block_size > 31 || (p->block_size & 1) == 0) return SBM_ERR_BLOCK_SIZE;
+  if (p->num_disparities < 32 || p->num_disparities > 256 || (p->num_disparities & 31)) return SBM_ERR_NUM_DISPARITIES;
+  const int hwsz = p->block_size >> 1;
+  if (p->width - p->num_disparities - 1 - 2 * hwsz < 1 || p->height - 2 * hwsz < 1) return SBM_ERR_SIZE;
+  if (((p->num_disparities + hwsz + 1) & 31) == 0) return SBM_ERR_UNSUPPORTED;
+  return SBM_OK;
+}
+
+static int ensure_fpga(sbm_handle* h, int n, int W, int H, bool need_xs) {
+  auto& f = h->fp;
+  const bool fits = n <= f.n && W == f.W && H == f.H && f.flag.p;
+  if (!fits) {
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    release_set(f);
+    const size_t npix = (size_t)n * W * H;
+    HIPCHK(h, f.rec.grow(npix * 8, h->stream));
+    HIPCHK(h, f.flag.grow((size_t)n * sizeof(int), h->stream));
+    HIPCHK(h, hipMemsetAsync(f.flag.p, 0, (size_t)n * sizeof(int), h->stream));   // generation stamps: 0 = never saturated
+    f.gen = 0;
+    f.n = n; f.W = W; f.H = H;
+  }
+  if (need_xs) {
+    const size_t npix = (size_t)f.n * W * H;
+    HIPCHK(h, f.xs_l.grow(npix + 64, h->stream));
+    HIPCHK(h, f.xs_r.grow(npix + 64, h->stream));
+  }
+  return SBM_OK;
+}
+
+int sbm_fpga_bm_device(sbm_handle* h, int n, const void* d_xsbl_l, const void* d_xsbl_r, const sbm_fpga_params* p,
+                       void* d_disp, int sync) {
+  if (!h || !d_xsbl_l || !d_xsbl_r || !p || !d_disp) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  int st = sbm_fpga_params_validate(p);
+  if (st != SBM_OK) return st;
+  if (n > 65535) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  st = ensure_fpga(h, n, p->width, p->height, false);
+  if (st != SBM_OK) return st;
+  HIPCHK(h, launch_fpga_bm((const uint8_t*)d_xsbl_l, (const uint8_t*)d_xsbl_r, h->fp.rec.p, h->fp.flag.as<int>(), ++h->fp.gen, (int16_t*)d_disp, n, *p,
+                           h->stream));
+  if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+
+int sbm_fpga_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_right, const sbm_fpga_params* p,
+                            void* d_disp, int sync) {
+  if (!h || !d_left || !d_right || !p || !d_disp) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  int st = sbm_fpga_params_validate(p);
+  if (st != SBM_OK) return st;
+  if (n > 65534) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  st = ensure_fpga(h, n, p->width, p->height, true);
+  if (st != SBM_OK) return st;
+  HIPCHK(h, launch_prefilter_dense((const uint8_t*)d_left, h->fp.xs_l.as<uint8_t>(), n, p->width, p->height, 1, 31, h->stream));
+  HIPCHK(h, launch_prefilter_dense((const uint8_t*)d_right, h->fp.xs_r.as<uint8_t>(), n, p->width, p->height, 1, 31, h->stream));
+  HIPCHK(h, launch_fpga_bm(h->fp.xs_l.as<uint8_t>(), h->fp.xs_r.as<uint8_t>(), h->fp.rec.p, h->fp.flag.as<int>(), ++h->fp.gen, (int16_t*)d_disp, n, *p, h->stream));
+  if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+
+// host-memory forms of the PL blocks for one frame: staged through the handle's device staging buffers (2-D copies
+// take care of the caller's strides)
+int sbm_fpga_compute(sbm_handle* h, const uint8_t* left, size_t left_stride, const uint8_t* right, size_t right_stride,
+                     const sbm_fpga_params* p, int16_t* disp, size_t disp_stride) {
+  if (!h || !left || !right || !p || !disp) return SBM_ERR_NULL;
+  int st = sbm_fpga_params_validate(p);
+  if (st != SBM_OK) return st;
+  const int W = p->width, H = p->height;
+  if (left_stride < (size_t)W || right_stride < (size_t)W || disp_stride < (size_t)W * 2) return SBM_ERR_SIZE;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  st = ensure_staging(h, 1, W, H);
+  if (st != SBM_OK) return st;
+  HIPCHK(h, hipMemcpy2DAsync(h->st.l.as<uint8_t>(), W, left, left_stride, W, H, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpy2DAsync(h->st.r.as<uint8_t>(), W, right, right_stride, W, H, hipMemcpyHostToDevice, h->stream));
+  st = sbm_fpga_compute_device(h, 1, h->st.l.as<uint8_t>(), h->st.r.as<uint8_t>(), p, h->st.d.as<int16_t>(), 0);
+  if (st != SBM_OK) return st;
+  HIPCHK(h, hipMemcpy2DAsync(disp, disp_stride, h->st.d.as<int16_t>(), (size_t)W * 2, (size_t)W * 2, H, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+
+}  // extern "C"

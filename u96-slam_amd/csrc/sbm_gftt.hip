@@ -13,7 +13,7 @@
 // through the horizontal 3-sum (two DPP wave shifts + one v_add3_u32 serve both; a 3-sum is at most 3 * 16256 < 2^16) and
 // through the vertical one, where v_pk_add_u16 clamp IS gftt_box.v's 16-bit limiter. Lanes 0 and 63 only serve as
 // neighbours (62 outputs per wavefront).
-#include "sbm_common.h"
+#include "sbm_handle.h"
 
 namespace sbm {
 
@@ -284,3 +284,42 @@ hipError_t launch_gftt_eig(const uint8_t* img, uint16_t* eig, unsigned* maxv, in
 }
 
 }  // namespace sbm
+
+// ---- entry points --------------------------------------------------------------------------------------------------------
+using namespace sbm;
+
+extern "C" {
+
+int sbm_gftt_eig(sbm_handle* h, const uint8_t* img, size_t img_stride, int width, int height, uint16_t* eig, size_t eig_stride,
+                 uint32_t* max_out) {
+  if (!h || !img || !eig) return SBM_ERR_NULL;
+  if (width < 3 || height < 5 || width > 1023 || height > 511) return SBM_ERR_SIZE;
+  if (img_stride < (size_t)width || eig_stride < (size_t)width * 2) return SBM_ERR_SIZE;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  int st = ensure_staging(h, 1, width, height);
+  if (st != SBM_OK) return st;
+  // st.l: image, st.d: map, st.r: the Max word
+  HIPCHK(h, hipMemcpy2DAsync(h->st.l.as<uint8_t>(), width, img, img_stride, width, height, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, launch_gftt_eig(h->st.l.as<uint8_t>(), h->st.d.as<uint16_t>(), h->st.r.as<unsigned>(), 1, width, height, h->stream));
+  HIPCHK(h, hipMemcpy2DAsync(eig, eig_stride, h->st.d.p, (size_t)width * 2, (size_t)width * 2, height, hipMemcpyDeviceToHost, h->stream));
+  uint32_t mx = 0;
+  HIPCHK(h, hipMemcpyAsync(&mx, h->st.r.p, sizeof(mx), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (max_out) *max_out = mx;
+  return SBM_OK;
+}
+
+int sbm_gftt_eig_device(sbm_handle* h, int n, const void* d_img, int width, int height, void* d_eig, void* d_max, int sync) {
+  if (!h || !d_img || !d_eig || !d_max) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  if (width < 3 || height < 5 || width > 1023 || height > 511) return SBM_ERR_SIZE;
+  if (n > 65535) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  HIPCHK(h, launch_gftt_eig((const uint8_t*)d_img, (uint16_t*)d_eig, (unsigned*)d_max, n, width, height, h->stream));
+  if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+
+}  // extern "C"

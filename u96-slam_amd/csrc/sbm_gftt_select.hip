@@ -20,9 +20,33 @@
 #include <math.h>
 #include <string.h>
 
-#include "sbm_common.h"
+#include <algorithm>
+#include <cmath>
+
+#include "sbm_handle.h"
 
 namespace sbm {
+
+// One workgroup per image. The cell table of the minimum-distance trim (16 B per cell, ceil(W/cell) * ceil(H/cell) cells) sits in
+// LDS next to the sort keys when it fits (global_table = false), else in device scratch of table_bytes_per_image per image,
+// zeroed by the launch.
+constexpr size_t kGftSelLds = 160 * 1024;     // LDS of one workgroup
+constexpr int kGftSelKeysMax = 8192;          // keys sorted per value window (64 KiB)
+constexpr int kGftSelWMax = 2048;             // width and height limit: (x, y) pack into 16 bits each, indices into 22 bits
+struct GftSelGeom {
+  int W, H, img0;
+  int cap;                  // points per image slot: max_features > 0 ? max_features : (W - 2) * (H - 2)
+  int trim;                 // min_distance >= 1
+  int cell, gw, gh, lim;    // cvRound(min_distance), grid size, ceil(min_distance^2)
+  int nkeys;                // key capacity of a value window (a power of two)
+  double q;                 // quality_level
+  unsigned long long magic; // floor(2^40 / W) + 1: y = (p * magic) >> 40
+};
+struct GftSelPlan {
+  GftSelGeom g;
+  bool global_table;
+  size_t lds_bytes, table_bytes_per_image;
+};
 
 constexpr int GS_THREADS = 1024, GS_WAVES = GS_THREADS / 64;
 constexpr int GS_FIXED_LDS = 1280;   // hist[256], wave sums[16], scalars[16] (words), rounded to 16 B
@@ -320,7 +344,7 @@ __global__ void __launch_bounds__(GS_THREADS) gftt_select_kernel(const uint16_t*
   if (tid == 0) count[img] = sh->acc;
 }
 
-GftSelPlan gftt_select_plan(int W, int H, int max_features, double quality, double min_distance) {
+static GftSelPlan gftt_select_plan(int W, int H, int max_features, double quality, double min_distance) {
   GftSelPlan pl;
   memset(&pl, 0, sizeof(pl));
   GftSelGeom& g = pl.g;
@@ -352,8 +376,9 @@ GftSelPlan gftt_select_plan(int W, int H, int max_features, double quality, doub
   return pl;
 }
 
-hipError_t launch_gftt_select(const uint16_t* eig, const unsigned* maxv, float* kpts, int* count, unsigned* gtab, const GftSelPlan& pl,
-                              int img0, int n, hipStream_t s) {
+// eig: dense uint16 maps, maxv: their Max words (null: each map's maximum); images [img0, img0 + n) of the batch
+static hipError_t launch_gftt_select(const uint16_t* eig, const unsigned* maxv, float* kpts, int* count, unsigned* gtab, const GftSelPlan& pl,
+                                     int img0, int n, hipStream_t s) {
   GftSelGeom g = pl.g;
   g.img0 = img0;
   if (pl.global_table) {
@@ -372,3 +397,111 @@ hipError_t launch_gftt_select(const uint16_t* eig, const unsigned* maxv, float* 
 }
 
 }  // namespace sbm
+
+// ---- entry points --------------------------------------------------------------------------------------------------------
+using namespace sbm;
+
+extern "C" {
+
+void sbm_gftt_select_params_default(sbm_gftt_select_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->max_features = 1500;
+  p->quality_level = 0.01;
+  p->min_distance = 7.0;
+  p->block_size = 3;
+}
+
+int sbm_gftt_select_params_validate(const sbm_gftt_select_params* p, int width, int height) {
+  if (!p) return SBM_ERR_NULL;
+  if (width < 3 || height < 3) return SBM_ERR_SIZE;
+  if (width > kGftSelWMax || height > kGftSelWMax) return SBM_ERR_UNSUPPORTED;
+  if (!std::isfinite(p->quality_level) || p->quality_level < 0) return SBM_ERR_UNSUPPORTED;
+  if (!std::isfinite(p->min_distance) || p->min_distance < 0 || p->min_distance > 255) return SBM_ERR_UNSUPPORTED;
+  return SBM_OK;
+}
+
+int sbm_gftt_select_device(sbm_handle* h, int n, const void* d_eig, const void* d_max, int width, int height,
+                           const sbm_gftt_select_params* p, void* d_kpts, void* d_count, int sync) {
+  if (!h || !p || !d_eig || !d_kpts || !d_count) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  const int st = sbm_gftt_select_params_validate(p, width, height);
+  if (st != SBM_OK) return st;
+  if (n > 65535) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  return gftt_select_run(h, n, nullptr, d_eig, d_max, width, height, p, d_kpts, d_count, sync);
+}
+
+int sbm_gftt_detect_device(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_select_params* p,
+                           void* d_eig, void* d_max, void* d_kpts, void* d_count, int sync) {
+  if (!h || !p || !d_img || !d_eig || !d_max || !d_kpts || !d_count) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  if (width < 3 || height < 5 || width > 1023 || height > 511) return SBM_ERR_SIZE;   // the eigenvalue map's limits
+  const int st = sbm_gftt_select_params_validate(p, width, height);
+  if (st != SBM_OK) return st;
+  if (n > 65535) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  return gftt_select_run(h, n, d_img, d_eig, d_max, width, height, p, d_kpts, d_count, sync);
+}
+
+int sbm_gftt_select(sbm_handle* h, const uint16_t* eig, size_t eig_stride, int width, int height, uint16_t max_eig,
+                    const sbm_gftt_select_params* p, float* kpts, size_t capacity, int* count) {
+  if (!h || !p || !eig || !kpts || !count) return SBM_ERR_NULL;
+  int st = sbm_gftt_select_params_validate(p, width, height);
+  if (st != SBM_OK) return st;
+  const size_t cap = p->max_features > 0 ? (size_t)p->max_features : (size_t)(width - 2) * (height - 2);
+  if (eig_stride < (size_t)width * 2 || capacity < cap) return SBM_ERR_SIZE;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  st = ensure_staging(h, 1, width, height);
+  if (st != SBM_OK) return st;
+  HIPCHK(h, h->gs.out.grow(cap * 2 * sizeof(float) + 16, h->stream));   // points, then the count
+  // st.d: the map, st.r: the Max word
+  const uint32_t mx = max_eig;
+  HIPCHK(h, hipMemcpy2DAsync(h->st.d.p, (size_t)width * 2, eig, eig_stride, (size_t)width * 2, height, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->st.r.p, &mx, sizeof(mx), hipMemcpyHostToDevice, h->stream));
+  float* d_k = h->gs.out.as<float>();
+  int* d_n = (int*)(d_k + cap * 2);
+  st = gftt_select_run(h, 1, nullptr, h->st.d.p, h->st.r.p, width, height, p, d_k, d_n, 0);
+  if (st != SBM_OK) {
+    hipStreamSynchronize(h->stream);   // `mx` is read by an enqueued copy
+    return st;
+  }
+  int k = 0;
+  HIPCHK(h, hipMemcpyAsync(&k, d_n, sizeof(k), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (k > 0) HIPCHK(h, hipMemcpy(kpts, d_k, (size_t)k * 2 * sizeof(float), hipMemcpyDeviceToHost));
+  *count = k;
+  return SBM_OK;
+}
+
+}  // extern "C"
+
+// Enqueues the eigenvalue maps (d_img given) and the selection of n dense maps; profiling times the two.
+int sbm::gftt_select_run(sbm_handle* h, int n, const void* d_img, const void* d_eig, const void* d_max, int width, int height,
+                         const sbm_gftt_select_params* p, void* d_kpts, void* d_count, int sync) {
+  StageClock& clk = h->gs.clock;   // stages: eig, select, total
+  HIPCHK(h, clk.start(h->profiling != 0));
+  HIPCHK(h, clk.mark(0, h->stream));
+  if (d_img)
+    HIPCHK(h, launch_gftt_eig((const uint8_t*)d_img, (uint16_t*)d_eig, (unsigned*)d_max, n, width, height, h->stream));
+  HIPCHK(h, clk.mark(1, h->stream));
+  const GftSelPlan pl = gftt_select_plan(width, height, p->max_features, p->quality_level, p->min_distance);
+  // the global-table kernel works through the images in chunks whose tables stay within 2 GiB
+  int chunk = n;
+  if (pl.global_table) {
+    chunk = (int)std::min<size_t>(n, std::max<size_t>(1, ((size_t)2 << 30) / pl.table_bytes_per_image));
+    HIPCHK(h, h->gs.tab.grow(pl.table_bytes_per_image * chunk, h->stream));
+  }
+  for (int c0 = 0; c0 < n; c0 += chunk)
+    HIPCHK(h, launch_gftt_select((const uint16_t*)d_eig, (const unsigned*)d_max, (float*)d_kpts, (int*)d_count, h->gs.tab.as<unsigned>(),
+                                 pl, c0, std::min(chunk, n - c0), h->stream));
+  HIPCHK(h, clk.mark(2, h->stream));
+  if (d_img) HIPCHK(h, clk.add(0, 0, 1));
+  HIPCHK(h, clk.add(1, 1, 2));
+  HIPCHK(h, clk.add(2, 0, 2));
+  if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}

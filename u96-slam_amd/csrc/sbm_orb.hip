@@ -9,10 +9,21 @@
 //             half to even (OpenCV's vectorised column filter), or half up with kReadOrbHalfUp.
 //   compact   one workgroup per frame keeps the points with cvRound(x) in [e, W - e) and cvRound(y) in [e, H - e), in order.
 //   describe  eight lanes per kept keypoint, four descriptor bytes per lane; the 512 sample offsets dy * W + dx come from the
-//             host (sbm_api.hip) as a kernel argument and are copied to LDS.
-#include "sbm_common.h"
+//             host (orb_offsets below) as a kernel argument and are copied to LDS.
+#include <algorithm>
+#include <cmath>
+
+#include "sbm_handle.h"
 
 namespace sbm {
+
+// Launches. blur: n dense u8 frames -> n dense u8 frames (W, H >= 4);
+// compact: runByImageBorder per frame (one workgroup each; in place allowed); desc: frames [f0, f0 + n) of the batch, `blur`
+// holding exactly those n frames, 32 bytes per kept keypoint at (f * cap + j) * 32.
+constexpr int kReadOrbHalfUp = 128;   // SBM_CV_READING: the blur's column filter rounds half up instead of half to even
+struct OrbOffsets {
+  int off[512];   // dy * W + dx of the 512 rotated pattern points, in pattern order
+};
 
 namespace {
 
@@ -171,22 +182,186 @@ __global__ void __launch_bounds__(256) orb_desc_kernel(const uint8_t* __restrict
 
 }  // namespace
 
-hipError_t launch_orb_blur(const uint8_t* src, uint8_t* dst, int n, int W, int H, int half_up, hipStream_t s) {
+static hipError_t launch_orb_blur(const uint8_t* src, uint8_t* dst, int n, int W, int H, int half_up, hipStream_t s) {
   const int tx = (W + kBlurTW - 1) / kBlurTW, ty = (H + kBlurTH - 1) / kBlurTH;
   hipLaunchKernelGGL(orb_blur_kernel, dim3(tx * ty, n), dim3(256), 0, s, src, dst, W, H, tx, half_up);
   return hipGetLastError();
 }
 
-hipError_t launch_orb_compact(const float* kin, const int* cin, float* kout, int* cout, int n, int cap, int W, int H, int edge,
-                              hipStream_t s) {
+static hipError_t launch_orb_compact(const float* kin, const int* cin, float* kout, int* cout, int n, int cap, int W, int H, int edge,
+                                     hipStream_t s) {
   hipLaunchKernelGGL(orb_compact_kernel, dim3(n), dim3(256), 0, s, kin, cin, kout, cout, cap, W, H, edge);
   return hipGetLastError();
 }
 
-hipError_t launch_orb_desc(const uint8_t* blur, const float* kpts, const int* count, uint8_t* desc, int f0, int n, int cap, int W,
-                           int H, const OrbOffsets& offs, hipStream_t s) {
+static hipError_t launch_orb_desc(const uint8_t* blur, const float* kpts, const int* count, uint8_t* desc, int f0, int n, int cap, int W,
+                                  int H, const OrbOffsets& offs, hipStream_t s) {
   hipLaunchKernelGGL(orb_desc_kernel, dim3((cap + 31) / 32, n), dim3(256), 0, s, blur, kpts, count, desc, cap, W, H, f0, offs);
   return hipGetLastError();
 }
 
 }  // namespace sbm
+
+// ---- entry points --------------------------------------------------------------------------------------------------------
+using namespace sbm;
+
+extern "C" {
+
+void sbm_orb_params_default(sbm_orb_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->edge_threshold = 19;
+  p->angle = -1.f;
+  p->blur_ksize = 7;
+  p->blur_sigma = 2.0;
+}
+
+int sbm_orb_params_validate(const sbm_orb_params* p) {
+  if (!p) return SBM_ERR_NULL;
+  if (p->edge_threshold < 18 || p->edge_threshold > 4096) return SBM_ERR_UNSUPPORTED;
+  if (!std::isfinite(p->angle)) return SBM_ERR_UNSUPPORTED;
+  if (p->blur_ksize != 7 || p->blur_sigma != 2.0) return SBM_ERR_UNSUPPORTED;
+  return SBM_OK;
+}
+
+// The 512 sample offsets of computeOrbDescriptors' GET_VALUE, as the reference evaluates them: float products and differences
+// without contraction (hipcc contracts by default), cvRound half to even.
+static int orb_offsets(const int* pattern, float angle_deg, int W, OrbOffsets* o) {
+#pragma clang fp contract(off)
+  for (int i = 0; i < 1024; i++)
+    if (pattern[i] < -13 || pattern[i] > 13) return SBM_ERR_UNSUPPORTED;
+  const float angle = angle_deg * (float)(3.14159265358979323846 / 180.f);
+  const float a = (float)cos((double)angle), b = (float)sin((double)angle);
+  for (int i = 0; i < 512; i++) {
+    const float px = (float)pattern[2 * i], py = (float)pattern[2 * i + 1];
+    const float x = px * a - py * b, y = px * b + py * a;
+    o->off[i] = (int)std::nearbyint(y) * W + (int)std::nearbyint(x);
+  }
+  return SBM_OK;
+}
+
+static int orb_check(int n, int width, int height, int cap, const void* d_kpts, const void* d_kpts_out, const void* d_desc) {
+  if (n <= 0) return SBM_ERR_BATCH;
+  if (width < 1 || height < 1 || width > 8192 || height > 8192 || cap < 1) return SBM_ERR_SIZE;
+  if (n > 65535) return SBM_ERR_UNSUPPORTED;
+  if (((uintptr_t)d_kpts & 7) || ((uintptr_t)d_kpts_out & 7) || ((uintptr_t)d_desc & 3)) return SBM_ERR_UNSUPPORTED;
+  return SBM_OK;
+}
+
+// Enqueues compaction, blur and descriptors; profiling times them, the compaction as part of the descriptors.
+static int orb_run(sbm_handle* h, int n, const void* d_img, int width, int height, int cap, const void* d_kpts, const void* d_count,
+                   const OrbOffsets& offs, const sbm_orb_params* p, void* d_kpts_out, void* d_count_out, void* d_desc,
+                   void* d_blur, int sync) {
+  StageClock& clk = h->orb.clock;   // stages: blur, desc, total
+  HIPCHK(h, clk.start(h->profiling != 0));
+  const int edge = p->edge_threshold;
+  HIPCHK(h, clk.mark(0, h->stream));
+  HIPCHK(h, launch_orb_compact((const float*)d_kpts, (const int*)d_count, (float*)d_kpts_out, (int*)d_count_out, n, cap, width,
+                               height, edge, h->stream));
+  HIPCHK(h, clk.mark(1, h->stream));
+  HIPCHK(h, clk.add(1, 0, 1));
+  if (width > 2 * edge && height > 2 * edge) {   // else every keypoint is gone and nothing needs the blur
+    const int reading = env_switch("SBM_CV_READING", 0);
+    const size_t plane = (size_t)width * height;
+    int chunk = n;
+    if (!d_blur) {
+      chunk = (int)std::min<size_t>(n, std::max<size_t>(1, ((size_t)256 << 20) / plane));
+      HIPCHK(h, h->orb.blur.grow(plane * chunk, h->stream));
+    }
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+      const int m = std::min(chunk, n - c0);
+      uint8_t* bc = d_blur ? (uint8_t*)d_blur + plane * c0 : h->orb.blur.as<uint8_t>();
+      HIPCHK(h, clk.mark(0, h->stream));
+      HIPCHK(h, launch_orb_blur((const uint8_t*)d_img + plane * c0, bc, m, width, height, (reading & kReadOrbHalfUp) ? 1 : 0,
+                                h->stream));
+      HIPCHK(h, clk.mark(1, h->stream));
+      HIPCHK(h, launch_orb_desc(bc, (const float*)d_kpts_out, (const int*)d_count_out, (uint8_t*)d_desc, c0, m, cap, width, height,
+                                offs, h->stream));
+      HIPCHK(h, clk.mark(2, h->stream));
+      HIPCHK(h, clk.add(0, 0, 1));
+      HIPCHK(h, clk.add(1, 1, 2));
+    }
+  }
+  if (clk.on) clk.ms[2] = clk.ms[0] + clk.ms[1];
+  if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+
+int sbm_orb_describe_device(sbm_handle* h, int n, const void* d_img, int width, int height, int cap, const void* d_kpts,
+                            const void* d_count, const int* pattern, const sbm_orb_params* p, void* d_kpts_out, void* d_count_out,
+                            void* d_desc, void* d_blur, int sync) {
+  if (!h || !d_img || !d_kpts || !d_count || !pattern || !p || !d_kpts_out || !d_count_out || !d_desc) return SBM_ERR_NULL;
+  int st = sbm_orb_params_validate(p);
+  if (st == SBM_OK) st = orb_check(n, width, height, cap, d_kpts, d_kpts_out, d_desc);
+  if (st != SBM_OK) return st;
+  OrbOffsets offs;
+  st = orb_offsets(pattern, p->angle, width, &offs);
+  if (st != SBM_OK) return st;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  return orb_run(h, n, d_img, width, height, cap, d_kpts, d_count, offs, p, d_kpts_out, d_count_out, d_desc, d_blur, sync);
+}
+
+int sbm_orb_features_device(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_select_params* gp,
+                            const int* pattern, const sbm_orb_params* p, void* d_eig, void* d_max, void* d_kpts, void* d_count,
+                            void* d_desc, void* d_blur, int sync) {
+  if (!h || !gp || !d_img || !d_eig || !d_max || !d_kpts || !d_count || !pattern || !p || !d_desc) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  if (width < 3 || height < 5 || width > 1023 || height > 511) return SBM_ERR_SIZE;   // the eigenvalue map's limits
+  int st = sbm_gftt_select_params_validate(gp, width, height);
+  if (st == SBM_OK) st = sbm_orb_params_validate(p);
+  const int cap = gp->max_features > 0 ? gp->max_features : (width - 2) * (height - 2);
+  if (st == SBM_OK) st = orb_check(n, width, height, cap, d_kpts, d_kpts, d_desc);
+  if (st != SBM_OK) return st;
+  OrbOffsets offs;
+  st = orb_offsets(pattern, p->angle, width, &offs);
+  if (st != SBM_OK) return st;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  st = gftt_select_run(h, n, d_img, d_eig, d_max, width, height, gp, d_kpts, d_count, 0);
+  if (st != SBM_OK) return st;
+  return orb_run(h, n, d_img, width, height, cap, d_kpts, d_count, offs, p, d_kpts, d_count, d_desc, d_blur, sync);
+}
+
+int sbm_orb_describe(sbm_handle* h, const uint8_t* img, size_t img_stride, int width, int height, const float* kpts, int count,
+                     const int* pattern, const sbm_orb_params* p, float* kpts_out, int* count_out, uint8_t* desc) {
+  if (!h || !img || !pattern || !p || !count_out || (count > 0 && (!kpts || !kpts_out || !desc))) return SBM_ERR_NULL;
+  if (count < 0 || img_stride < (size_t)width) return SBM_ERR_SIZE;
+  const int cap = std::max(count, 1);
+  int st = sbm_orb_params_validate(p);
+  if (st == SBM_OK) st = orb_check(1, width, height, cap, nullptr, nullptr, nullptr);
+  if (st != SBM_OK) return st;
+  OrbOffsets offs;
+  st = orb_offsets(pattern, p->angle, width, &offs);
+  if (st != SBM_OK) return st;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  st = ensure_staging(h, 1, width, height);
+  if (st != SBM_OK) return st;
+  const size_t kb = (size_t)cap * 8, out_bytes = 2 * kb + (size_t)cap * 32 + 16;   // points in, points out, descriptors, counts
+  HIPCHK(h, h->orb.io.grow(out_bytes, h->stream));
+  char* io = h->orb.io.as<char>();
+  float* d_ki = (float*)io;
+  float* d_ko = (float*)(io + kb);
+  uint8_t* d_de = (uint8_t*)(io + 2 * kb);
+  int* d_n = (int*)(io + 2 * kb + (size_t)cap * 32);
+  HIPCHK(h, hipMemcpy2DAsync(h->st.l.p, width, img, img_stride, width, height, hipMemcpyHostToDevice, h->stream));
+  if (count > 0) HIPCHK(h, hipMemcpyAsync(d_ki, kpts, (size_t)count * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_n, &count, sizeof(int), hipMemcpyHostToDevice, h->stream));
+  st = orb_run(h, 1, h->st.l.p, width, height, cap, d_ki, d_n, offs, p, d_ko, d_n + 1, d_de, nullptr, 0);
+  if (st != SBM_OK) {
+    hipStreamSynchronize(h->stream);   // `count` is read by an enqueued copy
+    return st;
+  }
+  int k = 0;
+  HIPCHK(h, hipMemcpyAsync(&k, d_n + 1, sizeof(k), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (k > 0) {
+    HIPCHK(h, hipMemcpy(kpts_out, d_ko, (size_t)k * 8, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(desc, d_de, (size_t)k * 32, hipMemcpyDeviceToHost));
+  }
+  *count_out = k;
+  return SBM_OK;
+}
+
+}  // extern "C"

@@ -16,9 +16,13 @@
 // The speckle filter is the block matcher's (launch_speckle).
 #include <algorithm>
 
-#include "sbm_common.h"
+#include "sbm_handle.h"
 
 namespace sbm {
+
+constexpr int kReadSgbmNoMedian = 32;        // SBM_CV_READING: no medianBlur stage
+constexpr int kReadSgbmBottomClamped = 64;   // SBM_CV_READING: rows with y + SH2 >= H (y > 0) sum a clamped window
+constexpr int kSgbmNdMax = 512, kSgbmWMax = 8192;
 
 namespace {
 
@@ -309,14 +313,14 @@ hipError_t with_nv(int D, F f) {
 
 }  // namespace
 
-hipError_t launch_sgbm_cost(const uint8_t* left, const uint8_t* right, int16_t* hsum, int16_t* C, const SgbmGeom& g, hipStream_t s) {
+static hipError_t launch_sgbm_cost(const uint8_t* left, const uint8_t* right, int16_t* hsum, int16_t* C, const SgbmGeom& g, hipStream_t s) {
   hipLaunchKernelGGL(sgbm_hsum_kernel, dim3(g.H, g.n), dim3(256), (size_t)4 * g.W, s, left, right, hsum, g);
   const int plane = g.W1 * g.D;
   hipLaunchKernelGGL(sgbm_vsum_kernel, dim3((plane + 255) / 256, g.n), dim3(256), 0, s, hsum, C, g);
   return hipGetLastError();
 }
 
-hipError_t launch_sgbm_paths(const int16_t* C, int16_t* S, const SgbmGeom& g, hipStream_t s) {
+static hipError_t launch_sgbm_paths(const int16_t* C, int16_t* S, const SgbmGeom& g, hipStream_t s) {
   // the pass-1 directions of OpenCV's sweep, then pass 2 (MODE_HH) or the fifth path (MODE_SGBM)
   static const int kDirs[8][2] = {{1, 0}, {1, 1}, {0, 1}, {-1, 1}, {-1, 0}, {-1, -1}, {0, -1}, {1, -1}};
   const int ndir = g.fullDP ? 8 : 5;
@@ -334,7 +338,7 @@ hipError_t launch_sgbm_paths(const int16_t* C, int16_t* S, const SgbmGeom& g, hi
   return hipSuccess;
 }
 
-hipError_t launch_sgbm_select(const int16_t* S, int16_t* pre, const SgbmGeom& g, hipStream_t s) {
+static hipError_t launch_sgbm_select(const int16_t* S, int16_t* pre, const SgbmGeom& g, hipStream_t s) {
   return with_nv(g.D, [&](auto nv) {
     constexpr int NV = decltype(nv)::value;
     hipLaunchKernelGGL(sgbm_select_kernel<NV>, dim3(g.H, g.n), dim3(256), (size_t)6 * g.W, s, S, pre, g);
@@ -342,15 +346,181 @@ hipError_t launch_sgbm_select(const int16_t* S, int16_t* pre, const SgbmGeom& g,
   });
 }
 
-hipError_t launch_sgbm_median(const int16_t* src, int16_t* dst, int n, int W, int H, hipStream_t s) {
+static hipError_t launch_sgbm_median(const int16_t* src, int16_t* dst, int n, int W, int H, hipStream_t s) {
   hipLaunchKernelGGL(sgbm_median_kernel, dim3((W + 255) / 256, H, n), dim3(256), 0, s, src, dst, W, H);
   return hipGetLastError();
 }
 
-hipError_t launch_sgbm_fill(int16_t* dst, size_t count, int v, hipStream_t s) {
+static hipError_t launch_sgbm_fill(int16_t* dst, size_t count, int v, hipStream_t s) {
   const size_t blocks = std::min<size_t>((count + 255) / 256, 65535);
   hipLaunchKernelGGL(sgbm_fill_kernel, dim3((unsigned)std::max<size_t>(blocks, 1)), dim3(256), 0, s, dst, count, v);
   return hipGetLastError();
 }
 
 }  // namespace sbm
+
+// ---- entry points --------------------------------------------------------------------------------------------------------
+using namespace sbm;
+
+extern "C" {
+
+void sbm_sgbm_params_default(sbm_sgbm_params* p, int min_disparity, int num_disparities, int block_size) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->min_disparity = min_disparity;
+  p->num_disparities = num_disparities;
+  p->block_size = block_size;
+  p->mode = SBM_SGBM_MODE_SGBM;
+}
+
+static void sgbm_effective(const sbm_sgbm_params& p, int& bs, int& ftzero, int& P1, int& P2) {
+  bs = 2 * ((p.block_size > 0 ? p.block_size : 5) / 2) + 1;
+  ftzero = std::max(p.prefilter_cap, 15) | 1;
+  P1 = p.p1 > 0 ? p.p1 : 2;
+  P2 = std::max(p.p2 > 0 ? p.p2 : 5, P1 + 1);
+}
+
+int sbm_sgbm_params_validate(const sbm_sgbm_params* p, int width, int height) {
+  if (!p) return SBM_ERR_NULL;
+  if (width <= 0 || height <= 0) return SBM_ERR_SIZE;
+  if (p->num_disparities <= 0 || p->num_disparities % 16 != 0) return SBM_ERR_NUM_DISPARITIES;
+  if (p->mode != SBM_SGBM_MODE_SGBM && p->mode != SBM_SGBM_MODE_HH) return SBM_ERR_UNSUPPORTED;
+  if (p->num_disparities > kSgbmNdMax || width > kSgbmWMax || height > 65535 || p->prefilter_cap > 63 ||
+      p->uniqueness_ratio > 65535 || (p->speckle_window_size > 0 && p->speckle_range < 0))
+    return SBM_ERR_UNSUPPORTED;
+  // (every disparity * 16 of the map, (minDisparity - 1) * 16 included, must fit int16)
+  if (p->min_disparity < -2047 || (long)p->min_disparity + p->num_disparities > 2047) return SBM_ERR_UNSUPPORTED;
+  int bs, ftzero, P1, P2;
+  sgbm_effective(*p, bs, ftzero, P1, P2);
+  if ((long)bs * bs * (2 * ftzero + 63) + P2 > 32767) return SBM_ERR_UNSUPPORTED;   // the exactness envelope
+  return SBM_OK;
+}
+
+// Device scratch of one chunk of pairs -- C, S, the map before the median and (speckle filter on) its scratch -- stays within
+// kSgbmChunkBytes; a single pair larger than that runs alone.
+static constexpr size_t kSgbmChunkBytes = (size_t)2 << 30;
+
+int sbm_sgbm_compute_device(sbm_handle* h, const sbm_sgbm_params* p, int n, const void* d_left, const void* d_right, int width,
+                            int height, void* d_disp, int sync) {
+  if (!h || !p || !d_left || !d_right || !d_disp) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  int st = sbm_sgbm_params_validate(p, width, height);
+  if (st != SBM_OK) return st;
+  if (n > 32767) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+
+  SgbmGeom g;
+  memset(&g, 0, sizeof(g));
+  int bs, ftzero, P1, P2;
+  sgbm_effective(*p, bs, ftzero, P1, P2);
+  g.W = width; g.H = height;
+  g.minD = p->min_disparity; g.D = p->num_disparities;
+  g.minX1 = std::max(g.minD + g.D, 0); g.maxX1 = width + std::min(g.minD, 0); g.W1 = g.maxX1 - g.minX1;
+  g.SW2 = bs / 2; g.P1 = P1; g.P2 = P2; g.ftzero = ftzero;
+  g.uniq = p->uniqueness_ratio >= 0 ? p->uniqueness_ratio : 10;
+  g.d12 = p->disp12_max_diff > 0 ? p->disp12_max_diff : 1;
+  g.fullDP = p->mode == SBM_SGBM_MODE_HH;
+  g.reading = env_switch("SBM_CV_READING", 0);
+  const bool speckle = p->speckle_window_size > 0;
+  const size_t npix = (size_t)width * height;
+  const size_t pair_cs = g.W1 >= 1 ? (size_t)g.W1 * height * g.D * sizeof(int16_t) : 0;
+  const size_t pair_bytes = 2 * pair_cs + npix * sizeof(int16_t) + (speckle ? SpeckleScratch::bytes(1, width, height, nullptr) : 0);
+  const int chunk = (int)std::min<size_t>(n, std::max<size_t>(1, kSgbmChunkBytes / pair_bytes));
+  auto& sgs = h->sg;
+  HIPCHK(h, sgs.C.grow(pair_cs * chunk, h->stream));
+  HIPCHK(h, sgs.S.grow(pair_cs * chunk, h->stream));
+  HIPCHK(h, sgs.pre.grow((size_t)chunk * npix * sizeof(int16_t), h->stream));
+  if (speckle) HIPCHK(h, sgs.spk.ensure(chunk, width, height, h->stream));
+  g.n = n;
+  sgs.last = g;
+  sgs.have_last = true;
+  sgs.last_one_chunk = chunk == n;
+  int16_t *C = sgs.C.as<int16_t>(), *S = sgs.S.as<int16_t>(), *pre = sgs.pre.as<int16_t>();
+
+  StageClock& clk = sgs.clock;   // stages: cost, aggregate, select, median, speckle, total
+  HIPCHK(h, clk.start(h->profiling != 0));
+  const uint8_t* dl = (const uint8_t*)d_left;
+  const uint8_t* dr = (const uint8_t*)d_right;
+  const int inv = (g.minD - 1) * 16;
+  const int max_diff = (int)std::min<long>(16L * p->speckle_range, 1L << 17);
+  // every stage, the median and the speckle filter included, runs chunk by chunk
+  for (int c0 = 0; c0 < n; c0 += chunk) {
+    SgbmGeom gc = g;
+    gc.n = std::min(chunk, n - c0);
+    int16_t* out = (int16_t*)d_disp + (size_t)c0 * npix;
+    HIPCHK(h, clk.mark(0, h->stream));
+    if (pair_cs) {
+      HIPCHK(h, launch_sgbm_cost(dl + (size_t)c0 * npix, dr + (size_t)c0 * npix, S, C, gc, h->stream));
+      HIPCHK(h, clk.mark(1, h->stream));
+      HIPCHK(h, launch_sgbm_paths(C, S, gc, h->stream));
+      HIPCHK(h, clk.mark(2, h->stream));
+      HIPCHK(h, launch_sgbm_select(S, pre, gc, h->stream));
+    } else {   // no computable column: every pixel is invalid (the median and the speckle filter keep it so)
+      HIPCHK(h, clk.mark(1, h->stream));
+      HIPCHK(h, clk.mark(2, h->stream));
+      HIPCHK(h, launch_sgbm_fill(pre, (size_t)gc.n * npix, inv, h->stream));
+    }
+    HIPCHK(h, clk.mark(3, h->stream));
+    if (g.reading & kReadSgbmNoMedian)
+      HIPCHK(h, hipMemcpyAsync(out, pre, (size_t)gc.n * npix * sizeof(int16_t), hipMemcpyDeviceToDevice, h->stream));
+    else
+      HIPCHK(h, launch_sgbm_median(pre, out, gc.n, width, height, h->stream));
+    HIPCHK(h, clk.mark(4, h->stream));
+    if (speckle) {
+      // the block matcher's filter, with cv::StereoSGBM's arguments: newVal = (minD - 1) * 16, maxDiff = 16 * speckleRange (the
+      // block matcher's own x16 reading bit does not apply here)
+      Geom sg;
+      memset(&sg, 0, sizeof(sg));
+      sg.W = width; sg.H = height; sg.n = gc.n; sg.filtered = inv; sg.reading = 0;
+      HIPCHK(h, launch_speckle(out, sgs.spk, sg, p->speckle_window_size, max_diff, h->stream));
+    }
+    HIPCHK(h, clk.mark(5, h->stream));
+    for (int i = 0; i < 5; i++) HIPCHK(h, clk.add(i, i, i + 1));
+    HIPCHK(h, clk.add(5, 0, 5));
+  }
+  if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+
+int sbm_sgbm_compute(sbm_handle* h, const sbm_sgbm_params* p, const uint8_t* left, size_t left_stride, const uint8_t* right,
+                     size_t right_stride, int width, int height, int16_t* disp, size_t disp_stride) {
+  if (!h || !p || !left || !right || !disp) return SBM_ERR_NULL;
+  int st = sbm_sgbm_params_validate(p, width, height);
+  if (st != SBM_OK) return st;
+  if (left_stride < (size_t)width || right_stride < (size_t)width || disp_stride < (size_t)width * 2) return SBM_ERR_SIZE;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  st = ensure_staging(h, 1, width, height);
+  if (st != SBM_OK) return st;
+  HIPCHK(h, hipMemcpy2DAsync(h->st.l.as<uint8_t>(), width, left, left_stride, width, height, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpy2DAsync(h->st.r.as<uint8_t>(), width, right, right_stride, width, height, hipMemcpyHostToDevice, h->stream));
+  st = sbm_sgbm_compute_device(h, p, 1, h->st.l.as<uint8_t>(), h->st.r.as<uint8_t>(), width, height, h->st.d.as<int16_t>(), 0);
+  if (st != SBM_OK) return st;
+  HIPCHK(h, hipMemcpy2DAsync(disp, disp_stride, h->st.d.as<int16_t>(), (size_t)width * 2, (size_t)width * 2, height, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+
+}  // extern "C"
+
+// sbm_debug_fetch of the last call: which = 4 (C), 5 (S), 6 (the map before the median); one chunk only
+int sbm::sgbm_debug_fetch(sbm_handle* h, int which, void* dst, size_t dst_bytes) {
+  if (!h->sg.have_last) return SBM_ERR_UNSUPPORTED;
+  const SgbmGeom& g = h->sg.last;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (!h->sg.last_one_chunk) return SBM_ERR_UNSUPPORTED;
+  if (which == 6) {
+    const size_t bytes = (size_t)g.n * g.W * g.H * sizeof(int16_t);
+    if (dst_bytes < bytes) return SBM_ERR_SIZE;
+    HIPCHK(h, hipMemcpy(dst, h->sg.pre.p, bytes, hipMemcpyDeviceToHost));
+    return SBM_OK;
+  }
+  if (g.W1 < 1) return SBM_ERR_UNSUPPORTED;
+  const size_t bytes = (size_t)g.n * g.H * g.W1 * g.D * sizeof(int16_t);
+  if (dst_bytes < bytes) return SBM_ERR_SIZE;
+  HIPCHK(h, hipMemcpy(dst, which == 4 ? h->sg.C.p : h->sg.S.p, bytes, hipMemcpyDeviceToHost));
+  return SBM_OK;
+}

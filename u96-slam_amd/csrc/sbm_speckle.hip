@@ -7,7 +7,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "sbm_common.h"
+#include "sbm_handle.h"
 
 namespace sbm {
 
@@ -911,8 +911,24 @@ __global__ void __launch_bounds__(256) speckle_apply_list_kernel(int16_t* __rest
   }
 }
 
-hipError_t launch_speckle(int16_t* disp, void* runs, int32_t* nheads, uint32_t* seam, int32_t* nseam, const Geom& g, int max_size,
-                          int max_diff, hipStream_t s) {
+// The band walk cuts a row into up to kSpkMaxSeg column segments with books of their own, hence the padding. runs: 16 bytes per
+// pixel plus kSpkRecordPad per row (run records of the band walk, or the per-pixel labels + sizes of the row-walking kernels);
+// nheads: kSpkMaxSeg int32 per row (runs per row and segment); seam: W + kSpkSeamPad uint32 per pair of rows, nseam: kSpkMaxSeg
+// int32 per pair of rows (contacts across band seams).
+size_t SpeckleScratch::bytes(int n, int W, int H, size_t* part) {
+  const size_t rows = (size_t)n * H, seams = (size_t)n * ((H + 1) / 2);
+  const size_t b[4] = {rows * ((size_t)W + kSpkRecordPad) * 16, rows * kSpkMaxSeg * sizeof(int32_t),
+                       seams * ((size_t)W + kSpkSeamPad) * sizeof(uint32_t), seams * kSpkMaxSeg * sizeof(int32_t)};
+  if (part)
+    for (int i = 0; i < 4; i++) part[i] = b[i];
+  return b[0] + b[1] + b[2] + b[3];
+}
+
+hipError_t launch_speckle(int16_t* disp, const SpeckleScratch& sc, const Geom& g, int max_size, int max_diff, hipStream_t s) {
+  void* runs = sc.runs.p;
+  int32_t* nheads = sc.nheads.as<int32_t>();
+  uint32_t* seam = sc.seam.as<uint32_t>();
+  int32_t* nseam = sc.nseam.as<int32_t>();
   dim3 grid((g.H + 3) / 4, g.n);
   if (g.reading & kReadSpeckleX16) max_diff = (int)std::min<long>((long)max_diff * 16, 1L << 17);
   max_diff = std::min(max_diff, 1 << 17);   // int16 values: any larger range joins everything alike
