@@ -10,7 +10,7 @@ OBJS := $(SRCS:.hip=.o)
 
 all: $(LIB) oracle oracle_sgbm oracle_gftt oracle_orb
 
-FAST_HDRS := $(CSRC)/sbm_sad_fast_core.h $(CSRC)/sbm_sad_fast_strip.h $(CSRC)/sbm_sad_fast_kernel.h $(CSRC)/sbm_sad_fast_dev.h $(CSRC)/sbm_sad_border_wave.h
+FAST_HDRS := $(CSRC)/sbm_sad_fast_core.h $(CSRC)/sbm_sad_fast_strip.h $(CSRC)/sbm_sad_fast_kernel.h $(CSRC)/sbm_sad_border_wave.h
 $(CSRC)/sbm_sad_fast.o $(CSRC)/sbm_sad_fast_pw1.o $(CSRC)/sbm_sad_fast_pw2.o $(CSRC)/sbm_sad_fast_pw3.o: $(FAST_HDRS)
 
 $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/sbm_common.h $(CSRC)/sbm_handle.h include/sbm.h

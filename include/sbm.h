@@ -82,12 +82,8 @@
  *                                          reading a given OpenCV implements -- adopting it is a default flip here, not a rewrite;
  *                                          bits 32 and 64 belong to the semi-global matcher (see sbm_sgbm_params below),
  *                                          bit 128 to the ORB descriptor's blur (see sbm_orb_params below)
- * Tuning knobs of the measurement scripts (SBM_FAST_NSEG, SBM_FAST_TAPER, SBM_FAST_UNIQ_PLAIN,
- * SBM_FAST_SPLIT, SBM_PF_ROWS, SBM_HOST_CHUNK, SBM_HOST_PIPELINE, SBM_DEV_*; the interior kernel's are listed in
- * u96-slam_amd/csrc/sbm_sad_fast_dev.h) exist only in development builds (-DSBM_DEV, tools/exp/r05_devlib.sh); this library
- * ignores them. The Python mirror adds SBM_LIB_AB (file name of another build of this
- * library inside u96-slam_amd/lib/, A-B measurements only); bench.py reads SBM_BENCH_BACKEND / SBM_BENCH_FEED /
- * SBM_BENCH_SG_FAULT (tests of its multi-process control flow).
+ * The Python mirror adds SBM_LIB_AB (file name of another build of this library inside u96-slam_amd/lib/, A-B measurements
+ * only); bench.py reads SBM_BENCH_BACKEND / SBM_BENCH_FEED / SBM_BENCH_SG_FAULT (tests of its multi-process control flow).
  */
 #ifndef SBM_H_
 #define SBM_H_

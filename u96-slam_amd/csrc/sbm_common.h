@@ -10,22 +10,13 @@
 namespace sbm {
 
 // Environment switches of the library -- the complete list, documented for integrators in include/sbm.h ("Environment").
-//   env_switch(): read in every build. They select a tested fallback or a code path that the GPU tests compare with the
-//                 default one: SBM_FAST_INPLACE (0: the sliding-sum kernel in place of the interior one), SBM_FAST_PFSHIFT,
-//                 SBM_FAST_CS3, SBM_SPECKLE_LISTS, SBM_SPECKLE_BAND, SBM_SPECKLE_SEG, SBM_HOST_ZEROCOPY, SBM_WIDE, SBM_CV_READING.
-//   SBM_TUNE():   tuning knobs behind the sweeps of tools/exp (SBM_FAST_NSEG, SBM_FAST_TAPER,
-//                 SBM_FAST_UNIQ_PLAIN, SBM_FAST_SPLIT, SBM_PF_ROWS, SBM_HOST_CHUNK, SBM_HOST_PIPELINE, SBM_DEV_*): compiled in
-//                 only with -DSBM_DEV (the development library of tools/exp/r05_devlib.sh; sbm_sad_fast_dev.h lists the interior
-//                 kernel's); the product ignores them.
+// They select a tested fallback or a code path that the GPU tests compare with the default one: SBM_FAST_INPLACE (0: the
+// sliding-sum kernel in place of the interior one), SBM_FAST_PFSHIFT, SBM_FAST_CS3, SBM_SPECKLE_LISTS, SBM_SPECKLE_BAND,
+// SBM_SPECKLE_SEG, SBM_HOST_ZEROCOPY, SBM_WIDE, SBM_CV_READING.
 inline int env_switch(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
 }
-#ifdef SBM_DEV
-#define SBM_TUNE(name, dflt) ::sbm::env_switch(name, dflt)
-#else
-#define SBM_TUNE(name, dflt) (dflt)
-#endif
 
 // Geometry of one launch, derived on the host from sbm_params and the image size. Naming follows
 // cv::StereoBM (calib3d stereobm.cpp): lofs/rofs/width1, buffer index d <-> true disparity nd-1-d+mindisp.

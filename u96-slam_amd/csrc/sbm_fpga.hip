@@ -129,11 +129,9 @@ __device__ __forceinline__ u32 pk_max(u32 a, u32 b) {
 // writes UniFiltCtrl) -- the second minimum of bm_calc_det.v / bm_calc_upd.v then feeds nothing: the search is a plain first
 // minimum, the merge across phases "strictly smaller wins", and the sub-pixel fraction (nine divider steps) is taken once per
 // pixel, for the final winner, from its two neighbour sums carried along.
-#ifndef SBM_FPGA_WPE2   // wavefronts per SIMD the register allocation of the two-phase kernel aims at (development builds compare)
-#define SBM_FPGA_WPE2 3
-#endif
+constexpr int kFpgaWpe2 = 3;   // wavefronts per SIMD the register allocation of the two-phase kernel aims at
 template <int NPH, bool LEAN>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NPH == 1 ? 4 : (NPH == 2 ? SBM_FPGA_WPE2 : 1)))) fpga_bm_kernel(FpgaArgs a) {
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NPH == 1 ? 4 : (NPH == 2 ? kFpgaWpe2 : 1)))) fpga_bm_kernel(FpgaArgs a) {
   const int lane = threadIdx.x;
   const int pair = blockIdx.z;
   if (a.exact && a.flag[pair] != a.gen) return;

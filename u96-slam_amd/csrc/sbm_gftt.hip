@@ -271,7 +271,7 @@ hipError_t launch_gftt_eig(const uint8_t* img, uint16_t* eig, unsigned* maxv, in
   hipError_t e = hipMemsetAsync(maxv, 0, (size_t)n * sizeof(unsigned), s);
   if (e != hipSuccess) return e;
   // rows per wavefront: every segment re-reads 4 rows; long segments once the batch fills the chip anyway
-  const bool two = W >= 8 && !SBM_TUNE("SBM_DEV_GFTT_ONE", 0);
+  const bool two = W >= 8;
   const int nv = two ? GF2_NV : GF_NV;
   const int strips = (W + nv - 1) / nv;
   int seg = 64;

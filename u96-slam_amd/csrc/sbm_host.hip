@@ -12,30 +12,6 @@
 
 using namespace sbm;
 
-#ifdef SBM_DEV   // development builds: wall-clock stamps of the host-buffer entry point's phases (tools/exp/r05_host_attrib.py)
-static double g_hp_acc[8];
-static unsigned long long g_hp_calls;
-struct HostProf {
-  std::chrono::steady_clock::time_point t;
-  HostProf() : t(std::chrono::steady_clock::now()) {}
-  void stamp(int i) {
-    const auto n = std::chrono::steady_clock::now();
-    g_hp_acc[i] += std::chrono::duration<double, std::micro>(n - t).count();
-    t = n;
-  }
-};
-#define HP_BEGIN() HostProf hp_; g_hp_calls++
-#define HP(i) hp_.stamp(i)
-extern "C" int sbm_dev_host_prof(double* out8, unsigned long long* calls) {
-  for (int i = 0; i < 8; i++) { out8[i] = g_hp_acc[i]; g_hp_acc[i] = 0; }
-  *calls = g_hp_calls; g_hp_calls = 0;
-  return 0;
-}
-#else
-#define HP_BEGIN() do { } while (0)
-#define HP(i) do { } while (0)
-#endif
-
 static inline void cpu_relax() {
 #if defined(__x86_64__) || defined(__i386__)
   __builtin_ia32_pause();
@@ -108,15 +84,12 @@ static int pipelined_enqueue(sbm_handle* h, int n, const uint8_t* const* left, c
   // Chunk plan. Small chunks overlap more of the transfers but run the kernels on part-filled launches (8 KITTI pairs cost
   // 0.36 ms on the device, 64 pairs 1.2 ms), so: a small FIRST chunk (the computation starts after one short transfer), a
   // small LAST one (only its computation and its maps are left when the inputs have arrived) and large ones in between.
-  // Measured on 64 KITTI pairs from pinned memory (profiles/r03_host_feed.json). SBM_HOST_CHUNK=<pairs>: uniform chunks.
-  static const int chunk_env = SBM_TUNE("SBM_HOST_CHUNK", 0);
+  // Measured on 64 KITTI pairs from pinned memory (profiles/r03_host_feed.json). Fewer than 32 pairs: chunks of 8.
   int start[sbm_handle::kChunks + 1];
   int nch = 0;
   start[0] = 0;
-  if (chunk_env > 0 || n < 32) {
-    int chunk = chunk_env > 0 ? chunk_env : 8;
-    while ((n + chunk - 1) / chunk > sbm_handle::kChunks) chunk *= 2;
-    for (int i = 0; i < n; i += chunk) start[++nch] = std::min(n, i + chunk);
+  if (n < 32) {
+    for (int i = 0; i < n; i += 8) start[++nch] = std::min(n, i + 8);
   } else {
     const int edge = 8, mid = n - 2 * edge;
     int nmid = std::max(1, (mid + 23) / 24);                     // middle chunks of at most 24 pairs
@@ -409,12 +382,10 @@ int sbm_compute_batch(sbm_handle* h, int n, const uint8_t* const* left, size_t l
   if (left_stride < (size_t)width || right_stride < (size_t)width || disp_stride < (size_t)width * 2) return SBM_ERR_SIZE;
   for (int i = 0; i < n; i++)
     if (!left[i] || !right[i] || !disp[i]) return SBM_ERR_NULL;
-  HP_BEGIN();
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
   st = ensure_staging(h, n, width, height);
   if (st != SBM_OK) return st;
-  HP(0);
   uint8_t *st_l = h->st.l.as<uint8_t>(), *st_r = h->st.r.as<uint8_t>();
   int16_t* st_d = h->st.d.as<int16_t>();
   const size_t npix1 = (size_t)width * height;
@@ -423,8 +394,7 @@ int sbm_compute_batch(sbm_handle* h, int n, const uint8_t* const* left, size_t l
   // transfer per row (measured 5.6 ms per 1242x375 pair against 0.2 ms packed).
   const bool in_dense = left_stride == (size_t)width && right_stride == (size_t)width;
   const bool out_dense = disp_stride == (size_t)width * 2;
-  static const int pipe_env = SBM_TUNE("SBM_HOST_PIPELINE", 1);
-  if (in_dense && out_dense && n >= 16 && pipe_env && !h->profiling)
+  if (in_dense && out_dense && n >= 16 && !h->profiling)
     return compute_batch_pipelined(h, n, left, right, width, height, disp);
   if (!in_dense || !out_dense) {
     const size_t need = (size_t)n * npix1 * 4;
@@ -453,10 +423,8 @@ int sbm_compute_batch(sbm_handle* h, int n, const uint8_t* const* left, size_t l
     HIPCHK(h, hipMemcpyAsync(st_l, pin_l, (size_t)n * npix1, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(st_r, pin_r, (size_t)n * npix1, hipMemcpyHostToDevice, h->stream));
   }
-  HP(1);
   st = sbm_compute_device(h, n, st_l, st_r, width, height, st_d, 0);
   if (st != SBM_OK) return st;
-  HP(2);
   // Small calls into PAGEABLE caller memory (what a cv::Mat is): copy kernel into pinned host memory + flag, then the rows go to
   // the caller from there (see maps_out_kernel; 640x480: 0.199 -> 0.187 ms per call). Pinned caller memory takes the D2H copy
   // below: the DMA engine writes it directly and nothing is left for the CPU to copy (0.158 against 0.180 ms through the kernel).
@@ -470,13 +438,10 @@ int sbm_compute_batch(sbm_handle* h, int n, const uint8_t* const* left, size_t l
   if (zero_copy) {
     st = maps_out_to_caller(h, st_d, n, npix1, disp);
     if (st != SBM_OK) return st;
-    HP(4);
   } else if (out_dense) {
     for (int i = 0; i < n; i++)
       HIPCHK(h, hipMemcpyAsync(disp[i], st_d + i * npix1, npix1 * 2, hipMemcpyDeviceToHost, h->stream));
-    HP(3);
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HP(4);
   } else {
     HIPCHK(h, hipMemcpyAsync(pin_d, st_d, (size_t)n * npix1 * 2, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));

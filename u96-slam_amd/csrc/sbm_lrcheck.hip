@@ -276,10 +276,8 @@ hipError_t launch_lrcheck(const int16_t* disp_pre, const int32_t* cost, int16_t*
     // then the narrowest block (a multiple of 64) that does. Measured (profiles/r04_lr_sweep.txt): what counts is how few idle
     // pixel slots the cover leaves and, for rows up to ~1300 columns, few wavefronts per row -- 2 pixels x 5 iterations x one
     // (640 columns) or two (1242) wavefronts; wider rows do best with 4 pixels x 256 threads x 2..4 iterations.
-    int px = g.W <= 1280 ? 2 : 4;
-    int bsmax = px == 4 ? 256 : (g.W <= 640 ? 64 : 128);
-    if (SBM_TUNE("SBM_DEV_LR_PX", 0)) px = SBM_TUNE("SBM_DEV_LR_PX", 0) == 2 ? 2 : 4;
-    if (SBM_TUNE("SBM_DEV_LR_BS", 0)) bsmax = std::max(64, std::min(320, SBM_TUNE("SBM_DEV_LR_BS", 0) / 64 * 64));
+    const int px = g.W <= 1280 ? 2 : 4;
+    const int bsmax = px == 4 ? 256 : (g.W <= 640 ? 64 : 128);
     const int groups = (g.W + px - 1) / px;
     const int nit = (groups + bsmax - 1) / bsmax;
     const int bs = (((groups + nit - 1) / nit + 63) / 64) * 64;
@@ -289,9 +287,6 @@ hipError_t launch_lrcheck(const int16_t* disp_pre, const int32_t* cost, int16_t*
     switch (nit * 8 + px) {
       SBM_LR_CASE(1, 2) SBM_LR_CASE(2, 2) SBM_LR_CASE(3, 2) SBM_LR_CASE(4, 2) SBM_LR_CASE(5, 2)   // up to 1280 columns
       SBM_LR_CASE(2, 4) SBM_LR_CASE(3, 4) SBM_LR_CASE(4, 4)                                       // 1281 .. 4096 columns
-#ifdef SBM_DEV
-      SBM_LR_CASE(1, 4) SBM_LR_CASE(5, 4) SBM_LR_CASE(6, 4) SBM_LR_CASE(7, 4) SBM_LR_CASE(8, 4) SBM_LR_CASE(6, 2) SBM_LR_CASE(7, 2) SBM_LR_CASE(8, 2)
-#endif
       default: launched = false;
     }
 #undef SBM_LR_CASE

@@ -185,10 +185,8 @@ __global__ void __launch_bounds__(256) prefilter_kernel(const uint8_t* __restric
 // Rows per thread tile (PF_ROWS + 2 row pieces are loaded for PF_ROWS output rows). Measured on MI355X
 // (tools/bench_prefilter.py, profiles/r02_prefilter.json): 4 rows is best while source + destination fit the 256 MB
 // Infinity Cache (4.3 vs 4.0 TB/s at 119 MB), 8 rows beyond it (4.4-4.9 vs 4.1-4.5 TB/s at 1.9-2.1 GB, i.e. 98-105 % of
-// the runtime's device-to-device copy of the same bytes). SBM_PF_ROWS=2|4|8 overrides.
+// the runtime's device-to-device copy of the same bytes).
 static int pf_rows(size_t bytes_in_out) {
-  static const int env = [] { const int v = SBM_TUNE("SBM_PF_ROWS", 0); return (v == 2 || v == 4 || v == 8) ? v : 0; }();
-  if (env) return env;
   return bytes_in_out > ((size_t)256 << 20) ? 8 : 4;
 }
 
@@ -201,7 +199,7 @@ hipError_t launch_prefilter(const uint8_t* d_left, const uint8_t* d_right, uint8
   const PfMap m{-g.cap, g.cap, g.cap, kPfBias, 0, g.pfshift, (g.reading & kReadOddRowComputed) ? 0 : 1};
 #define SBM_PF(R) hipLaunchKernelGGL(prefilter_kernel<R>, grid, dim3(256), 0, s, d_left, d_right, pf_l, pf_r, g.W, g.H, g.pitch, g.padl, \
                      (size_t)g.W * g.H, (size_t)g.plane, (size_t)g.n * g.W * g.H, (size_t)g.n * g.W * g.H, m)
-  if (rows == 2) SBM_PF(2); else if (rows == 8) SBM_PF(8); else SBM_PF(4);
+  if (rows == 8) SBM_PF(8); else SBM_PF(4);
 #undef SBM_PF
   return hipGetLastError();
 }
@@ -293,7 +291,7 @@ hipError_t launch_prefilter_dense(const uint8_t* d_src, uint8_t* d_dst, int n, i
                          W, 0, img, img, img, img, m);                                                                      \
     }                                                                                                                       \
   } while (0)
-  if (rows == 2) SBM_PFD(2); else if (rows == 8) SBM_PFD(8); else SBM_PFD(4);
+  if (rows == 8) SBM_PFD(8); else SBM_PFD(4);
 #undef SBM_PFD
   return hipGetLastError();
 }

@@ -40,10 +40,9 @@
 //
 // Source layout: sbm_sad_fast_core.h (arguments, LDS carve-up, exchange plan, the per-row tail: winner search / uniqueness /
 // neighbours / sub-pixel), sbm_sad_fast_strip.h (the strip), sbm_sad_border_wave.h (the clamped border columns, extra wavefronts
-// of the same launch), sbm_sad_fast_kernel.h (kernel + layout choice), sbm_sad_fast_dev.h (development knobs), and this file:
-// the host side -- envelope, device self-test of the in-place accumulate, strips / row segments of a launch -- plus the kernels
-// of the windows 15 and 21. The ~270 instantiations compile as four translation units side by side (this one, sbm_sad_fast_pw1 /
-// _pw2 / _pw3.hip: the other windows).
+// of the same launch), sbm_sad_fast_kernel.h (kernel + layout choice), and this file: the host side -- envelope, device
+// self-test of the in-place accumulate, strips / row segments of a launch -- plus the kernels of the windows 15 and 21. The ~270
+// instantiations compile as four translation units side by side (this one, sbm_sad_fast_pw1 / _pw2 / _pw3.hip: the other windows).
 #include "sbm_sad_fast_kernel.h"
 
 namespace sbm {
@@ -185,11 +184,12 @@ hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* di
   // (a workgroup target of 24 000 / 5 600 with segments of at least three window heights) was tuned at 64 / 16 / 4 pairs only.
   // (one round of the chip for the cooperating 128-disparity wavefronts: 12 wavefronts per CU in workgroups of 2 / 3 / 4)
   const int round1 = g.nd <= 256 ? 1536 : (g.nd <= 384 ? 1024 : 768);
+  constexpr double kSegC = 0.196;   // c of the model above
   int nseg = 1;
   {
     const double prime = 0.2 * (g.wsz - 1);
     const double slots = g.nd <= 64 ? 4096.0 : (g.nd <= 128 ? 3072.0 : (double)round1);
-    nseg = (int)(std::sqrt(fast_tune().seg_c1000 * 1e-3 * slots * rows / ((double)strips * g.n * prime)) + 0.5);
+    nseg = (int)(std::sqrt(kSegC * slots * rows / ((double)strips * g.n * prime)) + 0.5);
     nseg = std::max(1, std::min(nseg, std::max(1, rows / g.wsz)));   // (at least one window height per segment here; see below)
   }
   // Launches that do not fill the chip (round 5, profiles/r05_small_launch_segments.txt): a wavefront's row segment is a serial
@@ -198,26 +198,24 @@ hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* di
   // pairs) split the disparities over more wavefronts per workgroup instead (launch_nd: `split`) and take as many segments
   // as keep them under 1 024 workgroups. One 640x480 nd 64 w 21 pair: SAD stage 0.054 -> 0.049 ms, one KITTI pair 0.052 ->
   // 0.036, 8 KITTI pairs 0.209 -> 0.14, 16 pairs 640x480 0.203 -> 0.12, 4 pairs 1080p nd 256 0.64 -> 0.57.
-  const int small_rows = fast_tune().small_rows;
-  const long fill = fast_tune().fill;
-  const int maxseg = std::max(nseg, std::min(64, rows / small_rows));
+  constexpr int kSmallRows = 8;   // shortest row segment of a launch that does not fill the chip
+  constexpr long kFill = 5000;     // workgroups such a launch is cut into
+  const int maxseg = std::max(nseg, std::min(64, rows / kSmallRows));
   const long per_seg = (long)strips * g.n;
   if (per_seg * maxseg * (g.nd > 128 ? (g.nd + 127) / 128 : 1) < 1800) {
     nseg = std::max(nseg, (int)std::min<long>(maxseg, 1023 / per_seg));
   } else {
     const int nseg1 = nseg;
-    while (per_seg * nseg < fill && nseg < maxseg) nseg++;
+    while (per_seg * nseg < kFill && nseg < maxseg) nseg++;
     // (two cooperating 128-disparity wavefronts: 1 536 workgroups are one round of the chip; a launch that ends between 1 and
     // 1.5 rounds pays a second, mostly empty round -- one 1080p nd 256 pair: 64 segments 0.204 ms, 36..48 segments 0.189..0.196)
     if (g.nd > 128 && per_seg * nseg > round1 && 2 * per_seg * nseg < 3 * round1) nseg = std::max(nseg1, (int)((long)round1 * 1450 / 1536 / per_seg));
   }
-  if (fast_tune().nseg > 0) nseg = std::min(fast_tune().nseg, std::max(1, rows / 2));
   // taper: the last third of the rows is cut into segments of 2/3, 1/2, 1/3 ... of the regular length
-  const int taper = fast_tune().taper;
   nseg = std::min(nseg, 64);
   int ns = 0;
   a.segrow[0] = g.row0;
-  if (!taper || nseg < 3) {
+  if (nseg < 3) {
     const int seg = (rows + nseg - 1) / nseg;
     for (int y = g.row0; y < g.row1; y += seg) a.segrow[++ns] = std::min(y + seg, g.row1);
   } else {
@@ -235,18 +233,14 @@ hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* di
   a.strips = strips; a.nseg = nseg; a.npairs = g.n;
   {
     const long maxs = (long)g.wsz * g.wsz * 2 * g.cap;
-    a.uniq_plain = fast_tune().uniq_plain && 8 * ((maxs * g.uniq / 100 + 1) << g.pfshift) <= 65535;   // (8 registers per accumulator)
+    a.uniq_plain = 8 * ((maxs * g.uniq / 100 + 1) << g.pfshift) <= 65535;   // (8 registers per accumulator)
   }
-  const bool split = (long)strips * nseg * g.n < 1024 && fast_tune().split;
+  const bool split = (long)strips * nseg * g.n < 1024;
   hipError_t e;
   switch (g.wsz) {
     case 15: e = launch_nd<5, 3>(a, border, split, s); break;
     case 21: e = launch_nd<7, 3>(a, border, split, s); break;
-#ifdef SBM_DEV_FEW   // (development builds, sbm_sad_fast_dev.h: only the bench workloads' windows)
-    default: e = hipErrorInvalidValue; break;
-#else
     default: e = launch_sad_fast_pw1(a, g.wsz, border, split, s); break;   // the other windows: sbm_sad_fast_pw1 / _pw2 / _pw3.hip
-#endif
   }
   *xa = a.xc0; *xb = a.xc1;
   return e;

@@ -3,7 +3,6 @@
 // windows). gfx950 only.
 #pragma once
 #include "sbm_sad_fast_core.h"
-#include "sbm_sad_fast_dev.h"
 #include "sbm_sad_fast_strip.h"
 
 namespace sbm {
@@ -85,7 +84,7 @@ sad_fast_kernel(FastArgs a) {
 // Tuning constants of the border jobs' row segments (chip- and kernel-version specific; they only move time, never results):
 // the launch's expected duration is priced at kBorderModelRate pixel-disparities per second (the interior kernel's rate when
 // the segments were tuned: 3.6e12, profiles/r04_border_bseg.txt), a border row at kBorderRowUs + kBorderColUs per output
-// column (tools/exp/r04_bwprof.py), and a chain may last kBorderChainShare of the launch.
+// column (a round-4 probe script, in git history: DESIGN.md section 6), and a chain may last kBorderChainShare of the launch.
 constexpr double kBorderModelRate = 3.6e12, kBorderRowUs = 2.0, kBorderColUs = 0.25, kBorderChainShare = 0.205;
 
 template <int NDW, int NWAVES, int NTERM, int PW>
@@ -104,7 +103,7 @@ static hipError_t launch_t(FastArgs a, bool border, hipStream_t s) {
     a.bord = (a.bnw + NWAVES - 1) / NWAVES;
     lds = std::max(lds, (size_t)NWAVES * BL::BYTES);
     // A border wavefront is a serial chain of rows (~2 us + 0.25 us per output column and row, a quarter of that for each of
-    // its w-1 priming rows -- measured alone on the chip, tools/exp/r04_bwprof.py); it must end well inside the launch, so the
+    // its w-1 priming rows -- measured alone on the chip: kBorderRowUs, kBorderColUs); it must end well inside the launch, so the
     // border jobs get their own, finer row segments: a chain of about a fifth of the launch's expected duration (640x480 nd 64
     // w 21 x 64 pairs, where the border columns weigh most: 10 rows per segment 0.520 ms per step, 13 rows 0.537, 6 rows 0.533 --
     // profiles/r04_border_bseg.txt; KITTI x 64 is flat between 32 and 96 rows).
@@ -112,18 +111,12 @@ static hipError_t launch_t(FastArgs a, bool border, hipStream_t s) {
     const double t_kernel_us = (double)a.npairs * a.W * rows * a.nd / kBorderModelRate * 1e6;
     const double t_row_us = kBorderRowUs + kBorderColUs * (wsz / 2);
     int bseg = (int)(kBorderChainShare * t_kernel_us / t_row_us - 0.25 * (wsz - 1));
-    if (fast_tune().bseg > 0) bseg = fast_tune().bseg;
     bseg = std::max(4, std::min(bseg, rows));
     a.nbseg = (rows + bseg - 1) / bseg;
     a.bseg = (rows + a.nbseg - 1) / a.nbseg;
     a.nbseg = (rows + a.bseg - 1) / a.bseg;
   }
   dim3 grid((unsigned)(a.bord * a.nbseg + a.strips * a.npairs * a.nseg));
-  if (fast_tune().print)   // development builds: the launch geometry
-    fprintf(stderr, "[sbm] <%d,%d,%d,%d> strips %d (cs3 %d) nseg %d pairs %d bord %d x %d grid %u lds %zu\n", NDW, NWAVES, NTERM, PW, a.strips, a.strips3,
-            a.nseg, a.npairs, a.bord, a.nbseg, grid.x, lds);
-  // development builds: time the border wavefronts alone (results are wrong by construction)
-  if (fast_tune().border_only) grid.x = (unsigned)(a.bord * a.nbseg);
   // (the masked-count kernels are right for every count up to NDW * NWAVES; <64,4> only runs one-pair calls beyond 192
   // disparities: its masked kernel serves 256 as well)
   // (three and four 128-disparity wavefronts, 257 .. 512 disparities: exact kernels for 384 and 512 -- 5-7 % over the masked ones,

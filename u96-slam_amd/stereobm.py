@@ -149,7 +149,7 @@ class StereoBMError(RuntimeError):
 
 def library_path():
     """lib/libsbm_hip.so, or -- SBM_LIB_AB=<file name> -- another build of the same HIP engine inside lib/ for kernel A/B
-    runs (tools/exp). Only a bare libsbm_hip*.so name is accepted and the file must exist: never a fallback, never a path."""
+    runs. Only a bare libsbm_hip*.so name is accepted and the file must exist: never a fallback, never a path."""
     name = os.environ.get("SBM_LIB_AB", "libsbm_hip.so")
     if name != os.path.basename(name) or not (name.startswith("libsbm_hip") and name.endswith(".so")):
         raise ImportError(f"SBM_LIB_AB={name!r}: expected the bare name of a libsbm_hip*.so inside {_HERE / 'lib'}")
