@@ -70,9 +70,10 @@ def lib():
     return _LIB
 
 
-def compute(p, left, right, reading=0, stages=False):
+def compute(p, left, right, reading=0, stages=False, pre_only=False):
     """cv::StereoSGBM::compute restated. Returns the int16 map, or (map, dict(C, S, pre)) with stages=True; C and S are
-    (H, width1, numDisparities) int16 (None when width1 < 1)."""
+    (H, width1, numDisparities) int16 (None when width1 < 1). pre_only=True returns (map, pre) and keeps no C or S volume on
+    the host (MODE_SGBM then holds one row of them)."""
     left = np.ascontiguousarray(left, dtype=np.uint8)
     right = np.ascontiguousarray(right, dtype=np.uint8)
     assert left.shape == right.shape and left.ndim == 2
@@ -94,4 +95,6 @@ def compute(p, left, right, reading=0, stages=False):
         disp = sbm_oracle.filter_speckles(disp, (p.min_disparity - 1) * 16, p.speckle_window_size, 16 * p.speckle_range)
     if stages:
         return disp, dict(C=C, S=S, pre=pre)
+    if pre_only:
+        return disp, pre
     return disp

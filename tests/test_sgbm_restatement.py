@@ -191,6 +191,10 @@ def _pair(seed, H, W, kind="noise"):
         L[:, W // 2:] = 120
         R = np.roll(L, -3, axis=1)
         return L, R
+    if kind == "far":   # a smooth pair shifted by a third to two thirds of the width: winners in the upper disparities
+        shift = int(rng.integers(W // 3, 2 * W // 3))
+        base = (np.cumsum(rng.integers(-6, 7, (H, W + 40 + shift)), axis=1) % 256).astype(np.uint8)
+        return np.ascontiguousarray(base[:, 20:20 + W]), np.ascontiguousarray(base[:, 20 + shift:20 + shift + W])
     base = rng.integers(0, 256, (H, W + 40)).astype(np.uint8)
     if kind == "smooth":
         base = (np.cumsum(rng.integers(-6, 7, (H, W + 40)), axis=1) % 256).astype(np.uint8)
@@ -219,6 +223,21 @@ CASES = [
     (0, 32, 11, 50, 9000, 1, 63, 0, 0, 0, HH, 20, 120, "binary"),  # S saturated at every disparity: no winner
     (0, 32, 11, 50, 9000, 1, 63, 0, 0, 0, SG, 20, 120, "binary"),
     (-3, 32, 11, 50, 9000, 1, 63, 15, 0, 0, HH, 20, 120, "binary"),
+    # every lane layout of the GPU kernels (NV = 2 / 4 / 8 disparities per lane, partly masked) on tiny frames
+    (0, 80, 3, 8, 72, 1, 0, 10, 0, 0, HH, 6, 110, "far"),         # width1 = 30
+    (-20, 144, 5, 0, 0, 4, 0, 15, 0, 0, SG, 5, 180, "far"),       # width1 = 36
+    (3, 272, 1, 4, 40, 32, 31, 0, 10, 1, HH, 4, 300, "far"),      # width1 = 25
+    (-4, 272, 11, 100, 1000, 0, 0, 15, 0, 0, SG, 6, 310, "smooth"),
+    (0, 512, 3, 0, 0, 0, 0, 15, 0, 0, HH, 3, 542, "far"),         # width1 = 30
+    (-256, 512, 7, 10, 200, 0, 0, 0, 20, 2, SG, 6, 540, "far"),   # width1 = 28
+    (5, 512, 5, 8, 64, 4, 63, 0, 0, 0, HH, 5, 560, "noise"),
+    # frames one, two and three rows tall
+    (0, 32, 3, 0, 0, 0, 0, 0, 0, 0, HH, 1, 60, "smooth"),
+    (-4, 16, 5, 4, 40, 1, 0, 15, 0, 0, SG, 1, 45, "noise"),
+    (-4, 16, 5, 4, 40, 1, 0, 15, 0, 0, HH, 2, 50, "smooth"),
+    (2, 48, 7, 0, 0, 32, 0, 10, 4, 1, SG, 2, 90, "far"),
+    (2, 48, 7, 0, 0, 32, 0, 10, 4, 1, HH, 3, 90, "far"),
+    (-8, 80, 9, 8, 300, 4, 0, 0, 0, 0, SG, 3, 120, "smooth"),
 ]
 
 
