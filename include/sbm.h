@@ -81,7 +81,8 @@
  *                                          under both readings of each, and tools/verify_with_opencv.py (numpy + cv2 only) names the
  *                                          reading a given OpenCV implements -- adopting it is a default flip here, not a rewrite;
  *                                          bits 32 and 64 belong to the semi-global matcher (see sbm_sgbm_params below),
- *                                          bit 128 to the ORB descriptor's blur (see sbm_orb_params below)
+ *                                          bit 128 to the ORB descriptor's blur (see sbm_orb_params below),
+ *                                          bit 256 to the keypoint matcher's radius test (see sbm_match_params below)
  * The Python mirror adds SBM_LIB_AB (file name of another build of this library inside u96-slam_amd/lib/, A-B measurements
  * only); bench.py reads SBM_BENCH_BACKEND / SBM_BENCH_FEED / SBM_BENCH_SG_FAULT (tests of its multi-process control flow).
  */
@@ -474,6 +475,81 @@ int sbm_orb_describe(sbm_handle* h, const uint8_t* img, size_t img_stride, int w
 int sbm_orb_features_device(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_select_params* gp,
                             const int* pattern, const sbm_orb_params* p, void* d_eig, void* d_max, void* d_kpts, void* d_count,
                             void* d_desc, void* d_blur, int sync);
+
+/* ---- keypoint matching: computeTransform's matchingNoGuess / matchingGuess (src/slam/src/core/Registration.cpp) --------------
+ * What the reference does with a frame's descriptors first: match the current frame against the key frame, brute force on the
+ * first frame and after a failed guess (matchingNoGuess, Registration.cpp:311-335), else guided by the motion guess
+ * (matchingGuess, :250-303). Restated bit for bit, for 32-byte descriptor rows; Hamming distance = popcount(a XOR b), 0..256.
+ *   k-NN-2    over a query's candidate set, in increasing train index, as batchDistance inserts: a candidate enters only on a
+ *             strictly smaller distance, so on equal distances the lower index ranks first. Result: best (index, d0), second d1.
+ *   NNDR      accept when (float)d0 < nndr * (float)d1, in float (nndr = 0.8f). For every d0, d1 in 0..256 this equals
+ *             5 * d0 < 4 * d1: a tie between the two best is always rejected, so the tie order never changes an output.
+ *   no-guess  queries: from-rows 0..nf-1; candidates: all nt to-rows; a query matches its best row when NNDR passes. nt == 0: no
+ *             pairs. nt == 1: the reference reads matches[i][1] out of range (undefined); defined here as NO pairs.
+ *   guided    queries: the from-points whose projection is valid (see projection), in increasing from-index; a to-keypoint is a
+ *             candidate when sqrtf(dx * dx + dy * dy) < radius (radius = 40.0f; float, each product rounded, the sum unfused, the
+ *             square root correctly rounded, a strict <) -- recalled from OpenCV's radiusMatch / normL2Sqr, not pinned; bit 256 of
+ *             SBM_CV_READING reads the sum as fmaf(dy, dy, dx * dx) (an aarch64 OpenCV build may contract). The engine compares
+ *             the sum with the least float whose rounded square root reaches the radius (just below 1600 for 40: NOT d2 < 1600).
+ *             0 candidates: no match; exactly 1: that candidate, WITHOUT NNDR (:207-210); 2 or more: k-NN-2 + NNDR over them.
+ *   unique    (both modes) a match (q -> t) is kept iff q is the smallest query index whose accepted match is t: the std::set
+ *             rule, a rejected duplicate does not fall back to its second best. Pairs (from, to) as int32, increasing from.
+ *   project   (matchingGuess_Projection, :36-74) T = guessCameraRef as a 3x4 float matrix (computed by the caller), K = fx, fy,
+ *             cx, cy (double), W x H the camera model's image size. Per point p (float x, y, z; NaN = no depth): zc = T's third
+ *             row applied to p in float, unfused, left to right (transformPoint, Stereo.cpp:189-198); X = R p + t in double with
+ *             R, t promoted from T; inv = Z != 0 ? 1.0 / Z : 1.0; u = (float)(X * inv * fx + cx), v likewise; valid iff
+ *             0 < u < W - 1 && 0 < v < H - 1 && zc > 0; invalid points are written as (NaN, NaN), so a NaN point is never valid.
+ *             NOT reproduced: OpenCV's Rodrigues round trip (R -> rvec -> R, through an SVD) and its zero-distortion terms, so
+ *             projected coordinates can differ from cv::projectPoints in the last bits; that can only matter within rounding of
+ *             the 40 px radius or of the image-border bounds. The guided matcher is exact given its projected points (a caller with
+ *             OpenCV may pass cv::projectPoints' output to sbm_match_guess_device instead).
+ * Store layout: descriptors and counts exactly as sbm_orb_describe_device writes them -- frame i's rows from d_desc + i * cap * 32,
+ * d_count n int32 read on the device and clamped to [0, cap]. A job is a (from frame, to frame) pair of frames in [0, n);
+ * from == to and repeated frames are allowed. Job j's pairs go to d_pairs + j * cap (int32 pairs), their number to d_npairs[j].
+ * d_knn (NULL, or m * cap records of 4 int32, for tests and diagnostics): per query slot (best index, d0, d1, candidate count)
+ * over its candidate set; best = -1 and d0 / d1 = 257 where there are fewer candidates; slots past the from-count hold
+ * (-1, 257, 257, 0).
+ * Limits (status codes): n, m >= 1 (SBM_ERR_BATCH), m <= 65 535 (SBM_ERR_UNSUPPORTED), cap 1..65 535 (SBM_ERR_SIZE), every frame
+ * index in [0, n) (SBM_ERR_SIZE); d_desc and d_knn 16-byte, d_pairs, d_kpts and d_proj 8-byte, d_count, d_npairs and d_xyz
+ * 4-byte aligned (SBM_ERR_UNSUPPORTED).
+ * Kernels: k-NN over (job, 64-query tile, train slice) with partial records, a claim kernel (merge, NNDR,
+ * atomicMin of the query into its train row's owner slot), and one workgroup per job that emits the owners' pairs. Up to 64
+ * jobs per launch sequence; handle scratch for one launch stays within 256 MiB. Everything is enqueued on the handle's stream;
+ * nothing synchronises the host unless sync != 0 (the counts stay on the device).
+ * sbm_get_profile: while profiling is enabled (any mode) these calls synchronise and record "match_knn", "match_unique" (claim +
+ * emit), "match_project" and "match_total" (ms of the last call). */
+typedef struct sbm_match_params {
+  float nndr;     /* NNDR ratio, default 0.8f; finite, in (0, 1]        */
+  float radius;   /* guided search radius in pixels, default 40.0f; > 0 */
+} sbm_match_params;
+
+/* Fill *p with the reference's values: 0.8f, 40.0f. */
+void sbm_match_params_default(sbm_match_params* p);
+/* SBM_ERR_NULL, SBM_ERR_UNSUPPORTED (a field outside the limits above), else SBM_OK. */
+int sbm_match_params_validate(const sbm_match_params* p);
+/* matchingNoGuess for m jobs over a store of n frames (jobs: 2 * m host ints, copied with the call). */
+int sbm_match_device(sbm_handle* h, int n, int m, const int* jobs, const void* d_desc, const void* d_count, int cap,
+                     const sbm_match_params* p, void* d_pairs, void* d_npairs, void* d_knn, int sync);
+/* matchingGuess's matching for m jobs: d_kpts holds the frames' keypoints in the layout sbm_orb_describe_device leaves its kept
+ * keypoints in (frame i's float (x, y) pairs from i * cap * 2; the to-frames' are read), d_proj job j's cap projected float pairs
+ * from j * cap * 2 as sbm_project_points_device writes them (a NaN coordinate has no candidates). */
+int sbm_match_guess_device(sbm_handle* h, int n, int m, const int* jobs, const void* d_desc, const void* d_count, int cap,
+                           const void* d_kpts, const void* d_proj, const sbm_match_params* p, void* d_pairs, void* d_npairs,
+                           void* d_knn, int sync);
+/* matchingGuess_Projection for m jobs: job j projects frame from[j]'s points (d_xyz: frame i's float (x, y, z) from i * cap * 3,
+ * each slice as sbm_keypoints3d_device writes it; count d_count[from[j]]) with its own T (T + 12 j, host), into d_proj + j * cap * 2;
+ * slots past the count are written as NaN. K: fx, fy, cx, cy (host). Limits as above, width and height >= 1 (SBM_ERR_SIZE). */
+int sbm_project_points_device(sbm_handle* h, int n, int m, const int* from, const void* d_xyz, const void* d_count, int cap,
+                              const float* T, const double* K, int width, int height, void* d_proj, int sync);
+/* Host forms for ONE job, shaped like the reference's calls, synchronous: descriptor rows strided (strides in bytes, >= 32),
+ * pairs receives up to nf int32 pairs, *npairs their number. nf or nt may be 0; max(nf, nt) <= 65 535 (SBM_ERR_SIZE). */
+int sbm_match(sbm_handle* h, const uint8_t* desc_from, size_t stride_from, int nf, const uint8_t* desc_to, size_t stride_to, int nt,
+              const sbm_match_params* p, int* pairs, int* npairs);
+/* matchingGuess: xyz_from nf float (x, y, z) points, kpts_to nt float (x, y) keypoints, both descriptor sets, T (12 floats), K
+ * (4 doubles), the image size; projection included. */
+int sbm_match_guess(sbm_handle* h, const float* xyz_from, const float* kpts_to, const uint8_t* desc_from, size_t stride_from, int nf,
+                    const uint8_t* desc_to, size_t stride_to, int nt, const float* T, const double* K, int width, int height,
+                    const sbm_match_params* p, int* pairs, int* npairs);
 
 /* ---- semi-global matcher: cv::StereoSGBM (the reference's DEPTH_METHOD_CV_SGBM, main.cpp:218-234) -------------------------
  * Restatement of cv::StereoSGBM::compute() for 8-bit single-channel pairs in MODE_HH (two passes, 8 paths: the reference's

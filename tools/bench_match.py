@@ -1,0 +1,166 @@
+"""Measure the keypoint matching (matchingNoGuess / matchingGuess at the reference's values) on ORB descriptors the engine computes
+from 640 x 480 frames and print one JSON line:
+
+  match_ms / single_match_ms     device time per sbm_match_device call (events on the engine's stream, median over --steps) for
+                                 --n jobs (frame i against frame i + 1) and for one job
+  guess_ms / single_guess_ms     the same for sbm_match_guess_device (projections precomputed)
+  project_ms                     sbm_project_points_device for --n jobs
+  pairs_per_job                  mean no-guess pair count
+  bit_exact_first_8              pairs, counts and k-NN records of the first 8 jobs (both modes) equal the CPU restatement's
+  restatement_host_ms            the CPU restatement (oracle_match/, single-threaded C) of one no-guess job: for scale only
+
+  python tools/bench_match.py --frames golden|synth [--n 64] [--steps 20] [--warmup 3] [--out FILE]
+
+--step-only runs the timed --n-job no-guess and guided calls and nothing else, for a kernel trace.
+"""
+import argparse
+import ctypes
+import json
+import pathlib
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "oracle_match"))
+
+K = (458.0, 457.0, 320.5, 240.5)
+
+
+def frames(kind, n):
+    if kind == "golden":
+        g = np.load(ROOT / "tests" / "golden" / "ref_pair_640x480.npz")
+        two = [g["rect_l"], g["rect_r"]]
+        return np.stack([two[i % 2] for i in range(n)])
+    from u96_slam_amd import synth
+
+    L, _ = synth.make_batch(0, n, 640, 480, 64)
+    return np.ascontiguousarray(L)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", choices=("golden", "synth"), default="golden")
+    ap.add_argument("--n", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--step-only", action="store_true")
+    ap.add_argument("--out")
+    a = ap.parse_args()
+
+    import torch
+
+    import _pkg
+    import match_ref
+
+    pkg = _pkg.load()
+    bm = pkg.StereoBM.create(64, 21)
+    L, h = bm._L, bm._h
+    imgs = frames(a.frames, a.n + 1)
+    n1, H, W = imgs.shape
+    m = a.n
+    pat = np.load(ROOT / "tests" / "golden" / "orb_pattern.npz")["pattern"]
+    desc, kpts, count = bm.orb_features(torch.from_numpy(imgs).to("cuda:0"), pat)
+    cap = desc.shape[1]
+    cn = count.cpu().numpy()
+    kn = kpts.cpu().numpy()
+    xyz = np.full((n1, cap, 3), np.nan, np.float32)          # depth from a fixed plane-and-ramp scene
+    for i in range(n1):
+        k = kn[i, :cn[i]]
+        z = (np.float32(3.0) + k[:, 1] / np.float32(160.0)).astype(np.float32)
+        xyz[i, :cn[i], 0] = (k[:, 0] - K[2]) * z / K[0]
+        xyz[i, :cn[i], 1] = (k[:, 1] - K[3]) * z / K[1]
+        xyz[i, :cn[i], 2] = z
+    d_xyz = torch.from_numpy(xyz).to("cuda:0")
+    jobs = np.ascontiguousarray(np.array([(i, i + 1) for i in range(m)], np.int32))
+    T = np.tile(np.array([1, 0, 0, -0.02, 0, 1, 0, 0.01, 0, 0, 1, 0.0], np.float32), (m, 1))
+    Kd = np.array(K, np.float64)
+    fr = np.ascontiguousarray(jobs[:, 0])
+    mp = pkg.match_params()
+    pairs = torch.zeros((m, cap, 2), dtype=torch.int32, device="cuda:0")
+    npairs = torch.zeros((m,), dtype=torch.int32, device="cuda:0")
+    rec = torch.zeros((m, cap, 4), dtype=torch.int32, device="cuda:0")
+    proj = torch.zeros((m, cap, 2), dtype=torch.float32, device="cuda:0")
+    torch.cuda.synchronize()
+    stream = torch.cuda.ExternalStream(L.sbm_stream(h), device="cuda:0")
+
+    def check(st):
+        if st != 0:
+            raise RuntimeError(f"status {st}")
+
+    calls = {
+        "project": lambda k: check(L.sbm_project_points_device(h, n1, k, fr.ctypes.data, d_xyz.data_ptr(), count.data_ptr(), cap,
+                                                               T.ctypes.data, Kd.ctypes.data, W, H, proj.data_ptr(), 0)),
+        "match": lambda k: check(L.sbm_match_device(h, n1, k, jobs.ctypes.data, desc.data_ptr(), count.data_ptr(), cap,
+                                                    ctypes.byref(mp), pairs.data_ptr(), npairs.data_ptr(), None, 0)),
+        "guess": lambda k: check(L.sbm_match_guess_device(h, n1, k, jobs.ctypes.data, desc.data_ptr(), count.data_ptr(), cap,
+                                                          kpts.data_ptr(), proj.data_ptr(), ctypes.byref(mp), pairs.data_ptr(),
+                                                          npairs.data_ptr(), None, 0)),
+    }
+
+    def timed(name, k):
+        for _ in range(a.warmup):
+            calls[name](k)
+        check(L.sbm_synchronize(h))
+        ts = []
+        for _ in range(a.steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            calls[name](k)
+            e1.record(stream)
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return statistics.median(ts)
+
+    calls["project"](m)
+    if a.step_only:
+        timed("match", m)
+        timed("guess", m)
+        return
+    res = {"tool": "bench_match", "frames": a.frames, "n": m, "width": W, "height": H, "cap": cap,
+           "points_per_frame": float(np.mean(cn))}
+    res["project_ms"] = timed("project", m)
+    res["match_ms"] = timed("match", m)
+    res["single_match_ms"] = timed("match", 1)
+    res["guess_ms"] = timed("guess", m)
+    res["single_guess_ms"] = timed("guess", 1)
+    dn = desc.cpu().numpy()
+    pn = proj.cpu().numpy()
+    exact = True
+    npn = []
+    for guided in (False, True):
+        fn = L.sbm_match_guess_device if guided else L.sbm_match_device
+        args = (h, n1, m, jobs.ctypes.data, desc.data_ptr(), count.data_ptr(), cap) + (
+            (kpts.data_ptr(), proj.data_ptr()) if guided else ()) + (ctypes.byref(mp), pairs.data_ptr(), npairs.data_ptr(),
+                                                                     rec.data_ptr(), 1)
+        check(fn(*args))
+        P, N, R = pairs.cpu().numpy(), npairs.cpu().numpy(), rec.cpu().numpy()
+        if not guided:
+            npn = N
+        for j in range(min(m, 8)):
+            f, t = jobs[j]
+            wp, wr = match_ref.match(dn[f, :cn[f]], dn[t, :cn[t]], pn[j, :cn[f]] if guided else None,
+                                     kn[t, :cn[t]] if guided else None)
+            exact &= int(N[j]) == len(wp) and bool(np.array_equal(P[j, :N[j]], wp)) and bool(np.array_equal(R[j, :cn[f]], wr))
+        if guided:
+            res["guess_pairs_per_job"] = float(np.mean(N))
+    wp = match_ref.project(xyz[0, :cn[0]], T[0], Kd, W, H)
+    exact &= bool(np.array_equal(pn[0, :cn[0]], wp, equal_nan=True))
+    res["bit_exact_first_8"] = exact
+    res["pairs_per_job"] = float(np.mean(npn))
+    t0 = time.perf_counter()
+    for _ in range(3):
+        match_ref.match(dn[0, :cn[0]], dn[1, :cn[1]])
+    res["restatement_host_ms"] = (time.perf_counter() - t0) / 3 * 1e3
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        pathlib.Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        pathlib.Path(a.out).write_text(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

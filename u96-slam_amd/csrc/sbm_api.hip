@@ -1,7 +1,7 @@
 // sbm_api.hip -- C-ABI of libsbm_hip.so (declared in include/sbm.h): parameters, the handle's life and its pool, the block
 // matcher on device buffers, profiling and debug dispatch, and the thin rectify / prefilter / consumer entry points. The other
-// families' entry points sit with their kernels (sbm_fpga, sbm_sgbm, sbm_gftt, sbm_gftt_select, sbm_orb); the block matcher's
-// host-buffer paths are in sbm_host.hip. Replaces cv::StereoBM::compute at src/slam/src/core/main.cpp:201-216.
+// families' entry points sit with their kernels (sbm_fpga, sbm_sgbm, sbm_gftt, sbm_gftt_select, sbm_orb, sbm_match); the block
+// matcher's host-buffer paths are in sbm_host.hip. Replaces cv::StereoBM::compute at src/slam/src/core/main.cpp:201-216.
 //
 // Stage order (same as cv::StereoBM::compute): prefilter both images -> SAD/WTA on the valid-ROI rows
 // (fast kernel: interior columns + the clamped border columns as extra wavefronts of the same launch; generic kernel otherwise) -> LR check + invalid
@@ -88,6 +88,7 @@ static void free_buffers(sbm_handle* h) {
   h->sg.have_last = false;
   release_all(h->gs);
   release_all(h->orb);
+  release_all(h->mt);
 }
 
 // The reference re-creates its matcher for every frame (cv::StereoBM::create inside the loop, main.cpp:201). Streams,
@@ -101,7 +102,7 @@ static int g_pool_n = 0;
 
 static size_t scratch_bytes(sbm_handle* h) {
   return bytes_held(h->bm) + bytes_held(h->fp) + bytes_held(h->st) + h->pin_bytes + bytes_held(h->fq) + bytes_held(h->sg) +
-         bytes_held(h->gs) + bytes_held(h->orb);
+         bytes_held(h->gs) + bytes_held(h->orb) + bytes_held(h->mt);
 }
 
 // Stage times: the block matcher's, and every family's stage clock, start at zero.
@@ -114,6 +115,7 @@ static void reset_profile(sbm_handle* h, int enabled) {
   h->sg.clock.reset();
   h->gs.clock.reset();
   h->orb.clock.reset();
+  h->mt.clock.reset();
 }
 
 static void destroy_now(sbm_handle* h);
@@ -152,9 +154,11 @@ int sbm_create(sbm_handle** out, const sbm_params* p, int device) {
   static const char* const kSgbm[] = {"sgbm_cost", "sgbm_aggregate", "sgbm_select", "sgbm_median", "sgbm_speckle", "sgbm_total"};
   static const char* const kGftt[] = {"gftt_select_eig", "gftt_select_select", "gftt_select_total"};
   static const char* const kOrb[] = {"orb_blur", "orb_desc", "orb_total"};
+  static const char* const kMatch[] = {"match_knn", "match_unique", "match_total", "match_project"};
   h->sg.clock.init(kSgbm);
   h->gs.clock.init(kGftt);
   h->orb.clock.init(kOrb);
+  h->mt.clock.init(kMatch);
   DeviceScope dscope(device);
   if (dscope.enter() != hipSuccess) {
     delete h;
@@ -212,6 +216,7 @@ static void destroy_now(sbm_handle* h) {
   h->sg.clock.release();
   h->gs.clock.release();
   h->orb.clock.release();
+  h->mt.clock.release();
   for (int r = 0; r < sbm_handle::kRing; r++)
     for (int i = 0; i < sbm_handle::kMarks; i++)
       if (h->ev[r][i]) hipEventDestroy(h->ev[r][i]);
@@ -547,6 +552,7 @@ int sbm_get_profile(sbm_handle* h, const char* name, float* ms) {
     const float* t = h->sg.clock.find(name);
     if (!t) t = h->gs.clock.find(name);
     if (!t) t = h->orb.clock.find(name);
+    if (!t) t = h->mt.clock.find(name);
     if (!t) return SBM_ERR_UNSUPPORTED;
     *ms = *t;
   }

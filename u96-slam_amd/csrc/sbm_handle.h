@@ -217,6 +217,11 @@ struct sbm_handle {
     sbm::StageClock clock;
     template <class F> void each(F f) { f(blur); f(io); }
   } orb;
+  struct {   // keypoint matching: partial k-NN records, owner and accepted tables of one launch; the host forms' staging
+    sbm::DevBuf scratch, io;
+    sbm::StageClock clock;
+    template <class F> void each(F f) { f(scratch); f(io); }
+  } mt;
 };
 
 namespace sbm {

@@ -141,6 +141,29 @@ def orb_pattern_array(pattern):
     return p
 
 
+class MatchParams(ctypes.Structure):
+    """`sbm_match_params` of include/sbm.h: the NNDR ratio and guided radius of computeTransform's matching (Registration.cpp)."""
+
+    _fields_ = [("nndr", ctypes.c_float), ("radius", ctypes.c_float)]
+
+
+def match_params(nndr=0.8, radius=40.0):
+    """The reference's values by default."""
+    return MatchParams(float(nndr), float(radius))
+
+
+def match_validate(params):
+    """Status code of sbm_match_params_validate (0 = ok)."""
+    return load_library().sbm_match_params_validate(ctypes.byref(params))
+
+
+def _jobs_array(jobs):
+    j = np.ascontiguousarray(np.asarray(jobs, dtype=np.int32).reshape(-1, 2))
+    if j.shape[0] == 0:
+        raise StereoBMError(-24, "no jobs")
+    return j
+
+
 class StereoBMError(RuntimeError):
     def __init__(self, code, message):
         super().__init__(f"sbm status {code}: {message}")
@@ -231,6 +254,15 @@ def load_library():
     L.sbm_orb_describe_device.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp, op, vp, vp, vp, vp, ci]
     L.sbm_orb_describe.argtypes = [vp, vp, sz, ci, ci, vp, ci, vp, op, vp, ctypes.POINTER(ctypes.c_int), vp]
     L.sbm_orb_features_device.argtypes = [vp, ci, vp, ci, ci, gp, vp, op, vp, vp, vp, vp, vp, vp, ci]
+    mp_ = ctypes.POINTER(MatchParams)
+    L.sbm_match_params_default.argtypes = [mp_]
+    L.sbm_match_params_default.restype = None
+    L.sbm_match_params_validate.argtypes = [mp_]
+    L.sbm_match_device.argtypes = [vp, ci, ci, vp, vp, vp, ci, mp_, vp, vp, vp, ci]
+    L.sbm_match_guess_device.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, mp_, vp, vp, vp, ci]
+    L.sbm_project_points_device.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, ci, ci, vp, ci]
+    L.sbm_match.argtypes = [vp, vp, sz, ci, vp, sz, ci, mp_, vp, ctypes.POINTER(ci)]
+    L.sbm_match_guess.argtypes = [vp, vp, vp, vp, sz, ci, vp, sz, ci, vp, vp, ci, ci, mp_, vp, ctypes.POINTER(ci)]
     L.sbm_stream.argtypes = [vp]
     L.sbm_stream.restype = vp
     L.sbm_strerror.argtypes = [ci]
@@ -755,6 +787,135 @@ class StereoBM:
         if not sync:
             self._inflight.append((i3, eig, mx, kpts, count, desc, bl))
         return (desc, kpts, count, bl) if blur else (desc, kpts, count)
+
+    # ---- keypoint matching of computeTransform (src/slam/src/core/Registration.cpp) ---------------------------------------
+    def _match_store(self, desc, count):
+        import torch
+
+        if desc.dtype != torch.uint8 or desc.dim() != 3 or desc.shape[2] != 32 or not desc.is_contiguous() or not desc.is_cuda:
+            raise StereoBMError(-2, "desc must be a contiguous uint8 CUDA tensor (n, cap, 32)")
+        c1 = count.reshape(-1)
+        if c1.dtype != torch.int32 or c1.numel() != desc.shape[0] or not c1.is_cuda or not c1.is_contiguous():
+            raise StereoBMError(-2, "count must be a contiguous int32 CUDA tensor of n values")
+        return desc.shape[0], desc.shape[1], c1
+
+    def _match_out(self, m, cap, knn, dev):
+        import torch
+
+        pairs = torch.full((m, cap, 2), -1, dtype=torch.int32, device=dev)
+        npairs = torch.zeros((m,), dtype=torch.int32, device=dev)
+        rec = torch.zeros((m, cap, 4), dtype=torch.int32, device=dev) if knn else None
+        return pairs, npairs, rec
+
+    def match(self, desc, count, jobs, params=None, knn=False, sync=True):
+        """matchingNoGuess for every (from, to) job over a store in sbm_orb_describe_device's layout: desc uint8 (n, cap, 32),
+        count int32 (n,) on the device. Returns (pairs int32 (m, cap, 2), npairs int32 (m,)) [+ records int32 (m, cap, 4)
+        with knn=True]; pair slots past npairs hold -1."""
+        import torch
+
+        n, cap, c1 = self._match_store(desc, count)
+        j = _jobs_array(jobs)
+        p = params if params is not None else match_params()
+        pairs, npairs, rec = self._match_out(j.shape[0], cap, knn, desc.device)
+        torch.cuda.current_stream(desc.device).synchronize()
+        _check(self._L.sbm_match_device(self._h, n, j.shape[0], j.ctypes.data, desc.data_ptr(), c1.data_ptr(), cap, ctypes.byref(p),
+                                        pairs.data_ptr(), npairs.data_ptr(), None if rec is None else rec.data_ptr(),
+                                        1 if sync else 0), self._h)
+        if not sync:
+            self._inflight.append((desc, c1, pairs, npairs, rec))
+        return (pairs, npairs, rec) if knn else (pairs, npairs)
+
+    def match_guess(self, desc, count, kpts, proj, jobs, params=None, knn=False, sync=True):
+        """matchingGuess's matching: kpts float32 (n, cap, 2) the frames' keypoints, proj float32 (m, cap, 2) each job's projected
+        from-points (project_points; NaN = not a query). Returns as match()."""
+        import torch
+
+        n, cap, c1 = self._match_store(desc, count)
+        j = _jobs_array(jobs)
+        for t, shape in ((kpts, (n, cap, 2)), (proj, (j.shape[0], cap, 2))):
+            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+                raise StereoBMError(-2, f"expected a contiguous float32 CUDA tensor {shape}")
+        p = params if params is not None else match_params()
+        pairs, npairs, rec = self._match_out(j.shape[0], cap, knn, desc.device)
+        torch.cuda.current_stream(desc.device).synchronize()
+        _check(self._L.sbm_match_guess_device(self._h, n, j.shape[0], j.ctypes.data, desc.data_ptr(), c1.data_ptr(), cap,
+                                              kpts.data_ptr(), proj.data_ptr(), ctypes.byref(p), pairs.data_ptr(),
+                                              npairs.data_ptr(), None if rec is None else rec.data_ptr(), 1 if sync else 0),
+               self._h)
+        if not sync:
+            self._inflight.append((desc, c1, kpts, proj, pairs, npairs, rec))
+        return (pairs, npairs, rec) if knn else (pairs, npairs)
+
+    def project_points(self, xyz, count, from_frames, T, K, size, sync=True):
+        """matchingGuess_Projection for m jobs: xyz float32 (n, cap, 3) and count int32 (n,) on the device, from_frames (m,) ints,
+        T (m, 12) float32 (guessCameraRef per job), K = (fx, fy, cx, cy), size = (W, H). Returns float32 (m, cap, 2), NaN where
+        a point is not valid."""
+        import torch
+
+        if xyz.dtype != torch.float32 or xyz.dim() != 3 or xyz.shape[2] != 3 or not xyz.is_contiguous() or not xyz.is_cuda:
+            raise StereoBMError(-2, "xyz must be a contiguous float32 CUDA tensor (n, cap, 3)")
+        n, cap = xyz.shape[0], xyz.shape[1]
+        c1 = count.reshape(-1)
+        if c1.dtype != torch.int32 or c1.numel() != n or not c1.is_cuda or not c1.is_contiguous():
+            raise StereoBMError(-2, "count must be a contiguous int32 CUDA tensor of n values")
+        fr = np.ascontiguousarray(np.asarray(from_frames, np.int32).reshape(-1))
+        m = fr.shape[0]
+        Tm = np.ascontiguousarray(np.asarray(T, np.float32).reshape(m, 12))
+        Kd = np.ascontiguousarray(np.asarray(K, np.float64).reshape(4))
+        proj = torch.zeros((max(m, 1), cap, 2), dtype=torch.float32, device=xyz.device)
+        torch.cuda.current_stream(xyz.device).synchronize()
+        _check(self._L.sbm_project_points_device(self._h, n, m, fr.ctypes.data, xyz.data_ptr(), c1.data_ptr(), cap, Tm.ctypes.data,
+                                                 Kd.ctypes.data, int(size[0]), int(size[1]), proj.data_ptr(), 1 if sync else 0),
+               self._h)
+        if not sync:
+            self._inflight.append((xyz, c1, proj))
+        return proj
+
+    @staticmethod
+    def _desc_rows(d):
+        d = np.asarray(d, dtype=np.uint8).reshape(-1, 32)
+        if d.strides[1] != 1:
+            d = np.ascontiguousarray(d)
+        return d
+
+    def match_host(self, desc_from, desc_to, params=None):
+        """matchingNoGuess(descriptorsFrom, descriptorsTo) on (k, 32) uint8 host rows (row stride may exceed 32): (k, 2) int32
+        (from, to) pairs in increasing from."""
+        a, b = self._desc_rows(desc_from), self._desc_rows(desc_to)
+        p = params if params is not None else match_params()
+        out = np.zeros((max(a.shape[0], 1), 2), np.int32)
+        k = ctypes.c_int()
+        _check(self._L.sbm_match(self._h, a.ctypes.data, a.strides[0], a.shape[0], b.ctypes.data, b.strides[0], b.shape[0],
+                                 ctypes.byref(p), out.ctypes.data, ctypes.byref(k)), self._h)
+        return out[:k.value].copy()
+
+    def match_guess_host(self, xyz_from, kpts_to, desc_from, desc_to, T, K, size, params=None):
+        """matchingGuess on host arrays: xyz_from (nf, 3) float32, kpts_to (nt, 2) float32, both descriptor sets, T (12,)
+        float32 guessCameraRef, K = (fx, fy, cx, cy), size = (W, H). Returns (k, 2) int32 pairs."""
+        a, b = self._desc_rows(desc_from), self._desc_rows(desc_to)
+        x = np.ascontiguousarray(np.asarray(xyz_from, np.float32).reshape(-1, 3))
+        kp = np.ascontiguousarray(np.asarray(kpts_to, np.float32).reshape(-1, 2))
+        if x.shape[0] != a.shape[0] or kp.shape[0] != b.shape[0]:
+            raise StereoBMError(-2, "one 3-D point per from-row and one keypoint per to-row")
+        x1 = x if x.shape[0] else np.zeros((1, 3), np.float32)
+        k1 = kp if kp.shape[0] else np.zeros((1, 2), np.float32)
+        Tm = np.ascontiguousarray(np.asarray(T, np.float32).reshape(12))
+        Kd = np.ascontiguousarray(np.asarray(K, np.float64).reshape(4))
+        p = params if params is not None else match_params()
+        out = np.zeros((max(a.shape[0], 1), 2), np.int32)
+        k = ctypes.c_int()
+        _check(self._L.sbm_match_guess(self._h, x1.ctypes.data, k1.ctypes.data, a.ctypes.data, a.strides[0], a.shape[0],
+                                       b.ctypes.data, b.strides[0], b.shape[0], Tm.ctypes.data, Kd.ctypes.data, int(size[0]),
+                                       int(size[1]), ctypes.byref(p), out.ctypes.data, ctypes.byref(k)), self._h)
+        return out[:k.value].copy()
+
+    def match_profile(self):
+        out = {}
+        for k in ("match_knn", "match_unique", "match_total", "match_project"):
+            v = ctypes.c_float()
+            _check(self._L.sbm_get_profile(self._h, k.encode(), ctypes.byref(v)), self._h)
+            out[k] = v.value
+        return out
 
     def orb_profile(self):
         out = {}
