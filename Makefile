@@ -8,7 +8,7 @@ HIPFLAGS ?= --offload-arch=gfx950 --offload-compress -O3 -std=c++17 -fPIC -Wall 
 SRCS := $(CSRC)/sbm_api.hip $(CSRC)/sbm_host.hip $(CSRC)/sbm_prefilter.hip $(CSRC)/sbm_sad_generic.hip $(CSRC)/sbm_sad_wide.hip $(CSRC)/sbm_sad_fast.hip $(CSRC)/sbm_sad_fast_pw1.hip $(CSRC)/sbm_sad_fast_pw2.hip $(CSRC)/sbm_sad_fast_pw3.hip $(CSRC)/sbm_lrcheck.hip $(CSRC)/sbm_speckle.hip $(CSRC)/sbm_consume.hip $(CSRC)/sbm_rectify.hip $(CSRC)/sbm_fpga.hip $(CSRC)/sbm_gftt.hip $(CSRC)/sbm_gftt_select.hip $(CSRC)/sbm_orb.hip $(CSRC)/sbm_match.hip $(CSRC)/sbm_sgbm.hip
 OBJS := $(SRCS:.hip=.o)
 
-all: $(LIB) oracle oracle_sgbm oracle_gftt oracle_orb oracle_match
+all: $(LIB) oracle
 
 FAST_HDRS := $(CSRC)/sbm_sad_fast_core.h $(CSRC)/sbm_sad_fast_strip.h $(CSRC)/sbm_sad_fast_kernel.h $(CSRC)/sbm_sad_border_wave.h
 $(CSRC)/sbm_sad_fast.o $(CSRC)/sbm_sad_fast_pw1.o $(CSRC)/sbm_sad_fast_pw2.o $(CSRC)/sbm_sad_fast_pw3.o: $(FAST_HDRS)
@@ -23,24 +23,8 @@ $(LIB): $(OBJS)
 oracle:
 	$(MAKE) -C oracle
 
-oracle_sgbm:
-	$(MAKE) -C oracle_sgbm
-
-oracle_gftt:
-	$(MAKE) -C oracle_gftt
-
-oracle_orb:
-	$(MAKE) -C oracle_orb
-
-oracle_match:
-	$(MAKE) -C oracle_match
-
 clean:
 	rm -f $(OBJS) $(LIB)
 	$(MAKE) -C oracle clean
-	$(MAKE) -C oracle_sgbm clean
-	$(MAKE) -C oracle_gftt clean
-	$(MAKE) -C oracle_orb clean
-	$(MAKE) -C oracle_match clean
 
-.PHONY: all oracle oracle_sgbm oracle_gftt oracle_orb oracle_match clean
+.PHONY: all oracle clean

@@ -1,34 +1,23 @@
-"""ctypes binding of the CPU restatement of generateKeypoints2 (oracle_gftt/libgftt_select_ref.so). TEST INFRASTRUCTURE ONLY.
+"""ctypes binding of the CPU restatement of generateKeypoints2 (oracle/libgftt_select_ref.so). TEST INFRASTRUCTURE ONLY.
 
 select(eig, max_eig, ...) takes one uint16 (H, W) map, dense or with a row stride, and returns float32 (k, 2) points (x, y) in
 acceptance order. The defaults are the reference's constants (GFTT.cpp:50-53).
 """
 import ctypes
-import pathlib
-import subprocess
 
 import numpy as np
 
-_HERE = pathlib.Path(__file__).resolve().parent
+import oracle_lib
+
 _LIB = None
 
 DEFAULTS = dict(max_features=1500, quality_level=0.01, min_distance=7.0, block_size=3)
 
 
-def build():
-    r = subprocess.run(["make", "-C", str(_HERE)], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("building the GFTT selection restatement failed:\n" + r.stdout + r.stderr)
-    return _HERE / "libgftt_select_ref.so"
-
-
 def lib():
     global _LIB
     if _LIB is None:
-        path = _HERE / "libgftt_select_ref.so"
-        if not path.exists():
-            build()
-        L = ctypes.CDLL(str(path))
+        L = oracle_lib.load("libgftt_select_ref.so")
         vp, sz, ci, cd = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_double
         L.gfsr_select.argtypes = [vp, sz, ci, ci, ctypes.c_uint, ci, cd, cd, vp, ctypes.c_long]
         L.gfsr_select.restype = ctypes.c_long

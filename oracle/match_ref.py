@@ -1,4 +1,4 @@
-"""The CPU restatement of matchingNoGuess / matchingGuess (oracle_match/libmatch_ref.so) through ctypes, and a literal numpy
+"""The CPU restatement of matchingNoGuess / matchingGuess (oracle/libmatch_ref.so) through ctypes, and a literal numpy
 transcription of the Registration.cpp loops that the C file is held to. TEST INFRASTRUCTURE ONLY.
 
     match(desc_from, desc_to, proj=None, kpts_to=None, radius=40.0, nndr=0.8, fused=False) -> (pairs (k, 2) int32, rec (nf, 4))
@@ -13,27 +13,19 @@ d0 == d1 -- NNDR rejects every such query, and the pairs are the same (test_matc
 import ctypes
 import math
 from fractions import Fraction
-import pathlib
-import subprocess
 
 import numpy as np
 
-_HERE = pathlib.Path(__file__).resolve().parent
+import oracle_lib
+
 _LIB = None
 NONE = 257
-
-
-def build():
-    r = subprocess.run(["make", "-C", str(_HERE)], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("building the matching restatement failed:\n" + r.stdout + r.stderr)
-    return _HERE / "libmatch_ref.so"
 
 
 def lib():
     global _LIB
     if _LIB is None:
-        L = ctypes.CDLL(str(build()))
+        L = oracle_lib.load("libmatch_ref.so")
         vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
         L.match_ref_hamming.argtypes = [vp, vp]
         L.match_ref_project.argtypes = [vp, ci, vp, vp, ci, ci, vp]

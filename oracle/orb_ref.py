@@ -1,4 +1,4 @@
-"""The CPU restatement of computeDescriptor (oracle_orb/liborb_ref.so) through ctypes, and a literal numpy transcription of the
+"""The CPU restatement of computeDescriptor (oracle/liborb_ref.so) through ctypes, and a literal numpy transcription of the
 same steps that the C file is held to. TEST INFRASTRUCTURE ONLY.
 
     describe(img, kpts, pattern, angle=-1.0, edge=19, half_up=False) -> (kept (k, 2) float32, desc (k, 32) uint8, blur (H, W))
@@ -11,30 +11,19 @@ keypoint is erased by the size rule (W or H <= 2 edge).
 """
 import ctypes
 import math
-import pathlib
-import subprocess
 
 import numpy as np
 
-_HERE = pathlib.Path(__file__).resolve().parent
+import oracle_lib
+
 _LIB = None
 BORDER = 23
-
-
-def build():
-    r = subprocess.run(["make", "-C", str(_HERE)], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("building the ORB restatement failed:\n" + r.stdout + r.stderr)
-    return _HERE / "liborb_ref.so"
 
 
 def lib():
     global _LIB
     if _LIB is None:
-        path = _HERE / "liborb_ref.so"
-        if not path.exists():
-            build()
-        L = ctypes.CDLL(str(path))
+        L = oracle_lib.load("liborb_ref.so")
         vp, ci, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
         L.orb_taps.argtypes = [vp]
         L.orb_taps.restype = None

@@ -7,11 +7,11 @@ package (u96-slam_amd/) never does. See oracle/sbm_oracle.h for what is restated
 import ctypes
 import os
 import pathlib
-import subprocess
 
 import numpy as np
 
-_HERE = pathlib.Path(__file__).resolve().parent
+import oracle_lib
+
 _LIB = None
 
 
@@ -85,24 +85,11 @@ def make_params(num_disparities=64, block_size=21, prefilter_cap=31, min_dispari
     return p
 
 
-def build(force=False):
-    so = _HERE / "libsbm_oracle.so"
-    srcs = [_HERE / "sbm_oracle.c", _HERE / "sbm_oracle_fpga.c", _HERE / "sbm_oracle_simd.c", _HERE / "sbm_oracle.h"]
-    if force or not so.exists() or so.stat().st_mtime < max(f.stat().st_mtime for f in srcs):
-        subprocess.run(["make", "-C", str(_HERE), "libsbm_oracle.so"], check=True, capture_output=True)
-    return so
-
-
 def lib():
     global _LIB
     if _LIB is None:
         override = os.environ.get("SBM_ORACLE_LIB")   # e.g. the sanitizer build, see oracle/Makefile
-        so = pathlib.Path(override).resolve() if override else build()
-        try:
-            L = ctypes.CDLL(str(so))
-        except OSError:
-            so = build(force=True)
-            L = ctypes.CDLL(str(so))
+        L = ctypes.CDLL(str(pathlib.Path(override).resolve())) if override else oracle_lib.load("libsbm_oracle.so")
         u8p, i16p, i32p = (ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int16), ctypes.POINTER(ctypes.c_int32))
         sz, ci = ctypes.c_size_t, ctypes.c_int
         pp = ctypes.POINTER(SbmParams)

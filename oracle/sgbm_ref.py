@@ -1,19 +1,15 @@
-"""ctypes binding of the CPU restatement of cv::StereoSGBM (oracle_sgbm/libsgbm_ref.so). TEST INFRASTRUCTURE ONLY.
+"""ctypes binding of the CPU restatement of cv::StereoSGBM (oracle/libsgbm_ref.so). TEST INFRASTRUCTURE ONLY.
 
 compute() runs sgbm_ref.c (costs, paths, selection, LR check, median) and then the block matcher's speckle restatement
 (sbm_oracle.filter_speckles) with newVal = (minDisparity - 1) * 16 and maxDiff = 16 * speckleRange, as
 cv::StereoSGBM::compute does.
 """
 import ctypes
-import pathlib
-import subprocess
-import sys
 
 import numpy as np
 
-_HERE = pathlib.Path(__file__).resolve().parent
-sys.path.insert(0, str(_HERE.parent / "oracle"))
-import sbm_oracle  # noqa: E402
+import oracle_lib
+import sbm_oracle
 
 _LIB = None
 
@@ -52,17 +48,10 @@ def width1(p, w):
     return w + min(p.min_disparity, 0) - max(p.min_disparity + p.num_disparities, 0)
 
 
-def build():
-    r = subprocess.run(["make", "-C", str(_HERE)], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("building the SGBM restatement failed:\n" + r.stdout + r.stderr)
-    return _HERE / "libsgbm_ref.so"
-
-
 def lib():
     global _LIB
     if _LIB is None:
-        L = ctypes.CDLL(str(build()))
+        L = oracle_lib.load("libsgbm_ref.so")
         vp, sz, ci = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
         L.sgbmr_compute.argtypes = [ctypes.POINTER(SgbmParams), vp, sz, vp, sz, ci, ci, vp, vp, vp, vp, ci]
         L.sgbmr_compute.restype = ci

@@ -1,4 +1,4 @@
-"""The CPU restatement of generateKeypoints2 (oracle_gftt/) against a literal Python transcription of GFTT.cpp:41-170: crafted
+"""The CPU restatement of generateKeypoints2 (oracle/gftt_select_ref.c) against a literal Python transcription of GFTT.cpp:41-170: crafted
 maps, every parameter edge, a seeded fuzz, strided maps and the prefix property of the cap."""
 import pathlib
 import sys
@@ -7,7 +7,6 @@ import numpy as np
 import pytest
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle_gftt"))
 sys.path.insert(0, str(ROOT / "tests"))
 import gftt_select_ref as ref  # noqa: E402
 from gftt_select_cases import PARAM_EDGES, crafted_maps, literal_generate_keypoints2, random_case  # noqa: E402

@@ -1,5 +1,5 @@
 """GPU keypoint selection (u96-slam_amd/csrc/sbm_gftt_select.hip) bit for bit against the CPU restatement of generateKeypoints2
-(oracle_gftt/): counts and every (x, y) in order, through the device, detect, host and asynchronous entry points."""
+(oracle/gftt_select_ref.c): counts and every (x, y) in order, through the device, detect, host and asynchronous entry points."""
 import pathlib
 import subprocess
 import sys
@@ -8,7 +8,6 @@ import numpy as np
 import pytest
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle_gftt"))
 sys.path.insert(0, str(ROOT / "tests"))
 import gftt_select_ref as ref  # noqa: E402
 from gftt_select_cases import PARAM_EDGES, crafted_maps, random_case  # noqa: E402

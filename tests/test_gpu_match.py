@@ -1,18 +1,17 @@
 """GPU keypoint matching (u96-slam_amd/csrc/sbm_match.hip) bit for bit against the CPU restatement of matchingNoGuess /
-matchingGuess (oracle_match/): every k-NN record, pair and count, in both modes and under both readings of the radius test, on
+matchingGuess (oracle/match_ref.c): every k-NN record, pair and count, in both modes and under both readings of the radius test, on
 descriptors the engine itself computed from the golden pair, synthetic frames at the 1 500-point cap, crafted sets, and through
 the projection, host, asynchronous and C++ entry points."""
 import ctypes
 import pathlib
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import match_ref as ref
+
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle_match"))
-import match_ref as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 READINGS = [False, True]

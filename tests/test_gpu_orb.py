@@ -1,18 +1,16 @@
-"""GPU ORB descriptors (u96-slam_amd/csrc/sbm_orb.hip) bit for bit against the CPU restatement of computeDescriptor (oracle_orb/):
+"""GPU ORB descriptors (u96-slam_amd/csrc/sbm_orb.hip) bit for bit against the CPU restatement of computeDescriptor (oracle/orb_ref.c):
 blurred frames, kept keypoints and counts, and every descriptor byte, under both readings of the blur's rounding, through the
 device, features, host and asynchronous entry points. The pattern is the reference's, from tests/golden/orb_pattern.npz."""
 import ctypes
 import pathlib
-import sys
 
 import numpy as np
 import pytest
 
+import gftt_select_ref as gref
+import orb_ref as ref
+
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle_orb"))
-sys.path.insert(0, str(ROOT / "oracle_gftt"))
-import gftt_select_ref as gref  # noqa: E402
-import orb_ref as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 READINGS = [False, True]

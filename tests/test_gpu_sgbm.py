@@ -1,16 +1,15 @@
-"""The semi-global matcher on the GPU against the CPU restatement (oracle_sgbm/), bit for bit: the reference's call on the golden
+"""The semi-global matcher on the GPU against the CPU restatement (oracle/sgbm_ref.c), bit for bit: the reference's call on the golden
 pair (Python mirror and the C++ call-site program), C and S stage by stage, a seeded fuzz over the parameter space, batches,
 host/device/asynchronous entry points, and every documented limit with the first value past it."""
 import pathlib
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import sgbm_ref
+
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle_sgbm"))
-import sgbm_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 HH, SG = sgbm_ref.MODE_HH, sgbm_ref.MODE_SGBM

@@ -1,4 +1,4 @@
-"""The semi-global matcher on the GPU against the CPU restatement (oracle_sgbm/), bit for bit, where the kernels' layout can go
+"""The semi-global matcher on the GPU against the CPU restatement (oracle/sgbm_ref.c), bit for bit, where the kernels' layout can go
 wrong: every lane layout of sgbm_path_kernel / sgbm_select_kernel (NV = 1/2/4/8 disparities per lane, fully and partly masked)
 with winners placed on purpose in lane 0, in the last active lane and on both sides of a lane boundary; path grids of 1-5 rows and
 63/64/65 columns with every chain count mod 4; whole frames at camera sizes (the reference call on a 640 x 480 batch, KITTI,
@@ -7,15 +7,11 @@ with winners placed on purpose in lane 0, in the last active lane and on both si
 Every case compares the whole final map with sgbm_ref.compute under the same parameters and reading; where the batch is one
 chunk it also compares C, S and the map before the median (debug_fetch 4 / 5 / 6)."""
 import concurrent.futures
-import pathlib
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle_sgbm"))
-import sgbm_ref  # noqa: E402
+import sgbm_ref
 
 pytestmark = pytest.mark.gpu
 HH, SG = sgbm_ref.MODE_HH, sgbm_ref.MODE_SGBM

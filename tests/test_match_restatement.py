@@ -1,15 +1,10 @@
-"""The CPU restatement of matchingNoGuess / matchingGuess (oracle_match/match_ref.c) held to its literal numpy transcription of the
+"""The CPU restatement of matchingNoGuess / matchingGuess (oracle/match_ref.c) held to its literal numpy transcription of the
 Registration.cpp loops (match_ref.py), and the facts the restatement rests on: the NNDR rule as integers, the radius test at
 squared distances around 1 600 under both readings, and the projection's edge cases."""
-import pathlib
-import sys
-
 import numpy as np
 import pytest
 
-ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle_match"))
-import match_ref as ref  # noqa: E402
+import match_ref as ref
 
 
 def same(a, b, guided):

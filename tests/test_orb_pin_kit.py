@@ -8,7 +8,6 @@ import numpy as np
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 KIT = ROOT / "tests" / "golden" / "pin_kit_orb.npz"
 sys.path.insert(0, str(ROOT / "tools"))
-sys.path.insert(0, str(ROOT / "oracle_orb"))
 
 
 def test_kit_reproduces_from_restatement():

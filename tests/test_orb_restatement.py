@@ -1,16 +1,15 @@
-"""The CPU restatement of computeDescriptor (oracle_orb/orb_ref.c) held to its literal numpy transcription (orb_ref.py), and the
+"""The CPU restatement of computeDescriptor (oracle/orb_ref.c) held to its literal numpy transcription (orb_ref.py), and the
 facts the restatement rests on: the derived taps, the rotated pattern's distance from every rounding boundary at -1 degree, the
 border rule's edges."""
 import math
 import pathlib
-import sys
 
 import numpy as np
 import pytest
 
+import orb_ref as ref
+
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle_orb"))
-import orb_ref as ref  # noqa: E402
 
 
 @pytest.fixture(scope="module")

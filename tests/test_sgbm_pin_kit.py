@@ -11,7 +11,6 @@ import pytest
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 KIT = ROOT / "tests" / "golden" / "pin_kit_sgbm.npz"
 sys.path.insert(0, str(ROOT / "tools"))
-sys.path.insert(0, str(ROOT / "oracle_sgbm"))
 
 
 def test_kit_reproduces_from_restatement():
@@ -51,7 +50,7 @@ def StereoSGBM_create(**kw):
 
 @pytest.mark.parametrize("reading", [0, 32, 64, 96])
 def test_verifier_names_the_reading(tmp_path, reading):
-    (tmp_path / "cv2.py").write_text(STAND_IN.format(ref=str(ROOT / "oracle_sgbm")))
+    (tmp_path / "cv2.py").write_text(STAND_IN.format(ref=str(ROOT / "oracle")))
     env = dict(os.environ, PYTHONPATH=str(tmp_path), STAND_IN_READING=str(reading))
     r = subprocess.run([sys.executable, str(ROOT / "tools" / "verify_sgbm_with_opencv.py"), str(KIT)], capture_output=True,
                        text=True, env=env, timeout=300)

@@ -1,18 +1,13 @@
-"""The CPU restatement of cv::StereoSGBM (oracle_sgbm/) against an independently written numpy textbook form, bit for bit.
+"""The CPU restatement of cv::StereoSGBM (oracle/sgbm_ref.c) against an independently written numpy textbook form, bit for bit.
 
-The textbook form below shares no code with oracle_sgbm/sgbm_ref.c: per-pixel Birchfield-Tomasi costs on whole arrays, an
+The textbook form below shares no code with oracle/sgbm_ref.c: per-pixel Birchfield-Tomasi costs on whole arrays, an
 explicit (2r+1)^2 box sum, one explicit loop per path direction, S = min(32767, sum of the path costs) (the envelope argument
 of include/sbm.h), the selection loop with x descending, the LR check, a 3x3 median by sorting and a flood-fill speckle filter.
 """
-import pathlib
-import sys
-
 import numpy as np
 import pytest
 
-ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle_sgbm"))
-import sgbm_ref  # noqa: E402
+import sgbm_ref
 
 HH, SG = sgbm_ref.MODE_HH, sgbm_ref.MODE_SGBM
 

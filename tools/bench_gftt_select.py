@@ -8,7 +8,7 @@ and print one JSON line:
   candidates_per_frame             interior pixels over the threshold (mean over the frames)
   scanned_per_frame                candidates taken in order until the last accepted point (mean): what the trim must see
   points_per_frame                 accepted points (mean)
-  restatement_host_ms              the CPU restatement (oracle_gftt/, single-threaded C) on one frame: for scale only
+  restatement_host_ms              the CPU restatement (oracle/gftt_select_ref.c, single-threaded C) on one frame: for scale only
 
   python tools/bench_gftt_select.py --frames golden|synth [--n 64] [--steps 20] [--warmup 3] [--out FILE]
 
@@ -27,7 +27,6 @@ import numpy as np
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "oracle"))
-sys.path.insert(0, str(ROOT / "oracle_gftt"))
 
 
 def frames(kind, n):

@@ -7,7 +7,7 @@ from 640 x 480 frames and print one JSON line:
   project_ms                     sbm_project_points_device for --n jobs
   pairs_per_job                  mean no-guess pair count
   bit_exact_first_8              pairs, counts and k-NN records of the first 8 jobs (both modes) equal the CPU restatement's
-  restatement_host_ms            the CPU restatement (oracle_match/, single-threaded C) of one no-guess job: for scale only
+  restatement_host_ms            the CPU restatement (oracle/match_ref.c, single-threaded C) of one no-guess job: for scale only
 
   python tools/bench_match.py --frames golden|synth [--n 64] [--steps 20] [--warmup 3] [--out FILE]
 
@@ -25,7 +25,7 @@ import numpy as np
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "oracle_match"))
+sys.path.insert(0, str(ROOT / "oracle"))
 
 K = (458.0, 457.0, 320.5, 240.5)
 

@@ -6,7 +6,7 @@ print one JSON line:
   features_ms / single_features_ms   the same for sbm_orb_features_device (detection + descriptors, one call)
   kept_per_frame                     keypoints left after the border rule (mean)
   bit_exact_first_8                  descriptors and kept points of the first 8 frames equal the CPU restatement's
-  restatement_host_ms                the CPU restatement (oracle_orb/, single-threaded C) on one frame: for scale only
+  restatement_host_ms                the CPU restatement (oracle/orb_ref.c, single-threaded C) on one frame: for scale only
 
   python tools/bench_orb.py --frames golden|synth [--n 64] [--steps 20] [--warmup 3] [--out FILE]
 
@@ -25,8 +25,6 @@ import numpy as np
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "oracle"))
-sys.path.insert(0, str(ROOT / "oracle_gftt"))
-sys.path.insert(0, str(ROOT / "oracle_orb"))
 
 
 def frames(kind, n):

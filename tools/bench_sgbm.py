@@ -6,7 +6,7 @@
   single_host_call_ms         wall time of the host entry point for one pair (the main.cpp:233 shape: copies in and out)
   stages_ms                   per-stage device time of one n-pair call (sbm_get_profile "sgbm_*", synchronised per chunk)
   algorithmic                 bytes the stages must move and path-update lane operations, and the bound they imply
-  restatement_host_ms         the CPU restatement (oracle_sgbm/, single-threaded C) on one pair: a port, for scale only
+  restatement_host_ms         the CPU restatement (oracle/sgbm_ref.c, single-threaded C) on one pair: a port, for scale only
 
   python tools/bench_sgbm.py --pairs 64 --steps 5 --warmup 2 [--out profiles/sgbm_bench.json]
 
@@ -22,7 +22,7 @@ import time
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "oracle_sgbm"))
+sys.path.insert(0, str(ROOT / "oracle"))
 
 REF_ARGS = (-64, 128, 11, 100, 1000, 32, 0, 15, 1000, 16, 1)
 HBM_TBS = 6.29   # measured copy bandwidth of the MI355X (profiles/hbm_calibration.json)

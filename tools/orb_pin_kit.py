@@ -8,7 +8,7 @@
 The frames are crafted: each is a grid of disjoint 7 x 7 blocks, and every block's centre is a tie (S = 65536 q + 32768) whose q
 alternates between even (the readings differ there) and odd (they agree). The kit holds, per frame, the blurred frame under
 both readings and, for every pixel that survives the border rule as a keypoint, the descriptors under both readings -- all from
-the CPU restatement (oracle_orb/); tests/test_gpu_orb.py holds the engine to the same arrays. Deterministic (fixed
+the CPU restatement (oracle/orb_ref.c); tests/test_gpu_orb.py holds the engine to the same arrays. Deterministic (fixed
 seeds): rerunning reproduces the committed kit bit for bit."""
 import pathlib
 import sys
@@ -16,7 +16,7 @@ import sys
 import numpy as np
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle_orb"))
+sys.path.insert(0, str(ROOT / "oracle"))
 OUT = ROOT / "tests" / "golden" / "pin_kit_orb.npz"
 BLOCKS = 10   # 10 x 10 blocks: 70 x 70 frames
 

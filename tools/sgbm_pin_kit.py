@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Write tests/golden/pin_kit_sgbm.npz: inputs, cv::StereoSGBM parameters and this engine's outputs (via the CPU restatement
-it is bit-exact against, oracle_sgbm/) under every combination of the SGBM readings nobody could pin (SBM_CV_READING bits
+it is bit-exact against, oracle/sgbm_ref.c) under every combination of the SGBM readings nobody could pin (SBM_CV_READING bits
 32 = no medianBlur, 64 = bottom rows with a clamped window). tools/verify_sgbm_with_opencv.py runs a real OpenCV on the kit
 and names the reading it implements.
 
@@ -15,7 +15,7 @@ import sys
 import numpy as np
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle_sgbm"))
+sys.path.insert(0, str(ROOT / "oracle"))
 import sgbm_ref  # noqa: E402
 
 READINGS = (0, sgbm_ref.READ_NO_MEDIAN, sgbm_ref.READ_BOTTOM_CLAMPED, sgbm_ref.READ_NO_MEDIAN | sgbm_ref.READ_BOTTOM_CLAMPED)

@@ -6,7 +6,7 @@ For every case it runs cv2.StereoSGBM_create with the stored parameters on the s
 engine's map under each stored reading of SBM_CV_READING (bit 32: no medianBlur stage, bit 64: bottom rows with a clamped
 window). It prints, per case, the readings that agree (or the pixel count of the closest one), and at the end the reading that
 agrees on every case -- the engine's default is 0; any other value is a default flip (u96-slam_amd/csrc/sbm_common.h
-kReadSgbm*, oracle_sgbm/sgbm_ref.c SGBMR_READ_*). Exit code 0 = reading 0 agrees everywhere."""
+kReadSgbm*, oracle/sgbm_ref.c SGBMR_READ_*). Exit code 0 = reading 0 agrees everywhere."""
 import sys
 
 import numpy as np
