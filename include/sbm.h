@@ -551,6 +551,132 @@ int sbm_match_guess(sbm_handle* h, const float* xyz_from, const float* kpts_to, 
                     const uint8_t* desc_to, size_t stride_to, int nt, const float* T, const double* K, int width, int height,
                     const sbm_match_params* p, int* pairs, int* npairs);
 
+/* ---- motion estimation: computeTransform's estimateMotion (src/slam/src/core/Registration.cpp:337-397) -----------------------
+ * What the reference does with the matcher's pairs: estimateMotion3DTo2D (MotionEstimation.cpp:59-241) -> its solvePnPRansac
+ * (:243-374, refineIterations 1, minInliers 20, refineSigma 3) -> cv3::solvePnPRansac / RANSACPointSetRegistrator
+ * (src/slam/src/opencv/CvSolvePnP.cpp). Restated as follows, per job (from frame f, to frame t, the matcher's pairs):
+ *   gather    (MotionEstimation.cpp:85-118, Registration.cpp:337-365) over the pairs in increasing from-index (std::map order,
+ *             the matcher's output order): object point xyz_from[f], image point kpts_to[t]; a pair whose 3-D point is not finite
+ *             in all three coordinates is dropped (and so is a pair with an index outside [0, min(count, cap))). N = what remains,
+ *             the reference's num_matches; matches = their from-indices. The motion guess has NO effect on the output (EPnP ignores
+ *             useExtrinsicGuess, the refine starts from the RANSAC model, and the guess is echoed only when RANSAC fails, which
+ *             returns a null transform), so no guess is taken. N < min_inliers: SBM_PNP_FEW_MATCHES.
+ *   RANSAC    (CvSolvePnP.cpp:112-210, 216-236, 326-419) six-point EPnP hypotheses, at most `iterations`, confidence 0.99.
+ *             cv::RNG((uint64)-1) re-seeded per job; uniform(0, N) = the multiply-with-carry step state = (uint64)(unsigned)state *
+ *             4164903690 + (state >> 32), draw (unsigned)state % N; getSubset redraws duplicates; no partial-subset checks and the
+ *             default checkSubset, so the subsets depend on N alone. Inlier test: computeError returns the NORM of the residual
+ *             and findInliers compares it with threshold * threshold: err <= 4.0f px for reprojection_error 2. A hypothesis
+ *             becomes the best iff its count > max(best, 5) (the earliest wins a tie), and then niters = RANSACUpdateNumIters(0.99,
+ *             (N - count) / N, 6, niters). N == 6: one EPnP on all six, every point an inlier, no scoring. The final EPnP over
+ *             all inliers (:180-184) is dead (its pose is overwritten by the best model; EPnP always succeeds): not run. P3P
+ *             (N == 4) cannot be reached. No hypothesis scores above 5: SBM_PNP_NO_MODEL (no inliers).
+ *   refine    (MotionEstimation.cpp:291-373) when the RANSAC inliers number >= min_inliers and refine_iterations > 0: per round,
+ *             cv::solvePnP(ITERATIVE, useExtrinsicGuess) on the current inlier set (Levenberg-Marquardt, at most 20 iterations),
+ *             then computeReprojErrors over all N points (e = (float)norm(residual) <= threshold, no squaring here), the float
+ *             variance and threshold = min(reprojection_error, refine_sigma * sqrt(variance)); the loop breaks when the new set
+ *             has fewer than min_inliers points or equals the current one. The std::swap pair at the end: on a normal exit the
+ *             inlier list is the set the last solve RAN ON (for one round: the RANSAC set), on a break the set the last
+ *             reprojection PRODUCED. The pose is always the refined one (new_rvec shares rvec's data).
+ *   result    (MotionEstimation.cpp:120-241) final inliers < min_inliers: SBM_PNP_FEW_RANSAC_INLIERS (no refine ran) or
+ *             SBM_PNP_FEW_REFINED_INLIERS, null transform. Else SBM_PNP_OK: R = Rodrigues(rvec), transform =
+ *             (localTransform * pnp).inverse() in the reference's float Transform arithmetic, and the covariance scales: medians
+ *             (element size >> 1 after sorting) of the squared 3-D distances and of the acos angles over the inliers whose
+ *             xyz_to[t] is finite, each clamped below at 1e-4 (1 when there is no such inlier: covariance = identity). The inlier
+ *             list (from-indices) is written whatever the status, as the reference returns it.
+ * Deviations and readings (recalled from OpenCV code that is not vendored, NOT pinned -- as the radius test of the matcher):
+ * EPnP's control points (PCA of the points), barycentric coordinates (cvInvert by SVD), M^T M and its SVD, the betas
+ * (cvSolve by SVD) and epnp::qr_solve's Gauss-Newton; cv::SVD as a one-sided Jacobi SVD with hypot read as sqrt(p*p + b*b);
+ * undistortPoints' float normalisation of the image points; projectPoints' zero-distortion arithmetic; Rodrigues both ways
+ * (R -> rvec without OpenCV's SVD re-orthonormalisation); CvLevMarq's step schedule (lambda 10^-3, x10 on a worse error up to
+ * 10^16, /10 otherwise, stop at 20 iterations or a relative step < FLT_EPSILON) and its 6 x 6 solve by SVD; the Eigen float
+ * product, quaternion renormalisation and 4 x 4 inverse of Transform. RANSAC scores each hypothesis with R, t as EPnP
+ * produced them (OpenCV round-trips through rvec; that moves the pose by ulps). With has_local == 0 (or no model) the
+ * localTransform product is skipped.
+ * Parity contract (GPU vs the sequential C restatement, tests/pnp_ref): bit for bit -- N, every subset, every hypothesis' R, t
+ * and count, the best iteration, the final niters and the RANSAC inliers. Refined pose (rvec, tvec, R): 1e-9 relative (the
+ * transcendental functions of Rodrigues differ between host and device libraries by ulps); transform and covariance scales:
+ * float ulps (4 ulps relative to the largest entry); status, num_matches, num_inliers and the inlier list exact except for a
+ * point whose residual lies within 1e-6 px of the refine threshold. A degenerate job whose refine runs the translation off
+ * towards infinity (|t| >= 1e6, e.g. every image point alike) amplifies those ulps without bound: only its exact fields are
+ * compared. RANSACUpdateNumIters' log / pow differ between libraries
+ * too: for every N <= 4096 and every count, num / denom lies farther than 1e-9 from a multiple of 0.5, so the rounding, and
+ * with it niters, cannot differ (tests/test_pnp_restatement.py walks it). That argument is shown for N <= 4 096 only; above it
+ * (up to the cap, 65 535) bit-for-bit niters and best iteration are expected but not proven.
+ * Store layout: d_xyz frame i's float (x, y, z) from i * cap * 3 (sbm_keypoints3d_device per frame), d_kpts frame i's float
+ * (x, y) from i * cap * 2 (sbm_orb_describe_device's kept keypoints), d_count n int32 clamped to [0, cap]; job j = (from, to)
+ * frames in [0, n) reads the pairs d_pairs + j * cap (int32 pairs) and d_npairs[j] (clamped to [0, cap]) as sbm_match*_device
+ * writes them. Out: d_result m records; d_inliers m * cap int32, job j's list from j * cap (slots past num_inliers untouched);
+ * d_hyp NULL, or m * iterations sbm_pnp_hypothesis (for tests: every hypothesis, whether or not the RANSAC loop reached it;
+ * jobs without RANSAC hold subset -1, count -1, R = t = 0; N == 6: record 0 is the one solve, count 6).
+ * Limits (status codes): n, m >= 1 (SBM_ERR_BATCH), m <= 65 535 (SBM_ERR_UNSUPPORTED), cap 1..65 535 (SBM_ERR_SIZE), every
+ * frame index in [0, n) (SBM_ERR_SIZE), K finite with fx, fy != 0 (SBM_ERR_UNSUPPORTED); d_xyz, d_count, d_npairs, d_inliers
+ * 4-byte, d_kpts, d_pairs, d_result and d_hyp 8-byte aligned (SBM_ERR_UNSUPPORTED).
+ * Kernels: gather + draw (one workgroup per job), hypotheses (one lane per (job, iteration)), score (one
+ * wavefront per (job, iteration)), finish (one wavefront per job: the RANSAC replay, the refine with wavefront reductions, the
+ * transform and the covariance medians). Up to 64 jobs per launch sequence; handle scratch stays within 256 MiB. Everything is
+ * enqueued on the handle's stream; nothing synchronises the host unless sync != 0.
+ * sbm_get_profile: while profiling is enabled these calls synchronise and record "pnp_hyp" (gather, draw, hypotheses),
+ * "pnp_score", "pnp_refine" (replay, refine, result) and "pnp_total" (ms of the last call). */
+enum {
+  SBM_PNP_OK = 0,
+  SBM_PNP_FEW_MATCHES = 1,          /* N < min_inliers                                */
+  SBM_PNP_NO_MODEL = 2,             /* RANSAC found no model                          */
+  SBM_PNP_FEW_RANSAC_INLIERS = 3,   /* RANSAC's inliers < min_inliers (no refine ran) */
+  SBM_PNP_FEW_REFINED_INLIERS = 4   /* the refine left < min_inliers                  */
+};
+
+typedef struct sbm_pnp_params {
+  int32_t min_inliers;        /* minInliers, default 20; 6..65 535                                     */
+  int32_t refine_iterations;  /* refineIterations, default 1; 0..100                                   */
+  int32_t iterations;         /* RANSAC's iterationsCount, default 300; 1..1000                        */
+  float reprojection_error;   /* default 2.0f; finite, > 0 (RANSAC gates at its square)                */
+  float refine_sigma;         /* default 3.0f; finite, >= 0                                            */
+  int32_t pad;
+  double confidence;          /* default 0.99; in (0, 1)                                               */
+} sbm_pnp_params;
+
+/* One job's result: 216 bytes. */
+typedef struct sbm_pnp_result {
+  int32_t status;            /* SBM_PNP_*                                                               */
+  int32_t num_matches;       /* N                                                                       */
+  int32_t num_inliers;       /* length of the job's inlier list                                        */
+  int32_t ransac_inliers;    /* the best hypothesis' count (0 without a model)                         */
+  int32_t best_iteration;    /* the RANSAC iteration of the model, -1 without one                      */
+  int32_t niters;            /* RANSAC's final niters (0 when RANSAC did not run)                      */
+  int32_t refine_solves;     /* LM solves the refine ran                                               */
+  int32_t refine_exit;       /* -1 not run, 0 normal exit, 1 break: too few, 2 break: unchanged        */
+  double rvec[3];            /* the PnP pose (camera from object): rotation vector, translation, R    */
+  double tvec[3];
+  double R[9];
+  double cov_dist;           /* covariance scales: the 3 x 3 blocks of the identity are multiplied by */
+  double cov_angle;
+  float transform[12];       /* (localTransform * pnp).inverse(), 3 x 4 row-major; zeros unless OK    */
+} sbm_pnp_result;
+
+/* One RANSAC hypothesis (d_hyp): 128 bytes. */
+typedef struct sbm_pnp_hypothesis {
+  int32_t subset[6];
+  int32_t count;             /* inliers at err <= reprojection_error^2                                  */
+  int32_t pad;
+  double R[9];
+  double t[3];
+} sbm_pnp_hypothesis;
+
+/* Fill *p with the reference's values: 20, 1, 300, 2.0f, 3.0f, 0.99. */
+void sbm_pnp_params_default(sbm_pnp_params* p);
+/* SBM_ERR_NULL, SBM_ERR_UNSUPPORTED (a field outside the limits above), else SBM_OK. */
+int sbm_pnp_params_validate(const sbm_pnp_params* p);
+/* estimateMotion for m jobs (jobs: 2 * m host ints (from, to), copied with the call). K: fx, fy, cx, cy of the left camera (host
+ * doubles); model: NULL or the camera model whose localTransform (local, has_local) applies. */
+int sbm_estimate_motion_device(sbm_handle* h, int n, int m, const int* jobs, const void* d_xyz, const void* d_kpts, const void* d_count,
+                               int cap, const void* d_pairs, const void* d_npairs, const double* K, const sbm_stereo_model* model,
+                               const sbm_pnp_params* p, void* d_result, void* d_inliers, void* d_hyp, int sync);
+/* Host form for ONE job, shaped like estimateMotion: xyz_from nf float (x, y, z), kpts_to and xyz_to nt float pairs / triples,
+ * npairs (from, to) int32 pairs; inliers receives up to npairs from-indices. Synchronous. max(nf, nt, npairs) <= 65 535. */
+int sbm_estimate_motion(sbm_handle* h, const float* xyz_from, int nf, const float* kpts_to, const float* xyz_to, int nt,
+                        const int* pairs, int npairs, const double* K, const sbm_stereo_model* model, const sbm_pnp_params* p,
+                        sbm_pnp_result* result, int* inliers);
+
 /* ---- semi-global matcher: cv::StereoSGBM (the reference's DEPTH_METHOD_CV_SGBM, main.cpp:218-234) -------------------------
  * Restatement of cv::StereoSGBM::compute() for 8-bit single-channel pairs in MODE_HH (two passes, 8 paths: the reference's
  * mode, main.cpp:219-230) and MODE_SGBM (OpenCV's default: one pass, 5 paths). Output contract as for the block matcher:

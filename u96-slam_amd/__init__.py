@@ -15,7 +15,8 @@ from .stereobm import (StereoBM, StereoBMError, SbmParams, StereoModel, library_
                        PREFILTER_NORMALIZED_RESPONSE, RectCam, make_rect_cam, PREFILTER_FLAVOUR_CV, PREFILTER_FLAVOUR_RTL, trim,
                        FpgaParams, fpga_params, fpga_params_from_regs, fpga_sad_size_reg, fpga_validate, compute_multi,
                        GfttSelectParams, gftt_select_params, gftt_select_validate, gftt_select_capacity,
-                       OrbParams, orb_params, orb_validate, MatchParams, match_params, match_validate)
+                       OrbParams, orb_params, orb_validate, MatchParams, match_params, match_validate,
+                       PnpParams, pnp_params, pnp_validate, pnp_records, PNP_RESULT_DTYPE, PNP_HYP_DTYPE)
 from .stereosgbm import StereoSGBM, SgbmParams, sgbm_params, sgbm_validate  # noqa: F401
 
 __all__ = ["StereoBM", "StereoBMError", "SbmParams", "StereoModel", "library_path", "load_library", "PREFILTER_XSOBEL",
@@ -23,4 +24,5 @@ __all__ = ["StereoBM", "StereoBMError", "SbmParams", "StereoModel", "library_pat
            "FpgaParams", "fpga_params", "fpga_params_from_regs", "fpga_sad_size_reg", "fpga_validate", "compute_multi",
            "StereoSGBM", "SgbmParams", "sgbm_params", "sgbm_validate", "GfttSelectParams", "gftt_select_params",
            "gftt_select_validate", "gftt_select_capacity", "OrbParams", "orb_params", "orb_validate", "MatchParams",
-           "match_params", "match_validate"]
+           "match_params", "match_validate", "PnpParams", "pnp_params", "pnp_validate", "pnp_records", "PNP_RESULT_DTYPE",
+           "PNP_HYP_DTYPE"]

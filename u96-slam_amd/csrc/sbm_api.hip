@@ -89,6 +89,7 @@ static void free_buffers(sbm_handle* h) {
   release_all(h->gs);
   release_all(h->orb);
   release_all(h->mt);
+  release_all(h->pnp);
 }
 
 // The reference re-creates its matcher for every frame (cv::StereoBM::create inside the loop, main.cpp:201). Streams,
@@ -102,7 +103,8 @@ static int g_pool_n = 0;
 
 static size_t scratch_bytes(sbm_handle* h) {
   return bytes_held(h->bm) + bytes_held(h->fp) + bytes_held(h->st) + h->pin_bytes + bytes_held(h->fq) + bytes_held(h->sg) +
-         bytes_held(h->gs) + bytes_held(h->orb) + bytes_held(h->mt);
+         bytes_held(h->gs) + bytes_held(h->orb) + bytes_held(h->mt) +
+         bytes_held(h->pnp);
 }
 
 // Stage times: the block matcher's, and every family's stage clock, start at zero.
@@ -116,6 +118,7 @@ static void reset_profile(sbm_handle* h, int enabled) {
   h->gs.clock.reset();
   h->orb.clock.reset();
   h->mt.clock.reset();
+  h->pnp.clock.reset();
 }
 
 static void destroy_now(sbm_handle* h);
@@ -159,6 +162,8 @@ int sbm_create(sbm_handle** out, const sbm_params* p, int device) {
   h->gs.clock.init(kGftt);
   h->orb.clock.init(kOrb);
   h->mt.clock.init(kMatch);
+  static const char* const kPnp[] = {"pnp_hyp", "pnp_score", "pnp_refine", "pnp_total"};
+  h->pnp.clock.init(kPnp);
   DeviceScope dscope(device);
   if (dscope.enter() != hipSuccess) {
     delete h;
@@ -217,6 +222,7 @@ static void destroy_now(sbm_handle* h) {
   h->gs.clock.release();
   h->orb.clock.release();
   h->mt.clock.release();
+  h->pnp.clock.release();
   for (int r = 0; r < sbm_handle::kRing; r++)
     for (int i = 0; i < sbm_handle::kMarks; i++)
       if (h->ev[r][i]) hipEventDestroy(h->ev[r][i]);
@@ -553,6 +559,7 @@ int sbm_get_profile(sbm_handle* h, const char* name, float* ms) {
     if (!t) t = h->gs.clock.find(name);
     if (!t) t = h->orb.clock.find(name);
     if (!t) t = h->mt.clock.find(name);
+    if (!t) t = h->pnp.clock.find(name);
     if (!t) return SBM_ERR_UNSUPPORTED;
     *ms = *t;
   }

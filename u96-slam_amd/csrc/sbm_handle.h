@@ -222,6 +222,11 @@ struct sbm_handle {
     sbm::StageClock clock;
     template <class F> void each(F f) { f(scratch); f(io); }
   } mt;
+  struct {   // motion estimation: compacted points, subsets, hypotheses, counts and refine lists of one launch; host-form staging
+    sbm::DevBuf scratch, io;
+    sbm::StageClock clock;
+    template <class F> void each(F f) { f(scratch); f(io); }
+  } pnp;
 };
 
 namespace sbm {
