@@ -82,7 +82,8 @@
  *                                          reading a given OpenCV implements -- adopting it is a default flip here, not a rewrite;
  *                                          bits 32 and 64 belong to the semi-global matcher (see sbm_sgbm_params below),
  *                                          bit 128 to the ORB descriptor's blur (see sbm_orb_params below),
- *                                          bit 256 to the keypoint matcher's radius test (see sbm_match_params below)
+ *                                          bit 256 to the keypoint matcher's radius test (see sbm_match_params below),
+ *                                          bit 512 to cv::goodFeaturesToTrack's float sums (see sbm_gftt_cv_params below)
  * The Python mirror adds SBM_LIB_AB (file name of another build of this library inside u96-slam_amd/lib/, A-B measurements
  * only); bench.py reads SBM_BENCH_BACKEND / SBM_BENCH_FEED / SBM_BENCH_SG_FAULT (tests of its multi-process control flow).
  */
@@ -419,6 +420,98 @@ int sbm_gftt_select(sbm_handle* h, const uint16_t* eig, size_t eig_stride, int w
 int sbm_gftt_detect_device(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_select_params* p,
                            void* d_eig, void* d_max, void* d_kpts, void* d_count, int sync);
 
+/* ---- GFTT keypoints of OpenCV: generateKeypoints (src/slam/src/core/GFTT.cpp:11-25; main.cpp:239) ---------------------------
+ * The detector of the reference's KPTS_METHOD_CV_GFTT modes (SLAM_BATCH among them, Parameters.cpp:163-168):
+ * cv::GFTTDetector::create(1500, 0.01, 7.0, 3, false, 0.04)->detect(img, kpts) (GFTT.cpp:13-24 holds those six constants), i.e.
+ * cv::goodFeaturesToTrack on the 8-bit frame without a mask. OpenCV is not part of the reference tree: every step below is
+ * RECALLED from OpenCV's imgproc (cornerMinEigenVal, Sobel / sepFilter2D, boxFilter, goodFeaturesToTrack), NOT pinned by anything
+ * here, unless it says otherwise. The engine, tests/gftt_cv_ref (sequential C and a numpy transcription of this text) and
+ * tests/golden/pin_kit_gftt_cv.npz implement exactly this text; all arithmetic is IEEE binary32 / binary64 without contraction.
+ *   scale     s = (float)(1.0 / (4 * 3 * 255.0)): 1 / (2^(aperture - 1) * blockSize * 255) in double, aperture 3, blockSize 3,
+ *             rounded to float with the Sobel kernel it multiplies; f1 = s, f0 = 2 * s (exact).
+ *   image     p[y][x] with BORDER_REFLECT_101 outside the frame (p[-1] = p[1], p[n] = p[n - 2]).
+ *   tap       the scaled symmetric three-tap: tap(c, q) = f1 * q + f0 * c, both products and the sum rounded to float; q is the
+ *             sum of the two outer samples. Bit 512 of SBM_CV_READING: tap(c, q) = fmaf(f1, q, f0 * c), what a contracting
+ *             build makes of OpenCV's `s0 = f0 * c; s0 += f1 * (a + b)` (the precedent is bit 256).
+ *   Dx        rows first, taps [-1, 0, 1] on the pixels: d[y][x] = p[y][x + 1] - p[y][x - 1], an exact integer; then columns:
+ *             dx = tap(d[y][x], d[y - 1][x] + d[y + 1][x]) (the integer sum is exact in float).
+ *   Dy        rows first: r[y][x] = tap(p[y][x], p[y][x - 1] + p[y][x + 1]) (integers, exact in float); then columns, taps
+ *             [-1, 0, 1]: dy = r[y + 1][x] - r[y - 1][x], rounded to float.
+ *   products  xx = dx * dx, xy = dx * dy, yy = dy * dy, each rounded to float, at every pixel of the frame.
+ *   box       unnormalised 3 x 3 sum of each product plane, BORDER_REFLECT_101 OF THE PRODUCT PLANE (the product at column -1 is
+ *             the product at column 1; it is not recomputed from the reflected image, whose dx changes sign there). For a float
+ *             source OpenCV's box filter accumulates in double and rounds once: here, per row the three products are added
+ *             left to right in double, the three row sums top to bottom in double, and the result is rounded to float. OpenCV
+ *             slides its row and column sums (add the entering value, subtract the leaving one); the two agree wherever every
+ *             partial sum is exact in 53 bits. That holds for the dx products (|dx| is 0 or at least about s, at most 1 / 3: 24-bit
+ *             values whose exponents span about 20 bits) but is NOT shown for dy, which is a rounded difference of rounded
+ *             floats and can be a tiny non-zero value where the exact difference is 0; there the last bit of the double sum --
+ *             29 bits below the float result's -- could depend on the order. The order above is the contract. The alternative
+ *             reading "float sums" was judged not live (createBoxFilter picks a double sum type for every float source) and has
+ *             no bit; bit 1024 stays free.
+ *   eig       a = xx * 0.5f; b = xy; c = yy * 0.5f; eig = (a + c) - sqrtf((a - c) * (a - c) + b * b), all float, the square
+ *             root correctly rounded. Bit 512: the radicand is fmaf(a - c, a - c, b * b). Rounding can leave eig a few ulps
+ *             below zero (or -0); no value is NaN.
+ *   maximum   over the whole map, borders included, in the total order "numeric, -0 below +0" (the order of the float's bit
+ *             pattern after the usual flip: bits ^ 0x80000000 for a clear sign bit, ~bits for a set one; the engine reduces
+ *             with atomicMax on that key, so negative values order correctly too). d_max receives it as a float.
+ *   threshold thr = (float)((double)maximum * quality_level); t = v > thr ? v : 0.0f (THRESH_TOZERO).
+ *   candidate 1 <= y < H - 1, 1 <= x < W - 1, t != 0 and t equal to the maximum of t over the pixel's 3 x 3 neighbourhood (the
+ *             dilation; every neighbour of an interior pixel is inside the frame). Each pixel of a plateau is a candidate.
+ *   order     value descending (float comparison; candidates are never +-0 or NaN, so that is the order of the flipped bit
+ *             pattern), ties by the HIGHER raster index y * W + x first: the deterministic greaterThanPtr the reference's
+ *             own copy carries (GFTT.cpp:31-39). (A stock OpenCV that sorts by value alone leaves ties to std::sort.)
+ *   trim      the cell table, the 3 x 3 cell test, the cap and the prefix property exactly as stated for generateKeypoints2 above
+ *             (min_distance >= 1: cells of cvRound(min_distance); min_distance < 1: no trim; stop after max_features > 0).
+ *   output    points (x, y) as float in acceptance order; the adaptor makes cv::KeyPoint(pt, (float)block_size).
+ * Out of scope: the Harris response (use_harris != 0 -> SBM_ERR_UNSUPPORTED; k is carried only), masks, block_size other than
+ * 3 (SBM_ERR_UNSUPPORTED), apertures other than 3, colour input, sub-pixel refinement.
+ * Limits: width and height 3..2048 (SBM_ERR_SIZE below 3, SBM_ERR_UNSUPPORTED above 2048), at most 65 535 frames per call,
+ * quality_level finite and >= 0, min_distance finite and in [0, 255] (SBM_ERR_UNSUPPORTED otherwise); d_eig 4-byte aligned.
+ * Kernels: a tiled map kernel (frame tile with a 2-pixel halo in LDS -> products with a 1-pixel halo ->
+ * box, eigenvalue, one atomicMax per workgroup), a candidate kernel that appends 64-bit keys (flipped value << 32 | raster
+ * index) to a per-frame list, and one workgroup of 1024 threads per frame that sorts the list (in LDS up to 8192 keys, in the
+ * list itself beyond) and runs the trim shared with generateKeypoints2. Device scratch, held by the handle: per frame of a
+ * chunk 8 B times the next power of two >= (W - 2) * (H - 2) for the list (32 MiB at 2048 x 2048: every interior pixel can be a
+ * candidate), 4 B per pixel when d_eig is absent, and the cell table as above; a call works through its frames in chunks whose
+ * lists and maps stay within 256 MiB each (one frame at a time when a single frame is larger).
+ * sbm_get_profile: while profiling is enabled (any mode) these calls synchronise and record "gftt_cv_eig" (map and maximum),
+ * "gftt_cv_select" (candidates, order, trim) and "gftt_cv_total" (ms of the last call, summed over its chunks). */
+typedef struct sbm_gftt_cv_params {  /* cv::GFTTDetector::create's arguments, in its order (GFTT.cpp:13-24) */
+  int32_t max_features;     /* maxCorners, default 1500; <= 0: no limit                          */
+  double quality_level;     /* qualityLevel, default 0.01                                        */
+  double min_distance;      /* minDistance, default 7.0                                          */
+  int32_t block_size;       /* blockSize, default 3 (nothing else is supported)                  */
+  int32_t use_harris;       /* useHarrisDetector, default 0 (nothing else is supported)          */
+  double k;                 /* Harris k, default 0.04; carried, unused                           */
+} sbm_gftt_cv_params;
+
+/* Fill *p with the reference's constants: 1500, 0.01, 7.0, 3, 0, 0.04. */
+void sbm_gftt_cv_params_default(sbm_gftt_cv_params* p);
+/* SBM_ERR_NULL, SBM_ERR_SIZE (width or height < 3), SBM_ERR_UNSUPPORTED (above 2048, block_size != 3, use_harris != 0, or a
+ * parameter outside the limits above), else SBM_OK. */
+int sbm_gftt_cv_params_validate(const sbm_gftt_cv_params* p, int width, int height);
+/* The map alone: n dense u8 frames in DEVICE memory -> d_eig n * height * width float, d_max n float (NULL: not wanted).
+ * Asynchronous on the handle's stream unless sync != 0. */
+int sbm_gftt_cv_eig_device(sbm_handle* h, int n, const void* d_img, int width, int height, void* d_eig, void* d_max, int sync);
+/* generateKeypoints on n dense u8 frames in DEVICE memory. d_kpts / d_count exactly as sbm_gftt_select_device writes them (cap =
+ * max_features > 0 ? max_features : (width - 2) * (height - 2); frame i's float pairs from i * cap * 2; entries past the count are
+ * left as they were), so sbm_orb_describe_device and sbm_keypoints3d_device take them as they are. d_eig (n * height * width
+ * float) and d_max (n float) are optional outputs: NULL = not wanted. Asynchronous on the handle's stream unless sync != 0. */
+int sbm_gftt_cv_detect_device(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_cv_params* p,
+                              void* d_eig, void* d_max, void* d_kpts, void* d_count, int sync);
+/* The selection alone, on maps the caller already has: d_eig n * height * width float and d_max n float (both required, read
+ * only; a d_max that is not the map's maximum moves the threshold, nothing else). Values must not be NaN. The sibling of
+ * sbm_gftt_select_device; it is also how a map of equal values -- every interior pixel a candidate, which no frame produces
+ * through the map above, whose reflected border forces dx = 0 in column 0 -- reaches the ordering and the trim. */
+int sbm_gftt_cv_select_device(sbm_handle* h, int n, const void* d_eig, const void* d_max, int width, int height,
+                              const sbm_gftt_cv_params* p, void* d_kpts, void* d_count, int sync);
+/* Host form for ONE frame, shaped like generateKeypoints(img, kpts2d): img strided (img_stride in bytes), kpts at least cap float
+ * pairs (capacity counts pairs; SBM_ERR_SIZE below cap), *count receives the number of points. Synchronous. */
+int sbm_gftt_cv_detect(sbm_handle* h, const uint8_t* img, size_t img_stride, int width, int height, const sbm_gftt_cv_params* p,
+                       float* kpts, size_t capacity, int* count);
+/* sbm_orb_features_cv_device, this detector followed by the descriptors in one call, is declared with the ORB entry points. */
+
 /* ---- ORB descriptors: computeDescriptor (src/slam/src/opencv/CvORB.cpp; main.cpp:246-248) ----------------------------------
  * The reference's descriptor step for the keypoints generateKeypoints2 produces (cv::KeyPoint(pt, blockSize): angle -1, octave
  * 0), on the device, so that a frame's keypoints, descriptors and depth stay there. What the reference computes at level 0:
@@ -475,6 +568,13 @@ int sbm_orb_describe(sbm_handle* h, const uint8_t* img, size_t img_stride, int w
 int sbm_orb_features_device(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_select_params* gp,
                             const int* pattern, const sbm_orb_params* p, void* d_eig, void* d_max, void* d_kpts, void* d_count,
                             void* d_desc, void* d_blur, int sync);
+
+/* The whole KPTS_METHOD_CV_GFTT + desc front end (SLAM_BATCH's) on n dense u8 frames: sbm_gftt_cv_detect_device (d_eig, d_max
+ * optional as there), then sbm_orb_describe_device on its output with the keypoints compacted in place, in one call on the
+ * handle's stream. The detector's limits apply. */
+int sbm_orb_features_cv_device(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_cv_params* gp,
+                               const int* pattern, const sbm_orb_params* p, void* d_eig, void* d_max, void* d_kpts, void* d_count,
+                               void* d_desc, void* d_blur, int sync);
 
 /* ---- keypoint matching: computeTransform's matchingNoGuess / matchingGuess (src/slam/src/core/Registration.cpp) --------------
  * What the reference does with a frame's descriptors first: match the current frame against the key frame, brute force on the

@@ -1,9 +1,10 @@
 // sbm_gftt.hpp -- header-only C++ adaptor for the keypoint selection of the reference's FPGA feature path (sbm.h,
-// sbm_gftt_select*), so that the call
+// sbm_gftt_select*) and for the OpenCV detector of its CV_GFTT modes (sbm_gftt_cv*), so that the calls
 //
 //     generateKeypoints2(eig, maxEigen, kpts2d);          // src/slam/src/core/main.cpp:241-243 (GFTT.cpp:41-170)
+//     generateKeypoints(imageLeft, kpts2d);               // src/slam/src/core/main.cpp:239     (GFTT.cpp:11-25)
 //
-// compiles against the MI355X engine unchanged once this header replaces GFTT.h's declaration. The
+// compile against the MI355X engine unchanged once this header replaces GFTT.h's declaration. The
 // reference-signature overload exists when OpenCV headers are present (SBM_HAVE_OPENCV, as in sbm_stereobm.hpp); it fills
 // cv::KeyPoint(pt, block_size) in acceptance order. The plain form takes a raw strided uint16 map and returns (x, y) pairs.
 // Failures throw sbm::Error.
@@ -83,6 +84,72 @@ inline void generateKeypoints2(const uint16_t* eig, size_t eig_stride, int width
 inline void generateKeypoints2(cv::Mat& eig, unsigned short max, std::vector<cv::KeyPoint>& kpts2d) {
   default_gftt_select().select(eig, max, kpts2d);
 }
+#endif
+
+// ---- generateKeypoints(img, kpts2d): the OpenCV detector of the CV_GFTT modes (src/slam/src/core/main.cpp:239, GFTT.cpp:11-25;
+// sbm.h, sbm_gftt_cv*) -- the frame goes in, cv::KeyPoint(pt, block_size) come out in acceptance order.
+class GfttCv {
+ public:
+  // the reference's constants (1500, 0.01, 7.0, 3, false, 0.04) unless p is given; `device` selects the HIP device
+  explicit GfttCv(int device = 0, const sbm_gftt_cv_params* p = nullptr) {
+    if (p) p_ = *p; else sbm_gftt_cv_params_default(&p_);
+    sbm_params bm;
+    sbm_params_default(&bm, 0, 0);   // the handle's block-matcher parameters are not used by the detector
+    check(sbm_create(&h_, &bm, device));
+  }
+  ~GfttCv() { sbm_destroy(h_); }
+  GfttCv(const GfttCv&) = delete;
+  GfttCv& operator=(const GfttCv&) = delete;
+
+  const sbm_gftt_cv_params& params() const { return p_; }
+  void setParams(const sbm_gftt_cv_params& p) { p_ = p; }
+  sbm_handle* handle() { return h_; }
+
+  // One strided 8-bit frame (stride in bytes) -> xy = x0, y0, x1, y1, ... in acceptance order.
+  void detect(const uint8_t* img, size_t img_stride, int width, int height, std::vector<float>& xy) {
+    const int vst = sbm_gftt_cv_params_validate(&p_, width, height);
+    if (vst != SBM_OK) check(vst);
+    const size_t cap = p_.max_features > 0 ? (size_t)p_.max_features : (size_t)(width - 2) * (height - 2);
+    xy.resize(2 * cap);
+    int k = 0;
+    check(sbm_gftt_cv_detect(h_, img, img_stride, width, height, &p_, xy.data(), cap, &k));
+    xy.resize(2 * (size_t)k);
+  }
+
+#ifdef SBM_HAVE_OPENCV
+  // generateKeypoints(img, kpts2d): img a CV_8UC1 frame (any row step)
+  void detect(cv::Mat& img, std::vector<cv::KeyPoint>& kpts2d) {
+#ifndef SBM_MOCK_OPENCV
+    if (img.depth() != CV_8U || img.channels() != 1) throw Error(SBM_ERR_SIZE, "img must be CV_8UC1");
+#endif
+    std::vector<float> xy;
+    detect(img.ptr<uint8_t>(0), (size_t)img.step, img.cols, img.rows, xy);
+    kpts2d.resize(xy.size() / 2);
+    for (size_t i = 0; i < kpts2d.size(); i++)
+      kpts2d[i] = cv::KeyPoint(cv::Point2f(xy[2 * i], xy[2 * i + 1]), (float)p_.block_size);
+  }
+#endif
+
+ private:
+  static void check(int st) {
+    if (st != SBM_OK) throw Error(st, sbm_strerror(st));
+  }
+  sbm_handle* h_ = nullptr;
+  sbm_gftt_cv_params p_;
+};
+
+// One detector per process on device 0, created at the first call (what the reference's free function needs).
+inline GfttCv& default_gftt_cv() {
+  static GfttCv s;
+  return s;
+}
+
+inline void generateKeypoints(const uint8_t* img, size_t img_stride, int width, int height, std::vector<float>& xy) {
+  default_gftt_cv().detect(img, img_stride, width, height, xy);
+}
+
+#ifdef SBM_HAVE_OPENCV
+inline void generateKeypoints(cv::Mat& img, std::vector<cv::KeyPoint>& kpts2d) { default_gftt_cv().detect(img, kpts2d); }
 #endif
 
 }  // namespace sbm

@@ -15,6 +15,7 @@ from .stereobm import (StereoBM, StereoBMError, SbmParams, StereoModel, library_
                        PREFILTER_NORMALIZED_RESPONSE, RectCam, make_rect_cam, PREFILTER_FLAVOUR_CV, PREFILTER_FLAVOUR_RTL, trim,
                        FpgaParams, fpga_params, fpga_params_from_regs, fpga_sad_size_reg, fpga_validate, compute_multi,
                        GfttSelectParams, gftt_select_params, gftt_select_validate, gftt_select_capacity,
+                       GfttCvParams, gftt_cv_params, gftt_cv_validate,
                        OrbParams, orb_params, orb_validate, MatchParams, match_params, match_validate,
                        PnpParams, pnp_params, pnp_validate, pnp_records, PNP_RESULT_DTYPE, PNP_HYP_DTYPE)
 from .stereosgbm import StereoSGBM, SgbmParams, sgbm_params, sgbm_validate  # noqa: F401
@@ -25,4 +26,4 @@ __all__ = ["StereoBM", "StereoBMError", "SbmParams", "StereoModel", "library_pat
            "StereoSGBM", "SgbmParams", "sgbm_params", "sgbm_validate", "GfttSelectParams", "gftt_select_params",
            "gftt_select_validate", "gftt_select_capacity", "OrbParams", "orb_params", "orb_validate", "MatchParams",
            "match_params", "match_validate", "PnpParams", "pnp_params", "pnp_validate", "pnp_records", "PNP_RESULT_DTYPE",
-           "PNP_HYP_DTYPE"]
+           "PNP_HYP_DTYPE", "GfttCvParams", "gftt_cv_params", "gftt_cv_validate"]

@@ -87,6 +87,7 @@ static void free_buffers(sbm_handle* h) {
   release_all(h->sg);
   h->sg.have_last = false;
   release_all(h->gs);
+  release_all(h->gc);
   release_all(h->orb);
   release_all(h->mt);
   release_all(h->pnp);
@@ -103,7 +104,7 @@ static int g_pool_n = 0;
 
 static size_t scratch_bytes(sbm_handle* h) {
   return bytes_held(h->bm) + bytes_held(h->fp) + bytes_held(h->st) + h->pin_bytes + bytes_held(h->fq) + bytes_held(h->sg) +
-         bytes_held(h->gs) + bytes_held(h->orb) + bytes_held(h->mt) +
+         bytes_held(h->gs) + bytes_held(h->gc) + bytes_held(h->orb) + bytes_held(h->mt) +
          bytes_held(h->pnp);
 }
 
@@ -116,6 +117,7 @@ static void reset_profile(sbm_handle* h, int enabled) {
   h->ms_prefilter = h->ms_sad = h->ms_border = h->ms_lr = h->ms_speckle = h->ms_total = 0.f;
   h->sg.clock.reset();
   h->gs.clock.reset();
+  h->gc.clock.reset();
   h->orb.clock.reset();
   h->mt.clock.reset();
   h->pnp.clock.reset();
@@ -164,6 +166,8 @@ int sbm_create(sbm_handle** out, const sbm_params* p, int device) {
   h->mt.clock.init(kMatch);
   static const char* const kPnp[] = {"pnp_hyp", "pnp_score", "pnp_refine", "pnp_total"};
   h->pnp.clock.init(kPnp);
+  static const char* const kGfttCv[] = {"gftt_cv_eig", "gftt_cv_select", "gftt_cv_total"};
+  h->gc.clock.init(kGfttCv);
   DeviceScope dscope(device);
   if (dscope.enter() != hipSuccess) {
     delete h;
@@ -220,6 +224,7 @@ static void destroy_now(sbm_handle* h) {
   free_buffers(h);
   h->sg.clock.release();
   h->gs.clock.release();
+  h->gc.clock.release();
   h->orb.clock.release();
   h->mt.clock.release();
   h->pnp.clock.release();
@@ -557,6 +562,7 @@ int sbm_get_profile(sbm_handle* h, const char* name, float* ms) {
   else {
     const float* t = h->sg.clock.find(name);
     if (!t) t = h->gs.clock.find(name);
+    if (!t) t = h->gc.clock.find(name);
     if (!t) t = h->orb.clock.find(name);
     if (!t) t = h->mt.clock.find(name);
     if (!t) t = h->pnp.clock.find(name);

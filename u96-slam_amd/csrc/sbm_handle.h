@@ -212,6 +212,12 @@ struct sbm_handle {
     sbm::StageClock clock;
     template <class F> void each(F f) { f(tab); f(out); }
   } gs;
+  struct {   // OpenCV-flavour keypoint detection: key lists, maxima and counts (and the maps nobody asked for) of one chunk of
+             // frames; the cell tables of the global-table kernel; the points and count of the host-memory entry point
+    sbm::DevBuf keys, small, eig, tab, out;
+    sbm::StageClock clock;
+    template <class F> void each(F f) { f(keys); f(small); f(eig); f(tab); f(out); }
+  } gc;
   struct {   // ORB descriptors: blurred frames of one chunk; the keypoints, counts and descriptors of the host-memory entry point
     sbm::DevBuf blur, io;
     sbm::StageClock clock;
@@ -238,6 +244,10 @@ int ensure_staging(sbm_handle* h, int n, int W, int H);
 // Keypoint selection of n maps on the handle's stream, the eigenvalue maps first when d_img is given (sbm_gftt_select.hip).
 int gftt_select_run(sbm_handle* h, int n, const void* d_img, const void* d_eig, const void* d_max, int width, int height,
                     const sbm_gftt_select_params* p, void* d_kpts, void* d_count, int sync);
+// cv::goodFeaturesToTrack on n dense frames on the handle's stream (sbm_gftt_cv.hip); d_eig, d_max and d_kpts / d_count may be
+// null (not wanted; without d_kpts only the maps are computed).
+int gftt_cv_run(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_cv_params* p, void* d_eig, void* d_max,
+                void* d_kpts, void* d_count, int sync);
 // sbm_debug_fetch of the last semi-global matcher call: which = 4 (C), 5 (S), 6 (the map before the median) (sbm_sgbm.hip).
 int sgbm_debug_fetch(sbm_handle* h, int which, void* dst, size_t dst_bytes);
 

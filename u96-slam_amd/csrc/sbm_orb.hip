@@ -323,6 +323,27 @@ int sbm_orb_features_device(sbm_handle* h, int n, const void* d_img, int width, 
   return orb_run(h, n, d_img, width, height, cap, d_kpts, d_count, offs, p, d_kpts, d_count, d_desc, d_blur, sync);
 }
 
+int sbm_orb_features_cv_device(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_cv_params* gp,
+                               const int* pattern, const sbm_orb_params* p, void* d_eig, void* d_max, void* d_kpts, void* d_count,
+                               void* d_desc, void* d_blur, int sync) {
+  if (!h || !gp || !d_img || !d_kpts || !d_count || !pattern || !p || !d_desc) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  int st = sbm_gftt_cv_params_validate(gp, width, height);
+  if (st == SBM_OK) st = sbm_orb_params_validate(p);
+  const int cap = gp->max_features > 0 ? gp->max_features : (width - 2) * (height - 2);
+  if (st == SBM_OK) st = orb_check(n, width, height, cap, d_kpts, d_kpts, d_desc);
+  if (st == SBM_OK && (((uintptr_t)d_eig & 3) || ((uintptr_t)d_max & 3))) st = SBM_ERR_UNSUPPORTED;
+  if (st != SBM_OK) return st;
+  OrbOffsets offs;
+  st = orb_offsets(pattern, p->angle, width, &offs);
+  if (st != SBM_OK) return st;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  st = gftt_cv_run(h, n, d_img, width, height, gp, d_eig, d_max, d_kpts, d_count, 0);
+  if (st != SBM_OK) return st;
+  return orb_run(h, n, d_img, width, height, cap, d_kpts, d_count, offs, p, d_kpts, d_count, d_desc, d_blur, sync);
+}
+
 int sbm_orb_describe(sbm_handle* h, const uint8_t* img, size_t img_stride, int width, int height, const float* kpts, int count,
                      const int* pattern, const sbm_orb_params* p, float* kpts_out, int* count_out, uint8_t* desc) {
   if (!h || !img || !pattern || !p || !count_out || (count > 0 && (!kpts || !kpts_out || !desc))) return SBM_ERR_NULL;

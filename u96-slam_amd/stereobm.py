@@ -116,6 +116,24 @@ def gftt_select_capacity(params, width, height):
     return params.max_features if params.max_features > 0 else (width - 2) * (height - 2)
 
 
+class GfttCvParams(ctypes.Structure):
+    """`sbm_gftt_cv_params` of include/sbm.h: cv::GFTTDetector::create's arguments (src/slam/src/core/GFTT.cpp:13-24)."""
+
+    _fields_ = [("max_features", ctypes.c_int32), ("quality_level", ctypes.c_double), ("min_distance", ctypes.c_double),
+                ("block_size", ctypes.c_int32), ("use_harris", ctypes.c_int32), ("k", ctypes.c_double)]
+
+
+def gftt_cv_params(max_features=1500, quality_level=0.01, min_distance=7.0, block_size=3, use_harris=False, k=0.04):
+    """The reference's constants by default."""
+    return GfttCvParams(int(max_features), float(quality_level), float(min_distance), int(block_size), int(bool(use_harris)),
+                        float(k))
+
+
+def gftt_cv_validate(params, width, height):
+    """Status code of sbm_gftt_cv_params_validate (0 = ok)."""
+    return load_library().sbm_gftt_cv_params_validate(ctypes.byref(params), width, height)
+
+
 class OrbParams(ctypes.Structure):
     """`sbm_orb_params` of include/sbm.h: computeDescriptor's constants (src/slam/src/opencv/CvORB.cpp) and the keypoints' angle."""
 
@@ -282,6 +300,14 @@ def load_library():
     L.sbm_gftt_select_device.argtypes = [vp, ci, vp, vp, ci, ci, gp, vp, vp, ci]
     L.sbm_gftt_select.argtypes = [vp, vp, sz, ci, ci, ctypes.c_uint16, gp, vp, sz, ctypes.POINTER(ctypes.c_int)]
     L.sbm_gftt_detect_device.argtypes = [vp, ci, vp, ci, ci, gp, vp, vp, vp, vp, ci]
+    gcp = ctypes.POINTER(GfttCvParams)
+    L.sbm_gftt_cv_params_default.argtypes = [gcp]
+    L.sbm_gftt_cv_params_default.restype = None
+    L.sbm_gftt_cv_params_validate.argtypes = [gcp, ci, ci]
+    L.sbm_gftt_cv_eig_device.argtypes = [vp, ci, vp, ci, ci, vp, vp, ci]
+    L.sbm_gftt_cv_detect_device.argtypes = [vp, ci, vp, ci, ci, gcp, vp, vp, vp, vp, ci]
+    L.sbm_gftt_cv_select_device.argtypes = [vp, ci, vp, vp, ci, ci, gcp, vp, vp, ci]
+    L.sbm_gftt_cv_detect.argtypes = [vp, vp, sz, ci, ci, gcp, vp, sz, ctypes.POINTER(ctypes.c_int)]
     op = ctypes.POINTER(OrbParams)
     L.sbm_orb_params_default.argtypes = [op]
     L.sbm_orb_params_default.restype = None
@@ -289,6 +315,7 @@ def load_library():
     L.sbm_orb_describe_device.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp, op, vp, vp, vp, vp, ci]
     L.sbm_orb_describe.argtypes = [vp, vp, sz, ci, ci, vp, ci, vp, op, vp, ctypes.POINTER(ctypes.c_int), vp]
     L.sbm_orb_features_device.argtypes = [vp, ci, vp, ci, ci, gp, vp, op, vp, vp, vp, vp, vp, vp, ci]
+    L.sbm_orb_features_cv_device.argtypes = [vp, ci, vp, ci, ci, gcp, vp, op, vp, vp, vp, vp, vp, vp, ci]
     mp_ = ctypes.POINTER(MatchParams)
     L.sbm_match_params_default.argtypes = [mp_]
     L.sbm_match_params_default.restype = None
@@ -743,6 +770,126 @@ class StereoBM:
         _check(self._L.sbm_gftt_select(self._h, eig.ctypes.data, eig.strides[0], w, h, int(max_eig) & 0xffff, ctypes.byref(p),
                                        out.ctypes.data, max(cap, 0), ctypes.byref(k)), self._h)
         return out[:k.value].copy()
+
+    # ---- OpenCV's detector: generateKeypoints (src/slam/src/core/GFTT.cpp:11-25) ------------------------------------------------
+    @staticmethod
+    def _gftt_cv_params(params, kw):
+        if params is None:
+            return gftt_cv_params(**kw)
+        if kw:
+            raise TypeError("pass either a GfttCvParams or keyword parameters")
+        return params
+
+    def gftt_cv_eig(self, img, sync=True):
+        """cv::cornerMinEigenVal (block 3, aperture 3) of torch CUDA uint8 frames (n,H,W) or (H,W), as include/sbm.h states it:
+        (float32 maps (n,H,W), float32 maxima (n,))."""
+        import torch
+
+        self._check_device_images(img)
+        i3 = (img if img.dim() == 3 else img[None]).contiguous()
+        n, h, w = i3.shape
+        eig = torch.empty((n, h, w), dtype=torch.float32, device=i3.device)
+        mx = torch.empty((n,), dtype=torch.float32, device=i3.device)
+        torch.cuda.current_stream(i3.device).synchronize()
+        _check(self._L.sbm_gftt_cv_eig_device(self._h, n, i3.data_ptr(), w, h, eig.data_ptr(), mx.data_ptr(), 1 if sync else 0),
+               self._h)
+        if not sync:
+            self._inflight.append((i3, eig, mx))
+        return eig, mx
+
+    def gftt_cv_detect(self, img, params=None, maps=True, sync=True, **kw):
+        """generateKeypoints on torch CUDA uint8 frames (n,H,W) or (H,W). Returns (kpts float32 (n, cap, 2), count int32 (n,)) in
+        gftt_select's layout, plus (maps (n,H,W) float32, maxima (n,) float32) when maps=True; maps=False passes no d_eig /
+        d_max (the maps then live in the engine's scratch only)."""
+        import torch
+
+        p = self._gftt_cv_params(params, kw)
+        self._check_device_images(img)
+        i3 = (img if img.dim() == 3 else img[None]).contiguous()
+        n, h, w = i3.shape
+        cap = gftt_select_capacity(p, w, h)
+        eig = torch.empty((n, h, w), dtype=torch.float32, device=i3.device) if maps else None
+        mx = torch.empty((n,), dtype=torch.float32, device=i3.device) if maps else None
+        kpts = torch.zeros((n, max(cap, 1), 2), dtype=torch.float32, device=i3.device)
+        count = torch.zeros((n,), dtype=torch.int32, device=i3.device)
+        torch.cuda.current_stream(i3.device).synchronize()
+        _check(self._L.sbm_gftt_cv_detect_device(self._h, n, i3.data_ptr(), w, h, ctypes.byref(p),
+                                                  eig.data_ptr() if maps else None, mx.data_ptr() if maps else None,
+                                                  kpts.data_ptr(), count.data_ptr(), 1 if sync else 0), self._h)
+        if not sync:
+            self._inflight.append((i3, eig, mx, kpts, count))
+        return (kpts, count, eig, mx) if maps else (kpts, count)
+
+    def gftt_cv_select(self, eig, mx, params=None, sync=True, **kw):
+        """The selection of generateKeypoints on float32 torch CUDA maps (n,H,W) or (H,W) and their maxima mx (n,) float32."""
+        import torch
+
+        p = self._gftt_cv_params(params, kw)
+        e3 = eig if eig.dim() == 3 else eig[None]
+        if e3.dim() != 3 or not e3.is_cuda or e3.dtype != torch.float32:
+            raise StereoBMError(-2, "eig must be a float32 torch CUDA (n,H,W) or (H,W) tensor")
+        e3 = e3.contiguous()
+        n, h, w = e3.shape
+        m1 = mx.reshape(-1).to(device=e3.device, dtype=torch.float32).contiguous()
+        if m1.numel() != n:
+            raise StereoBMError(-2, f"mx holds {m1.numel()} values for {n} maps")
+        cap = gftt_select_capacity(p, w, h)
+        kpts = torch.zeros((n, max(cap, 1), 2), dtype=torch.float32, device=e3.device)
+        count = torch.zeros((n,), dtype=torch.int32, device=e3.device)
+        torch.cuda.current_stream(e3.device).synchronize()
+        _check(self._L.sbm_gftt_cv_select_device(self._h, n, e3.data_ptr(), m1.data_ptr(), w, h, ctypes.byref(p), kpts.data_ptr(),
+                                                  count.data_ptr(), 1 if sync else 0), self._h)
+        if not sync:
+            self._inflight.append((e3, m1, kpts, count))
+        return kpts, count
+
+    def gftt_cv_detect_host(self, img, params=None, **kw):
+        """numpy uint8 (H,W) frame (rows may be strided) -> numpy float32 (k, 2) points, as generateKeypoints(img, kpts2d) fills
+        kpts2d."""
+        p = self._gftt_cv_params(params, kw)
+        if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or img.ndim != 2 or img.strides[1] != 1 or \
+                img.strides[0] < img.shape[1]:
+            raise StereoBMError(-2, "img must be an (H,W) uint8 array with dense rows")
+        h, w = img.shape
+        cap = gftt_select_capacity(p, w, h)
+        out = np.zeros((max(cap, 1), 2), np.float32)
+        k = ctypes.c_int()
+        _check(self._L.sbm_gftt_cv_detect(self._h, img.ctypes.data, img.strides[0], w, h, ctypes.byref(p), out.ctypes.data,
+                                          max(cap, 0), ctypes.byref(k)), self._h)
+        return out[:k.value].copy()
+
+    def orb_features_cv(self, img, pattern, gftt=None, angle=-1.0, edge_threshold=19, params=None, blur=False, sync=True, **kw):
+        """The KPTS_METHOD_CV_GFTT + desc front end (SLAM_BATCH's) on torch CUDA uint8 frames (n,H,W) or (H,W): generateKeypoints,
+        computeDescriptor, in one call. gftt: a GfttCvParams (or keyword parameters of gftt_cv_params). Returns (desc (n, cap,
+        32), kpts (n, cap, 2), count (n,)) [+ blurred frames]."""
+        import torch
+
+        gp = self._gftt_cv_params(gftt, kw)
+        p = self._orb_params(params, angle, edge_threshold)
+        pat = orb_pattern_array(pattern)
+        self._check_device_images(img)
+        i3 = (img if img.dim() == 3 else img[None]).contiguous()
+        n, h, w = i3.shape
+        cap = max(gftt_select_capacity(gp, w, h), 1)
+        kpts = torch.zeros((n, cap, 2), dtype=torch.float32, device=i3.device)
+        count = torch.zeros((n,), dtype=torch.int32, device=i3.device)
+        desc = torch.zeros((n, cap, 32), dtype=torch.uint8, device=i3.device)
+        bl = torch.zeros((n, h, w), dtype=torch.uint8, device=i3.device) if blur else None
+        torch.cuda.current_stream(i3.device).synchronize()
+        _check(self._L.sbm_orb_features_cv_device(self._h, n, i3.data_ptr(), w, h, ctypes.byref(gp), pat.ctypes.data,
+                                                   ctypes.byref(p), None, None, kpts.data_ptr(), count.data_ptr(), desc.data_ptr(),
+                                                   None if bl is None else bl.data_ptr(), 1 if sync else 0), self._h)
+        if not sync:
+            self._inflight.append((i3, kpts, count, desc, bl))
+        return (desc, kpts, count, bl) if blur else (desc, kpts, count)
+
+    def gftt_cv_profile(self):
+        out = {}
+        for k in ("gftt_cv_eig", "gftt_cv_select", "gftt_cv_total"):
+            v = ctypes.c_float()
+            _check(self._L.sbm_get_profile(self._h, k.encode(), ctypes.byref(v)), self._h)
+            out[k] = v.value
+        return out
 
     # ---- ORB descriptors of computeDescriptor (src/slam/src/opencv/CvORB.cpp) -------------------------------------------------
     @staticmethod
