@@ -52,7 +52,8 @@ constexpr int kReadLrTieLater = 16;       // validateDisparity: on equal cost th
 // With Geom::pfshift = 2 the planes store 4*value+1 (<= 253): every absolute difference, hence every SAD, is a multiple
 // of 4, which leaves the two low bits of the packed 16-bit sums free for a register tag in the interior kernel's
 // winner search (sbm_sad_fast.hip; chosen by sad_fast_pfshift() when 4*maxS still fits 16 bits; pfshift = 1: 2*value+1,
-// one tag bit, where only 2*maxS fits). The border wavefronts of the same launch work on the scaled sums too; only the
+// one tag bit, where only 2*maxS fits). The tag is carried by the sums themselves: one lane of every window starts its
+// vertical accumulators at the tag (FastTag, sbm_sad_fast_core.h). The border wavefronts of the same launch work on the scaled sums too; only the
 // uniqueness threshold and the stored cost go back to the unscaled sum.
 constexpr int kPfBias = 1;
 

@@ -134,21 +134,36 @@ struct DmaLds {
 // the smaller buffer index, as cv's strict '<' scan.
 // On pre-scaled planes (sbm_common.h, pfshift) every sum is a multiple of 4 (2), so the low bits of each packed half can carry a
 // register tag: registers j, j + NR/4, j + NR/2, j + 3NR/4 (tags 0..3 = the top two bits of the buffer index) are reduced with
-// packed 16-bit minima first -- one OR (a full-rate instruction) and one v_pk_min_u16 per register instead of two key builds and
-// a v_min3_u32 -- and only the NR/4 (NR/2 with one tag bit: windows 17..21, where only 2 maxS fits 16 bits) survivors get 32-bit
-// keys; the smaller (sum, tag, low index bits) triple is the smaller buffer index. One tagged variant per instantiation, chosen
-// by the window: a third alternative in the same body makes the register allocator spill hundreds of bytes everywhere.
+// packed 16-bit minima first -- one v_pk_min_u16 per register instead of two key builds and a v_min3_u32 -- and only the NR/4
+// (NR/2 with one tag bit: windows 17..21, where only 2 maxS fits 16 bits) survivors get 32-bit keys; the smaller (sum, tag, low
+// index bits) triple is the smaller buffer index. One tagged variant per instantiation, chosen by the window: a third
+// alternative in the same body makes the register allocator spill hundreds of bytes everywhere.
+// The sums ARRIVE tagged (FastTag): the tag of a register is the same on every row, so it is not ORed in here but carried by the
+// vertical sums from the start of the strip. A window sum is NTERM vertical sums at lane distance KS, lanes l + KS k, k < NTERM;
+// (l + KS k) / KS = l / KS + k runs over NTERM consecutive integers, exactly one of which is a multiple of NTERM. The lanes with
+// (lane / KS) % NTERM == 0 (carriers) start their accumulators at tag * 0x0001000100010001, all others at 0, so every window
+// sum -- direct or through the intermediate level of HPlan, which still adds every term exactly once -- holds its register's tag
+// exactly once, in the bits the scaling leaves free. The in-place accumulate adds on top of it and the leaving row takes away
+// less than it finds, as before; (maxS << pfshift) + tag fits a packed half by sad_fast_pfshift(). The untagged search below
+// (pfshift 0, or not this window's tag width) gets untagged sums: tag_unit() is 0 then.
+template <int WSZ>
+struct FastTag {
+  static constexpr int BITS = WSZ <= 15 ? 2 : 1;       // tag bits of this window's tagged search
+  static constexpr int NGRP = 1 << BITS;               // tag groups: NR / NGRP consecutive registers each
+  // 0x00010001 where the tagged search runs (wavefront-uniform, a scalar), else 0; times the group number = a register's tag
+  static __device__ __forceinline__ u32 tag_unit(const int pfshift) { return pfshift == BITS ? 0x00010001u : 0u; }
+};
 template <int NR, int WSZ>
 __device__ __forceinline__ u32 fast_first_min(const u32 (&S)[NR], const int pfshift) {
   u32 best = 0xffffffffu;
-  constexpr int TSMAX = WSZ <= 15 ? 2 : 1;
+  constexpr int TSMAX = FastTag<WSZ>::BITS;
   if (NR >= 16 && TSMAX == 2 && pfshift == 2) {
     constexpr int NG = NR / 4;
     u32 b[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
 #pragma unroll
     for (int j = 0; j < NG; j++) {
-      const u32 g01 = pk_min(S[j], S[j + NG] | 0x00010001u);
-      const u32 g23 = pk_min(S[j + 2 * NG] | 0x00020002u, S[j + 3 * NG] | 0x00030003u);
+      const u32 g01 = pk_min(S[j], S[j + NG]);                    // (tags 0..3 ride in the sums: FastTag)
+      const u32 g23 = pk_min(S[j + 2 * NG], S[j + 3 * NG]);
       const u32 gm = pk_min(g01, g23);
       const u32 klo = (gm << 16) | (u32)(2 * j);
       const u32 khi = (gm & 0xffff0000u) | (u32)(2 * j + 1);
@@ -159,10 +174,9 @@ __device__ __forceinline__ u32 fast_first_min(const u32 (&S)[NR], const int pfsh
   } else if (NR >= 16 && TSMAX == 1 && pfshift == 1) {
     constexpr int NG = NR / 2;
     u32 b[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
-    const u32 tag1 = 0x00010001u;
 #pragma unroll
     for (int j = 0; j < NG; j++) {
-      const u32 gm = pk_min(S[j], S[j + NG] | tag1);
+      const u32 gm = pk_min(S[j], S[j + NG]);
       const u32 klo = (gm << 16) | (u32)(2 * j);
       const u32 khi = (gm & 0xffff0000u) | (u32)(2 * j + 1);
       b[j & 3] = umin3(b[j & 3], klo, khi);
@@ -186,11 +200,15 @@ __device__ __forceinline__ u32 fast_first_min(const u32 (&S)[NR], const int pfsh
   return best;
 }
 
-// the uniqueness threshold on the (scaled) sums: T = thresh + 1 with cv's thresh = minsad + minsad * uniq / 100 on the unscaled sum
+// the uniqueness threshold on the (scaled) sums: T = thresh + 1 with cv's thresh = minsad + minsad * uniq / 100 on the unscaled sum.
+// Clamped to 65536 - (1 << pfshift), so that T plus a register tag still fits a packed half (fast_deficits). The clamp decides
+// nothing: it is reached only when (thresh + 1) << pfshift is beyond it, every scaled sum is at most maxS << pfshift, which is
+// below the clamp (maxS is even and (maxS << pfshift) + (1 << pfshift) - 1 <= 65535, sad_fast_pfshift()), so with or without
+// the clamp every disparity has a positive deficit and the pixel is rejected.
 __device__ __forceinline__ u32 fast_uniq_threshold(const int minsad, const int uniq, const int pfshift) {
   const int ms = minsad >> pfshift;
   const int thresh = ms + (ms * uniq / 100);
-  return (u32)min((thresh + 1) << pfshift, 65535);
+  return (u32)min((thresh + 1) << pfshift, 65536 - (1 << pfshift));
 }
 
 // Uniqueness, part 1: saturating sum of the deficits max(T - S[d], 0), per 16-bit half. Independent accumulators of 8 registers
@@ -198,8 +216,13 @@ __device__ __forceinline__ u32 fast_uniq_threshold(const int minsad, const int u
 // at most T - minsad <= maxS*uniq/100 + 1; when 8 of them cannot reach 65536 (host check, uniq_plain) the partial sums are plain
 // 32-bit adds of the packed halves -- no carry can cross -- and only the final combine saturates. Saturating adds give
 // min(65535, sum) in any grouping.
-template <int NR>
-__device__ __forceinline__ u32 fast_deficits(const u32 (&S)[NR], const u32 T, const int uniq_plain) {
+// The sums carry their register's tag (FastTag) and fast_unique tests for equality, so the subtrahend of tag group g is
+// T + g as well: (T + g) - (S + g) saturates at 0 exactly where T - S does, and T + g <= 65535 by fast_uniq_threshold's clamp.
+// One add per group and row; tag_unit() is 0 where the sums are untagged.
+template <int NR, int WSZ>
+__device__ __forceinline__ u32 fast_deficits(const u32 (&S)[NR], const u32 T, const int uniq_plain, const int pfshift) {
+  constexpr int NGRP = FastTag<WSZ>::NGRP, NG = NR / NGRP;
+  const u32 tg = FastTag<WSZ>::tag_unit(pfshift);
   const u32 T2 = T | (T << 16);
   constexpr int NACC = NR >= 32 ? NR / 8 : 4;
   u32 ac[NACC];
@@ -207,14 +230,22 @@ __device__ __forceinline__ u32 fast_deficits(const u32 (&S)[NR], const u32 T, co
   for (int k = 0; k < NACC; k++) ac[k] = 0u;
   if (uniq_plain) {
 #pragma unroll
-    for (int j = 0; j < NR; j++) ac[j % NACC] += pk_sub_sat(T2, S[j]);
+    for (int g = 0; g < NGRP; g++) {
+      const u32 Tg = T2 + (u32)g * tg;
+#pragma unroll
+      for (int j = g * NG; j < (g + 1) * NG; j++) ac[j % NACC] += pk_sub_sat(Tg, S[j]);
+    }
   } else {
     // (an opaque copy of the threshold: otherwise the compiler hoists the NR subtractions both paths share above
     // the branch and keeps all of them live at once -- 32 registers at the kernel's pressure peak)
     u32 T2s = T2;
     asm("" : "+v"(T2s));
 #pragma unroll
-    for (int j = 0; j < NR; j++) ac[j % NACC] = pk_add_sat(ac[j % NACC], pk_sub_sat(T2s, S[j]));
+    for (int g = 0; g < NGRP; g++) {
+      const u32 Tg = T2s + (u32)g * tg;
+#pragma unroll
+      for (int j = g * NG; j < (g + 1) * NG; j++) ac[j % NACC] = pk_add_sat(ac[j % NACC], pk_sub_sat(Tg, S[j]));
+    }
   }
 #pragma unroll
   for (int n = NACC; n > 1; n >>= 1)
@@ -234,7 +265,7 @@ __device__ __forceinline__ void fast_neighbours_quads(const u32 (&S)[2 * NQ], co
 }
 // ... and the binary tree over the quads: bit `lvl` of each index picks the odd entry (src0 = bytes 4..7) or the even one (src1 =
 // bytes 0..3): selector halves 0x0100 / 0x0504 (low, index ln) and 0x0302 / 0x0706 (high, index lp) = base + bit * 0x0404.
-// Returns S[ln] | S[lp] << 16.
+// Returns S[ln] | S[lp] << 16, with the tags of their registers (FastTag): the caller masks them off.
 template <int NQ>
 __device__ __forceinline__ u32 fast_neighbours_tree(u32 (&X)[NQ], const u32 lnp) {
   int lvl = 2;

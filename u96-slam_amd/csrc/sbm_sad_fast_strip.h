@@ -63,9 +63,19 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
   // vertical sums, packed 4 x u16 per quad (low dword = indices 4q, 4q+1, high dword = 4q+2, 4q+3), accumulated in place
   // (v_mqsad_pk_u16_u8 with vdst == src2: right on gfx950 although LLVM marks vdst early-clobber -- tools/ubench/mqsad_alias, 9.4e9
   // results, and the device self-test mqsad_inplace_ok(); a device that fails it takes the sliding-sum kernel instead)
+  // The carrier lanes -- (lane / KS) % NTERM == 0: exactly one of the NTERM lanes of any window -- start at the tag the winner
+  // search gives the quad's two registers, in all four halves, so that every window sum arrives tagged (FastTag,
+  // sbm_sad_fast_core.h); all lanes start at 0 where the untagged search runs. Built from the lane index here, dead before the
+  // priming rows.
   u64 VB[NQ];
+  {
+    const u32 unit = (lane_u / (unsigned)KS) % (unsigned)NTERM == 0u ? FastTag<WSZ>::tag_unit(a.pfshift) : 0u;
 #pragma unroll
-  for (int q = 0; q < NQ; q++) VB[q] = 0ull;
+    for (int q = 0; q < NQ; q++) {
+      const u32 tq = (u32)((2 * q) / (NR / FastTag<WSZ>::NGRP)) * unit;
+      VB[q] = __builtin_bit_cast(u64, make_uint2(tq, tq));
+    }
+  }
   u32 Vt = 0;  // texture: window-row sum of the 3-column |L - cap|
 
   // buffer_load_dword ... lds: lane i of load `it` writes its 4 source bytes (row piece bytes 64 it + i .. + 3: a byte-granular
@@ -283,7 +293,7 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
     u32 acc = 0, T = 0;
     if (a.uniq > 0) {
       T = fast_uniq_threshold(minsad, a.uniq, a.pfshift);
-      acc = fast_deficits<NR>(S, T, a.uniq_plain);
+      acc = fast_deficits<NR, WSZ>(S, T, a.uniq_plain, a.pfshift);
     }
 
     // ---- neighbours S[mind-1], S[mind+1] (mirrored at the ends) ----------------------------------------------------------
@@ -296,7 +306,9 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
       u32 X[NQ];
       const u32 lnp = (u32)ln | ((u32)lp << 16);
       fast_neighbours_quads<NQ>(S, lnp, X);
-      X0 = fast_neighbours_tree<NQ>(X, lnp);
+      // (without the tags of their registers; on untagged sums the bits are 0 anyway: every sum is a multiple of 1 << pfshift.
+      // Masked here, in front of the merge area: what the cooperating wavefronts exchange is clean.)
+      X0 = fast_neighbours_tree<NQ>(X, lnp) & ~(((1u << a.pfshift) - 1u) * 0x00010001u);
     }
     int nn = (int)(X0 & 0xffffu), pp = (int)(X0 >> 16);
     u32 acc_lo = acc & 0xffffu, acc_hi = acc >> 16;
