@@ -3,7 +3,10 @@ sdoira/U96-SLAM, src/slam/src/core/main.cpp:197-217).
 
 Layout
   csrc/         hand-written HIP kernels (gfx950) + the C-ABI (include/sbm.h)  -> lib/libsbm_hip.so
-  stereobm.py   host-side mirror of the cv::StereoBM interface over that C-ABI (ctypes)
+  _abi.py       ctypes mirror of include/sbm.h: structures, loader with the one argtypes table, status check
+  _engine.py    the base of both classes: one handle, its in-flight buffers, the one call path to the device entry points
+  _frontend.py _fpga.py _gftt.py _orb.py _match.py _pnp.py   one family of entry points each, as mixins of StereoBM
+  stereobm.py   host-side mirror of the cv::StereoBM interface (the dense path) and every public name of the above
   stereosgbm.py the same for cv::StereoSGBM (MODE_HH / MODE_SGBM)
   synth.py      deterministic synthetic stereo frames
   shard.py      one-process-per-GPU sharding of pair batches (torch.distributed; RCCL on GPU, gloo on CPU)

@@ -1,0 +1,247 @@
+"""ctypes mirror of include/sbm.h: every structure and constant of the C-ABI, the loader of lib/libsbm_hip.so with the one
+table of argument types, and the status check. Nothing here owns a handle; the classes over it are in _engine.py."""
+import ctypes
+import os
+import pathlib
+
+import numpy as np
+
+PREFILTER_NORMALIZED_RESPONSE = 0
+PREFILTER_XSOBEL = 1
+PREFILTER_FLAVOUR_CV = 0
+PREFILTER_FLAVOUR_RTL = 1
+
+_HERE = pathlib.Path(__file__).resolve().parent
+_LIB = None
+
+
+class SbmParams(ctypes.Structure):
+    """`sbm_params` of include/sbm.h."""
+
+    _fields_ = [
+        ("prefilter_type", ctypes.c_int32), ("prefilter_size", ctypes.c_int32), ("prefilter_cap", ctypes.c_int32),
+        ("block_size", ctypes.c_int32), ("min_disparity", ctypes.c_int32), ("num_disparities", ctypes.c_int32),
+        ("texture_threshold", ctypes.c_int32), ("uniqueness_ratio", ctypes.c_int32),
+        ("speckle_window_size", ctypes.c_int32), ("speckle_range", ctypes.c_int32), ("disp12_max_diff", ctypes.c_int32),
+        ("roi1", ctypes.c_int32 * 4), ("roi2", ctypes.c_int32 * 4),
+    ]
+
+
+class SgbmParams(ctypes.Structure):
+    """Mirror of `sbm_sgbm_params` (include/sbm.h), in cv::StereoSGBM::create argument order."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("min_disparity", "num_disparities", "block_size", "p1", "p2", "disp12_max_diff",
+                                                "prefilter_cap", "uniqueness_ratio", "speckle_window_size", "speckle_range", "mode")]
+
+
+class StereoModel(ctypes.Structure):
+    """`sbm_stereo_model` of include/sbm.h: the StereoCameraModel entries the reference's reprojection reads
+    (include/core/StereoCameraModel.h:25-34) plus the optional local transform."""
+
+    _fields_ = [(k, ctypes.c_double) for k in ("fx_l", "fy_l", "cx_l", "cy_l", "Tx_l", "fx_r", "fy_r", "cx_r", "Tx_r")] + [
+        ("local", ctypes.c_float * 12), ("has_local", ctypes.c_int32)]
+
+
+class RectCam(ctypes.Structure):
+    """`sbm_rect_cam` of include/sbm.h = struct RECT_PARAM_CH (src/StereoBM/src/fpga.h:250-256), one camera."""
+
+    _fields_ = [("f", ctypes.c_int32 * 2), ("c", ctypes.c_int32 * 2), ("f2inv", ctypes.c_int32 * 2),
+                ("c2_f2", ctypes.c_int32 * 2), ("rot", (ctypes.c_int32 * 3) * 3)]
+
+
+class FpgaParams(ctypes.Structure):
+    """`sbm_fpga_params` of include/sbm.h: the fields of the BM register block (struct FPGA_REG_BM,
+    src/StereoBM/src/fpga.h:154-169) as decoded by src/dvp/rtl/bm.v:172-193."""
+
+    _fields_ = [(k, ctypes.c_int32) for k in ("width", "height", "block_size", "num_disparities", "uni_enable", "uni_mode",
+                                              "uni_threshold")]
+
+
+class GfttSelectParams(ctypes.Structure):
+    """`sbm_gftt_select_params` of include/sbm.h: generateKeypoints2's constants (src/slam/src/core/GFTT.cpp:50-53)."""
+
+    _fields_ = [("max_features", ctypes.c_int32), ("quality_level", ctypes.c_double), ("min_distance", ctypes.c_double),
+                ("block_size", ctypes.c_int32)]
+
+
+class GfttCvParams(ctypes.Structure):
+    """`sbm_gftt_cv_params` of include/sbm.h: cv::GFTTDetector::create's arguments (src/slam/src/core/GFTT.cpp:13-24)."""
+
+    _fields_ = [("max_features", ctypes.c_int32), ("quality_level", ctypes.c_double), ("min_distance", ctypes.c_double),
+                ("block_size", ctypes.c_int32), ("use_harris", ctypes.c_int32), ("k", ctypes.c_double)]
+
+
+class OrbParams(ctypes.Structure):
+    """`sbm_orb_params` of include/sbm.h: computeDescriptor's constants (src/slam/src/opencv/CvORB.cpp) and the keypoints' angle."""
+
+    _fields_ = [("edge_threshold", ctypes.c_int32), ("angle", ctypes.c_float), ("blur_ksize", ctypes.c_int32),
+                ("blur_sigma", ctypes.c_double)]
+
+
+class MatchParams(ctypes.Structure):
+    """`sbm_match_params` of include/sbm.h: the NNDR ratio and guided radius of computeTransform's matching (Registration.cpp)."""
+
+    _fields_ = [("nndr", ctypes.c_float), ("radius", ctypes.c_float)]
+
+
+class PnpParams(ctypes.Structure):
+    """`sbm_pnp_params` of include/sbm.h: estimateMotion's minInliers, refineIterations and solvePnPRansac's constants."""
+
+    _fields_ = [("min_inliers", ctypes.c_int32), ("refine_iterations", ctypes.c_int32), ("iterations", ctypes.c_int32),
+                ("reprojection_error", ctypes.c_float), ("refine_sigma", ctypes.c_float), ("pad", ctypes.c_int32),
+                ("confidence", ctypes.c_double)]
+
+
+# `sbm_pnp_result` (216 bytes) and `sbm_pnp_hypothesis` (128 bytes) as numpy record types
+PNP_RESULT_DTYPE = np.dtype([("status", "<i4"), ("num_matches", "<i4"), ("num_inliers", "<i4"), ("ransac_inliers", "<i4"),
+                             ("best_iteration", "<i4"), ("niters", "<i4"), ("refine_solves", "<i4"), ("refine_exit", "<i4"),
+                             ("rvec", "<f8", 3), ("tvec", "<f8", 3), ("R", "<f8", 9), ("cov_dist", "<f8"), ("cov_angle", "<f8"),
+                             ("transform", "<f4", 12)])
+PNP_HYP_DTYPE = np.dtype([("subset", "<i4", 6), ("count", "<i4"), ("pad", "<i4"), ("R", "<f8", 9), ("t", "<f8", 3)])
+PNP_OK, PNP_FEW_MATCHES, PNP_NO_MODEL, PNP_FEW_RANSAC_INLIERS, PNP_FEW_REFINED_INLIERS = 0, 1, 2, 3, 4
+
+
+class StereoBMError(RuntimeError):
+    def __init__(self, code, message):
+        super().__init__(f"sbm status {code}: {message}")
+        self.code = code
+
+
+def _torch():
+    """torch, imported on first use and nowhere else: importing the package must not import it, and the numpy-only host entry
+    points work without it."""
+    import torch
+    return torch
+
+
+def library_path():
+    """lib/libsbm_hip.so, or -- SBM_LIB_AB=<file name> -- another build of the same HIP engine inside lib/ for kernel A/B
+    runs. Only a bare libsbm_hip*.so name is accepted and the file must exist: never a fallback, never a path."""
+    name = os.environ.get("SBM_LIB_AB", "libsbm_hip.so")
+    if name != os.path.basename(name) or not (name.startswith("libsbm_hip") and name.endswith(".so")):
+        raise ImportError(f"SBM_LIB_AB={name!r}: expected the bare name of a libsbm_hip*.so inside {_HERE / 'lib'}")
+    return _HERE / "lib" / name
+
+
+def loaded_library_name():
+    """File name of the engine library this process uses (bench.py prints it)."""
+    return library_path().name
+
+
+def load_library():
+    """Load lib/libsbm_hip.so. Fails loudly when it has not been built (no fallback of any kind)."""
+    global _LIB
+    if _LIB is not None:
+        return _LIB
+    # torch ships its own HIP runtime; when both live in one process it must be the first one loaded so that
+    # libsbm_hip.so binds to the same runtime (device memory and streams are shared with torch).
+    try:
+        _torch()
+    except ImportError:
+        pass
+    path = library_path()
+    if not path.exists():
+        raise ImportError(f"{path} is missing: build it with `make` (or __graft_entry__.build()); "
+                          "this package has no CPU fallback")
+    L = ctypes.CDLL(str(path))
+    vp, ci, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+    pp = ctypes.POINTER(SbmParams)
+    L.sbm_params_default.argtypes = [pp, ci, ci]
+    L.sbm_params_default.restype = None
+    L.sbm_params_validate.argtypes = [pp, ci, ci]
+    L.sbm_create.argtypes = [ctypes.POINTER(vp), pp, ci]
+    L.sbm_destroy.argtypes = [vp]
+    L.sbm_destroy.restype = None
+    L.sbm_set_params.argtypes = [vp, pp]
+    L.sbm_get_params.argtypes = [vp, pp]
+    L.sbm_compute.argtypes = [vp, vp, sz, vp, sz, ci, ci, vp, sz]
+    L.sbm_compute_batch.argtypes = [vp, ci, ctypes.POINTER(vp), sz, ctypes.POINTER(vp), sz, ci, ci, ctypes.POINTER(vp), sz]
+    L.sbm_compute_device.argtypes = [vp, ci, vp, vp, ci, ci, vp, ci]
+    L.sbm_synchronize.argtypes = [vp]
+    L.sbm_submit_dense.argtypes = [vp, ci, vp, vp, ci, ci, vp]
+    L.sbm_wait_oldest.argtypes = [vp]
+    L.sbm_compute_batch_multi.argtypes = [ctypes.POINTER(vp), ci, ci, vp, vp, ci, ci, vp]
+    L.sbm_debug_fetch.argtypes = [vp, ci, vp, sz]
+    L.sbm_set_profiling.argtypes = [vp, ci]
+    L.sbm_get_profile.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_float)]
+    L.sbm_last_kernel_name.argtypes = [vp, ctypes.c_char_p, sz]
+    sp = ctypes.POINTER(SgbmParams)
+    L.sbm_sgbm_params_default.argtypes = [sp, ci, ci, ci]
+    L.sbm_sgbm_params_default.restype = None
+    L.sbm_sgbm_params_validate.argtypes = [sp, ci, ci]
+    L.sbm_sgbm_compute.argtypes = [vp, sp, vp, sz, vp, sz, ci, ci, vp, sz]
+    L.sbm_sgbm_compute_device.argtypes = [vp, sp, ci, vp, vp, ci, ci, vp, ci]
+    mp = ctypes.POINTER(StereoModel)
+    L.sbm_disparity_to_float_device.argtypes = [vp, ci, vp, ci, ci, vp, ci]
+    L.sbm_decimate_device.argtypes = [vp, ci, vp, ci, ci, ci, vp, ci]
+    L.sbm_reproject_device.argtypes = [vp, ci, vp, ci, ci, ci, mp, ci, vp, ci]
+    L.sbm_keypoints3d_device.argtypes = [vp, vp, ci, ci, vp, ci, mp, ctypes.c_float, ctypes.c_float, vp, ci]
+    L.sbm_rect_map_device.argtypes = [vp, ctypes.POINTER(RectCam), ci, ci, vp, ci]
+    L.sbm_rect_remap_device.argtypes = [vp, ci, vp, vp, ci, ci, vp, ci]
+    L.sbm_prefilter_device.argtypes = [vp, ci, vp, ci, ci, ci, ci, vp, ci]
+    fp = ctypes.POINTER(FpgaParams)
+    u32 = ctypes.c_uint32
+    L.sbm_fpga_params_from_regs.argtypes = [u32, u32, u32, fp]
+    L.sbm_fpga_sad_size_reg.argtypes = [fp]
+    L.sbm_fpga_sad_size_reg.restype = u32
+    L.sbm_fpga_params_validate.argtypes = [fp]
+    L.sbm_fpga_bm_device.argtypes = [vp, ci, vp, vp, fp, vp, ci]
+    L.sbm_fpga_compute_device.argtypes = [vp, ci, vp, vp, fp, vp, ci]
+    L.sbm_gftt_eig_device.argtypes = [vp, ci, vp, ci, ci, vp, vp, ci]
+    L.sbm_fpga_compute.argtypes = [vp, vp, sz, vp, sz, fp, vp, sz]
+    L.sbm_gftt_eig.argtypes = [vp, vp, sz, ci, ci, vp, sz, ctypes.POINTER(u32)]
+    gp = ctypes.POINTER(GfttSelectParams)
+    L.sbm_gftt_select_params_default.argtypes = [gp]
+    L.sbm_gftt_select_params_default.restype = None
+    L.sbm_gftt_select_params_validate.argtypes = [gp, ci, ci]
+    L.sbm_gftt_select_device.argtypes = [vp, ci, vp, vp, ci, ci, gp, vp, vp, ci]
+    L.sbm_gftt_select.argtypes = [vp, vp, sz, ci, ci, ctypes.c_uint16, gp, vp, sz, ctypes.POINTER(ctypes.c_int)]
+    L.sbm_gftt_detect_device.argtypes = [vp, ci, vp, ci, ci, gp, vp, vp, vp, vp, ci]
+    gcp = ctypes.POINTER(GfttCvParams)
+    L.sbm_gftt_cv_params_default.argtypes = [gcp]
+    L.sbm_gftt_cv_params_default.restype = None
+    L.sbm_gftt_cv_params_validate.argtypes = [gcp, ci, ci]
+    L.sbm_gftt_cv_eig_device.argtypes = [vp, ci, vp, ci, ci, vp, vp, ci]
+    L.sbm_gftt_cv_detect_device.argtypes = [vp, ci, vp, ci, ci, gcp, vp, vp, vp, vp, ci]
+    L.sbm_gftt_cv_select_device.argtypes = [vp, ci, vp, vp, ci, ci, gcp, vp, vp, ci]
+    L.sbm_gftt_cv_detect.argtypes = [vp, vp, sz, ci, ci, gcp, vp, sz, ctypes.POINTER(ctypes.c_int)]
+    op = ctypes.POINTER(OrbParams)
+    L.sbm_orb_params_default.argtypes = [op]
+    L.sbm_orb_params_default.restype = None
+    L.sbm_orb_params_validate.argtypes = [op]
+    L.sbm_orb_describe_device.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp, op, vp, vp, vp, vp, ci]
+    L.sbm_orb_describe.argtypes = [vp, vp, sz, ci, ci, vp, ci, vp, op, vp, ctypes.POINTER(ctypes.c_int), vp]
+    L.sbm_orb_features_device.argtypes = [vp, ci, vp, ci, ci, gp, vp, op, vp, vp, vp, vp, vp, vp, ci]
+    L.sbm_orb_features_cv_device.argtypes = [vp, ci, vp, ci, ci, gcp, vp, op, vp, vp, vp, vp, vp, vp, ci]
+    mp_ = ctypes.POINTER(MatchParams)
+    L.sbm_match_params_default.argtypes = [mp_]
+    L.sbm_match_params_default.restype = None
+    L.sbm_match_params_validate.argtypes = [mp_]
+    L.sbm_match_device.argtypes = [vp, ci, ci, vp, vp, vp, ci, mp_, vp, vp, vp, ci]
+    L.sbm_match_guess_device.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, mp_, vp, vp, vp, ci]
+    L.sbm_project_points_device.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, ci, ci, vp, ci]
+    L.sbm_match.argtypes = [vp, vp, sz, ci, vp, sz, ci, mp_, vp, ctypes.POINTER(ci)]
+    L.sbm_match_guess.argtypes = [vp, vp, vp, vp, sz, ci, vp, sz, ci, vp, vp, ci, ci, mp_, vp, ctypes.POINTER(ci)]
+    pp_ = ctypes.POINTER(PnpParams)
+    L.sbm_pnp_params_default.argtypes = [pp_]
+    L.sbm_pnp_params_default.restype = None
+    L.sbm_pnp_params_validate.argtypes = [pp_]
+    L.sbm_estimate_motion_device.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, mp, pp_, vp, vp, vp, ci]
+    L.sbm_estimate_motion.argtypes = [vp, vp, ci, vp, vp, ci, vp, ci, vp, mp, pp_, vp, vp]
+    L.sbm_stream.argtypes = [vp]
+    L.sbm_stream.restype = vp
+    L.sbm_strerror.argtypes = [ci]
+    L.sbm_strerror.restype = ctypes.c_char_p
+    L.sbm_last_hip_error.argtypes = [vp]
+    L.sbm_version.restype = ci
+    _LIB = L
+    return L
+
+
+def _check(code, handle=None):
+    if code != 0:
+        L = load_library()
+        msg = L.sbm_strerror(code).decode()
+        if code == -21 and handle:
+            msg += f" (hipError {L.sbm_last_hip_error(handle)})"
+        raise StereoBMError(code, msg)
