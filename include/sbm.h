@@ -425,7 +425,7 @@ int sbm_gftt_detect_device(sbm_handle* h, int n, const void* d_img, int width, i
  * cv::GFTTDetector::create(1500, 0.01, 7.0, 3, false, 0.04)->detect(img, kpts) (GFTT.cpp:13-24 holds those six constants), i.e.
  * cv::goodFeaturesToTrack on the 8-bit frame without a mask. OpenCV is not part of the reference tree: every step below is
  * RECALLED from OpenCV's imgproc (cornerMinEigenVal, Sobel / sepFilter2D, boxFilter, goodFeaturesToTrack), NOT pinned by anything
- * here, unless it says otherwise. The engine, tests/gftt_cv_ref (sequential C and a numpy transcription of this text) and
+ * here, unless it says otherwise. The engine, oracle/gftt_cv_ref (sequential C and a numpy transcription of this text) and
  * tests/golden/pin_kit_gftt_cv.npz implement exactly this text; all arithmetic is IEEE binary32 / binary64 without contraction.
  *   scale     s = (float)(1.0 / (4 * 3 * 255.0)): 1 / (2^(aperture - 1) * blockSize * 255) in double, aperture 3, blockSize 3,
  *             rounded to float with the Sobel kernel it multiplies; f1 = s, f0 = 2 * s (exact).
@@ -692,7 +692,7 @@ int sbm_match_guess(sbm_handle* h, const float* xyz_from, const float* kpts_to, 
  * product, quaternion renormalisation and 4 x 4 inverse of Transform. RANSAC scores each hypothesis with R, t as EPnP
  * produced them (OpenCV round-trips through rvec; that moves the pose by ulps). With has_local == 0 (or no model) the
  * localTransform product is skipped.
- * Parity contract (GPU vs the sequential C restatement, tests/pnp_ref): bit for bit -- N, every subset, every hypothesis' R, t
+ * Parity contract (GPU vs the sequential C restatement, oracle/pnp_ref): bit for bit -- N, every subset, every hypothesis' R, t
  * and count, the best iteration, the final niters and the RANSAC inliers. Refined pose (rvec, tvec, R): 1e-9 relative (the
  * transcendental functions of Rodrigues differ between host and device libraries by ulps); transform and covariance scales:
  * float ulps (4 ulps relative to the largest entry); status, num_matches, num_inliers and the inlier list exact except for a

@@ -1,5 +1,5 @@
 """The sequential CPU restatement of the reference's generateKeypoints (cv::goodFeaturesToTrack as include/sbm.h states it):
-tests/gftt_cv_ref/libgftt_cv_ref.so through ctypes, and an independent numpy transcription of the header's text that the C file is
+oracle/libgftt_cv_ref.so through ctypes, and an independent numpy transcription of the header's text that the C file is
 held to. TEST INFRASTRUCTURE ONLY.
 
     set_reading(bits)                                              the SBM_CV_READING bits of both (512)
@@ -10,34 +10,20 @@ held to. TEST INFRASTRUCTURE ONLY.
     sqrtf(x)                                                       the C library's float square root, element by element
 """
 import ctypes
-import fcntl
-import pathlib
-import subprocess
 
 import numpy as np
 
-HERE = pathlib.Path(__file__).resolve().parent
+import oracle_lib
+
 _LIB = None
 _READING = 0
 READ_FUSED = 512
 
 
-def _make(*flags):
-    with open(HERE / "Makefile") as mk:
-        fcntl.flock(mk, fcntl.LOCK_EX)
-        r = subprocess.run(["make", "-C", str(HERE), *flags, "libgftt_cv_ref.so"], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("building tests/gftt_cv_ref/libgftt_cv_ref.so failed:\n" + r.stdout + r.stderr)
-    return HERE / "libgftt_cv_ref.so"
-
-
 def lib():
     global _LIB
     if _LIB is None:
-        try:
-            L = ctypes.CDLL(str(_make()))
-        except OSError:
-            L = ctypes.CDLL(str(_make("-B")))
+        L = oracle_lib.load("libgftt_cv_ref.so")
         vp, ci, cd, sz, cl = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_long
         L.gftt_cv_ref_set_reading.argtypes = [ci]
         L.gftt_cv_ref_set_reading.restype = None

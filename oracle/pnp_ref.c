@@ -1,5 +1,5 @@
 /* pnp_ref.c -- the sequential CPU restatement of estimateMotion3DTo2D (include/sbm.h, "motion estimation"). TEST
- * INFRASTRUCTURE ONLY; built with -O2 -ffp-contract=off (tests/pnp_ref/Makefile).
+ * INFRASTRUCTURE ONLY; built with -O2 -ffp-contract=off (oracle/Makefile).
  *
  * The arithmetic comes from u96-slam_amd/csrc/sbm_pnp_math.h, the same file the kernels compile. What this file restates is the
  * control flow of the reference in its own order: gather, then the RANSAC loop with draw, solve, score and update interleaved
@@ -10,8 +10,8 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "../../include/sbm.h"
-#include "../../u96-slam_amd/csrc/sbm_pnp_math.h"
+#include "../include/sbm.h"
+#include "../u96-slam_amd/csrc/sbm_pnp_math.h"
 
 /* CvLevMarq's lambda = exp(lambdaLg10 * log(10)), lambdaLg10 in -16..16: computed on the host, passed to the kernels. */
 void pnp_ref_lambda_table(double* tab) {

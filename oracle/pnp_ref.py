@@ -1,4 +1,4 @@
-"""The sequential CPU restatement of estimateMotion3DTo2D (tests/pnp_ref/libpnp_ref.so) through ctypes, and a literal
+"""The sequential CPU restatement of estimateMotion3DTo2D (oracle/libpnp_ref.so) through ctypes, and a literal
 transcription of the reference's loops that the C file is held to. TEST INFRASTRUCTURE ONLY.
 
     estimate(xyz_from, kpts_to, xyz_to, pairs, K, local=None, params=None, hyp=True)
@@ -13,16 +13,16 @@ The *_np functions transcribe CvSolvePnP.cpp (RNG::uniform, getSubset, RANSACPoi
 MotionEstimation.cpp (solvePnPRansac's refine loop with its two std::swap calls) line by line in Python.
 """
 import ctypes
-import fcntl
 import math
 import pathlib
-import subprocess
 import sys
 
 import numpy as np
 
+import oracle_lib
+
 HERE = pathlib.Path(__file__).resolve().parent
-sys.path.insert(0, str(HERE.parents[1]))
+sys.path.insert(0, str(HERE.parents[0]))
 from _pkg import load as _load_pkg  # noqa: E402
 
 _pkg = _load_pkg()
@@ -30,22 +30,10 @@ PNP_RESULT_DTYPE, PNP_HYP_DTYPE, PnpParams, pnp_params = _pkg.PNP_RESULT_DTYPE, 
 _LIB = None
 
 
-def _make(*flags):
-    with open(HERE / "Makefile") as mk:
-        fcntl.flock(mk, fcntl.LOCK_EX)
-        r = subprocess.run(["make", "-C", str(HERE), *flags, "libpnp_ref.so"], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("building tests/pnp_ref/libpnp_ref.so failed:\n" + r.stdout + r.stderr)
-    return HERE / "libpnp_ref.so"
-
-
 def lib():
     global _LIB
     if _LIB is None:
-        try:
-            L = ctypes.CDLL(str(_make()))
-        except OSError:
-            L = ctypes.CDLL(str(_make("-B")))
+        L = oracle_lib.load("libpnp_ref.so")
         vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
         L.pnp_ref_update_num_iters.argtypes = [cd, cd, ci, ci]
         L.pnp_ref_draw.argtypes = [ci, ci, vp]

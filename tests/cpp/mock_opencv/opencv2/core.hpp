@@ -1,13 +1,15 @@
-// tests/cpp/mock_opencv/opencv2/core.hpp -- a MOCK of the handful of OpenCV core names that include/sbm_stereobm.hpp's
-// cv::InputArray / cv::OutputArray overload and tests/cpp/callsite_main.cpp use.  Test infrastructure only.
+// tests/cpp/mock_opencv/opencv2/core.hpp -- a MOCK of the handful of OpenCV core names that the cv:: overloads of
+// include/sbm_*.hpp and the call-site programs of tests/cpp/ use.  Test infrastructure only.
 //
-// Written from scratch from the list of names that overload touches (cv::Mat, cv::Mat_<T>, cv::Rect, cv::Size,
+// Written from scratch from the list of names those overloads touch (cv::Mat, cv::Mat_<T>, cv::Rect, cv::Size,
 // cv::InputArray / cv::OutputArray with getMat / create / fixedType / type / size, Mat::convertTo, CV_Error,
-// cv::Exception); it is not derived from OpenCV's headers and reproduces none of OpenCV's arithmetic.  What it is for:
+// cv::Exception, and the few names of the feature call sites, each in a section of its own at the end); it is not derived
+// from OpenCV's headers and reproduces none of OpenCV's arithmetic.  What it is for:
 // this image (and the GPU box) has no OpenCV, so the overload the maintainer's one-line diff at
 // src/slam/src/core/main.cpp:201-215 relies on had never been through a compiler.  Building against this mock proves that
 // text compiles and runs -- the call shape, the CV_16SC1 / fixed-CV_32F destination rule, the error -> cv::Exception
-// mapping.  It pins NOTHING about cv::StereoBM's results; where real OpenCV headers exist the test uses those instead.
+// mapping.  It pins NOTHING about cv::StereoBM's results or any other OpenCV arithmetic; where real OpenCV headers exist
+// the test uses those instead.
 #ifndef SBM_MOCK_OPENCV_CORE_HPP_
 #define SBM_MOCK_OPENCV_CORE_HPP_
 
@@ -141,6 +143,39 @@ inline void Mat::convertTo(const _OutputArray& dst, int rtype, double alpha) con
     for (int x = 0; x < cols; x++) d[x] = (float)(s[x] * alpha);
   }
 }
+
+// ---- keypoint call sites (include/sbm_gftt.hpp's reference-signature overload): cv::Point2f and cv::KeyPoint, written from
+// the constructor the reference calls (cv::KeyPoint(pt, size), GFTT.cpp:166), with OpenCV's documented defaults for the other
+// fields
+struct Point2f {
+  float x = 0.f, y = 0.f;
+  Point2f() {}
+  Point2f(float x_, float y_) : x(x_), y(y_) {}
+};
+
+struct KeyPoint {
+  Point2f pt;
+  float size = 0.f, angle = -1.f, response = 0.f;
+  int octave = 0, class_id = -1;
+  KeyPoint() {}
+  KeyPoint(Point2f p, float s, float a = -1.f, float r = 0.f, int o = 0, int c = -1)
+      : pt(p), size(s), angle(a), response(r), octave(o), class_id(c) {}
+};
+
+// ---- descriptor call site (computeDescriptor(image, cv::noArray(), kpts2d, true, desc), main.cpp:246-248): cv::noArray()
+inline InputArray noArray() {
+  static Mat empty;
+  static _InputArray a(empty);
+  return a;
+}
+
+// ---- matching call site (matchingGuess's kptsFrom3D, Registration.cpp:250-303): cv::Point3f. The motion-estimation call site
+// (estimateMotion3DTo2D's std::map<int, cv::Point3f> and std::map<int, cv::KeyPoint>, Registration.cpp:337-397) adds no name
+struct Point3f {
+  float x = 0.f, y = 0.f, z = 0.f;
+  Point3f() {}
+  Point3f(float x_, float y_, float z_) : x(x_), y(y_), z(z_) {}
+};
 
 }  // namespace cv
 

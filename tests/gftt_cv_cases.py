@@ -7,7 +7,6 @@ import numpy as np
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "tests"))
-sys.path.insert(0, str(ROOT / "tests" / "gftt_cv_ref"))
 from gftt_select_cases import PARAM_EDGES  # noqa: E402,F401
 
 READINGS = (0, 512)

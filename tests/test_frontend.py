@@ -7,6 +7,8 @@ directly against the reference-produced golden vectors data/ref_xsbl_{l,r} (pinn
 import numpy as np
 import pytest
 
+from gpu_support import torch_cuda  # noqa: F401
+
 # calibration data set "220426" of the reference firmware (fpga.c:190-226): values only, quoted as test vectors
 CAM_L = dict(f=(40419817, 40382910), c=(320, 240), f2inv=(6338213, 6338213), c2_f2=(4984405, 5932596),
              rot=[[16598538, -120818, 2439034], [137992, 16776300, -108069], [-2438123, 126979, 16598626]])
@@ -98,15 +100,6 @@ def test_oracle_rect_remap_properties(oracle):
 
 
 # ------------------------------------------------------------------------------------------------ GPU --------------
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a visible MI355X (torch.cuda.is_available() is False)")
-    return torch
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("W,H", [(640, 480), (1242, 375), (333, 77), (1920, 1080)])
 def test_gpu_rect_map_bit_exact(torch_cuda, pkg, oracle, W, H):

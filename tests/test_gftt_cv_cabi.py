@@ -55,7 +55,7 @@ def test_null_arguments(pkg):
 
 @pytest.mark.parametrize("mock", [False, True], ids=["plain", "mock_opencv"])
 def test_adaptor_compiles_and_links(tmp_path, pkg, mock):
-    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv_features")] if mock else []
+    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv")] if mock else []
     lib = ROOT / "u96-slam_amd" / "lib"
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", str(ROOT / "include"), *extra,
                         str(ROOT / "tests" / "cpp" / "gftt_cv_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip",

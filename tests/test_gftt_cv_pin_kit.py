@@ -48,7 +48,7 @@ def goodFeaturesToTrack(img, maxCorners, qualityLevel, minDistance, blockSize=3,
 
 @pytest.mark.parametrize("reading", [0, 512])
 def test_verifier_names_the_reading(tmp_path, reading):
-    (tmp_path / "cv2.py").write_text(STAND_IN.format(ref=str(ROOT / "tests" / "gftt_cv_ref")))
+    (tmp_path / "cv2.py").write_text(STAND_IN.format(ref=str(ROOT / "oracle")))
     env = dict(os.environ, PYTHONPATH=str(tmp_path), STAND_IN_READING=str(reading))
     r = subprocess.run([sys.executable, str(ROOT / "tools" / "verify_gftt_cv_with_opencv.py"), str(KIT)], capture_output=True,
                        text=True, env=env, timeout=300)

@@ -1,4 +1,4 @@
-"""The sequential C restatement of generateKeypoints (tests/gftt_cv_ref/gftt_cv_ref.c) against the independent numpy transcription
+"""The sequential C restatement of generateKeypoints (oracle/gftt_cv_ref.c) against the independent numpy transcription
 of include/sbm.h's text, bit for bit: maps as uint32 views, maxima, candidate counts and every keypoint in order, under reading 0
 and under each reading bit. No GPU."""
 import numpy as np

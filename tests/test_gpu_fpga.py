@@ -4,6 +4,8 @@ this stage (no RTL output in the reference, no simulator): see tests/test_oracle
 import numpy as np
 import pytest
 
+from gpu_support import dev
+
 pytestmark = pytest.mark.gpu
 
 
@@ -16,22 +18,16 @@ def bm(pkg):
     return pkg.StereoBM.create(64, 21)
 
 
-def _dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
 def test_reference_stimulus_firmware_registers(pkg, bm, oracle, golden):
     """data/ref_xsbl_{l,r} = the RTL's own BM stimulus (sim_dvp.v:460-490), configured through the register words the
     firmware writes (fpga.c:155,158)."""
     p = pkg.fpga_params_from_regs((480 << 16) + 640, 0x00150040, 0)
     assert (p.width, p.height, p.block_size, p.num_disparities, p.uni_enable) == (640, 480, 21, 64, 0)
-    got = bm.fpga_bm(_dev(golden["xsbl_l"]), _dev(golden["xsbl_r"]), p).cpu().numpy()
+    got = bm.fpga_bm(dev(golden["xsbl_l"]), dev(golden["xsbl_r"]), p).cpu().numpy()
     ref = oracle.fpga_bm(golden["xsbl_l"], golden["xsbl_r"], 21, 64)
     assert np.array_equal(got, ref), int((got != ref).sum())
     # whole PL pipeline from the rectified pair: xsbl2 prefilter on the device, then the matcher
-    got2 = bm.fpga_compute(_dev(golden["rect_l"]), _dev(golden["rect_r"]), p).cpu().numpy()
+    got2 = bm.fpga_compute(dev(golden["rect_l"]), dev(golden["rect_r"]), p).cpu().numpy()
     assert np.array_equal(got2, ref)
 
 
@@ -45,7 +41,7 @@ def test_random_frames_and_uniqueness_filter(pkg, bm, oracle, W, H, wsz, nd):
     xl = np.clip(xl.astype(int) + rng.integers(-4, 5, xl.shape), 0, 63).astype(np.uint8)
     for uni in ((0, 0, 0), (1, 0, 0x2c0), (1, 1, 0x100)):
         p = pkg.fpga_params(W, H, wsz, nd, *uni)
-        got = bm.fpga_bm(_dev(xl), _dev(xr), p).cpu().numpy()
+        got = bm.fpga_bm(dev(xl), dev(xr), p).cpu().numpy()
         for i in range(n):
             ref = oracle.fpga_bm(xl[i], xr[i], wsz, nd, *uni)
             assert np.array_equal(got[i], ref), (i, uni, int((got[i] != ref).sum()))
@@ -62,7 +58,7 @@ def test_saturating_column_sums_take_the_exact_pass(pkg, bm, oracle):
     xl[1] = rng.integers(0, 64, (H, W))          # pair 1 never saturates: stays on the segmented result
     xr[1] = np.roll(xl[1], -9, axis=1)
     p = pkg.fpga_params(W, H, 21, 64)
-    got = bm.fpga_bm(_dev(xl), _dev(xr), p).cpu().numpy()
+    got = bm.fpga_bm(dev(xl), dev(xr), p).cpu().numpy()
     for i in range(2):
         ref = oracle.fpga_bm(xl[i], xr[i], 21, 64)
         assert np.array_equal(got[i], ref), (i, int((got[i] != ref).sum()))
@@ -106,7 +102,7 @@ def test_first_and_last_samples_of_a_batch(pkg, bm, oracle, W, H, wsz, nd, amp, 
     xr = (rng.integers(0, amp, (n, H, W)) * (63 if amp == 2 else 1)).astype(np.uint8)
     xl = np.stack([np.roll(xr[i], int(rng.integers(0, nd)), axis=1) for i in range(n)])
     p = pkg.fpga_params(W, H, wsz, nd, 0, 0, 0)
-    got = bm.fpga_bm(_dev(xl), _dev(xr), p).cpu().numpy()
+    got = bm.fpga_bm(dev(xl), dev(xr), p).cpu().numpy()
     for i in range(n):
         ref = oracle.fpga_bm(xl[i], xr[i], wsz, nd, 0, 0, 0)
         assert np.array_equal(got[i], ref), (i, int((got[i] != ref).sum()), np.argwhere(got[i] != ref)[:3].tolist())

@@ -10,19 +10,12 @@ import zlib
 import numpy as np
 import pytest
 
+from gpu_support import torch_cuda  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 FULL = dict(prefilter_cap=31, texture_threshold=10, uniqueness_ratio=10, speckle_window_size=50, speckle_range=32,
             disp12_max_diff=1)
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a visible MI355X (torch.cuda.is_available() is False)")
-    return torch
 
 
 def make_engine(pkg, nd, wsz, **kw):

@@ -1,5 +1,5 @@
 """GPU generateKeypoints (u96-slam_amd/csrc/sbm_gftt_cv.hip) bit for bit against the sequential C restatement
-(tests/gftt_cv_ref): maps as uint32 views, maxima, counts and every (x, y) in order, for every frame of every batch, under
+(oracle/gftt_cv_ref): maps as uint32 views, maxima, counts and every (x, y) in order, for every frame of every batch, under
 reading 0 and under each reading bit, through the device, map-level, host, asynchronous and front-end entry points. Equality is
 exact: both sides perform the same IEEE operations without contraction."""
 import ctypes
@@ -15,13 +15,9 @@ sys.path.insert(0, str(ROOT / "tests"))
 from gftt_cv_cases import PARAM_EDGES, READINGS, crafted_frames, plateau_maps, random_case  # noqa: E402
 import gftt_cv_ref as ref  # noqa: E402
 import orb_ref  # noqa: E402
+from gpu_support import bm, build_callsite, dev  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def bm(pkg):
-    return pkg.StereoBM.create(64, 21)
 
 
 @pytest.fixture(scope="module")
@@ -38,12 +34,6 @@ def reading(monkeypatch, request):
     ref.set_reading(request.param)
     yield request.param
     ref.set_reading(0)
-
-
-def dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def bits(a):
@@ -269,12 +259,8 @@ def test_profile_records_stages(bm, golden):
 
 @pytest.mark.parametrize("mock", [False, True], ids=["plain", "mock_opencv"])
 def test_cpp_callsite_through_the_adaptor(tmp_path, golden, mock):
-    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv_features")] if mock else []
-    lib = ROOT / "u96-slam_amd" / "lib"
-    exe = tmp_path / "cs"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", str(ROOT / "include"), *extra,
-                        str(ROOT / "tests" / "cpp" / "gftt_cv_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip",
-                        f"-Wl,-rpath,{lib}", "-o", str(exe)], capture_output=True, text=True)
+    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv")] if mock else []
+    exe, r = build_callsite(tmp_path, "gftt_cv_callsite_main.cpp", extra, flags=("-Wall", "-Werror"))
     assert r.returncode == 0, r.stderr
     img = golden["rect_l"]
     (tmp_path / "img.raw").write_bytes(img.tobytes())

@@ -11,22 +11,9 @@ ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "tests"))
 import gftt_select_ref as ref  # noqa: E402
 from gftt_select_cases import PARAM_EDGES, crafted_maps, random_case  # noqa: E402
+from gpu_support import bm, build_callsite, dev  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def bm(pkg):
-    return pkg.StereoBM.create(64, 21)
-
-
-def dev(a):
-    import torch
-
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint16:
-        return torch.from_numpy(a.view(np.int16)).to("cuda:0")
-    return torch.from_numpy(a).to("cuda:0")
 
 
 def check(kpts, count, i, want, what=""):
@@ -201,12 +188,8 @@ def test_profile_records_stages(bm, golden):
 def test_cpp_callsite_through_the_adaptor(tmp_path, oracle, golden, mock):
     e, m = oracle.gftt_eig(golden["rect_l"])
     H, W = e.shape
-    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv_features")] if mock else []
-    lib = ROOT / "u96-slam_amd" / "lib"
-    exe = tmp_path / "cs"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-I", str(ROOT / "include"), *extra,
-                        str(ROOT / "tests" / "cpp" / "gftt_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip", f"-Wl,-rpath,{lib}",
-                        "-o", str(exe)], capture_output=True, text=True)
+    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv")] if mock else []
+    exe, r = build_callsite(tmp_path, "gftt_callsite_main.cpp", extra)
     assert r.returncode == 0, r.stderr
     (tmp_path / "eig.raw").write_bytes(np.ascontiguousarray(e).tobytes())
     r = subprocess.run([str(exe), str(tmp_path / "eig.raw"), str(W), str(H), str(m), str(tmp_path / "k.raw")],

@@ -12,17 +12,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "tests"))
+from gpu_support import torch_cuda  # noqa: E402,F401
 
 UNSUPPORTED = -23
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a visible MI355X (torch.cuda.is_available() is False)")
-    return torch
 
 
 def smooth_pair(rng, h, w, shift, noise=3):

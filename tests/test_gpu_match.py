@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import match_ref as ref
+from gpu_support import bm, build_callsite, dev  # noqa: F401
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 
@@ -20,11 +21,6 @@ K = (320.0, 321.5, 319.5, 239.25)
 W, H = 640, 480
 
 
-@pytest.fixture(scope="module")
-def bm(pkg):
-    return pkg.StereoBM.create(64, 21)
-
-
 @pytest.fixture
 def fused(monkeypatch, request):
     if request.param:
@@ -32,12 +28,6 @@ def fused(monkeypatch, request):
     else:
         monkeypatch.delenv("SBM_CV_READING", raising=False)
     return request.param
-
-
-def dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def store(frames, cap=None, marker=0xA5):
@@ -397,11 +387,8 @@ def test_limits_on_the_device(bm, pkg):
 
 
 def test_cpp_callsite_through_the_adaptor(tmp_path):
-    lib = ROOT / "u96-slam_amd" / "lib"
-    exe = tmp_path / "cs"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", str(ROOT / "include"), "-DSBM_TEST_WITH_OPENCV", "-I",
-                        str(ROOT / "tests" / "cpp" / "mock_opencv_match"), str(ROOT / "tests" / "cpp" / "match_callsite_main.cpp"),
-                        "-L", str(lib), "-lsbm_hip", f"-Wl,-rpath,{lib}", "-o", str(exe)], capture_output=True, text=True)
+    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv")]
+    exe, r = build_callsite(tmp_path, "match_callsite_main.cpp", extra, flags=("-Wall", "-Werror"))
     assert r.returncode == 0, r.stderr[-3000:]
     rng = np.random.default_rng(66)
     fr, to = planted(rng, 400, 350)

@@ -8,25 +8,14 @@ import threading
 import numpy as np
 import pytest
 
+from gpu_support import build_callsite, torch_cuda  # noqa: F401
+
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 
 
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a visible MI355X (torch.cuda.is_available() is False)")
-    return torch
-
-
 def _build(tmp_path, pkg):
-    exe = tmp_path / "multi_main"
-    lib = pkg.library_path()
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-pthread", "-D__HIP_PLATFORM_AMD__", "-I", str(ROOT / "include"), "-I", "/opt/rocm/include",
-                        str(ROOT / "tests" / "cpp" / "multi_main.cpp"), "-o", str(exe), str(lib), "-L/opt/rocm/lib", "-lamdhip64",
-                        f"-Wl,-rpath,{lib.parent}", "-Wl,-rpath,/opt/rocm/lib"], capture_output=True, text=True)
-    return exe, r
+    return build_callsite(tmp_path, "multi_main.cpp", ("-I", "/opt/rocm/include"), flags=("-pthread", "-D__HIP_PLATFORM_AMD__"),
+                          exe="multi_main", pkg=pkg, libs=("-L/opt/rocm/lib", "-lamdhip64"))
 
 
 @pytest.mark.gpu

@@ -9,17 +9,13 @@ import pytest
 
 import gftt_select_ref as gref
 import orb_ref as ref
+from gpu_support import bm, build_callsite, dev  # noqa: F401
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 
 pytestmark = pytest.mark.gpu
 READINGS = [False, True]
 RIDS = ["half_even", "half_up"]
-
-
-@pytest.fixture(scope="module")
-def bm(pkg):
-    return pkg.StereoBM.create(64, 21)
 
 
 @pytest.fixture(scope="module")
@@ -35,12 +31,6 @@ def reading(monkeypatch, request):
     else:
         monkeypatch.delenv("SBM_CV_READING", raising=False)
     return half_up
-
-
-def dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def slots(kp_list, cap):
@@ -300,12 +290,8 @@ def test_cpp_callsite_through_the_adaptor(tmp_path, oracle, golden, pattern, moc
     e, m = oracle.gftt_eig(img)
     kpts = gref.select(e, m)
     H, W = img.shape
-    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv_orb")] if mock else []
-    lib = ROOT / "u96-slam_amd" / "lib"
-    exe = tmp_path / "cs"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-I", str(ROOT / "include"), *extra,
-                        str(ROOT / "tests" / "cpp" / "orb_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip", f"-Wl,-rpath,{lib}",
-                        "-o", str(exe)], capture_output=True, text=True)
+    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv")] if mock else []
+    exe, r = build_callsite(tmp_path, "orb_callsite_main.cpp", extra)
     assert r.returncode == 0, r.stderr[-3000:]
     np.ascontiguousarray(img).tofile(tmp_path / "img.raw")
     np.ascontiguousarray(kpts, np.float32).tofile(tmp_path / "kpts.raw")

@@ -7,17 +7,10 @@ import pathlib
 import numpy as np
 import pytest
 
+from gpu_support import build_callsite, torch_cuda  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a visible MI355X (torch.cuda.is_available() is False)")
-    return torch
 
 
 def run_engine(pkg, oracle, params_kw, L, R, stages=True):
@@ -479,14 +472,7 @@ def test_normalized_response_prefilter(torch_cuda, pkg, oracle, h, w, kw):
 
 # ---- the C++ boundary, exercised the way the reference calls it -----------------------------------
 def _build_callsite(tmp_path, pkg, extra=()):
-    import subprocess
-
-    exe = tmp_path / "callsite_main"
-    lib = pkg.library_path()
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-I", str(ROOT / "include"), *extra, str(ROOT / "tests" / "cpp" / "callsite_main.cpp"),
-                        "-o", str(exe), str(lib), f"-Wl,-rpath,{lib.parent}", "-Wl,-rpath,/opt/rocm/lib"],
-                       capture_output=True, text=True)
-    return exe, r
+    return build_callsite(tmp_path, "callsite_main.cpp", extra, exe="callsite_main", pkg=pkg)
 
 
 @pytest.mark.gpu

@@ -1,35 +1,23 @@
-"""estimate_motion on the MI355X against the sequential C restatement (tests/pnp_ref): subsets, hypotheses and counts bit for
+"""estimate_motion on the MI355X against the sequential C restatement (oracle/pnp_ref): subsets, hypotheses and counts bit for
 bit, the RANSAC outcome exactly, the refined pose to 1e-9, the transform and covariance scales to float ulps, status and inlier
 lists exactly; synthetic scenes against their true pose; the golden pair through the whole front end."""
 import ctypes
 import math
 import pathlib
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "tests" / "pnp_ref"))
+import pnp_ref
+from gpu_support import bm, build_callsite, dev  # noqa: F401
 
-import pnp_ref  # noqa: E402
+ROOT = pathlib.Path(__file__).resolve().parents[1]
 
 pytestmark = pytest.mark.gpu
 
 K = np.array([718.856, 718.856, 607.1928, 185.2157])
 LOCAL = [0, 0, 1, 0.1, -1, 0, 0, 0.05, 0, -1, 0, 1.2]   # camera -> base: z forward becomes x
 GATE = 1e-6                                              # px around a refine round's threshold
-
-
-@pytest.fixture(scope="module")
-def bm(pkg):
-    return pkg.StereoBM.create(64, 21)
-
-
-def dev(a):
-    import torch
-
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
 def rot(a):
@@ -339,12 +327,8 @@ def test_cpp_callsite_through_the_adaptor(tmp_path, mock):
     not consecutive, ids without a from-point (absent from words3A), without a to-point; against the restatement."""
     import subprocess
 
-    lib = ROOT / "u96-slam_amd" / "lib"
-    exe = tmp_path / "cs"
-    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv_pnp")] if mock else []
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", str(ROOT / "include"), *extra,
-                        str(ROOT / "tests" / "cpp" / "pnp_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip",
-                        f"-Wl,-rpath,{lib}", "-o", str(exe)], capture_output=True, text=True)
+    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv")] if mock else []
+    exe, r = build_callsite(tmp_path, "pnp_callsite_main.cpp", extra, flags=("-Wall", "-Werror"))
     assert r.returncode == 0, r.stderr[-3000:]
     rng = np.random.default_rng(77)
     st = Store(rng, [500], 500, 0.3, nan=0.1, noise=0.5)

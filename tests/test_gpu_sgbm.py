@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import sgbm_ref
+from gpu_support import build_callsite
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 
@@ -57,11 +58,7 @@ def test_reference_call_on_golden_pair(pkg, golden):
 
 
 def _build_callsite(tmp_path, extra=()):
-    exe = tmp_path / "sgbm_callsite"
-    lib = ROOT / "u96-slam_amd" / "lib"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-I", str(ROOT / "include"), *extra,
-                        str(ROOT / "tests" / "cpp" / "sgbm_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip",
-                        f"-Wl,-rpath,{lib}", "-o", str(exe)], capture_output=True, text=True)
+    exe, r = build_callsite(tmp_path, "sgbm_callsite_main.cpp", extra, exe="sgbm_callsite")
     assert r.returncode == 0, r.stderr
     return exe
 

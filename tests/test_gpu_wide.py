@@ -10,15 +10,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "tests"))
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a visible MI355X (torch.cuda.is_available() is False)")
-    return torch
+from gpu_support import torch_cuda  # noqa: E402,F401
 
 
 # (width, height, pairs, parameters): every case is outside the fast envelope

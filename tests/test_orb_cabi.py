@@ -1,6 +1,6 @@
 """The ORB descriptor C-ABI without a GPU: the reference's values as defaults, a status code for every validation failure, and
 the C++ adaptor compiling against the library (plain, and with the reference's signature against the OpenCV mock of
-tests/cpp/mock_opencv_orb)."""
+tests/cpp/mock_opencv)."""
 import ctypes
 import math
 import pathlib
@@ -57,7 +57,7 @@ def test_the_profile_names_are_documented():
 
 @pytest.mark.parametrize("mock", [False, True], ids=["plain", "mock_opencv"])
 def test_cpp_adaptor_compiles(tmp_path, mock):
-    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv_orb")] if mock else []
+    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv")] if mock else []
     lib = ROOT / "u96-slam_amd" / "lib"
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", str(ROOT / "include"), *extra,
                         str(ROOT / "tests" / "cpp" / "orb_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip", f"-Wl,-rpath,{lib}",

@@ -1,18 +1,16 @@
-"""The motion-estimation restatement on the CPU: the C file (tests/pnp_ref) against the literal transcription of the reference's
+"""The motion-estimation restatement on the CPU: the C file (oracle/pnp_ref.c) against the literal transcription of the reference's
 loops (pnp_ref.py) -- RNG and subsets, the RANSAC replay, the refine loop and its swap rule --, the RANSACUpdateNumIters walk that
 makes niters library-independent, EPnP and the whole job against known poses, and the C-ABI's parameters without a GPU."""
 import ctypes
 import math
 import pathlib
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "tests" / "pnp_ref"))
+import pnp_ref
 
-import pnp_ref  # noqa: E402
+ROOT = pathlib.Path(__file__).resolve().parents[1]
 
 K = np.array([718.856, 718.856, 607.1928, 185.2157])
 
@@ -241,7 +239,7 @@ def test_gather_and_the_work_without_hypotheses():
 def test_cpp_adaptor_compiles(tmp_path, mock):
     import subprocess
 
-    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv_pnp")] if mock else []
+    extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv")] if mock else []
     lib = ROOT / "u96-slam_amd" / "lib"
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", str(ROOT / "include"), *extra,
                         str(ROOT / "tests" / "cpp" / "pnp_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip",

@@ -8,7 +8,7 @@ JSON line:
                                    share of --hbm-gbps (8000: the MI355X's nominal HBM3E bandwidth)
   single_*                         the same three for one frame
   candidates_per_frame / points_per_frame   from the restatement on the first 8 frames / from the device counts
-  restatement_1core_ms             tests/gftt_cv_ref (sequential C) per frame on one core
+  restatement_1core_ms             oracle/gftt_cv_ref (sequential C) per frame on one core
   restatement_16proc_ms            --n frames over 16 host processes, wall time
   fpga_flavour_detect_ms           sbm_gftt_detect_device (the PL's uint16 map + generateKeypoints2) on the same frames, same run;
                                    null where the frames exceed that map's limits (width 1023, height 511)
@@ -32,7 +32,6 @@ import numpy as np
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "oracle"))
-sys.path.insert(0, str(ROOT / "tests" / "gftt_cv_ref"))
 
 
 def frames(kind, n):

@@ -21,7 +21,6 @@ import numpy as np
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "oracle"))
-sys.path.insert(0, str(ROOT / "tests" / "pnp_ref"))
 
 K = np.array([718.856, 718.856, 607.1928, 185.2157])
 

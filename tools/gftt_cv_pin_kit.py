@@ -7,7 +7,7 @@ radicand), for whoever has an OpenCV at hand.
     python tools/verify_gftt_cv_with_opencv.py [kit]       (numpy + cv2 only) names the reading a given OpenCV implements
 
 Per frame and reading the kit holds the float map of cornerMinEigenVal(img, 3, 3), its maximum, and the keypoints of
-goodFeaturesToTrack(img, 1500, 0.01, 7.0, blockSize 3) in order -- all from the CPU restatement (tests/gftt_cv_ref);
+goodFeaturesToTrack(img, 1500, 0.01, 7.0, blockSize 3) in order -- all from the CPU restatement (oracle/gftt_cv_ref);
 tests/test_gftt_cv_pin_kit.py regenerates them bit for bit. The frames: a crop of the golden left frame, noise, noise of low
 contrast (small derivatives: where a fused sum differs most often), and two identical corners whose responses tie exactly (the
 order of a tie is the reference's greaterThanPtr; a stock OpenCV may order it differently, and the verifier says so).
@@ -18,7 +18,7 @@ import sys
 import numpy as np
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "tests" / "gftt_cv_ref"))
+sys.path.insert(0, str(ROOT / "oracle"))
 OUT = ROOT / "tests" / "golden" / "pin_kit_gftt_cv.npz"
 READINGS = (0, 512)
 PARAMS = (1500, 0.01, 7.0)

@@ -1,6 +1,6 @@
 /* sbm_pnp_math.h -- the double-precision arithmetic of estimateMotion3DTo2D (include/sbm.h), written once
- * and compiled twice: as HIP device code in sbm_pnp.hip (with contraction off) and as C11 in the sequential restatement under
- * tests/pnp_ref/ (-ffp-contract=off). Only + - * / and sqrt reach the bits that must agree; the transcendental calls (acos, cos,
+ * and compiled twice: as HIP device code in sbm_pnp.hip (with contraction off) and as C11 in the tests' sequential restatement,
+ * pnp_ref.c (-ffp-contract=off). Only + - * / and sqrt reach the bits that must agree; the transcendental calls (acos, cos,
  * sin in Rodrigues; acos in the covariance angles) are the places where libm and the device library may differ in the last ulp.
  * Plain C on purpose: no templates, no references, fixed-size arrays, every loop bounded. */
 #ifndef SBM_PNP_MATH_H_
