@@ -838,6 +838,108 @@ int sbm_sgbm_compute_device(sbm_handle* h, const sbm_sgbm_params* p, int n, cons
  * sbm_get_profile: while profiling is enabled (any mode) SGBM calls synchronise after each chunk and record "sgbm_cost",
  * "sgbm_aggregate", "sgbm_select", "sgbm_median", "sgbm_speckle", "sgbm_total" (ms of the last call, summed over its chunks). */
 
+/* ---- pyramidal LK stereo: computeCorrespondences (src/slam/src/core/Stereo.cpp:9-51; DEPTH_METHOD_CV_LK) --------------------
+ * The reference's sparse depth provider: generateKeypoints3D (Stereo.cpp:119-155) calls computeCorrespondences, which tracks
+ * every left keypoint into the right image with calcOpticalFlowPyrLKStereo (src/slam/src/opencv/CvLKStereo.cpp: OpenCV's
+ * pyramidal LK with the y update forced to 0) -- window 15 x 3, 5 pyramid levels, 30 iterations, eps 0.01,
+ * OPTFLOW_LK_GET_MIN_EIGENVALS, threshold 1e-4 -- and gates the result on 0.5 < d <= 128; generateKeypoints3DStereo then takes
+ * disparity = left.x - right.x under the status mask (Stereo.cpp:85-87). Each step below is marked REF (pinned by the reference's
+ * own source) or RECALLED (OpenCV, not part of the reference tree, pinned by nothing here). The engine, tests/lk_stereo_ref
+ * (sequential C, and a numpy transcription of the RECALLED half) and tests/golden/pin_kit_lk.npz implement exactly this text.
+ * All arithmetic is IEEE binary32 / binary64 WITHOUT contraction: an aarch64 build of the reference may fuse some of the
+ * multiply-adds below (A11 * A22 - A12 * A12, the radicand, A12 * b2 - A22 * b1); the uncontracted reading is the contract, and
+ * no SBM_CV_READING bit is spent on the other.
+ *  Pyramid (RECALLED: cv::buildOpticalFlowPyramid(img, pyr, winSize, maxLevel, withDerivatives)):
+ *   level 0   the frame. Level k = pyrDown of level k - 1: size ((w + 1) / 2, (h + 1) / 2); out(x, y) = (s + 128) >> 8 with s the
+ *             separable [1 4 6 4 1] x [1 4 6 4 1] integer sum around (2x, 2y), BORDER_REFLECT_101.
+ *   count     after level k is built the next size is computed; building stops, and k is the last level, when that size has
+ *             width <= win_width or height <= win_height, or when k = max_level. The left pyramid is built first and the right
+ *             one with the left's count (equal sizes: the same count).
+ *   padding   every level is padded by the window size with BORDER_REFLECT_101 (p[-1] = p[1], p[n] = p[n - 2], repeated when
+ *             the level is narrower than the padding); the derivative plane is padded with zeros (BORDER_CONSTANT).
+ *   deriv     left only, Scharr on the UNPADDED level, reflect-101 at both borders, int16 (dx, dy) interleaved:
+ *             dx = 3 (p[y-1][x+1] - p[y-1][x-1]) + 10 (p[y][x+1] - p[y][x-1]) + 3 (p[y+1][x+1] - p[y+1][x-1]), dy transposed.
+ *   The engine stores no padding: it applies the two border rules when it reads.
+ *  Tracker (REF: CvLKStereo.cpp:147-361), per point, levels from the last down to 0, nothing shared between points:
+ *   point     prev = pt * (float)(1. / (1 << level)); next = prev at the last level, else next = (previous level's next) * 2.f;
+ *             the output is set to next before anything can skip the level.
+ *   window    halfWin = ((w - 1) * 0.5f, (h - 1) * 0.5f); prev -= halfWin; iprev = cvFloor(prev); the level is skipped when
+ *             iprev.x is outside [-w, cols) or iprev.y outside [-h, rows) (at level 0: status 0, err 0).
+ *   weights   a = prev.x - iprev.x, b = prev.y - iprev.y; iw00 = cvRound((1.f - a) * (1.f - b) * 16384) (float products left to
+ *             right, cvRound = round half to even), iw01 from a * (1.f - b), iw10 from (1.f - a) * b, iw11 = 16384 - the others.
+ *   patch     over the window in raster order: I = (bilinear sum of the 4 pixels + 256) >> 9; Ix, Iy = (bilinear sum of the 4
+ *             derivatives + 8192) >> 14 (arithmetic shift); iA11 += (float)(Ix * Ix), iA12 += (float)(Ix * Iy), iA22 +=
+ *             (float)(Iy * Iy): float accumulators, int products, every addition rounded. That order is the contract.
+ *   matrix    A = iA * 2^-20; D = A11 * A22 - A12 * A12; minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 *
+ *             A12)) / (2 * w * h), all float, square root and division correctly rounded. err = minEig. The level is skipped
+ *             (at level 0: status 0) when (double)minEig < min_eig_threshold or D < FLT_EPSILON. D = 1.f / D.
+ *   iterate   next -= halfWin; at most max_count times (clamped to 0..100): inext = cvFloor(next); out of the same range ->
+ *             stop (at level 0: status 0). Weights as above from next; over the window in raster order diff = ((bilinear sum
+ *             of the right image + 256) >> 9) - I; ib1 += (float)(diff * Ix), ib2 += (float)(diff * Iy) (the products pass
+ *             2^24: conversion and sums both round); b = ib * 2^-20; delta = ((A12 * b2 - A22 * b1) * D, 0) -- the reference's
+ *             one change to OpenCV; next += delta; output = next + halfWin; stop when (double)dx * dx + (double)dy * dy <=
+ *             eps^2 (epsilon clamped to 0..10 and squared in double); stop with output -= delta * 0.5f when this is not the
+ *             first iteration and |delta.x + previous delta.x| < 0.01 (and the same for y).
+ *   status    1 unless cleared at level 0; err = level 0's minEig, or 0 where the point is outside at level 0.
+ *  Gate (REF: Stereo.cpp:41-48): where status is set, d = left.x - right.x; status = 0 when d <= min_disparity or d >
+ *   max_disparity. A NEGATIVE max_disparity switches the gate off: the outputs are calcOpticalFlowPyrLKStereo's own.
+ *  Out of scope (SBM_ERR_UNSUPPORTED): OPTFLOW_USE_INITIAL_FLOW, flags without OPTFLOW_LK_GET_MIN_EIGENVALS (the L1 patch
+ *   error), any other flag bit, any window other than 15 x 3; not expressible: caller-supplied pyramids, colour input.
+ *  Limits: width and height 2..2048 (SBM_ERR_SIZE below 2 and for the reference's assertions win > 2, max_level >= 0;
+ *   SBM_ERR_UNSUPPORTED above 2048), at most 65 535 pairs per call, cap >= 1; pointers to floats and counts 4-byte aligned.
+ *   Coordinates must be finite and within +-2^30 at every level (cvFloor of anything else is undefined in the reference too).
+ *  Kernels: per level one pyrDown launch over both images of every pair of a chunk and one Scharr launch
+ *   over its left images, then ONE tracker launch, one wavefront per keypoint, that walks the levels. Device scratch, held by the
+ *   handle: per pair of a chunk the levels above 0 of both images (1 B per pixel each) and the derivatives of every left level
+ *   (4 B per pixel), ~6.7 B per frame pixel; a call works through its pairs in chunks of at most 256 MiB of it.
+ *  sbm_get_profile: while profiling is enabled (any mode) sbm_lk_stereo_device synchronises and records "lk_pyramid", "lk_track"
+ *   and "lk_total" (ms of the last call, summed over its chunks). */
+#define SBM_LK_USE_INITIAL_FLOW 4    /* cv::OPTFLOW_USE_INITIAL_FLOW: unsupported                     */
+#define SBM_LK_GET_MIN_EIGENVALS 8   /* cv::OPTFLOW_LK_GET_MIN_EIGENVALS: required                    */
+
+typedef struct sbm_lk_params {  /* computeCorrespondences' constants (Stereo.cpp:16-37) */
+  int32_t win_width;         /* winSize.width, 15 (nothing else is supported)                         */
+  int32_t win_height;        /* winSize.height, 3 (nothing else is supported)                         */
+  int32_t max_level;         /* maxLevel, 5                                                           */
+  int32_t max_count;         /* TermCriteria maxCount, 30; clamped to 0..100                          */
+  float epsilon;             /* TermCriteria epsilon, 0.01f; clamped to 0..10                         */
+  int32_t flags;             /* SBM_LK_GET_MIN_EIGENVALS                                              */
+  double min_eig_threshold;  /* minEigThreshold, 1e-4                                                 */
+  float min_disparity;       /* 0.5f                                                                  */
+  float max_disparity;       /* 128.f; negative: no gate                                              */
+} sbm_lk_params;
+
+/* Fill *p with the reference's constants: 15, 3, 5, 30, 0.01f, GET_MIN_EIGENVALS, 1e-4, 0.5f, 128.f. */
+void sbm_lk_params_default(sbm_lk_params* p);
+/* SBM_ERR_NULL, SBM_ERR_SIZE, SBM_ERR_UNSUPPORTED as listed above, else SBM_OK. */
+int sbm_lk_params_validate(const sbm_lk_params* p, int width, int height);
+/* The pyramid alone, of n dense u8 frames in DEVICE memory, so that each level can be checked and used on its own. Layout, level
+ * major: level l (size w_l x h_l, w_0 = width, w_l = (w_{l-1} + 1) / 2) starts n * (sum of w_k * h_k over k < l) bytes into
+ * d_levels and holds the n frames' planes back to back; d_deriv (required when with_deriv != 0) has the same layout counted in
+ * (dx, dy) int16 pairs. Both must hold every level the count rule above keeps (at most n * 4 / 3 * width * height + n elements).
+ * *levels_out (host memory, may be NULL) receives the index of the last level. Synchronous. */
+int sbm_lk_pyramid_device(sbm_handle* h, int n, const void* d_img, int width, int height, int with_deriv, const sbm_lk_params* p,
+                          void* d_levels, void* d_deriv, int* levels_out);
+/* computeCorrespondences on n dense pairs in DEVICE memory. d_kpts / d_count exactly as sbm_gftt_cv_detect_device and
+ * sbm_gftt_select_device write them: n * cap float pairs, n int32 read on the device (a count above cap reads as cap). Outputs:
+ * d_right_pts n * cap float pairs, d_status n * cap bytes, d_err n * cap floats (NULL: not wanted); entries past a frame's count
+ * are left as they were. Asynchronous on the handle's stream unless sync != 0, with the ordering rules of sbm_compute_device. */
+int sbm_lk_stereo_device(sbm_handle* h, int n, const void* d_left, const void* d_right, int width, int height, const void* d_kpts,
+                         const void* d_count, int cap, const sbm_lk_params* p, void* d_right_pts, void* d_status, void* d_err,
+                         int sync);
+/* Host form for ONE pair, shaped like computeCorrespondences(left, right, leftCorners, status): strided 8-bit images (strides in
+ * bytes), npts (x, y) pairs; right_pts npts pairs, status npts bytes, err npts floats or NULL. npts == 0 returns SBM_OK and
+ * touches nothing. Synchronous. */
+int sbm_lk_stereo(sbm_handle* h, const uint8_t* left, size_t left_stride, const uint8_t* right, size_t right_stride, int width,
+                  int height, const float* pts, int npts, const sbm_lk_params* p, float* right_pts, uint8_t* status, float* err);
+/* The sparse branch of generateKeypoints3DStereo (Stereo.cpp:53-117) on what sbm_lk_stereo_device wrote: per slot below the
+ * frame's count a NaN triple where the status is 0, else projectDisparityTo3D(left, left.x - right.x, model), the depth range
+ * check and localTransform -- the same device function as sbm_keypoints3d_device, so the two agree bit for bit on equal
+ * disparities. d_xyz: n * cap * 3 floats; entries past a frame's count are left as they were. */
+int sbm_keypoints3d_lk_device(sbm_handle* h, int n, const void* d_kpts, const void* d_right_pts, const void* d_status,
+                              const void* d_count, int cap, const sbm_stereo_model* model, float min_depth, float max_depth,
+                              void* d_xyz, int sync);
+
 /* The raw HIP stream (hipStream_t) as void*, so callers can order their own work behind ours (record an event on it
  * after sbm_compute_device(..., sync = 0)) or ours behind theirs (hipStreamWaitEvent on it before the call). Every entry
  * point selects the handle's device for the duration of the call and restores the caller's current device on return. */

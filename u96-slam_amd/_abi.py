@@ -92,6 +92,17 @@ class PnpParams(ctypes.Structure):
                 ("confidence", ctypes.c_double)]
 
 
+class LkParams(ctypes.Structure):
+    """`sbm_lk_params` of include/sbm.h: computeCorrespondences' constants (src/slam/src/core/Stereo.cpp:16-37)."""
+
+    _fields_ = [("win_width", ctypes.c_int32), ("win_height", ctypes.c_int32), ("max_level", ctypes.c_int32),
+                ("max_count", ctypes.c_int32), ("epsilon", ctypes.c_float), ("flags", ctypes.c_int32),
+                ("min_eig_threshold", ctypes.c_double), ("min_disparity", ctypes.c_float), ("max_disparity", ctypes.c_float)]
+
+
+LK_USE_INITIAL_FLOW = 4
+LK_GET_MIN_EIGENVALS = 8
+
 # `sbm_pnp_result` (216 bytes) and `sbm_pnp_hypothesis` (128 bytes) as numpy record types
 PNP_RESULT_DTYPE = np.dtype([("status", "<i4"), ("num_matches", "<i4"), ("num_inliers", "<i4"), ("ransac_inliers", "<i4"),
                              ("best_iteration", "<i4"), ("niters", "<i4"), ("refine_solves", "<i4"), ("refine_exit", "<i4"),
@@ -228,6 +239,14 @@ def load_library():
     L.sbm_pnp_params_validate.argtypes = [pp_]
     L.sbm_estimate_motion_device.argtypes = [vp, ci, ci, vp, vp, vp, vp, ci, vp, vp, vp, mp, pp_, vp, vp, vp, ci]
     L.sbm_estimate_motion.argtypes = [vp, vp, ci, vp, vp, ci, vp, ci, vp, mp, pp_, vp, vp]
+    lp = ctypes.POINTER(LkParams)
+    L.sbm_lk_params_default.argtypes = [lp]
+    L.sbm_lk_params_default.restype = None
+    L.sbm_lk_params_validate.argtypes = [lp, ci, ci]
+    L.sbm_lk_pyramid_device.argtypes = [vp, ci, vp, ci, ci, ci, lp, vp, vp, ctypes.POINTER(ci)]
+    L.sbm_lk_stereo_device.argtypes = [vp, ci, vp, vp, ci, ci, vp, vp, ci, lp, vp, vp, vp, ci]
+    L.sbm_lk_stereo.argtypes = [vp, vp, sz, vp, sz, ci, ci, vp, ci, lp, vp, vp, vp]
+    L.sbm_keypoints3d_lk_device.argtypes = [vp, ci, vp, vp, vp, vp, ci, mp, ctypes.c_float, ctypes.c_float, vp, ci]
     L.sbm_stream.argtypes = [vp]
     L.sbm_stream.restype = vp
     L.sbm_strerror.argtypes = [ci]

@@ -121,6 +121,9 @@ hipError_t launch_reproject(const int16_t* disp, float* xyz, int n, int W, int H
                             int apply_local, hipStream_t s);
 hipError_t launch_keypoints3d(const int16_t* disp, const float* kp, float* xyz, int W, int H, int nk,
                               const sbm_stereo_model& m, float min_depth, float max_depth, hipStream_t s);
+// The sparse branch of the same function: disparity = left.x - right.x under the status mask, n frames of cap slots each.
+hipError_t launch_keypoints3d_lk(const float* kp, const float* rp, const uint8_t* status, const int* count, int n, int cap,
+                                 const sbm_stereo_model& m, float min_depth, float max_depth, float* xyz, hipStream_t s);
 
 // Semi-global matcher (sbm_sgbm.hip). Naming follows cv::StereoSGBM (calib3d stereosgbm.cpp): computable columns
 // X = minX1 + x, x in [0, W1); buffer index d <-> disparity minD + d; P1, P2, d12 and uniq are the effective values.

@@ -76,6 +76,20 @@ __global__ void __launch_bounds__(256) reproject_kernel(const int16_t* __restric
   xyz[3 * o + 2] = p.z;
 }
 
+// Stereo.cpp:88-112: what both branches of generateKeypoints3DStereo do with a keypoint and its disparity
+__device__ __forceinline__ Pt3 keypoint_depth(float kx, float ky, float d, const sbm_stereo_model& m, float min_depth,
+                                              float max_depth) {
+  Pt3 pt = nan3();
+  if (d != 0.0f) {
+    const Pt3 t = project_disparity(kx, ky, d, m);
+    if (finite3(t) && (min_depth < 0.0f || t.z > min_depth) && (max_depth <= 0.0f || t.z <= max_depth)) {
+      pt = t;
+      if (m.has_local) pt = transform_point(pt, m.local);
+    }
+  }
+  return pt;
+}
+
 // Stereo.cpp:66-112 (branch "from dense depth map")
 __global__ void __launch_bounds__(256) keypoints3d_kernel(const int16_t* __restrict__ disp, const float* __restrict__ kp,
                                                            float* __restrict__ xyz, int W, int H, int nk,
@@ -88,17 +102,27 @@ __global__ void __launch_bounds__(256) keypoints3d_kernel(const int16_t* __restr
   if (ix >= 0 && ix < W && iy >= 0 && iy < H) {   // the reference indexes unchecked; out-of-image keypoints -> NaN here
     float d = (float)disp[(size_t)iy * W + ix] / 16.0f;
     if (d < 0) d = 0;
-    if (d != 0.0f) {
-      const Pt3 t = project_disparity(kx, ky, d, m);
-      if (finite3(t) && (min_depth < 0.0f || t.z > min_depth) && (max_depth <= 0.0f || t.z <= max_depth)) {
-        pt = t;
-        if (m.has_local) pt = transform_point(pt, m.local);
-      }
-    }
+    pt = keypoint_depth(kx, ky, d, m, min_depth, max_depth);
   }
   xyz[3 * i + 0] = pt.x;
   xyz[3 * i + 1] = pt.y;
   xyz[3 * i + 2] = pt.z;
+}
+
+// Stereo.cpp:66-112 (the other branch: disparity = leftCorners[i].x - rightCorners[i].x where the mask is set); frame
+// blockIdx.y, slots below its count
+__global__ void __launch_bounds__(256) keypoints3d_lk_kernel(const float* __restrict__ kp, const float* __restrict__ rp,
+                                                              const uint8_t* __restrict__ status, const int* __restrict__ count,
+                                                              float* __restrict__ xyz, int cap, sbm_stereo_model m, float min_depth,
+                                                              float max_depth) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= min(count[blockIdx.y], cap)) return;
+  const size_t s = (size_t)blockIdx.y * cap + i;
+  Pt3 pt = nan3();
+  if (status[s]) pt = keypoint_depth(kp[2 * s], kp[2 * s + 1], kp[2 * s] - rp[2 * s], m, min_depth, max_depth);
+  xyz[3 * s + 0] = pt.x;
+  xyz[3 * s + 1] = pt.y;
+  xyz[3 * s + 2] = pt.z;
 }
 
 // cv::StereoBM::compute into a CV_32F destination: disp16.convertTo(dst, CV_32F, 1. / 16) -- exact in float
@@ -139,6 +163,13 @@ hipError_t launch_keypoints3d(const int16_t* disp, const float* kp, float* xyz, 
                               const sbm_stereo_model& m, float min_depth, float max_depth, hipStream_t s) {
   if (nk <= 0) return hipSuccess;
   hipLaunchKernelGGL(keypoints3d_kernel, dim3((nk + 255) / 256), dim3(256), 0, s, disp, kp, xyz, W, H, nk, m, min_depth,
+                     max_depth);
+  return hipGetLastError();
+}
+
+hipError_t launch_keypoints3d_lk(const float* kp, const float* rp, const uint8_t* status, const int* count, int n, int cap,
+                                 const sbm_stereo_model& m, float min_depth, float max_depth, float* xyz, hipStream_t s) {
+  hipLaunchKernelGGL(keypoints3d_lk_kernel, dim3((cap + 255) / 256, n), dim3(256), 0, s, kp, rp, status, count, xyz, cap, m, min_depth,
                      max_depth);
   return hipGetLastError();
 }

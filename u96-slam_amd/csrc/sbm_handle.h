@@ -233,6 +233,11 @@ struct sbm_handle {
     sbm::StageClock clock;
     template <class F> void each(F f) { f(scratch); f(io); }
   } pnp;
+  struct {   // LK stereo: levels 1.. of both images and the left derivatives of one chunk of pairs; the host form's staging
+    sbm::DevBuf pyr, deriv, io;
+    sbm::StageClock clock;
+    template <class F> void each(F f) { f(pyr); f(deriv); f(io); }
+  } lk;
 };
 
 namespace sbm {

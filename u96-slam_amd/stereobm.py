@@ -10,27 +10,28 @@ src/slam/src/core/main.cpp:201-215 of the reference:
 with the status code and OpenCV's message, where cv::StereoBM::compute would throw cv::Error.
 
 The C-ABI's structures and loader are in _abi.py, the handle and the one path to its device entry points in _engine.py, and
-each family beside the dense path in a module of its own (_frontend, _fpga, _gftt, _orb, _match, _pnp); StereoBM joins them,
+each family beside the dense path in a module of its own (_frontend, _fpga, _gftt, _orb, _match, _pnp, _lk); StereoBM joins them,
 and every name is offered from here as before.
 """
 import ctypes
 
 import numpy as np
 
-from . import _engine, _fpga, _frontend, _gftt, _match, _orb, _pnp
+from . import _engine, _fpga, _frontend, _gftt, _lk, _match, _orb, _pnp
 from ._abi import (PNP_FEW_MATCHES, PNP_FEW_RANSAC_INLIERS, PNP_FEW_REFINED_INLIERS, PNP_HYP_DTYPE, PNP_NO_MODEL, PNP_OK,  # noqa: F401
                    PNP_RESULT_DTYPE, PREFILTER_FLAVOUR_CV, PREFILTER_FLAVOUR_RTL, PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL,
-                   FpgaParams, GfttCvParams, GfttSelectParams, MatchParams, OrbParams, PnpParams, RectCam, SbmParams, StereoBMError,
+                   FpgaParams, GfttCvParams, GfttSelectParams, LK_GET_MIN_EIGENVALS, LK_USE_INITIAL_FLOW, LkParams, MatchParams, OrbParams, PnpParams, RectCam, SbmParams, StereoBMError,
                    StereoModel, _check, library_path, load_library, loaded_library_name)
 from ._fpga import fpga_params, fpga_params_from_regs, fpga_sad_size_reg, fpga_validate  # noqa: F401
 from ._frontend import make_rect_cam  # noqa: F401
 from ._gftt import gftt_cv_params, gftt_cv_validate, gftt_select_capacity, gftt_select_params, gftt_select_validate  # noqa: F401
+from ._lk import lk_level_sizes, lk_params, lk_validate  # noqa: F401
 from ._match import match_params, match_validate  # noqa: F401
 from ._orb import orb_params, orb_pattern_array, orb_validate  # noqa: F401
 from ._pnp import pnp_params, pnp_records, pnp_validate  # noqa: F401
 
 
-class StereoBM(_engine.Engine, _frontend.FrontEnd, _fpga.FpgaMatcher, _gftt.Gftt, _orb.Orb, _match.Match, _pnp.Pnp):
+class StereoBM(_engine.Engine, _frontend.FrontEnd, _fpga.FpgaMatcher, _gftt.Gftt, _orb.Orb, _match.Match, _pnp.Pnp, _lk.Lk):
     """cv::StereoBM look-alike. One instance owns one device handle (stream + scratch); not thread-safe."""
 
     def __init__(self, numDisparities=0, blockSize=21, device=0):
