@@ -117,7 +117,8 @@ enum {
   SBM_ERR_HIP = -21,             /* a HIP runtime call failed (see sbm_last_hip_error)                */
   SBM_ERR_NOMEM = -22,           /* device or host allocation failed                                  */
   SBM_ERR_UNSUPPORTED = -23,     /* valid OpenCV parameters this build cannot run (documented limits) */
-  SBM_ERR_BATCH = -24            /* batch count <= 0                                                  */
+  SBM_ERR_BATCH = -24,           /* batch count <= 0                                                  */
+  SBM_ERR_OCC_FULL = -25         /* occupancy map: points found the table full (see sbm_occ_overflow) */
 };
 
 #define SBM_PREFILTER_NORMALIZED_RESPONSE 0
@@ -939,6 +940,90 @@ int sbm_lk_stereo(sbm_handle* h, const uint8_t* left, size_t left_stride, const 
 int sbm_keypoints3d_lk_device(sbm_handle* h, int n, const void* d_kpts, const void* d_right_pts, const void* d_status,
                               const void* d_count, int cap, const sbm_stereo_model* model, float min_depth, float max_depth,
                               void* d_xyz, int sync);
+
+/* ---- occupancy map: buildOccupancyGridMap (src/slam/src/core/main.cpp:495-561) ----------------------------------------------
+ * The reference's last dense consumer of the disparity maps: for every key frame it reprojects every pixel of the decimated map,
+ * moves the point through the camera's local transform and the optimised pose, gates it on range, turns it into an octomap key
+ * (coordToKeyChecked) and calls tree.updateNode(key, true) -- one octree descent per point -- and at the end writes the tree with
+ * writeBinary("slam.bt"). Every update is a hit, so after writeBinary's toMaxLikelihood() + prune() the file depends only on the
+ * SET of distinct voxel keys. Here the per-pixel work and a concurrent set insert run on the device, only the distinct voxels
+ * cross PCIe, and the host writes the .bt stream from them. tests/occupancy_ref (sequential C) implements exactly this text, and
+ * tests/golden/occupancy_octomap.npz holds what the reference's own octomap (vendored under src/slam/src/octomap) answered for
+ * the norm, the key and the stream on a few thousand points.
+ *  Per plane p (with its pose, 12 floats r11 r12 r13 o14 / r21 .. / r31 .., the layout of sbm_stereo_model.local) and pixel
+ *  (row, col) of the (possibly decimated) int16 map, IEEE binary32 / binary64 without contraction:
+ *   disparity  d = (float)(disp / 16.0f) (main.cpp:529); the pixel is skipped unless d > 0.
+ *   reproject  pt = projectDisparityTo3D((col * scale, row * scale), d, model), exactly as sbm_reproject_device; skipped unless
+ *              all three coordinates are finite (main.cpp:533-536).
+ *   transform  pt = transformPoint(pt, model.local) when model.has_local, then pt = transformPoint(pt, pose): per row
+ *              r1 * x + r2 * y + r3 * z + o in float, left to right (Stereo.cpp:189-198; main.cpp:538-539).
+ *   gate       v = pt - origin in float, origin = (o14, o24, o34) of the pose; norm = sqrt((double)(v.x * v.x + v.y * v.y +
+ *              v.z * v.z)) with the sum in FLOAT (octomap's Vector3::norm); kept iff norm <= (double)(range_max * range_max),
+ *              the product in float. QUIRK, restated on purpose: the reference compares the norm, not its square, with the
+ *              SQUARED range (main.cpp:501, 544), so its 5 m gate keeps everything within 25 m.
+ *   key        per axis s = (int)floor(resolution_factor * (double)coord) + 32768, resolution_factor = 1. / resolution in double
+ *              (OcTreeBaseImpl.hxx:158, 310-321); kept iff 0 <= s < 65536 on all three axes. A coordinate that is not finite or
+ *              whose floor fits no int rejects the point (what x86 gives for the reference's cast). The reference does not look
+ *              at coordToKeyChecked's verdict and would update the tree with a half-written key; a rejected point is dropped here.
+ *   packed     k0 << 32 | k1 << 16 | k2 in a uint64_t (axis 0 = x); the all-ones word is the empty slot.
+ *  The reference takes the pose by ORDINAL, optimized_poses[i] with i counting from 1, not by node id; the engine uses the pose
+ *  the caller passes.
+ *  Map. sbm_occ_map is created from a handle with a capacity in voxels and uses that handle's stream, scratch and stage clock; it
+ *  must be destroyed before the handle, and like the handle it serves one thread at a time. Device state: an open-addressing
+ *  table of 64-bit keys, linear probing, with the smallest power of two of slots >= 2 * capacity (load factor <= 1/2 up to the
+ *  capacity); a uint32 hit count per slot (wraps at 2^32); a 64-bit overflow counter. 12 B per slot.
+ *  Insert, ONE launch from pixel to table (no n * h * w intermediate): a wavefront reduces its 64 keys to distinct leaders with
+ *  lane counts, and only the leaders do a 64-bit compare-and-swap on the key slot and an atomic add of the lane count. A key
+ *  that finds no free slot within min(slots, 1024) probes adds its lane count to the overflow counter and the entry point returns
+ *  SBM_ERR_OCC_FULL (with sync == 0 nothing is known yet: SBM_OK, and the next synchronous insert, sbm_occ_overflow or a fetch
+ *  reports it). Nothing is dropped silently: stored hits + overflow = accepted points. Key set and hit counts do not depend on
+ *  insertion order or on how planes are split across calls (as long as nothing overflowed). Up to the capacity no probe chain
+ *  comes near the bound; a map filled past it keeps storing while slots are free, with longer chains.
+ *  Fetch compacts the occupied slots and sorts them ascending by packed key, counts as payload, with an LSD radix sort over the
+ *  48 key bits (6 passes of 8 bits), all on the device.
+ *  sbm_get_profile: while profiling is enabled (any mode) inserts and fetches synchronise and record "occ_insert" / "occ_fetch"
+ *  (ms of the last call). */
+typedef struct sbm_occ_params {
+  double resolution;   /* octomap::OcTree(0.1): edge of a voxel, finite and > 0                  */
+  float range_max;     /* rangeMax_ 5.0f; squared in float and compared with the NORM (see gate) */
+  int32_t tree_depth;  /* 16 (octomap's fixed depth; nothing else is supported)                  */
+} sbm_occ_params;
+typedef struct sbm_occ_map sbm_occ_map; /* opaque */
+
+/* Fill *p with the reference's constants: 0.1, 5.0f, 16. */
+void sbm_occ_params_default(sbm_occ_params* p);
+/* SBM_ERR_NULL; SBM_ERR_SIZE for a resolution that is not finite and > 0 or a range_max that is NaN or negative;
+ * SBM_ERR_UNSUPPORTED for tree_depth != 16; else SBM_OK. */
+int sbm_occ_params_validate(const sbm_occ_params* p);
+/* A map for up to `capacity` voxels (1 .. 2^30) on the handle's device, empty. */
+int sbm_occ_create(sbm_handle* h, const sbm_occ_params* p, size_t capacity, sbm_occ_map** out);
+void sbm_occ_destroy(sbm_occ_map* map);
+/* Empties the table and the overflow counter without reallocating. Asynchronous on the handle's stream. */
+int sbm_occ_reset(sbm_occ_map* map);
+/* n planes of width x height int16 in DEVICE memory, densely packed; poses in HOST memory, n * 12 floats, read before the call
+ * returns. Asynchronous on the handle's stream unless sync != 0, with the ordering rules of sbm_compute_device. */
+int sbm_occ_insert_device(sbm_occ_map* map, int n, const void* d_disp, int width, int height, int scale,
+                          const sbm_stereo_model* model, const float* poses, int sync);
+/* The same from planes in HOST memory (n * height * width int16, dense). Synchronous. */
+int sbm_occ_insert(sbm_occ_map* map, int n, const int16_t* disp, int width, int height, int scale, const sbm_stereo_model* model,
+                   const float* poses);
+/* Distinct voxels stored / points that found the table full, so far. Both synchronise the handle's stream. */
+int sbm_occ_size(sbm_occ_map* map, size_t* size);
+int sbm_occ_overflow(sbm_occ_map* map, uint64_t* overflow);
+/* The stored voxels ascending by packed key into DEVICE memory: d_keys cap uint64 (8-byte aligned), d_hits cap uint32 (may be
+ * NULL); *count = sbm_occ_size. SBM_ERR_SIZE, with *count set and nothing written, when cap < count; SBM_ERR_OCC_FULL, with the
+ * outputs complete, when points overflowed. Synchronous; the map is left as it was. */
+int sbm_occ_fetch_device(sbm_occ_map* map, void* d_keys, void* d_hits, size_t cap, size_t* count);
+/* The same into HOST memory. */
+int sbm_occ_fetch(sbm_occ_map* map, uint64_t* keys, uint32_t* hits, size_t cap, size_t* count);
+/* Plain host code, no GPU: writes to `path` the octomap binary stream (.bt) that OcTree::writeBinary produces for a tree of
+ * depth 16 holding exactly these n packed keys (any order, duplicates allowed) as occupied leaves: the header lines ("size" =
+ * node count after prune()), then depth first per inner node 2 bits per child (01 occupied leaf, 11 inner, 00 none; children
+ * 0-3 in the first byte, 4-7 in the second; child index = bit of x + 2 * bit of y + 4 * bit of z as computeChildIdx), eight
+ * sibling leaves collapsed into their parent as prune() does, built by one pass over the keys in Morton order.
+ * SBM_ERR_NULL, SBM_ERR_SIZE (resolution, or a key above 48 bits), SBM_ERR_NOMEM, SBM_ERR_UNSUPPORTED (the file cannot be
+ * written). */
+int sbm_occ_write_binary(const uint64_t* keys, size_t n, double resolution, const char* path);
 
 /* The raw HIP stream (hipStream_t) as void*, so callers can order their own work behind ours (record an event on it
  * after sbm_compute_device(..., sync = 0)) or ours behind theirs (hipStreamWaitEvent on it before the call). Every entry

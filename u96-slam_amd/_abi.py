@@ -100,6 +100,13 @@ class LkParams(ctypes.Structure):
                 ("min_eig_threshold", ctypes.c_double), ("min_disparity", ctypes.c_float), ("max_disparity", ctypes.c_float)]
 
 
+class OccParams(ctypes.Structure):
+    """`sbm_occ_params` of include/sbm.h: buildOccupancyGridMap's constants (src/slam/src/core/main.cpp:499-501)."""
+
+    _fields_ = [("resolution", ctypes.c_double), ("range_max", ctypes.c_float), ("tree_depth", ctypes.c_int32)]
+
+
+ERR_OCC_FULL = -25
 LK_USE_INITIAL_FLOW = 4
 LK_GET_MIN_EIGENVALS = 8
 
@@ -247,6 +254,21 @@ def load_library():
     L.sbm_lk_stereo_device.argtypes = [vp, ci, vp, vp, ci, ci, vp, vp, ci, lp, vp, vp, vp, ci]
     L.sbm_lk_stereo.argtypes = [vp, vp, sz, vp, sz, ci, ci, vp, ci, lp, vp, vp, vp]
     L.sbm_keypoints3d_lk_device.argtypes = [vp, ci, vp, vp, vp, vp, ci, mp, ctypes.c_float, ctypes.c_float, vp, ci]
+    ocp = ctypes.POINTER(OccParams)
+    L.sbm_occ_params_default.argtypes = [ocp]
+    L.sbm_occ_params_default.restype = None
+    L.sbm_occ_params_validate.argtypes = [ocp]
+    L.sbm_occ_create.argtypes = [vp, ocp, sz, ctypes.POINTER(vp)]
+    L.sbm_occ_destroy.argtypes = [vp]
+    L.sbm_occ_destroy.restype = None
+    L.sbm_occ_reset.argtypes = [vp]
+    L.sbm_occ_insert_device.argtypes = [vp, ci, vp, ci, ci, ci, mp, vp, ci]
+    L.sbm_occ_insert.argtypes = [vp, ci, vp, ci, ci, ci, mp, vp]
+    L.sbm_occ_size.argtypes = [vp, ctypes.POINTER(sz)]
+    L.sbm_occ_overflow.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    L.sbm_occ_fetch_device.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_fetch.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_write_binary.argtypes = [vp, sz, ctypes.c_double, ctypes.c_char_p]
     L.sbm_stream.argtypes = [vp]
     L.sbm_stream.restype = vp
     L.sbm_strerror.argtypes = [ci]

@@ -1,6 +1,6 @@
 // sbm_api.hip -- C-ABI of libsbm_hip.so (declared in include/sbm.h): parameters, the handle's life and its pool, the block
 // matcher on device buffers, profiling and debug dispatch, and the thin rectify / prefilter / consumer entry points. The other
-// families' entry points sit with their kernels (sbm_fpga, sbm_sgbm, sbm_gftt, sbm_gftt_select, sbm_orb, sbm_match, sbm_pnp, sbm_lk); the block
+// families' entry points sit with their kernels (sbm_fpga, sbm_sgbm, sbm_gftt, sbm_gftt_select, sbm_orb, sbm_match, sbm_pnp, sbm_lk, sbm_occupancy); the block
 // matcher's host-buffer paths are in sbm_host.hip. Replaces cv::StereoBM::compute at src/slam/src/core/main.cpp:201-216.
 //
 // Stage order (same as cv::StereoBM::compute): prefilter both images -> SAD/WTA on the valid-ROI rows
@@ -69,6 +69,7 @@ const char* sbm_strerror(int code) {
     case SBM_ERR_NOMEM: return "out of memory";
     case SBM_ERR_UNSUPPORTED: return "configuration outside this build's limits";
     case SBM_ERR_BATCH: return "batch count must be positive";
+    case SBM_ERR_OCC_FULL: return "occupancy map full: points were counted as overflow, not stored (see sbm_occ_overflow)";
     default: return "unknown status";
   }
 }
@@ -92,6 +93,7 @@ static void free_buffers(sbm_handle* h) {
   release_all(h->mt);
   release_all(h->pnp);
   release_all(h->lk);
+  release_all(h->occ);
 }
 
 // The reference re-creates its matcher for every frame (cv::StereoBM::create inside the loop, main.cpp:201). Streams,
@@ -106,7 +108,7 @@ static int g_pool_n = 0;
 static size_t scratch_bytes(sbm_handle* h) {
   return bytes_held(h->bm) + bytes_held(h->fp) + bytes_held(h->st) + h->pin_bytes + bytes_held(h->fq) + bytes_held(h->sg) +
          bytes_held(h->gs) + bytes_held(h->gc) + bytes_held(h->orb) + bytes_held(h->mt) +
-         bytes_held(h->pnp) + bytes_held(h->lk);
+         bytes_held(h->pnp) + bytes_held(h->lk) + bytes_held(h->occ);
 }
 
 // Stage times: the block matcher's, and every family's stage clock, start at zero.
@@ -123,6 +125,7 @@ static void reset_profile(sbm_handle* h, int enabled) {
   h->mt.clock.reset();
   h->pnp.clock.reset();
   h->lk.clock.reset();
+  h->occ.clock.reset();
 }
 
 static void destroy_now(sbm_handle* h);
@@ -172,6 +175,8 @@ int sbm_create(sbm_handle** out, const sbm_params* p, int device) {
   h->gc.clock.init(kGfttCv);
   static const char* const kLk[] = {"lk_pyramid", "lk_track", "lk_total"};
   h->lk.clock.init(kLk);
+  static const char* const kOcc[] = {"occ_insert", "occ_fetch"};
+  h->occ.clock.init(kOcc);
   DeviceScope dscope(device);
   if (dscope.enter() != hipSuccess) {
     delete h;
@@ -233,6 +238,7 @@ static void destroy_now(sbm_handle* h) {
   h->mt.clock.release();
   h->pnp.clock.release();
   h->lk.clock.release();
+  h->occ.clock.release();
   for (int r = 0; r < sbm_handle::kRing; r++)
     for (int i = 0; i < sbm_handle::kMarks; i++)
       if (h->ev[r][i]) hipEventDestroy(h->ev[r][i]);
@@ -572,6 +578,7 @@ int sbm_get_profile(sbm_handle* h, const char* name, float* ms) {
     if (!t) t = h->mt.clock.find(name);
     if (!t) t = h->pnp.clock.find(name);
     if (!t) t = h->lk.clock.find(name);
+    if (!t) t = h->occ.clock.find(name);
     if (!t) return SBM_ERR_UNSUPPORTED;
     *ms = *t;
   }

@@ -1,0 +1,528 @@
+// sbm_occupancy.hip -- the occupancy voxel map of the reference's buildOccupancyGridMap (src/slam/src/core/main.cpp:495-561)
+// as a device-side set of octomap keys, and the host writer of the octomap binary stream.  gfx950.
+//
+// include/sbm.h ("occupancy map: buildOccupancyGridMap") states the arithmetic; the point functions are those of
+// sbm_consume.hip (sbm_consume_math.h). Nothing here contracts a multiply-add (the pragma below and -ffp-contract=off).
+//
+//   occ_insert_kernel   one thread per pixel: disparity -> point -> two transforms -> gate -> key; the wavefront then reduces
+//                       its 64 keys to distinct leaders with lane counts (ballot + readlane over the distinct values) and only
+//                       the leaders touch the table: a 64-bit compare-and-swap on the key slot, an atomic add of the lane count.
+//   occ_compact_kernel  occupied slots -> dense (key, hits) arrays, one atomic per wavefront.
+//   occ_hist / occ_scan / occ_scatter   one 8-bit pass of an LSD radix sort: digit counts per tile, an exclusive scan of the
+//                       digit-major count table, and a stable scatter (one wavefront per tile walks it 64 keys at a time and
+//                       ranks equal digits by ballots).
+#include <math.h>
+#include <stdio.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "sbm_consume_math.h"
+#include "sbm_handle.h"
+
+struct sbm_occ_map {
+  sbm_handle* h;
+  sbm_occ_params p;
+  size_t capacity;           // voxels the caller asked for
+  uint32_t slots;            // power of two >= 2 * capacity
+  sbm::DevBuf keys, hits;    // the table
+  sbm::DevBuf ctr;           // OccCounters
+  template <class F> void each(F f) { f(keys); f(hits); f(ctr); }
+};
+
+namespace sbm {
+
+#pragma clang fp contract(off)
+
+constexpr unsigned long long kOccEmpty = ~0ull;
+constexpr int kOccChunk = 64;        // planes per insert launch: their poses travel as kernel arguments (3 KiB)
+constexpr uint32_t kOccMaxProbe = 1024;
+constexpr int kOccTile = 1024;       // keys per workgroup of a radix pass
+constexpr size_t kOccMaxCapacity = (size_t)1 << 30;
+
+struct OccCounters {
+  unsigned long long overflow;   // points that found the table full
+  unsigned size;                 // occupied slots
+  unsigned cursor;               // compaction cursor of a fetch
+};
+
+struct OccPoses { float t[kOccChunk][12]; };
+
+struct OccGeom {
+  int W, H, scale;
+  float range_max_sqrd;          // range_max * range_max, formed in float on the host as main.cpp:501 does
+  double factor;                 // 1. / resolution
+  uint32_t mask, max_probe;
+};
+
+__device__ __forceinline__ uint32_t occ_hash(unsigned long long key, uint32_t mask) {
+  return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
+}
+
+// OcTreeBaseImpl.hxx:310-321 on one axis: floor in double, then 0 <= floor + 32768 < 65536. NaN fails both comparisons, and so
+// does every value whose floor fits no int (the reference's cast gives INT_MIN there, which its range test rejects).
+__device__ __forceinline__ bool occ_axis(double factor, float coord, unsigned* k) {
+#pragma clang fp contract(off)
+  const double f = floor(factor * (double)coord);
+  if (!(f >= -32768.0 && f < 32768.0)) return false;
+  *k = (unsigned)((int)f + 32768);
+  return true;
+}
+
+__global__ void __launch_bounds__(256) occ_insert_kernel(const int16_t* __restrict__ disp, OccGeom g, sbm_stereo_model m, OccPoses poses,
+                                                          unsigned long long* __restrict__ keys, unsigned* __restrict__ hits,
+                                                          OccCounters* __restrict__ ctr) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  unsigned long long key = kOccEmpty;
+  if (i < g.W * g.H) {
+    const int r = i / g.W, c = i % g.W;
+    const float d = (float)disp[(size_t)blockIdx.y * g.W * g.H + i] / 16.0f;       // main.cpp:529
+    if (d > 0) {
+      Pt3 p = project_disparity((float)(c * g.scale), (float)(r * g.scale), d, m);
+      if (finite3(p)) {
+        const float* pose = poses.t[blockIdx.y];
+        if (m.has_local) p = transform_point(p, m.local);
+        p = transform_point(p, pose);
+        const float vx = p.x - pose[3], vy = p.y - pose[7], vz = p.z - pose[11];
+        const float nsq = vx * vx + vy * vy + vz * vz;          // Vector3::norm_sq, a float expression
+        unsigned k0, k1, k2;
+        if (__dsqrt_rn((double)nsq) <= (double)g.range_max_sqrd && occ_axis(g.factor, p.x, &k0) && occ_axis(g.factor, p.y, &k1) &&
+            occ_axis(g.factor, p.z, &k2))
+          key = (unsigned long long)k0 << 32 | (unsigned long long)k1 << 16 | k2;
+      }
+    }
+  }
+  // the wavefront's distinct keys: the lowest lane of each value leads and learns how many lanes hold it
+  const int lane = threadIdx.x & 63;
+  const unsigned lo = (unsigned)key, hi = (unsigned)(key >> 32);
+  unsigned long long todo = __ballot(key != kOccEmpty);
+  unsigned count = 0;
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const unsigned llo = __builtin_amdgcn_readlane(lo, leader), lhi = __builtin_amdgcn_readlane(hi, leader);
+    const unsigned long long same = __ballot(lo == llo && hi == lhi);   // the empty word has hi = 0xFFFFFFFF: no key matches it
+    if (lane == leader) count = __popcll(same);
+    todo &= ~same;
+  }
+  if (!count) return;
+  uint32_t slot = occ_hash(key, g.mask);
+  for (uint32_t probe = 0; probe < g.max_probe; probe++, slot = (slot + 1) & g.mask) {
+    unsigned long long cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == kOccEmpty) {
+      cur = atomicCAS(&keys[slot], kOccEmpty, key);
+      if (cur == kOccEmpty) {
+        atomicAdd(&ctr->size, 1u);
+        cur = key;
+      }
+    }
+    if (cur == key) {
+      atomicAdd(&hits[slot], count);
+      return;
+    }
+  }
+  atomicAdd(&ctr->overflow, (unsigned long long)count);
+}
+
+__global__ void __launch_bounds__(256) occ_compact_kernel(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ hits,
+                                                           uint32_t slots, uint32_t cap, unsigned long long* __restrict__ out_keys,
+                                                           unsigned* __restrict__ out_hits, OccCounters* __restrict__ ctr) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  const unsigned long long k = i < slots ? keys[i] : kOccEmpty;
+  const unsigned long long live = __ballot(k != kOccEmpty);
+  if (!live) return;
+  const int lane = threadIdx.x & 63;
+  const int leader = __ffsll((long long)live) - 1;
+  unsigned base = 0;
+  if (lane == leader) base = atomicAdd(&ctr->cursor, (unsigned)__popcll(live));
+  base = __builtin_amdgcn_readlane(base, leader);
+  if (k == kOccEmpty) return;
+  const uint32_t o = base + __popcll(live & ((1ull << lane) - 1));
+  if (o >= cap) return;   // the host sized the outputs from ctr->size; a slot claimed since then has no room
+  out_keys[o] = k;
+  out_hits[o] = hits[i];
+}
+
+// digit counts of one tile: hist[digit * tiles + tile]
+__global__ void __launch_bounds__(256) occ_hist_kernel(const unsigned long long* __restrict__ keys, uint32_t n, int shift,
+                                                        unsigned* __restrict__ hist, uint32_t tiles) {
+  __shared__ unsigned cnt[256];
+  cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t base = blockIdx.x * kOccTile;
+  for (uint32_t j = threadIdx.x; j < kOccTile && base + j < n; j += 256) atomicAdd(&cnt[(keys[base + j] >> shift) & 255], 1u);
+  __syncthreads();
+  hist[threadIdx.x * tiles + blockIdx.x] = cnt[threadIdx.x];
+}
+
+// exclusive scan of the digit-major table in place; one workgroup, thread = digit
+__global__ void __launch_bounds__(256) occ_scan_kernel(unsigned* __restrict__ hist, uint32_t tiles) {
+  __shared__ unsigned total[256];
+  unsigned* row = hist + (size_t)threadIdx.x * tiles;
+  unsigned sum = 0;
+  for (uint32_t t = 0; t < tiles; t++) {
+    const unsigned v = row[t];
+    row[t] = sum;
+    sum += v;
+  }
+  total[threadIdx.x] = sum;
+  __syncthreads();
+  unsigned before = 0;
+  for (int d = 0; d < (int)threadIdx.x; d++) before += total[d];
+  for (uint32_t t = 0; t < tiles; t++) row[t] += before;
+}
+
+// stable scatter of one tile by one wavefront
+__global__ void __launch_bounds__(64) occ_scatter_kernel(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ vals,
+                                                          uint32_t n, int shift, const unsigned* __restrict__ hist, uint32_t tiles,
+                                                          unsigned long long* __restrict__ out_keys, unsigned* __restrict__ out_vals) {
+  __shared__ unsigned offs[256];
+  const int lane = threadIdx.x;
+  for (int d = lane; d < 256; d += 64) offs[d] = hist[(size_t)d * tiles + blockIdx.x];
+  __syncthreads();
+  const uint32_t base = blockIdx.x * kOccTile;
+  for (uint32_t j = 0; j < kOccTile && base + j < n; j += 64) {   // the condition is the same for every lane
+    const uint32_t i = base + j + lane;
+    const bool live = i < n;
+    const unsigned long long k = live ? keys[i] : 0;
+    const unsigned digit = (unsigned)(k >> shift) & 255;
+    unsigned long long same = __ballot(live);
+#pragma unroll
+    for (int b = 0; b < 8; b++) {
+      const unsigned long long has = __ballot((digit >> b) & 1);
+      same &= ((digit >> b) & 1) ? has : ~has;
+    }
+    const unsigned rank = __popcll(same & ((1ull << lane) - 1));
+    const unsigned pos = live ? offs[digit] + rank : 0;
+    __syncthreads();
+    if (live && rank + 1 == (unsigned)__popcll(same)) offs[digit] = pos + 1;   // the last lane of a digit moves its offset on
+    __syncthreads();
+    if (live && pos < n) {
+      out_keys[pos] = k;
+      out_vals[pos] = vals[i];
+    }
+  }
+}
+
+static int occ_read_counters(sbm_occ_map* map, OccCounters* c) {
+  sbm_handle* h = map->h;
+  HIPCHK(h, hipMemcpyAsync(c, map->ctr.p, sizeof(*c), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+
+static int occ_clear(sbm_occ_map* map) {
+  sbm_handle* h = map->h;
+  HIPCHK(h, hipMemsetAsync(map->keys.p, 0xFF, (size_t)map->slots * 8, h->stream));
+  HIPCHK(h, hipMemsetAsync(map->hits.p, 0, (size_t)map->slots * 4, h->stream));
+  HIPCHK(h, hipMemsetAsync(map->ctr.p, 0, sizeof(OccCounters), h->stream));
+  return SBM_OK;
+}
+
+static int occ_check_insert(const sbm_occ_map* map, int n, const void* disp, int width, int height, int scale,
+                            const sbm_stereo_model* model, const float* poses) {
+  if (!map || !disp || !model || !poses) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  if (width <= 0 || height <= 0 || scale <= 0) return SBM_ERR_SIZE;
+  if ((size_t)width * height > ((size_t)1 << 30) || (size_t)width * scale > ((size_t)1 << 24) || (size_t)height * scale > ((size_t)1 << 24))
+    return SBM_ERR_UNSUPPORTED;   // pixel coordinates stay exact in float, the pixel index in int
+  return SBM_OK;
+}
+
+static int occ_insert_run(sbm_occ_map* map, int n, const int16_t* d_disp, int W, int H, int scale, const sbm_stereo_model* model,
+                          const float* poses, int sync) {
+  sbm_handle* h = map->h;
+  StageClock& clk = h->occ.clock;   // stages: insert, fetch; each keeps its last call's time
+  const float fetch_ms = clk.ms[1];
+  HIPCHK(h, clk.start(h->profiling != 0));
+  clk.ms[1] = fetch_ms;
+  OccGeom g;
+  g.W = W;
+  g.H = H;
+  g.scale = scale;
+  g.range_max_sqrd = map->p.range_max * map->p.range_max;
+  g.factor = 1. / map->p.resolution;
+  g.mask = map->slots - 1;
+  g.max_probe = std::min(map->slots, kOccMaxProbe);
+  const size_t plane = (size_t)W * H;
+  HIPCHK(h, clk.mark(0, h->stream));
+  for (int c0 = 0; c0 < n; c0 += kOccChunk) {
+    const int m = std::min(kOccChunk, n - c0);
+    OccPoses ps;
+    memset(&ps, 0, sizeof(ps));
+    memcpy(ps.t, poses + (size_t)12 * c0, sizeof(float) * 12 * m);
+    hipLaunchKernelGGL(occ_insert_kernel, dim3((unsigned)((plane + 255) / 256), m), dim3(256), 0, h->stream, d_disp + plane * c0, g,
+                       *model, ps, map->keys.as<unsigned long long>(), map->hits.as<unsigned>(), map->ctr.as<OccCounters>());
+    HIPCHK(h, hipGetLastError());
+  }
+  HIPCHK(h, clk.mark(1, h->stream));
+  HIPCHK(h, clk.add(0, 0, 1));
+  if (!sync && !clk.on) return SBM_OK;
+  OccCounters c;
+  const int st = occ_read_counters(map, &c);
+  if (st != SBM_OK) return st;
+  return c.overflow ? SBM_ERR_OCC_FULL : SBM_OK;
+}
+
+// Sorted (key, hits) of the map into d_keys / d_hits (cap entries each; d_hits may be null: the counts then stay in scratch).
+static int occ_fetch_run(sbm_occ_map* map, unsigned long long* d_keys, unsigned* d_hits, size_t cap, size_t* count) {
+  sbm_handle* h = map->h;
+  StageClock& clk = h->occ.clock;
+  const float insert_ms = clk.ms[0];
+  HIPCHK(h, clk.start(h->profiling != 0));
+  clk.ms[0] = insert_ms;
+  OccCounters c;
+  int st = occ_read_counters(map, &c);
+  if (st != SBM_OK) return st;
+  const uint32_t n = c.size;
+  *count = n;
+  if (n > cap) return SBM_ERR_SIZE;
+  if (n) {
+    const uint32_t tiles = (n + kOccTile - 1) / kOccTile;
+    // second key array, second count array, and a first count array when the caller wants no counts
+    const size_t kb = ((size_t)n * 8 + 255) & ~(size_t)255, vb = ((size_t)n * 4 + 255) & ~(size_t)255;
+    HIPCHK(h, h->occ.sort.grow(kb + 2 * vb, h->stream));
+    HIPCHK(h, h->occ.hist.grow((size_t)256 * tiles * 4, h->stream));
+    unsigned long long* kk[2] = {d_keys, h->occ.sort.as<unsigned long long>()};
+    unsigned* vv[2] = {d_hits ? d_hits : (unsigned*)((char*)h->occ.sort.p + kb + vb), (unsigned*)((char*)h->occ.sort.p + kb)};
+    unsigned* hist = h->occ.hist.as<unsigned>();
+    HIPCHK(h, clk.mark(0, h->stream));
+    HIPCHK(h, hipMemsetAsync((char*)map->ctr.p + offsetof(OccCounters, cursor), 0, sizeof(unsigned), h->stream));
+    hipLaunchKernelGGL(occ_compact_kernel, dim3((map->slots + 255) / 256), dim3(256), 0, h->stream, map->keys.as<unsigned long long>(),
+                       map->hits.as<unsigned>(), map->slots, n, kk[0], vv[0], map->ctr.as<OccCounters>());
+    HIPCHK(h, hipGetLastError());
+    for (int pass = 0; pass < 6; pass++) {   // 48 key bits, 8 per pass: an even number of passes ends in the caller's arrays
+      const int a = pass & 1, b = a ^ 1;
+      hipLaunchKernelGGL(occ_hist_kernel, dim3(tiles), dim3(256), 0, h->stream, kk[a], n, 8 * pass, hist, tiles);
+      HIPCHK(h, hipGetLastError());
+      hipLaunchKernelGGL(occ_scan_kernel, dim3(1), dim3(256), 0, h->stream, hist, tiles);
+      HIPCHK(h, hipGetLastError());
+      hipLaunchKernelGGL(occ_scatter_kernel, dim3(tiles), dim3(64), 0, h->stream, kk[a], vv[a], n, 8 * pass, hist, tiles, kk[b], vv[b]);
+      HIPCHK(h, hipGetLastError());
+    }
+    HIPCHK(h, clk.mark(1, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    HIPCHK(h, clk.add(1, 0, 1));
+  }
+  return c.overflow ? SBM_ERR_OCC_FULL : SBM_OK;
+}
+
+// ---- the .bt stream ------------------------------------------------------------------------------------------------------
+// Morton code of a packed key: per bit, from the top, z y x -- a child index as computeChildIdx gives it
+static uint64_t occ_morton(uint64_t key) {
+  const uint64_t k0 = (key >> 32) & 0xFFFF, k1 = (key >> 16) & 0xFFFF, k2 = key & 0xFFFF;
+  uint64_t m = 0;
+  for (int b = 0; b < 16; b++) m |= ((k0 >> b & 1) | (k1 >> b & 1) << 1 | (k2 >> b & 1) << 2) << (3 * b);
+  return m;
+}
+
+// The inner node that covers codes [lo, hi) (sorted, distinct) with `level` key bits still undecided (16 at the root): its two
+// bytes, then its inner children depth first. A child whose range holds all 8^(level-1) codes below it is what prune() leaves
+// as one leaf. Returns the nodes written, this one included.
+static size_t occ_write_node(const uint64_t* lo, const uint64_t* hi, int level, std::vector<uint8_t>& body) {
+  const int shift = 3 * (level - 1);
+  const uint64_t full = (uint64_t)1 << shift;   // 8^(level-1)
+  const uint64_t* edge[9];
+  edge[0] = lo;
+  for (int c = 0; c < 8; c++) {
+    const uint64_t* e = edge[c];
+    while (e < hi && ((*e >> shift) & 7) == (uint64_t)c) e++;
+    edge[c + 1] = e;
+  }
+  uint8_t byte[2] = {0, 0};
+  size_t nodes = 1;
+  for (int c = 0; c < 8; c++) {
+    const uint64_t cnt = (uint64_t)(edge[c + 1] - edge[c]);
+    if (!cnt) continue;
+    byte[c / 4] |= (uint8_t)((cnt == full ? 2 : 3) << (2 * (c % 4)));   // bits (2c, 2c+1): 0,1 occupied leaf; 1,1 inner
+    if (cnt == full) nodes++;
+  }
+  body.push_back(byte[0]);
+  body.push_back(byte[1]);
+  for (int c = 0; c < 8; c++) {
+    const uint64_t cnt = (uint64_t)(edge[c + 1] - edge[c]);
+    if (cnt && cnt != full) nodes += occ_write_node(edge[c], edge[c + 1], level - 1, body);
+  }
+  return nodes;
+}
+
+}  // namespace sbm
+
+// ---- entry points --------------------------------------------------------------------------------------------------------
+using namespace sbm;
+
+extern "C" {
+
+void sbm_occ_params_default(sbm_occ_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->resolution = 0.1;
+  p->range_max = 5.0f;
+  p->tree_depth = 16;
+}
+
+int sbm_occ_params_validate(const sbm_occ_params* p) {
+  if (!p) return SBM_ERR_NULL;
+  if (!std::isfinite(p->resolution) || !(p->resolution > 0.) || !std::isfinite(1. / p->resolution)) return SBM_ERR_SIZE;
+  if (std::isnan(p->range_max) || p->range_max < 0.f) return SBM_ERR_SIZE;
+  if (p->tree_depth != 16) return SBM_ERR_UNSUPPORTED;
+  return SBM_OK;
+}
+
+int sbm_occ_create(sbm_handle* h, const sbm_occ_params* p, size_t capacity, sbm_occ_map** out) {
+  if (!h || !p || !out) return SBM_ERR_NULL;
+  *out = nullptr;
+  int st = sbm_occ_params_validate(p);
+  if (st != SBM_OK) return st;
+  if (capacity < 1) return SBM_ERR_SIZE;
+  if (capacity > kOccMaxCapacity) return SBM_ERR_UNSUPPORTED;
+  sbm_occ_map* map = new (std::nothrow) sbm_occ_map();
+  if (!map) return SBM_ERR_NOMEM;
+  memset(map, 0, sizeof(*map));
+  map->h = h;
+  map->p = *p;
+  map->capacity = capacity;
+  map->slots = 2;
+  while ((size_t)map->slots < 2 * capacity) map->slots <<= 1;
+  DeviceScope dscope(h->device);
+  hipError_t e = dscope.enter();
+  if (e == hipSuccess) e = map->keys.grow((size_t)map->slots * 8, h->stream);
+  if (e == hipSuccess) e = map->hits.grow((size_t)map->slots * 4, h->stream);
+  if (e == hipSuccess) e = map->ctr.grow(sizeof(OccCounters), h->stream);
+  st = SBM_OK;
+  if (e != hipSuccess) {
+    h->last_hip = (int)e;
+    st = e == hipErrorOutOfMemory ? SBM_ERR_NOMEM : SBM_ERR_HIP;
+  }
+  if (st == SBM_OK) st = occ_clear(map);
+  if (st != SBM_OK) {
+    release_all(*map);
+    delete map;
+    return st;
+  }
+  *out = map;
+  return SBM_OK;
+}
+
+void sbm_occ_destroy(sbm_occ_map* map) {
+  if (!map) return;
+  DeviceScope dscope(map->h->device);
+  dscope.enter();
+  hipStreamSynchronize(map->h->stream);
+  release_all(*map);
+  delete map;
+}
+
+int sbm_occ_reset(sbm_occ_map* map) {
+  if (!map) return SBM_ERR_NULL;
+  DeviceScope dscope(map->h->device);
+  HIPCHK(map->h, dscope.enter());
+  return occ_clear(map);
+}
+
+int sbm_occ_insert_device(sbm_occ_map* map, int n, const void* d_disp, int width, int height, int scale,
+                          const sbm_stereo_model* model, const float* poses, int sync) {
+  const int st = occ_check_insert(map, n, d_disp, width, height, scale, model, poses);
+  if (st != SBM_OK) return st;
+  if ((uintptr_t)d_disp & 1) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(map->h->device);
+  HIPCHK(map->h, dscope.enter());
+  return occ_insert_run(map, n, (const int16_t*)d_disp, width, height, scale, model, poses, sync);
+}
+
+int sbm_occ_insert(sbm_occ_map* map, int n, const int16_t* disp, int width, int height, int scale, const sbm_stereo_model* model,
+                   const float* poses) {
+  const int st = occ_check_insert(map, n, disp, width, height, scale, model, poses);
+  if (st != SBM_OK) return st;
+  sbm_handle* h = map->h;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  const size_t bytes = (size_t)n * width * height * sizeof(int16_t);
+  HIPCHK(h, h->occ.io.grow(bytes, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->occ.io.p, disp, bytes, hipMemcpyHostToDevice, h->stream));
+  return occ_insert_run(map, n, h->occ.io.as<int16_t>(), width, height, scale, model, poses, 1);
+}
+
+int sbm_occ_size(sbm_occ_map* map, size_t* size) {
+  if (!map || !size) return SBM_ERR_NULL;
+  DeviceScope dscope(map->h->device);
+  HIPCHK(map->h, dscope.enter());
+  OccCounters c;
+  const int st = occ_read_counters(map, &c);
+  if (st == SBM_OK) *size = c.size;
+  return st;
+}
+
+int sbm_occ_overflow(sbm_occ_map* map, uint64_t* overflow) {
+  if (!map || !overflow) return SBM_ERR_NULL;
+  DeviceScope dscope(map->h->device);
+  HIPCHK(map->h, dscope.enter());
+  OccCounters c;
+  const int st = occ_read_counters(map, &c);
+  if (st == SBM_OK) *overflow = c.overflow;
+  return st;
+}
+
+int sbm_occ_fetch_device(sbm_occ_map* map, void* d_keys, void* d_hits, size_t cap, size_t* count) {
+  if (!map || !count || (cap > 0 && !d_keys)) return SBM_ERR_NULL;
+  if (((uintptr_t)d_keys & 7) || ((uintptr_t)d_hits & 3)) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(map->h->device);
+  HIPCHK(map->h, dscope.enter());
+  return occ_fetch_run(map, (unsigned long long*)d_keys, (unsigned*)d_hits, cap, count);
+}
+
+int sbm_occ_fetch(sbm_occ_map* map, uint64_t* keys, uint32_t* hits, size_t cap, size_t* count) {
+  if (!map || !count || (cap > 0 && !keys)) return SBM_ERR_NULL;
+  sbm_handle* h = map->h;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  OccCounters c;
+  int st = occ_read_counters(map, &c);
+  if (st != SBM_OK) return st;
+  *count = c.size;
+  if (c.size > cap) return SBM_ERR_SIZE;
+  if (!c.size) return c.overflow ? SBM_ERR_OCC_FULL : SBM_OK;
+  const size_t kb = ((size_t)c.size * 8 + 255) & ~(size_t)255;
+  HIPCHK(h, h->occ.io.grow(kb + (size_t)c.size * 4, h->stream));
+  unsigned long long* d_k = h->occ.io.as<unsigned long long>();
+  unsigned* d_v = (unsigned*)((char*)h->occ.io.p + kb);
+  st = occ_fetch_run(map, d_k, d_v, c.size, count);
+  if (st != SBM_OK && st != SBM_ERR_OCC_FULL) return st;
+  HIPCHK(h, hipMemcpyAsync(keys, d_k, *count * 8, hipMemcpyDeviceToHost, h->stream));
+  if (hits) HIPCHK(h, hipMemcpyAsync(hits, d_v, *count * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return st;
+}
+
+int sbm_occ_write_binary(const uint64_t* keys, size_t n, double resolution, const char* path) {
+  if (!path || (n > 0 && !keys)) return SBM_ERR_NULL;
+  if (!std::isfinite(resolution) || !(resolution > 0.)) return SBM_ERR_SIZE;
+  std::vector<uint64_t> code;
+  std::vector<uint8_t> body;
+  size_t nodes = 0;
+  try {
+    code.reserve(n);
+    for (size_t i = 0; i < n; i++) {
+      if (keys[i] >> 48) return SBM_ERR_SIZE;
+      code.push_back(occ_morton(keys[i]));
+    }
+    std::sort(code.begin(), code.end());
+    code.erase(std::unique(code.begin(), code.end()), code.end());
+    if (!code.empty()) nodes = occ_write_node(code.data(), code.data() + code.size(), 16, body);
+  } catch (const std::bad_alloc&) {
+    return SBM_ERR_NOMEM;
+  }
+  FILE* f = fopen(path, "wb");
+  if (!f) return SBM_ERR_UNSUPPORTED;
+  // AbstractOccupancyOcTree::writeBinaryConst; `res` as operator<<(double) prints it (%g)
+  bool ok = fprintf(f,
+                    "# Octomap OcTree binary file\n# (feel free to add / change comments, but leave the first line as it is!)\n#\n"
+                    "id OcTree\nsize %zu\nres %g\ndata\n",
+                    nodes, resolution) > 0;
+  ok = ok && (body.empty() || fwrite(body.data(), 1, body.size(), f) == body.size());
+  ok = (fclose(f) == 0) && ok;
+  return ok ? SBM_OK : SBM_ERR_UNSUPPORTED;
+}
+
+}  // extern "C"
