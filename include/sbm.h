@@ -978,7 +978,9 @@ int sbm_keypoints3d_lk_device(sbm_handle* h, int n, const void* d_kpts, const vo
  *  SBM_ERR_OCC_FULL (with sync == 0 nothing is known yet: SBM_OK, and the next synchronous insert, sbm_occ_overflow or a fetch
  *  reports it). Nothing is dropped silently: stored hits + overflow = accepted points. Key set and hit counts do not depend on
  *  insertion order or on how planes are split across calls (as long as nothing overflowed). Up to the capacity no probe chain
- *  comes near the bound; a map filled past it keeps storing while slots are free, with longer chains.
+ *  comes near the bound; a map filled past it keeps storing, with longer chains, while a free slot lies within the probe bound
+ *  of the key's hash -- in a table of more than 1024 slots a key can overflow while slots further on are still free. A stored
+ *  key carries all its hits: its chain is full behind it, so a later point of that voxel finds it or nothing.
  *  Fetch compacts the occupied slots and sorts them ascending by packed key, counts as payload, with an LSD radix sort over the
  *  48 key bits (6 passes of 8 bits), all on the device.
  *  sbm_get_profile: while profiling is enabled (any mode) inserts and fetches synchronise and record "occ_insert" / "occ_fetch"
@@ -995,13 +997,17 @@ void sbm_occ_params_default(sbm_occ_params* p);
 /* SBM_ERR_NULL; SBM_ERR_SIZE for a resolution that is not finite and > 0 or a range_max that is NaN or negative;
  * SBM_ERR_UNSUPPORTED for tree_depth != 16; else SBM_OK. */
 int sbm_occ_params_validate(const sbm_occ_params* p);
-/* A map for up to `capacity` voxels (1 .. 2^30) on the handle's device, empty. */
+/* A map for up to `capacity` voxels (1 .. 2^30) on the handle's device, empty. The codes of sbm_occ_params_validate;
+ * SBM_ERR_SIZE for capacity 0, SBM_ERR_UNSUPPORTED above 2^30, both before anything is allocated; *out is NULL on failure. */
 int sbm_occ_create(sbm_handle* h, const sbm_occ_params* p, size_t capacity, sbm_occ_map** out);
 void sbm_occ_destroy(sbm_occ_map* map);
 /* Empties the table and the overflow counter without reallocating. Asynchronous on the handle's stream. */
 int sbm_occ_reset(sbm_occ_map* map);
 /* n planes of width x height int16 in DEVICE memory, densely packed; poses in HOST memory, n * 12 floats, read before the call
- * returns. Asynchronous on the handle's stream unless sync != 0, with the ordering rules of sbm_compute_device. */
+ * returns. Asynchronous on the handle's stream unless sync != 0, with the ordering rules of sbm_compute_device.
+ * Checked in this order, before anything is read or launched: SBM_ERR_NULL; SBM_ERR_BATCH for n <= 0; SBM_ERR_SIZE for a
+ * width, height or scale <= 0; SBM_ERR_UNSUPPORTED for a plane of more than 2^30 pixels, for width * scale or height * scale
+ * above 2^24, and for a d_disp that is not 2-byte aligned. The map is left as it was. */
 int sbm_occ_insert_device(sbm_occ_map* map, int n, const void* d_disp, int width, int height, int scale,
                           const sbm_stereo_model* model, const float* poses, int sync);
 /* The same from planes in HOST memory (n * height * width int16, dense). Synchronous. */
@@ -1012,7 +1018,9 @@ int sbm_occ_size(sbm_occ_map* map, size_t* size);
 int sbm_occ_overflow(sbm_occ_map* map, uint64_t* overflow);
 /* The stored voxels ascending by packed key into DEVICE memory: d_keys cap uint64 (8-byte aligned), d_hits cap uint32 (may be
  * NULL); *count = sbm_occ_size. SBM_ERR_SIZE, with *count set and nothing written, when cap < count; SBM_ERR_OCC_FULL, with the
- * outputs complete, when points overflowed. Synchronous; the map is left as it was. */
+ * outputs complete, when points overflowed. SBM_ERR_NULL for cap > 0 without d_keys, then SBM_ERR_UNSUPPORTED for a d_keys
+ * that is not 8-byte or a d_hits that is not 4-byte aligned, both before anything is launched. Without d_hits the counts are
+ * sorted along in scratch and dropped. Synchronous; the map is left as it was. */
 int sbm_occ_fetch_device(sbm_occ_map* map, void* d_keys, void* d_hits, size_t cap, size_t* count);
 /* The same into HOST memory. */
 int sbm_occ_fetch(sbm_occ_map* map, uint64_t* keys, uint32_t* hits, size_t cap, size_t* count);

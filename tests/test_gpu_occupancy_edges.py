@@ -1,0 +1,258 @@
+"""The occupancy map as a DATA STRUCTURE (u96-slam_amd/csrc/sbm_occupancy.hip): the set, its counts, the radix sort and the
+map's lifetime, against a closed form that needs no restatement (tests/occupancy_cases: under a zero rotation block a 1 x 1
+plane puts exactly the key of its pose's translation into the map), and the leader reduction on planes with a built
+per-wavefront key pattern against tests/occupancy_ref. tests/test_occupancy_restatement.py proves every expectation used here
+on the CPU. Keys, hits and size are compared for exact equality."""
+import ctypes
+import pathlib
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT / "tests"))
+import occupancy_cases as cases  # noqa: E402
+import occupancy_ref as occ  # noqa: E402
+from gpu_support import bm, dev  # noqa: E402,F401
+
+pytestmark = pytest.mark.gpu
+
+OK, ERR_NULL, ERR_SIZE, ERR_UNSUPPORTED, ERR_BATCH = 0, -1, -2, -23, -24      # include/sbm.h
+
+
+@pytest.fixture(scope="module")
+def model(pkg):
+    g = pkg.StereoModel()
+    m = occ.model()
+    ctypes.memmove(ctypes.byref(g), ctypes.byref(m), ctypes.sizeof(g))
+    return g
+
+
+def up(a):
+    """The planes on the device; a copy goes up, the shared cases are read-only."""
+    return dev(np.array(a, np.int16))
+
+
+def insert_status(pkg, omap, planes, model, poses):
+    """The status an insert of device planes reports: 0 or the code of the error it raises."""
+    try:
+        omap.insert(up(planes), model, poses, 1)
+    except pkg.StereoBMError as e:
+        return e.code
+    return OK
+
+
+def fetch_three_ways(pkg, omap):
+    """keys() / keys_device() / sbm_occ_fetch_device without a count array -> the three key arrays, the two count arrays."""
+    import torch
+
+    k_host, h_host = omap.keys(allow_overflow=True)
+    k_dev, h_dev = omap.keys_device(allow_overflow=True)
+    n = omap.size()
+    k_only = torch.full((max(n, 1),), -1, dtype=torch.int64, device="cuda:0")
+    got = ctypes.c_size_t()
+    torch.cuda.synchronize()
+    st = pkg.load_library().sbm_occ_fetch_device(omap._m, k_only.data_ptr(), None, n, ctypes.byref(got))
+    assert st in (OK, pkg.ERR_OCC_FULL) and got.value == n
+    keys = [k_host, k_dev.cpu().numpy().view(np.uint64), k_only[:n].cpu().numpy().view(np.uint64)]
+    return keys, [h_host, h_dev.cpu().numpy().view(np.uint32)]
+
+
+def assert_map_is(pkg, omap, want_keys, want_hits, what):
+    assert omap.size() == len(want_keys), (what, "size", omap.size(), len(want_keys))
+    assert omap.overflow() == 0, what
+    keys, hits = fetch_three_ways(pkg, omap)
+    for i, k in enumerate(keys):
+        assert np.array_equal(k, want_keys), (what, "keys", i)
+    for i, h in enumerate(hits):
+        assert np.array_equal(h, want_hits), (what, "hits", i)
+
+
+# ---- 1. sort shapes and digits -------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n", cases.SORT_SHAPES + (cases.MANY_TILES,))
+def test_sort_shapes_over_the_whole_key_range(pkg, bm, model, n):
+    """Exactly n distinct keys over all 48 bits, counts 1 2 3 1 2 3 along the sorted order. The 5000-key case holds key 0 and
+    0xFFFF_FFFF_FFFF; the latter is a key like any other, NOT the empty word (all 64 ones)."""
+    planes, poses, keys, hits = cases.lattice(n)
+    omap = pkg.OccupancyMap(bm, max(2 * n, 64) if n != cases.MANY_TILES else 1 << 17)
+    assert insert_status(pkg, omap, planes, model, poses) == OK
+    assert_map_is(pkg, omap, keys, hits, f"{n} keys")
+    if n == cases.WITH_ENDS:
+        got = omap.keys()[0]
+        assert got[0] == 0 and got[-1] == cases.KEY_MAX
+    omap.close()
+
+
+# ---- 2. low-entropy passes -----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("byte", range(6))
+def test_keys_that_differ_in_one_byte(pkg, bm, model, byte):
+    """300 planes over the 256 keys that differ in this byte only: five passes see one digit and must keep the order."""
+    planes, poses, keys, hits = cases.one_byte_case(byte)
+    omap = pkg.OccupancyMap(bm, 1024)
+    assert insert_status(pkg, omap, planes, model, poses) == OK
+    assert_map_is(pkg, omap, keys, hits, f"byte {byte}")
+    omap.close()
+
+
+# ---- 3. leader reduction -------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name", cases.PATTERNS)
+def test_leader_reduction_patterns(pkg, bm, model, name):
+    plane, pose = cases.pattern(name)
+    want_k, want_h = occ.insert(plane, 1, occ.model(), pose)
+    px = occ.pixel_keys(plane, 1, occ.model(), pose).reshape(-1)
+    assert int(want_h.sum()) == int((px != occ.EMPTY).sum())
+    if name == "abab":
+        assert len(want_k) == 2 and list(want_h) == [32, 32]
+    if name.startswith("tail"):
+        assert want_h[want_k == px[0]] == 2
+    omap = pkg.OccupancyMap(bm, 1024)
+    assert insert_status(pkg, omap, plane[None], model, pose) == OK
+    assert_map_is(pkg, omap, want_k, want_h, name)
+    omap.close()
+
+
+# ---- 4. contention -------------------------------------------------------------------------------------------------------
+
+def contention_planes():
+    t = np.array([[1.25 * i - 4, 0.35 * i, -0.45 * i + 1] for i in range(8)], np.float32)
+    return np.full((8, 128, 128), cases.VALID, np.int16), t
+
+
+def test_2048_wavefronts_on_eight_keys_and_on_one(pkg, bm, model):
+    planes, t = contention_planes()
+    d_planes = dev(planes)
+    keys8, hits8 = cases.closed_form(t)
+    assert len(keys8) == 8 and (hits8 == 1).all()
+    omap = pkg.OccupancyMap(bm, 4096)
+    omap.insert(d_planes, model, cases.zero_rotation_poses(t), 1)
+    assert_map_is(pkg, omap, keys8, np.full(8, 16384, np.uint32), "8 keys")
+    omap.reset()
+    omap.insert(d_planes, model, cases.zero_rotation_poses(np.tile(t[3], (8, 1))), 1)
+    assert_map_is(pkg, omap, cases.closed_form(t[3])[0], np.array([131072], np.uint32), "1 key")
+    omap.close()
+    # both into 8 slots: every slot is taken, so the wavefronts that lose a compare-and-swap settle in the next slot
+    omap = pkg.OccupancyMap(bm, 4)
+    omap.insert(d_planes, model, cases.zero_rotation_poses(t), 1)
+    assert_map_is(pkg, omap, keys8, np.full(8, 16384, np.uint32), "8 keys in 8 slots")
+    omap.insert(d_planes, model, cases.zero_rotation_poses(np.tile(t[3], (8, 1))), 1)
+    both = np.full(8, 16384, np.uint32)
+    both[keys8 == cases.closed_form(t[3])[0][0]] += 131072
+    assert_map_is(pkg, omap, keys8, both, "8 keys and 1 key in 8 slots")
+    omap.close()
+
+
+# ---- 5. past the capacity, in a table larger than the probe bound ------------------------------------------------------------
+
+@pytest.mark.parametrize("n", cases.PAST_CAPACITY)
+def test_past_the_capacity_nothing_is_lost(pkg, bm, model, n):
+    """Capacity 1024 is 2048 slots and a bound of 1024 probes. Whether 1500 or 2000 keys overflow depends on the hash and is
+    not asserted; 2300 keys cannot fit. A stored key's chain stays full behind it, so a later leader of the same key either
+    finds it or overflows entirely: a stored key carries ALL its hits."""
+    planes, poses, w_keys, w_hits = cases.lattice(n)
+    omap = pkg.OccupancyMap(bm, 1024)
+    status = insert_status(pkg, omap, planes, model, poses)
+    overflow, size = omap.overflow(), omap.size()
+    (s_keys, *other_keys), (s_hits, other_hits) = fetch_three_ways(pkg, omap)
+    assert all(np.array_equal(k, s_keys) for k in other_keys) and np.array_equal(other_hits, s_hits)
+    print(f"{n} keys into 2048 slots: stored {size}, overflow {overflow}, status {status}")
+    assert np.all(np.diff(s_keys.astype(np.int64)) > 0)
+    assert size == len(s_keys) <= 2048
+    stored = np.isin(w_keys, s_keys)
+    assert stored.sum() == len(s_keys)                                  # S is a subset of W
+    assert np.array_equal(s_hits, w_hits[stored])
+    assert overflow == int(w_hits[~stored].sum())
+    assert status == (pkg.ERR_OCC_FULL if overflow else OK)
+    if overflow:
+        with pytest.raises(pkg.StereoBMError) as e:
+            omap.keys()
+        assert e.value.code == pkg.ERR_OCC_FULL
+    else:
+        k, h = omap.keys()
+        assert np.array_equal(k, w_keys) and np.array_equal(h, w_hits)
+    if n > 2048:
+        assert overflow > 0
+    omap.close()
+
+
+# ---- 6. map lifetime -----------------------------------------------------------------------------------------------------
+
+def test_fetches_leave_the_map_alone_and_scratch_is_reused(pkg, bm, model):
+    planes, poses, keys, hits = cases.lattice(1025)
+    half = len(planes) // 2
+    omap = pkg.OccupancyMap(bm, 4096)
+    omap.insert(up(planes[:half]), model, poses[:half], 1)
+    assert_map_is(pkg, omap, *cases.closed_form(poses[:half, [3, 7, 11]]), "first half")
+    omap.insert(up(planes[half:]), model, poses[half:], 1)
+    assert_map_is(pkg, omap, keys, hits, "both halves: the cursor starts at 0 again and the fetch changed nothing")
+    assert_map_is(pkg, omap, keys, hits, "a second fetch in a row")
+    # a large fetch grows the scratch; a small one and the large one again reuse it. Two maps live on one engine.
+    big, small = pkg.OccupancyMap(bm, 8192), pkg.OccupancyMap(bm, 64)
+    planes5, poses5, keys5, hits5 = cases.lattice(5000)
+    planes3, poses3, keys3, hits3 = cases.lattice(3)
+    big.insert(up(planes5), model, poses5, 1)
+    small.insert(up(planes3), model, poses3, 1)
+    assert_map_is(pkg, big, keys5, hits5, "5000 keys")
+    assert_map_is(pkg, small, keys3, hits3, "3 keys after 5000")
+    assert_map_is(pkg, big, keys5, hits5, "5000 keys again")
+    assert_map_is(pkg, omap, keys, hits, "the first map, untouched by the other two")
+    assert not np.isin(keys3, keys5).any() and not np.isin(keys, keys5).any()
+    for m in (omap, big, small):
+        m.close()
+
+
+# ---- 7. status codes with a live map -----------------------------------------------------------------------------------------
+
+def test_status_codes_leave_a_live_map_alone(pkg, bm, model):
+    """Every rejected call returns the documented code before it touches a buffer or launches anything: the buffers passed are
+    far smaller than the sizes named."""
+    import torch
+
+    L = pkg.load_library()
+    planes, poses, keys, hits = cases.lattice(65)
+    omap = pkg.OccupancyMap(bm, 256)
+    omap.insert(up(planes), model, poses, 1)
+    d = dev(np.full(8, cases.VALID, np.int16))
+    host = np.full(8, cases.VALID, np.int16)
+    pose = np.ascontiguousarray(poses[:1])
+    m = ctypes.byref(model)
+
+    def ins_dev(n, ptr, w, h, scale):
+        return L.sbm_occ_insert_device(omap._m, n, ptr, w, h, scale, m, pose.ctypes.data, 1)
+
+    def ins_host(n, w, h, scale):
+        return L.sbm_occ_insert(omap._m, n, host.ctypes.data, w, h, scale, m, pose.ctypes.data)
+
+    for n in (0, -1):
+        assert ins_dev(n, d.data_ptr(), 1, 1, 1) == ERR_BATCH and ins_host(n, 1, 1, 1) == ERR_BATCH
+    for w, h, scale in ((0, 1, 1), (1, 0, 1), (1, 1, 0)):
+        assert ins_dev(1, d.data_ptr(), w, h, scale) == ERR_SIZE and ins_host(1, w, h, scale) == ERR_SIZE
+    limits = ((1 << 16, (1 << 14) + 1, 1),        # width * height > 2^30
+              (4097, 1, 4096),                    # width * scale > 2^24
+              (1, 4097, 4096))                    # height * scale > 2^24
+    for w, h, scale in limits:
+        assert ins_dev(1, d.data_ptr(), w, h, scale) == ERR_UNSUPPORTED and ins_host(1, w, h, scale) == ERR_UNSUPPORTED
+    assert ins_dev(1, d.data_ptr() + 1, 1, 1, 1) == ERR_UNSUPPORTED           # an odd plane pointer
+
+    n = omap.size()
+    k = torch.zeros((n + 1,), dtype=torch.int64, device="cuda:0")
+    v = torch.zeros((n + 1,), dtype=torch.int32, device="cuda:0")
+    got = ctypes.c_size_t()
+    torch.cuda.synchronize()
+    assert L.sbm_occ_fetch_device(omap._m, k.data_ptr() + 4, v.data_ptr(), n, ctypes.byref(got)) == ERR_UNSUPPORTED
+    assert L.sbm_occ_fetch_device(omap._m, k.data_ptr(), v.data_ptr() + 2, n, ctypes.byref(got)) == ERR_UNSUPPORTED
+    assert L.sbm_occ_fetch_device(omap._m, None, v.data_ptr(), n, ctypes.byref(got)) == ERR_NULL
+    assert L.sbm_occ_fetch(omap._m, None, None, n, ctypes.byref(got)) == ERR_NULL
+    assert not k.any() and not v.any()
+
+    p = pkg.occ_params()
+    out = ctypes.c_void_p(1)
+    assert L.sbm_occ_create(bm._h, ctypes.byref(p), 0, ctypes.byref(out)) == ERR_SIZE and not out.value
+    out = ctypes.c_void_p(1)
+    assert L.sbm_occ_create(bm._h, ctypes.byref(p), (1 << 30) + 1, ctypes.byref(out)) == ERR_UNSUPPORTED and not out.value
+
+    assert_map_is(pkg, omap, keys, hits, "after the rejected calls")
+    omap.close()

@@ -110,3 +110,87 @@ def test_squared_range_quirk():
     p = occ.params()
     assert occ.point([24, 0, 0], [0, 0, 0], p)[1] and not occ.point([25.1, 0, 0], [0, 0, 0], p)[1]
     assert occ.point([3, 0, 0], [0, 0, 0], occ.params(range_max=1.5))[1] is False   # 3 > 2.25
+
+
+# ---- the inputs of tests/test_gpu_occupancy_edges.py: their closed-form expectation against the restatement -----------------
+import occupancy_cases as cases  # noqa: E402
+
+
+def test_closed_form_at_the_range_edges():
+    """-3276.8f lies below -3276.8 and is rejected; +-3276.75f are the first and the last voxel; 3276.8f is out."""
+    t = np.zeros((5, 3), np.float32)
+    t[:, 0] = [-3276.8, -3276.75, 3276.75, 3276.8, 0.0]
+    planes, poses = cases.unit_planes(5), cases.zero_rotation_poses(t)
+    px = occ.pixel_keys(planes, 1, occ.model(), poses).reshape(-1)
+    assert list(px != occ.EMPTY) == [False, True, True, False, True]
+    assert list(cases.unpack(px[[1, 2, 4]])[:, 0]) == [0, 65535, 32768]
+    keys, hits = cases.closed_form(t)
+    want = occ.distinct(px)
+    assert np.array_equal(keys, want[0]) and np.array_equal(hits, want[1]) and len(keys) == 3
+
+
+@pytest.mark.parametrize("n", cases.LATTICE_SIZES)
+def test_lattice_case_is_what_it_claims(n):
+    planes, poses, keys, hits = cases.lattice(n)
+    assert len(keys) == n and np.all(np.diff(keys.astype(np.int64)) > 0) and int(keys.max()) <= cases.KEY_MAX
+    assert np.array_equal(hits, 1 + np.arange(n) % 3) and planes.shape == (int(hits.sum()), 1, 1)
+    for got in (occ.insert(planes, 1, occ.model(), poses), cases.closed_form(poses[:, [3, 7, 11]])):
+        assert np.array_equal(got[0], keys) and np.array_equal(got[1], hits)
+    if n >= 5000:
+        for byte in range(6):
+            assert len(np.unique((keys >> np.uint64(8 * byte)) & np.uint64(255))) >= 200, byte
+    if n == cases.WITH_ENDS:
+        assert keys[0] == 0 and keys[-1] == cases.KEY_MAX and keys[-1] != occ.EMPTY
+    # the planes do not arrive in key order
+    first = cases.closed_form(poses[:64, [3, 7, 11]])[0]
+    assert n < 64 or not np.array_equal(first, keys[:len(first)])
+
+
+@pytest.mark.parametrize("byte", range(6))
+def test_one_byte_case_is_what_it_claims(byte):
+    planes, poses, keys, hits = cases.one_byte_case(byte)
+    assert len(planes) == 300 and len(keys) == 256 and sorted(np.unique(hits)) == [1, 2]
+    got = occ.insert(planes, 1, occ.model(), poses)
+    assert np.array_equal(got[0], keys) and np.array_equal(got[1], hits)
+    for b in range(6):
+        digits = np.unique((keys >> np.uint64(8 * b)) & np.uint64(255))
+        assert len(digits) == (256 if b == byte else 1)
+
+
+def pattern_keys(name):
+    plane, pose = cases.pattern(name)
+    return occ.pixel_keys(plane, 1, occ.model(), pose).reshape(-1)
+
+
+def test_pattern_abab():
+    k = pattern_keys("abab")
+    assert len(k) == 64 and k[0] != k[1] and occ.EMPTY not in (k[0], k[1])
+    assert (k[0::2] == k[0]).all() and (k[1::2] == k[1]).all()
+
+
+def test_pattern_runs():
+    k = pattern_keys("runs")
+    assert len(k) == 128
+    groups = [k[g:g + 6] for g in range(0, 126, 6)]
+    for g in groups:                                           # K K - K K -
+        assert g[2] == occ.EMPTY and g[5] == occ.EMPTY and g[0] != occ.EMPTY and (g[[0, 1, 3, 4]] == g[0]).all()
+    assert all(a[0] != b[0] for a, b in zip(groups, groups[1:]))
+    assert (k[60:62] == k[63]).all() and k[63] == k[64] and k[62] == occ.EMPTY     # a run straddles the two wavefronts
+    first = [g[0] for g in groups[:10]]
+    assert len(set(first)) < len(first)                        # and a key comes back later in the same wavefront
+
+
+@pytest.mark.parametrize("name,w", [("tail65", 65), ("tail129", 129)])
+def test_pattern_tail(name, w):
+    k = pattern_keys(name)
+    assert len(k) == w and w % 64 == 1 and k[-1] == k[0] != occ.EMPTY
+    assert (k[1:-1] != k[0]).all() and (k != occ.EMPTY).all() and len(np.unique(k[:64])) > 8
+
+
+def test_pattern_blocks():
+    plane, _ = cases.pattern("blocks")
+    k = pattern_keys("blocks")
+    assert plane.shape == (3, 100) and (k != occ.EMPTY).all()
+    wave, block = np.arange(300) // 64, np.arange(300) // 256
+    spans = [(set(wave[(k == v) & (block == 0)]), set(block[k == v])) for v in np.unique(k)]
+    assert any(len(w0) >= 2 and b == {0, 1} for w0, b in spans)
