@@ -693,6 +693,13 @@ int sbm_match_guess(sbm_handle* h, const float* xyz_from, const float* kpts_to, 
  * product, quaternion renormalisation and 4 x 4 inverse of Transform. RANSAC scores each hypothesis with R, t as EPnP
  * produced them (OpenCV round-trips through rvec; that moves the pose by ulps). With has_local == 0 (or no model) the
  * localTransform product is skipped.
+ * Of these, what is mathematics is now held to an independent statement (tests/pnp_independent.py: expm, mpmath derivatives,
+ * numpy.linalg, scipy's LM; DESIGN.md section 12 lists blocks, inputs and bounds): the SVD and both solvers, Rodrigues with
+ * dR/dr and its inverse, the LM residual, Jacobian, accumulators and damped step, the refined pose as a minimum, the projection
+ * gate, the float variance, the Transform product / inverse and the covariance terms and medians. What stays a reading, seen
+ * and kept: the SVD's cut-off, the lambda schedule, z == 0 left undivided, no rvec round trip, and Rodrigues' inverse within
+ * 1e-5 of pi, which answers with the rule for pi itself (x >= 0, the signs of y and z from R01 and R02): the vector is then off
+ * by up to 2 (pi - angle) as a rotation, and is -r where the axis has x < 0 (2.2e-7 measured at pi - 1e-7).
  * Parity contract (GPU vs the sequential C restatement, oracle/pnp_ref): bit for bit -- N, every subset, every hypothesis' R, t
  * and count, the best iteration, the final niters and the RANSAC inliers. Refined pose (rvec, tvec, R): 1e-9 relative (the
  * transcendental functions of Rodrigues differ between host and device libraries by ulps); transform and covariance scales:

@@ -38,6 +38,30 @@ void pnp_ref_rodrigues(const double* rv, double* R) {
 
 void pnp_ref_rodrigues_inv(const double* R, double* rv) { pnp_rodrigues_inv(R, rv); }
 
+/* The header's blocks one by one, for tests that hold them to an independent statement (tests/pnp_independent.py). The
+ * matrices of the SVD are the header's own: rows of stride PNP_LD. */
+int pnp_ref_ld(void) { return PNP_LD; }
+void pnp_ref_jacobi_svd(double* At, double* W, double* Vt, int m, int n) { pnp_jacobi_svd(At, W, Vt, m, n); }
+void pnp_ref_svd_solve(const double* A, int m, int n, const double* b, double* x) { pnp_svd_solve(A, m, n, b, x); }
+void pnp_ref_qr_solve(double* A, double* b, double* X) { pnp_qr_solve(A, b, X); }
+void pnp_ref_rodrigues_d(const double* rv, double* R, double* dRdr) { pnp_rodrigues(rv, R, dRdr); }
+void pnp_ref_lm_points(const double* R, const double* dRdr, const double* t, const float* p, const float* m, int n, const double* K,
+                       int with_j, double* acc) {
+  for (int i = 0; i < n; i++) pnp_lm_point(R, dRdr, t, p + 3 * i, m + 2 * i, K, with_j, acc);
+}
+void pnp_ref_lm_step(const double* acc, double lambda, const double* prev, double* param) { pnp_lm_step(acc, lambda, prev, param); }
+int pnp_ref_lm_converged(const double* param, const double* prev) { return pnp_lm_converged(param, prev); }
+float pnp_ref_reproj_err(const double* R, const double* t, const float* p, const float* m, const double* K) {
+  return pnp_reproj_err(R, t, p, m, K);
+}
+float pnp_ref_variance(const float* v, int n) { return pnp_variance(v, n); }
+void pnp_ref_tf_mul(const float* A, const float* B, float* C) { pnp_tf_mul(A, B, C); }
+void pnp_ref_tf_inverse(const float* A, float* C) { pnp_tf_inverse(A, C); }
+void pnp_ref_transform(const double* R, const double* t, const float* local, float* out) { pnp_transform(R, t, local, out); }
+void pnp_ref_cov_terms(const float* obj, const float* to, const float* T, float* dist, float* ang) {
+  pnp_cov_terms(obj, to, T, dist, ang);
+}
+
 /* The RANSAC loop over given counts (what findInliers would return per iteration): best iteration, final niters, best count. */
 void pnp_ref_replay(const int* counts, int iterations, int n, double confidence, int* best, int* niters_out, int* maxgood) {
   int niters = iterations > 1 ? iterations : 1, good = 0, b = -1;

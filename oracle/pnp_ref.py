@@ -8,6 +8,10 @@ transcription of the reference's loops that the C file is held to. TEST INFRASTR
     refine_walk(ransac, sets, rounds, min_inliers) / refine_walk_np(...)     -> (final list, solves, exit)
     update_num_iters(p, ep, mp, max_iters)                                   -> RANSACUpdateNumIters
     epnp6(pw, uv, K) -> (R (3, 3), t (3,)); rodrigues(rvec) -> R; rodrigues_inv(R) -> rvec
+    The header's blocks one by one (for tests/pnp_independent.py's comparisons): jacobi_svd(A) -> (U, W, Vt); svd_solve(A, b);
+    qr_solve(A, b); rodrigues_d(rvec) -> (R, dRdr (3, 3, 3)); lm_points(R, dRdr, t, p, m, K, with_j) -> 28 accumulators;
+    lm_step(acc, lam, prev); lm_converged(param, prev); reproj_err(R, t, p, m, K); variance(v); tf_mul(A, B); tf_inverse(A);
+    transform(R, t, local); cov_terms(obj, to, T) -> (dist, angle)
 
 The *_np functions transcribe CvSolvePnP.cpp (RNG::uniform, getSubset, RANSACPointSetRegistrator::run) and
 MotionEstimation.cpp (solvePnPRansac's refine loop with its two std::swap calls) line by line in Python.
@@ -49,6 +53,15 @@ def lib():
         L.pnp_ref_refine_walk.argtypes = [vp, ci, vp, vp, ci, ci, ci, vp, vp, vp]
         L.pnp_ref_estimate.argtypes = [vp, ci, vp, vp, ci, vp, ci, vp, vp, ctypes.POINTER(PnpParams), vp, vp, vp, vp, vp, vp, vp, vp,
                                        vp]
+        cf = ctypes.c_float
+        for name, args, res in (("jacobi_svd", [vp, vp, vp, ci, ci], None), ("svd_solve", [vp, ci, ci, vp, vp], None),
+                                ("qr_solve", [vp, vp, vp], None), ("rodrigues_d", [vp, vp, vp], None),
+                                ("lm_points", [vp, vp, vp, vp, vp, ci, vp, ci, vp], None), ("lm_step", [vp, cd, vp, vp], None),
+                                ("lm_converged", [vp, vp], ci), ("reproj_err", [vp, vp, vp, vp, vp], cf),
+                                ("variance", [vp, ci], cf), ("tf_mul", [vp, vp, vp], None), ("tf_inverse", [vp, vp], None),
+                                ("transform", [vp, vp, vp, vp], None), ("cov_terms", [vp, vp, vp, vp, vp], None), ("ld", [], ci)):
+            f = getattr(L, "pnp_ref_" + name)
+            f.argtypes, f.restype = args, res
         _LIB = L
     return _LIB
 
@@ -85,6 +98,97 @@ def rodrigues_inv(R):
     R, rv = _a(R, np.float64).reshape(9), np.zeros(3)
     lib().pnp_ref_rodrigues_inv(R.ctypes.data, rv.ctypes.data)
     return rv
+
+
+def jacobi_svd(A):
+    """pnp_jacobi_svd of A (m x n, m >= n) -> (U (m, n), W (n,), Vt (n, n)): the header takes A's columns as rows of stride LD."""
+    A = _a(A, np.float64)
+    m, n = A.shape
+    ld = lib().pnp_ref_ld()
+    At, Vt, W = np.zeros((ld, ld)), np.zeros((ld, ld)), np.zeros(ld)
+    At[:n, :m] = A.T
+    lib().pnp_ref_jacobi_svd(At.ctypes.data, W.ctypes.data, Vt.ctypes.data, m, n)
+    return At[:n, :m].T.copy(), W[:n].copy(), Vt[:n, :n].copy()
+
+
+def svd_solve(A, b):
+    A, b = _a(A, np.float64), _a(b, np.float64)
+    x = np.zeros(A.shape[1])
+    lib().pnp_ref_svd_solve(A.ctypes.data, A.shape[0], A.shape[1], b.ctypes.data, x.ctypes.data)
+    return x
+
+
+def qr_solve(A, b, x0=None):
+    """epnp::qr_solve on a 6 x 4 system (copies; the header overwrites A and b). x0: what X holds before the call."""
+    A, b = _a(A, np.float64).reshape(6, 4).copy(), _a(b, np.float64).reshape(6).copy()
+    x = np.zeros(4) if x0 is None else _a(x0, np.float64).copy()
+    lib().pnp_ref_qr_solve(A.ctypes.data, b.ctypes.data, x.ctypes.data)
+    return x
+
+
+def rodrigues_d(rv):
+    """(R (3, 3), dRdr (3, 3, 3): dRdr[j] = dR / dr_j)."""
+    rv, R, d = _a(rv, np.float64), np.zeros(9), np.zeros(27)
+    lib().pnp_ref_rodrigues_d(rv.ctypes.data, R.ctypes.data, d.ctypes.data)
+    return R.reshape(3, 3), d.reshape(3, 3, 3)
+
+
+def lm_points(R, dRdr, t, p, m, K, with_j=1):
+    """The 28 accumulators of pnp_lm_point over the points p (n, 3) float32 and observations m (n, 2) float32, in order."""
+    R, d, t, Kd = _a(R, np.float64).reshape(9), _a(dRdr, np.float64).reshape(27), _a(t, np.float64), _a(K, np.float64)
+    p, m = _a(p, np.float32).reshape(-1, 3), _a(m, np.float32).reshape(-1, 2)
+    acc = np.zeros(28)
+    lib().pnp_ref_lm_points(R.ctypes.data, d.ctypes.data, t.ctypes.data, p.ctypes.data, m.ctypes.data, p.shape[0], Kd.ctypes.data,
+                            int(with_j), acc.ctypes.data)
+    return acc
+
+
+def lm_step(acc, lam, prev):
+    acc, prev, out = _a(acc, np.float64), _a(prev, np.float64), np.zeros(6)
+    lib().pnp_ref_lm_step(acc.ctypes.data, float(lam), prev.ctypes.data, out.ctypes.data)
+    return out
+
+
+def lm_converged(param, prev):
+    param, prev = _a(param, np.float64), _a(prev, np.float64)
+    return bool(lib().pnp_ref_lm_converged(param.ctypes.data, prev.ctypes.data))
+
+
+def reproj_err(R, t, p, m, K):
+    R, t, Kd = _a(R, np.float64).reshape(9), _a(t, np.float64), _a(K, np.float64)
+    p, m = _a(p, np.float32), _a(m, np.float32)
+    return np.float32(lib().pnp_ref_reproj_err(R.ctypes.data, t.ctypes.data, p.ctypes.data, m.ctypes.data, Kd.ctypes.data))
+
+
+def variance(v):
+    v = _a(v, np.float32)
+    return np.float32(lib().pnp_ref_variance(v.ctypes.data, v.size))
+
+
+def tf_mul(A, B):
+    A, B, C = _a(A, np.float32).reshape(12), _a(B, np.float32).reshape(12), np.zeros(12, np.float32)
+    lib().pnp_ref_tf_mul(A.ctypes.data, B.ctypes.data, C.ctypes.data)
+    return C.reshape(3, 4)
+
+
+def tf_inverse(A):
+    A, C = _a(A, np.float32).reshape(12), np.zeros(12, np.float32)
+    lib().pnp_ref_tf_inverse(A.ctypes.data, C.ctypes.data)
+    return C.reshape(3, 4)
+
+
+def transform(R, t, local=None):
+    R, t, out = _a(R, np.float64).reshape(9), _a(t, np.float64), np.zeros(12, np.float32)
+    lo = None if local is None else _a(local, np.float32).reshape(12)
+    lib().pnp_ref_transform(R.ctypes.data, t.ctypes.data, None if lo is None else lo.ctypes.data, out.ctypes.data)
+    return out.reshape(3, 4)
+
+
+def cov_terms(obj, to, T):
+    obj, to, T = _a(obj, np.float32), _a(to, np.float32), _a(T, np.float32).reshape(12)
+    out = np.zeros(2, np.float32)
+    lib().pnp_ref_cov_terms(obj.ctypes.data, to.ctypes.data, T.ctypes.data, out.ctypes.data, out.ctypes.data + 4)
+    return out[0], out[1]
 
 
 def replay(counts, n, confidence=0.99):
