@@ -852,7 +852,7 @@ int sbm_sgbm_compute_device(sbm_handle* h, const sbm_sgbm_params* p, int n, cons
  * pyramidal LK with the y update forced to 0) -- window 15 x 3, 5 pyramid levels, 30 iterations, eps 0.01,
  * OPTFLOW_LK_GET_MIN_EIGENVALS, threshold 1e-4 -- and gates the result on 0.5 < d <= 128; generateKeypoints3DStereo then takes
  * disparity = left.x - right.x under the status mask (Stereo.cpp:85-87). Each step below is marked REF (pinned by the reference's
- * own source) or RECALLED (OpenCV, not part of the reference tree, pinned by nothing here). The engine, tests/lk_stereo_ref
+ * own source) or RECALLED (OpenCV, not part of the reference tree, pinned by nothing here). The engine, oracle/lk_stereo_ref
  * (sequential C, and a numpy transcription of the RECALLED half) and tests/golden/pin_kit_lk.npz implement exactly this text.
  * All arithmetic is IEEE binary32 / binary64 WITHOUT contraction: an aarch64 build of the reference may fuse some of the
  * multiply-adds below (A11 * A22 - A12 * A12, the radicand, A12 * b2 - A22 * b1); the uncontracted reading is the contract, and
@@ -954,7 +954,7 @@ int sbm_keypoints3d_lk_device(sbm_handle* h, int n, const void* d_kpts, const vo
  * (coordToKeyChecked) and calls tree.updateNode(key, true) -- one octree descent per point -- and at the end writes the tree with
  * writeBinary("slam.bt"). Every update is a hit, so after writeBinary's toMaxLikelihood() + prune() the file depends only on the
  * SET of distinct voxel keys. Here the per-pixel work and a concurrent set insert run on the device, only the distinct voxels
- * cross PCIe, and the host writes the .bt stream from them. tests/occupancy_ref (sequential C) implements exactly this text, and
+ * cross PCIe, and the host writes the .bt stream from them. oracle/occupancy_ref (sequential C) implements exactly this text, and
  * tests/golden/occupancy_octomap.npz holds what the reference's own octomap (vendored under src/slam/src/octomap) answered for
  * the norm, the key and the stream on a few thousand points.
  *  Per plane p (with its pose, 12 floats r11 r12 r13 o14 / r21 .. / r31 .., the layout of sbm_stereo_model.local) and pixel

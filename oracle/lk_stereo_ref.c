@@ -2,7 +2,7 @@
  * (section "pyramidal LK stereo"): the pyramid of cv::buildOpticalFlowPyramid (RECALLED), the x-only tracker of
  * calcOpticalFlowPyrLKStereo (REF), computeCorrespondences' disparity gate and the sparse branch of generateKeypoints3DStereo.
  * Written from the header's text, one operation per line where rounding matters. TEST INFRASTRUCTURE ONLY.
- * Build: gcc -O2 -std=c11 -fPIC -ffp-contract=off -shared (tests/lk_stereo_ref.py does it on first use). */
+ * Build: oracle/Makefile, liblk_stereo_ref.so (REF_CFLAGS: -O2 -std=c11 -fPIC -ffp-contract=off). */
 #include <float.h>
 #include <math.h>
 #include <stdint.h>

@@ -1,6 +1,6 @@
 """The sequential CPU restatement of the reference's DEPTH_METHOD_CV_LK path (include/sbm.h, "pyramidal LK stereo"):
-tests/liblk_stereo_ref.so, compiled from tests/lk_stereo_ref.c on first use, through ctypes, and an independent numpy
-transcription of the RECALLED half (the pyramid of cv::buildOpticalFlowPyramid) that the C file is held to.
+oracle/liblk_stereo_ref.so (from oracle/lk_stereo_ref.c) through ctypes, and an independent numpy transcription of the
+RECALLED half (the pyramid of cv::buildOpticalFlowPyramid) that the C file is held to.
 TEST INFRASTRUCTURE ONLY.
 
     params(...)                                   the reference's constants by default (lk_ref_params)
@@ -13,14 +13,12 @@ TEST INFRASTRUCTURE ONLY.
     keypoints3d(pts, right_pts, status, model, min_depth, max_depth)   -> float32 (n, 3), NaN where invalid
 """
 import ctypes
-import fcntl
-import pathlib
-import subprocess
 
 import numpy as np
 
-HERE = pathlib.Path(__file__).resolve().parent
-SRC, SO = HERE / "lk_stereo_ref.c", HERE / "liblk_stereo_ref.so"
+import oracle_lib
+from sbm_oracle import StereoModel
+
 GET_MIN_EIGENVALS = 8
 CONVERGED, PREV_OUT, MIN_EIG, NEXT_OUT, MAX_COUNT, OSCILLATION = range(6)
 MAX_LEVELS = 16
@@ -33,35 +31,15 @@ class Params(ctypes.Structure):
                 ("min_eig_threshold", ctypes.c_double), ("min_disparity", ctypes.c_float), ("max_disparity", ctypes.c_float)]
 
 
-class Model(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_double) for k in ("fx_l", "fy_l", "cx_l", "cy_l", "Tx_l", "fx_r", "fy_r", "cx_r", "Tx_r")] + [
-        ("local", ctypes.c_float * 12), ("has_local", ctypes.c_int32)]
-
-
 def params(win_width=15, win_height=3, max_level=5, max_count=30, epsilon=0.01, flags=GET_MIN_EIGENVALS, min_eig_threshold=1e-4,
            min_disparity=0.5, max_disparity=128.0):
     return Params(win_width, win_height, max_level, max_count, epsilon, flags, min_eig_threshold, min_disparity, max_disparity)
 
 
-def _build():
-    # processes that start together take turns: one compiles, the others then find the library up to date
-    with open(SRC) as src:
-        fcntl.flock(src, fcntl.LOCK_EX)
-        if SO.exists() and SO.stat().st_mtime >= SRC.stat().st_mtime:
-            return
-        tmp = SO.with_suffix(".so.tmp")
-        r = subprocess.run(["gcc", "-O2", "-std=c11", "-fPIC", "-ffp-contract=off", "-shared", "-o", str(tmp), str(SRC), "-lm"],
-                           capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("building tests/liblk_stereo_ref.so failed:\n" + r.stdout + r.stderr)
-        tmp.replace(SO)
-
-
 def lib():
     global _LIB
     if _LIB is None:
-        _build()
-        L = ctypes.CDLL(str(SO))
+        L = oracle_lib.load("liblk_stereo_ref.so")
         vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
         pp = ctypes.POINTER(Params)
         L.lk_ref_levels.argtypes = [ci, ci, ci, ci, ci]
@@ -70,7 +48,7 @@ def lib():
         L.lk_ref_gate.argtypes = [vp, vp, vp, ci, cf, cf]
         L.lk_ref_gate.restype = None
         L.lk_ref_correspondences.argtypes = [vp, vp, ci, ci, vp, ci, pp, vp, vp, vp]
-        L.lk_ref_keypoints3d.argtypes = [vp, vp, vp, ci, ctypes.POINTER(Model), cf, cf, vp]
+        L.lk_ref_keypoints3d.argtypes = [vp, vp, vp, ci, ctypes.POINTER(StereoModel), cf, cf, vp]
         L.lk_ref_keypoints3d.restype = None
         _LIB = L
     return _LIB
@@ -218,7 +196,7 @@ def correspondences(left, right, pts, p=None):
 
 def make_model(fx=700.0, fy=705.0, cx=320.5, cy=241.25, baseline=0.12, cx_r=None, local=None):
     """A StereoCameraModel in the reference's convention: Tx_l = 0, Tx_r = -fx * baseline."""
-    m = Model()
+    m = StereoModel()
     m.fx_l, m.fy_l, m.cx_l, m.cy_l, m.Tx_l = fx, fy, cx, cy, 0.0
     m.fx_r, m.fy_r, m.cx_r, m.Tx_r = fx, fy, cx if cx_r is None else cx_r, -fx * baseline
     if local is not None:

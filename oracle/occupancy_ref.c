@@ -2,7 +2,7 @@
 // as include/sbm.h states it ("occupancy map: buildOccupancyGridMap"), and of the octomap binary stream that
 // OcTree::writeBinary produces for a tree of occupied leaves. TEST INFRASTRUCTURE ONLY: never linked into the engine, and
 // its writer (a pointer octree with an explicit prune) shares nothing with the library's (one pass over Morton-sorted keys).
-// Built with -O2 -ffp-contract=off: every float / double operation below is the one the C++ source performs.
+// Built by oracle/Makefile with -O2 -ffp-contract=off: every float / double operation below is the one the C++ source performs.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>

@@ -1,5 +1,5 @@
 """The sequential CPU restatement of the reference's buildOccupancyGridMap (include/sbm.h, "occupancy map"):
-tests/liboccupancy_ref.so, compiled from tests/occupancy_ref.c on first use, through ctypes. TEST INFRASTRUCTURE ONLY.
+oracle/liboccupancy_ref.so (from oracle/occupancy_ref.c) through ctypes. TEST INFRASTRUCTURE ONLY.
 
     params(resolution, range_max, tree_depth)      the reference's constants by default
     model(...) / pose_rows(poses)                   sbm_stereo_model; poses as float32 (n, 12)
@@ -12,14 +12,12 @@ tests/liboccupancy_ref.so, compiled from tests/occupancy_ref.c on first use, thr
     pack(k) / unpack(keys)                          (m, 3) uint16 <-> packed uint64
 """
 import ctypes
-import fcntl
-import pathlib
-import subprocess
 
 import numpy as np
 
-HERE = pathlib.Path(__file__).resolve().parent
-SRC, SO = HERE / "occupancy_ref.c", HERE / "liboccupancy_ref.so"
+import oracle_lib
+from sbm_oracle import StereoModel
+
 EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)
 GATE, KEY = 1, 2
 _LIB = None
@@ -29,17 +27,12 @@ class Params(ctypes.Structure):
     _fields_ = [("resolution", ctypes.c_double), ("range_max", ctypes.c_float), ("tree_depth", ctypes.c_int32)]
 
 
-class Model(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_double) for k in ("fx_l", "fy_l", "cx_l", "cy_l", "Tx_l", "fx_r", "fy_r", "cx_r", "Tx_r")] + [
-        ("local", ctypes.c_float * 12), ("has_local", ctypes.c_int32)]
-
-
 def params(resolution=0.1, range_max=5.0, tree_depth=16):
     return Params(float(resolution), float(range_max), int(tree_depth))
 
 
 def model(fx=400.0, fy=400.0, cx=320.0, cy=240.0, baseline=0.12, cx_r=None, local=None):
-    m = Model()
+    m = StereoModel()
     m.fx_l, m.fy_l, m.cx_l, m.cy_l, m.Tx_l = fx, fy, cx, cy, 0.0
     m.fx_r, m.fy_r, m.cx_r, m.Tx_r = fx, fy, cx if cx_r is None else cx_r, -fx * baseline
     if local is not None:
@@ -51,7 +44,7 @@ def model(fx=400.0, fy=400.0, cx=320.0, cy=240.0, baseline=0.12, cx_r=None, loca
 def model_from_array(a):
     """The 22 doubles a fixture stores: the nine intrinsics, the local transform, has_local."""
     a = np.asarray(a, np.float64)
-    m = Model()
+    m = StereoModel()
     for k, v in zip(("fx_l", "fy_l", "cx_l", "cy_l", "Tx_l", "fx_r", "fy_r", "cx_r", "Tx_r"), a[:9]):
         setattr(m, k, float(v))
     m.local[:] = [float(np.float32(v)) for v in a[9:21]]
@@ -64,27 +57,12 @@ def model_to_array(m):
                     np.float64)
 
 
-def _build():
-    # processes that start together take turns: one compiles, the others then find the library up to date
-    with open(SRC) as src:
-        fcntl.flock(src, fcntl.LOCK_EX)
-        if SO.exists() and SO.stat().st_mtime >= SRC.stat().st_mtime:
-            return
-        tmp = SO.with_suffix(".so.tmp")
-        r = subprocess.run(["gcc", "-O2", "-std=c11", "-fPIC", "-ffp-contract=off", "-shared", "-o", str(tmp), str(SRC), "-lm"],
-                           capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("building tests/liboccupancy_ref.so failed:\n" + r.stdout + r.stderr)
-        tmp.replace(SO)
-
-
 def lib():
     global _LIB
     if _LIB is None:
-        _build()
-        L = ctypes.CDLL(str(SO))
+        L = oracle_lib.load("liboccupancy_ref.so")
         vp, ci, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-        mp, pp = ctypes.POINTER(Model), ctypes.POINTER(Params)
+        mp, pp = ctypes.POINTER(StereoModel), ctypes.POINTER(Params)
         L.occ_ref_reproject.argtypes = [vp, ci, ci, ci, mp, ci, vp]
         L.occ_ref_reproject.restype = None
         L.occ_ref_world.argtypes = [vp, ci, ci, ci, mp, vp, vp]

@@ -1,5 +1,5 @@
-"""What the GPU test modules share: the call-site build, the torch_cuda and bm fixtures (imported by name into the modules that
-use them) and the upload helper. TEST INFRASTRUCTURE ONLY."""
+"""What the test modules share: the call-site build (CPU and GPU modules alike), and for the GPU modules the torch_cuda and bm
+fixtures (imported by name into the modules that use them) and the upload helper. TEST INFRASTRUCTURE ONLY."""
 import pathlib
 import subprocess
 
@@ -10,8 +10,8 @@ ROOT = pathlib.Path(__file__).resolve().parents[1]
 
 
 def build_callsite(tmp_path, source, extra=(), *, flags=(), exe="cs", pkg=None, libs=()):
-    """g++ over tests/cpp/<source> and the engine library -> (tmp_path / exe, the completed process). flags go in front of
-    -I include, extra behind it. With pkg the library is linked by its path (pkg.library_path()), libs follow it, and ROCm's
+    """g++ over tests/cpp/<source> (or over source as it is where it is an absolute path, such as a file a test wrote into
+    tmp_path) and the engine library -> (tmp_path / exe, the completed process). flags go in front of -I include, extra behind it. With pkg the library is linked by its path (pkg.library_path()), libs follow it, and ROCm's
     directory joins the rpath; without, it is linked as -L u96-slam_amd/lib -lsbm_hip."""
     exe = tmp_path / exe
     cmd = ["g++", "-std=c++17", "-O1", *flags, "-I", str(ROOT / "include"), *extra, str(ROOT / "tests" / "cpp" / source)]

@@ -1,5 +1,5 @@
 """Inputs for the occupancy map's data-structure tests whose expected result is a closed form, independent of
-tests/occupancy_ref.c. TEST INFRASTRUCTURE ONLY, no GPU.
+oracle/occupancy_ref.c. TEST INFRASTRUCTURE ONLY, no GPU.
 
 Under a pose whose rotation block is zero the world point of every valid pixel is the pose's translation, exactly:
 0*x + 0*y + 0*z + o equals o in float for finite x, y, z, and the norm of (point - origin) is 0. So n planes of 1 x 1 pixels at

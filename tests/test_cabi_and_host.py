@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from gpu_support import build_callsite
+
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 
 
@@ -103,10 +105,7 @@ int main() {
   return 0;
 }
 ''')
-    exe = tmp_path / "t"
-    lib = pkg.library_path()
-    r = subprocess.run(["g++", "-std=c++17", "-I", str(ROOT / "include"), str(src), "-o", str(exe), str(lib),
-                        f"-Wl,-rpath,{lib.parent}", "-Wl,-rpath,/opt/rocm/lib"], capture_output=True, text=True)
+    exe, r = build_callsite(tmp_path, src, exe="t", pkg=pkg)
     assert r.returncode == 0, r.stderr
     r = subprocess.run([str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, (r.stdout, r.stderr)

@@ -3,9 +3,10 @@ failure, the limits, and the C++ adaptor compiling against the library (plain, a
 OpenCV mocks)."""
 import math
 import pathlib
-import subprocess
 
 import pytest
+
+from gpu_support import build_callsite
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 
@@ -56,8 +57,5 @@ def test_null_arguments(pkg):
 @pytest.mark.parametrize("mock", [False, True], ids=["plain", "mock_opencv"])
 def test_adaptor_compiles_and_links(tmp_path, pkg, mock):
     extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv")] if mock else []
-    lib = ROOT / "u96-slam_amd" / "lib"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", str(ROOT / "include"), *extra,
-                        str(ROOT / "tests" / "cpp" / "gftt_cv_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip",
-                        f"-Wl,-rpath,{lib}", "-o", str(tmp_path / "cs")], capture_output=True, text=True)
+    _, r = build_callsite(tmp_path, "gftt_cv_callsite_main.cpp", extra, flags=("-Wall", "-Werror"))
     assert r.returncode == 0, r.stderr

@@ -6,6 +6,8 @@ import subprocess
 
 import pytest
 
+from gpu_support import build_callsite
+
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 
 
@@ -48,10 +50,7 @@ def test_capacity(pkg):
 @pytest.mark.parametrize("mock", [False, True], ids=["plain", "mock_opencv"])
 def test_gftt_adaptor_compiles_and_links(tmp_path, pkg, mock):
     extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv")] if mock else []
-    lib = ROOT / "u96-slam_amd" / "lib"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", str(ROOT / "include"), *extra,
-                        str(ROOT / "tests" / "cpp" / "gftt_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip", f"-Wl,-rpath,{lib}",
-                        "-o", str(tmp_path / "cs")], capture_output=True, text=True)
+    _, r = build_callsite(tmp_path, "gftt_callsite_main.cpp", extra, flags=("-Wall", "-Werror"))
     assert r.returncode == 0, r.stderr
     src = tmp_path / "t.cpp"
     src.write_text(r'''
@@ -64,7 +63,6 @@ int main() {
   return 0;
 }
 ''')
-    r = subprocess.run(["g++", "-std=c++17", "-I", str(ROOT / "include"), str(src), "-L", str(lib), "-lsbm_hip",
-                        f"-Wl,-rpath,{lib}", "-o", str(tmp_path / "t")], capture_output=True, text=True)
+    exe, r = build_callsite(tmp_path, src, exe="t")
     assert r.returncode == 0, r.stderr
-    assert subprocess.run([str(tmp_path / "t")]).returncode == 0
+    assert subprocess.run([str(exe)]).returncode == 0

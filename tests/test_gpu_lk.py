@@ -1,4 +1,4 @@
-"""GPU LK stereo (u96-slam_amd/csrc/sbm_lk.hip) bit for bit against the sequential C restatement (tests/lk_stereo_ref): every
+"""GPU LK stereo (u96-slam_amd/csrc/sbm_lk.hip) bit for bit against the sequential C restatement (oracle/lk_stereo_ref): every
 pyramid level and derivative plane, the tracker's right points, status and err (floats compared as uint32, no mismatch
 allowed), the sparse keypoint depths, the chain behind the detector, the host form and the C++ call site. Equality is exact: both
 sides perform the same IEEE operations, in the same order, without contraction."""

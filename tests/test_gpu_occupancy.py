@@ -1,4 +1,4 @@
-"""The GPU occupancy map (u96-slam_amd/csrc/sbm_occupancy.hip) against the sequential C restatement (tests/occupancy_ref) and
+"""The GPU occupancy map (u96-slam_amd/csrc/sbm_occupancy.hip) against the sequential C restatement (oracle/occupancy_ref) and
 the reference's own octomap (tests/golden/occupancy_octomap.npz): sorted keys, hit counts and size are compared for exact
 equality -- both sides perform the same IEEE operations in the same order without contraction, and a set has no order."""
 import ctypes

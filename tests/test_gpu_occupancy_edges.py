@@ -1,7 +1,7 @@
 """The occupancy map as a DATA STRUCTURE (u96-slam_amd/csrc/sbm_occupancy.hip): the set, its counts, the radix sort and the
 map's lifetime, against a closed form that needs no restatement (tests/occupancy_cases: under a zero rotation block a 1 x 1
 plane puts exactly the key of its pose's translation into the map), and the leader reduction on planes with a built
-per-wavefront key pattern against tests/occupancy_ref. tests/test_occupancy_restatement.py proves every expectation used here
+per-wavefront key pattern against oracle/occupancy_ref. tests/test_occupancy_restatement.py proves every expectation used here
 on the CPU. Keys, hits and size are compared for exact equality."""
 import ctypes
 import pathlib

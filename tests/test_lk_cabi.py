@@ -4,13 +4,13 @@ the OpenCV mocks)."""
 import ctypes
 import math
 import pathlib
-import subprocess
 import sys
 
 import pytest
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "tests"))
+from gpu_support import build_callsite  # noqa: E402
 
 
 def test_defaults_are_the_reference_constants(pkg):
@@ -79,8 +79,5 @@ def test_level_sizes_of_the_mirror_follow_the_restatement(pkg):
 @pytest.mark.parametrize("mock", [False, True], ids=["plain", "mock_opencv"])
 def test_adaptor_compiles_and_links(tmp_path, pkg, mock):
     extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv")] if mock else []
-    lib = ROOT / "u96-slam_amd" / "lib"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", str(ROOT / "include"), *extra,
-                        str(ROOT / "tests" / "cpp" / "lk_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip",
-                        f"-Wl,-rpath,{lib}", "-o", str(tmp_path / "cs")], capture_output=True, text=True)
+    _, r = build_callsite(tmp_path, "lk_callsite_main.cpp", extra, flags=("-Wall", "-Werror"))
     assert r.returncode == 0, r.stderr

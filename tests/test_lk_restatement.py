@@ -1,4 +1,4 @@
-"""The CPU restatement of the LK stereo path (tests/lk_stereo_ref) on its own: the C pyramid against the numpy transcription of
+"""The CPU restatement of the LK stereo path (oracle/lk_stereo_ref) on its own: the C pyramid against the numpy transcription of
 the header's RECALLED text, bit for bit; the properties the tracker must have on identical images; and every exit of the
 tracker occurring on the golden pair, often enough that a comparison against the restatement means something."""
 import pathlib

@@ -4,10 +4,11 @@ tests/cpp/mock_opencv)."""
 import ctypes
 import math
 import pathlib
-import subprocess
 
 import numpy as np
 import pytest
+
+from gpu_support import build_callsite
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 
@@ -62,8 +63,5 @@ def test_the_contract_is_documented():
 @pytest.mark.parametrize("mock", [False, True], ids=["plain", "mock_opencv"])
 def test_cpp_adaptor_compiles(tmp_path, mock):
     extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv")] if mock else []
-    lib = ROOT / "u96-slam_amd" / "lib"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", str(ROOT / "include"), *extra,
-                        str(ROOT / "tests" / "cpp" / "match_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip",
-                        f"-Wl,-rpath,{lib}", "-o", str(tmp_path / "cs")], capture_output=True, text=True)
+    _, r = build_callsite(tmp_path, "match_callsite_main.cpp", extra, flags=("-Wall", "-Werror"))
     assert r.returncode == 0, r.stderr[-3000:]

@@ -4,7 +4,6 @@ the reference's octomap wrote and against the restatement's writer, and the C++ 
 import ctypes
 import math
 import pathlib
-import subprocess
 import sys
 
 import numpy as np
@@ -13,6 +12,7 @@ import pytest
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT / "tests"))
 import occupancy_ref as occ  # noqa: E402
+from gpu_support import build_callsite  # noqa: E402
 
 GOLDEN = ROOT / "tests" / "golden" / "occupancy_octomap.npz"
 
@@ -31,8 +31,8 @@ def test_struct_layout_and_defaults(pkg):
     assert ctypes.sizeof(p) == 16 == ctypes.sizeof(occ.Params)
     assert [(f[0], f[1]) for f in pkg.OccParams._fields_] == [(f[0], f[1]) for f in occ.Params._fields_]
     assert (pkg.OccParams.resolution.offset, pkg.OccParams.range_max.offset, pkg.OccParams.tree_depth.offset) == (0, 8, 12)
-    assert ctypes.sizeof(pkg.StereoModel) == ctypes.sizeof(occ.Model) == 128
-    assert [f[0] for f in pkg.StereoModel._fields_] == [f[0] for f in occ.Model._fields_]
+    assert ctypes.sizeof(pkg.StereoModel) == ctypes.sizeof(occ.StereoModel) == 128
+    assert [f[0] for f in pkg.StereoModel._fields_] == [f[0] for f in occ.StereoModel._fields_]
     assert pkg.ERR_OCC_FULL == -25
     assert b"occupancy map full" in pkg.load_library().sbm_strerror(-25)
 
@@ -119,8 +119,5 @@ def test_write_binary_on_shapes_the_fixture_lacks(pkg, tmp_path):
 
 
 def test_adaptor_compiles_and_links(tmp_path, pkg):
-    lib = ROOT / "u96-slam_amd" / "lib"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", str(ROOT / "include"),
-                        str(ROOT / "tests" / "cpp" / "occupancy_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip",
-                        f"-Wl,-rpath,{lib}", "-o", str(tmp_path / "cs")], capture_output=True, text=True)
+    _, r = build_callsite(tmp_path, "occupancy_callsite_main.cpp", flags=("-Wall", "-Werror"))
     assert r.returncode == 0, r.stderr

@@ -1,4 +1,4 @@
-"""The CPU restatement of buildOccupancyGridMap (tests/occupancy_ref) against what the reference's own octomap recorded
+"""The CPU restatement of buildOccupancyGridMap (oracle/occupancy_ref) against what the reference's own octomap recorded
 (tests/golden/occupancy_octomap.npz, written by tools/make_occupancy_fixtures.py) and against the reprojection of the oracle."""
 import hashlib
 import pathlib

@@ -5,6 +5,8 @@ import subprocess
 
 import pytest
 
+from gpu_support import build_callsite
+
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 SG, HH, SG3, HH4 = 0, 1, 2, 3
 
@@ -61,11 +63,7 @@ def test_strerror_unchanged_for_sgbm_codes(pkg):
 @pytest.mark.parametrize("mock", [False, True], ids=["plain", "mock_opencv"])
 def test_sgbm_adaptor_compiles_and_links(tmp_path, pkg, mock):
     extra = ["-DSBM_TEST_WITH_OPENCV", "-I", str(ROOT / "tests" / "cpp" / "mock_opencv")] if mock else []
-    lib = ROOT / "u96-slam_amd" / "lib"
-    exe = tmp_path / "cs"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I", str(ROOT / "include"), *extra,
-                        str(ROOT / "tests" / "cpp" / "sgbm_callsite_main.cpp"), "-L", str(lib), "-lsbm_hip", f"-Wl,-rpath,{lib}",
-                        "-o", str(exe)], capture_output=True, text=True)
+    _, r = build_callsite(tmp_path, "sgbm_callsite_main.cpp", extra, flags=("-Wall", "-Werror"))
     assert r.returncode == 0, r.stderr
     src = tmp_path / "t.cpp"
     src.write_text(r'''
@@ -79,7 +77,6 @@ int main() {
   return 0;
 }
 ''')
-    r = subprocess.run(["g++", "-std=c++17", "-I", str(ROOT / "include"), str(src), "-L", str(lib), "-lsbm_hip",
-                        f"-Wl,-rpath,{lib}", "-o", str(tmp_path / "t")], capture_output=True, text=True)
+    exe, r = build_callsite(tmp_path, src, exe="t")
     assert r.returncode == 0, r.stderr
-    assert subprocess.run([str(tmp_path / "t")]).returncode == 0
+    assert subprocess.run([str(exe)]).returncode == 0

@@ -11,7 +11,7 @@
   sparse_route_ms / dense_route_ms    stereo_ms + depth3d_ms against dense_compute_ms + dense_kp3d_ms
   iterations_hist                     [level][iterations] point counts of the restatement over the first 4 pairs
   points_per_frame / tracked_per_frame   from the device counts and statuses
-  restatement_1core_ms                tests/lk_stereo_ref (sequential C) per pair on one core
+  restatement_1core_ms                oracle/lk_stereo_ref (sequential C) per pair on one core
   restatement_16proc_ms               --n pairs over 16 host processes, wall time
   bit_exact_first_4                   the device outputs of the first 4 pairs equal the restatement's
 
@@ -33,7 +33,6 @@ import numpy as np
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "oracle"))
-sys.path.insert(0, str(ROOT / "tests"))
 
 
 def pairs(kind, n):

@@ -8,7 +8,7 @@ print one JSON line:
   insert_again_ms      the same call into the map that already holds them (every key found, no slot claimed)
   fetch_ms             sbm_occ_fetch_device (compaction + 6 radix passes), host wall time (it synchronises)
   points / accepted / voxels / duplicate_rate   pixels fed, points kept by the gate and the key, distinct voxels, 1 - voxels/accepted
-  restatement_1core_ms tests/occupancy_ref (sequential C, per-pixel keys) + numpy's unique on the same input, one core
+  restatement_1core_ms oracle/occupancy_ref (sequential C, per-pixel keys) + numpy's unique on the same input, one core
   equal                the device's sorted keys and hit counts equal the restatement's
 
   python tools/bench_occupancy.py [--n 64] [--steps 20] [--warmup 3] [--capacity 262144] [--out FILE]
@@ -25,7 +25,7 @@ import numpy as np
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
-sys.path.insert(0, str(ROOT / "tests"))
+sys.path.insert(0, str(ROOT / "oracle"))
 
 
 def walk(n, h=120, w=160, seed=0):

@@ -7,7 +7,7 @@ crop of the golden pair and 64 points, for whoever has an OpenCV at hand.
 
 The kit holds the pair, the points, every pyramid level of both images, every derivative plane of the left one, and the tracker's
 outputs before the gate (right points, status, err) and the status after it -- all from the CPU restatement
-(tests/lk_stereo_ref); tests/test_lk_pin_kit.py regenerates them bit for bit. The pyramid is the half nothing in the reference
+(oracle/lk_stereo_ref); tests/test_lk_pin_kit.py regenerates them bit for bit. The pyramid is the half nothing in the reference
 pins (it is OpenCV's); the tracker is the reference's own source. Deterministic."""
 import pathlib
 import sys
@@ -15,7 +15,7 @@ import sys
 import numpy as np
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "tests"))
+sys.path.insert(0, str(ROOT / "oracle"))
 OUT = ROOT / "tests" / "golden" / "pin_kit_lk.npz"
 CROP = (slice(180, 300), slice(240, 400))   # rows, columns of the golden pair: 160 x 120
 

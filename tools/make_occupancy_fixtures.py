@@ -10,7 +10,7 @@ Run by hand, never by a test:
 It compiles the driver below (this project's text) against the octomap sources vendored in the reference tree
 (src/slam/src/octomap/*.cpp, headers under src/slam/include) into a temporary directory, feeds it the points and keeps only
 inputs and recorded outputs. The points are made here from disparity planes and poses through the front half of
-tests/occupancy_ref (reprojection and the two transforms), so that the GPU tests can feed the very same cases as planes:
+oracle/occupancy_ref (reprojection and the two transforms), so that the GPU tests can feed the very same cases as planes:
 
     scene   three 40 x 30 planes of a sloped scene (rows from 55 m down to 0.9 m, some invalid pixels) through three poses
     edge    1 x 1 planes under poses with a ZERO rotation block: the world point is the pose's translation, exactly, and the
@@ -31,7 +31,7 @@ import tempfile
 import numpy as np
 
 ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "tests"))
+sys.path.insert(0, str(ROOT / "oracle"))
 import occupancy_ref as occ  # noqa: E402
 
 OUT = ROOT / "tests" / "golden" / "occupancy_octomap.npz"
