@@ -899,7 +899,8 @@ int sbm_sgbm_compute_device(sbm_handle* h, const sbm_sgbm_params* p, int n, cons
  *  Kernels: per level one pyrDown launch over both images of every pair of a chunk and one Scharr launch
  *   over its left images, then ONE tracker launch, one wavefront per keypoint, that walks the levels. Device scratch, held by the
  *   handle: per pair of a chunk the levels above 0 of both images (1 B per pixel each) and the derivatives of every left level
- *   (4 B per pixel), ~6.7 B per frame pixel; a call works through its pairs in chunks of at most 256 MiB of it.
+ *   (4 B per pixel), ~6.7 B per frame pixel; a call works through its pairs in chunks of at most 256 MiB of it, and of at most
+ *   32 767 pairs where a level above 0 exists (one pyrDown launch holds both images of every pair of a chunk).
  *  sbm_get_profile: while profiling is enabled (any mode) sbm_lk_stereo_device synchronises and records "lk_pyramid", "lk_track"
  *   and "lk_total" (ms of the last call, summed over its chunks). */
 #define SBM_LK_USE_INITIAL_FLOW 4    /* cv::OPTFLOW_USE_INITIAL_FLOW: unsupported                     */

@@ -22,6 +22,7 @@ constexpr int kLkWinW = 15, kLkWinH = 3, kLkWin = kLkWinW * kLkWinH;   // the on
 constexpr int kLkMaxLevels = 8;                                         // 2048 -> 16 columns at level 7, the last one kept
 constexpr int kLkMaxDim = 2048;
 constexpr size_t kLkChunkBytes = (size_t)256 << 20;
+constexpr size_t kLkMaxGridZ = 65535;                                   // frames of one launch (gridDim.z, and gridDim.y of the tracker)
 constexpr int kLkFlagInitialFlow = 4, kLkFlagMinEig = 8;                // cv::OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS
 constexpr int kLkWaves = 4;                                             // keypoints per workgroup of the tracker
 
@@ -253,7 +254,7 @@ static inline dim3 lk_grid(int w, int h, int frames) { return dim3((w + 31) / 32
 static int lk_check(const sbm_lk_params* p, int n, int width, int height) {
   const int st = sbm_lk_params_validate(p, width, height);
   if (st != SBM_OK) return st;
-  return n > 65535 ? SBM_ERR_UNSUPPORTED : SBM_OK;
+  return (size_t)n > kLkMaxGridZ ? SBM_ERR_UNSUPPORTED : SBM_OK;
 }
 
 // Pyramids and tracker of n pairs on the handle's stream, chunk by chunk; profiling times them.
@@ -269,7 +270,9 @@ static int lk_run(sbm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_
     if (l) upper += (size_t)lw[l] * lh[l];
   }
   const size_t per_pair = 2 * upper + 4 * all;   // both images' upper levels, the left's derivatives
-  const int C = (int)std::min<size_t>(n, std::max<size_t>(1, kLkChunkBytes / per_pair));
+  // a chunk also has to fit one launch: pyrDown takes BOTH images of every pair of the chunk in gridDim.z (2 C frames <= 65 535)
+  const size_t fit = std::min<size_t>(std::max<size_t>(1, kLkChunkBytes / per_pair), L > 0 ? kLkMaxGridZ / 2 : kLkMaxGridZ);
+  const int C = (int)std::min<size_t>(n, fit);
   HIPCHK(h, h->lk.pyr.grow((size_t)C * 2 * upper + 256, h->stream));
   HIPCHK(h, h->lk.deriv.grow((size_t)C * 4 * all, h->stream));
   LkGeom g;
