@@ -19,6 +19,14 @@
 using namespace sbm;
 namespace sbm { thread_local char g_sad_kernel_name[96] = ""; }
 
+// The block matcher's stages as sbm_get_profile names them, and the marks sbm_compute_device records into one slot of the
+// handle's ring. "border" is never timed and reads 0: up to 256 disparities the clamped columns ride in the SAD launch.
+enum BmStage { kBmPrefilter, kBmSad, kBmBorder, kBmLr, kBmSpeckle, kBmTotal, kBmStageCount };
+enum BmMark { kBmBegin, kBmPrefiltered, kBmMatched, kBmChecked, kBmEnd, kBmMarkCount };
+static const char* const kBmNames[] = {"prefilter", "sad", "border", "lrcheck", "speckle", "total"};
+StageTable sbm::bm_stages() { return stage_table<kBmStageCount, 0>(kBmNames); }   // no marks of the clock's own: the ring has them
+static_assert(kBmMarkCount == sbm_handle::kMarks, "the ring holds one event per mark");
+
 extern "C" {
 
 void sbm_params_default(sbm_params* p, int num_disparities, int block_size) {
@@ -78,22 +86,13 @@ int sbm_version(void) { return SBM_VERSION_MAJOR * 1000 + SBM_VERSION_MINOR; }
 
 // Every device buffer and pinned staging buffer of the handle; streams and events stay.
 static void free_buffers(sbm_handle* h) {
-  release_set(h->bm);
-  release_set(h->fp);
-  free_staging(h);
-  // The device sets of the asynchronous dense feed have their own life: submissions may be outstanding (the newest one's
-  // trip home not even queued yet) while a synchronous host entry point resizes ITS staging, so only the feed's own realloc
-  // path (drained first) and the handle's end of life or parking free them.
-  release_set(h->fq);
-  release_all(h->sg);
-  h->sg.have_last = false;
-  release_all(h->gs);
-  release_all(h->gc);
-  release_all(h->orb);
-  release_all(h->mt);
-  release_all(h->pnp);
-  release_all(h->lk);
-  release_all(h->occ);
+  h->each_set([](auto& s) { release_all(s); });
+  // What goes with some sets' buffers (releasing those again is a no-op). bm, fp and fq are keyed on their shape and lose the key
+  // too. fq, the asynchronous feed's sets, may have submissions outstanding while a synchronous host entry point resizes ITS
+  // staging: free_staging leaves them alone, and only the feed's own realloc path (drained first) and this function free them.
+  release_set(h->bm); release_set(h->fp); release_set(h->fq);
+  free_staging(h);   // the host entry points' staging: its key, and the pinned host memory that mirrors it
+  h->sg.have_last = false;   // nothing of the last semi-global call is left for sbm_debug_fetch
 }
 
 // The reference re-creates its matcher for every frame (cv::StereoBM::create inside the loop, main.cpp:201). Streams,
@@ -106,32 +105,23 @@ static sbm_handle* g_pool[kPool];
 static int g_pool_n = 0;
 
 static size_t scratch_bytes(sbm_handle* h) {
-  return bytes_held(h->bm) + bytes_held(h->fp) + bytes_held(h->st) + h->pin_bytes + bytes_held(h->fq) + bytes_held(h->sg) +
-         bytes_held(h->gs) + bytes_held(h->gc) + bytes_held(h->orb) + bytes_held(h->mt) +
-         bytes_held(h->pnp) + bytes_held(h->lk) + bytes_held(h->occ);
+  size_t n = h->pin_bytes;
+  h->each_set([&](auto& s) { n += bytes_held(s); });
+  return n;
 }
 
-// Stage times: the block matcher's, and every family's stage clock, start at zero.
+// Stage times: every family's, the block matcher's among them, start at zero.
 static void reset_profile(sbm_handle* h, int enabled) {
   h->profiling = enabled;
-  h->calls = 0;
-  h->ncall = 0;
+  h->calls = h->ncall = 0;
   h->instr = false;
-  h->ms_prefilter = h->ms_sad = h->ms_border = h->ms_lr = h->ms_speckle = h->ms_total = 0.f;
-  h->sg.clock.reset();
-  h->gs.clock.reset();
-  h->gc.clock.reset();
-  h->orb.clock.reset();
-  h->mt.clock.reset();
-  h->pnp.clock.reset();
-  h->lk.clock.reset();
-  h->occ.clock.reset();
+  h->each_clock([](StageClock& c, const StageTable&) { c.reset(); });
 }
 
 static void destroy_now(sbm_handle* h);
 
 void sbm_trim(void) {
-  std::lock_guard<std::mutex> lk(g_pool_mu);
+  std::lock_guard<std::mutex> lock(g_pool_mu);
   for (int i = 0; i < g_pool_n; i++) destroy_now(g_pool[i]);
   g_pool_n = 0;
 }
@@ -142,15 +132,14 @@ int sbm_create(sbm_handle** out, const sbm_params* p, int device) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return SBM_ERR_NO_DEVICE;
   {
-    std::lock_guard<std::mutex> lk(g_pool_mu);
+    std::lock_guard<std::mutex> lock(g_pool_mu);
     for (int i = 0; i < g_pool_n; i++)
       if (g_pool[i]->device == device) {
         sbm_handle* h = g_pool[i];
         g_pool[i] = g_pool[--g_pool_n];
         h->p = *p;
         h->last_hip = 0;
-        h->have_last = false;
-        h->sg.have_last = false;
+        h->have_last = h->sg.have_last = false;
         reset_profile(h, 0);
         *out = h;
         return SBM_OK;
@@ -161,22 +150,6 @@ int sbm_create(sbm_handle** out, const sbm_params* p, int device) {
   memset(h, 0, sizeof(*h));
   h->p = *p;
   h->device = device;
-  static const char* const kSgbm[] = {"sgbm_cost", "sgbm_aggregate", "sgbm_select", "sgbm_median", "sgbm_speckle", "sgbm_total"};
-  static const char* const kGftt[] = {"gftt_select_eig", "gftt_select_select", "gftt_select_total"};
-  static const char* const kOrb[] = {"orb_blur", "orb_desc", "orb_total"};
-  static const char* const kMatch[] = {"match_knn", "match_unique", "match_total", "match_project"};
-  h->sg.clock.init(kSgbm);
-  h->gs.clock.init(kGftt);
-  h->orb.clock.init(kOrb);
-  h->mt.clock.init(kMatch);
-  static const char* const kPnp[] = {"pnp_hyp", "pnp_score", "pnp_refine", "pnp_total"};
-  h->pnp.clock.init(kPnp);
-  static const char* const kGfttCv[] = {"gftt_cv_eig", "gftt_cv_select", "gftt_cv_total"};
-  h->gc.clock.init(kGfttCv);
-  static const char* const kLk[] = {"lk_pyramid", "lk_track", "lk_total"};
-  h->lk.clock.init(kLk);
-  static const char* const kOcc[] = {"occ_insert", "occ_fetch"};
-  h->occ.clock.init(kOcc);
   DeviceScope dscope(device);
   if (dscope.enter() != hipSuccess) {
     delete h;
@@ -212,7 +185,7 @@ void sbm_destroy(sbm_handle* h) {
   h->fq_waited = h->fq_submitted;
   sync_all_streams(h);
   {
-    std::lock_guard<std::mutex> lk(g_pool_mu);
+    std::lock_guard<std::mutex> lock(g_pool_mu);
     if (g_pool_n < kPool) {
       if (scratch_bytes(h) > kPoolScratch) {
         free_buffers(h);
@@ -231,14 +204,7 @@ static void destroy_now(sbm_handle* h) {
   dscope.enter();
   sync_all_streams(h);
   free_buffers(h);
-  h->sg.clock.release();
-  h->gs.clock.release();
-  h->gc.clock.release();
-  h->orb.clock.release();
-  h->mt.clock.release();
-  h->pnp.clock.release();
-  h->lk.clock.release();
-  h->occ.clock.release();
+  h->each_clock([](StageClock& c, const StageTable&) { c.release(); });
   for (int r = 0; r < sbm_handle::kRing; r++)
     for (int i = 0; i < sbm_handle::kMarks; i++)
       if (h->ev[r][i]) hipEventDestroy(h->ev[r][i]);
@@ -329,7 +295,7 @@ static int ensure_scratch(sbm_handle* h, int n, int W, int H, int pitch, bool ne
   return SBM_OK;
 }
 
-static inline void mark(sbm_handle* h, int i) {
+static inline void mark(sbm_handle* h, BmMark i) {
   if (h->instr) hipEventRecord(h->ev[h->calls % sbm_handle::kRing][i], h->stream);
 }
 
@@ -338,20 +304,19 @@ static inline void mark(sbm_handle* h, int i) {
 static void collect_profile(sbm_handle* h) {
   unsigned nrec = std::min<unsigned>(h->calls, sbm_handle::kRing), first = 0;
   if (h->profiling == 1 && h->calls > 0) { first = (h->calls - 1) % sbm_handle::kRing; nrec = 1; }
-  // events 0..5 with 3 unused (it used to close the border kernel's side stream; one launch carries those columns now)
-  static const int kFrom[4] = {0, 1, 2, 4}, kTo[4] = {1, 2, 4, 5};
-  float acc[4] = {0, 0, 0, 0}, tot = 0.f;
+  static const BmStage kStage[kBmMarkCount - 1] = {kBmPrefilter, kBmSad, kBmLr, kBmSpeckle};   // stage i: from mark i to mark i + 1
+  float acc[kBmMarkCount - 1] = {}, tot = 0.f;
   for (unsigned r = first; r < first + nrec; r++) {
-    for (int i = 0; i < 4; i++) {
+    for (int i = 0; i < kBmMarkCount - 1; i++) {
       float ms = 0.f;
-      if (hipEventElapsedTime(&ms, h->ev[r][kFrom[i]], h->ev[r][kTo[i]]) == hipSuccess) acc[i] += ms;
+      if (hipEventElapsedTime(&ms, h->ev[r][i], h->ev[r][i + 1]) == hipSuccess) acc[i] += ms;
     }
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->ev[r][0], h->ev[r][5]) == hipSuccess) tot += ms;
+    if (hipEventElapsedTime(&ms, h->ev[r][kBmBegin], h->ev[r][kBmEnd]) == hipSuccess) tot += ms;
   }
   const float inv = nrec ? 1.f / nrec : 0.f;
-  h->ms_prefilter = acc[0] * inv; h->ms_sad = acc[1] * inv; h->ms_border = 0.f; h->ms_lr = acc[2] * inv;
-  h->ms_speckle = acc[3] * inv; h->ms_total = tot * inv;
+  for (int i = 0; i < kBmMarkCount - 1; i++) h->bm.clock.ms[kStage[i]] = acc[i] * inv;
+  h->bm.clock.ms[kBmTotal] = tot * inv;
 }
 
 int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_right, int width, int height,
@@ -432,7 +397,7 @@ int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_r
   int32_t* cost = h->bm.cost.as<int32_t>();
 
   h->instr = h->profiling && h->ev_ok && (h->profiling != 3 || (h->ncall & 3u) == 0);
-  mark(h, 0);
+  mark(h, kBmBegin);
   if (any_rows) {
     if (p.prefilter_type == SBM_PREFILTER_XSOBEL) {
       HIPCHK(h, launch_prefilter(dl, dr, pf_l, pf_r, g, h->stream));
@@ -441,7 +406,7 @@ int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_r
       HIPCHK(h, launch_prefilter_norm(dl, dr, pf_l, pf_r, h->bm.vsum.as<uint16_t>(), g, p.prefilter_size, h->stream));
     }
   }
-  mark(h, 1);
+  mark(h, kBmPrefiltered);
   if (any_rows) {
     if (fast) {
       int xa = 0, xb = 0;
@@ -461,12 +426,12 @@ int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_r
       snprintf(h->last_kernel, sizeof(h->last_kernel), "sad_generic_kernel");
     }
   }
-  mark(h, 2);
+  mark(h, kBmMatched);
   HIPCHK(h, launch_lrcheck(disp_pre, cost, out, h->bm.lr_keys.as<unsigned long long>(), g, p.disp12_max_diff, h->stream));
-  mark(h, 4);
+  mark(h, kBmChecked);
   if (speckle)
     HIPCHK(h, launch_speckle(out, h->bm.spk, g, p.speckle_window_size, p.speckle_range, h->stream));
-  mark(h, 5);
+  mark(h, kBmEnd);
   if (h->instr) h->calls++;
   h->ncall++;
   if (sync || h->profiling == 1) HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -564,24 +529,13 @@ int sbm_get_profile(sbm_handle* h, const char* name, float* ms) {
   HIPCHK(h, dscope.enter());
   HIPCHK(h, hipStreamSynchronize(h->stream));
   if (h->profiling && h->ev_ok) collect_profile(h);
-  if (!strcmp(name, "prefilter")) *ms = h->ms_prefilter;
-  else if (!strcmp(name, "sad")) *ms = h->ms_sad;
-  else if (!strcmp(name, "border")) *ms = h->ms_border;
-  else if (!strcmp(name, "lrcheck")) *ms = h->ms_lr;
-  else if (!strcmp(name, "speckle")) *ms = h->ms_speckle;
-  else if (!strcmp(name, "total")) *ms = h->ms_total;
-  else {
-    const float* t = h->sg.clock.find(name);
-    if (!t) t = h->gs.clock.find(name);
-    if (!t) t = h->gc.clock.find(name);
-    if (!t) t = h->orb.clock.find(name);
-    if (!t) t = h->mt.clock.find(name);
-    if (!t) t = h->pnp.clock.find(name);
-    if (!t) t = h->lk.clock.find(name);
-    if (!t) t = h->occ.clock.find(name);
-    if (!t) return SBM_ERR_UNSUPPORTED;
-    *ms = *t;
-  }
+  const float* t = nullptr;
+  h->each_clock([&](StageClock& c, const StageTable& tab) {
+    for (int i = 0; i < tab.nstage; i++)
+      if (!strcmp(name, tab.names[i])) t = &c.ms[i];
+  });
+  if (!t) return SBM_ERR_UNSUPPORTED;
+  *ms = *t;
   return SBM_OK;
 }
 

@@ -347,11 +347,15 @@ int sbm_gftt_cv_detect(sbm_handle* h, const uint8_t* img, size_t img_stride, int
 
 }  // extern "C"
 
+enum GfttCvStage { kGcEig, kGcSelect, kGcTotal, kGcStageCount };
+static const char* const kGfttCvNames[] = {"gftt_cv_eig", "gftt_cv_select", "gftt_cv_total"};
+StageTable sbm::gftt_cv_stages() { return stage_table<kGcStageCount, kGcStageCount>(kGfttCvNames); }
+
 // Enqueues maps and maxima (with d_img; without it d_eig and d_max are the caller's, read only) and (with d_kpts) candidates, order and trim of n dense frames, chunk by chunk; profiling times them.
 int sbm::gftt_cv_run(sbm_handle* h, int n, const void* d_img, int width, int height, const sbm_gftt_cv_params* p, void* d_eig,
                      void* d_max, void* d_kpts, void* d_count, int sync) {
-  StageClock& clk = h->gc.clock;   // stages: eig, select, total
-  HIPCHK(h, clk.start(h->profiling != 0));
+  StageClock& clk = h->gc.clock;
+  HIPCHK(h, clk.start(gftt_cv_stages(), h->profiling != 0));
   const int W = width, H = height;
   const size_t plane = (size_t)W * H;
   const bool select = d_kpts != nullptr;
@@ -390,13 +394,13 @@ int sbm::gftt_cv_run(sbm_handle* h, int n, const void* d_img, int width, int hei
     const int m = std::min(C, n - c0);
     float* eig = d_eig ? (float*)d_eig + plane * c0 : h->gc.eig.as<float>();
     const int vec = (W % 4 == 0 && ((uintptr_t)eig & 15) == 0) ? 1 : 0;
-    HIPCHK(h, clk.mark(0, h->stream));
+    HIPCHK(h, clk.mark(kGcEig, h->stream));
     if (d_img) {
       hipLaunchKernelGGL(mapk, dim3(tx * ty, m), dim3(256), 0, h->stream, (const uint8_t*)d_img + plane * c0, eig, keymax + c0, W, H,
                          tx, f1, vec);
       HIPCHK(h, hipGetLastError());
     }
-    HIPCHK(h, clk.mark(1, h->stream));
+    HIPCHK(h, clk.mark(kGcSelect, h->stream));
     if (select) {
       hipLaunchKernelGGL(gftt_cv_cand_kernel, dim3((unsigned)((plane + 256 * GC_CPT - 1) / (256 * GC_CPT)), m), dim3(256), 0, h->stream, eig, keymax + c0,
                          h->gc.keys.as<unsigned long long>(), ncand + c0, kstride, W, H, p->quality_level);
@@ -408,15 +412,14 @@ int sbm::gftt_cv_run(sbm_handle* h, int n, const void* d_img, int width, int hei
                          kstride, (float*)d_kpts, (int*)d_count, h->gc.tab.as<unsigned>(), g);
       HIPCHK(h, hipGetLastError());
     }
-    HIPCHK(h, clk.mark(2, h->stream));
-    HIPCHK(h, clk.add(0, 0, 1));
-    HIPCHK(h, clk.add(1, 1, 2));
+    HIPCHK(h, clk.mark(kGcTotal, h->stream));
+    for (int s = kGcEig; s < kGcTotal; s++) HIPCHK(h, clk.add(s, s, s + 1));
   }
   if (d_max && d_img) {
     hipLaunchKernelGGL(gftt_cv_max_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, keymax, (float*)d_max, n);
     HIPCHK(h, hipGetLastError());
   }
-  if (clk.on) clk.ms[2] = clk.ms[0] + clk.ms[1];
+  if (clk.on) clk.ms[kGcTotal] = clk.ms[kGcEig] + clk.ms[kGcSelect];
   if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
   return SBM_OK;
 }

@@ -306,15 +306,19 @@ int sbm_gftt_select(sbm_handle* h, const uint16_t* eig, size_t eig_stride, int w
 
 }  // extern "C"
 
+enum GfttSelectStage { kGsEig, kGsSelect, kGsTotal, kGsStageCount };
+static const char* const kGfttSelectNames[] = {"gftt_select_eig", "gftt_select_select", "gftt_select_total"};
+StageTable sbm::gftt_select_stages() { return stage_table<kGsStageCount, kGsStageCount>(kGfttSelectNames); }
+
 // Enqueues the eigenvalue maps (d_img given) and the selection of n dense maps; profiling times the two.
 int sbm::gftt_select_run(sbm_handle* h, int n, const void* d_img, const void* d_eig, const void* d_max, int width, int height,
                          const sbm_gftt_select_params* p, void* d_kpts, void* d_count, int sync) {
-  StageClock& clk = h->gs.clock;   // stages: eig, select, total
-  HIPCHK(h, clk.start(h->profiling != 0));
-  HIPCHK(h, clk.mark(0, h->stream));
+  StageClock& clk = h->gs.clock;
+  HIPCHK(h, clk.start(gftt_select_stages(), h->profiling != 0));
+  HIPCHK(h, clk.mark(kGsEig, h->stream));
   if (d_img)
     HIPCHK(h, launch_gftt_eig((const uint8_t*)d_img, (uint16_t*)d_eig, (unsigned*)d_max, n, width, height, h->stream));
-  HIPCHK(h, clk.mark(1, h->stream));
+  HIPCHK(h, clk.mark(kGsSelect, h->stream));
   const GftSelPlan pl = gftt_select_plan(width, height, p->max_features, p->quality_level, p->min_distance);
   // the global-table kernel works through the images in chunks whose tables stay within 2 GiB
   int chunk = n;
@@ -325,10 +329,10 @@ int sbm::gftt_select_run(sbm_handle* h, int n, const void* d_img, const void* d_
   for (int c0 = 0; c0 < n; c0 += chunk)
     HIPCHK(h, launch_gftt_select((const uint16_t*)d_eig, (const unsigned*)d_max, (float*)d_kpts, (int*)d_count, h->gs.tab.as<unsigned>(),
                                  pl, c0, std::min(chunk, n - c0), h->stream));
-  HIPCHK(h, clk.mark(2, h->stream));
-  if (d_img) HIPCHK(h, clk.add(0, 0, 1));
-  HIPCHK(h, clk.add(1, 1, 2));
-  HIPCHK(h, clk.add(2, 0, 2));
+  HIPCHK(h, clk.mark(kGsTotal, h->stream));
+  if (d_img) HIPCHK(h, clk.add(kGsEig, kGsEig, kGsSelect));
+  HIPCHK(h, clk.add(kGsSelect, kGsSelect, kGsTotal));
+  HIPCHK(h, clk.add(kGsTotal, kGsEig, kGsTotal));
   if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
   return SBM_OK;
 }

@@ -34,7 +34,7 @@ struct GftSelPlan {
 };
 
 constexpr int GS_THREADS = 1024, GS_WAVES = GS_THREADS / 64;
-constexpr int GS_FIXED_LDS = 1280;   // hist[256], wave sums[16], scalars[16] (words), rounded to 16 B
+constexpr int GS_FIXED_LDS = 1280;   // 256 words of hist, 16 wave sums, 16 scalars, rounded to 16 B
 
 struct GsShared {
   unsigned hist[256];

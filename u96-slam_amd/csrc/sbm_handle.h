@@ -86,21 +86,24 @@ struct SpeckleScratch {
 // cv filterSpeckles as parallel connected components (union-find) on n maps of W x H (g.n, g.W, g.H), sc sized for them.
 hipError_t launch_speckle(int16_t* disp, const SpeckleScratch& sc, const Geom& g, int max_size, int max_diff, hipStream_t s);
 
-// Stage times of one family's last call while profiling is on: events created on first use, the stage names sbm_get_profile
-// knows (set when the handle is made), and per stage the milliseconds of the last call summed over its chunks.
+// The stages of one family: the names sbm_get_profile answers, and how many marks one call records. Each family's file (the
+// block matcher's is sbm_api.hip) has the names, next to the enums that index its stages and marks and the code that times them.
+struct StageTable { const char* const* names; int nstage, nmark; };
+StageTable bm_stages(), sgbm_stages(), gftt_select_stages(), gftt_cv_stages(), orb_stages(), match_stages(), pnp_stages(), lk_stages(), occ_stages();
+
+// Stage times of one family's last call while profiling is on: one event per mark, created on the first profiled call, and per
+// stage the milliseconds of the last call summed over its chunks. All zero is a valid clock. A family whose stages run back to
+// back has one enum for both: mark s is recorded as stage s begins, the total's mark at the end.
 struct StageClock {
   static constexpr int kMax = 6;
-  const char* const* names;
-  int nstage;
   bool on;   // this call is timed
   hipEvent_t ev[kMax];
   float ms[kMax];
-  template <int N> void init(const char* const (&table)[N]) { static_assert(N <= kMax, ""); names = table; nstage = N; }
   // a call begins: with profiling, its times start at 0
-  hipError_t start(bool profiling) {
+  hipError_t start(const StageTable& t, bool profiling) {
     on = profiling;
     hipError_t e = hipSuccess;
-    for (int i = 0; on && i < nstage && e == hipSuccess; i++)
+    for (int i = 0; on && i < t.nmark && e == hipSuccess; i++)
       if (!ev[i]) e = hipEventCreate(&ev[i]);
     if (on) reset();
     return e;
@@ -120,12 +123,12 @@ struct StageClock {
     for (hipEvent_t& e : ev)
       if (e) { hipEventDestroy(e); e = nullptr; }
   }
-  const float* find(const char* name) const {
-    for (int i = 0; i < nstage; i++)
-      if (!strcmp(name, names[i])) return &ms[i];
-    return nullptr;
-  }
 };
+// A family's table from the counts its enums end in: a name table and an enum of different lengths do not build.
+template <int NStage, int NMark, int N> constexpr StageTable stage_table(const char* const (&names)[N]) {
+  static_assert(N == NStage && NStage <= StageClock::kMax && NMark <= StageClock::kMax, "stages and marks must fit StageClock::kMax");
+  return {names, NStage, NMark};
+}
 
 }  // namespace sbm
 
@@ -142,6 +145,7 @@ struct sbm_handle {
     sbm::DevBuf lr_keys;      // claim table of the LR check for rows wider than kLrLdsCols (lr_keys_bytes)
     sbm::DevBuf vsum;         // column sums of PREFILTER_NORMALIZED_RESPONSE (2 * n * W * H uint16), allocated on first use
     sbm::SpeckleScratch spk;
+    sbm::StageClock clock;    // stage times only: the marks are the handle's ring below (bm_stages() has no marks of its own)
     template <class F> void each(F f) { f(pf_l); f(pf_r); f(disp_pre); f(cost); f(lr_keys); f(vsum); spk.each(f); }
   } bm;
   struct {   // FPGA-flavour matcher, sized for n pairs of W x H
@@ -189,15 +193,14 @@ struct sbm_handle {
   bool have_last;
   // profiling: mode 1 = sync after every call and keep that call's stage times; mode 2 = record stage events of
   // every call into a ring WITHOUT syncing (bench.py's timed region); sbm_get_profile then averages the ring.
-  // mode 3 = mode 2 on every 4th call only (six event records cost ~25 us per call: sampling keeps the timed region honest)
+  // mode 3 = mode 2 on every 4th call only (five event records cost ~20 us per call: sampling keeps the timed region honest)
   int profiling;
   unsigned ncall;      // calls since profiling was (re)enabled
   bool instr;          // this call records events
-  static constexpr int kRing = 64, kMarks = 6;
+  static constexpr int kRing = 64, kMarks = 5;   // the marks of sbm_compute_device (BmMark in sbm_api.hip)
   hipEvent_t ev[kRing][kMarks];
   bool ev_ok;
   unsigned calls;  // calls recorded since profiling was (re)enabled
-  float ms_prefilter, ms_sad, ms_border, ms_lr, ms_speckle, ms_total;
   struct {   // semi-global matcher: C and S for a chunk of pairs, the map before the median, the speckle filter's scratch
     sbm::DevBuf C, S, pre;
     sbm::SpeckleScratch spk;
@@ -244,6 +247,13 @@ struct sbm_handle {
     sbm::StageClock clock;
     template <class F> void each(F f) { f(sort); f(hist); f(io); }
   } occ;
+  // The two lists a new family joins: f(set) for every set that owns DevBufs, f(clock, table) for every family with stage times.
+  template <class F> void each_set(F f) { f(bm); f(fp); f(st); f(fq); f(sg); f(gs); f(gc); f(orb); f(mt); f(pnp); f(lk); f(occ); }
+  template <class F> void each_clock(F f) {
+    using namespace sbm;
+    f(bm.clock, bm_stages()); f(sg.clock, sgbm_stages()); f(gs.clock, gftt_select_stages()); f(gc.clock, gftt_cv_stages()); f(orb.clock, orb_stages());
+    f(mt.clock, match_stages()); f(pnp.clock, pnp_stages()); f(lk.clock, lk_stages()); f(occ.clock, occ_stages());
+  }
 };
 
 namespace sbm {

@@ -257,11 +257,15 @@ static int lk_check(const sbm_lk_params* p, int n, int width, int height) {
   return (size_t)n > kLkMaxGridZ ? SBM_ERR_UNSUPPORTED : SBM_OK;
 }
 
+enum LkStage { kLkPyramid, kLkTrack, kLkTotal, kLkStageCount };
+static const char* const kLkNames[] = {"lk_pyramid", "lk_track", "lk_total"};
+StageTable lk_stages() { return stage_table<kLkStageCount, kLkStageCount>(kLkNames); }
+
 // Pyramids and tracker of n pairs on the handle's stream, chunk by chunk; profiling times them.
 static int lk_run(sbm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_right, int W, int H, const float* d_kpts,
                   const int* d_count, int cap, const sbm_lk_params* p, float* d_right_pts, uint8_t* d_status, float* d_err, int sync) {
-  StageClock& clk = h->lk.clock;   // stages: pyramid, track, total
-  HIPCHK(h, clk.start(h->profiling != 0));
+  StageClock& clk = h->lk.clock;
+  HIPCHK(h, clk.start(lk_stages(), h->profiling != 0));
   int lw[kLkMaxLevels], lh[kLkMaxLevels];
   const int L = lk_plan_levels(W, H, p->max_level, lw, lh);
   size_t upper = 0, all = 0;   // pixels per frame of levels 1..L, of levels 0..L
@@ -294,7 +298,7 @@ static int lk_run(sbm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_
     uint8_t* pyr = h->lk.pyr.as<uint8_t>();
     short* der = h->lk.deriv.as<short>();
     size_t poff = 0, doff = 0;
-    HIPCHK(h, clk.mark(0, h->stream));
+    HIPCHK(h, clk.mark(kLkPyramid, h->stream));
     for (int l = 0; l <= L; l++) {
       const size_t plane = (size_t)lw[l] * lh[l];
       LkLevel& v = g.lv[l];
@@ -318,15 +322,14 @@ static int lk_run(sbm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_
       v.d = dd;
       doff += plane * m;
     }
-    HIPCHK(h, clk.mark(1, h->stream));
+    HIPCHK(h, clk.mark(kLkTrack, h->stream));
     hipLaunchKernelGGL(lk_track_kernel, dim3((cap + kLkWaves - 1) / kLkWaves, m), dim3(64 * kLkWaves), 0, h->stream, g, d_kpts, d_count,
                        d_right_pts, d_status, d_err, c0);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, clk.mark(2, h->stream));
-    HIPCHK(h, clk.add(0, 0, 1));
-    HIPCHK(h, clk.add(1, 1, 2));
+    HIPCHK(h, clk.mark(kLkTotal, h->stream));
+    for (int s = kLkPyramid; s < kLkTotal; s++) HIPCHK(h, clk.add(s, s, s + 1));
   }
-  if (clk.on) clk.ms[2] = clk.ms[0] + clk.ms[1];
+  if (clk.on) clk.ms[kLkTotal] = clk.ms[kLkPyramid] + clk.ms[kLkTrack];
   if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
   return SBM_OK;
 }

@@ -229,11 +229,17 @@ static int match_check(int n, int m, const int* jobs, int cap, const void* d_des
   return SBM_OK;
 }
 
+// Stage times of a call, and the marks it records: match_run all three per launch, project_run the first two around its kernel.
+enum MatchStage { kMtKnn, kMtUnique, kMtTotal, kMtProject, kMtStageCount };
+enum MatchMark { kMtBegin, kMtMid, kMtEnd, kMtMarkCount };
+static const char* const kMatchNames[] = {"match_knn", "match_unique", "match_total", "match_project"};
+StageTable sbm::match_stages() { return stage_table<kMtStageCount, kMtMarkCount>(kMatchNames); }
+
 // Enqueues the three kernels per launch of up to kArgJobs jobs; with profiling, times k-NN and claim + emit.
 static int match_run(sbm_handle* h, int m, const int* jobs, const void* d_desc, const void* d_count, int cap,
                      const sbm_match_params* p, const void* d_kpts, const void* d_proj, void* d_pairs, void* d_npairs, void* d_knn,
                      bool guess) {
-  StageClock& clk = h->mt.clock;   // stages: match_knn, match_unique, match_total, match_project
+  StageClock& clk = h->mt.clock;
   const int reading = env_switch("SBM_CV_READING", 0);
   const int fused = (reading & kReadMatchFusedL2) ? 1 : 0;
   const float thr = radius_threshold(p->radius);
@@ -255,7 +261,7 @@ static int match_run(sbm_handle* h, int m, const int* jobs, const void* d_desc, 
     memset(&a, 0, sizeof(a));
     for (int j = 0; j < k; j++) a.j[j] = make_int2(jobs[2 * (j0 + j)], jobs[2 * (j0 + j) + 1]);
     const dim3 gk(qtiles, nslice, k), gc((cap + 255) / 256, k);
-    HIPCHK(h, clk.mark(0, h->stream));
+    HIPCHK(h, clk.mark(kMtBegin, h->stream));
     if (guess)
       hipLaunchKernelGGL(match_knn_kernel<true>, gk, dim3(64), 0, h->stream, (const uint8_t*)d_desc, (const int*)d_count,
                          (const float*)d_kpts, (const float*)d_proj, cap, slice_rows, j0, a, thr, fused, part, owner);
@@ -263,7 +269,7 @@ static int match_run(sbm_handle* h, int m, const int* jobs, const void* d_desc, 
       hipLaunchKernelGGL(match_knn_kernel<false>, gk, dim3(64), 0, h->stream, (const uint8_t*)d_desc, (const int*)d_count,
                          (const float*)nullptr, (const float*)nullptr, cap, slice_rows, j0, a, thr, fused, part, owner);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, clk.mark(1, h->stream));
+    HIPCHK(h, clk.mark(kMtMid, h->stream));
     if (guess)
       hipLaunchKernelGGL(match_claim_kernel<true>, gc, dim3(256), 0, h->stream, (const int*)d_count, cap, slice_rows, nslice, j0, a,
                          p->nndr, (const int4*)part, owner, acc, (int4*)d_knn);
@@ -274,11 +280,11 @@ static int match_run(sbm_handle* h, int m, const int* jobs, const void* d_desc, 
     hipLaunchKernelGGL(match_emit_kernel, dim3(k), dim3(256), 0, h->stream, (const int*)d_count, cap, j0, a, (const int*)owner,
                        (const int*)acc, (int2*)d_pairs, (int*)d_npairs);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, clk.mark(2, h->stream));
-    HIPCHK(h, clk.add(0, 0, 1));
-    HIPCHK(h, clk.add(1, 1, 2));
+    HIPCHK(h, clk.mark(kMtEnd, h->stream));
+    HIPCHK(h, clk.add(kMtKnn, kMtBegin, kMtMid));
+    HIPCHK(h, clk.add(kMtUnique, kMtMid, kMtEnd));
   }
-  if (clk.on) clk.ms[2] = clk.ms[0] + clk.ms[1] + clk.ms[3];
+  if (clk.on) clk.ms[kMtTotal] = clk.ms[kMtKnn] + clk.ms[kMtUnique] + clk.ms[kMtProject];
   return SBM_OK;
 }
 
@@ -293,12 +299,12 @@ static int project_run(sbm_handle* h, int m, const int* from, const void* d_xyz,
       a.from[j] = from[j0 + j];
       memcpy(a.T[j], T + (size_t)(j0 + j) * 12, 12 * sizeof(float));
     }
-    HIPCHK(h, clk.mark(0, h->stream));
+    HIPCHK(h, clk.mark(kMtBegin, h->stream));
     hipLaunchKernelGGL(match_project_kernel, dim3((cap + 255) / 256, k), dim3(256), 0, h->stream, (const float*)d_xyz,
                        (const int*)d_count, cap, j0, a, K[0], K[1], K[2], K[3], W, H, (float*)d_proj);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, clk.mark(1, h->stream));
-    HIPCHK(h, clk.add(3, 0, 1));
+    HIPCHK(h, clk.mark(kMtMid, h->stream));
+    HIPCHK(h, clk.add(kMtProject, kMtBegin, kMtMid));
   }
   return SBM_OK;
 }
@@ -338,7 +344,7 @@ int sbm_match_device(sbm_handle* h, int n, int m, const int* jobs, const void* d
   if (st != SBM_OK) return st;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
-  HIPCHK(h, h->mt.clock.start(h->profiling != 0));
+  HIPCHK(h, h->mt.clock.start(match_stages(), h->profiling != 0));
   st = match_run(h, m, jobs, d_desc, d_count, cap, p, nullptr, nullptr, d_pairs, d_npairs, d_knn, false);
   if (st == SBM_OK && sync) HIPCHK(h, hipStreamSynchronize(h->stream));
   return st;
@@ -354,7 +360,7 @@ int sbm_match_guess_device(sbm_handle* h, int n, int m, const int* jobs, const v
   if (st != SBM_OK) return st;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
-  HIPCHK(h, h->mt.clock.start(h->profiling != 0));
+  HIPCHK(h, h->mt.clock.start(match_stages(), h->profiling != 0));
   st = match_run(h, m, jobs, d_desc, d_count, cap, p, d_kpts, d_proj, d_pairs, d_npairs, d_knn, true);
   if (st == SBM_OK && sync) HIPCHK(h, hipStreamSynchronize(h->stream));
   return st;
@@ -367,9 +373,9 @@ int sbm_project_points_device(sbm_handle* h, int n, int m, const int* from, cons
   if (st != SBM_OK) return st;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
-  HIPCHK(h, h->mt.clock.start(h->profiling != 0));
+  HIPCHK(h, h->mt.clock.start(match_stages(), h->profiling != 0));
   st = project_run(h, m, from, d_xyz, d_count, cap, T, K, width, height, d_proj);
-  if (h->mt.clock.on) h->mt.clock.ms[2] = h->mt.clock.ms[3];
+  if (h->mt.clock.on) h->mt.clock.ms[kMtTotal] = h->mt.clock.ms[kMtProject];
   if (st == SBM_OK && sync) HIPCHK(h, hipStreamSynchronize(h->stream));
   return st;
 }
@@ -408,7 +414,7 @@ static int match_host(sbm_handle* h, bool guess, const float* xyz_from, const fl
   if (guess && nf > 0) HIPCHK(h, hipMemcpyAsync(d_xyz, xyz_from, (size_t)nf * 12, hipMemcpyHostToDevice, h->stream));
   if (guess && nt > 0) HIPCHK(h, hipMemcpyAsync(d_kp + (size_t)cap * 2, kpts_to, (size_t)nt * 8, hipMemcpyHostToDevice, h->stream));
   const int job[2] = {0, 1};
-  st = h->mt.clock.start(h->profiling != 0) == hipSuccess ? SBM_OK : SBM_ERR_HIP;
+  st = h->mt.clock.start(match_stages(), h->profiling != 0) == hipSuccess ? SBM_OK : SBM_ERR_HIP;
   if (st == SBM_OK && guess) st = project_run(h, 1, job, d_xyz, d_n, cap, T, K, width, height, d_proj);
   if (st == SBM_OK)
     st = match_run(h, 1, job, d_desc, d_n, cap, p, d_kp, d_proj, d_pairs, d_n + 2, nullptr, guess);

@@ -230,13 +230,19 @@ static int occ_check_insert(const sbm_occ_map* map, int n, const void* disp, int
   return SBM_OK;
 }
 
+// Stage times: an insert and a fetch are separate calls that share the clock's two marks, and each keeps the other's last time.
+enum OccStage { kOccInsert, kOccFetch, kOccStageCount };
+enum OccMark { kOccBegin, kOccEnd, kOccMarkCount };
+static const char* const kOccNames[] = {"occ_insert", "occ_fetch"};
+StageTable occ_stages() { return stage_table<kOccStageCount, kOccMarkCount>(kOccNames); }
+
 static int occ_insert_run(sbm_occ_map* map, int n, const int16_t* d_disp, int W, int H, int scale, const sbm_stereo_model* model,
                           const float* poses, int sync) {
   sbm_handle* h = map->h;
-  StageClock& clk = h->occ.clock;   // stages: insert, fetch; each keeps its last call's time
-  const float fetch_ms = clk.ms[1];
-  HIPCHK(h, clk.start(h->profiling != 0));
-  clk.ms[1] = fetch_ms;
+  StageClock& clk = h->occ.clock;
+  const float fetch_ms = clk.ms[kOccFetch];
+  HIPCHK(h, clk.start(occ_stages(), h->profiling != 0));
+  clk.ms[kOccFetch] = fetch_ms;
   OccGeom g;
   g.W = W;
   g.H = H;
@@ -246,7 +252,7 @@ static int occ_insert_run(sbm_occ_map* map, int n, const int16_t* d_disp, int W,
   g.mask = map->slots - 1;
   g.max_probe = std::min(map->slots, kOccMaxProbe);
   const size_t plane = (size_t)W * H;
-  HIPCHK(h, clk.mark(0, h->stream));
+  HIPCHK(h, clk.mark(kOccBegin, h->stream));
   for (int c0 = 0; c0 < n; c0 += kOccChunk) {
     const int m = std::min(kOccChunk, n - c0);
     OccPoses ps;
@@ -256,8 +262,8 @@ static int occ_insert_run(sbm_occ_map* map, int n, const int16_t* d_disp, int W,
                        *model, ps, map->keys.as<unsigned long long>(), map->hits.as<unsigned>(), map->ctr.as<OccCounters>());
     HIPCHK(h, hipGetLastError());
   }
-  HIPCHK(h, clk.mark(1, h->stream));
-  HIPCHK(h, clk.add(0, 0, 1));
+  HIPCHK(h, clk.mark(kOccEnd, h->stream));
+  HIPCHK(h, clk.add(kOccInsert, kOccBegin, kOccEnd));
   if (!sync && !clk.on) return SBM_OK;
   OccCounters c;
   const int st = occ_read_counters(map, &c);
@@ -269,9 +275,9 @@ static int occ_insert_run(sbm_occ_map* map, int n, const int16_t* d_disp, int W,
 static int occ_fetch_run(sbm_occ_map* map, unsigned long long* d_keys, unsigned* d_hits, size_t cap, size_t* count) {
   sbm_handle* h = map->h;
   StageClock& clk = h->occ.clock;
-  const float insert_ms = clk.ms[0];
-  HIPCHK(h, clk.start(h->profiling != 0));
-  clk.ms[0] = insert_ms;
+  const float insert_ms = clk.ms[kOccInsert];
+  HIPCHK(h, clk.start(occ_stages(), h->profiling != 0));
+  clk.ms[kOccInsert] = insert_ms;
   OccCounters c;
   int st = occ_read_counters(map, &c);
   if (st != SBM_OK) return st;
@@ -287,7 +293,7 @@ static int occ_fetch_run(sbm_occ_map* map, unsigned long long* d_keys, unsigned*
     unsigned long long* kk[2] = {d_keys, h->occ.sort.as<unsigned long long>()};
     unsigned* vv[2] = {d_hits ? d_hits : (unsigned*)((char*)h->occ.sort.p + kb + vb), (unsigned*)((char*)h->occ.sort.p + kb)};
     unsigned* hist = h->occ.hist.as<unsigned>();
-    HIPCHK(h, clk.mark(0, h->stream));
+    HIPCHK(h, clk.mark(kOccBegin, h->stream));
     HIPCHK(h, hipMemsetAsync((char*)map->ctr.p + offsetof(OccCounters, cursor), 0, sizeof(unsigned), h->stream));
     hipLaunchKernelGGL(occ_compact_kernel, dim3((map->slots + 255) / 256), dim3(256), 0, h->stream, map->keys.as<unsigned long long>(),
                        map->hits.as<unsigned>(), map->slots, n, kk[0], vv[0], map->ctr.as<OccCounters>());
@@ -301,9 +307,9 @@ static int occ_fetch_run(sbm_occ_map* map, unsigned long long* d_keys, unsigned*
       hipLaunchKernelGGL(occ_scatter_kernel, dim3(tiles), dim3(64), 0, h->stream, kk[a], vv[a], n, 8 * pass, hist, tiles, kk[b], vv[b]);
       HIPCHK(h, hipGetLastError());
     }
-    HIPCHK(h, clk.mark(1, h->stream));
+    HIPCHK(h, clk.mark(kOccEnd, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    HIPCHK(h, clk.add(1, 0, 1));
+    HIPCHK(h, clk.add(kOccFetch, kOccBegin, kOccEnd));
   }
   return c.overflow ? SBM_ERR_OCC_FULL : SBM_OK;
 }

@@ -205,6 +205,12 @@ static hipError_t launch_orb_desc(const uint8_t* blur, const float* kpts, const 
 // ---- entry points --------------------------------------------------------------------------------------------------------
 using namespace sbm;
 
+// The marks: kOrbBegin and kOrbMid around the compaction (it counts as descriptors), then per chunk before the blur, after it, after the descriptors.
+enum OrbStage { kOrbBlur, kOrbDesc, kOrbTotal, kOrbStageCount };
+enum OrbMark { kOrbBegin, kOrbMid, kOrbEnd, kOrbMarkCount };
+static const char* const kOrbNames[] = {"orb_blur", "orb_desc", "orb_total"};
+StageTable sbm::orb_stages() { return stage_table<kOrbStageCount, kOrbMarkCount>(kOrbNames); }
+
 extern "C" {
 
 void sbm_orb_params_default(sbm_orb_params* p) {
@@ -252,14 +258,14 @@ static int orb_check(int n, int width, int height, int cap, const void* d_kpts, 
 static int orb_run(sbm_handle* h, int n, const void* d_img, int width, int height, int cap, const void* d_kpts, const void* d_count,
                    const OrbOffsets& offs, const sbm_orb_params* p, void* d_kpts_out, void* d_count_out, void* d_desc,
                    void* d_blur, int sync) {
-  StageClock& clk = h->orb.clock;   // stages: blur, desc, total
-  HIPCHK(h, clk.start(h->profiling != 0));
+  StageClock& clk = h->orb.clock;
+  HIPCHK(h, clk.start(orb_stages(), h->profiling != 0));
   const int edge = p->edge_threshold;
-  HIPCHK(h, clk.mark(0, h->stream));
+  HIPCHK(h, clk.mark(kOrbBegin, h->stream));
   HIPCHK(h, launch_orb_compact((const float*)d_kpts, (const int*)d_count, (float*)d_kpts_out, (int*)d_count_out, n, cap, width,
                                height, edge, h->stream));
-  HIPCHK(h, clk.mark(1, h->stream));
-  HIPCHK(h, clk.add(1, 0, 1));
+  HIPCHK(h, clk.mark(kOrbMid, h->stream));
+  HIPCHK(h, clk.add(kOrbDesc, kOrbBegin, kOrbMid));
   if (width > 2 * edge && height > 2 * edge) {   // else every keypoint is gone and nothing needs the blur
     const int reading = env_switch("SBM_CV_READING", 0);
     const size_t plane = (size_t)width * height;
@@ -271,18 +277,18 @@ static int orb_run(sbm_handle* h, int n, const void* d_img, int width, int heigh
     for (int c0 = 0; c0 < n; c0 += chunk) {
       const int m = std::min(chunk, n - c0);
       uint8_t* bc = d_blur ? (uint8_t*)d_blur + plane * c0 : h->orb.blur.as<uint8_t>();
-      HIPCHK(h, clk.mark(0, h->stream));
+      HIPCHK(h, clk.mark(kOrbBegin, h->stream));
       HIPCHK(h, launch_orb_blur((const uint8_t*)d_img + plane * c0, bc, m, width, height, (reading & kReadOrbHalfUp) ? 1 : 0,
                                 h->stream));
-      HIPCHK(h, clk.mark(1, h->stream));
+      HIPCHK(h, clk.mark(kOrbMid, h->stream));
       HIPCHK(h, launch_orb_desc(bc, (const float*)d_kpts_out, (const int*)d_count_out, (uint8_t*)d_desc, c0, m, cap, width, height,
                                 offs, h->stream));
-      HIPCHK(h, clk.mark(2, h->stream));
-      HIPCHK(h, clk.add(0, 0, 1));
-      HIPCHK(h, clk.add(1, 1, 2));
+      HIPCHK(h, clk.mark(kOrbEnd, h->stream));
+      HIPCHK(h, clk.add(kOrbBlur, kOrbBegin, kOrbMid));
+      HIPCHK(h, clk.add(kOrbDesc, kOrbMid, kOrbEnd));
     }
   }
-  if (clk.on) clk.ms[2] = clk.ms[0] + clk.ms[1];
+  if (clk.on) clk.ms[kOrbTotal] = clk.ms[kOrbBlur] + clk.ms[kOrbDesc];
   if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
   return SBM_OK;
 }

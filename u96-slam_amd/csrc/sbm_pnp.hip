@@ -457,10 +457,14 @@ static int pnp_check(int n, int m, const int* jobs, int cap, const double* K, co
   return SBM_OK;
 }
 
+enum PnpStage { kPnpHyp, kPnpScore, kPnpRefine, kPnpTotal, kPnpStageCount };
+static const char* const kPnpNames[] = {"pnp_hyp", "pnp_score", "pnp_refine", "pnp_total"};
+StageTable pnp_stages() { return stage_table<kPnpStageCount, kPnpStageCount>(kPnpNames); }
+
 static int pnp_run(sbm_handle* h, int m, const int* jobs, const void* d_xyz, const void* d_kpts, const void* d_count, int cap,
                    const void* d_pairs, const void* d_npairs, const double* K, const sbm_stereo_model* model,
                    const sbm_pnp_params* p, void* d_result, void* d_inliers, void* d_hyp) {
-  StageClock& clk = h->pnp.clock;   // stages: pnp_hyp, pnp_score, pnp_refine, pnp_total
+  StageClock& clk = h->pnp.clock;
   PnpArgs a;
   memset(&a, 0, sizeof(a));
   for (int k = 0; k < 4; k++) a.K[k] = K[k];
@@ -485,7 +489,7 @@ static int pnp_run(sbm_handle* h, int m, const int* jobs, const void* d_xyz, con
     PnpJobs jb;
     memset(&jb, 0, sizeof(jb));
     for (int j = 0; j < k; j++) jb.j[j] = make_int2(jobs[2 * (j0 + j)], jobs[2 * (j0 + j) + 1]);
-    HIPCHK(h, clk.mark(0, h->stream));
+    HIPCHK(h, clk.mark(kPnpHyp, h->stream));
     hipLaunchKernelGGL(pnp_gather_kernel, dim3(k), dim3(kWave), 0, h->stream, (const float*)d_xyz, (const float*)d_kpts,
                        (const int*)d_count, (const int2*)d_pairs, (const int*)d_npairs, cap, j0, jb, iters, p->min_inliers,
                        scratch);
@@ -493,20 +497,18 @@ static int pnp_run(sbm_handle* h, int m, const int* jobs, const void* d_xyz, con
     hipLaunchKernelGGL(pnp_hyp_kernel, dim3((iters + kWave - 1) / kWave, k), dim3(kWave), 0, h->stream, cap, j0, iters,
                        p->min_inliers, a, scratch, (sbm_pnp_hypothesis*)d_hyp);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, clk.mark(1, h->stream));
+    HIPCHK(h, clk.mark(kPnpScore, h->stream));
     hipLaunchKernelGGL(pnp_score_kernel, dim3((iters + 3) / 4, k), dim3(256), 0, h->stream, cap, j0, iters, p->min_inliers, a,
                        scratch, (sbm_pnp_hypothesis*)d_hyp);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, clk.mark(2, h->stream));
+    HIPCHK(h, clk.mark(kPnpRefine, h->stream));
     hipLaunchKernelGGL(pnp_finish_kernel, dim3(k), dim3(kWave), 0, h->stream, (const float*)d_xyz, cap, j0, jb, a, scratch,
                        (sbm_pnp_result*)d_result, (int*)d_inliers);
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, clk.mark(3, h->stream));
-    HIPCHK(h, clk.add(0, 0, 1));
-    HIPCHK(h, clk.add(1, 1, 2));
-    HIPCHK(h, clk.add(2, 2, 3));
+    HIPCHK(h, clk.mark(kPnpTotal, h->stream));
+    for (int s = kPnpHyp; s < kPnpTotal; s++) HIPCHK(h, clk.add(s, s, s + 1));
   }
-  if (clk.on) clk.ms[3] = clk.ms[0] + clk.ms[1] + clk.ms[2];
+  if (clk.on) clk.ms[kPnpTotal] = clk.ms[kPnpHyp] + clk.ms[kPnpScore] + clk.ms[kPnpRefine];
   return SBM_OK;
 }
 
@@ -549,7 +551,7 @@ int sbm_estimate_motion_device(sbm_handle* h, int n, int m, const int* jobs, con
   if (st != SBM_OK) return st;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
-  HIPCHK(h, h->pnp.clock.start(h->profiling != 0));
+  HIPCHK(h, h->pnp.clock.start(pnp_stages(), h->profiling != 0));
   st = pnp_run(h, m, jobs, d_xyz, d_kpts, d_count, cap, d_pairs, d_npairs, K, model, p, d_result, d_inliers, d_hyp);
   if (st == SBM_OK && sync) HIPCHK(h, hipStreamSynchronize(h->stream));
   return st;
@@ -592,7 +594,7 @@ int sbm_estimate_motion(sbm_handle* h, const float* xyz_from, int nf, const floa
   }
   if (npairs > 0) HIPCHK(h, hipMemcpyAsync(d_pairs, pairs, (size_t)npairs * 8, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_n, cnt, sizeof(cnt), hipMemcpyHostToDevice, h->stream));
-  st = h->pnp.clock.start(h->profiling != 0) == hipSuccess ? SBM_OK : SBM_ERR_HIP;
+  st = h->pnp.clock.start(pnp_stages(), h->profiling != 0) == hipSuccess ? SBM_OK : SBM_ERR_HIP;
   if (st == SBM_OK) st = pnp_run(h, 1, job, d_xyz, d_kp, d_n, cap, d_pairs, d_n + 2, K, model, p, d_res, d_inl, nullptr);
   if (st != SBM_OK) {
     hipStreamSynchronize(h->stream);   // enqueued copies read the caller's arrays and `cnt`

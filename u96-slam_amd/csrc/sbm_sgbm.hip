@@ -362,6 +362,10 @@ static hipError_t launch_sgbm_fill(int16_t* dst, size_t count, int v, hipStream_
 // ---- entry points --------------------------------------------------------------------------------------------------------
 using namespace sbm;
 
+enum SgbmStage { kSgCost, kSgAggregate, kSgSelect, kSgMedian, kSgSpeckle, kSgTotal, kSgStageCount };
+static const char* const kSgbmNames[] = {"sgbm_cost", "sgbm_aggregate", "sgbm_select", "sgbm_median", "sgbm_speckle", "sgbm_total"};
+StageTable sbm::sgbm_stages() { return stage_table<kSgStageCount, kSgStageCount>(kSgbmNames); }
+
 extern "C" {
 
 void sbm_sgbm_params_default(sbm_sgbm_params* p, int min_disparity, int num_disparities, int block_size) {
@@ -438,8 +442,8 @@ int sbm_sgbm_compute_device(sbm_handle* h, const sbm_sgbm_params* p, int n, cons
   sgs.last_one_chunk = chunk == n;
   int16_t *C = sgs.C.as<int16_t>(), *S = sgs.S.as<int16_t>(), *pre = sgs.pre.as<int16_t>();
 
-  StageClock& clk = sgs.clock;   // stages: cost, aggregate, select, median, speckle, total
-  HIPCHK(h, clk.start(h->profiling != 0));
+  StageClock& clk = sgs.clock;
+  HIPCHK(h, clk.start(sgbm_stages(), h->profiling != 0));
   const uint8_t* dl = (const uint8_t*)d_left;
   const uint8_t* dr = (const uint8_t*)d_right;
   const int inv = (g.minD - 1) * 16;
@@ -449,24 +453,24 @@ int sbm_sgbm_compute_device(sbm_handle* h, const sbm_sgbm_params* p, int n, cons
     SgbmGeom gc = g;
     gc.n = std::min(chunk, n - c0);
     int16_t* out = (int16_t*)d_disp + (size_t)c0 * npix;
-    HIPCHK(h, clk.mark(0, h->stream));
+    HIPCHK(h, clk.mark(kSgCost, h->stream));
     if (pair_cs) {
       HIPCHK(h, launch_sgbm_cost(dl + (size_t)c0 * npix, dr + (size_t)c0 * npix, S, C, gc, h->stream));
-      HIPCHK(h, clk.mark(1, h->stream));
+      HIPCHK(h, clk.mark(kSgAggregate, h->stream));
       HIPCHK(h, launch_sgbm_paths(C, S, gc, h->stream));
-      HIPCHK(h, clk.mark(2, h->stream));
+      HIPCHK(h, clk.mark(kSgSelect, h->stream));
       HIPCHK(h, launch_sgbm_select(S, pre, gc, h->stream));
     } else {   // no computable column: every pixel is invalid (the median and the speckle filter keep it so)
-      HIPCHK(h, clk.mark(1, h->stream));
-      HIPCHK(h, clk.mark(2, h->stream));
+      HIPCHK(h, clk.mark(kSgAggregate, h->stream));
+      HIPCHK(h, clk.mark(kSgSelect, h->stream));
       HIPCHK(h, launch_sgbm_fill(pre, (size_t)gc.n * npix, inv, h->stream));
     }
-    HIPCHK(h, clk.mark(3, h->stream));
+    HIPCHK(h, clk.mark(kSgMedian, h->stream));
     if (g.reading & kReadSgbmNoMedian)
       HIPCHK(h, hipMemcpyAsync(out, pre, (size_t)gc.n * npix * sizeof(int16_t), hipMemcpyDeviceToDevice, h->stream));
     else
       HIPCHK(h, launch_sgbm_median(pre, out, gc.n, width, height, h->stream));
-    HIPCHK(h, clk.mark(4, h->stream));
+    HIPCHK(h, clk.mark(kSgSpeckle, h->stream));
     if (speckle) {
       // the block matcher's filter, with cv::StereoSGBM's arguments: newVal = (minD - 1) * 16, maxDiff = 16 * speckleRange (the
       // block matcher's own x16 reading bit does not apply here)
@@ -475,9 +479,9 @@ int sbm_sgbm_compute_device(sbm_handle* h, const sbm_sgbm_params* p, int n, cons
       sg.W = width; sg.H = height; sg.n = gc.n; sg.filtered = inv; sg.reading = 0;
       HIPCHK(h, launch_speckle(out, sgs.spk, sg, p->speckle_window_size, max_diff, h->stream));
     }
-    HIPCHK(h, clk.mark(5, h->stream));
-    for (int i = 0; i < 5; i++) HIPCHK(h, clk.add(i, i, i + 1));
-    HIPCHK(h, clk.add(5, 0, 5));
+    HIPCHK(h, clk.mark(kSgTotal, h->stream));
+    for (int s = kSgCost; s < kSgTotal; s++) HIPCHK(h, clk.add(s, s, s + 1));
+    HIPCHK(h, clk.add(kSgTotal, kSgCost, kSgTotal));
   }
   if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
   return SBM_OK;
