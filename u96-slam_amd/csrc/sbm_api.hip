@@ -17,7 +17,6 @@
 #include "sbm_handle.h"
 
 using namespace sbm;
-namespace sbm { thread_local char g_sad_kernel_name[96] = ""; }
 
 // The block matcher's stages as sbm_get_profile names them, and the marks sbm_compute_device records into one slot of the
 // handle's ring. "border" is never timed and reads 0: up to 256 disparities the clamped columns ride in the SAD launch.
@@ -256,6 +255,8 @@ int sbm_set_profiling(sbm_handle* h, int enabled) {
   return SBM_OK;
 }
 
+}  // extern "C"
+
 // cv getValidDisparityROI (calib3d stereosgbm.cpp) with cv::StereoBM's "empty rect = whole image" substitution.
 static void valid_roi(const sbm_params& p, int W, int H, int reading, int roi[4]) {
   int full[4] = {0, 0, W, H};
@@ -272,6 +273,79 @@ static void valid_roi(const sbm_params& p, int W, int H, int reading, int roi[4]
     roi[0] = roi[1] = roi[2] = roi[3] = 0;
   }
 }
+
+int sbm::bm_plan_geom(const sbm_params& p, int n, int width, int height, BmPlan* pl) {
+  const int st = sbm_params_validate(&p, width, height);
+  if (st != SBM_OK) return st;
+  if (n > 32767 || height > 65535) return SBM_ERR_UNSUPPORTED;
+  if (p.num_disparities > 4096) return SBM_ERR_UNSUPPORTED;
+  memset(pl, 0, sizeof(*pl));
+  Geom& g = pl->g;
+  g.W = width; g.H = height; g.n = n;
+  g.nd = p.num_disparities; g.mindisp = p.min_disparity; g.wsz = p.block_size; g.w2 = p.block_size / 2;
+  g.cap = p.prefilter_cap; g.tex = p.texture_threshold; g.uniq = p.uniqueness_ratio;
+  g.filtered = (p.min_disparity - 1) * 16;
+  g.lofs = std::max(g.nd - 1 + g.mindisp, 0);
+  g.rofs = -std::min(g.nd - 1 + g.mindisp, 0);
+  g.width1 = width - g.rofs - g.nd + 1;
+  g.xend = std::min(g.width1, width - g.lofs);
+  g.want_cost = p.disp12_max_diff >= 0;
+  // padded prefiltered planes: the fast kernel stages 16-byte pieces that may start up to nd+64 bytes left of
+  // column 0 and end up to 96 bytes right of column W-1
+  g.padl = ((g.nd + 64 + 63) / 64) * 64;
+  g.pitch = ((g.padl + width + 128 + 63) / 64) * 64;
+  g.plane = g.pitch * height;
+
+  int roi[4];
+  g.reading = env_switch("SBM_CV_READING", 0);
+  valid_roi(p, width, height, g.reading, roi);
+  g.row0 = std::max(roi[1], 0); g.row1 = std::min(roi[1] + roi[3], height);
+  g.col0 = std::max(std::min(roi[0], width), 0); g.col1 = std::max(std::min(roi[0] + roi[2], width), 0);
+  const bool range_fits = !(g.lofs >= width || g.rofs >= width || g.width1 < 1);
+  pl->any_rows = range_fits && roi[2] > 0 && roi[3] > 0 && g.row1 > g.row0;
+  if (!pl->any_rows) { g.row0 = g.row1 = 0; }
+  pl->in_envelope = pl->any_rows && sad_fast_supported(g);
+  return SBM_OK;
+}
+
+void sbm::bm_plan_launches(const sbm_params& p, bool inplace_ok, BmPlan* pl) {
+  Geom& g = pl->g;
+  pl->fast = pl->in_envelope && inplace_ok;
+  if (pl->fast) {
+    // 16-bit cost plane when every producer is a 16-bit-sum kernel (fast interior + border kernels, w/2 clamped columns on
+    // each side); the generic kernel needs int32
+    g.cost16 = 1;
+    g.pfshift = sad_fast_pfshift(g);   // pre-scaled planes for the interior kernel's tagged winner search
+    const int xhi = std::min(g.W - g.lofs - 1, g.W - g.rofs - g.nd);
+    const int fa = g.w2, fb = xhi - g.w2 + 1;   // the interior range the launch covers; xend - fb == w/2 by construction
+    // columns left and right of the fast range: clamped windows. They only matter if they can influence the output:
+    // through the LR check or when inside the valid ROI.
+    const bool borders_visible = g.want_cost || g.col0 < g.lofs + fa || g.col1 > g.lofs + fb;
+    // ... and then they ride in the interior launch as extra wavefronts (sbm_sad_border_wave.h): one SAD launch, one stream;
+    // beyond 256 disparities they come from the sliding-sum kernel in launches of their own
+    pl->border = borders_visible && sad_fast_borders_in_launch(g);
+    pl->wide_borders = borders_visible && !pl->border;
+    pl->sad = kSadFast;
+    sad_fast_plan(pl);
+    if (pl->wide_borders) { pl->wide_l[0] = 0; pl->wide_l[1] = pl->f.xc0; pl->wide_r[0] = pl->f.xc1; pl->wide_r[1] = g.xend; }
+  } else if (pl->any_rows) {
+    // (say so when the interior kernel was left out only because the in-place accumulate is off or its device self-test
+    // failed: 8-25x slower, see include/sbm.h)
+    const bool wide = sad_wide_supported(g) && env_switch("SBM_WIDE", 1);
+    pl->sad = wide ? kSadWide : kSadGeneric;
+    snprintf(pl->kernel, sizeof(pl->kernel), "%s",
+             !wide ? "sad_generic_kernel" : (pl->in_envelope ? "sad_wide_kernel [in-place accumulate unavailable]" : "sad_wide_kernel"));
+  }
+  pl->speckle = p.speckle_range >= 0 && p.speckle_window_size > 0;
+  if (pl->speckle) {
+    speckle_plan(g, p.speckle_window_size, p.speckle_range, &pl->spk);
+    size_t part[4];
+    SpeckleScratch::bytes(g.n, g.W, g.H, part);
+    for (int i = 0; i < 4; i++) pl->spk_bytes[i] = (long long)part[i];
+  }
+}
+
+extern "C" {
 
 static int ensure_scratch(sbm_handle* h, int n, int W, int H, int pitch, bool need_cost, bool need_speckle) {
   auto& s = h->bm;
@@ -323,68 +397,24 @@ int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_r
                        void* d_disp, int sync) {
   if (!h || !d_left || !d_right || !d_disp) return SBM_ERR_NULL;
   if (n <= 0) return SBM_ERR_BATCH;
-  int st = sbm_params_validate(&h->p, width, height);
-  if (st != SBM_OK) return st;
-  if (n > 32767 || height > 65535) return SBM_ERR_UNSUPPORTED;
   const sbm_params& p = h->p;
-  if (p.num_disparities > 4096) return SBM_ERR_UNSUPPORTED;
+  BmPlan pl;
+  const int st = bm_plan_geom(p, n, width, height, &pl);
+  if (st != SBM_OK) return st;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
-
-  Geom g;
-  memset(&g, 0, sizeof(g));
-  g.W = width; g.H = height; g.n = n;
-  g.nd = p.num_disparities; g.mindisp = p.min_disparity; g.wsz = p.block_size; g.w2 = p.block_size / 2;
-  g.cap = p.prefilter_cap; g.tex = p.texture_threshold; g.uniq = p.uniqueness_ratio;
-  g.filtered = (p.min_disparity - 1) * 16;
-  g.lofs = std::max(g.nd - 1 + g.mindisp, 0);
-  g.rofs = -std::min(g.nd - 1 + g.mindisp, 0);
-  g.width1 = width - g.rofs - g.nd + 1;
-  g.xend = std::min(g.width1, width - g.lofs);
-  g.want_cost = p.disp12_max_diff >= 0;
-  // padded prefiltered planes: the fast kernel stages 16-byte pieces that may start up to nd+64 bytes left of
-  // column 0 and end up to 96 bytes right of column W-1
-  g.padl = ((g.nd + 64 + 63) / 64) * 64;
-  g.pitch = ((g.padl + width + 128 + 63) / 64) * 64;
-  g.plane = g.pitch * height;
-  int16_t* out = (int16_t*)d_disp;
-
-  int roi[4];
-  g.reading = env_switch("SBM_CV_READING", 0);
-  valid_roi(p, width, height, g.reading, roi);
-  g.row0 = std::max(roi[1], 0); g.row1 = std::min(roi[1] + roi[3], height);
-  g.col0 = std::max(std::min(roi[0], width), 0); g.col1 = std::max(std::min(roi[0] + roi[2], width), 0);
-  const bool range_fits = !(g.lofs >= width || g.rofs >= width || g.width1 < 1);
-  const bool any_rows = range_fits && roi[2] > 0 && roi[3] > 0 && g.row1 > g.row0;
-  if (!any_rows) { g.row0 = g.row1 = 0; }
-  const bool speckle = p.speckle_range >= 0 && p.speckle_window_size > 0;
-
-  st = ensure_scratch(h, n, width, height, g.pitch, g.want_cost, speckle);
-  if (st != SBM_OK) return st;
-  h->last = g; h->have_last = true;
-
   // The interior kernel needs the in-place v_mqsad accumulate: its device self-test runs on this handle's stream, once per
   // device (a check that could not run fails this call with its HIP error and runs again on the next one). Without it the
   // sliding-sum kernel takes the whole envelope.
-  const bool in_envelope = any_rows && sad_fast_supported(g);
   bool inplace = false;
-  if (in_envelope) HIPCHK(h, mqsad_inplace_ok(h->stream, &inplace));
-  const bool fast = in_envelope && inplace;
-  // 16-bit cost plane when every producer is a 16-bit-sum kernel (fast interior + border kernels, w/2 clamped columns on
-  // each side); the generic kernel needs int32
-  int fa = 0, fb = 0;
-  if (fast) {
-    const int xhi = std::min(g.W - g.lofs - 1, g.W - g.rofs - g.nd);
-    fa = g.w2; fb = xhi - g.w2 + 1;   // the interior range launch_sad_fast covers; xend - fb == w/2 by construction
-    g.cost16 = 1;
-    g.pfshift = sad_fast_pfshift(g);   // pre-scaled planes for the interior kernel's tagged winner search
-  }
-  h->last = g;
-  // columns left and right of the fast range: clamped windows. They only matter if they can influence the output:
-  // through the LR check or when inside the valid ROI.
-  const bool borders_visible = g.want_cost || g.col0 < g.lofs + fa || g.col1 > g.lofs + fb;
-  // ... and then they ride in the interior launch as extra wavefronts (sbm_sad_border_wave.h): one SAD launch, one stream
-  const bool border = fast && borders_visible;
+  if (pl.in_envelope) HIPCHK(h, mqsad_inplace_ok(h->stream, &inplace));
+  bm_plan_launches(p, inplace, &pl);
+  const Geom& g = pl.g;
+  const int st2 = ensure_scratch(h, n, width, height, g.pitch, g.want_cost, pl.speckle);
+  if (st2 != SBM_OK) return st2;
+  h->last = g; h->have_last = true;
+  if (pl.any_rows) snprintf(h->last_kernel, sizeof(h->last_kernel), "%s", pl.kernel);
+
   // Stages run one after the other on the main stream. Overlapping LR + speckle of one sub-batch with the SAD kernel of
   // the next was built and measured in round 2 (profiles/r02_subbatch_pipeline.md; the code is in the history at commit
   // "Engine: device guard ..."): 1.47 ms -> 1.54 / 1.73 ms with 2 / 4 sub-batches, because four 126-VGPR wavefronts per
@@ -395,10 +425,11 @@ int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_r
   uint8_t *pf_l = h->bm.pf_l.as<uint8_t>(), *pf_r = h->bm.pf_r.as<uint8_t>();
   int16_t* disp_pre = h->bm.disp_pre.as<int16_t>();
   int32_t* cost = h->bm.cost.as<int32_t>();
+  int16_t* out = (int16_t*)d_disp;
 
   h->instr = h->profiling && h->ev_ok && (h->profiling != 3 || (h->ncall & 3u) == 0);
   mark(h, kBmBegin);
-  if (any_rows) {
+  if (pl.any_rows) {
     if (p.prefilter_type == SBM_PREFILTER_XSOBEL) {
       HIPCHK(h, launch_prefilter(dl, dr, pf_l, pf_r, g, h->stream));
     } else {
@@ -407,35 +438,38 @@ int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_r
     }
   }
   mark(h, kBmPrefiltered);
-  if (any_rows) {
-    if (fast) {
-      int xa = 0, xb = 0;
-      HIPCHK(h, launch_sad_fast(pf_l, pf_r, disp_pre, cost, g, &xa, &xb, border, h->stream));
-      snprintf(h->last_kernel, sizeof(h->last_kernel), "%s", g_sad_kernel_name);
-      if (border && !sad_fast_borders_in_launch(g)) {   // beyond 256 disparities: the clamped columns from the sliding-sum kernel
-        HIPCHK(h, launch_sad_wide(pf_l, pf_r, disp_pre, cost, g, 0, xa, h->stream));
-        HIPCHK(h, launch_sad_wide(pf_l, pf_r, disp_pre, cost, g, xb, g.xend, h->stream));
-      }
-    } else if (sad_wide_supported(g) && env_switch("SBM_WIDE", 1)) {
-      HIPCHK(h, launch_sad_wide(pf_l, pf_r, disp_pre, cost, g, 0, g.xend, h->stream));
-      // (say so when the interior kernel was left out only because the in-place accumulate is off or its device self-test
-      // failed: 8-25x slower, see include/sbm.h)
-      snprintf(h->last_kernel, sizeof(h->last_kernel), in_envelope ? "sad_wide_kernel [in-place accumulate unavailable]" : "sad_wide_kernel");
-    } else {
-      HIPCHK(h, launch_sad_generic(pf_l, pf_r, disp_pre, cost, g, 0, g.xend, h->stream));
-      snprintf(h->last_kernel, sizeof(h->last_kernel), "sad_generic_kernel");
+  if (pl.sad == kSadFast) {
+    HIPCHK(h, launch_sad_fast(pf_l, pf_r, disp_pre, cost, pl, h->stream));
+    if (pl.wide_borders) {   // beyond 256 disparities: the clamped columns from the sliding-sum kernel
+      HIPCHK(h, launch_sad_wide(pf_l, pf_r, disp_pre, cost, g, pl.wide_l[0], pl.wide_l[1], h->stream));
+      HIPCHK(h, launch_sad_wide(pf_l, pf_r, disp_pre, cost, g, pl.wide_r[0], pl.wide_r[1], h->stream));
     }
+  } else if (pl.sad == kSadWide) {
+    HIPCHK(h, launch_sad_wide(pf_l, pf_r, disp_pre, cost, g, 0, g.xend, h->stream));
+  } else if (pl.sad == kSadGeneric) {
+    HIPCHK(h, launch_sad_generic(pf_l, pf_r, disp_pre, cost, g, 0, g.xend, h->stream));
   }
   mark(h, kBmMatched);
   HIPCHK(h, launch_lrcheck(disp_pre, cost, out, h->bm.lr_keys.as<unsigned long long>(), g, p.disp12_max_diff, h->stream));
   mark(h, kBmChecked);
-  if (speckle)
-    HIPCHK(h, launch_speckle(out, h->bm.spk, g, p.speckle_window_size, p.speckle_range, h->stream));
+  if (pl.speckle) HIPCHK(h, launch_speckle(out, h->bm.spk, g, pl.spk, p.speckle_window_size, h->stream));
   mark(h, kBmEnd);
   if (h->instr) h->calls++;
   h->ncall++;
   if (sync || h->profiling == 1) HIPCHK(h, hipStreamSynchronize(h->stream));
   return SBM_OK;
+}
+
+// The plan of a call as sbm_compute_device would compute it for these parameters, given the in-place self-test's result: a copy
+// of BmPlan (sbm_common.h has the layout). No handle, no device. Not part of the public header: for the tests.
+int sbm_debug_plan(const sbm_params* p, int n, int width, int height, int inplace_ok, void* out, size_t out_bytes) {
+  if (!p || !out) return SBM_ERR_NULL;
+  if (out_bytes != sizeof(BmPlan)) return SBM_ERR_SIZE;
+  if (n <= 0) return SBM_ERR_BATCH;
+  BmPlan pl;
+  const int st = bm_plan(*p, n, width, height, inplace_ok != 0, &pl);
+  if (st == SBM_OK) memcpy(out, &pl, sizeof(pl));
+  return st;
 }
 
 int sbm_rect_map_device(sbm_handle* h, const sbm_rect_cam* cam, int width, int height, void* d_map, int sync) {

@@ -75,10 +75,55 @@ bool sad_wide_supported(const Geom& g);
 hipError_t launch_sad_wide(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* disp, int32_t* cost, const Geom& g, int xa, int xb,
                            hipStream_t s);
 
-// Fast path (interior columns, odd block sizes 5..31, up to 512 disparities, 16-bit sums: sad_fast_supported()). Outside its
-// envelope the launch does nothing and returns hipSuccess; *xa,*xb receive the column range it covered.
-// name of the SAD kernel instantiation of the calling thread's last launch (template tuple; sbm_last_kernel_name())
-extern thread_local char g_sad_kernel_name[96];
+// The plan of one sbm_compute_device call: everything the host decides before it launches anything, as plain data (no pointers,
+// no HIP types, no constructors), computed once per call by bm_plan() without a HIP call. The launchers execute it and recompute
+// nothing. sbm_debug_plan() (sbm_api.hip; not in include/sbm.h) copies it out as it stands, so the layout below IS that export's:
+// int32 words in declaration order (Geom's 26 first), the four scratch sizes as int64 (two words each, 8-byte aligned), the name
+// last. tests/test_bm_plan.py mirrors it with ctypes; the export refuses a mirror of another size.
+enum SadKernel { kSadNone = 0, kSadFast = 1, kSadWide = 2, kSadGeneric = 3 };
+struct FastPlan {            // the interior kernel's launch (sad_fast_plan, sbm_sad_fast.hip); zero unless BmPlan::fast
+  int xc0, xc1;              // interior centre columns [xc0,xc1) (relative to lofs); xc0 = w/2
+  int strips, strips3, nseg; // as FastArgs (sbm_sad_fast_core.h)
+  int segrow[66];
+  int split;                 // the disparities are spread over more, narrower wavefronts (launch_nd)
+  int uniq_plain;
+  int NDW, NWAVES, NTERM, PW, exact, dual;   // the instantiation sad_fast_kernel<NDW, NWAVES, NTERM, PW, exact, dual>
+  int bord, bnw, bseg, nbseg;                // the border jobs of the same launch, as FastArgs
+  int grid, block, lds;      // 1-D grid, threads per workgroup, dynamic LDS bytes
+};
+struct SpkPlan {             // the speckle filter's launches (speckle_plan, sbm_speckle.hip)
+  int lists;                 // band walk + record-driven kernels (else the four row-walking kernels; G, S, SW, nbands are 0 then)
+  int G, S, SW, nbands;      // rows per band, column segments per band and their width, bands per image
+  int max_diff;              // the effective maxDiff
+  int grid[4][2];            // x, y of the four launches in stream order (band / seam / count / apply, or runs / merge / count / apply)
+};
+struct BmPlan {
+  Geom g;
+  int any_rows;              // there is something to match (else every stage but the LR fill is skipped)
+  int in_envelope;           // any_rows and sad_fast_supported(): the call the in-place self-test is run for
+  int fast;                  // in_envelope and the in-place accumulate is available: the interior kernel runs
+  int border;                // the clamped border columns ride in the interior launch (visible, and up to 256 disparities)
+  int speckle;
+  int sad;                   // SadKernel
+  int wide_borders;          // beyond 256 disparities: the visible border columns [wide_l) and [wide_r) from launch_sad_wide
+  int wide_l[2], wide_r[2];
+  FastPlan f;
+  SpkPlan spk;
+  int spk_pad_;              // (keeps spk_bytes 8-byte aligned)
+  long long spk_bytes[4];    // SpeckleScratch::bytes: runs, nheads, seam, nseam (0 without the speckle filter)
+  char kernel[96];           // the SAD kernel's name as sbm_last_kernel_name reports it ("" when nothing is matched)
+};
+// Status codes of sbm_compute_device behind its null and batch checks, in its order; Geom, any_rows and in_envelope.
+int bm_plan_geom(const sbm_params& p, int n, int W, int H, BmPlan* pl);
+// The rest, once the result of mqsad_inplace_ok is known (it is only asked for calls in the envelope).
+void bm_plan_launches(const sbm_params& p, bool inplace_ok, BmPlan* pl);
+inline int bm_plan(const sbm_params& p, int n, int W, int H, bool inplace_ok, BmPlan* pl) {
+  const int st = bm_plan_geom(p, n, W, H, pl);
+  if (st == SBM_OK) bm_plan_launches(p, inplace_ok, pl);
+  return st;
+}
+
+// Fast path (interior columns, odd block sizes 5..31, up to 512 disparities, 16-bit sums: sad_fast_supported()).
 bool sad_fast_supported(const Geom& g);
 // device self-test behind the in-place v_mqsad accumulate, on stream s: *ok once it ran (cached per device); a HIP error when it
 // could not run (nothing cached)
@@ -86,10 +131,11 @@ hipError_t mqsad_inplace_ok(hipStream_t s, bool* ok);
 constexpr int kFastNdMax = 512;   // disparities the interior kernel takes (four cooperating 128-disparity wavefronts)
 bool sad_fast_borders_in_launch(const Geom& g);   // the clamped border columns ride in the interior launch (up to 256 disparities)
 int sad_fast_pfshift(const Geom& g);   // 2 or 1 when the interior kernel wants pre-scaled planes (see kPfBias), else 0
-// border: the w/2 clamped columns on each side of [xa,xb) are computed by extra wavefronts of the same launch
-// (sbm_sad_border_wave.h); without it the launch leaves them untouched.
-hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* disp, int32_t* cost, const Geom& g,
-                           int* xa, int* xb, bool border, hipStream_t s);
+// pl->f and the kernel's name for a call with pl->fast (g, border set): strips, row segments, layout, border jobs, grid and LDS
+void sad_fast_plan(BmPlan* pl);
+// The planned launch. With pl.border the w/2 clamped columns on each side of [xc0,xc1) are computed by extra wavefronts of the
+// same launch (sbm_sad_border_wave.h); without it the launch leaves them untouched.
+hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* disp, int32_t* cost, BmPlan& pl, hipStream_t s);
 
 // Left-right consistency (cv validateDisparity) + invalid rows/columns fill. Reads disp_pre/cost, writes disp_out.
 // Rows wider than kLrLdsCols keep their claim table in global memory: keys = n * H * W 64-bit words (lr_keys_bytes; null
@@ -103,6 +149,8 @@ hipError_t launch_lrcheck(const int16_t* disp_pre, const int32_t* cost, int16_t*
 
 // Speckle filter: launch_speckle and its scratch are in sbm_handle.h.
 constexpr int kSpkMaxSeg = 4, kSpkRecordPad = 288, kSpkSeamPad = 512;
+// The filter's launches for n maps of W x H (g.n, g.W, g.H; g.reading), cv's maxSpeckleSize and maxDiff.
+void speckle_plan(const Geom& g, int max_size, int max_diff, SpkPlan* k);
 
 // Stand-alone prefilter of dense images (either flavour) and the rectifier in front of it (sbm_rectify.hip).
 hipError_t launch_prefilter_dense(const uint8_t* d_src, uint8_t* d_dst, int n, int W, int H, int rtl, int cap,

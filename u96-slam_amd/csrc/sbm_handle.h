@@ -83,8 +83,9 @@ struct SpeckleScratch {
   }
 };
 
-// cv filterSpeckles as parallel connected components (union-find) on n maps of W x H (g.n, g.W, g.H), sc sized for them.
-hipError_t launch_speckle(int16_t* disp, const SpeckleScratch& sc, const Geom& g, int max_size, int max_diff, hipStream_t s);
+// cv filterSpeckles as parallel connected components (union-find) on n maps of W x H (g.n, g.W, g.H), sc sized for them: the
+// launches of speckle_plan(g, max_size, ...).
+hipError_t launch_speckle(int16_t* disp, const SpeckleScratch& sc, const Geom& g, const SpkPlan& k, int max_size, hipStream_t s);
 
 // The stages of one family: the names sbm_get_profile answers, and how many marks one call records. Each family's file (the
 // block matcher's is sbm_api.hip) has the names, next to the enums that index its stages and marks and the code that times them.

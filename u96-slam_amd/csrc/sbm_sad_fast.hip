@@ -41,8 +41,11 @@
 // Source layout: sbm_sad_fast_core.h (arguments, LDS carve-up, exchange plan, the per-row tail: winner search / uniqueness /
 // neighbours / sub-pixel), sbm_sad_fast_strip.h (the strip), sbm_sad_border_wave.h (the clamped border columns, extra wavefronts
 // of the same launch), sbm_sad_fast_kernel.h (kernel + layout choice), and this file: the host side -- envelope, device
-// self-test of the in-place accumulate, strips / row segments of a launch -- plus the kernels of the windows 15 and 21. The ~270
+// self-test of the in-place accumulate, the launch's part of the call's plan (sad_fast_plan: strips, row segments, split; launch_t
+// in sbm_sad_fast_kernel.h adds what depends on the instantiation) and the planned launch -- plus the kernels of the windows 15 and 21. The ~270
 // instantiations compile as four translation units side by side (this one, sbm_sad_fast_pw1 / _pw2 / _pw3.hip: the other windows).
+#include <string.h>
+
 #include "sbm_sad_fast_kernel.h"
 
 namespace sbm {
@@ -145,16 +148,21 @@ bool sad_fast_supported(const Geom& g) {
   return true;
 }
 
-hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* disp, int32_t* cost, const Geom& g,
-                           int* xa, int* xb, bool border, hipStream_t s) {
-  *xa = *xb = 0;
-  if (!sad_fast_supported(g)) return hipSuccess;
-  FastArgs a;
-  a.pf_l = pf_l; a.pf_r = pf_r; a.disp = disp; a.cost = g.want_cost ? reinterpret_cast<uint16_t*>(cost) : nullptr;
-  a.W = g.W; a.H = g.H; a.pitch = g.pitch; a.padl = g.padl; a.plane = g.plane;
-  a.nd = g.nd; a.mindisp = g.mindisp; a.lofs = g.lofs; a.rofs = g.rofs; a.tex = g.tex << g.pfshift; a.uniq = g.uniq;
-  a.filtered = g.filtered; a.capb = (g.cap << g.pfshift) + kPfBias; a.pfshift = g.pfshift;
-  a.row0 = g.row0; a.row1 = g.row1;
+// The window dispatch, for the plan (a == nullptr: launch_t fills it) and for the launch alike: the kernels of the windows 15 and
+// 21 are here, the others in sbm_sad_fast_pw1 / _pw2 / _pw3.hip.
+static hipError_t sad_fast_dispatch(BmPlan& pl, const FastArgs* a, hipStream_t s) {
+  switch (pl.g.wsz) {
+    case 15: return launch_nd<5, 3>(pl, a, s);
+    case 21: return launch_nd<7, 3>(pl, a, s);
+    default: return launch_sad_fast_pw1(pl, a, s);
+  }
+}
+
+// The interior launch of a call with pl->fast: strips, row segments, split, then -- through the window and layout dispatch, which
+// knows the per-instantiation constants -- the border jobs, grid, LDS and the kernel's name.
+void sad_fast_plan(BmPlan* pl) {
+  const Geom& g = pl->g;
+  FastPlan& a = pl->f;
   const int xhi = std::min(g.W - g.lofs - 1, g.W - g.rofs - g.nd);
   a.xc0 = g.w2; a.xc1 = xhi - g.w2 + 1;
   const int pw = g.wsz % 3 == 0 ? 3 : 1;
@@ -230,20 +238,31 @@ hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* di
     }
   }
   nseg = ns;
-  a.strips = strips; a.nseg = nseg; a.npairs = g.n;
+  a.strips = strips; a.nseg = nseg;
   {
     const long maxs = (long)g.wsz * g.wsz * 2 * g.cap;
     a.uniq_plain = 8 * ((maxs * g.uniq / 100 + 1) << g.pfshift) <= 65535;   // (8 registers per accumulator)
   }
-  const bool split = (long)strips * nseg * g.n < 1024;
-  hipError_t e;
-  switch (g.wsz) {
-    case 15: e = launch_nd<5, 3>(a, border, split, s); break;
-    case 21: e = launch_nd<7, 3>(a, border, split, s); break;
-    default: e = launch_sad_fast_pw1(a, g.wsz, border, split, s); break;   // the other windows: sbm_sad_fast_pw1 / _pw2 / _pw3.hip
-  }
-  *xa = a.xc0; *xb = a.xc1;
-  return e;
+  a.split = (long)strips * nseg * g.n < 1024;
+  sad_fast_dispatch(*pl, nullptr, nullptr);   // no arguments: the dispatch fills the plan
+}
+
+// The arguments of the planned launch.
+hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* disp, int32_t* cost, BmPlan& pl, hipStream_t s) {
+  const Geom& g = pl.g;
+  const FastPlan& f = pl.f;
+  FastArgs a;
+  a.pf_l = pf_l; a.pf_r = pf_r; a.disp = disp; a.cost = g.want_cost ? reinterpret_cast<uint16_t*>(cost) : nullptr;
+  a.W = g.W; a.H = g.H; a.pitch = g.pitch; a.padl = g.padl; a.plane = g.plane;
+  a.nd = g.nd; a.mindisp = g.mindisp; a.lofs = g.lofs; a.rofs = g.rofs; a.tex = g.tex << g.pfshift; a.uniq = g.uniq;
+  a.filtered = g.filtered; a.capb = (g.cap << g.pfshift) + kPfBias; a.pfshift = g.pfshift;
+  a.row0 = g.row0; a.row1 = g.row1;
+  static_assert(sizeof(a.segrow) == sizeof(f.segrow), "");
+  memcpy(a.segrow, f.segrow, sizeof(a.segrow));
+  a.strips = f.strips; a.nseg = f.nseg; a.npairs = g.n; a.strips3 = f.strips3; a.uniq_plain = f.uniq_plain;
+  a.xc0 = f.xc0; a.xc1 = f.xc1;
+  a.bord = f.bord; a.bnw = f.bnw; a.bseg = f.bseg; a.nbseg = f.nbseg;
+  return sad_fast_dispatch(pl, &a, s);
 }
 
 }  // namespace sbm

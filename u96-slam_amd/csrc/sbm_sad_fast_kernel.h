@@ -87,51 +87,64 @@ sad_fast_kernel(FastArgs a) {
 // column (a round-4 probe script, in git history: DESIGN.md section 6), and a chain may last kBorderChainShare of the launch.
 constexpr double kBorderModelRate = 3.6e12, kBorderRowUs = 2.0, kBorderColUs = 0.25, kBorderChainShare = 0.205;
 
+// One instantiation's part of the plan and its launch -- the one place that knows the per-instantiation constants (BorderLds<>::JW
+// and ::BYTES, DmaLds<>::WAVE_B, HAS_EXACT). a == nullptr: fill pl.f (border jobs, grid, LDS, instantiation) and the kernel's
+// name, launch nothing; otherwise launch what pl says with the arguments a (pl is only read).
 template <int NDW, int NWAVES, int NTERM, int PW>
-static hipError_t launch_t(FastArgs a, bool border, hipStream_t s) {
+static hipError_t launch_t(BmPlan& pl, const FastArgs* a, hipStream_t s) {
   constexpr bool DUAL = PW == 3;
-  // per wavefront the areas of DmaLds, then the workgroup's merge area
-  constexpr int WB1 = DmaLds<NDW, NWAVES, NTERM, PW, 1>::WAVE_B, WB3 = DmaLds<NDW, NWAVES, NTERM, PW, DUAL ? 3 : 1>::WAVE_B;
-  size_t lds = (size_t)NWAVES * (WB1 > WB3 ? WB1 : WB3) + (NWAVES > 1 ? (size_t)2 * NWAVES * 64 * (4 + 8) : 0);
-  a.bord = a.bnw = 0;
-  a.bseg = a.row1 - a.row0;
-  a.nbseg = 0;
-  if constexpr (NDW * NWAVES <= 256) if (border) {
-    // border wavefronts per segment: 2 sides x ceil(n / JW) groups of JW consecutive pairs, NWAVES of them per workgroup
-    using BL = BorderLds<(PW * NTERM) / 2, NDW * NWAVES>;
-    a.bnw = 2 * ((a.npairs + BL::JW - 1) / BL::JW);
-    a.bord = (a.bnw + NWAVES - 1) / NWAVES;
-    lds = std::max(lds, (size_t)NWAVES * BL::BYTES);
-    // A border wavefront is a serial chain of rows (~2 us + 0.25 us per output column and row, a quarter of that for each of
-    // its w-1 priming rows -- measured alone on the chip: kBorderRowUs, kBorderColUs); it must end well inside the launch, so the
-    // border jobs get their own, finer row segments: a chain of about a fifth of the launch's expected duration (640x480 nd 64
-    // w 21 x 64 pairs, where the border columns weigh most: 10 rows per segment 0.520 ms per step, 13 rows 0.537, 6 rows 0.533 --
-    // profiles/r04_border_bseg.txt; KITTI x 64 is flat between 32 and 96 rows).
-    const int rows = a.row1 - a.row0, wsz = PW * NTERM;
-    const double t_kernel_us = (double)a.npairs * a.W * rows * a.nd / kBorderModelRate * 1e6;
-    const double t_row_us = kBorderRowUs + kBorderColUs * (wsz / 2);
-    int bseg = (int)(kBorderChainShare * t_kernel_us / t_row_us - 0.25 * (wsz - 1));
-    bseg = std::max(4, std::min(bseg, rows));
-    a.nbseg = (rows + bseg - 1) / bseg;
-    a.bseg = (rows + a.nbseg - 1) / a.nbseg;
-    a.nbseg = (rows + a.bseg - 1) / a.bseg;
-  }
-  dim3 grid((unsigned)(a.bord * a.nbseg + a.strips * a.npairs * a.nseg));
   // (the masked-count kernels are right for every count up to NDW * NWAVES; <64,4> only runs one-pair calls beyond 192
   // disparities: its masked kernel serves 256 as well)
   // (three and four 128-disparity wavefronts, 257 .. 512 disparities: exact kernels for 384 and 512 -- 5-7 % over the masked ones,
   // profiles/r05_exact512.txt)
   constexpr bool HAS_EXACT = !(NDW == 64 && NWAVES == 4);
-  const bool exact = HAS_EXACT && a.nd == NDW * NWAVES;
-  snprintf(g_sad_kernel_name, sizeof(g_sad_kernel_name), "sad_fast_kernel<%d,%d,%d,%d,%s,%s> pfshift=%d",
-           NDW, NWAVES, NTERM, PW, exact ? "true" : "false", DUAL ? "true" : "false", a.pfshift);
+  if (!a) {
+    FastPlan& f = pl.f;
+    const Geom& g = pl.g;
+    // per wavefront the areas of DmaLds, then the workgroup's merge area
+    constexpr int WB1 = DmaLds<NDW, NWAVES, NTERM, PW, 1>::WAVE_B, WB3 = DmaLds<NDW, NWAVES, NTERM, PW, DUAL ? 3 : 1>::WAVE_B;
+    size_t lds = (size_t)NWAVES * (WB1 > WB3 ? WB1 : WB3) + (NWAVES > 1 ? (size_t)2 * NWAVES * 64 * (4 + 8) : 0);
+    f.bord = f.bnw = 0;
+    f.bseg = g.row1 - g.row0;
+    f.nbseg = 0;
+    if constexpr (NDW * NWAVES <= 256) if (pl.border) {
+      // border wavefronts per segment: 2 sides x ceil(n / JW) groups of JW consecutive pairs, NWAVES of them per workgroup
+      using BL = BorderLds<(PW * NTERM) / 2, NDW * NWAVES>;
+      f.bnw = 2 * ((g.n + BL::JW - 1) / BL::JW);
+      f.bord = (f.bnw + NWAVES - 1) / NWAVES;
+      lds = std::max(lds, (size_t)NWAVES * BL::BYTES);
+      // A border wavefront is a serial chain of rows (~2 us + 0.25 us per output column and row, a quarter of that for each of
+      // its w-1 priming rows -- measured alone on the chip: kBorderRowUs, kBorderColUs); it must end well inside the launch, so the
+      // border jobs get their own, finer row segments: a chain of about a fifth of the launch's expected duration (640x480 nd 64
+      // w 21 x 64 pairs, where the border columns weigh most: 10 rows per segment 0.520 ms per step, 13 rows 0.537, 6 rows 0.533 --
+      // profiles/r04_border_bseg.txt; KITTI x 64 is flat between 32 and 96 rows).
+      const int rows = g.row1 - g.row0, wsz = PW * NTERM;
+      const double t_kernel_us = (double)g.n * g.W * rows * g.nd / kBorderModelRate * 1e6;
+      const double t_row_us = kBorderRowUs + kBorderColUs * (wsz / 2);
+      int bseg = (int)(kBorderChainShare * t_kernel_us / t_row_us - 0.25 * (wsz - 1));
+      bseg = std::max(4, std::min(bseg, rows));
+      f.nbseg = (rows + bseg - 1) / bseg;
+      f.bseg = (rows + f.nbseg - 1) / f.nbseg;
+      f.nbseg = (rows + f.bseg - 1) / f.bseg;
+    }
+    f.grid = f.bord * f.nbseg + f.strips * g.n * f.nseg;
+    f.block = 64 * NWAVES;
+    f.lds = (int)lds;
+    f.NDW = NDW; f.NWAVES = NWAVES; f.NTERM = NTERM; f.PW = PW; f.dual = DUAL;
+    f.exact = HAS_EXACT && g.nd == NDW * NWAVES;
+    snprintf(pl.kernel, sizeof(pl.kernel), "sad_fast_kernel<%d,%d,%d,%d,%s,%s> pfshift=%d",
+             NDW, NWAVES, NTERM, PW, f.exact ? "true" : "false", DUAL ? "true" : "false", g.pfshift);
+    return hipSuccess;
+  }
+  const dim3 grid((unsigned)pl.f.grid);
+  const size_t lds = (size_t)pl.f.lds;
   if constexpr (HAS_EXACT) {
-    if (exact) {
-      hipLaunchKernelGGL((sad_fast_kernel<NDW, NWAVES, NTERM, PW, true, DUAL>), grid, dim3(64 * NWAVES), lds, s, a);
+    if (pl.f.exact) {
+      hipLaunchKernelGGL((sad_fast_kernel<NDW, NWAVES, NTERM, PW, true, DUAL>), grid, dim3(64 * NWAVES), lds, s, *a);
       return hipGetLastError();
     }
   }
-    hipLaunchKernelGGL((sad_fast_kernel<NDW, NWAVES, NTERM, PW, false, DUAL>), grid, dim3(64 * NWAVES), lds, s, a);
+    hipLaunchKernelGGL((sad_fast_kernel<NDW, NWAVES, NTERM, PW, false, DUAL>), grid, dim3(64 * NWAVES), lds, s, *a);
   return hipGetLastError();
 }
 
@@ -142,22 +155,24 @@ static hipError_t launch_t(FastArgs a, bool border, hipStream_t s) {
 // disparities to carry (1080p nd 192: 2.09 against 2.51 ms; profiles/r04_dma_nd.txt). `split`: launches that cannot fill the chip
 // (one pair per call) spread the disparities over two to four narrower wavefronts instead -- half the serial work per row.
 template <int NTERM, int PW>
-static hipError_t launch_nd(const FastArgs& a, bool border, bool split, hipStream_t s) {
-  if (a.nd > 384) return launch_t<128, 4, NTERM, PW>(a, border, s);
-  if (a.nd > 256) return launch_t<128, 3, NTERM, PW>(a, border, s);
-  if (a.nd <= 32) return launch_t<32, 1, NTERM, PW>(a, border, s);
-  if (a.nd <= 64) return split ? launch_t<32, 2, NTERM, PW>(a, border, s) : launch_t<64, 1, NTERM, PW>(a, border, s);
-  if (!split && a.nd <= 128) return launch_t<128, 1, NTERM, PW>(a, border, s);
-  if (!split && a.nd != 192) return launch_t<128, 2, NTERM, PW>(a, border, s);
-  if (a.nd <= 128) return launch_t<64, 2, NTERM, PW>(a, border, s);
-  if (a.nd <= 192) return launch_t<64, 3, NTERM, PW>(a, border, s);
-  return launch_t<64, 4, NTERM, PW>(a, border, s);
+static hipError_t launch_nd(BmPlan& pl, const FastArgs* a, hipStream_t s) {
+  const int nd = pl.g.nd;
+  const bool split = pl.f.split;
+  if (nd > 384) return launch_t<128, 4, NTERM, PW>(pl, a, s);
+  if (nd > 256) return launch_t<128, 3, NTERM, PW>(pl, a, s);
+  if (nd <= 32) return launch_t<32, 1, NTERM, PW>(pl, a, s);
+  if (nd <= 64) return split ? launch_t<32, 2, NTERM, PW>(pl, a, s) : launch_t<64, 1, NTERM, PW>(pl, a, s);
+  if (!split && nd <= 128) return launch_t<128, 1, NTERM, PW>(pl, a, s);
+  if (!split && nd != 192) return launch_t<128, 2, NTERM, PW>(pl, a, s);
+  if (nd <= 128) return launch_t<64, 2, NTERM, PW>(pl, a, s);
+  if (nd <= 192) return launch_t<64, 3, NTERM, PW>(pl, a, s);
+  return launch_t<64, 4, NTERM, PW>(pl, a, s);
 }
 
 // window dispatch of the other translation units (each holds the kernels of its windows; an unknown window falls through to the
-// next unit and ends as hipErrorInvalidValue)
-hipError_t launch_sad_fast_pw1(const FastArgs& a, int wsz, bool border, bool split, hipStream_t s);   // sbm_sad_fast_pw1.hip: 5, 7, 9, 11, 13
-hipError_t launch_sad_fast_pw2(const FastArgs& a, int wsz, bool border, bool split, hipStream_t s);   // sbm_sad_fast_pw2.hip: 17, 19, 23, 25
-hipError_t launch_sad_fast_pw3(const FastArgs& a, int wsz, bool border, bool split, hipStream_t s);   // sbm_sad_fast_pw3.hip: 27, 29, 31
+// next unit and ends as hipErrorInvalidValue). As launch_t: a == nullptr fills the plan, otherwise the planned launch.
+hipError_t launch_sad_fast_pw1(BmPlan& pl, const FastArgs* a, hipStream_t s);   // sbm_sad_fast_pw1.hip: 5, 7, 9, 11, 13
+hipError_t launch_sad_fast_pw2(BmPlan& pl, const FastArgs* a, hipStream_t s);   // sbm_sad_fast_pw2.hip: 17, 19, 23, 25
+hipError_t launch_sad_fast_pw3(BmPlan& pl, const FastArgs* a, hipStream_t s);   // sbm_sad_fast_pw3.hip: 27, 29, 31
 
 }  // namespace sbm

@@ -5,14 +5,14 @@
 
 namespace sbm {
 
-hipError_t launch_sad_fast_pw1(const FastArgs& a, int wsz, bool border, bool split, hipStream_t s) {
-  switch (wsz) {
-    case 9: return launch_nd<3, 3>(a, border, split, s);
-    case 5: return launch_nd<5, 1>(a, border, split, s);
-    case 7: return launch_nd<7, 1>(a, border, split, s);
-    case 11: return launch_nd<11, 1>(a, border, split, s);
-    case 13: return launch_nd<13, 1>(a, border, split, s);
-    default: return launch_sad_fast_pw2(a, wsz, border, split, s);
+hipError_t launch_sad_fast_pw1(BmPlan& pl, const FastArgs* a, hipStream_t s) {
+  switch (pl.g.wsz) {
+    case 9: return launch_nd<3, 3>(pl, a, s);
+    case 5: return launch_nd<5, 1>(pl, a, s);
+    case 7: return launch_nd<7, 1>(pl, a, s);
+    case 11: return launch_nd<11, 1>(pl, a, s);
+    case 13: return launch_nd<13, 1>(pl, a, s);
+    default: return launch_sad_fast_pw2(pl, a, s);
   }
 }
 

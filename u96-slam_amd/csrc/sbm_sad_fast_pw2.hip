@@ -5,13 +5,13 @@
 
 namespace sbm {
 
-hipError_t launch_sad_fast_pw2(const FastArgs& a, int wsz, bool border, bool split, hipStream_t s) {
-  switch (wsz) {
-    case 17: return launch_nd<17, 1>(a, border, split, s);
-    case 19: return launch_nd<19, 1>(a, border, split, s);
-    case 23: return launch_nd<23, 1>(a, border, split, s);
-    case 25: return launch_nd<25, 1>(a, border, split, s);
-    default: return launch_sad_fast_pw3(a, wsz, border, split, s);
+hipError_t launch_sad_fast_pw2(BmPlan& pl, const FastArgs* a, hipStream_t s) {
+  switch (pl.g.wsz) {
+    case 17: return launch_nd<17, 1>(pl, a, s);
+    case 19: return launch_nd<19, 1>(pl, a, s);
+    case 23: return launch_nd<23, 1>(pl, a, s);
+    case 25: return launch_nd<25, 1>(pl, a, s);
+    default: return launch_sad_fast_pw3(pl, a, s);
   }
 }
 

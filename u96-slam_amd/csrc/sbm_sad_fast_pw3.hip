@@ -5,11 +5,11 @@
 
 namespace sbm {
 
-hipError_t launch_sad_fast_pw3(const FastArgs& a, int wsz, bool border, bool split, hipStream_t s) {
-  switch (wsz) {
-    case 27: return launch_nd<9, 3>(a, border, split, s);
-    case 29: return launch_nd<29, 1>(a, border, split, s);
-    case 31: return launch_nd<31, 1>(a, border, split, s);
+hipError_t launch_sad_fast_pw3(BmPlan& pl, const FastArgs* a, hipStream_t s) {
+  switch (pl.g.wsz) {
+    case 27: return launch_nd<9, 3>(pl, a, s);
+    case 29: return launch_nd<29, 1>(pl, a, s);
+    case 31: return launch_nd<31, 1>(pl, a, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -477,7 +477,9 @@ int sbm_sgbm_compute_device(sbm_handle* h, const sbm_sgbm_params* p, int n, cons
       Geom sg;
       memset(&sg, 0, sizeof(sg));
       sg.W = width; sg.H = height; sg.n = gc.n; sg.filtered = inv; sg.reading = 0;
-      HIPCHK(h, launch_speckle(out, sgs.spk, sg, p->speckle_window_size, max_diff, h->stream));
+      SpkPlan k;
+      speckle_plan(sg, p->speckle_window_size, max_diff, &k);
+      HIPCHK(h, launch_speckle(out, sgs.spk, sg, k, p->speckle_window_size, h->stream));
     }
     HIPCHK(h, clk.mark(kSgTotal, h->stream));
     for (int s = kSgCost; s < kSgTotal; s++) HIPCHK(h, clk.add(s, s, s + 1));

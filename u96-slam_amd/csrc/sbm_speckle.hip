@@ -924,14 +924,10 @@ size_t SpeckleScratch::bytes(int n, int W, int H, size_t* part) {
   return b[0] + b[1] + b[2] + b[3];
 }
 
-hipError_t launch_speckle(int16_t* disp, const SpeckleScratch& sc, const Geom& g, int max_size, int max_diff, hipStream_t s) {
-  void* runs = sc.runs.p;
-  int32_t* nheads = sc.nheads.as<int32_t>();
-  uint32_t* seam = sc.seam.as<uint32_t>();
-  int32_t* nseam = sc.nseam.as<int32_t>();
-  dim3 grid((g.H + 3) / 4, g.n);
+void speckle_plan(const Geom& g, int max_size, int max_diff, SpkPlan* k) {
+  memset(k, 0, sizeof(*k));
   if (g.reading & kReadSpeckleX16) max_diff = (int)std::min<long>((long)max_diff * 16, 1L << 17);
-  max_diff = std::min(max_diff, 1 << 17);   // int16 values: any larger range joins everything alike
+  k->max_diff = std::min(max_diff, 1 << 17);   // int16 values: any larger range joins everything alike
   // Two implementations. Default: band walk (runs + merge in one pass, G rows per wavefront) + seam unions,
   // then count and apply driven by the rows' run records (16-bit run indices: W <= 65535; 32-bit byte offsets within an image's
   // record plane). Fallback (SBM_SPECKLE_LISTS=0 or SBM_SPECKLE_BAND=0, or outside those limits): four kernels that each walk
@@ -940,46 +936,62 @@ hipError_t launch_speckle(int16_t* disp, const SpeckleScratch& sc, const Geom& g
   const int lists_env = env_switch("SBM_SPECKLE_LISTS", 1);
   const int band_env = env_switch("SBM_SPECKLE_BAND", -1);
   // (maxSpeckleSize beyond kSpkMaxSize: the row-walking kernels -- see the count kernel's size sums)
-  const bool lists = nheads && seam && nseam && g.W <= 65535 && ((long)g.W + kSpkRecordPad) * g.H < (1L << 27) && max_size <= kSpkMaxSize &&
-                     lists_env != 0 && band_env != 0;
-  if (lists) {
+  k->lists = g.W <= 65535 && ((long)g.W + kSpkRecordPad) * g.H < (1L << 27) && max_size <= kSpkMaxSize && lists_env != 0 && band_env != 0;
+  if (!k->lists) {
+    for (auto& gr : k->grid) { gr[0] = (g.H + 3) / 4; gr[1] = g.n; }
+    return;
+  }
+  // 4 rows per wavefront once that still leaves ~6 000 band wavefronts (6 per SIMD), else 2: the walk of a band is a serial
+  // chain and the look-ahead row costs 1/G (profiles/r06_speckle.md; 8 rows never won). SBM_SPECKLE_BAND=2/4 forces a height.
+  int G = (long)g.n * g.H >= 24000 ? 4 : 2;
+  if (band_env == 2 || band_env == 4) G = band_env;
+  const int nbands = (g.H + G - 1) / G;
+  // Column segments per band (wavefronts of one workgroup): the walk of a band is a serial chain, so launches that leave the
+  // chip room are cut finer. SBM_SPECKLE_SEG=1/2/4 forces a count.
+  const int nchunks = (g.W + 63) / 64;
+  const long pairs_of_rows = (long)g.n * ((g.H + 1) / 2);
+  int S = pairs_of_rows < kSpkSeg4 ? 4 : (pairs_of_rows < kSpkSeg2 ? 2 : 1);
+  const int seg_env = env_switch("SBM_SPECKLE_SEG", 0);
+  if (seg_env == 1 || seg_env == 2 || seg_env == 4) S = seg_env;
+  while (S > 1 && nchunks < S) S >>= 1;
+  k->G = G; k->S = S; k->nbands = nbands;
+  k->SW = 64 * ((nchunks + S - 1) / S);
+  static_assert(kSpkWaves == 4, "the band walk's grid is the seam kernel's");
+  k->grid[0][0] = k->grid[1][0] = (nbands * S + 3) / 4;
+  k->grid[2][0] = k->grid[3][0] = (g.H * S + 3) / 4;
+  for (auto& gr : k->grid) gr[1] = g.n;
+}
+
+hipError_t launch_speckle(int16_t* disp, const SpeckleScratch& sc, const Geom& g, const SpkPlan& k, int max_size, hipStream_t s) {
+  void* runs = sc.runs.p;
+  int32_t* nheads = sc.nheads.as<int32_t>();
+  uint32_t* seam = sc.seam.as<uint32_t>();
+  int32_t* nseam = sc.nseam.as<int32_t>();
+  const int max_diff = k.max_diff, newval = g.filtered;
+  auto grid = [&](int i) { return dim3(k.grid[i][0], k.grid[i][1]); };
+  if (k.lists) {
     SpkRun* R = static_cast<SpkRun*>(runs);
-    // 4 rows per wavefront once that still leaves ~6 000 band wavefronts (6 per SIMD), else 2: the walk of a band is a serial
-    // chain and the look-ahead row costs 1/G (profiles/r06_speckle.md; 8 rows never won). SBM_SPECKLE_BAND=2/4 forces a height.
-    int G = (long)g.n * g.H >= 24000 ? 4 : 2;
-    if (band_env == 2 || band_env == 4) G = band_env;
-    const int nbands = (g.H + G - 1) / G;
-    // Column segments per band (wavefronts of one workgroup): the walk of a band is a serial chain, so launches that leave the
-    // chip room are cut finer. SBM_SPECKLE_SEG=1/2/4 forces a count.
-    const int nchunks = (g.W + 63) / 64;
-    const long pairs_of_rows = (long)g.n * ((g.H + 1) / 2);
-    int S = pairs_of_rows < kSpkSeg4 ? 4 : (pairs_of_rows < kSpkSeg2 ? 2 : 1);
-    const int seg_env = env_switch("SBM_SPECKLE_SEG", 0);
-    if (seg_env == 1 || seg_env == 2 || seg_env == 4) S = seg_env;
-    while (S > 1 && nchunks < S) S >>= 1;
-    dim3 bgrid((nbands * S + 3) / 4, g.n), vgrid((g.H * S + 3) / 4, g.n);
-    const int SW = 64 * ((nchunks + S - 1) / S), newval = g.filtered;
     auto launch = [&](auto seg) {
       constexpr int SS = decltype(seg)::value;
-      const SpkLayout<SS> lay{SW};
-      const dim3 wgrid((nbands * SS + kSpkWaves - 1) / kSpkWaves, g.n), wblock(64 * kSpkWaves);
-      if (G == 4) hipLaunchKernelGGL((speckle_band_kernel<4, SS>), wgrid, wblock, 0, s, disp, R, nheads, seam, nseam, lay, g.W, g.H, newval, max_diff);
-      else hipLaunchKernelGGL((speckle_band_kernel<2, SS>), wgrid, wblock, 0, s, disp, R, nheads, seam, nseam, lay, g.W, g.H, newval, max_diff);
-      hipLaunchKernelGGL(speckle_seam_kernel<SS>, bgrid, dim3(256), 0, s, R, seam, nseam, lay, g.H, G, max_size);
-      hipLaunchKernelGGL(speckle_count_list_kernel<SS>, vgrid, dim3(256), 0, s, R, nheads, lay, g.H, max_size);
-      hipLaunchKernelGGL(speckle_apply_list_kernel<SS>, vgrid, dim3(256), 0, s, disp, R, nheads, lay, g.W, g.H, newval, max_size);
+      const SpkLayout<SS> lay{k.SW};
+      const dim3 wblock(64 * kSpkWaves);
+      if (k.G == 4) hipLaunchKernelGGL((speckle_band_kernel<4, SS>), grid(0), wblock, 0, s, disp, R, nheads, seam, nseam, lay, g.W, g.H, newval, max_diff);
+      else hipLaunchKernelGGL((speckle_band_kernel<2, SS>), grid(0), wblock, 0, s, disp, R, nheads, seam, nseam, lay, g.W, g.H, newval, max_diff);
+      hipLaunchKernelGGL(speckle_seam_kernel<SS>, grid(1), dim3(256), 0, s, R, seam, nseam, lay, g.H, k.G, max_size);
+      hipLaunchKernelGGL(speckle_count_list_kernel<SS>, grid(2), dim3(256), 0, s, R, nheads, lay, g.H, max_size);
+      hipLaunchKernelGGL(speckle_apply_list_kernel<SS>, grid(3), dim3(256), 0, s, disp, R, nheads, lay, g.W, g.H, newval, max_size);
     };
-    if (S == 4) launch(std::integral_constant<int, 4>{});
-    else if (S == 2) launch(std::integral_constant<int, 2>{});
+    if (k.S == 4) launch(std::integral_constant<int, 4>{});
+    else if (k.S == 2) launch(std::integral_constant<int, 2>{});
     else launch(std::integral_constant<int, 1>{});
   } else {
     int* labels = static_cast<int*>(runs);
     int* counts = labels + (size_t)g.n * g.W * g.H;
-    hipLaunchKernelGGL(speckle_runs_kernel, grid, dim3(256), 0, s, disp, labels, counts, g.W, g.H, g.filtered, max_diff);
-    hipLaunchKernelGGL(speckle_merge_kernel, grid, dim3(256), 0, s, disp, labels, g.W, g.H, g.filtered, max_diff);
-    hipLaunchKernelGGL(speckle_count_kernel, grid, dim3(256), 0, s, disp, labels, counts, g.W, g.H, g.filtered, max_diff,
+    hipLaunchKernelGGL(speckle_runs_kernel, grid(0), dim3(256), 0, s, disp, labels, counts, g.W, g.H, newval, max_diff);
+    hipLaunchKernelGGL(speckle_merge_kernel, grid(1), dim3(256), 0, s, disp, labels, g.W, g.H, newval, max_diff);
+    hipLaunchKernelGGL(speckle_count_kernel, grid(2), dim3(256), 0, s, disp, labels, counts, g.W, g.H, newval, max_diff,
                        max_size);
-    hipLaunchKernelGGL(speckle_apply_kernel, grid, dim3(256), 0, s, disp, labels, counts, g.W, g.H, g.filtered, max_diff,
+    hipLaunchKernelGGL(speckle_apply_kernel, grid(3), dim3(256), 0, s, disp, labels, counts, g.W, g.H, newval, max_diff,
                        max_size);
   }
   return hipGetLastError();
