@@ -118,7 +118,8 @@ enum {
   SBM_ERR_NOMEM = -22,           /* device or host allocation failed                                  */
   SBM_ERR_UNSUPPORTED = -23,     /* valid OpenCV parameters this build cannot run (documented limits) */
   SBM_ERR_BATCH = -24,           /* batch count <= 0                                                  */
-  SBM_ERR_OCC_FULL = -25         /* occupancy map: points found the table full (see sbm_occ_overflow) */
+  SBM_ERR_OCC_FULL = -25,        /* occupancy map: points found the table full (see sbm_occ_overflow) */
+  SBM_ERR_VWD_FULL = -26         /* visual-word dictionary: a call's new words did not fit (sbm_vwd_overflow) */
 };
 
 #define SBM_PREFILTER_NORMALIZED_RESPONSE 0
@@ -1040,6 +1041,100 @@ int sbm_occ_fetch(sbm_occ_map* map, uint64_t* keys, uint32_t* hits, size_t cap, 
  * SBM_ERR_NULL, SBM_ERR_SIZE (resolution, or a key above 48 bits), SBM_ERR_NOMEM, SBM_ERR_UNSUPPORTED (the file cannot be
  * written). */
 int sbm_occ_write_binary(const uint64_t* keys, size_t n, double resolution, const char* path);
+
+/* ---- visual-word dictionary: addNewWords, computeLikelihood, limitKeypoints ---------------------------------------------------
+ * The reference's loop-closure thread, started by Mapper::process for each key frame: addWordIds -> VWDictionary::addNewWords
+ * (src/slam/src/core/Mapper.cpp:413-484, VWDictionary.cpp:40-115) and detectLoopClosure -> computeLikelihood
+ * (Mapper.cpp:536-677). The only stage whose cost grows with the run: up to 750 descriptors per key frame are searched against
+ * a dictionary that gains up to 750 words per key frame.
+ *  EXACT WHERE THE REFERENCE APPROXIMATES. The reference searches with FLANN, four randomised kd-trees and 32 checks; the answer
+ *  depends on its random trees and is not reproduced. The search here is exhaustive: every query is compared with every word.
+ *  That is the answer FLANN's converges to as its checks grow. No comparison against FLANN is made.
+ *  addNewWords(descriptors, nodeId), as defined here:
+ *   1 all n rows are searched, 2-NN, against the dictionary as it was BEFORE the call; words added by earlier rows of the same
+ *     call are not seen by later rows;
+ *   2 row i is unique if fewer than two neighbours came back, or if (float)d0 > nndr * (float)d1 -- one float multiply, one float
+ *     compare, not contracted;
+ *   3 a unique row becomes a new word; its id is the next integer, counting from 0, in row order (the id is the word's index in
+ *     the store); it gets one reference (nodeId, 1);
+ *   4 a row that is not unique calls addRef(nodeId) on its nearest word: that word's count for this node is incremented, or
+ *     (nodeId, 1) inserted;
+ *   5 the word id of every row is returned, in row order.
+ *  The metric. FlannIndex builds flann::Index<flann::L1<float>> over the bytes converted to float and searches through a pointer
+ *  cast to Index<L2<float>> (FlannIndex.cpp:51,92); the object that answers is the L1 one. SBM_VWD_L1, the default, is the sum of
+ *  absolute byte differences (<= 8160); SBM_VWD_L2 is the sum of squared byte differences (<= 2 080 800). Both are exact in float;
+ *  they are computed in integers and converted once for the NNDR test.
+ *  Defined where the reference is not: neighbours are ordered by (distance, dictionary index), so of two equally distant words
+ *  the older one ranks first and a row that is not unique goes to that word; a dictionary of one word gives every row fewer
+ *  than two neighbours, so every row is unique (the reference reads an unset index there); node_id < 1 is an invalid value
+ *  (SBM_ERR_UNSUPPORTED): the reference's VisualWord constructor silently adds no reference for node 0.
+ *  Store. sbm_vwd is created from a handle with a fixed capacity in words (1 .. 2^26) and uses that handle's stream, scratch and
+ *  stage clock; it must be destroyed before the handle and serves one thread at a time. Device state: 32 bytes and one squared
+ *  norm per word, the size, a counter of refused calls. A call whose new words would pass the capacity adds NOTHING (no word, no
+ *  reference, no node), returns SBM_ERR_VWD_FULL and raises sbm_vwd_overflow by one. Host state: per word its references
+ *  (node -> count), per node its word ids in row order and ni, its keypoint count including the ones cut by the limit
+ *  (n_keypoints_total >= n). Calls that name the same node again extend its word list and add to its ni.
+ *  Kernels. Search: one wavefront per (64-query tile, dictionary slice); slices = params.slices, or with 0 as many as give the
+ *  launch about 4096 wavefronts; slice s covers words [s * R, (s + 1) * R) with R = 64 * ceil(ceil(N / 64) / slices), and empty
+ *  slices are dropped. Decide: merges the slices in dictionary order and takes the uniqueness decision. Append: a prefix scan
+ *  over the unique flags in row order places row i at size + rank. Searches read rows < size, the append writes rows >= size.
+ *  2-NN record: four int32 (i0, d0, i1, d1), i = -1 and d = SBM_VWD_NONE where there is no such neighbour.
+ *  computeLikelihood, reproduced as written: the distinct word ids of the query node are walked in ascending order; ids <= 0 are
+ *  skipped (the very first word, id 0; the reference's negative ids of cut keypoints never reach the store and count only in
+ *  ni); logNnw = log10f(N / nw), N = (float)n_nodes the caller's total node count, nw the number of nodes that reference the
+ *  word; a zero logNnw is skipped; for each referencing node that is in the candidate list, score += (nwi * logNnw) / ni in
+ *  float, nwi that node's count, ni its keypoint count. The best hypothesis is the first strictly greatest score walking the
+ *  candidates in ascending id order, among ids > 0, starting from (0, 0.0f) (detectLoopClosure, Mapper.cpp:568-573).
+ *  limitKeypoints (SensorData.cpp:109-133): when max > 0 and n > max, keep the max highest fabs(response); among equal
+ *  responses the HIGHER index wins (reverse iteration of a multimap, which keeps insertion order among equal keys). Otherwise
+ *  every keypoint is kept.
+ *  sbm_get_profile: while profiling is enabled (any mode) searches and additions synchronise and record "vwd_search",
+ *  "vwd_append" (decide + append) and "vwd_total" (their float sum), ms of the last call. */
+enum { SBM_VWD_L1 = 0, SBM_VWD_L2 = 1 };
+#define SBM_VWD_NONE 2147483647
+typedef struct sbm_vwd_params {
+  int32_t metric;  /* SBM_VWD_L1 (what the reference's index answers with) or SBM_VWD_L2                   */
+  float nndr;      /* nndrRatio 0.8f; in (0, 1]                                                            */
+  int32_t slices;  /* dictionary slices per query tile, 0 = automatic; 0 .. 65 535                         */
+} sbm_vwd_params;
+typedef struct sbm_vwd sbm_vwd; /* opaque */
+
+/* The reference's constants: L1, 0.8f, automatic slices. */
+void sbm_vwd_params_default(sbm_vwd_params* p);
+/* SBM_ERR_NULL; SBM_ERR_UNSUPPORTED for an unknown metric, an nndr that is NaN, <= 0 or > 1, or slices outside 0 .. 65 535. */
+int sbm_vwd_params_validate(const sbm_vwd_params* p);
+/* An empty dictionary for up to `capacity` words on the handle's device. The codes of sbm_vwd_params_validate; SBM_ERR_SIZE for
+ * capacity 0, SBM_ERR_UNSUPPORTED above 2^26, both before anything is allocated; *out is NULL on failure. */
+int sbm_vwd_create(sbm_handle* h, size_t capacity, const sbm_vwd_params* p, sbm_vwd** out);
+void sbm_vwd_destroy(sbm_vwd* vwd);
+/* Forget every word, reference and node (and the overflow count); the store is kept. */
+int sbm_vwd_reset(sbm_vwd* vwd);
+int sbm_vwd_size(sbm_vwd* vwd, size_t* size);
+/* Calls refused so far because their new words did not fit. */
+int sbm_vwd_overflow(sbm_vwd* vwd, uint64_t* overflow);
+/* addNewWords on n rows of 32 bytes in DEVICE memory, dense, in the layout sbm_orb_describe_device writes (a frame's rows;
+ * 16-byte aligned, SBM_ERR_UNSUPPORTED otherwise). word_ids (host, n ints, may be NULL) receives the word id of every row.
+ * n 0 .. 65 535 and n_keypoints_total >= n (SBM_ERR_SIZE), node_id >= 1 (SBM_ERR_UNSUPPORTED). Synchronous: the ids come back
+ * to the host, which keeps the references. SBM_ERR_VWD_FULL as above. */
+int sbm_vwd_add_words_device(sbm_vwd* vwd, const void* d_desc, int n, int node_id, int n_keypoints_total, int* word_ids);
+/* The same on host rows, `stride` bytes apart (>= 32). */
+int sbm_vwd_add_words(sbm_vwd* vwd, const uint8_t* desc, size_t stride, int n, int node_id, int n_keypoints_total, int* word_ids);
+/* The 2-NN records of n device rows against the dictionary as it is, nothing added: d_knn receives n records (16-byte aligned). */
+int sbm_vwd_search_device(sbm_vwd* vwd, const void* d_desc, int n, void* d_knn, int sync);
+/* Words first .. first + count - 1 of the store, 32 bytes each, into host memory; SBM_ERR_SIZE beyond the size. */
+int sbm_vwd_fetch_words(sbm_vwd* vwd, size_t first, size_t count, uint8_t* rows);
+/* The references of one word, ascending by node: *count pairs into nodes / counts (cap entries each; SBM_ERR_SIZE with *count
+ * set when cap is too small, or for a word id outside the dictionary). */
+int sbm_vwd_references(sbm_vwd* vwd, int word_id, int* nodes, int* counts, int cap, int* count);
+/* computeLikelihood of node_id against n candidate node ids (any order; a repeated id is one candidate) with n_nodes the
+ * caller's total node count: scores[i] is candidates[i]'s score; *best_id / *best_score the highest hypothesis, (0, 0.0f) when
+ * none is positive. Host code. SBM_ERR_UNSUPPORTED for node_id < 1, SBM_ERR_SIZE for a node the dictionary has not seen or a
+ * negative n or n_nodes. */
+int sbm_vwd_likelihood(sbm_vwd* vwd, int node_id, const int* candidates, int n, int n_nodes, float* scores, int* best_id,
+                       float* best_score);
+/* limitKeypoints: keep_flags[i] = 1 for the keypoints kept, else 0. Pure host code, no handle. SBM_ERR_NULL, SBM_ERR_SIZE
+ * (n < 0), SBM_ERR_UNSUPPORTED for a NaN response (the reference's multimap has no order for it). */
+int sbm_vwd_limit_keypoints(const float* responses, int n, int max, uint8_t* keep_flags);
 
 /* The raw HIP stream (hipStream_t) as void*, so callers can order their own work behind ours (record an event on it
  * after sbm_compute_device(..., sync = 0)) or ours behind theirs (hipStreamWaitEvent on it before the call). Every entry

@@ -7,6 +7,7 @@ Layout
   _engine.py    the base of both classes: one handle, its in-flight buffers, the one call path to the device entry points
   _frontend.py _fpga.py _gftt.py _orb.py _match.py _pnp.py _lk.py   one family of entry points each, as mixins of StereoBM
   _occupancy.py OccupancyMap: the voxel map of buildOccupancyGridMap, made from a StereoBM / StereoSGBM's handle
+  _vwd.py       VWDictionary: the visual-word dictionary and loop-closure likelihood, made from such a handle too
   stereobm.py   host-side mirror of the cv::StereoBM interface (the dense path) and every public name of the above
   stereosgbm.py the same for cv::StereoSGBM (MODE_HH / MODE_SGBM)
   synth.py      deterministic synthetic stereo frames
@@ -25,6 +26,8 @@ from .stereobm import (StereoBM, StereoBMError, SbmParams, StereoModel, library_
                        LkParams, lk_params, lk_validate, lk_level_sizes, LK_GET_MIN_EIGENVALS, LK_USE_INITIAL_FLOW)
 from .stereosgbm import StereoSGBM, SgbmParams, sgbm_params, sgbm_validate  # noqa: F401
 from ._occupancy import OccupancyMap, OccParams, occ_params, occ_validate, occ_write_binary, ERR_OCC_FULL  # noqa: F401
+from ._vwd import (VWDictionary, VwdParams, vwd_params, vwd_validate, limit_keypoints, ERR_VWD_FULL, VWD_L1, VWD_L2,  # noqa: F401
+                   VWD_NONE)
 
 __all__ = ["StereoBM", "StereoBMError", "SbmParams", "StereoModel", "library_path", "load_library", "PREFILTER_XSOBEL",
            "PREFILTER_NORMALIZED_RESPONSE", "RectCam", "make_rect_cam", "PREFILTER_FLAVOUR_CV", "PREFILTER_FLAVOUR_RTL", "trim",
@@ -34,4 +37,5 @@ __all__ = ["StereoBM", "StereoBMError", "SbmParams", "StereoModel", "library_pat
            "match_params", "match_validate", "PnpParams", "pnp_params", "pnp_validate", "pnp_records", "PNP_RESULT_DTYPE",
            "PNP_HYP_DTYPE", "GfttCvParams", "gftt_cv_params", "gftt_cv_validate", "LkParams", "lk_params", "lk_validate",
            "lk_level_sizes", "LK_GET_MIN_EIGENVALS", "LK_USE_INITIAL_FLOW", "OccupancyMap", "OccParams", "occ_params", "occ_validate",
-           "occ_write_binary", "ERR_OCC_FULL"]
+           "occ_write_binary", "ERR_OCC_FULL", "VWDictionary", "VwdParams", "vwd_params", "vwd_validate", "limit_keypoints",
+           "ERR_VWD_FULL", "VWD_L1", "VWD_L2", "VWD_NONE"]

@@ -106,7 +106,16 @@ class OccParams(ctypes.Structure):
     _fields_ = [("resolution", ctypes.c_double), ("range_max", ctypes.c_float), ("tree_depth", ctypes.c_int32)]
 
 
+class VwdParams(ctypes.Structure):
+    """`sbm_vwd_params` of include/sbm.h: addNewWords' metric and NNDR ratio (VWDictionary.cpp:43), and the search's slice count."""
+
+    _fields_ = [("metric", ctypes.c_int32), ("nndr", ctypes.c_float), ("slices", ctypes.c_int32)]
+
+
 ERR_OCC_FULL = -25
+ERR_VWD_FULL = -26
+VWD_L1, VWD_L2 = 0, 1
+VWD_NONE = 2147483647
 LK_USE_INITIAL_FLOW = 4
 LK_GET_MIN_EIGENVALS = 8
 
@@ -269,6 +278,24 @@ def load_library():
     L.sbm_occ_fetch_device.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
     L.sbm_occ_fetch.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
     L.sbm_occ_write_binary.argtypes = [vp, sz, ctypes.c_double, ctypes.c_char_p]
+    wp = ctypes.POINTER(VwdParams)
+    pi = ctypes.POINTER(ci)
+    L.sbm_vwd_params_default.argtypes = [wp]
+    L.sbm_vwd_params_default.restype = None
+    L.sbm_vwd_params_validate.argtypes = [wp]
+    L.sbm_vwd_create.argtypes = [vp, sz, wp, ctypes.POINTER(vp)]
+    L.sbm_vwd_destroy.argtypes = [vp]
+    L.sbm_vwd_destroy.restype = None
+    L.sbm_vwd_reset.argtypes = [vp]
+    L.sbm_vwd_size.argtypes = [vp, ctypes.POINTER(sz)]
+    L.sbm_vwd_overflow.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    L.sbm_vwd_add_words_device.argtypes = [vp, vp, ci, ci, ci, vp]
+    L.sbm_vwd_add_words.argtypes = [vp, vp, sz, ci, ci, ci, vp]
+    L.sbm_vwd_search_device.argtypes = [vp, vp, ci, vp, ci]
+    L.sbm_vwd_fetch_words.argtypes = [vp, sz, sz, vp]
+    L.sbm_vwd_references.argtypes = [vp, ci, vp, vp, ci, pi]
+    L.sbm_vwd_likelihood.argtypes = [vp, ci, vp, ci, ci, vp, pi, ctypes.POINTER(ctypes.c_float)]
+    L.sbm_vwd_limit_keypoints.argtypes = [vp, ci, ci, vp]
     L.sbm_stream.argtypes = [vp]
     L.sbm_stream.restype = vp
     L.sbm_strerror.argtypes = [ci]

@@ -77,6 +77,7 @@ const char* sbm_strerror(int code) {
     case SBM_ERR_UNSUPPORTED: return "configuration outside this build's limits";
     case SBM_ERR_BATCH: return "batch count must be positive";
     case SBM_ERR_OCC_FULL: return "occupancy map full: points were counted as overflow, not stored (see sbm_occ_overflow)";
+    case SBM_ERR_VWD_FULL: return "visual-word dictionary full: the call's new words did not fit and nothing was added (see sbm_vwd_overflow)";
     default: return "unknown status";
   }
 }
