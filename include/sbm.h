@@ -1136,6 +1136,112 @@ int sbm_vwd_likelihood(sbm_vwd* vwd, int node_id, const int* candidates, int n, 
  * (n < 0), SBM_ERR_UNSUPPORTED for a NaN response (the reference's multimap has no order for it). */
 int sbm_vwd_limit_keypoints(const float* responses, int n, int max, uint8_t* keep_flags);
 
+/* ---- pose-graph optimiser: runOptimize, runOptimizeRobust ------------------------------------------------------------------------
+ * The reference's last stage between its motion estimates and its map (main.cpp:328, Optimizer.cpp, HyperGraph.cpp,
+ * GraphEdge.cpp, GraphVertex.cpp, g2o/SE3Gradient.cpp, getConnectedGraph of Mapper.cpp:195-255): Levenberg-Marquardt over SE3-SE3
+ * edges. All device arithmetic is fp64 and nothing is contracted. tests/pgo_cases.py restates every step in numpy;
+ * tests/golden/pgo_reference.npz records what the reference's own code computes (tools/make_pgo_fixtures.py).
+ *  Vertices are ordered by ascending id; that order, the fixed vertex left out, is the Hessian index. One vertex is fixed
+ *  (fixed_id, the reference's 1). Poses and measurements are 3 x 4 row-major doubles; the float-to-double conversion of addVertices
+ *  is the caller's. Edges are taken in the caller's order, which is the reference's multimap order (keyed by `from`).
+ *  Error. delta = (Z^-1 Xi^-1) Xj; e = (delta's translation, the vector part of Quaternion(R) normalised and negated when w < 0),
+ *  Quaternion(R) being Eigen's conversion with its trace-positive and its largest-diagonal branch; chi2 = e^T O e.
+ *  Jacobians. computeEdgeSE3Gradient as written, with A = Z^-1, B = Xi^-1 Xj, E = A B and dq/dR through S = 2 sqrt(tr + 1),
+ *  qw = S / 4, 1 / pow(qw, 3). That form is singular at a 180 degree error and is not repaired.
+ *  Quadratic form. b receives Jn^T(-O e) for each free end, the diagonal blocks Jn^T O Jn; there is ONE off-diagonal block, at
+ *  (row to, column from), inserted only when `from` is free.
+ *  coupling. SBM_PGO_COUPLING_REFERENCE (default): SimplicialLDLT reads the lower triangle only, so an edge whose `to` has the
+ *  SMALLER Hessian index keeps its diagonal blocks and its b but couples nothing -- the reference's loop closures are
+ *  Link(new id, old id), so this is its usual case. SBM_PGO_COUPLING_SYMMETRIC: every edge between two free vertices couples
+ *  them; what a caller who wants a correct optimiser passes. The recording shows the first reading.
+ *  Initial lambda. lambda0 = tau * max_diag, tau = 1e-5; constructQuadraticForm resets max_diag to 0 for EVERY edge, so max_diag
+ *  is the largest absolute diagonal entry of the LAST edge's free blocks, not of the matrix. Restated on purpose; reorder the edges
+ *  and lambda0 changes.
+ *  Iteration. Solve (A + lambda I) x = b, oplus on every free vertex, lambda *= scaleLambda: scale = sum x (lambda x + b) + 1e-3,
+ *  rho = (chi2 before - chi2 after) / scale, alpha = 1 - (2 rho - 1)^3 clamped to [1/3, 2/3]. There is no step rejection: a step
+ *  that raises chi2 is kept. oplus: fromCompactQuaternion returns the identity rotation when 1 - |v|^2 < 0 (the translation still
+ *  applies), else Quaternion(sqrt(w), v).toRotationMatrix(); estimate = estimate * increment.
+ *  sbm_pgo_optimize = runOptimize: num iterations, then computeActiveErrors; poses come back in ascending id order.
+ *  sbm_pgo_optimize_robust = runOptimizeRobust, the loop on the host: 1 getConnectedGraph(fixed_id) as written (the largest pending
+ *  id first, poses propagated through forward or inverted links, unique links kept, unreached vertices drop out); 2 five
+ *  iterations on the device, then the per-edge chi2; 3 among edges with |id1 - id2| != 1 and chi2 >= 10 the strictly greatest (the
+ *  first in link order among equals); 4 none: runOptimize(num) from the RE-PROPAGATED poses, not from the five-iteration result,
+ *  and stop; 5 else every link with that (from, to) is removed, and again. The removed links are reported in order.
+ *  Defined where the reference is not: where `to` is the fixed vertex and `from` is free the reference forms a negative triplet
+ *  index; here that coupling is dropped, the mathematically right answer. The reference erases links while iterating over them;
+ *  here "every link with that (from, to)". Propagation in getConnectedGraph is in double, pose[to] = pose[cur] * T or * T^-1,
+ *  without the float quaternion renormalisation of Transform::operator*; the caller's float map rounds at the end.
+ *  Elimination. Exact, not iterative. A free vertex is a JUNCTION when it touches a coupling between Hessian indices that are not
+ *  neighbours, or is promoted so that no stretch is longer than run_max; the stretches between junctions are RUNS, block
+ *  tridiagonal and independent. Every run is eliminated by block Thomas (16 lanes per run, one right-hand column each: b, 6 towards
+ *  the left junction, 6 towards the right); the Schur complement on the junctions is dense, factorised by block Cholesky, and
+ *  substituted back. One step of iterative refinement follows: the residual b - (A + lambda I) x is accumulated in twice the
+ *  working precision and solved against the same factors, and the correction is added to x. More than 1024 junctions
+ *  (plan.max_junctions) is SBM_ERR_UNSUPPORTED. No atomics anywhere: a result does not depend on scheduling.
+ *  Not guarded: a 6 x 6 pivot that is not positive -- from the singular dq/dR near 180 degrees, or from an information matrix
+ *  that is not positive definite, which sbm_pgo_params_check does not test -- makes sqrt return NaN; the call then returns
+ *  SBM_OK with NaN in *err and in the poses. The reference's LDLT goes on in the same situation (it logs a warning).
+ *  sbm_pgo_params_check: SBM_ERR_NULL for a null pointer; SBM_ERR_SIZE for num < 0, an empty graph (no vertex), a vertex id given
+ *  twice, an absent fixed_id, an edge naming an absent vertex; SBM_ERR_UNSUPPORTED for from == to, a non-finite pose, measurement
+ *  or information matrix, an unknown coupling, run_max outside 1 .. 65 536. No free vertices is SBM_OK with the poses unchanged.
+ *  sbm_get_profile: while profiling is enabled the LAST iteration of a call records "pgo_linearise", "pgo_assemble", "pgo_solve",
+ *  "pgo_update" and "pgo_total" (their float sum), ms. */
+enum { SBM_PGO_COUPLING_REFERENCE = 0, SBM_PGO_COUPLING_SYMMETRIC = 1 };
+enum { SBM_PGO_DEBUG_EDGES = 0, SBM_PGO_DEBUG_DIAG = 1, SBM_PGO_DEBUG_OFFDIAG = 2, SBM_PGO_DEBUG_B = 3, SBM_PGO_DEBUG_X = 4 };
+#define SBM_PGO_EDGE_RECORD 200 /* doubles per edge: e 6, chi2 1, pad 1, Ji 36, Jj 36, Ji^T O Ji 36, Jj^T O Jj 36, Ji^T O Jj 36, bi 6, bj 6 */
+typedef struct sbm_pgo_params {
+  int32_t num;       /* iterations of the final runOptimize; the reference passes 20; >= 0          */
+  int32_t fixed_id;  /* the vertex that stays; the reference fixes id 1                                */
+  int32_t coupling;  /* SBM_PGO_COUPLING_REFERENCE or SBM_PGO_COUPLING_SYMMETRIC                      */
+  int32_t run_max;   /* the longest run of the elimination, 1 .. 65 536; default 64                   */
+} sbm_pgo_params;
+typedef struct sbm_pgo_graph {
+  int32_t n_vertices;
+  const int32_t* ids;    /* n_vertices distinct ids, any order                                         */
+  const double* poses;   /* n_vertices x 12                                                            */
+  int32_t n_edges;
+  const int32_t* from;   /* n_edges vertex ids                                                         */
+  const int32_t* to;
+  const double* meas;    /* n_edges x 12                                                               */
+  const double* info;    /* n_edges x 36, row-major                                                    */
+} sbm_pgo_graph;
+typedef struct sbm_pgo_plan_info {
+  int32_t n_free, n_runs, n_junctions, schur_size /* 6 * n_junctions */, n_coupling /* edges with an off-diagonal block */,
+      longest_run, n_slots /* distinct coupled vertex pairs */, max_junctions;
+} sbm_pgo_plan_info;
+
+/* The reference's constants: 20 iterations, vertex 1 fixed, the lower-triangle reading, runs of up to 64. */
+void sbm_pgo_params_default(sbm_pgo_params* p);
+int sbm_pgo_params_check(const sbm_pgo_params* p, const sbm_pgo_graph* g);
+/* The partition, computed on the host without a device. vertex_run (n_free ints, may be NULL): per Hessian index its run, or -1
+ * for a junction. slot_rc (2 * n_slots ints, may be NULL; size it 2 * n_edges): (row, column) Hessian indices of every coupled
+ * pair, row > column, in the order of SBM_PGO_DEBUG_OFFDIAG. edge_couples (n_edges bytes, may be NULL). The codes of
+ * sbm_pgo_params_check; SBM_ERR_UNSUPPORTED with everything filled in when the junctions pass max_junctions. */
+int sbm_pgo_plan(const sbm_pgo_params* p, const sbm_pgo_graph* g, sbm_pgo_plan_info* info, int32_t* vertex_run, int32_t* slot_rc,
+                 uint8_t* edge_couples);
+/* runOptimize on host arrays: poses_out (n_vertices x 12, ascending id order), *err the final chi2. Synchronous. */
+int sbm_pgo_optimize(sbm_handle* h, const sbm_pgo_params* p, const sbm_pgo_graph* g, double* poses_out, double* err);
+/* runOptimizeRobust: *n_out vertices were reached; ids_out / poses_out (room for n_vertices) in ascending id order; removed
+ * receives up to removed_cap (from, to) pairs, *n_removed how many links were dropped. */
+int sbm_pgo_optimize_robust(sbm_handle* h, const sbm_pgo_params* p, const sbm_pgo_graph* g, int32_t* n_out, int32_t* ids_out,
+                            double* poses_out, double* err, int32_t* removed, int32_t removed_cap, int32_t* n_removed);
+/* The device forms: g->poses, g->meas and g->info are DEVICE memory (same layouts, poses in the order of g->ids), d_poses_out
+ * device memory for n_vertices x 12 doubles (ascending id order); ids, from and to stay host memory, since the partition is
+ * host code. The work runs on the handle's stream, which the call synchronises before it returns (chi2 comes home every
+ * iteration). Ids and topology are checked as in sbm_pgo_params_check; the values on the device are not read by the host, so
+ * non-finite ones are not refused. The results equal the host forms' bit for bit. The robust device form brings poses and
+ * measurements home once, because getConnectedGraph propagates on the host, and runs the host form. */
+int sbm_pgo_optimize_device(sbm_handle* h, const sbm_pgo_params* p, const sbm_pgo_graph* g, void* d_poses_out, double* err);
+int sbm_pgo_optimize_robust_device(sbm_handle* h, const sbm_pgo_params* p, const sbm_pgo_graph* g, int32_t* n_out, int32_t* ids_out,
+                                   void* d_poses_out, double* err, int32_t* removed, int32_t removed_cap, int32_t* n_removed);
+/* What the last optimisation on this handle launched: its partition, the lambda of its last iteration, its iteration count. */
+int sbm_pgo_last_plan(sbm_handle* h, sbm_pgo_plan_info* info, double* lambda, int32_t* iterations);
+/* The last iteration of the last optimisation (meant after a call of one iteration): SBM_PGO_DEBUG_EDGES n_edges records of
+ * SBM_PGO_EDGE_RECORD doubles; _DIAG n_free diagonal blocks of A (36 doubles, row-major; the lower triangle is what is read);
+ * _OFFDIAG n_slots lower blocks; _B and _X n_free x 6. SBM_ERR_SIZE when dst_bytes is too small, SBM_ERR_UNSUPPORTED before a
+ * call. */
+int sbm_pgo_debug_fetch(sbm_handle* h, int which, void* dst, size_t dst_bytes);
+
 /* The raw HIP stream (hipStream_t) as void*, so callers can order their own work behind ours (record an event on it
  * after sbm_compute_device(..., sync = 0)) or ours behind theirs (hipStreamWaitEvent on it before the call). Every entry
  * point selects the handle's device for the duration of the call and restores the caller's current device on return. */

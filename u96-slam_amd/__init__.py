@@ -8,6 +8,7 @@ Layout
   _frontend.py _fpga.py _gftt.py _orb.py _match.py _pnp.py _lk.py   one family of entry points each, as mixins of StereoBM
   _occupancy.py OccupancyMap: the voxel map of buildOccupancyGridMap, made from a StereoBM / StereoSGBM's handle
   _vwd.py       VWDictionary: the visual-word dictionary and loop-closure likelihood, made from such a handle too
+  _pgo.py       PoseGraph: the pose-graph optimiser (runOptimize / runOptimizeRobust), made from such a handle too
   stereobm.py   host-side mirror of the cv::StereoBM interface (the dense path) and every public name of the above
   stereosgbm.py the same for cv::StereoSGBM (MODE_HH / MODE_SGBM)
   synth.py      deterministic synthetic stereo frames
@@ -28,6 +29,8 @@ from .stereosgbm import StereoSGBM, SgbmParams, sgbm_params, sgbm_validate  # no
 from ._occupancy import OccupancyMap, OccParams, occ_params, occ_validate, occ_write_binary, ERR_OCC_FULL  # noqa: F401
 from ._vwd import (VWDictionary, VwdParams, vwd_params, vwd_validate, limit_keypoints, ERR_VWD_FULL, VWD_L1, VWD_L2,  # noqa: F401
                    VWD_NONE)
+from ._pgo import (PoseGraph, PgoParams, PgoPlanInfo, PgoGraph, pgo_params, pgo_check, pgo_plan, PGO_COUPLING_REFERENCE,  # noqa: F401
+                   PGO_COUPLING_SYMMETRIC, PGO_EDGE_RECORD)
 
 __all__ = ["StereoBM", "StereoBMError", "SbmParams", "StereoModel", "library_path", "load_library", "PREFILTER_XSOBEL",
            "PREFILTER_NORMALIZED_RESPONSE", "RectCam", "make_rect_cam", "PREFILTER_FLAVOUR_CV", "PREFILTER_FLAVOUR_RTL", "trim",
@@ -38,4 +41,5 @@ __all__ = ["StereoBM", "StereoBMError", "SbmParams", "StereoModel", "library_pat
            "PNP_HYP_DTYPE", "GfttCvParams", "gftt_cv_params", "gftt_cv_validate", "LkParams", "lk_params", "lk_validate",
            "lk_level_sizes", "LK_GET_MIN_EIGENVALS", "LK_USE_INITIAL_FLOW", "OccupancyMap", "OccParams", "occ_params", "occ_validate",
            "occ_write_binary", "ERR_OCC_FULL", "VWDictionary", "VwdParams", "vwd_params", "vwd_validate", "limit_keypoints",
-           "ERR_VWD_FULL", "VWD_L1", "VWD_L2", "VWD_NONE"]
+           "ERR_VWD_FULL", "VWD_L1", "VWD_L2", "VWD_NONE", "PoseGraph", "PgoParams", "PgoPlanInfo", "PgoGraph", "pgo_params", "pgo_check",
+           "pgo_plan", "PGO_COUPLING_REFERENCE", "PGO_COUPLING_SYMMETRIC", "PGO_EDGE_RECORD"]

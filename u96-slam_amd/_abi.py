@@ -112,6 +112,28 @@ class VwdParams(ctypes.Structure):
     _fields_ = [("metric", ctypes.c_int32), ("nndr", ctypes.c_float), ("slices", ctypes.c_int32)]
 
 
+class PgoParams(ctypes.Structure):
+    """`sbm_pgo_params` of include/sbm.h: runOptimize's iteration count, the fixed vertex, the coupling reading, the run length."""
+
+    _fields_ = [("num", ctypes.c_int32), ("fixed_id", ctypes.c_int32), ("coupling", ctypes.c_int32), ("run_max", ctypes.c_int32)]
+
+
+class PgoGraph(ctypes.Structure):
+    """`sbm_pgo_graph`: pointers to the caller's vertex and edge arrays."""
+
+    _fields_ = [("n_vertices", ctypes.c_int32), ("ids", ctypes.c_void_p), ("poses", ctypes.c_void_p), ("n_edges", ctypes.c_int32),
+                ("frm", ctypes.c_void_p), ("to", ctypes.c_void_p), ("meas", ctypes.c_void_p), ("info", ctypes.c_void_p)]
+
+
+class PgoPlanInfo(ctypes.Structure):
+    """`sbm_pgo_plan_info`: the partition of one graph into runs and junctions."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_free", "n_runs", "n_junctions", "schur_size", "n_coupling", "longest_run",
+                                              "n_slots", "max_junctions")]
+
+
+PGO_COUPLING_REFERENCE, PGO_COUPLING_SYMMETRIC = 0, 1
+PGO_EDGE_RECORD = 200
 ERR_OCC_FULL = -25
 ERR_VWD_FULL = -26
 VWD_L1, VWD_L2 = 0, 1
@@ -296,6 +318,19 @@ def load_library():
     L.sbm_vwd_references.argtypes = [vp, ci, vp, vp, ci, pi]
     L.sbm_vwd_likelihood.argtypes = [vp, ci, vp, ci, ci, vp, pi, ctypes.POINTER(ctypes.c_float)]
     L.sbm_vwd_limit_keypoints.argtypes = [vp, ci, ci, vp]
+    gp, qp, ip = ctypes.POINTER(PgoParams), ctypes.POINTER(PgoGraph), ctypes.POINTER(PgoPlanInfo)
+    L.sbm_pgo_params_default.argtypes = [gp]
+    L.sbm_pgo_params_default.restype = None
+    L.sbm_pgo_params_check.argtypes = [gp, qp]
+    L.sbm_pgo_plan.argtypes = [gp, qp, ip, vp, vp, vp]
+    L.sbm_pgo_optimize.argtypes = [vp, gp, qp, vp, ctypes.POINTER(ctypes.c_double)]
+    L.sbm_pgo_optimize_robust.argtypes = [vp, gp, qp, ctypes.POINTER(ctypes.c_int32), vp, vp, ctypes.POINTER(ctypes.c_double), vp,
+                                          ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
+    L.sbm_pgo_optimize_device.argtypes = [vp, gp, qp, vp, ctypes.POINTER(ctypes.c_double)]
+    L.sbm_pgo_optimize_robust_device.argtypes = [vp, gp, qp, ctypes.POINTER(ctypes.c_int32), vp, vp, ctypes.POINTER(ctypes.c_double),
+                                                 vp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]
+    L.sbm_pgo_last_plan.argtypes = [vp, ip, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)]
+    L.sbm_pgo_debug_fetch.argtypes = [vp, ci, vp, sz]
     L.sbm_stream.argtypes = [vp]
     L.sbm_stream.restype = vp
     L.sbm_strerror.argtypes = [ci]

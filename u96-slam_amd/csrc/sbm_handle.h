@@ -90,7 +90,7 @@ hipError_t launch_speckle(int16_t* disp, const SpeckleScratch& sc, const Geom& g
 // The stages of one family: the names sbm_get_profile answers, and how many marks one call records. Each family's file (the
 // block matcher's is sbm_api.hip) has the names, next to the enums that index its stages and marks and the code that times them.
 struct StageTable { const char* const* names; int nstage, nmark; };
-StageTable bm_stages(), sgbm_stages(), gftt_select_stages(), gftt_cv_stages(), orb_stages(), match_stages(), pnp_stages(), lk_stages(), occ_stages(), vwd_stages();
+StageTable bm_stages(), sgbm_stages(), gftt_select_stages(), gftt_cv_stages(), orb_stages(), match_stages(), pnp_stages(), lk_stages(), occ_stages(), vwd_stages(), pgo_stages();
 
 // Stage times of one family's last call while profiling is on: one event per mark, created on the first profiled call, and per
 // stage the milliseconds of the last call summed over its chunks. All zero is a valid clock. A family whose stages run back to
@@ -130,6 +130,11 @@ template <int NStage, int NMark, int N> constexpr StageTable stage_table(const c
   static_assert(N == NStage && NStage <= StageClock::kMax && NMark <= StageClock::kMax, "stages and marks must fit StageClock::kMax");
   return {names, NStage, NMark};
 }
+
+// The pose-graph optimiser's last call, for sbm_pgo_last_plan and sbm_pgo_debug_fetch: its sizes, the lambda of its last
+// iteration, and where that iteration's records lie in the handle's buffers (null until a call has finished).
+struct PgoLast { int ne, nfree, nslots, nj, nruns, iterations; double lambda; };
+struct PgoDebug { const double *rec, *D, *Eoff, *bv, *x; };
 
 }  // namespace sbm
 
@@ -254,12 +259,21 @@ struct sbm_handle {
     sbm::StageClock clock;
     template <class F> void each(F f) { f(scratch); f(ids); f(io); }
   } vwd;
+  struct {   // pose-graph optimiser: the graph (index lists, poses, measurements, information); the per-edge records and chi2;
+             // the block system, the runs' factors and columns, x; the dense Schur complement and its factor
+    sbm::DevBuf graph, edge, sys, schur;
+    sbm::StageClock clock;
+    sbm::PgoLast last;
+    sbm::PgoDebug dev;
+    sbm_pgo_plan_info plan;
+    template <class F> void each(F f) { f(graph); f(edge); f(sys); f(schur); }
+  } pgo;
   // The two lists a new family joins: f(set) for every set that owns DevBufs, f(clock, table) for every family with stage times.
-  template <class F> void each_set(F f) { f(bm); f(fp); f(st); f(fq); f(sg); f(gs); f(gc); f(orb); f(mt); f(pnp); f(lk); f(occ); f(vwd); }
+  template <class F> void each_set(F f) { f(bm); f(fp); f(st); f(fq); f(sg); f(gs); f(gc); f(orb); f(mt); f(pnp); f(lk); f(occ); f(vwd); f(pgo); }
   template <class F> void each_clock(F f) {
     using namespace sbm;
     f(bm.clock, bm_stages()); f(sg.clock, sgbm_stages()); f(gs.clock, gftt_select_stages()); f(gc.clock, gftt_cv_stages()); f(orb.clock, orb_stages());
-    f(mt.clock, match_stages()); f(pnp.clock, pnp_stages()); f(lk.clock, lk_stages()); f(occ.clock, occ_stages()); f(vwd.clock, vwd_stages());
+    f(mt.clock, match_stages()); f(pnp.clock, pnp_stages()); f(lk.clock, lk_stages()); f(occ.clock, occ_stages()); f(vwd.clock, vwd_stages()); f(pgo.clock, pgo_stages());
   }
 };
 
