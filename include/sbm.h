@@ -1042,6 +1042,99 @@ int sbm_occ_fetch(sbm_occ_map* map, uint64_t* keys, uint32_t* hits, size_t cap, 
  * written). */
 int sbm_occ_write_binary(const uint64_t* keys, size_t n, double resolution, const char* path);
 
+/* ---- occupancy map: ray-cast free space, insertPointCloud (OccupancyOcTreeBase.hxx:86-102, computeUpdate :169-270) -----------
+ * buildOccupancyGridMap computes a sensorOrigin per key frame (main.cpp:520) and never uses it: its map has occupied voxels and
+ * nothing else, so unknown and free space cannot be told apart. The second mode of sbm_occ_map is what octomap offers for that:
+ * the voxel state is a float log-odds, updated scan by scan exactly as insertPointCloud(scan, origin, maxrange, lazy_eval =
+ * false, discretize = false) without a bounding box updates the depth-16 leaves of an octomap::OcTree (pruning and expansion
+ * inside the tree never change a leaf's value, so the contract is per voxel). tests/occupancy_ray_cases.py is a literal
+ * transcription of this text, and tests/golden/occupancy_rays.npz holds what the reference's own octomap answered, bit for bit.
+ * IEEE binary32 / binary64 as written, no contraction, correctly rounded sqrt and division:
+ *  constants  logodds(p) = (float)log(p / (1 - p)), formed on the host at call time, for the five probabilities of
+ *             sbm_occ_ray_params (octomap's defaults, AbstractOccupancyOcTree.cpp:42-47).
+ *  scan       an origin and a list of points. A point that is not finite contributes nothing.
+ *  gate       v = p - origin in float; norm = sqrt((double)(v.x * v.x + v.y * v.y + v.z * v.z)), the sum in float; the point is
+ *             within range iff max_range < 0 or norm <= max_range (doubles). THIS gate is octomap's: the hit mode's
+ *             norm-against-squared-range quirk is not applied here.
+ *  within     ray cells: computeRayKeys(origin, p); p's voxel is occupied if coordToKeyChecked(p) passes (the key of the hit mode).
+ *  beyond     ray cells: computeRayKeys(origin, origin + dir * (float)max_range), dir = v / (float)norm per component when
+ *             norm > 0, all in float; no end point.
+ *  ray        computeRayKeys (OcTreeBaseImpl.hxx:542-648): nothing when either end has no key; nothing when both keys are equal;
+ *             else the origin's cell, then the 3-D DDA: d = end - origin in float, length = (float)norm(d), d /= length; per
+ *             axis step = sign(d) and, where step != 0, tMax = (keyToCoord(key) + (float)(step * resolution * 0.5) - origin) /
+ *             d and tDelta = resolution / |d| in double, else both the largest double. Each step advances the axis with the
+ *             smallest tMax (strict <: x only if below y and z, else y only if below z, else z), then stops if the key equals
+ *             the end's key, then stops if min(tMax) > length, else adds the cell. The end's cell is not part of the ray.
+ *             On the device the loop is also bounded by 3 * 65536 steps, which no ray between two keys reaches.
+ *  sets       free = union of the rays, occupied = union of the end points, free -= occupied.
+ *  update     every voxel of either set gets exactly ONE update per scan, u = miss or u = hit: an absent voxel starts at 0;
+ *             v += u in float; v = cmin if v < cmin, else cmax if v > cmax (updateNodeLogOdds; updateNode's early return for a
+ *             leaf at its clamp gives the same value).
+ *  order      scans are applied in call order and plane order; through the clamps the result depends on it.
+ *  Not provided: discretize, bounding boxes, change detection, insertPointCloudRays, castRay.
+ *  Mode. A map's mode is fixed by its first accepted insert after create or reset: hits (sbm_occ_insert*) or log-odds
+ *  (sbm_occ_insert_cloud*, sbm_occ_insert_rays*). An insert or a fetch of the other kind returns SBM_ERR_UNSUPPORTED and changes
+ *  nothing; a fetch of either kind serves an empty map. sbm_occ_size, sbm_occ_overflow and sbm_occ_reset serve both.
+ *  State. The log-odds of a slot lives in the slot's 32-bit count word; the first log-odds insert allocates 8 B per slot more (a
+ *  flag word and an entry of the scan's touched list), which reset keeps. The hit mode's 12 B per slot are unchanged.
+ *  Per scan two launches in stream order, no n * h * w intermediate: MARK, one lane per ray, walks the DDA in registers and for
+ *  every cell finds or claims the slot (the hit mode's compare-and-swap) and ORs "free" or "occupied this scan" into its flag
+ *  word, reading the word first so that the thousands of rays that share their first cells issue no atomic for a bit already
+ *  set; the lane whose OR found the word clear appends the slot to the touched list (one atomic per wavefront). APPLY runs over
+ *  the touched list: occupied wins, the update above, the flags are cleared. No float atomics, no spin waits, no grid barriers;
+ *  nothing depends on scheduling.
+ *  Overflow. A cell that finds no slot within the probe bound raises the overflow counter (once per ray that reaches it), and
+ *  the call, or with sync == 0 the next synchronous one, returns SBM_ERR_OCC_FULL. The table never frees a slot, so a stored
+ *  voxel has received every one of its updates and its value is exact; what is missing is whole voxels.
+ *  sbm_get_profile: "occ_rays_mark" / "occ_rays_apply", ms of the last log-odds insert summed over its scans. */
+typedef struct sbm_occ_ray_params {
+  double prob_hit;         /* 0.7    */
+  double prob_miss;        /* 0.4    */
+  double clamp_min;        /* 0.1192 */
+  double clamp_max;        /* 0.971  */
+  double occupancy_thres;  /* 0.5: a leaf is occupied iff its log-odds >= logodds(occupancy_thres) (the writer)   */
+  double max_range;        /* insertPointCloud's maxrange in metres; negative (the default, -1) means no limit    */
+} sbm_occ_ray_params;
+
+/* Fill *p with octomap's defaults. */
+void sbm_occ_ray_params_default(sbm_occ_ray_params* p);
+/* SBM_ERR_NULL; SBM_ERR_SIZE for a probability that is NaN or outside (0, 1), prob_hit < 0.5, prob_miss > 0.5, clamp_min >=
+ * clamp_max, or a max_range that is NaN; else SBM_OK. */
+int sbm_occ_ray_params_validate(const sbm_occ_ray_params* p);
+/* The five log-odds the inserts and the writer use, in the struct's order: hit, miss, clamp min, clamp max, threshold. Host
+ * code. The codes of sbm_occ_ray_params_validate, SBM_ERR_NULL without `logodds`. */
+int sbm_occ_ray_logodds(const sbm_occ_ray_params* p, float logodds[5]);
+/* One scan, octomap's own signature: n_points float triples in DEVICE memory (4-byte aligned), origin[3] and params in HOST
+ * memory, read before the call returns. Asynchronous on the handle's stream unless sync != 0. Checked before anything is
+ * launched: SBM_ERR_NULL (d_xyz may be NULL only for n_points == 0, an empty scan, which is accepted), the codes of
+ * sbm_occ_ray_params_validate, SBM_ERR_UNSUPPORTED for more than 2^30 points, a misaligned d_xyz or a map in hit mode;
+ * SBM_ERR_OCC_FULL as described above. */
+int sbm_occ_insert_cloud_device(sbm_occ_map* map, size_t n_points, const void* d_xyz, const float* origin,
+                                const sbm_occ_ray_params* params, int sync);
+/* The same from points in HOST memory. Synchronous. */
+int sbm_occ_insert_cloud(sbm_occ_map* map, size_t n_points, const float* xyz, const float* origin, const sbm_occ_ray_params* params);
+/* n scans from n disparity planes: plane i's points are the pixels sbm_occ_insert_device reprojects and transforms (d > 0, a
+ * finite reprojection, the local transform, then pose i; the same device function), its origin is (o14, o24, o34) of pose i
+ * (main.cpp:520). Arguments and their checks as sbm_occ_insert_device, then those of params. */
+int sbm_occ_insert_rays_device(sbm_occ_map* map, int n, const void* d_disp, int width, int height, int scale,
+                               const sbm_stereo_model* model, const float* poses, const sbm_occ_ray_params* params, int sync);
+/* The same from planes in HOST memory. Synchronous. */
+int sbm_occ_insert_rays(sbm_occ_map* map, int n, const int16_t* disp, int width, int height, int scale, const sbm_stereo_model* model,
+                        const float* poses, const sbm_occ_ray_params* params);
+/* sbm_occ_fetch_device / sbm_occ_fetch for a log-odds map: the stored voxels ascending by packed key with their float log-odds
+ * (the radix sort's 32-bit payload is the float's bits). Same arguments, checks and codes; SBM_ERR_UNSUPPORTED for a map in
+ * hit mode. */
+int sbm_occ_fetch_logodds_device(sbm_occ_map* map, void* d_keys, void* d_logodds, size_t cap, size_t* count);
+int sbm_occ_fetch_logodds(sbm_occ_map* map, uint64_t* keys, float* logodds, size_t cap, size_t* count);
+/* Plain host code, no GPU: what OcTree::writeBinary writes for a tree whose depth-16 leaves are exactly these n voxels (any
+ * order, each key once). First toMaxLikelihood: a leaf is occupied iff logodds >= occupancy_thres_log (the fifth value of
+ * sbm_occ_ray_logodds). Then prune(): eight sibling leaves of the same kind collapse, recursively. Then the stream of
+ * writeBinaryNode (OccupancyOcTreeBase.hxx:1031-1090) under sbm_occ_write_binary's header: per inner node 2 bits per child,
+ * 01 occupied leaf, 10 free leaf, 11 inner, 00 none; "size" is the node count after pruning. SBM_ERR_NULL, SBM_ERR_SIZE
+ * (resolution, a key above 48 bits, a key given twice, a NaN), SBM_ERR_NOMEM, SBM_ERR_UNSUPPORTED (the file cannot be written). */
+int sbm_occ_write_binary_logodds(const uint64_t* keys, const float* logodds, size_t n, double resolution, float occupancy_thres_log,
+                                 const char* path);
+
 /* ---- visual-word dictionary: addNewWords, computeLikelihood, limitKeypoints ---------------------------------------------------
  * The reference's loop-closure thread, started by Mapper::process for each key frame: addWordIds -> VWDictionary::addNewWords
  * (src/slam/src/core/Mapper.cpp:413-484, VWDictionary.cpp:40-115) and detectLoopClosure -> computeLikelihood

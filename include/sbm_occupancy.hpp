@@ -6,6 +6,8 @@
 // becomes one insert() per node and one writeBinary(): the per-pixel reprojection, transforms, range gate and
 // key run on the MI355X, only the distinct voxels come back, and the .bt stream is written from them. Failures throw sbm::Error;
 // a map that is too small throws with code SBM_ERR_OCC_FULL (nothing is dropped silently: overflow() counts the points).
+// insertRays() / insertPointCloud() / writeBinaryLogOdds() are the same loop with octomap's insertPointCloud in place of
+// updateNode: free space is ray-cast from each node's sensor origin and the .bt holds free and occupied leaves.
 #ifndef SBM_OCCUPANCY_HPP_
 #define SBM_OCCUPANCY_HPP_
 
@@ -23,6 +25,7 @@ class OccupancyMap {
   // octomap::OcTree tree(resolution) and the reference's rangeMax_ (0.1, 5.0f); capacity in voxels
   explicit OccupancyMap(size_t capacity, double resolution = 0.1, float range_max = 5.0f, int device = 0) {
     sbm_occ_params_default(&p_);
+    sbm_occ_ray_params_default(&rp_);
     p_.resolution = resolution;
     p_.range_max = range_max;
     sbm_params bm;
@@ -57,6 +60,43 @@ class OccupancyMap {
   }
   void reset() { check(sbm_occ_reset(m_)); }
 
+  // ---- log-odds mode: a map whose first insert is one of these holds a float log-odds per voxel, free space included ---------
+  // octomap's probabilities; rayParams().max_range is insertPointCloud's maxrange for insertRays (negative: no limit)
+  sbm_occ_ray_params& rayParams() { return rp_; }
+  // tree.insertPointCloud(scan, sensor_origin, maxrange): n float triples in host memory
+  void insertPointCloud(const float* xyz, size_t n, const float origin[3], double maxrange = -1.) {
+    sbm_occ_ray_params rp = rp_;
+    rp.max_range = maxrange;
+    check(sbm_occ_insert_cloud(m_, n, xyz, origin, &rp));
+  }
+  // One node as insert() takes it, ray-cast from the sensorOrigin the reference computes (main.cpp:520) and never uses: the
+  // pose's translation.
+  void insertRays(const int16_t* disp, int width, int height, int scale, const sbm_stereo_model& model, const float pose[12]) {
+    check(sbm_occ_insert_rays(m_, 1, disp, width, height, scale, &model, pose, &rp_));
+  }
+  void insertRaysDevice(int n, const void* d_disp, int width, int height, int scale, const sbm_stereo_model& model,
+                        const float* poses, bool sync = true) {
+    check(sbm_occ_insert_rays_device(m_, n, d_disp, width, height, scale, &model, poses, &rp_, sync ? 1 : 0));
+  }
+  // the stored voxels ascending by packed key with their log-odds
+  std::vector<uint64_t> leaves(std::vector<float>& logodds) {
+    std::vector<uint64_t> k(size());
+    logodds.assign(k.size(), 0.f);
+    size_t n = 0;
+    check(sbm_occ_fetch_logodds(m_, k.data(), logodds.data(), k.size(), &n));
+    k.resize(n);
+    logodds.resize(n);
+    return k;
+  }
+  // tree.writeBinary(path) of a log-odds map: free and occupied leaves, thresholded at rayParams().occupancy_thres
+  void writeBinaryLogOdds(const std::string& path) {
+    std::vector<float> v;
+    const std::vector<uint64_t> k = leaves(v);
+    float c[5];
+    check(sbm_occ_ray_logodds(&rp_, c));
+    check(sbm_occ_write_binary_logodds(k.data(), v.data(), k.size(), p_.resolution, c[4], path.c_str()));
+  }
+
   size_t size() {
     size_t n = 0;
     check(sbm_occ_size(m_, &n));
@@ -88,6 +128,7 @@ class OccupancyMap {
     if (st != SBM_OK) throw Error(st, sbm_strerror(st));
   }
   sbm_occ_params p_;
+  sbm_occ_ray_params rp_;
   sbm_handle* h_ = nullptr;
   sbm_occ_map* m_ = nullptr;
 };

@@ -27,6 +27,7 @@ from .stereobm import (StereoBM, StereoBMError, SbmParams, StereoModel, library_
                        LkParams, lk_params, lk_validate, lk_level_sizes, LK_GET_MIN_EIGENVALS, LK_USE_INITIAL_FLOW)
 from .stereosgbm import StereoSGBM, SgbmParams, sgbm_params, sgbm_validate  # noqa: F401
 from ._occupancy import OccupancyMap, OccParams, occ_params, occ_validate, occ_write_binary, ERR_OCC_FULL  # noqa: F401
+from ._occupancy import OccRayParams, occ_ray_params, occ_ray_validate, occ_ray_logodds, occ_write_binary_logodds  # noqa: F401
 from ._vwd import (VWDictionary, VwdParams, vwd_params, vwd_validate, limit_keypoints, ERR_VWD_FULL, VWD_L1, VWD_L2,  # noqa: F401
                    VWD_NONE)
 from ._pgo import (PoseGraph, PgoParams, PgoPlanInfo, PgoGraph, pgo_params, pgo_check, pgo_plan, PGO_COUPLING_REFERENCE,  # noqa: F401
@@ -40,6 +41,7 @@ __all__ = ["StereoBM", "StereoBMError", "SbmParams", "StereoModel", "library_pat
            "match_params", "match_validate", "PnpParams", "pnp_params", "pnp_validate", "pnp_records", "PNP_RESULT_DTYPE",
            "PNP_HYP_DTYPE", "GfttCvParams", "gftt_cv_params", "gftt_cv_validate", "LkParams", "lk_params", "lk_validate",
            "lk_level_sizes", "LK_GET_MIN_EIGENVALS", "LK_USE_INITIAL_FLOW", "OccupancyMap", "OccParams", "occ_params", "occ_validate",
-           "occ_write_binary", "ERR_OCC_FULL", "VWDictionary", "VwdParams", "vwd_params", "vwd_validate", "limit_keypoints",
+           "occ_write_binary", "ERR_OCC_FULL", "OccRayParams", "occ_ray_params", "occ_ray_validate", "occ_ray_logodds",
+           "occ_write_binary_logodds", "VWDictionary", "VwdParams", "vwd_params", "vwd_validate", "limit_keypoints",
            "ERR_VWD_FULL", "VWD_L1", "VWD_L2", "VWD_NONE", "PoseGraph", "PgoParams", "PgoPlanInfo", "PgoGraph", "pgo_params", "pgo_check",
            "pgo_plan", "PGO_COUPLING_REFERENCE", "PGO_COUPLING_SYMMETRIC", "PGO_EDGE_RECORD"]

@@ -106,6 +106,13 @@ class OccParams(ctypes.Structure):
     _fields_ = [("resolution", ctypes.c_double), ("range_max", ctypes.c_float), ("tree_depth", ctypes.c_int32)]
 
 
+class OccRayParams(ctypes.Structure):
+    """`sbm_occ_ray_params` of include/sbm.h: the probabilities of octomap's insertPointCloud and its maxrange (< 0: no limit)."""
+
+    _fields_ = [("prob_hit", ctypes.c_double), ("prob_miss", ctypes.c_double), ("clamp_min", ctypes.c_double),
+                ("clamp_max", ctypes.c_double), ("occupancy_thres", ctypes.c_double), ("max_range", ctypes.c_double)]
+
+
 class VwdParams(ctypes.Structure):
     """`sbm_vwd_params` of include/sbm.h: addNewWords' metric and NNDR ratio (VWDictionary.cpp:43), and the search's slice count."""
 
@@ -300,6 +307,18 @@ def load_library():
     L.sbm_occ_fetch_device.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
     L.sbm_occ_fetch.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
     L.sbm_occ_write_binary.argtypes = [vp, sz, ctypes.c_double, ctypes.c_char_p]
+    orp = ctypes.POINTER(OccRayParams)
+    L.sbm_occ_ray_params_default.argtypes = [orp]
+    L.sbm_occ_ray_params_default.restype = None
+    L.sbm_occ_ray_params_validate.argtypes = [orp]
+    L.sbm_occ_ray_logodds.argtypes = [orp, vp]
+    L.sbm_occ_insert_cloud_device.argtypes = [vp, sz, vp, vp, orp, ci]
+    L.sbm_occ_insert_cloud.argtypes = [vp, sz, vp, vp, orp]
+    L.sbm_occ_insert_rays_device.argtypes = [vp, ci, vp, ci, ci, ci, mp, vp, orp, ci]
+    L.sbm_occ_insert_rays.argtypes = [vp, ci, vp, ci, ci, ci, mp, vp, orp]
+    L.sbm_occ_fetch_logodds_device.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_fetch_logodds.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_write_binary_logodds.argtypes = [vp, vp, sz, ctypes.c_double, ctypes.c_float, ctypes.c_char_p]
     wp = ctypes.POINTER(VwdParams)
     pi = ctypes.POINTER(ci)
     L.sbm_vwd_params_default.argtypes = [wp]

@@ -1,11 +1,12 @@
 """The occupancy voxel map of the reference's buildOccupancyGridMap (src/slam/src/core/main.cpp:495-561): a device-side set of
-octomap keys fed straight from disparity planes, and the octomap binary stream (.bt) written from its distinct keys."""
+octomap keys fed straight from disparity planes, and the octomap binary stream (.bt) written from its distinct keys. Its second
+mode is octomap's insertPointCloud: float log-odds per voxel, free space ray-cast from each scan's origin."""
 import ctypes
 import os
 
 import numpy as np
 
-from ._abi import ERR_OCC_FULL, OccParams, StereoBMError, _check, _torch, load_library
+from ._abi import ERR_OCC_FULL, OccParams, OccRayParams, StereoBMError, _check, _torch, load_library
 
 
 def occ_params(resolution=0.1, range_max=5.0, tree_depth=16):
@@ -24,6 +25,36 @@ def occ_write_binary(keys, path, resolution=0.1):
     keys = np.ascontiguousarray(np.asarray(keys, np.uint64).reshape(-1))
     _check(load_library().sbm_occ_write_binary(keys.ctypes.data if len(keys) else None, len(keys), float(resolution),
                                                os.fsencode(path)))
+
+
+def occ_ray_params(prob_hit=0.7, prob_miss=0.4, clamp_min=0.1192, clamp_max=0.971, occupancy_thres=0.5, max_range=-1.0):
+    """octomap's constants by default; max_range < 0 means no limit."""
+    return OccRayParams(float(prob_hit), float(prob_miss), float(clamp_min), float(clamp_max), float(occupancy_thres),
+                        float(max_range))
+
+
+def occ_ray_validate(params):
+    """Status code of sbm_occ_ray_params_validate (0 = ok)."""
+    return load_library().sbm_occ_ray_params_validate(ctypes.byref(params))
+
+
+def occ_ray_logodds(params=None):
+    """float32 (5,): the log-odds of hit, miss, clamp min, clamp max and the occupancy threshold."""
+    out = np.empty(5, np.float32)
+    _check(load_library().sbm_occ_ray_logodds(ctypes.byref(params if params is not None else occ_ray_params()), out.ctypes.data))
+    return out
+
+
+def occ_write_binary_logodds(keys, logodds, path, resolution=0.1, occupancy_thres_log=0.0):
+    """Write the .bt stream OcTree::writeBinary produces for a tree whose leaves are these packed keys (uint64, each once) with
+    these float log-odds: occupied iff logodds >= occupancy_thres_log, pruned. Host code: needs no GPU."""
+    keys = np.ascontiguousarray(np.asarray(keys, np.uint64).reshape(-1))
+    logodds = np.ascontiguousarray(np.asarray(logodds, np.float32).reshape(-1))
+    if len(keys) != len(logodds):
+        raise StereoBMError(-2, f"{len(keys)} keys with {len(logodds)} log-odds")
+    _check(load_library().sbm_occ_write_binary_logodds(keys.ctypes.data if len(keys) else None,
+                                                       logodds.ctypes.data if len(keys) else None, len(keys), float(resolution),
+                                                       float(occupancy_thres_log), os.fsencode(path)))
 
 
 def _poses(poses, n):
@@ -88,6 +119,78 @@ class OccupancyMap:
         else:
             self._engine._inflight.append((d3,))
 
+    def _ray_params(self, params, kw):
+        if params is not None and kw:
+            raise TypeError("pass either an OccRayParams or keyword parameters")
+        self._rp = params if params is not None else occ_ray_params(**kw)
+        return ctypes.byref(self._rp)
+
+    def insert_cloud(self, points, origin, params=None, sync=True, **kw):
+        """octomap's insertPointCloud(scan, origin, maxrange): points (m, 3) as a torch CUDA float32 tensor or a numpy array
+        (the host form, always synchronous), origin three floats. The parameters of the last log-odds insert are the ones
+        write_binary_logodds thresholds with."""
+        rp = self._ray_params(params, kw)
+        o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3))
+        if isinstance(points, np.ndarray):
+            p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+            _check(self._L.sbm_occ_insert_cloud(self._m, len(p), p.ctypes.data if len(p) else None, o.ctypes.data, rp),
+                   self._engine._h)
+            return
+        torch = _torch()
+        if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or not points.is_cuda or points.dim() != 2 or \
+                points.shape[1] != 3 or points.device.index != self._engine._device:
+            raise StereoBMError(-2, "points must be a CUDA float32 (m, 3) tensor on the engine's device")
+        p = points.contiguous()
+        torch.cuda.current_stream(p.device).synchronize()
+        _check(self._L.sbm_occ_insert_cloud_device(self._m, p.shape[0], p.data_ptr() if p.shape[0] else None, o.ctypes.data, rp,
+                                                   1 if sync else 0), self._engine._h)
+        if sync:
+            self._engine._inflight.clear()
+        else:
+            self._engine._inflight.append((p,))
+
+    def insert_rays(self, disparity, model, poses, scale=1, params=None, sync=True, **kw):
+        """The arguments of insert(); plane i is one scan from the origin (o14, o24, o34) of pose i."""
+        rp = self._ray_params(params, kw)
+        if isinstance(disparity, np.ndarray):
+            d = np.ascontiguousarray(disparity, np.int16)
+            d = d[None] if d.ndim == 2 else d
+            n, h, w = d.shape
+            p = _poses(poses, n)
+            _check(self._L.sbm_occ_insert_rays(self._m, n, d.ctypes.data, w, h, int(scale), ctypes.byref(model), p.ctypes.data, rp),
+                   self._engine._h)
+            return
+        torch = _torch()
+        if not isinstance(disparity, torch.Tensor) or disparity.dtype != torch.int16 or not disparity.is_cuda or \
+                disparity.dim() not in (2, 3) or disparity.device.index != self._engine._device:
+            raise StereoBMError(-2, "disparity must be a CUDA int16 (n,H,W) or (H,W) tensor on the engine's device")
+        d3, n, h, w = self._engine._as3d(disparity)
+        p = _poses(poses, n)   # read before the call returns
+        torch.cuda.current_stream(d3.device).synchronize()
+        _check(self._L.sbm_occ_insert_rays_device(self._m, n, d3.data_ptr(), w, h, int(scale), ctypes.byref(model), p.ctypes.data,
+                                                  rp, 1 if sync else 0), self._engine._h)
+        if sync:
+            self._engine._inflight.clear()
+        else:
+            self._engine._inflight.append((d3,))
+
+    def fetch_logodds(self, allow_overflow=False):
+        """(packed keys uint64 ascending, log-odds float32) of a log-odds map as numpy arrays."""
+        n = self.size()
+        keys, lo = np.empty(n, np.uint64), np.empty(n, np.float32)
+        got = ctypes.c_size_t()
+        st = self._L.sbm_occ_fetch_logodds(self._m, keys.ctypes.data if n else None, lo.ctypes.data if n else None, n,
+                                           ctypes.byref(got))
+        if not (st == ERR_OCC_FULL and allow_overflow):
+            _check(st, self._engine._h)
+        return keys[:got.value], lo[:got.value]
+
+    def write_binary_logodds(self, path, params=None):
+        """tree.writeBinary(path) of a log-odds map, thresholded with `params` (default: those of the last log-odds insert)."""
+        rp = params if params is not None else getattr(self, "_rp", None) or occ_ray_params()
+        keys, lo = self.fetch_logodds()
+        occ_write_binary_logodds(keys, lo, path, self._p.resolution, float(occ_ray_logodds(rp)[4]))
+
     def size(self):
         v = ctypes.c_size_t()
         _check(self._L.sbm_occ_size(self._m, ctypes.byref(v)), self._engine._h)
@@ -128,4 +231,4 @@ class OccupancyMap:
         occ_write_binary(self.keys()[0], path, self._p.resolution)
 
     def profile(self):
-        return self._engine._profile(("occ_insert", "occ_fetch"))
+        return self._engine._profile(("occ_insert", "occ_fetch", "occ_rays_mark", "occ_rays_apply"))

@@ -7,6 +7,10 @@
 //   occ_insert_kernel   one thread per pixel: disparity -> point -> two transforms -> gate -> key; the wavefront then reduces
 //                       its 64 keys to distinct leaders with lane counts (ballot + readlane over the distinct values) and only
 //                       the leaders touch the table: a 64-bit compare-and-swap on the key slot, an atomic add of the lane count.
+//   occ_rays_*_kernel   the log-odds mode, octomap's insertPointCloud per scan: one lane per ray walks computeRayKeys' 3-D DDA in
+//                       registers and ORs "free" / "occupied this scan" into the flag word of every cell's slot; the lane whose OR
+//                       found the word clear appends the slot to the scan's touched list. occ_rays_apply_kernel then gives every
+//                       touched slot its ONE update (occupied wins) and clears the flags.
 //   occ_compact_kernel  occupied slots -> dense (key, hits) arrays, one atomic per wavefront.
 //   occ_hist / occ_scan / occ_scatter   one 8-bit pass of an LSD radix sort: digit counts per tile, an exclusive scan of the
 //                       digit-major count table, and a stable scatter (one wavefront per tile walks it 64 keys at a time and
@@ -26,9 +30,13 @@ struct sbm_occ_map {
   sbm_occ_params p;
   size_t capacity;           // voxels the caller asked for
   uint32_t slots;            // power of two >= 2 * capacity
-  sbm::DevBuf keys, hits;    // the table
+  unsigned scan;             // log-odds mode: scans applied since the last clear
+  int mode;                  // fixed by the first insert after create or reset: kOccModeNone, kOccModeHits, kOccModeLogOdds
+  sbm::DevBuf keys, hits;    // the table; in the log-odds mode a slot's `hits` word is its float log-odds
   sbm::DevBuf ctr;           // OccCounters
-  template <class F> void each(F f) { f(keys); f(hits); f(ctr); }
+  sbm::DevBuf flags, touched;   // log-odds mode only, from its first insert: per slot the flag word of the running scan, and the
+                                // slots that scan touched (4 B per slot each)
+  template <class F> void each(F f) { f(keys); f(hits); f(ctr); f(flags); f(touched); }
 };
 
 namespace sbm {
@@ -41,10 +49,15 @@ constexpr uint32_t kOccMaxProbe = 1024;
 constexpr int kOccTile = 1024;       // keys per workgroup of a radix pass
 constexpr size_t kOccMaxCapacity = (size_t)1 << 30;
 
+enum { kOccModeNone, kOccModeHits, kOccModeLogOdds };
+constexpr int kOccMaxSteps = 3 * 65536;   // of one ray: each step moves one key by one on one axis
+constexpr unsigned kOccFree = 1, kOccOccupied = 2;   // flag word of a slot within one scan
+
 struct OccCounters {
-  unsigned long long overflow;   // points that found the table full
+  unsigned long long overflow;   // points (log-odds mode: cells) that found the table full
   unsigned size;                 // occupied slots
   unsigned cursor;               // compaction cursor of a fetch
+  unsigned touched[2];           // log-odds mode: slots the running scan has touched, in [scan & 1]; the other is zero
 };
 
 struct OccPoses { float t[kOccChunk][12]; };
@@ -70,29 +83,35 @@ __device__ __forceinline__ bool occ_axis(double factor, float coord, unsigned* k
   return true;
 }
 
+// main.cpp:529-539 on pixel i of a plane: false where the reference skips the pixel, else the point after both transforms
+__device__ __forceinline__ bool occ_world_point(const int16_t* __restrict__ plane, int i, const OccGeom& g, const sbm_stereo_model& m,
+                                                const float* pose, Pt3* out) {
+#pragma clang fp contract(off)
+  const int r = i / g.W, c = i % g.W;
+  const float d = (float)plane[i] / 16.0f;       // main.cpp:529
+  if (!(d > 0)) return false;
+  Pt3 p = project_disparity((float)(c * g.scale), (float)(r * g.scale), d, m);
+  if (!finite3(p)) return false;
+  if (m.has_local) p = transform_point(p, m.local);
+  *out = transform_point(p, pose);
+  return true;
+}
+
 __global__ void __launch_bounds__(256) occ_insert_kernel(const int16_t* __restrict__ disp, OccGeom g, sbm_stereo_model m, OccPoses poses,
                                                           unsigned long long* __restrict__ keys, unsigned* __restrict__ hits,
                                                           OccCounters* __restrict__ ctr) {
 #pragma clang fp contract(off)
   const int i = blockIdx.x * 256 + threadIdx.x;
   unsigned long long key = kOccEmpty;
-  if (i < g.W * g.H) {
-    const int r = i / g.W, c = i % g.W;
-    const float d = (float)disp[(size_t)blockIdx.y * g.W * g.H + i] / 16.0f;       // main.cpp:529
-    if (d > 0) {
-      Pt3 p = project_disparity((float)(c * g.scale), (float)(r * g.scale), d, m);
-      if (finite3(p)) {
-        const float* pose = poses.t[blockIdx.y];
-        if (m.has_local) p = transform_point(p, m.local);
-        p = transform_point(p, pose);
-        const float vx = p.x - pose[3], vy = p.y - pose[7], vz = p.z - pose[11];
-        const float nsq = vx * vx + vy * vy + vz * vz;          // Vector3::norm_sq, a float expression
-        unsigned k0, k1, k2;
-        if (__dsqrt_rn((double)nsq) <= (double)g.range_max_sqrd && occ_axis(g.factor, p.x, &k0) && occ_axis(g.factor, p.y, &k1) &&
-            occ_axis(g.factor, p.z, &k2))
-          key = (unsigned long long)k0 << 32 | (unsigned long long)k1 << 16 | k2;
-      }
-    }
+  const float* pose = poses.t[blockIdx.y];
+  Pt3 p;
+  if (i < g.W * g.H && occ_world_point(disp + (size_t)blockIdx.y * g.W * g.H, i, g, m, pose, &p)) {
+    const float vx = p.x - pose[3], vy = p.y - pose[7], vz = p.z - pose[11];
+    const float nsq = vx * vx + vy * vy + vz * vz;          // Vector3::norm_sq, a float expression
+    unsigned k0, k1, k2;
+    if (__dsqrt_rn((double)nsq) <= (double)g.range_max_sqrd && occ_axis(g.factor, p.x, &k0) && occ_axis(g.factor, p.y, &k1) &&
+        occ_axis(g.factor, p.z, &k2))
+      key = (unsigned long long)k0 << 32 | (unsigned long long)k1 << 16 | k2;
   }
   // the wavefront's distinct keys: the lowest lane of each value leads and learns how many lanes hold it
   const int lane = threadIdx.x & 63;
@@ -123,6 +142,189 @@ __global__ void __launch_bounds__(256) occ_insert_kernel(const int16_t* __restri
     }
   }
   atomicAdd(&ctr->overflow, (unsigned long long)count);
+}
+
+// ---- log-odds mode: insertPointCloud (OccupancyOcTreeBase.hxx:86-102, computeUpdate :169-270) ------------------------------
+struct OccRay {                 // one call's constants
+  double max_range;             // < 0: no limit
+  double resolution, factor;    // factor = 1. / resolution
+  float hit, miss, cmin, cmax;  // log-odds
+  uint32_t mask, max_probe, slots;
+  uint32_t parity;              // which of OccCounters::touched counts this scan
+};
+
+struct OccPose { float t[12]; };     // the plane form's pose; the cloud form passes its origin in t[3], t[7], t[11]
+
+struct OccTable {
+  unsigned long long* keys;
+  float* logodds;
+  unsigned* flags;
+  unsigned* touched;
+  OccCounters* ctr;
+};
+
+// The whole wavefront calls this once per step (have: this lane has a cell). Finds or claims the cell's slot and ORs `bit` into
+// its flag word -- after reading it: thousands of rays share their first cells, and a set bit needs no atomic. The lanes whose OR
+// found the word clear append their slots to the scan's touched list, one atomic on the list's counter per wavefront. A cell
+// that finds no slot within the probe bound is counted as overflow.
+__device__ __forceinline__ void occ_mark_cell(unsigned long long key, unsigned bit, bool have, const OccRay& g, const OccTable& t) {
+  bool fresh = false;
+  uint32_t slot = 0;
+  if (have) {
+    bool found = false;
+    slot = occ_hash(key, g.mask);
+    for (uint32_t probe = 0; probe < g.max_probe; probe++, slot = (slot + 1) & g.mask) {
+      unsigned long long cur = __hip_atomic_load(&t.keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (cur == kOccEmpty) {
+        cur = atomicCAS(&t.keys[slot], kOccEmpty, key);
+        if (cur == kOccEmpty) {
+          atomicAdd(&t.ctr->size, 1u);
+          cur = key;
+        }
+      }
+      if (cur == key) {
+        found = true;
+        break;
+      }
+    }
+    if (found) {
+      unsigned old = __hip_atomic_load(&t.flags[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (!(old & bit)) {
+        old = atomicOr(&t.flags[slot], bit);
+        fresh = old == 0;
+      }
+    } else {
+      atomicAdd(&t.ctr->overflow, 1ull);
+    }
+  }
+  const unsigned long long mine = __ballot(fresh);
+  if (!mine) return;
+  const int lane = threadIdx.x & 63;
+  const int leader = __ffsll((long long)mine) - 1;
+  unsigned base = 0;
+  if (lane == leader) base = atomicAdd(&t.ctr->touched[g.parity], (unsigned)__popcll(mine));
+  base = __builtin_amdgcn_readlane(base, leader);
+  if (!fresh) return;
+  const uint32_t at = base + __popcll(mine & ((1ull << lane) - 1));
+  if (at < g.slots) t.touched[at] = slot;   // a slot is appended once per scan: the list of `slots` entries always has room
+}
+
+// One axis of computeRayKeys' initialisation (OcTreeBaseImpl.hxx:577-596)
+__device__ __forceinline__ void occ_ray_axis(float dir, unsigned key, float origin, double resolution, int* step, double* tmax,
+                                             double* tdelta) {
+#pragma clang fp contract(off)
+  *step = dir > 0.0f ? 1 : dir < 0.0f ? -1 : 0;
+  *tmax = *tdelta = 1.7976931348623157e308;   // std::numeric_limits<double>::max()
+  if (*step) {
+    double border = ((double)((int)key - 32768) + 0.5) * resolution;   // keyToCoord
+    border += (double)(float)((double)*step * resolution * 0.5);
+    *tmax = (border - (double)origin) / (double)dir;
+    *tdelta = resolution / fabs((double)dir);
+  }
+}
+
+// One ray of computeUpdate, by the whole wavefront (valid: this lane has a point): the range gate, the truncated end beyond it,
+// computeRayKeys (OcTreeBaseImpl.hxx:542-648) with every cell marked free as the DDA reaches it, and the end point marked occupied.
+__device__ __forceinline__ void occ_cast_ray(bool valid, Pt3 p, const float* o, const OccRay& g, const OccTable& t) {
+#pragma clang fp contract(off)
+  bool walking = false, ends = false;
+  unsigned c0 = 0, c1 = 0, c2 = 0, e0 = 0, e1 = 0, e2 = 0;
+  int s0 = 0, s1 = 0, s2 = 0;
+  double t0 = 0., t1 = 0., t2 = 0., d0 = 0., d1 = 0., d2 = 0., length = 0.;
+  if (valid && finite3(p)) {
+    const float ox = o[0], oy = o[1], oz = o[2];
+    float vx = p.x - ox, vy = p.y - oy, vz = p.z - oz;
+    const double n = __dsqrt_rn((double)(vx * vx + vy * vy + vz * vz));   // Vector3::norm: the sum in float
+    const bool within = g.max_range < 0.0 || n <= g.max_range;
+    Pt3 end = p;
+    if (!within) {                      // (p - origin).normalized() * (float)maxrange from the origin
+      if (n > 0) {
+        const float len = (float)n;
+        vx /= len;
+        vy /= len;
+        vz /= len;
+      }
+      const float r = (float)g.max_range;
+      end.x = ox + vx * r;
+      end.y = oy + vy * r;
+      end.z = oz + vz * r;
+    }
+    const bool end_ok = occ_axis(g.factor, end.x, &e0) && occ_axis(g.factor, end.y, &e1) && occ_axis(g.factor, end.z, &e2);
+    ends = within && end_ok;
+    if (end_ok && occ_axis(g.factor, ox, &c0) && occ_axis(g.factor, oy, &c1) && occ_axis(g.factor, oz, &c2) &&
+        !(c0 == e0 && c1 == e1 && c2 == e2)) {
+      walking = true;
+      float dx = end.x - ox, dy = end.y - oy, dz = end.z - oz;
+      const float len = (float)__dsqrt_rn((double)(dx * dx + dy * dy + dz * dz));
+      dx /= len;
+      dy /= len;
+      dz /= len;
+      length = (double)len;
+      occ_ray_axis(dx, c0, ox, g.resolution, &s0, &t0, &d0);
+      occ_ray_axis(dy, c1, oy, g.resolution, &s1, &t1, &d1);
+      occ_ray_axis(dz, c2, oz, g.resolution, &s2, &t2, &d2);
+    }
+  }
+  // The origin cell first, then one cell per step until the end cell's key or the ray's length is reached; the end cell is not
+  // part of the ray. The step count is bounded whatever the input: the wavefront leaves the loop when its last lane has.
+  int steps = 0;
+  while (__ballot(walking)) {
+    occ_mark_cell((unsigned long long)c0 << 32 | (unsigned long long)c1 << 16 | c2, kOccFree, walking, g, t);
+    if (walking) {
+      const int dim = t0 < t1 ? (t0 < t2 ? 0 : 2) : (t1 < t2 ? 1 : 2);   // the strict < of the reference: ties go to the later axis
+      if (dim == 0) {
+        c0 = (c0 + s0) & 0xFFFF;
+        t0 += d0;
+      } else if (dim == 1) {
+        c1 = (c1 + s1) & 0xFFFF;
+        t1 += d1;
+      } else {
+        c2 = (c2 + s2) & 0xFFFF;
+        t2 += d2;
+      }
+      if ((c0 == e0 && c1 == e1 && c2 == e2) || fmin(fmin(t0, t1), t2) > length || ++steps >= kOccMaxSteps) walking = false;
+    }
+  }
+  occ_mark_cell((unsigned long long)e0 << 32 | (unsigned long long)e1 << 16 | e2, kOccOccupied, ends, g, t);
+}
+
+// mark, cloud form: one lane per point of d_xyz
+__global__ void __launch_bounds__(256) occ_rays_mark_cloud_kernel(const float* __restrict__ xyz, size_t n, OccPose origin, OccRay g,
+                                                                   OccTable t) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  Pt3 p = nan3();
+  if (i < n) p = Pt3{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+  const float o[3] = {origin.t[3], origin.t[7], origin.t[11]};
+  occ_cast_ray(i < n, p, o, g, t);
+}
+
+// mark, plane form: one lane per pixel of one plane, through the front half of the hit insert; the origin is the pose's translation
+__global__ void __launch_bounds__(256) occ_rays_mark_plane_kernel(const int16_t* __restrict__ plane, OccGeom pg, sbm_stereo_model m,
+                                                                   OccPose pose, OccRay g, OccTable t) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  Pt3 p = nan3();
+  const bool valid = i < pg.W * pg.H && occ_world_point(plane, i, pg, m, pose.t, &p);
+  const float o[3] = {pose.t[3], pose.t[7], pose.t[11]};
+  occ_cast_ray(valid, p, o, g, t);
+}
+
+// apply: every slot the scan touched gets its one update (updateNodeLogOdds, OccupancyOcTreeBase.hxx:1097-1106; an absent voxel
+// starts at 0, which is what a fresh slot holds), occupied before free, and its flag word is cleared for the next scan. The
+// early return of updateNode for a leaf at its clamp gives what the clamp gives. No atomics: a slot is in the list once. The
+// two counts of OccCounters::touched take turns, so that no scan needs a memset between its two launches and the next scan's.
+__global__ void __launch_bounds__(256) occ_rays_apply_kernel(OccRay g, OccTable t) {
+#pragma clang fp contract(off)
+  const uint32_t n = min(t.ctr->touched[g.parity], g.slots);
+  if (blockIdx.x == 0 && threadIdx.x == 0) t.ctr->touched[g.parity ^ 1] = 0;   // the next scan's count; nobody reads it now
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const uint32_t slot = t.touched[i];
+    if (slot >= g.slots) continue;
+    float v = t.logodds[slot] + ((t.flags[slot] & kOccOccupied) ? g.hit : g.miss);
+    if (v < g.cmin) v = g.cmin;
+    else if (v > g.cmax) v = g.cmax;
+    t.logodds[slot] = v;
+    t.flags[slot] = 0;
+  }
 }
 
 __global__ void __launch_bounds__(256) occ_compact_kernel(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ hits,
@@ -217,6 +419,9 @@ static int occ_clear(sbm_occ_map* map) {
   HIPCHK(h, hipMemsetAsync(map->keys.p, 0xFF, (size_t)map->slots * 8, h->stream));
   HIPCHK(h, hipMemsetAsync(map->hits.p, 0, (size_t)map->slots * 4, h->stream));
   HIPCHK(h, hipMemsetAsync(map->ctr.p, 0, sizeof(OccCounters), h->stream));
+  if (map->flags.p) HIPCHK(h, hipMemsetAsync(map->flags.p, 0, (size_t)map->slots * 4, h->stream));
+  map->mode = kOccModeNone;
+  map->scan = 0;
   return SBM_OK;
 }
 
@@ -231,18 +436,27 @@ static int occ_check_insert(const sbm_occ_map* map, int n, const void* disp, int
 }
 
 // Stage times: an insert and a fetch are separate calls that share the clock's two marks, and each keeps the other's last time.
-enum OccStage { kOccInsert, kOccFetch, kOccStageCount };
-enum OccMark { kOccBegin, kOccEnd, kOccMarkCount };
-static const char* const kOccNames[] = {"occ_insert", "occ_fetch"};
+enum OccStage { kOccInsert, kOccFetch, kOccRaysMark, kOccRaysApply, kOccStageCount };
+enum OccMark { kOccBegin, kOccEnd, kOccMid, kOccMarkCount };
+static const char* const kOccNames[] = {"occ_insert", "occ_fetch", "occ_rays_mark", "occ_rays_apply"};
 StageTable occ_stages() { return stage_table<kOccStageCount, kOccMarkCount>(kOccNames); }
+
+// A call begins: it times stages a and b (the same for one) from zero and keeps the last times of the family's other stages.
+static hipError_t occ_clock_start(sbm_handle* h, int a, int b) {
+  StageClock& clk = h->occ.clock;
+  float keep[kOccStageCount];
+  for (int i = 0; i < kOccStageCount; i++) keep[i] = clk.ms[i];
+  const hipError_t e = clk.start(occ_stages(), h->profiling != 0);
+  for (int i = 0; i < kOccStageCount; i++)
+    if (clk.on && i != a && i != b) clk.ms[i] = keep[i];
+  return e;
+}
 
 static int occ_insert_run(sbm_occ_map* map, int n, const int16_t* d_disp, int W, int H, int scale, const sbm_stereo_model* model,
                           const float* poses, int sync) {
   sbm_handle* h = map->h;
   StageClock& clk = h->occ.clock;
-  const float fetch_ms = clk.ms[kOccFetch];
-  HIPCHK(h, clk.start(occ_stages(), h->profiling != 0));
-  clk.ms[kOccFetch] = fetch_ms;
+  HIPCHK(h, occ_clock_start(h, kOccInsert, kOccInsert));
   OccGeom g;
   g.W = W;
   g.H = H;
@@ -275,9 +489,7 @@ static int occ_insert_run(sbm_occ_map* map, int n, const int16_t* d_disp, int W,
 static int occ_fetch_run(sbm_occ_map* map, unsigned long long* d_keys, unsigned* d_hits, size_t cap, size_t* count) {
   sbm_handle* h = map->h;
   StageClock& clk = h->occ.clock;
-  const float insert_ms = clk.ms[kOccInsert];
-  HIPCHK(h, clk.start(occ_stages(), h->profiling != 0));
-  clk.ms[kOccInsert] = insert_ms;
+  HIPCHK(h, occ_clock_start(h, kOccFetch, kOccFetch));
   OccCounters c;
   int st = occ_read_counters(map, &c);
   if (st != SBM_OK) return st;
@@ -314,6 +526,126 @@ static int occ_fetch_run(sbm_occ_map* map, unsigned long long* d_keys, unsigned*
   return c.overflow ? SBM_ERR_OCC_FULL : SBM_OK;
 }
 
+// ---- log-odds mode, host side ----------------------------------------------------------------------------------------------
+static float occ_logodds(double p) { return (float)log(p / (1. - p)); }   // octomap_utils.h
+
+static int occ_ray_params_check(const sbm_occ_ray_params* p) {
+  if (!p) return SBM_ERR_NULL;
+  const double prob[5] = {p->prob_hit, p->prob_miss, p->clamp_min, p->clamp_max, p->occupancy_thres};
+  for (double v : prob)
+    if (!(v > 0. && v < 1.)) return SBM_ERR_SIZE;   // NaN fails both
+  if (p->prob_hit < 0.5 || p->prob_miss > 0.5 || !(p->clamp_min < p->clamp_max) || std::isnan(p->max_range)) return SBM_ERR_SIZE;
+  return SBM_OK;
+}
+
+// The first log-odds insert after create or reset allocates the flag words and the touched list and fixes the mode.
+static int occ_rays_begin(sbm_occ_map* map, const sbm_occ_ray_params* p, OccRay* g, OccTable* t) {
+  sbm_handle* h = map->h;
+  if (map->mode == kOccModeHits) return SBM_ERR_UNSUPPORTED;
+  if (!map->flags.p) {
+    HIPCHK(h, map->flags.grow((size_t)map->slots * 4, h->stream));
+    HIPCHK(h, hipMemsetAsync(map->flags.p, 0, (size_t)map->slots * 4, h->stream));
+  }
+  HIPCHK(h, map->touched.grow((size_t)map->slots * 4, h->stream));
+  map->mode = kOccModeLogOdds;
+  g->max_range = p->max_range;
+  g->resolution = map->p.resolution;
+  g->factor = 1. / map->p.resolution;
+  g->hit = occ_logodds(p->prob_hit);
+  g->miss = occ_logodds(p->prob_miss);
+  g->cmin = occ_logodds(p->clamp_min);
+  g->cmax = occ_logodds(p->clamp_max);
+  g->mask = map->slots - 1;
+  g->max_probe = std::min(map->slots, kOccMaxProbe);
+  g->slots = map->slots;
+  g->parity = 0;
+  t->keys = map->keys.as<unsigned long long>();
+  t->logodds = map->hits.as<float>();
+  t->flags = map->flags.as<unsigned>();
+  t->touched = map->touched.as<unsigned>();
+  t->ctr = map->ctr.as<OccCounters>();
+  return SBM_OK;
+}
+
+// One scan: `mark` launches its mark kernel; the apply launch follows in stream order.
+template <class Mark> static int occ_rays_scan(sbm_occ_map* map, OccRay& g, const OccTable& t, Mark mark) {
+  sbm_handle* h = map->h;
+  StageClock& clk = h->occ.clock;
+  g.parity = map->scan & 1;
+  HIPCHK(h, clk.mark(kOccBegin, h->stream));
+  mark();
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, clk.mark(kOccMid, h->stream));
+  hipLaunchKernelGGL(occ_rays_apply_kernel, dim3(std::min((map->slots + 255) / 256, 1024u)), dim3(256), 0, h->stream, g, t);
+  HIPCHK(h, hipGetLastError());
+  map->scan++;
+  HIPCHK(h, clk.mark(kOccEnd, h->stream));
+  HIPCHK(h, clk.add(kOccRaysMark, kOccBegin, kOccMid));
+  HIPCHK(h, clk.add(kOccRaysApply, kOccMid, kOccEnd));
+  return SBM_OK;
+}
+
+static int occ_rays_end(sbm_occ_map* map, int sync) {
+  if (!sync && !map->h->occ.clock.on) return SBM_OK;
+  OccCounters c;
+  const int st = occ_read_counters(map, &c);
+  if (st != SBM_OK) return st;
+  return c.overflow ? SBM_ERR_OCC_FULL : SBM_OK;
+}
+
+static int occ_check_cloud(const sbm_occ_map* map, size_t n, const void* xyz, const float* origin, const sbm_occ_ray_params* p) {
+  if (!map || !origin || !p || (n > 0 && !xyz)) return SBM_ERR_NULL;
+  const int st = occ_ray_params_check(p);
+  if (st != SBM_OK) return st;
+  if (n > ((size_t)1 << 30)) return SBM_ERR_UNSUPPORTED;
+  return SBM_OK;
+}
+
+static int occ_cloud_run(sbm_occ_map* map, size_t n, const float* d_xyz, const float* origin, const sbm_occ_ray_params* p, int sync) {
+  sbm_handle* h = map->h;
+  OccRay g;
+  OccTable t;
+  int st = occ_rays_begin(map, p, &g, &t);
+  if (st != SBM_OK) return st;
+  HIPCHK(h, occ_clock_start(h, kOccRaysMark, kOccRaysApply));
+  if (n) {
+    OccPose o;
+    memset(&o, 0, sizeof(o));
+    o.t[3] = origin[0], o.t[7] = origin[1], o.t[11] = origin[2];
+    st = occ_rays_scan(map, g, t, [&] {
+      hipLaunchKernelGGL(occ_rays_mark_cloud_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, d_xyz, n, o, g, t);
+    });
+    if (st != SBM_OK) return st;
+  }
+  return occ_rays_end(map, sync);
+}
+
+static int occ_planes_run(sbm_occ_map* map, int n, const int16_t* d_disp, int W, int H, int scale, const sbm_stereo_model* model,
+                          const float* poses, const sbm_occ_ray_params* p, int sync) {
+  sbm_handle* h = map->h;
+  OccRay g;
+  OccTable t;
+  int st = occ_rays_begin(map, p, &g, &t);
+  if (st != SBM_OK) return st;
+  HIPCHK(h, occ_clock_start(h, kOccRaysMark, kOccRaysApply));
+  OccGeom pg;
+  memset(&pg, 0, sizeof(pg));
+  pg.W = W;
+  pg.H = H;
+  pg.scale = scale;
+  const size_t plane = (size_t)W * H;
+  for (int i = 0; i < n; i++) {   // plane i is scan i: its launches follow those of plane i - 1 in stream order
+    OccPose pose;
+    memcpy(pose.t, poses + (size_t)12 * i, sizeof(pose.t));
+    st = occ_rays_scan(map, g, t, [&] {
+      hipLaunchKernelGGL(occ_rays_mark_plane_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, h->stream, d_disp + plane * i,
+                         pg, *model, pose, g, t);
+    });
+    if (st != SBM_OK) return st;
+  }
+  return occ_rays_end(map, sync);
+}
+
 // ---- the .bt stream ------------------------------------------------------------------------------------------------------
 // Morton code of a packed key: per bit, from the top, z y x -- a child index as computeChildIdx gives it
 static uint64_t occ_morton(uint64_t key) {
@@ -323,12 +655,14 @@ static uint64_t occ_morton(uint64_t key) {
   return m;
 }
 
-// The inner node that covers codes [lo, hi) (sorted, distinct) with `level` key bits still undecided (16 at the root): its two
-// bytes, then its inner children depth first. A child whose range holds all 8^(level-1) codes below it is what prune() leaves
-// as one leaf. Returns the nodes written, this one included.
+// A leaf of the stream: its Morton code above bit 0, and in bit 0 whether toMaxLikelihood makes it occupied. Sorting the words
+// sorts the codes.
+// The inner node that covers leaves [lo, hi) (sorted, distinct codes) with `level` key bits still undecided (16 at the root): its
+// two bytes, then its inner children depth first. A child whose range holds all 8^(level-1) codes below it, all of one kind, is
+// what prune() leaves as one leaf of that kind. Returns the nodes written, this one included.
 static size_t occ_write_node(const uint64_t* lo, const uint64_t* hi, int level, std::vector<uint8_t>& body) {
-  const int shift = 3 * (level - 1);
-  const uint64_t full = (uint64_t)1 << shift;   // 8^(level-1)
+  const int shift = 3 * (level - 1) + 1;
+  const uint64_t full = (uint64_t)1 << (shift - 1);   // 8^(level-1)
   const uint64_t* edge[9];
   edge[0] = lo;
   for (int c = 0; c < 8; c++) {
@@ -337,26 +671,73 @@ static size_t occ_write_node(const uint64_t* lo, const uint64_t* hi, int level, 
     edge[c + 1] = e;
   }
   uint8_t byte[2] = {0, 0};
+  bool inner[8];
   size_t nodes = 1;
   for (int c = 0; c < 8; c++) {
     const uint64_t cnt = (uint64_t)(edge[c + 1] - edge[c]);
+    inner[c] = false;
     if (!cnt) continue;
-    byte[c / 4] |= (uint8_t)((cnt == full ? 2 : 3) << (2 * (c % 4)));   // bits (2c, 2c+1): 0,1 occupied leaf; 1,1 inner
-    if (cnt == full) nodes++;
+    const uint64_t kind = *edge[c] & 1;
+    inner[c] = cnt != full;
+    for (const uint64_t* e = edge[c]; !inner[c] && e < edge[c + 1]; e++) inner[c] = (*e & 1) != kind;
+    // bits (2c, 2c+1): 0,1 occupied leaf; 1,0 free leaf; 1,1 inner
+    byte[c / 4] |= (uint8_t)((inner[c] ? 3 : kind ? 2 : 1) << (2 * (c % 4)));
+    if (!inner[c]) nodes++;
   }
   body.push_back(byte[0]);
   body.push_back(byte[1]);
-  for (int c = 0; c < 8; c++) {
-    const uint64_t cnt = (uint64_t)(edge[c + 1] - edge[c]);
-    if (cnt && cnt != full) nodes += occ_write_node(edge[c], edge[c + 1], level - 1, body);
-  }
+  for (int c = 0; c < 8; c++)
+    if (inner[c]) nodes += occ_write_node(edge[c], edge[c + 1], level - 1, body);
   return nodes;
+}
+
+// AbstractOccupancyOcTree::writeBinaryConst of the sorted leaves; `res` as operator<<(double) prints it (%g)
+static int occ_write_stream(const std::vector<uint64_t>& leaf, double resolution, const char* path) {
+  std::vector<uint8_t> body;
+  size_t nodes = 0;
+  try {
+    if (!leaf.empty()) nodes = occ_write_node(leaf.data(), leaf.data() + leaf.size(), 16, body);
+  } catch (const std::bad_alloc&) {
+    return SBM_ERR_NOMEM;
+  }
+  FILE* f = fopen(path, "wb");
+  if (!f) return SBM_ERR_UNSUPPORTED;
+  bool ok = fprintf(f,
+                    "# Octomap OcTree binary file\n# (feel free to add / change comments, but leave the first line as it is!)\n#\n"
+                    "id OcTree\nsize %zu\nres %g\ndata\n",
+                    nodes, resolution) > 0;
+  ok = ok && (body.empty() || fwrite(body.data(), 1, body.size(), f) == body.size());
+  ok = (fclose(f) == 0) && ok;
+  return ok ? SBM_OK : SBM_ERR_UNSUPPORTED;
 }
 
 }  // namespace sbm
 
 // ---- entry points --------------------------------------------------------------------------------------------------------
 using namespace sbm;
+
+// Sorted (key, payload) of the map into host memory, through the handle's staging
+static int occ_fetch_host(sbm_occ_map* map, uint64_t* keys, uint32_t* hits, size_t cap, size_t* count) {
+  sbm_handle* h = map->h;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  OccCounters c;
+  int st = occ_read_counters(map, &c);
+  if (st != SBM_OK) return st;
+  *count = c.size;
+  if (c.size > cap) return SBM_ERR_SIZE;
+  if (!c.size) return c.overflow ? SBM_ERR_OCC_FULL : SBM_OK;
+  const size_t kb = ((size_t)c.size * 8 + 255) & ~(size_t)255;
+  HIPCHK(h, h->occ.io.grow(kb + (size_t)c.size * 4, h->stream));
+  unsigned long long* d_k = h->occ.io.as<unsigned long long>();
+  unsigned* d_v = (unsigned*)((char*)h->occ.io.p + kb);
+  st = occ_fetch_run(map, d_k, d_v, c.size, count);
+  if (st != SBM_OK && st != SBM_ERR_OCC_FULL) return st;
+  HIPCHK(h, hipMemcpyAsync(keys, d_k, *count * 8, hipMemcpyDeviceToHost, h->stream));
+  if (hits) HIPCHK(h, hipMemcpyAsync(hits, d_v, *count * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return st;
+}
 
 extern "C" {
 
@@ -431,9 +812,10 @@ int sbm_occ_insert_device(sbm_occ_map* map, int n, const void* d_disp, int width
                           const sbm_stereo_model* model, const float* poses, int sync) {
   const int st = occ_check_insert(map, n, d_disp, width, height, scale, model, poses);
   if (st != SBM_OK) return st;
-  if ((uintptr_t)d_disp & 1) return SBM_ERR_UNSUPPORTED;
+  if ((uintptr_t)d_disp & 1 || map->mode == kOccModeLogOdds) return SBM_ERR_UNSUPPORTED;
   DeviceScope dscope(map->h->device);
   HIPCHK(map->h, dscope.enter());
+  map->mode = kOccModeHits;
   return occ_insert_run(map, n, (const int16_t*)d_disp, width, height, scale, model, poses, sync);
 }
 
@@ -441,12 +823,14 @@ int sbm_occ_insert(sbm_occ_map* map, int n, const int16_t* disp, int width, int 
                    const float* poses) {
   const int st = occ_check_insert(map, n, disp, width, height, scale, model, poses);
   if (st != SBM_OK) return st;
+  if (map->mode == kOccModeLogOdds) return SBM_ERR_UNSUPPORTED;
   sbm_handle* h = map->h;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
   const size_t bytes = (size_t)n * width * height * sizeof(int16_t);
   HIPCHK(h, h->occ.io.grow(bytes, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->occ.io.p, disp, bytes, hipMemcpyHostToDevice, h->stream));
+  map->mode = kOccModeHits;
   return occ_insert_run(map, n, h->occ.io.as<int16_t>(), width, height, scale, model, poses, 1);
 }
 
@@ -472,7 +856,7 @@ int sbm_occ_overflow(sbm_occ_map* map, uint64_t* overflow) {
 
 int sbm_occ_fetch_device(sbm_occ_map* map, void* d_keys, void* d_hits, size_t cap, size_t* count) {
   if (!map || !count || (cap > 0 && !d_keys)) return SBM_ERR_NULL;
-  if (((uintptr_t)d_keys & 7) || ((uintptr_t)d_hits & 3)) return SBM_ERR_UNSUPPORTED;
+  if (((uintptr_t)d_keys & 7) || ((uintptr_t)d_hits & 3) || map->mode == kOccModeLogOdds) return SBM_ERR_UNSUPPORTED;
   DeviceScope dscope(map->h->device);
   HIPCHK(map->h, dscope.enter());
   return occ_fetch_run(map, (unsigned long long*)d_keys, (unsigned*)d_hits, cap, count);
@@ -480,55 +864,132 @@ int sbm_occ_fetch_device(sbm_occ_map* map, void* d_keys, void* d_hits, size_t ca
 
 int sbm_occ_fetch(sbm_occ_map* map, uint64_t* keys, uint32_t* hits, size_t cap, size_t* count) {
   if (!map || !count || (cap > 0 && !keys)) return SBM_ERR_NULL;
-  sbm_handle* h = map->h;
-  DeviceScope dscope(h->device);
-  HIPCHK(h, dscope.enter());
-  OccCounters c;
-  int st = occ_read_counters(map, &c);
-  if (st != SBM_OK) return st;
-  *count = c.size;
-  if (c.size > cap) return SBM_ERR_SIZE;
-  if (!c.size) return c.overflow ? SBM_ERR_OCC_FULL : SBM_OK;
-  const size_t kb = ((size_t)c.size * 8 + 255) & ~(size_t)255;
-  HIPCHK(h, h->occ.io.grow(kb + (size_t)c.size * 4, h->stream));
-  unsigned long long* d_k = h->occ.io.as<unsigned long long>();
-  unsigned* d_v = (unsigned*)((char*)h->occ.io.p + kb);
-  st = occ_fetch_run(map, d_k, d_v, c.size, count);
-  if (st != SBM_OK && st != SBM_ERR_OCC_FULL) return st;
-  HIPCHK(h, hipMemcpyAsync(keys, d_k, *count * 8, hipMemcpyDeviceToHost, h->stream));
-  if (hits) HIPCHK(h, hipMemcpyAsync(hits, d_v, *count * 4, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return st;
+  if (map->mode == kOccModeLogOdds) return SBM_ERR_UNSUPPORTED;
+  return occ_fetch_host(map, keys, hits, cap, count);
 }
 
 int sbm_occ_write_binary(const uint64_t* keys, size_t n, double resolution, const char* path) {
   if (!path || (n > 0 && !keys)) return SBM_ERR_NULL;
   if (!std::isfinite(resolution) || !(resolution > 0.)) return SBM_ERR_SIZE;
-  std::vector<uint64_t> code;
-  std::vector<uint8_t> body;
-  size_t nodes = 0;
+  std::vector<uint64_t> leaf;
   try {
-    code.reserve(n);
+    leaf.reserve(n);
     for (size_t i = 0; i < n; i++) {
       if (keys[i] >> 48) return SBM_ERR_SIZE;
-      code.push_back(occ_morton(keys[i]));
+      leaf.push_back(occ_morton(keys[i]) << 1 | 1);
     }
-    std::sort(code.begin(), code.end());
-    code.erase(std::unique(code.begin(), code.end()), code.end());
-    if (!code.empty()) nodes = occ_write_node(code.data(), code.data() + code.size(), 16, body);
+    std::sort(leaf.begin(), leaf.end());
+    leaf.erase(std::unique(leaf.begin(), leaf.end()), leaf.end());
   } catch (const std::bad_alloc&) {
     return SBM_ERR_NOMEM;
   }
-  FILE* f = fopen(path, "wb");
-  if (!f) return SBM_ERR_UNSUPPORTED;
-  // AbstractOccupancyOcTree::writeBinaryConst; `res` as operator<<(double) prints it (%g)
-  bool ok = fprintf(f,
-                    "# Octomap OcTree binary file\n# (feel free to add / change comments, but leave the first line as it is!)\n#\n"
-                    "id OcTree\nsize %zu\nres %g\ndata\n",
-                    nodes, resolution) > 0;
-  ok = ok && (body.empty() || fwrite(body.data(), 1, body.size(), f) == body.size());
-  ok = (fclose(f) == 0) && ok;
-  return ok ? SBM_OK : SBM_ERR_UNSUPPORTED;
+  return occ_write_stream(leaf, resolution, path);
+}
+
+int sbm_occ_write_binary_logodds(const uint64_t* keys, const float* logodds, size_t n, double resolution, float occupancy_thres_log,
+                                 const char* path) {
+  if (!path || (n > 0 && (!keys || !logodds))) return SBM_ERR_NULL;
+  if (!std::isfinite(resolution) || !(resolution > 0.) || std::isnan(occupancy_thres_log)) return SBM_ERR_SIZE;
+  std::vector<uint64_t> leaf;
+  try {
+    leaf.reserve(n);
+    for (size_t i = 0; i < n; i++) {
+      if (keys[i] >> 48 || std::isnan(logodds[i])) return SBM_ERR_SIZE;
+      leaf.push_back(occ_morton(keys[i]) << 1 | (logodds[i] >= occupancy_thres_log ? 1 : 0));   // isNodeOccupied
+    }
+    std::sort(leaf.begin(), leaf.end());
+    for (size_t i = 1; i < leaf.size(); i++)
+      if (leaf[i] >> 1 == leaf[i - 1] >> 1) return SBM_ERR_SIZE;   // one value per voxel
+  } catch (const std::bad_alloc&) {
+    return SBM_ERR_NOMEM;
+  }
+  return occ_write_stream(leaf, resolution, path);
+}
+
+void sbm_occ_ray_params_default(sbm_occ_ray_params* p) {
+  if (!p) return;
+  p->prob_hit = 0.7;
+  p->prob_miss = 0.4;
+  p->clamp_min = 0.1192;
+  p->clamp_max = 0.971;
+  p->occupancy_thres = 0.5;
+  p->max_range = -1.;
+}
+
+int sbm_occ_ray_params_validate(const sbm_occ_ray_params* p) { return occ_ray_params_check(p); }
+
+int sbm_occ_ray_logodds(const sbm_occ_ray_params* p, float logodds[5]) {
+  if (!logodds) return SBM_ERR_NULL;
+  const int st = occ_ray_params_check(p);
+  if (st != SBM_OK) return st;
+  const double prob[5] = {p->prob_hit, p->prob_miss, p->clamp_min, p->clamp_max, p->occupancy_thres};
+  for (int i = 0; i < 5; i++) logodds[i] = occ_logodds(prob[i]);
+  return SBM_OK;
+}
+
+int sbm_occ_insert_cloud_device(sbm_occ_map* map, size_t n_points, const void* d_xyz, const float* origin,
+                                const sbm_occ_ray_params* params, int sync) {
+  const int st = occ_check_cloud(map, n_points, d_xyz, origin, params);
+  if (st != SBM_OK) return st;
+  if ((uintptr_t)d_xyz & 3) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(map->h->device);
+  HIPCHK(map->h, dscope.enter());
+  return occ_cloud_run(map, n_points, (const float*)d_xyz, origin, params, sync);
+}
+
+int sbm_occ_insert_cloud(sbm_occ_map* map, size_t n_points, const float* xyz, const float* origin, const sbm_occ_ray_params* params) {
+  const int st = occ_check_cloud(map, n_points, xyz, origin, params);
+  if (st != SBM_OK) return st;
+  if (map->mode == kOccModeHits) return SBM_ERR_UNSUPPORTED;
+  sbm_handle* h = map->h;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  if (n_points) {
+    HIPCHK(h, h->occ.io.grow(n_points * 12, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->occ.io.p, xyz, n_points * 12, hipMemcpyHostToDevice, h->stream));
+  }
+  return occ_cloud_run(map, n_points, h->occ.io.as<float>(), origin, params, 1);
+}
+
+int sbm_occ_insert_rays_device(sbm_occ_map* map, int n, const void* d_disp, int width, int height, int scale,
+                               const sbm_stereo_model* model, const float* poses, const sbm_occ_ray_params* params, int sync) {
+  int st = occ_check_insert(map, n, d_disp, width, height, scale, model, poses);
+  if (st == SBM_OK) st = occ_ray_params_check(params);
+  if (st != SBM_OK) return st;
+  if ((uintptr_t)d_disp & 1) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(map->h->device);
+  HIPCHK(map->h, dscope.enter());
+  return occ_planes_run(map, n, (const int16_t*)d_disp, width, height, scale, model, poses, params, sync);
+}
+
+int sbm_occ_insert_rays(sbm_occ_map* map, int n, const int16_t* disp, int width, int height, int scale, const sbm_stereo_model* model,
+                        const float* poses, const sbm_occ_ray_params* params) {
+  int st = occ_check_insert(map, n, disp, width, height, scale, model, poses);
+  if (st == SBM_OK) st = occ_ray_params_check(params);
+  if (st != SBM_OK) return st;
+  if (map->mode == kOccModeHits) return SBM_ERR_UNSUPPORTED;
+  sbm_handle* h = map->h;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  const size_t bytes = (size_t)n * width * height * sizeof(int16_t);
+  HIPCHK(h, h->occ.io.grow(bytes, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->occ.io.p, disp, bytes, hipMemcpyHostToDevice, h->stream));
+  return occ_planes_run(map, n, h->occ.io.as<int16_t>(), width, height, scale, model, poses, params, 1);
+}
+
+int sbm_occ_fetch_logodds_device(sbm_occ_map* map, void* d_keys, void* d_logodds, size_t cap, size_t* count) {
+  if (!map || !count || (cap > 0 && !d_keys)) return SBM_ERR_NULL;
+  if (((uintptr_t)d_keys & 7) || ((uintptr_t)d_logodds & 3)) return SBM_ERR_UNSUPPORTED;
+  if (map->mode == kOccModeHits) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(map->h->device);
+  HIPCHK(map->h, dscope.enter());
+  return occ_fetch_run(map, (unsigned long long*)d_keys, (unsigned*)d_logodds, cap, count);   // the float's bits are the payload
+}
+
+int sbm_occ_fetch_logodds(sbm_occ_map* map, uint64_t* keys, float* logodds, size_t cap, size_t* count) {
+  if (!map || !count || (cap > 0 && !keys)) return SBM_ERR_NULL;
+  if (map->mode == kOccModeHits) return SBM_ERR_UNSUPPORTED;
+  return occ_fetch_host(map, keys, (uint32_t*)logodds, cap, count);
 }
 
 }  // extern "C"
