@@ -1071,7 +1071,7 @@ int sbm_occ_write_binary(const uint64_t* keys, size_t n, double resolution, cons
  *             v += u in float; v = cmin if v < cmin, else cmax if v > cmax (updateNodeLogOdds; updateNode's early return for a
  *             leaf at its clamp gives the same value).
  *  order      scans are applied in call order and plane order; through the clamps the result depends on it.
- *  Not provided: discretize, bounding boxes, change detection, insertPointCloudRays, castRay.
+ *  Not provided: discretize, bounding boxes, change detection, insertPointCloudRays.
  *  Mode. A map's mode is fixed by its first accepted insert after create or reset: hits (sbm_occ_insert*) or log-odds
  *  (sbm_occ_insert_cloud*, sbm_occ_insert_rays*). An insert or a fetch of the other kind returns SBM_ERR_UNSUPPORTED and changes
  *  nothing; a fetch of either kind serves an empty map. sbm_occ_size, sbm_occ_overflow and sbm_occ_reset serve both.
@@ -1134,6 +1134,97 @@ int sbm_occ_fetch_logodds(sbm_occ_map* map, uint64_t* keys, float* logodds, size
  * (resolution, a key above 48 bits, a key given twice, a NaN), SBM_ERR_NOMEM, SBM_ERR_UNSUPPORTED (the file cannot be written). */
 int sbm_occ_write_binary_logodds(const uint64_t* keys, const float* logodds, size_t n, double resolution, float occupancy_thres_log,
                                  const char* path);
+
+/* ---- occupancy map: queries, search and castRay (OcTreeBaseImpl.hxx:408-470, OccupancyOcTreeBase.hxx:645-765) -----------------
+ * The read side of sbm_occ_map: "what is at this point?" and "what does this ray hit?", answered on the device for batches of
+ * points, rays, or the pixels of a virtual camera, from the table the inserts left in device memory. Both are stated per
+ * depth-16 voxel, as the inserts are: pruning and expansion inside octomap never change a depth-16 value, so search(point) and
+ * castRay on octomap's tree answer exactly this. tests/occupancy_query_cases.py is a literal transcription of this text, and
+ * tests/golden/occupancy_query.npz holds what the reference's own octomap answered, bit for bit. The calls never change the map
+ * and never return SBM_ERR_OCC_FULL. IEEE binary32 / binary64 as written, no contraction, correctly rounded sqrt and division:
+ *  voxel      log-odds mode: a stored voxel is OCCUPIED iff logodds >= occupancy_thres_log (isNodeOccupied), else FREE; a key
+ *             that is not stored is UNKNOWN. Hit mode: a stored voxel is OCCUPIED, the threshold is ignored; a key that is not
+ *             stored is UNKNOWN. A map without a mode (empty since create or reset): every key is UNKNOWN. A voxel that
+ *             overflowed out of the table (sbm_occ_overflow) is not stored and reads as UNKNOWN.
+ *  key        coordToKeyChecked per axis as the inserts state it: (int)floor(factor * (double)coord) + 32768 with factor = 1. /
+ *             resolution, kept iff 0 <= . < 65536; a coordinate that is not finite has no key.
+ *  centre     keyToCoord(k) = (float)(((double)(k - 32768) + 0.5) * resolution) per axis.
+ *  search     per point: SBM_OCC_CELL_OUT when the point has no key, else the voxel's state; with it a 4-byte value: in log-odds
+ *             mode the float log-odds, NaN (0x7FC00000) where nothing is stored or the point has no key; in hit mode the uint32
+ *             hit count, 0 there; without a mode 0.
+ *  castRay(origin, directionP, end, ignore_unknown, max_range), in the order of the source:
+ *   1 origin  key = coordToKeyChecked(origin); none: SBM_OCC_RAY_NONE.
+ *   2 start   the origin's voxel, BEFORE the direction is looked at: OCCUPIED -> SBM_OCC_RAY_HIT, end = centre(key), even for a
+ *             zero direction; UNKNOWN and ignore_unknown == 0 -> SBM_OCC_RAY_UNKNOWN, end = centre(key).
+ *   3 normal  direction = directionP.normalized(): len = sqrt((double)(x * x + y * y + z * z)), the sum in FLOAT left to right;
+ *             when len > 0 each component is divided by (float)len in float (Vector3.h:260-282).
+ *   4 steps   per axis step = 1 if direction > 0, -1 if direction < 0, else 0 (zero and NaN give 0). Where step != 0:
+ *             border = ((double)(key - 32768) + 0.5) * resolution, border += (double)step * resolution * 0.5 -- a DOUBLE
+ *             increment, where computeRayKeys of the insert casts that term to float --, tMax = (border - (double)origin) /
+ *             (double)direction, tDelta = resolution / |(double)direction|; else both the largest double. All three steps 0
+ *             (a zero, NaN or infinite directionP: inf / inf is NaN, finite / inf is 0): SBM_OCC_RAY_NONE.
+ *   5 loop    dim = the axis with the smallest tMax by the insert's strict < (x only if below y and z, else y only if below z,
+ *             else z). If step[dim] < 0 and key[dim] == 0, or step[dim] > 0 and key[dim] == 65535: SBM_OCC_RAY_BOUNDS, end =
+ *             centre(key), tested BEFORE the advance. Else key[dim] += step[dim], tMax[dim] += tDelta[dim], end = centre(key).
+ *             Only when max_range > 0 (0 means no limit, like any negative value): dist = 0.0; dist += (double)((end.x -
+ *             origin.x) * (end.x - origin.x)), then y, then z -- float differences, float products, a double sum (:741-749);
+ *             dist > max_range * max_range (double): SBM_OCC_RAY_RANGE. Then the voxel of key: OCCUPIED -> SBM_OCC_RAY_HIT;
+ *             UNKNOWN and ignore_unknown == 0 -> SBM_OCC_RAY_UNKNOWN; else the next step. On the device the loop is also
+ *             bounded by 3 * 65536 steps, which no ray reaches: each step moves one key one cell towards its limit.
+ *  One status per ray (int32) and one end (three floats):
+ *   SBM_OCC_RAY_HIT      the only case where octomap returns true; end = centre of the occupied cell.
+ *   SBM_OCC_RAY_RANGE    the ray left max_range; end = centre of the cell that left it.
+ *   SBM_OCC_RAY_UNKNOWN  the ray met an unknown cell with ignore_unknown == 0; end = its centre (the origin's cell included).
+ *   SBM_OCC_RAY_BOUNDS   the ray reached the edge of the key space; end = centre of the last cell inside it.
+ *   SBM_OCC_RAY_NONE     no key for the origin, or no direction; end = three NaN (octomap leaves its `end` untouched there).
+ *  view       sbm_occ_cast_view_device casts one ray per pixel (row, col) of a width x height virtual camera: q = ((float)
+ *             (((double)(col * scale) - cx_l) / fx_l), (float)(((double)(row * scale) - cy_l) / fy_l), 1.0f); T(p) =
+ *             transformPoint(transformPoint(p, model.local) when model.has_local, pose), the transform of the inserts; origin
+ *             o = T((0, 0, 0)), direction T(q) - o per component in float; ray row * width + col. The call is EXACTLY
+ *             sbm_occ_cast_rays on those rays and has no other contract.
+ *  Device. One lane per point, ray or pixel; the DDA state (three keys, three steps, six doubles) stays in registers and a
+ *  lane that has its answer leaves its loop. A lookup is a plain probe: the key's hash, then a linear walk to the key, an empty
+ *  slot or min(slots, 1024) probes, with ordinary cached loads and no atomics -- queries are stream-ordered after the inserts
+ *  and write nothing but their outputs. The view kernel maps each wavefront to an 8 x 8 pixel tile, so that its 64 rays stay in
+ *  neighbouring voxels.
+ *  sbm_get_profile: "occ_search" / "occ_cast", ms of the last search / cast call. */
+enum { SBM_OCC_CELL_OUT = -1, SBM_OCC_CELL_UNKNOWN = 0, SBM_OCC_CELL_FREE = 1, SBM_OCC_CELL_OCCUPIED = 2 };
+enum { SBM_OCC_RAY_NONE = 0, SBM_OCC_RAY_HIT = 1, SBM_OCC_RAY_RANGE = 2, SBM_OCC_RAY_UNKNOWN = 3, SBM_OCC_RAY_BOUNDS = 4 };
+typedef struct sbm_occ_query_params {
+  double max_range;           /* castRay's maxRange in metres; <= 0 (the default, -1) means no limit                     */
+  float occupancy_thres_log;  /* 0.0f: the fifth value of sbm_occ_ray_logodds; a voxel is occupied iff logodds >= this  */
+  int32_t ignore_unknown;     /* 0: an unknown cell ends the ray (castRay's ignoreUnknownCells = false)                  */
+} sbm_occ_query_params;
+
+/* Fill *p with castRay's defaults: -1, 0.0f, 0. */
+void sbm_occ_query_params_default(sbm_occ_query_params* p);
+/* SBM_ERR_NULL; SBM_ERR_SIZE for a max_range or a threshold that is NaN; else SBM_OK. */
+int sbm_occ_query_params_validate(const sbm_occ_query_params* p);
+/* search on n points: d_xyz n float triples, d_state n int32 (SBM_OCC_CELL_*), d_value n 4-byte values (may be NULL), all in
+ * DEVICE memory, 4-byte aligned. Asynchronous on the handle's stream unless sync != 0. Checked in this order before anything is
+ * launched: SBM_ERR_NULL (d_xyz and d_state may be NULL only for n == 0, which is accepted and launches nothing); SBM_ERR_SIZE
+ * for a NaN threshold; SBM_ERR_UNSUPPORTED for more than 2^30 points or a misaligned pointer. */
+int sbm_occ_search_device(sbm_occ_map* map, size_t n, const void* d_xyz, float occupancy_thres_log, void* d_state, void* d_value,
+                          int sync);
+/* The same on HOST memory. Synchronous. */
+int sbm_occ_search(sbm_occ_map* map, size_t n, const float* xyz, float occupancy_thres_log, int32_t* state, void* value);
+/* castRay on n rays: d_dirs n float triples, d_status n int32 (SBM_OCC_RAY_*), d_end n float triples (may be NULL), in DEVICE
+ * memory, 4-byte aligned. With shared_origin == 0 `origins` is n float triples in DEVICE memory; with shared_origin != 0 it is
+ * ONE origin, three floats in HOST memory, read before the call returns, that every ray starts from. params in HOST memory.
+ * Asynchronous on the handle's stream unless sync != 0. Checked in this order before anything is launched: SBM_ERR_NULL
+ * (origins, d_dirs and d_status may be NULL only for n == 0, which is accepted and launches nothing); the codes of
+ * sbm_occ_query_params_validate; SBM_ERR_UNSUPPORTED for more than 2^30 rays or a misaligned device pointer. */
+int sbm_occ_cast_rays_device(sbm_occ_map* map, size_t n, const void* origins, int shared_origin, const void* d_dirs,
+                             const sbm_occ_query_params* params, void* d_status, void* d_end, int sync);
+/* The same with every array in HOST memory (origins: n triples, or one with shared_origin != 0). Synchronous. */
+int sbm_occ_cast_rays(sbm_occ_map* map, size_t n, const float* origins, int shared_origin, const float* dirs,
+                      const sbm_occ_query_params* params, int32_t* status, float* end);
+/* One ray per pixel of a virtual camera (see "view"): d_status width * height int32, d_end as many float triples (may be NULL),
+ * DEVICE memory; model, pose (12 floats) and params in HOST memory, read before the call returns. Checked in this order:
+ * SBM_ERR_NULL; SBM_ERR_SIZE for a width, height or scale <= 0; the codes of sbm_occ_query_params_validate;
+ * SBM_ERR_UNSUPPORTED for more than 2^30 pixels, for width * scale or height * scale above 2^24, and for a misaligned pointer. */
+int sbm_occ_cast_view_device(sbm_occ_map* map, int width, int height, int scale, const sbm_stereo_model* model, const float* pose,
+                             const sbm_occ_query_params* params, void* d_status, void* d_end, int sync);
 
 /* ---- visual-word dictionary: addNewWords, computeLikelihood, limitKeypoints ---------------------------------------------------
  * The reference's loop-closure thread, started by Mapper::process for each key frame: addWordIds -> VWDictionary::addNewWords

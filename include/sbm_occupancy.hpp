@@ -8,6 +8,8 @@
 // a map that is too small throws with code SBM_ERR_OCC_FULL (nothing is dropped silently: overflow() counts the points).
 // insertRays() / insertPointCloud() / writeBinaryLogOdds() are the same loop with octomap's insertPointCloud in place of
 // updateNode: free space is ray-cast from each node's sensor origin and the .bt holds free and occupied leaves.
+// search() / castRay() / castRays() / castView() are octomap's search and castRay on the device: castRay has octomap's signature
+// and result for a call-site swap, the batch forms take arrays.
 #ifndef SBM_OCCUPANCY_HPP_
 #define SBM_OCCUPANCY_HPP_
 
@@ -97,6 +99,50 @@ class OccupancyMap {
     check(sbm_occ_write_binary_logodds(k.data(), v.data(), k.size(), p_.resolution, c[4], path.c_str()));
   }
 
+  // ---- queries: the map is not changed ---------------------------------------------------------------------------------------
+  // The threshold of isNodeOccupied for a log-odds map: logodds(rayParams().occupancy_thres)
+  float occupancyThresLog() const {
+    float c[5];
+    check(sbm_occ_ray_logodds(&rp_, c));
+    return c[4];
+  }
+  // tree.search(x, y, z): SBM_OCC_CELL_OUT / UNKNOWN / FREE / OCCUPIED; *logodds (may be null) receives the node's log-odds,
+  // NaN where there is no node (a log-odds map; in hit mode the word is the hit count)
+  int search(float x, float y, float z, float* logodds = nullptr) {
+    const float p[3] = {x, y, z};
+    int32_t state = 0;
+    check(sbm_occ_search(m_, 1, p, occupancyThresLog(), &state, logodds));
+    return state;
+  }
+  // n points (host memory) at once: states, and the 4-byte value words where values is not null
+  void search(const float* xyz, size_t n, int32_t* states, void* values = nullptr) {
+    check(sbm_occ_search(m_, n, xyz, occupancyThresLog(), states, values));
+  }
+  // tree.castRay(origin, direction, end, ignoreUnknownCells, maxRange): true iff the ray hit an occupied voxel, whose centre is
+  // then in end. Where octomap leaves end untouched (no key for the origin, no direction) so does this.
+  bool castRay(const float origin[3], const float direction[3], float end[3], bool ignoreUnknownCells = false, double maxRange = -1.0,
+               int* status = nullptr) {
+    const sbm_occ_query_params q = queryParams(ignoreUnknownCells, maxRange);
+    int32_t st = 0;
+    float e[3];
+    check(sbm_occ_cast_rays(m_, 1, origin, 1, direction, &q, &st, e));
+    if (st != SBM_OCC_RAY_NONE) end[0] = e[0], end[1] = e[1], end[2] = e[2];
+    if (status) *status = st;
+    return st == SBM_OCC_RAY_HIT;
+  }
+  // n rays in host memory: origins n triples, or one that every ray starts from (one_origin); ends may be null
+  void castRays(const float* origins, bool one_origin, const float* directions, size_t n, int32_t* status, float* ends,
+                bool ignoreUnknownCells = false, double maxRange = -1.0) {
+    const sbm_occ_query_params q = queryParams(ignoreUnknownCells, maxRange);
+    check(sbm_occ_cast_rays(m_, n, origins, one_origin ? 1 : 0, directions, &q, status, ends));
+  }
+  // One ray per pixel of a width x height virtual camera at `pose`, into DEVICE memory (d_end may be null)
+  void castView(int width, int height, int scale, const sbm_stereo_model& model, const float pose[12], void* d_status, void* d_end,
+                bool ignoreUnknownCells = false, double maxRange = -1.0, bool sync = true) {
+    const sbm_occ_query_params q = queryParams(ignoreUnknownCells, maxRange);
+    check(sbm_occ_cast_view_device(m_, width, height, scale, &model, pose, &q, d_status, d_end, sync ? 1 : 0));
+  }
+
   size_t size() {
     size_t n = 0;
     check(sbm_occ_size(m_, &n));
@@ -124,6 +170,14 @@ class OccupancyMap {
   }
 
  private:
+  sbm_occ_query_params queryParams(bool ignoreUnknownCells, double maxRange) const {
+    sbm_occ_query_params q;
+    sbm_occ_query_params_default(&q);
+    q.max_range = maxRange;
+    q.occupancy_thres_log = occupancyThresLog();
+    q.ignore_unknown = ignoreUnknownCells ? 1 : 0;
+    return q;
+  }
   static void check(int st) {
     if (st != SBM_OK) throw Error(st, sbm_strerror(st));
   }

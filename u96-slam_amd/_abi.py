@@ -113,6 +113,13 @@ class OccRayParams(ctypes.Structure):
                 ("clamp_max", ctypes.c_double), ("occupancy_thres", ctypes.c_double), ("max_range", ctypes.c_double)]
 
 
+class OccQueryParams(ctypes.Structure):
+    """`sbm_occ_query_params` of include/sbm.h: castRay's maxRange (<= 0: no limit), the log-odds threshold of isNodeOccupied and
+    ignoreUnknownCells."""
+
+    _fields_ = [("max_range", ctypes.c_double), ("occupancy_thres_log", ctypes.c_float), ("ignore_unknown", ctypes.c_int32)]
+
+
 class VwdParams(ctypes.Structure):
     """`sbm_vwd_params` of include/sbm.h: addNewWords' metric and NNDR ratio (VWDictionary.cpp:43), and the search's slice count."""
 
@@ -143,6 +150,8 @@ PGO_COUPLING_REFERENCE, PGO_COUPLING_SYMMETRIC = 0, 1
 PGO_EDGE_RECORD = 200
 ERR_OCC_FULL = -25
 ERR_VWD_FULL = -26
+OCC_CELL_OUT, OCC_CELL_UNKNOWN, OCC_CELL_FREE, OCC_CELL_OCCUPIED = -1, 0, 1, 2
+OCC_RAY_NONE, OCC_RAY_HIT, OCC_RAY_RANGE, OCC_RAY_UNKNOWN, OCC_RAY_BOUNDS = 0, 1, 2, 3, 4
 VWD_L1, VWD_L2 = 0, 1
 VWD_NONE = 2147483647
 LK_USE_INITIAL_FLOW = 4
@@ -319,6 +328,15 @@ def load_library():
     L.sbm_occ_fetch_logodds_device.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
     L.sbm_occ_fetch_logodds.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
     L.sbm_occ_write_binary_logodds.argtypes = [vp, vp, sz, ctypes.c_double, ctypes.c_float, ctypes.c_char_p]
+    oqp = ctypes.POINTER(OccQueryParams)
+    L.sbm_occ_query_params_default.argtypes = [oqp]
+    L.sbm_occ_query_params_default.restype = None
+    L.sbm_occ_query_params_validate.argtypes = [oqp]
+    L.sbm_occ_search_device.argtypes = [vp, sz, vp, ctypes.c_float, vp, vp, ci]
+    L.sbm_occ_search.argtypes = [vp, sz, vp, ctypes.c_float, vp, vp]
+    L.sbm_occ_cast_rays_device.argtypes = [vp, sz, vp, ci, vp, oqp, vp, vp, ci]
+    L.sbm_occ_cast_rays.argtypes = [vp, sz, vp, ci, vp, oqp, vp, vp]
+    L.sbm_occ_cast_view_device.argtypes = [vp, ci, ci, ci, mp, vp, oqp, vp, vp, ci]
     wp = ctypes.POINTER(VwdParams)
     pi = ctypes.POINTER(ci)
     L.sbm_vwd_params_default.argtypes = [wp]

@@ -6,7 +6,9 @@ import os
 
 import numpy as np
 
-from ._abi import ERR_OCC_FULL, OccParams, OccRayParams, StereoBMError, _check, _torch, load_library
+from ._abi import (ERR_OCC_FULL, OCC_CELL_FREE, OCC_CELL_OCCUPIED, OCC_CELL_OUT, OCC_CELL_UNKNOWN, OCC_RAY_BOUNDS,  # noqa: F401
+                   OCC_RAY_HIT, OCC_RAY_NONE, OCC_RAY_RANGE, OCC_RAY_UNKNOWN, OccParams, OccQueryParams, OccRayParams,
+                   StereoBMError, _check, _torch, load_library)
 
 
 def occ_params(resolution=0.1, range_max=5.0, tree_depth=16):
@@ -55,6 +57,16 @@ def occ_write_binary_logodds(keys, logodds, path, resolution=0.1, occupancy_thre
     _check(load_library().sbm_occ_write_binary_logodds(keys.ctypes.data if len(keys) else None,
                                                        logodds.ctypes.data if len(keys) else None, len(keys), float(resolution),
                                                        float(occupancy_thres_log), os.fsencode(path)))
+
+
+def occ_query_params(max_range=-1.0, occupancy_thres_log=0.0, ignore_unknown=False):
+    """castRay's defaults; max_range <= 0 means no limit. occupancy_thres_log is occ_ray_logodds(params)[4]."""
+    return OccQueryParams(float(max_range), float(occupancy_thres_log), int(bool(ignore_unknown)))
+
+
+def occ_query_validate(params):
+    """Status code of sbm_occ_query_params_validate (0 = ok)."""
+    return load_library().sbm_occ_query_params_validate(ctypes.byref(params))
 
 
 def _poses(poses, n):
@@ -191,6 +203,100 @@ class OccupancyMap:
         keys, lo = self.fetch_logodds()
         occ_write_binary_logodds(keys, lo, path, self._p.resolution, float(occ_ray_logodds(rp)[4]))
 
+    # ---- queries: octomap's search and castRay, per depth-16 voxel; the map is not changed ------------------------------------
+    def _query_params(self, params, kw):
+        if params is not None and kw:
+            raise TypeError("pass either an OccQueryParams or keyword parameters")
+        return params if params is not None else occ_query_params(**kw)
+
+    def _cuda_f32(self, a, what, cols=3):
+        torch = _torch()
+        if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or not a.is_cuda or a.dim() != 2 or a.shape[1] != cols or \
+                a.device.index != self._engine._device:
+            raise StereoBMError(-2, f"{what} must be a CUDA float32 (n, {cols}) tensor on the engine's device")
+        return a.contiguous()
+
+    def search(self, points, occupancy_thres_log=0.0, sync=True):
+        """octomap's search(point) on (n, 3) points: a torch CUDA float32 tensor (-> torch int32 states, int32 value words) or
+        a numpy array (the host form -> numpy int32 states, uint32 value words). A state is OCC_CELL_OUT / UNKNOWN / FREE /
+        OCCUPIED; the value word holds the float log-odds (NaN where nothing is stored) in log-odds mode, the hit count in hit
+        mode: view it as float32 for a log-odds map."""
+        if isinstance(points, np.ndarray):
+            p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+            state, value = np.empty(len(p), np.int32), np.empty(len(p), np.uint32)
+            _check(self._L.sbm_occ_search(self._m, len(p), p.ctypes.data if len(p) else None, float(occupancy_thres_log),
+                                          state.ctypes.data if len(p) else None, value.ctypes.data if len(p) else None), self._engine._h)
+            return state, value
+        torch = _torch()
+        p = self._cuda_f32(points, "points")
+        n = p.shape[0]
+        state = torch.empty((n,), dtype=torch.int32, device=p.device)
+        value = torch.empty((n,), dtype=torch.int32, device=p.device)
+        torch.cuda.current_stream(p.device).synchronize()
+        _check(self._L.sbm_occ_search_device(self._m, n, p.data_ptr() if n else None, float(occupancy_thres_log),
+                                             state.data_ptr() if n else None, value.data_ptr() if n else None, 1 if sync else 0),
+               self._engine._h)
+        self._after(sync, (p, state, value))
+        return state, value
+
+    def _after(self, sync, held):
+        if sync:
+            self._engine._inflight.clear()
+        else:
+            self._engine._inflight.append(held)
+
+    def cast_rays(self, origins, directions, params=None, sync=True, **kw):
+        """octomap's castRay on n rays -> (status, end): OCC_RAY_* per ray and the (n, 3) end points (NaN for OCC_RAY_NONE).
+        directions (n, 3) as a torch CUDA float32 tensor, with origins such a tensor or three floats that every ray starts
+        from; or both as numpy arrays (the host form, always synchronous)."""
+        qp = self._query_params(params, kw)
+        if isinstance(directions, np.ndarray):
+            d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+            o = np.ascontiguousarray(np.asarray(origins, np.float32)).reshape(-1, 3)
+            shared = len(o) == 1 and np.ndim(origins) == 1
+            if not shared and len(o) != len(d):
+                raise StereoBMError(-2, f"{len(o)} origins for {len(d)} rays")
+            status, end = np.empty(len(d), np.int32), np.empty((len(d), 3), np.float32)
+            _check(self._L.sbm_occ_cast_rays(self._m, len(d), o.ctypes.data if len(o) else None, int(shared),
+                                             d.ctypes.data if len(d) else None, ctypes.byref(qp), status.ctypes.data if len(d) else None,
+                                             end.ctypes.data if len(d) else None), self._engine._h)
+            return status, end
+        torch = _torch()
+        d = self._cuda_f32(directions, "directions")
+        n = d.shape[0]
+        shared = not isinstance(origins, torch.Tensor)
+        if shared:
+            o = np.ascontiguousarray(np.asarray(origins, np.float32).reshape(3))
+            o_ptr = o.ctypes.data
+        else:
+            o = self._cuda_f32(origins, "origins")
+            if o.shape[0] != n:
+                raise StereoBMError(-2, f"{o.shape[0]} origins for {n} rays")
+            o_ptr = o.data_ptr() if n else None
+        status = torch.empty((n,), dtype=torch.int32, device=d.device)
+        end = torch.empty((n, 3), dtype=torch.float32, device=d.device)
+        torch.cuda.current_stream(d.device).synchronize()
+        _check(self._L.sbm_occ_cast_rays_device(self._m, n, o_ptr, int(shared), d.data_ptr() if n else None, ctypes.byref(qp),
+                                                status.data_ptr() if n else None, end.data_ptr() if n else None, 1 if sync else 0),
+               self._engine._h)
+        self._after(sync, (o, d, status, end))
+        return status, end
+
+    def cast_view(self, width, height, model, pose, scale=1, params=None, sync=True, **kw):
+        """One ray per pixel of a width x height virtual camera at `pose` (12 floats), built on the device -> torch CUDA
+        (height, width) int32 statuses and (height, width, 3) float32 end points: cast_rays on the rays the header states."""
+        torch = _torch()
+        qp = self._query_params(params, kw)
+        p = _poses(pose, 1)
+        dev = torch.device("cuda", self._engine._device)
+        status = torch.empty((int(height), int(width)), dtype=torch.int32, device=dev)
+        end = torch.empty((int(height), int(width), 3), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.sbm_occ_cast_view_device(self._m, int(width), int(height), int(scale), ctypes.byref(model), p.ctypes.data,
+                                                ctypes.byref(qp), status.data_ptr(), end.data_ptr(), 1 if sync else 0), self._engine._h)
+        self._after(sync, (status, end))
+        return status, end
+
     def size(self):
         v = ctypes.c_size_t()
         _check(self._L.sbm_occ_size(self._m, ctypes.byref(v)), self._engine._h)
@@ -231,4 +337,4 @@ class OccupancyMap:
         occ_write_binary(self.keys()[0], path, self._p.resolution)
 
     def profile(self):
-        return self._engine._profile(("occ_insert", "occ_fetch", "occ_rays_mark", "occ_rays_apply"))
+        return self._engine._profile(("occ_insert", "occ_fetch", "occ_rays_mark", "occ_rays_apply", "occ_search", "occ_cast"))
