@@ -1226,6 +1226,100 @@ int sbm_occ_cast_rays(sbm_occ_map* map, size_t n, const float* origins, int shar
 int sbm_occ_cast_view_device(sbm_occ_map* map, int width, int height, int scale, const sbm_stereo_model* model, const float* pose,
                              const sbm_occ_query_params* params, void* d_status, void* d_end, int sync);
 
+/* ---- occupancy map: the octree above the voxels (OcTreeBaseImpl.hxx, OccupancyOcTreeBase.hxx: updateInnerOccupancy, prune,
+ * search(point, depth), begin_leafs(maxDepth), calcNumNodes, writeBinary) --------------------------------------------------------
+ * sbm_occ_tree is a SNAPSHOT of an sbm_occ_map with the sixteen levels octomap keeps above the depth-16 voxels, built and queried
+ * on the device. The map and every entry point above stay as they are: a build only reads the table. After non-lazy inserts an
+ * inner node's value in octomap is the maximum of its children (updateOccupancyChildren) and prune() collapses eight equal
+ * childless siblings; both are pure functions of the set of voxels and their values, so everything here is exact: integers,
+ * orders, float bits and bytes. tests/occupancy_tree_cases.py is a literal transcription of this text, and
+ * tests/golden/occupancy_tree.npz holds what the reference's own octomap answered.
+ *  leaves     the stored voxels of the map at build time, under one of two readings of their value:
+ *             SBM_OCC_TREE_LOGODDS (log-odds maps only; a hit-mode map: SBM_ERR_UNSUPPORTED): the stored float.
+ *             SBM_OCC_TREE_MAXLIKELIHOOD (both modes), toMaxLikelihood() as writeBinary applies it, with the constants of
+ *             sbm_occ_ray_logodds(params): a log-odds voxel with logodds >= threshold becomes the clamp-max log-odds, any other
+ *             log-odds voxel the clamp-min log-odds; every stored voxel of a hit-mode map becomes clamp-max.
+ *  nodes      for a depth d in 0..16 and a key prefix (key >> (16 - d) per axis) the node exists iff some stored voxel lies below
+ *             it; its value is the float maximum over those voxels. An empty map has no nodes, not even a root.
+ *  collapsed  a node at depth d < 16 is collapsed iff all 8^(16 - d) voxels below it are stored and their values compare equal
+ *             with float == (isNodeCollapsible applied bottom-up).
+ *  pruned     the pruned tree holds the nodes that have no collapsed proper ancestor. A leaf of it is a depth-16 node or a
+ *             collapsed node. The tree's size is its number of nodes: calcNumNodes after prune(), the `size` line of a .bt.
+ *  children   everywhere the child index is (x bit) | (y bit) << 1 | (z bit) << 2, from the top key bit down (computeChildIdx).
+ *  node key   octomap's centre key, adjustKeyAtDepth: at depth 16 the key itself; above, per axis, ((k >> l) << l) | (1 << (l - 1))
+ *             with l = 16 - d; packed as the map's 48-bit key.
+ *  search(point, depth)   OcTreeBaseImpl.hxx:408-471. depth 0 means 16. SBM_OCC_CELL_OUT for a point without a key;
+ *             SBM_OCC_CELL_UNKNOWN where no node of that depth covers the key; else occupied or free by value >=
+ *             occupancy_thres_log. The value is the node's float, NaN (0x7FC00000) for out and unknown. The found depth is that
+ *             of the node octomap returns: the shallowest collapsed node at or above the asked depth if there is one (it holds
+ *             the same value), else the asked depth; -1 for out and unknown.
+ *  leaves(max_depth)      begin_leafs(maxDepth). 0 means 16. Every leaf of the pruned tree at depth <= max_depth and every other
+ *             node of it at exactly max_depth, in octomap's iteration order, which is Morton order of the covered cubes; per
+ *             entry the centre key, the depth (int32) and the value.
+ *  binary     the body of writeBinaryNode (OccupancyOcTreeBase.hxx:1031-1090) of a MAXLIKELIHOOD tree: every non-leaf node of the
+ *             pruned tree contributes two bytes, in depth-first pre-order, per child two bits as sbm_occ_write_binary_logodds
+ *             states them; a leaf is occupied iff it holds clamp max, which is its voxels' own >= threshold. With the header of
+ *             sbm_occ_write_binary and `size` the node count the file equals, byte for byte, what sbm_occ_write_binary /
+ *             sbm_occ_write_binary_logodds write for the fetched voxels.
+ *  Not here: getMetricMin / getMetricMax (octomap forms them from float centres of pruned leaves, which the keys do not pin; the
+ *  key bounds of sbm_occ_tree_info are exact), bounding-box iterators, the .ot format, incremental update (a rebuild is the update).
+ *  Device. The compacted table is sorted by 48-bit Morton code with the map's radix sort; siblings are then
+ *  neighbours, and sixteen bottom-up passes (heads per tile, a scan, one write per head) make each level from the one below;
+ *  one top-down pass per depth marks what lies under a collapsed node and ranks the non-leaf nodes in pre-order, so that the .bt
+ *  body is one store per node. No spin waits, no grid barriers, and no atomics other than integer counts. A tree holds 20 bytes per
+ *  stored voxel and 32 per node above them.
+ *  sbm_get_profile: "occ_tree_build" / "occ_tree_query", ms of the last build / of the last search, leaves or binary call. */
+typedef struct sbm_occ_tree sbm_occ_tree;
+enum { SBM_OCC_TREE_LOGODDS = 0, SBM_OCC_TREE_MAXLIKELIHOOD = 1 };
+typedef struct sbm_occ_tree_counts {
+  uint64_t voxels;          /* stored voxels at build time                                                  */
+  uint64_t nodes, leaves;   /* of the pruned tree: calcNumNodes, getNumLeafNodes                            */
+  uint64_t nodes_at[17];    /* nodes of the pruned tree per depth 0..16                                     */
+  uint64_t leaves_at[17];   /* leaves of the pruned tree per depth                                          */
+  uint16_t key_min[3];      /* per axis over the stored voxels; an empty tree reports 65535 ...             */
+  uint16_t key_max[3];      /* ... and 0                                                                    */
+  uint32_t pad;
+} sbm_occ_tree_counts;
+
+/* A tree over `map`, empty until built. It uses the map's handle, which must outlive it; the map itself is read by
+ * sbm_occ_tree_build only and may be destroyed once no further build follows. SBM_ERR_NULL, SBM_ERR_NOMEM. */
+int sbm_occ_tree_create(sbm_occ_map* map, sbm_occ_tree** tree);
+void sbm_occ_tree_destroy(sbm_occ_tree* tree);
+/* Take a new snapshot of the map under `reading`, reusing the tree's buffers; later inserts do not change a built tree. params
+ * (host memory) gives the constants of SBM_OCC_TREE_MAXLIKELIHOOD and may be NULL only for SBM_OCC_TREE_LOGODDS. A map whose table
+ * overflowed builds the tree of what is stored and returns SBM_OK (the inserts reported the overflow). The call waits for the
+ * stream twice (the voxel count, the level sizes); what follows is asynchronous unless sync != 0. Checked in this order before
+ * anything is launched: SBM_ERR_NULL; SBM_ERR_SIZE for a reading that is neither, then the codes of sbm_occ_ray_params_validate
+ * where params is given; SBM_ERR_UNSUPPORTED for SBM_OCC_TREE_LOGODDS on a hit-mode map. After the voxel count is known:
+ * SBM_ERR_UNSUPPORTED for a map with 2^31 or more nodes above its voxels. A build that fails leaves an empty tree. */
+int sbm_occ_tree_build(sbm_occ_tree* tree, int reading, const sbm_occ_ray_params* params, int sync);
+/* The counts of the last build. A tree that was never built answers as an empty one, here and below. Waits for the stream. */
+int sbm_occ_tree_info(sbm_occ_tree* tree, sbm_occ_tree_counts* info);
+/* search(point, depth) on n points: d_xyz n float triples, d_state n int32 (SBM_OCC_CELL_*), d_value n 4-byte values (may be
+ * NULL), d_found_depth n int32 (may be NULL), DEVICE memory, 4-byte aligned. Asynchronous unless sync != 0. Checked in this order
+ * before anything is launched: SBM_ERR_NULL (d_xyz and d_state may be NULL only for n == 0, which is accepted and launches
+ * nothing); SBM_ERR_SIZE for a depth outside 0..16 or a NaN threshold; SBM_ERR_UNSUPPORTED for more than 2^30 points or a
+ * misaligned pointer. */
+int sbm_occ_tree_search_device(sbm_occ_tree* tree, size_t n, const void* d_xyz, int depth, float occupancy_thres_log, void* d_state,
+                               void* d_value, void* d_found_depth, int sync);
+/* The same on HOST memory. Synchronous. */
+int sbm_occ_tree_search(sbm_occ_tree* tree, size_t n, const float* xyz, int depth, float occupancy_thres_log, int32_t* state,
+                        void* value, int32_t* found_depth);
+/* leaves(max_depth) into d_keys (uint64, 8-byte aligned), d_depth (int32) and d_value (float, may be NULL), cap entries each, DEVICE
+ * memory. *count receives the number of entries; when it exceeds cap nothing is written and the call returns SBM_ERR_SIZE, as
+ * sbm_occ_fetch_device does. Synchronous. SBM_ERR_NULL (d_keys and d_depth may be NULL only for cap == 0); SBM_ERR_SIZE for a
+ * max_depth outside 0..16; SBM_ERR_UNSUPPORTED for a misaligned pointer. */
+int sbm_occ_tree_leaves_device(sbm_occ_tree* tree, int max_depth, void* d_keys, void* d_depth, void* d_value, size_t cap, size_t* count);
+/* The same into HOST memory. */
+int sbm_occ_tree_leaves(sbm_occ_tree* tree, int max_depth, uint64_t* keys, int32_t* depth, float* value, size_t cap, size_t* count);
+/* The .bt body into d_bytes (DEVICE memory, cap bytes); *nbytes receives its length, twice the number of non-leaf nodes; when it
+ * exceeds cap nothing is written and the call returns SBM_ERR_SIZE. Synchronous. SBM_ERR_NULL; SBM_ERR_UNSUPPORTED for a tree
+ * built with SBM_OCC_TREE_LOGODDS. */
+int sbm_occ_tree_binary_device(sbm_occ_tree* tree, void* d_bytes, size_t cap, size_t* nbytes);
+/* tree.writeBinary(path): the header with the tree's size and resolution, then that body. SBM_ERR_NULL; SBM_ERR_UNSUPPORTED for a
+ * tree built with SBM_OCC_TREE_LOGODDS or a file that cannot be written; SBM_ERR_NOMEM. */
+int sbm_occ_tree_write_binary(sbm_occ_tree* tree, const char* path);
+
 /* ---- visual-word dictionary: addNewWords, computeLikelihood, limitKeypoints ---------------------------------------------------
  * The reference's loop-closure thread, started by Mapper::process for each key frame: addWordIds -> VWDictionary::addNewWords
  * (src/slam/src/core/Mapper.cpp:413-484, VWDictionary.cpp:40-115) and detectLoopClosure -> computeLikelihood

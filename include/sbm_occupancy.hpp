@@ -10,17 +10,84 @@
 // updateNode: free space is ray-cast from each node's sensor origin and the .bt holds free and occupied leaves.
 // search() / castRay() / castRays() / castView() are octomap's search and castRay on the device: castRay has octomap's signature
 // and result for a call-site swap, the batch forms take arrays.
+// buildTree() gives an OccupancyTree: octomap's sixteen levels above the voxels as a snapshot on the device, with search(point,
+// depth), leaves(maxDepth), size() / getNumLeafNodes() and writeBinary() in octomap's spelling.
 #ifndef SBM_OCCUPANCY_HPP_
 #define SBM_OCCUPANCY_HPP_
 
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "sbm_stereobm.hpp"   // sbm::Error
 
 namespace sbm {
+
+// One entry of leaves(maxDepth): octomap's centre key packed as the map packs keys, the node's depth and its value
+struct OccupancyLeaf {
+  uint64_t key;
+  int32_t depth;
+  float value;
+};
+
+// The tree above the voxels of an OccupancyMap as it was when the tree was (re)built: updateInnerOccupancy() and prune() done.
+// The map's handle must outlive it.
+class OccupancyTree {
+ public:
+  OccupancyTree(sbm_occ_map* map, float occupancy_thres_log) : thres_(occupancy_thres_log) { check(sbm_occ_tree_create(map, &t_)); }
+  ~OccupancyTree() { sbm_occ_tree_destroy(t_); }
+  OccupancyTree(const OccupancyTree&) = delete;
+  OccupancyTree& operator=(const OccupancyTree&) = delete;
+  sbm_occ_tree* tree() { return t_; }
+
+  // a new snapshot: SBM_OCC_TREE_LOGODDS (the stored log-odds) or SBM_OCC_TREE_MAXLIKELIHOOD (toMaxLikelihood(), what .bt holds)
+  void rebuild(int reading, const sbm_occ_ray_params& params) { check(sbm_occ_tree_build(t_, reading, &params, 1)); }
+  sbm_occ_tree_counts info() {
+    sbm_occ_tree_counts c;
+    check(sbm_occ_tree_info(t_, &c));
+    return c;
+  }
+  size_t size() { return (size_t)info().nodes; }                  // tree.size() == calcNumNodes() after prune()
+  size_t getNumLeafNodes() { return (size_t)info().leaves; }
+  // tree.search(x, y, z, depth): SBM_OCC_CELL_*; *value (may be null) receives the node's float, NaN where there is no node;
+  // *found_depth (may be null) the depth of the node octomap returns, -1 where there is none
+  int search(float x, float y, float z, unsigned depth = 0, float* value = nullptr, int* found_depth = nullptr) {
+    const float p[3] = {x, y, z};
+    int32_t state = 0, fd = -1;
+    check(sbm_occ_tree_search(t_, 1, p, (int)depth, thres_, &state, value, &fd));
+    if (found_depth) *found_depth = fd;
+    return state;
+  }
+  // n points (host memory) at once
+  void search(const float* xyz, size_t n, unsigned depth, int32_t* states, void* values = nullptr, int32_t* found_depths = nullptr) {
+    check(sbm_occ_tree_search(t_, n, xyz, (int)depth, thres_, states, values, found_depths));
+  }
+  // for (it = tree.begin_leafs(maxDepth); it != tree.end_leafs(); ++it), in that order
+  std::vector<OccupancyLeaf> leaves(unsigned maxDepth = 0) {
+    size_t n = 0;
+    std::vector<uint64_t> k;
+    std::vector<int32_t> d;
+    std::vector<float> v;
+    int st = sbm_occ_tree_leaves(t_, (int)maxDepth, nullptr, nullptr, nullptr, 0, &n);   // the count
+    if (st != SBM_OK && st != SBM_ERR_SIZE) check(st);
+    k.resize(n), d.resize(n), v.resize(n);
+    check(sbm_occ_tree_leaves(t_, (int)maxDepth, k.data(), d.data(), v.data(), n, &n));
+    std::vector<OccupancyLeaf> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = OccupancyLeaf{k[i], d[i], v[i]};
+    return out;
+  }
+  // tree.writeBinary(path) of a SBM_OCC_TREE_MAXLIKELIHOOD tree
+  void writeBinary(const std::string& path) { check(sbm_occ_tree_write_binary(t_, path.c_str())); }
+
+ private:
+  static void check(int st) {
+    if (st != SBM_OK) throw Error(st, sbm_strerror(st));
+  }
+  float thres_;
+  sbm_occ_tree* t_ = nullptr;
+};
 
 class OccupancyMap {
  public:
@@ -141,6 +208,14 @@ class OccupancyMap {
                 bool ignoreUnknownCells = false, double maxRange = -1.0, bool sync = true) {
     const sbm_occ_query_params q = queryParams(ignoreUnknownCells, maxRange);
     check(sbm_occ_cast_view_device(m_, width, height, scale, &model, pose, &q, d_status, d_end, sync ? 1 : 0));
+  }
+
+  // The tree above the voxels as they are now (a snapshot; rebuild() it after further inserts). The default reading is what
+  // writeBinary holds; SBM_OCC_TREE_LOGODDS keeps the log-odds of a log-odds map.
+  std::unique_ptr<OccupancyTree> buildTree(int reading = SBM_OCC_TREE_MAXLIKELIHOOD) {
+    std::unique_ptr<OccupancyTree> t(new OccupancyTree(m_, occupancyThresLog()));
+    t->rebuild(reading, rp_);
+    return t;
   }
 
   size_t size() {

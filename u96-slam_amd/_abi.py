@@ -120,6 +120,14 @@ class OccQueryParams(ctypes.Structure):
     _fields_ = [("max_range", ctypes.c_double), ("occupancy_thres_log", ctypes.c_float), ("ignore_unknown", ctypes.c_int32)]
 
 
+class OccTreeCounts(ctypes.Structure):
+    """`sbm_occ_tree_counts` of include/sbm.h: what sbm_occ_tree_info reports of the last build."""
+
+    _fields_ = [("voxels", ctypes.c_uint64), ("nodes", ctypes.c_uint64), ("leaves", ctypes.c_uint64),
+                ("nodes_at", ctypes.c_uint64 * 17), ("leaves_at", ctypes.c_uint64 * 17), ("key_min", ctypes.c_uint16 * 3),
+                ("key_max", ctypes.c_uint16 * 3), ("pad", ctypes.c_uint32)]
+
+
 class VwdParams(ctypes.Structure):
     """`sbm_vwd_params` of include/sbm.h: addNewWords' metric and NNDR ratio (VWDictionary.cpp:43), and the search's slice count."""
 
@@ -152,6 +160,7 @@ ERR_OCC_FULL = -25
 ERR_VWD_FULL = -26
 OCC_CELL_OUT, OCC_CELL_UNKNOWN, OCC_CELL_FREE, OCC_CELL_OCCUPIED = -1, 0, 1, 2
 OCC_RAY_NONE, OCC_RAY_HIT, OCC_RAY_RANGE, OCC_RAY_UNKNOWN, OCC_RAY_BOUNDS = 0, 1, 2, 3, 4
+OCC_TREE_LOGODDS, OCC_TREE_MAXLIKELIHOOD = 0, 1
 VWD_L1, VWD_L2 = 0, 1
 VWD_NONE = 2147483647
 LK_USE_INITIAL_FLOW = 4
@@ -337,6 +346,17 @@ def load_library():
     L.sbm_occ_cast_rays_device.argtypes = [vp, sz, vp, ci, vp, oqp, vp, vp, ci]
     L.sbm_occ_cast_rays.argtypes = [vp, sz, vp, ci, vp, oqp, vp, vp]
     L.sbm_occ_cast_view_device.argtypes = [vp, ci, ci, ci, mp, vp, oqp, vp, vp, ci]
+    L.sbm_occ_tree_create.argtypes = [vp, ctypes.POINTER(vp)]
+    L.sbm_occ_tree_destroy.argtypes = [vp]
+    L.sbm_occ_tree_destroy.restype = None
+    L.sbm_occ_tree_build.argtypes = [vp, ci, orp, ci]
+    L.sbm_occ_tree_info.argtypes = [vp, ctypes.POINTER(OccTreeCounts)]
+    L.sbm_occ_tree_search_device.argtypes = [vp, sz, vp, ci, ctypes.c_float, vp, vp, vp, ci]
+    L.sbm_occ_tree_search.argtypes = [vp, sz, vp, ci, ctypes.c_float, vp, vp, vp]
+    L.sbm_occ_tree_leaves_device.argtypes = [vp, ci, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_tree_leaves.argtypes = [vp, ci, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_tree_binary_device.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_tree_write_binary.argtypes = [vp, ctypes.c_char_p]
     wp = ctypes.POINTER(VwdParams)
     pi = ctypes.POINTER(ci)
     L.sbm_vwd_params_default.argtypes = [wp]

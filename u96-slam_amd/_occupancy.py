@@ -7,8 +7,8 @@ import os
 import numpy as np
 
 from ._abi import (ERR_OCC_FULL, OCC_CELL_FREE, OCC_CELL_OCCUPIED, OCC_CELL_OUT, OCC_CELL_UNKNOWN, OCC_RAY_BOUNDS,  # noqa: F401
-                   OCC_RAY_HIT, OCC_RAY_NONE, OCC_RAY_RANGE, OCC_RAY_UNKNOWN, OccParams, OccQueryParams, OccRayParams,
-                   StereoBMError, _check, _torch, load_library)
+                   OCC_RAY_HIT, OCC_RAY_NONE, OCC_RAY_RANGE, OCC_RAY_UNKNOWN, OCC_TREE_LOGODDS, OCC_TREE_MAXLIKELIHOOD, OccParams,
+                   OccQueryParams, OccRayParams, OccTreeCounts, StereoBMError, _check, _torch, load_library)
 
 
 def occ_params(resolution=0.1, range_max=5.0, tree_depth=16):
@@ -336,5 +336,122 @@ class OccupancyMap:
         """tree.writeBinary(path) of the reference: the .bt stream of the stored voxels."""
         occ_write_binary(self.keys()[0], path, self._p.resolution)
 
+    def tree(self, reading=OCC_TREE_LOGODDS, params=None, sync=True):
+        """A built OccupancyTree over this map: the sixteen levels above the voxels, as a snapshot. reading OCC_TREE_LOGODDS
+        (log-odds maps) or OCC_TREE_MAXLIKELIHOOD, whose constants come from `params` (default: those of the last log-odds
+        insert)."""
+        return OccupancyTree(self).build(reading, params, sync)
+
     def profile(self):
         return self._engine._profile(("occ_insert", "occ_fetch", "occ_rays_mark", "occ_rays_apply", "occ_search", "occ_cast"))
+
+
+class OccupancyTree:
+    """octomap's tree above the voxels of an OccupancyMap (sbm_occ_tree): a snapshot, built and queried on the device. The
+    engine of the map must outlive it; the map is read by build() only."""
+
+    def __init__(self, omap):
+        self._map = omap
+        self._engine = omap._engine
+        self._L = omap._L
+        self._t = ctypes.c_void_p()
+        _check(self._L.sbm_occ_tree_create(omap._m, ctypes.byref(self._t)), self._engine._h)
+
+    def close(self):
+        t = getattr(self, "_t", None)
+        if t:
+            self._L.sbm_occ_tree_destroy(t)
+            self._t = None
+
+    def __del__(self):
+        self.close()
+
+    def build(self, reading=OCC_TREE_LOGODDS, params=None, sync=True):
+        """A new snapshot of the map; returns self."""
+        if params is None and reading == OCC_TREE_MAXLIKELIHOOD:
+            params = getattr(self._map, "_rp", None) or occ_ray_params()
+        self._rp = params
+        _check(self._L.sbm_occ_tree_build(self._t, int(reading), ctypes.byref(params) if params is not None else None,
+                                          1 if sync else 0), self._engine._h)
+        return self
+
+    def info(self):
+        """dict: voxels, nodes, leaves (calcNumNodes and getNumLeafNodes after prune()), nodes_at / leaves_at per depth 0..16,
+        key_min / key_max per axis over the stored voxels."""
+        c = OccTreeCounts()
+        _check(self._L.sbm_occ_tree_info(self._t, ctypes.byref(c)), self._engine._h)
+        return dict(voxels=c.voxels, nodes=c.nodes, leaves=c.leaves, nodes_at=list(c.nodes_at), leaves_at=list(c.leaves_at),
+                    key_min=list(c.key_min), key_max=list(c.key_max))
+
+    def search(self, points, depth=0, occupancy_thres_log=0.0, sync=True):
+        """octomap's search(point, depth) on (n, 3) points -> (state, value word, found depth): torch CUDA int32 tensors for a
+        torch CUDA float32 tensor, numpy int32 / uint32 / int32 for a numpy array (the host form). The value word holds the
+        node's float (NaN where there is none)."""
+        if isinstance(points, np.ndarray):
+            p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+            n = len(p)
+            state, value, found = np.empty(n, np.int32), np.empty(n, np.uint32), np.empty(n, np.int32)
+            _check(self._L.sbm_occ_tree_search(self._t, n, p.ctypes.data if n else None, int(depth), float(occupancy_thres_log),
+                                               state.ctypes.data if n else None, value.ctypes.data if n else None,
+                                               found.ctypes.data if n else None), self._engine._h)
+            return state, value, found
+        torch = _torch()
+        p = self._map._cuda_f32(points, "points")
+        n = p.shape[0]
+        state, value, found = (torch.empty((n,), dtype=torch.int32, device=p.device) for _ in range(3))
+        torch.cuda.current_stream(p.device).synchronize()
+        _check(self._L.sbm_occ_tree_search_device(self._t, n, p.data_ptr() if n else None, int(depth), float(occupancy_thres_log),
+                                                  state.data_ptr() if n else None, value.data_ptr() if n else None,
+                                                  found.data_ptr() if n else None, 1 if sync else 0), self._engine._h)
+        self._map._after(sync, (p, state, value, found))
+        return state, value, found
+
+    def _leaf_count(self, max_depth):
+        i = self.info()
+        d = int(max_depth) or 16
+        if not 0 < d <= 16:
+            raise StereoBMError(-2, f"max_depth {max_depth} is outside 0..16")
+        return sum(i["leaves_at"][:d + 1]) + i["nodes_at"][d] - i["leaves_at"][d]
+
+    def leaves(self, max_depth=0):
+        """octomap's begin_leafs(max_depth) -> (centre keys uint64, depths int32, values float32) as numpy arrays, in
+        octomap's iteration order."""
+        n = self._leaf_count(max_depth)
+        keys, depth, value = np.empty(n, np.uint64), np.empty(n, np.int32), np.empty(n, np.float32)
+        got = ctypes.c_size_t()
+        _check(self._L.sbm_occ_tree_leaves(self._t, int(max_depth), keys.ctypes.data if n else None, depth.ctypes.data if n else None,
+                                           value.ctypes.data if n else None, n, ctypes.byref(got)), self._engine._h)
+        return keys[:got.value], depth[:got.value], value[:got.value]
+
+    def leaves_device(self, max_depth=0):
+        """The same as torch CUDA tensors: keys int64, depths int32, values float32."""
+        torch = _torch()
+        n = self._leaf_count(max_depth)
+        dev = torch.device("cuda", self._engine._device)
+        keys = torch.empty((n,), dtype=torch.int64, device=dev)
+        depth = torch.empty((n,), dtype=torch.int32, device=dev)
+        value = torch.empty((n,), dtype=torch.float32, device=dev)
+        got = ctypes.c_size_t()
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.sbm_occ_tree_leaves_device(self._t, int(max_depth), keys.data_ptr() if n else None,
+                                                  depth.data_ptr() if n else None, value.data_ptr() if n else None, n,
+                                                  ctypes.byref(got)), self._engine._h)
+        return keys[:got.value], depth[:got.value], value[:got.value]
+
+    def binary(self):
+        """The body of the .bt stream (a MAXLIKELIHOOD tree) as a torch CUDA uint8 tensor: two bytes per non-leaf node."""
+        torch = _torch()
+        i = self.info()
+        n = 2 * (i["nodes"] - i["leaves"])
+        out = torch.empty((n,), dtype=torch.uint8, device=torch.device("cuda", self._engine._device))
+        got = ctypes.c_size_t()
+        torch.cuda.current_stream(out.device).synchronize()
+        _check(self._L.sbm_occ_tree_binary_device(self._t, out.data_ptr() if n else None, n, ctypes.byref(got)), self._engine._h)
+        return out[:got.value]
+
+    def write_binary(self, path):
+        """tree.writeBinary(path) of a MAXLIKELIHOOD tree."""
+        _check(self._L.sbm_occ_tree_write_binary(self._t, os.fsencode(path)), self._engine._h)
+
+    def profile(self):
+        return self._engine._profile(("occ_tree_build", "occ_tree_query"))
