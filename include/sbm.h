@@ -1320,6 +1320,82 @@ int sbm_occ_tree_binary_device(sbm_occ_tree* tree, void* d_bytes, size_t cap, si
  * tree built with SBM_OCC_TREE_LOGODDS or a file that cannot be written; SBM_ERR_NOMEM. */
 int sbm_occ_tree_write_binary(sbm_occ_tree* tree, const char* path);
 
+/* ---- occupancy map: load a .bt stream, readBinary (AbstractOccupancyOcTree.cpp:126-178, readHeader, readBinaryData /
+ * readBinaryNode at OccupancyOcTreeBase.hxx:937-1028) ---------------------------------------------------------------------------
+ * The other half of the writers above: a .bt stream becomes the log-odds map it describes, so that search, castRay, the tree and
+ * further insertPointCloud scans start from a saved map, as they do in octomap after readBinary. The pruned tree is parsed on the
+ * host in one pass (two bytes per inner node); the expansion of its leaves to depth-16 voxels, the work that grows with the map,
+ * runs on the device. tests/occupancy_load_cases.py is a literal transcription of this text, and tests/golden/occupancy_load.npz
+ * holds what the reference's own octomap read from the same streams.
+ *  header     the first line starts with "# Octomap OcTree binary file". Then whitespace-separated tokens up to the token `data`,
+ *             whose line ends the header: a token that begins with # skips its line; `id`, `size` and `res` take the next token
+ *             (size an unsigned decimal below 2^32, res as strtod reads it), in any order, the last one given counting; any
+ *             other keyword skips its line. id must be OcTree (or the "1" octomap itself renames to it), res must be > 0.
+ *  body       only when size > 0. One two-byte record per node that has children, the root's first: two bits per child, children
+ *             0-3 in the first byte and 4-7 in the second, child c in bits (2c, 2c + 1) of the 16-bit little-endian word, the
+ *             first of the pair lower: 01 an occupied leaf, 10 a free leaf, 11 a child whose own record follows, 00 no child.
+ *             The records of the 11 children follow in child order, depth first. The child index is computeChildIdx's, so
+ *             pre-order is Morton order of the cubes. An occupied leaf holds the clamp-max log-odds and a free leaf the
+ *             clamp-min log-odds: the fourth and third floats of sbm_occ_ray_logodds for the caller's sbm_occ_ray_params. A
+ *             record whose eight codes are all 00 leaves a childless node at clamp max, as readBinaryNode does: an occupied
+ *             leaf of that depth. Bytes after the last record are ignored, as octomap ignores them.
+ *  nodes      the root, plus one per child code other than 00. The stream is accepted iff this equals the header's size
+ *             (calcNumNodes() against size, AbstractOccupancyOcTree.cpp:172).
+ *  result     per depth-16 voxel below every leaf, that leaf's value -- the per-voxel reading of every section above: pruning
+ *             and expansion never change a depth-16 value. A leaf of depth d with Morton prefix c covers the 8^(16-d) voxels
+ *             whose codes are c << 3(16-d) | 0 .. 8^(16-d) - 1; its first key is the de-interleaved c << 3(16-d).
+ *  status     SBM_ERR_UNSUPPORTED: the first line is something else (the legacy binary header, tree type 3, is not provided),
+ *             another id or none, a file that cannot be opened or read. SBM_ERR_SIZE: the stream ends inside the header or
+ *             inside the tree, a number that does not parse, res not greater than 0, a 11 child of a depth-15 record (depth
+ *             17), size different from the nodes read. SBM_ERR_NOMEM. octomap itself does not look at the id of a stream it
+ *             reads into an OcTree and does not bound the depth; those two verdicts are this library's.
+ *  resolution the header carries `res` with 6 significant digits (%g). A load requires the file's res to EQUAL what this library's
+ *             own writers print for the map's resolution, parsed back (SBM_ERR_SIZE otherwise). The key set of a loaded map is
+ *             exact; its metric coordinates agree with the tree that was written to that precision, as octomap's do.
+ *  load       sbm_occ_load_binary / sbm_occ_read_binary, in this order before anything is launched or changed -- on any error
+ *             the map is exactly as it was: SBM_ERR_NULL; the codes of sbm_occ_ray_params_validate; the codes above; the
+ *             resolution; SBM_ERR_OCC_FULL when the expanded voxel count exceeds the map's capacity. Then, as readBinary does
+ *             clear() first, the map is reset whatever its mode was, put in log-odds mode with the flag words and the touched
+ *             list the first log-odds insert allocates (later sbm_occ_insert_cloud* / sbm_occ_insert_rays* scans continue on
+ *             the loaded map), the leaves are uploaded and expanded. size 0 leaves an empty map with no mode.
+ *  Device. Per leaf the host uploads a word (first Morton code << 8 | depth << 1 | occupied) and the exclusive prefix of the leaf
+ *  volumes (at most 2^30 voxels, 32 bits). One launch, one output voxel per lane: a binary search of the prefix array for the
+ *  leaf that holds the lane's index, the code as the leaf's first code OR'd with the offset, the packed key by de-interleaving
+ *  (the inverse of the tree build's five shift-and-mask steps), then the inserts' find-or-claim probe (the key's hash, a linear
+ *  walk, min(slots, 1024) probes) and a plain store of the float: the voxels of one load are distinct, so a slot has one writer.
+ *  The only atomics are the key's compare-and-swap and the size and overflow counters (one add per wavefront); no spin waits, no
+ *  grid barriers. The call returns once the leaves are uploaded; the reset and the expansion are asynchronous on the handle's
+ *  stream unless sync != 0 or profiling is on. A voxel that finds no slot within the probe bound counts as overflow and the call,
+ *  or with sync == 0 the next synchronous one, returns SBM_ERR_OCC_FULL, as for the inserts.
+ *  Not provided: the .ot format, the legacy header, a resolution other than the map's, trees of another depth than 16.
+ *  sbm_get_profile: "occ_load", ms of the last load's reset and expansion on the device. */
+typedef struct sbm_occ_binary_header {
+  double resolution;        /* res as parsed                                                                    */
+  uint64_t size;            /* the header's size                                                                */
+  uint64_t nodes;           /* nodes read: calcNumNodes() of the tree octomap would hold                        */
+  uint64_t leaves;          /* leaves of the pruned tree, childless nodes among them                            */
+  uint64_t occupied;        /* leaves that hold clamp max                                                       */
+  uint64_t voxels;          /* depth-16 voxels below the leaves: up to 2^48                                     */
+  uint64_t leaves_at[17];   /* leaves per depth 0..16                                                           */
+  uint16_t key_min[3];      /* per axis over those voxels; a stream without leaves reports 65535 ...            */
+  uint16_t key_max[3];      /* ... and 0                                                                        */
+  uint32_t pad;
+} sbm_occ_binary_header;
+
+/* Plain host code, no GPU: parse n bytes of a .bt stream and report its counts. On an error *out holds what was read up to it
+ * (for a size mismatch everything). SBM_ERR_NULL (bytes may be NULL only for n == 0), then the codes under "status". */
+int sbm_occ_binary_info(const void* bytes, size_t n, sbm_occ_binary_header* out);
+/* Plain host code, no GPU: the leaves in stream order, which is Morton order -- the packed key of the cube's lowest voxel, the
+ * depth, and 1 for occupied, 0 for free -- into arrays of cap entries. *count receives their number; when it exceeds cap nothing is
+ * written and the call returns SBM_ERR_SIZE. SBM_ERR_NULL (the arrays may be NULL only for cap == 0), then the codes under
+ * "status", which leave *count as it was. */
+int sbm_occ_binary_leaves(const void* bytes, size_t n, uint64_t* first_key, int32_t* depth, uint8_t* occupied, size_t cap, size_t* count);
+/* tree.readBinary(stream) from n bytes in HOST memory, read before the call returns; params (host) gives the two clamp log-odds.
+ * See "load" for the checks and their order and "Device" for what is asynchronous. */
+int sbm_occ_load_binary(sbm_occ_map* map, const void* bytes, size_t n, const sbm_occ_ray_params* params, int sync);
+/* tree.readBinary(filename): the same from a file; SBM_ERR_UNSUPPORTED when it cannot be opened or read. */
+int sbm_occ_read_binary(sbm_occ_map* map, const char* path, const sbm_occ_ray_params* params, int sync);
+
 /* ---- visual-word dictionary: addNewWords, computeLikelihood, limitKeypoints ---------------------------------------------------
  * The reference's loop-closure thread, started by Mapper::process for each key frame: addWordIds -> VWDictionary::addNewWords
  * (src/slam/src/core/Mapper.cpp:413-484, VWDictionary.cpp:40-115) and detectLoopClosure -> computeLikelihood

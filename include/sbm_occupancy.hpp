@@ -12,6 +12,7 @@
 // and result for a call-site swap, the batch forms take arrays.
 // buildTree() gives an OccupancyTree: octomap's sixteen levels above the voxels as a snapshot on the device, with search(point,
 // depth), leaves(maxDepth), size() / getNumLeafNodes() and writeBinary() in octomap's spelling.
+// readBinary() loads a .bt back into the map: the host parses the pruned tree, the device expands its leaves to voxels.
 #ifndef SBM_OCCUPANCY_HPP_
 #define SBM_OCCUPANCY_HPP_
 
@@ -164,6 +165,20 @@ class OccupancyMap {
     float c[5];
     check(sbm_occ_ray_logodds(&rp_, c));
     check(sbm_occ_write_binary_logodds(k.data(), v.data(), k.size(), p_.resolution, c[4], path.c_str()));
+  }
+
+  // tree.readBinary(filename) / tree.readBinary(stream): the map becomes what the .bt holds -- occupied leaves at the clamp max of
+  // rayParams(), free leaves at its clamp min, expanded to voxels on the device -- whatever it held before; further
+  // insertPointCloud / insertRays scans continue on it. octomap returns false where this throws (SBM_ERR_SIZE for a malformed
+  // stream or another resolution, SBM_ERR_UNSUPPORTED for a file that cannot be read or is no OcTree .bt, SBM_ERR_OCC_FULL for a
+  // map too small), and then the map is as it was.
+  bool readBinary(const std::string& filename) {
+    check(sbm_occ_read_binary(m_, filename.c_str(), &rp_, 1));
+    return true;
+  }
+  bool readBinary(const void* bytes, size_t n) {
+    check(sbm_occ_load_binary(m_, bytes, n, &rp_, 1));
+    return true;
   }
 
   // ---- queries: the map is not changed ---------------------------------------------------------------------------------------

@@ -1,0 +1,280 @@
+"""The GPU .bt loader (u96-slam_amd/csrc/sbm_occupancy.hip: the host parser and occ_load_kernel) against what the reference's own
+octomap read from the same streams (tests/golden/occupancy_load.npz) and, for key sets the fixture does not hold, against this
+library's own writers. Everything is compared for exact equality: sorted keys, the bits of the floats, and the bytes of the
+streams written back."""
+import ctypes
+import pathlib
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = pathlib.Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT / "tests"))
+import occupancy_load_cases as lc  # noqa: E402
+import occupancy_ref as occ  # noqa: E402
+from gpu_support import bm, build_callsite, dev, torch_cuda  # noqa: E402,F401
+
+pytestmark = pytest.mark.gpu
+GOLDEN = ROOT / "tests" / "golden"
+FX, STREAMS = lc.fixture()
+LOADABLE = sorted(n for n in STREAMS if n != "size1")          # size1 is one leaf of 2^48 voxels: see test_capacity
+QUERY = dict(np.load(GOLDEN / "occupancy_query.npz"))
+RAYS = dict(np.load(GOLDEN / "occupancy_rays.npz"))
+TREE = dict(np.load(GOLDEN / "occupancy_tree.npz"))
+CAPACITY = 1 << 16
+LONE = (0, 1, 2, 3, 4, 5, 6, 7, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025)
+
+
+def bits(a):
+    return np.asarray(a, np.float32).view(np.uint32)
+
+
+def gpu_params(pkg, rp, max_range=-1.0):
+    return pkg.occ_ray_params(rp.prob_hit, rp.prob_miss, rp.clamp_min, rp.clamp_max, rp.occupancy_thres, max_range)
+
+
+def recorded_voxels(name, tag="leaf"):
+    return lc.expand_centres(FX[f"{name}_{tag}_key"], FX[f"{name}_{tag}_depth"], FX[f"{name}_{tag}_value"])
+
+
+def scene_scan(index):
+    n = RAYS["scene_npoints"]
+    end = int(np.cumsum(n)[index])
+    return RAYS["scene_origins"][index], float(RAYS["scene_params"][5]), RAYS["scene_points"][end - int(n[index]):end]
+
+
+def same(got, want, what):
+    assert len(got[0]) == len(want[0]), (what, len(got[0]), len(want[0]))
+    assert np.array_equal(got[0], want[0]), (what, "keys")
+    assert np.array_equal(bits(got[1]), bits(want[1])), (what, "log-odds")
+
+
+@pytest.mark.parametrize("name", LOADABLE)
+def test_every_fixture_stream_loaded(pkg, bm, torch_cuda, tmp_path, name):
+    data, rp = STREAMS[name]
+    p = gpu_params(pkg, rp)
+    thres = float(pkg.occ_ray_logodds(p)[4])
+    omap = pkg.OccupancyMap(bm, CAPACITY)
+    try:
+        omap.load_binary(data, p)
+        want = recorded_voxels(name)
+        assert omap.size() == len(want[0]) == pkg.occ_binary_info(data)["voxels"] and omap.overflow() == 0
+        same(omap.fetch_logodds(), want, name)
+        omap.write_binary_logodds(tmp_path / "host.bt", p)
+        assert (tmp_path / "host.bt").read_bytes() == data                      # the input stream, byte for byte
+        tree = omap.tree(pkg.OCC_TREE_MAXLIKELIHOOD, p)
+        assert tree.info()["nodes"] == int(FX[f"{name}_size"])
+        assert tree.binary().cpu().numpy().tobytes() == data[data.index(b"data\n") + 5:]
+        tree.write_binary(tmp_path / "tree.bt")
+        assert (tmp_path / "tree.bt").read_bytes() == data
+        tree.close()
+        if f"{name}_search_found" in FX:
+            points = TREE[name[len("tree_"):] + "_points"]
+            found = FX[f"{name}_search_found"].astype(bool)
+            for got in (omap.search(dev(points), thres), omap.search(points, thres)):
+                st, v = (np.asarray(a.cpu() if hasattr(a, "cpu") else a) for a in got)
+                assert np.array_equal(st > 0, found), name
+                assert np.array_equal(v.view(np.uint32)[found], FX[f"{name}_search_value"][found]), name
+    finally:
+        omap.close()
+
+
+def query_scans(tree):
+    n = QUERY[f"{tree}_npoints"]
+    ends = np.cumsum(n)
+    return [(QUERY[f"{tree}_origins"][i], float(QUERY[f"{tree}_scan_range"][i]), QUERY[f"{tree}_points"][e - k:e])
+            for i, (k, e) in enumerate(zip(n, ends))]
+
+
+@pytest.mark.parametrize("tree", ["scene", "box"])
+def test_a_map_built_by_scans_written_and_loaded_into_a_second_map(pkg, bm, torch_cuda, tmp_path, tree):
+    probs = [float(v) for v in QUERY[f"{tree}_params"]]
+    p = pkg.occ_ray_params(*probs)
+    c = pkg.occ_ray_logodds(p)
+    first, second = pkg.OccupancyMap(bm, 1 << 14), pkg.OccupancyMap(bm, 1 << 14)
+    try:
+        for o, max_range, pts in query_scans(tree):
+            first.insert_cloud(dev(pts), o, pkg.occ_ray_params(*probs, max_range=max_range))
+        keys, lo = first.fetch_logodds()
+        assert np.array_equal(keys, QUERY[f"{tree}_keys"])
+        t = first.tree(pkg.OCC_TREE_MAXLIKELIHOOD, p)
+        t.write_binary(tmp_path / "first.bt")
+        t.close()
+        second.load_binary(tmp_path / "first.bt", p)
+        same(second.fetch_logodds(), (keys, np.where(lo >= c[4], c[3], c[2])), tree)     # the states under the threshold
+        sets = [str(s) for s in QUERY[f"{tree}_sets"] if f"{tree}_{s}_rays" in QUERY]
+        assert sets
+        for s in sets:
+            rays = QUERY[f"{tree}_{s}_rays"]
+            o, d = dev(np.ascontiguousarray(rays[:, :3])), dev(np.ascontiguousarray(rays[:, 3:]))
+            for ignore in (False, True):
+                for max_range in (-1.0, 2.5):
+                    q = pkg.occ_query_params(max_range, float(c[4]), ignore)
+                    a, b = first.cast_rays(o, d, q), second.cast_rays(o, d, q)
+                    assert bool((a[0] == b[0]).all()), (tree, s, "status")
+                    assert np.array_equal(a[1].cpu().numpy().view(np.uint32), b[1].cpu().numpy().view(np.uint32)), (tree, s, "end")
+    finally:
+        first.close()
+        second.close()
+
+
+@pytest.mark.parametrize("name", [str(s).split(":")[0] for s in FX["post_scan"]])
+def test_load_then_one_more_scan(pkg, bm, torch_cuda, name):
+    data, rp = STREAMS[name]
+    index = int(dict(str(s).split(":") for s in FX["post_scan"])[name])
+    o, max_range, pts = scene_scan(index)
+    omap = pkg.OccupancyMap(bm, CAPACITY)
+    try:
+        omap.load_binary(data, gpu_params(pkg, rp))
+        omap.insert_cloud(dev(pts), o, gpu_params(pkg, rp, max_range))
+        same(omap.fetch_logodds(), recorded_voxels(name, "post"), name)
+        assert omap.overflow() == 0
+    finally:
+        omap.close()
+
+
+def edge_keys(k):
+    """k lone voxels low in Morton order, then a full depth-13 cube, a full depth-12 cube and one depth-15 group"""
+    codes = np.concatenate([8 * np.arange(k), 100 * 512 + np.arange(512), 20 * 4096 + np.arange(4096), 20000 * 8 + np.arange(8)])
+    return np.sort(lc._unmorton_array(codes.astype(np.uint64)))
+
+
+@pytest.mark.parametrize("k", LONE)
+def test_lane_and_tile_edges(pkg, bm, torch_cuda, tmp_path, k):
+    keys = edge_keys(k)
+    c = pkg.occ_ray_logodds()
+    omap = pkg.OccupancyMap(bm, CAPACITY)
+    try:
+        for value, want in ((1.0, c[3]), (-1.0, c[2])):                  # every leaf occupied, then every leaf free
+            pkg.occ_write_binary_logodds(keys, np.full(len(keys), value, np.float32), tmp_path / "edge.bt", 0.1, 0.0)
+            data = (tmp_path / "edge.bt").read_bytes()
+            info = pkg.occ_binary_info(data)
+            assert info["voxels"] == len(keys) == k + 512 + 4096 + 8 and info["leaves"] == k + 3
+            assert info["leaves_at"][12] == info["leaves_at"][13] == info["leaves_at"][15] == 1
+            omap.load_binary(data)
+            same(omap.fetch_logodds(), (keys, np.full(len(keys), want, np.float32)), (k, value))
+            assert omap.overflow() == 0
+    finally:
+        omap.close()
+
+
+@pytest.mark.parametrize("k", range(8))
+def test_shift_streams_at_every_sibling_boundary(pkg, bm, torch_cuda, k):
+    data, rp = STREAMS[f"tree_shift_{k}"]
+    omap = pkg.OccupancyMap(bm, 5120 + k)                                # exactly the voxels of the stream
+    try:
+        omap.load_binary(data, gpu_params(pkg, rp))
+        keys, _ = omap.fetch_logodds()
+        assert np.array_equal(keys, TREE[f"shift_{k}_keys"]) and omap.overflow() == 0
+    finally:
+        omap.close()
+
+
+def scene_hits(pkg, omap):
+    m = pkg.StereoModel()
+    ref = occ.model_from_array(QUERY["scene_model"])
+    ctypes.memmove(ctypes.byref(m), ctypes.byref(ref), ctypes.sizeof(m))
+    omap.insert(dev(QUERY["scene_disp"]), m, QUERY["scene_poses"], int(QUERY["scene_scale"]))
+    keys, counts = omap.keys()
+    assert np.array_equal(keys, QUERY["scene_hits_keys"]) and np.array_equal(counts, QUERY["scene_hits_counts"])
+
+
+def refused(pkg, call, code):
+    with pytest.raises(pkg.StereoBMError) as e:
+        call()
+    assert e.value.code == code, (e.value.code, code)
+
+
+def test_capacity_and_what_a_refused_load_leaves(pkg, bm, torch_cuda, tmp_path):
+    data, rp = STREAMS["tree_shift_3"]                                   # 5123 voxels
+    p = gpu_params(pkg, rp)
+    exact, small = pkg.OccupancyMap(bm, 5123), pkg.OccupancyMap(bm, 5122)
+    other = pkg.OccupancyMap(bm, CAPACITY, resolution=0.05)
+    try:
+        exact.load_binary(data, p)
+        assert exact.size() == 5123 and exact.overflow() == 0
+        o, max_range, pts = scene_scan(0)
+        small.insert_cloud(dev(pts), o, gpu_params(pkg, rp, max_range))
+        before = small.fetch_logodds()
+        refused(pkg, lambda: small.load_binary(data, p), lc.OCC_FULL)                              # one voxel more than the capacity
+        refused(pkg, lambda: small.load_binary(STREAMS["size1"][0], p), lc.OCC_FULL)               # 2^48 voxels
+        for name, (bad, code) in lc.malformed(STREAMS["tree_scene"][0]).items():
+            refused(pkg, lambda: small.load_binary(bad, p), code)
+        refused(pkg, lambda: small.load_binary(tmp_path / "no-such-file.bt", p), lc.UNSUPPORTED)
+        refused(pkg, lambda: small.load_binary(STREAMS["tree_one"][0], pkg.occ_ray_params(clamp_min=0.99)), lc.SIZE)
+        refused(pkg, lambda: other.load_binary(STREAMS["tree_one"][0], p), lc.SIZE)                # res 0.1 into a 0.05 map
+        same(small.fetch_logodds(), before, "after the refused loads")
+        small.insert_cloud(dev(pts), o, gpu_params(pkg, rp, max_range))                            # and it is still a log-odds map
+        small.load_binary(STREAMS["octomap_empty"][0], p)                                          # size 0: empty, no mode
+        assert small.size() == 0
+        scene_hits(pkg, small)                                                                     # a hit-mode map ...
+        small.load_binary(STREAMS["tree_one"][0], p)                                               # ... is replaced by a load
+        same(small.fetch_logodds(), recorded_voxels("tree_one"), "over a hit-mode map")
+        refused(pkg, lambda: small.keys(), lc.UNSUPPORTED)
+        small.reset()                                                                              # reset after a load, then hits
+        scene_hits(pkg, small)
+    finally:
+        exact.close()
+        small.close()
+        other.close()
+
+
+def test_async_profile_and_path_form(pkg, torch_cuda, tmp_path):
+    data, rp = STREAMS["rays_random"]
+    eng = pkg.StereoBM.create(64, 21)
+    omap = pkg.OccupancyMap(eng, CAPACITY)
+    try:
+        p = gpu_params(pkg, rp)
+        omap.load_binary(data, p, sync=False)
+        assert omap.size() == pkg.occ_binary_info(data)["voxels"]             # a synchronous call follows the load in stream order
+        want = omap.fetch_logodds()
+        same(want, recorded_voxels("rays_random"), "sync=False")
+        (tmp_path / "random.bt").write_bytes(data)
+        omap.load_binary(str(tmp_path / "random.bt"), p)
+        same(omap.fetch_logodds(), want, "the path form")
+        omap.load_binary(np.frombuffer(data, np.uint8), p)
+        same(omap.fetch_logodds(), want, "an array of bytes")
+        eng.set_profiling(True)
+        omap.load_binary(data, p)
+        prof = omap.profile()
+        assert prof["occ_load"] > 0 and prof["occ_rays_mark"] == 0 and prof["occ_fetch"] == 0
+        omap.fetch_logodds()
+        assert omap.profile()["occ_load"] == prof["occ_load"]                 # a fetch keeps the load's time
+    finally:
+        eng.set_profiling(False)
+        omap.close()
+        eng.close()
+
+
+def test_cpp_call_site(pkg, torch_cuda, tmp_path):
+    name = "tree_scene"
+    data, rp = STREAMS[name]
+    assert bytes(gpu_params(pkg, rp)) == bytes(pkg.occ_ray_params())       # the adaptor's defaults are this stream's constants
+    exe, built = build_callsite(tmp_path, "occupancy_load_callsite_main.cpp")
+    assert built.returncode == 0, built.stderr
+    points = TREE["scene_points"]
+    index = int(dict(str(s).split(":") for s in FX["post_scan"])[name])
+    o, max_range, pts = scene_scan(index)
+    (tmp_path / "in.bt").write_bytes(data)
+    points.tofile(tmp_path / "points.raw")
+    scan = np.concatenate([np.float32([len(pts)]), o, pts.reshape(-1)]).astype(np.float32)
+    scan.tofile(tmp_path / "scan.raw")
+    after = recorded_voxels(name, "post")
+    for form in ([], ["bytes"]):
+        args = [str(exe), str(tmp_path / "in.bt"), str(CAPACITY), str(tmp_path / "points.raw"), str(len(points)), str(tmp_path / "scan.raw"),
+                str(len(scan)), repr(max_range), str(tmp_path / "out.raw"), str(tmp_path / "again.bt")] + form
+        r = subprocess.run(args, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert r.stdout.split() == ["loaded", str(pkg.occ_binary_info(data)["voxels"]), "after", str(len(after[0])), "overflow", "0"], r.stdout
+        assert (tmp_path / "again.bt").read_bytes() == data
+        raw = (tmp_path / "out.raw").read_bytes()
+        head = np.frombuffer(raw, np.dtype([("state", "<i4"), ("value", "<u4")]), len(points))
+        found = FX[f"{name}_search_found"].astype(bool)
+        assert np.array_equal(head["state"] > 0, found) and np.array_equal(head["value"][found], FX[f"{name}_search_value"][found])
+        tail = np.frombuffer(raw, np.dtype([("key", "<u8"), ("value", "<u4")]), len(after[0]), 8 * len(points))
+        assert np.array_equal(tail["key"], after[0]) and np.array_equal(tail["value"], bits(after[1]))
+    r = subprocess.run([str(exe), str(tmp_path / "missing.bt"), "16", str(tmp_path / "points.raw"), "0", str(tmp_path / "scan.raw"), "0", "-1",
+                        str(tmp_path / "out.raw"), str(tmp_path / "again.bt")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 4 and r.stdout.split() == ["error", str(lc.UNSUPPORTED)], r.stdout + r.stderr

@@ -1,0 +1,52 @@
+// Stand-alone host check of the .bt parser (sbm_occ_binary_info, sbm_occ_binary_leaves) under AddressSanitizer and
+// UndefinedBehaviorSanitizer: every truncation of each stream given, and every byte of it set to 0x00, 0xFF, 0x03, 0x55 and 0xAA
+// (every seventh byte for a stream above 4000 bytes), each from an exact-size heap copy so that a read past the end is seen.
+// Built and run by hand on the host, with its own instrumented copy of the parser and the library for everything else; it
+// never touches a GPU:
+//
+//     hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
+//           -Xarch_host -fno-sanitize-recover=undefined -I include -I u96-slam_amd/csrc u96-slam_amd/csrc/sbm_occupancy.hip \
+//           tools/occupancy_load_sanitize.cpp -L u96-slam_amd/lib -lsbm_hip -Wl,-rpath,$PWD/u96-slam_amd/lib -o occ_load_san
+//     ASAN_OPTIONS=detect_leaks=0 ./occ_load_san a.bt b.bt ...
+//
+// Prints the number of calls and how many streams were accepted; a finding ends the run with the sanitizer's report.
+#include <cstdio>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+#include "sbm.h"
+static std::vector<uint8_t> slurp(const char* p) {
+  std::vector<uint8_t> v; FILE* f = fopen(p, "rb"); if (!f) return v;
+  for (int c; (c = fgetc(f)) != EOF;) v.push_back((uint8_t)c);
+  fclose(f); return v;
+}
+static long run(const uint8_t* b, size_t n) {
+  // an exact-size heap copy, so that a read past the end is seen
+  uint8_t* copy = new uint8_t[n ? n : 1];
+  memcpy(copy, b, n);
+  sbm_occ_binary_header h;
+  int st = sbm_occ_binary_info(copy, n, &h);
+  size_t count = 0;
+  int st2 = sbm_occ_binary_leaves(copy, n, nullptr, nullptr, nullptr, 0, &count);
+  if (st == SBM_OK && count) {
+    std::vector<uint64_t> k(count); std::vector<int32_t> d(count); std::vector<uint8_t> o(count);
+    st2 = sbm_occ_binary_leaves(copy, n, k.data(), d.data(), o.data(), count, &count);
+    if (st2 != SBM_OK) { printf("inconsistent %d %d\n", st, st2); }
+  }
+  delete[] copy;
+  return st;
+}
+int main(int argc, char** argv) {
+  long calls = 0, ok = 0;
+  for (int a = 1; a < argc; a++) {
+    std::vector<uint8_t> v = slurp(argv[a]);
+    for (size_t cut = 0; cut <= v.size(); cut++) { ok += run(v.data(), cut) == SBM_OK; calls++; }
+    const size_t step = v.size() > 4000 ? 7 : 1;
+    for (size_t i = 0; i < v.size(); i += step)
+      for (int x : {0x00, 0xFF, 0x03, 0x55, 0xAA}) {
+        std::vector<uint8_t> w = v; w[i] = (uint8_t)x; ok += run(w.data(), w.size()) == SBM_OK; calls++;
+      }
+  }
+  printf("calls %ld accepted %ld\n", calls, ok);
+  return 0;
+}

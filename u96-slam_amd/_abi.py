@@ -128,6 +128,14 @@ class OccTreeCounts(ctypes.Structure):
                 ("key_max", ctypes.c_uint16 * 3), ("pad", ctypes.c_uint32)]
 
 
+class OccBinaryHeader(ctypes.Structure):
+    """`sbm_occ_binary_header` of include/sbm.h: what sbm_occ_binary_info reports of a .bt stream."""
+
+    _fields_ = [("resolution", ctypes.c_double), ("size", ctypes.c_uint64), ("nodes", ctypes.c_uint64), ("leaves", ctypes.c_uint64),
+                ("occupied", ctypes.c_uint64), ("voxels", ctypes.c_uint64), ("leaves_at", ctypes.c_uint64 * 17),
+                ("key_min", ctypes.c_uint16 * 3), ("key_max", ctypes.c_uint16 * 3), ("pad", ctypes.c_uint32)]
+
+
 class VwdParams(ctypes.Structure):
     """`sbm_vwd_params` of include/sbm.h: addNewWords' metric and NNDR ratio (VWDictionary.cpp:43), and the search's slice count."""
 
@@ -357,6 +365,10 @@ def load_library():
     L.sbm_occ_tree_leaves.argtypes = [vp, ci, vp, vp, vp, sz, ctypes.POINTER(sz)]
     L.sbm_occ_tree_binary_device.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
     L.sbm_occ_tree_write_binary.argtypes = [vp, ctypes.c_char_p]
+    L.sbm_occ_binary_info.argtypes = [vp, sz, ctypes.POINTER(OccBinaryHeader)]
+    L.sbm_occ_binary_leaves.argtypes = [vp, sz, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_load_binary.argtypes = [vp, vp, sz, orp, ci]
+    L.sbm_occ_read_binary.argtypes = [vp, ctypes.c_char_p, orp, ci]
     wp = ctypes.POINTER(VwdParams)
     pi = ctypes.POINTER(ci)
     L.sbm_vwd_params_default.argtypes = [wp]

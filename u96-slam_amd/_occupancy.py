@@ -8,7 +8,7 @@ import numpy as np
 
 from ._abi import (ERR_OCC_FULL, OCC_CELL_FREE, OCC_CELL_OCCUPIED, OCC_CELL_OUT, OCC_CELL_UNKNOWN, OCC_RAY_BOUNDS,  # noqa: F401
                    OCC_RAY_HIT, OCC_RAY_NONE, OCC_RAY_RANGE, OCC_RAY_UNKNOWN, OCC_TREE_LOGODDS, OCC_TREE_MAXLIKELIHOOD, OccParams,
-                   OccQueryParams, OccRayParams, OccTreeCounts, StereoBMError, _check, _torch, load_library)
+                   OccBinaryHeader, OccQueryParams, OccRayParams, OccTreeCounts, StereoBMError, _check, _torch, load_library)
 
 
 def occ_params(resolution=0.1, range_max=5.0, tree_depth=16):
@@ -57,6 +57,39 @@ def occ_write_binary_logodds(keys, logodds, path, resolution=0.1, occupancy_thre
     _check(load_library().sbm_occ_write_binary_logodds(keys.ctypes.data if len(keys) else None,
                                                        logodds.ctypes.data if len(keys) else None, len(keys), float(resolution),
                                                        float(occupancy_thres_log), os.fsencode(path)))
+
+
+def _stream(data):
+    """A .bt stream as a contiguous uint8 array (bytes, bytearray, memoryview or a numpy array of bytes)"""
+    if isinstance(data, np.ndarray):
+        return np.ascontiguousarray(data, np.uint8).reshape(-1)
+    return np.frombuffer(bytes(data), np.uint8)
+
+
+def occ_binary_info(data):
+    """What a .bt stream holds, parsed on the host (no GPU): dict of resolution, size (the header's), nodes (read), leaves,
+    occupied, voxels (depth-16 voxels below the leaves), leaves_at per depth 0..16, key_min / key_max per axis."""
+    b = _stream(data)
+    h = OccBinaryHeader()
+    _check(load_library().sbm_occ_binary_info(b.ctypes.data if len(b) else None, len(b), ctypes.byref(h)))
+    return dict(resolution=h.resolution, size=h.size, nodes=h.nodes, leaves=h.leaves, occupied=h.occupied, voxels=h.voxels,
+                leaves_at=list(h.leaves_at), key_min=list(h.key_min), key_max=list(h.key_max))
+
+
+def occ_binary_leaves(data):
+    """The leaves of a .bt stream in stream order, parsed on the host (no GPU) -> (packed key of each cube's lowest voxel uint64,
+    depth int32, occupied uint8)."""
+    b = _stream(data)
+    L = load_library()
+    n = ctypes.c_size_t()
+    ptr = b.ctypes.data if len(b) else None
+    st = L.sbm_occ_binary_leaves(ptr, len(b), None, None, None, 0, ctypes.byref(n))
+    if st != -2 or not n.value:      # -2 with a count: the arrays are too small, as asked
+        _check(st)
+    keys, depth, occ = np.empty(n.value, np.uint64), np.empty(n.value, np.int32), np.empty(n.value, np.uint8)
+    if n.value:
+        _check(L.sbm_occ_binary_leaves(ptr, len(b), keys.ctypes.data, depth.ctypes.data, occ.ctypes.data, n.value, ctypes.byref(n)))
+    return keys, depth, occ
 
 
 def occ_query_params(max_range=-1.0, occupancy_thres_log=0.0, ignore_unknown=False):
@@ -185,6 +218,20 @@ class OccupancyMap:
             self._engine._inflight.clear()
         else:
             self._engine._inflight.append((d3,))
+
+    def load_binary(self, data_or_path, params=None, sync=True, **kw):
+        """octomap's readBinary: replace the map's content by the voxels of a .bt stream -- bytes (or a uint8 array), or the
+        path of a file (str or os.PathLike). Occupied leaves hold the clamp-max log-odds of `params`, free leaves clamp min;
+        the map is then a log-odds map that further insert_cloud / insert_rays scans continue."""
+        rp = self._ray_params(params, kw)
+        if isinstance(data_or_path, (str, os.PathLike)):
+            st = self._L.sbm_occ_read_binary(self._m, os.fsencode(data_or_path), rp, 1 if sync else 0)
+        else:
+            b = _stream(data_or_path)
+            st = self._L.sbm_occ_load_binary(self._m, b.ctypes.data if len(b) else None, len(b), rp, 1 if sync else 0)
+        _check(st, self._engine._h)
+        if sync:
+            self._engine._inflight.clear()
 
     def fetch_logodds(self, allow_overflow=False):
         """(packed keys uint64 ascending, log-odds float32) of a log-odds map as numpy arrays."""
@@ -343,7 +390,8 @@ class OccupancyMap:
         return OccupancyTree(self).build(reading, params, sync)
 
     def profile(self):
-        return self._engine._profile(("occ_insert", "occ_fetch", "occ_rays_mark", "occ_rays_apply", "occ_search", "occ_cast"))
+        return self._engine._profile(("occ_insert", "occ_fetch", "occ_rays_mark", "occ_rays_apply", "occ_search", "occ_cast",
+                                     "occ_load"))
 
 
 class OccupancyTree:

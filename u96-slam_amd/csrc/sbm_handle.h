@@ -96,7 +96,7 @@ StageTable bm_stages(), sgbm_stages(), gftt_select_stages(), gftt_cv_stages(), o
 // stage the milliseconds of the last call summed over its chunks. All zero is a valid clock. A family whose stages run back to
 // back has one enum for both: mark s is recorded as stage s begins, the total's mark at the end.
 struct StageClock {
-  static constexpr int kMax = 8;
+  static constexpr int kMax = 12;
   bool on;   // this call is timed
   hipEvent_t ev[kMax];
   float ms[kMax];

@@ -13,15 +13,19 @@
 //                       touched slot its ONE update (occupied wins) and clears the flags.
 //   occ_search / occ_cast_rays / occ_cast_view   the read side, octomap's search and castRay: one lane per point, ray or pixel
 //                       probes the table with plain loads and walks castRay's DDA in registers; the map is not written.
+//   occ_load_kernel     readBinary: the host parses the pruned tree of a .bt stream, and one lane per depth-16 voxel finds its leaf
+//                       in the prefix array of the leaf volumes, de-interleaves its Morton code and claims its slot.
 //   occ_compact_kernel  occupied slots -> dense (key, hits) arrays, one atomic per wavefront.
 //   occ_hist / occ_scan / occ_scatter   one 8-bit pass of an LSD radix sort: digit counts per tile, an exclusive scan of the
 //                       digit-major count table, and a stable scatter (one wavefront per tile walks it 64 keys at a time and
 //                       ranks equal digits by ballots).
 #include <math.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include <algorithm>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "sbm_consume_math.h"
@@ -438,10 +442,10 @@ static int occ_check_insert(const sbm_occ_map* map, int n, const void* disp, int
 }
 
 // Stage times: an insert and a fetch are separate calls that share the clock's two marks, and each keeps the other's last time.
-enum OccStage { kOccInsert, kOccFetch, kOccRaysMark, kOccRaysApply, kOccSearch, kOccCast, kOccTreeBuild, kOccTreeQuery, kOccStageCount };
+enum OccStage { kOccInsert, kOccFetch, kOccRaysMark, kOccRaysApply, kOccSearch, kOccCast, kOccTreeBuild, kOccTreeQuery, kOccLoad, kOccStageCount };
 enum OccMark { kOccBegin, kOccEnd, kOccMid, kOccMarkCount };
 static const char* const kOccNames[] = {"occ_insert", "occ_fetch", "occ_rays_mark", "occ_rays_apply", "occ_search", "occ_cast",
-                                        "occ_tree_build", "occ_tree_query"};
+                                        "occ_tree_build", "occ_tree_query", "occ_load"};
 StageTable occ_stages() { return stage_table<kOccStageCount, kOccMarkCount>(kOccNames); }
 
 // A call begins: it times stages a and b (the same for one) from zero and keeps the last times of the family's other stages.
@@ -550,15 +554,22 @@ static int occ_ray_params_check(const sbm_occ_ray_params* p) {
   return SBM_OK;
 }
 
-// The first log-odds insert after create or reset allocates the flag words and the touched list and fixes the mode.
-static int occ_rays_begin(sbm_occ_map* map, const sbm_occ_ray_params* p, OccRay* g, OccTable* t) {
+// What the log-odds mode keeps beside the table, 8 B per slot: the flag words, clear between scans, and the touched list
+static int occ_logodds_alloc(sbm_occ_map* map) {
   sbm_handle* h = map->h;
-  if (map->mode == kOccModeHits) return SBM_ERR_UNSUPPORTED;
   if (!map->flags.p) {
     HIPCHK(h, map->flags.grow((size_t)map->slots * 4, h->stream));
     HIPCHK(h, hipMemsetAsync(map->flags.p, 0, (size_t)map->slots * 4, h->stream));
   }
   HIPCHK(h, map->touched.grow((size_t)map->slots * 4, h->stream));
+  return SBM_OK;
+}
+
+// The first log-odds insert after create or reset allocates the flag words and the touched list and fixes the mode.
+static int occ_rays_begin(sbm_occ_map* map, const sbm_occ_ray_params* p, OccRay* g, OccTable* t) {
+  if (map->mode == kOccModeHits) return SBM_ERR_UNSUPPORTED;
+  const int st = occ_logodds_alloc(map);
+  if (st != SBM_OK) return st;
   map->mode = kOccModeLogOdds;
   g->max_range = p->max_range;
   g->resolution = map->p.resolution;
@@ -979,6 +990,147 @@ static int occ_write_stream(const std::vector<uint64_t>& leaf, double resolution
   return occ_write_file(body, nodes, resolution, path);
 }
 
+// ---- reading a .bt stream (include/sbm.h, "occupancy map: load a .bt stream"): the host parser ------------------------------
+__host__ __device__ unsigned occ_unspread(unsigned long long x);   // below, with the Morton codes of the tree
+
+// A leaf as the parser hands it on and the device takes it: first Morton code of the cube << 8 | depth << 1 | occupied
+typedef unsigned long long OccBtLeaf;
+static uint64_t occ_bt_code(OccBtLeaf l) { return l >> 8; }
+static int occ_bt_depth(OccBtLeaf l) { return (int)(l >> 1 & 31); }
+
+struct OccBtParse {
+  sbm_occ_binary_header info;
+  std::vector<OccBtLeaf>* leaves;   // null: count only
+  bool bounds;                      // key_min / key_max are wanted
+  const uint8_t *at, *end;
+};
+
+// AbstractOcTree::readHeader on bytes [*pos, n): tokens up to the line `data`. SBM_ERR_SIZE where the stream ends first or a
+// number does not parse (octomap's stream fails there and its loop ends without `data`).
+static int occ_bt_header(const uint8_t* b, size_t n, size_t* pos, std::string* id, uint64_t* size, double* res) {
+  size_t i = *pos;
+  const auto space = [](uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); };
+  const auto skip_line = [&] {
+    while (i < n && b[i] != '\n') i++;
+    if (i < n) i++;
+  };
+  const auto token = [&](std::string* t) {
+    t->clear();
+    while (i < n && space(b[i])) i++;
+    while (i < n && !space(b[i])) t->push_back((char)b[i++]);
+    return !t->empty();
+  };
+  std::string t;
+  while (token(&t)) {
+    if (t == "data") {
+      skip_line();
+      *pos = i;
+      return SBM_OK;
+    }
+    if (t[0] == '#') {
+      skip_line();
+    } else if (t == "id") {
+      if (!token(id)) return SBM_ERR_SIZE;
+    } else if (t == "res" || t == "size") {
+      while (i < n && space(b[i])) i++;
+      char num[64];
+      size_t len = 0;
+      while (i + len < n && !space(b[i + len]) && len + 1 < sizeof(num)) num[len] = (char)b[i + len], len++;
+      num[len] = 0;
+      char* stop = num;
+      if (t == "res") {
+        *res = strtod(num, &stop);
+      } else {
+        if (num[0] < '0' || num[0] > '9') return SBM_ERR_SIZE;
+        const unsigned long long v = strtoull(num, &stop, 10);
+        if (v > 0xFFFFFFFFull) return SBM_ERR_SIZE;   // octomap's size is an unsigned
+        *size = v;
+      }
+      if (stop == num) return SBM_ERR_SIZE;
+      i += (size_t)(stop - num);   // what follows the number is the next token, as operator>> leaves it
+    } else {
+      skip_line();   // an unknown keyword: octomap warns and skips the line
+    }
+  }
+  return SBM_ERR_SIZE;
+}
+
+// A leaf of the pruned tree: the node with Morton prefix `code` at `depth`
+static int occ_bt_leaf(OccBtParse& p, uint64_t code, int depth, bool occupied) {
+  sbm_occ_binary_header& o = p.info;
+  const int level = 16 - depth;
+  o.leaves++;
+  o.leaves_at[depth]++;
+  o.occupied += occupied ? 1 : 0;
+  o.voxels += (uint64_t)1 << (3 * level);
+  const uint64_t first = code << (3 * level);
+  if (p.bounds) {
+    const unsigned k[3] = {occ_unspread(first), occ_unspread(first >> 1), occ_unspread(first >> 2)};
+    for (int a = 0; a < 3; a++) {
+      o.key_min[a] = (uint16_t)std::min<unsigned>(o.key_min[a], k[a]);
+      o.key_max[a] = (uint16_t)std::max<unsigned>(o.key_max[a], k[a] + (1u << level) - 1);
+    }
+  }
+  if (p.leaves) p.leaves->push_back(first << 8 | (OccBtLeaf)depth << 1 | (occupied ? 1u : 0u));
+  return SBM_OK;
+}
+
+// readBinaryNode of the node with Morton prefix `code` at `depth`, whose record is at p.at. Children in child order, depth first:
+// the leaves arrive in Morton order.
+static int occ_bt_node(OccBtParse& p, uint64_t code, int depth) {
+  if (p.end - p.at < 2) return SBM_ERR_SIZE;   // the stream ends inside the tree
+  const unsigned word = p.at[0] | (unsigned)p.at[1] << 8;
+  p.at += 2;
+  if (!word) return occ_bt_leaf(p, code, depth, true);   // a childless node keeps the clamp max readBinaryNode gave it
+  for (int c = 0; c < 8; c++) {
+    const unsigned kind = word >> (2 * c) & 3;
+    if (!kind) continue;
+    p.info.nodes++;
+    int st;
+    if (kind != 3) st = occ_bt_leaf(p, code << 3 | c, depth + 1, kind == 2);
+    else if (depth + 1 >= 16) st = SBM_ERR_SIZE;             // a node below depth 16
+    else st = occ_bt_node(p, code << 3 | c, depth + 1);
+    if (st != SBM_OK) return st;
+  }
+  return SBM_OK;
+}
+
+// AbstractOccupancyOcTree::readBinary on n bytes -> the header's counts and, with `leaves`, the leaves in stream order
+static int occ_bt_parse(const uint8_t* b, size_t n, sbm_occ_binary_header* info, std::vector<OccBtLeaf>* leaves, bool bounds = true) {
+  static const char magic[] = "# Octomap OcTree binary file";
+  OccBtParse p;
+  memset(&p.info, 0, sizeof(p.info));
+  for (int a = 0; a < 3; a++) p.info.key_min[a] = 0xFFFF;
+  p.leaves = leaves;
+  p.bounds = bounds && info != nullptr;
+  int st = SBM_OK;
+  size_t pos = 0;
+  std::string id;
+  try {
+    if (n < sizeof(magic) - 1 || memcmp(b, magic, sizeof(magic) - 1) != 0) {
+      st = SBM_ERR_UNSUPPORTED;   // the legacy header, or no .bt at all
+    } else {
+      while (pos < n && b[pos] != '\n') pos++;   // std::getline
+      if (pos < n) pos++;
+      st = occ_bt_header(b, n, &pos, &id, &p.info.size, &p.info.resolution);
+    }
+    if (st == SBM_OK && id != "OcTree" && id != "1") st = SBM_ERR_UNSUPPORTED;   // "1" is the id octomap itself renames
+    if (st == SBM_OK && !(p.info.resolution > 0.)) st = SBM_ERR_SIZE;
+    if (st == SBM_OK && p.info.size > 0) {
+      if (leaves) leaves->reserve((size_t)std::min<uint64_t>(p.info.size, 4 * (uint64_t)(n - pos)));   // a record has 8 children at most
+      p.at = b + pos;
+      p.end = b + n;
+      p.info.nodes = 1;
+      st = occ_bt_node(p, 0, 0);
+    }
+  } catch (const std::bad_alloc&) {
+    st = SBM_ERR_NOMEM;
+  }
+  if (st == SBM_OK && p.info.nodes != p.info.size) st = SBM_ERR_SIZE;   // calcNumNodes() against the header
+  if (info) *info = p.info;
+  return st;
+}
+
 // ---- the octree above the voxels (include/sbm.h, "occupancy map: the octree above the voxels") ------------------------------
 // A snapshot: the map's voxels sorted by Morton code are depth 16, and sixteen bottom-up passes put the sixteen levels above
 // them, each level its own ascending code array. Siblings are neighbours in that order, so a parent is made by the first of its
@@ -1040,6 +1192,74 @@ __host__ __device__ __forceinline__ unsigned occ_unspread(unsigned long long x) 
 // computeChildIdx from the top bit down: x in bit 0, y in bit 1, z in bit 2 of every triple (occ_morton, on the host)
 __host__ __device__ __forceinline__ unsigned long long occ_code(unsigned k0, unsigned k1, unsigned k2) {
   return occ_spread(k0) | occ_spread(k1) << 1 | occ_spread(k2) << 2;
+}
+
+// ---- loading a .bt stream: the expansion -----------------------------------------------------------------------------------
+// A pruned leaf of depth d stands for 8^(16-d) voxels whose Morton codes are its first code OR'd with 0 .. 8^(16-d) - 1.
+struct OccLoad {
+  uint32_t leaves, total;        // total: the voxels of all leaves, at most 2^30
+  uint32_t mask, max_probe;
+  unsigned vmin, vmax;           // float bits of the clamp log-odds: a free leaf's value and an occupied leaf's
+};
+
+#ifndef SBM_OCC_LOAD_SHARED
+#define SBM_OCC_LOAD_SHARED 0   // 1 builds the wavefront-shared leaf search, for tools/bench_occupancy_load.py to time
+#endif
+constexpr bool kOccLoadShared = SBM_OCC_LOAD_SHARED != 0;
+
+// One output voxel per lane. leaf[j]: first code << 8 | depth << 1 | occupied; first[j]: the voxels of the leaves before j
+// (strictly ascending, first[0] == 0). The voxels of one load are distinct, so a claimed slot has one writer: the value is a plain
+// store, and the only atomics are the key's compare-and-swap and the integer counters, one add per wavefront.
+__global__ void __launch_bounds__(256) occ_load_kernel(const unsigned long long* __restrict__ leaf, const unsigned* __restrict__ first,
+                                                        OccLoad g, unsigned long long* __restrict__ keys, unsigned* __restrict__ vals,
+                                                        OccCounters* __restrict__ ctr) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  const bool live = i < g.total;
+  bool claimed = false, lost = false;
+  if (live) {
+    uint32_t lo = 0, hi = g.leaves;   // the last leaf with first[leaf] <= i
+    if (kOccLoadShared) {             // lane 0's leaf first: a leaf holds at least one voxel, so lane l's is at most l leaves on
+      if ((threadIdx.x & 63) == 0)
+        while (hi - lo > 1) {
+          const uint32_t mid = lo + (hi - lo) / 2;
+          if (first[mid] <= i) lo = mid;
+          else hi = mid;
+        }
+      lo = __builtin_amdgcn_readfirstlane(lo);   // lane 0 is live wherever a lane of its wavefront is
+      hi = min(lo + (threadIdx.x & 63) + 1, g.leaves);
+    }
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (first[mid] <= i) lo = mid;
+      else hi = mid;
+    }
+    const unsigned long long word = leaf[lo];
+    const unsigned long long code = (word >> 8) | (unsigned long long)(i - first[lo]);
+    const unsigned long long key = (unsigned long long)occ_unspread(code) << 32 | (unsigned long long)occ_unspread(code >> 1) << 16 |
+                                   occ_unspread(code >> 2);
+    lost = true;
+    uint32_t slot = occ_hash(key, g.mask);
+    for (uint32_t probe = 0; probe < g.max_probe; probe++, slot = (slot + 1) & g.mask) {
+      unsigned long long cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (cur == kOccEmpty) {
+        cur = atomicCAS(&keys[slot], kOccEmpty, key);
+        if (cur == kOccEmpty) {
+          claimed = true;
+          cur = key;
+        }
+      }
+      if (cur == key) {
+        vals[slot] = (word & 1) ? g.vmax : g.vmin;
+        lost = false;
+        break;
+      }
+    }
+  }
+  const unsigned long long got = __ballot(claimed), over = __ballot(lost);
+  if ((threadIdx.x & 63) == 0) {
+    if (got) atomicAdd(&ctr->size, (unsigned)__popcll(got));
+    if (over) atomicAdd(&ctr->overflow, (unsigned long long)__popcll(over));
+  }
 }
 
 __device__ __forceinline__ unsigned occ_wave_min(unsigned v) {
@@ -1579,6 +1799,73 @@ static int occ_tree_binary_run(sbm_occ_tree* t, uint8_t* d_bytes, size_t cap, si
   });
 }
 
+// ---- loading a .bt stream, host side ----------------------------------------------------------------------------------------
+// What sbm_occ_write_binary* print for a resolution (%g), read back
+static double occ_printed_resolution(double resolution) {
+  char text[64];
+  snprintf(text, sizeof(text), "%g", resolution);
+  return strtod(text, nullptr);
+}
+
+// readBinary into the map. Everything that can refuse the stream comes before the map is touched.
+static int occ_load_run(sbm_occ_map* map, const uint8_t* bytes, size_t n, const sbm_occ_ray_params* p, int sync) {
+  sbm_handle* h = map->h;
+  sbm_occ_binary_header info;
+  std::vector<OccBtLeaf> leaves;
+  int st = occ_bt_parse(bytes, n, &info, &leaves, false);
+  if (st != SBM_OK) return st;
+  if (info.resolution != occ_printed_resolution(map->p.resolution)) return SBM_ERR_SIZE;
+  if (info.voxels > map->capacity) return SBM_ERR_OCC_FULL;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  StageClock& clk = h->occ.clock;
+  HIPCHK(h, occ_clock_start(h, kOccLoad, kOccLoad));
+  const size_t count = leaves.size();
+  if (!count) {                           // size 0: clear() and nothing else
+    st = occ_clear(map);
+    if (st == SBM_OK && sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+    return st;
+  }
+  std::vector<unsigned> first;
+  try {
+    first.resize(count);
+  } catch (const std::bad_alloc&) {
+    return SBM_ERR_NOMEM;
+  }
+  uint64_t run = 0;
+  for (size_t i = 0; i < count; i++) {
+    first[i] = (unsigned)run;             // below the capacity, which is at most 2^30
+    run += (uint64_t)1 << (3 * (16 - occ_bt_depth(leaves[i])));
+  }
+  st = occ_logodds_alloc(map);
+  if (st != SBM_OK) return st;
+  const size_t wb = occ_pad(count * 8);
+  HIPCHK(h, h->occ.io.grow(wb + count * 4, h->stream));
+  unsigned long long* d_word = h->occ.io.as<unsigned long long>();
+  unsigned* d_first = (unsigned*)(h->occ.io.as<char>() + wb);
+  HIPCHK(h, hipMemcpyAsync(d_word, leaves.data(), count * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_first, first.data(), count * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));   // the host arrays end with this call
+  OccLoad g;
+  g.leaves = (uint32_t)count;
+  g.total = (uint32_t)info.voxels;
+  g.mask = map->slots - 1;
+  g.max_probe = std::min(map->slots, kOccMaxProbe);
+  const float cmin = occ_logodds(p->clamp_min), cmax = occ_logodds(p->clamp_max);
+  memcpy(&g.vmin, &cmin, 4);
+  memcpy(&g.vmax, &cmax, 4);
+  HIPCHK(h, clk.mark(kOccBegin, h->stream));
+  st = occ_clear(map);
+  if (st != SBM_OK) return st;
+  map->mode = kOccModeLogOdds;
+  hipLaunchKernelGGL(occ_load_kernel, dim3((g.total + 255) / 256), dim3(256), 0, h->stream, d_word, d_first, g,
+                     map->keys.as<unsigned long long>(), map->hits.as<unsigned>(), map->ctr.as<OccCounters>());
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, clk.mark(kOccEnd, h->stream));
+  HIPCHK(h, clk.add(kOccLoad, kOccBegin, kOccEnd));
+  return occ_rays_end(map, sync);
+}
+
 static int occ_tree_depth_check(int depth) { return depth < 0 || depth > kOccDepth ? SBM_ERR_SIZE : SBM_OK; }
 
 }  // namespace sbm
@@ -1967,6 +2254,57 @@ int sbm_occ_cast_view_device(sbm_occ_map* map, int width, int height, int scale,
   return occ_query_run(map, kOccCast, true, sync, [&] {
     hipLaunchKernelGGL(occ_cast_view_kernel, dim3(blocks), dim3(256), 0, h->stream, v, *model, t, g, (int*)d_status, (float*)d_end);
   });
+}
+
+// ---- loading a .bt stream ---------------------------------------------------------------------------------------------------
+int sbm_occ_binary_info(const void* bytes, size_t n, sbm_occ_binary_header* out) {
+  if (!out || (n > 0 && !bytes)) return SBM_ERR_NULL;
+  return occ_bt_parse((const uint8_t*)bytes, n, out, nullptr);
+}
+
+int sbm_occ_binary_leaves(const void* bytes, size_t n, uint64_t* first_key, int32_t* depth, uint8_t* occupied, size_t cap, size_t* count) {
+  if (!count || (n > 0 && !bytes) || (cap > 0 && (!first_key || !depth || !occupied))) return SBM_ERR_NULL;
+  std::vector<OccBtLeaf> leaves;
+  const int st = occ_bt_parse((const uint8_t*)bytes, n, nullptr, &leaves);
+  if (st != SBM_OK) return st;
+  *count = leaves.size();
+  if (leaves.size() > cap) return SBM_ERR_SIZE;
+  for (size_t i = 0; i < leaves.size(); i++) {
+    const uint64_t c = occ_bt_code(leaves[i]);
+    first_key[i] = (uint64_t)occ_unspread(c) << 32 | (uint64_t)occ_unspread(c >> 1) << 16 | occ_unspread(c >> 2);
+    depth[i] = occ_bt_depth(leaves[i]);
+    occupied[i] = (uint8_t)(leaves[i] & 1);
+  }
+  return SBM_OK;
+}
+
+int sbm_occ_load_binary(sbm_occ_map* map, const void* bytes, size_t n, const sbm_occ_ray_params* params, int sync) {
+  if (!map || !params || (n > 0 && !bytes)) return SBM_ERR_NULL;
+  const int st = occ_ray_params_check(params);
+  if (st != SBM_OK) return st;
+  return occ_load_run(map, (const uint8_t*)bytes, n, params, sync);
+}
+
+int sbm_occ_read_binary(sbm_occ_map* map, const char* path, const sbm_occ_ray_params* params, int sync) {
+  if (!map || !path || !params) return SBM_ERR_NULL;
+  const int st = occ_ray_params_check(params);
+  if (st != SBM_OK) return st;
+  FILE* f = fopen(path, "rb");
+  if (!f) return SBM_ERR_UNSUPPORTED;
+  std::vector<uint8_t> data;
+  bool ok = true;
+  try {
+    uint8_t chunk[1 << 16];
+    size_t got;
+    while ((got = fread(chunk, 1, sizeof(chunk), f)) > 0) data.insert(data.end(), chunk, chunk + got);
+    ok = !ferror(f);
+  } catch (const std::bad_alloc&) {
+    fclose(f);
+    return SBM_ERR_NOMEM;
+  }
+  fclose(f);
+  if (!ok) return SBM_ERR_UNSUPPORTED;
+  return occ_load_run(map, data.data(), data.size(), params, sync);
 }
 
 // ---- the octree above the voxels ----------------------------------------------------------------------------------------
