@@ -1,7 +1,7 @@
-"""The GPU .bt loader (u96-slam_amd/csrc/sbm_occupancy.hip: the host parser and occ_load_kernel) against what the reference's own
-octomap read from the same streams (tests/golden/occupancy_load.npz) and, for key sets the fixture does not hold, against this
-library's own writers. Everything is compared for exact equality: sorted keys, the bits of the floats, and the bytes of the
-streams written back."""
+"""The GPU .bt loader (u96-slam_amd/csrc/sbm_occ_bt.hip: the host parser; sbm_occ_load.hip: occ_load_kernel) against what
+the reference's own octomap read from the same streams (tests/golden/occupancy_load.npz) and, for key sets the fixture does
+not hold, against this library's own writers. Everything is compared for exact equality: sorted keys, the bits of the floats,
+and the bytes of the streams written back."""
 import ctypes
 import pathlib
 import subprocess

@@ -1,4 +1,4 @@
-"""The GPU occupancy map's queries (u96-slam_amd/csrc/sbm_occupancy.hip: occ_search_kernel, occ_cast_rays_kernel,
+"""The GPU occupancy map's queries (u96-slam_amd/csrc/sbm_occ_query.hip: occ_search_kernel, occ_cast_rays_kernel,
 occ_cast_view_kernel) against what the reference's own octomap answered for search and castRay
 (tests/golden/occupancy_query.npz) and, for shapes the fixture does not hold, against the transcription
 tests/occupancy_query_cases.py, which tests/test_occupancy_query_restatement.py pins to the same fixture. Every map is built

@@ -1,4 +1,4 @@
-"""The GPU occupancy map's log-odds mode (u96-slam_amd/csrc/sbm_occupancy.hip: occ_rays_*_kernel) against what the reference's own
+"""The GPU occupancy map's log-odds mode (u96-slam_amd/csrc/sbm_occ_rays.hip: occ_rays_*_kernel) against what the reference's own
 octomap answered for insertPointCloud (tests/golden/occupancy_rays.npz) and, for shapes the fixture does not hold, against the
 restatement tests/occupancy_ray_cases.py, which tests/test_occupancy_rays_restatement.py pins to the same fixture. Everything is
 compared for exact equality: sorted keys and the bits of the float log-odds."""

@@ -1,4 +1,4 @@
-"""The GPU occupancy tree (u96-slam_amd/csrc/sbm_occupancy.hip: occ_tree_*_kernel) against what the reference's own octomap
+"""The GPU occupancy tree (u96-slam_amd/csrc/sbm_occ_tree.hip: occ_tree_*_kernel) against what the reference's own octomap
 holds above the voxels (tests/golden/occupancy_tree.npz), against the .bt streams octomap wrote for the earlier fixtures, and,
 for shapes the fixtures do not hold, against the transcription tests/occupancy_tree_cases.py, which
 tests/test_occupancy_tree_restatement.py pins to the same fixtures. Every map is built through the existing inserts and its

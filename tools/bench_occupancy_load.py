@@ -28,7 +28,7 @@ from another machine.
 The expansion's two leaf searches: the library searches the prefix array per lane. A second library whose wavefronts share the
 search (lane 0 finds its leaf, lane l looks at most l leaves on) is built by hand,
 
-    hipcc <the Makefile's HIPFLAGS> -ffp-contract=off -DSBM_OCC_LOAD_SHARED=1 -c u96-slam_amd/csrc/sbm_occupancy.hip -o occ_shared.o
+    hipcc <the Makefile's HIPFLAGS> -ffp-contract=off -DSBM_OCC_LOAD_SHARED=1 -c u96-slam_amd/csrc/sbm_occ_load.hip -o occ_shared.o
     hipcc --offload-arch=gfx950 --offload-compress -shared -fPIC -o u96-slam_amd/lib/libsbm_hip_occ_load_shared.so occ_shared.o <the other objects>
 
 and where it exists this tool times every map with it too, in a child process (SBM_LIB_AB), and checks that both load the same

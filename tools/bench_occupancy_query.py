@@ -16,7 +16,7 @@ of the machine that made the fixture) on the 160 x 120 view of this scene, read 
 The view kernel's two lane orders: the library maps a wavefront to an 8 x 8 pixel tile. A second library with the row order (64
 consecutive pixels of a row per wavefront) is built by hand,
 
-    hipcc <the Makefile's HIPFLAGS> -ffp-contract=off -DSBM_OCC_VIEW_TILED=0 -c u96-slam_amd/csrc/sbm_occupancy.hip -o occ_rows.o
+    hipcc <the Makefile's HIPFLAGS> -ffp-contract=off -DSBM_OCC_VIEW_TILED=0 -c u96-slam_amd/csrc/sbm_occ_query.hip -o occ_rows.o
     hipcc --offload-arch=gfx950 --offload-compress -shared -fPIC -o u96-slam_amd/lib/libsbm_hip_occ_rows.so occ_rows.o <the other objects>
 
 and where it exists this tool times the view with it too, in a child process (SBM_LIB_AB), and checks that both orders answer

@@ -1,12 +1,11 @@
 // Stand-alone host check of the .bt parser (sbm_occ_binary_info, sbm_occ_binary_leaves) under AddressSanitizer and
 // UndefinedBehaviorSanitizer: every truncation of each stream given, and every byte of it set to 0x00, 0xFF, 0x03, 0x55 and 0xAA
 // (every seventh byte for a stream above 4000 bytes), each from an exact-size heap copy so that a read past the end is seen.
-// Built and run by hand on the host, with its own instrumented copy of the parser and the library for everything else; it
-// never touches a GPU:
+// Built and run by hand on the host: the parser's file is host C++ (no HIP header, no HIP call), so the tool and that one file are
+// the whole program, under any C++17 compiler; it never touches a GPU:
 //
-//     hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined \
-//           -Xarch_host -fno-sanitize-recover=undefined -I include -I u96-slam_amd/csrc u96-slam_amd/csrc/sbm_occupancy.hip \
-//           tools/occupancy_load_sanitize.cpp -L u96-slam_amd/lib -lsbm_hip -Wl,-rpath,$PWD/u96-slam_amd/lib -o occ_load_san
+//     c++ -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -I include \
+//         u96-slam_amd/csrc/sbm_occ_bt.hip tools/occupancy_load_sanitize.cpp -o occ_load_san
 //     ASAN_OPTIONS=detect_leaks=0 ./occ_load_san a.bt b.bt ...
 //
 // Prints the number of calls and how many streams were accepted; a finding ends the run with the sanitizer's report.

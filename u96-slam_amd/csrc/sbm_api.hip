@@ -1,6 +1,6 @@
 // sbm_api.hip -- C-ABI of libsbm_hip.so (declared in include/sbm.h): parameters, the handle's life and its pool, the block
 // matcher on device buffers, profiling and debug dispatch, and the thin rectify / prefilter / consumer entry points. The other
-// families' entry points sit with their kernels (sbm_fpga, sbm_sgbm, sbm_gftt, sbm_gftt_select, sbm_orb, sbm_match, sbm_pnp, sbm_lk, sbm_occupancy); the block
+// families' entry points sit with their kernels (sbm_fpga, sbm_sgbm, sbm_gftt, sbm_gftt_select, sbm_orb, sbm_match, sbm_pnp, sbm_lk, sbm_occupancy and sbm_occ_*); the block
 // matcher's host-buffer paths are in sbm_host.hip. Replaces cv::StereoBM::compute at src/slam/src/core/main.cpp:201-216.
 //
 // Stage order (same as cv::StereoBM::compute): prefilter both images -> SAD/WTA on the valid-ROI rows

@@ -1,5 +1,5 @@
 // sbm_consume_math.h -- the reference's per-point arithmetic that the consumers of the disparity map share (sbm_consume.hip,
-// sbm_occupancy.hip): projectDisparityTo3D, isFinite and transformPoint (Stereo.cpp:157-199). Internal, gfx950 only.
+// the occupancy family through sbm_occ.h): projectDisparityTo3D, isFinite and transformPoint (Stereo.cpp:157-199). Internal, gfx950 only.
 // Types per operation as in the C++ source, and never a contracted multiply-add: the including files are built with
 // -ffp-contract=off or carry the pragma, and the functions below carry it too.
 #pragma once

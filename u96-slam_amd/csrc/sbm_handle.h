@@ -248,7 +248,7 @@ struct sbm_handle {
     template <class F> void each(F f) { f(pyr); f(deriv); f(io); }
   } lk;
   struct {   // occupancy maps made from this handle: the radix sort's second key / count arrays and its digit counts; the host
-             // forms' staging (planes in, keys and counts out). The tables themselves belong to each sbm_occ_map.
+             // forms' staging (planes in, keys and counts out). The tables themselves belong to each sbm_occ_map (sbm_occ.h).
     sbm::DevBuf sort, hist, io;
     sbm::StageClock clock;
     template <class F> void each(F f) { f(sort); f(hist); f(io); }

@@ -1,0 +1,258 @@
+// sbm_occ.h -- what more than one file of the occupancy family (sbm_occupancy.hip, sbm_occ_*.hip) needs, each thing once. Internal.
+// The first part is plain C++, for the host-only sbm_occ_bt.hip; the rest needs HIP (gfx950 only). Nothing here contracts a
+// multiply-add: every helper with float or double steps carries the pragma.
+#pragma once
+#include <stdint.h>
+#include <vector>
+
+#include "../../include/sbm.h"
+#ifdef __HIP__
+#include <algorithm>
+#include <new>
+#include "sbm_consume_math.h"
+#include "sbm_handle.h"
+#define SBM_OCC_HD __host__ __device__ __forceinline__
+#else
+#define SBM_OCC_HD inline
+#endif
+
+namespace sbm {
+// every third bit of a 16-bit key; unspread is its inverse
+SBM_OCC_HD unsigned long long occ_spread(unsigned long long x) {
+  x &= 0xFFFFull;
+  x = (x | x << 32) & 0x001F00000000FFFFull;
+  x = (x | x << 16) & 0x001F0000FF0000FFull;
+  x = (x | x << 8) & 0x100F00F00F00F00Full;
+  x = (x | x << 4) & 0x10C30C30C30C30C3ull;
+  x = (x | x << 2) & 0x1249249249249249ull;
+  return x;
+}
+SBM_OCC_HD unsigned occ_unspread(unsigned long long x) {
+  x &= 0x1249249249249249ull;
+  x = (x ^ x >> 2) & 0x10C30C30C30C30C3ull;
+  x = (x ^ x >> 4) & 0x100F00F00F00F00Full;
+  x = (x ^ x >> 8) & 0x001F0000FF0000FFull;
+  x = (x ^ x >> 16) & 0x001F00000000FFFFull;
+  x = (x ^ x >> 32) & 0xFFFFull;
+  return (unsigned)x;
+}
+
+SBM_OCC_HD unsigned long long occ_pack(unsigned k0, unsigned k1, unsigned k2) {
+  return (unsigned long long)k0 << 32 | (unsigned long long)k1 << 16 | k2;   // a packed key
+}
+// its Morton code, computeChildIdx from the top bit down: x in bit 0, y in bit 1, z in bit 2 of every triple; and the key of a code
+SBM_OCC_HD unsigned long long occ_code(unsigned k0, unsigned k1, unsigned k2) {
+  return occ_spread(k0) | occ_spread(k1) << 1 | occ_spread(k2) << 2;
+}
+SBM_OCC_HD unsigned long long occ_key_of_code(unsigned long long code) {
+  return occ_pack(occ_unspread(code), occ_unspread(code >> 1), occ_unspread(code >> 2));
+}
+
+// A leaf as the .bt parser hands it on and the device takes it: first Morton code of the cube << 8 | depth << 1 | occupied
+typedef unsigned long long OccBtLeaf;
+inline uint64_t occ_bt_code(OccBtLeaf l) { return l >> 8; }
+inline int occ_bt_depth(OccBtLeaf l) { return (int)(l >> 1 & 31); }
+#pragma GCC visibility push(hidden)   // sbm_occ_bt.hip: the parser (leaves in stream order) and the file of a written body
+int occ_bt_parse(const uint8_t* b, size_t n, sbm_occ_binary_header* info, std::vector<OccBtLeaf>* leaves, bool bounds = true);
+int occ_write_file(const std::vector<uint8_t>& body, size_t nodes, double resolution, const char* path);
+#pragma GCC visibility pop
+
+#ifdef __HIP__
+constexpr unsigned long long kOccEmpty = ~0ull;
+constexpr uint32_t kOccMaxProbe = 1024;
+constexpr int kOccTile = 1024;       // keys per workgroup of a radix pass, children per workgroup of a tree level
+constexpr int kOccDepth = 16;
+enum { kOccModeNone, kOccModeHits, kOccModeLogOdds };
+constexpr int kOccMaxSteps = 3 * 65536;   // of one ray: each step moves one key by one on one axis
+constexpr unsigned kOccFree = 1, kOccOccupied = 2;   // flag word of a slot within one scan
+constexpr unsigned kOccCollapsed = 1u << 8;   // info word of a tree node: bits 0-7 child mask, bit 8 collapsed,
+constexpr int kOccTopShift = 10;              // bits 10-14 the depth of the shallowest collapsed node at or above it, or
+constexpr unsigned kOccNoTop = 31;            // kOccNoTop
+constexpr unsigned kOccInnerTag = 1u << 31;   // payload of a selected node: its index among the leaves, or tag | index above them
+
+struct OccCounters {
+  unsigned long long overflow;   // points (log-odds mode: cells) that found the table full
+  unsigned size;                 // occupied slots
+  unsigned cursor;               // compaction cursor of a fetch
+  unsigned touched[2];           // log-odds mode: slots the running scan has touched, in [scan & 1]; the other is zero
+};
+struct OccPose { float t[12]; };     // one plane's pose; the cloud form passes its origin in t[3], t[7], t[11]
+struct OccGeom {                     // the planes of an insert
+  int W, H, scale;
+  float range_max_sqrd;          // range_max * range_max, formed in float on the host as main.cpp:501 does
+  double factor;                 // 1. / resolution
+  uint32_t mask, max_probe;
+};
+struct OccTreeStats {
+  unsigned long long diverge[kOccDepth + 1];                            // voxels by the depth at which they leave their left neighbour
+  unsigned long long nodes_at[kOccDepth + 1], leaves_at[kOccDepth + 1]; // of the pruned tree
+  unsigned kmin[3], kmax[3];
+  unsigned cursor, pad;                                                 // compaction cursor of a leaves call
+};
+struct OccLevel {                 // one depth of a built tree
+  unsigned long long* code;       // Morton prefixes (3 bits per depth), ascending
+  unsigned* val;                  // float bits: the maximum over the voxels below
+  unsigned* parent;               // index in the level above
+  unsigned* info;
+  unsigned *first, *inner, *rank; // above depth 16: the first child's index in the level below, the non-leaf nodes of the pruned
+                                  // tree in the subtree (this one included), the pre-order rank among them
+  uint32_t n;
+};
+
+// Stage times: the family's calls share the clock's marks, and each keeps the other stages' last times (occ_clock_start).
+enum OccStage { kOccInsert, kOccFetch, kOccRaysMark, kOccRaysApply, kOccSearch, kOccCast, kOccTreeBuild, kOccTreeQuery, kOccLoad, kOccStageCount };
+enum OccMark { kOccBegin, kOccEnd, kOccMid, kOccMarkCount };
+
+__device__ __forceinline__ uint32_t occ_hash(unsigned long long key, uint32_t mask) {
+  return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32) & mask;
+}
+// OcTreeBaseImpl.hxx:310-321 on one axis: floor in double, then 0 <= floor + 32768 < 65536. NaN fails both comparisons, and so
+// does every value whose floor fits no int (the reference's cast gives INT_MIN there, which its range test rejects).
+__device__ __forceinline__ bool occ_axis(double factor, float coord, unsigned* k) {
+#pragma clang fp contract(off)
+  const double f = floor(factor * (double)coord);
+  if (!(f >= -32768.0 && f < 32768.0)) return false;
+  *k = (unsigned)((int)f + 32768);
+  return true;
+}
+__device__ __forceinline__ float occ_key_coord(unsigned key, double resolution) {   // keyToCoord, then point3d's float
+#pragma clang fp contract(off)
+  return (float)(((double)((int)key - 32768) + 0.5) * resolution);
+}
+// main.cpp:529-539 on pixel i of a plane: false where the reference skips the pixel, else the point after both transforms
+__device__ __forceinline__ bool occ_world_point(const int16_t* __restrict__ plane, int i, const OccGeom& g, const sbm_stereo_model& m,
+                                                const float* pose, Pt3* out) {
+#pragma clang fp contract(off)
+  const int r = i / g.W, c = i % g.W;
+  const float d = (float)plane[i] / 16.0f;       // main.cpp:529
+  if (!(d > 0)) return false;
+  Pt3 p = project_disparity((float)(c * g.scale), (float)(r * g.scale), d, m);
+  if (!finite3(p)) return false;
+  if (m.has_local) p = transform_point(p, m.local);
+  *out = transform_point(p, pose);
+  return true;
+}
+
+// One axis of a 3-D DDA's initialisation. The one difference between its two sources: the border's half cell is rounded to
+// float before it is added (kHalfInFloat: computeRayKeys) or added in double (castRay).
+template <bool kHalfInFloat>
+__device__ __forceinline__ void occ_dda_axis(float dir, unsigned key, float origin, double resolution, int* step, double* tmax,
+                                             double* tdelta) {
+#pragma clang fp contract(off)
+  *step = dir > 0.0f ? 1 : dir < 0.0f ? -1 : 0;
+  *tmax = *tdelta = 1.7976931348623157e308;   // std::numeric_limits<double>::max()
+  if (*step) {
+    double border = ((double)((int)key - 32768) + 0.5) * resolution;   // keyToCoord
+    if (kHalfInFloat) border += (double)(float)((double)*step * resolution * 0.5);
+    else border += (double)*step * resolution * 0.5;
+    *tmax = (border - (double)origin) / (double)dir;
+    *tdelta = resolution / fabs((double)dir);
+  }
+}
+
+// Finds the key's slot or claims an empty one: a walk of at most max_probe slots from the key's hash, a relaxed load of each, a
+// 64-bit compare-and-swap on an empty one. false: no slot. It counts nothing: a caller told `claimed` owes OccCounters::size one.
+__device__ __forceinline__ bool occ_find_or_claim(unsigned long long* keys, unsigned long long key, uint32_t mask, uint32_t max_probe,
+                                                  uint32_t* at, bool* claimed) {
+  uint32_t slot = occ_hash(key, mask);
+  for (uint32_t probe = 0; probe < max_probe; probe++, slot = (slot + 1) & mask) {
+    unsigned long long cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == kOccEmpty) {
+      cur = atomicCAS(&keys[slot], kOccEmpty, key);
+      if (cur == kOccEmpty) {
+        *claimed = true;
+        cur = key;
+      }
+    }
+    if (cur == key) {
+      *at = slot;
+      return true;
+    }
+  }
+  return false;
+}
+
+// The wavefront's append to a list: one atomic add on the list's counter for all the lanes with `take`, each of which gets its
+// index (the others' means nothing). EVERY lane of the wavefront has to reach this call: it ballots and reads a lane.
+__device__ __forceinline__ unsigned occ_wave_append(bool take, unsigned* counter) {
+  const unsigned long long taking = __ballot(take);
+  if (!taking) return 0;
+  const int lane = threadIdx.x & 63;
+  const int leader = __ffsll((long long)taking) - 1;
+  unsigned base = 0;
+  if (lane == leader) base = atomicAdd(counter, (unsigned)__popcll(taking));
+  base = __builtin_amdgcn_readlane(base, leader);
+  return base + __popcll(taking & ((1ull << lane) - 1));
+}
+
+inline size_t occ_pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }   // arrays that share a buffer begin 256-aligned
+#pragma GCC visibility push(hidden)   // host functions that cross files (these: sbm_occupancy.hip). Hidden, as the two above and
+// unlike the rest of the project's, so that the family's internal names stay out of what the library exports
+int occ_read_counters(sbm_occ_map* map, OccCounters* c);
+int occ_clear(sbm_occ_map* map);
+void occ_probe(const sbm_occ_map* map, uint32_t* mask, uint32_t* max_probe);   // of a walk over the table's slots
+int occ_check_insert(const sbm_occ_map* map, int n, const void* disp, int width, int height, int scale, const sbm_stereo_model* model,
+                     const float* poses);
+hipError_t occ_clock_start(sbm_handle* h, int a, int b);   // a call begins that times stages a and b (the same for one)
+int occ_overflow_status(sbm_occ_map* map, int sync);       // what a call that wrote the table returns
+// The map's n occupied slots -> dense (key, word) arrays in no order
+int occ_compact_run(sbm_occ_map* map, uint32_t n, unsigned long long* d_keys, unsigned* d_vals);
+// LSD radix sort of n (48-bit key, 32-bit payload) pairs, 8 bits per pass: from kk[0] / vv[0] through kk[1] / vv[1], and the
+// even number of passes ends in kk[0] / vv[0]. hist: 256 counts per tile of kOccTile keys.
+int occ_sort_run(sbm_handle* h, unsigned long long* const kk[2], unsigned* const vv[2], uint32_t n, unsigned* hist);
+float occ_logodds(double p);   // these three are in sbm_occ_rays.hip
+int occ_ray_params_check(const sbm_occ_ray_params* p);
+int occ_logodds_alloc(sbm_occ_map* map);   // what the log-odds mode keeps beside the table
+#pragma GCC visibility pop
+
+// Times `stage` of a query around `launch` (-> status; the error of its last launch is looked at here). A query changes nothing
+// and reports no overflow, so with sync it only waits for the stream.
+template <class Launch> int occ_timed_run(sbm_handle* h, int stage, bool any, int sync, Launch launch) {
+  StageClock& clk = h->occ.clock;
+  HIPCHK(h, occ_clock_start(h, stage, stage));
+  if (any) {
+    HIPCHK(h, clk.mark(kOccBegin, h->stream));
+    const int st = launch();
+    if (st != SBM_OK) return st;
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, clk.mark(kOccEnd, h->stream));
+    HIPCHK(h, clk.add(stage, kOccBegin, kOccEnd));
+  }
+  if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+#endif  // __HIP__
+
+}  // namespace sbm
+
+#ifdef __HIP__
+struct sbm_occ_map {
+  sbm_handle* h;
+  sbm_occ_params p;
+  size_t capacity;           // voxels the caller asked for
+  uint32_t slots;            // power of two >= 2 * capacity
+  unsigned scan;             // log-odds mode: scans applied since the last clear
+  int mode;                  // fixed by the first insert after create or reset: kOccModeNone, kOccModeHits, kOccModeLogOdds
+  sbm::DevBuf keys, hits;    // the table; in the log-odds mode a slot's `hits` word is its float log-odds
+  sbm::DevBuf ctr;           // OccCounters
+  sbm::DevBuf flags, touched;   // log-odds mode only, from its first insert: per slot the flag word of the running scan, and the
+                                // slots that scan touched (4 B per slot each)
+  template <class F> void each(F f) { f(keys); f(hits); f(ctr); f(flags); f(touched); }
+};
+
+struct sbm_occ_tree {
+  sbm_handle* h;
+  sbm_occ_map* map;            // read by a build only
+  bool built, have_stats;      // levels are valid; `host` holds the last build's counts
+  int reading;
+  double resolution;
+  unsigned cmax;               // float bits of clamp max, what .bt calls occupied
+  uint32_t count[17];          // nodes per depth, pruned or not; count[16] is the voxels
+  size_t off[16], inner_total; // where depth d begins among the nodes above the leaves, and how many those are
+  sbm::OccTreeStats host;
+  sbm::DevBuf leaf, node;      // depth 16: code, value, parent, info (20 B per voxel); above: code, value, parent, info, first
+                               // child, subtree count, rank (32 B per node)
+  sbm::DevBuf stats, tiles;    // OccTreeStats; head counts per tile of the level being built
+  template <class F> void each(F f) { f(leaf); f(node); f(stats); f(tiles); }
+};
+#endif
