@@ -40,7 +40,10 @@
  * Device scratch per pixel of a call (n * W * H), held by the handle until the size changes: ~4 B (prefiltered planes with their
  * padding + the pre-check map), + 4 B with the LR check on (cost plane), + 8 B more when that check meets rows wider than 8192
  * columns (its claim table), + 16 * (W + 288) / W + ~2 B with the speckle filter on (run records, seam lists), + 4 B for
- * PREFILTER_NORMALIZED_RESPONSE. Every pixel of a host-memory call adds 4 B of staging.
+ * PREFILTER_NORMALIZED_RESPONSE. Every pixel of a host-memory call adds 4 B of staging. The interior SAD kernel of a batch that
+ * fills the chip more than once hands its vertical sums from one row segment to the next through scratch as well: per pair,
+ * column strip and row segment behind the first, 4 * numDisparities + 256 B (+ 8 B of flags) -- 16.25 KB at 128 disparities, 138 MB
+ * for 64 KITTI pairs (19 strips, 8 segments); a call whose slots would exceed 1 GiB recomputes the sums instead.
  *
  * The hand-tuned kernels accumulate in place with v_mqsad_pk_u16_u8 (vdst == src2), which the hardware does right and the
  * compiler's register model forbids; a device self-test (once per device and process, on the stream of the first call that would
@@ -52,7 +55,7 @@
  * returns SBM_ERR_HIP (SBM_ERR_NOMEM if its 8-byte allocation fails) with the error in sbm_last_hip_error(), nothing is
  * remembered, and the next call runs the self-test again.
  *
- * Environment. The library reads these nine variables (nothing else); an integrator never needs to set any of them:
+ * Environment. The library reads these ten variables (nothing else); an integrator never needs to set any of them:
  *   variable            default  read      who sets it, and what for
  *   SBM_FAST_INPLACE    1        once      0 = run the sliding-sum SAD kernel instead of the interior one (the fallback that
  *                                          is taken automatically when the device self-test of the in-place v_mqsad
@@ -60,6 +63,10 @@
  *   SBM_FAST_PFSHIFT    2        once      0 = unscaled prefiltered planes (plain winner search), 1 = at most one tag bit;
  *                                          GPU tests
  *   SBM_FAST_CS3        1        per call  0 = plain column strips only (no column-stride-3 strips); GPU tests
+ *   SBM_FAST_HANDOFF    1        per call  0 = every row segment of the interior SAD kernel recomputes its vertical sums from w - 1
+ *                                          priming rows; 1 = a segment takes the sums its predecessor left, where they are there
+ *                                          when it starts (same results either way); 2 = the segments are launches of their own,
+ *                                          so that every hand-off is taken; GPU tests / A-B measurements
  *   SBM_SPECKLE_LISTS   1        per call  0 = the speckle filter's row-walking kernels (one wavefront per row, per-pixel labels)
  *                                          instead of the band walk + run records; GPU tests
  *   SBM_SPECKLE_BAND    auto     per call  2 / 4 = band height of the speckle filter's band walk, 0 = row-walking kernels;

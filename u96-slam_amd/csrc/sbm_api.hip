@@ -348,7 +348,9 @@ void sbm::bm_plan_launches(const sbm_params& p, bool inplace_ok, BmPlan* pl) {
 
 extern "C" {
 
-static int ensure_scratch(sbm_handle* h, int n, int W, int H, int pitch, bool need_cost, bool need_speckle) {
+// ho_bytes / ho_flags: sad_fast_handoff_bytes() of the call's plan (0: nothing is handed over)
+static int ensure_scratch(sbm_handle* h, int n, int W, int H, int pitch, bool need_cost, bool need_speckle, size_t ho_bytes,
+                          size_t ho_flags) {
   auto& s = h->bm;
   const bool fits = n <= s.n && W == s.W && H == s.H && pitch == s.pitch && s.pf_l.p;
   if (!fits) {
@@ -367,6 +369,17 @@ static int ensure_scratch(sbm_handle* h, int n, int W, int H, int pitch, bool ne
   if (need_cost) HIPCHK(h, s.cost.grow(npix * sizeof(int32_t), h->stream));
   HIPCHK(h, s.lr_keys.grow(lr_keys_bytes(s.n, W, H, need_cost), h->stream));
   if (need_speckle) HIPCHK(h, s.spk.ensure(s.n, W, H, h->stream));
+  if (ho_bytes) {
+    // The flag words in front of the slots must never hold a number a later launch will use: they are cleared when the buffer is
+    // new, when another plan moves the boundary between flags and slots, and when the launch counter wraps.
+    const bool fresh = ho_bytes > s.handoff.bytes;
+    HIPCHK(h, s.handoff.grow(ho_bytes, h->stream));
+    if (fresh || ho_flags != s.ho_flags || s.ho_epoch == 0xffffffffu) {
+      HIPCHK(h, hipMemsetAsync(s.handoff.p, 0, ho_flags, h->stream));
+      s.ho_flags = ho_flags;
+      s.ho_epoch = 0;
+    }
+  }
   return SBM_OK;
 }
 
@@ -411,9 +424,12 @@ int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_r
   if (pl.in_envelope) HIPCHK(h, mqsad_inplace_ok(h->stream, &inplace));
   bm_plan_launches(p, inplace, &pl);
   const Geom& g = pl.g;
-  const int st2 = ensure_scratch(h, n, width, height, g.pitch, g.want_cost, pl.speckle);
+  size_t ho_flags = 0;
+  const size_t ho_bytes = sad_fast_handoff_bytes(pl, &ho_flags);
+  const int st2 = ensure_scratch(h, n, width, height, g.pitch, g.want_cost, pl.speckle, ho_bytes, ho_flags);
   if (st2 != SBM_OK) return st2;
   h->last = g; h->have_last = true;
+  h->bm.ho_links = 0;
   if (pl.any_rows) snprintf(h->last_kernel, sizeof(h->last_kernel), "%s", pl.kernel);
 
   // Stages run one after the other on the main stream. Overlapping LR + speckle of one sub-batch with the SAD kernel of
@@ -440,7 +456,9 @@ int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_r
   }
   mark(h, kBmPrefiltered);
   if (pl.sad == kSadFast) {
-    HIPCHK(h, launch_sad_fast(pf_l, pf_r, disp_pre, cost, pl, h->stream));
+    h->bm.ho_slots = (size_t)(pl.f.nseg - 1) * g.n * pl.f.strips;
+    HIPCHK(h, launch_sad_fast(pf_l, pf_r, disp_pre, cost, pl, ho_bytes ? h->bm.handoff.p : nullptr, ho_bytes ? ++h->bm.ho_epoch : 0u,
+                              &h->bm.ho_links, h->stream));
     if (pl.wide_borders) {   // beyond 256 disparities: the clamped columns from the sliding-sum kernel
       HIPCHK(h, launch_sad_wide(pf_l, pf_r, disp_pre, cost, g, pl.wide_l[0], pl.wide_l[1], h->stream));
       HIPCHK(h, launch_sad_wide(pf_l, pf_r, disp_pre, cost, g, pl.wide_r[0], pl.wide_r[1], h->stream));
@@ -625,6 +643,25 @@ int sbm_debug_fetch(sbm_handle* h, int which, void* dst, size_t dst_bytes) {
         for (int x = 0; x < g.W; x++)
           if (!live || x < g.lofs || x >= g.lofs + g.xend) row[x] = (int16_t)g.filtered;
       }
+    return SBM_OK;
+  }
+  if (which == 7) {
+    // the hand-off of the interior kernel's vertical sums in the last call: int32 { (segment, pair, strip) that took their sums
+    // over, those that could have }
+    if (dst_bytes < 2 * sizeof(int32_t)) return SBM_ERR_SIZE;
+    int32_t* d = (int32_t*)dst;
+    d[0] = 0;
+    d[1] = (int32_t)h->bm.ho_links;
+    if (!h->bm.ho_links) return SBM_OK;
+    // [slots] ready words, [slots] taken words: a slot that was taken holds the call's number in its taken word
+    const size_t slots = h->bm.ho_slots;
+    uint32_t* tmp = (uint32_t*)malloc(slots * sizeof(uint32_t));
+    if (!tmp) return SBM_ERR_NOMEM;
+    const hipError_t e = hipMemcpy(tmp, h->bm.handoff.as<uint32_t>() + slots, slots * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess)
+      for (size_t i = 0; i < slots; i++) d[0] += tmp[i] == h->bm.ho_epoch;
+    free(tmp);
+    HIPCHK(h, e);
     return SBM_OK;
   }
   return SBM_ERR_UNSUPPORTED;

@@ -11,7 +11,7 @@ namespace sbm {
 
 // Environment switches of the library -- the complete list, documented for integrators in include/sbm.h ("Environment").
 // They select a tested fallback or a code path that the GPU tests compare with the default one: SBM_FAST_INPLACE (0: the
-// sliding-sum kernel in place of the interior one), SBM_FAST_PFSHIFT, SBM_FAST_CS3, SBM_SPECKLE_LISTS, SBM_SPECKLE_BAND,
+// sliding-sum kernel in place of the interior one), SBM_FAST_PFSHIFT, SBM_FAST_CS3, SBM_FAST_HANDOFF, SBM_SPECKLE_LISTS, SBM_SPECKLE_BAND,
 // SBM_SPECKLE_SEG, SBM_HOST_ZEROCOPY, SBM_WIDE, SBM_CV_READING.
 inline int env_switch(const char* name, int dflt) {
   const char* e = getenv(name);
@@ -135,7 +135,12 @@ int sad_fast_pfshift(const Geom& g);   // 2 or 1 when the interior kernel wants 
 void sad_fast_plan(BmPlan* pl);
 // The planned launch. With pl.border the w/2 clamped columns on each side of [xc0,xc1) are computed by extra wavefronts of the
 // same launch (sbm_sad_border_wave.h); without it the launch leaves them untouched.
-hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* disp, int32_t* cost, BmPlan& pl, hipStream_t s);
+// handoff / epoch / links: the scratch through which a row segment leaves its vertical sums to the next one (sad_fast_handoff_bytes()
+// of it, the first *flag_bytes zero or written by earlier launches with smaller epochs; 0 bytes: this call hands nothing over),
+// this launch's number, and how many (segment, pair, strip) may take their sums over.
+size_t sad_fast_handoff_bytes(const BmPlan& pl, size_t* flag_bytes);
+hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* disp, int32_t* cost, BmPlan& pl, void* handoff,
+                           unsigned epoch, long* links, hipStream_t s);
 
 // Left-right consistency (cv validateDisparity) + invalid rows/columns fill. Reads disp_pre/cost, writes disp_out.
 // Rows wider than kLrLdsCols keep their claim table in global memory: keys = n * H * W 64-bit words (lr_keys_bytes; null

@@ -150,9 +150,14 @@ struct sbm_handle {
     sbm::DevBuf cost;         // allocated once the LR check is on
     sbm::DevBuf lr_keys;      // claim table of the LR check for rows wider than kLrLdsCols (lr_keys_bytes)
     sbm::DevBuf vsum;         // column sums of PREFILTER_NORMALIZED_RESPONSE (2 * n * W * H uint16), allocated on first use
+    sbm::DevBuf handoff;      // vertical sums between the interior kernel's row segments (sad_fast_handoff_bytes), on first use
+    size_t ho_flags;          // bytes at its start that hold ready / taken words: zero, or epochs of earlier launches
+    unsigned ho_epoch;        // number of the last interior launch that used it
+    size_t ho_slots;          // slots of the last call: (row segments - 1) * pairs * strips
+    long ho_links;            // (segment, pair, strip) that could take their sums over in the last call, for sbm_debug_fetch(7)
     sbm::SpeckleScratch spk;
     sbm::StageClock clock;    // stage times only: the marks are the handle's ring below (bm_stages() has no marks of its own)
-    template <class F> void each(F f) { f(pf_l); f(pf_r); f(disp_pre); f(cost); f(lr_keys); f(vsum); spk.each(f); }
+    template <class F> void each(F f) { f(pf_l); f(pf_r); f(disp_pre); f(cost); f(lr_keys); f(vsum); f(handoff); spk.each(f); }
   } bm;
   struct {   // FPGA-flavour matcher, sized for n pairs of W x H
     int n, W, H;

@@ -158,6 +158,46 @@ static hipError_t sad_fast_dispatch(BmPlan& pl, const FastArgs* a, hipStream_t s
   }
 }
 
+// SBM_FAST_HANDOFF, read per call (the GPU tests flip it): 1 (default) a row segment takes the vertical sums its predecessor
+// left, if they are there when it starts; 0 every segment primes; 2 the segments go out as launches of their own, top to bottom,
+// so that every hand-off is taken (for the tests of that path: it costs nseg launches).
+static int fast_handoff_mode() { return std::max(0, std::min(2, env_switch("SBM_FAST_HANDOFF", 1))); }
+
+// workgroups of a lone wavefront (up to 128 disparities) that the chip holds at once
+static int fast_slots(int nd) { return nd <= 64 ? 4096 : 3072; }
+
+// step of the first round's lengths (sad_fast_plan), as a share of a regular segment
+constexpr double kFirstRoundStep = 0.10, kFirstRoundSpan = 0.40;
+
+// Dispatch order of the row segments: at[p] = the segment whose per_seg workgroups (one per pair and strip) are dispatch
+// position p of the grid, behind the border jobs. Returns the stride D of the order, nseg where it is the identity.
+//
+// Segment k + 1 finds the sums of segment k only if k has FINISHED when k + 1 is dispatched, and nothing may wait. Workgroups
+// start in id order, each as a slot of the chip frees up: id j starts when j - slots + 1 workgroups have finished. With the
+// segments in their natural order k + 1 lies per_seg ids behind k -- KITTI x 64: 1 216 chains per segment set against 3 072 slots
+// -- so both run in the same round and no hand-off is ever taken. Put them D positions apart instead, D * per_seg >= slots + per_seg:
+// position p + D then starts only when (p + 1) * per_seg workgroups have finished, and those are the sets of the positions 0 .. p as
+// long as the sets finish in dispatch order -- a whole set's worth of finished workgroups lies between the predecessor's last one
+// and the successor's first, so jitter inside a set does not matter. (One position less, D * per_seg >= slots, makes the
+// successors start on the slots their own predecessors' set frees: a coin toss for the first of them.) Sets finish in dispatch
+// order once the launch is past its first round; the first round's sets all start together, which is why sad_fast_plan gives
+// them increasing lengths.
+// So D = ceil(slots / per_seg) + 1, the positions p, p + D, p + 2 D, ... hold consecutive segments (a chain), and the chains follow
+// each other: KITTI x 64, 8 segments, D = 4: positions 0..7 hold segments 0 2 4 6 1 3 5 7 -- segments 1, 3, 5, 7 take over, 4 of 8
+// prime instead of 8. The positions D .. nseg-1 are the ones that take over, and they are the last ones: the tapered, short
+// segments, which pay the largest priming share, are among them, and the launch still ends on short workgroups. The order
+// within a set -- pairs over XCDs -- is untouched. A launch of fewer than D + 1 segments keeps the natural order and primes.
+static int fast_segment_order(int nseg, long per_seg, int slots, int nd, unsigned char* at) {
+  for (int k = 0; k < 64; k++) at[k] = (unsigned char)k;
+  if (fast_handoff_mode() != 1 || nd > 128) return nseg;
+  const long D = (slots + per_seg - 1) / per_seg + 1;
+  if (D >= nseg) return nseg;
+  int base = 0;
+  for (int r = 0; r < (int)D; r++)
+    for (int p = r; p < nseg; p += (int)D) at[p] = (unsigned char)base++;
+  return (int)D;
+}
+
 // The interior launch of a call with pl->fast: strips, row segments, split, then -- through the window and layout dispatch, which
 // knows the per-instantiation constants -- the border jobs, grid, LDS and the kernel's name.
 void sad_fast_plan(BmPlan* pl) {
@@ -190,13 +230,18 @@ void sad_fast_plan(BmPlan* pl) {
   // 10-14, formula 12, round 4's rule 6: 0.476 -> 0.469 ms; 1080p nd 256 x64 best 6-8, formula 6.6, round 4's 4: 8.28 -> 8.19;
   // 2160p x32 best 8-12, formula 9, round 4's 3: 17.64 -> 16.97; 1080p x16 and 2160p x4 unchanged at 13 and 25). Round 4's rule
   // (a workgroup target of 24 000 / 5 600 with segments of at least three window heights) was tuned at 64 / 16 / 4 pairs only.
+  // Where segments take their sums over (fast_segment_order) only the first D positions still prime, so more segments cost less
+  // than this model charges. kSegC was NOT re-fitted: forced counts at KITTI x64 with the hand-off on gave 0.869 ms per step at
+  // the formula's 8 segments, 0.873 at 10, 0.867 at 12, 0.866 at 14, 0.863 at 16 (profiles/r06_sad_handoff.txt) -- under 1 %,
+  // at 1.5 to 2 times the hand-off scratch, and measured at one shape only.
   // (one round of the chip for the cooperating 128-disparity wavefronts: 12 wavefronts per CU in workgroups of 2 / 3 / 4)
   const int round1 = g.nd <= 256 ? 1536 : (g.nd <= 384 ? 1024 : 768);
   constexpr double kSegC = 0.196;   // c of the model above
+  const int slots_i = g.nd <= 64 ? 4096 : (g.nd <= 128 ? 3072 : round1);
   int nseg = 1;
   {
     const double prime = 0.2 * (g.wsz - 1);
-    const double slots = g.nd <= 64 ? 4096.0 : (g.nd <= 128 ? 3072.0 : (double)round1);
+    const double slots = slots_i;
     nseg = (int)(std::sqrt(kSegC * slots * rows / ((double)strips * g.n * prime)) + 0.5);
     nseg = std::max(1, std::min(nseg, std::max(1, rows / g.wsz)));   // (at least one window height per segment here; see below)
   }
@@ -227,15 +272,43 @@ void sad_fast_plan(BmPlan* pl) {
     const int seg = (rows + nseg - 1) / nseg;
     for (int y = g.row0; y < g.row1; y += seg) a.segrow[++ns] = std::min(y + seg, g.row1);
   } else {
-    // nseg segments with weights 1,...,1, 3/4, 1/2, 1/4 (sum nseg - 1.5): fewer rows to prime than nseg equal ones
-    const double unit = rows / (nseg - 1.5);
-    double acc = 0;
-    for (int k = 0; k < nseg; k++) {
-      const double wgt = k < nseg - 3 ? 1.0 : (k == nseg - 3 ? 0.75 : (k == nseg - 2 ? 0.5 : 0.25));
-      acc += wgt * unit;
-      const int y = k == nseg - 1 ? g.row1 : std::min(g.row1, g.row0 + (int)(acc + 0.5));
-      if (y > a.segrow[ns]) a.segrow[++ns] = y;
+    // The weights go by DISPATCH POSITION (fast_segment_order: which segment a position holds): 1, ..., 1, 3/4, 1/2, 1/4 --
+    // fewer rows to prime than nseg equal ones, and the last workgroups of the launch are short. Where the order is not the
+    // identity (segments take their sums over), the positions of the first round of the chip -- every one of them starts when the
+    // launch does -- also get 10 % fewer rows per position they lie in front of that round's last one (kFirstRoundStep): their sets then finish
+    // one after the other, in dispatch order, which is what the order's distance rule counts on.
+    unsigned char at[64];
+    const int stride = fast_segment_order(nseg, per_seg, slots_i, g.nd, at);
+    const int first_round = stride - 1;
+    int len[64];
+    {
+      // (many small sets in the first round: the steps shrink so that its first set keeps 1 - kFirstRoundSpan of a regular one)
+      const double step = first_round > 1 ? std::min(kFirstRoundStep, kFirstRoundSpan / (first_round - 1)) : 0.0;
+      double wgt[64], sum = 0;
+      for (int p = 0; p < nseg; p++) {
+        wgt[p] = p < nseg - 3 ? 1.0 : (p == nseg - 3 ? 0.75 : (p == nseg - 2 ? 0.5 : 0.25));
+        if (stride < nseg && p < first_round) wgt[p] = std::min(wgt[p], 1.0 - step * (first_round - 1 - p));
+        sum += wgt[p];
+      }
+      const double unit = rows / sum;
+      double acc = 0;
+      int y0 = 0;
+      for (int p = 0; p < nseg; p++) {
+        acc += wgt[p] * unit;
+        const int y1 = p == nseg - 1 ? rows : std::min(rows, (int)(acc + 0.5));
+        len[p] = y1 - y0;
+        y0 = y1;
+      }
     }
+    // positions that got no row drop out; the order is the one of the segments that remain
+    int np = 0;
+    for (int p = 0; p < nseg; p++)
+      if (len[p] > 0) len[np++] = len[p];
+    fast_segment_order(np, per_seg, slots_i, g.nd, at);
+    int seglen[64];
+    for (int p = 0; p < np; p++) seglen[at[p]] = len[p];
+    for (int k = 0; k < np; k++) a.segrow[k + 1] = a.segrow[k] + seglen[k];
+    ns = np;
   }
   nseg = ns;
   a.strips = strips; a.nseg = nseg;
@@ -247,8 +320,38 @@ void sad_fast_plan(BmPlan* pl) {
   sad_fast_dispatch(*pl, nullptr, nullptr);   // no arguments: the dispatch fills the plan
 }
 
-// The arguments of the planned launch.
-hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* disp, int32_t* cost, BmPlan& pl, hipStream_t s) {
+// Which segments take their sums over in this call (bit k: segment k from k - 1) and the dispatch order that goes with it: none
+// with cooperating wavefronts, a masked count or SBM_FAST_HANDOFF=0, every later segment where the segments are launches of their own, else
+// the segments behind the first D positions of fast_segment_order().
+static unsigned long long fast_handoff_links(const BmPlan& pl, unsigned char* at) {
+  const FastPlan& f = pl.f;
+  const int mode = fast_handoff_mode();
+  const int stride = fast_segment_order(f.nseg, (long)f.strips * pl.g.n, fast_slots(pl.g.nd), pl.g.nd, at);
+  if (mode == 0 || f.NWAVES != 1 || !f.exact || f.nseg < 2) return 0;   // (FastHandoff<>::ON)
+  unsigned long long links = 0;
+  for (int p = mode == 2 ? 1 : stride; p < f.nseg; p++) links |= 1ull << at[p];
+  return links;
+}
+
+// Scratch of the hand-off: per later segment, pair and strip a ready word and a taken word, then (256-byte aligned) a slot of the
+// sums. 0: this call hands nothing over (also where the slots would take more than kHandoffMaxBytes: it primes instead).
+constexpr size_t kHandoffMaxBytes = (size_t)1 << 30;
+size_t sad_fast_handoff_bytes(const BmPlan& pl, size_t* flag_bytes) {
+  unsigned char at[64];
+  *flag_bytes = 0;
+  if (!pl.fast || !fast_handoff_links(pl, at)) return 0;
+  const size_t slots = (size_t)(pl.f.nseg - 1) * pl.g.n * pl.f.strips;
+  const size_t fb = (2 * slots * sizeof(u32) + 255) & ~(size_t)255;
+  const size_t bytes = fb + slots * ((size_t)(pl.f.NDW / 4) * 512 + 256);
+  if (bytes > kHandoffMaxBytes) return 0;
+  *flag_bytes = fb;
+  return bytes;
+}
+
+// The arguments of the planned launch. handoff: sad_fast_handoff_bytes() of scratch whose ready and taken words no earlier
+// launch has written `epoch` to (null: nothing is handed over); *links: how many (segment, pair, strip) may take their sums over.
+hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* disp, int32_t* cost, BmPlan& pl, void* handoff,
+                           unsigned epoch, long* links, hipStream_t s) {
   const Geom& g = pl.g;
   const FastPlan& f = pl.f;
   FastArgs a;
@@ -262,7 +365,22 @@ hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* di
   a.strips = f.strips; a.nseg = f.nseg; a.npairs = g.n; a.strips3 = f.strips3; a.uniq_plain = f.uniq_plain;
   a.xc0 = f.xc0; a.xc1 = f.xc1;
   a.bord = f.bord; a.bnw = f.bnw; a.bseg = f.bseg; a.nbseg = f.nbseg;
-  return sad_fast_dispatch(pl, &a, s);
+  a.ho_link = fast_handoff_links(pl, a.segat);   // (fills the order)
+  if (!handoff) a.ho_link = 0;
+  a.ho = static_cast<u32*>(handoff); a.ho_epoch = epoch;
+  a.segbase = 0; a.grid = f.grid;
+  const long per_seg = (long)f.strips * g.n;
+  *links = (long)__builtin_popcountll(a.ho_link) * per_seg;
+  if (fast_handoff_mode() != 2 || !a.ho_link) return sad_fast_dispatch(pl, &a, s);
+  // the segments as launches of their own, top to bottom (the order is the identity); the border jobs ride in the first
+  for (int k = 0; k < f.nseg; k++) {
+    a.segbase = k;
+    a.grid = (int)per_seg + (k == 0 ? f.bord * f.nbseg : 0);
+    if (k == 1) a.bord = 0;
+    const hipError_t e = sad_fast_dispatch(pl, &a, s);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace sbm

@@ -19,6 +19,7 @@ typedef unsigned int u32;
 typedef unsigned long long u64;
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 struct FastArgs {
   const uint8_t* pf_l;
@@ -28,8 +29,15 @@ struct FastArgs {
   int W, H, pitch, padl, plane;
   int nd, mindisp, lofs, rofs, tex, uniq, filtered, capb;
   int row0, row1;            // rows [row0,row1)
-  int segrow[66];            // row segment k = rows [segrow[k], segrow[k+1]); long segments first, short ones last
+  int segrow[66];            // row segment k = rows [segrow[k], segrow[k+1]), top to bottom
   int strips, nseg, npairs;  // grid decomposition (1-D grid of strips*nseg*npairs workgroups)
+  // hand-off of the vertical sums from row segment k to segment k + 1 of the same (pair, strip): see sad_fast_strip_dma
+  unsigned char segat[64];   // dispatch position -> row segment (fast_segment_order, sbm_sad_fast.hip)
+  int grid;                  // workgroups of this launch (FastPlan::grid unless the segments go out as launches of their own)
+  int segbase;               // first dispatch position of this launch (0 unless the segments go out as launches of their own)
+  unsigned long long ho_link;   // bit k: segment k may take its sums from segment k - 1 (and segment k - 1 leaves them)
+  u32* ho;                   // [nseg - 1][npairs][strips] ready words, as many taken words, then (256-byte aligned) as many slots of FastHandoff<>::SLOT_B bytes
+  u32 ho_epoch;              // this launch's number: a ready word that holds it was written by this launch
   int strips3;               // the first strips3 strips (a multiple of 3) have column stride 3, the others stride 1
   int uniq_plain;            // 8 * (maxS * uniq / 100 + 1) fits 16 bits: deficit partial sums need no saturating adds
   int xc0, xc1;              // interior centre columns [xc0,xc1) (relative to lofs); xc0 = w/2
@@ -58,6 +66,17 @@ __device__ __forceinline__ u32 umin3(u32 a, u32 b, u32 c) {
   asm("v_min3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
   return r;
 }
+
+// Hand-off of the vertical sums between the row segments of a (pair, strip) (sad_fast_strip_dma): the lone wavefronts of the exact
+// kernels take part; the cooperating ones (two to four per workgroup) and the masked counts always prime (the masked
+// 128-disparity kernels sit at 162-166 of their 168 registers and the hand-off costs them two to three, w 29 a spill). A slot holds NDW / 4 quads of 64 lanes x 8 bytes, then the 64
+// texture sums: 16.25 KB at 128 disparities.
+constexpr int kHandoffAux = 16;   // cache policy of the slots' buffer loads and stores: sc1 (agent scope)
+template <int NDW, int NWAVES, bool EXACT_ND>
+struct FastHandoff {
+  static constexpr bool ON = NWAVES == 1 && EXACT_ND;
+  static constexpr int SLOT_B = (NDW / 4) * 512 + 256;
+};
 
 extern __shared__ __attribute__((aligned(16))) uint4 fast_lds[];  // the workgroup's LDS: per wavefront its strip areas, then the merge area
 

@@ -19,9 +19,11 @@ sad_fast_kernel(FastArgs a) {
   // XCD-aware decode of the 1-D workgroup id: consecutive ids go round-robin over the 8 XCDs (each with its own
   // 4 MiB L2), so give XCD k the pairs k, k+8, ...: all strips and row segments of a pair then share one L2.
   // (Placement only affects speed; any mapping is correct.)
-  // Row segments are the slowest-varying index and get shorter towards the end of the grid: every segment pays w-1
-  // priming rows, so few long segments keep that overhead low while the short last ones keep the tail of the launch
-  // (CUs idling while the last workgroups finish) short.
+  // Row segments are the slowest-varying index: a set of strips x pairs workgroups per dispatch position, and FastArgs::segat
+  // says which segment a position holds (fast_segment_order, sbm_sad_fast.hip: consecutive segments of a (pair, strip) lie far
+  // enough apart for the later one to find the earlier one's vertical sums). The positions get shorter towards the end of the
+  // grid: every segment that primes pays w-1 priming rows, so few long segments keep that overhead low while the short last ones
+  // keep the tail of the launch (CUs idling while the last workgroups finish) short.
   const int bpp = a.strips;                             // workgroups per pair and segment
   int strip, segi, pair;
   {
@@ -40,8 +42,9 @@ sad_fast_kernel(FastArgs a) {
     }
     const int sid = blockIdx.x - a.bord * a.nbseg;
     const int per_seg = a.strips * a.npairs;
-    segi = sid / per_seg;
-    const int b = sid - segi * per_seg;
+    const int pos = sid / per_seg;                      // dispatch position of the segment set
+    segi = a.segat[a.segbase + pos];
+    const int b = sid - pos * per_seg;
     const int full = (a.npairs / 8) * 8 * bpp;          // ids covered by complete groups of 8 pairs
     int p, inner;
     if (b < full) {
@@ -65,7 +68,7 @@ sad_fast_kernel(FastArgs a) {
     unsigned char* const wb = ldsb + wvk * D::WAVE_B;
     unsigned char* const xl = wb + 2 * D::AREA_B;
     sad_fast_strip_dma<NDW, NWAVES, NTERM, PW, EXACT_ND, CSV>(a, wb, wb + D::AREA_B, xl,
-                                                            reinterpret_cast<u32*>(ldsb + NWAVES * D::WAVE_B), cb, segi, pair);
+                                                            reinterpret_cast<u32*>(ldsb + NWAVES * D::WAVE_B), cb, segi, pair, strip);
   };
   if constexpr (DUAL) {
     constexpr int NV3 = 64 - (NTERM - 1), NV1 = 64 - PW * (NTERM - 1);
@@ -136,7 +139,7 @@ static hipError_t launch_t(BmPlan& pl, const FastArgs* a, hipStream_t s) {
              NDW, NWAVES, NTERM, PW, f.exact ? "true" : "false", DUAL ? "true" : "false", g.pfshift);
     return hipSuccess;
   }
-  const dim3 grid((unsigned)pl.f.grid);
+  const dim3 grid((unsigned)a->grid);
   const size_t lds = (size_t)pl.f.lds;
   if constexpr (HAS_EXACT) {
     if (pl.f.exact) {

@@ -20,7 +20,7 @@ template <int NDW, int NWAVES, int NTERM, int PW, bool EXACT_ND, int CS>
 __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned char* __restrict__ const b0c, unsigned char* __restrict__ const b1c,
                                                    unsigned char* __restrict__ const xl1c,
                                                    u32* __restrict__ const xkey,
-                                                   const int cbase, const int segi, const int pair) {
+                                                   const int cbase, const int segi, const int pair, const int strip) {
   using L = FastLds<NDW, NTERM, PW, CS>;
   using D = DmaLds<NDW, NWAVES, NTERM, PW, CS>;
   using P = HPlan<NTERM, PW>;
@@ -33,6 +33,7 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
   constexpr int KS = L::KS;
   constexpr int NV = 64 - KS * (NTERM - 1);   // lanes that produce an output
   constexpr int XCH = D::XCH, XS = L::XS;
+  constexpr bool HANDOFF = FastHandoff<NDW, NWAVES, EXACT_ND>::ON;
 
   const int lane = threadIdx.x & 63;
   const int wv = NWAVES > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
@@ -57,6 +58,10 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
   // texture column sums. Level 0 is b0 after its staged row has been consumed.
   uint4* const xq0 = b0;
   uint4* const xq1 = reinterpret_cast<uint4*>(xl1c);
+  // (in the kernels that hand their sums over, level 1 is written and read as ONE 16-byte vector: as uint4 -- four members -- the
+  // halves of an entry no longer found each other in the backend once a strip could start from loaded sums, and the row loop of
+  // <64,1,7,3> ran on 8-byte LDS instructions, 4 % slower; the other kernels keep the form they were tuned with)
+  typedef u32x4 __attribute__((may_alias)) u32x4a;
   auto xt_of = [](uint4* const xq) { return reinterpret_cast<u32*>(xq + (XCH / 2) * XS); };
   const u32 capw = (u32)a.capb * 0x01010101u;
 
@@ -151,16 +156,54 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
     Vt = leave ? Vt - tv : Vt + tv;
   };
 
-  // prime: rows ys-W2 .. ys+W2-1 alternate between the two areas, the next one arriving while one is consumed; the last one
-  // staged (into b0) is row ys+W2, the first output row's entering row
-  stage(ys - W2, b0);
-  for (int i = 0; i < 2 * W2; i += 2) {
-    landed();
-    stage(ys - W2 + i + 1, b1);
-    apply(b0, false);
-    landed();
-    stage(ys - W2 + i + 2, b0);
-    apply(b1, false);
+  // The sums a segment starts from. Segment k + 1 of a (pair, strip) needs rows ys-W2 .. ys+W2-1 in VB[] / Vt -- which is what
+  // segment k of the same (pair, strip) holds behind its last row once that row's leaving row is taken out as well. Where the
+  // launch says so (FastArgs::ho_link) segment k leaves them in its slot of FastArgs::ho (below the row loop) and segment k + 1
+  // LOOKS for them, once: if the slot's ready word holds this launch's number it loads them and skips the priming rows,
+  // otherwise it primes. It never waits -- a workgroup must not depend on another one being scheduled -- and both ways give the
+  // same integers (carrier-lane tags included: they are part of VB[]), so the output cannot depend on which one was taken.
+  // Visibility (the L2s of the eight XCDs are not coherent and a CU's L1 is never refreshed by another CU's stores): the ready
+  // word AND the sums are written and read the way relaxed agent-scope atomics are -- write-through stores, loads that bypass
+  // the L1 (sc1) -- the wavefront waits for all its stores before it writes the ready word, and the taker puts an agent-scope
+  // acquire between the ready word and the sums. There is no agent-scope RELEASE in front of the ready word: on this chip it writes
+  // back every dirty line of the XCD's L2, the maps of all its wavefronts included, and 4 864 of them cost the KITTI x 64 stage
+  // 80 us where the priming they replaced had cost 20 (profiles/r06_sad_handoff.txt); write-through sums leave nothing to write back.
+  const size_t ho_slots = HANDOFF ? (size_t)(a.nseg - 1) * a.npairs * a.strips : 0;
+  const size_t ho_mine = HANDOFF ? ((size_t)segi * a.npairs + pair) * a.strips + strip : 0;   // the slot this segment leaves; it takes ho_mine - npairs * strips
+  auto ho_rsrc = [&](const size_t slot) {
+    unsigned char* const p = reinterpret_cast<unsigned char*>(a.ho) + ((2 * ho_slots * sizeof(u32) + 255) & ~(size_t)255) + slot * FastHandoff<NDW, NWAVES, EXACT_ND>::SLOT_B;
+    return __builtin_amdgcn_make_buffer_rsrc(p, 0, FastHandoff<NDW, NWAVES, EXACT_ND>::SLOT_B, 0x00020000);
+  };
+  bool take = false;
+  if constexpr (HANDOFF) {
+    if ((a.ho_link >> segi) & 1) {
+      const size_t from = ho_mine - (size_t)a.npairs * a.strips;
+      take = __builtin_amdgcn_readfirstlane(__hip_atomic_load(a.ho + from, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == a.ho_epoch;
+      if (take) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        const __amdgpu_buffer_rsrc_t rs_h = ho_rsrc(from);
+#pragma unroll
+        for (int q = 0; q < NQ; q++) VB[q] = __builtin_bit_cast(u64, __builtin_amdgcn_raw_buffer_load_b64(rs_h, (int)(8 * lane_u), 512 * q, kHandoffAux));
+        Vt = __builtin_amdgcn_raw_buffer_load_b32(rs_h, (int)(4 * lane_u), 512 * NQ, kHandoffAux);
+        if (lane == 0) a.ho[ho_slots + from] = a.ho_epoch;   // "taken": counted by sbm_debug_fetch(7), read by nobody else
+        stage(ys + W2, b0);   // the first output row's entering row
+      }
+    }
+  }
+  // prime (every segment that did not take its sums over): rows ys-W2 .. ys+W2-1 alternate between the two areas, the next one
+  // arriving while one is consumed; the last one staged (into b0) is row ys+W2, the first output row's entering row. A priming
+  // row is a full v_mqsad pass (~700 SIMD-cycles at 128 disparities): w - 1 of them per segment were 5.3 % of the KITTI x64 stage
+  // when every segment primed (profiles/r06_sad_handoff.txt).
+  if (!take) {
+    stage(ys - W2, b0);
+    for (int i = 0; i < 2 * W2; i += 2) {
+      landed();
+      stage(ys - W2 + i + 1, b1);
+      apply(b0, false);
+      landed();
+      stage(ys - W2 + i + 2, b0);
+      apply(b1, false);
+    }
   }
   // outputs through buffer stores: per-pair descriptors, this lane's byte offset, the row in a scalar register. A row's
   // results leave one iteration late, behind the wait at the top of the next row -- that wait covers everything this wavefront
@@ -242,7 +285,10 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
           for (int k = 1; k < P::S1; k++) tA += xt_of(xq0)[lx + KS * k];
         if constexpr (P::PUB1) {
 #pragma unroll
-          for (int e = 0; e < XCH / 2; e++) xq1[e * XS + lane] = make_uint4(A[e][0], A[e][1], A[e][2], A[e][3]);
+          for (int e = 0; e < XCH / 2; e++) {
+            if constexpr (HANDOFF) *reinterpret_cast<u32x4a*>(xq1 + e * XS + lane) = (u32x4){A[e][0], A[e][1], A[e][2], A[e][3]};
+            else xq1[e * XS + lane] = make_uint4(A[e][0], A[e][1], A[e][2], A[e][3]);
+          }
           if (tex_now) xt_of(xq1)[lane] = tA;
           published();
         }
@@ -253,7 +299,14 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
 #pragma unroll
         for (int e = 0; e < XCH / 2; e++) {
 #pragma unroll
-          for (int t = 1; t < P::NTT; t++) add4(A[e], xq1[e * XS + lx + KS * P::S1 * t]);
+          for (int t = 1; t < P::NTT; t++) {
+            if constexpr (HANDOFF) {
+              const u32x4 r = *reinterpret_cast<const u32x4a*>(xq1 + e * XS + lx + KS * P::S1 * t);
+              add4(A[e], make_uint4(r.x, r.y, r.z, r.w));
+            } else {
+              add4(A[e], xq1[e * XS + lx + KS * P::S1 * t]);
+            }
+          }
 #pragma unroll
           for (int v = (P::NTT > 0 ? 0 : 1); v < P::NVV; v++) add4(A[e], xq0[e * XS + lx + KS * (OV + v)]);
         }
@@ -343,6 +396,25 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
     }
   }
   flush(ye - 1);   // the segment's last row
+  // Leave the sums for the next segment of this (pair, strip). Behind the last row VB[] / Vt hold rows ye-1-W2 .. ye-1+W2, and
+  // the last iteration has staged that row's successors all the same: b1 = row ye-1-W2, the row that leaves at row ye. It is
+  // taken out HERE, so that what is handed over is exactly the primed state of a segment that starts at ye (rows ye-W2 ..
+  // ye+W2-1: without row ye-1-W2, not yet with row ye+W2) and the successor's first row takes the y == ys path of the row loop
+  // like a primed one: it enters row ye+W2 itself and applies no leaving row.
+  if constexpr (HANDOFF) {
+    if (segi + 1 < a.nseg && ((a.ho_link >> (segi + 1)) & 1)) {
+      landed();
+      apply(b1, true);
+      const __amdgpu_buffer_rsrc_t rs_h = ho_rsrc(ho_mine);
+#pragma unroll
+      for (int q = 0; q < NQ; q++) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, VB[q]), rs_h, (int)(8 * lane_u), 512 * q, kHandoffAux);
+      __builtin_amdgcn_raw_buffer_store_b32(Vt, rs_h, (int)(4 * lane_u), 512 * NQ, kHandoffAux);
+      // every store above has reached memory before the ready word is written (written out: it must stay in front of that store
+      // whatever the compiler can prove about this wavefront's other memory operations)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (lane == 0) __hip_atomic_store(a.ho + ho_mine, a.ho_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
 }
 
 }  // namespace sbm

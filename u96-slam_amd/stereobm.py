@@ -173,9 +173,12 @@ class StereoBM(_engine.Engine, _frontend.FrontEnd, _fpga.FpgaMatcher, _gftt.Gftt
     def profile(self):
         return self._profile(("prefilter", "sad", "lrcheck", "speckle", "total"))
 
-    def debug_fetch(self, which, n, h, w):
-        dt = {0: np.uint8, 1: np.uint8, 2: np.int32, 3: np.int16}[which]
-        a = np.empty((n, h, w), dt)
+    def debug_fetch(self, which, n=0, h=0, w=0):
+        """Planes of the last device call: 0 / 1 the prefiltered images, 2 the cost plane, 3 the map before the LR check, each
+        (n, h, w); 7 the hand-off of the interior SAD kernel's vertical sums: int32 (row segments x pairs x strips that took
+        their sums over, those that could have)."""
+        dt = {0: np.uint8, 1: np.uint8, 2: np.int32, 3: np.int16, 7: np.int32}[which]
+        a = np.empty((2,) if which == 7 else (n, h, w), dt)
         _check(self._L.sbm_debug_fetch(self._h, which, a.ctypes.data, a.nbytes), self._h)
         return a
 
