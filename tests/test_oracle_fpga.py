@@ -8,6 +8,8 @@ blocks against their definitions, the firmware's register constants, and the geo
 import numpy as np
 import pytest
 
+import fpga_cases
+
 
 # ---- independent restatement (numpy) ---------------------------------------------------------------------------------
 def py_diven(DW, VW, QW, MSB_INV, dividend, divisor):
@@ -282,3 +284,76 @@ def test_gftt_oracle_properties(oracle, golden):
     t[20:, 30:] = 200
     ce, _ = oracle.gftt_eig(t)
     assert ce[18:23, 28:33].max() > 100 * max(1, int(ce[30, 28:33].max())) or ce[30, 28:33].max() == 0
+
+
+# ---- the oracle against the restatement where the GPU tests send it (tests/test_gpu_fpga_paths.py): beyond 128 disparities,
+# where disp1 fills its 8 bits and (disp1 + 1) & 255 wraps, on ties within and across phases, with the winner on the guard
+# lanes' neighbours, and with saturating column sums over several phases -- each under the three filter settings
+def _both(oracle, xl, xr, wsz, nd):
+    """Oracle == restatement under every filter setting; returns the oracle's maps."""
+    out = []
+    for uni in fpga_cases.UNI:
+        got = oracle.fpga_bm(xl, xr, wsz, nd, *uni)
+        ref = py_fpga_bm(xl, xr, wsz, nd, *uni)
+        assert np.array_equal(got, ref), (uni, np.argwhere(got != ref)[:5].tolist())
+        out.append(got)
+    return out
+
+
+@pytest.mark.parametrize("wsz", [3, 5])
+@pytest.mark.parametrize("nd", [64, 160, 224, 256])
+def test_ties_over_several_phases(oracle, nd, wsz):
+    H, W = wsz + 3, nd + 1 + 2 * (wsz // 2) + 7
+    rng = np.random.default_rng(nd * 10 + wsz)
+    maps = _both(oracle, *fpga_cases.two_level(rng, H, W), wsz, nd)
+    assert (maps[0] != -1).any()
+    maps = _both(oracle, *fpga_cases.periodic8(rng, H, W), wsz, nd)
+    # SAD 0 at disparities 3, 11, 19, ...: the first one wins every merge (strict '<'), neighbours are equal or the divisor is 0
+    inner = maps[0][wsz // 2:H - wsz // 2, nd + wsz // 2 + 1:W - wsz // 2].astype(int)
+    assert (np.abs(inner - 3 * 16) <= 4).all()
+    maps = _both(oracle, *fpga_cases.zeros(H, W), wsz, nd)
+    # every SAD 0: disparity 0 wins, the fraction's divisor is 0 with l >= r -> 0xC0 = -0.25 -> negative depth -> 0xFFFF
+    assert (maps[0] == -1).all()
+
+
+@pytest.mark.parametrize("s", fpga_cases.PHASE_END_SHIFTS)
+def test_winners_at_the_ends_of_a_phase(oracle, s):
+    wsz, nd = 5, 96
+    hw = wsz // 2
+    H, W = wsz + 2, nd + 1 + 2 * hw + 9
+    xl, xr = fpga_cases.shifted(np.random.default_rng(100 + s), H, W, s)
+    for m in _both(oracle, xl, xr, wsz, nd):
+        inner = m[hw:H - hw, nd + hw + 1:W - hw].astype(int)
+        if s == 0:
+            # disparity 0 with a fraction: zero or negative depths are 0xFFFF (bm_obuf2.v:119-154)
+            assert set(np.unique(inner)) <= {-1, 0}
+        else:
+            # SAD 0 at D = s (min1 = 0 passes every filter threshold); the fraction stays within +-0.25 px = +-4 units
+            assert (np.abs(inner - 16 * s) <= 4).all(), np.unique(inner)
+
+
+@pytest.mark.parametrize("wsz,nd", [(17, 64), (21, 96), (31, 160)])
+def test_saturation_over_several_phases(oracle, wsz, nd):
+    H, W = wsz + 6, nd + 1 + 2 * (wsz // 2) + 6
+    xl, xr = fpga_cases.saturating(np.random.default_rng(wsz * 1000 + nd), H, W)
+    assert fpga_cases.saturates(xl, xr, wsz, nd) > 1023
+    maps = _both(oracle, xl, xr, wsz, nd)
+    assert (maps[0] != -1).any()
+    # every column sum within a few units of the limiter: which lane wins depends on what was cut off rows earlier
+    xl, xr = fpga_cases.near_limit(np.random.default_rng(wsz), H, W, wsz)
+    assert fpga_cases.saturates(xl, xr, wsz, nd) > 1023
+    _both(oracle, xl, xr, wsz, nd)
+
+
+def test_saturates_helper_is_the_unclamped_column_sum():
+    rng = np.random.default_rng(1)
+    xl, xr = fpga_cases.noisy_shift(rng, 12, 60, 4)
+    wsz, nd = 5, 32
+    best = 0
+    for x in range(nd, 59):
+        for D in range(-1, nd + 1):
+            col = np.abs((xr[:, x - D] & 63).astype(int) - (xl[:, x] & 63).astype(int))
+            best = max(best, max(int(col[r:r + wsz].sum()) for r in range(12 - wsz + 1)))
+    assert fpga_cases.saturates(xl, xr, wsz, nd) == best
+    assert fpga_cases.saturates(*fpga_cases.constant(17, 80, 63, 0), 17, 32) == 17 * 63
+    assert fpga_cases.saturates(*fpga_cases.bounded(rng, 40, 120, 31, 7), 31, 64) <= 1023

@@ -106,7 +106,7 @@ def main():
     nf = 0 if args.big else max(10, args.iters // 4)
     for it in range(nf):
         wsz = int(rng.choice([3, 5, 9, 15, 21, 27, 31]))
-        nd = int(rng.choice([32, 64, 96, 128, 192, 256]))
+        nd = int(rng.choice([32, 64, 96, 128, 160, 192, 224, 256]))   # every launch grouping: [1] [2] [2,1] [4] [4,1] [4,2] [4,2,1] [4,4]
         hw = wsz // 2
         if (nd + hw + 1) % 32 == 0:
             continue

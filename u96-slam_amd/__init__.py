@@ -20,6 +20,7 @@ GPU raises. The CPU oracle lives in /oracle and is only used by the tests and by
 from .stereobm import (StereoBM, StereoBMError, SbmParams, StereoModel, library_path, load_library, PREFILTER_XSOBEL,  # noqa: F401
                        PREFILTER_NORMALIZED_RESPONSE, RectCam, make_rect_cam, PREFILTER_FLAVOUR_CV, PREFILTER_FLAVOUR_RTL, trim,
                        FpgaParams, fpga_params, fpga_params_from_regs, fpga_sad_size_reg, fpga_validate, compute_multi,
+                       FpgaPlan, fpga_plan,
                        GfttSelectParams, gftt_select_params, gftt_select_validate, gftt_select_capacity,
                        GfttCvParams, gftt_cv_params, gftt_cv_validate,
                        OrbParams, orb_params, orb_validate, MatchParams, match_params, match_validate,
@@ -40,6 +41,7 @@ from ._pgo import (PoseGraph, PgoParams, PgoPlanInfo, PgoGraph, pgo_params, pgo_
 __all__ = ["StereoBM", "StereoBMError", "SbmParams", "StereoModel", "library_path", "load_library", "PREFILTER_XSOBEL",
            "PREFILTER_NORMALIZED_RESPONSE", "RectCam", "make_rect_cam", "PREFILTER_FLAVOUR_CV", "PREFILTER_FLAVOUR_RTL", "trim",
            "FpgaParams", "fpga_params", "fpga_params_from_regs", "fpga_sad_size_reg", "fpga_validate", "compute_multi",
+           "FpgaPlan", "fpga_plan",
            "StereoSGBM", "SgbmParams", "sgbm_params", "sgbm_validate", "GfttSelectParams", "gftt_select_params",
            "gftt_select_validate", "gftt_select_capacity", "OrbParams", "orb_params", "orb_validate", "MatchParams",
            "match_params", "match_validate", "PnpParams", "pnp_params", "pnp_validate", "pnp_records", "PNP_RESULT_DTYPE",

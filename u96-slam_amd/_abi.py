@@ -57,6 +57,23 @@ class FpgaParams(ctypes.Structure):
                                               "uni_threshold")]
 
 
+class FpgaLaunch(ctypes.Structure):
+    """One launch of `FpgaPlan`: its first 32-disparity phase, how many it holds (1, 2 or 4), the lean instantiation."""
+
+    _fields_ = [(k, ctypes.c_int32) for k in ("phase0", "nph", "lean")]
+
+
+class FpgaPlan(ctypes.Structure):
+    """`FpgaPlan` of csrc/sbm_fpga.hip, as sbm_fpga_debug_plan copies it out: what the host decides before the matcher's launches."""
+
+    _fields_ = [(k, ctypes.c_int32) for k in ("hwsz", "hsad_wdt", "sad_wdt", "sad_hgt", "nv", "strips", "nphase", "nseg", "seg",
+                                              "grid_y", "track_sat", "exact", "xs", "lds", "nlaunch")] + [("launch", FpgaLaunch * 8)]
+
+    @property
+    def groups(self):
+        return [self.launch[i].nph for i in range(self.nlaunch)]
+
+
 class GfttSelectParams(ctypes.Structure):
     """`sbm_gftt_select_params` of include/sbm.h: generateKeypoints2's constants (src/slam/src/core/GFTT.cpp:50-53)."""
 
@@ -267,6 +284,7 @@ def load_library():
     L.sbm_fpga_sad_size_reg.argtypes = [fp]
     L.sbm_fpga_sad_size_reg.restype = u32
     L.sbm_fpga_params_validate.argtypes = [fp]
+    L.sbm_fpga_debug_plan.argtypes = [fp, ci, vp, sz]
     L.sbm_fpga_bm_device.argtypes = [vp, ci, vp, vp, fp, vp, ci]
     L.sbm_fpga_compute_device.argtypes = [vp, ci, vp, vp, fp, vp, ci]
     L.sbm_gftt_eig_device.argtypes = [vp, ci, vp, ci, ci, vp, vp, ci]

@@ -4,7 +4,7 @@ import ctypes
 
 import numpy as np
 
-from ._abi import FpgaParams, StereoBMError, _check, _torch, load_library
+from ._abi import FpgaParams, FpgaPlan, StereoBMError, _check, _torch, load_library
 
 
 def fpga_params(width, height, block_size=21, num_disparities=64, uni_enable=0, uni_mode=0, uni_threshold=0):
@@ -27,8 +27,15 @@ def fpga_validate(params):
     return int(load_library().sbm_fpga_params_validate(ctypes.byref(params)))
 
 
+def fpga_plan(params, n=1):
+    """The launch plan of fpga_bm for these parameters and n pairs (FpgaPlan; sbm_fpga_debug_plan: no handle, no device)."""
+    pl = FpgaPlan()
+    _check(load_library().sbm_fpga_debug_plan(ctypes.byref(params), n, ctypes.byref(pl), ctypes.sizeof(pl)))
+    return pl
+
+
 class FpgaMatcher:
-    def _fpga(self, fn, a, b, params):
+    def _fpga(self, fn, a, b, params, sync=True):
         torch = _torch()
         self._check_device_images(a, b)
         if a.shape != b.shape:
@@ -38,16 +45,17 @@ class FpgaMatcher:
         if (w, h) != (params.width, params.height):
             raise StereoBMError(-2, f"images are {w}x{h}, ImageSize says {params.width}x{params.height}")
         out = torch.empty(a.shape, dtype=torch.int16, device=a.device)
-        self._device_call(fn, (n, a3.data_ptr(), b.data_ptr(), ctypes.byref(params), out.data_ptr()), (a3, b, out))
+        self._device_call(fn, (n, a3.data_ptr(), b.data_ptr(), ctypes.byref(params), out.data_ptr()), (a3, b, out), sync)
         return out
 
-    def fpga_bm(self, xsbl_l, xsbl_r, params):
-        """RTL block matcher on x-Sobel planes (torch CUDA uint8, (n,H,W) or (H,W)) -> int16 s11.4, -1 = none."""
-        return self._fpga(self._L.sbm_fpga_bm_device, xsbl_l, xsbl_r, params)
+    def fpga_bm(self, xsbl_l, xsbl_r, params, sync=True):
+        """RTL block matcher on x-Sobel planes (torch CUDA uint8, (n,H,W) or (H,W)) -> int16 s11.4, -1 = none.
+        sync=False leaves the call running on the engine's stream (call synchronize() before reading the result)."""
+        return self._fpga(self._L.sbm_fpga_bm_device, xsbl_l, xsbl_r, params, sync)
 
-    def fpga_compute(self, left, right, params):
+    def fpga_compute(self, left, right, params, sync=True):
         """xsbl2.v prefilter + RTL block matcher on rectified frames: the PL pipeline behind Fpga::receiveDepthMap."""
-        return self._fpga(self._L.sbm_fpga_compute_device, left, right, params)
+        return self._fpga(self._L.sbm_fpga_compute_device, left, right, params, sync)
 
     def fpga_compute_host(self, left, right, params):
         """numpy uint8 (H,W) rectified pair -> numpy int16 (H,W): the frame Fpga::receiveDepthMap would hand out."""

@@ -25,6 +25,7 @@
 // one-segment launch (which exits immediately for unstamped pairs; not launched when wsz * 63 <= 1023) recomputes such
 // pairs strictly top to bottom.
 #include <algorithm>
+#include <cstring>
 
 #include "sbm_handle.h"
 
@@ -443,50 +444,88 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NPH == 
   if (a.track_sat && !a.exact && col_ok && (satmax & 0x04000400u)) atomicMax(a.flag + pair, a.gen);
 }
 
+// The plan of one matcher call: everything the host decides before it launches anything, as plain data, computed without a HIP
+// call. launch_fpga_bm executes it and recomputes nothing. sbm_fpga_debug_plan() (below; not in include/sbm.h) copies it out as
+// it stands, so the layout IS that export's: int32 words in declaration order. tests/test_fpga_plan.py mirrors it with ctypes;
+// the export refuses a mirror of another size.
+constexpr int kFpgaMaxLaunches = 8;
+struct FpgaLaunch {
+  int phase0, nph, lean;     // first phase, phases held in registers (1, 2 or 4), the LEAN instantiation
+};
+struct FpgaPlan {
+  int hwsz, hsad_wdt, sad_wdt, sad_hgt;   // bm.v:249-255
+  int nv, strips;            // outputs per strip (64 - 2 hwsz), strips = grid x
+  int nphase;                // 32-disparity phases of the range
+  int nseg, seg, grid_y;     // segmented pass: segments aimed at, output rows per segment, grid rows (<= nseg)
+  int track_sat;             // wsz * 63 > 1023: a column sum can saturate
+  int exact;                 // the one-segment pass for flagged pairs is launched (seg = sad_hgt, one grid row)
+  int xs, lds;               // FP_XS; dynamic LDS bytes of every launch
+  int nlaunch;               // launches per pass, in stream order
+  FpgaLaunch launch[kFpgaMaxLaunches];
+};
+
+static void fpga_plan(const sbm_fpga_params& p, int n, FpgaPlan* pl) {
+  memset(pl, 0, sizeof(*pl));
+  const int wsz = p.block_size;
+  pl->hwsz = wsz >> 1;
+  pl->hsad_wdt = p.width - p.num_disparities - 1; pl->sad_wdt = pl->hsad_wdt - 2 * pl->hwsz; pl->sad_hgt = p.height - 2 * pl->hwsz;
+  pl->track_sat = wsz * 63 > 1023;                 // 6-bit abs-diffs: a column sum of up to 16 rows cannot reach the limiter
+  pl->nv = 64 - 2 * pl->hwsz;
+  pl->strips = (pl->sad_wdt + pl->nv - 1) / pl->nv;
+  pl->nphase = p.num_disparities >> 5;
+  // segments: enough wavefronts for the chip, each paying wsz-1 priming rows
+  int nseg = 1;
+  while ((long)pl->strips * nseg * n < 4096 && pl->sad_hgt / (nseg + 1) >= 2 * wsz) nseg++;
+  pl->nseg = nseg;
+  pl->seg = (pl->sad_hgt + nseg - 1) / nseg;
+  pl->grid_y = (pl->sad_hgt + pl->seg - 1) / pl->seg;
+  pl->exact = nseg > 1 && pl->track_sat;           // else the first pass already ran top to bottom / nothing can saturate
+  pl->xs = FP_XS;
+  // prefix rows + the two staged-row areas of the widest launch (4 phases: 64 + 4 * 33 = 196 slots -> 4 loads of 64)
+  pl->lds = (int)((FP_NR * FP_XS + 2 * 256) * sizeof(u32));
+  const int nph = pl->nphase >= 4 ? 4 : pl->nphase;   // phases per launch: up to 4 live in one wavefront's registers
+  for (int k = 0; k < pl->nphase;) {
+    // the remaining phases in groups of 4, 2 or 1 (3 phases = 2 + 1, 6 = 4 + 2, ...)
+    const int left = pl->nphase - k, grp = left >= 4 && nph == 4 ? 4 : (left >= 2 ? 2 : 1);
+    FpgaLaunch& l = pl->launch[pl->nlaunch++];
+    l.phase0 = k; l.nph = grp;
+    l.lean = k == 0 && grp == pl->nphase && !p.uni_enable;   // the whole range in one launch, no uniqueness filter
+    k += grp;
+  }
+}
+
 // xl/xr: dense n*H*W x-Sobel planes on the device. rec: n*sad_hgt*sad_wdt uint2 (used beyond 128 disparities only),
 // flag: n ints, zero when allocated; gen: a number that grows with every call on these buffers (> 0).
 static hipError_t launch_fpga_bm(const uint8_t* xl, const uint8_t* xr, void* rec, int* flag, int gen, int16_t* disp, int n,
                           const sbm_fpga_params& p, hipStream_t s) {
+  FpgaPlan pl;
+  fpga_plan(p, n, &pl);
   FpgaArgs a;
-  const int W = p.width, H = p.height;
-  a.W = W; a.H = H;
-  a.nd = p.num_disparities; a.wsz = p.block_size; a.hwsz = p.block_size >> 1;
-  a.hsad_wdt = W - a.nd - 1; a.sad_wdt = a.hsad_wdt - 2 * a.hwsz; a.sad_hgt = H - 2 * a.hwsz;
+  a.W = p.width; a.H = p.height;
+  a.nd = p.num_disparities; a.wsz = p.block_size; a.hwsz = pl.hwsz;
+  a.hsad_wdt = pl.hsad_wdt; a.sad_wdt = pl.sad_wdt; a.sad_hgt = pl.sad_hgt;
   a.uni_enb = p.uni_enable; a.uni_mode = p.uni_mode; a.uni_thr = p.uni_threshold;
   a.xl = xl; a.xr = xr; a.rec = static_cast<uint2*>(rec); a.disp = disp; a.flag = flag; a.gen = gen;
-  a.track_sat = a.wsz * 63 > 1023;                 // 6-bit abs-diffs: a column sum of up to 16 rows cannot reach the limiter
-  const int NV = 64 - 2 * a.hwsz;
-  const int strips = (a.sad_wdt + NV - 1) / NV;
-  const int nphase = a.nd >> 5;
-  // segments: enough wavefronts for the chip, each paying wsz-1 priming rows
-  int nseg = 1;
-  while ((long)strips * nseg * n < 4096 && a.sad_hgt / (nseg + 1) >= 2 * a.wsz) nseg++;
-  // prefix rows + the two staged-row areas of the widest launch (4 phases: 64 + 4 * 33 = 196 slots -> 4 loads of 64)
-  const size_t lds = (size_t)(FP_NR * FP_XS + 2 * 256) * sizeof(u32);
-  const int nph = nphase >= 4 ? 4 : nphase;        // phases per launch: up to 4 live in one wavefront's registers
-  for (int pass = 0; pass < 2; pass++) {
+  a.track_sat = pl.track_sat;
+  const size_t lds = (size_t)pl.lds;
+  for (int pass = 0; pass < 1 + pl.exact; pass++) {
     // pass 0: segmented (exact unless a column sum saturates); pass 1: flagged pairs only, one segment top to bottom
     a.exact = pass;
-    const int ns = pass ? 1 : nseg;
-    a.seg = (a.sad_hgt + ns - 1) / ns;
-    if (pass == 1 && (nseg == 1 || !a.track_sat)) break;   // the first pass already ran top to bottom / nothing can saturate
-    const dim3 grid(strips, (a.sad_hgt + a.seg - 1) / a.seg, n);
-    for (int k = 0; k < nphase;) {
-      // the remaining phases in groups of 4, 2 or 1 (3 phases = 2 + 1, 6 = 4 + 2, ...)
-      const int left = nphase - k, grp = left >= 4 && nph == 4 ? 4 : (left >= 2 ? 2 : 1);
-      a.phase0 = k; a.first = k == 0; a.last = k + grp == nphase;
-      const bool lean = a.first && a.last && !a.uni_enb;   // the whole range in one launch, no uniqueness filter
-      if (grp == 4) {
-        if (lean) hipLaunchKernelGGL((fpga_bm_kernel<4, true>), grid, dim3(64), lds, s, a);
+    a.seg = pass ? pl.sad_hgt : pl.seg;
+    const dim3 grid(pl.strips, pass ? 1 : pl.grid_y, n);
+    for (int i = 0; i < pl.nlaunch; i++) {
+      const FpgaLaunch& l = pl.launch[i];
+      a.phase0 = l.phase0; a.first = i == 0; a.last = i == pl.nlaunch - 1;
+      if (l.nph == 4) {
+        if (l.lean) hipLaunchKernelGGL((fpga_bm_kernel<4, true>), grid, dim3(64), lds, s, a);
         else hipLaunchKernelGGL((fpga_bm_kernel<4, false>), grid, dim3(64), lds, s, a);
-      } else if (grp == 2) {
-        if (lean) hipLaunchKernelGGL((fpga_bm_kernel<2, true>), grid, dim3(64), lds, s, a);
+      } else if (l.nph == 2) {
+        if (l.lean) hipLaunchKernelGGL((fpga_bm_kernel<2, true>), grid, dim3(64), lds, s, a);
         else hipLaunchKernelGGL((fpga_bm_kernel<2, false>), grid, dim3(64), lds, s, a);
       } else {
-        if (lean) hipLaunchKernelGGL((fpga_bm_kernel<1, true>), grid, dim3(64), lds, s, a);
+        if (l.lean) hipLaunchKernelGGL((fpga_bm_kernel<1, true>), grid, dim3(64), lds, s, a);
         else hipLaunchKernelGGL((fpga_bm_kernel<1, false>), grid, dim3(64), lds, s, a);
       }
-      k += grp;
     }
   }
   return hipGetLastError();
@@ -528,6 +567,21 @@ int sbm_fpga_params_validate(const sbm_fpga_params* p) {
   const int hwsz = p->block_size >> 1;
   if (p->width - p->num_disparities - 1 - 2 * hwsz < 1 || p->height - 2 * hwsz < 1) return SBM_ERR_SIZE;
   if (((p->num_disparities + hwsz + 1) & 31) == 0) return SBM_ERR_UNSUPPORTED;
+  return SBM_OK;
+}
+
+// The plan of a call as sbm_fpga_bm_device would compute it for these parameters and n pairs: a copy of FpgaPlan (above has the
+// layout). No handle, no device. Not part of the public header: for the tests.
+int sbm_fpga_debug_plan(const sbm_fpga_params* p, int n, void* out, size_t out_bytes) {
+  if (!p || !out) return SBM_ERR_NULL;
+  if (out_bytes != sizeof(FpgaPlan)) return SBM_ERR_SIZE;
+  if (n <= 0) return SBM_ERR_BATCH;
+  const int st = sbm_fpga_params_validate(p);
+  if (st != SBM_OK) return st;
+  if (n > 65535) return SBM_ERR_UNSUPPORTED;
+  FpgaPlan pl;
+  fpga_plan(*p, n, &pl);
+  memcpy(out, &pl, sizeof(pl));
   return SBM_OK;
 }
 
