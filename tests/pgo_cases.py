@@ -507,7 +507,7 @@ def edge_cases():
 def shape_cases(run_max=4):
     """name -> graph: the shapes that hit each elimination path."""
     out = {"pair": chain_graph(2, seed=1, perturb=2e-2)}
-    for n in (3, run_max - 1, run_max, run_max + 1, 2 * run_max + 1):
+    for n in (3, max(run_max - 1, 1), run_max, run_max + 1, 2 * run_max + 1):   # a chain has an edge: run_max 1 has no chain0
         out[f"chain{n}"] = chain_graph(n + 1, seed=10 + n, noise=2e-2, perturb=2e-2)
     out["ring8_new_old"] = chain_graph(8, [(8, 2)], seed=3, noise=2e-2)
     out["ring8_old_new"] = chain_graph(8, [(2, 8)], seed=3, noise=2e-2)

@@ -48,6 +48,26 @@ struct DevBuf {
   void release() { hipFree(p); p = nullptr; bytes = 0; }
 };
 
+// Consecutive pieces of one buffer, each beginning on a 16-byte boundary (pad16). Over a null base it only counts. A layout is
+// one function of a Carve, run twice by carve(): the statements that place the pieces are the ones that size the buffer.
+struct Carve {
+  char* base;
+  size_t off = 0;
+  template <class T> T* take(size_t n) {
+    T* piece = base ? (T*)(base + off) : nullptr;
+    off += pad16(n * sizeof(T));
+    return piece;
+  }
+};
+template <class Layout> hipError_t carve(DevBuf& b, hipStream_t s, Layout layout) {
+  Carve count{nullptr};
+  layout(count);
+  const hipError_t e = b.grow(count.off, s);
+  Carve place{b.as<char>()};
+  if (e == hipSuccess) layout(place);
+  return e;
+}
+
 // The sets below list their buffers through each(f); these walk them.
 template <class Set> void release_all(Set& s) { s.each([](DevBuf& b) { b.release(); }); }
 template <class Set> size_t bytes_held(Set& s) {
@@ -132,9 +152,10 @@ template <int NStage, int NMark, int N> constexpr StageTable stage_table(const c
 }
 
 // The pose-graph optimiser's last call, for sbm_pgo_last_plan and sbm_pgo_debug_fetch: its sizes, the lambda of its last
-// iteration, and where that iteration's records lie in the handle's buffers (null until a call has finished).
-struct PgoLast { int ne, nfree, nslots, nj, nruns, iterations; double lambda; };
+// iteration, and where that iteration's records lie in the handle's buffers (null until a call has finished). One record, so
+// that a call resets all of it in one statement before it replaces any buffer.
 struct PgoDebug { const double *rec, *D, *Eoff, *bv, *x; };
+struct PgoLast { int ne, nfree, nslots, nj, nruns, iterations; double lambda; PgoDebug dev; };
 
 }  // namespace sbm
 
@@ -269,7 +290,6 @@ struct sbm_handle {
     sbm::DevBuf graph, edge, sys, schur;
     sbm::StageClock clock;
     sbm::PgoLast last;
-    sbm::PgoDebug dev;
     sbm_pgo_plan_info plan;
     template <class F> void each(F f) { f(graph); f(edge); f(sys); f(schur); }
   } pgo;

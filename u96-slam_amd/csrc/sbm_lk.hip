@@ -433,14 +433,17 @@ int sbm_lk_stereo(sbm_handle* h, const uint8_t* left, size_t left_stride, const 
   HIPCHK(h, dscope.enter());
   st = ensure_staging(h, 1, width, height);
   if (st != SBM_OK) return st;
-  // points, right points, errors, count, status
   const size_t np = (size_t)npts;
-  HIPCHK(h, h->lk.io.grow(np * 20 + 16 + np, h->stream));
-  float* d_p = h->lk.io.as<float>();
-  float* d_r = d_p + 2 * np;
-  float* d_e = d_r + 2 * np;
-  int* d_n = (int*)(d_e + np);
-  uint8_t* d_s = (uint8_t*)(d_n + 4);
+  float *d_p = nullptr, *d_r = nullptr, *d_e = nullptr;
+  int* d_n = nullptr;
+  uint8_t* d_s = nullptr;
+  HIPCHK(h, carve(h->lk.io, h->stream, [&](Carve& c) {
+    d_p = c.take<float>(2 * np);   // points
+    d_r = c.take<float>(2 * np);   // right points
+    d_e = c.take<float>(np);       // errors
+    d_n = c.take<int>(4);          // count (16 bytes)
+    d_s = c.take<uint8_t>(np);     // status
+  }));
   HIPCHK(h, hipMemcpy2DAsync(h->st.l.p, width, left, left_stride, width, height, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpy2DAsync(h->st.r.p, width, right, right_stride, width, height, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_p, pts, np * 8, hipMemcpyHostToDevice, h->stream));

@@ -395,17 +395,18 @@ static int match_host(sbm_handle* h, bool guess, const float* xyz_from, const fl
   if (st != SBM_OK) return st;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
-  // desc 2 frames, counts (2) + npairs (1) + pad, pairs, [points of frame 0, keypoints of frame 1, projections]
-  const size_t bd = (size_t)2 * cap * 32, bp = (size_t)cap * 8, bx = (size_t)2 * cap * 12, bk = (size_t)2 * cap * 8;
-  const size_t bytes = bd + 16 + bp + (guess ? bx + bk + bp : 0);
-  HIPCHK(h, h->mt.io.grow(bytes, h->stream));
-  char* io = h->mt.io.as<char>();
-  uint8_t* d_desc = (uint8_t*)io;
-  int* d_n = (int*)(io + bd);
-  int* d_pairs = (int*)(io + bd + 16);
-  float* d_xyz = (float*)(io + bd + 16 + bp);
-  float* d_kp = (float*)((char*)d_xyz + bx);
-  float* d_proj = (float*)((char*)d_kp + bk);
+  uint8_t* d_desc = nullptr;
+  int *d_n = nullptr, *d_pairs = nullptr;
+  float *d_xyz = nullptr, *d_kp = nullptr, *d_proj = nullptr;   // the guided form's
+  HIPCHK(h, carve(h->mt.io, h->stream, [&](Carve& c) {
+    d_desc = c.take<uint8_t>((size_t)2 * cap * 32);   // 2 frames
+    d_n = c.take<int>(4);                             // counts (2) + npairs (1) + pad
+    d_pairs = c.take<int>((size_t)cap * 2);
+    if (!guess) return;
+    d_xyz = c.take<float>((size_t)2 * cap * 3);       // points of frame 0 (2 frames)
+    d_kp = c.take<float>((size_t)2 * cap * 2);        // keypoints of frame 1 (2 frames)
+    d_proj = c.take<float>((size_t)cap * 2);          // projections
+  }));
   const int cnt[2] = {nf, nt};
   if (nf > 0) HIPCHK(h, hipMemcpy2DAsync(d_desc, 32, desc_from, stride_from, 32, nf, hipMemcpyHostToDevice, h->stream));
   if (nt > 0)

@@ -8,7 +8,8 @@
 //              block Thomas on the runs (16 lanes per run, one right-hand column each), the Schur complement on the junctions,
 //              a dense block Cholesky of it (one launch per block column), two triangular solves, back-substitution
 //   update     oplus per free vertex and the per-vertex terms of scaleLambda's sum
-// The partition into runs and junctions is host code (PgoPlan) and needs no device.
+// The partition into runs and junctions (PgoPlan) and getConnectedGraph are host code and need no device: sbm_pgo_plan.hip has
+// them, sbm_pgo.h what the two files share (the rigid-transform arithmetic among it).
 #include <math.h>
 
 #include <cmath>
@@ -18,12 +19,12 @@
 #include <vector>
 
 #include "sbm_handle.h"
+#include "sbm_pgo.h"
 
 #pragma clang fp contract(off)
 
 namespace sbm {
 
-constexpr int kPgoMaxJunctions = 1024;   // the dense Schur complement is (6 * 1024)^2 doubles at most, twice (S and its factor)
 constexpr int kPgoRunLanes = 16;         // lanes per run: 13 right-hand columns, 3 idle
 constexpr int kPgoCols = 13;             // b, the 6 columns towards the left junction, the 6 towards the right one
 
@@ -32,51 +33,7 @@ enum PgoMark { kPgBegin, kPgLinearised, kPgAssembled, kPgSolved, kPgEnd, kPgMark
 static const char* const kPgoNames[] = {"pgo_linearise", "pgo_assemble", "pgo_solve", "pgo_update", "pgo_total"};
 StageTable pgo_stages() { return stage_table<kPgStageCount, kPgMarkCount>(kPgoNames); }
 
-// ---- 3x3 / 6x6 arithmetic, every sum left to right ------------------------------------------------------------------------------
-struct Rt { double R[3][3], t[3]; };
-
-__host__ __device__ static inline double dot3(double a0, double a1, double a2, double b0, double b1, double b2) {
-  return (a0 * b0 + a1 * b1) + a2 * b2;
-}
-__host__ __device__ static inline void mul33(const double A[3][3], const double B[3][3], double C[3][3]) {
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) C[i][j] = dot3(A[i][0], A[i][1], A[i][2], B[0][j], B[1][j], B[2][j]);
-}
-__host__ __device__ static inline void mul3v(const double A[3][3], const double v[3], double o[3]) {
-  for (int i = 0; i < 3; i++) o[i] = dot3(A[i][0], A[i][1], A[i][2], v[0], v[1], v[2]);
-}
-__host__ __device__ static inline Rt load_rt(const double* p) {
-  Rt r;
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) r.R[i][j] = p[4 * i + j];
-    r.t[i] = p[4 * i + 3];
-  }
-  return r;
-}
-__host__ __device__ static inline void store_rt(const Rt& r, double* p) {
-  for (int i = 0; i < 3; i++) {
-    for (int j = 0; j < 3; j++) p[4 * i + j] = r.R[i][j];
-    p[4 * i + 3] = r.t[i];
-  }
-}
-__host__ __device__ static inline Rt inverse(const Rt& a) {
-  Rt r;
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) r.R[i][j] = a.R[j][i];
-  double v[3];
-  mul3v(r.R, a.t, v);
-  for (int i = 0; i < 3; i++) r.t[i] = -v[i];
-  return r;
-}
-__host__ __device__ static inline Rt compose(const Rt& a, const Rt& b) {
-  Rt r;
-  mul33(a.R, b.R, r.R);
-  double v[3];
-  mul3v(a.R, b.t, v);
-  for (int i = 0; i < 3; i++) r.t[i] = v[i] + a.t[i];
-  return r;
-}
-
+// ---- 6x6 arithmetic, every sum left to right (the 3x3 products and Rt are in sbm_pgo.h) --------------------------------------------
 // Eigen's Quaternion(Matrix3), both branches; q = (x, y, z, w)
 __device__ static inline void quat_from_matrix(const double m[3][3], double q[4]) {
   double t = (m[0][0] + m[1][1]) + m[2][2];
@@ -641,160 +598,16 @@ __global__ __launch_bounds__(64) void pgo_update_kernel(int nfree, const int* __
   store_rt(compose(load_rt(P), inc), P);
 }
 
-// ---- the partition: host code, no device ------------------------------------------------------------------------------------------
-struct PgoPlan {
-  int nv = 0, ne = 0, nfree = 0, nslots = 0, nruns = 0, nj = 0, ncoupling = 0, longest = 0;
-  std::vector<int> order;        // sorted position -> caller's vertex position
-  std::vector<int> ids;          // ascending
-  std::vector<int> hidx;         // per sorted vertex: Hessian index, -1 for the fixed one
-  std::vector<int> vfree;        // Hessian index -> sorted vertex
-  std::vector<int> vi, vj;       // per edge: sorted vertex of from / to
-  std::vector<uint8_t> couples;  // per edge
-  std::vector<int> inc_ptr, inc, slot_ptr, slot_edge, slot_rc;   // slot_rc: (row, col) Hessian indices, row > col
-  std::vector<int> sub;          // per Hessian index h: the slot of (h, h - 1) or -1
-  std::vector<int> jpos, jidx, vrun, run_first, run_len, jj;
-  std::vector<int> adj_ptr, adj;  // per Hessian index: its off-diagonal blocks, slot * 2 + (1 when it is the block's column)
-};
-
-// host_arrays: poses, meas and info are host memory and are read; the device forms check ids and topology only
-static int pgo_check(const sbm_pgo_params* p, const sbm_pgo_graph* g, bool host_arrays = true) {
-  if (!p || !g) return SBM_ERR_NULL;
-  if (p->num < 0) return SBM_ERR_SIZE;
-  if (p->coupling != SBM_PGO_COUPLING_REFERENCE && p->coupling != SBM_PGO_COUPLING_SYMMETRIC) return SBM_ERR_UNSUPPORTED;
-  if (p->run_max < 1 || p->run_max > 65536) return SBM_ERR_UNSUPPORTED;
-  if (g->n_vertices <= 0 || g->n_edges < 0) return SBM_ERR_SIZE;              // an empty graph
-  if (!g->ids || !g->poses || (g->n_edges > 0 && (!g->from || !g->to || !g->meas || !g->info))) return SBM_ERR_NULL;
-  for (size_t i = 0; host_arrays && i < 12 * (size_t)g->n_vertices; i++)
-    if (!std::isfinite(g->poses[i])) return SBM_ERR_UNSUPPORTED;
-  for (size_t i = 0; host_arrays && i < 12 * (size_t)g->n_edges; i++)
-    if (!std::isfinite(g->meas[i])) return SBM_ERR_UNSUPPORTED;
-  for (size_t i = 0; host_arrays && i < 36 * (size_t)g->n_edges; i++)
-    if (!std::isfinite(g->info[i])) return SBM_ERR_UNSUPPORTED;
-  try {
-    std::vector<int> ids(g->ids, g->ids + g->n_vertices);
-    std::sort(ids.begin(), ids.end());
-    if (std::adjacent_find(ids.begin(), ids.end()) != ids.end()) return SBM_ERR_SIZE;   // a vertex id given twice
-    if (!std::binary_search(ids.begin(), ids.end(), p->fixed_id)) return SBM_ERR_SIZE;  // an absent fixed_id
-    for (int k = 0; k < g->n_edges; k++) {
-      if (g->from[k] == g->to[k]) return SBM_ERR_UNSUPPORTED;
-      if (!std::binary_search(ids.begin(), ids.end(), g->from[k]) || !std::binary_search(ids.begin(), ids.end(), g->to[k]))
-        return SBM_ERR_SIZE;                                                            // an edge naming an absent vertex
-    }
-  } catch (const std::bad_alloc&) {
-    return SBM_ERR_NOMEM;
-  }
-  return SBM_OK;
-}
-
-// The partition of a checked graph. Junctions: both ends of every coupling between Hessian indices that are not neighbours, and
-// every (run_max + 1)-th vertex of a longer stretch. Runs: the maximal stretches of consecutive indices between junctions.
-static int pgo_make_plan(const sbm_pgo_params* p, const sbm_pgo_graph* g, PgoPlan& P) {
-  try {
-    const int nv = g->n_vertices, ne = g->n_edges;
-    P.nv = nv; P.ne = ne;
-    P.order.resize(nv);
-    for (int i = 0; i < nv; i++) P.order[i] = i;
-    std::sort(P.order.begin(), P.order.end(), [&](int a, int b) { return g->ids[a] < g->ids[b]; });
-    P.ids.resize(nv); P.hidx.resize(nv);
-    for (int i = 0; i < nv; i++) {
-      P.ids[i] = g->ids[P.order[i]];
-      P.hidx[i] = P.ids[i] == p->fixed_id ? -1 : P.nfree++;
-      if (P.hidx[i] >= 0) P.vfree.push_back(i);
-    }
-    const int nf = P.nfree;
-    P.vi.resize(ne); P.vj.resize(ne); P.couples.assign(ne, 0);
-    std::vector<std::vector<int>> inc(nf);
-    std::map<std::pair<int, int>, std::vector<int>> slots;
-    for (int k = 0; k < ne; k++) {
-      P.vi[k] = (int)(std::lower_bound(P.ids.begin(), P.ids.end(), g->from[k]) - P.ids.begin());
-      P.vj[k] = (int)(std::lower_bound(P.ids.begin(), P.ids.end(), g->to[k]) - P.ids.begin());
-      const int hi = P.hidx[P.vi[k]], hj = P.hidx[P.vj[k]];
-      if (hi >= 0) inc[hi].push_back(2 * k);
-      if (hj >= 0) inc[hj].push_back(2 * k + 1);
-      // the one off-diagonal block, at (to, from): SimplicialLDLT reads it only from the lower triangle; where `to` is fixed
-      // the reference forms a negative index, here the coupling is dropped
-      const bool both = hi >= 0 && hj >= 0;
-      if (both && (hj > hi || p->coupling == SBM_PGO_COUPLING_SYMMETRIC)) {
-        P.couples[k] = 1;
-        P.ncoupling++;
-        if (hj > hi) slots[{hj, hi}].push_back(2 * k);        // m^T
-        else slots[{hi, hj}].push_back(2 * k + 1);            // mirrored from the upper triangle: m
-      }
-    }
-    P.inc_ptr.assign(nf + 1, 0);
-    for (int h = 0; h < nf; h++) {
-      P.inc_ptr[h + 1] = P.inc_ptr[h] + (int)inc[h].size();
-      P.inc.insert(P.inc.end(), inc[h].begin(), inc[h].end());
-    }
-    P.sub.assign(nf, -1);
-    P.jpos.assign(nf, -1);
-    P.slot_ptr.push_back(0);
-    for (const auto& s : slots) {
-      const int r = s.first.first, c = s.first.second;
-      if (r - c == 1) P.sub[r] = P.nslots;
-      else P.jpos[r] = P.jpos[c] = 0;                          // marked; numbered below
-      P.slot_rc.push_back(r); P.slot_rc.push_back(c);
-      P.slot_edge.insert(P.slot_edge.end(), s.second.begin(), s.second.end());
-      P.slot_ptr.push_back((int)P.slot_edge.size());
-      P.nslots++;
-    }
-    int streak = 0;
-    for (int h = 0; h < nf; h++) {
-      if (P.jpos[h] >= 0) { streak = 0; continue; }
-      if (++streak > p->run_max) { P.jpos[h] = 0; streak = 0; }
-    }
-    P.vrun.assign(nf, -1);
-    for (int h = 0; h < nf; h++) {
-      if (P.jpos[h] >= 0) { P.jpos[h] = P.nj++; P.jidx.push_back(h); continue; }
-      if (h == 0 || P.jpos[h - 1] >= 0) { P.run_first.push_back(h); P.run_len.push_back(0); P.nruns++; }
-      P.vrun[h] = P.nruns - 1;
-      P.longest = std::max(P.longest, ++P.run_len.back());
-    }
-    std::vector<std::vector<int>> adj(nf);
-    for (int s = 0; s < P.nslots; s++) {
-      adj[P.slot_rc[2 * s]].push_back(2 * s);
-      adj[P.slot_rc[2 * s + 1]].push_back(2 * s + 1);
-    }
-    P.adj_ptr.assign(nf + 1, 0);
-    for (int h = 0; h < nf; h++) {
-      P.adj_ptr[h + 1] = P.adj_ptr[h] + (int)adj[h].size();
-      P.adj.insert(P.adj.end(), adj[h].begin(), adj[h].end());
-    }
-    for (int s = 0; s < P.nslots; s++) {
-      const int r = P.slot_rc[2 * s], c = P.slot_rc[2 * s + 1];
-      if (P.jpos[r] >= 0 && P.jpos[c] >= 0) { P.jj.push_back(s); P.jj.push_back(P.jpos[r]); P.jj.push_back(P.jpos[c]); }
-    }
-  } catch (const std::bad_alloc&) {
-    return SBM_ERR_NOMEM;
-  }
-  return P.nj > kPgoMaxJunctions ? SBM_ERR_UNSUPPORTED : SBM_OK;
-}
-
-static void pgo_plan_info(const PgoPlan& P, sbm_pgo_plan_info* o) {
-  o->n_free = P.nfree; o->n_runs = P.nruns; o->n_junctions = P.nj; o->schur_size = 6 * P.nj; o->n_coupling = P.ncoupling;
-  o->longest_run = P.longest; o->n_slots = P.nslots; o->max_junctions = kPgoMaxJunctions;
-}
-
 // ---- one optimisation on the device ------------------------------------------------------------------------------------------------
-template <class T> static hipError_t upload(DevBuf& b, size_t& off, const std::vector<T>& v, hipStream_t s, T** out) {
-  off = (off + 15) & ~(size_t)15;
-  *out = (T*)((char*)b.p + off);
-  const size_t n = v.size() * sizeof(T);
-  off += n;
-  return n ? hipMemcpyAsync(*out, v.data(), n, hipMemcpyHostToDevice, s) : hipSuccess;
-}
-static size_t padded(size_t n) { return (n + 15) & ~(size_t)15; }
-
 struct PgoDev {   // where the pieces of one call lie in the handle's buffers
-  int *vi, *vj, *hidx, *inc_ptr, *inc, *slot_ptr, *slot_edge, *sub, *jpos, *jidx, *vrun, *run_first, *run_len, *jj, *vfree, *adj_ptr, *adj, *slot_rc;
+  int *vi, *vj, *hidx, *inc_ptr, *inc, *slot_ptr, *slot_edge, *sub, *jpos, *jidx, *vrun, *run_first, *run_len, *jj, *vfree, *adj_ptr, *adj, *slot_rc, *order;
   double *poses, *meas, *info, *rec, *chi, *scal, *D, *bv, *Eoff, *Gs, *Ws, *Y, *x, *dotp, *S, *L, *xj, *rv;
 };
 
-// num iterations of HyperGraph::optimize on poses (sorted order, in place), then computeActiveErrors. edge_chi (may be null)
-// receives the final per-edge chi2. Edges arrive as the plan's vi / vj with meas / info in edge order.
-// The device form's arrays: poses in the caller's vertex order, measurements and information in edge order, and where the
-// optimised poses go (ascending id order).
-struct PgoDevIO { const double *poses, *meas, *info; double* poses_out; };
+// Where one optimisation reads its arrays and leaves its poses. Host memory: poses in ascending id order. The caller's device
+// memory: poses in the caller's vertex order (the gather kernel sorts them). Measurements and information in edge order; the
+// optimised poses go to poses_out in ascending id order.
+struct PgoIO { const double *poses, *meas, *info; double* poses_out; bool device; };
 
 __global__ __launch_bounds__(64) void pgo_gather_poses_kernel(int nv, const int* __restrict__ order, const double* __restrict__ src,
                                                                double* __restrict__ dst) {
@@ -803,81 +616,62 @@ __global__ __launch_bounds__(64) void pgo_gather_poses_kernel(int nv, const int*
   dst[t] = src[12 * (size_t)order[t / 12] + t % 12];
 }
 
-// With io the arrays are the caller's device memory (poses / meas / info are then ignored and may be null).
-static int pgo_optimize(sbm_handle* h, const PgoPlan& P, int num, double* poses, const double* meas, const double* info,
-                        double* err, double* edge_chi, const PgoDevIO* io = nullptr) {
+// num iterations of HyperGraph::optimize on the poses of io, then computeActiveErrors. edge_chi (host memory, may be null)
+// receives the final per-edge chi2. Edges arrive as the plan's vi / vj with meas / info in edge order.
+static int pgo_optimize(sbm_handle* h, const PgoPlan& P, int num, const PgoIO& io, double* err, double* edge_chi) {
   StageClock& clk = h->pgo.clock;
   hipStream_t s = h->stream;
   HIPCHK(h, clk.start(pgo_stages(), h->profiling != 0));
   const int nv = P.nv, ne = P.ne, nf = P.nfree, nj = P.nj;
-  const size_t nints = padded(4 * (P.vi.size() + P.vj.size() + P.hidx.size() + P.inc_ptr.size() + P.inc.size() + P.slot_ptr.size() +
-                                   P.slot_edge.size() + P.sub.size() + P.jpos.size() + P.jidx.size() + P.vrun.size() +
-                                   P.run_first.size() + P.run_len.size() + P.jj.size() + P.vfree.size() + P.adj_ptr.size() + P.adj.size() +
-                                   P.slot_rc.size() + P.order.size()) + 16 * 20);
-  HIPCHK(h, h->pgo.graph.grow(nints + 8 * (12 * (size_t)nv + 48 * (size_t)ne), s));
-  HIPCHK(h, h->pgo.edge.grow(8 * ((size_t)(kRec + 1) * std::max(ne, 1) + 8), s));
-  const size_t nsys = 36 * (size_t)nf * 3 + 36 * (size_t)std::max(P.nslots, 1) + (size_t)nf * (6 + kPgoCols * 6 + 6 + 1 + 6) + 6 * (size_t)nj + 8;
-  HIPCHK(h, h->pgo.sys.grow(8 * nsys, s));
   const size_t nS = blk(nj, 0);
-  HIPCHK(h, h->pgo.schur.grow(8 * 2 * std::max(nS, (size_t)36), s));
+  // before any buffer is replaced: a call that fails below leaves nothing for sbm_pgo_debug_fetch to copy from
+  h->pgo.last = PgoLast{ne, nf, P.nslots, nj, P.nruns, 0, 0.0, PgoDebug{}};
   PgoDev d;
-  size_t off = 0;
-  DevBuf& gb = h->pgo.graph;
-  HIPCHK(h, upload(gb, off, P.vi, s, &d.vi));
-  HIPCHK(h, upload(gb, off, P.vj, s, &d.vj));
-  HIPCHK(h, upload(gb, off, P.hidx, s, &d.hidx));
-  HIPCHK(h, upload(gb, off, P.inc_ptr, s, &d.inc_ptr));
-  HIPCHK(h, upload(gb, off, P.inc, s, &d.inc));
-  HIPCHK(h, upload(gb, off, P.slot_ptr, s, &d.slot_ptr));
-  HIPCHK(h, upload(gb, off, P.slot_edge, s, &d.slot_edge));
-  HIPCHK(h, upload(gb, off, P.sub, s, &d.sub));
-  HIPCHK(h, upload(gb, off, P.jpos, s, &d.jpos));
-  HIPCHK(h, upload(gb, off, P.jidx, s, &d.jidx));
-  HIPCHK(h, upload(gb, off, P.vrun, s, &d.vrun));
-  HIPCHK(h, upload(gb, off, P.run_first, s, &d.run_first));
-  HIPCHK(h, upload(gb, off, P.run_len, s, &d.run_len));
-  HIPCHK(h, upload(gb, off, P.jj, s, &d.jj));
-  HIPCHK(h, upload(gb, off, P.vfree, s, &d.vfree));
-  HIPCHK(h, upload(gb, off, P.adj_ptr, s, &d.adj_ptr));
-  HIPCHK(h, upload(gb, off, P.adj, s, &d.adj));
-  HIPCHK(h, upload(gb, off, P.slot_rc, s, &d.slot_rc));
-  int* d_order = nullptr;
-  HIPCHK(h, upload(gb, off, P.order, s, &d_order));
-  d.poses = (double*)((char*)gb.p + nints);
-  d.meas = d.poses + 12 * (size_t)nv;
-  d.info = d.meas + 12 * (size_t)ne;
-  if (io) {
-    hipLaunchKernelGGL(pgo_gather_poses_kernel, dim3((nv * 12 + 63) / 64), dim3(64), 0, s, nv, d_order, io->poses, d.poses);
+  HIPCHK(h, carve(h->pgo.graph, s, [&](Carve& c) {
+    P.each_index(d, [&](const std::vector<int>& v, int*& p) { p = c.take<int>(v.size()); });
+    d.poses = c.take<double>(12 * (size_t)nv);
+    d.meas = c.take<double>(12 * (size_t)ne);
+    d.info = c.take<double>(36 * (size_t)ne);
+  }));
+  HIPCHK(h, carve(h->pgo.edge, s, [&](Carve& c) {
+    d.scal = c.take<double>(8);          // chi2, scaleLambda's sum, max_diag
+    d.chi = c.take<double>(std::max(ne, 1));
+    d.rec = c.take<double>((size_t)kRec * std::max(ne, 1));
+  }));
+  HIPCHK(h, carve(h->pgo.sys, s, [&](Carve& c) {
+    d.D = c.take<double>(36 * (size_t)nf);
+    d.Gs = c.take<double>(36 * (size_t)nf);
+    d.Ws = c.take<double>(36 * (size_t)nf);
+    d.Eoff = c.take<double>(36 * (size_t)std::max(P.nslots, 1));
+    d.bv = c.take<double>(6 * (size_t)nf);
+    d.Y = c.take<double>((size_t)nf * kPgoCols * 6);
+    d.x = c.take<double>(6 * (size_t)nf);
+    d.dotp = c.take<double>(nf);
+    d.xj = c.take<double>(6 * (size_t)nj);
+    d.rv = c.take<double>(6 * (size_t)nf);
+  }));
+  HIPCHK(h, carve(h->pgo.schur, s, [&](Carve& c) {
+    d.S = c.take<double>(std::max(nS, (size_t)36));
+    d.L = c.take<double>(std::max(nS, (size_t)36));
+  }));
+  hipError_t up = hipSuccess;
+  P.each_index(d, [&](const std::vector<int>& v, int* p) {
+    if (up == hipSuccess && !v.empty()) up = hipMemcpyAsync(p, v.data(), 4 * v.size(), hipMemcpyHostToDevice, s);
+  });
+  HIPCHK(h, up);
+  const hipMemcpyKind in = io.device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                      out = io.device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  if (io.device) {
+    hipLaunchKernelGGL(pgo_gather_poses_kernel, dim3((nv * 12 + 63) / 64), dim3(64), 0, s, nv, d.order, io.poses, d.poses);
     HIPCHK(h, hipGetLastError());
-    if (ne) {
-      HIPCHK(h, hipMemcpyAsync(d.meas, io->meas, 96 * (size_t)ne, hipMemcpyDeviceToDevice, s));
-      HIPCHK(h, hipMemcpyAsync(d.info, io->info, 288 * (size_t)ne, hipMemcpyDeviceToDevice, s));
-    }
   } else {
-    HIPCHK(h, hipMemcpyAsync(d.poses, poses, 96 * (size_t)nv, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(d.poses, io.poses, 96 * (size_t)nv, in, s));
   }
-  if (ne && !io) {
-    HIPCHK(h, hipMemcpyAsync(d.meas, meas, 96 * (size_t)ne, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(d.info, info, 288 * (size_t)ne, hipMemcpyHostToDevice, s));
+  if (ne) {
+    HIPCHK(h, hipMemcpyAsync(d.meas, io.meas, 96 * (size_t)ne, in, s));
+    HIPCHK(h, hipMemcpyAsync(d.info, io.info, 288 * (size_t)ne, in, s));
   }
-  d.scal = h->pgo.edge.as<double>();          // chi2, scaleLambda's sum, max_diag
-  d.chi = d.scal + 8;
-  d.rec = d.chi + std::max(ne, 1);
-  d.D = h->pgo.sys.as<double>();
-  d.Gs = d.D + 36 * (size_t)nf;
-  d.Ws = d.Gs + 36 * (size_t)nf;
-  d.Eoff = d.Ws + 36 * (size_t)nf;
-  d.bv = d.Eoff + 36 * (size_t)std::max(P.nslots, 1);
-  d.Y = d.bv + 6 * (size_t)nf;
-  d.x = d.Y + (size_t)nf * kPgoCols * 6;
-  d.dotp = d.x + 6 * (size_t)nf;
-  d.xj = d.dotp + nf;
-  d.rv = d.xj + 6 * (size_t)nj;
-  d.S = h->pgo.schur.as<double>();
-  d.L = d.S + std::max(nS, (size_t)36);
   HIPCHK(h, hipMemsetAsync(d.scal, 0, 64, s));
-  h->pgo.dev = PgoDebug{};
-  h->pgo.last = PgoLast{ne, nf, P.nslots, nj, P.nruns, 0, 0.0};
   double scal[3] = {0, 0, 0}, lambda = 0.0, chi_prev = 0.0, dot_prev = 0.0;
   const dim3 b64(64);
   for (int it = 0; it < num && nf > 0; it++) {
@@ -968,127 +762,49 @@ static int pgo_optimize(sbm_handle* h, const PgoPlan& P, int num, double* poses,
   hipLaunchKernelGGL(pgo_reduce_kernel, dim3(1), dim3(256), 0, s, d.chi, ne, d.scal);
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(scal, d.scal, sizeof(scal), hipMemcpyDeviceToHost, s));
-  if (io) HIPCHK(h, hipMemcpyAsync(io->poses_out, d.poses, 96 * (size_t)nv, hipMemcpyDeviceToDevice, s));
-  else HIPCHK(h, hipMemcpyAsync(poses, d.poses, 96 * (size_t)nv, hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipMemcpyAsync(io.poses_out, d.poses, 96 * (size_t)nv, out, s));
   if (edge_chi && ne) HIPCHK(h, hipMemcpyAsync(edge_chi, d.chi, 8 * (size_t)ne, hipMemcpyDeviceToHost, s));
   HIPCHK(h, hipStreamSynchronize(s));
   *err = scal[0];
-  h->pgo.dev = PgoDebug{d.rec, d.D, d.Eoff, d.bv, d.x};
+  h->pgo.last.dev = PgoDebug{d.rec, d.D, d.Eoff, d.bv, d.x};
   return SBM_OK;
-}
-
-// getConnectedGraph as written, on links in the caller's multimap order (keyed by `from`). Propagation in double.
-struct PgoLinks { std::vector<int> from, to; std::vector<double> meas, info; };
-static void pgo_connected(int from_id, const std::map<int, Rt>& in, const PgoLinks& lin, std::map<int, Rt>& out, std::vector<int>& kept) {
-  out.clear(); kept.clear();
-  std::multimap<int, int> bi, by_from;   // by_from: from -> link index, in order
-  const int n = (int)lin.from.size();
-  for (int k = 0; k < n; k++) {
-    bi.insert({lin.from[k], lin.to[k]});
-    bi.insert({lin.to[k], lin.from[k]});
-    by_from.insert({lin.from[k], k});
-  }
-  auto find = [&](const std::multimap<int, int>& idx, int a, int b) {
-    for (auto r = idx.equal_range(a); r.first != r.second; ++r.first)
-      if (lin.to[r.first->second] == b) return r.first->second;
-    for (auto r = idx.equal_range(b); r.first != r.second; ++r.first)
-      if (lin.to[r.first->second] == a) return r.first->second;
-    return -1;
-  };
-  std::multimap<int, int> kept_by_from;
-  std::map<int, bool> pending;   // an ordered set
-  pending[from_id] = true;
-  while (!pending.empty()) {
-    const int cur = pending.rbegin()->first;
-    pending.erase(cur);
-    if (out.empty()) out.insert({cur, in.find(cur)->second});
-    for (auto r = bi.equal_range(cur); r.first != r.second; ++r.first) {
-      const int to = r.first->second;
-      const int k = find(by_from, cur, to);
-      if (pending.count(to)) continue;
-      if (!out.count(to)) {
-        const Rt T = load_rt(&lin.meas[12 * (size_t)k]);
-        out.insert({to, lin.from[k] == cur ? compose(out.at(cur), T) : compose(out.at(cur), inverse(T))});
-        pending[to] = true;
-      }
-      if (find(kept_by_from, cur, to) < 0) kept_by_from.insert({lin.from[k], k});
-    }
-  }
-  for (const auto& kv : kept_by_from) kept.push_back(kv.second);   // the out-multimap's order: by from, insertion order among equals
 }
 
 }  // namespace sbm
 
 using namespace sbm;
 
-extern "C" {
-
-void sbm_pgo_params_default(sbm_pgo_params* p) {
-  if (!p) return;
-  memset(p, 0, sizeof(*p));
-  p->num = 20;
-  p->fixed_id = 1;
-  p->coupling = SBM_PGO_COUPLING_REFERENCE;
-  p->run_max = 64;
-}
-
-int sbm_pgo_params_check(const sbm_pgo_params* p, const sbm_pgo_graph* g) { return pgo_check(p, g); }
-
-int sbm_pgo_plan(const sbm_pgo_params* p, const sbm_pgo_graph* g, sbm_pgo_plan_info* info, int32_t* vertex_run, int32_t* slot_rc,
-                 uint8_t* edge_couples) {
-  if (!info) return SBM_ERR_NULL;
-  int st = pgo_check(p, g);
-  if (st != SBM_OK) return st;
-  PgoPlan P;
-  st = pgo_make_plan(p, g, P);
-  if (st != SBM_OK && st != SBM_ERR_UNSUPPORTED) return st;
-  pgo_plan_info(P, info);
-  if (vertex_run) std::copy(P.vrun.begin(), P.vrun.end(), vertex_run);
-  if (slot_rc) std::copy(P.slot_rc.begin(), P.slot_rc.end(), slot_rc);
-  if (edge_couples) std::copy(P.couples.begin(), P.couples.end(), edge_couples);
-  return st;
-}
-
-int sbm_pgo_optimize(sbm_handle* h, const sbm_pgo_params* p, const sbm_pgo_graph* g, double* poses_out, double* err) {
+// runOptimize on the graph's arrays, host memory or (device) the caller's device memory: check, plan, optimise, and the plan for
+// sbm_pgo_last_plan. The host form's poses go up in ascending id order.
+static int pgo_run(sbm_handle* h, const sbm_pgo_params* p, const sbm_pgo_graph* g, bool device, double* poses_out, double* err) {
   if (!h || !poses_out || !err) return SBM_ERR_NULL;
-  int st = pgo_check(p, g);
+  int st = pgo_check(p, g, !device);
   if (st != SBM_OK) return st;
   try {
     PgoPlan P;
     st = pgo_make_plan(p, g, P);
     if (st != SBM_OK) return st;
-    std::vector<double> poses(12 * (size_t)P.nv);
-    for (int i = 0; i < P.nv; i++) memcpy(&poses[12 * (size_t)i], g->poses + 12 * (size_t)P.order[i], 96);
+    std::vector<double> sorted(device ? 0 : 12 * (size_t)P.nv);
+    for (int i = 0; !device && i < P.nv; i++) memcpy(&sorted[12 * (size_t)i], g->poses + 12 * (size_t)P.order[i], 96);
     DeviceScope dscope(h->device);
     HIPCHK(h, dscope.enter());
-    st = pgo_optimize(h, P, p->num, poses.data(), g->meas, g->info, err, nullptr);
+    st = pgo_optimize(h, P, p->num, PgoIO{device ? g->poses : sorted.data(), g->meas, g->info, poses_out, device}, err, nullptr);
     if (st != SBM_OK) return st;
     pgo_plan_info(P, &h->pgo.plan);
-    memcpy(poses_out, poses.data(), 96 * (size_t)P.nv);
   } catch (const std::bad_alloc&) {
     return SBM_ERR_NOMEM;
   }
   return SBM_OK;
+}
+
+extern "C" {
+
+int sbm_pgo_optimize(sbm_handle* h, const sbm_pgo_params* p, const sbm_pgo_graph* g, double* poses_out, double* err) {
+  return pgo_run(h, p, g, false, poses_out, err);
 }
 
 int sbm_pgo_optimize_device(sbm_handle* h, const sbm_pgo_params* p, const sbm_pgo_graph* g, void* d_poses_out, double* err) {
-  if (!h || !d_poses_out || !err) return SBM_ERR_NULL;
-  int st = pgo_check(p, g, false);
-  if (st != SBM_OK) return st;
-  try {
-    PgoPlan P;
-    st = pgo_make_plan(p, g, P);
-    if (st != SBM_OK) return st;
-    DeviceScope dscope(h->device);
-    HIPCHK(h, dscope.enter());
-    const PgoDevIO io = {g->poses, g->meas, g->info, (double*)d_poses_out};
-    st = pgo_optimize(h, P, p->num, nullptr, nullptr, nullptr, err, nullptr, &io);
-    if (st != SBM_OK) return st;
-    pgo_plan_info(P, &h->pgo.plan);
-  } catch (const std::bad_alloc&) {
-    return SBM_ERR_NOMEM;
-  }
-  return SBM_OK;
+  return pgo_run(h, p, g, true, (double*)d_poses_out, err);
 }
 
 // The robust loop propagates poses on the host, so poses and measurements come home once; every iteration is the host form's.
@@ -1144,12 +860,7 @@ int sbm_pgo_optimize_robust(sbm_handle* h, const sbm_pgo_params* p, const sbm_pg
       std::vector<int> kept;
       pgo_connected(p->fixed_id, in, alive, out, kept);
       PgoLinks sel;
-      for (int k : kept) {
-        sel.from.push_back(alive.from[k]);
-        sel.to.push_back(alive.to[k]);
-        sel.meas.insert(sel.meas.end(), &alive.meas[12 * (size_t)k], &alive.meas[12 * (size_t)k] + 12);
-        sel.info.insert(sel.info.end(), &alive.info[36 * (size_t)k], &alive.info[36 * (size_t)k] + 36);
-      }
+      for (int k : kept) sel.append(alive, (size_t)k);
       std::vector<int> ids;
       std::vector<double> poses0;
       for (const auto& kv : out) {
@@ -1162,9 +873,9 @@ int sbm_pgo_optimize_robust(sbm_handle* h, const sbm_pgo_params* p, const sbm_pg
       PgoPlan P;
       st = pgo_make_plan(p, &sg, P);
       if (st != SBM_OK) return st;
-      std::vector<double> poses(poses0), chi(sel.from.size() + 1);
+      std::vector<double> poses5(poses0.size()), chi(sel.size() + 1);
       double e5;
-      st = pgo_optimize(h, P, 5, poses.data(), sel.meas.data(), sel.info.data(), &e5, chi.data());
+      st = pgo_optimize(h, P, 5, PgoIO{poses0.data(), sel.meas.data(), sel.info.data(), poses5.data(), false}, &e5, chi.data());
       if (st != SBM_OK) return st;
       int worst = -1;
       double werr = 0;
@@ -1173,26 +884,19 @@ int sbm_pgo_optimize_robust(sbm_handle* h, const sbm_pgo_params* p, const sbm_pg
         if (a != b + 1 && b != a + 1 && chi[k] >= 10.0 && chi[k] > werr) { worst = (int)k; werr = chi[k]; }
       }
       if (worst < 0) {   // runOptimize from the re-propagated poses, not from the five-iteration result
-        poses = poses0;
-        st = pgo_optimize(h, P, p->num, poses.data(), sel.meas.data(), sel.info.data(), err, nullptr);
+        st = pgo_optimize(h, P, p->num, PgoIO{poses0.data(), sel.meas.data(), sel.info.data(), poses_out, false}, err, nullptr);
         if (st != SBM_OK) return st;
         pgo_plan_info(P, &h->pgo.plan);
         *n_out = (int32_t)ids.size();
         memcpy(ids_out, ids.data(), 4 * ids.size());
-        memcpy(poses_out, poses.data(), 8 * poses.size());
         return SBM_OK;
       }
       const int a = sel.from[(size_t)worst], b = sel.to[(size_t)worst];
       if (*n_removed < removed_cap) { removed[2 * *n_removed] = a; removed[2 * *n_removed + 1] = b; }
       ++*n_removed;
       PgoLinks next;
-      for (size_t k = 0; k < sel.from.size(); k++) {
-        if (sel.from[k] == a && sel.to[k] == b) continue;   // every link with that (from, to)
-        next.from.push_back(sel.from[k]);
-        next.to.push_back(sel.to[k]);
-        next.meas.insert(next.meas.end(), &sel.meas[12 * k], &sel.meas[12 * k] + 12);
-        next.info.insert(next.info.end(), &sel.info[36 * k], &sel.info[36 * k] + 36);
-      }
+      for (size_t k = 0; k < sel.size(); k++)
+        if (sel.from[k] != a || sel.to[k] != b) next.append(sel, k);   // every link with that (from, to) goes
       alive = std::move(next);
     }
   } catch (const std::bad_alloc&) {
@@ -1210,16 +914,16 @@ int sbm_pgo_last_plan(sbm_handle* h, sbm_pgo_plan_info* info, double* lambda, in
 
 int sbm_pgo_debug_fetch(sbm_handle* h, int which, void* dst, size_t dst_bytes) {
   if (!h || !dst) return SBM_ERR_NULL;
-  if (!h->pgo.dev.rec) return SBM_ERR_UNSUPPORTED;
   const auto& L = h->pgo.last;
+  if (!L.dev.rec) return SBM_ERR_UNSUPPORTED;
   const void* src = nullptr;
   size_t n = 0;
   switch (which) {
-    case SBM_PGO_DEBUG_EDGES: src = h->pgo.dev.rec; n = 8 * (size_t)kRec * L.ne; break;
-    case SBM_PGO_DEBUG_DIAG: src = h->pgo.dev.D; n = 288 * (size_t)L.nfree; break;
-    case SBM_PGO_DEBUG_OFFDIAG: src = h->pgo.dev.Eoff; n = 288 * (size_t)L.nslots; break;
-    case SBM_PGO_DEBUG_B: src = h->pgo.dev.bv; n = 48 * (size_t)L.nfree; break;
-    case SBM_PGO_DEBUG_X: src = h->pgo.dev.x; n = 48 * (size_t)L.nfree; break;
+    case SBM_PGO_DEBUG_EDGES: src = L.dev.rec; n = 8 * (size_t)kRec * L.ne; break;
+    case SBM_PGO_DEBUG_DIAG: src = L.dev.D; n = 288 * (size_t)L.nfree; break;
+    case SBM_PGO_DEBUG_OFFDIAG: src = L.dev.Eoff; n = 288 * (size_t)L.nslots; break;
+    case SBM_PGO_DEBUG_B: src = L.dev.bv; n = 48 * (size_t)L.nfree; break;
+    case SBM_PGO_DEBUG_X: src = L.dev.x; n = 48 * (size_t)L.nfree; break;
     default: return SBM_ERR_UNSUPPORTED;
   }
   if (dst_bytes < n) return SBM_ERR_SIZE;

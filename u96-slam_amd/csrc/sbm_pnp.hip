@@ -59,30 +59,28 @@ struct Slice {
   int* n;       // 4
 };
 
-__host__ __device__ inline size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 __host__ __device__ inline size_t slice_bytes(int cap, int iters) {
   const size_t c = (size_t)cap, c1 = c + 1;
-  return al16(c * 12) + al16(c * 8) + 2 * al16(c * 4) + al16((size_t)iters * 24) + al16((size_t)iters * 96) +
-         al16((size_t)iters * 4) + 5 * al16(c1 * 4) + 16;
+  return pad16(c * 12) + pad16(c * 8) + 2 * pad16(c * 4) + pad16((size_t)iters * 24) + pad16((size_t)iters * 96) +
+         pad16((size_t)iters * 4) + 5 * pad16(c1 * 4) + 16;
 }
 
 __host__ __device__ inline Slice slice_at(char* base, int job, int cap, int iters) {
   char* p = base + (size_t)job * slice_bytes(cap, iters);
   const size_t c = (size_t)cap, c1 = c + 1;
   Slice s;
-  s.X = (float*)p; p += al16(c * 12);
-  s.U = (float*)p; p += al16(c * 8);
-  s.mt = (int*)p; p += al16(c * 4);
-  s.tt = (int*)p; p += al16(c * 4);
-  s.sub = (int*)p; p += al16((size_t)iters * 24);
-  s.hR = (double*)p; p += al16((size_t)iters * 96);
-  s.cnt = (int*)p; p += al16((size_t)iters * 4);
-  s.setA = (int*)p; p += al16(c1 * 4);
-  s.setB = (int*)p; p += al16(c1 * 4);
-  s.err = (float*)p; p += al16(c1 * 4);
-  s.cd = (float*)p; p += al16(c1 * 4);
-  s.ca = (float*)p; p += al16(c1 * 4);
+  s.X = (float*)p; p += pad16(c * 12);
+  s.U = (float*)p; p += pad16(c * 8);
+  s.mt = (int*)p; p += pad16(c * 4);
+  s.tt = (int*)p; p += pad16(c * 4);
+  s.sub = (int*)p; p += pad16((size_t)iters * 24);
+  s.hR = (double*)p; p += pad16((size_t)iters * 96);
+  s.cnt = (int*)p; p += pad16((size_t)iters * 4);
+  s.setA = (int*)p; p += pad16(c1 * 4);
+  s.setB = (int*)p; p += pad16(c1 * 4);
+  s.err = (float*)p; p += pad16(c1 * 4);
+  s.cd = (float*)p; p += pad16(c1 * 4);
+  s.ca = (float*)p; p += pad16(c1 * 4);
   s.n = (int*)p;
   return s;
 }
@@ -575,17 +573,17 @@ int sbm_estimate_motion(sbm_handle* h, const float* xyz_from, int nf, const floa
   if (st != SBM_OK) return st;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
-  // xyz 2 frames, kpts 2 frames, counts (2) + npairs (1) + pad, pairs, result, inliers
-  const size_t bx = al16((size_t)2 * cap * 12), bk = al16((size_t)2 * cap * 8), bp = al16((size_t)cap * 8);
-  const size_t br = al16(sizeof(sbm_pnp_result)), bi = al16((size_t)cap * 4);
-  HIPCHK(h, h->pnp.io.grow(bx + bk + 16 + bp + br + bi, h->stream));
-  char* io = h->pnp.io.as<char>();
-  float* d_xyz = (float*)io;
-  float* d_kp = (float*)(io + bx);
-  int* d_n = (int*)(io + bx + bk);
-  int* d_pairs = (int*)(io + bx + bk + 16);
-  sbm_pnp_result* d_res = (sbm_pnp_result*)(io + bx + bk + 16 + bp);
-  int* d_inl = (int*)(io + bx + bk + 16 + bp + br);
+  float *d_xyz = nullptr, *d_kp = nullptr;
+  int *d_n = nullptr, *d_pairs = nullptr, *d_inl = nullptr;
+  sbm_pnp_result* d_res = nullptr;
+  HIPCHK(h, carve(h->pnp.io, h->stream, [&](Carve& c) {
+    d_xyz = c.take<float>((size_t)2 * cap * 3);   // 2 frames
+    d_kp = c.take<float>((size_t)2 * cap * 2);    // 2 frames
+    d_n = c.take<int>(4);                         // counts (2) + npairs (1) + pad
+    d_pairs = c.take<int>((size_t)cap * 2);
+    d_res = c.take<sbm_pnp_result>(1);
+    d_inl = c.take<int>(cap);
+  }));
   const int cnt[3] = {nf, nt, npairs};
   if (nf > 0) HIPCHK(h, hipMemcpyAsync(d_xyz, xyz_from, (size_t)nf * 12, hipMemcpyHostToDevice, h->stream));
   if (nt > 0) {
