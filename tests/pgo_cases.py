@@ -326,7 +326,9 @@ def optimize(g, num, trace=None):
         x = solve_lower(A, b, lam)
         tr["lam"].append(lam), tr["chi"].append(chi)
         tr.update(A=A, b=b, x=x, lin=lin)
-        tr["identity"] = bool(tr["identity"] or g.apply(x).any())
+        ident = bool(g.apply(x).any())                     # every iteration applies its update, whatever the earlier ones took
+        tr.setdefault("ident_its", []).append(ident)
+        tr["identity"] = bool(tr["identity"] or ident)
         dot = float(np.sum(x * (lam * x + b)))
         lam *= scale_lambda(dot, chi, float(np.sum(g.errors()[1])))
     return float(np.sum(g.errors()[1]))
@@ -384,8 +386,10 @@ def connected_graph(from_id, ids, poses, frm, to, meas):
     return np.array(oid, np.int64), np.stack([out[v] for v in oid]), np.array(kept, np.int64)
 
 
-def run_optimize_robust(ids, poses, frm, to, meas, info, num, fixed_id=1, coupling=REFERENCE):
-    """runOptimizeRobust. Returns (err, ids, poses, removed) with removed the (from, to) pairs in the order they were dropped."""
+def run_optimize_robust(ids, poses, frm, to, meas, info, num, fixed_id=1, coupling=REFERENCE, rounds=None):
+    """runOptimizeRobust. Returns (err, ids, poses, removed) with removed the (from, to) pairs in the order they were dropped.
+    rounds (a list) receives one (from, to, chi2) triple of arrays per round: every link of that round's graph after its five
+    iterations, the numbers the round decides on."""
     frm, to = np.asarray(frm, np.int64), np.asarray(to, np.int64)
     meas, info = np.asarray(meas, np.float64).reshape(-1, 3, 4), np.asarray(info, np.float64).reshape(-1, 6, 6)
     alive = np.arange(len(frm))
@@ -396,6 +400,8 @@ def run_optimize_robust(ids, poses, frm, to, meas, info, num, fixed_id=1, coupli
         g = Graph(oid, oposes, frm[sel], to[sel], meas[sel], info[sel], fixed_id, coupling)
         optimize(g, 5)
         chi = g.errors()[1]
+        if rounds is not None:
+            rounds.append((frm[sel].copy(), to[sel].copy(), chi.copy()))
         worst, werr = -1, 0.0
         for k in range(len(sel)):
             a, b = int(frm[sel[k]]), int(to[sel[k]])
@@ -484,6 +490,68 @@ def args(c):
     return c["ids"], c["poses"], c["frm"], c["to"], c["meas"], c["info"]
 
 
+def fixed(c):
+    """The fixed vertex a graph asks for: its own `fixed_id` where it carries one, else 1."""
+    return int(c.get("fixed_id", 1))
+
+
+# ---- builders over a graph: each returns a new graph with its links in multimap order (by `from`, stable) ----------------------
+def _with_links(c, frm, to, meas, info):
+    frm, to = np.asarray(frm, np.int64), np.asarray(to, np.int64)
+    order = np.argsort(frm, kind="stable")
+    out = dict(c, ids=np.array(c["ids"]), poses=np.array(c["poses"]), frm=frm[order], to=to[order],
+               meas=np.asarray(meas, np.float64)[order].copy(), info=np.asarray(info, np.float64)[order].copy())
+    return out
+
+
+def _inverse_meas(meas):
+    return join(*inverse(*split(meas)))
+
+
+def bidirectional(c):
+    """Every link also reversed, with the inverse measurement and the same information, as the reference's mapper stores them
+    (link_forward and link_reverse of the odometry path; addLink's inverse at the other node)."""
+    return _with_links(c, np.concatenate([c["frm"], c["to"]]), np.concatenate([c["to"], c["frm"]]),
+                       np.concatenate([c["meas"], _inverse_meas(c["meas"])]), np.concatenate([c["info"], c["info"]]))
+
+
+def reverse(c, which):
+    """The links chosen by the boolean mask `which` turned round, their measurements inverted."""
+    which = np.asarray(which, bool)
+    meas = np.array(c["meas"], np.float64)
+    meas[which] = _inverse_meas(meas[which])
+    return _with_links(c, np.where(which, c["to"], c["frm"]), np.where(which, c["frm"], c["to"]), meas, c["info"])
+
+
+def relabel(c, f):
+    """Ids mapped through f, which must be strictly increasing and keep 1 (the order of vertices and links stays)."""
+    new = np.array([f(int(v)) for v in c["ids"]], np.int64)
+    assert f(1) == 1 and (np.diff(new[np.argsort(c["ids"])]) > 0).all()
+    m = dict(zip((int(v) for v in c["ids"]), new.tolist()))
+    out = _with_links(c, [m[int(v)] for v in c["frm"]], [m[int(v)] for v in c["to"]], c["meas"], c["info"])
+    out["ids"] = new
+    if "fixed_id" in c:
+        out["fixed_id"] = m[int(c["fixed_id"])]
+    return out
+
+
+def gapped(v):
+    """The id map of the gapped forms: 1..3 stay, then every group of three ids starts 2 further on (4 5 6 -> 6 7 8,
+    7 8 9 -> 11 12 13, ...), so that every third odometry link joins ids that are not neighbours: a sub-diagonal block for the
+    plan, a removable loop closure for the robust loop's id rule."""
+    return v + 2 * ((v - 1) // 3)
+
+
+def with_outliers(c, sizes):
+    """The links (from, to) of `sizes` measure something wrong by a chosen size s: 25 s degrees and s (3, -2, 1) off."""
+    meas = np.array(c["meas"], np.float64)
+    for (a, b), s in sizes.items():
+        k = np.flatnonzero((c["frm"] == a) & (c["to"] == b))
+        assert len(k) == 1
+        meas[k[0]] = mul(meas[k[0]], pose(rot([0.3, 1, 0.2], 25.0 * s), s * np.array([3.0, -2.0, 1.0])))
+    return dict(c, meas=meas)
+
+
 def edge_cases():
     """Single edges 1 -> 2 with a chosen error rotation: identity; 1, 90 and 179 degrees (both branches of Quaternion(R)); an
     error whose quaternion has w < 0 before the flip; each with a non-diagonal SPD information matrix. One graph, one edge each,
@@ -518,6 +586,24 @@ def shape_cases(run_max=4):
     out["double_link"] = chain_graph(6, [(2, 3), (5, 2), (5, 2)], seed=8, noise=2e-2)
     for n in (65, 257):
         out[f"fan{n}"] = chain_graph(n + 1, [(k, 2) for k in range(4, n + 2)][:n - 2], seed=7, noise=1e-2)
+    # the shapes the reference's mapper hands over: links from the larger id to the smaller, both directions, ids with gaps,
+    # and a fixed vertex that is not the smallest id. 8 to 16 vertices each, whatever run_max is.
+    c = chain_graph(10, seed=71, noise=2e-2, perturb=2e-2)
+    # REFERENCE: no slot, no junction, a block-diagonal system. reversed_chain keeps the link at the fixed vertex as 1 -> 2, as
+    # getConnectedGraph's walk from vertex 1 always meets it, and is recorded; reversed_chain_all turns that one round too, a
+    # free `from` with a fixed `to`, on which the reference forms a negative triplet index and Eigen asserts: restatement alone.
+    out["reversed_chain"] = reverse(c, c["frm"] != 1)
+    out["reversed_chain_all"] = reverse(c, np.ones(len(c["frm"]), bool))
+    c = bidirectional(chain_graph(9, seed=72, noise=2e-2, perturb=2e-2))
+    keep = c["to"] != 1                                   # the same split: without the link 2 -> 1 the reference runs it
+    out["bidir_chain"] = dict(c, frm=c["frm"][keep], to=c["to"][keep], meas=c["meas"][keep], info=c["info"][keep])
+    out["bidir_chain_all"] = c
+    out["opposite_pair"] = chain_graph(8, [(2, 5), (5, 2)], seed=73, noise=2e-2)  # SYMMETRIC: m and m^T into the slot of (2, 5)
+    out["gaps"] = relabel(chain_graph(10, [(8, 3)], seed=74, noise=2e-2), gapped)
+    # the reference cannot run these two: with a fixed vertex that is not the smallest id it forms a negative triplet index and
+    # Eigen asserts. They are held to the restatement alone.
+    out["fixed_mid"] = dict(chain_graph(11, [(3, 9), (10, 2)], seed=75, noise=2e-2), fixed_id=6)
+    out["fixed_last"] = dict(chain_graph(11, [(11, 4), (2, 8)], seed=76, noise=2e-2), fixed_id=11)
     return out
 
 
@@ -529,6 +615,55 @@ def robust_case():
     good = [(4, 25), (11, 37), (20, 48), (33, 58)]
     bad = (27, 41)
     return chain_graph(60, good + [bad], seed=31, noise=1e-3, outliers={bad}, info=100.0 * np.eye(6), odo_info=1e4 * np.eye(6))
+
+
+MULTI_GOOD = [(37, 19), (21, 34), (40, 2), (27, 13)]
+MULTI_BAD = {(14, 36): 1.0, (20, 11): 0.7, (10, 44): 0.3}
+
+
+def multi_outlier_case():
+    """48 vertices, four good closures and three outliers of sizes 1, 0.7 and 0.3, closures in both directions of id. Seed and
+    sizes are chosen so that in this form, in bidirectional(), in relabel(, gapped) and in both together every round of the
+    robust loop decides by a factor of two (test_pgo_restatement.py checks that, on the reference's numbers too)."""
+    c = chain_graph(48, MULTI_GOOD + list(MULTI_BAD), seed=893, noise=1e-3, info=100.0 * np.eye(6), odo_info=1e4 * np.eye(6))
+    return with_outliers(c, MULTI_BAD)
+
+
+def first_round(c, from_id=1):
+    """The graph the robust loop's first round optimises: what getConnectedGraph reaches from from_id, one link per vertex
+    pair in the direction its walk met first, the poses propagated along the links."""
+    oid, op, kept = connected_graph(from_id, c["ids"], c["poses"], c["frm"], c["to"], c["meas"])
+    return dict(ids=oid, poses=op, frm=c["frm"][kept], to=c["to"][kept], meas=c["meas"][kept], info=c["info"][kept])
+
+
+IDENTITY_NUM = 6
+
+
+def identity_case():
+    """A plain (non-robust) graph whose FIRST update takes oplus' identity branch (|v| > 1 at some vertex) and which is then
+    iterated five times more: 16 vertices, every link in both directions, one closure (15, 2) wrong by 75 degrees and 10 units,
+    as the robust loop's first round sees it. Under the REFERENCE reading half the couplings are missing, the iteration does not
+    converge and chi2 keeps moving between 2.7e5 and 9.5e5."""
+    c = chain_graph(16, [(15, 2)], seed=81, noise=1e-3, info=100.0 * np.eye(6), odo_info=1e4 * np.eye(6))
+    return first_round(bidirectional(with_outliers(c, {(15, 2): 3.0})))
+
+
+def round_margins(rounds):
+    """Per robust round (from, to, chi2): (the two largest chi2 among the links the id rule lets the loop remove, largest
+    first; 0 where there is none). A round removes when the largest reaches THR."""
+    out = []
+    for frm, to, chi in rounds:
+        cand = np.sort(np.asarray(chi, np.float64)[np.abs(np.asarray(frm, np.int64) - np.asarray(to, np.int64)) != 1])[::-1]
+        out.append(tuple(np.concatenate([cand[:2], np.zeros(2)])[:2].tolist()))
+    return out
+
+
+def decided_by_a_factor_of_two(rounds):
+    """Every removing round's winner is at least 2 THR and twice the runner-up; the stopping round's candidates are at most
+    THR / 2; the last round and no other is the stopping one."""
+    m = round_margins(rounds)
+    removing = all(w >= 2 * THR and w >= 2 * r for w, r in m[:-1])
+    return bool(removing and m[-1][0] <= THR / 2)
 
 
 def unreachable_case():
@@ -544,7 +679,25 @@ def recorded_cases():
     out = {"iter40": (iteration_case(), 5, False), "ring8_new_old": (shape_cases()["ring8_new_old"], 3, False),
            "ring8_old_new": (shape_cases()["ring8_old_new"], 3, False), "edges": (edge_cases(), 0, False),
            "robust60": (robust_case(), 20, True), "unreachable": (unreachable_case(), 4, True)}
+    assert tuple(out) == ORIGINAL_CASES
+    # graphs shaped as the reference's mapper builds them; each is held to its own measured difference (name/E in the file)
+    m, sh = multi_outlier_case(), shape_cases()
+    out.update({"robust60_bidir": (bidirectional(robust_case()), 20, True), "multi48": (m, 20, True),
+                "multi48_bidir": (bidirectional(m), 20, True), "multi48_gaps": (relabel(m, gapped), 20, True),
+                "multi48_bidir_gaps": (relabel(bidirectional(m), gapped), 20, True),
+                "identity16": (identity_case(), IDENTITY_NUM, False), "reversed_chain": (sh["reversed_chain"], 3, False),
+                "bidir_chain": (sh["bidir_chain"], 3, False), "opposite_pair": (sh["opposite_pair"], 3, False)})
     return out
+
+
+ORIGINAL_CASES = ("iter40", "ring8_new_old", "ring8_old_new", "edges", "robust60", "unreachable")   # meta/E0 is measured on these
+ROBUST_CASES = ("robust60", "robust60_bidir", "multi48", "multi48_bidir", "multi48_gaps", "multi48_bidir_gaps")
+
+
+def tolerance(rec, name, factor):
+    """factor * E0 for the six original cases, factor * max(E0, the case's own measured E) for every later one."""
+    e0 = float(rec["meta/E0"])
+    return factor * (e0 if name in ORIGINAL_CASES else max(e0, float(rec[f"{name}/E"])))
 
 
 # ---- comparison with the recording (tests/test_pgo_restatement.py, tools/make_pgo_fixtures.py) --------------------------------------

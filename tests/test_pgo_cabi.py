@@ -78,8 +78,8 @@ SHAPES["iter40"], SHAPES["robust60"] = pc.iteration_case(), pc.robust_case()
 @pytest.mark.parametrize("name", list(SHAPES))
 def test_plan_invariants(pkg, name, run_max, coupling):
     c = SHAPES[name]
-    info, vrun, rc, couples = pkg.pgo_plan(pkg.pgo_params(coupling=coupling, run_max=run_max), *pc.args(c))
-    g = pc.Graph(*pc.args(c), coupling=coupling)
+    info, vrun, rc, couples = pkg.pgo_plan(pkg.pgo_params(coupling=coupling, run_max=run_max, fixed_id=pc.fixed(c)), *pc.args(c))
+    g = pc.Graph(*pc.args(c), fixed_id=pc.fixed(c), coupling=coupling)
     assert info.n_free == g.nfree == len(vrun) and info.schur_size == 6 * info.n_junctions
     assert np.array_equal(couples, g.couples()) and info.n_coupling == couples.sum()
     # every free vertex lies in exactly one run or is a junction; runs are stretches of consecutive indices, numbered in order
@@ -98,6 +98,53 @@ def test_plan_invariants(pkg, name, run_max, coupling):
     for r, c_ in rc.tolist():
         assert r > c_
         assert r - c_ == 1 or (vrun[r] == -1 and vrun[c_] == -1)
+
+
+def plan_of(pkg, name, coupling, run_max=64):
+    c = SHAPES[name]
+    return c, pkg.pgo_plan(pkg.pgo_params(coupling=coupling, run_max=run_max, fixed_id=pc.fixed(c)), *pc.args(c))
+
+
+@pytest.mark.parametrize("name", ["reversed_chain", "reversed_chain_all"])
+def test_reversed_chain_couples_nothing_under_the_reference_reading(pkg, name):
+    """Every link runs to the smaller Hessian index (or touches the fixed vertex): the lower triangle holds no block, the
+    system is block diagonal, no slot, no junction. The symmetric reading has the chain's n - 2 sub-diagonal slots."""
+    c, (info, vrun, rc, couples) = plan_of(pkg, name, pc.REFERENCE)
+    n = len(c["ids"])
+    assert (info.n_free, info.n_slots, info.n_junctions, info.n_coupling) == (n - 1, 0, 0, 0) and not couples.any() and len(rc) == 0
+    c, (info, vrun, rc, couples) = plan_of(pkg, name, pc.SYMMETRIC)
+    assert info.n_slots == n - 2 == info.n_coupling and info.n_junctions == 0
+    assert rc.tolist() == [[k + 1, k] for k in range(n - 2)]
+
+
+def test_opposite_pair_feeds_one_slot_from_two_edges(pkg):
+    """Closures (2, 5) and (5, 2): under the symmetric reading both couple Hessian indices 0 and 3, one as m^T and one as m, and
+    the plan has ONE slot for the pair; under the reference reading only (2, 5) couples."""
+    c, (info, vrun, rc, couples) = plan_of(pkg, "opposite_pair", pc.SYMMETRIC)
+    g = pc.Graph(*pc.args(c), coupling=pc.SYMMETRIC)
+    both = np.flatnonzero(((c["frm"] == 2) & (c["to"] == 5)) | ((c["frm"] == 5) & (c["to"] == 2)))
+    assert len(both) == 2 and couples[both].all()
+    assert sorted(g.hidx[g.vi][both].tolist()) == [0, 3] and rc.tolist().count([3, 0]) == 1      # ids 2 and 5, vertex 1 fixed
+    assert info.n_slots == (len(c["ids"]) - 2) + 1 and info.n_coupling == info.n_slots + 1      # two edges, one slot
+    c, (info, vrun, rc, couples) = plan_of(pkg, "opposite_pair", pc.REFERENCE)
+    assert couples[both].tolist() == [True, False] and c["frm"][both[0]] == 2 and rc.tolist().count([3, 0]) == 1
+
+
+@pytest.mark.parametrize("coupling", [pc.REFERENCE, pc.SYMMETRIC], ids=["reference", "symmetric"])
+@pytest.mark.parametrize("name", ["fixed_mid", "fixed_last"])
+def test_fixed_vertex_elsewhere_splits_the_chain(pkg, name, coupling):
+    """The fixed vertex has no Hessian index: the odometry links on either side of it couple nothing, so the Hessian
+    neighbours across it (fixed_mid) share no sub-diagonal slot, although their indices differ by 1."""
+    c, (info, vrun, rc, couples) = plan_of(pkg, name, coupling)
+    g = pc.Graph(*pc.args(c), fixed_id=pc.fixed(c), coupling=coupling)
+    fixed_pos = int(np.flatnonzero(g.ids == pc.fixed(c))[0])
+    assert g.hidx[fixed_pos] == -1 and info.n_free == len(c["ids"]) - 1
+    touching = (c["frm"] == pc.fixed(c)) | (c["to"] == pc.fixed(c))
+    assert touching.sum() >= 1 and not couples[touching].any()
+    if name == "fixed_mid":
+        below = int(g.hidx[fixed_pos - 1])
+        assert g.hidx[fixed_pos + 1] == below + 1 and [below + 1, below] not in rc.tolist()
+        assert any(r > below >= c_ for r, c_ in rc.tolist())             # the closures do span it
 
 
 def test_junction_cap_is_reported(pkg):

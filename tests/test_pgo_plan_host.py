@@ -48,8 +48,8 @@ def ints(words):
 @pytest.mark.parametrize("run_max", [1, 4, 64])
 def test_plan_is_the_librarys(pkg, run, run_max, coupling):
     for name, c in pc.shape_cases(run_max).items():
-        info, vrun, rc, couples = pkg.pgo_plan(pkg.pgo_params(coupling=coupling, run_max=run_max), *pc.args(c))
-        out = run(c, run_max, coupling)
+        info, vrun, rc, couples = pkg.pgo_plan(pkg.pgo_params(coupling=coupling, run_max=run_max, fixed_id=pc.fixed(c)), *pc.args(c))
+        out = run(c, run_max, coupling, pc.fixed(c))
         assert out["check"] == ["0"] and out["plan"] == ["0"], name
         assert ints(out["counts"]).tolist() == [info.n_free, info.n_runs, info.n_junctions, info.schur_size, info.n_coupling,
                                                 info.longest_run, info.n_slots, info.max_junctions], name
@@ -65,22 +65,33 @@ def second_round(c):
     return dict(c, frm=c["frm"][keep], to=c["to"][keep], meas=c["meas"][keep], info=c["info"][keep])
 
 
-CONNECTED = {"robust60": pc.robust_case(), "unreachable": pc.unreachable_case(), "double_link": pc.shape_cases()["double_link"],
-             "robust60_second_round": second_round(pc.robust_case())}
+# name -> (graph, the vertex the walk starts from). The bidirectional graphs are what the reference's mapper stores: the walk
+# keeps one link per vertex pair, in whichever direction it met first; started mid-chain most kept links run to a smaller id.
+CONNECTED = {"robust60": (pc.robust_case(), 1), "unreachable": (pc.unreachable_case(), 1),
+             "double_link": (pc.shape_cases()["double_link"], 1), "robust60_second_round": (second_round(pc.robust_case()), 1),
+             "robust60_bidir": (pc.bidirectional(pc.robust_case()), 1),
+             "multi48_bidir_gaps": (pc.relabel(pc.bidirectional(pc.multi_outlier_case()), pc.gapped), 1),
+             "multi48_bidir_from_mid": (pc.bidirectional(pc.multi_outlier_case()), 23)}
 
 
 @pytest.mark.parametrize("name", list(CONNECTED))
 def test_connected_graph_bit_for_bit(run, name):
-    c = CONNECTED[name]
+    c, start = CONNECTED[name]
     ids, poses, frm, to, meas, _ = pc.args(c)
-    oid, oposes, kept = pc.connected_graph(1, ids, poses, frm, to, meas)
-    out = run(c)
+    oid, oposes, kept = pc.connected_graph(start, ids, poses, frm, to, meas)
+    out = run(c, fixed_id=start)
     assert np.array_equal(ints(out["reached"]), oid)
     assert np.array_equal(ints(out["kept"]), kept)
     got = np.array([float.fromhex(w) for w in out["poses"]], np.float64).reshape(-1, 3, 4)
     assert got.tobytes() == np.ascontiguousarray(oposes, np.float64).tobytes()
     if name == "unreachable":
         assert 9 not in oid and len(oid) == len(ids) - 1
+    if "bidir" in name:                                       # one link per pair, and a good share of them towards the smaller id
+        pairs = [frozenset(p) for p in zip(frm[kept].tolist(), to[kept].tolist())]
+        assert len(set(pairs)) == len(pairs) == len(frm) // 2
+        down = int((frm[kept] > to[kept]).sum())
+        print(name, "kept", len(kept), "of them from the larger id to the smaller", down)
+        assert down >= (len(kept) // 3 if start != 1 else 3)
 
 
 TOPOLOGY = [r for r in REFUSALS if r[0] in ("ok", "duplicate_id", "fixed_absent", "edge_absent_from", "edge_absent_to", "self_edge")]
