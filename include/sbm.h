@@ -42,8 +42,11 @@
  * columns (its claim table), + 16 * (W + 288) / W + ~2 B with the speckle filter on (run records, seam lists), + 4 B for
  * PREFILTER_NORMALIZED_RESPONSE. Every pixel of a host-memory call adds 4 B of staging. The interior SAD kernel of a batch that
  * fills the chip more than once hands its vertical sums from one row segment to the next through scratch as well: per pair,
- * column strip and row segment behind the first, 4 * numDisparities + 256 B (+ 8 B of flags) -- 16.25 KB at 128 disparities, 138 MB
- * for 64 KITTI pairs (19 strips, 8 segments); a call whose slots would exceed 1 GiB recomputes the sums instead.
+ * column strip and row segment that can take its sums over (the segments behind the first D dispatch positions, D = the sets of
+ * pairs x strips workgroups the chip holds at once, rounded up, + 1), 128 * numDisparities + 256 B (+ 8 B of flags) -- 16.25 KB at
+ * 128 disparities, 174 MB for 64 KITTI pairs (19 strips, 13 segments, 9 of them linked), 72 MB for 64 pairs of 640 x 480 at 64 disparities (10 strips, 22
+ * segments, 14 linked). The segment count is held to what fits 1 GiB of slots; a call whose slots would still exceed that recomputes
+ * the sums instead.
  *
  * The hand-tuned kernels accumulate in place with v_mqsad_pk_u16_u8 (vdst == src2), which the hardware does right and the
  * compiler's register model forbids; a device self-test (once per device and process, on the stream of the first call that would

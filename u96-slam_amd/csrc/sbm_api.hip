@@ -456,9 +456,9 @@ int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_r
   }
   mark(h, kBmPrefiltered);
   if (pl.sad == kSadFast) {
-    h->bm.ho_slots = (size_t)(pl.f.nseg - 1) * g.n * pl.f.strips;
     HIPCHK(h, launch_sad_fast(pf_l, pf_r, disp_pre, cost, pl, ho_bytes ? h->bm.handoff.p : nullptr, ho_bytes ? ++h->bm.ho_epoch : 0u,
                               &h->bm.ho_links, h->stream));
+    h->bm.ho_slots = (size_t)h->bm.ho_links;   // one slot per (linked segment, pair, strip)
     if (pl.wide_borders) {   // beyond 256 disparities: the clamped columns from the sliding-sum kernel
       HIPCHK(h, launch_sad_wide(pf_l, pf_r, disp_pre, cost, g, pl.wide_l[0], pl.wide_l[1], h->stream));
       HIPCHK(h, launch_sad_wide(pf_l, pf_r, disp_pre, cost, g, pl.wide_r[0], pl.wide_r[1], h->stream));
@@ -489,6 +489,20 @@ int sbm_debug_plan(const sbm_params* p, int n, int width, int height, int inplac
   const int st = bm_plan(*p, n, width, height, inplace_ok != 0, &pl);
   if (st == SBM_OK) memcpy(out, &pl, sizeof(pl));
   return st;
+}
+
+// The hand-off scratch of that plan under the current SBM_FAST_HANDOFF: out[0] = sad_fast_handoff_bytes() (0: the call hands nothing
+// over), out[1] = the flag words in front of the slots. As sbm_debug_plan: for the tests, not part of the public header.
+int sbm_debug_handoff_bytes(const sbm_params* p, int n, int width, int height, int inplace_ok, uint64_t* out) {
+  if (!p || !out) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  BmPlan pl;
+  const int st = bm_plan(*p, n, width, height, inplace_ok != 0, &pl);
+  if (st != SBM_OK) return st;
+  size_t flags = 0;
+  out[0] = sad_fast_handoff_bytes(pl, &flags);
+  out[1] = flags;
+  return SBM_OK;
 }
 
 int sbm_rect_map_device(sbm_handle* h, const sbm_rect_cam* cam, int width, int height, void* d_map, int sync) {

@@ -174,7 +174,7 @@ struct sbm_handle {
     sbm::DevBuf handoff;      // vertical sums between the interior kernel's row segments (sad_fast_handoff_bytes), on first use
     size_t ho_flags;          // bytes at its start that hold ready / taken words: zero, or epochs of earlier launches
     unsigned ho_epoch;        // number of the last interior launch that used it
-    size_t ho_slots;          // slots of the last call: (row segments - 1) * pairs * strips
+    size_t ho_slots;          // slots of the last call: linked row segments * pairs * strips
     long ho_links;            // (segment, pair, strip) that could take their sums over in the last call, for sbm_debug_fetch(7)
     sbm::SpeckleScratch spk;
     sbm::StageClock clock;    // stage times only: the marks are the handle's ring below (bm_stages() has no marks of its own)

@@ -198,6 +198,75 @@ static int fast_segment_order(int nseg, long per_seg, int slots, int nd, unsigne
   return (int)D;
 }
 
+// Scratch of the hand-off: per LINKED segment (one that may take its sums over: the segments behind the first D dispatch
+// positions, every later segment in mode 2), pair and strip a ready word and a taken word, then (256-byte aligned) a slot of the
+// sums -- the sets of slots in segment order, as sad_fast_strip_dma numbers them. A segment whose successor cannot take over holds
+// no slot. Beyond kHandoffMaxBytes a call primes instead.
+constexpr size_t kHandoffMaxBytes = (size_t)1 << 30;
+static size_t fast_handoff_size(long linked, long per_seg, int ndw, size_t* flag_bytes) {
+  const size_t slots = (size_t)linked * per_seg;
+  *flag_bytes = (2 * slots * sizeof(u32) + 255) & ~(size_t)255;
+  return *flag_bytes + slots * ((size_t)(ndw / 4) * 512 + 256);
+}
+
+// The row segments of a launch whose later segments take their sums over -- where fast_handoff_links() links them: a lone
+// wavefront with an exact disparity count (32, 64, 128 disparities, not split), SBM_FAST_HANDOFF=1 and a dispatch order of
+// stride D < nseg for sad_fast_plan's own count nseg. Every other launch keeps sad_fast_plan's rule (returns 0); otherwise
+// the count, with len[p] the rows of DISPATCH POSITION p.
+//
+// Two prices. A segment at a position below D primes: w - 1 rows at 0.2 of a row each, as sad_fast_plan charges. A segment at a
+// later position pays one hand-off -- the extra leaving row, the slot's store and load, the wait in front of the ready word:
+// kHandoffRows = 0.7 of a row. Measured, KITTI x64 (1242x375 nd 128 w 15), 16 positions, every hand-off taken, the first-round
+// and the last three lengths held at the same rows while the ten positions between them were cut in two: 0.8653 -> 0.8792 ms per
+// step for 10 more segment sets = 1.39 us per set, against 2.0 us per row of a set (0.743 ms SAD stage / 372 row times); cut in
+// three, 8 rows each, 2.0 us. 640x480 nd 64 w 21 x64 the same way: 0.93 us per set against 0.72 us per row, 9 % of those
+// hand-offs missed and primed (profiles/r07_sad_segment_plan.txt, table 1).
+//
+// One rule for the lengths: they rise over the first round of the chip (positions 0 .. D-2, which start together: 10 % of a
+// regular segment per position, kFirstRoundStep, so that their sets finish in dispatch order), reach the regular length at
+// position D-1, and from there FALL LINEARLY to 1 / (n - D + 1) of it at the last position. Every round of the chip is then
+// shorter than the one before, the sets keep finishing in dispatch order, and the last, partly empty round lasts as long as the
+// shortest segments instead of a quarter of a regular one. Rows that the rounding leaves over go one each to the positions from
+// D-1 on, so the rise stays a rise and the last position stays the shortest. A flat middle with a taper over the last 3, 6, 9
+// or 12 positions, a geometric taper and shorter take-over positions behind a regular first round all measured slower or equal
+// (same file, tables 2 and 3).
+//
+// The count: as sad_fast_plan's model with the hand-off's price in place of the priming rows, n = sqrt(c' * slots * rows /
+// (per_seg * kHandoffRows)) -- but the tail this shape leaves is shorter than the 3/4, 1/2, 1/4 taper's that c = 0.196 was fitted
+// on, so c' = kSegCLinked = 0.12, fitted on the sweeps of that file: KITTI x64 flat within 0.002 ms from 12 to 16 (rule: 13),
+// 640x480 nd 64 w 21 x64 from 14 to 22 (22), KITTI nd 64 x64 from 11 to 15 (14); 8 KITTI pairs and 16 pairs 640x480, where
+// sad_fast_plan's fill rule already asks for more, best at 40 and 48 (35, 45). Past the flat part the time RISES with the count
+// (KITTI x64: 0.858 at 16, 0.867 at 20, 0.885 at 32): short segments pay more than 0.7 of a row per hand-off.
+// Never fewer segments than sad_fast_plan's, and no more than fit kHandoffMaxBytes of slots.
+constexpr double kHandoffRows = 0.7, kSegCLinked = 0.12;
+static int fast_linked_plan(const Geom& g, int rows, long per_seg, int slots, int nseg, int maxseg, int* len) {
+  if (nseg < 3 || (g.nd != 32 && g.nd != 64 && g.nd != 128)) return 0;
+  unsigned char at[64];
+  const int D = fast_segment_order(nseg, per_seg, slots, g.nd, at);
+  if (D >= nseg) return 0;
+  int n = (int)(std::sqrt(kSegCLinked * slots * rows / ((double)per_seg * kHandoffRows)) + 0.5);
+  n = std::max(nseg, std::min(n, std::min(maxseg, 64)));
+  size_t fb;
+  while (n > nseg && fast_handoff_size(n - D, per_seg, g.nd, &fb) > kHandoffMaxBytes) n--;
+  if (fast_handoff_size(n - D, per_seg, g.nd, &fb) > kHandoffMaxBytes) return 0;
+  const int fr = D - 1;   // positions of the first round
+  const double step = fr > 1 ? std::min(kFirstRoundStep, kFirstRoundSpan / (fr - 1)) : 0.0;
+  double wgt[64], sum = 0;
+  for (int p = 0; p < n; p++) {
+    wgt[p] = p < fr ? 1.0 - step * (fr - 1 - p) : (double)(n - p) / (n - fr);
+    sum += wgt[p];
+  }
+  const double unit = rows / sum;
+  int left = rows;
+  for (int p = 0; p < n; p++) {
+    len[p] = (int)(wgt[p] * unit);
+    left -= len[p];
+  }
+  for (int p = fr; p < n && left > 0; p++, left--) len[p]++;
+  for (int p = fr - 1; p >= 0 && left > 0; p--, left--) len[p]++;
+  return n;
+}
+
 // The interior launch of a call with pl->fast: strips, row segments, split, then -- through the window and layout dispatch, which
 // knows the per-instantiation constants -- the border jobs, grid, LDS and the kernel's name.
 void sad_fast_plan(BmPlan* pl) {
@@ -230,10 +299,8 @@ void sad_fast_plan(BmPlan* pl) {
   // 10-14, formula 12, round 4's rule 6: 0.476 -> 0.469 ms; 1080p nd 256 x64 best 6-8, formula 6.6, round 4's 4: 8.28 -> 8.19;
   // 2160p x32 best 8-12, formula 9, round 4's 3: 17.64 -> 16.97; 1080p x16 and 2160p x4 unchanged at 13 and 25). Round 4's rule
   // (a workgroup target of 24 000 / 5 600 with segments of at least three window heights) was tuned at 64 / 16 / 4 pairs only.
-  // Where segments take their sums over (fast_segment_order) only the first D positions still prime, so more segments cost less
-  // than this model charges. kSegC was NOT re-fitted: forced counts at KITTI x64 with the hand-off on gave 0.869 ms per step at
-  // the formula's 8 segments, 0.873 at 10, 0.867 at 12, 0.866 at 14, 0.863 at 16 (profiles/r06_sad_handoff.txt) -- under 1 %,
-  // at 1.5 to 2 times the hand-off scratch, and measured at one shape only.
+  // Where segments take their sums over (fast_segment_order) this count is only the start: fast_linked_plan below re-counts with
+  // the price of a hand-off in place of the priming rows and gives the lengths another shape.
   // (one round of the chip for the cooperating 128-disparity wavefronts: 12 wavefronts per CU in workgroups of 2 / 3 / 4)
   const int round1 = g.nd <= 256 ? 1536 : (g.nd <= 384 ? 1024 : 768);
   constexpr double kSegC = 0.196;   // c of the model above
@@ -266,6 +333,8 @@ void sad_fast_plan(BmPlan* pl) {
   }
   // taper: the last third of the rows is cut into segments of 2/3, 1/2, 1/3 ... of the regular length
   nseg = std::min(nseg, 64);
+  int len[64];
+  const int linked = fast_linked_plan(g, rows, per_seg, slots_i, nseg, maxseg, len);   // (0: not linked -- the lengths below)
   int ns = 0;
   a.segrow[0] = g.row0;
   if (nseg < 3) {
@@ -280,8 +349,9 @@ void sad_fast_plan(BmPlan* pl) {
     unsigned char at[64];
     const int stride = fast_segment_order(nseg, per_seg, slots_i, g.nd, at);
     const int first_round = stride - 1;
-    int len[64];
-    {
+    if (linked) {
+      nseg = linked;
+    } else {
       // (many small sets in the first round: the steps shrink so that its first set keeps 1 - kFirstRoundSpan of a regular one)
       const double step = first_round > 1 ? std::min(kFirstRoundStep, kFirstRoundSpan / (first_round - 1)) : 0.0;
       double wgt[64], sum = 0;
@@ -333,16 +403,16 @@ static unsigned long long fast_handoff_links(const BmPlan& pl, unsigned char* at
   return links;
 }
 
-// Scratch of the hand-off: per later segment, pair and strip a ready word and a taken word, then (256-byte aligned) a slot of the
-// sums. 0: this call hands nothing over (also where the slots would take more than kHandoffMaxBytes: it primes instead).
-constexpr size_t kHandoffMaxBytes = (size_t)1 << 30;
+// sad_fast_handoff_bytes: fast_handoff_size() of the call's linked segments. 0: this call hands nothing over (also where the slots
+// would take more than kHandoffMaxBytes: it primes instead).
 size_t sad_fast_handoff_bytes(const BmPlan& pl, size_t* flag_bytes) {
   unsigned char at[64];
   *flag_bytes = 0;
-  if (!pl.fast || !fast_handoff_links(pl, at)) return 0;
-  const size_t slots = (size_t)(pl.f.nseg - 1) * pl.g.n * pl.f.strips;
-  const size_t fb = (2 * slots * sizeof(u32) + 255) & ~(size_t)255;
-  const size_t bytes = fb + slots * ((size_t)(pl.f.NDW / 4) * 512 + 256);
+  if (!pl.fast) return 0;
+  const unsigned long long links = fast_handoff_links(pl, at);
+  if (!links) return 0;
+  size_t fb = 0;
+  const size_t bytes = fast_handoff_size(__builtin_popcountll(links), (long)pl.g.n * pl.f.strips, pl.f.NDW, &fb);
   if (bytes > kHandoffMaxBytes) return 0;
   *flag_bytes = fb;
   return bytes;

@@ -168,8 +168,11 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
   // acquire between the ready word and the sums. There is no agent-scope RELEASE in front of the ready word: on this chip it writes
   // back every dirty line of the XCD's L2, the maps of all its wavefronts included, and 4 864 of them cost the KITTI x 64 stage
   // 80 us where the priming they replaced had cost 20 (profiles/r06_sad_handoff.txt); write-through sums leave nothing to write back.
-  const size_t ho_slots = HANDOFF ? (size_t)(a.nseg - 1) * a.npairs * a.strips : 0;
-  const size_t ho_mine = HANDOFF ? ((size_t)segi * a.npairs + pair) * a.strips + strip : 0;   // the slot this segment leaves; it takes ho_mine - npairs * strips
+  // Slots exist for the LINKED segments only (the bits of ho_link), in segment order: segment k takes the slot whose set is
+  // numbered by the linked segments below k, and segment k - 1 leaves it there (scalar arithmetic: segi is workgroup-uniform).
+  const size_t ho_set = HANDOFF ? (size_t)a.npairs * a.strips : 0;
+  const size_t ho_slots = HANDOFF ? (size_t)__builtin_popcountll(a.ho_link) * ho_set : 0;
+  auto ho_slot = [&](const int k) { return (size_t)__builtin_popcountll(a.ho_link & ((1ull << k) - 1)) * ho_set + (size_t)pair * a.strips + strip; };
   auto ho_rsrc = [&](const size_t slot) {
     unsigned char* const p = reinterpret_cast<unsigned char*>(a.ho) + ((2 * ho_slots * sizeof(u32) + 255) & ~(size_t)255) + slot * FastHandoff<NDW, NWAVES, EXACT_ND>::SLOT_B;
     return __builtin_amdgcn_make_buffer_rsrc(p, 0, FastHandoff<NDW, NWAVES, EXACT_ND>::SLOT_B, 0x00020000);
@@ -177,7 +180,7 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
   bool take = false;
   if constexpr (HANDOFF) {
     if ((a.ho_link >> segi) & 1) {
-      const size_t from = ho_mine - (size_t)a.npairs * a.strips;
+      const size_t from = ho_slot(segi);
       take = __builtin_amdgcn_readfirstlane(__hip_atomic_load(a.ho + from, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == a.ho_epoch;
       if (take) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -405,6 +408,7 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
     if (segi + 1 < a.nseg && ((a.ho_link >> (segi + 1)) & 1)) {
       landed();
       apply(b1, true);
+      const size_t ho_mine = ho_slot(segi + 1);   // the slot this segment leaves: the one segment segi + 1 takes
       const __amdgpu_buffer_rsrc_t rs_h = ho_rsrc(ho_mine);
 #pragma unroll
       for (int q = 0; q < NQ; q++) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, VB[q]), rs_h, (int)(8 * lane_u), 512 * q, kHandoffAux);
