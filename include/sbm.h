@@ -58,7 +58,7 @@
  * returns SBM_ERR_HIP (SBM_ERR_NOMEM if its 8-byte allocation fails) with the error in sbm_last_hip_error(), nothing is
  * remembered, and the next call runs the self-test again.
  *
- * Environment. The library reads these ten variables (nothing else); an integrator never needs to set any of them:
+ * Environment. The library reads these eleven variables (nothing else); an integrator never needs to set any of them:
  *   variable            default  read      who sets it, and what for
  *   SBM_FAST_INPLACE    1        once      0 = run the sliding-sum SAD kernel instead of the interior one (the fallback that
  *                                          is taken automatically when the device self-test of the in-place v_mqsad
@@ -94,6 +94,9 @@
  *                                          bit 128 to the ORB descriptor's blur (see sbm_orb_params below),
  *                                          bit 256 to the keypoint matcher's radius test (see sbm_match_params below),
  *                                          bit 512 to cv::goodFeaturesToTrack's float sums (see sbm_gftt_cv_params below)
+ *   SBM_OCC_OT_HOST_PARSE 0      per call  1 = sbm_occ_ot_load / sbm_occ_ot_read parse the records with the one-pass host parser of
+ *                                          sbm_occ_ot_info instead of on the device (same maps, same codes); GPU tests / A-B
+ *                                          measurements
  * The Python mirror adds SBM_LIB_AB (file name of another build of this library inside u96-slam_amd/lib/, A-B measurements
  * only); bench.py reads SBM_BENCH_BACKEND / SBM_BENCH_FEED / SBM_BENCH_SG_FAULT (tests of its multi-process control flow).
  */
@@ -1272,7 +1275,8 @@ int sbm_occ_cast_view_device(sbm_occ_map* map, int width, int height, int scale,
  *             sbm_occ_write_binary and `size` the node count the file equals, byte for byte, what sbm_occ_write_binary /
  *             sbm_occ_write_binary_logodds write for the fetched voxels.
  *  Not here: getMetricMin / getMetricMax (octomap forms them from float centres of pruned leaves, which the keys do not pin; the
- *  key bounds of sbm_occ_tree_info are exact), bounding-box iterators, the .ot format, incremental update (a rebuild is the update).
+ *  key bounds of sbm_occ_tree_info are exact), bounding-box iterators, incremental update (a rebuild is the update). The .ot format
+ *  of a tree has a section of its own below ("the .ot format": sbm_occ_ot_body_device, sbm_occ_ot_write).
  *  Device. The compacted table is sorted by 48-bit Morton code with the map's radix sort; siblings are then
  *  neighbours, and sixteen bottom-up passes (heads per tile, a scan, one write per head) make each level from the one below;
  *  one top-down pass per depth marks what lies under a collapsed node and ranks the non-leaf nodes in pre-order, so that the .bt
@@ -1377,7 +1381,8 @@ int sbm_occ_tree_write_binary(sbm_occ_tree* tree, const char* path);
  *  grid barriers. The call returns once the leaves are uploaded; the reset and the expansion are asynchronous on the handle's
  *  stream unless sync != 0 or profiling is on. A voxel that finds no slot within the probe bound counts as overflow and the call,
  *  or with sync == 0 the next synchronous one, returns SBM_ERR_OCC_FULL, as for the inserts.
- *  Not provided: the .ot format, the legacy header, a resolution other than the map's, trees of another depth than 16.
+ *  Not provided: the legacy header, a resolution other than the map's, trees of another depth than 16. An .ot stream is refused
+ *  here and read by sbm_occ_ot_load / sbm_occ_ot_read ("the .ot format" below).
  *  sbm_get_profile: "occ_load", ms of the last load's reset and expansion on the device. */
 typedef struct sbm_occ_binary_header {
   double resolution;        /* res as parsed                                                                    */
@@ -1405,6 +1410,98 @@ int sbm_occ_binary_leaves(const void* bytes, size_t n, uint64_t* first_key, int3
 int sbm_occ_load_binary(sbm_occ_map* map, const void* bytes, size_t n, const sbm_occ_ray_params* params, int sync);
 /* tree.readBinary(filename): the same from a file; SBM_ERR_UNSUPPORTED when it cannot be opened or read. */
 int sbm_occ_read_binary(sbm_occ_map* map, const char* path, const sbm_occ_ray_params* params, int sync);
+
+/* ---- occupancy map: the .ot format, AbstractOcTree::write / read (AbstractOcTree.cpp:45-182, writeNodesRecurs / readNodesRecurs
+ * at OcTreeBaseImpl.hxx:763-844, OcTreeDataNode<float>::writeData / readData) -------------------------------------------------------
+ * The format that keeps the probabilities: a .bt thresholds every voxel to one of the two clamp values, so a map that went through
+ * a .bt continues from saturated values; an .ot holds every node's float. Scans, sbm_occ_ot_write, later sbm_occ_ot_read and
+ * more scans give the keys and float bits of the uninterrupted run. tests/occupancy_ot_cases.py is a literal transcription of
+ * this text, and tests/golden/occupancy_ot.npz holds what the reference's own octomap wrote and read.
+ *  header     written: "# Octomap OcTree file\n# (feel free to add / change comments, but leave the first line as it is!)\n#\n
+ *             id OcTree\nsize <nodes>\nres <resolution>\ndata\n", the resolution as the .bt writers print it (%g). Read: the first
+ *             line starts with "# Octomap OcTree file"; then the tokens of readHeader exactly as the .bt load section above states
+ *             them (comments, id / size / res in any order, unknown keywords skipped, the line of `data` ends the header). id must
+ *             be OcTree (or "1"), res > 0, and for a load res must EQUAL what this library prints for the map's resolution, parsed
+ *             back -- the .bt rule.
+ *  body       written for a tree built with SBM_OCC_TREE_LOGODDS (a SBM_OCC_TREE_MAXLIKELIHOOD tree, and with it every tree of a
+ *             hit-mode map: SBM_ERR_UNSUPPORTED -- the mirror image of `binary`, which refuses LOGODDS). Every node of the pruned
+ *             tree, in depth-first pre-order, contributes 5 bytes: its value as little-endian binary32 (the float maximum the
+ *             tree holds) and one byte whose bit c is set iff child c exists (computeChildIdx order). A leaf of the pruned tree
+ *             writes mask 0. `size` is the node count; an empty tree writes `size 0` and no body.
+ *             Read only when size > 0: `size` records of 5 bytes, the root's first; the children of a record follow in ascending
+ *             child index, depth first; a record with mask 0 is a leaf of its depth. The value of a record with children is not
+ *             kept: the map has no inner nodes, and a tree built afterwards recomputes them. Bytes after record `size` are ignored.
+ *  result     per depth-16 voxel below every leaf, that leaf's float, bits unchanged. Nothing is clamped (a load takes no
+ *             sbm_occ_ray_params): a leaf value outside the clamps of later scans is stored as it is. A scan after a load is exact
+ *             against octomap only for values inside the clamp interval of that scan's parameters: beyond the clamps octomap's
+ *             early return for a saturated node and the apply kernel's clamp(v + update) differ.
+ *  status     SBM_ERR_UNSUPPORTED: another first line (the .bt header included; nothing sniffs the format, and the .bt entry
+ *             points keep refusing an .ot header), another id or none, a leaf value that is not finite, a file that cannot be
+ *             opened or read. SBM_ERR_SIZE: the stream ends in the header, a number does not parse, res <= 0 or not the map's,
+ *             5 * size exceeds the body's bytes, the first `size` records are not exactly one complete tree (it completes
+ *             earlier, or is still open after them), a record at depth 16 has a child bit. SBM_ERR_OCC_FULL: the expanded voxel
+ *             count exceeds the map's capacity. SBM_ERR_NOMEM. In this order after SBM_ERR_NULL: first line, header tokens, id,
+ *             res, the map's resolution, 5 * size, the shape of the tree, the leaf values, the capacity. octomap's read() never
+ *             compares `size` with the nodes it read and reads past a short stream; those verdicts are this library's, and the
+ *             fixture records octomap's beside them.
+ *  load       everything is checked before the map is touched: a refused load leaves the map exactly as it was. A successful
+ *             load resets the map whatever its mode was, puts it in log-odds mode with what the first log-odds insert allocates,
+ *             and expands the leaves. size 0 leaves an empty map with no mode.
+ *  Device. Write: the first .ot call after a build ranks every node of the pruned tree in pre-order (a
+ *  bottom-up pass of subtree node counts, a top-down pass of ranks that also notes the node at every rank; 8 bytes per node above
+ *  the voxels and 4 per node, kept until the next build; a build that is never written as .ot costs what it did). The body is
+ *  mapped by rank, one node per lane; a workgroup's 1280 bytes are put together in LDS and stored as whole dwords, no atomics.
+ *  Load: every record is 5 bytes at 5 i, so the host parses only the header and uploads the first `size` records raw. With
+ *  c[i] = popcount(mask[i]): D[0] = 1, D[i + 1] = D[i] + c[i] - 1 is a device-wide scan (tiles of SBM_OCC_OT_SCAN_TILE records),
+ *  and the stream is one complete tree iff D[i] >= 1 for i < size and D[size] = 0; parent(i) is the largest j < i with
+ *  D[j] <= D[i], found through minima of D per SBM_OCC_OT_FAN records, minima of those per SBM_OCC_OT_FAN, and so on; i is child
+ *  number D[p] + c[p] - 1 - D[i] of its parent p, which with mask[p] gives its child index; each leaf walks up at most 16 parents
+ *  for its depth and Morton prefix (a 17th step: malformed); the leaves are compacted in record order, which is Morton order,
+ *  and their volumes 8^(16 - d) are scanned (64 bits, saturating) into the prefix array of the expansion. One read-back (flags,
+ *  leaf count, voxel total) is the load's only wait besides the upload. Every loop there has a bound that does not depend on the
+ *  stream. The expansion is the .bt loader's with the leaf's float as the stored word. Streams of more than 2^28 records, and
+ *  every stream with SBM_OCC_OT_HOST_PARSE=1, take the one-pass host parser of sbm_occ_ot_info instead: same maps, same codes.
+ *  Not provided: ColorOcTree / OcTreeStamped streams, the legacy headers, an .ot of a MAXLIKELIHOOD tree.
+ *  sbm_get_profile: "occ_tree_query", ms of the last body call (the ranking included when it ran); "occ_load", ms of the last
+ *  load on the device: the parse (where it ran there, its upload included), the reset and the expansion; a refused load leaves
+ *  the time of the last one. */
+#define SBM_OCC_OT_FAN 16          /* entries per tile of the parent search's minima hierarchy     */
+#define SBM_OCC_OT_SCAN_TILE 1024  /* records per workgroup of the device parse's scans            */
+typedef struct sbm_occ_ot_header {
+  double resolution;        /* res as parsed                                                                    */
+  uint64_t size;            /* the header's size                                                                */
+  uint64_t nodes;           /* records read                                                                     */
+  uint64_t leaves;          /* records with mask 0                                                              */
+  uint64_t voxels;          /* depth-16 voxels below the leaves: up to 2^48, counted and never expanded here    */
+  uint64_t leaves_at[17];   /* leaves per depth 0..16                                                           */
+  float value_min;          /* over the finite leaf values; a stream without one reports 0 ...                  */
+  float value_max;          /* ... and 0                                                                        */
+  uint16_t key_min[3];      /* per axis over those voxels; a stream without leaves reports 65535 ...            */
+  uint16_t key_max[3];      /* ... and 0                                                                        */
+  uint32_t pad;
+} sbm_occ_ot_header;
+
+/* The .ot body of a LOGODDS tree into d_bytes (DEVICE memory, 4-byte aligned, cap bytes); *nbytes receives its length, 5 * nodes;
+ * when it exceeds cap nothing is written and the call returns SBM_ERR_SIZE. Synchronous. SBM_ERR_NULL; SBM_ERR_UNSUPPORTED for a
+ * tree built with SBM_OCC_TREE_MAXLIKELIHOOD or a misaligned pointer. A tree that was never built answers as an empty one. */
+int sbm_occ_ot_body_device(sbm_occ_tree* tree, void* d_bytes, size_t cap, size_t* nbytes);
+/* tree.write(path): the header with the tree's size and resolution, then that body. SBM_ERR_NULL; SBM_ERR_UNSUPPORTED for a tree
+ * built with SBM_OCC_TREE_MAXLIKELIHOOD or a file that cannot be written; SBM_ERR_NOMEM. */
+int sbm_occ_ot_write(sbm_occ_tree* tree, const char* path);
+/* Plain host code, no GPU: parse n bytes of an .ot stream and report its counts. On an error *out holds what was read up to it.
+ * SBM_ERR_NULL (bytes may be NULL only for n == 0), then the codes under "status" but the map's. */
+int sbm_occ_ot_info(const void* bytes, size_t n, sbm_occ_ot_header* out);
+/* Plain host code, no GPU: the leaves in stream order, which is Morton order -- the packed key of the cube's lowest voxel, the
+ * depth and the value -- into arrays of cap entries. *count receives their number; when it exceeds cap nothing is written and the
+ * call returns SBM_ERR_SIZE. SBM_ERR_NULL (the arrays may be NULL only for cap == 0), then the codes under "status", which leave
+ * *count as it was. */
+int sbm_occ_ot_leaves(const void* bytes, size_t n, uint64_t* first_key, int32_t* depth, float* value, size_t cap, size_t* count);
+/* AbstractOcTree::read from n bytes in HOST memory, read before the call returns. No ray parameters: nothing is clamped. See
+ * "load" and "status"; the reset and the expansion are asynchronous on the handle's stream unless sync != 0 or profiling is on,
+ * and a voxel that finds no slot within the probe bound counts as overflow, as for sbm_occ_load_binary. */
+int sbm_occ_ot_load(sbm_occ_map* map, const void* bytes, size_t n, int sync);
+/* The same from a file; SBM_ERR_UNSUPPORTED when it cannot be opened or read. */
+int sbm_occ_ot_read(sbm_occ_map* map, const char* path, int sync);
 
 /* ---- visual-word dictionary: addNewWords, computeLikelihood, limitKeypoints ---------------------------------------------------
  * The reference's loop-closure thread, started by Mapper::process for each key frame: addWordIds -> VWDictionary::addNewWords

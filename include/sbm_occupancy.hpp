@@ -13,6 +13,8 @@
 // buildTree() gives an OccupancyTree: octomap's sixteen levels above the voxels as a snapshot on the device, with search(point,
 // depth), leaves(maxDepth), size() / getNumLeafNodes() and writeBinary() in octomap's spelling.
 // readBinary() loads a .bt back into the map: the host parses the pruned tree, the device expands its leaves to voxels.
+// write() / read() are octomap's .ot file, which keeps every voxel's log-odds: scans, write, read, more scans equal the
+// uninterrupted run.
 #ifndef SBM_OCCUPANCY_HPP_
 #define SBM_OCCUPANCY_HPP_
 
@@ -81,6 +83,8 @@ class OccupancyTree {
   }
   // tree.writeBinary(path) of a SBM_OCC_TREE_MAXLIKELIHOOD tree
   void writeBinary(const std::string& path) { check(sbm_occ_tree_write_binary(t_, path.c_str())); }
+  // tree.write(path) of a SBM_OCC_TREE_LOGODDS tree: the .ot file, every node's float
+  void write(const std::string& path) { check(sbm_occ_ot_write(t_, path.c_str())); }
 
  private:
   static void check(int st) {
@@ -178,6 +182,22 @@ class OccupancyMap {
   }
   bool readBinary(const void* bytes, size_t n) {
     check(sbm_occ_load_binary(m_, bytes, n, &rp_, 1));
+    return true;
+  }
+
+  // tree.write(path): the .ot file of a log-odds map as it is now, which keeps every voxel's log-odds (a .bt keeps which clamp
+  // it is nearer to)
+  void write(const std::string& path) { buildTree(SBM_OCC_TREE_LOGODDS)->write(path); }
+  // AbstractOcTree::read(filename) / read(stream) for an OcTree: the map becomes what the .ot holds, every voxel its leaf's float,
+  // unclamped, whatever it held before; further insertPointCloud / insertRays scans continue on it. octomap returns NULL where
+  // this throws (the codes of readBinary above, and SBM_ERR_UNSUPPORTED for a leaf value that is not finite), and then the map is
+  // as it was.
+  bool read(const std::string& filename) {
+    check(sbm_occ_ot_read(m_, filename.c_str(), 1));
+    return true;
+  }
+  bool read(const void* bytes, size_t n) {
+    check(sbm_occ_ot_load(m_, bytes, n, 1));
     return true;
   }
 

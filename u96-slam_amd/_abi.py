@@ -153,6 +153,17 @@ class OccBinaryHeader(ctypes.Structure):
                 ("key_min", ctypes.c_uint16 * 3), ("key_max", ctypes.c_uint16 * 3), ("pad", ctypes.c_uint32)]
 
 
+class OccOtHeader(ctypes.Structure):
+    """`sbm_occ_ot_header` of include/sbm.h: what sbm_occ_ot_info reports of an .ot stream."""
+
+    _fields_ = [("resolution", ctypes.c_double), ("size", ctypes.c_uint64), ("nodes", ctypes.c_uint64), ("leaves", ctypes.c_uint64),
+                ("voxels", ctypes.c_uint64), ("leaves_at", ctypes.c_uint64 * 17), ("value_min", ctypes.c_float),
+                ("value_max", ctypes.c_float), ("key_min", ctypes.c_uint16 * 3), ("key_max", ctypes.c_uint16 * 3), ("pad", ctypes.c_uint32)]
+
+
+OCC_OT_FAN, OCC_OT_SCAN_TILE = 16, 1024      # SBM_OCC_OT_FAN, SBM_OCC_OT_SCAN_TILE: the tile constants of the .ot device parse
+
+
 class VwdParams(ctypes.Structure):
     """`sbm_vwd_params` of include/sbm.h: addNewWords' metric and NNDR ratio (VWDictionary.cpp:43), and the search's slice count."""
 
@@ -387,6 +398,12 @@ def load_library():
     L.sbm_occ_binary_leaves.argtypes = [vp, sz, vp, vp, vp, sz, ctypes.POINTER(sz)]
     L.sbm_occ_load_binary.argtypes = [vp, vp, sz, orp, ci]
     L.sbm_occ_read_binary.argtypes = [vp, ctypes.c_char_p, orp, ci]
+    L.sbm_occ_ot_body_device.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_ot_write.argtypes = [vp, ctypes.c_char_p]
+    L.sbm_occ_ot_info.argtypes = [vp, sz, ctypes.POINTER(OccOtHeader)]
+    L.sbm_occ_ot_leaves.argtypes = [vp, sz, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_ot_load.argtypes = [vp, vp, sz, ci]
+    L.sbm_occ_ot_read.argtypes = [vp, ctypes.c_char_p, ci]
     wp = ctypes.POINTER(VwdParams)
     pi = ctypes.POINTER(ci)
     L.sbm_vwd_params_default.argtypes = [wp]

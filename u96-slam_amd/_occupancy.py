@@ -8,7 +8,7 @@ import numpy as np
 
 from ._abi import (ERR_OCC_FULL, OCC_CELL_FREE, OCC_CELL_OCCUPIED, OCC_CELL_OUT, OCC_CELL_UNKNOWN, OCC_RAY_BOUNDS,  # noqa: F401
                    OCC_RAY_HIT, OCC_RAY_NONE, OCC_RAY_RANGE, OCC_RAY_UNKNOWN, OCC_TREE_LOGODDS, OCC_TREE_MAXLIKELIHOOD, OccParams,
-                   OccBinaryHeader, OccQueryParams, OccRayParams, OccTreeCounts, StereoBMError, _check, _torch, load_library)
+                   OccBinaryHeader, OccOtHeader, OccQueryParams, OccRayParams, OccTreeCounts, StereoBMError, _check, _torch, load_library)
 
 
 def occ_params(resolution=0.1, range_max=5.0, tree_depth=16):
@@ -90,6 +90,33 @@ def occ_binary_leaves(data):
     if n.value:
         _check(L.sbm_occ_binary_leaves(ptr, len(b), keys.ctypes.data, depth.ctypes.data, occ.ctypes.data, n.value, ctypes.byref(n)))
     return keys, depth, occ
+
+
+def occ_ot_info(data):
+    """What an .ot stream holds, parsed on the host (no GPU): dict of resolution, size (the header's), nodes (records read), leaves,
+    voxels (depth-16 voxels below the leaves), leaves_at per depth 0..16, value_min / value_max over the finite leaf values,
+    key_min / key_max per axis."""
+    b = _stream(data)
+    h = OccOtHeader()
+    _check(load_library().sbm_occ_ot_info(b.ctypes.data if len(b) else None, len(b), ctypes.byref(h)))
+    return dict(resolution=h.resolution, size=h.size, nodes=h.nodes, leaves=h.leaves, voxels=h.voxels, leaves_at=list(h.leaves_at),
+                value_min=h.value_min, value_max=h.value_max, key_min=list(h.key_min), key_max=list(h.key_max))
+
+
+def occ_ot_leaves(data):
+    """The leaves of an .ot stream in stream order, parsed on the host (no GPU) -> (packed key of each cube's lowest voxel uint64,
+    depth int32, value float32)."""
+    b = _stream(data)
+    L = load_library()
+    n = ctypes.c_size_t()
+    ptr = b.ctypes.data if len(b) else None
+    st = L.sbm_occ_ot_leaves(ptr, len(b), None, None, None, 0, ctypes.byref(n))
+    if st != -2 or not n.value:      # -2 with a count: the arrays are too small, as asked
+        _check(st)
+    keys, depth, value = np.empty(n.value, np.uint64), np.empty(n.value, np.int32), np.empty(n.value, np.float32)
+    if n.value:
+        _check(L.sbm_occ_ot_leaves(ptr, len(b), keys.ctypes.data, depth.ctypes.data, value.ctypes.data, n.value, ctypes.byref(n)))
+    return keys, depth, value
 
 
 def occ_query_params(max_range=-1.0, occupancy_thres_log=0.0, ignore_unknown=False):
@@ -229,6 +256,19 @@ class OccupancyMap:
         else:
             b = _stream(data_or_path)
             st = self._L.sbm_occ_load_binary(self._m, b.ctypes.data if len(b) else None, len(b), rp, 1 if sync else 0)
+        _check(st, self._engine._h)
+        if sync:
+            self._engine._inflight.clear()
+
+    def load_ot(self, data_or_path, sync=True):
+        """octomap's AbstractOcTree::read: replace the map's content by the voxels of an .ot stream -- bytes (or a uint8 array),
+        or the path of a file (str or os.PathLike). Every voxel holds its leaf's float, unclamped; the map is then a log-odds map
+        that further insert_cloud / insert_rays scans continue."""
+        if isinstance(data_or_path, (str, os.PathLike)):
+            st = self._L.sbm_occ_ot_read(self._m, os.fsencode(data_or_path), 1 if sync else 0)
+        else:
+            b = _stream(data_or_path)
+            st = self._L.sbm_occ_ot_load(self._m, b.ctypes.data if len(b) else None, len(b), 1 if sync else 0)
         _check(st, self._engine._h)
         if sync:
             self._engine._inflight.clear()
@@ -500,6 +540,29 @@ class OccupancyTree:
     def write_binary(self, path):
         """tree.writeBinary(path) of a MAXLIKELIHOOD tree."""
         _check(self._L.sbm_occ_tree_write_binary(self._t, os.fsencode(path)), self._engine._h)
+
+    def ot_body(self):
+        """The body of the .ot stream (a LOGODDS tree) as a torch CUDA uint8 tensor: five bytes per node of the pruned tree."""
+        torch = _torch()
+        n = 5 * self.info()["nodes"]
+        out = torch.empty((n,), dtype=torch.uint8, device=torch.device("cuda", self._engine._device))
+        got = ctypes.c_size_t()
+        torch.cuda.current_stream(out.device).synchronize()
+        _check(self._L.sbm_occ_ot_body_device(self._t, out.data_ptr() if n else None, n, ctypes.byref(got)), self._engine._h)
+        return out[:got.value]
+
+    def ot(self):
+        """The whole .ot stream of a LOGODDS tree as bytes: the file write_ot writes, read back."""
+        import tempfile
+        with tempfile.TemporaryDirectory() as tmp:
+            path = os.path.join(tmp, "tree.ot")
+            self.write_ot(path)
+            with open(path, "rb") as f:
+                return f.read()
+
+    def write_ot(self, path):
+        """tree.write(path) of a LOGODDS tree."""
+        _check(self._L.sbm_occ_ot_write(self._t, os.fsencode(path)), self._engine._h)
 
     def profile(self):
         return self._engine._profile(("occ_tree_build", "occ_tree_query"))

@@ -1,8 +1,9 @@
 // sbm_occ.h -- what more than one file of the occupancy family (sbm_occupancy.hip, sbm_occ_*.hip) needs, each thing once. Internal.
-// The first part is plain C++, for the host-only sbm_occ_bt.hip; the rest needs HIP (gfx950 only). Nothing here contracts a
+// The first part is plain C++, for the host-only sbm_occ_bt.hip and sbm_occ_ot_host.hip; the rest needs HIP (gfx950 only). Nothing here contracts a
 // multiply-add: every helper with float or double steps carries the pragma.
 #pragma once
 #include <stdint.h>
+#include <string>
 #include <vector>
 
 #include "../../include/sbm.h"
@@ -55,6 +56,15 @@ inline int occ_bt_depth(OccBtLeaf l) { return (int)(l >> 1 & 31); }
 #pragma GCC visibility push(hidden)   // sbm_occ_bt.hip: the parser (leaves in stream order) and the file of a written body
 int occ_bt_parse(const uint8_t* b, size_t n, sbm_occ_binary_header* info, std::vector<OccBtLeaf>* leaves, bool bounds = true);
 int occ_write_file(const std::vector<uint8_t>& body, size_t nodes, double resolution, const char* path);
+int occ_read_file(const char* path, std::vector<uint8_t>* data);
+int occ_bt_header(const uint8_t* b, size_t n, size_t* pos, std::string* id, uint64_t* size, double* res);   // readHeader
+// sbm_occ_ot_host.hip, the .ot stream: its header alone (-> where the body begins), the whole host parse (leaf words without the occupied bit, and the
+// leaves' float bits), and the file. want_res > 0: what the file's res must equal
+int occ_ot_head(const uint8_t* b, size_t n, double want_res, sbm_occ_ot_header* info, size_t* body);
+int occ_ot_parse(const uint8_t* b, size_t n, double want_res, sbm_occ_ot_header* info, std::vector<OccBtLeaf>* words,
+                 std::vector<uint32_t>* values, bool bounds);
+int occ_ot_write_file(const std::vector<uint8_t>& body, size_t nodes, double resolution, const char* path);
+double occ_printed_resolution(double resolution);   // what the writers print for a resolution (%g), read back
 #pragma GCC visibility pop
 
 #ifdef __HIP__
@@ -203,6 +213,8 @@ int occ_sort_run(sbm_handle* h, unsigned long long* const kk[2], unsigned* const
 float occ_logodds(double p);   // these three are in sbm_occ_rays.hip
 int occ_ray_params_check(const sbm_occ_ray_params* p);
 int occ_logodds_alloc(sbm_occ_map* map);   // what the log-odds mode keeps beside the table
+OccLevel occ_tree_level(const sbm_occ_tree* t, int d);   // these two are in sbm_occ_tree.hip: depth d of a built tree (empty levels for
+int occ_tree_stats(sbm_occ_tree* t);                     // one that is not), and the counts of the last build into t->host, read once
 #pragma GCC visibility pop
 
 // Times `stage` of a query around `launch` (-> status; the error of its last launch is looked at here). A query changes nothing
@@ -244,6 +256,7 @@ struct sbm_occ_tree {
   sbm_handle* h;
   sbm_occ_map* map;            // read by a build only
   bool built, have_stats;      // levels are valid; `host` holds the last build's counts
+  bool ot_ranked;              // `ot` holds this build's pre-order ranks: filled by the first .ot call after a build
   int reading;
   double resolution;
   unsigned cmax;               // float bits of clamp max, what .bt calls occupied
@@ -253,6 +266,8 @@ struct sbm_occ_tree {
   sbm::DevBuf leaf, node;      // depth 16: code, value, parent, info (20 B per voxel); above: code, value, parent, info, first
                                // child, subtree count, rank (32 B per node)
   sbm::DevBuf stats, tiles;    // OccTreeStats; head counts per tile of the level being built
-  template <class F> void each(F f) { f(leaf); f(node); f(stats); f(tiles); }
+  sbm::DevBuf ot;              // .ot writes only (sbm_occ_ot.hip): per node above the leaves its subtree's nodes and its pre-order
+                               // rank among all nodes of the pruned tree, then the node at every rank
+  template <class F> void each(F f) { f(leaf); f(node); f(stats); f(tiles); f(ot); }
 };
 #endif

@@ -1,5 +1,6 @@
 // sbm_occ_bt.hip -- the octomap binary stream (.bt) on the host: the writer of AbstractOccupancyOcTree::writeBinaryConst for a
-// set of voxels, and the parser of readBinary that the loader (sbm_occ_load.hip) and the two inspection calls share.
+// set of voxels, and the parser of readBinary that the loader (sbm_occ_load.hip) and the two inspection calls share; readHeader,
+// which the .ot stream (sbm_occ_ot_host.hip) has too, and the file read of the read calls.
 // Host only: no HIP header and no HIP call, so any C++17 compiler builds this file alone (tools/occupancy_load_sanitize.cpp does).
 #include <stdio.h>
 #include <stdlib.h>
@@ -62,6 +63,13 @@ int occ_write_file(const std::vector<uint8_t>& body, size_t nodes, double resolu
   return ok ? SBM_OK : SBM_ERR_UNSUPPORTED;
 }
 
+// What sbm_occ_write_binary* print for a resolution (%g), read back
+double occ_printed_resolution(double resolution) {
+  char text[64];
+  snprintf(text, sizeof(text), "%g", resolution);
+  return strtod(text, nullptr);
+}
+
 // ---- reading a .bt stream (include/sbm.h, "occupancy map: load a .bt stream") ------------------------------------------------
 struct OccBtParse {
   sbm_occ_binary_header info;
@@ -72,7 +80,7 @@ struct OccBtParse {
 
 // AbstractOcTree::readHeader on bytes [*pos, n): tokens up to the line `data`. SBM_ERR_SIZE where the stream ends first or a
 // number does not parse (octomap's stream fails there and its loop ends without `data`).
-static int occ_bt_header(const uint8_t* b, size_t n, size_t* pos, std::string* id, uint64_t* size, double* res) {
+int occ_bt_header(const uint8_t* b, size_t n, size_t* pos, std::string* id, uint64_t* size, double* res) {
   size_t i = *pos;
   const auto space = [](uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); };
   const auto skip_line = [&] {
@@ -194,6 +202,24 @@ int occ_bt_parse(const uint8_t* b, size_t n, sbm_occ_binary_header* info, std::v
   if (st == SBM_OK && p.info.nodes != p.info.size) st = SBM_ERR_SIZE;   // calcNumNodes() against the header
   if (info) *info = p.info;
   return st;
+}
+
+// A whole file into memory: what the two read calls share
+int occ_read_file(const char* path, std::vector<uint8_t>* data) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return SBM_ERR_UNSUPPORTED;
+  bool ok = true;
+  try {
+    uint8_t chunk[1 << 16];
+    size_t got;
+    while ((got = fread(chunk, 1, sizeof(chunk), f)) > 0) data->insert(data->end(), chunk, chunk + got);
+    ok = !ferror(f);
+  } catch (const std::bad_alloc&) {
+    fclose(f);
+    return SBM_ERR_NOMEM;
+  }
+  fclose(f);
+  return ok ? SBM_OK : SBM_ERR_UNSUPPORTED;
 }
 
 // A voxel as the writer's leaf word: occ_code masks each field of the packed key to its 16 bits

@@ -60,13 +60,6 @@ __global__ void __launch_bounds__(256) occ_load_kernel(const unsigned long long*
 }
 
 // ---- loading a .bt stream, host side ----------------------------------------------------------------------------------------
-// What sbm_occ_write_binary* print for a resolution (%g), read back
-static double occ_printed_resolution(double resolution) {
-  char text[64];
-  snprintf(text, sizeof(text), "%g", resolution);
-  return strtod(text, nullptr);
-}
-
 // readBinary into the map. Everything that can refuse the stream comes before the map is touched.
 static int occ_load_run(sbm_occ_map* map, const uint8_t* bytes, size_t n, const sbm_occ_ray_params* p, int sync) {
   sbm_handle* h = map->h;
@@ -140,21 +133,9 @@ int sbm_occ_read_binary(sbm_occ_map* map, const char* path, const sbm_occ_ray_pa
   if (!map || !path || !params) return SBM_ERR_NULL;
   const int st = occ_ray_params_check(params);
   if (st != SBM_OK) return st;
-  FILE* f = fopen(path, "rb");
-  if (!f) return SBM_ERR_UNSUPPORTED;
   std::vector<uint8_t> data;
-  bool ok = true;
-  try {
-    uint8_t chunk[1 << 16];
-    size_t got;
-    while ((got = fread(chunk, 1, sizeof(chunk), f)) > 0) data.insert(data.end(), chunk, chunk + got);
-    ok = !ferror(f);
-  } catch (const std::bad_alloc&) {
-    fclose(f);
-    return SBM_ERR_NOMEM;
-  }
-  fclose(f);
-  if (!ok) return SBM_ERR_UNSUPPORTED;
+  const int rd = occ_read_file(path, &data);
+  if (rd != SBM_OK) return rd;
   return occ_load_run(map, data.data(), data.size(), params, sync);
 }
 }  // extern "C"

@@ -286,7 +286,7 @@ __global__ void __launch_bounds__(256) occ_tree_binary_kernel(OccLevel l, OccLev
 
 // ---- the tree, host side -------------------------------------------------------------------------------------------------
 // Depth d of a built tree; a tree that was never built, or whose build failed, has empty levels.
-static OccLevel occ_tree_level(const sbm_occ_tree* t, int d) {
+OccLevel occ_tree_level(const sbm_occ_tree* t, int d) {
   OccLevel l;
   memset(&l, 0, sizeof(l));
   if (!t->built) return l;
@@ -320,6 +320,7 @@ static int occ_tree_build_run(sbm_occ_tree* t, int reading, const sbm_occ_ray_pa
   HIPCHK(h, occ_clock_start(h, kOccTreeBuild, kOccTreeBuild));
   t->built = false;
   t->have_stats = false;
+  t->ot_ranked = false;
   t->reading = reading;
   t->resolution = map->p.resolution;
   memset(t->count, 0, sizeof(t->count));
@@ -418,7 +419,7 @@ static int occ_tree_build_run(sbm_occ_tree* t, int reading, const sbm_occ_ray_pa
 }
 
 // The counts of the last build, read once
-static int occ_tree_stats(sbm_occ_tree* t) {
+int occ_tree_stats(sbm_occ_tree* t) {
   sbm_handle* h = t->h;
   if (t->have_stats) return SBM_OK;
   memset(&t->host, 0, sizeof(t->host));
