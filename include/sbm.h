@@ -642,6 +642,24 @@ typedef struct sbm_match_params {
 void sbm_match_params_default(sbm_match_params* p);
 /* SBM_ERR_NULL, SBM_ERR_UNSUPPORTED (a field outside the limits above), else SBM_OK. */
 int sbm_match_params_validate(const sbm_match_params* p);
+/* The launch plan of a matching or projection call over m jobs on a store of capacity cap, as the calls below compute and
+ * execute it; depends on (cap, m) alone. No handle, no device: tests ask it which path a shape takes.
+ *   k-NN      grid (qtiles, nslice, jobs of the launch): query tiles of 64 slots, train slices of slice_rows rows (a multiple of
+ *             64; (nslice - 1) * slice_rows < cap <= nslice * slice_rows, 1 <= nslice <= 32). A job reads the first
+ *             ceil(nt / slice_rows) slices' partial records.
+ *   launches  jobs_per_launch = min(m, 64) jobs per k-NN / claim / emit sequence, launches = ceil(m / jobs_per_launch) of them;
+ *             sbm_project_points_device: proj_jobs_per_launch = min(m, 32), proj_launches = ceil(m / 32).
+ *   scratch   scratch_bytes = jobs_per_launch * cap * (16 * nslice + 8) of handle scratch, at most 256 MiB.
+ * sbm_match_plan: SBM_ERR_NULL (out), SBM_ERR_SIZE (out_bytes != sizeof(sbm_match_plan_info)), then the limits above in the calls'
+ * order: m < 1 SBM_ERR_BATCH, cap outside 1..65 535 SBM_ERR_SIZE, m > 65 535 SBM_ERR_UNSUPPORTED (*out zeroed). */
+typedef struct sbm_match_plan_info {
+  int32_t qtiles, nslice, slice_rows;
+  int32_t jobs_per_launch, launches;
+  int32_t proj_jobs_per_launch, proj_launches;
+  int32_t pad;
+  int64_t scratch_bytes;
+} sbm_match_plan_info;
+int sbm_match_plan(int cap, int m, sbm_match_plan_info* out, size_t out_bytes);
 /* matchingNoGuess for m jobs over a store of n frames (jobs: 2 * m host ints, copied with the call). */
 int sbm_match_device(sbm_handle* h, int n, int m, const int* jobs, const void* d_desc, const void* d_count, int cap,
                      const sbm_match_params* p, void* d_pairs, void* d_npairs, void* d_knn, int sync);

@@ -191,8 +191,13 @@ def radius_edge_cases(count=8, seed=0, radius=40.0):
     """(projection, keypoint) float32 pairs on the radius edge with dy != 0, one per 256 x 256 grid cell, of three kinds
     (count of each): 'band_unfused' / 'band_fused' -- the squared distance under that reading is below radius^2 but its rounded
     square root reaches the radius (so `d2 < radius^2` would wrongly take it); 'readings_differ' -- the two readings of the sum
-    decide the radius test differently. Returns (proj (k, 2), kpts (k, 2), kinds list)."""
+    decide the radius test differently. Returns (proj (k, 2), kpts (k, 2), kinds list). The search runs at the radius scaled
+    into [32, 64) by a power of two and every coordinate is scaled back at the end: both steps are exact in float32 and commute
+    with the squares, the sums and the rounded square root, so the kinds hold at the radius asked for (at 40 the scale is 1).
+    The band kinds exist only for a radius r at which the least float whose rounded root reaches r lies below fl(r * r)."""
     rng = np.random.default_rng(seed)
+    scale = np.float32(2.0 ** (math.floor(math.log2(float(np.float32(radius)))) - 5))
+    radius = float(np.float32(radius) / scale)
     r = np.float32(radius)
     r2 = np.float32(np.float64(r) * np.float64(r))
     N = 400000
@@ -227,4 +232,4 @@ def radius_edge_cases(count=8, seed=0, radius=40.0):
             proj.append((a[0] + ox, a[1] + oy))
             kpts.append((a[2] + ox, a[3] + oy))
             kinds.append(kind)
-    return np.array(proj, np.float32), np.array(kpts, np.float32), kinds
+    return np.array(proj, np.float32) * scale, np.array(kpts, np.float32) * scale, kinds

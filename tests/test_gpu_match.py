@@ -57,8 +57,8 @@ def planted(rng, n, nt, flips=(0, 3, 20, 60)):
     return fr, to
 
 
-def check_job(pairs, npairs, rec, j, dfrom, dto, proj=None, kto=None, fused=False, what=""):
-    want_p, want_r = ref.match(dfrom, dto, proj, kto, fused=fused)
+def check_job(pairs, npairs, rec, j, dfrom, dto, proj=None, kto=None, fused=False, what="", radius=40.0, nndr=0.8):
+    want_p, want_r = ref.match(dfrom, dto, proj, kto, radius=radius, nndr=nndr, fused=fused)
     k = int(npairs[j])
     assert k == len(want_p), (what, j, k, len(want_p))
     assert np.array_equal(pairs[j, :k], want_p), (what, j)

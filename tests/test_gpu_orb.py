@@ -44,8 +44,8 @@ def slots(kp_list, cap):
     return out, cnt
 
 
-def check_frame(desc, kk, cc, i, img, kpts, pattern, angle=-1.0, half_up=False, blur=None, what=""):
-    want_k, want_d, want_b = ref.describe(img, kpts, pattern, angle=angle, half_up=half_up)
+def check_frame(desc, kk, cc, i, img, kpts, pattern, angle=-1.0, half_up=False, blur=None, what="", edge=19):
+    want_k, want_d, want_b = ref.describe(img, kpts, pattern, angle=angle, edge=edge, half_up=half_up)
     k = int(cc[i])
     assert k == len(want_k), (what, i, k, len(want_k))
     assert np.array_equal(kk[i, :k], want_k), (what, i)
@@ -55,10 +55,10 @@ def check_frame(desc, kk, cc, i, img, kpts, pattern, angle=-1.0, half_up=False, 
         assert np.array_equal(blur[i], want_b), (what, i, int((blur[i] != want_b).sum()))
 
 
-def run_describe(bm, imgs, kp_list, pattern, cap=None, angle=-1.0, out=None):
+def run_describe(bm, imgs, kp_list, pattern, cap=None, angle=-1.0, out=None, edge=19):
     cap = cap or max(1, max(len(k) for k in kp_list))
     kp, cn = slots(kp_list, cap)
-    d, kk, cc, bl = bm.orb_describe(dev(imgs), dev(kp), dev(cn), pattern, angle=angle, blur=True, out=out)
+    d, kk, cc, bl = bm.orb_describe(dev(imgs), dev(kp), dev(cn), pattern, angle=angle, edge_threshold=edge, blur=True, out=out)
     return d.cpu().numpy(), kk.cpu().numpy(), cc.cpu().numpy(), bl.cpu().numpy()
 
 
@@ -138,9 +138,94 @@ def test_border_filter_edges(bm, pattern):
     assert not kept_x & f32([18.0, 18.49, 18.5, w - 19.49, w - 19.0, w - 18.5])
 
 
-def _raw_call(bm, pkg, imgs, kp, cn, pattern, cap, desc, kout=None, cout=None, sync=1):
+# ---- edge thresholds other than the reference's 19 ----------------------------------------------------------------------
+def corner_pattern(rng):
+    """A random pattern whose first points are the four corners (+-13, +-13): at 45 degrees they turn into (+-18, 0) and
+    (0, +-18), the farthest a sample can lie from its centre."""
+    pat = rng.integers(-13, 14, (512, 2))
+    pat[:8] = [(13, 13), (-13, -13), (13, -13), (-13, 13), (-13, 13), (13, 13), (-13, -13), (13, -13)]
+    return pat
+
+
+def edge_setup(edge, pattern):
+    """(pattern, angle) for a threshold: at 18 the samples must reach exactly 18 pixels from the centre in x and in y."""
+    if edge != 18:
+        return pattern, -1.0
+    pat = corner_pattern(np.random.default_rng(18))
+    dx, dy = ref.offsets_np(pat, 45.0)
+    assert (dx.min(), dx.max(), dy.min(), dy.max()) == (-18, 18, -18, 18)
+    return pat, 45.0
+
+
+@pytest.mark.parametrize("reading", READINGS, ids=RIDS, indirect=True)
+@pytest.mark.parametrize("edge", [18, 19, 31])
+def test_edge_thresholds(bm, pattern, edge, reading):
+    w, h = 100, 80
+    pat, angle = edge_setup(edge, pattern)
+    rng = np.random.default_rng(edge)
+    img = rng.integers(0, 256, (h, w), dtype=np.uint8)
+    xs = [edge - 1, edge - 0.51, edge - 0.49, edge, edge + 0.49, w - edge - 1.49, w - edge - 1, w - edge - 0.51, w - edge - 0.49,
+          w - edge]
+    ys = [edge - 1, edge - 0.51, edge - 0.49, edge, edge + 0.49, h - edge - 1.49, h - edge - 1, h - edge - 0.51, h - edge - 0.49,
+          h - edge]
+    kp = np.concatenate([np.array([(x, y) for x in xs for y in ys], np.float32), random_kpts(rng, w, h, 200)])
+    d, kk, cc, bl = run_describe(bm, img[None], [kp], pat, angle=angle, edge=edge)
+    check_frame(d, kk, cc, 0, img, kp, pat, angle=angle, half_up=reading, blur=bl, what=edge, edge=edge)
+    kept = {tuple(v) for v in kk[0, :cc[0]].tolist()}
+    corners = {(float(x), float(y)) for x in (edge, w - edge - 1) for y in (edge, h - edge - 1)}
+    assert corners <= kept                                  # centres whose samples reach column 0 / W - 1 and row 0 / H - 1
+    rx, ry = np.rint(kk[0, :cc[0], 0]), np.rint(kk[0, :cc[0], 1])
+    assert rx.min() == edge and rx.max() == w - edge - 1 and ry.min() == edge and ry.max() == h - edge - 1
+
+
+@pytest.mark.parametrize("edge", [18, 19, 31])
+def test_frame_with_one_centre(bm, pattern, edge):
+    s = 2 * edge + 1
+    pat, angle = edge_setup(edge, pattern)
+    img = np.random.default_rng(100 + edge).integers(0, 256, (s, s), dtype=np.uint8)
+    ys, xs = np.mgrid[0:s, 0:s]
+    kp = np.stack([xs.ravel(), ys.ravel()], 1).astype(np.float32)
+    d, kk, cc, bl = run_describe(bm, img[None], [kp], pat, angle=angle, edge=edge)
+    check_frame(d, kk, cc, 0, img, kp, pat, angle=angle, blur=bl, what=edge, edge=edge)
+    assert cc[0] == 1 and kk[0, 0].tolist() == [edge, edge]
+
+
+@pytest.mark.parametrize("edge", [18, 19, 31])
+def test_frame_of_twice_the_edge_keeps_nothing(bm, pattern, edge):
+    pat, angle = edge_setup(edge, pattern)
+    rng = np.random.default_rng(200 + edge)
+    for w, h in ((2 * edge, 100), (100, 2 * edge), (2 * edge, 2 * edge)):
+        img = rng.integers(0, 256, (h, w), dtype=np.uint8)
+        ys, xs = np.mgrid[0:h, 0:w]
+        kp = np.stack([xs.ravel(), ys.ravel()], 1).astype(np.float32)
+        d, kk, cc, bl = run_describe(bm, img[None], [kp], pat, angle=angle, edge=edge)
+        assert cc[0] == 0 and len(ref.describe(img, kp, pat, angle=angle, edge=edge)[0]) == 0
+        assert not d.any() and not bl.any()
+
+
+def test_edge_threshold_limits(bm, pkg, pattern):
+    import torch
+
+    assert pkg.orb_validate(pkg.orb_params(edge_threshold=17)) == -23
+    assert pkg.orb_validate(pkg.orb_params(edge_threshold=4097)) == -23
+    assert pkg.orb_validate(pkg.orb_params(edge_threshold=18)) == 0
+    assert pkg.orb_validate(pkg.orb_params(edge_threshold=4096)) == 0
+    imgs = torch.zeros((1, 64, 64), dtype=torch.uint8, device="cuda:0")
+    kp = torch.full((1, 4, 2), 32.0, dtype=torch.float32, device="cuda:0")
+    cn = torch.full((1,), 4, dtype=torch.int32, device="cuda:0")
+    desc = torch.zeros((1, 4, 32), dtype=torch.uint8, device="cuda:0")
+    assert _raw_call(bm, pkg, imgs, kp, cn, pattern, 4, desc, edge=17) == -23
+    assert _raw_call(bm, pkg, imgs, kp, cn, pattern, 4, desc, edge=4097) == -23
+    assert int(cn[0]) == 4                                  # a refused call writes nothing
+    img = np.random.default_rng(7).integers(0, 256, (80, 100), dtype=np.uint8)
+    k = random_kpts(np.random.default_rng(8), 100, 80, 50)
+    d, kk, cc, bl = run_describe(bm, img[None], [k], pattern, edge=4096)
+    assert cc[0] == 0 and not d.any() and not bl.any()
+
+
+def _raw_call(bm, pkg, imgs, kp, cn, pattern, cap, desc, kout=None, cout=None, sync=1, edge=19):
     L = pkg.load_library()
-    p = pkg.orb_params()
+    p = pkg.orb_params(edge_threshold=edge)
     pat = np.ascontiguousarray(pattern, dtype=np.int32).reshape(-1)
     n, h, w = imgs.shape
     kout = kp if kout is None else kout

@@ -53,8 +53,29 @@ def test_null_arguments(pkg):
                              ctypes.byref(k)) == -1
 
 
+def test_plan_null_and_size_checks(pkg):
+    L = pkg.load_library()
+    pl = pkg.MatchPlanInfo()
+    size = ctypes.sizeof(pl)
+    assert size == 40
+    assert L.sbm_match_plan(300, 1, None, size) == -1
+    assert L.sbm_match_plan(0, 0, None, 0) == -1                      # the null check comes first
+    for wrong in (0, size - 8, size - 1, size + 1, 2 * size):
+        pl.nslice = 77
+        assert L.sbm_match_plan(300, 1, ctypes.byref(pl), wrong) == -2
+        assert pl.nslice == 77                                        # a mirror of another size is not written to
+    assert L.sbm_match_plan(300, 1, ctypes.byref(pl), size) == 0
+    assert (pl.qtiles, pl.nslice, pl.slice_rows, pl.jobs_per_launch, pl.launches) == (5, 5, 64, 1, 1)
+    assert (pl.proj_jobs_per_launch, pl.proj_launches, pl.pad, pl.scratch_bytes) == (1, 1, 0, 300 * 88)
+    assert L.sbm_match_plan(65536, 1, ctypes.byref(pl), size) == -2   # a refused shape leaves a zeroed plan
+    assert (pl.nslice, pl.slice_rows, pl.scratch_bytes) == (0, 0, 0)
+    got = pkg.match_plan(300, 65)
+    assert (got.jobs_per_launch, got.launches, got.proj_launches) == (64, 2, 3)
+
+
 def test_the_contract_is_documented():
     h = (ROOT / "include" / "sbm.h").read_text()
+    assert "sbm_match_plan_info" in h and "int sbm_match_plan(int cap, int m" in h
     for k in ("match_knn", "match_unique", "match_total", "match_project"):
         assert f'"{k}"' in h
     assert "bit 256" in h and "nt == 1" in h and "NOT reproduced" in h

@@ -23,7 +23,7 @@ from .stereobm import (StereoBM, StereoBMError, SbmParams, StereoModel, library_
                        FpgaPlan, fpga_plan,
                        GfttSelectParams, gftt_select_params, gftt_select_validate, gftt_select_capacity,
                        GfttCvParams, gftt_cv_params, gftt_cv_validate,
-                       OrbParams, orb_params, orb_validate, MatchParams, match_params, match_validate,
+                       OrbParams, orb_params, orb_validate, MatchParams, MatchPlanInfo, match_params, match_plan, match_validate,
                        PnpParams, pnp_params, pnp_validate, pnp_records, PNP_RESULT_DTYPE, PNP_HYP_DTYPE,
                        LkParams, lk_params, lk_validate, lk_level_sizes, LK_GET_MIN_EIGENVALS, LK_USE_INITIAL_FLOW)
 from .stereosgbm import StereoSGBM, SgbmParams, sgbm_params, sgbm_validate  # noqa: F401
@@ -45,7 +45,7 @@ __all__ = ["StereoBM", "StereoBMError", "SbmParams", "StereoModel", "library_pat
            "FpgaPlan", "fpga_plan",
            "StereoSGBM", "SgbmParams", "sgbm_params", "sgbm_validate", "GfttSelectParams", "gftt_select_params",
            "gftt_select_validate", "gftt_select_capacity", "OrbParams", "orb_params", "orb_validate", "MatchParams",
-           "match_params", "match_validate", "PnpParams", "pnp_params", "pnp_validate", "pnp_records", "PNP_RESULT_DTYPE",
+           "match_params", "match_plan", "MatchPlanInfo", "match_validate", "PnpParams", "pnp_params", "pnp_validate", "pnp_records", "PNP_RESULT_DTYPE",
            "PNP_HYP_DTYPE", "GfttCvParams", "gftt_cv_params", "gftt_cv_validate", "LkParams", "lk_params", "lk_validate",
            "lk_level_sizes", "LK_GET_MIN_EIGENVALS", "LK_USE_INITIAL_FLOW", "OccupancyMap", "OccParams", "occ_params", "occ_validate",
            "occ_write_binary", "ERR_OCC_FULL", "OccRayParams", "occ_ray_params", "occ_ray_validate", "occ_ray_logodds",

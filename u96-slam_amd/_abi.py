@@ -101,6 +101,13 @@ class MatchParams(ctypes.Structure):
     _fields_ = [("nndr", ctypes.c_float), ("radius", ctypes.c_float)]
 
 
+class MatchPlanInfo(ctypes.Structure):
+    """`sbm_match_plan_info` of include/sbm.h: the launch plan of a matching / projection call, a function of (cap, m)."""
+
+    _fields_ = [(k, ctypes.c_int32) for k in ("qtiles", "nslice", "slice_rows", "jobs_per_launch", "launches",
+                                              "proj_jobs_per_launch", "proj_launches", "pad")] + [("scratch_bytes", ctypes.c_int64)]
+
+
 class PnpParams(ctypes.Structure):
     """`sbm_pnp_params` of include/sbm.h: estimateMotion's minInliers, refineIterations and solvePnPRansac's constants."""
 
@@ -328,6 +335,7 @@ def load_library():
     L.sbm_match_params_default.argtypes = [mp_]
     L.sbm_match_params_default.restype = None
     L.sbm_match_params_validate.argtypes = [mp_]
+    L.sbm_match_plan.argtypes = [ci, ci, vp, sz]
     L.sbm_match_device.argtypes = [vp, ci, ci, vp, vp, vp, ci, mp_, vp, vp, vp, ci]
     L.sbm_match_guess_device.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, mp_, vp, vp, vp, ci]
     L.sbm_project_points_device.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, vp, ci, ci, vp, ci]

@@ -4,7 +4,7 @@ import ctypes
 
 import numpy as np
 
-from ._abi import MatchParams, StereoBMError, _check, _torch, load_library
+from ._abi import MatchParams, MatchPlanInfo, StereoBMError, _check, _torch, load_library
 from ._engine import _count_values, _jobs_array
 
 
@@ -16,6 +16,14 @@ def match_params(nndr=0.8, radius=40.0):
 def match_validate(params):
     """Status code of sbm_match_params_validate (0 = ok)."""
     return load_library().sbm_match_params_validate(ctypes.byref(params))
+
+
+def match_plan(cap, m=1):
+    """The launch plan of a matching / projection call over m jobs on a store of capacity cap (sbm_match_plan: no handle, no
+    device). Raises StereoBMError for a cap or m the calls refuse."""
+    pl = MatchPlanInfo()
+    _check(load_library().sbm_match_plan(int(cap), int(m), ctypes.byref(pl), ctypes.sizeof(pl)))
+    return pl
 
 
 def _desc_rows(d):

@@ -29,7 +29,6 @@ constexpr int kMaxSlice = 32;    // train slices per query tile, at most
 constexpr int kArgJobs = 64;     // jobs per launch: their (from, to) pairs travel as a kernel argument
 constexpr int kProjJobs = 32;    // jobs per projection launch (their transforms travel as a kernel argument)
 constexpr int kTargetWaves = 8192;                        // slices are added until a launch has about this many wavefronts
-constexpr size_t kScratchBudget = (size_t)256 << 20;      // partial records + owner + accepted tables of one launch
 
 struct MatchJobs {
   int2 j[kArgJobs];   // (from frame, to frame)
@@ -216,11 +215,47 @@ using namespace sbm;
 
 static bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
 
-static int match_check(int n, int m, const int* jobs, int cap, const void* d_desc, const void* d_count, const void* d_pairs,
-                       const void* d_npairs, const void* d_knn) {
-  if (n <= 0 || m <= 0) return SBM_ERR_BATCH;
+// The limits on a call's job count and store capacity, shared by the checks and the plan.
+static int match_limits(int m, int cap) {
+  if (m <= 0) return SBM_ERR_BATCH;
   if (cap < 1 || cap > 65535) return SBM_ERR_SIZE;
   if (m > 65535) return SBM_ERR_UNSUPPORTED;
+  return SBM_OK;
+}
+
+// The plan of one call: everything the host decides before it launches anything, as plain data, computed without a HIP call.
+// match_run and project_run execute it and recompute nothing; sbm_match_plan (include/sbm.h) copies it out.
+//   slices   added until a launch has about kTargetWaves wavefronts, at most kMaxSlice, each a whole number of LDS stages; the
+//            count is then what those rows need, so the last slice is never empty at nt == cap.
+//   scratch  per job: nslice partial records (16 bytes) + owner + accepted (4 bytes each) per slot. For every legal (cap, m)
+//            jobs_per_launch == min(m, kArgJobs) and scratch_bytes <= 96 MiB, well within the 256 MiB the header promises
+//            (tests/test_match_plan.py enumerates every cap through the export), so no budget clamp cuts the jobs per launch.
+static int match_plan(int cap, int m, sbm_match_plan_info* pl) {
+  memset(pl, 0, sizeof(*pl));
+  const int st = match_limits(m, cap);
+  if (st != SBM_OK) return st;
+  const int qtiles = (cap + kTile - 1) / kTile;
+  const int mj = std::min(m, kArgJobs);
+  int nslice = std::max(1, (kTargetWaves + qtiles * mj - 1) / (qtiles * mj));
+  nslice = std::min({nslice, kMaxSlice, (cap + kStage - 1) / kStage});
+  const int slice_rows = ((cap + nslice - 1) / nslice + kStage - 1) / kStage * kStage;
+  nslice = (cap + slice_rows - 1) / slice_rows;
+  pl->qtiles = qtiles;
+  pl->nslice = nslice;
+  pl->slice_rows = slice_rows;
+  pl->jobs_per_launch = mj;
+  pl->launches = (m + mj - 1) / mj;
+  pl->proj_jobs_per_launch = std::min(m, kProjJobs);
+  pl->proj_launches = (m + kProjJobs - 1) / kProjJobs;
+  pl->scratch_bytes = (int64_t)mj * cap * (16 * (int64_t)nslice + 8);
+  return SBM_OK;
+}
+
+static int match_check(int n, int m, const int* jobs, int cap, const void* d_desc, const void* d_count, const void* d_pairs,
+                       const void* d_npairs, const void* d_knn) {
+  if (n <= 0) return SBM_ERR_BATCH;
+  const int st = match_limits(m, cap);
+  if (st != SBM_OK) return st;
   for (int j = 0; j < 2 * m; j++)
     if (jobs[j] < 0 || jobs[j] >= n) return SBM_ERR_SIZE;
   if (misaligned(d_desc, 16) || misaligned(d_count, 4) || misaligned(d_pairs, 8) || misaligned(d_npairs, 4) ||
@@ -243,15 +278,11 @@ static int match_run(sbm_handle* h, int m, const int* jobs, const void* d_desc, 
   const int reading = env_switch("SBM_CV_READING", 0);
   const int fused = (reading & kReadMatchFusedL2) ? 1 : 0;
   const float thr = radius_threshold(p->radius);
-  const int qtiles = (cap + kTile - 1) / kTile;
-  const int mj_max = std::min(m, kArgJobs);
-  int nslice = std::max(1, (kTargetWaves + qtiles * mj_max - 1) / (qtiles * mj_max));
-  nslice = std::min({nslice, kMaxSlice, (cap + kStage - 1) / kStage});
-  const int slice_rows = ((cap + nslice - 1) / nslice + kStage - 1) / kStage * kStage;
-  nslice = (cap + slice_rows - 1) / slice_rows;
-  const size_t per_job = (size_t)cap * (16 * (size_t)nslice + 8);
-  const int mj = (int)std::max<size_t>(1, std::min<size_t>(mj_max, kScratchBudget / per_job));
-  HIPCHK(h, h->mt.scratch.grow(per_job * mj, h->stream));
+  sbm_match_plan_info pl;
+  const int pst = match_plan(cap, m, &pl);
+  if (pst != SBM_OK) return pst;
+  const int qtiles = pl.qtiles, nslice = pl.nslice, slice_rows = pl.slice_rows, mj = pl.jobs_per_launch;
+  HIPCHK(h, h->mt.scratch.grow((size_t)pl.scratch_bytes, h->stream));
   int4* part = h->mt.scratch.as<int4>();
   int* owner = (int*)(part + (size_t)mj * nslice * cap);
   int* acc = owner + (size_t)mj * cap;
@@ -291,8 +322,12 @@ static int match_run(sbm_handle* h, int m, const int* jobs, const void* d_desc, 
 static int project_run(sbm_handle* h, int m, const int* from, const void* d_xyz, const void* d_count, int cap, const float* T,
                        const double* K, int W, int H, void* d_proj) {
   StageClock& clk = h->mt.clock;
-  for (int j0 = 0; j0 < m; j0 += kProjJobs) {
-    const int k = std::min(kProjJobs, m - j0);
+  sbm_match_plan_info pl;
+  const int pst = match_plan(cap, m, &pl);
+  if (pst != SBM_OK) return pst;
+  const int pj = pl.proj_jobs_per_launch;
+  for (int j0 = 0; j0 < m; j0 += pj) {
+    const int k = std::min(pj, m - j0);
     ProjJobs a;
     memset(&a, 0, sizeof(a));
     for (int j = 0; j < k; j++) {
@@ -334,6 +369,12 @@ int sbm_match_params_validate(const sbm_match_params* p) {
   if (!std::isfinite(p->nndr) || !std::isfinite(p->radius)) return SBM_ERR_UNSUPPORTED;
   if (!(p->nndr > 0.f && p->nndr <= 1.f) || !(p->radius > 0.f)) return SBM_ERR_UNSUPPORTED;
   return SBM_OK;
+}
+
+int sbm_match_plan(int cap, int m, sbm_match_plan_info* out, size_t out_bytes) {
+  if (!out) return SBM_ERR_NULL;
+  if (out_bytes != sizeof(sbm_match_plan_info)) return SBM_ERR_SIZE;
+  return match_plan(cap, m, out);
 }
 
 int sbm_match_device(sbm_handle* h, int n, int m, const int* jobs, const void* d_desc, const void* d_count, int cap,

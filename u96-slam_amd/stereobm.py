@@ -20,13 +20,13 @@ import numpy as np
 from . import _engine, _fpga, _frontend, _gftt, _lk, _match, _orb, _pnp
 from ._abi import (PNP_FEW_MATCHES, PNP_FEW_RANSAC_INLIERS, PNP_FEW_REFINED_INLIERS, PNP_HYP_DTYPE, PNP_NO_MODEL, PNP_OK,  # noqa: F401
                    PNP_RESULT_DTYPE, PREFILTER_FLAVOUR_CV, PREFILTER_FLAVOUR_RTL, PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL,
-                   FpgaParams, FpgaPlan, GfttCvParams, GfttSelectParams, LK_GET_MIN_EIGENVALS, LK_USE_INITIAL_FLOW, LkParams, MatchParams, OrbParams, PnpParams, RectCam, SbmParams, StereoBMError,
+                   FpgaParams, FpgaPlan, GfttCvParams, GfttSelectParams, LK_GET_MIN_EIGENVALS, LK_USE_INITIAL_FLOW, LkParams, MatchParams, MatchPlanInfo, OrbParams, PnpParams, RectCam, SbmParams, StereoBMError,
                    StereoModel, _check, library_path, load_library, loaded_library_name)
 from ._fpga import fpga_params, fpga_params_from_regs, fpga_plan, fpga_sad_size_reg, fpga_validate  # noqa: F401
 from ._frontend import make_rect_cam  # noqa: F401
 from ._gftt import gftt_cv_params, gftt_cv_validate, gftt_select_capacity, gftt_select_params, gftt_select_validate  # noqa: F401
 from ._lk import lk_level_sizes, lk_params, lk_validate  # noqa: F401
-from ._match import match_params, match_validate  # noqa: F401
+from ._match import match_params, match_plan, match_validate  # noqa: F401
 from ._orb import orb_params, orb_pattern_array, orb_validate  # noqa: F401
 from ._pnp import pnp_params, pnp_records, pnp_validate  # noqa: F401
 
