@@ -5,11 +5,11 @@ updateNode(key, true) on the accepted ones, getNumLeafNodes(), size() and the by
 
 Run by hand, never by a test:
 
-    python tools/make_occupancy_fixtures.py --reference /path/to/U96-SLAM
+    python tools/make_occupancy_fixtures.py --reference /path/to/U96-SLAM [--out DIR]
 
-It compiles the driver below (this project's text) against the octomap sources vendored in the reference tree
-(src/slam/src/octomap/*.cpp, headers under src/slam/include) into a temporary directory, feeds it the points and keeps only
-inputs and recorded outputs. The points are made here from disparity planes and poses through the front half of
+It compiles its driver, tools/octomap_drivers/hits.cpp (this project's text), against the octomap sources vendored in the
+reference tree (src/slam/src/octomap/*.cpp, headers under src/slam/include; tools/octomap_kit.py builds them once, outside the
+history), feeds it the points and keeps only inputs and recorded outputs. The points are made here from disparity planes and poses through the front half of
 oracle/occupancy_ref (reprojection and the two transforms), so that the GPU tests can feed the very same cases as planes:
 
     scene   three 40 x 30 planes of a sloped scene (rows from 55 m down to 0.9 m, some invalid pixels) through three poses
@@ -20,92 +20,14 @@ oracle/occupancy_ref (reprojection and the two transforms), so that the GPU test
     norm    1 x 1 planes under a model whose local transform has a zero rotation block and the translation (15, 20, 0) -- norm
             exactly 25 -- through scaling and translating poses: offsets on both sides of norm 25
 """
-import argparse
-import hashlib
-import pathlib
 import struct
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 
-ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle"))
-import occupancy_ref as occ  # noqa: E402
+import octomap_kit as kit
+from octomap_kit import down, f32, occ, up, voxel
 
-OUT = ROOT / "tests" / "golden" / "occupancy_octomap.npz"
 NGROUPS = 3   # tree 0: every accepted point; tree 1: the blocks alone; tree 2: nothing
-
-DRIVER = r"""
-// Driver of tools/make_occupancy_fixtures.py: the calls of buildOccupancyGridMap's inner loop on recorded points.
-#include <octomap/octomap.h>
-#include <cstdio>
-#include <cstdint>
-#include <sstream>
-#include <vector>
-
-int main(int argc, char** argv) {
-  if (argc != 3) return 2;
-  FILE* in = fopen(argv[1], "rb");
-  FILE* out = fopen(argv[2], "wb");
-  if (!in || !out) return 2;
-  double resolution;
-  float range_max;
-  int32_t n, groups;
-  if (fread(&resolution, 8, 1, in) != 1 || fread(&range_max, 4, 1, in) != 1 || fread(&n, 4, 1, in) != 1 ||
-      fread(&groups, 4, 1, in) != 1)
-    return 3;
-  std::vector<float> pts(6 * (size_t)n);
-  std::vector<uint8_t> mask(n);
-  if (fread(pts.data(), 4, pts.size(), in) != pts.size() || fread(mask.data(), 1, n, in) != (size_t)n) return 3;
-  float rangeMaxSqrd = range_max * range_max;
-  std::vector<octomap::OcTree*> trees;
-  for (int g = 0; g < groups; g++) trees.push_back(new octomap::OcTree(resolution));
-  for (int i = 0; i < n; i++) {
-    const float* p = &pts[6 * (size_t)i];
-    octomap::point3d pt(p[0], p[1], p[2]);
-    octomap::point3d sensorOrigin(p[3], p[4], p[5]);
-    octomap::point3d v(pt.x() - sensorOrigin.x(), pt.y() - sensorOrigin.y(), pt.z() - sensorOrigin.z());
-    double norm = v.norm();
-    octomap::OcTreeKey key(0, 0, 0);
-    uint8_t ok = trees[0]->coordToKeyChecked(pt, key) ? 1 : 0;
-    uint16_t k[3] = {0, 0, 0};
-    if (ok) { k[0] = key[0]; k[1] = key[1]; k[2] = key[2]; }
-    fwrite(&norm, 8, 1, out);
-    fwrite(&ok, 1, 1, out);
-    fwrite(k, 2, 3, out);
-    if (norm <= rangeMaxSqrd && ok)
-      for (int g = 0; g < groups; g++)
-        if (mask[i] >> g & 1) trees[g]->updateNode(key, true);
-  }
-  for (int g = 0; g < groups; g++) {
-    std::ostringstream s;
-    trees[g]->writeBinary(s);
-    uint32_t leafs = (uint32_t)trees[g]->getNumLeafNodes(), size = (uint32_t)trees[g]->size();
-    std::string b = s.str();
-    uint32_t len = (uint32_t)b.size();
-    fwrite(&leafs, 4, 1, out);
-    fwrite(&size, 4, 1, out);
-    fwrite(&len, 4, 1, out);
-    fwrite(b.data(), 1, len, out);
-  }
-  fclose(out);
-  return 0;
-}
-"""
-
-
-def f32(v):
-    return np.float32(v)
-
-
-def up(v):
-    return np.nextafter(f32(v), f32(np.inf))
-
-
-def down(v):
-    return np.nextafter(f32(v), f32(-np.inf))
 
 
 def scene():
@@ -155,16 +77,13 @@ def edge_points():
     axis_values([edge, f32(3276.8), down(3276.8), up(3276.8), f32(-3276.8), up(-3276.8), down(-3276.8), f32(3276.9), f32(-3276.9),
                  f32(2e8), f32(-2e8), f32(3e9), f32(-3e9), f32(1e10), f32(3e38), f32(np.inf), f32(-np.inf), f32(np.nan)])
 
-    def voxel(j):   # centre of the voxel with key 32768 + j
-        return f32((j + 0.5) * 0.1)
-
     def cube(base, size, skip=None):
         for i in range(size):
             for j in range(size):
                 for k in range(size):
                     if (i, j, k) == skip:
                         continue
-                    pts.append([voxel(base[0] + i), voxel(base[1] + j), voxel(base[2] + k)])
+                    pts.append([f32(voxel(base[0] + i)), f32(voxel(base[1] + j)), f32(voxel(base[2] + k))])
                     block.append(True)
 
     cube((1000, -2000, 400), 2)                 # collapses one level
@@ -186,10 +105,7 @@ def norm_poses():
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--reference", required=True, help="checkout of the reference project (read only)")
-    args = ap.parse_args()
-    ref = pathlib.Path(args.reference) / "src" / "slam"
+    args = kit.arguments(__doc__)
     resolution, range_max, scale = 0.1, np.float32(5.0), 4
 
     scene_disp, scene_poses, m = scene()
@@ -218,35 +134,21 @@ def main():
     group = np.concatenate(group)
     n = len(pts)
 
-    with tempfile.TemporaryDirectory() as tmp:
-        tmp = pathlib.Path(tmp)
-        (tmp / "driver.cpp").write_text(DRIVER)
-        srcs = sorted(str(p) for p in (ref / "src" / "octomap").glob("*.cpp"))
-        subprocess.run(["g++", "-O1", "-std=c++11", "-I", str(ref / "include"), "-I", str(ref / "include" / "octomap"), "-o",
-                        str(tmp / "driver"), str(tmp / "driver.cpp")] + srcs, check=True)
-        with open(tmp / "in.bin", "wb") as f:
-            f.write(struct.pack("<dfii", resolution, float(range_max), n, NGROUPS))
-            f.write(np.concatenate([pts, origins], axis=1).astype(np.float32).tobytes())
-            f.write(group.tobytes())
-        subprocess.run([str(tmp / "driver"), str(tmp / "in.bin"), str(tmp / "out.bin")], check=True)
-        raw = (tmp / "out.bin").read_bytes()
-    rec = np.frombuffer(raw[:15 * n], np.dtype([("norm", "<f8"), ("ok", "u1"), ("key", "<u2", 3)]))
-    off = 15 * n
-    trees = {}
-    for name in ("all", "blocks", "empty"):
-        leafs, size, length = struct.unpack_from("<III", raw, off)
-        off += 12
-        trees[name] = (leafs, size, np.frombuffer(raw[off:off + length], np.uint8))
-        off += length
-    assert off == len(raw)
+    code, raw = kit.run(kit.build(args.reference, "hits"), "hits", lambda f: f.write(
+        struct.pack("<dfii", resolution, float(range_max), n, NGROUPS) + np.concatenate([pts, origins], axis=1).astype(np.float32).tobytes() +
+        group.tobytes()))
+    assert code == 0, code
+    r = kit.Reader(raw)
+    rec = r.take(np.dtype([("norm", "<f8"), ("ok", "u1"), ("key", "<u2", 3)]), n)
+    trees = {name: (r.one("<u4"), r.one("<u4"), r.stream()) for name in ("all", "blocks", "empty")}
+    r.done()
     out = dict(resolution=np.float64(resolution), range_max=range_max, scale=np.int32(scale), model=occ.model_to_array(m),
                model_edge=occ.model_to_array(m_edge), scene_disp=scene_disp, scene_poses=scene_poses, edge_disp=edge_disp,
                edge_poses=edge_poses, norm_poses=nposes, points=pts, origins=origins, group=group, norm=rec["norm"].copy(),
                ok=rec["ok"].copy(), keys=rec["key"].copy())
     for name, (leafs, size, data) in trees.items():
         out[f"leafs_{name}"], out[f"size_{name}"], out[f"bt_{name}"] = np.uint32(leafs), np.uint32(size), data
-    np.savez_compressed(OUT, **out)
-    OUT.with_suffix(".sha256").write_text(hashlib.sha256(OUT.read_bytes()).hexdigest() + "  " + OUT.name + "\n")
+    OUT = kit.save(args.out, "octomap", out, kit.numpy_npz)
     gate = rec["norm"] <= float(range_max * range_max)
     print(f"{OUT}: {OUT.stat().st_size} bytes, {n} points, {int(rec['ok'].sum())} keyed, {int((gate & (rec['ok'] == 1)).sum())} "
           f"accepted, norms above the gate {int((~gate & np.isfinite(rec['norm'])).sum())}; trees "

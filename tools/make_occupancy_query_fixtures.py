@@ -8,10 +8,11 @@ that the .npz regenerates to the same bytes).
 
 Run by hand, never by a test:
 
-    python tools/make_occupancy_query_fixtures.py --reference /path/to/U96-SLAM
+    python tools/make_occupancy_query_fixtures.py --reference /path/to/U96-SLAM [--out DIR]
 
-It compiles the driver below (this project's text; it calls octomap's API only) against the octomap sources vendored in the
-reference tree into a temporary directory, and keeps only inputs and recorded outputs. Log-odds trees are built with
+It compiles its driver, tools/octomap_drivers/query.cpp (this project's text; it calls octomap's API only), against the octomap
+sources vendored in the reference tree (tools/octomap_kit.py builds them once, outside the history), and keeps only inputs and
+recorded outputs. Log-odds trees are built with
 insertPointCloud of recorded scans, the hit tree with updateNode(key, true) over a recorded key list. The statuses beside
 octomap's answers are the transcription's (tests/occupancy_query_cases.py); the generator asserts that they agree with every
 recorded return value and `end`. Trees and query sets:
@@ -34,149 +35,17 @@ recorded return value and `end`. Trees and query sets:
       random   1024 random rays with max_range 6
       search   512 points, every second on a voxel face
 """
-import argparse
-import hashlib
-import io
-import json
-import pathlib
+import functools
 import struct
-import subprocess
-import sys
-import tempfile
-import zipfile
 
 import numpy as np
 
-ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle"))
-sys.path.insert(0, str(ROOT / "tests"))
-sys.path.insert(0, str(ROOT / "tools"))
-import bench_occupancy_rays as bench  # noqa: E402
-import make_occupancy_fixtures as hitfix  # noqa: E402
-import occupancy_query_cases as qc  # noqa: E402
-import occupancy_ray_cases as rc  # noqa: E402
-
-OUT = ROOT / "tests" / "golden" / "occupancy_query.npz"
-CPU = ROOT / "tests" / "golden" / "occupancy_query_cpu.json"
-RESOLUTION = 0.1
-PROBS = ("prob_hit", "prob_miss", "clamp_min", "clamp_max", "occupancy_thres")
-BENCH_PLANES, BENCH_RANGE = 4, 25.0
-
-DRIVER = r"""
-// Driver of tools/make_occupancy_query_fixtures.py: trees from recorded scans or key lists, then search and castRay.
-#include <octomap/octomap.h>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdint>
-#include <vector>
-
-template <class T> static bool rd(FILE* f, T* p, size_t n) { return fread(p, sizeof(T), n, f) == n; }
-
-int main(int argc, char** argv) {
-  if (argc != 3) return 2;
-  FILE* in = fopen(argv[1], "rb");
-  FILE* out = fopen(argv[2], "wb");
-  if (!in || !out) return 2;
-  int32_t ntrees;
-  if (!rd(in, &ntrees, 1)) return 3;
-  for (int t = 0; t < ntrees; t++) {
-    double prob[5], resolution;
-    int32_t hits, nscans, nsets;
-    if (!rd(in, prob, 5) || !rd(in, &resolution, 1) || !rd(in, &hits, 1) || !rd(in, &nscans, 1)) return 3;
-    octomap::OcTree tree(resolution);
-    tree.setProbHit(prob[0]);
-    tree.setProbMiss(prob[1]);
-    tree.setClampingThresMin(prob[2]);
-    tree.setClampingThresMax(prob[3]);
-    tree.setOccupancyThres(prob[4]);
-    float constants[5] = {tree.getProbHitLog(), tree.getProbMissLog(), tree.getClampingThresMinLog(), tree.getClampingThresMaxLog(),
-                          tree.getOccupancyThresLog()};
-    fwrite(constants, 4, 5, out);
-    if (hits) {       // nscans counts keys
-      std::vector<uint16_t> k(3 * (size_t)nscans);
-      if (!rd(in, k.data(), k.size())) return 3;
-      for (int i = 0; i < nscans; i++) tree.updateNode(octomap::OcTreeKey(k[3 * i], k[3 * i + 1], k[3 * i + 2]), true);
-    } else {
-      for (int s = 0; s < nscans; s++) {
-        float o[3];
-        double max_range;
-        int32_t n;
-        if (!rd(in, o, 3) || !rd(in, &max_range, 1) || !rd(in, &n, 1)) return 3;
-        std::vector<float> pts(3 * (size_t)n);
-        if (!rd(in, pts.data(), pts.size())) return 3;
-        octomap::Pointcloud scan;
-        for (int i = 0; i < n; i++) scan.push_back(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
-        tree.insertPointCloud(scan, octomap::point3d(o[0], o[1], o[2]), max_range);
-      }
-    }
-    {
-      octomap::OcTree copy(tree);
-      copy.expand();
-      std::vector<uint16_t> keys;
-      std::vector<float> values;
-      for (octomap::OcTree::leaf_iterator it = copy.begin_leafs(), end = copy.end_leafs(); it != end; ++it) {
-        if (it.getDepth() != 16) return 4;
-        octomap::OcTreeKey k = it.getKey();
-        keys.push_back(k[0]);
-        keys.push_back(k[1]);
-        keys.push_back(k[2]);
-        values.push_back(it->getLogOdds());
-      }
-      uint32_t leaves = (uint32_t)values.size();
-      fwrite(&leaves, 4, 1, out);
-      fwrite(keys.data(), 2, keys.size(), out);
-      fwrite(values.data(), 4, values.size(), out);
-    }
-    if (!rd(in, &nsets, 1)) return 3;
-    for (int q = 0; q < nsets; q++) {
-      int32_t npoints, nrays, timing;
-      if (!rd(in, &npoints, 1) || !rd(in, &nrays, 1) || !rd(in, &timing, 1)) return 3;
-      for (int i = 0; i < npoints; i++) {
-        float p[3];
-        if (!rd(in, p, 3)) return 3;
-        octomap::OcTreeNode* node = tree.search(octomap::point3d(p[0], p[1], p[2]));
-        int32_t found = node ? 1 : 0, occupied = node && tree.isNodeOccupied(node) ? 1 : 0;
-        float value = node ? node->getLogOdds() : 0.f;
-        fwrite(&found, 4, 1, out);
-        fwrite(&occupied, 4, 1, out);
-        fwrite(&value, 4, 1, out);
-      }
-      std::vector<float> rays(6 * (size_t)nrays);
-      std::vector<int32_t> ignore(nrays);
-      std::vector<double> range(nrays);
-      for (int i = 0; i < nrays; i++)
-        if (!rd(in, &rays[6 * i], 6) || !rd(in, &ignore[i], 1) || !rd(in, &range[i], 1)) return 3;
-      std::vector<int32_t> ret(nrays);
-      std::vector<float> ends(3 * (size_t)nrays);
-      auto t0 = std::chrono::steady_clock::now();
-      for (int i = 0; i < nrays; i++) {
-        const float* r = &rays[6 * i];
-        octomap::point3d end(NAN, NAN, NAN);
-        ret[i] = tree.castRay(octomap::point3d(r[0], r[1], r[2]), octomap::point3d(r[3], r[4], r[5]), end, ignore[i] != 0, range[i]) ? 1 : 0;
-        ends[3 * i] = end.x();
-        ends[3 * i + 1] = end.y();
-        ends[3 * i + 2] = end.z();
-      }
-      double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      if (timing) {
-        fwrite(&ms, 8, 1, out);
-      } else {
-        fwrite(ret.data(), 4, ret.size(), out);
-        fwrite(ends.data(), 4, ends.size(), out);
-      }
-    }
-  }
-  fclose(out);
-  return 0;
-}
-"""
+import octomap_kit as kit
+from octomap_kit import BENCH_PLANES, BENCH_RANGE, PROBS, RESOLUTION, bench, occ, rc
+import occupancy_query_cases as qc
 
 F = np.float32
-
-
-def voxel(j):
-    return ((np.asarray(j, np.float64) + 0.5) * RESOLUTION).astype(np.float32)
+voxel = functools.partial(kit.voxel, dtype=np.float32)
 
 
 def rays(rows):
@@ -203,7 +72,7 @@ def view_rays_numpy(width, height, scale, m, pose):
 
 
 def scene_sets(hits):
-    disp, poses, m = hitfix.scene()
+    disp, poses, m = kit.scene("query")
     rng = np.random.default_rng(23)
     o, d = view_rays_numpy(40, 30, 4, m, poses[0])
     qo, qd = qc.view_rays(40, 30, 4, m, poses[0])
@@ -295,19 +164,17 @@ def make_trees():
                                    ignore=np.zeros(0, np.int32), max_range=np.zeros(0))
     trees["thres"] = thres
 
-    disp, poses, m = hitfix.scene()
+    disp, poses, m = kit.scene("query")
     trees["scene"] = dict(params=rc.RayParams(), scans=[(pose[[3, 7, 11]], 6.0, rc.plane_points(d, 4, m, pose)) for d, pose in zip(disp, poses)],
                           sets=scene_sets(False))
-    keys, counts = hitfix.occ.insert(disp, 4, m, poses)
+    keys, counts = occ.insert(disp, 4, m, poses)
     trees["scene_hits"] = dict(params=rc.RayParams(), hit_keys=keys, hit_counts=counts, sets=scene_sets(True))
 
-    planes, bposes = bench.synth_planes(BENCH_PLANES)
-    bm = bench.synth_model()
-    o, d = view_rays_numpy(bench.W, bench.H, bench.SCALE, bm, bposes[0])
+    _, bposes = bench.synth_planes(BENCH_PLANES)
+    o, d = view_rays_numpy(bench.W, bench.H, bench.SCALE, bench.synth_model(), bposes[0])
     timing = dict(points=np.zeros((0, 3), np.float32), rays=np.concatenate([o, d], 1), ignore=np.ones(len(o), np.int32),
                   max_range=np.full(len(o), BENCH_RANGE), timing=True)
-    trees["bench"] = dict(params=rc.RayParams(), timing=True, sets={"view": timing},
-                          scans=[(pose[[3, 7, 11]], BENCH_RANGE, rc.plane_points(pl, bench.SCALE, bm, pose)) for pl, pose in zip(planes, bposes)])
+    trees["bench"] = dict(params=rc.RayParams(), timing=True, sets={"view": timing}, scans=kit.bench_scans())
     return trees
 
 
@@ -322,66 +189,33 @@ def restated_map(tree, constants):
     return qc.Map(dict(t.v), qc.LOGODDS, constants[4], RESOLUTION)
 
 
-def write_npz(path, arrays):
-    """np.savez_compressed with fixed member dates: the same arrays give the same bytes."""
-    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
-        for k, v in arrays.items():
-            buf = io.BytesIO()
-            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
-            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
-            info.compress_type = zipfile.ZIP_DEFLATED
-            z.writestr(info, buf.getvalue())
-
-
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--reference", required=True, help="checkout of the reference project (read only)")
-    args = ap.parse_args()
-    ref = pathlib.Path(args.reference) / "src" / "slam"
+    args = kit.arguments(__doc__)
     trees = make_trees()
-    with tempfile.TemporaryDirectory() as tmp:
-        tmp = pathlib.Path(tmp)
-        (tmp / "driver.cpp").write_text(DRIVER)
-        srcs = sorted(str(p) for p in (ref / "src" / "octomap").glob("*.cpp"))
-        subprocess.run(["g++", "-O1", "-std=c++11", "-I", str(ref / "include"), "-I", str(ref / "include" / "octomap"), "-o",
-                        str(tmp / "driver"), str(tmp / "driver.cpp")] + srcs, check=True)
-        with open(tmp / "in.bin", "wb") as f:
-            f.write(struct.pack("<i", len(trees)))
-            for t in trees.values():
-                rp = t["params"]
-                hits = "hit_keys" in t
-                f.write(struct.pack("<6dii", *[getattr(rp, k) for k in PROBS], RESOLUTION, int(hits), len(t["hit_keys"] if hits else t["scans"])))
-                if hits:
-                    f.write(hitfix.occ.unpack(t["hit_keys"]).astype(np.uint16).tobytes())
-                else:
-                    for o, mr, p in t["scans"]:
-                        f.write(np.asarray(o, np.float32).tobytes() + struct.pack("<di", mr, len(p)) + np.asarray(p, np.float32).tobytes())
-                f.write(struct.pack("<i", len(t["sets"])))
-                for s in t["sets"].values():
-                    f.write(struct.pack("<iii", len(s["points"]), len(s["rays"]), int(s.get("timing", False))))
-                    f.write(s["points"].astype(np.float32).tobytes())
-                    for r, ig, mr in zip(s["rays"], s["ignore"], s["max_range"]):
-                        f.write(r.astype(np.float32).tobytes() + struct.pack("<id", int(ig), float(mr)))
-        subprocess.run([str(tmp / "driver"), str(tmp / "in.bin"), str(tmp / "out.bin")], check=True, stderr=subprocess.DEVNULL)
-        raw = (tmp / "out.bin").read_bytes()
+
+    def write(f):
+        f.write(kit.ints(len(trees)))
+        for t in trees.values():
+            hits = "hit_keys" in t
+            f.write(kit.head(t["params"]) + kit.ints(hits) + (kit.hits(t["hit_keys"]) if hits else kit.scans(t["scans"])))   # each key once
+            f.write(kit.ints(len(t["sets"])))
+            for s in t["sets"].values():
+                f.write(kit.ints(s.get("timing", False)) + kit.points(s["points"]) + kit.ints(len(s["rays"])))
+                for r, ig, mr in zip(s["rays"], s["ignore"], s["max_range"]):
+                    f.write(r.astype(np.float32).tobytes() + struct.pack("<id", int(ig), float(mr)))
+
+    code, raw = kit.run(kit.build(args.reference, "query"), "query", write)
+    assert code == 0, code
+    r = kit.Reader(raw)
     out = dict(resolution=np.float64(RESOLUTION), trees=np.array([n for n, t in trees.items() if not t.get("timing")]))
-    off, report, cpu, seen = 0, [], {}, set()
+    report, cpu, seen = [], {}, set()
     for name, t in trees.items():
-        consts = np.frombuffer(raw, np.float32, 5, off).copy()
-        off += 20
-        (n,) = struct.unpack_from("<I", raw, off)
-        off += 4
-        k = np.frombuffer(raw, np.uint16, 3 * n, off).reshape(n, 3).astype(np.uint64)
-        off += 6 * n
-        v = np.frombuffer(raw, np.float32, n, off)
-        off += 4 * n
-        packed = (k[:, 0] << np.uint64(32)) | (k[:, 1] << np.uint64(16)) | k[:, 2]
-        order = np.argsort(packed)
-        keys, values = packed[order], v[order]
+        consts = r.take("<f4", 5).copy()
+        n = r.one("<u4")
+        keys, values = r.voxels(n)
         if t.get("timing"):
             s = t["sets"]["view"]
-            (ms,) = struct.unpack_from("<d", raw, off)
-            off += 8
+            ms = r.one("<f8")
             cpu = dict(scene="tools/bench_occupancy_rays.py synth_planes", planes=BENCH_PLANES, insert_max_range=BENCH_RANGE,
                        view=[bench.W, bench.H, bench.SCALE], ignore_unknown=1, max_range=BENCH_RANGE, rays=len(s["rays"]), leaves=int(n),
                        octomap_ms_per_ray=ms / len(s["rays"]),
@@ -408,12 +242,9 @@ def main():
         for sname, s in t["sets"].items():
             tag = f"{name}_{sname}"
             npts, nr = len(s["points"]), len(s["rays"])
-            rec = np.frombuffer(raw, np.uint32, 3 * npts, off).reshape(npts, 3)
-            off += 12 * npts
-            ret = np.frombuffer(raw, np.int32, nr, off).copy()
-            off += 4 * nr
-            end = np.frombuffer(raw, np.float32, 3 * nr, off).reshape(nr, 3).copy()
-            off += 12 * nr
+            rec = r.take("<u4", 3 * npts).reshape(npts, 3)
+            ret = r.take("<i4", nr).copy()
+            end = r.take("<f4", 3 * nr).reshape(nr, 3).copy()
             if npts:
                 state, value = m.search_all(s["points"])
                 found, occupied = rec[:, 0].astype(bool), rec[:, 1].astype(bool)
@@ -427,8 +258,8 @@ def main():
                 out[f"{tag}_state"] = state
             if nr:
                 status = np.empty(nr, np.int32)
-                for i, (r, ig, mr) in enumerate(zip(s["rays"], s["ignore"], s["max_range"])):
-                    status[i], e = m.cast_ray(r[:3], r[3:], bool(ig), float(mr))
+                for i, (ray, ig, mr) in enumerate(zip(s["rays"], s["ignore"], s["max_range"])):
+                    status[i], e = m.cast_ray(ray[:3], ray[3:], bool(ig), float(mr))
                     assert (status[i] == qc.RAY_HIT) == bool(ret[i]), (tag, i, "return value")
                     assert (status[i] == qc.RAY_NONE) == bool(np.isnan(end[i]).all()), (tag, i, "untouched end")
                     assert status[i] == qc.RAY_NONE or np.array_equal(e.view(np.uint32), end[i].view(np.uint32)), (tag, i, "end")
@@ -442,7 +273,7 @@ def main():
                 report.append(f"{tag}: {nr} rays, statuses {np.bincount(status, minlength=5).tolist()}")
             else:
                 report.append(f"{tag}: {npts} points, states {np.bincount(state + 1, minlength=4).tolist()}")
-    assert off == len(raw)
+    r.done()
     assert seen == {0, 1, 2, 3, 4}, seen
     c = out["thres_constants"]
     assert c[3] == c[4], "thres: the threshold is not the clamp"
@@ -451,11 +282,9 @@ def main():
     assert out["wall2_range_status"].tolist() == [1, 1, 2, 1, 1, 2], out["wall2_range_status"]
     out["wall2_range_values"] = np.array(trees["wall2"]["range_values"], np.float64)
     assert out["gap_gap_status"].tolist() == [3, 3, 1, 2], out["gap_gap_status"]
-    disp, poses, m = hitfix.scene()
-    out["scene_disp"], out["scene_poses"], out["scene_model"], out["scene_scale"] = disp, poses, hitfix.occ.model_to_array(m), np.int32(4)
-    write_npz(OUT, out)
-    OUT.with_suffix(".sha256").write_text(hashlib.sha256(OUT.read_bytes()).hexdigest() + "  " + OUT.name + "\n")
-    CPU.write_text(json.dumps(cpu, indent=1) + "\n")
+    disp, poses, m = kit.scene("query")
+    out["scene_disp"], out["scene_poses"], out["scene_model"], out["scene_scale"] = disp, poses, occ.model_to_array(m), np.int32(4)
+    OUT = kit.save(args.out, "query", out, cpu=cpu)
     print(f"{OUT}: {OUT.stat().st_size} bytes\n  " + "\n  ".join(report))
 
 

@@ -6,10 +6,11 @@ tree and the milliseconds octomap took for one plane of the benchmark's syntheti
 
 Run by hand, never by a test:
 
-    python tools/make_occupancy_ray_fixtures.py --reference /path/to/U96-SLAM
+    python tools/make_occupancy_ray_fixtures.py --reference /path/to/U96-SLAM [--out DIR]
 
-It compiles the driver below (this project's text; it calls octomap's API only) against the octomap sources vendored in the
-reference tree into a temporary directory, feeds it the scans and keeps only inputs and recorded outputs. The cases:
+It compiles its driver, tools/octomap_drivers/rays.cpp (this project's text; it calls octomap's API only), against the octomap
+sources vendored in the reference tree (tools/octomap_kit.py builds them once, outside the history), feeds it the scans and keeps
+only inputs and recorded outputs. The cases:
 
     axes    single rays along +-x, +-y, +-z, one per scan: two steps are 0 and their tMax is the double maximum
     ties    origin at a voxel centre, ends along (+-1, +-1, +-1) * k * 0.1 and (1, 1, 0) * k * 0.1: equal tMax on two and three
@@ -24,108 +25,10 @@ reference tree into a temporary directory, feeds it the scans and keeps only inp
     random  1024 rays from one origin, lengths 0 - 6 m, every second end on a voxel face; the seed is the first whose census has a ray that ends on the length test
     block / mixed   a full 2 x 2 x 2 block of free voxels under a far wall; the same with one voxel hit instead
 """
-import argparse
-import hashlib
-import pathlib
-import struct
-import subprocess
-import sys
-import tempfile
-
 import numpy as np
 
-ROOT = pathlib.Path(__file__).resolve().parents[1]
-sys.path.insert(0, str(ROOT / "oracle"))
-sys.path.insert(0, str(ROOT / "tests"))
-sys.path.insert(0, str(ROOT / "tools"))
-import bench_occupancy_rays as bench  # noqa: E402
-import make_occupancy_fixtures as hitfix  # noqa: E402
-import occupancy_ray_cases as rc  # noqa: E402
-
-OUT = ROOT / "tests" / "golden" / "occupancy_rays.npz"
-RESOLUTION = 0.1
-PROBS = ("prob_hit", "prob_miss", "clamp_min", "clamp_max", "occupancy_thres")
-
-DRIVER = r"""
-// Driver of tools/make_occupancy_ray_fixtures.py: insertPointCloud on recorded scans, the leaves after every scan.
-#include <octomap/octomap.h>
-#include <chrono>
-#include <cstdio>
-#include <cstdint>
-#include <sstream>
-#include <vector>
-
-int main(int argc, char** argv) {
-  if (argc != 3) return 2;
-  FILE* in = fopen(argv[1], "rb");
-  FILE* out = fopen(argv[2], "wb");
-  if (!in || !out) return 2;
-  int32_t ncases;
-  if (fread(&ncases, 4, 1, in) != 1) return 3;
-  for (int c = 0; c < ncases; c++) {
-    double prob[5], max_range, resolution;
-    int32_t nscans, timing;
-    if (fread(prob, 8, 5, in) != 5 || fread(&max_range, 8, 1, in) != 1 || fread(&resolution, 8, 1, in) != 1 ||
-        fread(&nscans, 4, 1, in) != 1 || fread(&timing, 4, 1, in) != 1)
-      return 3;
-    octomap::OcTree tree(resolution);
-    tree.setProbHit(prob[0]);
-    tree.setProbMiss(prob[1]);
-    tree.setClampingThresMin(prob[2]);
-    tree.setClampingThresMax(prob[3]);
-    tree.setOccupancyThres(prob[4]);
-    float constants[5] = {tree.getProbHitLog(), tree.getProbMissLog(), tree.getClampingThresMinLog(), tree.getClampingThresMaxLog(),
-                          tree.getOccupancyThresLog()};
-    fwrite(constants, 4, 5, out);
-    for (int s = 0; s < nscans; s++) {
-      float o[3];
-      int32_t n;
-      if (fread(o, 4, 3, in) != 3 || fread(&n, 4, 1, in) != 1) return 3;
-      std::vector<float> pts(3 * (size_t)n);
-      if (fread(pts.data(), 4, pts.size(), in) != pts.size()) return 3;
-      octomap::Pointcloud scan;
-      for (int i = 0; i < n; i++) scan.push_back(pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
-      octomap::point3d origin(o[0], o[1], o[2]);
-      auto t0 = std::chrono::steady_clock::now();
-      tree.insertPointCloud(scan, origin, max_range);
-      double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      octomap::OcTree copy(tree);
-      copy.expand();
-      std::vector<uint16_t> keys;
-      std::vector<float> values;
-      for (octomap::OcTree::leaf_iterator it = copy.begin_leafs(), end = copy.end_leafs(); it != end; ++it) {
-        if (it.getDepth() != 16) return 4;
-        octomap::OcTreeKey k = it.getKey();
-        keys.push_back(k[0]);
-        keys.push_back(k[1]);
-        keys.push_back(k[2]);
-        values.push_back(it->getLogOdds());
-      }
-      uint32_t leaves = (uint32_t)values.size();
-      fwrite(&leaves, 4, 1, out);
-      if (timing) {
-        fwrite(&ms, 8, 1, out);
-      } else {
-        fwrite(keys.data(), 2, keys.size(), out);
-        fwrite(values.data(), 4, values.size(), out);
-      }
-    }
-    std::ostringstream s;
-    tree.writeBinary(s);
-    std::string b = s.str();
-    uint32_t size = (uint32_t)tree.size(), len = timing ? 0 : (uint32_t)b.size();
-    fwrite(&size, 4, 1, out);
-    fwrite(&len, 4, 1, out);
-    fwrite(b.data(), 1, len, out);
-  }
-  fclose(out);
-  return 0;
-}
-"""
-
-
-def f32(v):
-    return np.float32(v)
+import octomap_kit as kit
+from octomap_kit import PROBS, RESOLUTION, bench, f32, occ, rc, up, voxel
 
 
 def pts(*rows):
@@ -138,23 +41,15 @@ def case(scans, timing=False, **probs):
                 scans=[(np.asarray(o, np.float32), np.asarray(p, np.float32).reshape(-1, 3)) for o, p in scans])
 
 
-def up(v):
-    return np.nextafter(f32(v), f32(np.inf))
-
-
 def clamp_planes():
     """Sixteen 8 x 8 planes at scale 40: a wall 2 m ahead eight times, then 3 m ahead eight times, through poses a few
     millimetres apart. The local transform only rotates, so a pixel's two rays are collinear and the second crosses the first's
     end point. -> (planes, poses, model, scale)"""
     rng = np.random.default_rng(5)
     planes = np.stack([np.full((8, 8), 16 * 24 if k < 8 else 16 * 16, np.int16) for k in range(16)])
-    poses = np.tile(np.asarray(hitfix.occ.pose_rows([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0])), (16, 1))
+    poses = np.tile(np.asarray(occ.pose_rows([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0])), (16, 1))
     poses[:, [3, 7, 11]] = rng.uniform(-0.004, 0.004, (16, 3)).astype(np.float32) + np.float32([0.01, 0.02, 0.03])
-    return planes, poses, hitfix.occ.model(cx=140.0, cy=140.0, local=[0, 0, 1, 0, -1, 0, 0, 0, 0, -1, 0, 0]), 40
-
-
-def voxel(j):
-    return (np.asarray(j, np.float64) + 0.5) * RESOLUTION
+    return planes, poses, occ.model(cx=140.0, cy=140.0, local=[0, 0, 1, 0, -1, 0, 0, 0, 0, -1, 0, 0]), 40
 
 
 def make_cases():
@@ -179,7 +74,7 @@ def make_cases():
     cases["bounds"] = case([((0, 0, 0), np.concatenate([odd, inside])), ((4000.0, 0, 0), np.concatenate([inside, pts((2.0, 0.1, 0.1))])),
                             ((0.5, 0.5, 0.5), np.concatenate([inside, odd]))])
     cases["bounds_range"] = case([((0, 0, 0), np.concatenate([odd[:3], inside]))], max_range=3.0)
-    disp, poses, m = hitfix.scene()
+    disp, poses, m = kit.scene("rays")
     cases["scene"] = case([(pose[[3, 7, 11]], rc.plane_points(d, 4, m, pose)) for d, pose in zip(disp, poses)], max_range=6.0)
     disp, poses, m, scale = clamp_planes()
     cases["clamp"] = case([(pose[[3, 7, 11]], rc.plane_points(d, scale, m, pose)) for d, pose in zip(disp, poses)])
@@ -213,10 +108,8 @@ def make_cases():
     mixed = beyond.copy()
     mixed[5] = block[5]
     cases["mixed"] = case([(centre, mixed)])
-    planes, bposes = bench.synth_planes(1)
-    cloud = rc.plane_points(planes[0], bench.SCALE, bench.synth_model(), bposes[0])
     for r in bench.RANGES:
-        cases[f"bench_{int(r)}"] = case([(bposes[0][[3, 7, 11]], cloud)], timing=True, max_range=r)
+        cases[f"bench_{int(r)}"] = case([(o, p) for o, _, p in kit.bench_scans(1, r)], timing=True, max_range=r)
     return cases
 
 
@@ -249,56 +142,35 @@ def check_cases(cases):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--reference", required=True, help="checkout of the reference project (read only)")
-    args = ap.parse_args()
-    ref = pathlib.Path(args.reference) / "src" / "slam"
+    args = kit.arguments(__doc__)
     cases = make_cases()
     check_cases(cases)
-    with tempfile.TemporaryDirectory() as tmp:
-        tmp = pathlib.Path(tmp)
-        (tmp / "driver.cpp").write_text(DRIVER)
-        srcs = sorted(str(p) for p in (ref / "src" / "octomap").glob("*.cpp"))
-        subprocess.run(["g++", "-O1", "-std=c++11", "-I", str(ref / "include"), "-I", str(ref / "include" / "octomap"), "-o",
-                        str(tmp / "driver"), str(tmp / "driver.cpp")] + srcs, check=True)
-        with open(tmp / "in.bin", "wb") as f:
-            f.write(struct.pack("<i", len(cases)))
-            for c in cases.values():
-                rp = c["params"]
-                f.write(struct.pack("<7dii", *[getattr(rp, k) for k in PROBS], rp.max_range, RESOLUTION, len(c["scans"]), int(c["timing"])))
-                for o, p in c["scans"]:
-                    f.write(o.astype(np.float32).tobytes() + struct.pack("<i", len(p)) + p.astype(np.float32).tobytes())
-        subprocess.run([str(tmp / "driver"), str(tmp / "in.bin"), str(tmp / "out.bin")], check=True, stderr=subprocess.DEVNULL)
-        raw = (tmp / "out.bin").read_bytes()
+
+    def write(f):
+        f.write(kit.ints(len(cases)))
+        for c in cases.values():
+            f.write(kit.head(c["params"]) + kit.ints(c["timing"]) + kit.scans([(o, c["params"].max_range, p) for o, p in c["scans"]]))
+
+    code, raw = kit.run(kit.build(args.reference, "rays"), "rays", write)
+    assert code == 0, code
+    r = kit.Reader(raw)
     out = dict(resolution=np.float64(RESOLUTION), names=np.array([n for n, c in cases.items() if not c["timing"]]))
-    off = 0
     report = []
     for name, c in cases.items():
-        consts = np.frombuffer(raw, np.float32, 5, off).copy()
-        off += 20
+        consts = r.take("<f4", 5).copy()
         counts, keys, values = [], [], []
         for _ in c["scans"]:
-            (n,) = struct.unpack_from("<I", raw, off)
-            off += 4
+            n = r.one("<u4")
             counts.append(n)
             if c["timing"]:
-                (ms,) = struct.unpack_from("<d", raw, off)
-                off += 8
+                ms = r.one("<f8")
                 out[f"{name.replace('bench_', 'bench_cpu_ms_')}"] = np.float64(ms)
                 out[f"{name.replace('bench_', 'bench_leaves_')}"] = np.uint32(n)
                 continue
-            k = np.frombuffer(raw, np.uint16, 3 * n, off).reshape(n, 3).astype(np.uint64)
-            off += 6 * n
-            v = np.frombuffer(raw, np.float32, n, off)
-            off += 4 * n
-            packed = (k[:, 0] << np.uint64(32)) | (k[:, 1] << np.uint64(16)) | k[:, 2]
-            order = np.argsort(packed)
-            keys.append(packed[order])
-            values.append(v[order])
-        size, length = struct.unpack_from("<II", raw, off)
-        off += 8
-        bt = np.frombuffer(raw, np.uint8, length, off).copy()
-        off += length
+            k, v = r.voxels(n)
+            keys.append(k)
+            values.append(v)
+        size, bt = r.one("<u4"), r.stream()
         if c["timing"]:
             report.append(f"{name}: {ms:.1f} ms, {counts[0]} leaves")
             continue
@@ -313,16 +185,15 @@ def main():
         out[f"{name}_logodds"] = np.concatenate(values)
         out[f"{name}_size"] = np.uint32(size)
         out[f"{name}_bt"] = bt
-        report.append(f"{name}: {len(c['scans'])} scans, {counts[-1]} leaves, {size} nodes, {length} B")
-    assert off == len(raw)
+        report.append(f"{name}: {len(c['scans'])} scans, {counts[-1]} leaves, {size} nodes, {len(bt)} B")
+    r.done()
     out["random_seed"] = np.int32(cases["random"]["seed"])
     out["random_length_stops"] = np.int32(cases["random"]["census"][rc.LENGTH])
-    disp, poses, m = hitfix.scene()
-    out["scene_disp"], out["scene_poses"], out["scene_model"], out["scene_scale"] = disp, poses, hitfix.occ.model_to_array(m), np.int32(4)
+    disp, poses, m = kit.scene("rays")
+    out["scene_disp"], out["scene_poses"], out["scene_model"], out["scene_scale"] = disp, poses, occ.model_to_array(m), np.int32(4)
     disp, poses, m, scale = clamp_planes()
-    out["clamp_disp"], out["clamp_poses"], out["clamp_model"], out["clamp_scale"] = disp, poses, hitfix.occ.model_to_array(m), np.int32(scale)
-    np.savez_compressed(OUT, **out)
-    OUT.with_suffix(".sha256").write_text(hashlib.sha256(OUT.read_bytes()).hexdigest() + "  " + OUT.name + "\n")
+    out["clamp_disp"], out["clamp_poses"], out["clamp_model"], out["clamp_scale"] = disp, poses, occ.model_to_array(m), np.int32(scale)
+    OUT = kit.save(args.out, "rays", out, kit.numpy_npz)
     print(f"{OUT}: {OUT.stat().st_size} bytes\n  " + "\n  ".join(report))
 
 
