@@ -40,7 +40,7 @@ PGO_OBJS := $(CSRC)/sbm_pgo.o $(CSRC)/sbm_pgo_plan.o
 $(PGO_OBJS): $(CSRC)/sbm_pgo.h
 $(PGO_OBJS): HIPFLAGS += -ffp-contract=off
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/sbm_common.h $(CSRC)/sbm_handle.h include/sbm.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/sbm_common.h $(CSRC)/sbm_carve.h $(CSRC)/sbm_handle.h include/sbm.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(LIB): $(OBJS)

@@ -151,6 +151,15 @@ def test_host_strided_and_async(bm):
         check(kp, cn, i, ref.select(m, 65535), i)
 
 
+def test_host_form_output_of_a_larger_call_is_not_read(bm):
+    """Large, small, large on one handle: the points and the count are placed anew in an output buffer that only grows."""
+    m = np.random.default_rng(37).integers(0, 65536, (47, 61)).astype(np.uint16)
+    for mf in (501, 1, 3, 17, 501):
+        got = bm.gftt_select_host(m, 65535, max_features=mf, quality_level=0.01, min_distance=1.0)
+        want = ref.select(m, 65535, mf, 0.01, 1.0)
+        assert 0 < len(want) <= mf and np.array_equal(got, want), mf
+
+
 def test_detect_then_keypoints3d(bm, pkg, oracle, golden):
     import torch
 

@@ -81,6 +81,23 @@ def test_every_fixture_stream_loaded(pkg, bm, torch_cuda, tmp_path, name):
         omap.close()
 
 
+def test_staging_of_a_larger_load_and_fetch_is_not_read(pkg, bm, torch_cuda):
+    """Large, small, large through one handle: the leaf words and prefix of a load, and the keys and values of a fetch, are
+    placed anew in staging that only grows."""
+    by_size = sorted(LOADABLE, key=lambda n: len(FX[f"{n}_leaf_key"]))
+    small, large = by_size[0], by_size[-1]
+    assert len(FX[f"{small}_leaf_key"]) < len(FX[f"{large}_leaf_key"])
+    omap = pkg.OccupancyMap(bm, CAPACITY)
+    try:
+        for name in (large, small, large):
+            data, rp = STREAMS[name]
+            omap.load_binary(data, gpu_params(pkg, rp))
+            same(omap.fetch_logodds(), recorded_voxels(name), name)
+            assert omap.overflow() == 0
+    finally:
+        omap.close()
+
+
 def query_scans(tree):
     n = QUERY[f"{tree}_npoints"]
     ends = np.cumsum(n)

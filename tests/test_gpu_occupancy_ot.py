@@ -337,6 +337,23 @@ def test_device_parse_where_the_tile_sums_take_a_run_per_thread(pkg, bm, torch_c
         omap.close()
 
 
+@pytest.mark.parametrize("on", [True, False], ids=["host_parse", "device_parse"])
+def test_staging_of_a_larger_load_is_not_read(pkg, bm, torch_cuda, on):
+    """Large, small, large through one handle: the arrays of a load are placed anew in staging that only grows."""
+    large = edge_voxels(257)
+    streams = [large, dict(list(large.items())[:1]), dict(list(large.items())[:17]), large]
+    omap = pkg.OccupancyMap(bm, CAPACITY)
+    try:
+        for voxels in streams:
+            with host_parse(on):
+                omap.load_ot(oc.of_records(oc.of_voxels(voxels)))
+            keys = sorted(voxels)
+            same(omap.fetch_logodds(), (np.array(keys, np.uint64), [voxels[x] for x in keys]), len(voxels))
+            assert omap.overflow() == 0
+    finally:
+        omap.close()
+
+
 # ---- 6. refusals ------------------------------------------------------------------------------------------------------------------
 def test_refusals_leave_the_map_untouched_on_both_parse_paths(pkg, bm, torch_cuda, tmp_path):
     good = bytes(FX["scene_ot_0"])

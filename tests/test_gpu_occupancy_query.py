@@ -222,6 +222,26 @@ def test_ten_thousand_queries_leave_the_map_as_it_was(pkg, bm, tree):
         omap.close()
 
 
+def test_host_staging_of_a_larger_query_is_not_read(pkg, bm):
+    """Large, small, large through one handle: the host forms place points, states and values (directions, origins, statuses
+    and ends) anew in staging that only grows, at counts whose arrays end off the staging's alignment."""
+    omap, thres = build(pkg, bm, "scene")
+    try:
+        rays, status, end = FX["scene_view_rays"], FX["scene_view_status"], FX["scene_view_end"]
+        pts, state, value = FX["scene_search_points"], FX["scene_search_state"], FX["scene_search_value"]
+        q = pkg.occ_query_params(6.0, thres, True)
+        for n in (257, 1, 17, 257):
+            o, d = np.ascontiguousarray(rays[:n, :3]), np.ascontiguousarray(rays[:n, 3:])
+            same_rays(omap.cast_rays(o, d, q), status[:n], end[:n], ("host", n))
+            if len({tuple(r) for r in o.view(np.uint32).tolist()}) == 1:
+                same_rays(omap.cast_rays(o[0], d, q), status[:n], end[:n], ("host, one origin", n))
+            st, v = omap.search(np.ascontiguousarray(pts[:n]), thres)
+            assert np.array_equal(st, state[:n]), n
+            assert np.array_equal(np.asarray(v).view(np.uint32), value[:n].view(np.uint32)), n
+    finally:
+        omap.close()
+
+
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
 def test_wavefront_and_workgroup_edges(pkg, bm, torch_cuda, n):
     torch = torch_cuda

@@ -312,6 +312,18 @@ def test_host_form(bm, golden, pattern, reading):
     assert d0.shape == (0, 32) and k0.shape == (0, 2)
 
 
+def test_host_form_staging_of_a_larger_call_is_not_read(bm, pattern):
+    """Large, small, large on one handle: points in, points out, descriptors and counts are placed anew in staging that only
+    grows, at odd capacities."""
+    rng = np.random.default_rng(29)
+    img = rng.integers(0, 256, (80, 96), dtype=np.uint8)
+    kp = np.stack([rng.uniform(15, 81, 257), rng.uniform(15, 65, 257)], 1).astype(np.float32)
+    for n in (257, 1, 3, 17, 257):
+        d, k = bm.orb_describe_host(img, kp[:n], pattern)
+        want_k, want_d, _ = ref.describe(img, kp[:n], pattern)
+        assert len(want_k) > 0 and np.array_equal(k, want_k) and np.array_equal(d, want_d), n
+
+
 def test_async_features(bm, oracle, golden, pattern):
     imgs = np.stack([golden["rect_r"], golden["rect_l"]])
     d, kk, cc = bm.orb_features(dev(imgs), pattern, sync=False)

@@ -208,6 +208,24 @@ def test_three_calls_and_a_repeated_frame(pkg, bm, metric):
 
 
 @METRICS
+def test_scratch_and_staging_of_a_larger_call_are_not_read(pkg, bm, metric):
+    """Large, small, large through the host form on one handle: partial records, merged records and flags are placed anew in
+    scratch that only grows, the rows in staging that only grows."""
+    def frames(rng):
+        a = rng.integers(0, 256, (130, 32), dtype=np.uint8)
+        b = rng.integers(0, 256, (130, 32), dtype=np.uint8)
+        return [(a, 2), (b[:1], 3), (b[1:18], 4), (np.concatenate([b[18:], a[:40]]), 5)]
+
+    p = fresh(pkg, bm, metric)
+    try:
+        for rows, node in tie_free_frames(metric, 61, frames):
+            p.add(rows, node, device=False)
+        p.check_refs()
+    finally:
+        p.close()
+
+
+@METRICS
 def test_overflow_adds_nothing(pkg, bm, metric):
     _, rows = vc.make_case(41, 130, 0, metric)
     p = Pair(pkg, bm, metric, capacity=100)

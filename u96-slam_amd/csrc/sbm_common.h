@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/sbm.h"
+#include "sbm_carve.h"
 
 #include <stdlib.h>
 
@@ -17,9 +18,6 @@ inline int env_switch(const char* name, int dflt) {
   const char* e = getenv(name);
   return e ? atoi(e) : dflt;
 }
-
-// Bytes up to the next 16-byte boundary: where pieces that share a buffer begin (the occupancy family's begin at 256: occ_pad).
-__host__ __device__ inline size_t pad16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
 // Geometry of one launch, derived on the host from sbm_params and the image size. Naming follows
 // cv::StereoBM (calib3d stereobm.cpp): lofs/rofs/width1, buffer index d <-> true disparity nd-1-d+mindisp.

@@ -331,10 +331,10 @@ int sbm_gftt_cv_detect(sbm_handle* h, const uint8_t* img, size_t img_stride, int
   HIPCHK(h, dscope.enter());
   st = ensure_staging(h, 1, width, height);
   if (st != SBM_OK) return st;
-  HIPCHK(h, h->gc.out.grow(cap * 2 * sizeof(float) + 16, h->stream));   // points, then the count
+  float* d_k;
+  int* d_n;   // points on 8-byte boundaries, then the count
+  HIPCHK(h, carve(h->gc.out, h->stream, [&](Carve& c) { d_k = c.take<float>(cap * 2); d_n = c.take<int>(4); }, 8));
   HIPCHK(h, hipMemcpy2DAsync(h->st.l.p, width, img, img_stride, width, height, hipMemcpyHostToDevice, h->stream));
-  float* d_k = h->gc.out.as<float>();
-  int* d_n = (int*)(d_k + cap * 2);
   st = gftt_cv_run(h, 1, h->st.l.p, width, height, p, nullptr, nullptr, d_k, d_n, 0);
   if (st != SBM_OK) return st;
   int k = 0;
@@ -374,13 +374,13 @@ int sbm::gftt_cv_run(sbm_handle* h, int n, const void* d_img, int width, int hei
   if (!d_eig) chunk = std::min(chunk, std::max<size_t>(1, kGcChunkBytes / (plane * 4)));
   if (select && pl.global_table) chunk = std::min(chunk, std::max<size_t>(1, ((size_t)2 << 30) / pl.table_bytes_per_image));
   const int C = (int)chunk;
-  HIPCHK(h, h->gc.small.grow((size_t)n * 8, h->stream));   // n keys of the maxima, then n candidate counts
+  unsigned* keymax;
+  int* ncand;   // n keys of the maxima, then n candidate counts, on 4-byte boundaries
+  HIPCHK(h, carve(h->gc.small, h->stream, [&](Carve& c) { keymax = c.take<unsigned>(n); ncand = c.take<int>(n); }, 4));
   if (select) HIPCHK(h, h->gc.keys.grow(kstride * 8 * C, h->stream));
   if (!d_eig) HIPCHK(h, h->gc.eig.grow(plane * 4 * C + 16, h->stream));
   if (select && pl.global_table) HIPCHK(h, h->gc.tab.grow(pl.table_bytes_per_image * C, h->stream));
-  unsigned* keymax = h->gc.small.as<unsigned>();
-  int* ncand = (int*)(keymax + n);
-  HIPCHK(h, hipMemsetAsync(keymax, 0, (size_t)n * 8, h->stream));
+  HIPCHK(h, hipMemsetAsync(keymax, 0, (char*)(ncand + n) - (char*)keymax, h->stream));   // both pieces
   if (!d_img) {   // the caller's maps and maxima
     hipLaunchKernelGGL(gftt_cv_key_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, (const float*)d_max, keymax, n);
     HIPCHK(h, hipGetLastError());

@@ -284,13 +284,13 @@ int sbm_gftt_select(sbm_handle* h, const uint16_t* eig, size_t eig_stride, int w
   HIPCHK(h, dscope.enter());
   st = ensure_staging(h, 1, width, height);
   if (st != SBM_OK) return st;
-  HIPCHK(h, h->gs.out.grow(cap * 2 * sizeof(float) + 16, h->stream));   // points, then the count
+  float* d_k;
+  int* d_n;   // points on 8-byte boundaries, then the count
+  HIPCHK(h, carve(h->gs.out, h->stream, [&](Carve& c) { d_k = c.take<float>(cap * 2); d_n = c.take<int>(4); }, 8));
   // st.d: the map, st.r: the Max word
   const uint32_t mx = max_eig;
   HIPCHK(h, hipMemcpy2DAsync(h->st.d.p, (size_t)width * 2, eig, eig_stride, (size_t)width * 2, height, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->st.r.p, &mx, sizeof(mx), hipMemcpyHostToDevice, h->stream));
-  float* d_k = h->gs.out.as<float>();
-  int* d_n = (int*)(d_k + cap * 2);
   st = gftt_select_run(h, 1, nullptr, h->st.d.p, h->st.r.p, width, height, p, d_k, d_n, 0);
   if (st != SBM_OK) {
     hipStreamSynchronize(h->stream);   // `mx` is read by an enqueued copy

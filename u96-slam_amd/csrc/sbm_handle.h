@@ -48,22 +48,10 @@ struct DevBuf {
   void release() { hipFree(p); p = nullptr; bytes = 0; }
 };
 
-// Consecutive pieces of one buffer, each beginning on a 16-byte boundary (pad16). Over a null base it only counts. A layout is
-// one function of a Carve, run twice by carve(): the statements that place the pieces are the ones that size the buffer.
-struct Carve {
-  char* base;
-  size_t off = 0;
-  template <class T> T* take(size_t n) {
-    T* piece = base ? (T*)(base + off) : nullptr;
-    off += pad16(n * sizeof(T));
-    return piece;
-  }
-};
-template <class Layout> hipError_t carve(DevBuf& b, hipStream_t s, Layout layout) {
-  Carve count{nullptr};
-  layout(count);
-  const hipError_t e = b.grow(count.off, s);
-  Carve place{b.as<char>()};
+// A buffer grown to a layout (sbm_carve.h) and the layout placed in it: the counting pass sizes it, the second pass places.
+template <class Layout> hipError_t carve(DevBuf& b, hipStream_t s, Layout layout, size_t align = 16) {
+  const hipError_t e = b.grow(carve_bytes(layout, align), s);
+  Carve place{b.as<char>(), 0, align};
   if (e == hipSuccess) layout(place);
   return e;
 }

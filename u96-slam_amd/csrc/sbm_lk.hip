@@ -277,8 +277,18 @@ static int lk_run(sbm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_
   // a chunk also has to fit one launch: pyrDown takes BOTH images of every pair of the chunk in gridDim.z (2 C frames <= 65 535)
   const size_t fit = std::min<size_t>(std::max<size_t>(1, kLkChunkBytes / per_pair), L > 0 ? kLkMaxGridZ / 2 : kLkMaxGridZ);
   const int C = (int)std::min<size_t>(n, fit);
-  HIPCHK(h, h->lk.pyr.grow((size_t)C * 2 * upper + 256, h->stream));
-  HIPCHK(h, h->lk.deriv.grow((size_t)C * 4 * all, h->stream));
+  // pyr: level l >= 1 of m pairs is 2 m frames (left, then right), the levels packed to the byte, and 256 bytes behind the last;
+  // deriv: level l of the m left frames, a pair of shorts per pixel. Sized for a whole chunk, placed for each chunk's pairs.
+  uint8_t* lev[kLkMaxLevels];
+  short* der[kLkMaxLevels];
+  int m = C;
+  const auto pyr_layout = [&](Carve& c) {
+    for (int l = 1; l <= L; l++) lev[l] = c.take<uint8_t>((size_t)lw[l] * lh[l] * 2 * m);
+    c.take<uint8_t>(256);
+  };
+  const auto deriv_layout = [&](Carve& c) { for (int l = 0; l <= L; l++) der[l] = c.take<short>((size_t)lw[l] * lh[l] * 2 * m); };
+  HIPCHK(h, carve(h->lk.pyr, h->stream, pyr_layout, 1));
+  HIPCHK(h, carve(h->lk.deriv, h->stream, deriv_layout, 4));
   LkGeom g;
   memset(&g, 0, sizeof(g));
   g.L = L;
@@ -292,12 +302,9 @@ static int lk_run(sbm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_
   g.max_disp = p->max_disparity;
   const size_t plane0 = (size_t)W * H;
   for (int c0 = 0; c0 < n; c0 += C) {
-    const int m = std::min(C, n - c0);
-    // level l >= 1 of the chunk: 2 m frames (left, then right) from pyr + 2 m * (pixels of levels 1..l-1); derivatives of level l:
-    // m frames from deriv + m * (pixels of levels 0..l-1) pairs
-    uint8_t* pyr = h->lk.pyr.as<uint8_t>();
-    short* der = h->lk.deriv.as<short>();
-    size_t poff = 0, doff = 0;
+    m = std::min(C, n - c0);
+    Carve pc{h->lk.pyr.as<char>(), 0, 1}, dc{h->lk.deriv.as<char>(), 0, 4};
+    pyr_layout(pc), deriv_layout(dc);
     HIPCHK(h, clk.mark(kLkPyramid, h->stream));
     for (int l = 0; l <= L; l++) {
       const size_t plane = (size_t)lw[l] * lh[l];
@@ -308,19 +315,17 @@ static int lk_run(sbm_handle* h, int n, const uint8_t* d_left, const uint8_t* d_
         v.I = d_left + plane0 * c0;
         v.J = d_right + plane0 * c0;
       } else {
-        uint8_t* dst = pyr + poff;
+        uint8_t* dst = lev[l];
         hipLaunchKernelGGL(lk_pyrdown_kernel, lk_grid(lw[l], lh[l], 2 * m), dim3(256), 0, h->stream, g.lv[l - 1].I, g.lv[l - 1].J, m, dst,
                            lw[l - 1], lh[l - 1], lw[l], lh[l]);
         HIPCHK(h, hipGetLastError());
         v.I = dst;
         v.J = dst + plane * m;
-        poff += plane * 2 * m;
       }
-      short* dd = der + 2 * doff;
+      short* dd = der[l];
       hipLaunchKernelGGL(lk_scharr_kernel, lk_grid(lw[l], lh[l], m), dim3(256), 0, h->stream, v.I, dd, lw[l], lh[l]);
       HIPCHK(h, hipGetLastError());
       v.d = dd;
-      doff += plane * m;
     }
     HIPCHK(h, clk.mark(kLkTrack, h->stream));
     hipLaunchKernelGGL(lk_track_kernel, dim3((cap + kLkWaves - 1) / kLkWaves, m), dim3(64 * kLkWaves), 0, h->stream, g, d_kpts, d_count,

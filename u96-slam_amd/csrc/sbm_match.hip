@@ -230,6 +230,10 @@ static int match_limits(int m, int cap) {
 //   scratch  per job: nslice partial records (16 bytes) + owner + accepted (4 bytes each) per slot. For every legal (cap, m)
 //            jobs_per_launch == min(m, kArgJobs) and scratch_bytes <= 96 MiB, well within the 256 MiB the header promises
 //            (tests/test_match_plan.py enumerates every cap through the export), so no budget clamp cuts the jobs per launch.
+// One launch's scratch. Whole words on 4-byte boundaries: nothing is padded, which keeps the published scratch_bytes exact.
+struct MatchScratch { int4* part; int *owner, *acc; };
+constexpr size_t kMatchAlign = 4;
+static MatchScratch match_scratch(Carve& c, size_t slots, int nslice) { return {c.take<int4>(slots * nslice), c.take<int>(slots), c.take<int>(slots)}; }
 static int match_plan(int cap, int m, sbm_match_plan_info* pl) {
   memset(pl, 0, sizeof(*pl));
   const int st = match_limits(m, cap);
@@ -247,7 +251,7 @@ static int match_plan(int cap, int m, sbm_match_plan_info* pl) {
   pl->launches = (m + mj - 1) / mj;
   pl->proj_jobs_per_launch = std::min(m, kProjJobs);
   pl->proj_launches = (m + kProjJobs - 1) / kProjJobs;
-  pl->scratch_bytes = (int64_t)mj * cap * (16 * (int64_t)nslice + 8);
+  pl->scratch_bytes = (int64_t)carve_bytes([&](Carve& c) { match_scratch(c, (size_t)mj * cap, nslice); }, kMatchAlign);
   return SBM_OK;
 }
 
@@ -282,10 +286,9 @@ static int match_run(sbm_handle* h, int m, const int* jobs, const void* d_desc, 
   const int pst = match_plan(cap, m, &pl);
   if (pst != SBM_OK) return pst;
   const int qtiles = pl.qtiles, nslice = pl.nslice, slice_rows = pl.slice_rows, mj = pl.jobs_per_launch;
-  HIPCHK(h, h->mt.scratch.grow((size_t)pl.scratch_bytes, h->stream));
-  int4* part = h->mt.scratch.as<int4>();
-  int* owner = (int*)(part + (size_t)mj * nslice * cap);
-  int* acc = owner + (size_t)mj * cap;
+  MatchScratch sc;
+  HIPCHK(h, carve(h->mt.scratch, h->stream, [&](Carve& c) { sc = match_scratch(c, (size_t)mj * cap, nslice); }, kMatchAlign));
+  const auto [part, owner, acc] = sc;
   for (int j0 = 0; j0 < m; j0 += mj) {
     const int k = std::min(mj, m - j0);
     MatchJobs a;

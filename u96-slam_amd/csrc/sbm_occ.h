@@ -195,7 +195,7 @@ __device__ __forceinline__ unsigned occ_wave_append(bool take, unsigned* counter
   return base + __popcll(taking & ((1ull << lane) - 1));
 }
 
-inline size_t occ_pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }   // arrays that share a buffer begin 256-aligned
+constexpr size_t occ_pad = 256;   // the family's alignment: arrays that share a buffer begin on it (Carve, sbm_carve.h)
 #pragma GCC visibility push(hidden)   // host functions that cross files (these: sbm_occupancy.hip). Hidden, as the two above and
 // unlike the rest of the project's, so that the family's internal names stay out of what the library exports
 int occ_read_counters(sbm_occ_map* map, OccCounters* c);
@@ -215,6 +215,13 @@ int occ_ray_params_check(const sbm_occ_ray_params* p);
 int occ_logodds_alloc(sbm_occ_map* map);   // what the log-odds mode keeps beside the table
 OccLevel occ_tree_level(const sbm_occ_tree* t, int d);   // these two are in sbm_occ_tree.hip: depth d of a built tree (empty levels for
 int occ_tree_stats(sbm_occ_tree* t);                     // one that is not), and the counts of the last build into t->host, read once
+// The radix sort's second key / payload arrays for n pairs in the handle's sort buffer and, where asked, a first payload array
+inline hipError_t occ_sort_carve(sbm_handle* h, size_t n, unsigned long long** keys, unsigned** vals, unsigned** first_vals = nullptr) {
+  return carve(h->occ.sort, h->stream, [&](Carve& c) {
+    *keys = c.take<unsigned long long>(n), *vals = c.take<unsigned>(n);
+    if (first_vals) *first_vals = c.take<unsigned>(n);
+  }, occ_pad);
+}
 #pragma GCC visibility pop
 
 // Times `stage` of a query around `launch` (-> status; the error of its last launch is looked at here). A query changes nothing
@@ -231,6 +238,43 @@ template <class Launch> int occ_timed_run(sbm_handle* h, int stage, bool any, in
     HIPCHK(h, clk.add(stage, kOccBegin, kOccEnd));
   }
   if (sync) HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+// The host form of a point search through the handle's staging: n triples in; n states, n values and (depths: a tree's) n found
+// depths out, each copied where the caller wants it. search(d_xyz, d_state, d_value, d_found) enqueues the query (-> status).
+template <class Search> int occ_search_host(sbm_handle* h, size_t n, const float* xyz, bool depths, int32_t* state, void* value,
+                                            int32_t* found_depth, Search search) {
+  struct { float* xyz; int* state; unsigned* value; int* found; } io = {};
+  if (n) {
+    HIPCHK(h, carve(h->occ.io, h->stream, [&](Carve& c) {
+      io = {c.take<float>(n * 3), c.take<int>(n), c.take<unsigned>(n), c.take<int>(depths ? n : 0)};
+    }, occ_pad));
+    HIPCHK(h, hipMemcpyAsync(io.xyz, xyz, n * 12, hipMemcpyHostToDevice, h->stream));
+  }
+  const int st = search(io.xyz, io.state, io.value, io.found);
+  if (st != SBM_OK) return st;
+  if (n) {
+    HIPCHK(h, hipMemcpyAsync(state, io.state, n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (value) HIPCHK(h, hipMemcpyAsync(value, io.value, n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (found_depth) HIPCHK(h, hipMemcpyAsync(found_depth, io.found, n * 4, hipMemcpyDeviceToHost, h->stream));
+  }
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+// The body of a written tree through the handle's staging: `bytes` of it from run(d_bytes, &got) (-> status) into *body.
+template <class Run> int occ_body_host(sbm_handle* h, size_t bytes, std::vector<uint8_t>* body, Run run) {
+  try {
+    body->resize(bytes);
+  } catch (const std::bad_alloc&) {
+    return SBM_ERR_NOMEM;
+  }
+  if (!bytes) return SBM_OK;
+  size_t got = 0;
+  HIPCHK(h, h->occ.io.grow(bytes, h->stream));
+  const int st = run(h->occ.io.as<uint8_t>(), &got);
+  if (st != SBM_OK) return st;
+  HIPCHK(h, hipMemcpyAsync(body->data(), h->occ.io.p, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
   return SBM_OK;
 }
 #endif  // __HIP__

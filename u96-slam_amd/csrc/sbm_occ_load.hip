@@ -92,10 +92,9 @@ static int occ_load_run(sbm_occ_map* map, const uint8_t* bytes, size_t n, const 
   }
   st = occ_logodds_alloc(map);
   if (st != SBM_OK) return st;
-  const size_t wb = occ_pad(count * 8);
-  HIPCHK(h, h->occ.io.grow(wb + count * 4, h->stream));
-  unsigned long long* d_word = h->occ.io.as<unsigned long long>();
-  unsigned* d_first = (unsigned*)(h->occ.io.as<char>() + wb);
+  unsigned long long* d_word;
+  unsigned* d_first;
+  HIPCHK(h, carve(h->occ.io, h->stream, [&](Carve& c) { d_word = c.take<unsigned long long>(count); d_first = c.take<unsigned>(count); }, occ_pad));
   HIPCHK(h, hipMemcpyAsync(d_word, leaves.data(), count * 8, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_first, first.data(), count * 4, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));   // the host arrays end with this call

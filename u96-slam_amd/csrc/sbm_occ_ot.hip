@@ -105,15 +105,6 @@ __global__ void __launch_bounds__(256) occ_ot_body_kernel(const unsigned* __rest
 struct OccOtRanks {   // the pieces of sbm_occ_tree::ot
   unsigned *cnt, *rank, *order;
 };
-static OccOtRanks occ_ot_ranks(const sbm_occ_tree* t) {
-  OccOtRanks r;
-  char* b = t->ot.as<char>();
-  const size_t w = occ_pad(4 * t->inner_total);
-  r.cnt = (unsigned*)b;
-  r.rank = (unsigned*)(b + w);
-  r.order = (unsigned*)(b + 2 * w);
-  return r;
-}
 
 static int occ_ot_body_run(sbm_occ_tree* t, uint8_t* d_bytes, size_t cap, size_t* nbytes) {
   sbm_handle* h = t->h;
@@ -125,9 +116,11 @@ static int occ_ot_body_run(sbm_occ_tree* t, uint8_t* d_bytes, size_t cap, size_t
   if (*nbytes > cap) return SBM_ERR_SIZE;
   return occ_timed_run(h, kOccTreeQuery, nodes > 0, 1, [&]() -> int {
     const uint32_t n = (uint32_t)nodes;   // below 2^31 + 2^30: a build refuses 2^31 nodes above the voxels
+    OccOtRanks r;   // grown by the first call after a build, placed alike by the later ones
+    HIPCHK(h, carve(t->ot, h->stream, [&](Carve& c) {
+      r = {c.take<unsigned>(t->inner_total), c.take<unsigned>(t->inner_total), c.take<unsigned>(n)};
+    }, occ_pad));
     if (!t->ot_ranked) {
-      HIPCHK(h, t->ot.grow(2 * occ_pad(4 * t->inner_total) + occ_pad(4 * (size_t)n), h->stream));
-      const OccOtRanks r = occ_ot_ranks(t);
       for (int d = kOccDepth - 1; d >= 0; d--) {   // bottom-up
         const OccLevel l = occ_tree_level(t, d);
         hipLaunchKernelGGL(occ_ot_count_kernel, dim3((l.n + 255) / 256), dim3(256), 0, h->stream, l,
@@ -150,7 +143,7 @@ static int occ_ot_body_run(sbm_occ_tree* t, uint8_t* d_bytes, size_t cap, size_t
     ref.leaf_val = occ_tree_level(t, kOccDepth).val;
     ref.node_val = occ_tree_level(t, 0).val;
     ref.node_info = occ_tree_level(t, 0).info;
-    hipLaunchKernelGGL(occ_ot_body_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, occ_ot_ranks(t).order, n, ref, d_bytes);
+    hipLaunchKernelGGL(occ_ot_body_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, r.order, n, ref, d_bytes);
     return SBM_OK;
   });
 }
@@ -441,41 +434,33 @@ struct OccOtArrays {   // of one load in the handle's io buffer: leaf words, pre
   unsigned *leaf_at, *link;
   OtPair* tile;
   OccOtResult* res;
-  size_t bytes;
 };
-static OccOtArrays occ_ot_arrays(char* base, size_t n, bool parse) {
-  OccOtArrays a;
-  memset(&a, 0, sizeof(a));
-  size_t off = 0;
-  const auto take = [&](size_t bytes) {   // over a null base it only counts
-    char* p = base ? base + off : nullptr;
-    off += occ_pad(bytes);
-    return (void*)p;
-  };
-  a.word = (unsigned long long*)take(8 * n);
-  a.first = (unsigned*)take(4 * n);
-  a.val = (unsigned*)take(4 * n);
-  if (parse) {
+// The handle's io buffer grown to the arrays of n leaves or, with parse, n records
+static hipError_t occ_ot_arrays(sbm_handle* h, size_t n, bool parse, OccOtArrays* a) {
+  memset(a, 0, sizeof(*a));
+  return carve(h->occ.io, h->stream, [&](Carve& c) {
+    a->word = c.take<unsigned long long>(n);
+    a->first = c.take<unsigned>(n);
+    a->val = c.take<unsigned>(n);
+    if (!parse) return;
     const size_t tiles = (n + kOtTile - 1) / kOtTile;
-    a.vol = (unsigned long long*)take(8 * n);
-    a.vol_tile = (unsigned long long*)take(8 * tiles);
-    a.rec = (uint8_t*)take(5 * n);
-    a.D = (int*)take(4 * (n + 1));
-    a.minima = (int*)take(4 * (n / (kOtFan - 1) + kOtMaxLevels));   // n/16 + n/256 + ... and one entry of rounding per level
-    a.leaf_at = (unsigned*)take(4 * n);
-    a.link = (unsigned*)take(4 * n);
-    a.tile = (OtPair*)take(sizeof(OtPair) * tiles);
-    a.res = (OccOtResult*)take(sizeof(OccOtResult));
-  }
-  a.bytes = off;
-  return a;
+    a->vol = c.take<unsigned long long>(n);
+    a->vol_tile = c.take<unsigned long long>(tiles);
+    a->rec = c.take<uint8_t>(5 * n);
+    a->D = c.take<int>(n + 1);
+    a->minima = c.take<int>(n / (kOtFan - 1) + kOtMaxLevels);   // n/16 + n/256 + ... and one entry of rounding per level
+    a->leaf_at = c.take<unsigned>(n);
+    a->link = c.take<unsigned>(n);
+    a->tile = c.take<OtPair>(tiles);
+    a->res = c.take<OccOtResult>(1);
+  }, occ_pad);
 }
 
 // The first n records (n >= 1) -> the leaves in the io buffer in record order, their prefix array, and what the host checks: the
 // flags, the leaf count and the voxel total. One wait, at the end.
 static int occ_ot_device_parse(sbm_handle* h, const uint8_t* records, uint32_t n, OccOtArrays* out, OccOtResult* result) {
-  HIPCHK(h, h->occ.io.grow(occ_ot_arrays(nullptr, n, true).bytes, h->stream));
-  const OccOtArrays a = occ_ot_arrays(h->occ.io.as<char>(), n, true);
+  OccOtArrays& a = *out;
+  HIPCHK(h, occ_ot_arrays(h, n, true, out));
   const uint32_t tiles = (n + kOtTile - 1) / kOtTile, blocks = (n + 255) / 256;
   HIPCHK(h, hipMemcpyAsync(a.rec, records, 5 * (size_t)n, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemsetAsync(a.res, 0, sizeof(OccOtResult), h->stream));
@@ -516,7 +501,6 @@ static int occ_ot_device_parse(sbm_handle* h, const uint8_t* records, uint32_t n
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, hipMemcpyAsync(result, a.res, sizeof(OccOtResult), hipMemcpyDeviceToHost, h->stream));   // nothing between this copy
   HIPCHK(h, hipStreamSynchronize(h->stream));                                                        // and its wait can return
-  *out = a;
   return SBM_OK;
 }
 
@@ -557,8 +541,7 @@ static int occ_ot_load_body(sbm_occ_map* map, const uint8_t* bytes, size_t n, in
       first[i] = (unsigned)run;               // below the capacity, which is at most 2^30
       run += (uint64_t)1 << (3 * (16 - occ_bt_depth(words[i])));
     }
-    HIPCHK(h, h->occ.io.grow(occ_ot_arrays(nullptr, words.size(), false).bytes, h->stream));
-    a = occ_ot_arrays(h->occ.io.as<char>(), words.size(), false);
+    HIPCHK(h, occ_ot_arrays(h, words.size(), false, &a));
     HIPCHK(h, hipMemcpyAsync(a.word, words.data(), words.size() * 8, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(a.first, first.data(), first.size() * 4, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(a.val, values.data(), values.size() * 4, hipMemcpyHostToDevice, h->stream));
@@ -634,20 +617,8 @@ int sbm_occ_ot_write(sbm_occ_tree* tree, const char* path) {
   for (int d = 0; d <= kOccDepth; d++) nodes += tree->host.nodes_at[d];
   const size_t bytes = (size_t)(5 * nodes);
   std::vector<uint8_t> body;
-  try {
-    body.resize(bytes);
-  } catch (const std::bad_alloc&) {
-    return SBM_ERR_NOMEM;
-  }
-  if (bytes) {
-    size_t got = 0;
-    HIPCHK(h, h->occ.io.grow(bytes, h->stream));
-    st = occ_ot_body_run(tree, h->occ.io.as<uint8_t>(), bytes, &got);
-    if (st != SBM_OK) return st;
-    HIPCHK(h, hipMemcpyAsync(body.data(), h->occ.io.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return occ_ot_write_file(body, (size_t)nodes, tree->resolution, path);
+  st = occ_body_host(h, bytes, &body, [&](uint8_t* d_bytes, size_t* got) { return occ_ot_body_run(tree, d_bytes, bytes, got); });
+  return st != SBM_OK ? st : occ_ot_write_file(body, (size_t)nodes, tree->resolution, path);
 }
 
 int sbm_occ_ot_load(sbm_occ_map* map, const void* bytes, size_t n, int sync) {

@@ -249,22 +249,11 @@ int sbm_occ_search(sbm_occ_map* map, size_t n, const float* xyz, float occupancy
   if (!map || (n > 0 && (!xyz || !state))) return SBM_ERR_NULL;
   if (std::isnan(occupancy_thres_log)) return SBM_ERR_SIZE;
   if (n > ((size_t)1 << 30)) return SBM_ERR_UNSUPPORTED;
-  sbm_handle* h = map->h;
-  DeviceScope dscope(h->device);
-  HIPCHK(h, dscope.enter());
-  if (n) {   // io: n triples, n states, n values
-    HIPCHK(h, h->occ.io.grow(n * 20, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->occ.io.p, xyz, n * 12, hipMemcpyHostToDevice, h->stream));
-  }
-  char* io = h->occ.io.as<char>();
-  const int st = occ_search_run(map, n, (const float*)io, occupancy_thres_log, (int*)(io + n * 12), (unsigned*)(io + n * 16), 0);
-  if (st != SBM_OK) return st;
-  if (n) {
-    HIPCHK(h, hipMemcpyAsync(state, io + n * 12, n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (value) HIPCHK(h, hipMemcpyAsync(value, io + n * 16, n * 4, hipMemcpyDeviceToHost, h->stream));
-  }
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return SBM_OK;
+  DeviceScope dscope(map->h->device);
+  HIPCHK(map->h, dscope.enter());
+  return occ_search_host(map->h, n, xyz, false, state, value, nullptr, [&](const float* d_xyz, int* d_state, unsigned* d_value, int*) {
+    return occ_search_run(map, n, d_xyz, occupancy_thres_log, d_state, d_value, 0);
+  });
 }
 
 int sbm_occ_cast_rays_device(sbm_occ_map* map, size_t n, const void* origins, int shared_origin, const void* d_dirs,
@@ -286,19 +275,19 @@ int sbm_occ_cast_rays(sbm_occ_map* map, size_t n, const float* origins, int shar
   sbm_handle* h = map->h;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
-  char* io = nullptr;
-  if (n) {   // io: n directions, n origins, n statuses, n ends
-    HIPCHK(h, h->occ.io.grow(n * 40, h->stream));
-    io = h->occ.io.as<char>();
-    HIPCHK(h, hipMemcpyAsync(io, dirs, n * 12, hipMemcpyHostToDevice, h->stream));
-    if (!shared_origin) HIPCHK(h, hipMemcpyAsync(io + n * 12, origins, n * 12, hipMemcpyHostToDevice, h->stream));
+  struct { float *dirs, *origins; int* status; float* end; } io = {};
+  if (n) {
+    HIPCHK(h, carve(h->occ.io, h->stream, [&](Carve& c) {
+      io = {c.take<float>(n * 3), c.take<float>(n * 3), c.take<int>(n), c.take<float>(n * 3)};
+    }, occ_pad));
+    HIPCHK(h, hipMemcpyAsync(io.dirs, dirs, n * 12, hipMemcpyHostToDevice, h->stream));
+    if (!shared_origin) HIPCHK(h, hipMemcpyAsync(io.origins, origins, n * 12, hipMemcpyHostToDevice, h->stream));
   }
-  st = occ_cast_run(map, n, shared_origin ? nullptr : (const float*)(io + n * 12), shared_origin ? origins : nullptr, (const float*)io,
-                    params, (int*)(io + n * 24), (float*)(io + n * 28), 0);
+  st = occ_cast_run(map, n, shared_origin ? nullptr : io.origins, shared_origin ? origins : nullptr, io.dirs, params, io.status, io.end, 0);
   if (st != SBM_OK) return st;
   if (n) {
-    HIPCHK(h, hipMemcpyAsync(status, io + n * 24, n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (end) HIPCHK(h, hipMemcpyAsync(end, io + n * 28, n * 12, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(status, io.status, n * 4, hipMemcpyDeviceToHost, h->stream));
+    if (end) HIPCHK(h, hipMemcpyAsync(end, io.end, n * 12, hipMemcpyDeviceToHost, h->stream));
   }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return SBM_OK;

@@ -285,31 +285,30 @@ __global__ void __launch_bounds__(256) occ_tree_binary_kernel(OccLevel l, OccLev
 }
 
 // ---- the tree, host side -------------------------------------------------------------------------------------------------
-// Depth d of a built tree; a tree that was never built, or whose build failed, has empty levels.
+// t->leaf: the voxels' codes, values, parents and info words. t->node (inner): seven arrays over all the depths above 16, depth 0 first.
+static void occ_level_layout(Carve& c, size_t n, bool inner, OccLevel* l) {
+  l->code = c.take<unsigned long long>(n);
+  l->val = c.take<unsigned>(n);
+  l->parent = c.take<unsigned>(n);
+  l->info = c.take<unsigned>(n);
+  if (!inner) return;
+  l->first = c.take<unsigned>(n);
+  l->inner = c.take<unsigned>(n);
+  l->rank = c.take<unsigned>(n);
+}
+
+// Depth d of a built tree, from the two layouts and the build's counts; a tree that was never built, or whose build failed, has
+// empty levels.
 OccLevel occ_tree_level(const sbm_occ_tree* t, int d) {
   OccLevel l;
   memset(&l, 0, sizeof(l));
   if (!t->built) return l;
+  const bool inner = d < kOccDepth;   // the layout of the build, placed again with its counts
+  Carve c{(inner ? t->node : t->leaf).as<char>(), 0, occ_pad};
+  occ_level_layout(c, inner ? t->inner_total : t->count[d], inner, &l);
+  const size_t o = inner ? t->off[d] : 0;   // the leaves' three missing arrays stay null
+  l.code += o, l.val += o, l.parent += o, l.info += o, l.first += o, l.inner += o, l.rank += o;
   l.n = t->count[d];
-  if (d == kOccDepth) {   // leaf: codes, values, parents, info words
-    char* b = t->leaf.as<char>();
-    const size_t n = l.n;
-    l.code = (unsigned long long*)b;
-    l.val = (unsigned*)(b + occ_pad(8 * n));
-    l.parent = (unsigned*)(b + occ_pad(8 * n) + occ_pad(4 * n));
-    l.info = (unsigned*)(b + occ_pad(8 * n) + 2 * occ_pad(4 * n));
-    return l;
-  }
-  char* b = t->node.as<char>();   // node: seven arrays over all the depths above 16, depth 0 first
-  const size_t all = t->inner_total, w = occ_pad(4 * all), o = t->off[d];
-  unsigned* word = (unsigned*)(b + occ_pad(8 * all));
-  l.code = (unsigned long long*)b + o;
-  l.val = word + o;
-  l.parent = (unsigned*)((char*)word + w) + o;
-  l.info = (unsigned*)((char*)word + 2 * w) + o;
-  l.first = (unsigned*)((char*)word + 3 * w) + o;
-  l.inner = (unsigned*)((char*)word + 4 * w) + o;
-  l.rank = (unsigned*)((char*)word + 5 * w) + o;
   return l;
 }
 
@@ -351,12 +350,12 @@ static int occ_tree_build_run(sbm_occ_tree* t, int reading, const sbm_occ_ray_pa
     return SBM_OK;
   }
   const uint32_t tiles = (n + kOccTile - 1) / kOccTile, blocks = (n + 255) / 256;
-  const size_t kb = occ_pad((size_t)n * 8), vb = occ_pad((size_t)n * 4);
-  HIPCHK(h, t->leaf.grow(kb + 3 * vb, h->stream));
-  HIPCHK(h, h->occ.sort.grow(kb + vb, h->stream));
+  OccLevel leaf;
+  HIPCHK(h, carve(t->leaf, h->stream, [&](Carve& c) { occ_level_layout(c, n, false, &leaf); }, occ_pad));
+  unsigned long long* kk[2] = {leaf.code};
+  unsigned* vv[2] = {leaf.val};
+  HIPCHK(h, occ_sort_carve(h, n, &kk[1], &vv[1]));
   HIPCHK(h, h->occ.hist.grow((size_t)256 * tiles * 4, h->stream));
-  unsigned long long* kk[2] = {t->leaf.as<unsigned long long>(), h->occ.sort.as<unsigned long long>()};
-  unsigned* vv[2] = {(unsigned*)(t->leaf.as<char>() + kb), (unsigned*)(h->occ.sort.as<char>() + kb)};
   HIPCHK(h, clk.mark(kOccBegin, h->stream));
   st = occ_compact_run(map, n, kk[0], vv[0]);
   if (st != SBM_OK) return st;
@@ -383,7 +382,8 @@ static int occ_tree_build_run(sbm_occ_tree* t, int reading, const sbm_occ_ray_pa
   if (t->count[kOccDepth] != n) return SBM_ERR_HIP;
   if (inner_total >= ((unsigned long long)1 << 31)) return SBM_ERR_UNSUPPORTED;   // ranks and subtree counts are 32-bit
   t->inner_total = (size_t)inner_total;
-  HIPCHK(h, t->node.grow(occ_pad(8 * t->inner_total) + 6 * occ_pad(4 * t->inner_total), h->stream));
+  const auto node_layout = [&](Carve& c) { OccLevel all; occ_level_layout(c, t->inner_total, true, &all); };   // occ_tree_level places it
+  HIPCHK(h, t->node.grow(carve_bytes(node_layout, occ_pad), h->stream));
   HIPCHK(h, t->tiles.grow((size_t)tiles * 4, h->stream));
   t->built = true;   // occ_tree_level answers from here on; a failure below takes it back
   st = [&]() -> int {
@@ -461,13 +461,12 @@ static int occ_tree_leaves_run(sbm_occ_tree* t, int max_depth, unsigned long lon
   const uint32_t n = (uint32_t)total;
   return occ_timed_run(h, kOccTreeQuery, n > 0, 1, [&]() -> int {
     const uint32_t tiles = (n + kOccTile - 1) / kOccTile;
-    const size_t kb = occ_pad((size_t)n * 8);
-    HIPCHK(h, h->occ.sort.grow(kb + occ_pad((size_t)n * 4), h->stream));
+    unsigned long long* kk[2] = {d_keys};
+    unsigned* vv[2] = {(unsigned*)d_depth};
+    HIPCHK(h, occ_sort_carve(h, n, &kk[1], &vv[1]));
     HIPCHK(h, h->occ.hist.grow((size_t)256 * tiles * 4, h->stream));
     OccTreeStats* stats = t->stats.as<OccTreeStats>();
     HIPCHK(h, hipMemsetAsync(&stats->cursor, 0, sizeof(unsigned), h->stream));
-    unsigned long long* kk[2] = {d_keys, h->occ.sort.as<unsigned long long>()};
-    unsigned* vv[2] = {(unsigned*)d_depth, (unsigned*)(h->occ.sort.as<char>() + kb)};
     OccTreeRef ref;
     memset(&ref, 0, sizeof(ref));
     ref.leaf_val = occ_tree_level(t, kOccDepth).val;
@@ -584,24 +583,11 @@ int sbm_occ_tree_search(sbm_occ_tree* tree, size_t n, const float* xyz, int dept
   if (!tree || (n > 0 && (!xyz || !state))) return SBM_ERR_NULL;
   if (occ_tree_depth_check(depth) != SBM_OK || std::isnan(occupancy_thres_log)) return SBM_ERR_SIZE;
   if (n > ((size_t)1 << 30)) return SBM_ERR_UNSUPPORTED;
-  sbm_handle* h = tree->h;
-  DeviceScope dscope(h->device);
-  HIPCHK(h, dscope.enter());
-  if (n) {   // io: n triples, n states, n values, n depths
-    HIPCHK(h, h->occ.io.grow(n * 24, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->occ.io.p, xyz, n * 12, hipMemcpyHostToDevice, h->stream));
-  }
-  char* io = h->occ.io.as<char>();
-  const int st = occ_tree_search_run(tree, n, (const float*)io, depth ? depth : kOccDepth, occupancy_thres_log, (int*)(io + n * 12),
-                                     (unsigned*)(io + n * 16), (int*)(io + n * 20), 0);
-  if (st != SBM_OK) return st;
-  if (n) {
-    HIPCHK(h, hipMemcpyAsync(state, io + n * 12, n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (value) HIPCHK(h, hipMemcpyAsync(value, io + n * 16, n * 4, hipMemcpyDeviceToHost, h->stream));
-    if (found_depth) HIPCHK(h, hipMemcpyAsync(found_depth, io + n * 20, n * 4, hipMemcpyDeviceToHost, h->stream));
-  }
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return SBM_OK;
+  DeviceScope dscope(tree->h->device);
+  HIPCHK(tree->h, dscope.enter());
+  return occ_search_host(tree->h, n, xyz, true, state, value, found_depth, [&](const float* d_xyz, int* d_state, unsigned* d_value, int* d_found) {
+    return occ_tree_search_run(tree, n, d_xyz, depth ? depth : kOccDepth, occupancy_thres_log, d_state, d_value, d_found, 0);
+  });
 }
 
 int sbm_occ_tree_leaves_device(sbm_occ_tree* tree, int max_depth, void* d_keys, void* d_depth, void* d_value, size_t cap, size_t* count) {
@@ -627,14 +613,13 @@ int sbm_occ_tree_leaves(sbm_occ_tree* tree, int max_depth, uint64_t* keys, int32
   *count = n;
   if (n > cap) return SBM_ERR_SIZE;
   if (!n) return SBM_OK;
-  const size_t kb = occ_pad(n * 8), vb = occ_pad(n * 4);
-  HIPCHK(h, h->occ.io.grow(kb + 2 * vb, h->stream));
-  char* io = h->occ.io.as<char>();
-  st = occ_tree_leaves_run(tree, max_depth, (unsigned long long*)io, (int*)(io + kb), (unsigned*)(io + kb + vb), n, count);
+  struct { unsigned long long* keys; int* depth; unsigned* value; } io;
+  HIPCHK(h, carve(h->occ.io, h->stream, [&](Carve& c) { io = {c.take<unsigned long long>(n), c.take<int>(n), c.take<unsigned>(n)}; }, occ_pad));
+  st = occ_tree_leaves_run(tree, max_depth, io.keys, io.depth, io.value, n, count);
   if (st != SBM_OK) return st;
-  HIPCHK(h, hipMemcpyAsync(keys, io, n * 8, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, hipMemcpyAsync(depth, io + kb, n * 4, hipMemcpyDeviceToHost, h->stream));
-  if (value) HIPCHK(h, hipMemcpyAsync(value, io + kb + vb, n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(keys, io.keys, n * 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(depth, io.depth, n * 4, hipMemcpyDeviceToHost, h->stream));
+  if (value) HIPCHK(h, hipMemcpyAsync(value, io.value, n * 4, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   return SBM_OK;
 }
@@ -659,19 +644,7 @@ int sbm_occ_tree_write_binary(sbm_occ_tree* tree, const char* path) {
   for (int d = 0; d <= kOccDepth; d++) nodes += tree->host.nodes_at[d], leaves += tree->host.leaves_at[d];
   const size_t bytes = (size_t)(2 * (nodes - leaves));
   std::vector<uint8_t> body;
-  try {
-    body.resize(bytes);
-  } catch (const std::bad_alloc&) {
-    return SBM_ERR_NOMEM;
-  }
-  if (bytes) {
-    size_t got = 0;
-    HIPCHK(h, h->occ.io.grow(bytes, h->stream));
-    st = occ_tree_binary_run(tree, h->occ.io.as<uint8_t>(), bytes, &got);
-    if (st != SBM_OK) return st;
-    HIPCHK(h, hipMemcpyAsync(body.data(), h->occ.io.p, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-  }
-  return occ_write_file(body, (size_t)nodes, tree->resolution, path);
+  st = occ_body_host(h, bytes, &body, [&](uint8_t* d_bytes, size_t* got) { return occ_tree_binary_run(tree, d_bytes, bytes, got); });
+  return st != SBM_OK ? st : occ_write_file(body, (size_t)nodes, tree->resolution, path);
 }
 }  // extern "C"

@@ -228,7 +228,7 @@ int occ_sort_run(sbm_handle* h, unsigned long long* const kk[2], unsigned* const
 
 int occ_compact_run(sbm_occ_map* map, uint32_t n, unsigned long long* d_keys, unsigned* d_vals) {
   sbm_handle* h = map->h;
-  HIPCHK(h, hipMemsetAsync((char*)map->ctr.p + offsetof(OccCounters, cursor), 0, sizeof(unsigned), h->stream));
+  HIPCHK(h, hipMemsetAsync(&map->ctr.as<OccCounters>()->cursor, 0, sizeof(unsigned), h->stream));
   hipLaunchKernelGGL(occ_compact_kernel, dim3((map->slots + 255) / 256), dim3(256), 0, h->stream, map->keys.as<unsigned long long>(),
                      map->hits.as<unsigned>(), map->slots, n, d_keys, d_vals, map->ctr.as<OccCounters>());
   HIPCHK(h, hipGetLastError());
@@ -248,12 +248,12 @@ static int occ_fetch_run(sbm_occ_map* map, unsigned long long* d_keys, unsigned*
   if (n > cap) return SBM_ERR_SIZE;
   if (n) {
     const uint32_t tiles = (n + kOccTile - 1) / kOccTile;
-    // second key array, second count array, and a first count array when the caller wants no counts
-    const size_t kb = occ_pad((size_t)n * 8), vb = occ_pad((size_t)n * 4);
-    HIPCHK(h, h->occ.sort.grow(kb + 2 * vb, h->stream));
+    // second key array, second count array, and a first count array for the caller who wants no counts
+    unsigned long long* kk[2] = {d_keys};
+    unsigned* vv[2];
+    HIPCHK(h, occ_sort_carve(h, n, &kk[1], &vv[1], &vv[0]));
+    if (d_hits) vv[0] = d_hits;
     HIPCHK(h, h->occ.hist.grow((size_t)256 * tiles * 4, h->stream));
-    unsigned long long* kk[2] = {d_keys, h->occ.sort.as<unsigned long long>()};
-    unsigned* vv[2] = {d_hits ? d_hits : (unsigned*)((char*)h->occ.sort.p + kb + vb), (unsigned*)((char*)h->occ.sort.p + kb)};
     unsigned* hist = h->occ.hist.as<unsigned>();
     HIPCHK(h, clk.mark(kOccBegin, h->stream));
     st = occ_compact_run(map, n, kk[0], vv[0]);
@@ -280,10 +280,9 @@ static int occ_fetch_host(sbm_occ_map* map, uint64_t* keys, uint32_t* hits, size
   *count = c.size;
   if (c.size > cap) return SBM_ERR_SIZE;
   if (!c.size) return c.overflow ? SBM_ERR_OCC_FULL : SBM_OK;
-  const size_t kb = occ_pad((size_t)c.size * 8);
-  HIPCHK(h, h->occ.io.grow(kb + (size_t)c.size * 4, h->stream));
-  unsigned long long* d_k = h->occ.io.as<unsigned long long>();
-  unsigned* d_v = (unsigned*)((char*)h->occ.io.p + kb);
+  unsigned long long* d_k;
+  unsigned* d_v;
+  HIPCHK(h, carve(h->occ.io, h->stream, [&](Carve& cv) { d_k = cv.take<unsigned long long>(c.size); d_v = cv.take<unsigned>(c.size); }, occ_pad));
   st = occ_fetch_run(map, d_k, d_v, c.size, count);
   if (st != SBM_OK && st != SBM_ERR_OCC_FULL) return st;
   HIPCHK(h, hipMemcpyAsync(keys, d_k, *count * 8, hipMemcpyDeviceToHost, h->stream));

@@ -365,13 +365,13 @@ int sbm_orb_describe(sbm_handle* h, const uint8_t* img, size_t img_stride, int w
   HIPCHK(h, dscope.enter());
   st = ensure_staging(h, 1, width, height);
   if (st != SBM_OK) return st;
-  const size_t kb = (size_t)cap * 8, out_bytes = 2 * kb + (size_t)cap * 32 + 16;   // points in, points out, descriptors, counts
-  HIPCHK(h, h->orb.io.grow(out_bytes, h->stream));
-  char* io = h->orb.io.as<char>();
-  float* d_ki = (float*)io;
-  float* d_ko = (float*)(io + kb);
-  uint8_t* d_de = (uint8_t*)(io + 2 * kb);
-  int* d_n = (int*)(io + 2 * kb + (size_t)cap * 32);
+  float *d_ki, *d_ko;
+  uint8_t* d_de;
+  int* d_n;
+  HIPCHK(h, carve(h->orb.io, h->stream, [&](Carve& c) {   // on 8-byte boundaries: two point lists before them keep the descriptors on 16
+    d_ki = c.take<float>((size_t)cap * 2); d_ko = c.take<float>((size_t)cap * 2);
+    d_de = c.take<uint8_t>((size_t)cap * 32); d_n = c.take<int>(4);   // count in, count out
+  }, 8));
   HIPCHK(h, hipMemcpy2DAsync(h->st.l.p, width, img, img_stride, width, height, hipMemcpyHostToDevice, h->stream));
   if (count > 0) HIPCHK(h, hipMemcpyAsync(d_ki, kpts, (size_t)count * 8, hipMemcpyHostToDevice, h->stream));
   HIPCHK(h, hipMemcpyAsync(d_n, &count, sizeof(int), hipMemcpyHostToDevice, h->stream));

@@ -42,47 +42,41 @@ struct PnpArgs {
   double confidence;
 };
 
-// One job's slice of the launch scratch.
+// One job's slice of the launch scratch; slice_layout has the sizes.
 struct Slice {
-  float* X;     // cap * 3 compacted object points
-  float* U;     // cap * 2 compacted image points
-  int* mt;      // cap from-indices (the reference's matches)
-  int* tt;      // cap to-indices
-  int* sub;     // iterations * 6
-  double* hR;   // iterations * 12 (R, t)
-  int* cnt;     // iterations
-  int* setA;    // cap + 1
-  int* setB;    // cap + 1
-  float* err;   // cap + 1
-  float* cd;    // cap + 1
-  float* ca;    // cap + 1
-  int* n;       // 4
+  float *X, *U;           // compacted object and image points
+  int *mt, *tt;           // from- and to-indices (the reference's matches)
+  int *sub, *cnt;         // per iteration: the subset and the count,
+  double* hR;             // and (R, t)
+  int *setA, *setB;       // refine lists
+  float *err, *cd, *ca;
+  int* n;
 };
 
-__host__ __device__ inline size_t slice_bytes(int cap, int iters) {
-  const size_t c = (size_t)cap, c1 = c + 1;
-  return pad16(c * 12) + pad16(c * 8) + 2 * pad16(c * 4) + pad16((size_t)iters * 24) + pad16((size_t)iters * 96) +
-         pad16((size_t)iters * 4) + 5 * pad16(c1 * 4) + 16;
-}
-
-__host__ __device__ inline Slice slice_at(char* base, int job, int cap, int iters) {
-  char* p = base + (size_t)job * slice_bytes(cap, iters);
-  const size_t c = (size_t)cap, c1 = c + 1;
+// The slice's layout: sized by its counting pass, placed by the same statements (host and kernels alike).
+__host__ __device__ inline Slice slice_layout(Carve& c, int cap, int iters) {
+  const size_t n = (size_t)cap, n1 = n + 1, it = (size_t)iters;
   Slice s;
-  s.X = (float*)p; p += pad16(c * 12);
-  s.U = (float*)p; p += pad16(c * 8);
-  s.mt = (int*)p; p += pad16(c * 4);
-  s.tt = (int*)p; p += pad16(c * 4);
-  s.sub = (int*)p; p += pad16((size_t)iters * 24);
-  s.hR = (double*)p; p += pad16((size_t)iters * 96);
-  s.cnt = (int*)p; p += pad16((size_t)iters * 4);
-  s.setA = (int*)p; p += pad16(c1 * 4);
-  s.setB = (int*)p; p += pad16(c1 * 4);
-  s.err = (float*)p; p += pad16(c1 * 4);
-  s.cd = (float*)p; p += pad16(c1 * 4);
-  s.ca = (float*)p; p += pad16(c1 * 4);
-  s.n = (int*)p;
+  s.X = c.take<float>(n * 3);   // n = cap points, n1 = cap + 1
+  s.U = c.take<float>(n * 2);
+  s.mt = c.take<int>(n);
+  s.tt = c.take<int>(n);
+  s.sub = c.take<int>(it * 6);
+  s.hR = c.take<double>(it * 12);   // (R, t)
+  s.cnt = c.take<int>(it);
+  s.setA = c.take<int>(n1);
+  s.setB = c.take<int>(n1);
+  s.err = c.take<float>(n1);
+  s.cd = c.take<float>(n1);
+  s.ca = c.take<float>(n1);
+  s.n = c.take<int>(4);
   return s;
+}
+__host__ __device__ inline size_t slice_bytes(int cap, int iters) { return carve_bytes([&](Carve& c) { slice_layout(c, cap, iters); }); }
+__host__ __device__ inline Slice slice_at(char* base, int job, int cap, int iters) {
+  __builtin_assume(base != nullptr);   // the launch scratch: a kernel's thirteen pointers need no null test
+  Carve place{base + (size_t)job * slice_bytes(cap, iters)};
+  return slice_layout(place, cap, iters);
 }
 
 __device__ __forceinline__ int clamp_count(int c, int cap) { return min(max(c, 0), cap); }
@@ -480,7 +474,7 @@ static int pnp_run(sbm_handle* h, int m, const int* jobs, const void* d_xyz, con
   const int iters = p->iterations;
   const size_t per_job = slice_bytes(cap, iters);
   const int mj = (int)std::max<size_t>(1, std::min<size_t>(kArgJobs, kScratchBudget / per_job));
-  HIPCHK(h, h->pnp.scratch.grow(per_job * mj, h->stream));
+  HIPCHK(h, h->pnp.scratch.grow(per_job * mj, h->stream));   // one piece of mj slices, each the counting pass of slice_layout: slice_at
   char* scratch = h->pnp.scratch.as<char>();
   for (int j0 = 0; j0 < m; j0 += mj) {
     const int k = std::min(mj, m - j0);

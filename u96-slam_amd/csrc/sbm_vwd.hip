@@ -255,11 +255,11 @@ static int vwd_run(sbm_vwd* v, const uint8_t* d_desc, int n, int4* d_knn_out, in
   HIPCHK(h, clk.start(vwd_stages(), h->profiling != 0));
   int nslice, slice_rows;
   vwd_plan(n, v->size, v->p.slices, &nslice, &slice_rows);
-  const size_t bpart = (size_t)nslice * n * sizeof(int4), bknn = (size_t)n * sizeof(int4);
-  HIPCHK(h, h->vwd.scratch.grow(bpart + bknn + (size_t)n, h->stream));
-  int4* part = h->vwd.scratch.as<int4>();
-  int4* knn = d_knn_out ? d_knn_out : (int4*)((char*)h->vwd.scratch.p + bpart);
-  uint8_t* unique = d_ids ? (uint8_t*)h->vwd.scratch.p + bpart + bknn : nullptr;
+  int4 *part, *knn;
+  uint8_t* unique;
+  HIPCHK(h, carve(h->vwd.scratch, h->stream, [&](Carve& c) { part = c.take<int4>((size_t)nslice * n); knn = c.take<int4>(n); unique = c.take<uint8_t>(n); }));
+  if (d_knn_out) knn = d_knn_out;
+  if (!d_ids) unique = nullptr;
   const VwdCounters* ctr = v->ctr.as<VwdCounters>();
   const bool l2 = v->p.metric == SBM_VWD_L2;
   const dim3 gs((n + kTile - 1) / kTile, nslice);
