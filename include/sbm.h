@@ -58,7 +58,7 @@
  * returns SBM_ERR_HIP (SBM_ERR_NOMEM if its 8-byte allocation fails) with the error in sbm_last_hip_error(), nothing is
  * remembered, and the next call runs the self-test again.
  *
- * Environment. The library reads these eleven variables (nothing else); an integrator never needs to set any of them:
+ * Environment. The library reads these twelve variables (nothing else); an integrator never needs to set any of them:
  *   variable            default  read      who sets it, and what for
  *   SBM_FAST_INPLACE    1        once      0 = run the sliding-sum SAD kernel instead of the interior one (the fallback that
  *                                          is taken automatically when the device self-test of the in-place v_mqsad
@@ -70,6 +70,9 @@
  *                                          priming rows; 1 = a segment takes the sums its predecessor left, where they are there
  *                                          when it starts (same results either way); 2 = the segments are launches of their own,
  *                                          so that every hand-off is taken; GPU tests / A-B measurements
+ *   SBM_FAST_FOLD       1        per call  0 = the last plain strip of a 128-disparity, window-15 launch runs as a plain strip even
+ *                                          where it has at most 22 columns (1 = folded over its disparity halves: same results);
+ *                                          GPU tests / A-B measurements
  *   SBM_SPECKLE_LISTS   1        per call  0 = the speckle filter's row-walking kernels (one wavefront per row, per-pixel labels)
  *                                          instead of the band walk + run records; GPU tests
  *   SBM_SPECKLE_BAND    auto     per call  2 / 4 = band height of the speckle filter's band walk, 0 = row-walking kernels;

@@ -505,6 +505,18 @@ int sbm_debug_handoff_bytes(const sbm_params* p, int n, int width, int height, i
   return SBM_OK;
 }
 
+// Whether that plan's last strip runs folded over its disparity halves under the current SBM_FAST_FOLD: out[0] = its columns
+// (sad_fast_fold_cols; 0: it does not fold). As sbm_debug_plan: for the tests, not part of the public header.
+int sbm_debug_fold(const sbm_params* p, int n, int width, int height, int inplace_ok, int* out) {
+  if (!p || !out) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  BmPlan pl;
+  const int st = bm_plan(*p, n, width, height, inplace_ok != 0, &pl);
+  if (st != SBM_OK) return st;
+  out[0] = sad_fast_fold_cols(pl);
+  return SBM_OK;
+}
+
 int sbm_rect_map_device(sbm_handle* h, const sbm_rect_cam* cam, int width, int height, void* d_map, int sync) {
   if (!h || !cam || !d_map) return SBM_ERR_NULL;
   if (width <= 0 || height <= 0 || width > 32767 || height > 32767) return SBM_ERR_SIZE;

@@ -12,7 +12,7 @@ namespace sbm {
 
 // Environment switches of the library -- the complete list, documented for integrators in include/sbm.h ("Environment").
 // They select a tested fallback or a code path that the GPU tests compare with the default one: SBM_FAST_INPLACE (0: the
-// sliding-sum kernel in place of the interior one), SBM_FAST_PFSHIFT, SBM_FAST_CS3, SBM_FAST_HANDOFF, SBM_SPECKLE_LISTS, SBM_SPECKLE_BAND,
+// sliding-sum kernel in place of the interior one), SBM_FAST_PFSHIFT, SBM_FAST_CS3, SBM_FAST_HANDOFF, SBM_FAST_FOLD, SBM_SPECKLE_LISTS, SBM_SPECKLE_BAND,
 // SBM_SPECKLE_SEG, SBM_HOST_ZEROCOPY, SBM_WIDE, SBM_CV_READING, SBM_OCC_OT_HOST_PARSE.
 inline int env_switch(const char* name, int dflt) {
   const char* e = getenv(name);
@@ -134,6 +134,9 @@ bool sad_fast_borders_in_launch(const Geom& g);   // the clamped border columns 
 int sad_fast_pfshift(const Geom& g);   // 2 or 1 when the interior kernel wants pre-scaled planes (see kPfBias), else 0
 // pl->f and the kernel's name for a call with pl->fast (g, border set): strips, row segments, layout, border jobs, grid and LDS
 void sad_fast_plan(BmPlan* pl);
+// Columns of the launch's last strip if it runs folded over its disparity halves (sbm_sad_fast_fold.h), else 0: a function of
+// the plan and SBM_FAST_FOLD alone.
+int sad_fast_fold_cols(const BmPlan& pl);
 // The planned launch. With pl.border the w/2 clamped columns on each side of [xc0,xc1) are computed by extra wavefronts of the
 // same launch (sbm_sad_border_wave.h); without it the launch leaves them untouched.
 // handoff / epoch / links: the scratch through which a row segment leaves its vertical sums to the next one (sad_fast_handoff_bytes()

@@ -390,6 +390,20 @@ void sad_fast_plan(BmPlan* pl) {
   sad_fast_dispatch(*pl, nullptr, nullptr);   // no arguments: the dispatch fills the plan
 }
 
+// The folded leftover strip (sbm_sad_fast_fold.h): the columns R of the launch's last strip if that strip runs folded, else 0.
+// It does when the strip is a plain one with R <= FoldLds::NV = 22 columns, the window is 15, the count exactly 128 and the layout
+// the lone wavefront -- KITTI: 1 101 interior columns = 18 stride-3 strips + 21. SBM_FAST_FOLD=0 (read per call: the GPU tests
+// flip it) keeps the plain strip.
+int sad_fast_fold_cols(const BmPlan& pl) {
+  const FastPlan& f = pl.f;
+  if (!pl.fast || env_switch("SBM_FAST_FOLD", 1) == 0) return 0;
+  if (f.NDW != FoldLds::NDW || f.NWAVES != 1 || !f.exact || f.NTERM * f.PW != FoldLds::NTERM * FoldLds::PW || !f.dual) return 0;
+  if (f.strips <= f.strips3) return 0;   // (no plain strip)
+  const int nv3 = 64 - (f.NTERM - 1), nv1 = 64 - f.PW * (f.NTERM - 1);
+  const int cols = (f.xc1 - f.xc0) - ((f.strips3 / 3) * 3 * nv3 + (f.strips - 1 - f.strips3) * nv1);
+  return cols >= 1 && cols <= FoldLds::NV ? cols : 0;
+}
+
 // Which segments take their sums over in this call (bit k: segment k from k - 1) and the dispatch order that goes with it: none
 // with cooperating wavefronts, a masked count or SBM_FAST_HANDOFF=0, every later segment where the segments are launches of their own, else
 // the segments behind the first D positions of fast_segment_order().
@@ -434,6 +448,7 @@ hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* di
   memcpy(a.segrow, f.segrow, sizeof(a.segrow));
   a.strips = f.strips; a.nseg = f.nseg; a.npairs = g.n; a.strips3 = f.strips3; a.uniq_plain = f.uniq_plain;
   a.xc0 = f.xc0; a.xc1 = f.xc1;
+  a.fold = sad_fast_fold_cols(pl) > 0;
   a.bord = f.bord; a.bnw = f.bnw; a.bseg = f.bseg; a.nbseg = f.nbseg;
   a.ho_link = fast_handoff_links(pl, a.segat);   // (fills the order)
   if (!handoff) a.ho_link = 0;

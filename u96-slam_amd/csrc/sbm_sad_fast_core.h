@@ -39,6 +39,7 @@ struct FastArgs {
   u32* ho;                   // [nseg - 1][npairs][strips] ready words, as many taken words, then (256-byte aligned) as many slots of FastHandoff<>::SLOT_B bytes
   u32 ho_epoch;              // this launch's number: a ready word that holds it was written by this launch
   int strips3;               // the first strips3 strips (a multiple of 3) have column stride 3, the others stride 1
+  int fold;                  // the last strip (a plain one) runs folded over its disparity halves (sad_fast_fold_cols, sbm_sad_fast_fold.h)
   int uniq_plain;            // 8 * (maxS * uniq / 100 + 1) fits 16 bits: deficit partial sums need no saturating adds
   int xc0, xc1;              // interior centre columns [xc0,xc1) (relative to lofs); xc0 = w/2
   int pfshift;               // the planes hold (value << pfshift) + 1: every sum below is scaled by 1 << pfshift (0 or 2)
@@ -141,6 +142,27 @@ struct DmaLds {
   static constexpr int PAT_OFS = STAGE_B > XLEV_B ? STAGE_B : XLEV_B;       // the left patterns of a staged row
   static constexpr int AREA_B = PAT_OFS + 256;
   static constexpr int WAVE_B = 2 * AREA_B + (P::NLEV - 1) * XLEV_B;
+};
+
+// LDS of the folded leftover strip (sbm_sad_fast_fold.h: the 128-disparity lone wavefront, window 15, folded over its two
+// disparity halves on at most NV columns): 5-column sums at lane stride 1, a 3-term window. It runs in place of the launch's
+// last plain strip, so it must fit what the launch allocates for that one: the same 192 staged dword slots (its highest window
+// read is slot 31 + 64 + 4 * 15 + 8 = 163) and an exchange level of XS = 74 entries against the plain strip's 76.
+struct FoldLds {
+  using Plain = DmaLds<128, 1, 5, 3, 1>;
+  static constexpr int NDW = 128, NTERM = 3, PW = 5, KS = 5;
+  static constexpr int NQ = NDW / 2 / 4;                                    // disparity quads of a lane: half the range
+  static constexpr int NV = 32 - KS * (NTERM - 1);                          // columns that produce an output: 22
+  static constexpr int NSLOT = ((31 + NDW / 2 + 4 * (NQ - 1) + 8 + 1) + 63) / 64 * 64;
+  static constexpr int XS = 64 + KS * (NTERM - 1);
+  static constexpr int XCH = 2;
+  static constexpr int STAGE_B = NSLOT * 4;
+  static constexpr int XLEV_B = ((XCH / 2) * XS + (XS * 4 + 15) / 16) * 16;
+  static constexpr int PAT_OFS = STAGE_B > XLEV_B ? STAGE_B : XLEV_B;
+  static constexpr int AREA_B = PAT_OFS + 256;
+  static constexpr int WAVE_B = 2 * AREA_B;
+  static_assert(NSLOT == 192 && XS == 74, "the folded strip stages 192 dword slots and exchanges 74 entries");
+  static_assert(NSLOT <= Plain::L::NSLOT && WAVE_B <= Plain::WAVE_B, "the folded strip fits the plain strip's LDS");
 };
 
 // ---------------------------------------------------------------------------------------------------------------------------

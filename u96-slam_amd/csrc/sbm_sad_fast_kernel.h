@@ -4,6 +4,7 @@
 #pragma once
 #include "sbm_sad_fast_core.h"
 #include "sbm_sad_fast_strip.h"
+#include "sbm_sad_fast_fold.h"
 
 namespace sbm {
 
@@ -76,7 +77,16 @@ sad_fast_kernel(FastArgs a) {
       const int t = strip / 3;
       strip_at(std::integral_constant<int, 3>{}, t * (3 * NV3) + (strip - 3 * t));
     } else {
-      strip_at(std::integral_constant<int, 1>{}, (a.strips3 / 3) * (3 * NV3) + (strip - a.strips3) * NV1);
+      const int cb = (a.strips3 / 3) * (3 * NV3) + (strip - a.strips3) * NV1;
+      // the third strip kind: a last plain strip of few columns runs folded over its disparity halves (sbm_sad_fast_fold.h) --
+      // in the plain strip's LDS (FoldLds) and hand-off slot
+      if constexpr (NDW == FoldLds::NDW && NWAVES == 1 && EXACT_ND && NTERM * PW == FoldLds::NTERM * FoldLds::PW) {
+        if (a.fold && strip == a.strips - 1) {
+          sad_fast_strip_fold(a, ldsb, ldsb + FoldLds::AREA_B, cb, segi, pair, strip);
+          return;
+        }
+      }
+      strip_at(std::integral_constant<int, 1>{}, cb);
     }
   } else {
     constexpr int NV1 = 64 - PW * (NTERM - 1);
