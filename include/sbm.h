@@ -1105,7 +1105,7 @@ int sbm_occ_write_binary(const uint64_t* keys, size_t n, double resolution, cons
  *             v += u in float; v = cmin if v < cmin, else cmax if v > cmax (updateNodeLogOdds; updateNode's early return for a
  *             leaf at its clamp gives the same value).
  *  order      scans are applied in call order and plane order; through the clamps the result depends on it.
- *  Not provided: discretize, bounding boxes, change detection, insertPointCloudRays.
+ *  Not provided: insertPointCloudRays (per-ray updates whose result depends on thread order); the other switches are below, under "insert options".
  *  Mode. A map's mode is fixed by its first accepted insert after create or reset: hits (sbm_occ_insert*) or log-odds
  *  (sbm_occ_insert_cloud*, sbm_occ_insert_rays*). An insert or a fetch of the other kind returns SBM_ERR_UNSUPPORTED and changes
  *  nothing; a fetch of either kind serves an empty map. sbm_occ_size, sbm_occ_overflow and sbm_occ_reset serve both.
@@ -1523,6 +1523,84 @@ int sbm_occ_ot_leaves(const void* bytes, size_t n, uint64_t* first_key, int32_t*
 int sbm_occ_ot_load(sbm_occ_map* map, const void* bytes, size_t n, int sync);
 /* The same from a file; SBM_ERR_UNSUPPORTED when it cannot be opened or read. */
 int sbm_occ_ot_read(sbm_occ_map* map, const char* path, int sync);
+
+/* ---- occupancy map: insert options, discretize, the bounding box and change detection (OccupancyOcTreeBase.hxx:148-165,
+ * 222-259, 415-427, 891-918) ------------------------------------------------------------------------------------------------------
+ * The three switches of insertPointCloud that a long-running mapper needs, for the log-odds mode above ("occupancy map: ray-cast
+ * free space"), whose every statement stays true when all three are off. All three are per-voxel contracts.
+ * tests/occupancy_option_cases.py is a literal transcription of this text, and tests/golden/occupancy_options.npz holds what the
+ * reference's own octomap answered: after every scan the leaves and the changed keys, bit for bit.
+ *  discretize computeDiscreteUpdate: per point and per axis k = (uint16)((int)floor(factor * (double)coord) + 32768), the
+ *             UNCHECKED coordToKey. QUIRK, restated on purpose: a coordinate outside +-3276.8 m whose floor still fits an int
+ *             wraps modulo 65536 and lands inside the map (x = 3300 gives key 232, centre -3253.55). A point with a coordinate
+ *             that is not finite, or whose floor fits no int, is dropped (the reference's cast is undefined there). The
+ *             distinct keys of the scan each give ONE point, keyToCoord(k) per axis = (float)(((double)((int)k - 32768) + 0.5)
+ *             * resolution), and that list goes through the scan unchanged: the range gate, the truncation and the box tests
+ *             see the voxel centre, not the original point. The result is a set; it does not depend on which duplicate wins.
+ *  box        two float points, min and max, with their keys from coordToKeyChecked; a new map holds (0, 0, 0) twice. Setting a
+ *             point that has no key (NaN included) returns SBM_ERR_SIZE and leaves the box as it was (octomap logs an error and
+ *             keeps a half-written key). min > max on an axis is accepted: nothing is inside such a box. With the limit on, per
+ *             point p: its voxel is occupied iff inBBX(p) in FLOAT (>= min and <= max per axis, both inclusive) and p is within
+ *             range and coordToKeyChecked(p) passes, whether or not a ray exists; the ray runs to p, or to the truncated end when
+ *             p is beyond max_range; its cells are taken in order while inBBX(key) holds (by KEY, inclusive), and the first cell
+ *             outside ENDS THE RAY. An origin outside the box therefore frees nothing, even when the ray crosses the box later.
+ *             free -= occupied as before.
+ *  changes    per voxel one of three states: none, created (octomap's true), flipped (octomap's false). While detection is on,
+ *             the one update a voxel gets per scan makes a voxel that was absent before the scan `created`; otherwise, if
+ *             isNodeOccupied (logodds >= logodds(occupancy_thres)) differs before and after the update: none -> flipped, flipped
+ *             -> none (octomap erases the entry), created stays. sbm_occ_reset_change_detection clears every state; disabling
+ *             stops recording and keeps what is recorded. A voxel lost to overflow records nothing.
+ *             DIVERGENCE: sbm_occ_reset and the .bt / .ot loaders clear the states (octomap's clear() keeps keys of nodes that
+ *             no longer exist). The two switches and the box survive a reset. The loaders record nothing, as readBinary / read
+ *             record nothing.
+ *  lazy_eval  only defers octomap's inner nodes; the depth-16 values are identical. The C++ adaptor accepts the flag and ignores it.
+ *  Mode. The box, detection and discretize belong to the log-odds mode. SBM_ERR_UNSUPPORTED, and nothing changes: enabling the
+ *  box or detection on a map in hit mode; a hit insert (sbm_occ_insert*) on a map with either switch on; a change fetch or count
+ *  on a map in hit mode.
+ *  Device. The switches select instantiations of the MARK and APPLY kernels; with both off the launches
+ *  are the ones of the section above. Box: MARK tests every cell, the origin's included, against the key box before it marks it,
+ *  and the end point against the float box. Changes: one byte per slot, allocated by the first enable; the lane whose
+ *  compare-and-swap claimed a slot ORs "created this scan" into the flag word with its bit, and APPLY, which visits a touched slot
+ *  once, steps the state without an atomic. Discretize: a launch before MARK, one lane per point, claims the wrapped key in a
+ *  per-scan scratch set (64-bit compare-and-swap, open addressing over at least twice the points, cleared per scan in stream
+ *  order); the claiming lane appends the key to a list, and MARK runs one lane per list entry. No float atomics, no spin waits,
+ *  no grid barriers. sbm_get_profile: no new names; the dedupe counts under "occ_rays_mark", the change fetch under "occ_fetch". */
+/* The box's two points (HOST memory). SBM_ERR_NULL; SBM_ERR_SIZE when a coordinate of either has no key: the box is then as it
+ * was. Host code: serves a map in either mode. */
+int sbm_occ_set_bbx(sbm_occ_map* map, const float min[3], const float max[3]);
+/* useBBXLimit(enable != 0) for the inserts that follow. SBM_ERR_NULL; SBM_ERR_UNSUPPORTED to enable on a map in hit mode. */
+int sbm_occ_use_bbx_limit(sbm_occ_map* map, int enable);
+/* The box as it is: its points, their keys and the switch; every output may be NULL. SBM_ERR_NULL without a map. */
+int sbm_occ_get_bbx(sbm_occ_map* map, float min[3], float max[3], uint16_t min_key[3], uint16_t max_key[3], int* enabled);
+/* enableChangeDetection(enable != 0) for the inserts that follow. The first enable allocates one byte per slot. SBM_ERR_NULL;
+ * SBM_ERR_UNSUPPORTED to enable on a map in hit mode. */
+int sbm_occ_enable_change_detection(sbm_occ_map* map, int enable);
+/* isChangeDetectionEnabled into *enabled. SBM_ERR_NULL. */
+int sbm_occ_change_detection_enabled(sbm_occ_map* map, int* enabled);
+/* resetChangeDetection: every state becomes none, in stream order. SBM_ERR_NULL. */
+int sbm_occ_reset_change_detection(sbm_occ_map* map);
+/* numChangesDetected into *count. Synchronous. SBM_ERR_NULL; SBM_ERR_UNSUPPORTED for a map in hit mode. */
+int sbm_occ_num_changes(sbm_occ_map* map, size_t* count);
+/* changedKeys, as sbm_occ_fetch_logodds_device fetches: the changed voxels ascending by packed key (octomap's KeyBoolMap has no
+ * order of its own) through the map's radix sort, with one byte per key in d_created (may be NULL): 1 created, 0 flipped. d_keys
+ * (8-byte aligned) and d_created hold cap entries in DEVICE memory; *count receives the number of changes, and when it exceeds
+ * cap nothing is written and the call returns SBM_ERR_SIZE. Synchronous; the map is left as it was. SBM_ERR_NULL (d_keys may be
+ * NULL only for cap == 0); SBM_ERR_UNSUPPORTED for a misaligned d_keys or a map in hit mode. */
+int sbm_occ_fetch_changes_device(sbm_occ_map* map, void* d_keys, void* d_created, size_t cap, size_t* count);
+/* The same into HOST memory. */
+int sbm_occ_fetch_changes(sbm_occ_map* map, uint64_t* keys, uint8_t* created, size_t cap, size_t* count);
+/* insertPointCloud(scan, origin, maxrange, lazy_eval, discretize = true): the arguments, checks and codes of
+ * sbm_occ_insert_cloud_device / sbm_occ_insert_cloud, the scan discretised as stated above. */
+int sbm_occ_insert_cloud_discrete_device(sbm_occ_map* map, size_t n_points, const void* d_xyz, const float* origin,
+                                         const sbm_occ_ray_params* params, int sync);
+int sbm_occ_insert_cloud_discrete(sbm_occ_map* map, size_t n_points, const float* xyz, const float* origin,
+                                  const sbm_occ_ray_params* params);
+/* The arguments, checks and codes of sbm_occ_insert_rays_device / sbm_occ_insert_rays; every plane is one discretised scan of the
+ * points sbm_occ_insert_rays_device gives it (the pixels the hit insert reprojects and transforms). */
+int sbm_occ_insert_rays_discrete_device(sbm_occ_map* map, int n, const void* d_disp, int width, int height, int scale,
+                                        const sbm_stereo_model* model, const float* poses, const sbm_occ_ray_params* params, int sync);
+int sbm_occ_insert_rays_discrete(sbm_occ_map* map, int n, const int16_t* disp, int width, int height, int scale,
+                                 const sbm_stereo_model* model, const float* poses, const sbm_occ_ray_params* params);
 
 /* ---- visual-word dictionary: addNewWords, computeLikelihood, limitKeypoints ---------------------------------------------------
  * The reference's loop-closure thread, started by Mapper::process for each key frame: addWordIds -> VWDictionary::addNewWords

@@ -15,6 +15,8 @@
 // readBinary() loads a .bt back into the map: the host parses the pruned tree, the device expands its leaves to voxels.
 // write() / read() are octomap's .ot file, which keeps every voxel's log-odds: scans, write, read, more scans equal the
 // uninterrupted run.
+// setBBXMin() / setBBXMax() / useBBXLimit(), enableChangeDetection() / changedKeys() and the discretize flag of insertPointCloud
+// are octomap's three insert switches, in its spelling.
 #ifndef SBM_OCCUPANCY_HPP_
 #define SBM_OCCUPANCY_HPP_
 
@@ -22,6 +24,7 @@
 #include <cstdint>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "sbm_stereobm.hpp"   // sbm::Error
@@ -138,19 +141,82 @@ class OccupancyMap {
   // octomap's probabilities; rayParams().max_range is insertPointCloud's maxrange for insertRays (negative: no limit)
   sbm_occ_ray_params& rayParams() { return rp_; }
   // tree.insertPointCloud(scan, sensor_origin, maxrange): n float triples in host memory
-  void insertPointCloud(const float* xyz, size_t n, const float origin[3], double maxrange = -1.) {
+  // lazy_eval only defers octomap's inner nodes, which the map does not hold: accepted and ignored. discretize casts one ray
+  // per end voxel instead of one per point (computeDiscreteUpdate).
+  void insertPointCloud(const float* xyz, size_t n, const float origin[3], double maxrange = -1., bool lazy_eval = false,
+                        bool discretize = false) {
+    (void)lazy_eval;
     sbm_occ_ray_params rp = rp_;
     rp.max_range = maxrange;
-    check(sbm_occ_insert_cloud(m_, n, xyz, origin, &rp));
+    check(discretize ? sbm_occ_insert_cloud_discrete(m_, n, xyz, origin, &rp) : sbm_occ_insert_cloud(m_, n, xyz, origin, &rp));
   }
   // One node as insert() takes it, ray-cast from the sensorOrigin the reference computes (main.cpp:520) and never uses: the
   // pose's translation.
-  void insertRays(const int16_t* disp, int width, int height, int scale, const sbm_stereo_model& model, const float pose[12]) {
-    check(sbm_occ_insert_rays(m_, 1, disp, width, height, scale, &model, pose, &rp_));
+  void insertRays(const int16_t* disp, int width, int height, int scale, const sbm_stereo_model& model, const float pose[12],
+                  bool lazy_eval = false, bool discretize = false) {
+    (void)lazy_eval;
+    check(discretize ? sbm_occ_insert_rays_discrete(m_, 1, disp, width, height, scale, &model, pose, &rp_)
+                     : sbm_occ_insert_rays(m_, 1, disp, width, height, scale, &model, pose, &rp_));
   }
   void insertRaysDevice(int n, const void* d_disp, int width, int height, int scale, const sbm_stereo_model& model,
-                        const float* poses, bool sync = true) {
-    check(sbm_occ_insert_rays_device(m_, n, d_disp, width, height, scale, &model, poses, &rp_, sync ? 1 : 0));
+                        const float* poses, bool sync = true, bool lazy_eval = false, bool discretize = false) {
+    (void)lazy_eval;
+    check(discretize ? sbm_occ_insert_rays_discrete_device(m_, n, d_disp, width, height, scale, &model, poses, &rp_, sync ? 1 : 0)
+                     : sbm_occ_insert_rays_device(m_, n, d_disp, width, height, scale, &model, poses, &rp_, sync ? 1 : 0));
+  }
+
+  // ---- insert options of the log-odds mode, in octomap's spelling (sbm.h, "occupancy map: insert options") -------------------
+  // A point without a key throws (SBM_ERR_SIZE) and leaves the box as it was, where octomap logs an error.
+  void setBBXMin(const float min[3]) {
+    const Box b = box();
+    check(sbm_occ_set_bbx(m_, min, b.max));
+  }
+  void setBBXMax(const float max[3]) {
+    const Box b = box();
+    check(sbm_occ_set_bbx(m_, b.min, max));
+  }
+  void useBBXLimit(bool enable) { check(sbm_occ_use_bbx_limit(m_, enable ? 1 : 0)); }
+  bool bbxSet() { return box().enabled != 0; }
+  void getBBXMin(float min[3]) {
+    const Box b = box();
+    min[0] = b.min[0], min[1] = b.min[1], min[2] = b.min[2];
+  }
+  void getBBXMax(float max[3]) {
+    const Box b = box();
+    max[0] = b.max[0], max[1] = b.max[1], max[2] = b.max[2];
+  }
+  // inBBX(point): in float, both bounds inclusive; inBBX(key): by key, both inclusive
+  bool inBBX(const float p[3]) {
+    const Box b = box();
+    return p[0] >= b.min[0] && p[1] >= b.min[1] && p[2] >= b.min[2] && p[0] <= b.max[0] && p[1] <= b.max[1] && p[2] <= b.max[2];
+  }
+  bool inBBX(const uint16_t key[3]) {
+    const Box b = box();
+    return key[0] >= b.min_key[0] && key[1] >= b.min_key[1] && key[2] >= b.min_key[2] && key[0] <= b.max_key[0] &&
+           key[1] <= b.max_key[1] && key[2] <= b.max_key[2];
+  }
+  void enableChangeDetection(bool enable) { check(sbm_occ_enable_change_detection(m_, enable ? 1 : 0)); }
+  bool isChangeDetectionEnabled() {
+    int on = 0;
+    check(sbm_occ_change_detection_enabled(m_, &on));
+    return on != 0;
+  }
+  void resetChangeDetection() { check(sbm_occ_reset_change_detection(m_)); }
+  size_t numChangesDetected() {
+    size_t n = 0;
+    check(sbm_occ_num_changes(m_, &n));
+    return n;
+  }
+  // changedKeysBegin() .. changedKeysEnd() as (packed key, created) pairs ascending by key: created is octomap's true, a voxel
+  // whose occupancy flipped its false
+  std::vector<std::pair<uint64_t, bool>> changedKeys() {
+    std::vector<uint64_t> k(numChangesDetected());
+    std::vector<uint8_t> c(k.size());
+    size_t n = 0;
+    check(sbm_occ_fetch_changes(m_, k.data(), c.data(), k.size(), &n));
+    std::vector<std::pair<uint64_t, bool>> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = std::make_pair(k[i], c[i] != 0);
+    return out;
   }
   // the stored voxels ascending by packed key with their log-odds
   std::vector<uint64_t> leaves(std::vector<float>& logodds) {
@@ -287,6 +353,16 @@ class OccupancyMap {
     q.occupancy_thres_log = occupancyThresLog();
     q.ignore_unknown = ignoreUnknownCells ? 1 : 0;
     return q;
+  }
+  struct Box {
+    float min[3], max[3];
+    uint16_t min_key[3], max_key[3];
+    int enabled;
+  };
+  Box box() {
+    Box b;
+    check(sbm_occ_get_bbx(m_, b.min, b.max, b.min_key, b.max_key, &b.enabled));
+    return b;
   }
   static void check(int st) {
     if (st != SBM_OK) throw Error(st, sbm_strerror(st));

@@ -3,12 +3,14 @@
 it, both sides of the record protocol between a generator and its driver (tools/octomap_drivers/driver.h describes it), the
 deterministic .npz writer, and the small arithmetic of keys, voxels and floats.
 
-The fixtures depend on each other in the order of FIXTURES: a generator reads earlier fixtures from tests/golden (load()) and
-writes its own to --out. Run as a program, this file runs the whole chain:
+The fixtures depend on each other in the order of FIXTURES, then of LATER_FIXTURES: a generator reads earlier fixtures from
+tests/golden (load()) and writes its own to --out. Run as a program, this file runs the whole chain, FIXTURES first:
 
     python tools/octomap_kit.py --reference /path/to/U96-SLAM [--out DIR]
 
-A new fixture adds a driver tools/octomap_drivers/<name>.cpp, a generator with its cases, and its line in FIXTURES.
+FIXTURES is closed: tests/test_occupancy_fixture_kit.py pins its six names. A new fixture adds a driver
+tools/octomap_drivers/<name>.cpp, a generator with its cases, and its line in LATER_FIXTURES; load() takes every fixture of
+LATER_FIXTURES as later than all of FIXTURES.
 """
 import argparse
 import concurrent.futures
@@ -37,6 +39,8 @@ BUILD = ROOT / "oracle" / "_ref" / "octomap_kit"        # untracked: the archive
 # fixture -> its generator, in the order in which they depend on each other
 FIXTURES = {"octomap": "make_occupancy_fixtures.py", "rays": "make_occupancy_ray_fixtures.py", "query": "make_occupancy_query_fixtures.py",
             "tree": "make_occupancy_tree_fixtures.py", "load": "make_occupancy_load_fixtures.py", "ot": "make_occupancy_ot_fixtures.py"}
+# fixtures added after that list was closed, in their own order of dependence; they may read every fixture above
+LATER_FIXTURES = {"options": "make_occupancy_option_fixtures.py"}
 RESOLUTION = 0.1
 PROBS = ("prob_hit", "prob_miss", "clamp_min", "clamp_max", "occupancy_thres")
 DEFAULT_PROBS = [getattr(rc.RayParams(), k) for k in PROBS]
@@ -193,8 +197,8 @@ def save(out_dir, name, arrays, writer=write_npz, cpu=None):
 
 
 def load(name, by):
-    """The committed fixture `name`, for the generator of fixture `by`, which has to come later in FIXTURES"""
-    order = list(FIXTURES)
+    """The committed fixture `name`, for the generator of fixture `by`, which has to come later in FIXTURES + LATER_FIXTURES"""
+    order = list(FIXTURES) + list(LATER_FIXTURES)
     assert order.index(name) < order.index(by), f"{by} cannot depend on {name}"
     return dict(np.load(GOLDEN / f"occupancy_{name}.npz"))
 
@@ -257,5 +261,5 @@ def bench_scans(planes=BENCH_PLANES, max_range=BENCH_RANGE):
 
 if __name__ == "__main__":
     args = arguments(__doc__)
-    for tool in FIXTURES.values():
+    for tool in list(FIXTURES.values()) + list(LATER_FIXTURES.values()):
         subprocess.run([sys.executable, str(ROOT / "tools" / tool), "--reference", args.reference, "--out", args.out], check=True)

@@ -412,6 +412,20 @@ def load_library():
     L.sbm_occ_ot_leaves.argtypes = [vp, sz, vp, vp, vp, sz, ctypes.POINTER(sz)]
     L.sbm_occ_ot_load.argtypes = [vp, vp, sz, ci]
     L.sbm_occ_ot_read.argtypes = [vp, ctypes.c_char_p, ci]
+    # occupancy map: insert options
+    L.sbm_occ_set_bbx.argtypes = [vp, vp, vp]
+    L.sbm_occ_use_bbx_limit.argtypes = [vp, ci]
+    L.sbm_occ_get_bbx.argtypes = [vp, vp, vp, vp, vp, ctypes.POINTER(ci)]
+    L.sbm_occ_enable_change_detection.argtypes = [vp, ci]
+    L.sbm_occ_change_detection_enabled.argtypes = [vp, ctypes.POINTER(ci)]
+    L.sbm_occ_reset_change_detection.argtypes = [vp]
+    L.sbm_occ_num_changes.argtypes = [vp, ctypes.POINTER(sz)]
+    L.sbm_occ_fetch_changes_device.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_fetch_changes.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_insert_cloud_discrete_device.argtypes = L.sbm_occ_insert_cloud_device.argtypes
+    L.sbm_occ_insert_cloud_discrete.argtypes = L.sbm_occ_insert_cloud.argtypes
+    L.sbm_occ_insert_rays_discrete_device.argtypes = L.sbm_occ_insert_rays_device.argtypes
+    L.sbm_occ_insert_rays_discrete.argtypes = L.sbm_occ_insert_rays.argtypes
     wp = ctypes.POINTER(VwdParams)
     pi = ctypes.POINTER(ci)
     L.sbm_vwd_params_default.argtypes = [wp]

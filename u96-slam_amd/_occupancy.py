@@ -1,6 +1,7 @@
 """The occupancy voxel map of the reference's buildOccupancyGridMap (src/slam/src/core/main.cpp:495-561): a device-side set of
 octomap keys fed straight from disparity planes, and the octomap binary stream (.bt) written from its distinct keys. Its second
-mode is octomap's insertPointCloud: float log-odds per voxel, free space ray-cast from each scan's origin."""
+mode is octomap's insertPointCloud: float log-odds per voxel, free space ray-cast from each scan's origin, with octomap's three
+insert switches: discretize, the bounding box and change detection."""
 import ctypes
 import os
 
@@ -200,13 +201,14 @@ class OccupancyMap:
     def insert_cloud(self, points, origin, params=None, sync=True, **kw):
         """octomap's insertPointCloud(scan, origin, maxrange): points (m, 3) as a torch CUDA float32 tensor or a numpy array
         (the host form, always synchronous), origin three floats. The parameters of the last log-odds insert are the ones
-        write_binary_logodds thresholds with."""
+        write_binary_logodds thresholds with. discretize=True casts one ray per end voxel instead of one per point."""
+        discrete = "_discrete" if kw.pop("discretize", False) else ""
         rp = self._ray_params(params, kw)
         o = np.ascontiguousarray(np.asarray(origin, np.float32).reshape(3))
         if isinstance(points, np.ndarray):
             p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
-            _check(self._L.sbm_occ_insert_cloud(self._m, len(p), p.ctypes.data if len(p) else None, o.ctypes.data, rp),
-                   self._engine._h)
+            _check(getattr(self._L, f"sbm_occ_insert_cloud{discrete}")(self._m, len(p), p.ctypes.data if len(p) else None, o.ctypes.data,
+                                                                       rp), self._engine._h)
             return
         torch = _torch()
         if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or not points.is_cuda or points.dim() != 2 or \
@@ -214,23 +216,25 @@ class OccupancyMap:
             raise StereoBMError(-2, "points must be a CUDA float32 (m, 3) tensor on the engine's device")
         p = points.contiguous()
         torch.cuda.current_stream(p.device).synchronize()
-        _check(self._L.sbm_occ_insert_cloud_device(self._m, p.shape[0], p.data_ptr() if p.shape[0] else None, o.ctypes.data, rp,
-                                                   1 if sync else 0), self._engine._h)
+        _check(getattr(self._L, f"sbm_occ_insert_cloud{discrete}_device")(self._m, p.shape[0], p.data_ptr() if p.shape[0] else None,
+                                                                          o.ctypes.data, rp, 1 if sync else 0), self._engine._h)
         if sync:
             self._engine._inflight.clear()
         else:
             self._engine._inflight.append((p,))
 
     def insert_rays(self, disparity, model, poses, scale=1, params=None, sync=True, **kw):
-        """The arguments of insert(); plane i is one scan from the origin (o14, o24, o34) of pose i."""
+        """The arguments of insert(); plane i is one scan from the origin (o14, o24, o34) of pose i. discretize=True as for
+        insert_cloud."""
+        discrete = "_discrete" if kw.pop("discretize", False) else ""
         rp = self._ray_params(params, kw)
         if isinstance(disparity, np.ndarray):
             d = np.ascontiguousarray(disparity, np.int16)
             d = d[None] if d.ndim == 2 else d
             n, h, w = d.shape
             p = _poses(poses, n)
-            _check(self._L.sbm_occ_insert_rays(self._m, n, d.ctypes.data, w, h, int(scale), ctypes.byref(model), p.ctypes.data, rp),
-                   self._engine._h)
+            _check(getattr(self._L, f"sbm_occ_insert_rays{discrete}")(self._m, n, d.ctypes.data, w, h, int(scale), ctypes.byref(model),
+                                                                      p.ctypes.data, rp), self._engine._h)
             return
         torch = _torch()
         if not isinstance(disparity, torch.Tensor) or disparity.dtype != torch.int16 or not disparity.is_cuda or \
@@ -239,12 +243,68 @@ class OccupancyMap:
         d3, n, h, w = self._engine._as3d(disparity)
         p = _poses(poses, n)   # read before the call returns
         torch.cuda.current_stream(d3.device).synchronize()
-        _check(self._L.sbm_occ_insert_rays_device(self._m, n, d3.data_ptr(), w, h, int(scale), ctypes.byref(model), p.ctypes.data,
-                                                  rp, 1 if sync else 0), self._engine._h)
+        _check(getattr(self._L, f"sbm_occ_insert_rays{discrete}_device")(self._m, n, d3.data_ptr(), w, h, int(scale), ctypes.byref(model),
+                                                                         p.ctypes.data, rp, 1 if sync else 0), self._engine._h)
         if sync:
             self._engine._inflight.clear()
         else:
             self._engine._inflight.append((d3,))
+
+    # ---- insert options: octomap's bounding box and change detection, for the log-odds inserts that follow --------------------
+    def set_bbx(self, lo, hi):
+        """setBBXMin(lo), setBBXMax(hi): two points of three floats. A point without a key raises (code -2) and the box stays."""
+        lo = np.ascontiguousarray(np.asarray(lo, np.float32).reshape(3))
+        hi = np.ascontiguousarray(np.asarray(hi, np.float32).reshape(3))
+        _check(self._L.sbm_occ_set_bbx(self._m, lo.ctypes.data, hi.ctypes.data), self._engine._h)
+
+    def use_bbx_limit(self, enable=True):
+        _check(self._L.sbm_occ_use_bbx_limit(self._m, int(bool(enable))), self._engine._h)
+
+    def bbx(self):
+        """dict: min, max (float32 (3,)), min_key, max_key (uint16 (3,)), enabled"""
+        lo, hi, klo, khi = np.empty(3, np.float32), np.empty(3, np.float32), np.empty(3, np.uint16), np.empty(3, np.uint16)
+        on = ctypes.c_int()
+        _check(self._L.sbm_occ_get_bbx(self._m, lo.ctypes.data, hi.ctypes.data, klo.ctypes.data, khi.ctypes.data, ctypes.byref(on)),
+               self._engine._h)
+        return dict(min=lo, max=hi, min_key=klo, max_key=khi, enabled=bool(on.value))
+
+    def enable_change_detection(self, enable=True):
+        _check(self._L.sbm_occ_enable_change_detection(self._m, int(bool(enable))), self._engine._h)
+
+    def change_detection_enabled(self):
+        on = ctypes.c_int()
+        _check(self._L.sbm_occ_change_detection_enabled(self._m, ctypes.byref(on)), self._engine._h)
+        return bool(on.value)
+
+    def reset_change_detection(self):
+        _check(self._L.sbm_occ_reset_change_detection(self._m), self._engine._h)
+
+    def num_changes(self):
+        v = ctypes.c_size_t()
+        _check(self._L.sbm_occ_num_changes(self._m, ctypes.byref(v)), self._engine._h)
+        return v.value
+
+    def changes(self):
+        """octomap's changedKeys -> (packed keys uint64 ascending, uint8: 1 created, 0 occupancy flipped) as numpy arrays."""
+        n = self.num_changes()
+        keys, created = np.empty(n, np.uint64), np.empty(n, np.uint8)
+        got = ctypes.c_size_t()
+        _check(self._L.sbm_occ_fetch_changes(self._m, keys.ctypes.data if n else None, created.ctypes.data if n else None, n,
+                                             ctypes.byref(got)), self._engine._h)
+        return keys[:got.value], created[:got.value]
+
+    def changes_device(self):
+        """The same as torch CUDA tensors: keys int64, created uint8."""
+        torch = _torch()
+        n = self.num_changes()
+        dev = torch.device("cuda", self._engine._device)
+        keys = torch.empty((n,), dtype=torch.int64, device=dev)
+        created = torch.empty((n,), dtype=torch.uint8, device=dev)
+        got = ctypes.c_size_t()
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.sbm_occ_fetch_changes_device(self._m, keys.data_ptr() if n else None, created.data_ptr() if n else None, n,
+                                                    ctypes.byref(got)), self._engine._h)
+        return keys[:got.value], created[:got.value]
 
     def load_binary(self, data_or_path, params=None, sync=True, **kw):
         """octomap's readBinary: replace the map's content by the voxels of a .bt stream -- bytes (or a uint8 array), or the

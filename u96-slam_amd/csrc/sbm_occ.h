@@ -75,6 +75,8 @@ constexpr int kOccDepth = 16;
 enum { kOccModeNone, kOccModeHits, kOccModeLogOdds };
 constexpr int kOccMaxSteps = 3 * 65536;   // of one ray: each step moves one key by one on one axis
 constexpr unsigned kOccFree = 1, kOccOccupied = 2;   // flag word of a slot within one scan
+constexpr unsigned kOccCreated = 4;                  // ... under change detection: the scan claimed the slot
+enum : uint8_t { kOccChangeNone, kOccChangeCreated, kOccChangeFlipped };   // change state of a slot (octomap's changed_keys: true, false)
 constexpr unsigned kOccCollapsed = 1u << 8;   // info word of a tree node: bits 0-7 child mask, bit 8 collapsed,
 constexpr int kOccTopShift = 10;              // bits 10-14 the depth of the shallowest collapsed node at or above it, or
 constexpr unsigned kOccNoTop = 31;            // kOccNoTop
@@ -160,6 +162,16 @@ __device__ __forceinline__ void occ_dda_axis(float dir, unsigned key, float orig
   }
 }
 
+// The UNCHECKED coordToKey of computeDiscreteUpdate on one axis (OcTreeBaseImpl.h:357-359): the sum wraps modulo 65536. false
+// where the coordinate is not finite or its floor fits no int, where the reference's cast is undefined.
+__device__ __forceinline__ bool occ_axis_wrapped(double factor, float coord, unsigned* k) {
+#pragma clang fp contract(off)
+  const double f = floor(factor * (double)coord);
+  if (!(f >= -2147483648.0 && f < 2147483648.0)) return false;
+  *k = ((unsigned)(int)f + 32768u) & 0xFFFFu;
+  return true;
+}
+
 // Finds the key's slot or claims an empty one: a walk of at most max_probe slots from the key's hash, a relaxed load of each, a
 // 64-bit compare-and-swap on an empty one. false: no slot. It counts nothing: a caller told `claimed` owes OccCounters::size one.
 __device__ __forceinline__ bool occ_find_or_claim(unsigned long long* keys, unsigned long long key, uint32_t mask, uint32_t max_probe,
@@ -213,6 +225,7 @@ int occ_sort_run(sbm_handle* h, unsigned long long* const kk[2], unsigned* const
 float occ_logodds(double p);   // these three are in sbm_occ_rays.hip
 int occ_ray_params_check(const sbm_occ_ray_params* p);
 int occ_logodds_alloc(sbm_occ_map* map);   // what the log-odds mode keeps beside the table
+bool occ_axis_host(double factor, float coord, unsigned* k);   // occ_axis on the host (sbm_occ_options.hip)
 OccLevel occ_tree_level(const sbm_occ_tree* t, int d);   // these two are in sbm_occ_tree.hip: depth d of a built tree (empty levels for
 int occ_tree_stats(sbm_occ_tree* t);                     // one that is not), and the counts of the last build into t->host, read once
 // The radix sort's second key / payload arrays for n pairs in the handle's sort buffer and, where asked, a first payload array
@@ -293,7 +306,13 @@ struct sbm_occ_map {
   sbm::DevBuf ctr;           // OccCounters
   sbm::DevBuf flags, touched;   // log-odds mode only, from its first insert: per slot the flag word of the running scan, and the
                                 // slots that scan touched (4 B per slot each)
-  template <class F> void each(F f) { f(keys); f(hits); f(ctr); f(flags); f(touched); }
+  // insert options of the log-odds mode (sbm_occ_options.hip); sbm_occ_reset keeps the switches and the box
+  bool use_bbx, detect;         // useBBXLimit, enableChangeDetection
+  float bbx_min[3], bbx_max[3];
+  unsigned bbx_min_key[3], bbx_max_key[3];
+  sbm::DevBuf change;           // from the first enable: one byte of change state per slot
+  sbm::DevBuf dedupe;           // from the first discretised insert: one scan's key set, key list and count
+  template <class F> void each(F f) { f(keys); f(hits); f(ctr); f(flags); f(touched); f(change); f(dedupe); }
 };
 
 struct sbm_occ_tree {

@@ -4,6 +4,13 @@
 //   occ_rays_mark_*_kernel   one lane per ray walks computeRayKeys' 3-D DDA in registers and ORs "free" / "occupied this scan" into the
 //                       flag word of every cell's slot; the lane whose OR found the word clear appends the slot to the touched list.
 //   occ_rays_apply_kernel   gives every touched slot its ONE update (occupied wins) and clears the flags.
+// The insert options (include/sbm.h, "occupancy map: insert options") are template parameters of these kernels: kBox tests
+// every cell against the bounding box before it is marked, kTrack carries "created this scan" from the claiming lane to APPLY,
+// which steps the slot's change state. The <false, false> instantiations are the kernels without options.
+//   occ_dedupe_*_kernel     discretize: one lane per point claims its wrapped key in the scan's scratch set; the claiming lane
+//                       appends the key to a list, from which occ_rays_mark_list_kernel casts one ray per voxel centre.
+#include <type_traits>
+
 #include "sbm_occ.h"
 
 namespace sbm {
@@ -15,6 +22,9 @@ struct OccRay {                 // one call's constants
   float hit, miss, cmin, cmax;  // log-odds
   uint32_t mask, max_probe, slots;
   uint32_t parity;              // which of OccCounters::touched counts this scan
+  float thres;                  // kTrack: isNodeOccupied is logodds >= thres
+  float bmin[3], bmax[3];       // kBox: inBBX(point), in float
+  unsigned kmin[3], kmax[3];    //       inBBX(key)
 };
 struct OccTable {
   unsigned long long* keys;
@@ -22,12 +32,20 @@ struct OccTable {
   unsigned* flags;
   unsigned* touched;
   OccCounters* ctr;
+  uint8_t* change;              // kTrack: a change state per slot
+};
+struct OccDedupe {                // one discretised scan's scratch
+  unsigned long long* set;        // open addressing over `slots` entries (a power of two, at least twice the points)
+  unsigned long long* list;       // the distinct keys, in no order
+  unsigned* count;
+  uint32_t slots, cap;            // entries of the set, of the list (the scan's points)
 };
 
 // The whole wavefront calls this once per step (have: this lane has a cell). Finds or claims the cell's slot and ORs `bit` into
 // its flag word -- after reading it: thousands of rays share their first cells, and a set bit needs no atomic. The lanes whose OR
 // found the word clear append their slots to the scan's touched list, one atomic on the list's counter per wavefront. A cell
 // that finds no slot within the probe bound is counted as overflow.
+template <bool kTrack>
 __device__ __forceinline__ void occ_mark_cell(unsigned long long key, unsigned bit, bool have, const OccRay& g, const OccTable& t) {
   bool fresh = false;
   uint32_t slot = 0;
@@ -36,9 +54,12 @@ __device__ __forceinline__ void occ_mark_cell(unsigned long long key, unsigned b
     const bool found = occ_find_or_claim(t.keys, key, g.mask, g.max_probe, &slot, &claimed);
     if (claimed) atomicAdd(&t.ctr->size, 1u);
     if (found) {
+      // kTrack: the claiming lane brings "created" with its bit. Another lane may have found the key and set its own bit first;
+      // then that lane is the fresh one, and this OR still lands before APPLY.
+      const unsigned bits = kTrack && claimed ? bit | kOccCreated : bit;
       unsigned old = __hip_atomic_load(&t.flags[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (!(old & bit)) {
-        old = atomicOr(&t.flags[slot], bit);
+      if ((old & bits) != bits) {
+        old = atomicOr(&t.flags[slot], bits);
         fresh = old == 0;
       }
     } else {
@@ -51,6 +72,9 @@ __device__ __forceinline__ void occ_mark_cell(unsigned long long key, unsigned b
 
 // One ray of computeUpdate, by the whole wavefront (valid: this lane has a point): the range gate, the truncated end beyond it,
 // computeRayKeys (OcTreeBaseImpl.hxx:542-648) with every cell marked free as the DDA reaches it, and the end point marked occupied.
+// kBox (computeUpdate's second branch, OccupancyOcTreeBase.hxx:222-259): the end point also has to be in the float box, and the
+// first cell outside the key box, the origin's included, ends the ray.
+template <bool kBox, bool kTrack>
 __device__ __forceinline__ void occ_cast_ray(bool valid, Pt3 p, const float* o, const OccRay& g, const OccTable& t) {
 #pragma clang fp contract(off)
   bool walking = false, ends = false;
@@ -77,6 +101,7 @@ __device__ __forceinline__ void occ_cast_ray(bool valid, Pt3 p, const float* o, 
     }
     const bool end_ok = occ_axis(g.factor, end.x, &e0) && occ_axis(g.factor, end.y, &e1) && occ_axis(g.factor, end.z, &e2);
     ends = within && end_ok;
+    if (kBox) ends = ends && p.x >= g.bmin[0] && p.y >= g.bmin[1] && p.z >= g.bmin[2] && p.x <= g.bmax[0] && p.y <= g.bmax[1] && p.z <= g.bmax[2];
     if (end_ok && occ_axis(g.factor, ox, &c0) && occ_axis(g.factor, oy, &c1) && occ_axis(g.factor, oz, &c2) &&
         !(c0 == e0 && c1 == e1 && c2 == e2)) {
       walking = true;
@@ -95,7 +120,9 @@ __device__ __forceinline__ void occ_cast_ray(bool valid, Pt3 p, const float* o, 
   // part of the ray. The step count is bounded whatever the input: the wavefront leaves the loop when its last lane has.
   int steps = 0;
   while (__ballot(walking)) {
-    occ_mark_cell(occ_pack(c0, c1, c2), kOccFree, walking, g, t);
+    if (kBox && walking && !(c0 >= g.kmin[0] && c1 >= g.kmin[1] && c2 >= g.kmin[2] && c0 <= g.kmax[0] && c1 <= g.kmax[1] && c2 <= g.kmax[2]))
+      walking = false;   // the lane stays in the loop's shape: every lane of the wavefront reaches the append below
+    occ_mark_cell<kTrack>(occ_pack(c0, c1, c2), kOccFree, walking, g, t);
     if (walking) {
       const int dim = t0 < t1 ? (t0 < t2 ? 0 : 2) : (t1 < t2 ? 1 : 2);   // the strict < of the reference: ties go to the later axis
       if (dim == 0) {
@@ -111,45 +138,101 @@ __device__ __forceinline__ void occ_cast_ray(bool valid, Pt3 p, const float* o, 
       if ((c0 == e0 && c1 == e1 && c2 == e2) || fmin(fmin(t0, t1), t2) > length || ++steps >= kOccMaxSteps) walking = false;
     }
   }
-  occ_mark_cell(occ_pack(e0, e1, e2), kOccOccupied, ends, g, t);
+  occ_mark_cell<kTrack>(occ_pack(e0, e1, e2), kOccOccupied, ends, g, t);
 }
 
 // mark, cloud form: one lane per point of d_xyz
+template <bool kBox, bool kTrack>
 __global__ void __launch_bounds__(256) occ_rays_mark_cloud_kernel(const float* __restrict__ xyz, size_t n, OccPose origin, OccRay g,
                                                                    OccTable t) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   Pt3 p = nan3();
   if (i < n) p = Pt3{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
   const float o[3] = {origin.t[3], origin.t[7], origin.t[11]};
-  occ_cast_ray(i < n, p, o, g, t);
+  occ_cast_ray<kBox, kTrack>(i < n, p, o, g, t);
 }
 
 // mark, plane form: one lane per pixel of one plane, through the front half of the hit insert; the origin is the pose's translation
+template <bool kBox, bool kTrack>
 __global__ void __launch_bounds__(256) occ_rays_mark_plane_kernel(const int16_t* __restrict__ plane, OccGeom pg, sbm_stereo_model m,
                                                                    OccPose pose, OccRay g, OccTable t) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   Pt3 p = nan3();
   const bool valid = i < pg.W * pg.H && occ_world_point(plane, i, pg, m, pose.t, &p);
   const float o[3] = {pose.t[3], pose.t[7], pose.t[11]};
-  occ_cast_ray(valid, p, o, g, t);
+  occ_cast_ray<kBox, kTrack>(valid, p, o, g, t);
+}
+
+// discretize (computeDiscreteUpdate, OccupancyOcTreeBase.hxx:148-165). The whole wavefront calls this (valid: this lane has a
+// point): the point's wrapped key is claimed in the scan's set, and the lanes that claimed append it to the list. The set has at
+// least twice as many entries as the scan has points and is empty when the scan begins, so the walk over all of it finds a place.
+__device__ __forceinline__ void occ_dedupe_point(bool valid, Pt3 p, double factor, const OccDedupe& d) {
+  bool claimed = false;
+  unsigned k0 = 0, k1 = 0, k2 = 0;
+  if (valid && occ_axis_wrapped(factor, p.x, &k0) && occ_axis_wrapped(factor, p.y, &k1) && occ_axis_wrapped(factor, p.z, &k2)) {
+    uint32_t at;
+    occ_find_or_claim(d.set, occ_pack(k0, k1, k2), d.slots - 1, d.slots, &at, &claimed);
+  }
+  const uint32_t at = occ_wave_append(claimed, d.count);
+  if (claimed && at < d.cap) d.list[at] = occ_pack(k0, k1, k2);
+}
+__global__ void __launch_bounds__(256) occ_dedupe_cloud_kernel(const float* __restrict__ xyz, size_t n, double factor, OccDedupe d) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  Pt3 p = nan3();
+  if (i < n) p = Pt3{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+  occ_dedupe_point(i < n, p, factor, d);
+}
+__global__ void __launch_bounds__(256) occ_dedupe_plane_kernel(const int16_t* __restrict__ plane, OccGeom pg, sbm_stereo_model m,
+                                                                OccPose pose, double factor, OccDedupe d) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  Pt3 p = nan3();
+  const bool valid = i < pg.W * pg.H && occ_world_point(plane, i, pg, m, pose.t, &p);
+  occ_dedupe_point(valid, p, factor, d);
+}
+// mark, list form: one lane per distinct key of a discretised scan, the voxel's centre (keyToCoord) as its point. The grid is
+// sized for the scan's points; the lanes beyond the list's count idle.
+template <bool kBox, bool kTrack>
+__global__ void __launch_bounds__(256) occ_rays_mark_list_kernel(OccDedupe d, OccPose origin, OccRay g, OccTable t) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  const bool valid = i < min(*d.count, d.cap);
+  Pt3 p = nan3();
+  if (valid) {
+    const unsigned long long k = d.list[i];
+    p = Pt3{occ_key_coord((unsigned)(k >> 32) & 0xFFFF, g.resolution), occ_key_coord((unsigned)(k >> 16) & 0xFFFF, g.resolution),
+            occ_key_coord((unsigned)k & 0xFFFF, g.resolution)};
+  }
+  const float o[3] = {origin.t[3], origin.t[7], origin.t[11]};
+  occ_cast_ray<kBox, kTrack>(valid, p, o, g, t);
 }
 
 // apply: every slot the scan touched gets its one update (updateNodeLogOdds, OccupancyOcTreeBase.hxx:1097-1106; an absent voxel
 // starts at 0, which is what a fresh slot holds), occupied before free, and its flag word is cleared for the next scan. The
 // early return of updateNode for a leaf at its clamp gives what the clamp gives. No atomics: a slot is in the list once. The
 // two counts of OccCounters::touched take turns, so that no scan needs a memset between its two launches and the next scan's.
-__global__ void __launch_bounds__(256) occ_rays_apply_kernel(OccRay g, OccTable t) {
+// kTrack (updateNodeRecurs, OccupancyOcTreeBase.hxx:415-427): a slot the scan claimed becomes `created`; another whose
+// isNodeOccupied differs before and after the update goes none -> flipped -> none, and a created one stays.
+template <bool kTrack> __global__ void __launch_bounds__(256) occ_rays_apply_kernel(OccRay g, OccTable t) {
 #pragma clang fp contract(off)
   const uint32_t n = min(t.ctr->touched[g.parity], g.slots);
   if (blockIdx.x == 0 && threadIdx.x == 0) t.ctr->touched[g.parity ^ 1] = 0;   // the next scan's count; nobody reads it now
   for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
     const uint32_t slot = t.touched[i];
     if (slot >= g.slots) continue;
-    float v = t.logodds[slot] + ((t.flags[slot] & kOccOccupied) ? g.hit : g.miss);
+    const unsigned f = t.flags[slot];
+    const float before = t.logodds[slot];
+    float v = before + ((f & kOccOccupied) ? g.hit : g.miss);
     if (v < g.cmin) v = g.cmin;
     else if (v > g.cmax) v = g.cmax;
     t.logodds[slot] = v;
     t.flags[slot] = 0;
+    if (kTrack) {
+      if (f & kOccCreated) {
+        t.change[slot] = kOccChangeCreated;
+      } else if ((before >= g.thres) != (v >= g.thres)) {
+        const uint8_t s = t.change[slot];
+        if (s != kOccChangeCreated) t.change[slot] = s == kOccChangeNone ? kOccChangeFlipped : kOccChangeNone;
+      }
+    }
   }
 }
 
@@ -192,12 +275,48 @@ static int occ_rays_begin(sbm_occ_map* map, const sbm_occ_ray_params* p, OccRay*
   occ_probe(map, &g->mask, &g->max_probe);
   g->slots = map->slots;
   g->parity = 0;
+  g->thres = occ_logodds(p->occupancy_thres);
+  for (int i = 0; i < 3; i++) {
+    g->bmin[i] = map->bbx_min[i], g->bmax[i] = map->bbx_max[i];
+    g->kmin[i] = map->bbx_min_key[i], g->kmax[i] = map->bbx_max_key[i];
+  }
   t->keys = map->keys.as<unsigned long long>();
   t->logodds = map->hits.as<float>();
   t->flags = map->flags.as<unsigned>();
   t->touched = map->touched.as<unsigned>();
   t->ctr = map->ctr.as<OccCounters>();
+  t->change = map->change.as<uint8_t>();
   return SBM_OK;
+}
+
+// f(box, track) with the map's two switches as compile-time constants: which instantiation of a mark or apply kernel runs
+template <class F> static void occ_with_options(const sbm_occ_map* map, F f) {
+  if (map->use_bbx) {
+    if (map->detect) f(std::true_type{}, std::true_type{});
+    else f(std::true_type{}, std::false_type{});
+  } else {
+    if (map->detect) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
+  }
+}
+
+// The scratch of one discretised scan of n points, placed in the map's dedupe buffer: the set, the list and its count
+static int occ_dedupe_begin(sbm_occ_map* map, size_t n, OccDedupe* d) {
+  sbm_handle* h = map->h;
+  d->cap = (uint32_t)n;
+  d->slots = 2;
+  while ((size_t)d->slots < 2 * n) d->slots <<= 1;
+  HIPCHK(h, carve(map->dedupe, h->stream, [&](Carve& c) {
+    d->set = c.take<unsigned long long>(d->slots), d->list = c.take<unsigned long long>(n), d->count = c.take<unsigned>(1);
+  }, occ_pad));
+  return SBM_OK;
+}
+// A discretised scan's first steps, inside the mark stage's time: the set and the count are cleared in stream order, then `dedupe`
+// launches its kernel
+template <class Dedupe> static void occ_dedupe_run(sbm_handle* h, const OccDedupe& d, Dedupe dedupe) {
+  if (hipMemsetAsync(d.set, 0xFF, (size_t)d.slots * 8, h->stream) != hipSuccess) return;   // occ_rays_scan looks at the last error
+  if (hipMemsetAsync(d.count, 0, sizeof(unsigned), h->stream) != hipSuccess) return;
+  dedupe();
 }
 
 // One scan: `mark` launches its mark kernel; the apply launch follows in stream order.
@@ -209,7 +328,10 @@ template <class Mark> static int occ_rays_scan(sbm_occ_map* map, OccRay& g, cons
   mark();
   HIPCHK(h, hipGetLastError());
   HIPCHK(h, clk.mark(kOccMid, h->stream));
-  hipLaunchKernelGGL(occ_rays_apply_kernel, dim3(std::min((map->slots + 255) / 256, 1024u)), dim3(256), 0, h->stream, g, t);
+  occ_with_options(map, [&](auto, auto track) {
+    hipLaunchKernelGGL((occ_rays_apply_kernel<decltype(track)::value>), dim3(std::min((map->slots + 255) / 256, 1024u)), dim3(256), 0,
+                       h->stream, g, t);
+  });
   HIPCHK(h, hipGetLastError());
   map->scan++;
   HIPCHK(h, clk.mark(kOccEnd, h->stream));
@@ -226,7 +348,8 @@ static int occ_check_cloud(const sbm_occ_map* map, size_t n, const void* xyz, co
   return SBM_OK;
 }
 
-static int occ_cloud_run(sbm_occ_map* map, size_t n, const float* d_xyz, const float* origin, const sbm_occ_ray_params* p, int sync) {
+static int occ_cloud_run(sbm_occ_map* map, size_t n, const float* d_xyz, const float* origin, const sbm_occ_ray_params* p, int sync,
+                         bool discrete = false) {
   sbm_handle* h = map->h;
   OccRay g;
   OccTable t;
@@ -237,8 +360,16 @@ static int occ_cloud_run(sbm_occ_map* map, size_t n, const float* d_xyz, const f
     OccPose o;
     memset(&o, 0, sizeof(o));
     o.t[3] = origin[0], o.t[7] = origin[1], o.t[11] = origin[2];
+    const dim3 grid((unsigned)((n + 255) / 256));
+    OccDedupe d;
+    if (discrete && (st = occ_dedupe_begin(map, n, &d)) != SBM_OK) return st;
     st = occ_rays_scan(map, g, t, [&] {
-      hipLaunchKernelGGL(occ_rays_mark_cloud_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, d_xyz, n, o, g, t);
+      if (discrete) occ_dedupe_run(h, d, [&] { hipLaunchKernelGGL(occ_dedupe_cloud_kernel, grid, dim3(256), 0, h->stream, d_xyz, n, g.factor, d); });
+      occ_with_options(map, [&](auto box, auto track) {
+        constexpr bool kBox = decltype(box)::value, kTrack = decltype(track)::value;
+        if (discrete) hipLaunchKernelGGL((occ_rays_mark_list_kernel<kBox, kTrack>), grid, dim3(256), 0, h->stream, d, o, g, t);
+        else hipLaunchKernelGGL((occ_rays_mark_cloud_kernel<kBox, kTrack>), grid, dim3(256), 0, h->stream, d_xyz, n, o, g, t);
+      });
     });
     if (st != SBM_OK) return st;
   }
@@ -246,7 +377,7 @@ static int occ_cloud_run(sbm_occ_map* map, size_t n, const float* d_xyz, const f
 }
 
 static int occ_planes_run(sbm_occ_map* map, int n, const int16_t* d_disp, int W, int H, int scale, const sbm_stereo_model* model,
-                          const float* poses, const sbm_occ_ray_params* p, int sync) {
+                          const float* poses, const sbm_occ_ray_params* p, int sync, bool discrete = false) {
   sbm_handle* h = map->h;
   OccRay g;
   OccTable t;
@@ -262,9 +393,19 @@ static int occ_planes_run(sbm_occ_map* map, int n, const int16_t* d_disp, int W,
   for (int i = 0; i < n; i++) {   // plane i is scan i: its launches follow those of plane i - 1 in stream order
     OccPose pose;
     memcpy(pose.t, poses + (size_t)12 * i, sizeof(pose.t));
+    const dim3 grid((unsigned)((plane + 255) / 256));
+    OccDedupe d;
+    if (discrete && (st = occ_dedupe_begin(map, plane, &d)) != SBM_OK) return st;
     st = occ_rays_scan(map, g, t, [&] {
-      hipLaunchKernelGGL(occ_rays_mark_plane_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, h->stream, d_disp + plane * i,
-                         pg, *model, pose, g, t);
+      if (discrete)
+        occ_dedupe_run(h, d, [&] {
+          hipLaunchKernelGGL(occ_dedupe_plane_kernel, grid, dim3(256), 0, h->stream, d_disp + plane * i, pg, *model, pose, g.factor, d);
+        });
+      occ_with_options(map, [&](auto box, auto track) {
+        constexpr bool kBox = decltype(box)::value, kTrack = decltype(track)::value;
+        if (discrete) hipLaunchKernelGGL((occ_rays_mark_list_kernel<kBox, kTrack>), grid, dim3(256), 0, h->stream, d, pose, g, t);
+        else hipLaunchKernelGGL((occ_rays_mark_plane_kernel<kBox, kTrack>), grid, dim3(256), 0, h->stream, d_disp + plane * i, pg, *model, pose, g, t);
+      });
     });
     if (st != SBM_OK) return st;
   }
@@ -296,17 +437,18 @@ int sbm_occ_ray_logodds(const sbm_occ_ray_params* p, float logodds[5]) {
   return SBM_OK;
 }
 
-int sbm_occ_insert_cloud_device(sbm_occ_map* map, size_t n_points, const void* d_xyz, const float* origin,
-                                const sbm_occ_ray_params* params, int sync) {
+static int occ_insert_cloud_device(sbm_occ_map* map, size_t n_points, const void* d_xyz, const float* origin,
+                                   const sbm_occ_ray_params* params, int sync, bool discrete) {
   const int st = occ_check_cloud(map, n_points, d_xyz, origin, params);
   if (st != SBM_OK) return st;
   if ((uintptr_t)d_xyz & 3) return SBM_ERR_UNSUPPORTED;
   DeviceScope dscope(map->h->device);
   HIPCHK(map->h, dscope.enter());
-  return occ_cloud_run(map, n_points, (const float*)d_xyz, origin, params, sync);
+  return occ_cloud_run(map, n_points, (const float*)d_xyz, origin, params, sync, discrete);
 }
 
-int sbm_occ_insert_cloud(sbm_occ_map* map, size_t n_points, const float* xyz, const float* origin, const sbm_occ_ray_params* params) {
+static int occ_insert_cloud_host(sbm_occ_map* map, size_t n_points, const float* xyz, const float* origin, const sbm_occ_ray_params* params,
+                                 bool discrete) {
   const int st = occ_check_cloud(map, n_points, xyz, origin, params);
   if (st != SBM_OK) return st;
   if (map->mode == kOccModeHits) return SBM_ERR_UNSUPPORTED;
@@ -317,22 +459,22 @@ int sbm_occ_insert_cloud(sbm_occ_map* map, size_t n_points, const float* xyz, co
     HIPCHK(h, h->occ.io.grow(n_points * 12, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->occ.io.p, xyz, n_points * 12, hipMemcpyHostToDevice, h->stream));
   }
-  return occ_cloud_run(map, n_points, h->occ.io.as<float>(), origin, params, 1);
+  return occ_cloud_run(map, n_points, h->occ.io.as<float>(), origin, params, 1, discrete);
 }
 
-int sbm_occ_insert_rays_device(sbm_occ_map* map, int n, const void* d_disp, int width, int height, int scale,
-                               const sbm_stereo_model* model, const float* poses, const sbm_occ_ray_params* params, int sync) {
+static int occ_insert_rays_device(sbm_occ_map* map, int n, const void* d_disp, int width, int height, int scale,
+                                  const sbm_stereo_model* model, const float* poses, const sbm_occ_ray_params* params, int sync, bool discrete) {
   int st = occ_check_insert(map, n, d_disp, width, height, scale, model, poses);
   if (st == SBM_OK) st = occ_ray_params_check(params);
   if (st != SBM_OK) return st;
   if ((uintptr_t)d_disp & 1) return SBM_ERR_UNSUPPORTED;
   DeviceScope dscope(map->h->device);
   HIPCHK(map->h, dscope.enter());
-  return occ_planes_run(map, n, (const int16_t*)d_disp, width, height, scale, model, poses, params, sync);
+  return occ_planes_run(map, n, (const int16_t*)d_disp, width, height, scale, model, poses, params, sync, discrete);
 }
 
-int sbm_occ_insert_rays(sbm_occ_map* map, int n, const int16_t* disp, int width, int height, int scale, const sbm_stereo_model* model,
-                        const float* poses, const sbm_occ_ray_params* params) {
+static int occ_insert_rays_host(sbm_occ_map* map, int n, const int16_t* disp, int width, int height, int scale, const sbm_stereo_model* model,
+                                const float* poses, const sbm_occ_ray_params* params, bool discrete) {
   int st = occ_check_insert(map, n, disp, width, height, scale, model, poses);
   if (st == SBM_OK) st = occ_ray_params_check(params);
   if (st != SBM_OK) return st;
@@ -343,6 +485,38 @@ int sbm_occ_insert_rays(sbm_occ_map* map, int n, const int16_t* disp, int width,
   const size_t bytes = (size_t)n * width * height * sizeof(int16_t);
   HIPCHK(h, h->occ.io.grow(bytes, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->occ.io.p, disp, bytes, hipMemcpyHostToDevice, h->stream));
-  return occ_planes_run(map, n, h->occ.io.as<int16_t>(), width, height, scale, model, poses, params, 1);
+  return occ_planes_run(map, n, h->occ.io.as<int16_t>(), width, height, scale, model, poses, params, 1, discrete);
+}
+
+int sbm_occ_insert_cloud_device(sbm_occ_map* map, size_t n_points, const void* d_xyz, const float* origin,
+                                const sbm_occ_ray_params* params, int sync) {
+  return occ_insert_cloud_device(map, n_points, d_xyz, origin, params, sync, false);
+}
+int sbm_occ_insert_cloud(sbm_occ_map* map, size_t n_points, const float* xyz, const float* origin, const sbm_occ_ray_params* params) {
+  return occ_insert_cloud_host(map, n_points, xyz, origin, params, false);
+}
+int sbm_occ_insert_rays_device(sbm_occ_map* map, int n, const void* d_disp, int width, int height, int scale,
+                               const sbm_stereo_model* model, const float* poses, const sbm_occ_ray_params* params, int sync) {
+  return occ_insert_rays_device(map, n, d_disp, width, height, scale, model, poses, params, sync, false);
+}
+int sbm_occ_insert_rays(sbm_occ_map* map, int n, const int16_t* disp, int width, int height, int scale, const sbm_stereo_model* model,
+                        const float* poses, const sbm_occ_ray_params* params) {
+  return occ_insert_rays_host(map, n, disp, width, height, scale, model, poses, params, false);
+}
+int sbm_occ_insert_cloud_discrete_device(sbm_occ_map* map, size_t n_points, const void* d_xyz, const float* origin,
+                                         const sbm_occ_ray_params* params, int sync) {
+  return occ_insert_cloud_device(map, n_points, d_xyz, origin, params, sync, true);
+}
+int sbm_occ_insert_cloud_discrete(sbm_occ_map* map, size_t n_points, const float* xyz, const float* origin,
+                                  const sbm_occ_ray_params* params) {
+  return occ_insert_cloud_host(map, n_points, xyz, origin, params, true);
+}
+int sbm_occ_insert_rays_discrete_device(sbm_occ_map* map, int n, const void* d_disp, int width, int height, int scale,
+                                        const sbm_stereo_model* model, const float* poses, const sbm_occ_ray_params* params, int sync) {
+  return occ_insert_rays_device(map, n, d_disp, width, height, scale, model, poses, params, sync, true);
+}
+int sbm_occ_insert_rays_discrete(sbm_occ_map* map, int n, const int16_t* disp, int width, int height, int scale,
+                                 const sbm_stereo_model* model, const float* poses, const sbm_occ_ray_params* params) {
+  return occ_insert_rays_host(map, n, disp, width, height, scale, model, poses, params, true);
 }
 }  // extern "C"

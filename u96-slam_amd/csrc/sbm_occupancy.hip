@@ -143,6 +143,7 @@ int occ_clear(sbm_occ_map* map) {
   HIPCHK(h, hipMemsetAsync(map->hits.p, 0, (size_t)map->slots * 4, h->stream));
   HIPCHK(h, hipMemsetAsync(map->ctr.p, 0, sizeof(OccCounters), h->stream));
   if (map->flags.p) HIPCHK(h, hipMemsetAsync(map->flags.p, 0, (size_t)map->slots * 4, h->stream));
+  if (map->change.p) HIPCHK(h, hipMemsetAsync(map->change.p, 0, map->slots, h->stream));   // the switches and the box stay
   map->mode = kOccModeNone;
   map->scan = 0;
   return SBM_OK;
@@ -324,6 +325,7 @@ int sbm_occ_create(sbm_handle* h, const sbm_occ_params* p, size_t capacity, sbm_
   map->capacity = capacity;
   map->slots = 2;
   while ((size_t)map->slots < 2 * capacity) map->slots <<= 1;
+  for (int i = 0; i < 3; i++) map->bbx_min_key[i] = map->bbx_max_key[i] = 32768;   // the keys of the box's two points, (0, 0, 0)
   DeviceScope dscope(h->device);
   hipError_t e = dscope.enter();
   if (e == hipSuccess) e = map->keys.grow((size_t)map->slots * 8, h->stream);
@@ -364,7 +366,7 @@ int sbm_occ_insert_device(sbm_occ_map* map, int n, const void* d_disp, int width
                           const sbm_stereo_model* model, const float* poses, int sync) {
   const int st = occ_check_insert(map, n, d_disp, width, height, scale, model, poses);
   if (st != SBM_OK) return st;
-  if ((uintptr_t)d_disp & 1 || map->mode == kOccModeLogOdds) return SBM_ERR_UNSUPPORTED;
+  if ((uintptr_t)d_disp & 1 || map->mode == kOccModeLogOdds || map->use_bbx || map->detect) return SBM_ERR_UNSUPPORTED;
   DeviceScope dscope(map->h->device);
   HIPCHK(map->h, dscope.enter());
   map->mode = kOccModeHits;
@@ -375,7 +377,7 @@ int sbm_occ_insert(sbm_occ_map* map, int n, const int16_t* disp, int width, int 
                    const float* poses) {
   const int st = occ_check_insert(map, n, disp, width, height, scale, model, poses);
   if (st != SBM_OK) return st;
-  if (map->mode == kOccModeLogOdds) return SBM_ERR_UNSUPPORTED;
+  if (map->mode == kOccModeLogOdds || map->use_bbx || map->detect) return SBM_ERR_UNSUPPORTED;
   sbm_handle* h = map->h;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
