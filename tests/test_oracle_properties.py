@@ -4,6 +4,8 @@ import numpy as np
 import pytest
 from scipy import ndimage
 
+from postfilter_cases import np_speckles, np_validate
+
 
 def rand_pair(rng, h, w, shift=5, noise=3):
     base = rng.integers(0, 256, (h, w + 64), dtype=np.uint8)
@@ -107,34 +109,6 @@ def test_range_does_not_fit_and_status_codes(oracle):
         assert oracle.compute_status(oracle.make_params(**args), 40, 32) == code, kw
 
 
-def np_validate(disp, cost, mind, nd, tol_px):
-    """Independent numpy restatement of SURVEY.md Appendix A.5."""
-    disp = disp.copy()
-    h, w = disp.shape
-    inv = (mind - 1) * 16
-    for y in range(h):
-        d2 = np.full(w, inv, np.int64)
-        c2 = np.full(w, np.iinfo(np.int64).max, np.int64)
-        row = disp[y].astype(np.int64)
-        for x in range(max(mind + nd, 0), w + min(mind, 0)):
-            d = row[x]
-            if d == inv:
-                continue
-            x2 = x - ((d + 8) >> 4)
-            if c2[x2] > cost[y, x]:
-                c2[x2], d2[x2] = cost[y, x], d
-        for x in range(max(mind + nd, 0), w + min(mind, 0)):
-            d = row[x]
-            if d == inv:
-                continue
-            bad = []
-            for xx in (x - (d >> 4), x - ((d + 15) >> 4)):
-                bad.append(0 <= xx < w and d2[xx] > inv and abs(d2[xx] - d) > tol_px * 16)
-            if all(bad):
-                disp[y, x] = inv
-    return disp
-
-
 def test_validate_disparity_matches_numpy(oracle):
     rng = np.random.default_rng(5)
     h, w, nd = 12, 90, 32
@@ -171,31 +145,6 @@ def test_lr_claim_key_with_the_disparity_picks_cv_winner():
                 by_key = c[np.argmin(key)]
                 assert by_x == by_key
                 assert ((int(key.min()) & 0xffff) - 0x8000) == d[by_x]   # and the key carries the winner's disparity
-
-
-def np_speckles(img, new_val, max_size, max_diff):
-    """Independent restatement of Appendix A.6 as plain connected components (graph edges between
-    4-neighbours that are both valid and within max_diff), via scipy.sparse.csgraph."""
-    from scipy.sparse import coo_matrix
-    from scipy.sparse.csgraph import connected_components
-
-    h, w = img.shape
-    v = img.astype(np.int64)
-    valid = v != new_val
-    idx = np.arange(h * w).reshape(h, w)
-    rows, cols = [], []
-    m = valid[:, :-1] & valid[:, 1:] & (np.abs(v[:, :-1] - v[:, 1:]) <= max_diff)
-    rows.append(idx[:, :-1][m]); cols.append(idx[:, 1:][m])
-    m = valid[:-1] & valid[1:] & (np.abs(v[:-1] - v[1:]) <= max_diff)
-    rows.append(idx[:-1][m]); cols.append(idx[1:][m])
-    r, c = np.concatenate(rows), np.concatenate(cols)
-    g = coo_matrix((np.ones(r.size), (r, c)), shape=(h * w, h * w))
-    _, lab = connected_components(g, directed=False)
-    sizes = np.bincount(lab)
-    out = img.copy()
-    kill = valid.ravel() & (sizes[lab] <= max_size)
-    out.ravel()[kill] = new_val
-    return out
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])

@@ -279,6 +279,7 @@ def load_library():
     L.sbm_wait_oldest.argtypes = [vp]
     L.sbm_compute_batch_multi.argtypes = [ctypes.POINTER(vp), ci, ci, vp, vp, ci, ci, vp]
     L.sbm_debug_fetch.argtypes = [vp, ci, vp, sz]
+    L.sbm_debug_postfilter.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, vp, sz]   # for the tests: not in include/sbm.h
     L.sbm_set_profiling.argtypes = [vp, ci]
     L.sbm_get_profile.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_float)]
     L.sbm_last_kernel_name.argtypes = [vp, ctypes.c_char_p, sz]

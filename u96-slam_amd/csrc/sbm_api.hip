@@ -407,6 +407,19 @@ static void collect_profile(sbm_handle* h) {
   h->bm.clock.ms[kBmTotal] = tot * inv;
 }
 
+// The tail of a call, behind the SAD kernels: LR check + valid-ROI fill from disp_pre / cost into out (stages & 1), then the
+// speckle filter on out where the plan has one (stages & 2). sbm_compute_device runs both; sbm_debug_postfilter runs the same
+// code on a caller's map.
+static int post_filters(sbm_handle* h, const BmPlan& pl, const int16_t* disp_pre, const int32_t* cost, int16_t* out, int stages) {
+  const sbm_params& p = h->p;
+  if (stages & 1) {
+    HIPCHK(h, launch_lrcheck(disp_pre, cost, out, h->bm.lr_keys.as<unsigned long long>(), pl.g, p.disp12_max_diff, h->stream));
+    mark(h, kBmChecked);
+  }
+  if ((stages & 2) && pl.speckle) HIPCHK(h, launch_speckle(out, h->bm.spk, pl.g, pl.spk, p.speckle_window_size, h->stream));
+  return SBM_OK;
+}
+
 int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_right, int width, int height,
                        void* d_disp, int sync) {
   if (!h || !d_left || !d_right || !d_disp) return SBM_ERR_NULL;
@@ -469,9 +482,8 @@ int sbm_compute_device(sbm_handle* h, int n, const void* d_left, const void* d_r
     HIPCHK(h, launch_sad_generic(pf_l, pf_r, disp_pre, cost, g, 0, g.xend, h->stream));
   }
   mark(h, kBmMatched);
-  HIPCHK(h, launch_lrcheck(disp_pre, cost, out, h->bm.lr_keys.as<unsigned long long>(), g, p.disp12_max_diff, h->stream));
-  mark(h, kBmChecked);
-  if (pl.speckle) HIPCHK(h, launch_speckle(out, h->bm.spk, g, pl.spk, p.speckle_window_size, h->stream));
+  const int st3 = post_filters(h, pl, disp_pre, cost, out, 3);
+  if (st3 != SBM_OK) return st3;
   mark(h, kBmEnd);
   if (h->instr) h->calls++;
   h->ncall++;
@@ -514,6 +526,106 @@ int sbm_debug_fold(const sbm_params* p, int n, int width, int height, int inplac
   const int st = bm_plan(*p, n, width, height, inplace_ok != 0, &pl);
   if (st != SBM_OK) return st;
   out[0] = sad_fast_fold_cols(pl);
+  return SBM_OK;
+}
+
+// The post-filters of sbm_compute_device on a caller's map: the call is planned as sbm_compute_device plans it for the handle's
+// parameters and n maps of width x height (same environment switches, same self-test, same scratch), the prefilter and the SAD
+// kernels are skipped, disp_pre / cost (host, n * height * width each) take the place of what they would have left in the handle's
+// planes, and post_filters() runs: stages 1 = LR check + valid-ROI fill, 2 = speckle filter, 3 = both; disp (host) receives the
+// map. With stages == 2 the map goes to the filter as it is and every pixel of it counts (no ROI fill); the handle's parameters
+// must switch the filter on, and the block size is not held against the image then (the filter reads no window), so maps of
+// fewer rows than the smallest block can be filtered.
+// The input must be what the SAD kernels produce (SBM_ERR_UNSUPPORTED otherwise; lrcheck16_kernel's inner wavefronts test no range):
+// a pixel is (minDisparity - 1) * 16 or within [minDisparity * 16, (minDisparity + numDisparities - 1) * 16]; costs are
+// non-negative, and where the plan's cost plane is 16 bits (Geom::cost16) at most 65534 at valid pixels -- the int32 costs are
+// narrowed and every filtered pixel gets 0xffff, as the SAD kernels store it. cost may be null when nothing reads it (stages == 2,
+// disp12MaxDiff < 0).
+// info (info_count >= kPostInfoCount int32) says what ran: [0] stages, [1] LrKernel or -1, [2] nit, [3] px, [4] block size, [5] cost16,
+// [6] the speckle filter ran, [7] SpkPlan::lists, [8] G, [9] S, [10] SW, [11] max_diff, [12..15] row0, row1, col0, col1 of the valid
+// ROI, [16] lofs, [17] xend. As sbm_debug_plan: for the tests, not part of the public header.
+constexpr size_t kPostInfoCount = 18;
+int sbm_debug_postfilter(sbm_handle* h, int n, int width, int height, const int16_t* disp_pre, const int32_t* cost, int stages,
+                         int16_t* disp, int32_t* info, size_t info_count) {
+  if (!disp_pre || !disp || !info) return SBM_ERR_NULL;
+  if (n <= 0) return SBM_ERR_BATCH;
+  if (width <= 0 || height <= 0) return SBM_ERR_SIZE;
+  if (info_count < kPostInfoCount) return SBM_ERR_SIZE;
+  if (stages < 1 || stages > 3) return SBM_ERR_UNSUPPORTED;
+  if (!h) return SBM_ERR_NULL;   // (last of the argument checks: the others can be tested without a device)
+  const sbm_params& p = h->p;
+  BmPlan pl;
+  int st = bm_plan_geom(p, n, width, height, &pl);
+  if (st == SBM_ERR_BLOCK_SIZE && stages == 2 && n <= 32767 && height <= 65535) {
+    sbm_params q = p;
+    q.block_size = 5;
+    if (sbm_params_validate(&q, 64, 64) == SBM_OK && p.num_disparities <= 4096) {   // nothing but the block against the image
+      memset(&pl, 0, sizeof(pl));
+      pl.g.W = width; pl.g.H = height; pl.g.n = n;
+      pl.g.nd = p.num_disparities; pl.g.mindisp = p.min_disparity; pl.g.filtered = (p.min_disparity - 1) * 16;
+      pl.g.reading = env_switch("SBM_CV_READING", 0);
+      st = SBM_OK;
+    }
+  }
+  if (st != SBM_OK) return st;
+  const bool lr_reads_cost = (stages & 1) && p.disp12_max_diff >= 0;
+  if (lr_reads_cost && !cost) return SBM_ERR_NULL;
+  if (stages == 2 && !(p.speckle_range >= 0 && p.speckle_window_size > 0)) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  bool inplace = false;
+  if (pl.in_envelope) HIPCHK(h, mqsad_inplace_ok(h->stream, &inplace));
+  bm_plan_launches(p, inplace, &pl);
+  const Geom& g = pl.g;
+
+  // the input contract, and the cost plane as the plan's SAD kernels would have stored it
+  const size_t npix = (size_t)n * width * height;
+  const int lo = g.mindisp * 16, hi = (g.mindisp + g.nd - 1) * 16;
+  for (size_t i = 0; i < npix; i++)
+    if (disp_pre[i] != g.filtered && (disp_pre[i] < lo || disp_pre[i] > hi)) return SBM_ERR_UNSUPPORTED;
+  uint16_t* c16 = nullptr;
+  if (lr_reads_cost) {
+    for (size_t i = 0; i < npix; i++)
+      if (cost[i] < 0 || (g.cost16 && disp_pre[i] != g.filtered && cost[i] > 65534)) return SBM_ERR_UNSUPPORTED;
+    if (g.cost16) {
+      c16 = (uint16_t*)malloc(npix * sizeof(uint16_t));
+      if (!c16) return SBM_ERR_NOMEM;
+      for (size_t i = 0; i < npix; i++) c16[i] = disp_pre[i] == g.filtered ? (uint16_t)0xffff : (uint16_t)cost[i];
+    }
+  }
+  struct Tmp {   // the narrowed plane and the device map, whichever way the entry is left
+    uint16_t* c16;
+    void* out = nullptr;
+    ~Tmp() { free(c16); if (out) hipFree(out); }
+  } tmp{c16};
+
+  size_t ho_flags = 0;
+  const size_t ho_bytes = sad_fast_handoff_bytes(pl, &ho_flags);
+  st = ensure_scratch(h, n, width, height, g.pitch, g.want_cost, pl.speckle, ho_bytes, ho_flags);
+  if (st != SBM_OK) return st;
+  h->have_last = false;   // the planes no longer hold a call's stages
+  h->instr = false;       // and this is no call for the stage clock
+  HIPCHK(h, hipMalloc(&tmp.out, npix * sizeof(int16_t)));
+  int16_t* out = (int16_t*)tmp.out;
+  if (stages & 1) {
+    HIPCHK(h, hipMemcpyAsync(h->bm.disp_pre.p, disp_pre, npix * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+    if (lr_reads_cost)
+      HIPCHK(h, hipMemcpyAsync(h->bm.cost.p, g.cost16 ? (const void*)c16 : (const void*)cost,
+                               npix * (g.cost16 ? sizeof(uint16_t) : sizeof(int32_t)), hipMemcpyHostToDevice, h->stream));
+  } else {
+    HIPCHK(h, hipMemcpyAsync(out, disp_pre, npix * sizeof(int16_t), hipMemcpyHostToDevice, h->stream));
+  }
+  st = post_filters(h, pl, h->bm.disp_pre.as<int16_t>(), h->bm.cost.as<int32_t>(), out, stages);
+  if (st != SBM_OK) return st;
+  HIPCHK(h, hipMemcpyAsync(disp, out, npix * sizeof(int16_t), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+
+  const LrChoice lc = lr_choice(g, p.disp12_max_diff);
+  const bool lr = (stages & 1) != 0, spk = (stages & 2) && pl.speckle;
+  const int32_t rep[kPostInfoCount] = {stages, lr ? lc.kernel : -1, lr ? lc.nit : 0, lr ? lc.px : 0, lr ? lc.bs : 0, g.cost16,
+                                       spk, spk ? pl.spk.lists : 0, spk ? pl.spk.G : 0, spk ? pl.spk.S : 0, spk ? pl.spk.SW : 0,
+                                       spk ? pl.spk.max_diff : 0, g.row0, g.row1, g.col0, g.col1, g.lofs, g.xend};
+  memcpy(info, rep, sizeof(rep));
   return SBM_OK;
 }
 

@@ -155,6 +155,11 @@ inline size_t lr_keys_bytes(int n, int W, int H, bool do_lr) {
 }
 hipError_t launch_lrcheck(const int16_t* disp_pre, const int32_t* cost, int16_t* disp_out, unsigned long long* keys,
                           const Geom& g, int disp12_max_diff, hipStream_t s);
+// The kernel launch_lrcheck picks (host only; sbm_debug_postfilter reports it): the fill alone when the check is off, lrcheck16_kernel
+// <nit, px> in blocks of bs threads, or the generic kernel with its claim table in LDS or in global memory (nit, px, bs are 0 then).
+enum LrKernel { kLrCopy = 0, kLrFast16 = 1, kLrGenericLds = 2, kLrGenericGlobal = 3 };
+struct LrChoice { int kernel, nit, px, bs; };
+LrChoice lr_choice(const Geom& g, int disp12_max_diff);
 
 // Speckle filter: launch_speckle and its scratch are in sbm_handle.h.
 constexpr int kSpkMaxSeg = 4, kSpkRecordPad = 288, kSpkSeamPad = 512;

@@ -258,20 +258,13 @@ __global__ void __launch_bounds__(320) lrcheck16_kernel(LrArgs a) {
   }
 }
 
-hipError_t launch_lrcheck(const int16_t* disp_pre, const int32_t* cost, int16_t* disp_out, unsigned long long* keys,
-                          const Geom& g, int disp12_max_diff, hipStream_t s) {
-  LrArgs a;
-  a.keys = keys;
-  a.disp_pre = disp_pre; a.cost = cost; a.disp_out = disp_out; a.cost16 = g.cost16;
-  a.W = g.W; a.H = g.H; a.mindisp = g.mindisp; a.nd = g.nd; a.tol = disp12_max_diff * 16; a.filtered = g.filtered;
-  a.row0 = g.row0; a.row1 = g.row1; a.col0 = g.col0; a.col1 = g.col1; a.do_lr = disp12_max_diff >= 0;
-  a.cx0 = g.lofs; a.cx1 = g.lofs + g.xend;
-  a.cost_short = (g.reading & kReadCostShort) != 0; a.tie_later = (g.reading & kReadLrTieLater) != 0;
+LrChoice lr_choice(const Geom& g, int disp12_max_diff) {
+  LrChoice c = {kLrCopy, 0, 0, 0};
+  if (disp12_max_diff < 0) return c;
+  const bool cost_short = (g.reading & kReadCostShort) != 0, tie_later = (g.reading & kReadLrTieLater) != 0;
   // (the 16-bit verdict of lrcheck16_kernel: disparities of one map less than 16384 apart, tolerance clamped to that -- a larger
   // one passes everything either way)
-  if (a.do_lr && g.cost16 && g.W <= 4096 && (g.nd + 1) * 16 <= 16384 && !a.cost_short && !a.tie_later) {
-    a.tol = std::min(a.tol, 16384);
-    const size_t lds16 = (size_t)(g.W + 3 + 64 + 8) * sizeof(unsigned);   // claims, pads, per-lane dummy slots
+  if (g.cost16 && g.W <= 4096 && (g.nd + 1) * 16 <= 16384 && !cost_short && !tie_later) {
     // PX pixels per thread and iteration, blocks of at most BSMAX threads, the fewest iterations that cover the row with them and
     // then the narrowest block (a multiple of 64) that does. Measured (profiles/r04_lr_sweep.txt): what counts is how few idle
     // pixel slots the cover leaves and, for rows up to ~1300 columns, few wavefronts per row -- 2 pixels x 5 iterations x one
@@ -281,23 +274,39 @@ hipError_t launch_lrcheck(const int16_t* disp_pre, const int32_t* cost, int16_t*
     const int groups = (g.W + px - 1) / px;
     const int nit = (groups + bsmax - 1) / bsmax;
     const int bs = (((groups + nit - 1) / nit + 63) / 64) * 64;
-    const dim3 grid(g.H, g.n), block(bs);
-    bool launched = true;
+    // the instantiations launch_lrcheck has: up to 1280 columns, and 1281 .. 4096 (no such instantiation: the generic kernel)
+    if (px == 2 ? (nit >= 1 && nit <= 5) : (nit >= 2 && nit <= 4)) return LrChoice{kLrFast16, nit, px, bs};
+  }
+  c.kernel = g.W > kLrLdsCols ? kLrGenericGlobal : kLrGenericLds;
+  return c;
+}
+
+hipError_t launch_lrcheck(const int16_t* disp_pre, const int32_t* cost, int16_t* disp_out, unsigned long long* keys,
+                          const Geom& g, int disp12_max_diff, hipStream_t s) {
+  LrArgs a;
+  a.keys = keys;
+  a.disp_pre = disp_pre; a.cost = cost; a.disp_out = disp_out; a.cost16 = g.cost16;
+  a.W = g.W; a.H = g.H; a.mindisp = g.mindisp; a.nd = g.nd; a.tol = disp12_max_diff * 16; a.filtered = g.filtered;
+  a.row0 = g.row0; a.row1 = g.row1; a.col0 = g.col0; a.col1 = g.col1; a.do_lr = disp12_max_diff >= 0;
+  a.cx0 = g.lofs; a.cx1 = g.lofs + g.xend;
+  a.cost_short = (g.reading & kReadCostShort) != 0; a.tie_later = (g.reading & kReadLrTieLater) != 0;
+  const LrChoice c = lr_choice(g, disp12_max_diff);
+  if (c.kernel == kLrFast16) {
+    a.tol = std::min(a.tol, 16384);
+    const size_t lds16 = (size_t)(g.W + 3 + 64 + 8) * sizeof(unsigned);   // claims, pads, per-lane dummy slots
+    const dim3 grid(g.H, g.n), block(c.bs);
 #define SBM_LR_CASE(N, P) case N * 8 + P: hipLaunchKernelGGL((lrcheck16_kernel<N, P>), grid, block, lds16, s, a); break;
-    switch (nit * 8 + px) {
+    switch (c.nit * 8 + c.px) {
       SBM_LR_CASE(1, 2) SBM_LR_CASE(2, 2) SBM_LR_CASE(3, 2) SBM_LR_CASE(4, 2) SBM_LR_CASE(5, 2)   // up to 1280 columns
       SBM_LR_CASE(2, 4) SBM_LR_CASE(3, 4) SBM_LR_CASE(4, 4)                                       // 1281 .. 4096 columns
-      default: launched = false;
+      default: return hipErrorInvalidValue;   // (lr_choice names these eight only)
     }
 #undef SBM_LR_CASE
-    if (launched) return hipGetLastError();
-    a.tol = disp12_max_diff * 16;   // (no such instantiation: the generic kernel below)
-  }
-  if (a.do_lr && g.W > kLrLdsCols) {
+  } else if (c.kernel == kLrGenericGlobal) {
     if (!keys) return hipErrorInvalidValue;   // (the caller sizes the table with lr_keys_bytes)
     hipLaunchKernelGGL(lrcheck_kernel<true>, dim3(g.H, g.n), dim3(256), 0, s, a);
   } else {
-    const size_t lds = a.do_lr ? (size_t)g.W * sizeof(unsigned long long) : 0;
+    const size_t lds = c.kernel == kLrGenericLds ? (size_t)g.W * sizeof(unsigned long long) : 0;
     hipLaunchKernelGGL(lrcheck_kernel<false>, dim3(g.H, g.n), dim3(256), lds, s, a);
   }
   return hipGetLastError();

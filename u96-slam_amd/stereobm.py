@@ -182,6 +182,30 @@ class StereoBM(_engine.Engine, _frontend.FrontEnd, _fpga.FpgaMatcher, _gftt.Gftt
         _check(self._L.sbm_debug_fetch(self._h, which, a.ctypes.data, a.nbytes), self._h)
         return a
 
+    POSTFILTER_INFO = ("stages", "lr_kernel", "nit", "px", "bs", "cost16", "speckle", "lists", "G", "S", "SW", "max_diff",
+                       "row0", "row1", "col0", "col1", "lofs", "xend")
+    LR_COPY, LR_FAST16, LR_GENERIC_LDS, LR_GENERIC_GLOBAL = 0, 1, 2, 3
+
+    def debug_postfilter(self, pre, cost=None, stages=3):
+        """sbm_debug_postfilter (for the tests): this matcher's post-filters on the caller's (n,H,W) or (H,W) int16 map and int32
+        costs (None where nothing reads them), planned as compute() plans them. stages: 1 = LR check + valid-ROI fill,
+        2 = speckle filter on the whole map, 3 = both. Returns (map, info) with info a dict over POSTFILTER_INFO."""
+        pre = np.ascontiguousarray(pre, np.int16)
+        single = pre.ndim == 2
+        p3 = pre[None] if single else pre
+        if p3.ndim != 3:
+            raise StereoBMError(-2, "expected an (H,W) or (n,H,W) map")
+        if cost is not None:
+            cost = np.ascontiguousarray(cost, np.int32)
+            if cost.size != p3.size:
+                raise StereoBMError(-2, "the cost plane must have the map's size")
+        n, h, w = p3.shape
+        out = np.empty_like(p3)
+        info = np.zeros(len(self.POSTFILTER_INFO), np.int32)
+        _check(self._L.sbm_debug_postfilter(self._h, n, w, h, p3.ctypes.data, None if cost is None else cost.ctypes.data, int(stages),
+                                            out.ctypes.data, info.ctypes.data, info.size), self._h)
+        return (out[0] if single else out), dict(zip(self.POSTFILTER_INFO, info.tolist()))
+
 
 def compute_multi(engines, left, right, disparity):
     """sbm_compute_batch_multi: one dense (n,H,W) uint8 host batch over several StereoBM engines (normally one per GPU),
