@@ -1602,6 +1602,74 @@ int sbm_occ_insert_rays_discrete_device(sbm_occ_map* map, int n, const void* d_d
 int sbm_occ_insert_rays_discrete(sbm_occ_map* map, int n, const int16_t* disp, int width, int height, int scale,
                                  const sbm_stereo_model* model, const float* poses, const sbm_occ_ray_params* params);
 
+/* ---- occupancy map: growth, a table that rehashes itself into a larger one on the device ---------------------------------------
+ * octomap has no full map: updateNode and insertPointCloud never refuse a voxel. sbm_occ_create fixes a capacity, and a voxel
+ * that finds no slot is counted (SBM_ERR_OCC_FULL, sbm_occ_overflow) and lost. A mapper that cannot know its voxel count in
+ * advance either reserves more by hand (sbm_occ_reserve) or lets the map grow (sbm_occ_set_growth). No statement of the sections
+ * above depends on which slot a key sits in, so the contract is one sentence: a map that grew is, bit for bit, what the same
+ * calls produce on a map created large enough -- keys, hit counts or log-odds bits, change states, every fetch, query, tree and
+ * written file. tests/test_gpu_occupancy_growth.py holds it to the octomap fixtures from a capacity of 1.
+ *  Off by default. Growth is a switch, off in a new map; a map that never enables it and never reserves behaves as stated above
+ *  and its calls launch what they launched before this section existed: growth-off maps launch the same kernels, and none of
+ *  this section's.
+ *  Policy, stated once in sbm_occ_growth_step: a step doubles the capacity, reaches at least what is needed -- the size the
+ *  counters report, twice that size where a cell found no slot, the voxel count of a load --, and clamps to the ceiling
+ *  (max_capacity; 0 is the create limit of 2^30 voxels). The slots follow as sbm_occ_create rounds them: the
+ *  power of two >= 2 * capacity. A step begins only when a cell found no slot or the size has passed the nominal capacity, so the
+ *  load stays at or below one half and the capacity at or below max(the created capacity, 4 * size).
+ *  Log-odds inserts (cloud, planes, discretised; every box / change-detection instantiation). The host reads the counters
+ *  between MARK and APPLY. MARK is idempotent: it claims keys and ORs bits, and a slot enters the touched list only when its flag
+ *  word was clear. If cells were lost the table is rehashed -- flag words, "created this scan" among them, move with their
+ *  keys, and the touched list is rebuilt from them --, the overflow counter goes back to its value before the scan, and the same
+ *  MARK runs again, until nothing is lost or the ceiling stops it; then APPLY runs once.
+ *  Hit inserts add counts and cannot run twice. The host keeps an upper bound on the size (launched pixels add up; every counter
+ *  read makes it exact). A launch whose pixels, added to that bound, exceed the capacity is preceded by a claim pass: the
+ *  insert's own front half, which claims keys, counts the ones that found no slot and adds no hit. It is redone after a rehash;
+ *  after it the unchanged insert kernel finds every key.
+ *  Loaders. sbm_occ_load_binary / sbm_occ_read_binary and sbm_occ_ot_load / sbm_occ_ot_read know the voxel count before they
+ *  touch the map; with growth on they reserve it where they returned SBM_ERR_OCC_FULL (a count above the ceiling still does).
+ *  Stopped. Where the ceiling or a refused allocation stops a step, the call finishes exactly as a growth-off call on the table
+ *  it has: lost cells are counted, the call returns SBM_ERR_OCC_FULL, and sbm_last_hip_error holds the allocation's error.
+ *  Synchronisation. With growth on, every insert and load waits for its own launches to read the counters: sync == 0 calls may
+ *  synchronise internally and are NOT capturable in a graph. With growth off nothing changes. A rehash allocates the new table
+ *  beside the old one (12 B per slot, 20 B in log-odds mode, 21 B with change states) and frees the old one after the move.
+ *  DIVERGENCE from a pre-sized map, none in content: the order of slots, and therefore nothing a caller can see. A tree built
+ *  before a growth answers as built (it is a snapshot). The probe bound (1024 slots) is unchanged; a key that finds no slot
+ *  within it in the larger table -- not seen at a load of one half -- is counted as lost.
+ *  Device. One lane per old slot; a stored key takes its place through the table's 64-bit
+ *  compare-and-swap (keys are distinct: every swap on an empty slot claims), plain vector stores carry its words, and the lanes
+ *  with a set flag word append their new slot to the touched list with one atomic per wavefront. No float atomics, no spin
+ *  waits, no grid barriers. sbm_get_profile: no new names; growth inside a call counts under that call's stage ("occ_rays_mark",
+ *  "occ_insert", "occ_load"), and an explicit sbm_occ_reserve records nothing. */
+typedef struct sbm_occ_growth_info {
+  int32_t enabled;        /* the switch */
+  int32_t reserved;
+  uint64_t capacity;      /* nominal, in voxels */
+  uint64_t slots;         /* of the table: the power of two >= 2 * capacity */
+  uint64_t max_capacity;  /* the ceiling in voxels (2^30 where none was given) */
+  uint64_t grown;         /* tables moved into a larger one so far, reserves and loads included */
+  uint64_t moved;         /* slots those moves carried */
+  uint64_t redone;        /* MARK launches and claim passes run again after a move */
+} sbm_occ_growth_info;
+/* The nominal capacity into *capacity. Host code. SBM_ERR_NULL; *capacity is written only on SBM_OK. */
+int sbm_occ_capacity(sbm_occ_map* map, size_t* capacity);
+/* Moves the map into a table for at least `capacity` voxels, on the device, in stream order behind earlier asynchronous calls;
+ * synchronous. Independent of the switch. It never shrinks: a value at or below the current capacity is SBM_OK and does
+ * nothing. Everything the map holds is the same afterwards: keys, hit counts or log-odds bits, change states, the overflow
+ * counter, mode, scan parity, the switches and the box. SBM_ERR_NULL; SBM_ERR_UNSUPPORTED above 2^30; SBM_ERR_NOMEM when an
+ * allocation is refused (SBM_ERR_HIP for another error): in all of these the map stays exactly as it was. */
+int sbm_occ_reserve(sbm_occ_map* map, size_t capacity);
+/* The switch (enable != 0) for the inserts and loads that follow, and its ceiling: max_capacity voxels, 0 meaning the create
+ * limit of 2^30. Survives sbm_occ_reset, as the other switches do. Host code: serves a map in either mode. SBM_ERR_NULL;
+ * SBM_ERR_UNSUPPORTED for a ceiling above 2^30, and nothing changes. A ceiling below the current capacity stops every step. */
+int sbm_occ_set_growth(sbm_occ_map* map, int enable, size_t max_capacity);
+/* The switch, the table and the counts so far into *out. Host code. SBM_ERR_NULL; *out is written only on SBM_OK. */
+int sbm_occ_get_growth(sbm_occ_map* map, sbm_occ_growth_info* out);
+/* The policy, plain host code: the capacity a growth step goes to from `capacity` when `need` voxels are known, under the
+ * ceiling max_capacity (0 or above 2^30: 2^30). *next = min(max(2 * capacity, need, 1), ceiling). SBM_ERR_NULL;
+ * SBM_ERR_OCC_FULL when capacity is already at or above the ceiling, and *next is left alone. */
+int sbm_occ_growth_step(size_t capacity, size_t need, size_t max_capacity, size_t* next);
+
 /* ---- visual-word dictionary: addNewWords, computeLikelihood, limitKeypoints ---------------------------------------------------
  * The reference's loop-closure thread, started by Mapper::process for each key frame: addWordIds -> VWDictionary::addNewWords
  * (src/slam/src/core/Mapper.cpp:413-484, VWDictionary.cpp:40-115) and detectLoopClosure -> computeLikelihood

@@ -17,6 +17,7 @@
 // uninterrupted run.
 // setBBXMin() / setBBXMax() / useBBXLimit(), enableChangeDetection() / changedKeys() and the discretize flag of insertPointCloud
 // are octomap's three insert switches, in its spelling.
+// reserve() / setGrowth() let the table grow on the device, so that a long-running mapper need not know its voxel count.
 #ifndef SBM_OCCUPANCY_HPP_
 #define SBM_OCCUPANCY_HPP_
 
@@ -217,6 +218,21 @@ class OccupancyMap {
     std::vector<std::pair<uint64_t, bool>> out(n);
     for (size_t i = 0; i < n; i++) out[i] = std::make_pair(k[i], c[i] != 0);
     return out;
+  }
+  // ---- growth (sbm.h, "occupancy map: growth"): octomap never reports a full map ------------------------------------------------
+  // reserve() moves the map into a table for at least `capacity` voxels and keeps everything it holds; setGrowth(true) lets
+  // every insert and load do so when it needs to, up to max_capacity voxels (0: the create limit), instead of SBM_ERR_OCC_FULL.
+  void reserve(size_t capacity) { check(sbm_occ_reserve(m_, capacity)); }
+  size_t capacity() {
+    size_t n = 0;
+    check(sbm_occ_capacity(m_, &n));
+    return n;
+  }
+  void setGrowth(bool enable, size_t max_capacity = 0) { check(sbm_occ_set_growth(m_, enable ? 1 : 0, max_capacity)); }
+  sbm_occ_growth_info growth() {
+    sbm_occ_growth_info g;
+    check(sbm_occ_get_growth(m_, &g));
+    return g;
   }
   // the stored voxels ascending by packed key with their log-odds
   std::vector<uint64_t> leaves(std::vector<float>& logodds) {

@@ -168,6 +168,13 @@ class OccOtHeader(ctypes.Structure):
                 ("value_max", ctypes.c_float), ("key_min", ctypes.c_uint16 * 3), ("key_max", ctypes.c_uint16 * 3), ("pad", ctypes.c_uint32)]
 
 
+class OccGrowthInfo(ctypes.Structure):
+    """`sbm_occ_growth_info` of include/sbm.h: what sbm_occ_get_growth reports of a map's table and its growth so far."""
+
+    _fields_ = [("enabled", ctypes.c_int32), ("reserved", ctypes.c_int32), ("capacity", ctypes.c_uint64), ("slots", ctypes.c_uint64),
+                ("max_capacity", ctypes.c_uint64), ("grown", ctypes.c_uint64), ("moved", ctypes.c_uint64), ("redone", ctypes.c_uint64)]
+
+
 OCC_OT_FAN, OCC_OT_SCAN_TILE = 16, 1024      # SBM_OCC_OT_FAN, SBM_OCC_OT_SCAN_TILE: the tile constants of the .ot device parse
 
 
@@ -427,6 +434,11 @@ def load_library():
     L.sbm_occ_insert_cloud_discrete.argtypes = L.sbm_occ_insert_cloud.argtypes
     L.sbm_occ_insert_rays_discrete_device.argtypes = L.sbm_occ_insert_rays_device.argtypes
     L.sbm_occ_insert_rays_discrete.argtypes = L.sbm_occ_insert_rays.argtypes
+    L.sbm_occ_capacity.argtypes = [vp, ctypes.POINTER(sz)]
+    L.sbm_occ_reserve.argtypes = [vp, sz]
+    L.sbm_occ_set_growth.argtypes = [vp, ci, sz]
+    L.sbm_occ_get_growth.argtypes = [vp, ctypes.POINTER(OccGrowthInfo)]
+    L.sbm_occ_growth_step.argtypes = [sz, sz, sz, ctypes.POINTER(sz)]
     wp = ctypes.POINTER(VwdParams)
     pi = ctypes.POINTER(ci)
     L.sbm_vwd_params_default.argtypes = [wp]

@@ -9,7 +9,7 @@ import numpy as np
 
 from ._abi import (ERR_OCC_FULL, OCC_CELL_FREE, OCC_CELL_OCCUPIED, OCC_CELL_OUT, OCC_CELL_UNKNOWN, OCC_RAY_BOUNDS,  # noqa: F401
                    OCC_RAY_HIT, OCC_RAY_NONE, OCC_RAY_RANGE, OCC_RAY_UNKNOWN, OCC_TREE_LOGODDS, OCC_TREE_MAXLIKELIHOOD, OccParams,
-                   OccBinaryHeader, OccOtHeader, OccQueryParams, OccRayParams, OccTreeCounts, StereoBMError, _check, _torch, load_library)
+                   OccBinaryHeader, OccGrowthInfo, OccOtHeader, OccQueryParams, OccRayParams, OccTreeCounts, StereoBMError, _check, _torch, load_library)
 
 
 def occ_params(resolution=0.1, range_max=5.0, tree_depth=16):
@@ -130,6 +130,14 @@ def occ_query_validate(params):
     return load_library().sbm_occ_query_params_validate(ctypes.byref(params))
 
 
+def occ_growth_step(capacity, need=0, max_capacity=0):
+    """The growth policy (sbm_occ_growth_step, host code): the capacity a step goes to from `capacity` when `need` voxels are
+    known, under the ceiling max_capacity (0: 2^30). Raises StereoBMError(ERR_OCC_FULL) at the ceiling."""
+    nxt = ctypes.c_size_t()
+    _check(load_library().sbm_occ_growth_step(int(capacity), int(need), int(max_capacity), ctypes.byref(nxt)))
+    return nxt.value
+
+
 def _poses(poses, n):
     p = np.ascontiguousarray(np.asarray(poses, np.float32).reshape(-1, 12))
     if p.shape[0] != n:
@@ -139,9 +147,11 @@ def _poses(poses, n):
 
 class OccupancyMap:
     """A map for up to `capacity` voxels on the device of `engine` (a StereoBM or StereoSGBM), which must outlive it: the map
-    uses the engine's handle, stream and scratch. Not thread-safe."""
+    uses the engine's handle, stream and scratch. Not thread-safe. grow=True lets the table rehash itself into a larger one
+    instead of filling up, up to max_capacity voxels (0: the create limit of 2^30)."""
 
     def __init__(self, engine, capacity, params=None, **kw):
+        grow, max_capacity = kw.pop("grow", False), kw.pop("max_capacity", 0)
         if params is not None and kw:
             raise TypeError("pass either an OccParams or keyword parameters")
         self._p = params if params is not None else occ_params(**kw)
@@ -149,6 +159,8 @@ class OccupancyMap:
         self._L = engine._L
         self._m = ctypes.c_void_p()
         _check(self._L.sbm_occ_create(engine._h, ctypes.byref(self._p), int(capacity), ctypes.byref(self._m)), engine._h)
+        if grow or max_capacity:
+            self.set_growth(grow, max_capacity)
 
     def close(self):
         m = getattr(self, "_m", None)
@@ -305,6 +317,31 @@ class OccupancyMap:
         _check(self._L.sbm_occ_fetch_changes_device(self._m, keys.data_ptr() if n else None, created.data_ptr() if n else None, n,
                                                     ctypes.byref(got)), self._engine._h)
         return keys[:got.value], created[:got.value]
+
+    # ---- growth: a larger table on the device, by hand (reserve) or whenever an insert or a load needs it (set_growth) ----------
+    @property
+    def capacity(self):
+        """The nominal capacity in voxels; the table has the power of two >= twice as many slots."""
+        v = ctypes.c_size_t()
+        _check(self._L.sbm_occ_capacity(self._m, ctypes.byref(v)), self._engine._h)
+        return v.value
+
+    def reserve(self, capacity):
+        """Move the map into a table for at least `capacity` voxels; everything it holds stays. Never shrinks."""
+        _check(self._L.sbm_occ_reserve(self._m, int(capacity)), self._engine._h)
+        self._engine._inflight.clear()
+
+    def set_growth(self, enable=True, max_capacity=0):
+        """Let inserts and loads grow the table instead of reporting ERR_OCC_FULL, up to max_capacity voxels (0: 2^30). With
+        growth on, sync=False calls may synchronise internally."""
+        _check(self._L.sbm_occ_set_growth(self._m, int(bool(enable)), int(max_capacity)), self._engine._h)
+
+    def growth(self):
+        """dict: enabled, capacity, slots, max_capacity, grown (tables moved), moved (slots carried), redone (launches run again)"""
+        g = OccGrowthInfo()
+        _check(self._L.sbm_occ_get_growth(self._m, ctypes.byref(g)), self._engine._h)
+        return dict(enabled=g.enabled, capacity=g.capacity, slots=g.slots, max_capacity=g.max_capacity, grown=g.grown, moved=g.moved,
+                    redone=g.redone)
 
     def load_binary(self, data_or_path, params=None, sync=True, **kw):
         """octomap's readBinary: replace the map's content by the voxels of a .bt stream -- bytes (or a uint8 array), or the

@@ -226,6 +226,19 @@ float occ_logodds(double p);   // these three are in sbm_occ_rays.hip
 int occ_ray_params_check(const sbm_occ_ray_params* p);
 int occ_logodds_alloc(sbm_occ_map* map);   // what the log-odds mode keeps beside the table
 bool occ_axis_host(double factor, float coord, unsigned* k);   // occ_axis on the host (sbm_occ_options.hip)
+// sbm_occ_grow.hip. The map into a table for `capacity` voxels (more than it has, at most 2^30): everything a slot holds moves with its key,
+// and the running scan's touched list is rebuilt from the flag words. A refused allocation leaves the map as it was.
+int occ_rehash(sbm_occ_map* map, size_t capacity);
+bool occ_can_reserve(const sbm_occ_map* map, size_t voxels);   // growth is on and its ceiling admits so many voxels
+// A growing map after a launch that claimed keys (MARK, the hit insert's claim pass): reads the counters into *c and grows the
+// table if cells were lost (overflow above `before`) or the size has passed the capacity. *again: cells were lost and the table
+// grew, the overflow counter is back at `before`, and the caller launches the same claims again and calls this again. Where the
+// ceiling or an allocation stops the growth the lost cells stay counted and *again is false.
+int occ_grow_settle(sbm_occ_map* map, unsigned long long before, OccCounters* c, bool* again);
+int occ_overflow_before(sbm_occ_map* map, unsigned long long* before);   // the overflow counter as a launch on a growing map finds it
+int occ_set_overflow(sbm_occ_map* map, unsigned long long value);       // in stream order
+// The hit insert's claim pass over m planes (at most the 64 of one insert launch) with their poses: keys claimed, no hit added
+int occ_claim_launch(sbm_occ_map* map, const int16_t* d_disp, const OccGeom& g, const sbm_stereo_model* model, const float* poses, int m);
 OccLevel occ_tree_level(const sbm_occ_tree* t, int d);   // these two are in sbm_occ_tree.hip: depth d of a built tree (empty levels for
 int occ_tree_stats(sbm_occ_tree* t);                     // one that is not), and the counts of the last build into t->host, read once
 // The radix sort's second key / payload arrays for n pairs in the handle's sort buffer and, where asked, a first payload array
@@ -312,6 +325,13 @@ struct sbm_occ_map {
   unsigned bbx_min_key[3], bbx_max_key[3];
   sbm::DevBuf change;           // from the first enable: one byte of change state per slot
   sbm::DevBuf dedupe;           // from the first discretised insert: one scan's key set, key list and count
+  // growth (sbm_occ_grow.hip); sbm_occ_reset keeps the switch and the ceiling
+  bool grow;                    // sbm_occ_set_growth
+  size_t max_capacity;          // its ceiling in voxels; 0: the create limit
+  size_t size_bound;            // hit mode: what the host can say the size does not exceed without reading it (launched points add up)
+  bool overflow_known;          // `overflow` below is the device's counter: only a growing map keeps this up
+  unsigned long long overflow;
+  unsigned long long grown, moved, redone;   // tables grown, slots moved, scans or launches redone so far
   template <class F> void each(F f) { f(keys); f(hits); f(ctr); f(flags); f(touched); f(change); f(dedupe); }
 };
 

@@ -1,0 +1,270 @@
+// sbm_occ_grow.hip -- the occupancy map's growth: the table rehashed into a larger one on the device, the policy that says how
+// large, and the claim pass that lets the hit insert, whose counts cannot be added twice, learn that a launch fits before it
+// runs.  gfx950. include/sbm.h ("occupancy map: growth") states the contract; a map that never enables growth and never
+// reserves launches nothing of this file.
+//
+//   occ_rehash_kernel   one lane per old slot: a stored key takes its place in the new table (occ_find_or_claim: keys are
+//                       distinct, so every compare-and-swap on an empty slot claims) and carries its 32-bit word, its flag word
+//                       and its change byte; a slot whose flag word is set enters the running scan's touched list.
+//   occ_claim_kernel    the hit insert's front half: pixel -> point -> gate -> key, the wavefront's leaders claim their keys and
+//                       count those that found no slot. It adds no hit, so it can run again on a larger table.
+#include "sbm_occ.h"
+
+namespace sbm {
+#pragma clang fp contract(off)
+
+constexpr size_t kOccGrowMax = (size_t)1 << 30;   // sbm_occ_create's limit
+constexpr int kOccClaimChunk = 64;                // as the insert's launches: the poses travel as kernel arguments
+struct OccClaimPoses { float t[kOccClaimChunk][12]; };
+
+struct OccRehash {
+  const unsigned long long* old_keys;
+  const unsigned* old_vals;
+  const unsigned* old_flags;       // null in hit mode
+  const uint8_t* old_change;       // null where detection was never enabled
+  uint32_t old_slots;
+  unsigned long long* keys;
+  unsigned* vals;
+  unsigned* flags;
+  uint8_t* change;
+  unsigned* touched;
+  uint32_t mask, max_probe, slots;
+  uint32_t parity;                 // which of OccCounters::touched the running scan counts in
+  OccCounters* ctr;
+};
+
+__global__ void __launch_bounds__(256) occ_rehash_kernel(OccRehash r) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  const unsigned long long key = i < r.old_slots ? r.old_keys[i] : kOccEmpty;
+  bool listed = false;
+  uint32_t slot = 0;
+  if (key != kOccEmpty) {
+    bool claimed = false;
+    if (occ_find_or_claim(r.keys, key, r.mask, r.max_probe, &slot, &claimed)) {
+      r.vals[slot] = r.old_vals[i];
+      const unsigned f = r.old_flags ? r.old_flags[i] : 0;
+      if (f) {
+        r.flags[slot] = f;
+        listed = true;
+      }
+      if (r.old_change) {
+        const uint8_t s = r.old_change[i];
+        if (s != kOccChangeNone) r.change[slot] = s;
+      }
+    } else {   // a probe walk of the larger table that ends without a slot: the voxel is lost, and counted as lost
+      atomicAdd(&r.ctr->overflow, 1ull);
+      atomicSub(&r.ctr->size, 1u);
+    }
+  }
+  const uint32_t at = occ_wave_append(listed, &r.ctr->touched[r.parity]);   // every lane is here
+  if (listed && at < r.slots) r.touched[at] = slot;
+}
+
+__global__ void __launch_bounds__(256) occ_claim_kernel(const int16_t* __restrict__ disp, OccGeom g, sbm_stereo_model m, OccClaimPoses poses,
+                                                         unsigned long long* __restrict__ keys, OccCounters* __restrict__ ctr) {
+#pragma clang fp contract(off)
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  unsigned long long key = kOccEmpty;
+  const float* pose = poses.t[blockIdx.y];
+  Pt3 p;
+  if (i < g.W * g.H && occ_world_point(disp + (size_t)blockIdx.y * g.W * g.H, i, g, m, pose, &p)) {
+    const float vx = p.x - pose[3], vy = p.y - pose[7], vz = p.z - pose[11];
+    const float nsq = vx * vx + vy * vy + vz * vz;          // the gate of occ_insert_kernel, expression for expression
+    unsigned k0, k1, k2;
+    if (__dsqrt_rn((double)nsq) <= (double)g.range_max_sqrd && occ_axis(g.factor, p.x, &k0) && occ_axis(g.factor, p.y, &k1) &&
+        occ_axis(g.factor, p.z, &k2))
+      key = occ_pack(k0, k1, k2);
+  }
+  // the wavefront's distinct keys: the lowest lane of each value leads
+  const int lane = threadIdx.x & 63;
+  const unsigned lo = (unsigned)key, hi = (unsigned)(key >> 32);
+  unsigned long long todo = __ballot(key != kOccEmpty);
+  bool leads = false;
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const unsigned llo = __builtin_amdgcn_readlane(lo, leader), lhi = __builtin_amdgcn_readlane(hi, leader);
+    const unsigned long long same = __ballot(lo == llo && hi == lhi);
+    if (lane == leader) leads = true;
+    todo &= ~same;
+  }
+  if (!leads) return;
+  uint32_t slot;
+  bool claimed = false;
+  const bool found = occ_find_or_claim(keys, key, g.mask, g.max_probe, &slot, &claimed);
+  if (claimed) atomicAdd(&ctr->size, 1u);
+  if (!found) atomicAdd(&ctr->overflow, 1ull);
+}
+
+static size_t occ_ceiling(const sbm_occ_map* map) { return map->max_capacity ? map->max_capacity : kOccGrowMax; }
+
+bool occ_can_reserve(const sbm_occ_map* map, size_t voxels) { return map->grow && voxels <= occ_ceiling(map); }
+
+int occ_overflow_before(sbm_occ_map* map, unsigned long long* before) {
+  if (!map->overflow_known) {
+    OccCounters c;
+    const int st = occ_read_counters(map, &c);
+    if (st != SBM_OK) return st;
+    map->overflow = c.overflow;
+    map->overflow_known = true;
+  }
+  *before = map->overflow;
+  return SBM_OK;
+}
+
+int occ_set_overflow(sbm_occ_map* map, unsigned long long value) {
+  sbm_handle* h = map->h;
+  map->overflow = value;       // the copy reads the map's own word, which outlives it
+  map->overflow_known = true;
+  HIPCHK(h, hipMemcpyAsync(&map->ctr.as<OccCounters>()->overflow, &map->overflow, sizeof(value), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return SBM_OK;
+}
+
+int occ_rehash(sbm_occ_map* map, size_t capacity) {
+  sbm_handle* h = map->h;
+  uint32_t slots = 2;
+  while ((size_t)slots < 2 * capacity) slots <<= 1;
+  // the new buffers beside the old ones: a refused allocation frees what it got and leaves the map as it was
+  DevBuf keys = {}, vals = {}, flags = {}, touched = {}, change = {};
+  hipError_t e = keys.grow((size_t)slots * 8, h->stream);
+  if (e == hipSuccess) e = vals.grow((size_t)slots * 4, h->stream);
+  if (e == hipSuccess && map->flags.p) e = flags.grow((size_t)slots * 4, h->stream);
+  if (e == hipSuccess && map->touched.p) e = touched.grow((size_t)slots * 4, h->stream);
+  if (e == hipSuccess && map->change.p) e = change.grow(slots, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(keys.p, 0xFF, (size_t)slots * 8, h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(vals.p, 0, (size_t)slots * 4, h->stream);
+  if (e == hipSuccess && flags.p) e = hipMemsetAsync(flags.p, 0, (size_t)slots * 4, h->stream);
+  if (e == hipSuccess && change.p) e = hipMemsetAsync(change.p, 0, slots, h->stream);
+  OccRehash r;
+  r.parity = map->scan & 1;
+  OccCounters* ctr = map->ctr.as<OccCounters>();
+  if (e == hipSuccess) e = hipMemsetAsync(&ctr->touched[r.parity], 0, sizeof(unsigned), h->stream);   // the kernel counts the list anew
+  if (e == hipSuccess) {
+    r.old_keys = map->keys.as<unsigned long long>();
+    r.old_vals = map->hits.as<unsigned>();
+    r.old_flags = map->flags.as<unsigned>();
+    r.old_change = map->change.as<uint8_t>();
+    r.old_slots = map->slots;
+    r.keys = keys.as<unsigned long long>();
+    r.vals = vals.as<unsigned>();
+    r.flags = flags.as<unsigned>();
+    r.change = change.as<uint8_t>();
+    r.touched = touched.as<unsigned>();
+    r.mask = slots - 1;
+    r.max_probe = std::min(slots, kOccMaxProbe);
+    r.slots = slots;
+    r.ctr = ctr;
+    if (!r.touched) r.old_flags = nullptr;   // no list, no flags: the log-odds mode allocates both
+    hipLaunchKernelGGL(occ_rehash_kernel, dim3((map->slots + 255) / 256), dim3(256), 0, h->stream, r);
+    e = hipGetLastError();
+  }
+  OccCounters c = {};
+  if (e == hipSuccess) e = hipMemcpyAsync(&c, ctr, sizeof(c), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // the old table is read no more
+  if (e != hipSuccess) {
+    for (DevBuf* b : {&keys, &vals, &flags, &touched, &change}) b->release();
+    h->last_hip = (int)e;
+    return e == hipErrorOutOfMemory ? SBM_ERR_NOMEM : SBM_ERR_HIP;
+  }
+  std::swap(map->keys, keys);
+  std::swap(map->hits, vals);
+  if (flags.p) std::swap(map->flags, flags);
+  if (touched.p) std::swap(map->touched, touched);
+  if (change.p) std::swap(map->change, change);
+  for (DevBuf* b : {&keys, &vals, &flags, &touched, &change}) b->release();
+  map->capacity = capacity;
+  map->slots = slots;
+  map->grown++;
+  map->moved += c.size;
+  if (map->overflow_known && c.overflow != map->overflow) map->overflow_known = false;
+  return SBM_OK;
+}
+
+int occ_grow_settle(sbm_occ_map* map, unsigned long long before, OccCounters* c, bool* again) {
+  *again = false;
+  int st = occ_read_counters(map, c);
+  if (st != SBM_OK) return st;
+  const bool lost = c->overflow > before;
+  map->overflow = c->overflow;
+  map->overflow_known = true;
+  if (!lost && c->size <= map->capacity) return SBM_OK;
+  // A lost cell says the scan is still adding voxels: twice the size it has reached, which a full table (size = slots) turns
+  // into four times the capacity, and which stays within four times whatever the size ends at.
+  size_t next;
+  if (sbm_occ_growth_step(map->capacity, lost ? 2 * (size_t)c->size : c->size, map->max_capacity, &next) != SBM_OK) return SBM_OK;   // at the ceiling
+  st = occ_rehash(map, next);
+  if (st == SBM_ERR_NOMEM) return SBM_OK;   // refused: the call goes on with the table it has, the error is in last_hip
+  if (st != SBM_OK || !lost) return st;     // the size alone asked: flags and list moved with the keys, nothing is redone
+  st = occ_set_overflow(map, before);
+  if (st != SBM_OK) return st;
+  map->redone++;
+  *again = true;
+  return SBM_OK;
+}
+
+// The hit insert's claim pass over m planes (sbm_occupancy.hip launches it where a growing map cannot show that they fit)
+int occ_claim_launch(sbm_occ_map* map, const int16_t* d_disp, const OccGeom& g, const sbm_stereo_model* model, const float* poses, int m) {
+  sbm_handle* h = map->h;
+  OccClaimPoses ps;
+  memset(&ps, 0, sizeof(ps));
+  memcpy(ps.t, poses, sizeof(float) * 12 * m);
+  const size_t plane = (size_t)g.W * g.H;
+  hipLaunchKernelGGL(occ_claim_kernel, dim3((unsigned)((plane + 255) / 256), m), dim3(256), 0, h->stream, d_disp, g, *model, ps,
+                     map->keys.as<unsigned long long>(), map->ctr.as<OccCounters>());
+  HIPCHK(h, hipGetLastError());
+  return SBM_OK;
+}
+
+}  // namespace sbm
+using namespace sbm;
+
+extern "C" {
+
+int sbm_occ_growth_step(size_t capacity, size_t need, size_t max_capacity, size_t* next) {
+  if (!next) return SBM_ERR_NULL;
+  const size_t ceiling = max_capacity && max_capacity < kOccGrowMax ? max_capacity : kOccGrowMax;
+  if (capacity >= ceiling) return SBM_ERR_OCC_FULL;
+  size_t n = std::max<size_t>(2 * capacity, 1);
+  if (n < need) n = need;
+  *next = std::min(n, ceiling);
+  return SBM_OK;
+}
+
+int sbm_occ_capacity(sbm_occ_map* map, size_t* capacity) {
+  if (!map || !capacity) return SBM_ERR_NULL;
+  *capacity = map->capacity;
+  return SBM_OK;
+}
+
+int sbm_occ_reserve(sbm_occ_map* map, size_t capacity) {
+  if (!map) return SBM_ERR_NULL;
+  if (capacity <= map->capacity) return SBM_OK;
+  if (capacity > kOccGrowMax) return SBM_ERR_UNSUPPORTED;
+  DeviceScope dscope(map->h->device);
+  HIPCHK(map->h, dscope.enter());
+  return occ_rehash(map, capacity);
+}
+
+int sbm_occ_set_growth(sbm_occ_map* map, int enable, size_t max_capacity) {
+  if (!map) return SBM_ERR_NULL;
+  if (max_capacity > kOccGrowMax) return SBM_ERR_UNSUPPORTED;
+  map->grow = enable != 0;
+  map->max_capacity = max_capacity;
+  map->overflow_known = false;   // inserts with growth off do not keep the host's copy
+  return SBM_OK;
+}
+
+int sbm_occ_get_growth(sbm_occ_map* map, sbm_occ_growth_info* out) {
+  if (!map || !out) return SBM_ERR_NULL;
+  memset(out, 0, sizeof(*out));
+  out->enabled = map->grow ? 1 : 0;
+  out->capacity = map->capacity;
+  out->slots = map->slots;
+  out->max_capacity = occ_ceiling(map);
+  out->grown = map->grown;
+  out->moved = map->moved;
+  out->redone = map->redone;
+  return SBM_OK;
+}
+
+}  // extern "C"

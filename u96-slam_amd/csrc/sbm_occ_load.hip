@@ -68,7 +68,7 @@ static int occ_load_run(sbm_occ_map* map, const uint8_t* bytes, size_t n, const 
   int st = occ_bt_parse(bytes, n, &info, &leaves, false);
   if (st != SBM_OK) return st;
   if (info.resolution != occ_printed_resolution(map->p.resolution)) return SBM_ERR_SIZE;
-  if (info.voxels > map->capacity) return SBM_ERR_OCC_FULL;
+  if (info.voxels > map->capacity && !occ_can_reserve(map, info.voxels)) return SBM_ERR_OCC_FULL;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
   StageClock& clk = h->occ.clock;
@@ -101,7 +101,6 @@ static int occ_load_run(sbm_occ_map* map, const uint8_t* bytes, size_t n, const 
   OccLoad g;
   g.leaves = (uint32_t)count;
   g.total = (uint32_t)info.voxels;
-  occ_probe(map, &g.mask, &g.max_probe);
   const float cmin = occ_logodds(p->clamp_min), cmax = occ_logodds(p->clamp_max);
   memcpy(&g.vmin, &cmin, 4);
   memcpy(&g.vmax, &cmax, 4);
@@ -109,6 +108,12 @@ static int occ_load_run(sbm_occ_map* map, const uint8_t* bytes, size_t n, const 
   st = occ_clear(map);
   if (st != SBM_OK) return st;
   map->mode = kOccModeLogOdds;
+  if (info.voxels > map->capacity) {       // a growing map reserves the stream's voxels: the emptied table moves nothing
+    st = occ_rehash(map, info.voxels);
+    if (st != SBM_OK && st != SBM_ERR_NOMEM) return st;   // refused: the load goes on into the table it has and counts what it loses
+    map->overflow_known = st == SBM_OK;
+  }
+  occ_probe(map, &g.mask, &g.max_probe);
   hipLaunchKernelGGL(occ_load_kernel, dim3((g.total + 255) / 256), dim3(256), 0, h->stream, d_word, d_first, g,
                      map->keys.as<unsigned long long>(), map->hits.as<unsigned>(), map->ctr.as<OccCounters>());
   HIPCHK(h, hipGetLastError());

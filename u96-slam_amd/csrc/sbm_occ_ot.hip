@@ -528,7 +528,7 @@ static int occ_ot_load_body(sbm_occ_map* map, const uint8_t* bytes, size_t n, in
     std::vector<unsigned> first;
     st = occ_ot_parse(bytes, n, want, &info, &words, &values, false);
     if (st != SBM_OK) return st;
-    if (info.voxels > map->capacity) return SBM_ERR_OCC_FULL;
+    if (info.voxels > map->capacity && !occ_can_reserve(map, info.voxels)) return SBM_ERR_OCC_FULL;
     leaves = words.size();
     voxels = info.voxels;
     try {
@@ -557,7 +557,7 @@ static int occ_ot_load_body(sbm_occ_map* map, const uint8_t* bytes, size_t n, in
     leaves = r.leaves;
     voxels = r.voxels;
     if (!leaves || leaves > records) return SBM_ERR_HIP;   // cannot happen: a complete tree has a leaf
-    if (voxels > map->capacity) return SBM_ERR_OCC_FULL;
+    if (voxels > map->capacity && !occ_can_reserve(map, voxels)) return SBM_ERR_OCC_FULL;
   }
   st = occ_logodds_alloc(map);
   if (st != SBM_OK) return st;
@@ -565,11 +565,16 @@ static int occ_ot_load_body(sbm_occ_map* map, const uint8_t* bytes, size_t n, in
   OccOtLoad g;
   g.leaves = (uint32_t)leaves;
   g.total = (uint32_t)voxels;
-  occ_probe(map, &g.mask, &g.max_probe);
   HIPCHK(h, clk.mark(kOccBegin, h->stream));
   st = occ_clear(map);
   if (st != SBM_OK) return st;
   map->mode = kOccModeLogOdds;
+  if (voxels > map->capacity) {            // a growing map reserves the stream's voxels: the emptied table moves nothing
+    st = occ_rehash(map, voxels);
+    if (st != SBM_OK && st != SBM_ERR_NOMEM) return st;   // refused: the load goes on into the table it has and counts what it loses
+    map->overflow_known = st == SBM_OK;
+  }
+  occ_probe(map, &g.mask, &g.max_probe);
   hipLaunchKernelGGL(occ_ot_expand_kernel, dim3((g.total + 255) / 256), dim3(256), 0, h->stream, a.word, a.first, a.val, g,
                      map->keys.as<unsigned long long>(), map->hits.as<unsigned>(), map->ctr.as<OccCounters>());
   HIPCHK(h, hipGetLastError());

@@ -259,6 +259,18 @@ int occ_logodds_alloc(sbm_occ_map* map) {
   return SBM_OK;
 }
 
+// The table as a scan's launches see it: its walk and its arrays. A growing map states it again after every growth.
+static void occ_rays_table(sbm_occ_map* map, OccRay* g, OccTable* t) {
+  occ_probe(map, &g->mask, &g->max_probe);
+  g->slots = map->slots;
+  t->keys = map->keys.as<unsigned long long>();
+  t->logodds = map->hits.as<float>();
+  t->flags = map->flags.as<unsigned>();
+  t->touched = map->touched.as<unsigned>();
+  t->ctr = map->ctr.as<OccCounters>();
+  t->change = map->change.as<uint8_t>();
+}
+
 // The first log-odds insert after create or reset allocates the flag words and the touched list and fixes the mode.
 static int occ_rays_begin(sbm_occ_map* map, const sbm_occ_ray_params* p, OccRay* g, OccTable* t) {
   if (map->mode == kOccModeHits) return SBM_ERR_UNSUPPORTED;
@@ -272,20 +284,13 @@ static int occ_rays_begin(sbm_occ_map* map, const sbm_occ_ray_params* p, OccRay*
   g->miss = occ_logodds(p->prob_miss);
   g->cmin = occ_logodds(p->clamp_min);
   g->cmax = occ_logodds(p->clamp_max);
-  occ_probe(map, &g->mask, &g->max_probe);
-  g->slots = map->slots;
   g->parity = 0;
   g->thres = occ_logodds(p->occupancy_thres);
   for (int i = 0; i < 3; i++) {
     g->bmin[i] = map->bbx_min[i], g->bmax[i] = map->bbx_max[i];
     g->kmin[i] = map->bbx_min_key[i], g->kmax[i] = map->bbx_max_key[i];
   }
-  t->keys = map->keys.as<unsigned long long>();
-  t->logodds = map->hits.as<float>();
-  t->flags = map->flags.as<unsigned>();
-  t->touched = map->touched.as<unsigned>();
-  t->ctr = map->ctr.as<OccCounters>();
-  t->change = map->change.as<uint8_t>();
+  occ_rays_table(map, g, t);
   return SBM_OK;
 }
 
@@ -319,14 +324,31 @@ template <class Dedupe> static void occ_dedupe_run(sbm_handle* h, const OccDedup
   dedupe();
 }
 
-// One scan: `mark` launches its mark kernel; the apply launch follows in stream order.
-template <class Mark> static int occ_rays_scan(sbm_occ_map* map, OccRay& g, const OccTable& t, Mark mark) {
+// One scan: `mark` launches its mark kernel; the apply launch follows in stream order. On a growing map the host reads the
+// counters in between: MARK only claims keys and ORs bits, and a slot enters the touched list only when its flag word was clear,
+// so the same MARK runs again on a larger table, which brought the flags along, until no cell is lost.
+template <class Mark> static int occ_rays_scan(sbm_occ_map* map, OccRay& g, OccTable& t, Mark mark) {
   sbm_handle* h = map->h;
   StageClock& clk = h->occ.clock;
   g.parity = map->scan & 1;
+  unsigned long long before = 0;
+  if (map->grow) {
+    const int st = occ_overflow_before(map, &before);
+    if (st != SBM_OK) return st;
+  }
   HIPCHK(h, clk.mark(kOccBegin, h->stream));
   mark();
   HIPCHK(h, hipGetLastError());
+  for (bool again = map->grow; again;) {
+    OccCounters c;
+    const int st = occ_grow_settle(map, before, &c, &again);
+    if (st != SBM_OK) return st;
+    occ_rays_table(map, &g, &t);
+    if (again) {
+      mark();
+      HIPCHK(h, hipGetLastError());
+    }
+  }
   HIPCHK(h, clk.mark(kOccMid, h->stream));
   occ_with_options(map, [&](auto, auto track) {
     hipLaunchKernelGGL((occ_rays_apply_kernel<decltype(track)::value>), dim3(std::min((map->slots + 255) / 256, 1024u)), dim3(256), 0,

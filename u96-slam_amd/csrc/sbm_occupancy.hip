@@ -146,6 +146,9 @@ int occ_clear(sbm_occ_map* map) {
   if (map->change.p) HIPCHK(h, hipMemsetAsync(map->change.p, 0, map->slots, h->stream));   // the switches and the box stay
   map->mode = kOccModeNone;
   map->scan = 0;
+  map->size_bound = 0;
+  map->overflow = 0;
+  map->overflow_known = true;
   return SBM_OK;
 }
 
@@ -179,6 +182,7 @@ hipError_t occ_clock_start(sbm_handle* h, int a, int b) {
 }
 
 int occ_overflow_status(sbm_occ_map* map, int sync) {
+  if (!sync && map->grow && map->overflow_known) return map->overflow ? SBM_ERR_OCC_FULL : SBM_OK;   // read inside the call
   if (!sync && !map->h->occ.clock.on) return SBM_OK;
   OccCounters c;
   const int st = occ_read_counters(map, &c);
@@ -201,6 +205,27 @@ static int occ_insert_run(sbm_occ_map* map, int n, const int16_t* d_disp, int W,
   HIPCHK(h, clk.mark(kOccBegin, h->stream));
   for (int c0 = 0; c0 < n; c0 += kOccChunk) {
     const int m = std::min(kOccChunk, n - c0);
+    const size_t points = plane * m;
+    if (map->grow && map->size_bound + points > map->capacity) {
+      // The launch cannot be shown to fit and its counts cannot be added twice: a claim pass first, redone on a larger table
+      // while it loses keys. After it the insert finds every key, unless the ceiling or an allocation stopped the growth:
+      // then the insert itself counts what it loses, as on a map that does not grow.
+      unsigned long long before;
+      int st = occ_overflow_before(map, &before);
+      OccCounters c = {};
+      for (bool again = true; st == SBM_OK && again;) {
+        occ_probe(map, &g.mask, &g.max_probe);
+        st = occ_claim_launch(map, d_disp + plane * c0, g, model, poses + (size_t)12 * c0, m);
+        if (st == SBM_OK) st = occ_grow_settle(map, before, &c, &again);
+      }
+      if (st == SBM_OK && c.overflow > before) st = occ_set_overflow(map, before);
+      if (st != SBM_OK) return st;
+      occ_probe(map, &g.mask, &g.max_probe);
+      map->size_bound = c.size;
+      map->overflow_known = c.overflow == before;   // an insert that loses points counts them on the device
+    } else {
+      map->size_bound = std::min(map->size_bound + points, (size_t)map->slots);
+    }
     OccPoses ps;
     memset(&ps, 0, sizeof(ps));
     memcpy(ps.t, poses + (size_t)12 * c0, sizeof(float) * 12 * m);
