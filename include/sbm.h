@@ -1118,7 +1118,8 @@ int sbm_occ_write_binary(const uint64_t* keys, size_t n, double resolution, cons
  *  the touched list: occupied wins, the update above, the flags are cleared. No float atomics, no spin waits, no grid barriers;
  *  nothing depends on scheduling.
  *  Overflow. A cell that finds no slot within the probe bound raises the overflow counter (once per ray that reaches it), and
- *  the call, or with sync == 0 the next synchronous one, returns SBM_ERR_OCC_FULL. The table never frees a slot, so a stored
+ *  the call, or with sync == 0 the next synchronous one, returns SBM_ERR_OCC_FULL. The table never frees a slot -- the one
+ *  exception is a delete ("occupancy map: edit voxels by key"), which moves the map into a fresh table --, so a stored
  *  voxel has received every one of its updates and its value is exact; what is missing is whole voxels.
  *  sbm_get_profile: "occ_rays_mark" / "occ_rays_apply", ms of the last log-odds insert summed over its scans. */
 typedef struct sbm_occ_ray_params {
@@ -1669,6 +1670,103 @@ int sbm_occ_get_growth(sbm_occ_map* map, sbm_occ_growth_info* out);
  * ceiling max_capacity (0 or above 2^30: 2^30). *next = min(max(2 * capacity, need, 1), ceiling). SBM_ERR_NULL;
  * SBM_ERR_OCC_FULL when capacity is already at or above the ceiling, and *next is left alone. */
 int sbm_occ_growth_step(size_t capacity, size_t need, size_t max_capacity, size_t* next);
+
+/* ---- occupancy map: edit voxels by key, updateNode, setNodeValue and deleteNode (OccupancyOcTreeBase.hxx:273-285, 307-327,
+ * 373-433, 1097-1107; OcTreeBaseImpl.hxx:501-509, 681-716) --------------------------------------------------------------------------
+ * A scan is not the only way to write a map: a caller marks or clears single voxels, seeds a prior, replays the keys that
+ * sbm_occ_fetch_changes of another map produced, and forgets voxels, which is how a map at its ceiling keeps a sliding window
+ * around the robot. Everything is stated per depth-16 voxel, as the inserts are; arithmetic is IEEE binary32 as written, with
+ * no contraction. tests/occupancy_edit_cases.py is a literal transcription of this text, and tests/golden/occupancy_edit.npz
+ * holds what the reference's own octomap answered after every step, bit for bit.
+ *  Items. An item is (key or point, op, value); cmin, cmax and thres are the log-odds of the call's clamp_min, clamp_max and
+ *  occupancy_thres (sbm_occ_ray_logodds); v is the voxel's log-odds.
+ *   SBM_OCC_EDIT_UPDATE  updateNode(key, float u). EARLY ABORT: if the voxel exists and (u >= 0 && v >= cmax) or (u <= 0 && v <=
+ *             cmin), nothing happens at all, and no change record is made either. Otherwise an absent voxel is created at 0;
+ *             then v = v + u; v = cmin if v < cmin, else cmax if v > cmax (a NaN passes both tests and stays).
+ *             updateNode(key, bool) is this with u = the hit or the miss log-odds; the adaptors form it on the host from
+ *             sbm_occ_ray_params, as sbm_occ_ray_logodds does. The C-ABI takes floats only.
+ *   SBM_OCC_EDIT_SET     setNodeValue(key, float x). x = min(max(x, cmin), cmax) with the two std:: comparisons as written,
+ *             max(a, b) = a < b ? b : a and min(a, b) = b < a ? b : a, so a NaN stays NaN. An absent voxel is created. v = x.
+ *   SBM_OCC_EDIT_DELETE  deleteNode(key, depth 16): the voxel is removed with all it holds, its log-odds and its change state.
+ *             The value is not read. Deleting what is not there is not an error.
+ *  deleteNode(key, depth d) of sbm_occ_delete: d 0 means 16; d outside 0..16 gives SBM_ERR_UNSUPPORTED. Every stored voxel whose
+ *  three key components agree with the given key in their top d bits is removed with all it holds: log-odds or hit count, and the
+ *  change state. The rest of the map is untouched.
+ *  Change detection steps as octomap's leaf code does, per item, while detection is on: a voxel created by the item gets
+ *  `created`; else, where v >= thres differs before and after the item: none -> flipped, flipped -> none, and created stays.
+ *  Point forms. The key is coordToKeyChecked per axis (floor(factor * (double)coord) + 32768 within 0..65535). An item whose point
+ *  has no key is skipped, where octomap returns NULL or false.
+ *  Key forms. Keys are the packed k0 << 32 | k1 << 16 | k2. An item with a bit above 47 set is skipped. An op outside the three
+ *  values cannot be checked on the host for device arrays: such an item is skipped too. Skipped items are counted.
+ *  ORDER. Items of one call that name the same voxel take effect in item order: the clamps, setNodeValue and deletes in between
+ *  make the result depend on it (set then update differs from update then set; delete then update creates again from 0). Items
+ *  of different voxels do not interact. Calls take effect in call order.
+ *  DIVERGENCE, deleting the last voxel: it leaves an empty map here, and search says unknown. octomap keeps a childless root,
+ *  which its search then returns for every key.
+ *  DIVERGENCE, a deleted voxel's change record: it goes with the voxel here. octomap keeps the key in changed_keys, and its
+ *  std::map::insert then does not overwrite it when the voxel is created again.
+ *  Modes. Update and set belong to the log-odds mode: they fix the mode of a fresh map, as sbm_occ_insert_cloud does, and on a hit
+ *  map they return SBM_ERR_UNSUPPORTED and leave the map as it was (so does any sbm_occ_edit* call on a hit map, whatever its
+ *  items). Deletes (sbm_occ_delete*, sbm_occ_delete_box) serve both modes and leave the mode of a fresh map open: a hit map loses
+ *  the key and its count.
+ *  Large batches. n is up to 2^30. A batch is worked through in chunks of SBM_OCC_EDIT_CHUNK = 2097152 items, in item order, so
+ *  that scratch stays bounded: 28 B per item of a chunk (sorted keys, indices, the sort's second buffers, one slot per item).
+ *  Full table. With growth off an update or set item whose voxel finds no slot within the probe bound raises the overflow
+ *  counter once and is counted as lost; the call returns SBM_ERR_OCC_FULL; that voxel gets none of its items, every other voxel
+ *  gets all of its own. With growth on the claim pass is idempotent and is settled as MARK is ("occupancy map: growth"): the
+ *  table is rehashed and the same claims run again until nothing is lost or the ceiling stops it.
+ *  Deletes and the table. A call that removes something moves the map into a fresh table of the same capacity without the
+ *  removed slots -- it never shrinks --, so lookups, inserts, fetches and queries stay exactly as they are: there are no
+ *  tombstones. The move's buffers are allocated before anything is applied (per chunk; a batch of up to one chunk is applied
+ *  whole or not at all): a refused allocation returns SBM_ERR_NOMEM, with the error in sbm_last_hip_error, and the map is exactly
+ *  as it was. A call that may remove -- sbm_occ_delete*, sbm_occ_delete_box, and sbm_occ_edit* given ops -- synchronises whatever
+ *  `sync` says (the host counts the delete items, and reads what was removed), and cannot be captured in a graph; sbm_occ_edit*
+ *  with ops == NULL on a map that does not grow is asynchronous as the inserts are. Afterwards the size counter, and the hit
+ *  mode's host-side bound on it, are right; the overflow counter is unchanged; a tree built earlier is a snapshot and answers as
+ *  built. The insert's bounding box and its switch are not touched by sbm_occ_delete_box.
+ *  Device. CLAIM: one lane per item finds or claims the slot (the table's 64-bit compare-and-swap; delete
+ *  items only look) and counts claims, losses and skips. ORDER: the map's LSD radix sort orders (packed key, item index) pairs; it
+ *  is stable, so item order inside a voxel's run survives. APPLY: one lane per run head -- found from the sorted keys, not from
+ *  lane position -- walks its run with the rules above from the slot's current word to its final one, steps the change byte and
+ *  marks the slot in a removal mask if the voxel ends the batch absent. REMOVE: range and box deletes mark by predicate, one lane
+ *  per slot; the move is the growth section's, with the mask. Per-slot values are written with plain vector stores. No float
+ *  atomics, no spin waits, no grid barriers. sbm_get_profile: no new names; CLAIM counts under "occ_rays_mark"; ORDER, APPLY and
+ *  the move under "occ_rays_apply"; a delete on a hit map under "occ_insert". */
+enum { SBM_OCC_EDIT_UPDATE = 0, SBM_OCC_EDIT_SET = 1, SBM_OCC_EDIT_DELETE = 2 };
+#define SBM_OCC_EDIT_CHUNK 2097152
+typedef struct sbm_occ_edit_info {
+  uint64_t items;         /* of the last edit or delete call (sbm_occ_delete_box: 0) */
+  uint64_t skipped;       /* items without a key, with a key above bit 47 or with an unknown op */
+  uint64_t lost;          /* update and set items whose voxel found no slot */
+  uint64_t created;       /* voxels that were absent when the call began and were given a slot */
+  uint64_t removed;       /* voxels taken out of the table */
+} sbm_occ_edit_info;
+/* n mixed items in item order: d_keys n packed keys (8-byte aligned), d_ops n bytes (SBM_OCC_EDIT_*; NULL means all updates),
+ * d_values n floats (4-byte aligned), all in DEVICE memory; params (HOST memory) gives the clamps and the threshold. Asynchronous
+ * on the handle's stream unless sync != 0, profiling is on, growth is on or d_ops is given (see "Deletes and the table").
+ * SBM_ERR_NULL (d_keys and d_values may be NULL only for n == 0); SBM_ERR_SIZE for params sbm_occ_ray_params_validate rejects;
+ * SBM_ERR_UNSUPPORTED for n above 2^30, a misaligned array or a map in hit mode; SBM_ERR_NOMEM; SBM_ERR_OCC_FULL. */
+int sbm_occ_edit_device(sbm_occ_map* map, size_t n, const void* d_keys, const void* d_ops, const void* d_values,
+                        const sbm_occ_ray_params* params, int sync);
+/* The same from HOST memory, read before the call returns. Synchronous. */
+int sbm_occ_edit(sbm_occ_map* map, size_t n, const uint64_t* keys, const uint8_t* ops, const float* values,
+                 const sbm_occ_ray_params* params);
+/* The same with n float triples (4-byte aligned, DEVICE memory) in place of the keys. */
+int sbm_occ_edit_points_device(sbm_occ_map* map, size_t n, const void* d_xyz, const void* d_ops, const void* d_values,
+                               const sbm_occ_ray_params* params, int sync);
+int sbm_occ_edit_points(sbm_occ_map* map, size_t n, const float* xyz, const uint8_t* ops, const float* values,
+                        const sbm_occ_ray_params* params);
+/* deleteNode(key, depth) for n packed keys in DEVICE memory (8-byte aligned). Synchronous; either mode. SBM_ERR_NULL (d_keys may
+ * be NULL only for n == 0); SBM_ERR_UNSUPPORTED for a depth outside 0..16, n above 2^30 or a misaligned array; SBM_ERR_NOMEM. */
+int sbm_occ_delete_device(sbm_occ_map* map, size_t n, const void* d_keys, int depth);
+/* The same from HOST memory. */
+int sbm_occ_delete(sbm_occ_map* map, size_t n, const uint64_t* keys, int depth);
+/* Removes every voxel inside (outside != 0: outside) the key box, inclusive on both ends: inBBX(key) of "insert options" with
+ * these bounds, the loop octomap's users write (collect the depth-16 keys that pass the test, then deleteNode each). min > max on
+ * an axis is the empty box: nothing is inside it. Synchronous; either mode. SBM_ERR_NULL; SBM_ERR_NOMEM. */
+int sbm_occ_delete_box(sbm_occ_map* map, const uint16_t min_key[3], const uint16_t max_key[3], int outside);
+/* Synchronises and returns the counts of the last edit or delete call. SBM_ERR_NULL; *out is written only on SBM_OK. */
+int sbm_occ_last_edit(sbm_occ_map* map, sbm_occ_edit_info* out);
 
 /* ---- visual-word dictionary: addNewWords, computeLikelihood, limitKeypoints ---------------------------------------------------
  * The reference's loop-closure thread, started by Mapper::process for each key frame: addWordIds -> VWDictionary::addNewWords

@@ -18,9 +18,12 @@
 // setBBXMin() / setBBXMax() / useBBXLimit(), enableChangeDetection() / changedKeys() and the discretize flag of insertPointCloud
 // are octomap's three insert switches, in its spelling.
 // reserve() / setGrowth() let the table grow on the device, so that a long-running mapper need not know its voxel count.
+// updateNode() / setNodeValue() / deleteNode() / deleteBBX() edit and forget voxels by key or point, in octomap's spelling; the
+// vector forms take a batch in item order.
 #ifndef SBM_OCCUPANCY_HPP_
 #define SBM_OCCUPANCY_HPP_
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <memory>
@@ -234,6 +237,103 @@ class OccupancyMap {
     check(sbm_occ_get_growth(m_, &g));
     return g;
   }
+  // ---- edits by key (sbm.h, "occupancy map: edit voxels by key"), in octomap's spelling ----------------------------------------------
+  // Keys are packed k0 << 32 | k1 << 16 | k2 (packKey). lazy_eval only defers octomap's inner nodes: accepted and ignored. Where
+  // octomap returns NULL or false for a point without a key, nothing happens here either. The clamps and the threshold are those
+  // of rayParams().
+  static uint64_t packKey(const uint16_t key[3]) { return (uint64_t)key[0] << 32 | (uint64_t)key[1] << 16 | key[2]; }
+  // tree.updateNode(key, log_odds_update) / updateNode(point, log_odds_update)
+  void updateNode(uint64_t key, float log_odds_update, bool lazy_eval = false) {
+    (void)lazy_eval;
+    check(sbm_occ_edit(m_, 1, &key, nullptr, &log_odds_update, &rp_));
+  }
+  void updateNode(const float point[3], float log_odds_update, bool lazy_eval = false) {
+    (void)lazy_eval;
+    check(sbm_occ_edit_points(m_, 1, point, nullptr, &log_odds_update, &rp_));
+  }
+  // tree.updateNode(key, occupied) / updateNode(point, occupied): the hit or the miss log-odds of rayParams(), formed here
+  void updateNode(uint64_t key, bool occupied, bool lazy_eval = false) { updateNode(key, hitOrMiss(occupied), lazy_eval); }
+  void updateNode(const float point[3], bool occupied, bool lazy_eval = false) { updateNode(point, hitOrMiss(occupied), lazy_eval); }
+  // the same for a batch, in item order: one update each, or one for all
+  void updateNode(const std::vector<uint64_t>& keys, const std::vector<float>& log_odds_updates, bool lazy_eval = false) {
+    (void)lazy_eval;
+    if (keys.size() != log_odds_updates.size()) throw Error(SBM_ERR_SIZE, "updateNode: keys and updates differ in number");
+    check(sbm_occ_edit(m_, keys.size(), keys.data(), nullptr, log_odds_updates.data(), &rp_));
+  }
+  void updateNode(const std::vector<uint64_t>& keys, bool occupied, bool lazy_eval = false) {
+    updateNode(keys, std::vector<float>(keys.size(), hitOrMiss(occupied)), lazy_eval);
+  }
+  // points: n float triples
+  void updateNode(const float* xyz, size_t n, const float* log_odds_updates, bool lazy_eval = false) {
+    (void)lazy_eval;
+    check(sbm_occ_edit_points(m_, n, xyz, nullptr, log_odds_updates, &rp_));
+  }
+  void updateNode(const float* xyz, size_t n, bool occupied, bool lazy_eval = false) {
+    const std::vector<float> u(n, hitOrMiss(occupied));
+    updateNode(xyz, n, u.data(), lazy_eval);
+  }
+  // tree.setNodeValue(key, log_odds_value) / setNodeValue(point, log_odds_value), and for a batch
+  void setNodeValue(uint64_t key, float log_odds_value, bool lazy_eval = false) {
+    (void)lazy_eval;
+    const uint8_t op = SBM_OCC_EDIT_SET;
+    check(sbm_occ_edit(m_, 1, &key, &op, &log_odds_value, &rp_));
+  }
+  void setNodeValue(const float point[3], float log_odds_value, bool lazy_eval = false) {
+    (void)lazy_eval;
+    const uint8_t op = SBM_OCC_EDIT_SET;
+    check(sbm_occ_edit_points(m_, 1, point, &op, &log_odds_value, &rp_));
+  }
+  void setNodeValue(const std::vector<uint64_t>& keys, const std::vector<float>& log_odds_values, bool lazy_eval = false) {
+    (void)lazy_eval;
+    if (keys.size() != log_odds_values.size()) throw Error(SBM_ERR_SIZE, "setNodeValue: keys and values differ in number");
+    const std::vector<uint8_t> ops(keys.size(), (uint8_t)SBM_OCC_EDIT_SET);
+    check(sbm_occ_edit(m_, keys.size(), keys.data(), ops.data(), log_odds_values.data(), &rp_));
+  }
+  // mixed items in item order: ops SBM_OCC_EDIT_UPDATE / SET / DELETE (empty: all updates)
+  void edit(const std::vector<uint64_t>& keys, const std::vector<uint8_t>& ops, const std::vector<float>& values) {
+    if (keys.size() != values.size() || (!ops.empty() && ops.size() != keys.size())) throw Error(SBM_ERR_SIZE, "edit: arrays differ in number");
+    check(sbm_occ_edit(m_, keys.size(), keys.data(), ops.empty() ? nullptr : ops.data(), values.data(), &rp_));
+  }
+  // tree.deleteNode(key, depth) / deleteNode(point, depth): depth 0 means 16; always true where octomap says whether a node went
+  bool deleteNode(uint64_t key, unsigned depth = 0) {
+    check(sbm_occ_delete(m_, 1, &key, (int)depth));
+    return true;
+  }
+  bool deleteNode(const float point[3], unsigned depth = 0) {
+    uint64_t key;
+    if (!coordToKeyChecked(point, &key)) return false;
+    return deleteNode(key, depth);
+  }
+  bool deleteNode(const std::vector<uint64_t>& keys, unsigned depth = 0) {
+    check(sbm_occ_delete(m_, keys.size(), keys.data(), (int)depth));
+    return true;
+  }
+  // The loop octomap's users write over a box -- for every leaf with inBBX(key): deleteNode(key) -- with these bounds, both
+  // inclusive; outside = true removes everything else instead: the sliding window around the robot. The insert's box stays.
+  void deleteBBX(const uint16_t min[3], const uint16_t max[3], bool outside = false) { check(sbm_occ_delete_box(m_, min, max, outside ? 1 : 0)); }
+  void deleteBBX(const float min[3], const float max[3], bool outside = false) {
+    uint64_t lo, hi;
+    if (!coordToKeyChecked(min, &lo) || !coordToKeyChecked(max, &hi)) throw Error(SBM_ERR_SIZE, "deleteBBX: a bound has no key");
+    const uint16_t a[3] = {(uint16_t)(lo >> 32), (uint16_t)(lo >> 16), (uint16_t)lo}, b[3] = {(uint16_t)(hi >> 32), (uint16_t)(hi >> 16), (uint16_t)hi};
+    deleteBBX(a, b, outside);
+  }
+  // coordToKeyChecked(point, key): the packed key of a point, false where it has none
+  bool coordToKeyChecked(const float point[3], uint64_t* key) const {
+    uint64_t k = 0;
+    for (int i = 0; i < 3; i++) {
+      const double f = std::floor((1. / p_.resolution) * (double)point[i]);
+      if (!(f >= -32768.0 && f < 32768.0)) return false;
+      k = k << 16 | (uint64_t)((int)f + 32768);
+    }
+    *key = k;
+    return true;
+  }
+  // items, skipped, lost to a full table, voxels created and removed by the last edit or delete call
+  sbm_occ_edit_info lastEdit() {
+    sbm_occ_edit_info e;
+    check(sbm_occ_last_edit(m_, &e));
+    return e;
+  }
   // the stored voxels ascending by packed key with their log-odds
   std::vector<uint64_t> leaves(std::vector<float>& logodds) {
     std::vector<uint64_t> k(size());
@@ -369,6 +469,11 @@ class OccupancyMap {
     q.occupancy_thres_log = occupancyThresLog();
     q.ignore_unknown = ignoreUnknownCells ? 1 : 0;
     return q;
+  }
+  float hitOrMiss(bool occupied) const {
+    float c[5];
+    check(sbm_occ_ray_logodds(&rp_, c));
+    return occupied ? c[0] : c[1];
   }
   struct Box {
     float min[3], max[3];

@@ -3,14 +3,16 @@
 it, both sides of the record protocol between a generator and its driver (tools/octomap_drivers/driver.h describes it), the
 deterministic .npz writer, and the small arithmetic of keys, voxels and floats.
 
-The fixtures depend on each other in the order of FIXTURES, then of LATER_FIXTURES: a generator reads earlier fixtures from
-tests/golden (load()) and writes its own to --out. Run as a program, this file runs the whole chain, FIXTURES first:
+The fixtures depend on each other in the order of FIXTURES, then of LATER_FIXTURES, then of MORE_FIXTURES: a generator reads
+earlier fixtures from tests/golden (load()) and writes its own to --out. Run as a program, this file runs the whole chain in
+that order:
 
     python tools/octomap_kit.py --reference /path/to/U96-SLAM [--out DIR]
 
 FIXTURES is closed: tests/test_occupancy_fixture_kit.py pins its six names. A new fixture adds a driver
-tools/octomap_drivers/<name>.cpp, a generator with its cases, and its line in LATER_FIXTURES; load() takes every fixture of
-LATER_FIXTURES as later than all of FIXTURES.
+tools/octomap_drivers/<name>.cpp, a generator with its cases, and its line in MORE_FIXTURES, the open mapping: LATER_FIXTURES is
+pinned as well (tests/test_occupancy_options_cabi.py), and no test pins what MORE_FIXTURES holds. load() takes every fixture of
+LATER_FIXTURES as later than all of FIXTURES, and every fixture of MORE_FIXTURES as later than both.
 """
 import argparse
 import concurrent.futures
@@ -41,6 +43,8 @@ FIXTURES = {"octomap": "make_occupancy_fixtures.py", "rays": "make_occupancy_ray
             "tree": "make_occupancy_tree_fixtures.py", "load": "make_occupancy_load_fixtures.py", "ot": "make_occupancy_ot_fixtures.py"}
 # fixtures added after that list was closed, in their own order of dependence; they may read every fixture above
 LATER_FIXTURES = {"options": "make_occupancy_option_fixtures.py"}
+# open: every later fixture goes here, in its order of dependence; they may read every fixture of the two mappings above
+MORE_FIXTURES = {"edit": "make_occupancy_edit_fixtures.py"}
 RESOLUTION = 0.1
 PROBS = ("prob_hit", "prob_miss", "clamp_min", "clamp_max", "occupancy_thres")
 DEFAULT_PROBS = [getattr(rc.RayParams(), k) for k in PROBS]
@@ -50,10 +54,11 @@ CXX = ["g++", "-O1", "-std=c++11"]          # the recorded float bits and CPU ti
 
 # ---- build ----
 
-def build(reference, driver):
+def build(reference, driver, extra=()):
     """The reference's octomap sources, compiled once into a static archive (kept under a name made of the sources' and the
     flags' hash, so that every generator of a chain finds it), and tools/octomap_drivers/<driver>.cpp linked against it
-    -> the binary's path"""
+    -> the binary's path. extra: flags added to CXX for the archive and the driver alike, which then have an archive of their own"""
+    CXX = globals()["CXX"] + list(extra)
     ref = pathlib.Path(reference) / "src" / "slam"
     include = ["-I", str(ref / "include"), "-I", str(ref / "include" / "octomap")]
     srcs = sorted(str(p) for p in (ref / "src" / "octomap").glob("*.cpp"))
@@ -197,8 +202,9 @@ def save(out_dir, name, arrays, writer=write_npz, cpu=None):
 
 
 def load(name, by):
-    """The committed fixture `name`, for the generator of fixture `by`, which has to come later in FIXTURES + LATER_FIXTURES"""
-    order = list(FIXTURES) + list(LATER_FIXTURES)
+    """The committed fixture `name`, for the generator of fixture `by`, which has to come later in FIXTURES + LATER_FIXTURES +
+    MORE_FIXTURES"""
+    order = list(FIXTURES) + list(LATER_FIXTURES) + list(MORE_FIXTURES)
     assert order.index(name) < order.index(by), f"{by} cannot depend on {name}"
     return dict(np.load(GOLDEN / f"occupancy_{name}.npz"))
 
@@ -261,5 +267,5 @@ def bench_scans(planes=BENCH_PLANES, max_range=BENCH_RANGE):
 
 if __name__ == "__main__":
     args = arguments(__doc__)
-    for tool in list(FIXTURES.values()) + list(LATER_FIXTURES.values()):
+    for tool in list(FIXTURES.values()) + list(LATER_FIXTURES.values()) + list(MORE_FIXTURES.values()):
         subprocess.run([sys.executable, str(ROOT / "tools" / tool), "--reference", args.reference, "--out", args.out], check=True)

@@ -175,6 +175,15 @@ class OccGrowthInfo(ctypes.Structure):
                 ("max_capacity", ctypes.c_uint64), ("grown", ctypes.c_uint64), ("moved", ctypes.c_uint64), ("redone", ctypes.c_uint64)]
 
 
+class OccEditInfo(ctypes.Structure):
+    """`sbm_occ_edit_info` of include/sbm.h: what sbm_occ_last_edit reports of the last edit or delete call."""
+
+    _fields_ = [("items", ctypes.c_uint64), ("skipped", ctypes.c_uint64), ("lost", ctypes.c_uint64), ("created", ctypes.c_uint64),
+                ("removed", ctypes.c_uint64)]
+
+
+OCC_EDIT_UPDATE, OCC_EDIT_SET, OCC_EDIT_DELETE = 0, 1, 2      # SBM_OCC_EDIT_*: the op of an item
+OCC_EDIT_CHUNK = 2097152                                     # SBM_OCC_EDIT_CHUNK: items per chunk of a large batch
 OCC_OT_FAN, OCC_OT_SCAN_TILE = 16, 1024      # SBM_OCC_OT_FAN, SBM_OCC_OT_SCAN_TILE: the tile constants of the .ot device parse
 
 
@@ -439,6 +448,15 @@ def load_library():
     L.sbm_occ_set_growth.argtypes = [vp, ci, sz]
     L.sbm_occ_get_growth.argtypes = [vp, ctypes.POINTER(OccGrowthInfo)]
     L.sbm_occ_growth_step.argtypes = [sz, sz, sz, ctypes.POINTER(sz)]
+    # edits by key: items (keys or points, ops, values) in device or host memory
+    L.sbm_occ_edit_device.argtypes = [vp, sz, vp, vp, vp, orp, ci]
+    L.sbm_occ_edit.argtypes = [vp, sz, vp, vp, vp, orp]
+    L.sbm_occ_edit_points_device.argtypes = L.sbm_occ_edit_device.argtypes
+    L.sbm_occ_edit_points.argtypes = L.sbm_occ_edit.argtypes
+    L.sbm_occ_delete_device.argtypes = [vp, sz, vp, ci]
+    L.sbm_occ_delete.argtypes = [vp, sz, vp, ci]
+    L.sbm_occ_delete_box.argtypes = [vp, vp, vp, ci]
+    L.sbm_occ_last_edit.argtypes = [vp, ctypes.POINTER(OccEditInfo)]
     wp = ctypes.POINTER(VwdParams)
     pi = ctypes.POINTER(ci)
     L.sbm_vwd_params_default.argtypes = [wp]

@@ -7,7 +7,7 @@ import os
 
 import numpy as np
 
-from ._abi import (ERR_OCC_FULL, OCC_CELL_FREE, OCC_CELL_OCCUPIED, OCC_CELL_OUT, OCC_CELL_UNKNOWN, OCC_RAY_BOUNDS,  # noqa: F401
+from ._abi import (ERR_OCC_FULL, OCC_EDIT_CHUNK, OCC_EDIT_DELETE, OCC_EDIT_SET, OCC_EDIT_UPDATE, OccEditInfo, OCC_CELL_FREE, OCC_CELL_OCCUPIED, OCC_CELL_OUT, OCC_CELL_UNKNOWN, OCC_RAY_BOUNDS,  # noqa: F401
                    OCC_RAY_HIT, OCC_RAY_NONE, OCC_RAY_RANGE, OCC_RAY_UNKNOWN, OCC_TREE_LOGODDS, OCC_TREE_MAXLIKELIHOOD, OccParams,
                    OccBinaryHeader, OccGrowthInfo, OccOtHeader, OccQueryParams, OccRayParams, OccTreeCounts, StereoBMError, _check, _torch, load_library)
 
@@ -342,6 +342,101 @@ class OccupancyMap:
         _check(self._L.sbm_occ_get_growth(self._m, ctypes.byref(g)), self._engine._h)
         return dict(enabled=g.enabled, capacity=g.capacity, slots=g.slots, max_capacity=g.max_capacity, grown=g.grown, moved=g.moved,
                     redone=g.redone)
+
+    # ---- edits by key: octomap's updateNode, setNodeValue and deleteNode on batches of items ----------------------------------------
+    def edit(self, items, ops, values, params=None, sync=True, **kw):
+        """Mixed items in item order: `items` packed keys (n,) or points (n, 3); ops (n,) uint8 of OCC_EDIT_UPDATE / SET / DELETE,
+        or None for all updates; values (n,) float32: the log-odds update or the value to set. All three as torch CUDA tensors
+        (keys int64, points and values float32, ops uint8) or all as numpy arrays (the host form, always synchronous). Items that
+        name the same voxel take effect in item order. A call given ops may delete and is synchronous whatever `sync` says.
+        Raises StereoBMError(ERR_OCC_FULL) when a voxel found no slot."""
+        rp = self._ray_params(params, kw)
+        if isinstance(items, np.ndarray) or not hasattr(items, "data_ptr"):
+            it = np.asarray(items)
+            points = it.ndim == 2
+            it = np.ascontiguousarray(it, np.float32).reshape(-1, 3) if points else np.ascontiguousarray(it, np.uint64).reshape(-1)
+            n = len(it)
+            v = np.ascontiguousarray(np.asarray(values, np.float32).reshape(-1))
+            o = None if ops is None else np.ascontiguousarray(np.asarray(ops, np.uint8).reshape(-1))
+            if len(v) != n or (o is not None and len(o) != n):
+                raise StereoBMError(-2, f"{n} items with {len(v)} values" + ("" if o is None else f" and {len(o)} ops"))
+            call = self._L.sbm_occ_edit_points if points else self._L.sbm_occ_edit
+            _check(call(self._m, n, it.ctypes.data if n else None, o.ctypes.data if o is not None and n else None,
+                        v.ctypes.data if n else None, rp), self._engine._h)
+            self._engine._inflight.clear()
+            return
+        torch = _torch()
+        points = items.dim() == 2
+        want = torch.float32 if points else torch.int64
+        for t, dtype, what in ((items, want, "items"), (values, torch.float32, "values")) + (() if ops is None else ((ops, torch.uint8, "ops"),)):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or t.device.index != self._engine._device:
+                raise StereoBMError(-2, f"{what} must be a CUDA {dtype} tensor on the engine's device")
+        it, v, o = items.contiguous(), values.contiguous().reshape(-1), None if ops is None else ops.contiguous().reshape(-1)
+        n = it.shape[0]
+        if (points and it.shape[1] != 3) or v.shape[0] != n or (o is not None and o.shape[0] != n):
+            raise StereoBMError(-2, "items (n,) keys or (n, 3) points, with n values and n ops")
+        torch.cuda.current_stream(it.device).synchronize()
+        call = self._L.sbm_occ_edit_points_device if points else self._L.sbm_occ_edit_device
+        _check(call(self._m, n, it.data_ptr() if n else None, o.data_ptr() if o is not None and n else None, v.data_ptr() if n else None, rp,
+                    1 if sync else 0), self._engine._h)
+        self._after(sync or o is not None, (it, v, o))
+
+    def update_nodes(self, items, values, params=None, sync=True, **kw):
+        """octomap's updateNode(key | point, float) per item. values: (n,) log-odds updates, or one bool for every item --
+        updateNode(., occupied): the hit or the miss log-odds of the parameters, formed on the host."""
+        if isinstance(values, (bool, np.bool_)):
+            rp = params if params is not None else occ_ray_params(**kw)
+            params, kw = rp, {}
+            u = float(occ_ray_logodds(rp)[0 if values else 1])
+            n = len(items)
+            values = np.full(n, u, np.float32) if not hasattr(items, "data_ptr") else _torch().full((n,), u, dtype=_torch().float32, device=items.device)
+        self.edit(items, None, values, params, sync, **kw)
+
+    def set_node_values(self, items, values, params=None, sync=True, **kw):
+        """octomap's setNodeValue(key | point, float) per item."""
+        n = len(items)
+        if hasattr(items, "data_ptr"):
+            ops = _torch().full((n,), OCC_EDIT_SET, dtype=_torch().uint8, device=items.device)
+        else:
+            ops = np.full(n, OCC_EDIT_SET, np.uint8)
+        self.edit(items, ops, values, params, sync, **kw)
+
+    def delete_nodes(self, keys, depth=0):
+        """octomap's deleteNode(key, depth) per key: every stored voxel that agrees with a key in the top `depth` bits of each
+        component goes, with all it holds (depth 0 means 16). keys: packed, a torch CUDA int64 tensor or a numpy array; points
+        (n, 3) as a numpy array are turned into keys on the host (a point without a key is left out). Synchronous; either mode."""
+        if hasattr(keys, "data_ptr"):
+            torch = _torch()
+            if keys.dtype != torch.int64 or not keys.is_cuda or keys.dim() != 1 or keys.device.index != self._engine._device:
+                raise StereoBMError(-2, "keys must be a CUDA int64 (n,) tensor on the engine's device")
+            k = keys.contiguous()
+            torch.cuda.current_stream(k.device).synchronize()
+            _check(self._L.sbm_occ_delete_device(self._m, k.shape[0], k.data_ptr() if k.shape[0] else None, int(depth)), self._engine._h)
+        else:
+            k = np.asarray(keys)
+            if k.ndim == 2:
+                f = np.floor(np.float64(1.0 / self._p.resolution) * k.astype(np.float32).astype(np.float64))
+                with np.errstate(invalid="ignore"):
+                    ok = ((f >= -32768) & (f < 32768)).all(axis=1)
+                q = (f[ok] + 32768).astype(np.uint64)
+                k = q[:, 0] << np.uint64(32) | q[:, 1] << np.uint64(16) | q[:, 2]
+            k = np.ascontiguousarray(k, np.uint64).reshape(-1)
+            _check(self._L.sbm_occ_delete(self._m, len(k), k.ctypes.data if len(k) else None, int(depth)), self._engine._h)
+        self._engine._inflight.clear()
+
+    def delete_box(self, min_key, max_key, outside=False):
+        """Remove every voxel inside (outside=True: outside) the key box, both ends inclusive; min > max on an axis is the empty
+        box. Synchronous; either mode; the insert's own box is not touched."""
+        lo = np.ascontiguousarray(np.asarray(min_key, np.uint16).reshape(3))
+        hi = np.ascontiguousarray(np.asarray(max_key, np.uint16).reshape(3))
+        _check(self._L.sbm_occ_delete_box(self._m, lo.ctypes.data, hi.ctypes.data, int(bool(outside))), self._engine._h)
+        self._engine._inflight.clear()
+
+    def last_edit(self):
+        """dict: items, skipped, lost (to a full table), created, removed of the last edit or delete call. Synchronises."""
+        e = OccEditInfo()
+        _check(self._L.sbm_occ_last_edit(self._m, ctypes.byref(e)), self._engine._h)
+        return dict(items=e.items, skipped=e.skipped, lost=e.lost, created=e.created, removed=e.removed)
 
     def load_binary(self, data_or_path, params=None, sync=True, **kw):
         """octomap's readBinary: replace the map's content by the voxels of a .bt stream -- bytes (or a uint8 array), or the

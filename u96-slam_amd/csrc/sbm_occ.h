@@ -66,6 +66,26 @@ int occ_ot_parse(const uint8_t* b, size_t n, double want_res, sbm_occ_ot_header*
 int occ_ot_write_file(const std::vector<uint8_t>& body, size_t nodes, double resolution, const char* path);
 double occ_printed_resolution(double resolution);   // what the writers print for a resolution (%g), read back
 #pragma GCC visibility pop
+// The edits' host arithmetic (sbm_occ_edit.hip; tools/occupancy_edit_sanitize.cpp runs it under the sanitizers). A batch of n items
+// goes through in chunks of SBM_OCC_EDIT_CHUNK, in item order: how many, and the items [*begin, *begin + *count) of chunk c
+inline size_t occ_edit_chunks(size_t n) { return n / SBM_OCC_EDIT_CHUNK + (n % SBM_OCC_EDIT_CHUNK != 0); }
+inline void occ_edit_chunk(size_t n, size_t c, size_t* begin, size_t* count) {
+  *begin = c * (size_t)SBM_OCC_EDIT_CHUNK;
+  *count = *begin >= n ? 0 : n - *begin < (size_t)SBM_OCC_EDIT_CHUNK ? n - *begin : (size_t)SBM_OCC_EDIT_CHUNK;
+}
+// deleteNode's depth (0 means 16) -> the bits of a packed key in which a voxel has to agree with the given key: the top `depth`
+// bits of each component. false: a depth outside 0..16
+inline bool occ_depth_mask(int depth, uint64_t* mask) {
+  if (depth < 0 || depth > 16) return false;
+  const uint64_t m = (0xFFFFull << (16 - (depth ? depth : 16))) & 0xFFFFull;
+  *mask = m << 32 | m << 16 | m;
+  return true;
+}
+// a key box as the box delete's kernel takes it: is the packed key inside (both ends inclusive; min > max on an axis: nothing is)
+SBM_OCC_HD bool occ_key_in_box(unsigned long long key, const unsigned kmin[3], const unsigned kmax[3]) {
+  const unsigned k0 = (unsigned)(key >> 32) & 0xFFFF, k1 = (unsigned)(key >> 16) & 0xFFFF, k2 = (unsigned)key & 0xFFFF;
+  return k0 >= kmin[0] && k0 <= kmax[0] && k1 >= kmin[1] && k1 <= kmax[1] && k2 >= kmin[2] && k2 <= kmax[2];
+}
 
 #ifdef __HIP__
 constexpr unsigned long long kOccEmpty = ~0ull;
@@ -207,6 +227,48 @@ __device__ __forceinline__ unsigned occ_wave_append(bool take, unsigned* counter
   return base + __popcll(taking & ((1ull << lane) - 1));
 }
 
+// A move of the table (sbm_occ_grow.hip: into a larger one; sbm_occ_edit.hip: into one of the same size without the removed slots)
+struct OccRehash {
+  const unsigned long long* old_keys;
+  const unsigned* old_vals;
+  const unsigned* old_flags;       // null in hit mode
+  const uint8_t* old_change;       // null where detection was never enabled
+  uint32_t old_slots;
+  unsigned long long* keys;
+  unsigned* vals;
+  unsigned* flags;
+  uint8_t* change;
+  unsigned* touched;
+  uint32_t mask, max_probe, slots;
+  uint32_t parity;                 // which of OccCounters::touched the running scan counts in
+  OccCounters* ctr;
+};
+// One lane of a move, old slot i with `key` (kOccEmpty: nothing to move). EVERY lane of the wavefront has to reach this call.
+__device__ __forceinline__ void occ_move_lane(const OccRehash& r, uint32_t i, unsigned long long key) {
+  bool listed = false;
+  uint32_t slot = 0;
+  if (key != kOccEmpty) {
+    bool claimed = false;
+    if (occ_find_or_claim(r.keys, key, r.mask, r.max_probe, &slot, &claimed)) {
+      r.vals[slot] = r.old_vals[i];
+      const unsigned f = r.old_flags ? r.old_flags[i] : 0;
+      if (f) {
+        r.flags[slot] = f;
+        listed = true;
+      }
+      if (r.old_change) {
+        const uint8_t s = r.old_change[i];
+        if (s != kOccChangeNone) r.change[slot] = s;
+      }
+    } else {   // a probe walk of the new table that ends without a slot: the voxel is lost, and counted as lost
+      atomicAdd(&r.ctr->overflow, 1ull);
+      atomicSub(&r.ctr->size, 1u);
+    }
+  }
+  const uint32_t at = occ_wave_append(listed, &r.ctr->touched[r.parity]);   // every lane is here
+  if (listed && at < r.slots) r.touched[at] = slot;
+}
+
 constexpr size_t occ_pad = 256;   // the family's alignment: arrays that share a buffer begin on it (Carve, sbm_carve.h)
 #pragma GCC visibility push(hidden)   // host functions that cross files (these: sbm_occupancy.hip). Hidden, as the two above and
 // unlike the rest of the project's, so that the family's internal names stay out of what the library exports
@@ -229,6 +291,15 @@ bool occ_axis_host(double factor, float coord, unsigned* k);   // occ_axis on th
 // sbm_occ_grow.hip. The map into a table for `capacity` voxels (more than it has, at most 2^30): everything a slot holds moves with its key,
 // and the running scan's touched list is rebuilt from the flag words. A refused allocation leaves the map as it was.
 int occ_rehash(sbm_occ_map* map, size_t capacity);
+// The same move in two steps, for a caller that must know the new table exists before it changes anything: the buffers of a table
+// of `slots` slots beside the map's (a refused allocation frees what it got; the error is in last_hip), then the move itself into a
+// table for `capacity` voxels. remove (null: nothing), one byte per old slot: the slots that stay behind, `removed` of them, which
+// leave the size counter. *c: the counters after the move. The buffers are released either way.
+struct OccMoveBufs { DevBuf keys, vals, flags, touched, change; uint32_t slots; };
+int occ_move_alloc(sbm_occ_map* map, uint32_t slots, OccMoveBufs* b);
+int occ_move_run(sbm_occ_map* map, size_t capacity, OccMoveBufs* b, const uint8_t* remove, unsigned removed, OccCounters* c);
+void occ_move_release(OccMoveBufs* b);
+void occ_remove_launch(sbm_handle* h, const OccRehash& r, const uint8_t* remove, unsigned removed);   // sbm_occ_edit.hip: the move that leaves slots behind
 bool occ_can_reserve(const sbm_occ_map* map, size_t voxels);   // growth is on and its ceiling admits so many voxels
 // A growing map after a launch that claimed keys (MARK, the hit insert's claim pass): reads the counters into *c and grows the
 // table if cells were lost (overflow above `before`) or the size has passed the capacity. *again: cells were lost and the table
@@ -332,7 +403,11 @@ struct sbm_occ_map {
   bool overflow_known;          // `overflow` below is the device's counter: only a growing map keeps this up
   unsigned long long overflow;
   unsigned long long grown, moved, redone;   // tables grown, slots moved, scans or launches redone so far
-  template <class F> void each(F f) { f(keys); f(hits); f(ctr); f(flags); f(touched); f(change); f(dedupe); }
+  // edits (sbm_occ_edit.hip)
+  sbm::DevBuf edit, edit_mask;  // from the first edit or delete: its counts; from the first call that may delete: the removal
+                                // mask, one byte per slot, clear between calls
+  unsigned long long edit_items;   // of the last edit or delete call
+  template <class F> void each(F f) { f(keys); f(hits); f(ctr); f(flags); f(touched); f(change); f(dedupe); f(edit); f(edit_mask); }
 };
 
 struct sbm_occ_tree {

@@ -3,9 +3,10 @@
 // runs.  gfx950. include/sbm.h ("occupancy map: growth") states the contract; a map that never enables growth and never
 // reserves launches nothing of this file.
 //
-//   occ_rehash_kernel   one lane per old slot: a stored key takes its place in the new table (occ_find_or_claim: keys are
-//                       distinct, so every compare-and-swap on an empty slot claims) and carries its 32-bit word, its flag word
-//                       and its change byte; a slot whose flag word is set enters the running scan's touched list.
+//   occ_rehash_kernel   one lane per old slot (occ_move_lane, sbm_occ.h): a stored key takes its place in the new table
+//                       (occ_find_or_claim: keys are distinct, so every compare-and-swap on an empty slot claims) and carries its
+//                       32-bit word, its flag word and its change byte; a slot whose flag word is set enters the running scan's
+//                       touched list. The edits' move (sbm_occ_edit.hip) is the same lane behind a removal mask.
 //   occ_claim_kernel    the hit insert's front half: pixel -> point -> gate -> key, the wavefront's leaders claim their keys and
 //                       count those that found no slot. It adds no hit, so it can run again on a larger table.
 #include "sbm_occ.h"
@@ -17,47 +18,9 @@ constexpr size_t kOccGrowMax = (size_t)1 << 30;   // sbm_occ_create's limit
 constexpr int kOccClaimChunk = 64;                // as the insert's launches: the poses travel as kernel arguments
 struct OccClaimPoses { float t[kOccClaimChunk][12]; };
 
-struct OccRehash {
-  const unsigned long long* old_keys;
-  const unsigned* old_vals;
-  const unsigned* old_flags;       // null in hit mode
-  const uint8_t* old_change;       // null where detection was never enabled
-  uint32_t old_slots;
-  unsigned long long* keys;
-  unsigned* vals;
-  unsigned* flags;
-  uint8_t* change;
-  unsigned* touched;
-  uint32_t mask, max_probe, slots;
-  uint32_t parity;                 // which of OccCounters::touched the running scan counts in
-  OccCounters* ctr;
-};
-
 __global__ void __launch_bounds__(256) occ_rehash_kernel(OccRehash r) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  const unsigned long long key = i < r.old_slots ? r.old_keys[i] : kOccEmpty;
-  bool listed = false;
-  uint32_t slot = 0;
-  if (key != kOccEmpty) {
-    bool claimed = false;
-    if (occ_find_or_claim(r.keys, key, r.mask, r.max_probe, &slot, &claimed)) {
-      r.vals[slot] = r.old_vals[i];
-      const unsigned f = r.old_flags ? r.old_flags[i] : 0;
-      if (f) {
-        r.flags[slot] = f;
-        listed = true;
-      }
-      if (r.old_change) {
-        const uint8_t s = r.old_change[i];
-        if (s != kOccChangeNone) r.change[slot] = s;
-      }
-    } else {   // a probe walk of the larger table that ends without a slot: the voxel is lost, and counted as lost
-      atomicAdd(&r.ctr->overflow, 1ull);
-      atomicSub(&r.ctr->size, 1u);
-    }
-  }
-  const uint32_t at = occ_wave_append(listed, &r.ctr->touched[r.parity]);   // every lane is here
-  if (listed && at < r.slots) r.touched[at] = slot;
+  occ_move_lane(r, i, i < r.old_slots ? r.old_keys[i] : kOccEmpty);
 }
 
 __global__ void __launch_bounds__(256) occ_claim_kernel(const int16_t* __restrict__ disp, OccGeom g, sbm_stereo_model m, OccClaimPoses poses,
@@ -120,18 +83,31 @@ int occ_set_overflow(sbm_occ_map* map, unsigned long long value) {
   return SBM_OK;
 }
 
-int occ_rehash(sbm_occ_map* map, size_t capacity) {
+void occ_move_release(OccMoveBufs* b) {
+  for (DevBuf* d : {&b->keys, &b->vals, &b->flags, &b->touched, &b->change}) d->release();
+}
+
+// the new buffers beside the old ones: a refused allocation frees what it got and leaves the map as it was
+int occ_move_alloc(sbm_occ_map* map, uint32_t slots, OccMoveBufs* b) {
   sbm_handle* h = map->h;
-  uint32_t slots = 2;
-  while ((size_t)slots < 2 * capacity) slots <<= 1;
-  // the new buffers beside the old ones: a refused allocation frees what it got and leaves the map as it was
-  DevBuf keys = {}, vals = {}, flags = {}, touched = {}, change = {};
-  hipError_t e = keys.grow((size_t)slots * 8, h->stream);
-  if (e == hipSuccess) e = vals.grow((size_t)slots * 4, h->stream);
-  if (e == hipSuccess && map->flags.p) e = flags.grow((size_t)slots * 4, h->stream);
-  if (e == hipSuccess && map->touched.p) e = touched.grow((size_t)slots * 4, h->stream);
-  if (e == hipSuccess && map->change.p) e = change.grow(slots, h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(keys.p, 0xFF, (size_t)slots * 8, h->stream);
+  *b = OccMoveBufs{};
+  b->slots = slots;
+  hipError_t e = b->keys.grow((size_t)slots * 8, h->stream);
+  if (e == hipSuccess) e = b->vals.grow((size_t)slots * 4, h->stream);
+  if (e == hipSuccess && map->flags.p) e = b->flags.grow((size_t)slots * 4, h->stream);
+  if (e == hipSuccess && map->touched.p) e = b->touched.grow((size_t)slots * 4, h->stream);
+  if (e == hipSuccess && map->change.p) e = b->change.grow(slots, h->stream);
+  if (e == hipSuccess) return SBM_OK;
+  occ_move_release(b);
+  h->last_hip = (int)e;
+  return e == hipErrorOutOfMemory ? SBM_ERR_NOMEM : SBM_ERR_HIP;
+}
+
+int occ_move_run(sbm_occ_map* map, size_t capacity, OccMoveBufs* b, const uint8_t* remove, unsigned removed, OccCounters* c) {
+  sbm_handle* h = map->h;
+  const uint32_t slots = b->slots;
+  DevBuf &keys = b->keys, &vals = b->vals, &flags = b->flags, &touched = b->touched, &change = b->change;
+  hipError_t e = hipMemsetAsync(keys.p, 0xFF, (size_t)slots * 8, h->stream);
   if (e == hipSuccess) e = hipMemsetAsync(vals.p, 0, (size_t)slots * 4, h->stream);
   if (e == hipSuccess && flags.p) e = hipMemsetAsync(flags.p, 0, (size_t)slots * 4, h->stream);
   if (e == hipSuccess && change.p) e = hipMemsetAsync(change.p, 0, slots, h->stream);
@@ -155,14 +131,15 @@ int occ_rehash(sbm_occ_map* map, size_t capacity) {
     r.slots = slots;
     r.ctr = ctr;
     if (!r.touched) r.old_flags = nullptr;   // no list, no flags: the log-odds mode allocates both
-    hipLaunchKernelGGL(occ_rehash_kernel, dim3((map->slots + 255) / 256), dim3(256), 0, h->stream, r);
+    if (remove) occ_remove_launch(h, r, remove, removed);
+    else hipLaunchKernelGGL(occ_rehash_kernel, dim3((map->slots + 255) / 256), dim3(256), 0, h->stream, r);
     e = hipGetLastError();
   }
-  OccCounters c = {};
-  if (e == hipSuccess) e = hipMemcpyAsync(&c, ctr, sizeof(c), hipMemcpyDeviceToHost, h->stream);
+  *c = OccCounters{};
+  if (e == hipSuccess) e = hipMemcpyAsync(c, ctr, sizeof(*c), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);   // the old table is read no more
   if (e != hipSuccess) {
-    for (DevBuf* b : {&keys, &vals, &flags, &touched, &change}) b->release();
+    occ_move_release(b);
     h->last_hip = (int)e;
     return e == hipErrorOutOfMemory ? SBM_ERR_NOMEM : SBM_ERR_HIP;
   }
@@ -171,12 +148,23 @@ int occ_rehash(sbm_occ_map* map, size_t capacity) {
   if (flags.p) std::swap(map->flags, flags);
   if (touched.p) std::swap(map->touched, touched);
   if (change.p) std::swap(map->change, change);
-  for (DevBuf* b : {&keys, &vals, &flags, &touched, &change}) b->release();
+  occ_move_release(b);
   map->capacity = capacity;
   map->slots = slots;
+  if (map->overflow_known && c->overflow != map->overflow) map->overflow_known = false;
+  return SBM_OK;
+}
+
+int occ_rehash(sbm_occ_map* map, size_t capacity) {
+  uint32_t slots = 2;
+  while ((size_t)slots < 2 * capacity) slots <<= 1;
+  OccMoveBufs b;
+  OccCounters c;
+  int st = occ_move_alloc(map, slots, &b);
+  if (st == SBM_OK) st = occ_move_run(map, capacity, &b, nullptr, 0, &c);
+  if (st != SBM_OK) return st;
   map->grown++;
   map->moved += c.size;
-  if (map->overflow_known && c.overflow != map->overflow) map->overflow_known = false;
   return SBM_OK;
 }
 
