@@ -1296,9 +1296,10 @@ int sbm_occ_cast_view_device(sbm_occ_map* map, int width, int height, int scale,
  *             states them; a leaf is occupied iff it holds clamp max, which is its voxels' own >= threshold. With the header of
  *             sbm_occ_write_binary and `size` the node count the file equals, byte for byte, what sbm_occ_write_binary /
  *             sbm_occ_write_binary_logodds write for the fetched voxels.
- *  Not here: getMetricMin / getMetricMax (octomap forms them from float centres of pruned leaves, which the keys do not pin; the
- *  key bounds of sbm_occ_tree_info are exact), bounding-box iterators, incremental update (a rebuild is the update). The .ot format
- *  of a tree has a section of its own below ("the .ot format": sbm_occ_ot_body_device, sbm_occ_ot_write).
+ *  Elsewhere: getMetricMin / getMetricMax / volume, the bounding-box leaf iterator and getUnknownLeafCenters read a tree through the
+ *  section "the read side for planners" below (octomap forms the metric bounds in double from the leaves' centre keys and depths,
+ *  which the snapshot holds). Not here: incremental update (a rebuild is the update). The .ot format of a tree has a section of its
+ *  own below ("the .ot format": sbm_occ_ot_body_device, sbm_occ_ot_write).
  *  Device. The compacted table is sorted by 48-bit Morton code with the map's radix sort; siblings are then
  *  neighbours, and sixteen bottom-up passes (heads per tile, a scan, one write per head) make each level from the one below;
  *  one top-down pass per depth marks what lies under a collapsed node and ranks the non-leaf nodes in pre-order, so that the .bt
@@ -1767,6 +1768,103 @@ int sbm_occ_delete(sbm_occ_map* map, size_t n, const uint64_t* keys, int depth);
 int sbm_occ_delete_box(sbm_occ_map* map, const uint16_t min_key[3], const uint16_t max_key[3], int outside);
 /* Synchronises and returns the counts of the last edit or delete call. SBM_ERR_NULL; *out is written only on SBM_OK. */
 int sbm_occ_last_edit(sbm_occ_map* map, sbm_occ_edit_info* out);
+
+/* ---- occupancy map: the read side for planners (begin_leafs_bbx, OcTreeIterator.hxx:335-460; getUnknownLeafCenters and getMetricMin /
+ * getMetricMax / volume, OcTreeBaseImpl.hxx:872-1116; getRayIntersection, OccupancyOcTreeBase.hxx:768-853) ---------------------------
+ * How a planner or an explorer reads an octomap, on the device and without fetching the voxels: the leaves inside a box, the cells
+ * of a box that are still unknown, the metric bounds of the map, and where a ray enters the voxel it hit. Each is octomap's own
+ * function restated operation by operation; tests/occupancy_planner_cases.py is a literal transcription of this text and
+ * tests/golden/occupancy_planner.npz holds what the reference's own octomap answered, which the device equals bit for bit. The
+ * first three read an sbm_occ_tree SNAPSHOT (a tree that was never built answers as an empty one), the fourth needs the map's
+ * resolution only. All are read-only: the map, the tree and every entry point above stay as they are, and a tree or map that
+ * never calls these launches what it launched before. The names do not begin with sbm_occ_tree_ although three take a tree: that
+ * prefix is the closed set of the section "the octree above the voxels".
+ *  leaves in a key box   begin_leafs_bbx(min, max, maxDepth). Output layout, order, the cap / *count / SBM_ERR_SIZE rule and the
+ *             max_depth rule (0 means 16) are those of sbm_occ_tree_leaves_device; the entries are the subsequence of
+ *             leaves(max_depth) that the iterator visits. singleIncrement pushes a child at depth d with centre key c and
+ *             off = 32768 >> d iff, on every axis, min <= c + off && max >= c - off, in int. The test is LOOSE BY ONE KEY at the
+ *             upper side of a cube (a cube covers c - off .. c + off - 1): a box whose minimum equals a cube's one-past-end key
+ *             still visits that cube. The root itself is never tested. A node's own test implies its ancestors' tests -- the
+ *             interval [c - off, c + off] of a child lies inside its parent's, on either side and at depth 16 as well, where off
+ *             is 0 and the child's key is c or c - 1 of its parent -- so one lane per node decides for itself, and the visited set
+ *             is: every entry of leaves(max_depth) that passes its own test. A box with min > max on an axis visits no depth-16
+ *             voxel (off is 0 there); a node above them whose loose interval holds both bounds is still visited, as octomap does.
+ *             The point form applies coordToKeyChecked to both corners; if either has no key it returns SBM_OK with a count of 0.
+ *             DIVERGENCE: octomap's constructor says "set to end iterator" there, but it leaves the root on the stack and its loop
+ *             visits the root once; the fixture records that entry, the library returns none.
+ *  unknown cells in a box   getUnknownLeafCenters(centres, pmin, pmax, depth), literally: depth 0 means 16; each corner is clamped
+ *             to keyToCoord(coordToKey(p, depth), depth) as floats; step_size is the float of resolution * pow(2, 16 - depth);
+ *             steps[i] = floor(diff[i] / step_size) with diff the float difference of the clamped corners; each coordinate is a
+ *             running float sum from the clamped pmin, incremented BEFORE the query, so the cell at pmin itself is never asked and
+ *             the reported floats are not keyToCoord centres; a centre is reported iff search(p, depth) is NULL, which covers a
+ *             point without a key. Output: float triples in octomap's push order, x outermost and z innermost. Each axis resets
+ *             to the clamped pmin, so the three running sums are independent: the host forms three tables of at most 65 536
+ *             floats, sequentially, and one lane per cell of the steps[0] x steps[1] x steps[2] grid does the lookup of search at
+ *             the asked level. DIVERGENCES: coordToKey is unchecked in octomap and wraps its 16-bit cast for a corner outside the
+ *             key space; such a corner (a NaN among them) is refused with SBM_ERR_SIZE. A step count that is negative (pmax below
+ *             pmin on an axis), which octomap casts to unsigned with no defined result, is 0 steps: nothing is reported.
+ *  metric bounds   getMetricMin / getMetricMax, the const forms: over every leaf of the pruned tree the minimum of
+ *             keyToCoord(centre key, depth) - getNodeSize(depth) / 2.0 and the maximum of the same centre plus half the size, all
+ *             in double, with keyToCoord's three cases (depth 0: 0.0; depth 16: (key - 32768 + 0.5) * resolution; between:
+ *             (floor((key - 32768) / 2^(16 - depth)) + 0.5) * getNodeSize(depth)). An empty tree answers six zeros. At a fixed
+ *             depth these are non-decreasing functions of the key, so the device reduces the smallest and largest centre key per
+ *             axis and depth with integer minima / maxima (no float atomics) and the host forms at most 17 x 6 doubles; the result
+ *             is cached in the tree until the next build. Size is max - min and volume is x * y * z of the size. The bounds of
+ *             the pruned tree and of its expanded voxels may differ in the last bit, as they do in octomap (the fixture records
+ *             both); octomap's non-const calcMinMax forms the maximum as (centre - half) + size, which may differ likewise (the
+ *             fixture records it, the library does not provide it).
+ *  ray entry   getRayIntersection(origin, direction, center, intersection, delta), literally: the half cell is
+ *             float(resolution / 2.0); Vector3::dot multiplies and adds in float and returns double; operator- and
+ *             direction * float(d) + origin are float; per axis whose normal . direction != 0.0 the two planes are met at
+ *             d = (point - origin) . normal / (normal . direction) in double, and a meeting point passes unless one of its two
+ *             other coordinates is below the lower plane - 1e-6 or above the upper plane + 1e-6, compared in double; outD is the
+ *             minimum of d over the planes that pass; the result is direction * float(outD + delta) + origin. The direction is
+ *             NOT normalised here, and a negative d counts (an origin inside the voxel, a voxel behind the origin). found 0
+ *             leaves a NaN triple (0x7FC00000) where octomap leaves `intersection` untouched, the convention of SBM_OCC_RAY_NONE.
+ *             A zero direction meets no plane: not found. A NaN or infinite direction needs no special case: normal . direction
+ *             is NaN (x * 0 of an infinite x) or the value itself, != 0.0 holds, and every comparison with a NaN meeting point
+ *             is false, so the plane passes: found is 1. std::min(outD, d) leaves outD where d is NaN, and the result carries NaN
+ *             in the coordinates where the float arithmetic gives it (0 * inf, anything * NaN), exactly as octomap. getNormals is NOT provided: it needs octomap's marching-cubes tables.
+ *  Device. One launch per step, integer counters per wavefront, kernel boundaries only. The box iterator
+ *  runs a count pass, reads the count, then selects, sorts and gathers as sbm_occ_tree_leaves_device does. The unknown cells count
+ *  per tile of 1024 cells, scan the tile counts and write in linear cell order. No kernel contracts a multiply-add.
+ *  sbm_get_profile: the tree calls add to "occ_tree_query", the ray entries to "occ_cast". */
+/* begin_leafs_bbx by keys into d_keys (uint64, 8-byte aligned), d_depth (int32) and d_value (float, may be NULL), cap entries each,
+ * DEVICE memory; min_key / max_key are HOST memory. *count receives the number of entries; when it exceeds cap nothing is written
+ * and the call returns SBM_ERR_SIZE. Synchronous; waits for the stream twice. Checked in this order before anything is launched:
+ * SBM_ERR_NULL (d_keys and d_depth may be NULL only for cap == 0); SBM_ERR_SIZE for a max_depth outside 0..16;
+ * SBM_ERR_UNSUPPORTED for a misaligned pointer. */
+int sbm_occ_bbx_leaves_device(sbm_occ_tree* tree, const uint16_t min_key[3], const uint16_t max_key[3], int max_depth, void* d_keys,
+                              void* d_depth, void* d_value, size_t cap, size_t* count);
+/* The same into HOST memory. */
+int sbm_occ_bbx_leaves(sbm_occ_tree* tree, const uint16_t min_key[3], const uint16_t max_key[3], int max_depth, uint64_t* keys,
+                       int32_t* depth, float* value, size_t cap, size_t* count);
+/* begin_leafs_bbx by points (HOST memory): the same checks, then coordToKeyChecked of both corners; a corner without a key gives
+ * SBM_OK and a count of 0. */
+int sbm_occ_bbx_leaves_points_device(sbm_occ_tree* tree, const float min[3], const float max[3], int max_depth, void* d_keys, void* d_depth,
+                                     void* d_value, size_t cap, size_t* count);
+int sbm_occ_bbx_leaves_points(sbm_occ_tree* tree, const float min[3], const float max[3], int max_depth, uint64_t* keys, int32_t* depth,
+                              float* value, size_t cap, size_t* count);
+/* getUnknownLeafCenters into d_xyz (cap float triples, DEVICE memory, 4-byte aligned); pmin / pmax are HOST memory. *count receives
+ * the number of centres; when it exceeds cap nothing is written and the call returns SBM_ERR_SIZE. Synchronous. Checked in this
+ * order before anything is launched: SBM_ERR_NULL (d_xyz may be NULL only for cap == 0); SBM_ERR_SIZE for a depth outside 0..16,
+ * then for a corner outside the key space; SBM_ERR_UNSUPPORTED for a misaligned pointer, then for more than 2^30 cells. */
+int sbm_occ_unknown_device(sbm_occ_tree* tree, const float pmin[3], const float pmax[3], int depth, void* d_xyz, size_t cap, size_t* count);
+/* The same into HOST memory. */
+int sbm_occ_unknown(sbm_occ_tree* tree, const float pmin[3], const float pmax[3], int depth, float* xyz, size_t cap, size_t* count);
+/* getMetricMin and getMetricMax of the tree. The first call after a build reduces on the device and waits for the stream; later
+ * calls answer from the tree. SBM_ERR_NULL. */
+int sbm_occ_metric(sbm_occ_tree* tree, double min[3], double max[3]);
+/* getRayIntersection on n rays: d_dirs, d_centres and d_xyz n float triples, d_found n int32 (may be NULL), DEVICE memory, 4-byte
+ * aligned. Origins follow sbm_occ_cast_rays_device: n triples in DEVICE memory, or with shared_origin != 0 three floats in HOST
+ * memory that every ray starts from. Read-only, one lane per ray. Asynchronous unless sync != 0. Checked in this order before
+ * anything is launched: SBM_ERR_NULL (the arrays may be NULL only for n == 0, which is accepted and launches nothing);
+ * SBM_ERR_SIZE for a NaN delta; SBM_ERR_UNSUPPORTED for more than 2^30 rays or a misaligned pointer. */
+int sbm_occ_ray_intersections_device(sbm_occ_map* map, size_t n, const void* origins, int shared_origin, const void* d_dirs,
+                                     const void* d_centres, double delta, void* d_xyz, void* d_found, int sync);
+/* The same on HOST memory. Synchronous. */
+int sbm_occ_ray_intersections(sbm_occ_map* map, size_t n, const float* origins, int shared_origin, const float* dirs, const float* centres,
+                              double delta, float* xyz, int32_t* found);
 
 /* ---- visual-word dictionary: addNewWords, computeLikelihood, limitKeypoints ---------------------------------------------------
  * The reference's loop-closure thread, started by Mapper::process for each key frame: addWordIds -> VWDictionary::addNewWords

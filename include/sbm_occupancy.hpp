@@ -20,6 +20,8 @@
 // reserve() / setGrowth() let the table grow on the device, so that a long-running mapper need not know its voxel count.
 // updateNode() / setNodeValue() / deleteNode() / deleteBBX() edit and forget voxels by key or point, in octomap's spelling; the
 // vector forms take a batch in item order.
+// leafs_bbx() / getUnknownLeafCenters() / getMetricMin() / getMetricMax() / getMetricSize() / volume() on a tree and
+// getRayIntersection() on the map are octomap's read side for planners, in its spelling.
 #ifndef SBM_OCCUPANCY_HPP_
 #define SBM_OCCUPANCY_HPP_
 
@@ -88,6 +90,50 @@ class OccupancyTree {
     for (size_t i = 0; i < n; i++) out[i] = OccupancyLeaf{k[i], d[i], v[i]};
     return out;
   }
+  // for (it = tree.begin_leafs_bbx(min, max, maxDepth); it != tree.end_leafs_bbx(); ++it), by keys (both ends inclusive) ...
+  std::vector<OccupancyLeaf> leafs_bbx(const uint16_t min[3], const uint16_t max[3], unsigned maxDepth = 0) {
+    return listed([&](uint64_t* k, int32_t* d, float* v, size_t cap, size_t* n) {
+      return sbm_occ_bbx_leaves(t_, min, max, (int)maxDepth, k, d, v, cap, n);
+    });
+  }
+  // ... and by points: a corner without a key visits nothing
+  std::vector<OccupancyLeaf> leafs_bbx(const float min[3], const float max[3], unsigned maxDepth = 0) {
+    return listed([&](uint64_t* k, int32_t* d, float* v, size_t cap, size_t* n) {
+      return sbm_occ_bbx_leaves_points(t_, min, max, (int)maxDepth, k, d, v, cap, n);
+    });
+  }
+  // tree.getUnknownLeafCenters(node_centers, pmin, pmax, depth): x y z triples appended in octomap's push order
+  void getUnknownLeafCenters(std::vector<float>& node_centers, const float pmin[3], const float pmax[3], unsigned depth = 0) {
+    size_t n = 0;
+    int st = sbm_occ_unknown(t_, pmin, pmax, (int)depth, nullptr, 0, &n);   // the count
+    if (st != SBM_OK && !(st == SBM_ERR_SIZE && n > 0)) check(st);
+    const size_t at = node_centers.size();
+    node_centers.resize(at + 3 * n);
+    check(sbm_occ_unknown(t_, pmin, pmax, (int)depth, node_centers.data() + at, n, &n));
+  }
+  void getMetricMin(double& x, double& y, double& z) {
+    double lo[3], hi[3];
+    check(sbm_occ_metric(t_, lo, hi));
+    x = lo[0], y = lo[1], z = lo[2];
+  }
+  void getMetricMax(double& x, double& y, double& z) {
+    double lo[3], hi[3];
+    check(sbm_occ_metric(t_, lo, hi));
+    x = hi[0], y = hi[1], z = hi[2];
+  }
+  void getMetricSize(double& x, double& y, double& z) {
+    double minX, minY, minZ, maxX, maxY, maxZ;
+    getMetricMax(maxX, maxY, maxZ);
+    getMetricMin(minX, minY, minZ);
+    x = maxX - minX;
+    y = maxY - minY;
+    z = maxZ - minZ;
+  }
+  double volume() {
+    double x, y, z;
+    getMetricSize(x, y, z);
+    return x * y * z;
+  }
   // tree.writeBinary(path) of a SBM_OCC_TREE_MAXLIKELIHOOD tree
   void writeBinary(const std::string& path) { check(sbm_occ_tree_write_binary(t_, path.c_str())); }
   // tree.write(path) of a SBM_OCC_TREE_LOGODDS tree: the .ot file, every node's float
@@ -96,6 +142,19 @@ class OccupancyTree {
  private:
   static void check(int st) {
     if (st != SBM_OK) throw Error(st, sbm_strerror(st));
+  }
+  // a listing call run twice: for its count, then into arrays of that size
+  template <class Call> std::vector<OccupancyLeaf> listed(Call call) {
+    size_t n = 0;
+    int st = call(nullptr, nullptr, nullptr, 0, &n);
+    if (st != SBM_OK && !(st == SBM_ERR_SIZE && n > 0)) check(st);
+    std::vector<uint64_t> k(n);
+    std::vector<int32_t> d(n);
+    std::vector<float> v(n);
+    check(call(k.data(), d.data(), v.data(), n, &n));
+    std::vector<OccupancyLeaf> out(n);
+    for (size_t i = 0; i < n; i++) out[i] = OccupancyLeaf{k[i], d[i], v[i]};
+    return out;
   }
   float thres_;
   sbm_occ_tree* t_ = nullptr;
@@ -419,6 +478,21 @@ class OccupancyMap {
                 bool ignoreUnknownCells = false, double maxRange = -1.0) {
     const sbm_occ_query_params q = queryParams(ignoreUnknownCells, maxRange);
     check(sbm_occ_cast_rays(m_, n, origins, one_origin ? 1 : 0, directions, &q, status, ends));
+  }
+  // tree.getRayIntersection(origin, direction, center, intersection, delta): true iff the (un-normalised) ray's line enters the
+  // voxel around center, at intersection; where octomap leaves intersection untouched so does this.
+  bool getRayIntersection(const float origin[3], const float direction[3], const float center[3], float intersection[3], double delta = 0.0) {
+    int32_t found = 0;
+    float p[3];
+    check(sbm_occ_ray_intersections(m_, 1, origin, 1, direction, center, delta, p, &found));
+    if (found) intersection[0] = p[0], intersection[1] = p[1], intersection[2] = p[2];
+    return found != 0;
+  }
+  // n rays in host memory: origins n triples, or one that every ray starts from (one_origin); a ray that is not found leaves a NaN
+  // triple; found may be null
+  void getRayIntersections(const float* origins, bool one_origin, const float* directions, const float* centers, size_t n,
+                           float* intersections, int32_t* found = nullptr, double delta = 0.0) {
+    check(sbm_occ_ray_intersections(m_, n, origins, one_origin ? 1 : 0, directions, centers, delta, intersections, found));
   }
   // One ray per pixel of a width x height virtual camera at `pose`, into DEVICE memory (d_end may be null)
   void castView(int width, int height, int scale, const sbm_stereo_model& model, const float pose[12], void* d_status, void* d_end,

@@ -457,6 +457,16 @@ def load_library():
     L.sbm_occ_delete.argtypes = [vp, sz, vp, ci]
     L.sbm_occ_delete_box.argtypes = [vp, vp, vp, ci]
     L.sbm_occ_last_edit.argtypes = [vp, ctypes.POINTER(OccEditInfo)]
+    # the read side for planners: a box's corners and a ray's shared origin are host memory
+    L.sbm_occ_bbx_leaves_device.argtypes = [vp, vp, vp, ci, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_bbx_leaves.argtypes = L.sbm_occ_bbx_leaves_device.argtypes
+    L.sbm_occ_bbx_leaves_points_device.argtypes = L.sbm_occ_bbx_leaves_device.argtypes
+    L.sbm_occ_bbx_leaves_points.argtypes = L.sbm_occ_bbx_leaves_device.argtypes
+    L.sbm_occ_unknown_device.argtypes = [vp, vp, vp, ci, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_unknown.argtypes = L.sbm_occ_unknown_device.argtypes
+    L.sbm_occ_metric.argtypes = [vp, vp, vp]
+    L.sbm_occ_ray_intersections_device.argtypes = [vp, sz, vp, ci, vp, vp, ctypes.c_double, vp, vp, ci]
+    L.sbm_occ_ray_intersections.argtypes = [vp, sz, vp, ci, vp, vp, ctypes.c_double, vp, vp]
     wp = ctypes.POINTER(VwdParams)
     pi = ctypes.POINTER(ci)
     L.sbm_vwd_params_default.argtypes = [wp]

@@ -561,6 +561,46 @@ class OccupancyMap:
         self._after(sync, (o, d, status, end))
         return status, end
 
+    def ray_intersections(self, origins, directions, centres, delta=0.0, sync=True):
+        """octomap's getRayIntersection on n rays -> (found, xyz): int32 per ray and the (n, 3) points where each ray enters the
+        voxel around its centre (NaN where found is 0). directions and centres (n, 3) as torch CUDA float32 tensors, with origins
+        such a tensor or three floats that every ray starts from; or all as numpy arrays (the host form, always synchronous).
+        The directions are not normalised."""
+        if isinstance(directions, np.ndarray):
+            d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+            c = np.ascontiguousarray(centres, np.float32).reshape(-1, 3)
+            o = np.ascontiguousarray(np.asarray(origins, np.float32)).reshape(-1, 3)
+            shared = len(o) == 1 and np.ndim(origins) == 1
+            if (not shared and len(o) != len(d)) or len(c) != len(d):
+                raise StereoBMError(-2, f"{len(o)} origins and {len(c)} centres for {len(d)} rays")
+            n = len(d)
+            found, xyz = np.empty(n, np.int32), np.empty((n, 3), np.float32)
+            _check(self._L.sbm_occ_ray_intersections(self._m, n, o.ctypes.data if len(o) else None, int(shared), d.ctypes.data if n else None,
+                                                     c.ctypes.data if n else None, float(delta), xyz.ctypes.data if n else None,
+                                                     found.ctypes.data if n else None), self._engine._h)
+            return found, xyz
+        torch = _torch()
+        d = self._cuda_f32(directions, "directions")
+        c = self._cuda_f32(centres, "centres")
+        n = d.shape[0]
+        shared = not isinstance(origins, torch.Tensor)
+        if shared:
+            o = np.ascontiguousarray(np.asarray(origins, np.float32).reshape(3))
+            o_ptr = o.ctypes.data
+        else:
+            o = self._cuda_f32(origins, "origins")
+            o_ptr = o.data_ptr() if n else None
+        if (not shared and o.shape[0] != n) or c.shape[0] != n:
+            raise StereoBMError(-2, f"origins and centres must hold {n} rows")
+        found = torch.empty((n,), dtype=torch.int32, device=d.device)
+        xyz = torch.empty((n, 3), dtype=torch.float32, device=d.device)
+        torch.cuda.current_stream(d.device).synchronize()
+        _check(self._L.sbm_occ_ray_intersections_device(self._m, n, o_ptr, int(shared), d.data_ptr() if n else None,
+                                                        c.data_ptr() if n else None, float(delta), xyz.data_ptr() if n else None,
+                                                        found.data_ptr() if n else None, 1 if sync else 0), self._engine._h)
+        self._after(sync, (o, d, c, found, xyz))
+        return found, xyz
+
     def cast_view(self, width, height, model, pose, scale=1, params=None, sync=True, **kw):
         """One ray per pixel of a width x height virtual camera at `pose` (12 floats), built on the device -> torch CUDA
         (height, width) int32 statuses and (height, width, 3) float32 end points: cast_rays on the rays the header states."""
@@ -717,6 +757,91 @@ class OccupancyTree:
                                                   depth.data_ptr() if n else None, value.data_ptr() if n else None, n,
                                                   ctypes.byref(got)), self._engine._h)
         return keys[:got.value], depth[:got.value], value[:got.value]
+
+    def _box(self, lo, hi):
+        """-> (by points, two host arrays of three)"""
+        points = np.asarray(lo).dtype.kind == "f" or np.asarray(hi).dtype.kind == "f"
+        dt = np.float32 if points else np.uint16
+        if not points and (np.asarray(lo).min() < 0 or np.asarray(hi).min() < 0 or np.asarray(lo).max() > 65535 or np.asarray(hi).max() > 65535):
+            raise StereoBMError(-2, "a key lies in 0..65535")
+        return points, np.ascontiguousarray(np.asarray(lo, dt).reshape(3)), np.ascontiguousarray(np.asarray(hi, dt).reshape(3))
+
+    def _leaves_bbx(self, lo, hi, max_depth, device):
+        points, lo, hi = self._box(lo, hi)
+        call = getattr(self._L, "sbm_occ_bbx_leaves" + ("_points" if points else "") + ("_device" if device else ""))
+        got = ctypes.c_size_t()
+        st = call(self._t, lo.ctypes.data, hi.ctypes.data, int(max_depth), None, None, None, 0, ctypes.byref(got))       # the count
+        if st not in (0, -2) or (st == -2 and got.value == 0):
+            _check(st, self._engine._h)
+        n = got.value
+        if device:
+            torch = _torch()
+            dev = torch.device("cuda", self._engine._device)
+            keys = torch.empty((n,), dtype=torch.int64, device=dev)
+            depth = torch.empty((n,), dtype=torch.int32, device=dev)
+            value = torch.empty((n,), dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            ptr = [a.data_ptr() if n else None for a in (keys, depth, value)]
+        else:
+            keys, depth, value = np.empty(n, np.uint64), np.empty(n, np.int32), np.empty(n, np.float32)
+            ptr = [a.ctypes.data if n else None for a in (keys, depth, value)]
+        _check(call(self._t, lo.ctypes.data, hi.ctypes.data, int(max_depth), ptr[0], ptr[1], ptr[2], n, ctypes.byref(got)), self._engine._h)
+        return keys[:got.value], depth[:got.value], value[:got.value]
+
+    def leaves_bbx(self, lo, hi, max_depth=0):
+        """octomap's begin_leafs_bbx(min, max, max_depth) -> (centre keys uint64, depths int32, values float32) as numpy arrays in
+        octomap's iteration order. lo / hi: three integer keys each (both ends inclusive), or three floats each (the point
+        form: a corner without a key visits nothing)."""
+        return self._leaves_bbx(lo, hi, max_depth, False)
+
+    def leaves_bbx_device(self, lo, hi, max_depth=0):
+        """The same as torch CUDA tensors: keys int64, depths int32, values float32."""
+        return self._leaves_bbx(lo, hi, max_depth, True)
+
+    def _unknown(self, pmin, pmax, depth, device):
+        lo = np.ascontiguousarray(np.asarray(pmin, np.float32).reshape(3))
+        hi = np.ascontiguousarray(np.asarray(pmax, np.float32).reshape(3))
+        call = self._L.sbm_occ_unknown_device if device else self._L.sbm_occ_unknown
+        got = ctypes.c_size_t()
+        st = call(self._t, lo.ctypes.data, hi.ctypes.data, int(depth), None, 0, ctypes.byref(got))       # the count
+        if st not in (0, -2) or (st == -2 and got.value == 0):
+            _check(st, self._engine._h)
+        n = got.value
+        if device:
+            torch = _torch()
+            dev = torch.device("cuda", self._engine._device)
+            xyz = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            ptr = xyz.data_ptr() if n else None
+        else:
+            xyz = np.empty((n, 3), np.float32)
+            ptr = xyz.ctypes.data if n else None
+        _check(call(self._t, lo.ctypes.data, hi.ctypes.data, int(depth), ptr, n, ctypes.byref(got)), self._engine._h)
+        return xyz[:got.value]
+
+    def unknown_centers(self, pmin, pmax, depth=0):
+        """octomap's getUnknownLeafCenters(centres, pmin, pmax, depth) -> (n, 3) float32 numpy array in octomap's push order."""
+        return self._unknown(pmin, pmax, depth, False)
+
+    def unknown_centers_device(self, pmin, pmax, depth=0):
+        """The same as a torch CUDA float32 tensor."""
+        return self._unknown(pmin, pmax, depth, True)
+
+    def metric_min_max(self):
+        """octomap's getMetricMin and getMetricMax -> (min, max), float64 arrays of three; six zeros for an empty tree."""
+        lo, hi = np.zeros(3, np.float64), np.zeros(3, np.float64)
+        _check(self._L.sbm_occ_metric(self._t, lo.ctypes.data, hi.ctypes.data), self._engine._h)
+        return lo, hi
+
+    def metric_size(self):
+        """octomap's getMetricSize: max - min per axis."""
+        lo, hi = self.metric_min_max()
+        return np.array([hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]], np.float64)
+
+    def volume(self):
+        """octomap's volume(): x * y * z of the metric size."""
+        x, y, z = (float(v) for v in self.metric_size())
+        return x * y * z
 
     def binary(self):
         """The body of the .bt stream (a MAXLIKELIHOOD tree) as a torch CUDA uint8 tensor: two bytes per non-leaf node."""

@@ -87,6 +87,74 @@ SBM_OCC_HD bool occ_key_in_box(unsigned long long key, const unsigned kmin[3], c
   return k0 >= kmin[0] && k0 <= kmax[0] && k1 >= kmin[1] && k1 <= kmax[1] && k2 >= kmin[2] && k2 <= kmax[2];
 }
 
+// The planners' host arithmetic (sbm_occ_planner.hip; tools/occupancy_planner_sanitize.cpp runs it under the sanitizers), octomap's
+// own statements in double and float. A translation unit that uses it is built without contraction.
+constexpr size_t kOccUnknownMaxCells = (size_t)1 << 30;
+// keyToCoord(key, depth), OcTreeBaseImpl.hxx:394-405: the root, the voxels, between
+inline double occ_key_to_coord(unsigned key, int depth, double resolution) {
+  if (depth == 0) return 0.0;
+  if (depth == 16) return ((double)((int)key - 32768) + 0.5) * resolution;
+  const double span = (double)(1 << (16 - depth));
+  return (__builtin_floor(((double)key - 32768.0) / span) + 0.5) * (resolution * span);   // getNodeSize(depth) is resolution * span
+}
+// The UNCHECKED coordToKey(coordinate, depth) of OcTreeBaseImpl.hxx:297-306 before its cast to 16 bits, which wraps there. false
+// where the key leaves 0..65535 (a NaN among them): the divergence include/sbm.h states
+inline bool occ_coord_to_key_at(double factor, float coord, int depth, unsigned* key) {
+  const double f = __builtin_floor(factor * (double)coord);
+  if (!(f >= -32768.0 && f < 32768.0)) return false;
+  const int diff = 16 - depth, keyval = (int)f;
+  const int k = diff ? (keyval & ~((1 << diff) - 1)) + (1 << (diff - 1)) + 32768 : keyval + 32768;   // (keyval >> diff) << diff
+  if (k < 0 || k > 65535) return false;
+  *key = (unsigned)k;
+  return true;
+}
+// getUnknownLeafCenters up to its loops (OcTreeBaseImpl.hxx:1046-1062): the clamped lower corner, the step and the step counts.
+// A count that is negative or NaN (pmax below pmin on an axis; octomap's cast to unsigned is undefined there) is 0.
+struct OccUnknownPlan {
+  float lo[3], step;
+  uint32_t steps[3];
+};
+inline int occ_unknown_plan(double resolution, const float pmin[3], const float pmax[3], int depth, OccUnknownPlan* p) {
+  if (depth < 0 || depth > 16) return SBM_ERR_SIZE;
+  depth = depth ? depth : 16;
+  const double factor = 1. / resolution;
+  p->step = (float)(resolution * (double)(1 << (16 - depth)));   // resolution * pow(2, tree_depth - depth)
+  size_t cells = 1;
+  float hi[3];
+  for (int a = 0; a < 3; a++) {
+    unsigned klo, khi;
+    if (!occ_coord_to_key_at(factor, pmin[a], depth, &klo) || !occ_coord_to_key_at(factor, pmax[a], depth, &khi)) return SBM_ERR_SIZE;
+    p->lo[a] = (float)occ_key_to_coord(klo, depth, resolution);
+    hi[a] = (float)occ_key_to_coord(khi, depth, resolution);
+  }
+  for (int a = 0; a < 3; a++) {
+    const float diff = hi[a] - p->lo[a];
+    const float n = __builtin_floorf(diff / p->step);
+    p->steps[a] = n >= 1.0f && n <= 65536.0f ? (uint32_t)n : 0u;   // two keys of 0..65535 are never further apart
+    cells *= p->steps[a];                                          // at most 2^48
+  }
+  return cells > kOccUnknownMaxCells ? SBM_ERR_UNSUPPORTED : SBM_OK;
+}
+// One axis of its loops: out[i] is the running float sum after i + 1 increments, which is what the loop asks and reports
+inline void occ_unknown_axis(float start, float step, uint32_t n, float* out) {
+  volatile float p = start;   // every sum is rounded to float before the next
+  for (uint32_t i = 0; i < n; i++) {
+    p = p + step;
+    out[i] = p;
+  }
+}
+// getMetricMin / getMetricMax (the const forms, OcTreeBaseImpl.hxx:959-1013) from the smallest and largest centre key among the
+// leaves of one depth: keyToCoord is non-decreasing in the key, and so are its rounded sums with the depth's half size, so the
+// extreme keys of a depth give that depth's extreme bounds, bit for bit. lo / hi come in with what the depths so far gave.
+inline void occ_metric_fold(int depth, const unsigned kmin[3], const unsigned kmax[3], double resolution, double lo[3], double hi[3]) {
+  const double half = (resolution * (double)(1 << (16 - depth))) / 2.0;
+  for (int a = 0; a < 3; a++) {
+    const double x = occ_key_to_coord(kmin[a], depth, resolution) - half, y = occ_key_to_coord(kmax[a], depth, resolution) + half;
+    if (x < lo[a]) lo[a] = x;
+    if (y > hi[a]) hi[a] = y;
+  }
+}
+
 #ifdef __HIP__
 constexpr unsigned long long kOccEmpty = ~0ull;
 constexpr uint32_t kOccMaxProbe = 1024;
@@ -227,6 +295,16 @@ __device__ __forceinline__ unsigned occ_wave_append(bool take, unsigned* counter
   return base + __popcll(taking & ((1ull << lane) - 1));
 }
 
+// The wavefront's minimum / maximum in every lane. EVERY lane of the wavefront has to reach the call.
+__device__ __forceinline__ unsigned occ_wave_min(unsigned v) {
+  for (int o = 32; o; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o));
+  return v;
+}
+__device__ __forceinline__ unsigned occ_wave_max(unsigned v) {
+  for (int o = 32; o; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
+  return v;
+}
+
 // A move of the table (sbm_occ_grow.hip: into a larger one; sbm_occ_edit.hip: into one of the same size without the removed slots)
 struct OccRehash {
   const unsigned long long* old_keys;
@@ -312,6 +390,16 @@ int occ_set_overflow(sbm_occ_map* map, unsigned long long value);       // in st
 int occ_claim_launch(sbm_occ_map* map, const int16_t* d_disp, const OccGeom& g, const sbm_stereo_model* model, const float* poses, int m);
 OccLevel occ_tree_level(const sbm_occ_tree* t, int d);   // these two are in sbm_occ_tree.hip: depth d of a built tree (empty levels for
 int occ_tree_stats(sbm_occ_tree* t);                     // one that is not), and the counts of the last build into t->host, read once
+// A selection of n of the tree's nodes as (first Morton code of the cube, where the node is) pairs appended at the tree's cursor
+// (occ_tree_select_kernel and its siblings), between these two: begin places the sort's arrays beside d_keys / d_depth and zeroes
+// the cursor, end sorts the pairs and turns them in place into centre keys, depths and values
+struct OccSelection {
+  unsigned long long* kk[2];
+  unsigned* vv[2];
+  uint32_t n;
+};
+int occ_tree_select_begin(sbm_occ_tree* t, uint32_t n, unsigned long long* d_keys, int* d_depth, OccSelection* s);
+int occ_tree_select_end(sbm_occ_tree* t, const OccSelection& s, unsigned* d_value);
 // The radix sort's second key / payload arrays for n pairs in the handle's sort buffer and, where asked, a first payload array
 inline hipError_t occ_sort_carve(sbm_handle* h, size_t n, unsigned long long** keys, unsigned** vals, unsigned** first_vals = nullptr) {
   return carve(h->occ.sort, h->stream, [&](Carve& c) {
@@ -415,6 +503,8 @@ struct sbm_occ_tree {
   sbm_occ_map* map;            // read by a build only
   bool built, have_stats;      // levels are valid; `host` holds the last build's counts
   bool ot_ranked;              // `ot` holds this build's pre-order ranks: filled by the first .ot call after a build
+  bool have_metric;            // `metric` holds this build's metric bounds (sbm_occ_planner.hip): filled by the first call after a build
+  double metric[6];            // min x y z, max x y z
   int reading;
   double resolution;
   unsigned cmax;               // float bits of clamp max, what .bt calls occupied

@@ -17,15 +17,6 @@
 
 namespace sbm {
 
-__device__ __forceinline__ unsigned occ_wave_min(unsigned v) {
-  for (int o = 32; o; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o));
-  return v;
-}
-__device__ __forceinline__ unsigned occ_wave_max(unsigned v) {
-  for (int o = 32; o; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
-  return v;
-}
-
 struct OccReading {   // how a stored word becomes a leaf's value
   int max_likelihood, hits;
   float thres;
@@ -320,6 +311,7 @@ static int occ_tree_build_run(sbm_occ_tree* t, int reading, const sbm_occ_ray_pa
   t->built = false;
   t->have_stats = false;
   t->ot_ranked = false;
+  t->have_metric = false;
   t->reading = reading;
   t->resolution = map->p.resolution;
   memset(t->count, 0, sizeof(t->count));
@@ -460,29 +452,43 @@ static int occ_tree_leaves_run(sbm_occ_tree* t, int max_depth, unsigned long lon
   if (total > cap) return SBM_ERR_SIZE;
   const uint32_t n = (uint32_t)total;
   return occ_timed_run(h, kOccTreeQuery, n > 0, 1, [&]() -> int {
-    const uint32_t tiles = (n + kOccTile - 1) / kOccTile;
-    unsigned long long* kk[2] = {d_keys};
-    unsigned* vv[2] = {(unsigned*)d_depth};
-    HIPCHK(h, occ_sort_carve(h, n, &kk[1], &vv[1]));
-    HIPCHK(h, h->occ.hist.grow((size_t)256 * tiles * 4, h->stream));
+    OccSelection s;
+    int st = occ_tree_select_begin(t, n, d_keys, d_depth, &s);
+    if (st != SBM_OK) return st;
     OccTreeStats* stats = t->stats.as<OccTreeStats>();
-    HIPCHK(h, hipMemsetAsync(&stats->cursor, 0, sizeof(unsigned), h->stream));
-    OccTreeRef ref;
-    memset(&ref, 0, sizeof(ref));
-    ref.leaf_val = occ_tree_level(t, kOccDepth).val;
-    ref.node_val = occ_tree_level(t, 0).val;
-    for (int d = 0; d < kOccDepth; d++) ref.off[d] = (uint32_t)t->off[d];
     for (int d = 0; d <= max_depth; d++) {
       const OccLevel l = occ_tree_level(t, d);
       const unsigned tag = d == kOccDepth ? 0u : kOccInnerTag | (unsigned)t->off[d];
-      hipLaunchKernelGGL(occ_tree_select_kernel, dim3((l.n + 255) / 256), dim3(256), 0, h->stream, l, d, max_depth, tag, n, kk[0], vv[0], stats);
+      hipLaunchKernelGGL(occ_tree_select_kernel, dim3((l.n + 255) / 256), dim3(256), 0, h->stream, l, d, max_depth, tag, n, s.kk[0], s.vv[0], stats);
       HIPCHK(h, hipGetLastError());
     }
-    const int st = occ_sort_run(h, kk, vv, n, h->occ.hist.as<unsigned>());
-    if (st != SBM_OK) return st;
-    hipLaunchKernelGGL(occ_tree_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, d_keys, d_depth, d_value, n, ref);
-    return SBM_OK;
+    return occ_tree_select_end(t, s, d_value);
   });
+}
+
+int occ_tree_select_begin(sbm_occ_tree* t, uint32_t n, unsigned long long* d_keys, int* d_depth, OccSelection* s) {
+  sbm_handle* h = t->h;
+  const uint32_t tiles = (n + kOccTile - 1) / kOccTile;
+  s->n = n;
+  s->kk[0] = d_keys;
+  s->vv[0] = (unsigned*)d_depth;
+  HIPCHK(h, occ_sort_carve(h, n, &s->kk[1], &s->vv[1]));
+  HIPCHK(h, h->occ.hist.grow((size_t)256 * tiles * 4, h->stream));
+  HIPCHK(h, hipMemsetAsync(&t->stats.as<OccTreeStats>()->cursor, 0, sizeof(unsigned), h->stream));
+  return SBM_OK;
+}
+
+int occ_tree_select_end(sbm_occ_tree* t, const OccSelection& s, unsigned* d_value) {
+  sbm_handle* h = t->h;
+  OccTreeRef ref;
+  memset(&ref, 0, sizeof(ref));
+  ref.leaf_val = occ_tree_level(t, kOccDepth).val;
+  ref.node_val = occ_tree_level(t, 0).val;
+  for (int d = 0; d < kOccDepth; d++) ref.off[d] = (uint32_t)t->off[d];
+  const int st = occ_sort_run(h, s.kk, s.vv, s.n, h->occ.hist.as<unsigned>());
+  if (st != SBM_OK) return st;
+  hipLaunchKernelGGL(occ_tree_gather_kernel, dim3((s.n + 255) / 256), dim3(256), 0, h->stream, s.kk[0], (int*)s.vv[0], d_value, s.n, ref);
+  return SBM_OK;
 }
 
 static int occ_tree_binary_run(sbm_occ_tree* t, uint8_t* d_bytes, size_t cap, size_t* nbytes) {
