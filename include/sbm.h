@@ -1484,7 +1484,8 @@ int sbm_occ_read_binary(sbm_occ_map* map, const char* path, const sbm_occ_ray_pa
  *  leaf count, voxel total) is the load's only wait besides the upload. Every loop there has a bound that does not depend on the
  *  stream. The expansion is the .bt loader's with the leaf's float as the stored word. Streams of more than 2^28 records, and
  *  every stream with SBM_OCC_OT_HOST_PARSE=1, take the one-pass host parser of sbm_occ_ot_info instead: same maps, same codes.
- *  Not provided: ColorOcTree / OcTreeStamped streams, the legacy headers, an .ot of a MAXLIKELIHOOD tree.
+ *  Not provided: OcTreeStamped streams, the legacy headers, an .ot of a MAXLIKELIHOOD tree. A ColorOcTree stream is refused by
+ *  these calls and written and read by sbm_occ_color_ot_* ("colour per voxel" below).
  *  sbm_get_profile: "occ_tree_query", ms of the last body call (the ranking included when it ran); "occ_load", ms of the last
  *  load on the device: the parse (where it ran there, its upload included), the reset and the expansion; a refused load leaves
  *  the time of the last one. */
@@ -1865,6 +1866,116 @@ int sbm_occ_ray_intersections_device(sbm_occ_map* map, size_t n, const void* ori
 /* The same on HOST memory. Synchronous. */
 int sbm_occ_ray_intersections(sbm_occ_map* map, size_t n, const float* origins, int shared_origin, const float* dirs, const float* centres,
                               double delta, float* xyz, int32_t* found);
+
+/* ---- occupancy map: colour per voxel (ColorOcTree::setNodeColor, averageNodeColor; ColorOcTree.cpp:96-105, 146-161) -----------
+ * A colour beside the log-odds of every voxel, as octomap's ColorOcTree keeps one per node: the coloured map a camera builds.
+ * tests/occupancy_color_cases.py is a literal transcription of this text and tests/golden/occupancy_color.npz holds what the
+ * reference's own octomap answered, which the device equals in every integer.
+ *  Storage. One 32-bit word per slot, r | g << 8 | b << 16 (the top byte is zero). "Not set" is octomap's own convention: white
+ *  (255, 255, 255) is isColorSet() == false, and there is no separate flag, so white given as a colour UNSETS the voxel. Colour
+ *  exists in the log-odds mode only: every call below answers SBM_ERR_UNSUPPORTED on a hit map. The words are allocated at the
+ *  first call that writes colours (sbm_occ_color_keys* / sbm_occ_color_points*), as the change bytes are at the first enable;
+ *  such a call fixes the mode of a fresh map to log-odds, as an edit does, so that a hit insert after it is refused; a
+ *  map that never makes such a call allocates nothing and launches exactly what it launched before, and the reads below answer
+ *  white for every voxel of it.
+ *  What moves or drops a slot carries or drops its colour: growth and the deletes' move carry the word with the key;
+ *  sbm_occ_reset and the .bt / .ot loaders leave every voxel white; a voxel created by an insert or an edit is white, and so is
+ *  one that was deleted and created again, also inside ONE edit batch (delete then set of a coloured voxel: the edit's APPLY
+ *  stores white where a run passes through a delete and ends present, since no move drops that slot).
+ *  The batch. Item i is (key or point, rgb word; the word's top byte is ignored). Both ops search(key) first: an item whose
+ *  voxel is unknown does nothing. A packed key with a bit above 47 set, and a point outside the key space (coordToKeyChecked
+ *  fails; a NaN among them), is skipped.
+ *   SBM_OCC_COLOR_SET      setNodeColor: the voxel's colour is the item's.
+ *   SBM_OCC_COLOR_AVERAGE  averageNodeColor: if the voxel is white the item's colour, else per channel (prev + new) / 2 in int
+ *                          (truncating). The result depends on the order, and a chain that passes through white starts over.
+ *  The op is per call. The items of one voxel take effect in item order, calls in call order; items of different voxels do not
+ *  interact. n is up to 2^30, worked through in chunks of SBM_OCC_EDIT_CHUNK items in item order.
+ *  Device. One lane per item looks its slot up (a look-up, never a claim); the map's stable radix sort of (key, item index)
+ *  brings each voxel's items together in item order; one lane per run head -- found from the sorted keys, not from lane position
+ *  -- walks its run sequentially from the slot's word to its final one, whatever the run's length (no closed form: the white
+ *  restart breaks it), and stores it with a plain vector store. No atomics on colour words.
+ *  DIVERGENCE, pruning during inserts. octomap with lazy_eval = false prunes and re-expands while it inserts; pruneNode and
+ *  expandNode smear colours through copyData, and which transient prunes happen depends on the iteration order of an
+ *  unordered_set. Here a colour belongs to ONE depth-16 voxel and is never smeared: the recordings drive octomap with lazy_eval =
+ *  true inserts (no pruning during inserts) and colour by key on the unpruned tree. For the same reason, after octomap reads a
+ *  pruned stream a colour call there colours a whole pruned leaf where this map colours one voxel, unless expand() is called first.
+ *  Not provided: integrateNodeColor. It needs a double exp per voxel, and (uint8_t)(prev * p + r * (0.99 - p)) with prev == r
+ *  sits on an integer boundary; whether the device's exp equals glibc's in every bit has not been measured and cannot be
+ *  assumed. Not provided either: OcTreeStamped, colour in hit mode, writeColorHistogram, and a colour argument on the insert
+ *  calls: the caller colours after inserting, as octomap's users do.
+ *  The tree. ColorOcTree::isNodeCollapsible ignores colour, so the pruned tree has the structure of the plain tree ("the octree
+ *  above the voxels"); an sbm_occ_tree built over a map that has colours gets a colour word per node, octomap's after prune();
+ *  updateInnerOccupancy(), in one bottom-up pass over the levels the build has. getAverageChildColor() is int sums of r, g, b over
+ *  the children whose colour is SET, each divided by their count (truncating), or white if none is set. A node that is not
+ *  collapsed takes it (updateColorChildren). A collapsed node takes child 0's colour (copyData) and, if that is set, replaces it
+ *  by getAverageChildColor(): so a collapsed node whose child 0 is white is white even if its siblings are coloured. Bottom-up, a
+ *  node over collapsed children uses their collapsed colours. The pass runs only when the map has colours: the build over a
+ *  colourless map is unchanged, and its nodes answer white. sbm_occ_color_leaves* is sbm_occ_tree_leaves* with the colour word of
+ *  every entry, in the same order, for both readings; the colour of an entry is found by a binary search over its depth's codes.
+ *  The stream. AbstractOcTree::write with `id ColorOcTree`: the .ot header with that id line, then eight bytes per node of the
+ *  pruned LOGODDS tree in pre-order -- the float value, r, g, b, the child mask (0 for a leaf) -- written on the device by the
+ *  ranks of the plain .ot writer as two dwords per node. Loading (AbstractOcTree::read) parses on the host in one pass, as the
+ *  .bt loader does, and expands on the device: every voxel of a leaf's cube takes the leaf's float, unclamped, and the leaf's
+ *  colour. Status and refusals are those of "the .ot format" with eight bytes per record; a stream whose id is not ColorOcTree
+ *  (a plain OcTree among them) is SBM_ERR_UNSUPPORTED, as sbm_occ_ot_* keep refusing `id ColorOcTree`; a refused stream leaves
+ *  the map as it was. An inner node's colour in a stream is read and dropped, as its value is.
+ *  sbm_get_profile: no new names. The batch is timed under "occ_rays_apply", the search under "occ_search", the fetch under
+ *  "occ_fetch" (DESIGN.md section 29). */
+enum { SBM_OCC_COLOR_SET = 0, SBM_OCC_COLOR_AVERAGE = 1 };
+#define SBM_OCC_COLOR_WHITE 0x00FFFFFFu
+typedef struct sbm_occ_color_info {
+  uint64_t items;    /* of the last colour batch                                              */
+  uint64_t found;    /* items whose voxel exists: they took effect                            */
+  uint64_t unknown;  /* items with a valid key whose voxel is unknown: no-ops                 */
+  uint64_t skipped;  /* items without a key: a bit above 47, or a point outside the key space */
+} sbm_occ_color_info;
+/* n items in item order: d_keys n packed keys (8-byte aligned), d_rgb n colour words (4-byte aligned), in DEVICE memory. op is
+ * SBM_OCC_COLOR_*. Asynchronous on the handle's stream unless sync != 0. Checked in this order before anything is launched:
+ * SBM_ERR_NULL (the arrays may be NULL only for n == 0); SBM_ERR_UNSUPPORTED for another op, more than 2^30 items, a hit map or a
+ * misaligned pointer. SBM_ERR_NOMEM where the colour words cannot be allocated: the map is as it was. */
+int sbm_occ_color_keys_device(sbm_occ_map* map, size_t n, const void* d_keys, const void* d_rgb, int op, int sync);
+/* The same on HOST memory. Synchronous. */
+int sbm_occ_color_keys(sbm_occ_map* map, size_t n, const uint64_t* keys, const uint32_t* rgb, int op);
+/* The same by points: d_xyz n float triples (4-byte aligned); a point's key is coordToKeyChecked's. */
+int sbm_occ_color_points_device(sbm_occ_map* map, size_t n, const void* d_xyz, const void* d_rgb, int op, int sync);
+int sbm_occ_color_points(sbm_occ_map* map, size_t n, const float* xyz, const uint32_t* rgb, int op);
+/* Synchronises and returns the counts of the last colour batch (zeros before the first). SBM_ERR_NULL; *out is written only on
+ * SBM_OK. */
+int sbm_occ_color_last(sbm_occ_map* map, sbm_occ_color_info* out);
+/* sbm_occ_search_device with a colour: d_color n colour words (may be NULL, as d_value may). An unknown voxel and a point
+ * outside the key space answer SBM_OCC_COLOR_WHITE and the quiet NaN 0x7FC00000. Read-only; it allocates nothing. The checks are
+ * sbm_occ_search_device's, and SBM_ERR_UNSUPPORTED on a hit map. */
+int sbm_occ_color_search_device(sbm_occ_map* map, size_t n, const void* d_xyz, float occupancy_thres_log, void* d_state, void* d_value,
+                                void* d_color, int sync);
+/* The same on HOST memory. Synchronous. */
+int sbm_occ_color_search(sbm_occ_map* map, size_t n, const float* xyz, float occupancy_thres_log, int32_t* state, void* value,
+                         uint32_t* color);
+/* sbm_occ_fetch_logodds_device with the colours: the voxels in ascending order of their packed keys, d_logodds and d_colors cap
+ * 4-byte words each (either may be NULL). Same cap / *count / SBM_ERR_SIZE / SBM_ERR_OCC_FULL rule. Read-only. */
+int sbm_occ_color_fetch_device(sbm_occ_map* map, void* d_keys, void* d_logodds, void* d_colors, size_t cap, size_t* count);
+int sbm_occ_color_fetch(sbm_occ_map* map, uint64_t* keys, float* logodds, uint32_t* colors, size_t cap, size_t* count);
+/* sbm_occ_tree_leaves_device with d_color, cap colour words in DEVICE memory, 4-byte aligned (NULL: exactly that call). Same
+ * entries, order, checks and cap / *count rule. Synchronous. */
+int sbm_occ_color_leaves_device(sbm_occ_tree* tree, int max_depth, void* d_keys, void* d_depth, void* d_value, void* d_color, size_t cap,
+                                size_t* count);
+/* The same on HOST memory; value may be NULL, color not. */
+int sbm_occ_color_leaves(sbm_occ_tree* tree, int max_depth, uint64_t* keys, int32_t* depth, float* value, uint32_t* color, size_t cap,
+                         size_t* count);
+/* The ColorOcTree body of a LOGODDS tree into d_bytes (DEVICE memory, 4-byte aligned, cap bytes); *nbytes receives its length,
+ * 8 * nodes; the rules of sbm_occ_ot_body_device. */
+int sbm_occ_color_ot_body_device(sbm_occ_tree* tree, void* d_bytes, size_t cap, size_t* nbytes);
+/* tree.write(path) of a ColorOcTree: the header, then that body. The codes of sbm_occ_ot_write. */
+int sbm_occ_color_ot_write(sbm_occ_tree* tree, const char* path);
+/* Plain host code, no GPU: sbm_occ_ot_info and sbm_occ_ot_leaves for a ColorOcTree stream, the leaves with their colour words. */
+int sbm_occ_color_ot_info(const void* bytes, size_t n, sbm_occ_ot_header* out);
+int sbm_occ_color_ot_leaves(const void* bytes, size_t n, uint64_t* first_key, int32_t* depth, float* value, uint32_t* color, size_t cap,
+                            size_t* count);
+/* AbstractOcTree::read of a ColorOcTree stream from n bytes in HOST memory, read before the call returns: the map's content is
+ * replaced by the stream's voxels and their colours. Synchronous whatever `sync` says (the parse is the host's). The codes of
+ * sbm_occ_ot_load. */
+int sbm_occ_color_ot_load(sbm_occ_map* map, const void* bytes, size_t n, int sync);
+/* The same from a file; SBM_ERR_UNSUPPORTED when it cannot be opened or read. */
+int sbm_occ_color_ot_read(sbm_occ_map* map, const char* path, int sync);
 
 /* ---- visual-word dictionary: addNewWords, computeLikelihood, limitKeypoints ---------------------------------------------------
  * The reference's loop-closure thread, started by Mapper::process for each key frame: addWordIds -> VWDictionary::addNewWords

@@ -138,6 +138,16 @@ class OccupancyTree {
   void writeBinary(const std::string& path) { check(sbm_occ_tree_write_binary(t_, path.c_str())); }
   // tree.write(path) of a SBM_OCC_TREE_LOGODDS tree: the .ot file, every node's float
   void write(const std::string& path) { check(sbm_occ_ot_write(t_, path.c_str())); }
+  // ColorOcTree: begin_leafs(maxDepth) with every entry's colour word (r | g << 8 | b << 16; white: none set), octomap's after
+  // prune(); updateInnerOccupancy(), and tree.write(path) with `id ColorOcTree`
+  std::vector<OccupancyLeaf> leavesColors(std::vector<uint32_t>& colors, unsigned max_depth = 0) {
+    return listed([&](uint64_t* k, int32_t* d, float* v, size_t cap, size_t* n) {   // a count, then one listing with the colours
+      if (cap) colors.assign(cap, SBM_OCC_COLOR_WHITE);
+      else colors.clear();
+      return sbm_occ_color_leaves(t_, (int)max_depth, k, d, v, cap ? colors.data() : nullptr, cap, n);
+    });
+  }
+  void writeColor(const std::string& path) { check(sbm_occ_color_ot_write(t_, path.c_str())); }
 
  private:
   static void check(int st) {
@@ -442,6 +452,54 @@ class OccupancyMap {
     return true;
   }
 
+  // ---- ColorOcTree: a colour per voxel of a log-odds map (include/sbm.h, "occupancy map: colour per voxel") ----------------------
+  // tree.setNodeColor(key, r, g, b) / averageNodeColor(key, r, g, b): true where octomap returns the node, false where its search
+  // finds none (nothing happens then). White (255, 255, 255) is "no colour set". integrateNodeColor is not provided.
+  static uint32_t packColor(uint8_t r, uint8_t g, uint8_t b) { return (uint32_t)r | (uint32_t)g << 8 | (uint32_t)b << 16; }
+  bool setNodeColor(uint64_t key, uint8_t r, uint8_t g, uint8_t b) { return colorOne(&key, nullptr, packColor(r, g, b), SBM_OCC_COLOR_SET); }
+  bool setNodeColor(const float point[3], uint8_t r, uint8_t g, uint8_t b) { return colorOne(nullptr, point, packColor(r, g, b), SBM_OCC_COLOR_SET); }
+  bool averageNodeColor(uint64_t key, uint8_t r, uint8_t g, uint8_t b) { return colorOne(&key, nullptr, packColor(r, g, b), SBM_OCC_COLOR_AVERAGE); }
+  bool averageNodeColor(const float point[3], uint8_t r, uint8_t g, uint8_t b) {
+    return colorOne(nullptr, point, packColor(r, g, b), SBM_OCC_COLOR_AVERAGE);
+  }
+  // batches in item order: the loop a user writes over a coloured cloud, in one call
+  void setNodeColor(const std::vector<uint64_t>& keys, const std::vector<uint32_t>& colors) {
+    if (keys.size() != colors.size()) throw Error(SBM_ERR_SIZE, "setNodeColor: keys and colors differ in length");
+    check(sbm_occ_color_keys(m_, keys.size(), keys.data(), colors.data(), SBM_OCC_COLOR_SET));
+  }
+  void averageNodeColor(const std::vector<uint64_t>& keys, const std::vector<uint32_t>& colors) {
+    if (keys.size() != colors.size()) throw Error(SBM_ERR_SIZE, "averageNodeColor: keys and colors differ in length");
+    check(sbm_occ_color_keys(m_, keys.size(), keys.data(), colors.data(), SBM_OCC_COLOR_AVERAGE));
+  }
+  void setNodeColor(const float* xyz, size_t n, const uint32_t* colors) { check(sbm_occ_color_points(m_, n, xyz, colors, SBM_OCC_COLOR_SET)); }
+  void averageNodeColor(const float* xyz, size_t n, const uint32_t* colors) { check(sbm_occ_color_points(m_, n, xyz, colors, SBM_OCC_COLOR_AVERAGE)); }
+  sbm_occ_color_info lastColor() {
+    sbm_occ_color_info i;
+    check(sbm_occ_color_last(m_, &i));
+    return i;
+  }
+  // tree.search(x, y, z) of a ColorOcTree: the state, and the node's log-odds and colour word (white where there is no node)
+  int search(float x, float y, float z, float* logodds, uint32_t* color) {
+    const float p[3] = {x, y, z};
+    int32_t state = 0;
+    check(sbm_occ_color_search(m_, 1, p, occupancyThresLog(), &state, logodds, color));
+    return state;
+  }
+  void search(const float* xyz, size_t n, int32_t* states, void* values, uint32_t* colors) {
+    check(sbm_occ_color_search(m_, n, xyz, occupancyThresLog(), states, values, colors));
+  }
+  // tree.write(path) of a ColorOcTree as the map is now, and AbstractOcTree::read of one: every voxel its leaf's float and colour.
+  // octomap colours a whole pruned leaf after read() where this map colours one voxel, unless expand() is called there first.
+  void writeColor(const std::string& path) { buildTree(SBM_OCC_TREE_LOGODDS)->writeColor(path); }
+  bool readColor(const std::string& filename) {
+    check(sbm_occ_color_ot_read(m_, filename.c_str(), 1));
+    return true;
+  }
+  bool readColor(const void* bytes, size_t n) {
+    check(sbm_occ_color_ot_load(m_, bytes, n, 1));
+    return true;
+  }
+
   // ---- queries: the map is not changed ---------------------------------------------------------------------------------------
   // The threshold of isNodeOccupied for a log-odds map: logodds(rayParams().occupancy_thres)
   float occupancyThresLog() const {
@@ -543,6 +601,10 @@ class OccupancyMap {
     q.occupancy_thres_log = occupancyThresLog();
     q.ignore_unknown = ignoreUnknownCells ? 1 : 0;
     return q;
+  }
+  bool colorOne(const uint64_t* key, const float* point, uint32_t color, int op) {
+    check(key ? sbm_occ_color_keys(m_, 1, key, &color, op) : sbm_occ_color_points(m_, 1, point, &color, op));
+    return lastColor().found == 1;
   }
   float hitOrMiss(bool occupied) const {
     float c[5];

@@ -182,6 +182,14 @@ class OccEditInfo(ctypes.Structure):
                 ("removed", ctypes.c_uint64)]
 
 
+class OccColorInfo(ctypes.Structure):
+    """`sbm_occ_color_info` of include/sbm.h: what sbm_occ_color_last reports of the last colour batch."""
+
+    _fields_ = [("items", ctypes.c_uint64), ("found", ctypes.c_uint64), ("unknown", ctypes.c_uint64), ("skipped", ctypes.c_uint64)]
+
+
+OCC_COLOR_SET, OCC_COLOR_AVERAGE = 0, 1      # SBM_OCC_COLOR_*: the op of a colour batch
+OCC_COLOR_WHITE = 0x00FFFFFF                 # SBM_OCC_COLOR_WHITE: the colour word of a voxel without a colour
 OCC_EDIT_UPDATE, OCC_EDIT_SET, OCC_EDIT_DELETE = 0, 1, 2      # SBM_OCC_EDIT_*: the op of an item
 OCC_EDIT_CHUNK = 2097152                                     # SBM_OCC_EDIT_CHUNK: items per chunk of a large batch
 OCC_OT_FAN, OCC_OT_SCAN_TILE = 16, 1024      # SBM_OCC_OT_FAN, SBM_OCC_OT_SCAN_TILE: the tile constants of the .ot device parse
@@ -457,6 +465,25 @@ def load_library():
     L.sbm_occ_delete.argtypes = [vp, sz, vp, ci]
     L.sbm_occ_delete_box.argtypes = [vp, vp, vp, ci]
     L.sbm_occ_last_edit.argtypes = [vp, ctypes.POINTER(OccEditInfo)]
+    # colour per voxel: batches (keys or points, colour words), the coloured search and fetch
+    L.sbm_occ_color_keys_device.argtypes = [vp, sz, vp, vp, ci, ci]
+    L.sbm_occ_color_keys.argtypes = [vp, sz, vp, vp, ci]
+    L.sbm_occ_color_points_device.argtypes = L.sbm_occ_color_keys_device.argtypes
+    L.sbm_occ_color_points.argtypes = L.sbm_occ_color_keys.argtypes
+    L.sbm_occ_color_last.argtypes = [vp, ctypes.POINTER(OccColorInfo)]
+    L.sbm_occ_color_search_device.argtypes = [vp, sz, vp, ctypes.c_float, vp, vp, vp, ci]
+    L.sbm_occ_color_search.argtypes = [vp, sz, vp, ctypes.c_float, vp, vp, vp]
+    L.sbm_occ_color_fetch_device.argtypes = [vp, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_color_fetch.argtypes = [vp, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    # ... on a tree's nodes, and the ColorOcTree stream
+    L.sbm_occ_color_leaves_device.argtypes = [vp, ci, vp, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_color_leaves.argtypes = [vp, ci, vp, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_color_ot_body_device.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_color_ot_write.argtypes = [vp, ctypes.c_char_p]
+    L.sbm_occ_color_ot_info.argtypes = [vp, sz, ctypes.POINTER(OccOtHeader)]
+    L.sbm_occ_color_ot_leaves.argtypes = [vp, sz, vp, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_color_ot_load.argtypes = [vp, vp, sz, ci]
+    L.sbm_occ_color_ot_read.argtypes = [vp, ctypes.c_char_p, ci]
     # the read side for planners: a box's corners and a ray's shared origin are host memory
     L.sbm_occ_bbx_leaves_device.argtypes = [vp, vp, vp, ci, vp, vp, vp, sz, ctypes.POINTER(sz)]
     L.sbm_occ_bbx_leaves.argtypes = L.sbm_occ_bbx_leaves_device.argtypes

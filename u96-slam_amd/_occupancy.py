@@ -7,7 +7,7 @@ import os
 
 import numpy as np
 
-from ._abi import (ERR_OCC_FULL, OCC_EDIT_CHUNK, OCC_EDIT_DELETE, OCC_EDIT_SET, OCC_EDIT_UPDATE, OccEditInfo, OCC_CELL_FREE, OCC_CELL_OCCUPIED, OCC_CELL_OUT, OCC_CELL_UNKNOWN, OCC_RAY_BOUNDS,  # noqa: F401
+from ._abi import (ERR_OCC_FULL, OCC_COLOR_AVERAGE, OCC_COLOR_SET, OCC_COLOR_WHITE, OccColorInfo, OCC_EDIT_CHUNK, OCC_EDIT_DELETE, OCC_EDIT_SET, OCC_EDIT_UPDATE, OccEditInfo, OCC_CELL_FREE, OCC_CELL_OCCUPIED, OCC_CELL_OUT, OCC_CELL_UNKNOWN, OCC_RAY_BOUNDS,  # noqa: F401
                    OCC_RAY_HIT, OCC_RAY_NONE, OCC_RAY_RANGE, OCC_RAY_UNKNOWN, OCC_TREE_LOGODDS, OCC_TREE_MAXLIKELIHOOD, OccParams,
                    OccBinaryHeader, OccGrowthInfo, OccOtHeader, OccQueryParams, OccRayParams, OccTreeCounts, StereoBMError, _check, _torch, load_library)
 
@@ -118,6 +118,46 @@ def occ_ot_leaves(data):
     if n.value:
         _check(L.sbm_occ_ot_leaves(ptr, len(b), keys.ctypes.data, depth.ctypes.data, value.ctypes.data, n.value, ctypes.byref(n)))
     return keys, depth, value
+
+
+def occ_color_ot_info(data):
+    """occ_ot_info for a ColorOcTree stream (eight bytes per node), parsed on the host (no GPU)."""
+    b = _stream(data)
+    h = OccOtHeader()
+    _check(load_library().sbm_occ_color_ot_info(b.ctypes.data if len(b) else None, len(b), ctypes.byref(h)))
+    return dict(resolution=h.resolution, size=h.size, nodes=h.nodes, leaves=h.leaves, voxels=h.voxels, leaves_at=list(h.leaves_at),
+                value_min=h.value_min, value_max=h.value_max, key_min=list(h.key_min), key_max=list(h.key_max))
+
+
+def occ_color_ot_leaves(data):
+    """The leaves of a ColorOcTree stream in stream order, parsed on the host (no GPU) -> (packed key of each cube's lowest voxel
+    uint64, depth int32, value float32, colour word uint32)."""
+    b = _stream(data)
+    L = load_library()
+    n = ctypes.c_size_t()
+    ptr = b.ctypes.data if len(b) else None
+    st = L.sbm_occ_color_ot_leaves(ptr, len(b), None, None, None, None, 0, ctypes.byref(n))
+    if st != -2 or not n.value:      # -2 with a count: the arrays are too small, as asked
+        _check(st)
+    keys, depth, value, color = np.empty(n.value, np.uint64), np.empty(n.value, np.int32), np.empty(n.value, np.float32), np.empty(n.value, np.uint32)
+    if n.value:
+        _check(L.sbm_occ_color_ot_leaves(ptr, len(b), keys.ctypes.data, depth.ctypes.data, value.ctypes.data, color.ctypes.data, n.value, ctypes.byref(n)))
+    return keys, depth, value, color
+
+
+def occ_color_words(colors):
+    """(n, 3) uint8 r, g, b, or (n,) words -> (n,) uint32 words r | g << 8 | b << 16"""
+    c = np.asarray(colors)
+    if c.ndim == 2:
+        c = c.astype(np.uint32) & np.uint32(255)
+        c = c[:, 0] | c[:, 1] << np.uint32(8) | c[:, 2] << np.uint32(16)
+    return np.ascontiguousarray(c, np.uint32).reshape(-1)
+
+
+def occ_color_rgb(words):
+    """(n,) colour words -> (n, 3) uint8 r, g, b"""
+    w = np.asarray(words).astype(np.uint32)
+    return np.stack([w & 255, w >> 8 & 255, w >> 16 & 255], axis=1).astype(np.uint8)
 
 
 def occ_query_params(max_range=-1.0, occupancy_thres_log=0.0, ignore_unknown=False):
@@ -437,6 +477,109 @@ class OccupancyMap:
         e = OccEditInfo()
         _check(self._L.sbm_occ_last_edit(self._m, ctypes.byref(e)), self._engine._h)
         return dict(items=e.items, skipped=e.skipped, lost=e.lost, created=e.created, removed=e.removed)
+
+    # ---- colour per voxel: octomap's ColorOcTree::setNodeColor and averageNodeColor on batches of items ----------------------------
+    def _color(self, items, colors, op, sync):
+        if isinstance(items, np.ndarray) or not hasattr(items, "data_ptr"):
+            it = np.asarray(items)
+            points = it.ndim == 2
+            it = np.ascontiguousarray(it, np.float32).reshape(-1, 3) if points else np.ascontiguousarray(it, np.uint64).reshape(-1)
+            n = len(it)
+            c = occ_color_words(colors)
+            if len(c) != n:
+                raise StereoBMError(-2, f"{n} items with {len(c)} colours")
+            call = self._L.sbm_occ_color_points if points else self._L.sbm_occ_color_keys
+            _check(call(self._m, n, it.ctypes.data if n else None, c.ctypes.data if n else None, op), self._engine._h)
+            self._engine._inflight.clear()
+            return
+        torch = _torch()
+        points = items.dim() == 2
+        want = torch.float32 if points else torch.int64
+        for t, dtype, what in ((items, want, "items"), (colors, torch.int32, "colors")):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or t.device.index != self._engine._device:
+                raise StereoBMError(-2, f"{what} must be a CUDA {dtype} tensor on the engine's device")
+        it, c = items.contiguous(), colors.contiguous().reshape(-1)
+        n = it.shape[0]
+        if (points and it.shape[1] != 3) or c.shape[0] != n:
+            raise StereoBMError(-2, "items (n,) keys or (n, 3) points, with n colour words")
+        torch.cuda.current_stream(it.device).synchronize()
+        call = self._L.sbm_occ_color_points_device if points else self._L.sbm_occ_color_keys_device
+        _check(call(self._m, n, it.data_ptr() if n else None, c.data_ptr() if n else None, op, 1 if sync else 0), self._engine._h)
+        self._after(sync, (it, c))
+
+    def set_colors(self, items, colors, sync=True):
+        """octomap's setNodeColor(key, r, g, b) per item, in item order. `items` packed keys (n,) or points (n, 3); colors (n, 3)
+        uint8 r, g, b or (n,) words r | g << 8 | b << 16. Both as numpy arrays (the host form, synchronous) or as torch CUDA
+        tensors (keys int64, points float32, colour WORDS int32). An item whose voxel is unknown does nothing; white (255, 255,
+        255) unsets. Log-odds maps only."""
+        self._color(items, colors, OCC_COLOR_SET, sync)
+
+    def average_colors(self, items, colors, sync=True):
+        """octomap's averageNodeColor per item, in item order: the item's colour where the voxel has none, else (prev + new) / 2
+        per channel in int. Arguments as set_colors."""
+        self._color(items, colors, OCC_COLOR_AVERAGE, sync)
+
+    def last_colors(self):
+        """dict: items, found, unknown (a valid key without a voxel), skipped (no key) of the last colour batch. Synchronises."""
+        e = OccColorInfo()
+        _check(self._L.sbm_occ_color_last(self._m, ctypes.byref(e)), self._engine._h)
+        return dict(items=e.items, found=e.found, unknown=e.unknown, skipped=e.skipped)
+
+    def search_colors(self, points, occupancy_thres_log=0.0, sync=True):
+        """search(point) with the voxel's colour, on (n, 3) points: a numpy array -> numpy (int32 states, uint32 value words, uint32
+        colour words), or a torch CUDA float32 tensor -> three torch int32 tensors. An unknown voxel, a point outside the key
+        space and every voxel of a map without colours answer OCC_COLOR_WHITE. occ_color_rgb turns words into (n, 3) uint8."""
+        if isinstance(points, np.ndarray):
+            p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+            n = len(p)
+            state, value, color = np.empty(n, np.int32), np.empty(n, np.uint32), np.empty(n, np.uint32)
+            _check(self._L.sbm_occ_color_search(self._m, n, p.ctypes.data if n else None, float(occupancy_thres_log), state.ctypes.data if n else None,
+                                                value.ctypes.data if n else None, color.ctypes.data if n else None), self._engine._h)
+            return state, value, color
+        torch = _torch()
+        p = self._cuda_f32(points, "points")
+        n = p.shape[0]
+        state, value, color = (torch.empty((n,), dtype=torch.int32, device=p.device) for _ in range(3))
+        torch.cuda.current_stream(p.device).synchronize()
+        _check(self._L.sbm_occ_color_search_device(self._m, n, p.data_ptr() if n else None, float(occupancy_thres_log), state.data_ptr() if n else None,
+                                                   value.data_ptr() if n else None, color.data_ptr() if n else None, 1 if sync else 0), self._engine._h)
+        self._after(sync, (p, state, value, color))
+        return state, value, color
+
+    def fetch_colors(self, allow_overflow=False):
+        """(packed keys uint64 ascending, log-odds float32, colour words uint32) of a log-odds map as numpy arrays."""
+        n = self.size()
+        keys, lo, col = np.empty(n, np.uint64), np.empty(n, np.float32), np.empty(n, np.uint32)
+        got = ctypes.c_size_t()
+        st = self._L.sbm_occ_color_fetch(self._m, keys.ctypes.data if n else None, lo.ctypes.data if n else None, col.ctypes.data if n else None, n,
+                                         ctypes.byref(got))
+        if not (st == ERR_OCC_FULL and allow_overflow):
+            _check(st, self._engine._h)
+        return keys[:got.value], lo[:got.value], col[:got.value]
+
+    def fetch_colors_device(self):
+        """The same as torch CUDA tensors: keys int64, log-odds float32, colour words int32."""
+        torch = _torch()
+        n = self.size()
+        dev = torch.device("cuda", self._engine._device)
+        keys, lo, col = torch.empty((n,), dtype=torch.int64, device=dev), torch.empty((n,), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+        got = ctypes.c_size_t()
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.sbm_occ_color_fetch_device(self._m, keys.data_ptr() if n else None, lo.data_ptr() if n else None, col.data_ptr() if n else None, n,
+                                                  ctypes.byref(got)), self._engine._h)
+        return keys[:got.value], lo[:got.value], col[:got.value]
+
+    def load_color_ot(self, data_or_path, sync=True):
+        """AbstractOcTree::read of a ColorOcTree stream -- bytes (or a uint8 array), or the path of a file: the map's content is
+        replaced by the stream's voxels, each with its leaf's float and its leaf's colour. A plain OcTree stream is refused
+        (load_ot reads that)."""
+        if isinstance(data_or_path, (str, os.PathLike)):
+            st = self._L.sbm_occ_color_ot_read(self._m, os.fsencode(data_or_path), 1 if sync else 0)
+        else:
+            b = _stream(data_or_path)
+            st = self._L.sbm_occ_color_ot_load(self._m, b.ctypes.data if len(b) else None, len(b), 1 if sync else 0)
+        _check(st, self._engine._h)
+        self._engine._inflight.clear()
 
     def load_binary(self, data_or_path, params=None, sync=True, **kw):
         """octomap's readBinary: replace the map's content by the voxels of a .bt stream -- bytes (or a uint8 array), or the
@@ -880,6 +1023,54 @@ class OccupancyTree:
     def write_ot(self, path):
         """tree.write(path) of a LOGODDS tree."""
         _check(self._L.sbm_occ_ot_write(self._t, os.fsencode(path)), self._engine._h)
+
+    # ---- colours: the tree over a map that has them holds octomap's colour per node after prune(); updateInnerOccupancy() ----
+    def leaves_colors(self, max_depth=0):
+        """leaves(max_depth) with the colour word of every entry -> (centre keys uint64, depths int32, values float32, colour
+        words uint32) as numpy arrays in octomap's iteration order. White for every node of a tree built over a colourless map."""
+        n = self._leaf_count(max_depth)
+        keys, depth, value, color = np.empty(n, np.uint64), np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.uint32)
+        got = ctypes.c_size_t()
+        _check(self._L.sbm_occ_color_leaves(self._t, int(max_depth), keys.ctypes.data if n else None, depth.ctypes.data if n else None,
+                                            value.ctypes.data if n else None, color.ctypes.data if n else None, n, ctypes.byref(got)), self._engine._h)
+        return keys[:got.value], depth[:got.value], value[:got.value], color[:got.value]
+
+    def leaves_colors_device(self, max_depth=0):
+        """The same as torch CUDA tensors: keys int64, depths int32, values float32, colour words int32."""
+        torch = _torch()
+        n = self._leaf_count(max_depth)
+        dev = torch.device("cuda", self._engine._device)
+        keys, depth = torch.empty((n,), dtype=torch.int64, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+        value, color = torch.empty((n,), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+        got = ctypes.c_size_t()
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.sbm_occ_color_leaves_device(self._t, int(max_depth), keys.data_ptr() if n else None, depth.data_ptr() if n else None,
+                                                   value.data_ptr() if n else None, color.data_ptr() if n else None, n, ctypes.byref(got)),
+               self._engine._h)
+        return keys[:got.value], depth[:got.value], value[:got.value], color[:got.value]
+
+    def color_ot_body(self):
+        """The body of the ColorOcTree stream (a LOGODDS tree) as a torch CUDA uint8 tensor: eight bytes per node of the pruned tree."""
+        torch = _torch()
+        n = 8 * self.info()["nodes"]
+        out = torch.empty((n,), dtype=torch.uint8, device=torch.device("cuda", self._engine._device))
+        got = ctypes.c_size_t()
+        torch.cuda.current_stream(out.device).synchronize()
+        _check(self._L.sbm_occ_color_ot_body_device(self._t, out.data_ptr() if n else None, n, ctypes.byref(got)), self._engine._h)
+        return out[:got.value]
+
+    def color_ot(self):
+        """The whole ColorOcTree stream of a LOGODDS tree as bytes: the file write_color_ot writes, read back."""
+        import tempfile
+        with tempfile.TemporaryDirectory() as tmp:
+            path = os.path.join(tmp, "tree.ot")
+            self.write_color_ot(path)
+            with open(path, "rb") as f:
+                return f.read()
+
+    def write_color_ot(self, path):
+        """tree.write(path) of a ColorOcTree: `id ColorOcTree`, a LOGODDS tree."""
+        _check(self._L.sbm_occ_color_ot_write(self._t, os.fsencode(path)), self._engine._h)
 
     def profile(self):
         return self._engine._profile(("occ_tree_build", "occ_tree_query"))

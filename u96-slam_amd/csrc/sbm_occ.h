@@ -65,6 +65,10 @@ int occ_ot_parse(const uint8_t* b, size_t n, double want_res, sbm_occ_ot_header*
                  std::vector<uint32_t>* values, bool bounds);
 int occ_ot_write_file(const std::vector<uint8_t>& body, size_t nodes, double resolution, const char* path);
 double occ_printed_resolution(double resolution);   // what the writers print for a resolution (%g), read back
+// sbm_occ_color_host.hip, the ColorOcTree stream: as the three above with eight bytes per node and the leaves' colour words
+int occ_color_ot_parse(const uint8_t* b, size_t n, double want_res, sbm_occ_ot_header* info, std::vector<OccBtLeaf>* words,
+                       std::vector<uint32_t>* values, std::vector<uint32_t>* colors, bool bounds);
+int occ_color_ot_write_file(const std::vector<uint8_t>& body, size_t nodes, double resolution, const char* path);
 #pragma GCC visibility pop
 // The edits' host arithmetic (sbm_occ_edit.hip; tools/occupancy_edit_sanitize.cpp runs it under the sanitizers). A batch of n items
 // goes through in chunks of SBM_OCC_EDIT_CHUNK, in item order: how many, and the items [*begin, *begin + *count) of chunk c
@@ -169,6 +173,7 @@ constexpr unsigned kOccCollapsed = 1u << 8;   // info word of a tree node: bits 
 constexpr int kOccTopShift = 10;              // bits 10-14 the depth of the shallowest collapsed node at or above it, or
 constexpr unsigned kOccNoTop = 31;            // kOccNoTop
 constexpr unsigned kOccInnerTag = 1u << 31;   // payload of a selected node: its index among the leaves, or tag | index above them
+constexpr unsigned kOccWhite = 0x00FFFFFFu;   // colour word of a slot (r | g << 8 | b << 16): octomap's "no colour set"
 
 struct OccCounters {
   unsigned long long overflow;   // points (log-odds mode: cells) that found the table full
@@ -282,6 +287,30 @@ __device__ __forceinline__ bool occ_find_or_claim(unsigned long long* keys, unsi
   return false;
 }
 
+// What the batches by key share (sbm_occ_edit.hip, sbm_occ_color.hip)
+constexpr unsigned long long kOccKeyBits = (1ull << 48) - 1;   // a packed key; the radix sort orders these bits
+constexpr uint32_t kOccNoSlot = ~0u;
+// The key's slot, without claiming: the walk of occ_find_or_claim, which ends at the first empty slot.
+__device__ __forceinline__ bool occ_find(const unsigned long long* keys, unsigned long long key, uint32_t mask, uint32_t max_probe,
+                                         uint32_t* at) {
+  uint32_t slot = occ_hash(key, mask);
+  for (uint32_t probe = 0; probe < max_probe; probe++, slot = (slot + 1) & mask) {
+    const unsigned long long cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == key) {
+      *at = slot;
+      return true;
+    }
+    if (cur == kOccEmpty) return false;
+  }
+  return false;
+}
+
+// `count` lanes of the wavefront add one each: one atomic by the first lane. EVERY lane has to reach this call.
+template <class T> __device__ __forceinline__ void occ_wave_count(bool count, T* counter) {
+  const unsigned long long counting = __ballot(count);
+  if (counting && (threadIdx.x & 63) == 0) atomicAdd(counter, (T)__popcll(counting));
+}
+
 // The wavefront's append to a list: one atomic add on the list's counter for all the lanes with `take`, each of which gets its
 // index (the others' means nothing). EVERY lane of the wavefront has to reach this call: it ballots and reads a lane.
 __device__ __forceinline__ unsigned occ_wave_append(bool take, unsigned* counter) {
@@ -311,11 +340,13 @@ struct OccRehash {
   const unsigned* old_vals;
   const unsigned* old_flags;       // null in hit mode
   const uint8_t* old_change;       // null where detection was never enabled
+  const unsigned* old_colors;      // null on a map without colours (sbm_occ_color.hip)
   uint32_t old_slots;
   unsigned long long* keys;
   unsigned* vals;
   unsigned* flags;
   uint8_t* change;
+  unsigned* colors;
   unsigned* touched;
   uint32_t mask, max_probe, slots;
   uint32_t parity;                 // which of OccCounters::touched the running scan counts in
@@ -338,6 +369,7 @@ __device__ __forceinline__ void occ_move_lane(const OccRehash& r, uint32_t i, un
         const uint8_t s = r.old_change[i];
         if (s != kOccChangeNone) r.change[slot] = s;
       }
+      if (r.old_colors) r.colors[slot] = r.old_colors[i];
     } else {   // a probe walk of the new table that ends without a slot: the voxel is lost, and counted as lost
       atomicAdd(&r.ctr->overflow, 1ull);
       atomicSub(&r.ctr->size, 1u);
@@ -373,7 +405,7 @@ int occ_rehash(sbm_occ_map* map, size_t capacity);
 // of `slots` slots beside the map's (a refused allocation frees what it got; the error is in last_hip), then the move itself into a
 // table for `capacity` voxels. remove (null: nothing), one byte per old slot: the slots that stay behind, `removed` of them, which
 // leave the size counter. *c: the counters after the move. The buffers are released either way.
-struct OccMoveBufs { DevBuf keys, vals, flags, touched, change; uint32_t slots; };
+struct OccMoveBufs { DevBuf keys, vals, flags, touched, change, color; uint32_t slots; };
 int occ_move_alloc(sbm_occ_map* map, uint32_t slots, OccMoveBufs* b);
 int occ_move_run(sbm_occ_map* map, size_t capacity, OccMoveBufs* b, const uint8_t* remove, unsigned removed, OccCounters* c);
 void occ_move_release(OccMoveBufs* b);
@@ -390,6 +422,8 @@ int occ_set_overflow(sbm_occ_map* map, unsigned long long value);       // in st
 int occ_claim_launch(sbm_occ_map* map, const int16_t* d_disp, const OccGeom& g, const sbm_stereo_model* model, const float* poses, int m);
 OccLevel occ_tree_level(const sbm_occ_tree* t, int d);   // these two are in sbm_occ_tree.hip: depth d of a built tree (empty levels for
 int occ_tree_stats(sbm_occ_tree* t);                     // one that is not), and the counts of the last build into t->host, read once
+int occ_ot_rank_run(sbm_occ_tree* t, uint32_t n, const unsigned** order);   // sbm_occ_ot.hip: the node at every pre-order rank of the pruned tree
+int occ_color_tree_run(sbm_occ_tree* t);   // sbm_occ_color.hip: a colour word per node of the tree just built, over a map with colours
 // A selection of n of the tree's nodes as (first Morton code of the cube, where the node is) pairs appended at the tree's cursor
 // (occ_tree_select_kernel and its siblings), between these two: begin places the sort's arrays beside d_keys / d_depth and zeroes
 // the cursor, end sorts the pairs and turns them in place into centre keys, depths and values
@@ -495,7 +529,10 @@ struct sbm_occ_map {
   sbm::DevBuf edit, edit_mask;  // from the first edit or delete: its counts; from the first call that may delete: the removal
                                 // mask, one byte per slot, clear between calls
   unsigned long long edit_items;   // of the last edit or delete call
-  template <class F> void each(F f) { f(keys); f(hits); f(ctr); f(flags); f(touched); f(change); f(dedupe); f(edit); f(edit_mask); }
+  // colours (sbm_occ_color.hip)
+  sbm::DevBuf color, color_counts;   // from the first colour call: one colour word per slot, kOccWhite where none is set; its counts
+  unsigned long long color_items;    // of the last colour call
+  template <class F> void each(F f) { f(keys); f(hits); f(ctr); f(flags); f(touched); f(change); f(dedupe); f(edit); f(edit_mask); f(color); f(color_counts); }
 };
 
 struct sbm_occ_tree {
@@ -516,6 +553,8 @@ struct sbm_occ_tree {
   sbm::DevBuf stats, tiles;    // OccTreeStats; head counts per tile of the level being built
   sbm::DevBuf ot;              // .ot writes only (sbm_occ_ot.hip): per node above the leaves its subtree's nodes and its pre-order
                                // rank among all nodes of the pruned tree, then the node at every rank
-  template <class F> void each(F f) { f(leaf); f(node); f(stats); f(tiles); f(ot); }
+  bool colored;                // `color` holds this build's colour words (sbm_occ_color.hip): the map had colours when it was built
+  sbm::DevBuf color;           // a colour word per voxel, then per node above them in the order of `node`
+  template <class F> void each(F f) { f(leaf); f(node); f(stats); f(tiles); f(ot); f(color); }
 };
 #endif

@@ -17,9 +17,6 @@
 namespace sbm {
 #pragma clang fp contract(off)
 
-constexpr unsigned long long kOccKeyBits = (1ull << 48) - 1;   // a packed key; the radix sort orders these bits
-constexpr uint32_t kOccNoSlot = ~0u;
-
 struct OccEditCounts {
   unsigned claim_skipped, claim_lost;   // of the last CLAIM launch, which may run again: APPLY adds them to the totals
   unsigned deletes;                     // delete items of a chunk whose ops are in device memory
@@ -41,6 +38,7 @@ struct OccEdit {
   float* logodds;
   unsigned* flags;
   uint8_t* change;                        // null where detection was never enabled
+  unsigned* colors;                       // null on a map without colours (sbm_occ_color.hip)
   uint8_t* remove;                        // null without ops: nothing can delete
   OccCounters* ctr;
   OccEditCounts* counts;
@@ -48,27 +46,6 @@ struct OccEdit {
   unsigned* index;                        // its index, the sort's payload
   uint32_t* slot_of;                      // per item (unsorted): its slot, or kOccNoSlot
 };
-
-// The key's slot, without claiming: the walk of occ_find_or_claim, which ends at the first empty slot.
-__device__ __forceinline__ bool occ_find(const unsigned long long* keys, unsigned long long key, uint32_t mask, uint32_t max_probe,
-                                         uint32_t* at) {
-  uint32_t slot = occ_hash(key, mask);
-  for (uint32_t probe = 0; probe < max_probe; probe++, slot = (slot + 1) & mask) {
-    const unsigned long long cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (cur == key) {
-      *at = slot;
-      return true;
-    }
-    if (cur == kOccEmpty) return false;
-  }
-  return false;
-}
-
-// `count` lanes of the wavefront add one each: one atomic by the first lane. EVERY lane has to reach this call.
-template <class T> __device__ __forceinline__ void occ_wave_count(bool count, T* counter) {
-  const unsigned long long counting = __ballot(count);
-  if (counting && (threadIdx.x & 63) == 0) atomicAdd(counter, (T)__popcll(counting));
-}
 
 __global__ void __launch_bounds__(256) occ_count_deletes_kernel(const uint8_t* __restrict__ ops, uint32_t n, OccEditCounts* __restrict__ counts) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -144,7 +121,7 @@ __global__ void __launch_bounds__(256) occ_edit_apply_kernel(OccEdit e) {
     }
     if (slot != kOccNoSlot) {   // else: skipped items, deletes of an absent voxel, or a voxel that found no slot
       created = (e.flags[slot] & kOccCreated) != 0;
-      bool present = !created;
+      bool present = !created, reborn = false;
       float v = e.logodds[slot];   // a claimed slot holds 0
       uint8_t state = e.change ? e.change[slot] : (uint8_t)kOccChangeNone;
       for (uint32_t k = j; k < e.n; k++) {
@@ -155,6 +132,7 @@ __global__ void __launch_bounds__(256) occ_edit_apply_kernel(OccEdit e) {
         const unsigned op = e.ops ? e.ops[item] : (unsigned)SBM_OCC_EDIT_UPDATE;
         if (op == SBM_OCC_EDIT_DELETE) {   // deleteNode: the voxel goes with all it holds
           present = false;
+          reborn = true;   // whatever the run makes of the voxel after this is a new node: white
           state = kOccChangeNone;
           continue;
         }
@@ -183,6 +161,7 @@ __global__ void __launch_bounds__(256) occ_edit_apply_kernel(OccEdit e) {
       if (present) {
         e.logodds[slot] = v;
         if (e.change) e.change[slot] = state;
+        if (reborn && e.colors) e.colors[slot] = kOccWhite;   // deleted and created again inside the run: no move drops the word
       } else if (e.remove) {   // only a delete item makes a voxel absent, and a chunk with one has a mask
         e.remove[slot] = 1;
         removed = true;
@@ -381,6 +360,7 @@ static int occ_edit_chunk_run(sbm_occ_map* map, const OccEditInput& in, uint32_t
     e.logodds = map->hits.as<float>();
     e.flags = map->flags.as<unsigned>();
     e.change = map->change.as<uint8_t>();
+    e.colors = map->color.as<unsigned>();
     e.remove = deletes ? map->edit_mask.as<uint8_t>() : nullptr;
     e.ctr = map->ctr.as<OccCounters>();
     if ((st = chk(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned), h->stream))) != SBM_OK) return fail(st);   // claim_skipped, claim_lost

@@ -84,7 +84,7 @@ int occ_set_overflow(sbm_occ_map* map, unsigned long long value) {
 }
 
 void occ_move_release(OccMoveBufs* b) {
-  for (DevBuf* d : {&b->keys, &b->vals, &b->flags, &b->touched, &b->change}) d->release();
+  for (DevBuf* d : {&b->keys, &b->vals, &b->flags, &b->touched, &b->change, &b->color}) d->release();
 }
 
 // the new buffers beside the old ones: a refused allocation frees what it got and leaves the map as it was
@@ -97,6 +97,7 @@ int occ_move_alloc(sbm_occ_map* map, uint32_t slots, OccMoveBufs* b) {
   if (e == hipSuccess && map->flags.p) e = b->flags.grow((size_t)slots * 4, h->stream);
   if (e == hipSuccess && map->touched.p) e = b->touched.grow((size_t)slots * 4, h->stream);
   if (e == hipSuccess && map->change.p) e = b->change.grow(slots, h->stream);
+  if (e == hipSuccess && map->color.p) e = b->color.grow((size_t)slots * 4, h->stream);
   if (e == hipSuccess) return SBM_OK;
   occ_move_release(b);
   h->last_hip = (int)e;
@@ -106,11 +107,12 @@ int occ_move_alloc(sbm_occ_map* map, uint32_t slots, OccMoveBufs* b) {
 int occ_move_run(sbm_occ_map* map, size_t capacity, OccMoveBufs* b, const uint8_t* remove, unsigned removed, OccCounters* c) {
   sbm_handle* h = map->h;
   const uint32_t slots = b->slots;
-  DevBuf &keys = b->keys, &vals = b->vals, &flags = b->flags, &touched = b->touched, &change = b->change;
+  DevBuf &keys = b->keys, &vals = b->vals, &flags = b->flags, &touched = b->touched, &change = b->change, &color = b->color;
   hipError_t e = hipMemsetAsync(keys.p, 0xFF, (size_t)slots * 8, h->stream);
   if (e == hipSuccess) e = hipMemsetAsync(vals.p, 0, (size_t)slots * 4, h->stream);
   if (e == hipSuccess && flags.p) e = hipMemsetAsync(flags.p, 0, (size_t)slots * 4, h->stream);
   if (e == hipSuccess && change.p) e = hipMemsetAsync(change.p, 0, slots, h->stream);
+  if (e == hipSuccess && color.p) e = hipMemsetD32Async((hipDeviceptr_t)color.p, (int)kOccWhite, slots, h->stream);
   OccRehash r;
   r.parity = map->scan & 1;
   OccCounters* ctr = map->ctr.as<OccCounters>();
@@ -120,11 +122,13 @@ int occ_move_run(sbm_occ_map* map, size_t capacity, OccMoveBufs* b, const uint8_
     r.old_vals = map->hits.as<unsigned>();
     r.old_flags = map->flags.as<unsigned>();
     r.old_change = map->change.as<uint8_t>();
+    r.old_colors = color.p ? map->color.as<unsigned>() : nullptr;
     r.old_slots = map->slots;
     r.keys = keys.as<unsigned long long>();
     r.vals = vals.as<unsigned>();
     r.flags = flags.as<unsigned>();
     r.change = change.as<uint8_t>();
+    r.colors = color.as<unsigned>();
     r.touched = touched.as<unsigned>();
     r.mask = slots - 1;
     r.max_probe = std::min(slots, kOccMaxProbe);
@@ -148,6 +152,7 @@ int occ_move_run(sbm_occ_map* map, size_t capacity, OccMoveBufs* b, const uint8_
   if (flags.p) std::swap(map->flags, flags);
   if (touched.p) std::swap(map->touched, touched);
   if (change.p) std::swap(map->change, change);
+  if (color.p) std::swap(map->color, color);
   occ_move_release(b);
   map->capacity = capacity;
   map->slots = slots;

@@ -106,6 +106,36 @@ struct OccOtRanks {   // the pieces of sbm_occ_tree::ot
   unsigned *cnt, *rank, *order;
 };
 
+// The pre-order ranks of the n nodes of the pruned tree (n >= 1): *order names the node at every rank. Ranked by the first call
+// after a build, placed alike by the later ones. The coloured stream (sbm_occ_color.hip) maps its body by the same ranks.
+int occ_ot_rank_run(sbm_occ_tree* t, uint32_t n, const unsigned** order) {
+  sbm_handle* h = t->h;
+  OccOtRanks r;
+  HIPCHK(h, carve(t->ot, h->stream, [&](Carve& c) {
+    r = {c.take<unsigned>(t->inner_total), c.take<unsigned>(t->inner_total), c.take<unsigned>(n)};
+  }, occ_pad));
+  *order = r.order;
+  if (t->ot_ranked) return SBM_OK;
+  for (int d = kOccDepth - 1; d >= 0; d--) {   // bottom-up
+    const OccLevel l = occ_tree_level(t, d);
+    hipLaunchKernelGGL(occ_ot_count_kernel, dim3((l.n + 255) / 256), dim3(256), 0, h->stream, l,
+                       d + 1 < kOccDepth ? r.cnt + t->off[d + 1] : nullptr, r.cnt + t->off[d]);
+    HIPCHK(h, hipGetLastError());
+  }
+  HIPCHK(h, hipMemsetAsync(r.rank, 0, 4, h->stream));                  // the root is node 0 above the voxels, at rank 0
+  HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)r.order, (int)kOccInnerTag, 1, h->stream));
+  for (int d = 0; d < kOccDepth; d++) {        // top-down
+    const OccLevel l = occ_tree_level(t, d);
+    const bool inner = d + 1 < kOccDepth;
+    hipLaunchKernelGGL(occ_ot_rank_kernel, dim3((l.n + 255) / 256), dim3(256), 0, h->stream, l, r.rank + t->off[d],
+                       inner ? r.cnt + t->off[d + 1] : nullptr, inner ? r.rank + t->off[d + 1] : nullptr,
+                       inner ? kOccInnerTag | (unsigned)t->off[d + 1] : 0u, r.order, n);
+    HIPCHK(h, hipGetLastError());
+  }
+  t->ot_ranked = true;
+  return SBM_OK;
+}
+
 static int occ_ot_body_run(sbm_occ_tree* t, uint8_t* d_bytes, size_t cap, size_t* nbytes) {
   sbm_handle* h = t->h;
   int st = occ_tree_stats(t);
@@ -116,34 +146,14 @@ static int occ_ot_body_run(sbm_occ_tree* t, uint8_t* d_bytes, size_t cap, size_t
   if (*nbytes > cap) return SBM_ERR_SIZE;
   return occ_timed_run(h, kOccTreeQuery, nodes > 0, 1, [&]() -> int {
     const uint32_t n = (uint32_t)nodes;   // below 2^31 + 2^30: a build refuses 2^31 nodes above the voxels
-    OccOtRanks r;   // grown by the first call after a build, placed alike by the later ones
-    HIPCHK(h, carve(t->ot, h->stream, [&](Carve& c) {
-      r = {c.take<unsigned>(t->inner_total), c.take<unsigned>(t->inner_total), c.take<unsigned>(n)};
-    }, occ_pad));
-    if (!t->ot_ranked) {
-      for (int d = kOccDepth - 1; d >= 0; d--) {   // bottom-up
-        const OccLevel l = occ_tree_level(t, d);
-        hipLaunchKernelGGL(occ_ot_count_kernel, dim3((l.n + 255) / 256), dim3(256), 0, h->stream, l,
-                           d + 1 < kOccDepth ? r.cnt + t->off[d + 1] : nullptr, r.cnt + t->off[d]);
-        HIPCHK(h, hipGetLastError());
-      }
-      HIPCHK(h, hipMemsetAsync(r.rank, 0, 4, h->stream));                  // the root is node 0 above the voxels, at rank 0
-      HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)r.order, (int)kOccInnerTag, 1, h->stream));
-      for (int d = 0; d < kOccDepth; d++) {        // top-down
-        const OccLevel l = occ_tree_level(t, d);
-        const bool inner = d + 1 < kOccDepth;
-        hipLaunchKernelGGL(occ_ot_rank_kernel, dim3((l.n + 255) / 256), dim3(256), 0, h->stream, l, r.rank + t->off[d],
-                           inner ? r.cnt + t->off[d + 1] : nullptr, inner ? r.rank + t->off[d + 1] : nullptr,
-                           inner ? kOccInnerTag | (unsigned)t->off[d + 1] : 0u, r.order, n);
-        HIPCHK(h, hipGetLastError());
-      }
-      t->ot_ranked = true;
-    }
+    const unsigned* order;
+    const int st = occ_ot_rank_run(t, n, &order);
+    if (st != SBM_OK) return st;
     OccOtRef ref;
     ref.leaf_val = occ_tree_level(t, kOccDepth).val;
     ref.node_val = occ_tree_level(t, 0).val;
     ref.node_info = occ_tree_level(t, 0).info;
-    hipLaunchKernelGGL(occ_ot_body_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, r.order, n, ref, d_bytes);
+    hipLaunchKernelGGL(occ_ot_body_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, order, n, ref, d_bytes);
     return SBM_OK;
   });
 }

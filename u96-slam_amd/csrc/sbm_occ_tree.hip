@@ -312,6 +312,7 @@ static int occ_tree_build_run(sbm_occ_tree* t, int reading, const sbm_occ_ray_pa
   t->have_stats = false;
   t->ot_ranked = false;
   t->have_metric = false;
+  t->colored = false;
   t->reading = reading;
   t->resolution = map->p.resolution;
   memset(t->count, 0, sizeof(t->count));
@@ -400,6 +401,7 @@ static int occ_tree_build_run(sbm_occ_tree* t, int reading, const sbm_occ_ray_pa
     }
     return SBM_OK;
   }();
+  if (st == SBM_OK && map->color.p) st = occ_color_tree_run(t);   // only over a map with colours
   if (st != SBM_OK) {
     t->built = false;
     return st;

@@ -144,6 +144,7 @@ int occ_clear(sbm_occ_map* map) {
   HIPCHK(h, hipMemsetAsync(map->ctr.p, 0, sizeof(OccCounters), h->stream));
   if (map->flags.p) HIPCHK(h, hipMemsetAsync(map->flags.p, 0, (size_t)map->slots * 4, h->stream));
   if (map->change.p) HIPCHK(h, hipMemsetAsync(map->change.p, 0, map->slots, h->stream));   // the switches and the box stay
+  if (map->color.p) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)map->color.p, (int)kOccWhite, map->slots, h->stream));   // every voxel white
   map->mode = kOccModeNone;
   map->scan = 0;
   map->size_bound = 0;
