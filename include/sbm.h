@@ -58,7 +58,7 @@
  * returns SBM_ERR_HIP (SBM_ERR_NOMEM if its 8-byte allocation fails) with the error in sbm_last_hip_error(), nothing is
  * remembered, and the next call runs the self-test again.
  *
- * Environment. The library reads these twelve variables (nothing else); an integrator never needs to set any of them:
+ * Environment. The library reads these thirteen variables (nothing else); an integrator never needs to set any of them:
  *   variable            default  read      who sets it, and what for
  *   SBM_FAST_INPLACE    1        once      0 = run the sliding-sum SAD kernel instead of the interior one (the fallback that
  *                                          is taken automatically when the device self-test of the in-place v_mqsad
@@ -72,6 +72,10 @@
  *                                          so that every hand-off is taken; GPU tests / A-B measurements
  *   SBM_FAST_FOLD       1        per call  0 = the last plain strip of a 128-disparity, window-15 launch runs as a plain strip even
  *                                          where it has at most 22 columns (1 = folded over its disparity halves: same results);
+ *                                          GPU tests / A-B measurements
+ *   SBM_FAST_NBR        1        per call  0 = the lone wavefronts of the interior SAD kernel select the winner's two neighbour sums in
+ *                                          the full tree over all disparities on every row (1 = only in the groups of 32 disparities
+ *                                          that a row's winners touch, the tree where they touch more than half: same results);
  *                                          GPU tests / A-B measurements
  *   SBM_SPECKLE_LISTS   1        per call  0 = the speckle filter's row-walking kernels (one wavefront per row, per-pixel labels)
  *                                          instead of the band walk + run records; GPU tests

@@ -12,7 +12,7 @@ namespace sbm {
 
 // Environment switches of the library -- the complete list, documented for integrators in include/sbm.h ("Environment").
 // They select a tested fallback or a code path that the GPU tests compare with the default one: SBM_FAST_INPLACE (0: the
-// sliding-sum kernel in place of the interior one), SBM_FAST_PFSHIFT, SBM_FAST_CS3, SBM_FAST_HANDOFF, SBM_FAST_FOLD, SBM_SPECKLE_LISTS, SBM_SPECKLE_BAND,
+// sliding-sum kernel in place of the interior one), SBM_FAST_PFSHIFT, SBM_FAST_CS3, SBM_FAST_HANDOFF, SBM_FAST_FOLD, SBM_FAST_NBR, SBM_SPECKLE_LISTS, SBM_SPECKLE_BAND,
 // SBM_SPECKLE_SEG, SBM_HOST_ZEROCOPY, SBM_WIDE, SBM_CV_READING, SBM_OCC_OT_HOST_PARSE.
 inline int env_switch(const char* name, int dflt) {
   const char* e = getenv(name);

@@ -449,6 +449,7 @@ hipError_t launch_sad_fast(const uint8_t* pf_l, const uint8_t* pf_r, int16_t* di
   a.strips = f.strips; a.nseg = f.nseg; a.npairs = g.n; a.strips3 = f.strips3; a.uniq_plain = f.uniq_plain;
   a.xc0 = f.xc0; a.xc1 = f.xc1;
   a.fold = sad_fast_fold_cols(pl) > 0;
+  a.nbr_tree = env_switch("SBM_FAST_NBR", 1) == 0;   // (read per call, as SBM_FAST_FOLD: the GPU tests flip it)
   a.bord = f.bord; a.bnw = f.bnw; a.bseg = f.bseg; a.nbseg = f.nbseg;
   a.ho_link = fast_handoff_links(pl, a.segat);   // (fills the order)
   if (!handoff) a.ho_link = 0;

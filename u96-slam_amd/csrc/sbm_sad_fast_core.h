@@ -40,6 +40,7 @@ struct FastArgs {
   u32 ho_epoch;              // this launch's number: a ready word that holds it was written by this launch
   int strips3;               // the first strips3 strips (a multiple of 3) have column stride 3, the others stride 1
   int fold;                  // the last strip (a plain one) runs folded over its disparity halves (sad_fast_fold_cols, sbm_sad_fast_fold.h)
+  int nbr_tree;              // SBM_FAST_NBR=0: the lone-wavefront strips look their neighbour sums up in the full tree on every row (fast_neighbours_grouped)
   int uniq_plain;            // 8 * (maxS * uniq / 100 + 1) fits 16 bits: deficit partial sums need no saturating adds
   int xc0, xc1;              // interior centre columns [xc0,xc1) (relative to lofs); xc0 = w/2
   int pfshift;               // the planes hold (value << pfshift) + 1: every sum below is scaled by 1 << pfshift (0 or 2)
@@ -318,6 +319,57 @@ __device__ __forceinline__ u32 fast_neighbours_tree(u32 (&X)[NQ], const u32 lnp)
     lvl++;
   }
   return X[0];
+}
+
+// The same pair, looked up only where somebody asks. The tree above selects among all 4 NQ sums for every lane, although a lane
+// wants two of them and the winners of a row's 60 columns lie close together wherever disparity is piecewise smooth. A GROUP is 32
+// consecutive buffer indices: 16 registers of S, 8 quads, index bits 5 and up. Group g is ACTIVE when ballot(ln or lp lies in it)
+// & live is not empty, with `live` the wavefront-uniform mask of the lanes whose result is stored as a disparity at all:
+// producing lanes that passed the texture test. Halo lanes hold garbage winners and textureless lanes are FILTERED whatever their
+// neighbours are, so neither may switch a group on; a lane outside `live` gets back whatever the groups of the others leave in
+// its halves. An active group runs the quad selection on its 8 quads and three tree levels (index bits 2..4), 15 v_perm_b32, and
+// a 16th puts its pair into exactly the result halves whose index lies in the group (selector 0x03020100 + 0x0404 per half that
+// does). All of it is 32-bit arithmetic on the packed pair: written with 16-bit vector types the compiler takes the halves apart
+// into compares and selects, several times the instructions. The branches are on scalars: the wavefront never diverges.
+// With more than half of the groups active (three of four, two of two) the full tree is the cheaper way and is taken as it
+// stands, and so it is with force_tree (FastArgs::nbr_tree, SBM_FAST_NBR=0): same integers on either path. Returns
+// S[ln] | S[lp] << 16 with their registers' tags, as the tree.
+template <int NQ>
+__device__ __forceinline__ u32 fast_neighbours_grouped(const u32 (&S)[2 * NQ], const u32 lnp, const unsigned long long live, const int force_tree) {
+  constexpr int NG = NQ / 8;
+  static_assert(NG == 2 || NG == 4, "two or four groups of 8 quads");
+  constexpr u32 ONE = 0x00010001u;
+  // A live lane has lp = ln + 2, or both mirrored onto one index at the ends of the range: it needs the groups from ln's to lp's,
+  // group g iff ln < 32 (g + 1) and lp >= 32 g -- the second read off the packed pair as it stands
+  u32 act = 0;                                                // bit g: a live lane needs group g (one scalar, not NG lane masks)
+#pragma unroll
+  for (int g = 0; g < NG; g++) {
+    unsigned long long need = live;
+    if (g < NG - 1) need &= __builtin_amdgcn_ballot_w64((lnp & 0xffffu) < (u32)(32 * (g + 1)));
+    if (g > 0) need &= __builtin_amdgcn_ballot_w64(lnp >= ((u32)(32 * g) << 16));
+    act |= min((u32)__builtin_popcountll(need), 1u) << g;     // (scalar arithmetic all the way: no boolean to move through a vector register)
+  }
+  if (force_tree || __builtin_popcount(act) > NG / 2) {
+    u32 X[NQ];
+    fast_neighbours_quads<NQ>(S, lnp, X);
+    return fast_neighbours_tree<NQ>(X, lnp);
+  }
+  const u32 gl = (lnp >> 5) & ((u32)(NG - 1) * ONE);          // gn | gp << 16
+  u32 r = 0;
+#pragma unroll
+  for (int g = 0; g < NG; g++) {
+    if ((act >> g) & 1u) {
+      u32 X[8];
+      const u32 sel = __umul24(lnp & 0x00030003u, 0x0202u) + 0x01000100u;   // (as fast_neighbours_quads)
+#pragma unroll
+      for (int q = 0; q < 8; q++) X[q] = __builtin_amdgcn_perm(S[16 * g + 2 * q + 1], S[16 * g + 2 * q], sel);
+      const u32 p = fast_neighbours_tree<8>(X, lnp);
+      // per half: NG - (group ^ g) is NG where the index lies in group g and 1 .. NG - 1 elsewhere (no borrow between the halves)
+      const u32 in_g = (((u32)NG * ONE - (gl ^ ((u32)g * ONE))) >> (NG == 4 ? 2 : 1)) & ONE;
+      r = __builtin_amdgcn_perm(p, r, __umul24(in_g, 0x0404u) + 0x03020100u);
+    }
+  }
+  return r;
 }
 
 // Uniqueness, part 2: any d outside [mind-1, mind+1] with S[d] <= thresh rejects -- the deficit sums of the two halves (even /

@@ -42,6 +42,7 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
   const int c = cbase + CS * lane;                      // this lane's column (relative to lofs): V covers c..c+2
   const int xc = c + W2;                                // centre column this lane produces
   const bool produces = lane < NV && xc >= a.xc0 && xc < a.xc1;
+  const unsigned long long prod_mask = __builtin_amdgcn_ballot_w64(produces);   // (wavefront-uniform: the neighbour look-up's live lanes)
   const int ys = a.segrow[segi];
   const int ye = a.segrow[segi + 1];
   // wavefront-uniform bases (scalar registers; the per-row step is scalar arithmetic) + this lane's 32-bit offset
@@ -358,13 +359,19 @@ __device__ __forceinline__ void sad_fast_strip_dma(const FastArgs& a, unsigned c
     const int ln = min(max(in_ - d0, 0), NDW - 1), lp = min(max(ip_ - d0, 0), NDW - 1);  // local (clamped) indices
     u32 X0;
     {
-      // via a byte-permute selection tree (low half of every selector follows ln, high half lp)
-      u32 X[NQ];
+      // via a byte-permute selection (low half of every selector follows ln, high half lp): the lone wavefronts with two or four
+      // index groups look only into the groups their live lanes need (fast_neighbours_grouped), the others into the whole tree
       const u32 lnp = (u32)ln | ((u32)lp << 16);
-      fast_neighbours_quads<NQ>(S, lnp, X);
+      if constexpr (NWAVES == 1 && NQ >= 16) {
+        X0 = fast_neighbours_grouped<NQ>(S, lnp, tex_ok & prod_mask, a.nbr_tree);
+      } else {
+        u32 X[NQ];
+        fast_neighbours_quads<NQ>(S, lnp, X);
+        X0 = fast_neighbours_tree<NQ>(X, lnp);
+      }
       // (without the tags of their registers; on untagged sums the bits are 0 anyway: every sum is a multiple of 1 << pfshift.
       // Masked here, in front of the merge area: what the cooperating wavefronts exchange is clean.)
-      X0 = fast_neighbours_tree<NQ>(X, lnp) & ~(((1u << a.pfshift) - 1u) * 0x00010001u);
+      X0 &= ~(((1u << a.pfshift) - 1u) * 0x00010001u);
     }
     int nn = (int)(X0 & 0xffffu), pp = (int)(X0 >> 16);
     u32 acc_lo = acc & 0xffffu, acc_hi = acc >> 16;
