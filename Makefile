@@ -5,7 +5,7 @@ CSRC := $(PKG)/csrc
 LIB := $(PKG)/lib/libsbm_hip.so
 # --offload-compress: the device code objects are stored compressed (10.5 MB -> 2.3 MB; ~4 ms of decompression at first use)
 HIPFLAGS ?= --offload-arch=gfx950 --offload-compress -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-value -Wno-unused-result
-SRCS := $(CSRC)/sbm_api.hip $(CSRC)/sbm_host.hip $(CSRC)/sbm_prefilter.hip $(CSRC)/sbm_sad_generic.hip $(CSRC)/sbm_sad_wide.hip $(CSRC)/sbm_sad_fast.hip $(CSRC)/sbm_sad_fast_pw1.hip $(CSRC)/sbm_sad_fast_pw2.hip $(CSRC)/sbm_sad_fast_pw3.hip $(CSRC)/sbm_lrcheck.hip $(CSRC)/sbm_speckle.hip $(CSRC)/sbm_consume.hip $(CSRC)/sbm_rectify.hip $(CSRC)/sbm_fpga.hip $(CSRC)/sbm_gftt.hip $(CSRC)/sbm_gftt_select.hip $(CSRC)/sbm_gftt_cv.hip $(CSRC)/sbm_orb.hip $(CSRC)/sbm_match.hip $(CSRC)/sbm_pnp.hip $(CSRC)/sbm_lk.hip $(CSRC)/sbm_sgbm.hip $(CSRC)/sbm_occupancy.hip $(CSRC)/sbm_occ_rays.hip $(CSRC)/sbm_occ_options.hip $(CSRC)/sbm_occ_grow.hip $(CSRC)/sbm_occ_edit.hip $(CSRC)/sbm_occ_color.hip $(CSRC)/sbm_occ_color_host.hip $(CSRC)/sbm_occ_query.hip $(CSRC)/sbm_occ_tree.hip $(CSRC)/sbm_occ_planner.hip $(CSRC)/sbm_occ_bt.hip $(CSRC)/sbm_occ_load.hip $(CSRC)/sbm_occ_ot.hip $(CSRC)/sbm_occ_ot_host.hip $(CSRC)/sbm_vwd.hip $(CSRC)/sbm_pgo.hip $(CSRC)/sbm_pgo_plan.hip
+SRCS := $(CSRC)/sbm_api.hip $(CSRC)/sbm_host.hip $(CSRC)/sbm_prefilter.hip $(CSRC)/sbm_sad_generic.hip $(CSRC)/sbm_sad_wide.hip $(CSRC)/sbm_sad_fast.hip $(CSRC)/sbm_sad_fast_pw1.hip $(CSRC)/sbm_sad_fast_pw2.hip $(CSRC)/sbm_sad_fast_pw3.hip $(CSRC)/sbm_lrcheck.hip $(CSRC)/sbm_speckle.hip $(CSRC)/sbm_consume.hip $(CSRC)/sbm_rectify.hip $(CSRC)/sbm_fpga.hip $(CSRC)/sbm_gftt.hip $(CSRC)/sbm_gftt_select.hip $(CSRC)/sbm_gftt_cv.hip $(CSRC)/sbm_orb.hip $(CSRC)/sbm_match.hip $(CSRC)/sbm_pnp.hip $(CSRC)/sbm_lk.hip $(CSRC)/sbm_sgbm.hip $(CSRC)/sbm_occupancy.hip $(CSRC)/sbm_occ_rays.hip $(CSRC)/sbm_occ_options.hip $(CSRC)/sbm_occ_grow.hip $(CSRC)/sbm_occ_edit.hip $(CSRC)/sbm_occ_color.hip $(CSRC)/sbm_occ_color_host.hip $(CSRC)/sbm_occ_stamp.hip $(CSRC)/sbm_occ_query.hip $(CSRC)/sbm_occ_tree.hip $(CSRC)/sbm_occ_planner.hip $(CSRC)/sbm_occ_bt.hip $(CSRC)/sbm_occ_load.hip $(CSRC)/sbm_occ_ot.hip $(CSRC)/sbm_occ_ot_host.hip $(CSRC)/sbm_vwd.hip $(CSRC)/sbm_pgo.hip $(CSRC)/sbm_pgo_plan.hip
 OBJS := $(SRCS:.hip=.o)
 
 all: $(LIB) oracle
@@ -26,7 +26,7 @@ $(CSRC)/sbm_lk.o: HIPFLAGS += -ffp-contract=off
 
 # occupancy map: one file per family over sbm_occ.h; the point arithmetic it shares with the other consumers of the map; its
 # float and double steps must match the host restatement's
-OCC_OBJS := $(CSRC)/sbm_occupancy.o $(CSRC)/sbm_occ_rays.o $(CSRC)/sbm_occ_options.o $(CSRC)/sbm_occ_grow.o $(CSRC)/sbm_occ_edit.o $(CSRC)/sbm_occ_color.o $(CSRC)/sbm_occ_color_host.o $(CSRC)/sbm_occ_query.o $(CSRC)/sbm_occ_tree.o $(CSRC)/sbm_occ_planner.o $(CSRC)/sbm_occ_bt.o $(CSRC)/sbm_occ_load.o $(CSRC)/sbm_occ_ot.o $(CSRC)/sbm_occ_ot_host.o
+OCC_OBJS := $(CSRC)/sbm_occupancy.o $(CSRC)/sbm_occ_rays.o $(CSRC)/sbm_occ_options.o $(CSRC)/sbm_occ_grow.o $(CSRC)/sbm_occ_edit.o $(CSRC)/sbm_occ_color.o $(CSRC)/sbm_occ_color_host.o $(CSRC)/sbm_occ_stamp.o $(CSRC)/sbm_occ_query.o $(CSRC)/sbm_occ_tree.o $(CSRC)/sbm_occ_planner.o $(CSRC)/sbm_occ_bt.o $(CSRC)/sbm_occ_load.o $(CSRC)/sbm_occ_ot.o $(CSRC)/sbm_occ_ot_host.o
 $(OCC_OBJS): $(CSRC)/sbm_occ.h
 $(CSRC)/sbm_consume.o $(OCC_OBJS): $(CSRC)/sbm_consume_math.h
 $(OCC_OBJS): HIPFLAGS += -ffp-contract=off

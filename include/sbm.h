@@ -1905,8 +1905,9 @@ int sbm_occ_ray_intersections(sbm_occ_map* map, size_t n, const float* origins, 
  *  pruned stream a colour call there colours a whole pruned leaf where this map colours one voxel, unless expand() is called first.
  *  Not provided: integrateNodeColor. It needs a double exp per voxel, and (uint8_t)(prev * p + r * (0.99 - p)) with prev == r
  *  sits on an integer boundary; whether the device's exp equals glibc's in every bit has not been measured and cannot be
- *  assumed. Not provided either: OcTreeStamped, colour in hit mode, writeColorHistogram, and a colour argument on the insert
- *  calls: the caller colours after inserting, as octomap's users do.
+ *  assumed. Not provided either: colour in hit mode, writeColorHistogram, and a colour argument on the insert
+ *  calls: the caller colours after inserting, as octomap's users do. OcTreeStamped's stamps are a section of their own ("occupancy
+ *  map: time stamps per voxel"); a map holds colours or stamps, not both.
  *  The tree. ColorOcTree::isNodeCollapsible ignores colour, so the pruned tree has the structure of the plain tree ("the octree
  *  above the voxels"); an sbm_occ_tree built over a map that has colours gets a colour word per node, octomap's after prune();
  *  updateInnerOccupancy(), in one bottom-up pass over the levels the build has. getAverageChildColor() is int sums of r, g, b over
@@ -1980,6 +1981,113 @@ int sbm_occ_color_ot_leaves(const void* bytes, size_t n, uint64_t* first_key, in
 int sbm_occ_color_ot_load(sbm_occ_map* map, const void* bytes, size_t n, int sync);
 /* The same from a file; SBM_ERR_UNSUPPORTED when it cannot be opened or read. */
 int sbm_occ_color_ot_read(sbm_occ_map* map, const char* path, int sync);
+
+/* ---- occupancy map: time stamps per voxel (OcTreeStamped.h, OcTreeStamped.cpp:43-68) -----------------------------------------
+ * When a voxel was last observed, beside its log-odds, as octomap's OcTreeStamped keeps one per node: what a long-running mapper
+ * needs to forget what it has not seen for a while. tests/occupancy_stamped_cases.py is a literal transcription of this text and
+ * tests/golden/occupancy_stamped.npz holds what the reference's own octomap answered, which the device equals in every integer.
+ *  Storage and the clock. One uint32 per slot. The time is the MAP'S CLOCK, a uint32 the caller sets (sbm_occ_stamp_set_time;
+ *  0 after create): the library never reads the wall clock, and nothing requires the clock to be monotone. Every stamping call
+ *  uses the clock as it is at the time of the call. sbm_occ_stamp_enable allocates the words, zeroed: existing voxels have stamp
+ *  0, as after a load. It fixes the mode of a fresh map to log-odds, as a colour call or an edit does; a hit map is refused with
+ *  SBM_ERR_UNSUPPORTED, and so is a map that already holds colour words: a map is one octomap class. For the same reason a
+ *  stamped map refuses every colour write (sbm_occ_color_keys*, sbm_occ_color_points*, sbm_occ_color_ot_load / _read) with
+ *  SBM_ERR_UNSUPPORTED and is as it was. A map that holds stamp words stays a log-odds map: sbm_occ_reset empties it and keeps the
+ *  words and the clock, and sbm_occ_insert* (the hit insert) answers SBM_ERR_UNSUPPORTED on it, before and after a reset. A map that never enables stamps allocates nothing and launches exactly what it launched
+ *  before; the reads below answer stamp 0 for every voxel of it, and the degrade and the forget refuse it.
+ *  Stamping. Every per-voxel updateNode with a log-odds update stamps the voxel with the clock (OcTreeStamped::updateNodeLogOdds:
+ *  the plain update, then updateTimestamp()) UNLESS updateNode's early return applies (OccupancyOcTreeBase.hxx:307-317), which
+ *  comes before updateNodeLogOdds: the voxel exists, and (update >= 0 and value >= clamp max) or (update <= 0 and value <= clamp
+ *  min). An update of exactly 0 tests both. So a wall hit ten times at clocks 1000..1009 saturates at the fifth hit and keeps stamp
+ *  1004, and the degrade below degrades it although it was seen a second ago; after that it is below the clamp and the next hit
+ *  stamps it again. This is octomap's behaviour, restated, not repaired. It covers the scan inserts (sbm_occ_insert_cloud*,
+ *  sbm_occ_insert_rays*, their _discrete forms, with and without the bounding box and change detection: each touched voxel gets
+ *  its one update, occupied before free) and the UPDATE items of the edit batches, where a voxel's items take effect in item
+ *  order: the voxel's stamp after the batch is the clock if any UPDATE item passed the early-return test at its turn, else the
+ *  stamp it had. setNodeValue (SBM_OCC_EDIT_SET) never stamps, and a voxel it creates has stamp 0. A deleted voxel goes with its
+ *  stamp: created again, also inside ONE edit batch, it starts from stamp 0.
+ *  Carry. Growth and the deletes' move carry the word with the key; sbm_occ_reset and every loader (.bt, .ot) leave stamp 0
+ *  everywhere (octomap's streams carry no stamps: OcTreeNodeStamped does not override writeData / readData). The clock stays.
+ *  sbm_occ_stamp_degrade is degradeOutdatedNodes(time_thres): every voxel with logodds >= the occupancy threshold and
+ *  (uint32)(clock - stamp) > time_thres gets one miss update, clamped (integrateMissNoTime: v + miss, then below clamp min ->
+ *  clamp min, above clamp max -> clamp max). The subtraction wraps in 32 bits as octomap's unsigned int does: a clock below a
+ *  stamp makes a huge age. The stamp is untouched and change detection is untouched. One lane per slot, plain stores.
+ *  sbm_occ_stamp_forget is an extension, not octomap: every voxel with (uint32)(clock - stamp) > time_thres is deleted, whatever
+ *  its value, through the delete family's move into a fresh table; its counts are those of a delete (sbm_occ_last_edit). In
+ *  octomap's terms: a leaf loop that collects those keys, then deleteNode of each.
+ *  Device. The stamp is a template switch of the scan's APPLY and of the edit's APPLY (one device function each, instantiated as
+ *  the kernel a map without stamps launches, unchanged in name, arguments and registers, and as a stamped kernel that takes the
+ *  words and the clock as two more arguments; the host picks beside kBox / kTrack): a plain vector store by the
+ *  lane that owns the slot (a slot is in the touched list once, and a run has one walker), no atomics on stamp words. On a
+ *  stamped map the scan's MARK always notes "created this scan", which the early-return test needs.
+ *  DIVERGENCE, pruning during inserts: as for colour, a stamp belongs to ONE depth-16 voxel; the recordings drive octomap with
+ *  lazy_eval = true, so that it never prunes while it inserts (pruneNode would smear stamps through copyData).
+ *  The tree. sbm_occ_tree_build over a map that holds stamp words builds octomap's STAMPED pruned tree, in both readings:
+ *  OcTreeNodeStamped's operator== compares value AND stamp, so isNodeCollapsible is "all eight present, all leaves, equal value,
+ *  equal stamp", applied bottom-up: eight siblings of equal value and equal stamps are 16 nodes and 1 leaf, with one stamp
+ *  different 24 nodes and 8 leaves. The pruned tree of a stamped map is therefore NOT the plain tree's wherever such stamps
+ *  differ: node counts, leaf order and the .bt and .ot bytes follow the stamped structure. A collapsed node has its children's
+ *  common stamp (copyData); every other inner node has the map's clock at build time (updateInnerOccupancy()); the root's stamp
+ *  is getLastUpdateTime() (sbm_occ_stamp_root). The stamp is gathered per voxel by key and the test is a template switch of the
+ *  level kernel; all other tree calls (info, search, leaves, the .bt body, the planner calls, sbm_occ_ot_body_device) work on that
+ *  structure unchanged. sbm_occ_stamp_leaves* is sbm_occ_tree_leaves* with the stamp of every entry, in the same order. A snapshot
+ *  of a map without stamps is built exactly as before, and its entries answer stamp 0.
+ *  The stream. AbstractOcTree::write with `id OcTreeStamped`: OcTreeNodeStamped does not override writeData, so the records are
+ *  the plain five bytes per node, over the stamped structure, under the other id line; sbm_occ_stamp_ot_info / _leaves / _load /
+ *  _read are the plain .ot parsers (on the device for the load) with the other id test, and a tree read back has stamp 0
+ *  everywhere. sbm_occ_ot_* and sbm_occ_color_ot_* keep refusing `id OcTreeStamped`, sbm_occ_stamp_ot_* refuse every other id; a
+ *  refused stream leaves the map as it was. writeBinary of an OcTreeStamped names the class in its header too; sbm_occ_tree_
+ *  write_binary writes `id OcTree` over the same body. integrateNodeColor, insertPointCloudRays and getNormals stay out as before.
+ *  sbm_get_profile: no new names. The degrade is timed under "occ_rays_apply", as the edits' APPLY is; the forget as a delete; the
+ *  search under "occ_search", the fetch under "occ_fetch" (DESIGN.md section 30). */
+/* Allocates the stamp words of a log-odds map, zeroed; a second call does nothing. SBM_ERR_NULL; SBM_ERR_UNSUPPORTED for a hit
+ * map and for a map that holds colour words; SBM_ERR_NOMEM where the words cannot be allocated: the map is as it was. */
+int sbm_occ_stamp_enable(sbm_occ_map* map);
+/* *enabled: 1 if the map holds stamp words, else 0. SBM_ERR_NULL. Host only. */
+int sbm_occ_stamp_enabled(const sbm_occ_map* map, int* enabled);
+/* The map's clock: set, and read back. SBM_ERR_NULL. Host only: no launch, and they work whether stamps are enabled or not. */
+int sbm_occ_stamp_set_time(sbm_occ_map* map, uint32_t clock);
+int sbm_occ_stamp_time(const sbm_occ_map* map, uint32_t* clock);
+/* degradeOutdatedNodes(time_thres) with the miss, the clamps and the occupancy threshold of params. *degraded: how many voxels
+ * got the miss update. Synchronous. Checked in this order before anything is launched: SBM_ERR_NULL; the codes of
+ * sbm_occ_ray_params_validate; SBM_ERR_UNSUPPORTED for a map without stamps. */
+int sbm_occ_stamp_degrade(sbm_occ_map* map, uint32_t time_thres, const sbm_occ_ray_params* params, uint64_t* degraded);
+/* Deletes every voxel with (uint32)(clock - stamp) > time_thres. removed (may be NULL): how many. Synchronous. SBM_ERR_NULL;
+ * SBM_ERR_UNSUPPORTED for a map without stamps; SBM_ERR_NOMEM where the move's table cannot be allocated: the map is as it was. */
+int sbm_occ_stamp_forget(sbm_occ_map* map, uint32_t time_thres, uint64_t* removed);
+/* sbm_occ_search_device with the stamp: d_stamp n uint32 (may be NULL, as d_value may). An unknown voxel and a point outside
+ * the key space answer stamp 0 and the quiet NaN 0x7FC00000. Read-only; it allocates nothing. The checks are
+ * sbm_occ_search_device's, and SBM_ERR_UNSUPPORTED on a hit map. */
+int sbm_occ_stamp_search_device(sbm_occ_map* map, size_t n, const void* d_xyz, float occupancy_thres_log, void* d_state, void* d_value,
+                                void* d_stamp, int sync);
+/* The same on HOST memory. Synchronous. */
+int sbm_occ_stamp_search(sbm_occ_map* map, size_t n, const float* xyz, float occupancy_thres_log, int32_t* state, void* value,
+                         uint32_t* stamp);
+/* sbm_occ_fetch_logodds_device with the stamps, through the map's radix sort: the voxels in ascending order of their packed keys,
+ * d_logodds and d_stamps cap 4-byte words each (either may be NULL). Same cap / *count / SBM_ERR_SIZE / SBM_ERR_OCC_FULL rule.
+ * Read-only. */
+int sbm_occ_stamp_fetch_device(sbm_occ_map* map, void* d_keys, void* d_logodds, void* d_stamps, size_t cap, size_t* count);
+int sbm_occ_stamp_fetch(sbm_occ_map* map, uint64_t* keys, float* logodds, uint32_t* stamps, size_t cap, size_t* count);
+/* sbm_occ_tree_leaves_device with d_stamp, cap uint32 in DEVICE memory, 4-byte aligned (NULL: exactly that call): the stamp of
+ * every entry, in the same order. Same entries, order, checks and cap / *count rule. 0 for every entry of a snapshot of a map
+ * without stamps. Synchronous. */
+int sbm_occ_stamp_leaves_device(sbm_occ_tree* tree, int max_depth, void* d_keys, void* d_depth, void* d_value, void* d_stamp, size_t cap,
+                                size_t* count);
+/* The same on HOST memory; value may be NULL, stamp not. */
+int sbm_occ_stamp_leaves(sbm_occ_tree* tree, int max_depth, uint64_t* keys, int32_t* depth, float* value, uint32_t* stamp, size_t cap,
+                         size_t* count);
+/* getLastUpdateTime(): the root's stamp, 0 for a snapshot without stamps or without a voxel. SBM_ERR_NULL. Synchronous. */
+int sbm_occ_stamp_root(sbm_occ_tree* tree, uint32_t* stamp);
+/* tree.write(path) of an OcTreeStamped: the .ot header with `id OcTreeStamped`, then the plain body (sbm_occ_ot_body_device) of
+ * the stamped snapshot. The codes of sbm_occ_ot_write; SBM_ERR_UNSUPPORTED for a snapshot of a map without stamps. */
+int sbm_occ_stamp_ot_write(sbm_occ_tree* tree, const char* path);
+/* sbm_occ_ot_info / _leaves / _load / _read for a stream whose id is OcTreeStamped: the same parsers (on the device for the load),
+ * the same codes; any other id, a plain OcTree among them, is SBM_ERR_UNSUPPORTED, and a refused stream leaves the map as it
+ * was. The loaded map has stamp 0 everywhere. */
+int sbm_occ_stamp_ot_info(const void* bytes, size_t n, sbm_occ_ot_header* out);
+int sbm_occ_stamp_ot_leaves(const void* bytes, size_t n, uint64_t* first_key, int32_t* depth, float* value, size_t cap, size_t* count);
+int sbm_occ_stamp_ot_load(sbm_occ_map* map, const void* bytes, size_t n, int sync);
+int sbm_occ_stamp_ot_read(sbm_occ_map* map, const char* path, int sync);
 
 /* ---- visual-word dictionary: addNewWords, computeLikelihood, limitKeypoints ---------------------------------------------------
  * The reference's loop-closure thread, started by Mapper::process for each key frame: addWordIds -> VWDictionary::addNewWords

@@ -148,6 +148,23 @@ class OccupancyTree {
     });
   }
   void writeColor(const std::string& path) { check(sbm_occ_color_ot_write(t_, path.c_str())); }
+  // of a snapshot over a map with stamps, octomap's STAMPED pruned tree: begin_leafs(maxDepth) with getTimestamp() of every entry,
+  // getLastUpdateTime() (the root's stamp), and tree.write(path) with `id OcTreeStamped`
+  std::vector<OccupancyLeaf> leavesStamped(std::vector<uint32_t>& stamps, unsigned max_depth = 0) {
+    std::vector<OccupancyLeaf> out = leaves(max_depth);
+    std::vector<uint64_t> keys(out.size());
+    std::vector<int32_t> depth(out.size());
+    stamps.assign(out.size(), 0u);
+    size_t n = 0;
+    check(sbm_occ_stamp_leaves(t_, (int)max_depth, keys.data(), depth.data(), nullptr, stamps.data(), out.size(), &n));
+    return out;
+  }
+  unsigned int getLastUpdateTime() {
+    uint32_t s = 0;
+    check(sbm_occ_stamp_root(t_, &s));
+    return s;
+  }
+  void writeStamped(const std::string& path) { check(sbm_occ_stamp_ot_write(t_, path.c_str())); }
 
  private:
   static void check(int st) {
@@ -497,6 +514,66 @@ class OccupancyMap {
   }
   bool readColor(const void* bytes, size_t n) {
     check(sbm_occ_color_ot_load(m_, bytes, n, 1));
+    return true;
+  }
+
+  // ---- time stamps per voxel, in octomap's spelling (OcTreeStamped; sbm.h, "occupancy map: time stamps per voxel") -----------
+  // OcTreeStamped reads time(NULL); this map has a clock of its own, which the caller sets: every updateNode of an insert or an
+  // edit stamps its voxel with time() unless octomap's early return applies. A map holds colours or stamps, not both. The
+  // tree snapshot of such a map is octomap's stamped pruned tree (OccupancyTree::leavesStamped, getLastUpdateTime, writeStamped).
+  void enableStamps() { check(sbm_occ_stamp_enable(m_)); }
+  bool stampsEnabled() {
+    int on = 0;
+    check(sbm_occ_stamp_enabled(m_, &on));
+    return on != 0;
+  }
+  void setTime(uint32_t clock) { check(sbm_occ_stamp_set_time(m_, clock)); }
+  uint32_t time() {
+    uint32_t c = 0;
+    check(sbm_occ_stamp_time(m_, &c));
+    return c;
+  }
+  // tree.degradeOutdatedNodes(time_thres) -> how many voxels got the miss update
+  uint64_t degradeOutdatedNodes(unsigned int time_thres) {
+    uint64_t n = 0;
+    check(sbm_occ_stamp_degrade(m_, time_thres, &rp_, &n));
+    return n;
+  }
+  // not octomap: deletes every voxel whose stamp is more than time_thres behind the clock -> how many
+  uint64_t forgetOlderThan(unsigned int time_thres) {
+    uint64_t n = 0;
+    check(sbm_occ_stamp_forget(m_, time_thres, &n));
+    return n;
+  }
+  // tree.search(x, y, z) of an OcTreeStamped: the state, and the node's log-odds and getTimestamp() (0 where there is no node)
+  int searchStamped(float x, float y, float z, float* logodds, uint32_t* stamp) {
+    const float p[3] = {x, y, z};
+    int32_t state = 0;
+    check(sbm_occ_stamp_search(m_, 1, p, occupancyThresLog(), &state, logodds, stamp));
+    return state;
+  }
+  void searchStamped(const float* xyz, size_t n, int32_t* states, void* values, uint32_t* stamps) {
+    check(sbm_occ_stamp_search(m_, n, xyz, occupancyThresLog(), states, values, stamps));
+  }
+  // the voxels in ascending order of their packed keys, with log-odds and stamps
+  std::vector<uint64_t> leavesStamped(std::vector<float>& logodds, std::vector<uint32_t>& stamps) {
+    std::vector<uint64_t> keys(size());
+    logodds.resize(keys.size());
+    stamps.resize(keys.size());
+    size_t n = 0;
+    check(sbm_occ_stamp_fetch(m_, keys.data(), logodds.data(), stamps.data(), keys.size(), &n));
+    keys.resize(n), logodds.resize(n), stamps.resize(n);
+    return keys;
+  }
+
+  // tree.write(path) of an OcTreeStamped as the map is now, and AbstractOcTree::read of one: stamps 0 everywhere afterwards
+  void writeStamped(const std::string& path) { buildTree(SBM_OCC_TREE_LOGODDS)->writeStamped(path); }
+  bool readStamped(const std::string& filename) {
+    check(sbm_occ_stamp_ot_read(m_, filename.c_str(), 1));
+    return true;
+  }
+  bool readStamped(const void* bytes, size_t n) {
+    check(sbm_occ_stamp_ot_load(m_, bytes, n, 1));
     return true;
   }
 

@@ -44,7 +44,8 @@ FIXTURES = {"octomap": "make_occupancy_fixtures.py", "rays": "make_occupancy_ray
 # fixtures added after that list was closed, in their own order of dependence; they may read every fixture above
 LATER_FIXTURES = {"options": "make_occupancy_option_fixtures.py"}
 # open: every later fixture goes here, in its order of dependence; they may read every fixture of the two mappings above
-MORE_FIXTURES = {"edit": "make_occupancy_edit_fixtures.py", "planner": "make_occupancy_planner_fixtures.py", "color": "make_occupancy_color_fixtures.py"}
+MORE_FIXTURES = {"edit": "make_occupancy_edit_fixtures.py", "planner": "make_occupancy_planner_fixtures.py", "color": "make_occupancy_color_fixtures.py",
+                 "stamped": "make_occupancy_stamped_fixtures.py"}
 RESOLUTION = 0.1
 PROBS = ("prob_hit", "prob_miss", "clamp_min", "clamp_max", "occupancy_thres")
 DEFAULT_PROBS = [getattr(rc.RayParams(), k) for k in PROBS]

@@ -35,6 +35,7 @@ from ._occupancy import OccupancyTree, OccTreeCounts, OCC_TREE_LOGODDS, OCC_TREE
 from ._occupancy import OccBinaryHeader, occ_binary_info, occ_binary_leaves  # noqa: F401
 from ._occupancy import OccOtHeader, occ_ot_info, occ_ot_leaves  # noqa: F401
 from ._occupancy import OccGrowthInfo, occ_growth_step  # noqa: F401
+from ._occupancy import occ_stamped_ot_info, occ_stamped_ot_leaves  # noqa: F401
 from ._occupancy import OccColorInfo, OCC_COLOR_AVERAGE, OCC_COLOR_SET, OCC_COLOR_WHITE, occ_color_ot_info, occ_color_ot_leaves, occ_color_rgb, occ_color_words  # noqa: F401
 from ._occupancy import OccEditInfo, OCC_EDIT_CHUNK, OCC_EDIT_DELETE, OCC_EDIT_SET, OCC_EDIT_UPDATE  # noqa: F401
 from ._vwd import (VWDictionary, VwdParams, vwd_params, vwd_validate, limit_keypoints, ERR_VWD_FULL, VWD_L1, VWD_L2,  # noqa: F401
@@ -54,6 +55,6 @@ __all__ = ["StereoBM", "StereoBMError", "SbmParams", "StereoModel", "library_pat
            "occ_write_binary", "ERR_OCC_FULL", "OccRayParams", "occ_ray_params", "occ_ray_validate", "occ_ray_logodds",
            "occ_write_binary_logodds", "OccQueryParams", "occ_query_params", "occ_query_validate", "OCC_CELL_OUT", "OCC_CELL_UNKNOWN",
            "OCC_CELL_FREE", "OCC_CELL_OCCUPIED", "OCC_RAY_NONE", "OCC_RAY_HIT", "OCC_RAY_RANGE", "OCC_RAY_UNKNOWN", "OCC_RAY_BOUNDS",
-           "OccupancyTree", "OccTreeCounts", "OccBinaryHeader", "occ_binary_info", "occ_binary_leaves", "OccOtHeader", "occ_ot_info", "occ_ot_leaves", "OccGrowthInfo", "occ_growth_step", "OccColorInfo", "OCC_COLOR_AVERAGE", "OCC_COLOR_SET", "OCC_COLOR_WHITE", "occ_color_ot_info", "occ_color_ot_leaves", "occ_color_rgb", "occ_color_words", "OccEditInfo", "OCC_EDIT_CHUNK", "OCC_EDIT_DELETE", "OCC_EDIT_SET", "OCC_EDIT_UPDATE", "OCC_TREE_LOGODDS", "OCC_TREE_MAXLIKELIHOOD", "VWDictionary", "VwdParams", "vwd_params", "vwd_validate", "limit_keypoints",
+           "OccupancyTree", "OccTreeCounts", "OccBinaryHeader", "occ_binary_info", "occ_binary_leaves", "OccOtHeader", "occ_ot_info", "occ_ot_leaves", "OccGrowthInfo", "occ_growth_step", "occ_stamped_ot_info", "occ_stamped_ot_leaves", "OccColorInfo", "OCC_COLOR_AVERAGE", "OCC_COLOR_SET", "OCC_COLOR_WHITE", "occ_color_ot_info", "occ_color_ot_leaves", "occ_color_rgb", "occ_color_words", "OccEditInfo", "OCC_EDIT_CHUNK", "OCC_EDIT_DELETE", "OCC_EDIT_SET", "OCC_EDIT_UPDATE", "OCC_TREE_LOGODDS", "OCC_TREE_MAXLIKELIHOOD", "VWDictionary", "VwdParams", "vwd_params", "vwd_validate", "limit_keypoints",
            "ERR_VWD_FULL", "VWD_L1", "VWD_L2", "VWD_NONE", "PoseGraph", "PgoParams", "PgoPlanInfo", "PgoGraph", "pgo_params", "pgo_check",
            "pgo_plan", "PGO_COUPLING_REFERENCE", "PGO_COUPLING_SYMMETRIC", "PGO_EDGE_RECORD"]

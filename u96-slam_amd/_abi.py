@@ -484,6 +484,27 @@ def load_library():
     L.sbm_occ_color_ot_leaves.argtypes = [vp, sz, vp, vp, vp, vp, sz, ctypes.POINTER(sz)]
     L.sbm_occ_color_ot_load.argtypes = [vp, vp, sz, ci]
     L.sbm_occ_color_ot_read.argtypes = [vp, ctypes.c_char_p, ci]
+    # time stamps per voxel: the map's clock, the degrade, forgetting by age, the stamped search and fetch
+    u32 = ctypes.c_uint32
+    L.sbm_occ_stamp_enable.argtypes = [vp]
+    L.sbm_occ_stamp_enabled.argtypes = [vp, ctypes.POINTER(ci)]
+    L.sbm_occ_stamp_set_time.argtypes = [vp, u32]
+    L.sbm_occ_stamp_time.argtypes = [vp, ctypes.POINTER(u32)]
+    L.sbm_occ_stamp_degrade.argtypes = [vp, u32, vp, ctypes.POINTER(ctypes.c_uint64)]
+    L.sbm_occ_stamp_forget.argtypes = [vp, u32, ctypes.POINTER(ctypes.c_uint64)]
+    L.sbm_occ_stamp_search_device.argtypes = [vp, sz, vp, ctypes.c_float, vp, vp, vp, ci]
+    L.sbm_occ_stamp_search.argtypes = [vp, sz, vp, ctypes.c_float, vp, vp, vp]
+    L.sbm_occ_stamp_fetch_device.argtypes = [vp, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_stamp_fetch.argtypes = [vp, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    # ... on a tree's nodes, and the OcTreeStamped stream
+    L.sbm_occ_stamp_leaves_device.argtypes = [vp, ci, vp, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_stamp_leaves.argtypes = [vp, ci, vp, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_stamp_root.argtypes = [vp, ctypes.POINTER(u32)]
+    L.sbm_occ_stamp_ot_write.argtypes = [vp, ctypes.c_char_p]
+    L.sbm_occ_stamp_ot_info.argtypes = [vp, sz, ctypes.POINTER(OccOtHeader)]
+    L.sbm_occ_stamp_ot_leaves.argtypes = [vp, sz, vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.sbm_occ_stamp_ot_load.argtypes = [vp, vp, sz, ci]
+    L.sbm_occ_stamp_ot_read.argtypes = [vp, ctypes.c_char_p, ci]
     # the read side for planners: a box's corners and a ray's shared origin are host memory
     L.sbm_occ_bbx_leaves_device.argtypes = [vp, vp, vp, ci, vp, vp, vp, sz, ctypes.POINTER(sz)]
     L.sbm_occ_bbx_leaves.argtypes = L.sbm_occ_bbx_leaves_device.argtypes

@@ -120,6 +120,27 @@ def occ_ot_leaves(data):
     return keys, depth, value
 
 
+def occ_stamped_ot_info(data):
+    """occ_ot_info for an `id OcTreeStamped` stream (the plain five-byte records), parsed on the host (no GPU)."""
+    b = _stream(data)
+    h = OccOtHeader()
+    _check(load_library().sbm_occ_stamp_ot_info(b.ctypes.data if len(b) else None, len(b), ctypes.byref(h)))
+    return dict(resolution=h.resolution, size=h.size, nodes=h.nodes, leaves=h.leaves, voxels=h.voxels, leaves_at=list(h.leaves_at),
+                value_min=h.value_min, value_max=h.value_max, key_min=list(h.key_min), key_max=list(h.key_max))
+
+
+def occ_stamped_ot_leaves(data):
+    """The leaves of an `id OcTreeStamped` stream in stream order, parsed on the host (no GPU) -> (packed key of each cube's lowest
+    voxel uint64, depth int32, value float32). The stream carries no stamps."""
+    b = _stream(data)
+    n = occ_stamped_ot_info(b)["leaves"]
+    keys, depth, value = np.empty(n, np.uint64), np.empty(n, np.int32), np.empty(n, np.float32)
+    got = ctypes.c_size_t()
+    _check(load_library().sbm_occ_stamp_ot_leaves(b.ctypes.data if len(b) else None, len(b), keys.ctypes.data if n else None,
+                                                  depth.ctypes.data if n else None, value.ctypes.data if n else None, n, ctypes.byref(got)))
+    return keys[:got.value], depth[:got.value], value[:got.value]
+
+
 def occ_color_ot_info(data):
     """occ_ot_info for a ColorOcTree stream (eight bytes per node), parsed on the host (no GPU)."""
     b = _stream(data)
@@ -478,6 +499,88 @@ class OccupancyMap:
         _check(self._L.sbm_occ_last_edit(self._m, ctypes.byref(e)), self._engine._h)
         return dict(items=e.items, skipped=e.skipped, lost=e.lost, created=e.created, removed=e.removed)
 
+    # ---- time stamps per voxel: octomap's OcTreeStamped on the map's own clock ------------------------------------------------------
+    def enable_stamps(self):
+        """One uint32 stamp per voxel from here on (existing voxels: 0). Log-odds maps only; a map holds colours or stamps, not
+        both. Every updateNode of a scan or an edit then stamps its voxel with the map's clock unless octomap's early return
+        applies (the voxel exists and sits at the clamp in the direction of the update)."""
+        _check(self._L.sbm_occ_stamp_enable(self._m), self._engine._h)
+
+    def stamps_enabled(self):
+        on = ctypes.c_int()
+        _check(self._L.sbm_occ_stamp_enabled(self._m, ctypes.byref(on)), self._engine._h)
+        return bool(on.value)
+
+    def set_time(self, clock):
+        """The map's clock, a uint32 the caller sets: what the stamping calls write. The library never reads the wall clock."""
+        _check(self._L.sbm_occ_stamp_set_time(self._m, int(clock) & 0xFFFFFFFF), self._engine._h)
+
+    def time(self):
+        c = ctypes.c_uint32()
+        _check(self._L.sbm_occ_stamp_time(self._m, ctypes.byref(c)), self._engine._h)
+        return c.value
+
+    def degrade_outdated(self, time_thres, params=None):
+        """octomap's degradeOutdatedNodes(time_thres): every occupied voxel with (uint32)(clock - stamp) > time_thres gets one miss
+        update, clamped; the stamps stay. -> how many voxels it degraded. Synchronous."""
+        p = params if params is not None else getattr(self, "_rp", None) or occ_ray_params()   # as the snapshot: the last insert's
+        n = ctypes.c_uint64()
+        _check(self._L.sbm_occ_stamp_degrade(self._m, int(time_thres) & 0xFFFFFFFF, ctypes.byref(p), ctypes.byref(n)), self._engine._h)
+        self._engine._inflight.clear()
+        return n.value
+
+    def forget_older_than(self, time_thres):
+        """Delete every voxel with (uint32)(clock - stamp) > time_thres, whatever its value (an extension, not octomap) -> how
+        many. Synchronous; last_edit() holds its counts."""
+        n = ctypes.c_uint64()
+        _check(self._L.sbm_occ_stamp_forget(self._m, int(time_thres) & 0xFFFFFFFF, ctypes.byref(n)), self._engine._h)
+        self._engine._inflight.clear()
+        return n.value
+
+    def search_stamps(self, points, occupancy_thres_log=0.0, sync=True):
+        """search(point) with the voxel's stamp, on (n, 3) points: a numpy array -> numpy (int32 states, uint32 value words, uint32
+        stamps), or a torch CUDA float32 tensor -> three torch int32 tensors. An unknown voxel, a point outside the key space and
+        every voxel of a map without stamps answer 0."""
+        if isinstance(points, np.ndarray):
+            p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+            n = len(p)
+            state, value, stamp = np.empty(n, np.int32), np.empty(n, np.uint32), np.empty(n, np.uint32)
+            _check(self._L.sbm_occ_stamp_search(self._m, n, p.ctypes.data if n else None, float(occupancy_thres_log), state.ctypes.data if n else None,
+                                                value.ctypes.data if n else None, stamp.ctypes.data if n else None), self._engine._h)
+            return state, value, stamp
+        torch = _torch()
+        p = self._cuda_f32(points, "points")
+        n = p.shape[0]
+        state, value, stamp = (torch.empty((n,), dtype=torch.int32, device=p.device) for _ in range(3))
+        torch.cuda.current_stream(p.device).synchronize()
+        _check(self._L.sbm_occ_stamp_search_device(self._m, n, p.data_ptr() if n else None, float(occupancy_thres_log), state.data_ptr() if n else None,
+                                                   value.data_ptr() if n else None, stamp.data_ptr() if n else None, 1 if sync else 0), self._engine._h)
+        self._after(sync, (p, state, value, stamp))
+        return state, value, stamp
+
+    def fetch_stamps(self, allow_overflow=False):
+        """(packed keys uint64 ascending, log-odds float32, stamps uint32) of a log-odds map as numpy arrays."""
+        n = self.size()
+        keys, lo, stamps = np.empty(n, np.uint64), np.empty(n, np.float32), np.empty(n, np.uint32)
+        got = ctypes.c_size_t()
+        st = self._L.sbm_occ_stamp_fetch(self._m, keys.ctypes.data if n else None, lo.ctypes.data if n else None, stamps.ctypes.data if n else None, n,
+                                         ctypes.byref(got))
+        if not (st == ERR_OCC_FULL and allow_overflow):
+            _check(st, self._engine._h)
+        return keys[:got.value], lo[:got.value], stamps[:got.value]
+
+    def fetch_stamps_device(self):
+        """The same as torch CUDA tensors: keys int64, log-odds float32, stamps int32."""
+        torch = _torch()
+        n = self.size()
+        dev = torch.device("cuda", self._engine._device)
+        keys, lo, stamps = torch.empty((n,), dtype=torch.int64, device=dev), torch.empty((n,), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+        got = ctypes.c_size_t()
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.sbm_occ_stamp_fetch_device(self._m, keys.data_ptr() if n else None, lo.data_ptr() if n else None, stamps.data_ptr() if n else None, n,
+                                                  ctypes.byref(got)), self._engine._h)
+        return keys[:got.value], lo[:got.value], stamps[:got.value]
+
     # ---- colour per voxel: octomap's ColorOcTree::setNodeColor and averageNodeColor on batches of items ----------------------------
     def _color(self, items, colors, op, sync):
         if isinstance(items, np.ndarray) or not hasattr(items, "data_ptr"):
@@ -604,6 +707,18 @@ class OccupancyMap:
         else:
             b = _stream(data_or_path)
             st = self._L.sbm_occ_ot_load(self._m, b.ctypes.data if len(b) else None, len(b), 1 if sync else 0)
+        _check(st, self._engine._h)
+        if sync:
+            self._engine._inflight.clear()
+
+    def load_stamped_ot(self, data_or_path, sync=True):
+        """AbstractOcTree::read of an `id OcTreeStamped` stream -- bytes (or a uint8 array), or the path of a file: as load_ot, and
+        every stamp is 0 afterwards (the stream carries none). A plain OcTree stream is refused (load_ot reads that)."""
+        if isinstance(data_or_path, (str, os.PathLike)):
+            st = self._L.sbm_occ_stamp_ot_read(self._m, os.fsencode(data_or_path), 1 if sync else 0)
+        else:
+            b = _stream(data_or_path)
+            st = self._L.sbm_occ_stamp_ot_load(self._m, b.ctypes.data if len(b) else None, len(b), 1 if sync else 0)
         _check(st, self._engine._h)
         if sync:
             self._engine._inflight.clear()
@@ -1048,6 +1163,50 @@ class OccupancyTree:
                                                    value.data_ptr() if n else None, color.data_ptr() if n else None, n, ctypes.byref(got)),
                self._engine._h)
         return keys[:got.value], depth[:got.value], value[:got.value], color[:got.value]
+
+    # ---- stamps: the tree over a map that has them is octomap's STAMPED pruned tree (siblings collapse only where the stamps agree) ----
+    def leaves_stamps(self, max_depth=0):
+        """leaves(max_depth) with the stamp of every entry -> (centre keys uint64, depths int32, values float32, stamps uint32) as
+        numpy arrays in octomap's iteration order. 0 for every node of a tree built over a map without stamps."""
+        n = self._leaf_count(max_depth)
+        keys, depth, value, stamp = np.empty(n, np.uint64), np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.uint32)
+        got = ctypes.c_size_t()
+        _check(self._L.sbm_occ_stamp_leaves(self._t, int(max_depth), keys.ctypes.data if n else None, depth.ctypes.data if n else None,
+                                            value.ctypes.data if n else None, stamp.ctypes.data if n else None, n, ctypes.byref(got)), self._engine._h)
+        return keys[:got.value], depth[:got.value], value[:got.value], stamp[:got.value]
+
+    def leaves_stamps_device(self, max_depth=0):
+        """The same as torch CUDA tensors: keys int64, depths int32, values float32, stamps int32."""
+        torch = _torch()
+        n = self._leaf_count(max_depth)
+        dev = torch.device("cuda", self._engine._device)
+        keys, depth = torch.empty((n,), dtype=torch.int64, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+        value, stamp = torch.empty((n,), dtype=torch.float32, device=dev), torch.empty((n,), dtype=torch.int32, device=dev)
+        got = ctypes.c_size_t()
+        torch.cuda.current_stream(dev).synchronize()
+        _check(self._L.sbm_occ_stamp_leaves_device(self._t, int(max_depth), keys.data_ptr() if n else None, depth.data_ptr() if n else None,
+                                                   value.data_ptr() if n else None, stamp.data_ptr() if n else None, n, ctypes.byref(got)),
+               self._engine._h)
+        return keys[:got.value], depth[:got.value], value[:got.value], stamp[:got.value]
+
+    def last_update_time(self):
+        """octomap's getLastUpdateTime(): the root's stamp (the map's clock at build time unless the root itself collapsed)."""
+        c = ctypes.c_uint32()
+        _check(self._L.sbm_occ_stamp_root(self._t, ctypes.byref(c)), self._engine._h)
+        return c.value
+
+    def write_stamped_ot(self, path):
+        """tree.write(path) of an OcTreeStamped: `id OcTreeStamped`, a LOGODDS tree built over a map with stamps."""
+        _check(self._L.sbm_occ_stamp_ot_write(self._t, os.fsencode(path)), self._engine._h)
+
+    def stamped_ot(self):
+        """The whole OcTreeStamped stream as bytes: the file write_stamped_ot writes, read back."""
+        import tempfile
+        with tempfile.TemporaryDirectory() as tmp:
+            path = os.path.join(tmp, "tree.ot")
+            self.write_stamped_ot(path)
+            with open(path, "rb") as f:
+                return f.read()
 
     def color_ot_body(self):
         """The body of the ColorOcTree stream (a LOGODDS tree) as a torch CUDA uint8 tensor: eight bytes per node of the pruned tree."""

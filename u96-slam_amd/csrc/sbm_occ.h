@@ -60,10 +60,10 @@ int occ_read_file(const char* path, std::vector<uint8_t>* data);
 int occ_bt_header(const uint8_t* b, size_t n, size_t* pos, std::string* id, uint64_t* size, double* res);   // readHeader
 // sbm_occ_ot_host.hip, the .ot stream: its header alone (-> where the body begins), the whole host parse (leaf words without the occupied bit, and the
 // leaves' float bits), and the file. want_res > 0: what the file's res must equal
-int occ_ot_head(const uint8_t* b, size_t n, double want_res, sbm_occ_ot_header* info, size_t* body);
+int occ_ot_head(const uint8_t* b, size_t n, double want_res, sbm_occ_ot_header* info, size_t* body, bool stamped = false);   // stamped: the id has to be OcTreeStamped
 int occ_ot_parse(const uint8_t* b, size_t n, double want_res, sbm_occ_ot_header* info, std::vector<OccBtLeaf>* words,
-                 std::vector<uint32_t>* values, bool bounds);
-int occ_ot_write_file(const std::vector<uint8_t>& body, size_t nodes, double resolution, const char* path);
+                 std::vector<uint32_t>* values, bool bounds, bool stamped = false);
+int occ_ot_write_file(const std::vector<uint8_t>& body, size_t nodes, double resolution, const char* path, const char* id = "OcTree");
 double occ_printed_resolution(double resolution);   // what the writers print for a resolution (%g), read back
 // sbm_occ_color_host.hip, the ColorOcTree stream: as the three above with eight bytes per node and the leaves' colour words
 int occ_color_ot_parse(const uint8_t* b, size_t n, double want_res, sbm_occ_ot_header* info, std::vector<OccBtLeaf>* words,
@@ -353,7 +353,10 @@ struct OccRehash {
   OccCounters* ctr;
 };
 // One lane of a move, old slot i with `key` (kOccEmpty: nothing to move). EVERY lane of the wavefront has to reach this call.
-__device__ __forceinline__ void occ_move_lane(const OccRehash& r, uint32_t i, unsigned long long key) {
+// old_stamps / stamps: the stamp words of a stamped map (sbm_occ_stamp.hip), which the stamped forms of the two move kernels pass;
+// they are arguments of their own, so that the kernels of a map without stamps are what they were.
+__device__ __forceinline__ void occ_move_lane(const OccRehash& r, uint32_t i, unsigned long long key, const unsigned* old_stamps = nullptr,
+                                              unsigned* stamps = nullptr) {
   bool listed = false;
   uint32_t slot = 0;
   if (key != kOccEmpty) {
@@ -370,6 +373,7 @@ __device__ __forceinline__ void occ_move_lane(const OccRehash& r, uint32_t i, un
         if (s != kOccChangeNone) r.change[slot] = s;
       }
       if (r.old_colors) r.colors[slot] = r.old_colors[i];
+      if (old_stamps) stamps[slot] = old_stamps[i];
     } else {   // a probe walk of the new table that ends without a slot: the voxel is lost, and counted as lost
       atomicAdd(&r.ctr->overflow, 1ull);
       atomicSub(&r.ctr->size, 1u);
@@ -405,11 +409,11 @@ int occ_rehash(sbm_occ_map* map, size_t capacity);
 // of `slots` slots beside the map's (a refused allocation frees what it got; the error is in last_hip), then the move itself into a
 // table for `capacity` voxels. remove (null: nothing), one byte per old slot: the slots that stay behind, `removed` of them, which
 // leave the size counter. *c: the counters after the move. The buffers are released either way.
-struct OccMoveBufs { DevBuf keys, vals, flags, touched, change, color; uint32_t slots; };
+struct OccMoveBufs { DevBuf keys, vals, flags, touched, change, color, stamp; uint32_t slots; };
 int occ_move_alloc(sbm_occ_map* map, uint32_t slots, OccMoveBufs* b);
 int occ_move_run(sbm_occ_map* map, size_t capacity, OccMoveBufs* b, const uint8_t* remove, unsigned removed, OccCounters* c);
 void occ_move_release(OccMoveBufs* b);
-void occ_remove_launch(sbm_handle* h, const OccRehash& r, const uint8_t* remove, unsigned removed);   // sbm_occ_edit.hip: the move that leaves slots behind
+void occ_remove_launch(sbm_handle* h, const OccRehash& r, const uint8_t* remove, unsigned removed, const unsigned* old_stamps, unsigned* stamps);   // sbm_occ_edit.hip: the move that leaves slots behind
 bool occ_can_reserve(const sbm_occ_map* map, size_t voxels);   // growth is on and its ceiling admits so many voxels
 // A growing map after a launch that claimed keys (MARK, the hit insert's claim pass): reads the counters into *c and grows the
 // table if cells were lost (overflow above `before`) or the size has passed the capacity. *again: cells were lost and the table
@@ -532,7 +536,10 @@ struct sbm_occ_map {
   // colours (sbm_occ_color.hip)
   sbm::DevBuf color, color_counts;   // from the first colour call: one colour word per slot, kOccWhite where none is set; its counts
   unsigned long long color_items;    // of the last colour call
-  template <class F> void each(F f) { f(keys); f(hits); f(ctr); f(flags); f(touched); f(change); f(dedupe); f(edit); f(edit_mask); f(color); f(color_counts); }
+  // time stamps (sbm_occ_stamp.hip)
+  sbm::DevBuf stamp, stamp_count;    // from sbm_occ_stamp_enable: one uint32 per slot, 0 where nothing stamped; the degrade's count
+  uint32_t clock;                    // the map's clock: what a stamping call writes (sbm_occ_stamp_set_time)
+  template <class F> void each(F f) { f(keys); f(hits); f(ctr); f(flags); f(touched); f(change); f(dedupe); f(edit); f(edit_mask); f(color); f(color_counts); f(stamp); f(stamp_count); }
 };
 
 struct sbm_occ_tree {
@@ -555,6 +562,15 @@ struct sbm_occ_tree {
                                // rank among all nodes of the pruned tree, then the node at every rank
   bool colored;                // `color` holds this build's colour words (sbm_occ_color.hip): the map had colours when it was built
   sbm::DevBuf color;           // a colour word per voxel, then per node above them in the order of `node`
-  template <class F> void each(F f) { f(leaf); f(node); f(stats); f(tiles); f(ot); f(color); }
+  bool stamped;                // `stamp` holds this build's stamps (sbm_occ_stamp.hip): the map had stamps when it was built, and the
+                               // structure is octomap's STAMPED pruned tree
+  sbm::DevBuf stamp;           // a stamp per voxel, then per node above them in the order of `node`
+  template <class F> void each(F f) { f(leaf); f(node); f(stats); f(tiles); f(ot); f(color); f(stamp); }
 };
+// where the two parts of a built tree's stamps are (the layout of the build, placed again with its counts)
+inline void occ_tree_stamps(const sbm_occ_tree* t, unsigned** leaf, unsigned** node) {
+  sbm::Carve c{t->stamp.as<char>(), 0, sbm::occ_pad};
+  *leaf = c.take<unsigned>(t->count[sbm::kOccDepth]);
+  *node = c.take<unsigned>(t->inner_total);
+}
 #endif

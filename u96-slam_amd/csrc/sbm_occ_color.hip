@@ -310,6 +310,7 @@ static int occ_color_call(sbm_occ_map* map, size_t n, const OccColorInput& in, i
   if (!map || (n > 0 && (!(in.keys || in.xyz) || !in.rgb))) return SBM_ERR_NULL;
   if (op != SBM_OCC_COLOR_SET && op != SBM_OCC_COLOR_AVERAGE) return SBM_ERR_UNSUPPORTED;
   if (n > kOccColorMax || map->mode == kOccModeHits) return SBM_ERR_UNSUPPORTED;
+  if (map->stamp.p) return SBM_ERR_UNSUPPORTED;   // a map is one octomap class: a stamped map takes no colour (sbm_occ_stamp.hip)
   if (!in.host && (((uintptr_t)in.keys & 7) || ((uintptr_t)in.xyz & 3) || ((uintptr_t)in.rgb & 3))) return SBM_ERR_UNSUPPORTED;
   sbm_handle* h = map->h;
   StageClock& clk = h->occ.clock;
@@ -548,6 +549,7 @@ static int occ_color_load_run(sbm_occ_map* map, const uint8_t* bytes, size_t n) 
   sbm_handle* h = map->h;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
+  if (map->stamp.p) return SBM_ERR_UNSUPPORTED;   // a stamped map takes no colour: the map is as it was
   const float last = h->occ.clock.ms[kOccLoad];
   HIPCHK(h, occ_clock_start(h, kOccLoad, kOccLoad));
   bool touched = false;

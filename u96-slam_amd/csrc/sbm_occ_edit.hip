@@ -100,7 +100,10 @@ __global__ void __launch_bounds__(256) occ_edit_claim_kernel(OccEdit e) {
   occ_wave_count(lost, &e.ctr->overflow);
 }
 
-__global__ void __launch_bounds__(256) occ_edit_apply_kernel(OccEdit e) {
+// kStamp (sbm.h, "occupancy map: time stamps per voxel"): the run's walk also carries the slot's stamp word -- the clock if any
+// update item of the run passed the early-return test at its turn, else the old stamp, restarted at 0 by a delete; setNodeValue
+// never stamps. One plain store by the run's one walker. Without kStamp this is the kernel of a map without stamps.
+template <bool kStamp> __device__ __forceinline__ void occ_edit_apply(const OccEdit& e, unsigned* __restrict__ stamps, uint32_t clock) {
 #pragma clang fp contract(off)
   const uint32_t j = blockIdx.x * 256 + threadIdx.x;
   if (j == 0) {   // the counts of the CLAIM launch that stood
@@ -124,6 +127,8 @@ __global__ void __launch_bounds__(256) occ_edit_apply_kernel(OccEdit e) {
       bool present = !created, reborn = false;
       float v = e.logodds[slot];   // a claimed slot holds 0
       uint8_t state = e.change ? e.change[slot] : (uint8_t)kOccChangeNone;
+      uint32_t stamp = 0;
+      if (kStamp) stamp = stamps[slot];   // a claimed slot holds 0
       for (uint32_t k = j; k < e.n; k++) {
         const unsigned long long key = e.sort_keys[k];
         if ((key & kOccKeyBits) != low) break;
@@ -134,6 +139,7 @@ __global__ void __launch_bounds__(256) occ_edit_apply_kernel(OccEdit e) {
           present = false;
           reborn = true;   // whatever the run makes of the voxel after this is a new node: white
           state = kOccChangeNone;
+          if (kStamp) stamp = 0;
           continue;
         }
         float x = e.values[item];
@@ -145,6 +151,7 @@ __global__ void __launch_bounds__(256) occ_edit_apply_kernel(OccEdit e) {
           v = v + x;
           if (v < e.cmin) v = e.cmin;
           else if (v > e.cmax) v = e.cmax;
+          if (kStamp) stamp = clock;       // OcTreeStamped::updateNodeLogOdds: updateTimestamp()
         } else {                           // setNodeValue: std::min(std::max(x, cmin), cmax)
           x = x < e.cmin ? e.cmin : x;
           x = e.cmax < x ? e.cmax : x;
@@ -161,6 +168,7 @@ __global__ void __launch_bounds__(256) occ_edit_apply_kernel(OccEdit e) {
       if (present) {
         e.logodds[slot] = v;
         if (e.change) e.change[slot] = state;
+        if (kStamp) stamps[slot] = stamp;
         if (reborn && e.colors) e.colors[slot] = kOccWhite;   // deleted and created again inside the run: no move drops the word
       } else if (e.remove) {   // only a delete item makes a voxel absent, and a chunk with one has a mask
         e.remove[slot] = 1;
@@ -170,6 +178,10 @@ __global__ void __launch_bounds__(256) occ_edit_apply_kernel(OccEdit e) {
   }
   occ_wave_count(created, &e.counts->created);   // every lane is here
   occ_wave_count(removed, &e.counts->removed);
+}
+__global__ void __launch_bounds__(256) occ_edit_apply_kernel(OccEdit e) { occ_edit_apply<false>(e, nullptr, 0u); }
+__global__ void __launch_bounds__(256) occ_edit_apply_stamped_kernel(OccEdit e, unsigned* __restrict__ stamps, uint32_t clock) {
+  occ_edit_apply<true>(e, stamps, clock);
 }
 
 // The given keys of a range delete under the depth mask, as the sort takes them; a key above bit 47 is skipped (kOccEmpty).
@@ -246,6 +258,20 @@ __global__ void __launch_bounds__(256) occ_mark_box_kernel(const unsigned long l
   occ_block_count(marked, &counts->removed);   // every lane is here
 }
 
+// Forget by age (sbm_occ_stamp_forget): a voxel whose stamp is more than time_thres behind the clock, in octomap's 32-bit wrap
+__global__ void __launch_bounds__(256) occ_mark_older_kernel(const unsigned long long* __restrict__ keys, uint32_t slots,
+                                                              const unsigned* __restrict__ stamps, uint32_t clock, uint32_t time_thres,
+                                                              uint8_t* __restrict__ remove, OccEditCounts* __restrict__ counts) {
+  unsigned marked = 0;
+  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < slots; i += gridDim.x * 256) {
+    if (keys[i] != kOccEmpty && (uint32_t)(clock - stamps[i]) > time_thres) {
+      remove[i] = 1;
+      marked++;
+    }
+  }
+  occ_block_count(marked, &counts->removed);   // every lane is here
+}
+
 // The move behind the mask: a marked slot stays behind, the others move as a growth moves them. `removed`, the marked slots as the
 // marking passes counted them, leaves the size counter in one step.
 __global__ void __launch_bounds__(256) occ_remove_kernel(OccRehash r, const uint8_t* __restrict__ remove, unsigned removed) {
@@ -256,8 +282,20 @@ __global__ void __launch_bounds__(256) occ_remove_kernel(OccRehash r, const uint
   occ_move_lane(r, i, key);   // every lane is here
 }
 
-void occ_remove_launch(sbm_handle* h, const OccRehash& r, const uint8_t* remove, unsigned removed) {
-  hipLaunchKernelGGL(occ_remove_kernel, dim3((r.old_slots + 255) / 256), dim3(256), 0, h->stream, r, remove, removed);
+// the same on a stamped map: the stamp word moves with the key
+__global__ void __launch_bounds__(256) occ_remove_stamped_kernel(OccRehash r, const uint8_t* __restrict__ remove, unsigned removed,
+                                                                  const unsigned* __restrict__ old_stamps, unsigned* __restrict__ stamps) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) atomicSub(&r.ctr->size, removed);
+  unsigned long long key = i < r.old_slots ? r.old_keys[i] : kOccEmpty;
+  if (key != kOccEmpty && remove[i]) key = kOccEmpty;
+  occ_move_lane(r, i, key, old_stamps, stamps);   // every lane is here
+}
+
+void occ_remove_launch(sbm_handle* h, const OccRehash& r, const uint8_t* remove, unsigned removed, const unsigned* old_stamps, unsigned* stamps) {
+  const dim3 grid((r.old_slots + 255) / 256);
+  if (old_stamps) hipLaunchKernelGGL(occ_remove_stamped_kernel, grid, dim3(256), 0, h->stream, r, remove, removed, old_stamps, stamps);
+  else hipLaunchKernelGGL(occ_remove_kernel, grid, dim3(256), 0, h->stream, r, remove, removed);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
@@ -383,7 +421,8 @@ static int occ_edit_chunk_run(sbm_occ_map* map, const OccEditInput& in, uint32_t
   }
   if ((st = chk(clk.mark(kOccMid, h->stream))) != SBM_OK) return fail(st);
   if ((st = occ_sort_run(h, kk, vv, n, h->occ.hist.as<unsigned>())) != SBM_OK) return fail(st);
-  hipLaunchKernelGGL(occ_edit_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, e);
+  if (map->stamp.p) hipLaunchKernelGGL(occ_edit_apply_stamped_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, e, map->stamp.as<unsigned>(), map->clock);
+  else hipLaunchKernelGGL(occ_edit_apply_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, e);
   if ((st = chk(hipGetLastError())) != SBM_OK) return fail(st);
   if (deletes && (st = occ_edit_settle_removal(map, &move, before_counts.removed)) != SBM_OK) return st;
   HIPCHK(h, clk.mark(kOccEnd, h->stream));
@@ -576,6 +615,23 @@ int sbm_occ_delete_box(sbm_occ_map* map, const uint16_t min_key[3], const uint16
                        b, map->edit_mask.as<uint8_t>(), map->edit.as<OccEditCounts>());
     return SBM_OK;
   });
+}
+
+int sbm_occ_stamp_forget(sbm_occ_map* map, uint32_t time_thres, uint64_t* removed) {
+  if (!map) return SBM_ERR_NULL;
+  if (!map->stamp.p) return SBM_ERR_UNSUPPORTED;
+  sbm_handle* h = map->h;
+  DeviceScope dscope(h->device);
+  HIPCHK(h, dscope.enter());
+  int st = occ_delete_call(map, 0, [&]() -> int {
+    hipLaunchKernelGGL(occ_mark_older_kernel, dim3(std::min((map->slots + 255) / 256, kOccMarkBlocks)), dim3(256), 0, h->stream, map->keys.as<unsigned long long>(),
+                       map->slots, map->stamp.as<unsigned>(), map->clock, time_thres, map->edit_mask.as<uint8_t>(), map->edit.as<OccEditCounts>());
+    return SBM_OK;
+  });
+  if (st != SBM_OK || !removed) return st;
+  OccEditCounts c;
+  if ((st = occ_edit_counts(map, &c)) == SBM_OK) *removed = c.removed;
+  return st;
 }
 
 int sbm_occ_last_edit(sbm_occ_map* map, sbm_occ_edit_info* out) {

@@ -22,6 +22,11 @@ __global__ void __launch_bounds__(256) occ_rehash_kernel(OccRehash r) {
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   occ_move_lane(r, i, i < r.old_slots ? r.old_keys[i] : kOccEmpty);
 }
+// the same on a stamped map (sbm_occ_stamp.hip): the stamp word moves with the key
+__global__ void __launch_bounds__(256) occ_rehash_stamped_kernel(OccRehash r, const unsigned* __restrict__ old_stamps, unsigned* __restrict__ stamps) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  occ_move_lane(r, i, i < r.old_slots ? r.old_keys[i] : kOccEmpty, old_stamps, stamps);
+}
 
 __global__ void __launch_bounds__(256) occ_claim_kernel(const int16_t* __restrict__ disp, OccGeom g, sbm_stereo_model m, OccClaimPoses poses,
                                                          unsigned long long* __restrict__ keys, OccCounters* __restrict__ ctr) {
@@ -85,6 +90,7 @@ int occ_set_overflow(sbm_occ_map* map, unsigned long long value) {
 
 void occ_move_release(OccMoveBufs* b) {
   for (DevBuf* d : {&b->keys, &b->vals, &b->flags, &b->touched, &b->change, &b->color}) d->release();
+  if (b->stamp.p) b->stamp.release();   // a map without stamps makes the calls it made before
 }
 
 // the new buffers beside the old ones: a refused allocation frees what it got and leaves the map as it was
@@ -98,6 +104,7 @@ int occ_move_alloc(sbm_occ_map* map, uint32_t slots, OccMoveBufs* b) {
   if (e == hipSuccess && map->touched.p) e = b->touched.grow((size_t)slots * 4, h->stream);
   if (e == hipSuccess && map->change.p) e = b->change.grow(slots, h->stream);
   if (e == hipSuccess && map->color.p) e = b->color.grow((size_t)slots * 4, h->stream);
+  if (e == hipSuccess && map->stamp.p) e = b->stamp.grow((size_t)slots * 4, h->stream);
   if (e == hipSuccess) return SBM_OK;
   occ_move_release(b);
   h->last_hip = (int)e;
@@ -107,12 +114,13 @@ int occ_move_alloc(sbm_occ_map* map, uint32_t slots, OccMoveBufs* b) {
 int occ_move_run(sbm_occ_map* map, size_t capacity, OccMoveBufs* b, const uint8_t* remove, unsigned removed, OccCounters* c) {
   sbm_handle* h = map->h;
   const uint32_t slots = b->slots;
-  DevBuf &keys = b->keys, &vals = b->vals, &flags = b->flags, &touched = b->touched, &change = b->change, &color = b->color;
+  DevBuf &keys = b->keys, &vals = b->vals, &flags = b->flags, &touched = b->touched, &change = b->change, &color = b->color, &stamp = b->stamp;
   hipError_t e = hipMemsetAsync(keys.p, 0xFF, (size_t)slots * 8, h->stream);
   if (e == hipSuccess) e = hipMemsetAsync(vals.p, 0, (size_t)slots * 4, h->stream);
   if (e == hipSuccess && flags.p) e = hipMemsetAsync(flags.p, 0, (size_t)slots * 4, h->stream);
   if (e == hipSuccess && change.p) e = hipMemsetAsync(change.p, 0, slots, h->stream);
   if (e == hipSuccess && color.p) e = hipMemsetD32Async((hipDeviceptr_t)color.p, (int)kOccWhite, slots, h->stream);
+  if (e == hipSuccess && stamp.p) e = hipMemsetAsync(stamp.p, 0, (size_t)slots * 4, h->stream);
   OccRehash r;
   r.parity = map->scan & 1;
   OccCounters* ctr = map->ctr.as<OccCounters>();
@@ -135,7 +143,9 @@ int occ_move_run(sbm_occ_map* map, size_t capacity, OccMoveBufs* b, const uint8_
     r.slots = slots;
     r.ctr = ctr;
     if (!r.touched) r.old_flags = nullptr;   // no list, no flags: the log-odds mode allocates both
-    if (remove) occ_remove_launch(h, r, remove, removed);
+    const unsigned* old_stamps = stamp.p ? map->stamp.as<unsigned>() : nullptr;   // the word moves only where it exists
+    if (remove) occ_remove_launch(h, r, remove, removed, old_stamps, stamp.as<unsigned>());
+    else if (old_stamps) hipLaunchKernelGGL(occ_rehash_stamped_kernel, dim3((map->slots + 255) / 256), dim3(256), 0, h->stream, r, old_stamps, stamp.as<unsigned>());
     else hipLaunchKernelGGL(occ_rehash_kernel, dim3((map->slots + 255) / 256), dim3(256), 0, h->stream, r);
     e = hipGetLastError();
   }
@@ -153,6 +163,7 @@ int occ_move_run(sbm_occ_map* map, size_t capacity, OccMoveBufs* b, const uint8_
   if (touched.p) std::swap(map->touched, touched);
   if (change.p) std::swap(map->change, change);
   if (color.p) std::swap(map->color, color);
+  if (stamp.p) std::swap(map->stamp, stamp);
   occ_move_release(b);
   map->capacity = capacity;
   map->slots = slots;

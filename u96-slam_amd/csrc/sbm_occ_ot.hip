@@ -515,13 +515,13 @@ static int occ_ot_device_parse(sbm_handle* h, const uint8_t* records, uint32_t n
 }
 
 // AbstractOcTree::read into the map. Everything that can refuse the stream comes before the map is touched; *touched tells.
-static int occ_ot_load_body(sbm_occ_map* map, const uint8_t* bytes, size_t n, int sync, bool* touched) {
+static int occ_ot_load_body(sbm_occ_map* map, const uint8_t* bytes, size_t n, int sync, bool* touched, bool stamped) {
   sbm_handle* h = map->h;
   StageClock& clk = h->occ.clock;
   const double want = occ_printed_resolution(map->p.resolution);
   sbm_occ_ot_header info;
   size_t body = 0;
-  int st = occ_ot_head(bytes, n, want, &info, &body);
+  int st = occ_ot_head(bytes, n, want, &info, &body, stamped);
   if (st != SBM_OK) return st;
   const bool host_parse = env_switch("SBM_OCC_OT_HOST_PARSE", 0) != 0 || info.size > kOtMaxRecords;
   if (!info.size) {                           // size 0: clear() and nothing else
@@ -536,7 +536,7 @@ static int occ_ot_load_body(sbm_occ_map* map, const uint8_t* bytes, size_t n, in
     std::vector<OccBtLeaf> words;
     std::vector<uint32_t> values;
     std::vector<unsigned> first;
-    st = occ_ot_parse(bytes, n, want, &info, &words, &values, false);
+    st = occ_ot_parse(bytes, n, want, &info, &words, &values, false, stamped);
     if (st != SBM_OK) return st;
     if (info.voxels > map->capacity && !occ_can_reserve(map, info.voxels)) return SBM_ERR_OCC_FULL;
     leaves = words.size();
@@ -595,14 +595,14 @@ static int occ_ot_load_body(sbm_occ_map* map, const uint8_t* bytes, size_t n, in
 
 // The device parse is part of the timed stage, so the clock starts before the stream is judged; a load that is refused puts the
 // last load's time back, as it leaves the map.
-static int occ_ot_load_run(sbm_occ_map* map, const uint8_t* bytes, size_t n, int sync) {
+static int occ_ot_load_run(sbm_occ_map* map, const uint8_t* bytes, size_t n, int sync, bool stamped = false) {
   sbm_handle* h = map->h;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
   const float last = h->occ.clock.ms[kOccLoad];
   HIPCHK(h, occ_clock_start(h, kOccLoad, kOccLoad));
   bool touched = false;
-  const int st = occ_ot_load_body(map, bytes, n, sync, &touched);
+  const int st = occ_ot_load_body(map, bytes, n, sync, &touched, stamped);
   if (!touched) h->occ.clock.ms[kOccLoad] = last;
   return st;
 }
@@ -620,7 +620,7 @@ int sbm_occ_ot_body_device(sbm_occ_tree* tree, void* d_bytes, size_t cap, size_t
   return occ_ot_body_run(tree, (uint8_t*)d_bytes, cap, nbytes);
 }
 
-int sbm_occ_ot_write(sbm_occ_tree* tree, const char* path) {
+static int occ_ot_write_to(sbm_occ_tree* tree, const char* path, bool stamped) {
   if (!tree || !path) return SBM_ERR_NULL;
   if (tree->reading != SBM_OCC_TREE_LOGODDS && tree->built) return SBM_ERR_UNSUPPORTED;
   sbm_handle* h = tree->h;
@@ -633,7 +633,29 @@ int sbm_occ_ot_write(sbm_occ_tree* tree, const char* path) {
   const size_t bytes = (size_t)(5 * nodes);
   std::vector<uint8_t> body;
   st = occ_body_host(h, bytes, &body, [&](uint8_t* d_bytes, size_t* got) { return occ_ot_body_run(tree, d_bytes, bytes, got); });
-  return st != SBM_OK ? st : occ_ot_write_file(body, (size_t)nodes, tree->resolution, path);
+  return st != SBM_OK ? st : occ_ot_write_file(body, (size_t)nodes, tree->resolution, path, stamped ? "OcTreeStamped" : "OcTree");
+}
+
+int sbm_occ_ot_write(sbm_occ_tree* tree, const char* path) { return occ_ot_write_to(tree, path, false); }
+
+// AbstractOcTree::write of an OcTreeStamped: the plain writer's ranks and five-byte records over the stamped structure, the other id
+int sbm_occ_stamp_ot_write(sbm_occ_tree* tree, const char* path) {
+  if (!tree || !path) return SBM_ERR_NULL;
+  if (tree->built && !tree->stamped) return SBM_ERR_UNSUPPORTED;   // a snapshot of a map without stamps is a plain OcTree
+  return occ_ot_write_to(tree, path, true);
+}
+
+int sbm_occ_stamp_ot_load(sbm_occ_map* map, const void* bytes, size_t n, int sync) {
+  if (!map || (n > 0 && !bytes)) return SBM_ERR_NULL;
+  return occ_ot_load_run(map, (const uint8_t*)bytes, n, sync, true);
+}
+
+int sbm_occ_stamp_ot_read(sbm_occ_map* map, const char* path, int sync) {
+  if (!map || !path) return SBM_ERR_NULL;
+  std::vector<uint8_t> data;
+  const int st = occ_read_file(path, &data);
+  if (st != SBM_OK) return st;
+  return occ_ot_load_run(map, data.data(), data.size(), sync, true);
 }
 
 int sbm_occ_ot_load(sbm_occ_map* map, const void* bytes, size_t n, int sync) {

@@ -15,13 +15,13 @@
 namespace sbm {
 
 // AbstractOcTree::write: the header, `res` printed as the .bt writers print it, then five bytes per node
-int occ_ot_write_file(const std::vector<uint8_t>& body, size_t nodes, double resolution, const char* path) {
+int occ_ot_write_file(const std::vector<uint8_t>& body, size_t nodes, double resolution, const char* path, const char* id) {
   FILE* f = fopen(path, "wb");
   if (!f) return SBM_ERR_UNSUPPORTED;
   bool ok = fprintf(f,
                     "# Octomap OcTree file\n# (feel free to add / change comments, but leave the first line as it is!)\n#\n"
-                    "id OcTree\nsize %zu\nres %g\ndata\n",
-                    nodes, resolution) > 0;
+                    "id %s\nsize %zu\nres %g\ndata\n",
+                    id, nodes, resolution) > 0;
   ok = ok && (body.empty() || fwrite(body.data(), 1, body.size(), f) == body.size());
   ok = (fclose(f) == 0) && ok;
   return ok ? SBM_OK : SBM_ERR_UNSUPPORTED;
@@ -29,7 +29,7 @@ int occ_ot_write_file(const std::vector<uint8_t>& body, size_t nodes, double res
 
 // AbstractOcTree::read up to the body: the first line, readHeader's tokens, the id, res, and that the body holds `size` records.
 // `want_res` (> 0): the map's printed resolution, which the file's must equal.
-int occ_ot_head(const uint8_t* b, size_t n, double want_res, sbm_occ_ot_header* info, size_t* body) {
+int occ_ot_head(const uint8_t* b, size_t n, double want_res, sbm_occ_ot_header* info, size_t* body, bool stamped) {
   static const char magic[] = "# Octomap OcTree file";
   memset(info, 0, sizeof(*info));
   for (int a = 0; a < 3; a++) info->key_min[a] = 0xFFFF;
@@ -40,7 +40,7 @@ int occ_ot_head(const uint8_t* b, size_t n, double want_res, sbm_occ_ot_header* 
   std::string id;
   const int st = occ_bt_header(b, n, &pos, &id, &info->size, &info->resolution);
   if (st != SBM_OK) return st;
-  if (id != "OcTree" && id != "1") return SBM_ERR_UNSUPPORTED;
+  if (stamped ? id != "OcTreeStamped" : (id != "OcTree" && id != "1")) return SBM_ERR_UNSUPPORTED;   // the one difference of the stamped stream
   if (!(info->resolution > 0.)) return SBM_ERR_SIZE;
   if (want_res > 0. && info->resolution != want_res) return SBM_ERR_SIZE;
   if (info->size > (n - pos) / 5) return SBM_ERR_SIZE;
@@ -105,9 +105,9 @@ static int occ_ot_node(OccOtParse& p, uint64_t code, int depth) {
 // The body after occ_ot_head accepted the stream: the shape of the tree over the first `size` records, then the leaf values.
 // The cubes of a tree are disjoint, so `voxels` is at most 2^48.
 int occ_ot_parse(const uint8_t* b, size_t n, double want_res, sbm_occ_ot_header* info, std::vector<OccBtLeaf>* words,
-                 std::vector<uint32_t>* values, bool bounds) {
+                 std::vector<uint32_t>* values, bool bounds, bool stamped) {
   size_t body = 0;
-  int st = occ_ot_head(b, n, want_res, info, &body);
+  int st = occ_ot_head(b, n, want_res, info, &body, stamped);
   if (st != SBM_OK || !info->size) return st;
   OccOtParse p;
   p.info = info;
@@ -140,12 +140,12 @@ int sbm_occ_ot_info(const void* bytes, size_t n, sbm_occ_ot_header* out) {
   return occ_ot_parse((const uint8_t*)bytes, n, 0., out, nullptr, nullptr, true);
 }
 
-int sbm_occ_ot_leaves(const void* bytes, size_t n, uint64_t* first_key, int32_t* depth, float* value, size_t cap, size_t* count) {
+static int occ_ot_leaves_of(const void* bytes, size_t n, uint64_t* first_key, int32_t* depth, float* value, size_t cap, size_t* count, bool stamped) {
   if (!count || (n > 0 && !bytes) || (cap > 0 && (!first_key || !depth || !value))) return SBM_ERR_NULL;
   sbm_occ_ot_header info;
   std::vector<OccBtLeaf> words;
   std::vector<uint32_t> values;
-  const int st = occ_ot_parse((const uint8_t*)bytes, n, 0., &info, &words, &values, false);
+  const int st = occ_ot_parse((const uint8_t*)bytes, n, 0., &info, &words, &values, false, stamped);
   if (st != SBM_OK) return st;
   *count = words.size();
   if (words.size() > cap) return SBM_ERR_SIZE;
@@ -155,5 +155,16 @@ int sbm_occ_ot_leaves(const void* bytes, size_t n, uint64_t* first_key, int32_t*
     memcpy(&value[i], &values[i], 4);
   }
   return SBM_OK;
+}
+int sbm_occ_ot_leaves(const void* bytes, size_t n, uint64_t* first_key, int32_t* depth, float* value, size_t cap, size_t* count) {
+  return occ_ot_leaves_of(bytes, n, first_key, depth, value, cap, count, false);
+}
+// the `id OcTreeStamped` stream: the plain records (OcTreeNodeStamped writes no stamp), so the plain parser with the other id test
+int sbm_occ_stamp_ot_info(const void* bytes, size_t n, sbm_occ_ot_header* out) {
+  if (!out || (n > 0 && !bytes)) return SBM_ERR_NULL;
+  return occ_ot_parse((const uint8_t*)bytes, n, 0., out, nullptr, nullptr, true, true);
+}
+int sbm_occ_stamp_ot_leaves(const void* bytes, size_t n, uint64_t* first_key, int32_t* depth, float* value, size_t cap, size_t* count) {
+  return occ_ot_leaves_of(bytes, n, first_key, depth, value, cap, count, true);
 }
 }  // extern "C"

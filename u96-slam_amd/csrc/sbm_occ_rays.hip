@@ -211,7 +211,12 @@ __global__ void __launch_bounds__(256) occ_rays_mark_list_kernel(OccDedupe d, Oc
 // two counts of OccCounters::touched take turns, so that no scan needs a memset between its two launches and the next scan's.
 // kTrack (updateNodeRecurs, OccupancyOcTreeBase.hxx:415-427): a slot the scan claimed becomes `created`; another whose
 // isNodeOccupied differs before and after the update goes none -> flipped -> none, and a created one stays.
-template <bool kTrack> __global__ void __launch_bounds__(256) occ_rays_apply_kernel(OccRay g, OccTable t) {
+// kStamp (OcTreeStamped::updateNodeLogOdds; sbm.h, "occupancy map: time stamps per voxel"): the slot's stamp word becomes the map's
+// clock unless updateNode's early return applies -- the voxel existed before the scan (MARK's "created" bit is clear) and sits at
+// the clamp in the direction of its update. A plain store by the one lane that owns the slot. The instantiations without kStamp are
+// the kernels of a map without stamps, statement for statement.
+template <bool kTrack, bool kStamp>
+__device__ __forceinline__ void occ_rays_apply(const OccRay& g, const OccTable& t, unsigned* __restrict__ stamps, uint32_t clock) {
 #pragma clang fp contract(off)
   const uint32_t n = min(t.ctr->touched[g.parity], g.slots);
   if (blockIdx.x == 0 && threadIdx.x == 0) t.ctr->touched[g.parity ^ 1] = 0;   // the next scan's count; nobody reads it now
@@ -225,6 +230,11 @@ template <bool kTrack> __global__ void __launch_bounds__(256) occ_rays_apply_ker
     else if (v > g.cmax) v = g.cmax;
     t.logodds[slot] = v;
     t.flags[slot] = 0;
+    if (kStamp) {
+      const float u = (f & kOccOccupied) ? g.hit : g.miss;
+      const bool early = !(f & kOccCreated) && ((u >= 0.f && before >= g.cmax) || (u <= 0.f && before <= g.cmin));
+      if (!early) stamps[slot] = clock;
+    }
     if (kTrack) {
       if (f & kOccCreated) {
         t.change[slot] = kOccChangeCreated;
@@ -234,6 +244,13 @@ template <bool kTrack> __global__ void __launch_bounds__(256) occ_rays_apply_ker
       }
     }
   }
+}
+template <bool kTrack> __global__ void __launch_bounds__(256) occ_rays_apply_kernel(OccRay g, OccTable t) {
+  occ_rays_apply<kTrack, false>(g, t, nullptr, 0u);
+}
+template <bool kTrack>
+__global__ void __launch_bounds__(256) occ_rays_apply_stamped_kernel(OccRay g, OccTable t, unsigned* __restrict__ stamps, uint32_t clock) {
+  occ_rays_apply<kTrack, true>(g, t, stamps, clock);
 }
 
 // ---- log-odds mode, host side ----------------------------------------------------------------------------------------------
@@ -305,6 +322,14 @@ template <class F> static void occ_with_options(const sbm_occ_map* map, F f) {
   }
 }
 
+// The same for a MARK launch. On a stamped map MARK always carries "created this scan" (the kTrack instantiations, which exist
+// already): the stamped APPLY needs it for updateNode's early return, and the plain APPLY clears the bit with the others.
+template <class F> static void occ_with_mark_options(const sbm_occ_map* map, F f) {
+  if (!map->stamp.p) return occ_with_options(map, f);
+  if (map->use_bbx) f(std::true_type{}, std::true_type{});
+  else f(std::false_type{}, std::true_type{});
+}
+
 // The scratch of one discretised scan of n points, placed in the map's dedupe buffer: the set, the list and its count
 static int occ_dedupe_begin(sbm_occ_map* map, size_t n, OccDedupe* d) {
   sbm_handle* h = map->h;
@@ -351,8 +376,11 @@ template <class Mark> static int occ_rays_scan(sbm_occ_map* map, OccRay& g, OccT
   }
   HIPCHK(h, clk.mark(kOccMid, h->stream));
   occ_with_options(map, [&](auto, auto track) {
-    hipLaunchKernelGGL((occ_rays_apply_kernel<decltype(track)::value>), dim3(std::min((map->slots + 255) / 256, 1024u)), dim3(256), 0,
-                       h->stream, g, t);
+    const dim3 grid(std::min((map->slots + 255) / 256, 1024u));
+    if (map->stamp.p)   // the clock as it is at this call
+      hipLaunchKernelGGL((occ_rays_apply_stamped_kernel<decltype(track)::value>), grid, dim3(256), 0, h->stream, g, t, map->stamp.as<unsigned>(), map->clock);
+    else
+      hipLaunchKernelGGL((occ_rays_apply_kernel<decltype(track)::value>), grid, dim3(256), 0, h->stream, g, t);
   });
   HIPCHK(h, hipGetLastError());
   map->scan++;
@@ -387,7 +415,7 @@ static int occ_cloud_run(sbm_occ_map* map, size_t n, const float* d_xyz, const f
     if (discrete && (st = occ_dedupe_begin(map, n, &d)) != SBM_OK) return st;
     st = occ_rays_scan(map, g, t, [&] {
       if (discrete) occ_dedupe_run(h, d, [&] { hipLaunchKernelGGL(occ_dedupe_cloud_kernel, grid, dim3(256), 0, h->stream, d_xyz, n, g.factor, d); });
-      occ_with_options(map, [&](auto box, auto track) {
+      occ_with_mark_options(map, [&](auto box, auto track) {
         constexpr bool kBox = decltype(box)::value, kTrack = decltype(track)::value;
         if (discrete) hipLaunchKernelGGL((occ_rays_mark_list_kernel<kBox, kTrack>), grid, dim3(256), 0, h->stream, d, o, g, t);
         else hipLaunchKernelGGL((occ_rays_mark_cloud_kernel<kBox, kTrack>), grid, dim3(256), 0, h->stream, d_xyz, n, o, g, t);
@@ -423,7 +451,7 @@ static int occ_planes_run(sbm_occ_map* map, int n, const int16_t* d_disp, int W,
         occ_dedupe_run(h, d, [&] {
           hipLaunchKernelGGL(occ_dedupe_plane_kernel, grid, dim3(256), 0, h->stream, d_disp + plane * i, pg, *model, pose, g.factor, d);
         });
-      occ_with_options(map, [&](auto box, auto track) {
+      occ_with_mark_options(map, [&](auto box, auto track) {
         constexpr bool kBox = decltype(box)::value, kTrack = decltype(track)::value;
         if (discrete) hipLaunchKernelGGL((occ_rays_mark_list_kernel<kBox, kTrack>), grid, dim3(256), 0, h->stream, d, pose, g, t);
         else hipLaunchKernelGGL((occ_rays_mark_plane_kernel<kBox, kTrack>), grid, dim3(256), 0, h->stream, d_disp + plane * i, pg, *model, pose, g, t);

@@ -100,7 +100,13 @@ __global__ void __launch_bounds__(256) occ_tree_scan_kernel(unsigned* __restrict
 
 // One level: every head writes its parent and tells its (at most eight) children where it is. tile_off: the scanned tile counts,
 // or null for a level of one tile. leaves: the children are depth 16.
-__global__ void __launch_bounds__(256) occ_tree_parents_kernel(OccLevel c, OccLevel p, const unsigned* __restrict__ tile_off, int leaves) {
+// kStamp (sbm.h, "occupancy map: time stamps per voxel"): octomap's STAMPED pruned tree. OcTreeNodeStamped::operator== compares value
+// and stamp, so eight siblings collapse only if their stamps are equal too; the collapsed node has the common stamp (copyData), every
+// other inner node the map's clock at build time (updateInnerOccupancy). cs / ps: the stamps of the child and the parent level.
+// Without kStamp this is the kernel of a map without stamps, statement for statement.
+template <bool kStamp>
+__device__ __forceinline__ void occ_tree_parents(const OccLevel& c, const OccLevel& p, const unsigned* __restrict__ tile_off, int leaves,
+                                                 const unsigned* __restrict__ cs, unsigned* __restrict__ ps, uint32_t clock) {
   __shared__ unsigned wsum[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   unsigned running = tile_off ? tile_off[blockIdx.x] : 0;
@@ -124,6 +130,7 @@ __global__ void __launch_bounds__(256) occ_tree_parents_kernel(OccLevel c, OccLe
       const unsigned v = c.val[j];
       if (__uint_as_float(v) > __uint_as_float(best)) best = v;              // updateOccupancyChildren: the maximum
       equal = equal && __uint_as_float(v) == __uint_as_float(v0);            // isNodeCollapsible: float ==
+      if (kStamp) equal = equal && cs[j] == cs[i];                             // ... and the stamp
       mask |= 1u << (unsigned)(c.code[j] & 7);
       if (!leaves) {
         all_leaves = all_leaves && (c.info[j] & kOccCollapsed);
@@ -137,7 +144,24 @@ __global__ void __launch_bounds__(256) occ_tree_parents_kernel(OccLevel c, OccLe
     p.first[at] = i;
     p.info[at] = mask | (collapsed ? kOccCollapsed : 0u);
     p.inner[at] = collapsed ? 0u : 1u + inner;
+    if (kStamp) ps[at] = collapsed ? cs[i] : clock;
   }
+}
+__global__ void __launch_bounds__(256) occ_tree_parents_kernel(OccLevel c, OccLevel p, const unsigned* __restrict__ tile_off, int leaves) {
+  occ_tree_parents<false>(c, p, tile_off, leaves, nullptr, nullptr, 0u);
+}
+__global__ void __launch_bounds__(256) occ_tree_parents_stamped_kernel(OccLevel c, OccLevel p, const unsigned* __restrict__ tile_off, int leaves,
+                                                                       const unsigned* __restrict__ cs, unsigned* __restrict__ ps, uint32_t clock) {
+  occ_tree_parents<true>(c, p, tile_off, leaves, cs, ps, clock);
+}
+// depth 16 of a stamped build: the voxel's own stamp, looked up by its key (the tree holds Morton codes)
+__global__ void __launch_bounds__(256) occ_tree_leaf_stamps_kernel(const unsigned long long* __restrict__ code, uint32_t n,
+                                                                   const unsigned long long* __restrict__ keys, const unsigned* __restrict__ stamps,
+                                                                   uint32_t mask, uint32_t max_probe, unsigned* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  uint32_t slot;
+  out[i] = occ_find(keys, occ_key_of_code(code[i]), mask, max_probe, &slot) ? stamps[slot] : 0u;
 }
 
 // Top-down, depth by depth (the level above is finished: an earlier launch). A node is in the pruned tree iff nothing above it is
@@ -313,6 +337,7 @@ static int occ_tree_build_run(sbm_occ_tree* t, int reading, const sbm_occ_ray_pa
   t->ot_ranked = false;
   t->have_metric = false;
   t->colored = false;
+  t->stamped = false;
   t->reading = reading;
   t->resolution = map->p.resolution;
   memset(t->count, 0, sizeof(t->count));
@@ -378,6 +403,17 @@ static int occ_tree_build_run(sbm_occ_tree* t, int reading, const sbm_occ_ray_pa
   const auto node_layout = [&](Carve& c) { OccLevel all; occ_level_layout(c, t->inner_total, true, &all); };   // occ_tree_level places it
   HIPCHK(h, t->node.grow(carve_bytes(node_layout, occ_pad), h->stream));
   HIPCHK(h, t->tiles.grow((size_t)tiles * 4, h->stream));
+  const bool stamped = map->stamp.p != nullptr;   // only over a map with stamps: the stamped pruned tree
+  unsigned *leaf_stamp = nullptr, *node_stamp = nullptr;
+  if (stamped) {
+    HIPCHK(h, carve(t->stamp, h->stream, [&](Carve& c) { c.take<unsigned>(n), c.take<unsigned>(t->inner_total); }, occ_pad));
+    occ_tree_stamps(t, &leaf_stamp, &node_stamp);
+    uint32_t mask, max_probe;
+    occ_probe(map, &mask, &max_probe);
+    hipLaunchKernelGGL(occ_tree_leaf_stamps_kernel, dim3(blocks), dim3(256), 0, h->stream, kk[0], n, map->keys.as<unsigned long long>(),
+                       map->stamp.as<unsigned>(), mask, max_probe, leaf_stamp);
+    HIPCHK(h, hipGetLastError());
+  }
   t->built = true;   // occ_tree_level answers from here on; a failure below takes it back
   st = [&]() -> int {
     for (int d = kOccDepth - 1; d >= 0; d--) {   // bottom-up: the parents of depth d + 1
@@ -391,7 +427,11 @@ static int occ_tree_build_run(sbm_occ_tree* t, int reading, const sbm_occ_ray_pa
         hipLaunchKernelGGL(occ_tree_scan_kernel, dim3(1), dim3(256), 0, h->stream, tile_off, ct);
         HIPCHK(h, hipGetLastError());
       }
-      hipLaunchKernelGGL(occ_tree_parents_kernel, dim3(ct), dim3(256), 0, h->stream, child, parent, tile_off, d + 1 == kOccDepth ? 1 : 0);
+      if (stamped)
+        hipLaunchKernelGGL(occ_tree_parents_stamped_kernel, dim3(ct), dim3(256), 0, h->stream, child, parent, tile_off, d + 1 == kOccDepth ? 1 : 0,
+                           d + 1 == kOccDepth ? leaf_stamp : node_stamp + t->off[d + 1], node_stamp + t->off[d], map->clock);
+      else
+        hipLaunchKernelGGL(occ_tree_parents_kernel, dim3(ct), dim3(256), 0, h->stream, child, parent, tile_off, d + 1 == kOccDepth ? 1 : 0);
       HIPCHK(h, hipGetLastError());
     }
     for (int d = 0; d <= kOccDepth; d++) {       // top-down
@@ -402,6 +442,7 @@ static int occ_tree_build_run(sbm_occ_tree* t, int reading, const sbm_occ_ray_pa
     return SBM_OK;
   }();
   if (st == SBM_OK && map->color.p) st = occ_color_tree_run(t);   // only over a map with colours
+  if (st == SBM_OK) t->stamped = stamped;
   if (st != SBM_OK) {
     t->built = false;
     return st;

@@ -145,6 +145,7 @@ int occ_clear(sbm_occ_map* map) {
   if (map->flags.p) HIPCHK(h, hipMemsetAsync(map->flags.p, 0, (size_t)map->slots * 4, h->stream));
   if (map->change.p) HIPCHK(h, hipMemsetAsync(map->change.p, 0, map->slots, h->stream));   // the switches and the box stay
   if (map->color.p) HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)map->color.p, (int)kOccWhite, map->slots, h->stream));   // every voxel white
+  if (map->stamp.p) HIPCHK(h, hipMemsetAsync(map->stamp.p, 0, (size_t)map->slots * 4, h->stream));   // every stamp 0; the clock stays
   map->mode = kOccModeNone;
   map->scan = 0;
   map->size_bound = 0;
@@ -393,6 +394,7 @@ int sbm_occ_insert_device(sbm_occ_map* map, int n, const void* d_disp, int width
   const int st = occ_check_insert(map, n, d_disp, width, height, scale, model, poses);
   if (st != SBM_OK) return st;
   if ((uintptr_t)d_disp & 1 || map->mode == kOccModeLogOdds || map->use_bbx || map->detect) return SBM_ERR_UNSUPPORTED;
+  if (map->stamp.p) return SBM_ERR_UNSUPPORTED;   // stamp words belong to a log-odds map, also after sbm_occ_reset has cleared the mode
   DeviceScope dscope(map->h->device);
   HIPCHK(map->h, dscope.enter());
   map->mode = kOccModeHits;
@@ -404,6 +406,7 @@ int sbm_occ_insert(sbm_occ_map* map, int n, const int16_t* disp, int width, int 
   const int st = occ_check_insert(map, n, disp, width, height, scale, model, poses);
   if (st != SBM_OK) return st;
   if (map->mode == kOccModeLogOdds || map->use_bbx || map->detect) return SBM_ERR_UNSUPPORTED;
+  if (map->stamp.p) return SBM_ERR_UNSUPPORTED;   // stamp words belong to a log-odds map, also after sbm_occ_reset has cleared the mode
   sbm_handle* h = map->h;
   DeviceScope dscope(h->device);
   HIPCHK(h, dscope.enter());
